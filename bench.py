@@ -32,19 +32,25 @@ product's batch flow (include/latok_hip.h "batch flow", `--in-flight 2`): consec
 two workspaces and two output bitmasks, so the string-index and resolve launches of one batch run in the shadow of the other
 batch's tile kernel; every pass still runs all three kernels and every result is complete when the clock stops.  The same K
 steps one batch at a time (`--in-flight 1`, what earlier rounds reported as `value`) are timed right after and ride along as
-`serial`.  `value` = UTF-8 bytes of all ranks x K / whole-job WALL time (in
+`serial` (--full).  `value` = UTF-8 bytes of all ranks x K / whole-job WALL time (in
 process: last rank out - first rank in, one clock; under a launcher: max over ranks of the rank's wall time).  The
 HIP-event time of the same K steps rides along (`ms_per_step_events`, `value_events`, `ms_per_rank`); round 2 reported
 that one as `value` (0.7-2 % higher), round 1 and this round the wall time, as the contract reads.
 
-Prints ONE JSON line (rank 0).  Besides the contract keys it carries
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: build the shard, warm up, time the K steps,
+write the outputs (--dump-outputs) and print the contract keys.  With `--full` the line also carries
+  serial       -- the same K steps one batch at a time (batch flow on)
   roofline     -- dominant kernel (k_tiles_main): algorithmic HBM bytes per launch / its HIP-event time, vs 8 TB/s; measured
                   on every rank (frac_per_rank), `frac` is the slowest rank's
   sustained    -- >= 1 s of back-to-back steps outside the timed region (clock / thermal drift shows here)
+  sensors_rank0 -- sclk / mclk / power from sysfs around the timed region and during the sustained run
   cpu_baseline -- at every N: the reference's own C functions (oracle/_ref, built from the reference's latok.c) under a
                   restated NumPy glue, 1 thread, timed on this host on the same corpus;
                   cpu_baseline_port = oracle/latok_oracle.c (1 thread); cpu_baseline_fused_allcores = the fused CPU
                   model (oracle/fused_model.cpp) over all host cores.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (rank 0's boundary bitmask) as .npy files, see
+dump_outputs(); the corpus is seeded, so the same arguments give the same inputs and outputs run to run.
 """
 import argparse
 import ctypes as C
@@ -75,6 +81,9 @@ WORKLOADS = {
 }
 SCALING = {"C2": "weak", "C3": "weak", "C4": "strong", "C5": "strong"}
 PMC_SUMMARIES = [os.path.join(ROOT, "profiles", n) for n in ("r04_pmc_summary.json", "r03_pmc_summary.json", "r02_pmc_summary.json")]
+DUMP_BLOCK_WORDS = 128       # --dump-outputs: the bitmask is cut into blocks of 128 words = 8192 chars
+DUMP_SAMPLE_BLOCKS = 1024    # ... of which this many (chosen by DUMP_SEED) are written char by char: 32 MiB of float32
+DUMP_SEED = 0x1A70D0
 
 
 # ---- host-side facts about a GPU, read from sysfs without touching the HIP runtime ------------------------------------------
@@ -612,6 +621,51 @@ class Shard:
     def alg_read(self):
         return 4 * self.total + 8 * (self.n_str + 1)   # 4 B/code point + 8 B/string row offset
 
+    def last_step_mask(self, steps):
+        """device bitmask the last of `steps` timed passes wrote: the flow alternates, pass i writes d_bits2 when i is odd"""
+        return self.d_bits2 if self.flow and (steps - 1) & 1 else self.d_bits
+
+
+def dump_outputs(sh, out_dir, steps):
+    """--dump-outputs: the u64 boundary bitmask the last timed step handed its caller (bit i of word w: char 64 w + i starts a
+    token; rank 0's batch), as arrays two builds can be compared with:
+      split_mask_block_counts.npy  float32  boundaries in every block of 8192 chars of the whole batch (the last may be short)
+      split_mask_sample_flags.npy  float32  0 / 1 per char of DUMP_SAMPLE_BLOCKS blocks picked by DUMP_SEED (every block when
+                                            the batch has no more), block after block
+      split_mask_sample_start.npy  float64  first char of each of those blocks"""
+    lib, chk = sh.lib, sh.api.check
+    total = sh.total
+    words = (total + 63) // 64
+    block_chars = 64 * DUMP_BLOCK_WORDS
+    n_blocks = (words + DUMP_BLOCK_WORDS - 1) // DUMP_BLOCK_WORDS
+    if n_blocks <= DUMP_SAMPLE_BLOCKS:
+        pick = np.arange(n_blocks, dtype=np.int64)
+    else:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_blocks, DUMP_SAMPLE_BLOCKS, replace=False))
+    mask = sh.last_step_mask(steps)
+    counts = np.zeros(n_blocks, np.float32)
+    flags = []
+    chunk_words = 1 << 20                                # 8 MiB of the bitmask per copy (a whole number of blocks)
+    buf = np.empty(chunk_words, np.uint64)
+    for w0 in range(0, words, chunk_words):
+        nw = min(chunk_words, words - w0)
+        chk(lib.latok_memcpy_d2h(buf.ctypes.data, mask + 8 * w0, 8 * nw))
+        part = buf[:nw].copy()
+        if w0 + nw == words and total % 64:             # bits past the last char are not part of the output
+            part[-1] &= np.uint64((1 << (total % 64)) - 1)
+        b0 = w0 // DUMP_BLOCK_WORDS
+        pad = np.zeros((nw + DUMP_BLOCK_WORDS - 1) // DUMP_BLOCK_WORDS * DUMP_BLOCK_WORDS, np.uint8)
+        pad[:nw] = np.bitwise_count(part)
+        counts[b0:b0 + pad.size // DUMP_BLOCK_WORDS] = pad.reshape(-1, DUMP_BLOCK_WORDS).sum(axis=1)
+        for b in pick[(pick >= b0) & (pick < b0 + pad.size // DUMP_BLOCK_WORDS)]:
+            lo = (int(b) - b0) * DUMP_BLOCK_WORDS
+            bits = np.unpackbits(part[lo:lo + DUMP_BLOCK_WORDS].view(np.uint8), bitorder="little")
+            flags.append(bits[:min(block_chars, total - int(b) * block_chars)].astype(np.float32))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "split_mask_block_counts.npy"), counts)
+    np.save(os.path.join(out_dir, "split_mask_sample_flags.npy"), np.concatenate(flags) if flags else np.zeros(0, np.float32))
+    np.save(os.path.join(out_dir, "split_mask_sample_start.npy"), (pick * block_chars).astype(np.float64))
+
 
 def measure_shard(sh, args, gate, phase):
     """The measurement protocol of one rank of the in-process job.  `phase()` is a no-op context when every rank has a GPU
@@ -622,11 +676,18 @@ def measure_shard(sh, args, gate, phase):
     sh.warmup(args.warmup)
     sh.warmup_flow(args.warmup)
     dev = getattr(sh, "device", 0)
-    sens_before = gpu_sensors(dev)                       # (before the settle passes: nothing may sit between them and the timed region --
-    n_settle = sh.settle(args.settle_s)                  # a few ms of sysfs reads there would let the clocks drop again)
+    sens_before = gpu_sensors(dev) if args.full else None   # (before the settle passes: nothing may sit between them and the timed
+    n_settle = sh.settle(args.settle_s)                     # region -- a few ms of sysfs reads there would let the clocks drop again)
     chk(lib.latok_gate_wait(gate, GATE_TIMEOUT_S))      # every shard is resident and warm before anyone's clock starts
     with phase():
         rec = sh.timed(args.steps, None if args.take_turns else gate)
+        if args.dump_outputs and sh.rank == 0:
+            dump_outputs(sh, args.dump_outputs, args.steps)
+    rec.update(rank=sh.rank, n_str=sh.n_str, total=sh.total, utf8=sh.utf8, distinct_inputs=sh.distinct, flow=sh.flow,
+               settle_steps=n_settle)
+    if not args.full:
+        sh.free()
+        return rec
     rec["sensors"] = {"before_settle_passes": sens_before, "after_timed_region": gpu_sensors(dev)}
     serial = None
     if sh.flow:   # the same K steps one batch at a time (what `value` was before the batch flow), beside the headline
@@ -637,11 +698,10 @@ def measure_shard(sh, args, gate, phase):
     with phase():
         k_ms, n_fix = sh.kernel_only(args.steps)
     rec["serial"] = serial
-    rec["settle_steps"] = n_settle
     with phase():
         rec["kernel_flow_ms"] = sh.kernel_in_flow(args.steps)
-    rec.update(rank=sh.rank, n_str=sh.n_str, total=sh.total, utf8=sh.utf8, alg_read=sh.alg_read(), kernel_ms=k_ms, n_fix=n_fix,
-               sustained=None, measured_read=None, distinct_inputs=sh.distinct, flow=sh.flow, kernel_launches=getattr(sh, "kernel_launches", None))
+    rec.update(alg_read=sh.alg_read(), kernel_ms=k_ms, n_fix=n_fix, sustained=None, measured_read=None,
+               kernel_launches=getattr(sh, "kernel_launches", None))
     chk(lib.latok_gate_wait(gate, GATE_TIMEOUT_S))
     if sh.rank == 0:   # outside the timed region, the other ranks are done
         if args.sustain_s > 0 and rec["ms_events"] > 0:
@@ -746,34 +806,38 @@ def run_under_launcher(api, args, rank, world, local_rank):
         sh.build()
         sh.warmup(args.warmup)
         sh.warmup_flow(args.warmup)
-        sens_before = gpu_sensors(device)
+        sens_before = gpu_sensors(device) if args.full else None
         n_settle = sh.settle(args.settle_s)
         dist.barrier()
         with _Barrier("timed"):
             rec = sh.timed(args.steps, None)
-        rec["sensors"] = {"before_settle_passes": sens_before, "after_timed_region": gpu_sensors(device)}
+            if args.dump_outputs and rank == 0:
+                dump_outputs(sh, args.dump_outputs, args.steps)
         rec["host"] = pin
-        serial = None
-        if sh.flow:
+        rec.update(rank=rank, n_str=sh.n_str, total=sh.total, utf8=sh.utf8, distinct_inputs=sh.distinct, flow=sh.flow,
+                   settle_steps=n_settle)
+        if args.full:
+            rec["sensors"] = {"before_settle_passes": sens_before, "after_timed_region": gpu_sensors(device)}
+            serial = None
+            if sh.flow:
+                dist.barrier()
+                with _Barrier("timed-serial"):
+                    serial = sh.timed(args.steps, None, flow=False)
             dist.barrier()
-            with _Barrier("timed-serial"):
-                serial = sh.timed(args.steps, None, flow=False)
-        dist.barrier()
-        with _Barrier("kernel"):
-            k_ms, n_fix = sh.kernel_only(args.steps)
-        rec["serial"] = serial
-        rec["settle_steps"] = n_settle
-        with _Barrier("kernel-flow"):
-            rec["kernel_flow_ms"] = sh.kernel_in_flow(args.steps)
-        rec.update(rank=rank, n_str=sh.n_str, total=sh.total, utf8=sh.utf8, alg_read=sh.alg_read(), kernel_ms=k_ms, n_fix=n_fix,
-                   sustained=None, measured_read=None, distinct_inputs=sh.distinct, flow=sh.flow, kernel_launches=getattr(sh, "kernel_launches", None))
-        dist.barrier()
-        if rank == 0:
-            if args.sustain_s > 0 and rec["ms_events"] > 0:
-                with SensorWatch(device) as watch:
-                    rec["sustained"] = sh.sustained(args.sustain_s, rec["ms_events"] / args.steps)
-                rec["sensors"]["during_sustained_run"] = watch.summary()
-            rec["measured_read"] = sh.stream_read()
+            with _Barrier("kernel"):
+                k_ms, n_fix = sh.kernel_only(args.steps)
+            rec["serial"] = serial
+            with _Barrier("kernel-flow"):
+                rec["kernel_flow_ms"] = sh.kernel_in_flow(args.steps)
+            rec.update(alg_read=sh.alg_read(), kernel_ms=k_ms, n_fix=n_fix, sustained=None, measured_read=None,
+                       kernel_launches=getattr(sh, "kernel_launches", None))
+            dist.barrier()
+            if rank == 0:
+                if args.sustain_s > 0 and rec["ms_events"] > 0:
+                    with SensorWatch(device) as watch:
+                        rec["sustained"] = sh.sustained(args.sustain_s, rec["ms_events"] / args.steps)
+                    rec["sensors"]["during_sustained_run"] = watch.summary()
+                rec["measured_read"] = sh.stream_read()
         sh.free()
         gathered = [None] * world
         dist.all_gather_object(gathered, rec)
@@ -787,7 +851,7 @@ def run_under_launcher(api, args, rank, world, local_rank):
 
 
 def build_line(args, recs, mode, devices, same_start):
-    """the ONE JSON line, from the per-rank records (rank order)"""
+    """the ONE JSON line, from the per-rank records (rank order); what only --full measures is added by full_line()"""
     world = len(recs)
     _, _, _, _, _, desc = WORKLOADS[args.workload]
     K = args.steps
@@ -800,21 +864,8 @@ def build_line(args, recs, mode, devices, same_start):
     else:
         job_s = max(walls)
     ev_max = max(r["ms_events"] for r in recs) / 1e3
-    flow = all(r.get("serial") for r in recs)
-    serial = None
-    if flow:   # the same K steps, one batch at a time on one stream
-        sr = [r["serial"] for r in recs]
-        s_job = ((max(x["t1_ns"] for x in sr) - min(x["t0_ns"] for x in sr)) / 1e9 if same_start
-                 else max((x["t1_ns"] - x["t0_ns"]) / 1e9 for x in sr))
-        serial = {"ms_per_step": s_job / K * 1e3, "value": utf8_all * K / s_job / 1e9,
-                  "ms_per_rank": [x["ms_events"] / K for x in sr],
-                  "what": "the same K steps with ONE batch in flight (index -> tiles -> resolve back to back on one stream): "
-                          "`value` of rounds 1-3 before the batch flow"}
-    traffic, traffic_src = pmc_traffic(args.workload, recs[0]["total"], 2 if flow else 1, bool(flow and all(r.get("distinct_inputs") for r in recs)))
-    fracs = [r["alg_read"] / (r["kernel_ms"] / 1e3) / 1e9 / HBM_PEAK_GBS for r in recs]
-    worst = min(range(world), key=lambda i: fracs[i])
+    flow = all(r.get("flow") for r in recs)
     r0 = recs[0]
-    achieved = recs[worst]["alg_read"] / (recs[worst]["kernel_ms"] / 1e3) / 1e9
     value = utf8_all * K / job_s / 1e9
     line = {
         "metric": "input UTF-8 GB/s tokenized (fused feature+split-mask path)",
@@ -830,6 +881,7 @@ def build_line(args, recs, mode, devices, same_start):
         "higher_is_better": True, "scaling": SCALING[args.workload], "vs_baseline": None,
         "dtype": "u64", "dtype_note": "u32 code points in, 64-bit bit-sliced boolean words, u64 bitmask out (integer / bit ops)",
         "data": "synthetic",
+        "full": bool(args.full),
         "config": {"workload": f"{args.workload}: {desc}", "strings_per_gpu": r0["n_str"], "strings_total": sum(r["n_str"] for r in recs),
                    "chars_total": sum(r["total"] for r in recs), "utf8_bytes_total": utf8_all,
                    "sharding": f"{world} x independent contiguous string-id shards, no collective on the data path",
@@ -837,12 +889,10 @@ def build_line(args, recs, mode, devices, same_start):
         "in_flight": 2 if flow else 1,
         "distinct_inputs": bool(flow and all(r.get("distinct_inputs") for r in recs)),
         "ranks": [{"rank": r["rank"], **(r.get("host") or {})} for r in recs],
-        "sensors_rank0": r0.get("sensors"),
         "in_flight_note": ("batch flow (latok_flow_split_mask): step i+1 is submitted while step i runs, on a second stream with its own "
                            "workspace and its own output bitmask; every step launches all three kernels and is complete when the "
                            "clock stops; with `distinct_inputs` the odd steps read a second copy of the shard at another address, so the two "
-                           "batches in flight share no input lines in L2 / MALL; `serial` = the same K steps one at a time") if flow else "one batch at a time",
-        "serial": serial,
+                           "batches in flight share no input lines in L2 / MALL; `serial` (--full) = the same K steps one at a time") if flow else "one batch at a time",
         "timing": ("host monotonic clock, inputs resident in HBM: every rank's region = [gate ->] clock -> K pipeline passes -> "
                    "stream(s) synchronise -> clock inside one library call; value = bytes of all ranks x K / "
                    + ("(last rank out - first rank in)" if same_start else "max over ranks of the rank's own wall time")
@@ -854,6 +904,44 @@ def build_line(args, recs, mode, devices, same_start):
         "start_skew_us": (max(r["t0_ns"] for r in recs) - min(r["t0_ns"] for r in recs)) / 1e3 if same_start else None,
         "timed_region_launches": ("one hipGraph replay of the K passes per rank" if all(r.get("graph") for r in recs)
                                   else "3 kernel launches per pass" + (", passes alternating between two streams" if flow else "")),
+    }
+    serial = full_line(args, recs, line, flow, same_start) if args.full else None
+    if args.take_turns:
+        line["rehearsal"] = ("ranks took turns on shared GPU(s): per-rank times are single-GPU times; value_projected is what "
+                             f"{world} such GPUs would give -- a rehearsal of the N > 1 code path, not a measurement of {world} GPUs")
+        proj = max(walls)
+        line["value_projected"] = utf8_all * K / proj / 1e9
+        line["ms_per_step_projected"] = proj / K * 1e3
+        line["value"] = None
+        line["ms_per_step"] = None
+        if serial:
+            serial["value"] = serial["ms_per_step"] = None
+            serial["ms_per_step_projected"] = max((x["t1_ns"] - x["t0_ns"]) / 1e9 for x in (r["serial"] for r in recs)) / K * 1e3
+    return line
+
+
+def full_line(args, recs, line, flow, same_start):
+    """--full: the measurements beside the headline (serial steps, roofline, sustained run, sensors) into `line`; returns `serial`"""
+    world = len(recs)
+    K = args.steps
+    utf8_all = sum(r["utf8"] for r in recs)
+    serial = None
+    if flow:   # the same K steps, one batch at a time on one stream
+        sr = [r["serial"] for r in recs]
+        s_job = ((max(x["t1_ns"] for x in sr) - min(x["t0_ns"] for x in sr)) / 1e9 if same_start
+                 else max((x["t1_ns"] - x["t0_ns"]) / 1e9 for x in sr))
+        serial = {"ms_per_step": s_job / K * 1e3, "value": utf8_all * K / s_job / 1e9,
+                  "ms_per_rank": [x["ms_events"] / K for x in sr],
+                  "what": "the same K steps with ONE batch in flight (index -> tiles -> resolve back to back on one stream): "
+                          "`value` of rounds 1-3 before the batch flow"}
+    traffic, traffic_src = pmc_traffic(args.workload, recs[0]["total"], 2 if flow else 1, bool(flow and all(r.get("distinct_inputs") for r in recs)))
+    fracs = [r["alg_read"] / (r["kernel_ms"] / 1e3) / 1e9 / HBM_PEAK_GBS for r in recs]
+    worst = min(range(world), key=lambda i: fracs[i])
+    r0 = recs[0]
+    achieved = recs[worst]["alg_read"] / (recs[worst]["kernel_ms"] / 1e3) / 1e9
+    line.update({
+        "sensors_rank0": r0.get("sensors"),
+        "serial": serial,
         "sustained": r0["sustained"],
         "fix_tiles_rank0": r0["n_fix"], "tiles_rank0": (r0["total"] + _lib.TILE_CHARS - 1) // _lib.TILE_CHARS,
         "roofline": {"bound": "hbm", "kernel": "k_tiles_main", "achieved": achieved, "peak": HBM_PEAK_GBS,
@@ -877,19 +965,8 @@ def build_line(args, recs, mode, devices, same_start):
                                        "of the kernel (`kernel_ms`, all CUs, nothing else on the GPU)") if flow else None,
                      "measured_stream_read": r0["measured_read"],
                      "frac_of_measured_read": (r0["alg_read"] / (r0["kernel_ms"] / 1e3) / 1e9 / r0["measured_read"]) if r0["measured_read"] else None},
-    }
-    if args.take_turns:
-        line["rehearsal"] = ("ranks took turns on shared GPU(s): per-rank times are single-GPU times; value_projected is what "
-                             f"{world} such GPUs would give -- a rehearsal of the N > 1 code path, not a measurement of {world} GPUs")
-        proj = max(walls)
-        line["value_projected"] = utf8_all * K / proj / 1e9
-        line["ms_per_step_projected"] = proj / K * 1e3
-        line["value"] = None
-        line["ms_per_step"] = None
-        if serial:
-            serial["value"] = serial["ms_per_step"] = None
-            serial["ms_per_step_projected"] = max((x["t1_ns"] - x["t0_ns"]) / 1e9 for x in sr) / K * 1e3
-    return line
+    })
+    return serial
 
 
 def parse_args(argv=None):
@@ -897,11 +974,15 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is beside the headline: serial steps, roofline, sustained run, sensors, CPU baselines")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's output (rank 0's boundary bitmask) as DIR/*.npy")
     ap.add_argument("--workload", default="C2", choices=sorted(WORKLOADS))
     ap.add_argument("--strings", type=int, default=0, help="strings per GPU (weak workloads) / in total (strong); default: the workload's")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baselines out")
     ap.add_argument("--cpu-strings", type=int, default=1_000_000)
-    ap.add_argument("--sustain-s", type=float, default=1.0, help="length of the sustained run after the timed region (0 = off)")
+    ap.add_argument("--sustain-s", type=float, default=1.0, help="--full: length of the sustained run after the timed region (0 = off)")
     ap.add_argument("--devices", default="", help="in-process mode: comma-separated HIP device of each rank (default 0..N-1); "
                                                   "a device may repeat (rehearsal on fewer GPUs)")
     ap.add_argument("--dist-backend", default="gloo", choices=["gloo"],
@@ -931,6 +1012,8 @@ def parse_args(argv=None):
                     help="rehearsal on shared GPU(s): the ranks run their timed regions one after the other, so each rank's "
                          "time is what a GPU of its own would give; the line is marked as a rehearsal and carries no `value`")
     args = ap.parse_args(argv)
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
         ap.error("--gpus and --steps must be >= 1, --warmup >= 0")
     if args.in_flight == 0:
@@ -1109,7 +1192,7 @@ def main(argv=None, api=None, out=None):
         mode, same_start = "one process, one context + host thread per GPU (no launcher, no torch, no RCCL)", not args.take_turns
     if rank == 0:
         line = build_line(args, recs, mode, devices, same_start)
-        if not args.no_cpu_baseline:   # next to the GPU number at every N: the host's cores, same corpus (rank 0's shard head)
+        if args.full and not args.no_cpu_baseline:   # next to the GPU number at every N: the host's cores, same corpus (rank 0's shard head)
             n_cpu = min(args.cpu_strings, recs[0]["n_str"], 1_000_000 if args.workload != "C5" else 64)
             line.update(cpu_baselines("C2" if args.workload == "C4" else args.workload, n_cpu))
         print(json.dumps(line), file=out or sys.stdout, flush=True)

@@ -15,6 +15,9 @@ Everything here is DATA: inputs and the outputs the reference itself produced fo
   * corpus_samples.json   -- first 10 000 strings of the C2 / C3 synthetic corpora: SHA-256 of the code points, of the
                              offsets table and of the reference's boundary offsets, so a GPU box without the reference can
                              check generator + kernel end to end.
+  * random_differential.json -- the seeded random strings of tests/test_oracle_golden.py's differential tests: matrix checksum
+                             and split values of the reference's own C under the restated glue (oracle.RefGlue), and SHA-256
+                             digests (per chunk of strings) of the REAL reference's split values and tokens.
 
 Run:  make -C oracle ref && make -C latok_amd/csrc && python3 tests/golden/make_golden.py
 """
@@ -236,6 +239,24 @@ def golden_rules(dt):
     dump("rules_strings.json", {"source": "real reference gen_split_mask with other combo matrices installed", "sets": out})
 
 
+def golden_random_differential(dt):
+    """tests/test_oracle_golden.py: test_refglue_matches_oracle_when_built and test_live_differential_against_reference"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_oracle_golden import differential_digest, live_differential_strings, refglue_strings, texts_sha256
+    import latok_oracle
+    glue = latok_oracle.RefGlue()
+    texts = refglue_strings()
+    refglue = {"texts_sha256": texts_sha256(texts), "items": [
+        {"matrix_sha256": hashlib.sha256(np.ascontiguousarray(glue.gen_parse_matrix(t)).tobytes()).hexdigest(),
+         "splits": glue.split_values(t).astype(int).tolist()} for t in texts]}
+    texts, chunk = live_differential_strings(), 500
+    live = {"texts_sha256": texts_sha256(texts), "chunk": chunk, "chunk_sha256": [
+        differential_digest(texts[i:i + chunk], lambda s: dt.gen_split_mask(dt._gen_parse_matrix(s)), lambda s: list(dt.tokenize(s)))
+        for i in range(0, len(texts), chunk)]}
+    dump("random_differential.json", {"source": "real reference: its latok.c (oracle/_ref) under the restated glue (refglue); "
+                                                "its latok.c + its own latok/core/*.py (live)", "refglue": refglue, "live": live})
+
+
 def main():
     dt = ref_loader.load_ref_python()
     ext = ref_loader.load_ref_ext()
@@ -246,6 +267,7 @@ def main():
     golden_c1(dt)
     golden_corpus(dt)
     golden_rules(dt)
+    golden_random_differential(dt)
 
 
 if __name__ == "__main__":

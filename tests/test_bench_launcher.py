@@ -12,6 +12,7 @@ import sys
 import threading
 import time
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -37,6 +38,9 @@ class FakeLib:
         self.timed_serial = []               # ... of the `serial` region behind it (batch flow on)
         self.flow_calls = 0
         self.second_inputs = []              # (device, cps_b, row_b) of every latok_bench_set_second_input
+        self.beside = []                     # names of the measurements beside the headline (kernel alone, stream read, ...)
+        self.flow_masks = {}                 # device -> (bits_a, bits_b) of its timed flow region
+        self.reads = []                      # (device, allocation, byte offset, bytes) of every latok_memcpy_d2h
 
     def __getattr__(self, name):            # gate functions, corpus offsets: the real thing
         return getattr(self.real, name)
@@ -52,9 +56,10 @@ class FakeLib:
 
     def latok_dev_alloc(self, nbytes):
         with self.lock:
-            self.next_ptr += 0x1000
-            self.live[self.next_ptr] = (self._dev(), nbytes)
-            return self.next_ptr
+            p = self.next_ptr                # (allocations do not overlap: a read can be traced to its buffer)
+            self.next_ptr += 0x1000 + (nbytes + 0xFFF) // 0x1000 * 0x1000
+            self.live[p] = (self._dev(), nbytes)
+            return p
 
     def latok_dev_free(self, p):
         with self.lock:
@@ -62,6 +67,17 @@ class FakeLib:
         return 0
 
     def latok_memcpy_h2d(self, d, s, n):
+        return 0
+
+    def latok_memcpy_d2h(self, dst, src, n):
+        """device memory reads back as fake_words() of the byte offset into its allocation"""
+        with self.lock:
+            base = max(p for p in self.live if p <= src)
+            assert src + n <= base + self.live[base][1], "read past the end of an allocation"
+            self.reads.append((self._dev(), base, src - base, n))
+        assert (src - base) % 8 == 0 and n % 8 == 0
+        words = fake_words((src - base) // 8, n // 8)
+        C.memmove(dst, words.ctypes.data, n)
         return 0
 
     def latok_corpus_fill_device(self, seed, model, sid0, n_str, d_row, d_cps, stream):
@@ -82,6 +98,9 @@ class FakeLib:
         return 0
 
     def latok_bench_split_mask(self, cps, row, n_str, total, bits, warmup, iters, ms_total, ms_tiles, n_fix):
+        if iters > 0:
+            with self.lock:
+                self.beside.append("kernel_only" if ms_total is None else "sustained")
         if ms_total is not None:
             ms_total._obj.value = self.ms_per_pass * iters
         if ms_tiles is not None:
@@ -115,6 +134,7 @@ class FakeLib:
             return 0
         with self.lock:
             self.flow_calls += 1
+            self.flow_masks.setdefault(self._dev(), (bits_a, bits_b))
         return self._region(iters, gate, ms, t0, t1, self.timed)
 
     def latok_bench_set_second_input(self, cps_b, row_b):
@@ -123,12 +143,22 @@ class FakeLib:
         return 0
 
     def latok_bench_tiles_flow(self, cps, row, n_str, total, bits_a, bits_b, iters, ms):
+        with self.lock:
+            self.beside.append("tiles_flow")
         ms._obj.value = 0.8 * self.ms_per_pass * iters
         return 0
 
     def latok_bench_stream_read(self, buf, nbytes, warmup, iters, ms):
+        with self.lock:
+            self.beside.append("stream_read")
         ms._obj.value = 1.0
         return 0
+
+
+def fake_words(w0, n):
+    """the fake device's memory: 64-bit word w holds a fixed hash of w"""
+    w = np.arange(w0, w0 + n, dtype=np.uint64)
+    return (w * np.uint64(0x9E3779B97F4A7C15)) ^ (w >> np.uint64(3))
 
 
 class FakeApi:
@@ -174,7 +204,8 @@ def _run(argv, api):
     return json.loads(lines[0])
 
 
-BASE = ["--steps", "5", "--warmup", "1", "--strings", "2000", "--no-cpu-baseline", "--sustain-s", "0", "--settle-s", "0"]
+BASE = ["--steps", "5", "--warmup", "1", "--strings", "2000", "--full", "--no-cpu-baseline", "--sustain-s", "0", "--settle-s", "0"]
+PLAIN = ["--steps", "5", "--warmup", "1", "--strings", "2000", "--settle-s", "0"]      # what a plain run is given
 
 
 @pytest.mark.parametrize("n", [1, 2, 4, 8])
@@ -221,6 +252,65 @@ def test_in_flight_1_times_one_batch_at_a_time(monkeypatch):
     assert line["in_flight"] == 1 and line["serial"] is None and api.lib.flow_calls == 0 and len(api.lib.timed) == 2
 
 
+@pytest.mark.parametrize("n", [1, 2])
+def test_plain_run_measures_only_the_headline(n, monkeypatch):
+    """without --full: warm-up, the K timed steps and the line's contract keys; nothing measured beside them, no sysfs reads"""
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(bench, "gpu_sensors", lambda *a, **kw: pytest.fail("sensors read in a plain run"))
+    monkeypatch.setattr(bench, "cpu_baselines", lambda *a, **kw: pytest.fail("CPU baseline in a plain run"))
+    api = FakeApi(n_dev=2)
+    line = _run(["--gpus", str(n)] + PLAIN, api)
+    assert api.lib.beside == [] and api.lib.timed_serial == [] and len(api.lib.timed) == n and api.lib.flow_calls == n
+    assert not api.lib.live and all(c.destroyed for c in api.contexts)
+    for key in ("serial", "roofline", "sustained", "sensors_rank0", "fix_tiles_rank0", "cpu_baseline"):
+        assert key not in line
+    assert line["full"] is False and line["steps"] == 5 and line["in_flight"] == 2 and line["distinct_inputs"] is True
+    assert line["higher_is_better"] is True and line["unit"] == "GB/s" and line["dtype"] == "u64" and line["metric"].startswith("input UTF-8")
+    t0s, t1s = [t[2] for t in api.lib.timed], [t[3] for t in api.lib.timed]
+    assert line["ms_per_step"] * 5 == pytest.approx((max(t1s) - min(t0s)) / 1e6, rel=1e-6)
+    assert line["value"] == pytest.approx(line["config"]["utf8_bytes_total"] * 5 / (line["ms_per_step"] * 5 / 1e3) / 1e9, rel=1e-6)
+
+
+@pytest.mark.parametrize("steps,flow", [(5, True), (4, True), (3, False)])
+def test_dump_outputs_writes_the_last_steps_bitmask(tmp_path, monkeypatch, steps, flow):
+    """--dump-outputs: rank 0's bitmask of the LAST timed step (the flow alternates between two), read back after the timed
+    region: boundaries per 8192-char block of the whole batch, 0 / 1 flags of a seeded sample of blocks, their first chars"""
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BLOCKS", 8)
+    model, seed, lo, hi, _, _ = bench.WORKLOADS["C2"]
+    row = np.zeros(2001, np.int64)
+    assert _lib.load().latok_corpus_offsets(seed, 0, 2000, lo, hi, row.ctypes.data) == 0
+    total = int(row[-1])                                         # rank 0's batch
+    words = (total + 63) // 64
+    bits = np.unpackbits(fake_words(0, words).view(np.uint8), bitorder="little")[:total]
+    out = tmp_path / "outs"
+    argv = ["--gpus", "2", "--steps", str(steps), "--warmup", "1", "--strings", "2000", "--settle-s", "0",
+            "--dump-outputs", str(out)] + ([] if flow else ["--in-flight", "1"])
+    api = FakeApi(n_dev=2)
+    _run(argv, api)
+    reads = api.lib.reads
+    assert {r[0] for r in reads} == {0}, "rank 0 alone reads its output back"
+    assert len({r[1] for r in reads}) == 1 and sum(r[3] for r in reads) == 8 * words
+    if flow:
+        a, b = api.lib.flow_masks[0]
+        assert reads[0][1] == (b if (steps - 1) & 1 else a)
+    counts = np.load(out / "split_mask_block_counts.npy")
+    flags = np.load(out / "split_mask_sample_flags.npy")
+    start = np.load(out / "split_mask_sample_start.npy")
+    assert counts.dtype == np.float32 and flags.dtype == np.float32 and start.dtype == np.float64
+    n_blocks = (total + 8191) // 8192
+    assert n_blocks > 8 and counts.size == n_blocks and start.size == 8
+    assert np.all(np.diff(start) > 0) and np.all(start % 8192 == 0) and start[-1] < total
+    # every block count and every sampled flag is what the device held (bits past the last char of the batch left out)
+    padded = np.zeros(n_blocks * 8192, np.uint8)
+    padded[:total] = bits
+    assert np.array_equal(counts, padded.reshape(-1, 8192).sum(axis=1))
+    assert np.array_equal(flags, np.concatenate([bits[int(s):int(s) + 8192] for s in start]))
+    # the same arguments pick the same blocks
+    _run(argv, FakeApi(n_dev=2))
+    assert np.array_equal(np.load(out / "split_mask_sample_start.npy"), start)
+
+
 def test_devices_may_repeat_and_take_turns_serialises(monkeypatch):
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     api = FakeApi(n_dev=1, ms_per_pass=4.0)
@@ -235,7 +325,7 @@ def test_devices_may_repeat_and_take_turns_serialises(monkeypatch):
 def test_strong_scaling_workload_cuts_the_whole_batch(monkeypatch):
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     api = FakeApi(n_dev=4)
-    line = _run(["--gpus", "4", "--workload", "C4", "--steps", "2", "--warmup", "0", "--strings", "1001", "--no-cpu-baseline",
+    line = _run(["--gpus", "4", "--workload", "C4", "--steps", "2", "--warmup", "0", "--strings", "1001", "--full", "--no-cpu-baseline",
                  "--sustain-s", "0"], api)
     fills = sorted(set(api.lib.fills), key=lambda f: f[1])      # (each shard is filled twice: the flow's two input copies)
     assert fills[0][1] == 0 and sum(f[2] for f in fills) == 1001

@@ -1297,7 +1297,9 @@ def test_calls_on_different_streams_are_ordered(gpu, oracle):
     import ctypes as C2
     from latok_amd import _lib, batch
     lib = gpu
-    hip = C2.CDLL("libamdhip64.so")
+    # the HIP runtime the library itself is linked against (a symbol looked up through its handle is searched in its
+    # dependencies): a bare CDLL("libamdhip64.so") binds the copy torch bundles once torch is loaded in the process
+    hip = lib
     s1, s2 = C2.c_void_p(), C2.c_void_p()
     assert hip.hipStreamCreate(C2.byref(s1)) == 0 and hip.hipStreamCreate(C2.byref(s2)) == 0
     rng = random.Random(5150)

@@ -1,6 +1,6 @@
 """The oracle (oracle/latok_oracle.c) pinned against the reference's own golden material and reference-generated
-fixtures (tests/golden/, made by make_golden.py from the REAL reference); plus, when the reference is present (build
-container), a live differential run against it.  CPU only."""
+fixtures (tests/golden/, made by make_golden.py from the REAL reference), random strings included; plus, wherever
+oracle/_ref is built, a live run of the reference's own C against it.  CPU only."""
 import ctypes as C
 import hashlib
 import json
@@ -108,41 +108,57 @@ def test_empty_string_conventions(oracle):
     assert oracle.tokenize(" ") == []
 
 
-def test_refglue_matches_oracle_when_built(oracle):
-    """oracle/_ref (the reference's own C, compiled from its own source) under the restated glue == the restatement."""
-    import ref_loader
-    if not ref_loader.ref_ext_available():
-        pytest.skip("oracle/_ref not built")
-    glue = oracle.RefGlue()
+def refglue_strings():
     rng = random.Random(2)
-    for text in random_strings(rng, 300, 1, 120, ALPHABETS["mixed"]) + random_strings(rng, 100, 1, 300, ALPHABETS["words"]):
-        assert np.array_equal(glue.gen_parse_matrix(text), oracle.gen_parse_matrix(text))
-        assert np.array_equal(glue.split_values(text), oracle.split_values(text))
+    return random_strings(rng, 300, 1, 120, ALPHABETS["mixed"]) + random_strings(rng, 100, 1, 300, ALPHABETS["words"])
+
+
+def live_differential_strings():
+    rng = random.Random(99)
+    alpha = list("abcXYZ  \t.,:/@#$^!1 9éあ日\U0001f913́Ⅷ")
+    return ["".join(rng.choice(alpha) for _ in range(rng.randint(1, 60))) for _ in range(20000)]
+
+
+def texts_sha256(texts):
+    return hashlib.sha256("\x00".join(texts).encode("utf-8", "surrogatepass")).hexdigest()
+
+
+def differential_digest(texts, split_values, tokenize):
+    """SHA-256 over the split values (int64 LE) and the tokens (NUL-joined UTF-8) of every string, in order"""
+    h = hashlib.sha256()
+    for text in texts:
+        h.update(np.asarray(split_values(text)).astype("<i8").tobytes())
+        h.update(("\x00".join(tokenize(text)) + "\x01").encode("utf-8", "surrogatepass"))
+    return h.hexdigest()
+
+
+def test_refglue_matches_oracle_when_built(oracle):
+    """The reference's own C (compiled from its own source) under the restated glue == the restatement, on random strings:
+    against what it gave when random_differential.json was made, and live whenever oracle/_ref is built."""
+    import ref_loader
+    g = load("random_differential.json")["refglue"]
+    texts = refglue_strings()
+    assert texts_sha256(texts) == g["texts_sha256"], "the random strings differ from the ones the fixture was made from"
+    for text, it in zip(texts, g["items"]):
+        assert hashlib.sha256(np.ascontiguousarray(oracle.gen_parse_matrix(text)).tobytes()).hexdigest() == it["matrix_sha256"], text
+        assert oracle.split_values(text).tolist() == it["splits"], text
+    assert len(g["items"]) == len(texts)
+    if ref_loader.ref_ext_available():
+        glue = oracle.RefGlue()
+        for text in texts:
+            assert np.array_equal(glue.gen_parse_matrix(text), oracle.gen_parse_matrix(text))
+            assert np.array_equal(glue.split_values(text), oracle.split_values(text))
 
 
 def test_live_differential_against_reference(oracle):
-    """Build container only: the real reference (its C + its own Python glue) vs the restatement on random input."""
-    import ref_loader
-    if not ref_loader.ref_python_available():
-        pytest.skip("/root/reference not present (expected on the GPU box)")
-    import subprocess
-    import sys
-    code = r'''
-import sys, random, numpy as np
-sys.path.insert(0, %r)
-import ref_loader, latok_oracle as orc
-dt = ref_loader.load_ref_python()
-rng = random.Random(99)
-alpha = list("abcXYZ  \t.,:/@#$^!1 9éあ日\U0001f913́Ⅷ")
-for it in range(20000):
-    s = "".join(rng.choice(alpha) for _ in range(rng.randint(1, 60)))
-    r = dt.gen_split_mask(dt._gen_parse_matrix(s))
-    assert np.array_equal(r, orc.split_values(s)), s
-    assert list(dt.tokenize(s)) == orc.tokenize(s), s
-print("ok")
-''' % os.path.join(os.path.dirname(GOLDEN), "..", "oracle")
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
+    """The real reference (its C + its own Python glue) vs the restatement on 20 000 random strings: split values and tokens
+    of every string, digested per chunk, against what the reference gave when random_differential.json was made."""
+    g = load("random_differential.json")["live"]
+    texts, chunk = live_differential_strings(), g["chunk"]
+    assert texts_sha256(texts) == g["texts_sha256"], "the random strings differ from the ones the fixture was made from"
+    got = [differential_digest(texts[i:i + chunk], oracle.split_values, oracle.tokenize) for i in range(0, len(texts), chunk)]
+    bad = [i for i, (a, b) in enumerate(zip(got, g["chunk_sha256"])) if a != b]
+    assert len(got) == len(g["chunk_sha256"]) and not bad, f"strings {[(i * chunk, (i + 1) * chunk) for i in bad]} differ"
 
 
 def test_reference_generated_rule_tables(oracle):

@@ -1,6 +1,6 @@
-import ctypes as C, sys
+import ctypes as C, os, sys
 import numpy as np
-sys.path.insert(0,'/root/repo')
+sys.path.insert(0,os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from latok_amd import _lib
 lib=_lib.ensure_init()
 for model,(lo,hi) in ((0,(64,192)),(1,(128,384))):
