@@ -205,6 +205,16 @@ struct Ctx {
     hipEvent_t turn_event = nullptr;     // recorded behind the last kernel of every call (StreamTurn)
     hipStream_t turn_stream = nullptr;
     bool turn_stream_valid = false;
+    // test hooks: latok_debug_set_plan_cus (0 = the device's own CU count) and what the last run_pipeline launched
+    int plan_cus = 0;
+    struct LastPlan {
+        latok::LaunchPlan plan{};
+        int64_t n_tiles = 0;
+        int mode = 0;
+        bool small = false, valid = false;
+        const int64_t* fix_count = nullptr;
+        hipStream_t st = nullptr;
+    } last;
 };
 Ctx g_default;                       // latok_init / latok_shutdown
 thread_local Ctx* tl_ctx = nullptr;  // latok_ctx_set_current; nullptr = g_default
@@ -307,39 +317,14 @@ int run_pipeline(Ctx& g, const uint32_t* d_cps, const int64_t* d_row, int64_t n_
     P.n_str = n_str;
     P.total = total;
     P.n_tiles = n_tiles;
-    // A batch of a FLOW leaves part of the chip to the other batch in flight: its persistent tile kernel is planned for 7/8 of
-    // the CUs (4 free per XCD on MI355X), so the first workgroups of the NEXT batch's tile kernel start on the free CUs while
-    // this one still runs, finish early and free CUs for the batch after it -- the start-up (table copy, first tile) and the
-    // ragged end of every tile kernel then overlap another kernel's steady state instead of idling the chip.  Alone, the kernel
-    // is as fast on 224 CUs as on 256 (it is memory bound); in the flow C2 goes from 96 to 85.5-87 us per batch.  Measured on
-    // C2 (profiles/r03_ab_flow_cus.txt): fewer than 32 free CUs gain nothing (16: 97, 24: 96, 28: 94 us), 32: 85.5-87,
-    // 48: 87-90, 64: 87-91, 128 (two kernels side by side on half the chip each): 89.  A segment's tiles go round-robin over
-    // the workgroup's 12 waves, so a plan whose last round holds only a wave or two (216 CUs: 145 tiles = 12 rounds + 1 tile:
-    // 93-96 us) wastes what the free CUs gain: of the candidate shares the first whose last round is at least half full is taken.
-    int n_cu_eff = g.n_cu;
-    if (slot && g.n_cu >= 64) {
-        const int cand[3] = {g.n_cu * 7 / 8, g.n_cu * 13 / 16, g.n_cu * 3 / 4};
-        int best = cand[0], best_fill = -1;
-        for (int c = 0; c < 3; ++c) {
-            int st_ = 0;
-            int64_t ns_ = 0;
-            latok::plan_segments(n_tiles, cand[c], &st_, &ns_);
-            const int wpb = (d_u8 && unit_kind != 0 && !g.rules_on) ? 16 : latok::kWPB;   // waves per workgroup of the tile kernel (tile_wpb)
-            const int fill = (st_ - 1) % wpb + 1;                  // waves busy in a segment's last round
-            if (fill * 2 >= wpb) { best = cand[c]; break; }
-            if (fill > best_fill) { best = cand[c]; best_fill = fill; }
-        }
-        n_cu_eff = best;
-    }
-    if (n_cu_eff < 8) n_cu_eff = g.n_cu < 8 ? g.n_cu : 8;
-    latok::plan_segments(n_tiles, n_cu_eff, &P.seg_tiles, &P.n_segs);
-    // a small UTF-32 batch: one segment, and (below) one launch for the three stages
-    const bool one_launch = stages == 7 && !d_u8 && !tiles_begin && !tiles_end && n_tiles <= latok::kOneSegTiles &&
-                            (mode == latok::kModeBits || mode == latok::kModeRules) && one_segment_enabled();
-    if (one_launch) {
-        P.seg_tiles = (int)(n_tiles < latok::kOneSegTiles ? latok::kOneSegTiles : n_tiles);
-        P.n_segs = 1;
-    }
+    // (the CU share of a batch of a flow, the segment plan and the kernel variants: latok::plan_launch)
+    const int n_cu = g.plan_cus > 0 ? g.plan_cus : g.n_cu;   // latok_debug_set_plan_cus: plan and launch as if the chip had n_cu CUs
+    const bool one_launch_ok = stages == 7 && !d_u8 && !tiles_begin && !tiles_end && one_segment_enabled();
+    latok::LaunchPlan L;
+    latok::plan_launch(n_tiles, n_cu, slot != nullptr, mode, one_launch_ok, &L);
+    P.seg_tiles = L.seg_tiles;
+    P.n_segs = L.n_segs;
+    const bool one_launch = L.one_launch != 0;
     if ((size_t)P.n_segs * (sizeof(latok::Fn64) + sizeof(latok::Hd64)) > w_seg.cap || (size_t)n_tiles * 16 > w_summ.cap)
         return fail(LATOK_ERR_INVALID, "internal: workspace too small for %lld segments / %lld tiles", (long long)P.n_segs, (long long)n_tiles);
     if (d_codes && mode != latok::kModeBits && mode != latok::kModeRules)
@@ -371,15 +356,23 @@ int run_pipeline(Ctx& g, const uint32_t* d_cps, const int64_t* d_row, int64_t n_
     P.bm_a2 = bm_a2;
     P.bm_flags = bm_flags;
     P.done = (stages & 4) ? done : latok::DoneSignal{nullptr, 0, nullptr};
+    // what is launched, for latok_debug_last_plan (a few stores)
+    g.last.plan = L;
+    g.last.n_tiles = n_tiles;
+    g.last.mode = mode;
+    g.last.small = g.pin.d && (d_u8 ? (const void*)d_u8 : (const void*)d_cps) == g.pin.d;
+    g.last.fix_count = (const int64_t*)w_fix.p;
+    g.last.st = st;
+    g.last.valid = true;
     if (one_launch) {
         HIP_TRY(latok::launch_one_segment(P, mode, st));
         return LATOK_OK;
     }
     if (stages & 1) HIP_TRY(latok::launch_tile_index(P, st));   // (the kernel-timing loop of latok_bench_split_mask launches stage 1 alone)
     if (tiles_begin) HIP_TRY(hipEventRecord(tiles_begin, st));
-    if (stages & 2) HIP_TRY(latok::launch_split_tiles(P, mode, g.n_cu, st, slot != nullptr));   // (the plan may leave CUs free; the grid never exceeds the chip)
+    if (stages & 2) HIP_TRY(latok::launch_split_tiles(P, mode, L, st));
     if (tiles_end) HIP_TRY(hipEventRecord(tiles_end, st));
-    if (stages & 4) HIP_TRY(latok::launch_resolve_fix(P, mode, g.n_cu, st));
+    if (stages & 4) HIP_TRY(latok::launch_resolve_fix(P, mode, L, st));
     return LATOK_OK;
 }
 
@@ -485,6 +478,8 @@ static void ctx_release(Ctx& g) {   // caller holds g.mu (or owns g exclusively)
     g.pin_tot.release();
     g.done_ctr.release();
     g.rules_on = false;
+    g.plan_cus = 0;
+    g.last = Ctx::LastPlan{};
     for (DevBuf* b : {&g.t1, &g.t1rule, &g.tb6, &g.tb6rule, &g.t2code, &g.t2cls, &g.cw, &g.summ, &g.seg_agg, &g.fix_count, &g.h_cps, &g.h_row, &g.h_out,
                       &g.bits, &g.space, &g.kept, &g.wcnt, &g.wpref, &g.counts, &g.bases, &g.scan_tot, &g.tile_first, &g.u_bytes,
                       &g.u_boff, &g.u_cnt, &g.u_row, &g.u_pref, &g.u_lead, &g.u_bspace, &g.u_cpbits, &g.u_cpspace, &g.scalar, &g.h_aux, &g.chain, &g.chain_ctl, &g.codes})
@@ -2104,6 +2099,72 @@ int latok_debug_set_scan_epoch(unsigned epoch) {
     LATOK_ENTER();
     g.scan_epoch = epoch & 0x3FFFFu;
     return LATOK_OK;
+}
+
+/* test hook (not part of the ABI; needs no device): the constants that decide the tile pipeline's plans and host paths, so that
+ * tests take their thresholds from the library: out[0..8] = kTile, kWPB, kNarrowWPB, kSegMax, kOneSegTiles, kFastTailTiles,
+ * kSmallChars, kSmallStrings, tiles per workgroup of k_lead_compress.  Returns the number of values written. */
+extern "C" int latok_debug_limits(int64_t* out, int n) {
+    const int64_t v[9] = {latok::kTile, latok::kWPB, latok::kNarrowWPB, latok::kSegMax, latok::kOneSegTiles, latok::kFastTailTiles,
+                          kSmallChars, kSmallStrings, latok::kCompressWaves};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 9 ? n : 9;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
+// LaunchPlan as the hooks report it: out[0..11] = n_cu_eff, seg_tiles, n_segs, rounds, grid of k_tiles_main, grid of
+// k_resolve_fix, fast_tail, pf, wpb, nw, one_launch, n_tiles
+static int put_plan(const latok::LaunchPlan& L, int64_t n_tiles, int64_t* out, int n) {
+    const int64_t v[12] = {L.n_cu_eff, L.seg_tiles, L.n_segs, L.rounds, L.grid, L.one_launch ? 0 : L.grid, L.fast_tail, L.pf, L.wpb, L.nw,
+                           L.one_launch, n_tiles};
+    const int k = n < 12 ? n : 12;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
+/* test hook (not part of the ABI; needs no device): what run_pipeline would launch for a batch of n_tiles tiles on n_cu CUs,
+ * in_flow = a batch of a flow, mode = latok::kMode* after the rules (the one-launch path as a blocking UTF-32 call would take
+ * it).  Fills out as put_plan, returns the number of values written. */
+extern "C" int latok_debug_plan(int64_t n_tiles, int n_cu, int in_flow, int mode, int64_t* out, int n) {
+    if (!out || n < 0 || n_tiles < 1 || n_cu < 1 || mode < latok::kModeBits || mode > latok::kModeValuesRules)
+        return fail(LATOK_ERR_INVALID, "n_tiles >= 1, n_cu >= 1, mode 0..%d", latok::kModeValuesRules);
+    latok::LaunchPlan L;
+    latok::plan_launch(n_tiles, n_cu, in_flow != 0, mode, one_segment_enabled(), &L);
+    return put_plan(L, n_tiles, out, n);
+}
+
+/* test hook (not part of the ABI): the tile pipeline of the current context (k_tile_index / k_tiles_main / k_resolve_fix /
+ * k_one_segment) plans and launches as if the device had n_cu CUs; 0 = the device's own count.  The pipeline's workgroups
+ * never wait for one another (they share data between launches only), so a smaller grid only makes each persistent
+ * workgroup walk more segments.  Compaction, featurize and the other kernels keep their grids. */
+extern "C" int latok_debug_set_plan_cus(int n_cu) {
+    LATOK_ENTER();
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (n_cu != 0 && (n_cu < 8 || n_cu > g.n_cu)) return fail(LATOK_ERR_INVALID, "plan CUs must be 0 or 8..%d", g.n_cu);
+    g.plan_cus = n_cu;
+    return LATOK_OK;
+}
+
+/* test hook (not part of the ABI): what the last run_pipeline of the current context launched.  out[0] = mode (after the
+ * rules), out[1] = 1 if a host batch ran in place on pinned memory (small-batch path), out[2] = tiles recomputed by the
+ * resolve stage (read after a synchronisation of the call's stream), out[3..14] = the plan as latok_debug_plan reports it.
+ * Returns the number of values written, 0 when nothing has run. */
+extern "C" int latok_debug_last_plan(int64_t* out, int n) {
+    LATOK_ENTER();
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    if (!g.last.valid) return 0;
+    int64_t fix = 0;
+    HIP_TRY(hipStreamSynchronize(g.last.st));
+    HIP_TRY(hipMemcpy(&fix, g.last.fix_count, 8, hipMemcpyDeviceToHost));
+    const int64_t head[3] = {g.last.mode, g.last.small ? 1 : 0, fix};
+    int k = 0;
+    for (; k < 3 && k < n; ++k) out[k] = head[k];
+    if (n > 3) k += put_plan(g.last.plan, g.last.n_tiles, out + 3, n - 3);
+    return k;
 }
 
 /* test hook (not part of the ABI; needs no device): the flow's routing of batches to slots (flow_hazards.h) driven without a

@@ -485,7 +485,7 @@ __global__ __launch_bounds__(scatter_waves(KIND) * 64) void k_counts_scatter(
 // per row offset.
 // *odd is raised when the byte-space model and the decoder's model of MALFORMED input differ: a continuation byte with no lead
 // byte within the 3 bytes before it, or at the start of a string (the host then takes the staged decoder instead).
-constexpr int kCompressWaves = 16;                         // tiles per workgroup
+// kCompressWaves (kernels.h): tiles per workgroup
 constexpr int kCompressWords = kCompressWaves * 64;        // input words per workgroup = output words it can own (+ 1)
 template <bool TWO>   // TWO: a second byte-space mask (the SPACE plane, for token spans) is packed the same way into out_mask2
 __global__ __launch_bounds__(kCompressWaves * 64) void k_lead_compress(

@@ -148,12 +148,33 @@ struct FeatParams {
 hipError_t launch_features_tiles(const FeatParams& P, int n_cu, hipStream_t st);
 
 void plan_segments(int64_t n_tiles, int n_cu, int* seg_tiles, int64_t* n_segs);
-hipError_t launch_tile_index(const SplitParams& P, hipStream_t st);   // stage 0: P.tile_first (must be set)
-hipError_t launch_split_tiles(const SplitParams& P, int mode, int n_cu, hipStream_t st, bool in_flow = false);   // in_flow: a batch of a flow (deeper prefetch)
-hipError_t launch_resolve_fix(const SplitParams& P, int mode, int n_cu, hipStream_t st);
 // the three stages in one launch of one workgroup: batches of at most kOneSegTiles tiles planned as ONE segment
 // (P.n_segs = 1, P.seg_tiles >= P.n_tiles), UTF-32 bitmask modes (kModeBits / kModeRules)
 constexpr int64_t kOneSegTiles = 24;
+constexpr int64_t kFastTailTiles = 256;   // k_tiles_main<.., FAST_TAIL>: batches of at most ~1 M chars (beyond, one tile's latency is noise)
+constexpr int kNarrowWPB = 16;            // Latin-1 / UCS-2 tile kernels: 4 waves per SIMD (<= 128 VGPRs)
+constexpr int kCpsPrefetchRows = 2;       // rows (1 KiB) of the wave's next UTF-32 tile requested before phase 2 of the current one
+constexpr int kCpsPrefetchRowsFlow = 6;   // the same in a batch of a flow (split_kernels.hip)
+// What the tile pipeline launches for a batch: the segment plan and the kernel variants.  plan_launch is the only place
+// that decides it; run_pipeline launches what it says and the test hooks (latok_debug_plan / _last_plan) report it.
+struct LaunchPlan {
+    int n_cu_eff;        // CUs the segments are planned for (a batch of a flow: its share of the chip)
+    int seg_tiles;
+    int64_t n_segs;
+    int64_t rounds;      // segments the busiest workgroup walks
+    int grid;            // workgroups of k_tiles_main and k_resolve_fix (k_one_segment: 1)
+    int fast_tail;       // k_tiles_main<MODE, FAST_TAIL = true>
+    int pf;              // rows of the next UTF-32 tile prefetched (k_tiles_main's PF)
+    int wpb;             // waves per workgroup of the tile kernel
+    int nw;              // waves per workgroup of the resolve stage: nw * 64 >= seg_tiles
+    int one_launch;      // k_one_segment: the three stages in one launch
+};
+// n_cu: CUs of the device (or the context's test cap); one_launch_ok: the call may take k_one_segment (all three stages,
+// no timing events between them)
+void plan_launch(int64_t n_tiles, int n_cu, bool in_flow, int mode, bool one_launch_ok, LaunchPlan* L);
+hipError_t launch_tile_index(const SplitParams& P, hipStream_t st);   // stage 0: P.tile_first (must be set)
+hipError_t launch_split_tiles(const SplitParams& P, int mode, const LaunchPlan& L, hipStream_t st);
+hipError_t launch_resolve_fix(const SplitParams& P, int mode, const LaunchPlan& L, hipStream_t st);
 hipError_t launch_one_segment(const SplitParams& P, int mode, hipStream_t st);
 // batches of at most one tile, everything in one launch (split_kernels.hip: k_small_batch); P.t1 / P.t2 / P.rules / P.cps /
 // P.row_off / P.n_str / P.total must be set, kind 0 = offsets, 1 = token spans.  done (or NULL): a pinned host word that
@@ -194,6 +215,7 @@ hipError_t launch_counts_scatter(int kind, bool out32, const uint64_t* bits, con
                                  const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words,
                                  int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,
                                  const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st, DoneSignal done = DoneSignal{nullptr, 0, nullptr});
+constexpr int kCompressWaves = 16;   // k_lead_compress: tiles (= waves) per workgroup
 // code-point boundary mask + code-point row offsets from the byte-space mask and the lead-byte mask of a UTF-8 batch
 // (bmask2 / out_mask2: optionally a second mask -- the SPACE plane -- packed the same way, for token spans in code-point units)
 hipError_t launch_lead_compress(const uint64_t* bmask, const uint64_t* bmask2, const uint64_t* lead, const int64_t* tile_rank,

@@ -434,12 +434,12 @@ __device__ __forceinline__ uint32_t bytes_halo_load(const uint8_t* __restrict__ 
     return hb;
 }
 
-constexpr int kCpsPrefetchRows = 2;   // rows (1 KiB) of the wave's next UTF-32 tile requested before phase 2 of the current one
+// kCpsPrefetchRows (kernels.h): rows (1 KiB) of the wave's next UTF-32 tile requested before phase 2 of the current one
 // ... and in the tile kernel of a FLOW batch (two batches in flight, each planned for 7/8 of the CUs): six.  Same box, R = 2 / 4 / 5 / 6:
 // C2 through the flow 1 424 / 1 434 / 1 439 / 1 448 GB/s (sustained 1 472 / 1 487 / 1 489 / 1 500), C3 2 450 -> 2 585 (+5 %) -- but
 // one batch at a time 1 213 -> 1 205 on C2, 2 306 -> 2 266 on C3, the isolated kernel 94.5 -> 95.2 us: the depth that pays while another
-// kernel shares the memory system costs a little when the kernel is alone, so the launch scheme picks the instantiation.
-constexpr int kCpsPrefetchRowsFlow = 6;
+// kernel shares the memory system costs a little when the kernel is alone, so the launch scheme picks the instantiation
+// (kCpsPrefetchRowsFlow, kernels.h).
 constexpr int kCpsPrefetchMax = kCpsPrefetchRowsFlow;
 struct CpsPrefetch {
     u32x4 v[kCpsPrefetchMax];
@@ -1311,7 +1311,7 @@ constexpr int lds_total(int mode) { return mode_base(mode) == kModeBytes ? kLdsT
 // Waves per workgroup of the TILE kernel.  The Latin-1 kernel needs <= 128 VGPRs and its LDS map has room, so it runs 16 waves
 // per CU (4 per SIMD): its waves spend half their life in s_waitcnt, a fourth wave per SIMD fills part of that.  The
 // buffers of waves 12..15 sit behind the rest of the map, so that every other offset is the same for all kernels.
-constexpr int kNarrowWPB = 16;   // Latin-1 / UCS-2 tile kernels: 4 waves per SIMD (<= 128 VGPRs)
+// (kNarrowWPB, kernels.h)
 constexpr int tile_wpb(int mode) {
     return mode_base(mode) == kModeLatin1 && !mode_rules(mode) ? kNarrowWPB
          : (mode_base(mode) == kModeUcs2 && !mode_rules(mode) ? kNarrowWPB : kWPB);   // (the rule interpreter needs > 128 VGPRs)
@@ -2649,17 +2649,57 @@ void plan_segments(int64_t n_tiles, int n_cu, int* seg_tiles, int64_t* n_segs) {
     *n_segs = (n_tiles + s - 1) / s;
 }
 
-constexpr int64_t kFastTailTiles = 256;   // ~1 M chars: beyond that one tile's latency is noise
-static inline int grid_for(const SplitParams& P, int n_cu) {
-    return (int)(P.n_segs < n_cu ? (P.n_segs < 1 ? 1 : P.n_segs) : n_cu);
+void plan_launch(int64_t n_tiles, int n_cu, bool in_flow, int mode, bool one_launch_ok, LaunchPlan* L) {
+    const int wpb = tile_wpb(mode);
+    // A batch of a FLOW leaves part of the chip to the other batch in flight: its persistent tile kernel is planned for 7/8 of
+    // the CUs (4 free per XCD on MI355X), so the first workgroups of the NEXT batch's tile kernel start on the free CUs while
+    // this one still runs, finish early and free CUs for the batch after it -- the start-up (table copy, first tile) and the
+    // ragged end of every tile kernel then overlap another kernel's steady state instead of idling the chip.  Alone, the kernel
+    // is as fast on 224 CUs as on 256 (it is memory bound); in the flow C2 goes from 96 to 85.5-87 us per batch.  Measured on
+    // C2 (profiles/r03_ab_flow_cus.txt): fewer than 32 free CUs gain nothing (16: 97, 24: 96, 28: 94 us), 32: 85.5-87,
+    // 48: 87-90, 64: 87-91, 128 (two kernels side by side on half the chip each): 89.  A segment's tiles go round-robin over
+    // the workgroup's 12 waves, so a plan whose last round holds only a wave or two (216 CUs: 145 tiles = 12 rounds + 1 tile:
+    // 93-96 us) wastes what the free CUs gain: of the candidate shares the first whose last round is at least half full is taken.
+    int n_cu_eff = n_cu;
+    if (in_flow && n_cu >= 64) {
+        const int cand[3] = {n_cu * 7 / 8, n_cu * 13 / 16, n_cu * 3 / 4};
+        int best = cand[0], best_fill = -1;
+        for (int c = 0; c < 3; ++c) {
+            int st_ = 0;
+            int64_t ns_ = 0;
+            plan_segments(n_tiles, cand[c], &st_, &ns_);
+            const int fill = (st_ - 1) % wpb + 1;                  // waves busy in a segment's last round
+            if (fill * 2 >= wpb) { best = cand[c]; break; }
+            if (fill > best_fill) { best = cand[c]; best_fill = fill; }
+        }
+        n_cu_eff = best;
+    }
+    if (n_cu_eff < 8) n_cu_eff = n_cu < 8 ? n_cu : 8;
+    L->n_cu_eff = n_cu_eff;
+    plan_segments(n_tiles, n_cu_eff, &L->seg_tiles, &L->n_segs);
+    // a small UTF-32 batch: one segment, and one launch for the three stages
+    L->one_launch = one_launch_ok && n_tiles <= kOneSegTiles && (mode == kModeBits || mode == kModeRules);
+    if (L->one_launch) {
+        L->seg_tiles = (int)(n_tiles < kOneSegTiles ? kOneSegTiles : n_tiles);
+        L->n_segs = 1;
+    }
+    // (the plan may leave CUs free; the grid never exceeds the chip)
+    L->grid = L->one_launch ? 1 : (int)(L->n_segs < n_cu ? (L->n_segs < 1 ? 1 : L->n_segs) : n_cu);
+    L->rounds = (L->n_segs + L->grid - 1) / L->grid;
+    L->fast_tail = !L->one_launch && n_tiles <= kFastTailTiles && (mode == kModeBits || mode == kModeRules);
+    L->pf = mode == kModeBits && in_flow && !L->fast_tail && !L->one_launch ? kCpsPrefetchRowsFlow : kCpsPrefetchRows;
+    L->wpb = L->one_launch ? kWPB : wpb;
+    // The bitmask modes repair almost everything in place, so their resolve stage is pure latency and runs with as few
+    // waves as cover a segment; the modes that recompute tiles keep all 12 waves for that.
+    const bool narrow_resolve = mode == kModeBits || mode == kModeBytes || mode == kModeLatin1 || mode == kModeUcs2;
+    L->nw = L->one_launch || !narrow_resolve ? kWPB : (L->seg_tiles <= 128 ? 2 : (L->seg_tiles <= 256 ? 4 : kWPB));
 }
 
-hipError_t launch_split_tiles(const SplitParams& P, int mode, int n_cu, hipStream_t st, bool in_flow) {
-    const dim3 grid(grid_for(P, n_cu)), block(kWPB * 64);
-    const bool fast_tail = P.n_tiles <= kFastTailTiles;
-    if (mode == kModeBits && in_flow && !fast_tail) hipLaunchKernelGGL((k_tiles_main<kModeBits, false, kCpsPrefetchRowsFlow>), grid, block, 0, st, P);
-    else if (mode == kModeBits && fast_tail) hipLaunchKernelGGL((k_tiles_main<kModeBits, true>), grid, block, 0, st, P);
-    else if (mode == kModeRules && fast_tail) hipLaunchKernelGGL((k_tiles_main<kModeRules, true>), grid, block, 0, st, P);
+hipError_t launch_split_tiles(const SplitParams& P, int mode, const LaunchPlan& L, hipStream_t st) {
+    const dim3 grid(L.grid), block(kWPB * 64);
+    if (mode == kModeBits && L.pf == kCpsPrefetchRowsFlow) hipLaunchKernelGGL((k_tiles_main<kModeBits, false, kCpsPrefetchRowsFlow>), grid, block, 0, st, P);
+    else if (mode == kModeBits && L.fast_tail) hipLaunchKernelGGL((k_tiles_main<kModeBits, true>), grid, block, 0, st, P);
+    else if (mode == kModeRules && L.fast_tail) hipLaunchKernelGGL((k_tiles_main<kModeRules, true>), grid, block, 0, st, P);
     else if (mode == kModeBits) hipLaunchKernelGGL((k_tiles_main<kModeBits>), grid, block, 0, st, P);
     else if (mode == kModeValues) hipLaunchKernelGGL((k_tiles_main<kModeValues>), grid, block, 0, st, P);
     else if (mode == kModeRules) hipLaunchKernelGGL((k_tiles_main<kModeRules>), grid, block, 0, st, P);
@@ -2682,33 +2722,26 @@ hipError_t launch_one_segment(const SplitParams& P, int mode, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_resolve_fix(const SplitParams& P, int mode, int n_cu, hipStream_t st) {
-    const dim3 grid(grid_for(P, n_cu)), block(kWPB * 64);
-    // The bitmask mode repairs almost everything in place, so its resolve stage is pure latency and runs with as few
-    // waves as cover a segment; the modes that recompute tiles keep all 12 waves for that.
-    if (mode == kModeBits) {
-        if (P.seg_tiles <= 128) hipLaunchKernelGGL((k_resolve_fix<kModeBits, 2>), grid, dim3(128), 0, st, P);
-        else if (P.seg_tiles <= 256) hipLaunchKernelGGL((k_resolve_fix<kModeBits, 4>), grid, dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((k_resolve_fix<kModeBits, kWPB>), grid, block, 0, st, P);
-    } else if (mode == kModeValues) hipLaunchKernelGGL((k_resolve_fix<kModeValues, kWPB>), grid, block, 0, st, P);
+hipError_t launch_resolve_fix(const SplitParams& P, int mode, const LaunchPlan& L, hipStream_t st) {
+    if (L.nw * 64 < P.seg_tiles) return hipErrorInvalidValue;   // one thread per tile of a segment
+    const dim3 grid(L.grid), block(kWPB * 64);
+    // (byte space: ASCII tiles are repaired in place here too; measured better with few waves on C2 and C3)
+#define LATOK_RESOLVE_NW(M)                                                                            \
+    if (L.nw == 2) hipLaunchKernelGGL((k_resolve_fix<M, 2>), grid, dim3(128), 0, st, P);               \
+    else if (L.nw == 4) hipLaunchKernelGGL((k_resolve_fix<M, 4>), grid, dim3(256), 0, st, P);          \
+    else hipLaunchKernelGGL((k_resolve_fix<M, kWPB>), grid, block, 0, st, P)
+    if (mode == kModeBits) { LATOK_RESOLVE_NW(kModeBits); }
+    else if (mode == kModeValues) hipLaunchKernelGGL((k_resolve_fix<kModeValues, kWPB>), grid, block, 0, st, P);
     else if (mode == kModeRules) hipLaunchKernelGGL((k_resolve_fix<kModeRules, kWPB>), grid, block, 0, st, P);
     else if (mode == kModeBytesRules) hipLaunchKernelGGL((k_resolve_fix<kModeBytesRules, kWPB>), grid, block, 0, st, P);
     else if (mode == kModeLatin1Rules) hipLaunchKernelGGL((k_resolve_fix<kModeLatin1Rules, kWPB>), grid, block, 0, st, P);
     else if (mode == kModeUcs2Rules) hipLaunchKernelGGL((k_resolve_fix<kModeUcs2Rules, kWPB>), grid, block, 0, st, P);
     else if (mode == kModeValuesRules) hipLaunchKernelGGL((k_resolve_fix<kModeValuesRules, kWPB>), grid, block, 0, st, P);
-    else if (mode == kModeBytes) {   // (ASCII tiles are repaired in place here too; measured better with few waves on C2 and C3)
-        if (P.seg_tiles <= 128) hipLaunchKernelGGL((k_resolve_fix<kModeBytes, 2>), grid, dim3(128), 0, st, P);
-        else if (P.seg_tiles <= 256) hipLaunchKernelGGL((k_resolve_fix<kModeBytes, 4>), grid, dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((k_resolve_fix<kModeBytes, kWPB>), grid, block, 0, st, P);
-    } else if (mode == kModeLatin1) {
-        if (P.seg_tiles <= 128) hipLaunchKernelGGL((k_resolve_fix<kModeLatin1, 2>), grid, dim3(128), 0, st, P);
-        else if (P.seg_tiles <= 256) hipLaunchKernelGGL((k_resolve_fix<kModeLatin1, 4>), grid, dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((k_resolve_fix<kModeLatin1, kWPB>), grid, block, 0, st, P);
-    } else if (mode == kModeUcs2) {
-        if (P.seg_tiles <= 128) hipLaunchKernelGGL((k_resolve_fix<kModeUcs2, 2>), grid, dim3(128), 0, st, P);
-        else if (P.seg_tiles <= 256) hipLaunchKernelGGL((k_resolve_fix<kModeUcs2, 4>), grid, dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((k_resolve_fix<kModeUcs2, kWPB>), grid, block, 0, st, P);
-    } else hipLaunchKernelGGL((k_resolve_fix<kModeBlockMask, kWPB>), grid, block, 0, st, P);
+    else if (mode == kModeBytes) { LATOK_RESOLVE_NW(kModeBytes); }
+    else if (mode == kModeLatin1) { LATOK_RESOLVE_NW(kModeLatin1); }
+    else if (mode == kModeUcs2) { LATOK_RESOLVE_NW(kModeUcs2); }
+    else hipLaunchKernelGGL((k_resolve_fix<kModeBlockMask, kWPB>), grid, block, 0, st, P);
+#undef LATOK_RESOLVE_NW
     return hipGetLastError();
 }
 

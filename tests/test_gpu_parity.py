@@ -930,16 +930,28 @@ def test_runtime_rule_tables_are_validated(gpu):
 
 
 def test_small_batch_path_thresholds(gpu, oracle):
-    """Host-pointer calls up to 16 384 chars / 512 strings run on pinned mapped memory in place (api.cpp: kSmallChars,
-    kSmallStrings); the results must not depend on which side of the thresholds a batch falls."""
+    """Host-pointer calls up to kSmallChars chars / kSmallStrings strings run on pinned mapped memory in place (api.cpp);
+    the results must not depend on which side of the thresholds a batch falls.  The limits come from the library
+    (latok_debug_limits), and every case says which side it is on (latok_debug_last_plan)."""
     from latok_amd import batch
+    lim = np.zeros(8, np.int64)   # latok_debug_limits: ..., [6] kSmallChars, [7] kSmallStrings
+    gpu.latok_debug_limits.restype, gpu.latok_debug_limits.argtypes = C.c_int, [C.c_void_p, C.c_int]
+    assert gpu.latok_debug_limits(lim.ctypes.data, 8) == 8
+    sc, ss = int(lim[6]), int(lim[7])
     rng = random.Random(4242)
-    for total, n_str in [(16384, 1), (16385, 1), (16384, 512), (16384, 513), (16000, 512), (100, 513), (1, 1), (4096, 7)]:
+    fn = gpu.latok_debug_last_plan
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int]
+    for total, n_str in [(sc, 1), (sc + 1, 1), (sc, ss), (sc, ss + 1), (sc - 1, ss - 1), (sc + 1, ss), (100, ss + 1), (1, 1), (4096, 7)]:
         cuts = sorted(rng.sample(range(1, total), min(n_str - 1, total - 1))) if n_str > 1 else []
         cuts += [total] * (n_str - 1 - len(cuts))   # not enough room for distinct cuts: the rest are empty strings
-        blob = "".join(rng.choice(ALPHABETS["mixed"]) for _ in range(total))
+        blob = "".join(rng.choices(ALPHABETS["mixed"], k=total))
         texts = [blob[a:b] for a, b in zip([0] + cuts, cuts + [total])]
         assert len(texts) == n_str and sum(map(len, texts)) == total
+        cps, row = pack(texts)
+        assert np.array_equal(batch.split_mask_batch(cps, row), oracle.split_batch(cps, row, want_values=False)[1])
+        out = np.zeros(3, np.int64)
+        assert fn(out.ctypes.data, 3) == 3
+        assert out[1] == int(total <= sc and n_str <= ss), (total, n_str, out)
         _check_batch(oracle, texts)
         got = batch.tokenize_batch(texts)
         assert got == [oracle.tokenize(t) if t else [] for t in texts]

@@ -388,3 +388,91 @@ def test_flow_routing_orders_every_conflicting_pair():
             where = {}
         where[buf] = s
     reset()
+
+
+# field order of latok_debug_limits / latok_debug_plan (api.cpp)
+LIMIT_NAMES = ("kTile", "kWPB", "kNarrowWPB", "kSegMax", "kOneSegTiles", "kFastTailTiles", "kSmallChars", "kSmallStrings",
+               "kCompressWaves")
+PLAN_NAMES = ("n_cu_eff", "seg_tiles", "n_segs", "rounds", "grid_tiles", "grid_resolve", "fast_tail", "pf", "wpb", "nw", "one_launch",
+              "n_tiles")
+MODES = {"bits": 0, "values": 1, "block_mask": 2, "rules": 3, "bytes": 4, "latin1": 5, "ucs2": 6, "bytes_rules": 7,
+         "latin1_rules": 8, "ucs2_rules": 9, "values_rules": 10}
+
+
+def debug_limits():
+    from latok_amd import _lib
+    fn = _lib.load().latok_debug_limits
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int]
+    out = np.zeros(len(LIMIT_NAMES), np.int64)
+    assert fn(out.ctypes.data, out.size) == out.size
+    return dict(zip(LIMIT_NAMES, out.tolist()))
+
+
+def debug_plan(n_tiles, n_cu, in_flow, mode):
+    from latok_amd import _lib
+    fn = _lib.load().latok_debug_plan
+    fn.restype, fn.argtypes = C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    out = np.zeros(len(PLAN_NAMES), np.int64)
+    assert fn(n_tiles, n_cu, int(in_flow), mode, out.ctypes.data, out.size) == out.size
+    return dict(zip(PLAN_NAMES, out.tolist()))
+
+
+def test_limits_hook_matches_the_python_mirror():
+    from latok_amd import _lib, batch
+    lim = debug_limits()
+    assert lim["kTile"] == _lib.TILE_CHARS
+    assert (lim["kSmallChars"], lim["kSmallStrings"]) == (batch._SMALL_CHARS, batch._SMALL_STRINGS)
+    assert lim["kSegMax"] == lim["kWPB"] * 64 and lim["kWPB"] <= lim["kOneSegTiles"] <= lim["kFastTailTiles"]
+
+
+def test_launch_plan_sweep():
+    """latok_debug_plan reports what run_pipeline launches (latok::plan_launch is the only place that decides it), without a
+    device: over batch sizes from 1 tile to 10^6 (dense around every threshold), several chip sizes and both call kinds,
+    every plan covers its tiles with segments the kernels can hold, and every variant is taken exactly where it should be."""
+    lim = debug_limits()
+    wpb, seg_max, one, fast = lim["kWPB"], lim["kSegMax"], lim["kOneSegTiles"], lim["kFastTailTiles"]
+    edges = {1, one, fast, 10 ** 6}
+    for n_cu in (8, 64, 224, 256, 304):
+        for k in (wpb, 128, 256, seg_max):            # seg_tiles edges: n_cu * k tiles, one round / two rounds
+            edges |= {n_cu * k, 2 * n_cu * k}
+    tiles = set(range(1, 600)) | set(np.unique(np.geomspace(1, 10 ** 6, 400).astype(np.int64)).tolist())
+    for e in edges:
+        tiles |= {t for t in range(e - 3, e + 4) if 1 <= t <= 10 ** 6}
+    seen = set()
+    for n_cu in (8, 64, 224, 256, 304):
+        shares = {n_cu * 7 // 8, n_cu * 13 // 16, n_cu * 3 // 4}
+        for in_flow in (False, True):
+            for mode_name, mode in MODES.items():
+                for t in sorted(tiles) if mode_name in ("bits", "latin1") else sorted(tiles)[::7]:
+                    p = debug_plan(t, n_cu, in_flow, mode)
+                    st, ns = p["seg_tiles"], p["n_segs"]
+                    assert p["n_tiles"] == t
+                    utf32_one = mode_name in ("bits", "rules") and t <= one
+                    assert p["one_launch"] == int(utf32_one), (p, mode_name)
+                    if p["one_launch"]:
+                        assert ns == 1 and st >= t and p["grid_tiles"] == 1 and p["fast_tail"] == 0
+                        continue
+                    assert (ns - 1) * st < t <= ns * st, p
+                    assert wpb <= st <= seg_max, p
+                    assert p["nw"] * 64 >= st, p
+                    assert 1 <= p["grid_tiles"] == p["grid_resolve"] <= n_cu, p
+                    assert p["rounds"] == -(-ns // p["grid_tiles"]), p
+                    assert p["fast_tail"] == int(t <= fast and mode_name in ("bits", "rules")), (p, mode_name)
+                    assert p["wpb"] == (lim["kNarrowWPB"] if mode_name in ("latin1", "ucs2") else wpb), (p, mode_name)
+                    assert p["pf"] == (6 if in_flow and mode_name == "bits" and t > fast else 2), (p, mode_name)
+                    if in_flow and n_cu >= 64:
+                        assert p["n_cu_eff"] in shares, (p, shares)
+                    else:
+                        assert p["n_cu_eff"] == n_cu, p
+                    if mode_name in ("bits", "bytes", "latin1", "ucs2"):
+                        assert p["nw"] == (2 if st <= 128 else 4 if st <= 256 else wpb), p
+                    else:
+                        assert p["nw"] == wpb, p
+                    seen.add((st > wpb, p["nw"], p["rounds"] > 1, st == seg_max))
+    # the sweep reached every resolve width, multi-round plans and full-size segments
+    assert {nw for _, nw, _, _ in seen} == {2, 4, wpb}
+    assert any(r for _, _, r, _ in seen) and any(m for _, _, _, m in seen)
+    from latok_amd import _lib
+    fn = _lib.load().latok_debug_plan
+    out = np.zeros(12, np.int64)
+    assert fn(0, 8, 0, 0, out.ctypes.data, 12) < 0 and fn(1, 8, 0, 11, out.ctypes.data, 12) < 0
