@@ -15,6 +15,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <mutex>
@@ -145,6 +146,81 @@ static inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 constexpr int64_t kSmallChars = 262144;
 constexpr int64_t kSmallStrings = 16384;
 
+// The input form of a batch as the tile kernel reads it: UTF-32 code points, PEP 393 kind 1 / 2 code units (positions are
+// chars) or UTF-8 bytes (positions are bytes).  Code-point positions of a UTF-8 batch are not a kernel form: compact_common
+// and latok_split_mask_utf8_batch reach them through byte space or the decoder.
+enum class Form { Utf32, Latin1, Ucs2, Utf8 };
+struct Input {
+    const void* p = nullptr;
+    Form form = Form::Utf32;
+    size_t width() const { return form == Form::Utf32 ? 4 : form == Form::Ucs2 ? 2 : 1; }   // bytes per unit
+    bool narrow() const { return form == Form::Latin1 || form == Form::Ucs2; }
+};
+// the public PEP 393 kind (1 / 2 / 4, checked by the caller) or the flow's 0 (UTF-8 bytes)
+static Form form_of_kind(int kind) { return kind == 4 ? Form::Utf32 : kind == 2 ? Form::Ucs2 : kind == 1 ? Form::Latin1 : Form::Utf8; }
+// a CSR batch: units, row offsets [n_str + 1] and the total, both counted in units
+struct Batch {
+    Input in;
+    const int64_t* row = nullptr;
+    int64_t n_str = 0, total = 0;
+};
+
+// The device buffers of one batch in flight and the state of its chained scan: the context's own calls share one set, every
+// flow slot has another.
+struct Workspace {
+    DevBuf summ, seg_agg, fix_count, tile_first;   // tile stage (run_pipeline)
+    DevBuf bits, space, kept, wcnt, wpref, bases, scalar, chain, chain_ctl;   // compaction passes (enqueue_compaction_dev)
+    DevBuf codes, widened;                          // featurize: rule code of every char, PEP 393 units widened to UTF-32
+    // the single-pass scan of k_word_counts_scan keeps its look-back state (chain: per workgroup, chain_ctl: {ticket
+    // counter}) between launches: entries carry an epoch, so the array is cleared only when it is (re)allocated or when the
+    // 18-bit epoch wraps (next_scan_epoch); *_seen = DevBuf::gen of the allocations it was last cleared in
+    unsigned scan_epoch = 0, chain_seen = 0, chain_ctl_seen = 0;
+    bool chain_ready = false;
+    void release() {
+        for (DevBuf* b : {&summ, &seg_agg, &fix_count, &tile_first, &bits, &space, &kept, &wcnt, &wpref, &bases, &scalar, &chain,
+                          &chain_ctl, &codes, &widened})
+            b->release();
+        scan_epoch = chain_seen = chain_ctl_seen = 0;
+        chain_ready = false;
+    }
+};
+struct WsNeed {
+    DevBuf* buf;
+    size_t bytes;   // 0: the batch does not use the buffer
+};
+constexpr int kTileNeeds = 4;   // the first entries of ws_needs: the tile stage
+constexpr int kWsNeeds = 15;
+// The one sizing rule of a workspace: every buffer a batch of `units` positions uses and its byte size.  token spans (spans)
+// add the SPACE and kept planes, featurize (feats) the code bytes, and narrow units read by featurize (widen) a UTF-32 copy.
+static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, bool spans, bool feats, bool widen) {
+    const size_t t = (size_t)std::max<int64_t>((units + latok::kTile - 1) / latok::kTile, 1);
+    const size_t words = (size_t)((units + 63) / 64), c_tiles = (words + 63) / 64;
+    return {{{&w.summ, t * 16},
+             // one Fn64 + Hd64 pair per segment; plan_segments never makes a segment shorter than kWPB tiles (unless it is the
+             // only one), so n_segs <= t / kWPB + 1
+             {&w.seg_agg, (t / latok::kWPB + 2) * (sizeof(latok::Fn64) + sizeof(latok::Hd64))},
+             {&w.fix_count, 8},
+             {&w.tile_first, t * 8 + 8},   // per-tile string index (stage 0)
+             {&w.bits, words * 8 + 8},
+             {&w.space, spans ? words * 8 + 8 : 0},
+             {&w.kept, spans ? words * 8 + 8 : 0},
+             {&w.wcnt, c_tiles * 8 + 8},    // items per tile
+             {&w.wpref, words * 2 + 8},     // items of the tile before each word
+             {&w.bases, c_tiles * 8 + 8},   // rank of each tile's first item
+             {&w.scalar, 64},
+             {&w.chain, (size_t)latok::count_blocks((int64_t)words) * 8 + 64},
+             {&w.chain_ctl, 64},
+             {&w.codes, feats ? (size_t)units + latok::kTile + 256 : 0},   // read (never used) up to a tile behind the last char
+             {&w.widened, widen ? (size_t)units * 4 + 16 : 0}}};
+}
+static int ws_ensure(const WsNeed* needs, int n) {
+    for (int i = 0; i < n; ++i) {
+        const int rc = needs[i].buf->ensure(needs[i].bytes);
+        if (rc) return rc;
+    }
+    return LATOK_OK;
+}
+
 // One context = one device, one stream, one set of tables / workspaces / staging buffers, one rule-table state and one
 // lock.  Calls on the same context are serialised by its lock; calls on different contexts (other devices, or the same
 // device twice) share nothing and run concurrently.  Every entry point works on the calling thread's CURRENT context
@@ -160,10 +236,10 @@ struct Ctx {
     // runtime rule tables (latok_set_rules); off = the built-in default_tokenizer.py tables
     bool rules_on = false;
     lk_rule_tables rules;
-    // pipeline workspace (sized by tiles)
-    DevBuf summ, seg_agg, fix_count;
+    Workspace ws;                  // the workspace of the context's own calls
+    DevBuf& h_cps = ws.widened;    // UTF-32 staging of host-pointer calls: the same memory as the workspace's widened units
     // staging for host-pointer calls and for the offsets API
-    DevBuf h_cps, h_row, h_out, bits, space, kept, wcnt, wpref, counts, bases, scan_tot, scalar, h_aux, tile_first;
+    DevBuf h_row, h_out, counts, scan_tot, h_aux;
     PinBuf pin, pin_tot;   // pin_tot: 64 bytes the scans drop their grand totals into (read after a stream sync, no copy)
     unsigned long long small_seq = 0;   // completion word of the single-launch small-batch path (pin_tot word 2)
     DevBuf done_ctr;                    // workgroup counter of latok::DoneSignal (0 between launches)
@@ -173,25 +249,15 @@ struct Ctx {
     DevBuf u_bytes, u_boff, u_cnt, u_row, u_pref;   // UTF-8 ingest: uploaded bytes / byte offsets, per-string cp counts, cp offsets
     DevBuf u_lead, u_bspace, u_cpbits, u_cpspace;   // code-point results from byte space (cp_masks_via_bytes): lead-byte mask, byte-space
                                                     // SPACE plane, the packed code-point masks
-    DevBuf codes;              // featurize: rule code of every char (SplitParams::codes_out)
     // chunked host pipeline (compact_host_pipelined): copy streams, events and double buffers
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     hipEvent_t ev_in_ready[2] = {nullptr, nullptr}, ev_k_done[2] = {nullptr, nullptr}, ev_d2h_done[2] = {nullptr, nullptr};
     DevBuf pipe_in[2], pipe_row[2], pipe_counts[2], pipe_items[2], pipe_feat[2];
     PinBuf pipe_tot;
-    DevBuf chain, chain_ctl;   // k_word_counts_scan: look-back state per workgroup, {ticket counter}
-    unsigned scan_epoch = 0;
-    bool chain_ready = false;
-    unsigned chain_seen = 0, chain_ctl_seen = 0;   // DevBuf::gen of the allocations the state was last cleared in
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // batch flow (latok_flow_*): up to kFlowSlots device-resident batches in flight, each with its own stream and workspace
     struct FlowSlot {
-        DevBuf summ, seg_agg, fix_count, tile_first;
-        // compaction passes of the slot's batch (latok_flow_split_offsets / _token_spans): what the context's own calls keep
-        // in bits / space / kept / wcnt / wpref / bases / chain / chain_ctl / scalar
-        DevBuf bits, space, kept, wcnt, wpref, bases, chain, chain_ctl, scalar, codes, widened;   // codes / widened: featurize
-        unsigned scan_epoch = 0, chain_seen = 0, chain_ctl_seen = 0;
-        bool chain_ready = false;
+        Workspace ws;
         hipStream_t st = nullptr;
     };
     static constexpr int kFlowSlots = 4;
@@ -237,21 +303,6 @@ struct DeviceGuard {
     std::lock_guard<std::mutex> lk(g.mu);    \
     DeviceGuard device_guard_(g)
 
-static size_t ws_summ_bytes(int64_t n_tiles) { return (size_t)(n_tiles > 0 ? n_tiles : 1) * 16; }
-// one Fn64 + Hd64 pair per segment; plan_segments never makes a segment shorter than kWPB tiles (unless it is the
-// only one), so n_segs <= t / kWPB + 1
-static size_t ws_seg_bytes(int64_t n_tiles) {
-    return ((size_t)(n_tiles > 0 ? n_tiles : 1) / latok::kWPB + 2) * (sizeof(latok::Fn64) + sizeof(latok::Hd64));
-}
-static size_t ws_first_bytes(int64_t n_tiles) { return (size_t)(n_tiles > 0 ? n_tiles : 1) * 8 + 8; }   // per-tile string index (stage 0)
-int ensure_workspace(Ctx& g, int64_t n_tiles) {
-    int rc;
-    if ((rc = g.summ.ensure(ws_summ_bytes(n_tiles)))) return rc;
-    if ((rc = g.seg_agg.ensure(ws_seg_bytes(n_tiles)))) return rc;
-    if ((rc = g.fix_count.ensure(8))) return rc;
-    if ((rc = g.tile_first.ensure(ws_first_bytes(n_tiles)))) return rc;
-    return LATOK_OK;
-}
 
 int need_init(const Ctx& g) {
     if (!g.inited) return fail(LATOK_ERR_NOT_INIT, "latok_init() has not been called (no CPU fallback exists)");
@@ -283,54 +334,64 @@ static bool one_segment_enabled() {
     return on;
 }
 
-// enqueue the pipeline on device-resident data
-int run_pipeline(Ctx& g, const uint32_t* d_cps, const int64_t* d_row, int64_t n_str, int64_t total, uint64_t* d_bits,
-                 uint8_t* d_values, int mode, hipStream_t st, hipEvent_t tiles_begin = nullptr,
-                 hipEvent_t tiles_end = nullptr, const int8_t* bm_a1 = nullptr, const int8_t* bm_a2 = nullptr,
-                 const int* bm_flags = nullptr, uint64_t* d_space = nullptr, int64_t* d_tile_first = nullptr,
-                 const uint8_t* d_u8 = nullptr, int unit_kind = 0, int stages = 7,   // stages: 1 = tile index, 2 = tiles, 4 = resolve
-                 uint8_t* d_codes = nullptr,     // d_codes: also leave the rule code of every char (featurize)
-                 latok::DoneSignal done = latok::DoneSignal{nullptr, 0, nullptr},   // completion word stored by the last launch
-                 Ctx::FlowSlot* slot = nullptr,   // the workspace of a batch-flow slot instead of the context's own
-                 uint64_t* d_lead = nullptr, uint16_t* d_lead_pref = nullptr, int64_t* d_lead_cnt = nullptr) {   // byte space: also leave the
-                 // lead-byte mask, the leads of a tile before each word and the leads per tile (code-point results, mask_utf8_via_bytes)
+// One launch sequence of the tile pipeline on device-resident data.  Every field but the batch and the stream is optional.
+struct Pipe {
+    Batch b;                          // (the block mask has no units: its planes are bm_a1 / bm_a2)
+    int mode = latok::kModeBits;      // kModeBits / kModeValues / kModeBlockMask; the form of a non-UTF-32 batch picks the bitmask variant
+    uint64_t* bits = nullptr;
+    uint8_t* values = nullptr;
+    uint64_t* space = nullptr;        // also the SPACE plane (token spans)
+    uint64_t* lead = nullptr;         // byte space: also the lead-byte mask, the leads of a tile before each word and the leads
+    uint16_t* lead_pref = nullptr;    // per tile (code-point results, cp_masks_via_bytes)
+    int64_t* lead_cnt = nullptr;
+    uint8_t* codes = nullptr;         // also the rule code of every char (featurize)
+    const int8_t* bm_a1 = nullptr;    // kModeBlockMask: the two planes and {any(a1), any(a2)}
+    const int8_t* bm_a2 = nullptr;
+    const int* bm_flags = nullptr;
+    int stages = 7;                   // 1 = tile index, 2 = tiles, 4 = resolve
+    latok::DoneSignal done{nullptr, 0, nullptr};   // completion word stored by the last launch
+    hipEvent_t tiles_begin = nullptr, tiles_end = nullptr;
+    hipStream_t st = nullptr;
+};
+
+// enqueue the pipeline on workspace `w` (the context's own, or a flow slot's: flow_reserve sized it before anything was enqueued)
+int run_pipeline(Ctx& g, Workspace& w, const Pipe& a) {
+    const int64_t n_str = a.b.n_str, total = a.b.total;
     if (total <= 0 || n_str <= 0) return LATOK_OK;
-    if (d_u8) {   // byte space: UTF-8 bytes in, positions are bytes; or (unit_kind 1 / 2) fixed-width code units, positions are chars
+    const Input& in = a.b.in;
+    int mode = a.mode;
+    if (in.form != Form::Utf32) {   // byte space: UTF-8 bytes in, positions are bytes; or PEP 393 code units, positions are chars
         if (mode != latok::kModeBits) return fail(LATOK_ERR_INVALID, "byte-space input supports the bitmask outputs only");
-        if (((uintptr_t)d_u8 & 15) != 0)
-            return fail(LATOK_ERR_INVALID, unit_kind ? "device code-unit pointer must be 16-byte aligned" : "device UTF-8 pointer must be 16-byte aligned");
-        mode = unit_kind == 1 ? latok::kModeLatin1 : (unit_kind == 2 ? latok::kModeUcs2 : latok::kModeBytes);
+        if (((uintptr_t)in.p & 15) != 0)
+            return fail(LATOK_ERR_INVALID, in.narrow() ? "device code-unit pointer must be 16-byte aligned" : "device UTF-8 pointer must be 16-byte aligned");
+        mode = in.form == Form::Latin1 ? latok::kModeLatin1 : (in.form == Form::Ucs2 ? latok::kModeUcs2 : latok::kModeBytes);
     }
     // run-time rule tables (latok_set_rules): the same input form, rules interpreted from the kernel arguments
     if (g.rules_on && mode != latok::kModeBlockMask) mode = latok::mode_with_rules(mode);
     const int64_t n_tiles = (total + latok::kTile - 1) / latok::kTile;
-    DevBuf& w_summ = slot ? slot->summ : g.summ;
-    DevBuf& w_seg = slot ? slot->seg_agg : g.seg_agg;
-    DevBuf& w_fix = slot ? slot->fix_count : g.fix_count;
-    DevBuf& w_first = slot ? slot->tile_first : g.tile_first;
-    int rc = slot ? LATOK_OK : ensure_workspace(g, n_tiles);   // (a flow slot is sized by flow_submit before anything is enqueued)
+    int rc = ws_ensure(ws_needs(w, total, false, false, false).data(), kTileNeeds);
     if (rc) return rc;
     latok::SplitParams P;
-    P.cps = d_cps;
-    P.u8 = d_u8;
-    P.row_off = d_row;
+    P.cps = in.form == Form::Utf32 ? (const uint32_t*)in.p : nullptr;
+    P.u8 = in.form == Form::Utf32 ? nullptr : (const uint8_t*)in.p;
+    P.row_off = a.b.row;
     P.n_str = n_str;
     P.total = total;
     P.n_tiles = n_tiles;
     // (the CU share of a batch of a flow, the segment plan and the kernel variants: latok::plan_launch)
     const int n_cu = g.plan_cus > 0 ? g.plan_cus : g.n_cu;   // latok_debug_set_plan_cus: plan and launch as if the chip had n_cu CUs
-    const bool one_launch_ok = stages == 7 && !d_u8 && !tiles_begin && !tiles_end && one_segment_enabled();
+    const bool one_launch_ok = a.stages == 7 && in.form == Form::Utf32 && !a.tiles_begin && !a.tiles_end && one_segment_enabled();
     latok::LaunchPlan L;
-    latok::plan_launch(n_tiles, n_cu, slot != nullptr, mode, one_launch_ok, &L);
+    latok::plan_launch(n_tiles, n_cu, &w != &g.ws, mode, one_launch_ok, &L);
     P.seg_tiles = L.seg_tiles;
     P.n_segs = L.n_segs;
     const bool one_launch = L.one_launch != 0;
-    if ((size_t)P.n_segs * (sizeof(latok::Fn64) + sizeof(latok::Hd64)) > w_seg.cap || (size_t)n_tiles * 16 > w_summ.cap)
+    if ((size_t)P.n_segs * (sizeof(latok::Fn64) + sizeof(latok::Hd64)) > w.seg_agg.cap || (size_t)n_tiles * 16 > w.summ.cap)
         return fail(LATOK_ERR_INVALID, "internal: workspace too small for %lld segments / %lld tiles", (long long)P.n_segs, (long long)n_tiles);
-    if (d_codes && mode != latok::kModeBits && mode != latok::kModeRules)
+    if (a.codes && mode != latok::kModeBits && mode != latok::kModeRules)
         return fail(LATOK_ERR_INVALID, "internal: code bytes are written by the UTF-32 bitmask modes only");
     // rule codes (split code + NUM) when the rules are interpreted at run time or the code bytes are kept for featurize
-    const uint8_t* tables = (const uint8_t*)((latok::mode_rules(mode) || d_codes) ? g.t1rule.p : g.t1.p);
+    const uint8_t* tables = (const uint8_t*)((latok::mode_rules(mode) || a.codes) ? g.t1rule.p : g.t1.p);
     P.t1 = tables;
     P.t2 = tables + latok::kStage1Pad;
     if (latok::mode_base(mode) == latok::kModeBytes) {   // (byte space classifies through its own table, cut at 6 bits)
@@ -339,40 +400,40 @@ int run_pipeline(Ctx& g, const uint32_t* d_cps, const int64_t* d_row, int64_t n_
     }
     if (latok::mode_rules(mode)) P.rules = g.rules;
     else memset(&P.rules, 0, sizeof(P.rules));
-    P.bits_out = d_bits;
-    P.values_out = d_values;
-    P.space_out = d_space;
-    P.lead_out = d_lead;
-    P.lead_pref_out = d_lead_pref;
-    P.lead_cnt_out = d_lead_cnt;
-    P.codes_out = d_codes;
-    if (!d_tile_first) d_tile_first = (int64_t*)w_first.p;   // the per-tile string index lives in the workspace
-    P.tile_first = d_tile_first;
-    P.summ = (int4*)w_summ.p;
-    P.seg_fn = (latok::Fn64*)w_seg.p;
-    P.seg_hd = (latok::Hd64*)((char*)w_seg.p + (size_t)P.n_segs * sizeof(latok::Fn64));
-    P.fix_count = (int64_t*)w_fix.p;
-    P.bm_a1 = bm_a1;
-    P.bm_a2 = bm_a2;
-    P.bm_flags = bm_flags;
-    P.done = (stages & 4) ? done : latok::DoneSignal{nullptr, 0, nullptr};
+    P.bits_out = a.bits;
+    P.values_out = a.values;
+    P.space_out = a.space;
+    P.lead_out = a.lead;
+    P.lead_pref_out = a.lead_pref;
+    P.lead_cnt_out = a.lead_cnt;
+    P.codes_out = a.codes;
+    P.tile_first = (int64_t*)w.tile_first.p;   // the per-tile string index lives in the workspace
+    P.summ = (int4*)w.summ.p;
+    P.seg_fn = (latok::Fn64*)w.seg_agg.p;
+    P.seg_hd = (latok::Hd64*)((char*)w.seg_agg.p + (size_t)P.n_segs * sizeof(latok::Fn64));
+    P.fix_count = (int64_t*)w.fix_count.p;
+    P.bm_a1 = a.bm_a1;
+    P.bm_a2 = a.bm_a2;
+    P.bm_flags = a.bm_flags;
+    P.done = (a.stages & 4) ? a.done : latok::DoneSignal{nullptr, 0, nullptr};
     // what is launched, for latok_debug_last_plan (a few stores)
     g.last.plan = L;
     g.last.n_tiles = n_tiles;
     g.last.mode = mode;
-    g.last.small = g.pin.d && (d_u8 ? (const void*)d_u8 : (const void*)d_cps) == g.pin.d;
-    g.last.fix_count = (const int64_t*)w_fix.p;
-    g.last.st = st;
+    g.last.small = g.pin.d && in.p == g.pin.d;
+    g.last.fix_count = (const int64_t*)w.fix_count.p;
+    g.last.st = a.st;
     g.last.valid = true;
+    const hipStream_t st = a.st;
     if (one_launch) {
         HIP_TRY(latok::launch_one_segment(P, mode, st));
         return LATOK_OK;
     }
-    if (stages & 1) HIP_TRY(latok::launch_tile_index(P, st));   // (the kernel-timing loop of latok_bench_split_mask launches stage 1 alone)
-    if (tiles_begin) HIP_TRY(hipEventRecord(tiles_begin, st));
-    if (stages & 2) HIP_TRY(latok::launch_split_tiles(P, mode, L, st));
-    if (tiles_end) HIP_TRY(hipEventRecord(tiles_end, st));
-    if (stages & 4) HIP_TRY(latok::launch_resolve_fix(P, mode, L, st));
+    if (a.stages & 1) HIP_TRY(latok::launch_tile_index(P, st));   // (the kernel-timing loop of latok_bench_split_mask launches stage 1 alone)
+    if (a.tiles_begin) HIP_TRY(hipEventRecord(a.tiles_begin, st));
+    if (a.stages & 2) HIP_TRY(latok::launch_split_tiles(P, mode, L, st));
+    if (a.tiles_end) HIP_TRY(hipEventRecord(a.tiles_end, st));
+    if (a.stages & 4) HIP_TRY(latok::launch_resolve_fix(P, mode, L, st));
     return LATOK_OK;
 }
 
@@ -399,60 +460,98 @@ int resolve_total_device(const int64_t* d_row, int64_t n_str, int64_t* total_io,
     return LATOK_OK;
 }
 
-int split_common(Ctx& g, const uint32_t* cps, const int64_t* row_off, int64_t n_str, int64_t total, void* out, int mode,
-                 int flags, void* stream) {
+// the total of a call's batch, once per call: read from device row offsets when the caller passed total < 0 (one blocking
+// 8-byte read), checked against host row offsets
+int resolve_total(const int64_t* row_off, int64_t n_str, int64_t* total_io, bool dev, hipStream_t st) {
+    return dev ? resolve_total_device(row_off, n_str, total_io, st) : check_csr_host(row_off, n_str, total_io);
+}
+
+// Completion word of the pinned small path: the last launch stores done->seq into pin_tot word 2, which the host polls
+// (wait_done) instead of waiting for the stream.  done->word stays NULL when polling is off.
+int arm_done(Ctx& g, hipStream_t st, latok::DoneSignal* done) {
+    *done = latok::DoneSignal{nullptr, 0, nullptr};
+    if (!poll_completion()) return LATOK_OK;
+    int rc;
+    if ((rc = g.pin_tot.ensure(64)) || (rc = g.done_ctr.ensure(64))) return rc;
+    if (g.done_ctr.gen != g.done_ctr_seen) {
+        g.done_ctr_seen = g.done_ctr.gen;
+        HIP_TRY(hipMemsetAsync(g.done_ctr.p, 0, 64, st));
+    }
+    *done = latok::DoneSignal{(unsigned long long*)g.pin_tot.d + 2, ++g.small_seq, (unsigned*)g.done_ctr.p};
+    return LATOK_OK;
+}
+int wait_done(Ctx& g, const latok::DoneSignal& done, hipStream_t st) {
+    if (!(done.word && wait_completion_word((const unsigned long long*)g.pin_tot.h + 2, done.seq))) HIP_TRY(hipStreamSynchronize(st));
+    return LATOK_OK;
+}
+
+// the batch on the device: the caller's device pointers as they are, or a host batch of narrow units / UTF-8 bytes copied
+// into u_bytes / u_boff
+int units_on_device(Ctx& g, const Batch& b, bool dev, hipStream_t st, Batch* d) {
+    *d = b;
+    if (dev) return LATOK_OK;
+    int rc;
+    const size_t bytes = (size_t)b.total * b.in.width();
+    if ((rc = g.u_bytes.ensure(bytes + 16))) return rc;
+    if ((rc = g.u_boff.ensure((size_t)(b.n_str + 1) * 8))) return rc;
+    if (bytes > 0) HIP_TRY(hipMemcpyAsync(g.u_bytes.p, b.in.p, bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(g.u_boff.p, b.row, (size_t)(b.n_str + 1) * 8, hipMemcpyHostToDevice, st));
+    d->in.p = g.u_bytes.p;
+    d->row = (const int64_t*)g.u_boff.p;
+    return LATOK_OK;
+}
+
+// Shared body of the mask entry points: UTF-32 bits or values, PEP 393 units or UTF-8 bytes (bits).  Small UTF-32 host batches
+// run in place on pinned memory; the other host batches are staged on the device.
+int mask_common(Ctx& g, Input in, const int64_t* row_off, int64_t n_str, int64_t total, void* out, int mode, int flags, void* stream) {
     int rc = need_init(g);
     if (rc) return rc;
     StreamTurn turn(g, stream);
     hipStream_t st = turn.st;
-    if (flags & LATOK_DEVICE_PTRS) {
-        if ((rc = resolve_total_device(row_off, n_str, &total, st))) return rc;
-        if (total == 0) return LATOK_OK;
-        if (!cps || !out) return fail(LATOK_ERR_INVALID, "NULL buffer");
-        if (((uintptr_t)cps & 15) != 0) return fail(LATOK_ERR_INVALID, "device cps pointer must be 16-byte aligned");
-        return run_pipeline(g, cps, row_off, n_str, total, mode == latok::kModeBits ? (uint64_t*)out : nullptr,
-                            mode == latok::kModeValues ? (uint8_t*)out : nullptr, mode, st);
-    }
-    if ((rc = check_csr_host(row_off, n_str, &total))) return rc;
+    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0;
+    if ((rc = resolve_total(row_off, n_str, &total, dev, st))) return rc;
     if (total == 0) return LATOK_OK;
-    if (!cps || !out) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (!in.p || !out) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    Pipe a;
+    a.b = Batch{in, row_off, n_str, total};
+    a.mode = mode;
+    a.st = st;
+    auto set_out = [&](void* o) {
+        if (mode == latok::kModeBits) a.bits = (uint64_t*)o;
+        else a.values = (uint8_t*)o;
+    };
+    if (dev) {
+        if (in.form == Form::Utf32 && ((uintptr_t)in.p & 15) != 0) return fail(LATOK_ERR_INVALID, "device cps pointer must be 16-byte aligned");
+        set_out(out);
+        return run_pipeline(g, g.ws, a);
+    }
     const size_t out_bytes = mode == latok::kModeBits ? (size_t)((total + 63) / 64) * 8 : (size_t)total;
-    if (total <= kSmallChars && n_str <= kSmallStrings) {
+    if (in.form == Form::Utf32 && total <= kSmallChars && n_str <= kSmallStrings) {
         // small batch: stage in pinned mapped memory, kernels work on it in place, one synchronisation
-        const size_t o_row = ((size_t)total * 4 + 15) & ~(size_t)15, o_out = o_row + (size_t)(n_str + 1) * 8;
-        if ((rc = g.pin.ensure(o_out + ((out_bytes + 15) & ~(size_t)15)))) return rc;
-        memcpy(g.pin.h, cps, (size_t)total * 4);
+        const size_t o_row = align16((size_t)total * 4), o_out = o_row + (size_t)(n_str + 1) * 8;
+        if ((rc = g.pin.ensure(o_out + align16(out_bytes)))) return rc;
+        memcpy(g.pin.h, in.p, (size_t)total * 4);
         memcpy((char*)g.pin.h + o_row, row_off, (size_t)(n_str + 1) * 8);
-        char* d = (char*)g.pin.d;
-        latok::DoneSignal done{nullptr, 0, nullptr};
-        unsigned long long seq = 0;
-        if (poll_completion()) {   // the last launch stores a completion word (see compact_common)
-            if ((rc = g.pin_tot.ensure(64)) || (rc = g.done_ctr.ensure(64))) return rc;
-            if (g.done_ctr.gen != g.done_ctr_seen) {
-                g.done_ctr_seen = g.done_ctr.gen;
-                HIP_TRY(hipMemsetAsync(g.done_ctr.p, 0, 64, st));
-            }
-            seq = ++g.small_seq;
-            done = latok::DoneSignal{(unsigned long long*)g.pin_tot.d + 2, seq, (unsigned*)g.done_ctr.p};
-        }
-        rc = run_pipeline(g, (const uint32_t*)d, (const int64_t*)(d + o_row), n_str, total,
-                          mode == latok::kModeBits ? (uint64_t*)(d + o_out) : nullptr,
-                          mode == latok::kModeValues ? (uint8_t*)(d + o_out) : nullptr, mode, st, nullptr, nullptr, nullptr, nullptr,
-                          nullptr, nullptr, nullptr, nullptr, 0, 7, nullptr, done);
-        if (rc) return rc;
-        if (!(done.word && wait_completion_word((const unsigned long long*)g.pin_tot.h + 2, seq))) HIP_TRY(hipStreamSynchronize(st));
+        a.b.in.p = g.pin.d;
+        a.b.row = (const int64_t*)((char*)g.pin.d + o_row);
+        set_out((char*)g.pin.d + o_out);
+        if ((rc = arm_done(g, st, &a.done)) || (rc = run_pipeline(g, g.ws, a)) || (rc = wait_done(g, a.done, st))) return rc;
         memcpy(out, (char*)g.pin.h + o_out, out_bytes);
         return LATOK_OK;
     }
-    if ((rc = g.h_cps.ensure((size_t)total * 4))) return rc;
-    if ((rc = g.h_row.ensure((size_t)(n_str + 1) * 8))) return rc;
-    if ((rc = g.h_out.ensure(out_bytes))) return rc;
-    HIP_TRY(hipMemcpyAsync(g.h_cps.p, cps, (size_t)total * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(g.h_row.p, row_off, (size_t)(n_str + 1) * 8, hipMemcpyHostToDevice, st));
-    rc = run_pipeline(g, (const uint32_t*)g.h_cps.p, (const int64_t*)g.h_row.p, n_str, total,
-                      mode == latok::kModeBits ? (uint64_t*)g.h_out.p : nullptr,
-                      mode == latok::kModeValues ? (uint8_t*)g.h_out.p : nullptr, mode, st);
-    if (rc) return rc;
+    if (in.form == Form::Utf32) {
+        if ((rc = g.h_cps.ensure((size_t)total * 4))) return rc;
+        if ((rc = g.h_row.ensure((size_t)(n_str + 1) * 8))) return rc;
+        if ((rc = g.h_out.ensure(out_bytes))) return rc;
+        HIP_TRY(hipMemcpyAsync(g.h_cps.p, in.p, (size_t)total * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(g.h_row.p, row_off, (size_t)(n_str + 1) * 8, hipMemcpyHostToDevice, st));
+        a.b.in.p = g.h_cps.p;
+        a.b.row = (const int64_t*)g.h_row.p;
+    } else if ((rc = g.h_out.ensure(out_bytes)) || (rc = units_on_device(g, a.b, false, st, &a.b))) {
+        return rc;
+    }
+    set_out(g.h_out.p);
+    if ((rc = run_pipeline(g, g.ws, a))) return rc;
     HIP_TRY(hipMemcpyAsync(out, g.h_out.p, out_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return LATOK_OK;
@@ -480,10 +579,10 @@ static void ctx_release(Ctx& g) {   // caller holds g.mu (or owns g exclusively)
     g.rules_on = false;
     g.plan_cus = 0;
     g.last = Ctx::LastPlan{};
-    for (DevBuf* b : {&g.t1, &g.t1rule, &g.tb6, &g.tb6rule, &g.t2code, &g.t2cls, &g.cw, &g.summ, &g.seg_agg, &g.fix_count, &g.h_cps, &g.h_row, &g.h_out,
-                      &g.bits, &g.space, &g.kept, &g.wcnt, &g.wpref, &g.counts, &g.bases, &g.scan_tot, &g.tile_first, &g.u_bytes,
-                      &g.u_boff, &g.u_cnt, &g.u_row, &g.u_pref, &g.u_lead, &g.u_bspace, &g.u_cpbits, &g.u_cpspace, &g.scalar, &g.h_aux, &g.chain, &g.chain_ctl, &g.codes})
+    for (DevBuf* b : {&g.t1, &g.t1rule, &g.tb6, &g.tb6rule, &g.t2code, &g.t2cls, &g.cw, &g.h_row, &g.h_out, &g.counts, &g.scan_tot, &g.u_bytes,
+                      &g.u_boff, &g.u_cnt, &g.u_row, &g.u_pref, &g.u_lead, &g.u_bspace, &g.u_cpbits, &g.u_cpspace, &g.h_aux})
         b->release();
+    g.ws.release();
     for (auto& e : g.ev) {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
@@ -491,9 +590,6 @@ static void ctx_release(Ctx& g) {   // caller holds g.mu (or owns g exclusively)
     if (g.turn_event) (void)hipEventDestroy(g.turn_event);
     g.turn_event = nullptr;
     g.turn_stream_valid = false;
-    g.chain_ready = false;
-    g.chain_seen = g.chain_ctl_seen = 0;
-    g.scan_epoch = 0;
     for (int i = 0; i < 2; ++i) {
         for (DevBuf* b : {&g.pipe_in[i], &g.pipe_row[i], &g.pipe_counts[i], &g.pipe_items[i], &g.pipe_feat[i]}) b->release();
         for (hipEvent_t* e : {&g.ev_in_ready[i], &g.ev_k_done[i], &g.ev_d2h_done[i]}) {
@@ -508,11 +604,7 @@ static void ctx_release(Ctx& g) {   // caller holds g.mu (or owns g exclusively)
             (void)hipStreamDestroy(f.st);
         }
         f.st = nullptr;
-        for (DevBuf* b : {&f.summ, &f.seg_agg, &f.fix_count, &f.tile_first, &f.bits, &f.space, &f.kept, &f.wcnt, &f.wpref, &f.bases,
-                          &f.chain, &f.chain_ctl, &f.scalar, &f.codes, &f.widened})
-            b->release();
-        f.scan_epoch = f.chain_seen = f.chain_ctl_seen = 0;
-        f.chain_ready = false;
+        f.ws.release();
     }
     g.flow_held.clear();
     g.bench_cps_b = nullptr;
@@ -604,7 +696,7 @@ static int ctx_init_body(Ctx& g, int device) {
     }
     if ((rc = g.t2cls.ensure(sizeof(kStage2)))) return rc;
     if ((rc = g.cw.ensure(sizeof(kClassWord)))) return rc;
-    if ((rc = g.scalar.ensure(64))) return rc;
+    if ((rc = g.ws.scalar.ensure(64))) return rc;
     HIP_TRY(hipMemcpy(g.t1.p, t1.data(), t1.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy((char*)g.t1.p + t1.size(), t2code.data(), t2code.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(g.t2cls.p, kStage2, sizeof(kStage2), hipMemcpyHostToDevice));
@@ -700,7 +792,7 @@ int latok_reserve(int64_t max_chars, int64_t max_strings) {
     int rc = need_init(g);
     if (rc) return rc;
     if (max_chars < 0 || max_strings < 0) return fail(LATOK_ERR_INVALID, "negative size");
-    return ensure_workspace(g, (max_chars + latok::kTile - 1) / latok::kTile);
+    return ws_ensure(ws_needs(g.ws, max_chars, false, false, false).data(), kTileNeeds);
 }
 
 // one rule table: row-major int8 [rows x cols] as build_combo_matrix returns it -> per-row column sets
@@ -759,46 +851,30 @@ int latok_rules_active(void) {
 int latok_split_mask_batch(const uint32_t* cps, const int64_t* row_off, int64_t n_str, int64_t total_chars,
                            uint64_t* mask_bits_out, int flags, void* stream) {
     LATOK_ENTER();
-    return split_common(g, cps, row_off, n_str, total_chars, mask_bits_out, latok::kModeBits, flags, stream);
+    return mask_common(g, Input{cps, Form::Utf32}, row_off, n_str, total_chars, mask_bits_out, latok::kModeBits, flags, stream);
 }
 
 int latok_split_values_batch(const uint32_t* cps, const int64_t* row_off, int64_t n_str, int64_t total_chars,
                              uint8_t* values_out, int flags, void* stream) {
     LATOK_ENTER();
-    return split_common(g, cps, row_off, n_str, total_chars, values_out, latok::kModeValues, flags, stream);
+    return mask_common(g, Input{cps, Form::Utf32}, row_off, n_str, total_chars, values_out, latok::kModeValues, flags, stream);
 }
 
-// UTF-8 ingest: decode a CSR batch of UTF-8 strings into the library's device buffers (g.h_cps = packed code points,
-// g.u_row = code-point row offsets).  Inputs are host or device pointers per `dev`.  One blocking 8-byte read.
-// With `bytes_route`: when the batch has no continuation byte at all (pure ASCII, the common case) byte positions ARE
-// code-point positions, so nothing is decoded; *bytes_route = the device pointers for the byte-space tile kernel, whose
-// results are then valid in code-point units as they are.
-struct BytesRoute {
-    const uint8_t* d_u8 = nullptr;
-    const int64_t* d_boff = nullptr;
-};
-static int decode_utf8_to_workspace(Ctx& g, const uint8_t* u8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
-                                    bool dev, hipStream_t st, int64_t* total_cps_out, BytesRoute* bytes_route = nullptr) {
+// UTF-8 ingest: decode a CSR batch of UTF-8 strings (b: total resolved by the caller) into the library's device buffers
+// (g.h_cps = packed code points, g.u_row = code-point row offsets).  Inputs are host or device pointers per `dev`.  One
+// blocking 8-byte read.  With `bytes_route`: when the batch has no continuation byte at all (pure ASCII, the common case)
+// byte positions ARE code-point positions, so nothing is decoded; *bytes_route = the batch on the device for the byte-space
+// tile kernel, whose results are then valid in code-point units as they are (bytes_route->in.p = NULL: decoded).
+static int decode_utf8_to_workspace(Ctx& g, const Batch& b, bool dev, hipStream_t st, int64_t* total_cps_out, Batch* bytes_route = nullptr) {
     int rc;
     *total_cps_out = 0;
-    if (bytes_route) *bytes_route = BytesRoute();
-    const uint8_t* d_u8 = u8;
-    const int64_t* d_boff = byte_off;
-    if (dev) {
-        if ((rc = resolve_total_device(byte_off, n_str, &total_bytes, st))) return rc;
-    } else {
-        if ((rc = check_csr_host(byte_off, n_str, &total_bytes))) return rc;
-    }
+    if (bytes_route) *bytes_route = Batch();
+    const int64_t n_str = b.n_str, total_bytes = b.total;
     if (n_str == 0) return LATOK_OK;
-    if (total_bytes > 0 && !u8) return fail(LATOK_ERR_INVALID, "utf8 buffer is NULL");
-    if (!dev) {
-        if ((rc = g.u_bytes.ensure((size_t)total_bytes + 16))) return rc;
-        if ((rc = g.u_boff.ensure((size_t)(n_str + 1) * 8))) return rc;
-        if (total_bytes > 0) HIP_TRY(hipMemcpyAsync(g.u_bytes.p, u8, (size_t)total_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(g.u_boff.p, byte_off, (size_t)(n_str + 1) * 8, hipMemcpyHostToDevice, st));
-        d_u8 = (const uint8_t*)g.u_bytes.p;
-        d_boff = (const int64_t*)g.u_boff.p;
-    }
+    if (total_bytes > 0 && !b.in.p) return fail(LATOK_ERR_INVALID, "utf8 buffer is NULL");
+    Batch d;
+    if ((rc = units_on_device(g, b, dev, st, &d))) return rc;
+    const uint8_t* d_u8 = (const uint8_t*)d.in.p;
     const int64_t n_blocks = latok::utf8_blocks(total_bytes);
     if ((rc = g.u_cnt.ensure((size_t)n_blocks * 16 + 16))) return rc;               // block counts | block bases
     if ((rc = g.u_row.ensure((size_t)(n_str + 1) * 8))) return rc;
@@ -808,18 +884,17 @@ static int decode_utf8_to_workspace(Ctx& g, const uint8_t* u8, const int64_t* by
     int64_t* d_base = d_cnt + n_blocks;
     HIP_TRY(latok::launch_utf8_block_counts(d_u8, total_bytes, d_cnt, st));
     if ((rc = g.pin_tot.ensure(64))) return rc;
-    HIP_TRY(latok::launch_exclusive_scan(d_cnt, n_blocks, d_base, (int64_t*)g.scalar.p, (int64_t*)g.scan_tot.p, st,
+    HIP_TRY(latok::launch_exclusive_scan(d_cnt, n_blocks, d_base, (int64_t*)g.ws.scalar.p, (int64_t*)g.scan_tot.p, st,
                                          (int64_t*)g.pin_tot.d));
     HIP_TRY(hipStreamSynchronize(st));
     const int64_t total_cps = *(volatile const int64_t*)g.pin_tot.h;
     if (bytes_route && total_cps == total_bytes && ((uintptr_t)d_u8 & 15) == 0) {
-        bytes_route->d_u8 = d_u8;
-        bytes_route->d_boff = d_boff;
+        *bytes_route = d;
         *total_cps_out = total_cps;
         return LATOK_OK;
     }
     if ((rc = g.h_cps.ensure((size_t)total_cps * 4 + 16))) return rc;
-    HIP_TRY(latok::launch_utf8_decode(d_u8, total_bytes, d_boff, n_str, d_base, (uint16_t*)g.u_pref.p, total_cps,
+    HIP_TRY(latok::launch_utf8_decode(d_u8, total_bytes, d.row, n_str, d_base, (uint16_t*)g.u_pref.p, total_cps,
                                       (uint32_t*)g.h_cps.p, (int64_t*)g.u_row.p, st));
     *total_cps_out = total_cps;
     return LATOK_OK;
@@ -853,37 +928,37 @@ static int enqueue_features(Ctx& g, const uint8_t* d_codes, const int64_t* d_row
     return LATOK_OK;
 }
 
-// the single-pass scan of k_word_counts_scan keeps its state between launches: entries carry an epoch, so the array is
-// cleared only when it is (re)allocated or when the 18-bit epoch wraps
-struct ScanState {   // the chained scan's look-back words + epoch of one workspace set (the context's own, or a flow slot's)
-    DevBuf& chain;
-    DevBuf& chain_ctl;
-    unsigned& scan_epoch;
-    unsigned& chain_seen;
-    unsigned& chain_ctl_seen;
-    bool& chain_ready;
-};
-static ScanState scan_state(Ctx& g, Ctx::FlowSlot* slot) {
-    if (slot) return ScanState{slot->chain, slot->chain_ctl, slot->scan_epoch, slot->chain_seen, slot->chain_ctl_seen, slot->chain_ready};
-    return ScanState{g.chain, g.chain_ctl, g.scan_epoch, g.chain_seen, g.chain_ctl_seen, g.chain_ready};
-}
-static int next_scan_epoch(ScanState c, int64_t n_blocks, hipStream_t st, unsigned* epoch_out) {
-    int rc;
-    if ((rc = c.chain.ensure((size_t)n_blocks * 8 + 64))) return rc;
-    if ((rc = c.chain_ctl.ensure(64))) return rc;
-    c.scan_epoch = (c.scan_epoch + 1) & 0x3FFFFu;
+// the next epoch of the chained scan's state in workspace `w` (sized by ws_needs); the state is cleared when it is new
+static int next_scan_epoch(Workspace& w, hipStream_t st, unsigned* epoch_out) {
+    w.scan_epoch = (w.scan_epoch + 1) & 0x3FFFFu;
     // (the state array may have been re-allocated by this call or by an earlier reserve: fresh memory holds anything)
-    if (c.chain.gen != c.chain_seen || c.chain_ctl.gen != c.chain_ctl_seen || c.scan_epoch == 0 || !c.chain_ready) {
-        c.chain_seen = c.chain.gen;
-        c.chain_ctl_seen = c.chain_ctl.gen;
-        HIP_TRY(hipMemsetAsync(c.chain.p, 0, c.chain.cap, st));
-        HIP_TRY(hipMemsetAsync(c.chain_ctl.p, 0, 64, st));
-        c.scan_epoch = 1;
-        c.chain_ready = true;
+    if (w.chain.gen != w.chain_seen || w.chain_ctl.gen != w.chain_ctl_seen || w.scan_epoch == 0 || !w.chain_ready) {
+        w.chain_seen = w.chain.gen;
+        w.chain_ctl_seen = w.chain_ctl.gen;
+        HIP_TRY(hipMemsetAsync(w.chain.p, 0, w.chain.cap, st));
+        HIP_TRY(hipMemsetAsync(w.chain_ctl.p, 0, 64, st));
+        w.scan_epoch = 1;
+        w.chain_ready = true;
     }
-    *epoch_out = c.scan_epoch;
+    *epoch_out = w.scan_epoch;
     return LATOK_OK;
 }
+
+// One device-resident (chunk of a) batch for enqueue_compaction_dev
+struct Compaction {
+    Batch b;
+    bool spans = false, feats = false, o32 = false;   // offsets, token spans, or token spans + feature sums
+    void* counts = nullptr;           // per-string counts, then the records and feature sums: written only if the total fits `cap`
+    void* items = nullptr;
+    int8_t* feat = nullptr;
+    int64_t cap = 0;
+    int64_t* p_tot = nullptr;         // the total and the int32-overflow flag, as the device sees them ...
+    volatile int64_t* h_tot = nullptr;   // ... and the host (the context's pinned pair; NULL: a flow's result words)
+    latok::DoneSignal done{nullptr, 0, nullptr};
+    const uint64_t* pre_bits = nullptr;    // the two bitmasks are already there (code-point masks packed from byte space:
+    const uint64_t* pre_space = nullptr;   // cp_masks_via_bytes): only the string index is launched
+    hipStream_t st = nullptr;
+};
 
 // Device-side core of the compaction entry points, on one device-resident (chunk of a) batch: per-string boundary
 // offsets (spans = false), token spans, or token spans + feature sums (feats).  Launch sequence:
@@ -893,82 +968,61 @@ static int next_scan_epoch(ScanState c, int64_t n_blocks, hipStream_t st, unsign
 //                                             total fits `cap`
 // Nothing is synchronised here: the total and the int32-overflow flag land in the pinned pair p_tot[0..1] (h_tot = the
 // host's view of the same two words) when the stream gets there.
-static int enqueue_compaction_dev(Ctx& g, bool spans, bool feats, bool o32, const uint32_t* d_cps, const uint8_t* d_u8, int unit_kind,
-                                  const int64_t* d_row, int64_t n_str, int64_t total, void* d_counts, void* d_items, int8_t* d_feat,
-                                  int64_t cap, int64_t* p_tot, volatile int64_t* h_tot, hipStream_t st,
-                                  latok::DoneSignal done = latok::DoneSignal{nullptr, 0, nullptr},
-                                  Ctx::FlowSlot* slot = nullptr,     // slot: the workspaces of a batch-flow slot (offsets / spans only)
-                                  const uint64_t* pre_bits = nullptr, const uint64_t* pre_space = nullptr) {   // the two bitmasks are
-                                  // already there (code-point masks packed from byte space: cp_masks_via_bytes): only the string index is launched
+static int enqueue_compaction_dev(Ctx& g, Workspace& w, const Compaction& c) {
     int rc;
-    DevBuf& w_bits = slot ? slot->bits : g.bits;
-    DevBuf& w_space = slot ? slot->space : g.space;
-    DevBuf& w_kept = slot ? slot->kept : g.kept;
-    DevBuf& w_wcnt = slot ? slot->wcnt : g.wcnt;
-    DevBuf& w_bases = slot ? slot->bases : g.bases;
-    DevBuf& w_wpref = slot ? slot->wpref : g.wpref;
-    DevBuf& w_first = slot ? slot->tile_first : g.tile_first;
-    DevBuf& w_scalar = slot ? slot->scalar : g.scalar;
-    DevBuf& w_codes = slot ? slot->codes : g.codes;
-    DevBuf& w_widened = slot ? slot->widened : g.h_cps;
-    const ScanState sc = scan_state(g, slot);
-    if (d_u8 && unit_kind && feats) {
-        // featurize re-reads the code points: widen once, on the device
-        if (((uintptr_t)d_u8 & (size_t)(unit_kind - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned code units");
-        if ((rc = w_widened.ensure((size_t)total * 4 + 16))) return rc;
-        HIP_TRY(latok::launch_widen_units(d_u8, unit_kind, total, (uint32_t*)w_widened.p, st));
-        d_cps = (const uint32_t*)w_widened.p;
-        d_u8 = nullptr;
+    const int64_t total = c.b.total;
+    const hipStream_t st = c.st;
+    const bool widen = c.feats && c.b.in.narrow();   // featurize re-reads the code points: widen once, on the device
+    if (widen && ((uintptr_t)c.b.in.p & (c.b.in.width() - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned code units");
+    if ((rc = ws_ensure(ws_needs(w, total, c.spans, c.feats, widen).data(), kWsNeeds))) return rc;
+    Pipe a;
+    a.b = c.b;
+    a.st = st;
+    if (widen) {
+        HIP_TRY(latok::launch_widen_units(c.b.in.p, (int)c.b.in.width(), total, (uint32_t*)w.widened.p, st));
+        a.b.in = Input{w.widened.p, Form::Utf32};
     }
     const int64_t words = (total + 63) / 64;
-    if ((rc = w_bits.ensure((size_t)words * 8 + 8))) return rc;
-    if (spans && (rc = w_space.ensure((size_t)words * 8 + 8))) return rc;
-    if (spans && (rc = w_kept.ensure((size_t)words * 8 + 8))) return rc;
-    const int64_t c_tiles = (words + 63) / 64;
-    if ((rc = w_wcnt.ensure((size_t)c_tiles * 8 + 8))) return rc;       // items per tile
-    if ((rc = w_bases.ensure((size_t)c_tiles * 8 + 8))) return rc;      // rank of each tile's first item
-    if ((rc = w_wpref.ensure((size_t)words * 2 + 8))) return rc;        // items of the tile before each word
-    if ((rc = w_scalar.ensure(64))) return rc;
     unsigned epoch = 0;
-    if ((rc = next_scan_epoch(sc, latok::count_blocks(words), st, &epoch))) return rc;
-    uint64_t* d_bits = pre_bits ? const_cast<uint64_t*>(pre_bits) : (uint64_t*)w_bits.p;
-    uint64_t* d_space = spans ? (pre_bits ? const_cast<uint64_t*>(pre_space) : (uint64_t*)w_space.p) : nullptr;
-    uint64_t* d_kept = spans ? (uint64_t*)w_kept.p : nullptr;
-    const uint64_t* d_item_mask = spans ? d_kept : d_bits;
-    int64_t* d_rank = (int64_t*)w_bases.p;
-    int64_t* d_tcnt = (int64_t*)w_wcnt.p;
-    uint16_t* d_pref = (uint16_t*)w_wpref.p;
-    if ((rc = w_first.ensure((size_t)((total + latok::kTile - 1) / latok::kTile) * 8 + 8))) return rc;
-    int64_t* d_tile_first = (int64_t*)w_first.p;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    uint64_t* d_bits = c.pre_bits ? const_cast<uint64_t*>(c.pre_bits) : (uint64_t*)w.bits.p;
+    uint64_t* d_space = c.spans ? (c.pre_bits ? const_cast<uint64_t*>(c.pre_space) : (uint64_t*)w.space.p) : nullptr;
+    uint64_t* d_kept = c.spans ? (uint64_t*)w.kept.p : nullptr;
+    const uint64_t* d_item_mask = c.spans ? d_kept : d_bits;
+    int64_t* d_rank = (int64_t*)w.bases.p;
+    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
+    uint16_t* d_pref = (uint16_t*)w.wpref.p;
+    int64_t* d_tile_first = (int64_t*)w.tile_first.p;
     uint8_t* d_codes = nullptr;
-    if (feats) {   // the tile kernel leaves the rule code of every char: 1 B/char for k_features_tiles instead of 4 B/char + tables
-        const size_t code_bytes = (size_t)total + latok::kTile + 256;   // read (never used) up to a tile behind the last char
-        if ((rc = w_codes.ensure(code_bytes))) return rc;
-        d_codes = (uint8_t*)w_codes.p;
+    if (c.feats) {   // the tile kernel leaves the rule code of every char: 1 B/char for k_features_tiles instead of 4 B/char + tables
+        d_codes = (uint8_t*)w.codes.p;
         const size_t tail0 = (size_t)total & ~(size_t)(latok::kTile - 1);
-        HIP_TRY(hipMemsetAsync(d_codes + tail0, 0, code_bytes - tail0, st));
+        HIP_TRY(hipMemsetAsync(d_codes + tail0, 0, (size_t)total + latok::kTile + 256 - tail0, st));
     }
-    if ((rc = run_pipeline(g, d_cps, d_row, n_str, total, d_bits, nullptr, latok::kModeBits, st, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, d_space, d_tile_first, d_u8, unit_kind, pre_bits ? 1 : 7, d_codes,
-                           latok::DoneSignal{nullptr, 0, nullptr}, slot)))
-        return rc;
-    if (h_tot) {   // pinned pair of the context's own calls: cleared by the host
-        h_tot[0] = 0;
-        h_tot[1] = 0;
-    } else {       // a flow's result words live wherever the caller put them: cleared on the stream
-        HIP_TRY(hipMemsetAsync(p_tot, 0, 16, st));
+    a.bits = d_bits;
+    a.space = d_space;
+    a.codes = d_codes;
+    a.stages = c.pre_bits ? 1 : 7;
+    if ((rc = run_pipeline(g, w, a))) return rc;
+    if (c.h_tot) {   // pinned pair of the context's own calls: cleared by the host
+        c.h_tot[0] = 0;
+        c.h_tot[1] = 0;
+    } else {         // a flow's result words live wherever the caller put them: cleared on the stream
+        HIP_TRY(hipMemsetAsync(c.p_tot, 0, 16, st));
     }
-    int64_t* d_total = (int64_t*)w_scalar.p;
-    int* d_err = (int*)(p_tot + 1);
-    HIP_TRY(latok::launch_word_counts_scan(spans, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank,
-                                           (unsigned long long*)sc.chain.p, (unsigned*)sc.chain_ctl.p, epoch, d_total, p_tot, d_err + 1, st));   // (the scan's own flag: the upper half of the pinned word)
-    if (feats) {   // spans and sums come from one kernel
-        HIP_TRY(latok::launch_string_counts(o32, d_item_mask, d_rank, d_pref, d_row, n_str, total, d_total, d_counts, d_err, st));
-        return enqueue_features(g, d_codes, d_row, n_str, total, d_bits, d_space, d_kept, d_rank, d_tcnt, d_pref, d_tile_first, d_items,
-                                d_feat, o32, d_total, cap, st, done);
+    const int64_t* d_row = c.b.row;
+    const int64_t n_str = c.b.n_str;
+    int64_t* d_total = (int64_t*)w.scalar.p;
+    int* d_err = (int*)(c.p_tot + 1);
+    HIP_TRY(latok::launch_word_counts_scan(c.spans, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank,
+                                           (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total, c.p_tot, d_err + 1, st));   // (the scan's own flag: the upper half of the pinned word)
+    if (c.feats) {   // spans and sums come from one kernel
+        HIP_TRY(latok::launch_string_counts(c.o32, d_item_mask, d_rank, d_pref, d_row, n_str, total, d_total, c.counts, d_err, st));
+        return enqueue_features(g, d_codes, d_row, n_str, total, d_bits, d_space, d_kept, d_rank, d_tcnt, d_pref, d_tile_first, c.items,
+                                c.feat, c.o32, d_total, c.cap, st, c.done);
     }
-    HIP_TRY(latok::launch_counts_scatter(spans ? 1 : 0, o32, d_bits, d_space, d_item_mask, d_rank, d_tcnt, d_pref, words, total, d_row,
-                                         n_str, d_tile_first, d_items, d_total, cap, d_counts, d_err, st, done));
+    HIP_TRY(latok::launch_counts_scatter(c.spans ? 1 : 0, c.o32, d_bits, d_space, d_item_mask, d_rank, d_tcnt, d_pref, words, total, d_row,
+                                         n_str, d_tile_first, c.items, d_total, c.cap, c.counts, d_err, st, c.done));
     return LATOK_OK;
 }
 
@@ -1004,34 +1058,13 @@ static int ensure_pipe(Ctx& g) {
     return LATOK_OK;
 }
 
-static int compact_host_pipelined_body(Ctx& g, bool spans, bool feats, bool o32, const void* data, size_t unit_bytes, int unit_kind,
-                                       bool as_u8, const int64_t* row_off, int64_t n_str, int64_t total, void* counts_out,
-                                       void* items_out, int64_t items_cap, int64_t* n_items_out, int8_t* features_out,
-                                       hipStream_t st);
-
-static int compact_host_pipelined(Ctx& g, bool spans, bool feats, bool o32, const void* data, size_t unit_bytes, int unit_kind,
-                                  bool as_u8, const int64_t* row_off, int64_t n_str, int64_t total, void* counts_out,
-                                  void* items_out, int64_t items_cap, int64_t* n_items_out, int8_t* features_out, hipStream_t st) {
-    const int rc = compact_host_pipelined_body(g, spans, feats, o32, data, unit_bytes, unit_kind, as_u8, row_off, n_str, total,
-                                               counts_out, items_out, items_cap, n_items_out, features_out, st);
-    if (rc != LATOK_OK && g.s_h2d) {
-        // a failure in the middle leaves copies in flight that read and write the CALLER's arrays: drain them before the
-        // error is returned (the message of the failure is kept)
-        const std::string msg = g_err;
-        (void)hipStreamSynchronize(g.s_h2d);
-        (void)hipStreamSynchronize(st);
-        (void)hipStreamSynchronize(g.s_d2h);
-        g_err = msg;
-    }
-    return rc;
-}
-
-static int compact_host_pipelined_body(Ctx& g, bool spans, bool feats, bool o32, const void* data, size_t unit_bytes, int unit_kind,
-                                       bool as_u8, const int64_t* row_off, int64_t n_str, int64_t total, void* counts_out,
-                                       void* items_out, int64_t items_cap, int64_t* n_items_out, int8_t* features_out,
-                                       hipStream_t st) {
+static int compact_host_pipelined_body(Ctx& g, bool spans, bool feats, bool o32, const Batch& h, void* counts_out, void* items_out,
+                                       int64_t items_cap, int64_t* n_items_out, int8_t* features_out, hipStream_t st) {
     int rc;
     if ((rc = ensure_pipe(g))) return rc;
+    const int64_t* row_off = h.row;
+    const int64_t n_str = h.n_str;
+    const size_t unit_bytes = h.in.width();
     const size_t elt = o32 ? 4 : 8;
     const size_t item_bytes = (feats ? 4 : (spans ? 2 : 1)) * elt;
     // chunk boundaries (string ids): cut where the cumulative char count passes multiples of the chunk size
@@ -1055,18 +1088,8 @@ static int compact_host_pipelined_body(Ctx& g, bool spans, bool feats, bool o32,
         if (feats && (rc = g.pipe_feat[i].ensure((size_t)max_chars * LATOK_FEATURE_COUNT + 64))) return rc;
     }
     if ((rc = g.pipe_tot.ensure(8 * 16))) return rc;
-    {   // size every workspace for the largest chunk now: growing one later would free it under a chunk that is still running
-        const size_t w = (size_t)((max_chars + 63) / 64), t = (size_t)((max_chars + latok::kTile - 1) / latok::kTile);
-        if ((rc = ensure_workspace(g, (int64_t)t))) return rc;
-        if ((rc = g.bits.ensure(w * 8 + 8))) return rc;
-        if (spans && ((rc = g.space.ensure(w * 8 + 8)) || (rc = g.kept.ensure(w * 8 + 8)))) return rc;
-        if ((rc = g.wcnt.ensure(((w + 63) / 64) * 8 + 8)) || (rc = g.bases.ensure(((w + 63) / 64) * 8 + 8))) return rc;
-        if ((rc = g.wpref.ensure(w * 2 + 8))) return rc;
-        if ((rc = g.tile_first.ensure(t * 8 + 8))) return rc;
-        if (feats && (rc = g.codes.ensure((size_t)max_chars + latok::kTile + 256))) return rc;
-        if (as_u8 && unit_kind && feats && (rc = g.h_cps.ensure((size_t)max_chars * 4 + 16))) return rc;
-        if ((rc = g.chain.ensure((size_t)latok::count_blocks((int64_t)w) * 8 + 64))) return rc;
-    }
+    // size the workspace for the largest chunk now: growing a buffer later would free it under a chunk that is still running
+    if ((rc = ws_ensure(ws_needs(g.ws, max_chars, spans, feats, feats && h.in.narrow()).data(), kWsNeeds))) return rc;
     int64_t running = 0;
     bool overflow = false, too_long = false;
     std::vector<int64_t> n_of(n_chunks, 0);
@@ -1075,7 +1098,7 @@ static int compact_host_pipelined_body(Ctx& g, bool spans, bool feats, bool o32,
         HIP_TRY(hipEventSynchronize(g.ev_k_done[slot]));
         volatile int64_t* h = (volatile int64_t*)g.pipe_tot.h + 2 * (c & 7);
         const int64_t n = h[0];
-        if (h[1] >> 32) { g.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
+        if (h[1] >> 32) { g.ws.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
         if (h[1] & 0xFFFFFFFFll) too_long = true;
         n_of[c] = n;
         const int64_t s0 = cut[c], ns = cut[c + 1] - cut[c];
@@ -1098,7 +1121,7 @@ static int compact_host_pipelined_body(Ctx& g, bool spans, bool feats, bool o32,
         const int64_t s0 = cut[c], ns = cut[c + 1] - s0, c0 = row_off[s0], nc = row_off[cut[c + 1]] - c0;
         if (c >= 2) HIP_TRY(hipStreamWaitEvent(g.s_h2d, g.ev_k_done[slot], 0));
         if (nc > 0)
-            HIP_TRY(hipMemcpyAsync(g.pipe_in[slot].p, (const char*)data + (size_t)c0 * unit_bytes, (size_t)nc * unit_bytes,
+            HIP_TRY(hipMemcpyAsync(g.pipe_in[slot].p, (const char*)h.in.p + (size_t)c0 * unit_bytes, (size_t)nc * unit_bytes,
                                    hipMemcpyHostToDevice, g.s_h2d));
         HIP_TRY(hipMemcpyAsync(g.pipe_row[slot].p, row_off + s0, (size_t)(ns + 1) * 8, hipMemcpyHostToDevice, g.s_h2d));
         HIP_TRY(hipEventRecord(g.ev_in_ready[slot], g.s_h2d));
@@ -1112,16 +1135,24 @@ static int compact_host_pipelined_body(Ctx& g, bool spans, bool feats, bool o32,
         HIP_TRY(hipStreamWaitEvent(st, g.ev_in_ready[slot], 0));
         if (c >= 2) HIP_TRY(hipStreamWaitEvent(st, g.ev_d2h_done[slot], 0));
         HIP_TRY(latok::launch_rebase_rows((int64_t*)g.pipe_row[slot].p, ns + 1, c0, st));
-        volatile int64_t* h = (volatile int64_t*)g.pipe_tot.h + 2 * (c & 7);
-        int64_t* p = (int64_t*)g.pipe_tot.d + 2 * (c & 7);
+        volatile int64_t* h_tot = (volatile int64_t*)g.pipe_tot.h + 2 * (c & 7);
         if (nc > 0) {
-            rc = enqueue_compaction_dev(g, spans, feats, o32, as_u8 ? nullptr : (const uint32_t*)g.pipe_in[slot].p,
-                                        as_u8 ? (const uint8_t*)g.pipe_in[slot].p : nullptr, unit_kind, (const int64_t*)g.pipe_row[slot].p,
-                                        ns, nc, g.pipe_counts[slot].p, g.pipe_items[slot].p, (int8_t*)g.pipe_feat[slot].p, nc, p, h, st);
-            if (rc) return rc;
+            Compaction k;
+            k.b = Batch{Input{g.pipe_in[slot].p, h.in.form}, (const int64_t*)g.pipe_row[slot].p, ns, nc};
+            k.spans = spans;
+            k.feats = feats;
+            k.o32 = o32;
+            k.counts = g.pipe_counts[slot].p;
+            k.items = g.pipe_items[slot].p;
+            k.feat = (int8_t*)g.pipe_feat[slot].p;
+            k.cap = nc;
+            k.p_tot = (int64_t*)g.pipe_tot.d + 2 * (c & 7);
+            k.h_tot = h_tot;
+            k.st = st;
+            if ((rc = enqueue_compaction_dev(g, g.ws, k))) return rc;
         } else {   // only empty strings in this chunk
-            h[0] = 0;
-            h[1] = 0;
+            h_tot[0] = 0;
+            h_tot[1] = 0;
             HIP_TRY(hipMemsetAsync(g.pipe_counts[slot].p, 0, (size_t)ns * elt, st));
         }
         HIP_TRY(hipEventRecord(g.ev_k_done[slot], st));
@@ -1140,14 +1171,27 @@ static int compact_host_pipelined_body(Ctx& g, bool spans, bool feats, bool o32,
     return LATOK_OK;
 }
 
-// Shared body of the compaction entry points: argument checks, staging of host-pointer batches, one synchronisation.
-// Small UTF-8 host batches (one string per call is the usual C caller): decoded by the host with the device decoder's rule
-// -- one code point per lead byte, as many continuation bytes as the lead announces (utf8_decode.h) -- into UTF-32, so
-// that the call takes the pinned small-batch path of the code-point form; byte-space results are mapped back through the
-// byte position of every char.  Only when every string is structurally well-formed (each lead followed by exactly its
-// continuation bytes inside the string, no stray continuation byte): the two device paths define what malformed input
-// means, and they keep doing so.  cps / cp_row / bytepos: code points, code-point row offsets, byte position of every
-// char (+ one entry for the end).
+// h: a host batch of at least kPipeMinChars units, checked
+static int compact_host_pipelined(Ctx& g, bool spans, bool feats, bool o32, const Batch& h, void* counts_out, void* items_out,
+                                  int64_t items_cap, int64_t* n_items_out, int8_t* features_out, hipStream_t st) {
+    const int rc = compact_host_pipelined_body(g, spans, feats, o32, h, counts_out, items_out, items_cap, n_items_out, features_out, st);
+    if (rc != LATOK_OK && g.s_h2d) {
+        // a failure in the middle leaves copies in flight that read and write the CALLER's arrays: drain them before the
+        // error is returned (the message of the failure is kept)
+        const std::string msg = g_err;
+        (void)hipStreamSynchronize(g.s_h2d);
+        (void)hipStreamSynchronize(st);
+        (void)hipStreamSynchronize(g.s_d2h);
+        g_err = msg;
+    }
+    return rc;
+}
+
+// Host decode of a small UTF-8 batch (compact_common) with the device decoder's rule -- one code point per lead byte, as
+// many continuation bytes as the lead announces (utf8_decode.h) -- into UTF-32.  Only when every string is structurally
+// well-formed (each lead followed by exactly its continuation bytes inside the string, no stray continuation byte): the two
+// device paths define what malformed input means, and they keep doing so.  cps / cp_row / bytepos: code points, code-point
+// row offsets, byte position of every char (+ one entry for the end).
 static bool host_decode_small(const uint8_t* u8, const int64_t* boff, int64_t n_str, std::vector<uint32_t>& cps,
                               std::vector<int64_t>& cp_row, std::vector<int64_t>& bytepos) {
     const int64_t total = boff[n_str];
@@ -1182,48 +1226,61 @@ static bool host_decode_small(const uint8_t* u8, const int64_t* boff, int64_t n_
     return true;
 }
 
-static int cp_masks_via_bytes(Ctx& g, const uint8_t* d_u8, const int64_t* d_boff, int64_t n_str, int64_t total_bytes, uint64_t* d_out,
-                              uint64_t* d_out_space, int64_t cap_words, int64_t* d_cp_row, hipStream_t st, int64_t* total_cps_out,
-                              int* fallback_out);
-static int utf8_on_device(Ctx& g, const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, bool dev, hipStream_t st,
-                          const uint8_t** d_u8, const int64_t** d_boff);
-static int compact_common(Ctx& g, bool spans, const uint32_t* cps, const int64_t* row_off, int64_t n_str, int64_t total, void* counts_out,
-                          void* items_out, int64_t items_cap, int64_t* n_items_out, int flags, void* stream, int8_t* features_out,
-                          const uint8_t* utf8, bool byte_space, int unit_kind);
-
-// A small UTF-8 host batch through the UTF-32 small-batch path (host_decode_small); *taken = false: not this route (too
-// large, or malformed), nothing was done.  Byte space: a char position becomes the byte position of that char, relative
-// to its string.
-static int compact_small_utf8_host(Ctx& g, bool spans, const uint8_t* utf8, bool byte_space, const int64_t* byte_off, int64_t n_str,
-                                   int64_t total_bytes, void* counts_out, void* items_out, int64_t items_cap, int64_t* n_items_out,
-                                   int flags, void* stream, int8_t* features_out, bool* taken) {
-    *taken = false;
-    int64_t tb = total_bytes;
-    if (check_csr_host(byte_off, n_str, &tb) != LATOK_OK || tb <= 0 || tb > kSmallChars) return LATOK_OK;
-    if (!host_decode_small(utf8, byte_off, n_str, g.hd_cps, g.hd_row, g.hd_pos)) return LATOK_OK;
-    *taken = true;
-    const int rc = compact_common(g, spans, g.hd_cps.data(), g.hd_row.data(), n_str, (int64_t)g.hd_cps.size(), counts_out, items_out,
-                                  items_cap, n_items_out, flags, stream, features_out, nullptr, false, 0);
-    if (rc != LATOK_OK || !byte_space || !items_out) return rc;
-    const bool o32 = (flags & LATOK_OUT_INT32) != 0;
-    const int64_t per = spans ? 2 : 1;
-    int64_t k = 0;
-    for (int64_t s = 0; s < n_str; ++s) {
-        const int64_t n = o32 ? (int64_t)((const int32_t*)counts_out)[s] : ((const int64_t*)counts_out)[s];
-        const int64_t c0 = g.hd_row[(size_t)s], b0 = byte_off[s];
-        for (int64_t j = 0; j < n * per; ++j, ++k) {
-            if (o32) { int32_t* v = (int32_t*)items_out + k; *v = (int32_t)(g.hd_pos[(size_t)(c0 + *v)] - b0); }
-            else { int64_t* v = (int64_t*)items_out + k; *v = g.hd_pos[(size_t)(c0 + *v)] - b0; }
-        }
-    }
+// Code-point results of a UTF-8 batch WITHOUT a UTF-32 copy of it (the reference reads code points, latok.c:53-55,79; a UTF-8
+// caller has bytes): the byte-space tile kernel on the bytes, which also leaves the lead-byte mask and the lead counts per word
+// and per tile; one scan of the tile counts (k_scan_chained); then k_lead_compress packs the boundary bits at lead bytes (and,
+// for token spans, the SPACE plane) and turns the byte offsets into code-point offsets.  HBM traffic: the bytes once + ~5 bits per
+// byte of masks and ranks, against 1 + 4 + 4 bytes per char through the staged decoder.  Everything is on the device; nothing
+// waits for the host between the launches; the code-point total, the capacity check and the malformed-input flag are read
+// after one synchronisation.  *fallback_out = 1: the batch holds a continuation byte that the byte-space model and the
+// decoder treat differently (malformed UTF-8): the caller takes the decoder.
+//   d: the bytes on the device; d_out / d_out_space: where the packed masks go (cap_words words each; d_out_space NULL:
+//   boundaries only), d_cp_row [n_str + 1]
+static int cp_masks_via_bytes(Ctx& g, const Batch& d, uint64_t* d_out, uint64_t* d_out_space, int64_t cap_words, int64_t* d_cp_row,
+                              hipStream_t st, int64_t* total_cps_out, int* fallback_out) {
+    int rc;
+    *fallback_out = 0;
+    Workspace& w = g.ws;
+    const int64_t total_bytes = d.total, words_b = (total_bytes + 63) / 64, c_tiles = (words_b + 63) / 64;
+    if ((rc = ws_ensure(ws_needs(w, total_bytes, false, false, false).data(), kWsNeeds)) || (rc = g.u_lead.ensure((size_t)words_b * 8 + 8)) ||
+        (d_out_space && (rc = g.u_bspace.ensure((size_t)words_b * 8 + 8))) || (rc = g.pin_tot.ensure(64)))
+        return rc;
+    unsigned epoch = 0;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    uint64_t* d_bmask = (uint64_t*)w.bits.p;
+    uint64_t* d_lead = (uint64_t*)g.u_lead.p;
+    uint64_t* d_bspace = d_out_space ? (uint64_t*)g.u_bspace.p : nullptr;
+    Pipe a;
+    a.b = d;
+    a.bits = d_bmask;
+    a.space = d_bspace;
+    a.lead = d_lead;
+    a.lead_pref = (uint16_t*)w.wpref.p;
+    a.lead_cnt = (int64_t*)w.wcnt.p;
+    a.st = st;
+    if ((rc = run_pipeline(g, w, a))) return rc;
+    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+    int64_t* p_tot = (int64_t*)g.pin_tot.d;
+    h_tot[0] = 0;
+    h_tot[1] = 0;
+    h_tot[3] = 0;
+    int* d_err = (int*)(p_tot + 1);
+    HIP_TRY(latok::launch_tile_scan((const int64_t*)w.wcnt.p, c_tiles, (int64_t*)w.bases.p, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p,
+                                    epoch, (int64_t*)w.scalar.p, p_tot, d_err + 1, st));
+    HIP_TRY(latok::launch_lead_compress(d_bmask, d_bspace, d_lead, (const int64_t*)w.bases.p, (const int64_t*)w.wcnt.p,
+                                        (const uint16_t*)w.wpref.p, words_b, total_bytes, d.row, d.n_str, (const int64_t*)w.scalar.p, d_out,
+                                        d_out_space, cap_words, d_cp_row, (int*)(p_tot + 3), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_tot[1] != 0) { w.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the chained scan did not complete (flag %lld)", (long long)h_tot[1]); }
+    if (h_tot[3] != 0) { *fallback_out = 1; return LATOK_OK; }
+    *total_cps_out = h_tot[0];
     return LATOK_OK;
 }
 
-static int compact_common(Ctx& g, bool spans, const uint32_t* cps, const int64_t* row_off, int64_t n_str, int64_t total,
-                          void* counts_out, void* items_out, int64_t items_cap, int64_t* n_items_out, int flags,
-                          void* stream, int8_t* features_out = nullptr, const uint8_t* utf8 = nullptr,
-                          bool byte_space = false, int unit_kind = 0) {
-    const bool feats = features_out != nullptr;
+// Shared body of the compaction entry points: argument checks, staging of host-pointer batches, one synchronisation.
+// cp_units: a UTF-8 batch (b.row = byte offsets, b.total = bytes) whose results are in code-point units.
+static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units, void* counts_out, void* items_out, int8_t* features_out,
+                          int64_t items_cap, int64_t* n_items_out, int flags, void* stream) {
     const bool o32 = (flags & LATOK_OUT_INT32) != 0;
     int rc = need_init(g);
     if (rc) return rc;
@@ -1231,111 +1288,82 @@ static int compact_common(Ctx& g, bool spans, const uint32_t* cps, const int64_t
     *n_items_out = 0;
     if (items_cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
     const bool dev = (flags & LATOK_DEVICE_PTRS) != 0;
+    const int64_t* row_off = b.row;
+    const int64_t n_str = b.n_str;
     if (o32 && !dev && row_off && n_str > 0) {   // before anything is staged (device-resident row offsets: the kernel checks)
         for (int64_t s = 0; s < n_str; ++s)
             if (row_off[s + 1] - row_off[s] > 0x7FFFFFFFll)
                 return fail(LATOK_ERR_INVALID, "string %lld is too long for LATOK_OUT_INT32; use the 64-bit form", (long long)s);
     }
-    if (!dev && utf8 && unit_kind == 0 && row_off && n_str > 0 && n_str <= kSmallStrings && counts_out) {
-        bool taken = false;
-        rc = compact_small_utf8_host(g, spans, utf8, byte_space, row_off, n_str, total, counts_out, items_out, items_cap, n_items_out,
-                                     flags, stream, features_out, &taken);
-        if (taken) return rc;
+    if (!dev && (rc = check_csr_host(row_off, n_str, &b.total))) return rc;   // (device row offsets: below, on the call's stream)
+    // Small well-formed UTF-8 host batches (one string per call is the usual C caller) are decoded by the host
+    // (host_decode_small) and take the pinned small-batch path of the code-point form; byte-space results are mapped back:
+    // a char position becomes the byte position of that char, relative to its string.
+    if (!dev && b.in.form == Form::Utf8 && b.in.p && counts_out && n_str <= kSmallStrings && b.total > 0 && b.total <= kSmallChars &&
+        host_decode_small((const uint8_t*)b.in.p, row_off, n_str, g.hd_cps, g.hd_row, g.hd_pos)) {
+        const Batch cps{Input{g.hd_cps.data(), Form::Utf32}, g.hd_row.data(), n_str, (int64_t)g.hd_cps.size()};
+        rc = compact_common(g, spans, feats, cps, false, counts_out, items_out, features_out, items_cap, n_items_out, flags, stream);
+        if (rc != LATOK_OK || cp_units || !items_out) return rc;
+        const int64_t per = spans ? 2 : 1;
+        int64_t k = 0;
+        for (int64_t s = 0; s < n_str; ++s) {
+            const int64_t n = o32 ? (int64_t)((const int32_t*)counts_out)[s] : ((const int64_t*)counts_out)[s];
+            const int64_t c0 = g.hd_row[(size_t)s], b0 = row_off[s];
+            for (int64_t j = 0; j < n * per; ++j, ++k) {
+                if (o32) { int32_t* v = (int32_t*)items_out + k; *v = (int32_t)(g.hd_pos[(size_t)(c0 + *v)] - b0); }
+                else { int64_t* v = (int64_t*)items_out + k; *v = g.hd_pos[(size_t)(c0 + *v)] - b0; }
+            }
+        }
+        return LATOK_OK;
     }
     StreamTurn turn(g, stream);
     hipStream_t st = turn.st;
+    if (dev) {
+        if ((rc = resolve_total_device(row_off, n_str, &b.total, st))) return rc;
+        if (b.in.form == Form::Utf32 && b.total > 0 && ((uintptr_t)b.in.p & 15) != 0)
+            return fail(LATOK_ERR_INVALID, "device cps pointer must be 16-byte aligned");
+    }
+    if (n_str == 0) return LATOK_OK;
+    if (!counts_out) return fail(LATOK_ERR_INVALID, "counts_out is NULL");
+    if (b.total > 0 && !b.in.p) return fail(LATOK_ERR_INVALID, "NULL buffer");
     const size_t elt = o32 ? 4 : 8;                                   // width of counts and of every record field
     const size_t item_bytes = (feats ? 4 : (spans ? 2 : 1)) * elt;
-    const uint32_t* d_cps = cps;
-    const int64_t* d_row = row_off;
-    const uint8_t* d_u8 = nullptr;   // byte space: the tile kernel reads the UTF-8 bytes itself, results are byte offsets
+    if (!dev && !cp_units && b.total >= kPipeMinChars)
+        return compact_host_pipelined(g, spans, feats, o32, b, counts_out, items_out, items_cap, n_items_out, features_out, st);
+    Batch d = b;   // the batch as the kernels read it
     const uint64_t *pre_bits = nullptr, *pre_space = nullptr;   // code-point masks packed from byte space (UTF-8 in code-point units)
-    const size_t unit_bytes = (utf8 && byte_space) ? (unit_kind ? (size_t)unit_kind : 1) : 4;
-    if (!dev && !(utf8 && !byte_space)) {
-        // host pointers, fixed-width units or UTF-8 in byte space: checked here; large batches take the chunked pipeline
-        if ((rc = check_csr_host(row_off, n_str, &total))) return rc;
-        if (n_str == 0) return LATOK_OK;
-        if (!counts_out) return fail(LATOK_ERR_INVALID, "counts_out is NULL");
-        if (total >= kPipeMinChars)
-            return compact_host_pipelined(g, spans, feats, o32, utf8 ? (const void*)utf8 : (const void*)cps, unit_bytes, unit_kind,
-                                          utf8 != nullptr, row_off, n_str, total, counts_out, items_out, items_cap, n_items_out,
-                                          features_out, st);
-    }
-    // Small host batches of narrow units (the C-extension caller of INTEGRATION.md section C hands over ONE str per call in
-    // its PEP 393 kind) are widened to UTF-32 by the host straight into the pinned area and take the small-batch path below:
-    // positions are chars either way, so the results are the same, and the call costs one launch instead of staged copies
-    // (kind 1, one 105-char string: 110 -> 17 us).
-    bool widen = false;
-    if (!dev && utf8 && byte_space && n_str > 0 && total > 0 && total <= kSmallChars && n_str <= kSmallStrings) {
-        widen = unit_kind == 1 || unit_kind == 2;   // (small UTF-8 batches were decoded by the host above)
-    }
-    if (widen) {
-        d_cps = nullptr;   // (set below, with the pinned area)
-    } else if (utf8 && byte_space) {
-        // UTF-8 in byte space, or (unit_kind 1 / 2) PEP 393 code units: `total` positions of unit_bytes each
-        if (dev) {
-            if ((rc = resolve_total_device(row_off, n_str, &total, st))) return rc;
-            d_u8 = utf8;
-        } else if (n_str > 0) {
-            if ((rc = g.u_bytes.ensure((size_t)total * unit_bytes + 16))) return rc;
-            if ((rc = g.u_boff.ensure((size_t)(n_str + 1) * 8))) return rc;
-            if (total > 0) HIP_TRY(hipMemcpyAsync(g.u_bytes.p, utf8, (size_t)total * unit_bytes, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(g.u_boff.p, row_off, (size_t)(n_str + 1) * 8, hipMemcpyHostToDevice, st));
-            d_u8 = (const uint8_t*)g.u_bytes.p;
-            d_row = (const int64_t*)g.u_boff.p;
-        }
-        d_cps = nullptr;
-    } else if (utf8) {   // row_off = byte offsets, total = bytes; results are in code-point units
-        int64_t tb = total;
-        if (dev) {
-            if ((rc = resolve_total_device(row_off, n_str, &tb, st))) return rc;
-        } else if ((rc = check_csr_host(row_off, n_str, &tb))) {
-            return rc;
-        }
-        bool done_via_bytes = false;
-        if (!feats && n_str > 0 && tb > kSmallChars && (!dev || ((uintptr_t)utf8 & 15) == 0)) {
+    if (cp_units) {
+        bool via_bytes = false;
+        if (!feats && b.total > kSmallChars && (!dev || ((uintptr_t)b.in.p & 15) == 0)) {
             // large batches: the byte-space kernel + the masks packed at the lead bytes (no UTF-32 copy of the batch); the compaction
             // then runs on the code-point masks
-            const uint8_t* b8;
-            const int64_t* boff;
-            if ((rc = utf8_on_device(g, utf8, row_off, n_str, tb, dev, st, &b8, &boff))) return rc;
-            const int64_t words_b = (tb + 63) / 64;
+            Batch bytes;
+            if ((rc = units_on_device(g, b, dev, st, &bytes))) return rc;
+            const int64_t words_b = (b.total + 63) / 64;
             if ((rc = g.u_cpbits.ensure((size_t)words_b * 8 + 8)) || (spans && (rc = g.u_cpspace.ensure((size_t)words_b * 8 + 8))) ||
                 (rc = g.u_row.ensure((size_t)(n_str + 1) * 8)))
                 return rc;
             int fallback = 0;
             int64_t total_cps = 0;
-            if ((rc = cp_masks_via_bytes(g, b8, boff, n_str, tb, (uint64_t*)g.u_cpbits.p, spans ? (uint64_t*)g.u_cpspace.p : nullptr, words_b,
+            if ((rc = cp_masks_via_bytes(g, bytes, (uint64_t*)g.u_cpbits.p, spans ? (uint64_t*)g.u_cpspace.p : nullptr, words_b,
                                          (int64_t*)g.u_row.p, st, &total_cps, &fallback)))
                 return rc;
             if (!fallback) {
                 pre_bits = (const uint64_t*)g.u_cpbits.p;
                 pre_space = spans ? (const uint64_t*)g.u_cpspace.p : nullptr;
-                d_cps = nullptr;
-                d_row = (const int64_t*)g.u_row.p;
-                total = total_cps;
-                done_via_bytes = true;
+                d = Batch{Input{}, (const int64_t*)g.u_row.p, n_str, total_cps};
+                via_bytes = true;
             }
         }
-        if (!done_via_bytes) {   // small batches, featurize (re-reads code points), malformed input: decode on the device first
-            BytesRoute br;
-            if ((rc = decode_utf8_to_workspace(g, utf8, row_off, n_str, total, dev, st, &total, feats ? nullptr : &br))) return rc;
-            if (br.d_u8) {   // no multi-byte char in the batch: byte space == code-point space, skip the decode
-                d_u8 = br.d_u8;
-                d_row = br.d_boff;
-                d_cps = nullptr;
-            } else {
-                d_cps = (const uint32_t*)g.h_cps.p;
-                d_row = (const int64_t*)g.u_row.p;
-            }
+        if (!via_bytes) {   // small batches, featurize (re-reads code points), malformed input: decode on the device first
+            Batch bytes;
+            int64_t total_cps = 0;
+            if ((rc = decode_utf8_to_workspace(g, b, dev, st, &total_cps, feats ? nullptr : &bytes))) return rc;
+            // (no multi-byte char in the batch: byte space == code-point space, the decode was skipped)
+            d = bytes.in.p ? bytes : Batch{Input{g.h_cps.p, Form::Utf32}, (const int64_t*)g.u_row.p, n_str, total_cps};
         }
-    } else if (dev) {
-        if ((rc = resolve_total_device(row_off, n_str, &total, st))) return rc;
-        if (total > 0 && ((uintptr_t)cps & 15) != 0)
-            return fail(LATOK_ERR_INVALID, "device cps pointer must be 16-byte aligned");
     }
-    if (n_str == 0) return LATOK_OK;
-    if (!counts_out) return fail(LATOK_ERR_INVALID, "counts_out is NULL");
+    const int64_t total = d.total;
     if (total == 0) {   // only empty strings: all counts are 0
         if (dev) HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)n_str * elt, st));
         else memset(counts_out, 0, (size_t)n_str * elt);
@@ -1343,65 +1371,74 @@ static int compact_common(Ctx& g, bool spans, const uint32_t* cps, const int64_t
     }
     // small host batch: inputs and every output live in pinned mapped memory; nothing is copied by the runtime and the
     // call synchronises once (a string of ~100 chars: ~110 us of blocking copies otherwise)
-    const bool small = !dev && (!utf8 || widen) && total <= kSmallChars && n_str <= kSmallStrings;
+    const bool small = !dev && (b.in.form == Form::Utf32 || b.in.narrow()) && total <= kSmallChars && n_str <= kSmallStrings;
     size_t po_row = 0, po_counts = 0, po_items = 0, po_feat = 0;
     if (small) {
-        po_row = ((size_t)total * 4 + 15) & ~(size_t)15;
-        po_counts = po_row + (((size_t)(n_str + 1) * 8 + 15) & ~(size_t)15);
-        po_items = po_counts + (((size_t)n_str * elt + 15) & ~(size_t)15);
+        po_row = align16((size_t)total * 4);
+        po_counts = po_row + align16((size_t)(n_str + 1) * 8);
+        po_items = po_counts + align16((size_t)n_str * elt);
         po_feat = po_items + (size_t)total * item_bytes;      // at most one item per char
         if ((rc = g.pin.ensure(po_feat + (feats ? (size_t)total * LATOK_FEATURE_COUNT : 0) + 64))) return rc;
-        if (!widen) {
-            memcpy(g.pin.h, cps, (size_t)total * 4);
-        } else if (unit_kind == 2) {
-            uint32_t* w = (uint32_t*)g.pin.h;
-            for (int64_t i = 0; i < total; ++i) { uint16_t u; memcpy(&u, utf8 + 2 * i, 2); w[i] = u; }
+        // Narrow units (the C-extension caller of INTEGRATION.md section C hands over ONE str per call in its PEP 393 kind)
+        // are widened to UTF-32 by the host straight into the pinned area: positions are chars either way, so the results
+        // are the same, and the call costs one launch instead of staged copies (kind 1, one 105-char string: 110 -> 17 us).
+        uint32_t* w = (uint32_t*)g.pin.h;
+        if (b.in.form == Form::Utf32) {
+            memcpy(w, b.in.p, (size_t)total * 4);
+        } else if (b.in.form == Form::Ucs2) {
+            for (int64_t i = 0; i < total; ++i) { uint16_t u; memcpy(&u, (const char*)b.in.p + 2 * i, 2); w[i] = u; }
         } else {
-            uint32_t* w = (uint32_t*)g.pin.h;
-            for (int64_t i = 0; i < total; ++i) w[i] = utf8[i];
+            for (int64_t i = 0; i < total; ++i) w[i] = ((const uint8_t*)b.in.p)[i];
         }
         memcpy((char*)g.pin.h + po_row, row_off, (size_t)(n_str + 1) * 8);
-        d_cps = (const uint32_t*)g.pin.d;
-        d_row = (const int64_t*)((char*)g.pin.d + po_row);
-    } else if (!dev && !utf8) {
+        d.in = Input{g.pin.d, Form::Utf32};
+        d.row = (const int64_t*)((char*)g.pin.d + po_row);
+    } else if (!dev && b.in.form == Form::Utf32) {
         if ((rc = g.h_cps.ensure((size_t)total * 4 + 16))) return rc;
         if ((rc = g.h_row.ensure((size_t)(n_str + 1) * 8))) return rc;
-        HIP_TRY(hipMemcpyAsync(g.h_cps.p, cps, (size_t)total * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(g.h_cps.p, b.in.p, (size_t)total * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(g.h_row.p, row_off, (size_t)(n_str + 1) * 8, hipMemcpyHostToDevice, st));
-        d_cps = (const uint32_t*)g.h_cps.p;
-        d_row = (const int64_t*)g.h_row.p;
+        d.in.p = g.h_cps.p;
+        d.row = (const int64_t*)g.h_row.p;
+    } else if (!dev && !cp_units && (rc = units_on_device(g, b, false, st, &d))) {   // narrow units, UTF-8 in byte space
+        return rc;
     }
     if ((rc = g.pin_tot.ensure(64))) return rc;
     volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
     int64_t* p_tot = (int64_t*)g.pin_tot.d;
     // where the records go: the caller's device buffers, the pinned area, or (host pointers, mid-size batch) device staging
     // sized for the worst case of one item per char
-    void* d_counts = counts_out;
-    void* d_items = items_out;
-    int8_t* d_feat = features_out;
-    int64_t cap = items_out ? items_cap : 0;
+    Compaction k;
+    k.b = d;
+    k.spans = spans;
+    k.feats = feats;
+    k.o32 = o32;
+    k.counts = counts_out;
+    k.items = items_out;
+    k.feat = features_out;
+    k.cap = items_out ? items_cap : 0;
     if (small) {
-        d_counts = (char*)g.pin.d + po_counts;
-        d_items = (char*)g.pin.d + po_items;
-        d_feat = (int8_t*)((char*)g.pin.d + po_feat);
-        cap = total;
+        k.counts = (char*)g.pin.d + po_counts;
+        k.items = (char*)g.pin.d + po_items;
+        k.feat = (int8_t*)((char*)g.pin.d + po_feat);
+        k.cap = total;
     } else if (!dev) {
         if ((rc = g.counts.ensure((size_t)n_str * 8))) return rc;
         if ((rc = g.h_out.ensure((size_t)total * item_bytes))) return rc;
         if (feats && (rc = g.h_aux.ensure((size_t)total * LATOK_FEATURE_COUNT))) return rc;
-        d_counts = g.counts.p;
-        d_items = g.h_out.p;
-        d_feat = (int8_t*)g.h_aux.p;
-        cap = total;
+        k.counts = g.counts.p;
+        k.items = g.h_out.p;
+        k.feat = (int8_t*)g.h_aux.p;
+        k.cap = total;
     }
-    bool polled = false;
+    latok::DoneSignal done{nullptr, 0, nullptr};
     if (small && total <= latok::kTile) {
         // at most one tile (tokenize(text) / featurize(text): one string per call): one single-wave launch does everything
         // and stores a completion word the host polls
         latok::SplitParams P;
         memset(&P, 0, sizeof(P));
-        P.cps = d_cps;
-        P.row_off = d_row;
+        P.cps = (const uint32_t*)d.in.p;
+        P.row_off = d.row;
         P.n_str = n_str;
         P.total = total;
         P.n_tiles = 1;
@@ -1411,35 +1448,27 @@ static int compact_common(Ctx& g, bool spans, const uint32_t* cps, const int64_t
         if (g.rules_on) P.rules = g.rules;
         h_tot[0] = 0;
         h_tot[1] = 0;
-        const unsigned long long seq = ++g.small_seq;
-        unsigned long long* d_done = poll_completion() ? (unsigned long long*)(p_tot + 2) : nullptr;
-        HIP_TRY(latok::launch_small_batch(P, g.rules_on, feats ? 2 : (spans ? 1 : 0), o32, d_counts, d_items, d_feat, p_tot, d_done, seq, st));
-        polled = d_done && wait_completion_word((const unsigned long long*)(h_tot + 2), seq);
+        done = latok::DoneSignal{poll_completion() ? (unsigned long long*)(p_tot + 2) : nullptr, ++g.small_seq, nullptr};
+        HIP_TRY(latok::launch_small_batch(P, g.rules_on, feats ? 2 : (spans ? 1 : 0), o32, k.counts, k.items, k.feat, p_tot, done.word,
+                                          done.seq, st));
     } else {
         // several tiles in pinned memory: the last kernel's workgroups count themselves in and the last one stores the
         // completion word (latok::DoneSignal)
-        latok::DoneSignal done{nullptr, 0, nullptr};
-        unsigned long long seq = 0;
-        if (small && poll_completion()) {
-            if ((rc = g.done_ctr.ensure(64))) return rc;
-            if (g.done_ctr.gen != g.done_ctr_seen) {
-                g.done_ctr_seen = g.done_ctr.gen;
-                HIP_TRY(hipMemsetAsync(g.done_ctr.p, 0, 64, st));
-            }
-            seq = ++g.small_seq;
-            done = latok::DoneSignal{(unsigned long long*)(p_tot + 2), seq, (unsigned*)g.done_ctr.p};
-        }
-        if ((rc = enqueue_compaction_dev(g, spans, feats, o32, d_cps, d_u8, unit_kind, d_row, n_str, total, d_counts, d_items, d_feat,
-                                         cap, p_tot, h_tot, st, done, nullptr, pre_bits, pre_space)))
-            return rc;
-        polled = done.word && wait_completion_word((const unsigned long long*)(h_tot + 2), seq);
+        if (small && (rc = arm_done(g, st, &k.done))) return rc;
+        k.p_tot = p_tot;
+        k.h_tot = h_tot;
+        k.pre_bits = pre_bits;
+        k.pre_space = pre_space;
+        k.st = st;
+        if ((rc = enqueue_compaction_dev(g, g.ws, k))) return rc;
+        done = k.done;
     }
     // the one synchronisation: total and flag are in pinned memory now (a polled small batch has seen its completion
     // word, which the kernel stores after everything else; the launch itself retires on the stream a moment later)
-    if (!polled) HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = wait_done(g, done, st))) return rc;
     const int64_t n_items = h_tot[0];
     *n_items_out = n_items;
-    if (h_tot[1] >> 32) { g.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
+    if (h_tot[1] >> 32) { g.ws.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
     if (h_tot[1] & 0xFFFFFFFFll) return fail(LATOK_ERR_INVALID, "a string is too long for LATOK_OUT_INT32; use the 64-bit form");
     const bool fits = n_items <= items_cap && (n_items == 0 || items_out);
     if (small) {
@@ -1465,15 +1494,16 @@ int latok_split_offsets_batch(const uint32_t* cps, const int64_t* row_off, int64
                               int64_t* counts_out, int64_t* offsets_out, int64_t offsets_cap, int64_t* n_offsets_out,
                               int flags, void* stream) {
     LATOK_ENTER();
-    return compact_common(g, false, cps, row_off, n_str, total, counts_out, offsets_out, offsets_cap, n_offsets_out, flags,
-                          stream);
+    return compact_common(g, false, false, Batch{Input{cps, Form::Utf32}, row_off, n_str, total}, false, counts_out, offsets_out, nullptr,
+                          offsets_cap, n_offsets_out, flags, stream);
 }
 
 int latok_token_spans_batch(const uint32_t* cps, const int64_t* row_off, int64_t n_str, int64_t total,
                             int64_t* counts_out, int64_t* spans_out, int64_t spans_cap, int64_t* n_tokens_out, int flags,
                             void* stream) {
     LATOK_ENTER();
-    return compact_common(g, true, cps, row_off, n_str, total, counts_out, spans_out, spans_cap, n_tokens_out, flags, stream);
+    return compact_common(g, true, false, Batch{Input{cps, Form::Utf32}, row_off, n_str, total}, false, counts_out, spans_out, nullptr,
+                          spans_cap, n_tokens_out, flags, stream);
 }
 
 int latok_utf8_decode_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
@@ -1487,7 +1517,8 @@ int latok_utf8_decode_batch(const uint8_t* utf8, const int64_t* byte_off, int64_
     hipStream_t st = turn.st;
     const bool dev = (flags & LATOK_DEVICE_PTRS) != 0;
     int64_t total_cps = 0;
-    if ((rc = decode_utf8_to_workspace(g, utf8, byte_off, n_str, total_bytes, dev, st, &total_cps))) return rc;
+    if ((rc = resolve_total(byte_off, n_str, &total_bytes, dev, st))) return rc;
+    if ((rc = decode_utf8_to_workspace(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total_bytes}, dev, st, &total_cps))) return rc;
     *total_cps_out = total_cps;
     if (n_str == 0) return LATOK_OK;
     if (total_cps > cps_cap) return fail(LATOK_ERR_INVALID, "cps_cap too small: need %lld", (long long)total_cps);
@@ -1499,92 +1530,30 @@ int latok_utf8_decode_batch(const uint8_t* utf8, const int64_t* byte_off, int64_
     return LATOK_OK;
 }
 
-// Code-point results of a UTF-8 batch WITHOUT a UTF-32 copy of it (the reference reads code points, latok.c:53-55,79; a UTF-8
-// caller has bytes): the byte-space tile kernel on the bytes, which also leaves the lead-byte mask and the lead counts per word
-// and per tile; one scan of the tile counts (k_scan_chained); then k_lead_compress packs the boundary bits at lead bytes (and,
-// for token spans, the SPACE plane) and turns the byte offsets into code-point offsets.  HBM traffic: the bytes once + ~5 bits per
-// byte of masks and ranks, against 1 + 4 + 4 bytes per char through the staged decoder.  Everything is on the device; nothing
-// waits for the host between the launches; the code-point total, the capacity check and the malformed-input flag are read
-// after one synchronisation.  *fallback_out = 1: the batch holds a continuation byte that the byte-space model and the
-// decoder treat differently (malformed UTF-8): the caller takes the decoder.
-//   d_out / d_out_space: where the packed masks go (cap_words words each; d_out_space NULL: boundaries only), d_cp_row [n_str + 1]
-static int cp_masks_via_bytes(Ctx& g, const uint8_t* d_u8, const int64_t* d_boff, int64_t n_str, int64_t total_bytes, uint64_t* d_out,
-                              uint64_t* d_out_space, int64_t cap_words, int64_t* d_cp_row, hipStream_t st, int64_t* total_cps_out,
-                              int* fallback_out) {
+// b: the caller's UTF-8 batch, total resolved
+static int mask_utf8_via_bytes(Ctx& g, const Batch& b, bool dev, uint64_t* mask_bits_out, int64_t mask_cap_words, int64_t* cp_row_off_out,
+                               int64_t* total_cps_out, hipStream_t st, int* fallback_out) {
     int rc;
-    *fallback_out = 0;
-    const int64_t words_b = (total_bytes + 63) / 64, c_tiles = (words_b + 63) / 64;
-    if ((rc = g.bits.ensure((size_t)words_b * 8 + 8)) || (rc = g.u_lead.ensure((size_t)words_b * 8 + 8)) ||
-        (d_out_space && (rc = g.u_bspace.ensure((size_t)words_b * 8 + 8))) ||
-        (rc = g.wcnt.ensure((size_t)c_tiles * 8 + 8)) || (rc = g.bases.ensure((size_t)c_tiles * 8 + 8)) ||
-        (rc = g.wpref.ensure((size_t)words_b * 2 + 8)) || (rc = g.scalar.ensure(64)) || (rc = g.pin_tot.ensure(64)))
-        return rc;
-    unsigned epoch = 0;
-    if ((rc = next_scan_epoch(scan_state(g, nullptr), latok::count_blocks(words_b), st, &epoch))) return rc;
-    uint64_t* d_bmask = (uint64_t*)g.bits.p;
-    uint64_t* d_lead = (uint64_t*)g.u_lead.p;
-    uint64_t* d_bspace = d_out_space ? (uint64_t*)g.u_bspace.p : nullptr;
-    if ((rc = run_pipeline(g, nullptr, d_boff, n_str, total_bytes, d_bmask, nullptr, latok::kModeBits, st, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, d_bspace, nullptr, d_u8, 0, 7, nullptr, latok::DoneSignal{nullptr, 0, nullptr}, nullptr, d_lead,
-                           (uint16_t*)g.wpref.p, (int64_t*)g.wcnt.p)))
-        return rc;
-    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
-    int64_t* p_tot = (int64_t*)g.pin_tot.d;
-    h_tot[0] = 0;
-    h_tot[1] = 0;
-    h_tot[3] = 0;
-    int* d_err = (int*)(p_tot + 1);
-    HIP_TRY(latok::launch_tile_scan((const int64_t*)g.wcnt.p, c_tiles, (int64_t*)g.bases.p, (unsigned long long*)g.chain.p, (unsigned*)g.chain_ctl.p,
-                                    epoch, (int64_t*)g.scalar.p, p_tot, d_err + 1, st));
-    HIP_TRY(latok::launch_lead_compress(d_bmask, d_bspace, d_lead, (const int64_t*)g.bases.p, (const int64_t*)g.wcnt.p,
-                                        (const uint16_t*)g.wpref.p, words_b, total_bytes, d_boff, n_str, (const int64_t*)g.scalar.p, d_out,
-                                        d_out_space, cap_words, d_cp_row, (int*)(p_tot + 3), st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (h_tot[1] != 0) { g.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the chained scan did not complete (flag %lld)", (long long)h_tot[1]); }
-    if (h_tot[3] != 0) { *fallback_out = 1; return LATOK_OK; }
-    *total_cps_out = h_tot[0];
-    return LATOK_OK;
-}
-// bytes + byte offsets on the device, from the caller's pointers (uploaded when they are host pointers)
-static int utf8_on_device(Ctx& g, const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, bool dev, hipStream_t st,
-                          const uint8_t** d_u8, const int64_t** d_boff) {
-    int rc;
-    *d_u8 = utf8;
-    *d_boff = byte_off;
-    if (dev) return LATOK_OK;
-    if ((rc = g.u_bytes.ensure((size_t)total_bytes + 16))) return rc;
-    if ((rc = g.u_boff.ensure((size_t)(n_str + 1) * 8))) return rc;
-    HIP_TRY(hipMemcpyAsync(g.u_bytes.p, utf8, (size_t)total_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(g.u_boff.p, byte_off, (size_t)(n_str + 1) * 8, hipMemcpyHostToDevice, st));
-    *d_u8 = (const uint8_t*)g.u_bytes.p;
-    *d_boff = (const int64_t*)g.u_boff.p;
-    return LATOK_OK;
-}
-static int mask_utf8_via_bytes(Ctx& g, const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, bool dev,
-                               uint64_t* mask_bits_out, int64_t mask_cap_words, int64_t* cp_row_off_out, int64_t* total_cps_out,
-                               hipStream_t st, int* fallback_out) {
-    int rc;
-    const uint8_t* d_u8;
-    const int64_t* d_boff;
-    if ((rc = utf8_on_device(g, utf8, byte_off, n_str, total_bytes, dev, st, &d_u8, &d_boff))) return rc;
-    const int64_t words_b = (total_bytes + 63) / 64;
+    Batch d;
+    if ((rc = units_on_device(g, b, dev, st, &d))) return rc;
+    const int64_t words_b = (b.total + 63) / 64;
     const int64_t out_words = mask_cap_words < words_b ? mask_cap_words : words_b;   // (a batch has at most one char per byte)
     uint64_t* d_out = mask_bits_out;
     int64_t* d_cp_row = cp_row_off_out;
     if (!dev) {
-        if ((rc = g.h_out.ensure((size_t)out_words * 8 + 8)) || (rc = g.u_row.ensure((size_t)(n_str + 1) * 8))) return rc;
+        if ((rc = g.h_out.ensure((size_t)out_words * 8 + 8)) || (rc = g.u_row.ensure((size_t)(b.n_str + 1) * 8))) return rc;
         d_out = (uint64_t*)g.h_out.p;
         d_cp_row = (int64_t*)g.u_row.p;
     }
     int64_t total_cps = 0;
-    if ((rc = cp_masks_via_bytes(g, d_u8, d_boff, n_str, total_bytes, d_out, nullptr, out_words, d_cp_row, st, &total_cps, fallback_out))) return rc;
+    if ((rc = cp_masks_via_bytes(g, d, d_out, nullptr, out_words, d_cp_row, st, &total_cps, fallback_out))) return rc;
     if (*fallback_out) return LATOK_OK;
     *total_cps_out = total_cps;
     const int64_t words = (total_cps + 63) / 64;
     if (words > mask_cap_words) return fail(LATOK_ERR_INVALID, "mask_cap_words too small: need %lld", (long long)words);
     if (!dev) {
         if (words > 0) HIP_TRY(hipMemcpyAsync(mask_bits_out, d_out, (size_t)words * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(cp_row_off_out, d_cp_row, (size_t)(n_str + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(cp_row_off_out, d_cp_row, (size_t)(b.n_str + 1) * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     return LATOK_OK;
@@ -1600,47 +1569,36 @@ int latok_split_mask_utf8_batch(const uint8_t* utf8, const int64_t* byte_off, in
     StreamTurn turn(g, stream);
     hipStream_t st = turn.st;
     const bool dev = (flags & LATOK_DEVICE_PTRS) != 0;
+    if ((rc = resolve_total(byte_off, n_str, &total_bytes, dev, st))) return rc;
+    const Batch b{Input{utf8, Form::Utf8}, byte_off, n_str, total_bytes};
     // large batches: byte space + compaction of the mask (no UTF-32 copy)
-    {
-        int64_t tb = total_bytes;
-        if (dev) {
-            if ((rc = resolve_total_device(byte_off, n_str, &tb, st))) return rc;
-        } else if ((rc = check_csr_host(byte_off, n_str, &tb))) {
-            return rc;
-        }
-        if (n_str > 0 && tb > kSmallChars && utf8 && cp_row_off_out && mask_bits_out && mask_cap_words >= 0 &&
-            (!dev || ((uintptr_t)utf8 & 15) == 0)) {
-            int fallback = 0;
-            rc = mask_utf8_via_bytes(g, utf8, byte_off, n_str, tb, dev, mask_bits_out, mask_cap_words, cp_row_off_out, total_cps_out, st,
-                                     &fallback);
-            if (rc || !fallback) return rc;
-        }
+    if (n_str > 0 && total_bytes > kSmallChars && utf8 && cp_row_off_out && mask_bits_out && mask_cap_words >= 0 &&
+        (!dev || ((uintptr_t)utf8 & 15) == 0)) {
+        int fallback = 0;
+        rc = mask_utf8_via_bytes(g, b, dev, mask_bits_out, mask_cap_words, cp_row_off_out, total_cps_out, st, &fallback);
+        if (rc || !fallback) return rc;
     }
     int64_t total = 0;
-    BytesRoute br;
-    if ((rc = decode_utf8_to_workspace(g, utf8, byte_off, n_str, total_bytes, dev, st, &total, &br))) return rc;
+    Batch bytes;
+    if ((rc = decode_utf8_to_workspace(g, b, dev, st, &total, &bytes))) return rc;
     *total_cps_out = total;
     if (n_str == 0) return LATOK_OK;
     const int64_t words = (total + 63) / 64;
     if (words > mask_cap_words) return fail(LATOK_ERR_INVALID, "mask_cap_words too small: need %lld", (long long)words);
     if (!cp_row_off_out || (words > 0 && !mask_bits_out)) return fail(LATOK_ERR_INVALID, "NULL output buffer");
-    uint64_t* d_bits = mask_bits_out;
+    Pipe a;
+    // no multi-byte char: the byte-space kernel on the bytes, code-point offsets = byte offsets
+    a.b = bytes.in.p ? bytes : Batch{Input{g.h_cps.p, Form::Utf32}, (const int64_t*)g.u_row.p, n_str, total};
+    a.bits = mask_bits_out;
+    a.st = st;
     if (!dev) {
         if ((rc = g.h_out.ensure((size_t)words * 8 + 8))) return rc;
-        d_bits = (uint64_t*)g.h_out.p;
+        a.bits = (uint64_t*)g.h_out.p;
     }
-    if (br.d_u8) {   // no multi-byte char: the byte-space kernel on the bytes, code-point offsets = byte offsets
-        if ((rc = run_pipeline(g, nullptr, br.d_boff, n_str, total, d_bits, nullptr, latok::kModeBits, st, nullptr, nullptr,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, br.d_u8)))
-            return rc;
-    } else if ((rc = run_pipeline(g, (const uint32_t*)g.h_cps.p, (const int64_t*)g.u_row.p, n_str, total, d_bits, nullptr,
-                                  latok::kModeBits, st))) {
-        return rc;
-    }
+    if ((rc = run_pipeline(g, g.ws, a))) return rc;
     const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (!dev && words > 0) HIP_TRY(hipMemcpyAsync(mask_bits_out, d_bits, (size_t)words * 8, kind, st));
-    HIP_TRY(hipMemcpyAsync(cp_row_off_out, br.d_u8 ? (const void*)br.d_boff : (const void*)g.u_row.p, (size_t)(n_str + 1) * 8,
-                           kind, st));
+    if (!dev && words > 0) HIP_TRY(hipMemcpyAsync(mask_bits_out, a.bits, (size_t)words * 8, kind, st));
+    HIP_TRY(hipMemcpyAsync(cp_row_off_out, a.b.row, (size_t)(n_str + 1) * 8, kind, st));
     HIP_TRY(hipStreamSynchronize(st));
     return LATOK_OK;
 }
@@ -1649,69 +1607,39 @@ int latok_split_offsets_utf8_batch(const uint8_t* utf8, const int64_t* byte_off,
                                    int64_t* counts_out, int64_t* offsets_out, int64_t offsets_cap,
                                    int64_t* n_offsets_out, int flags, void* stream) {
     LATOK_ENTER();
-    static const uint8_t empty = 0;
-    return compact_common(g, false, nullptr, byte_off, n_str, total_bytes, counts_out, offsets_out, offsets_cap,
-                          n_offsets_out, flags, stream, nullptr, utf8 ? utf8 : &empty);
+    return compact_common(g, false, false, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total_bytes}, true, counts_out, offsets_out,
+                          nullptr, offsets_cap, n_offsets_out, flags, stream);
 }
 
 int latok_token_spans_utf8_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
                                  int64_t* counts_out, int64_t* spans_out, int64_t spans_cap, int64_t* n_tokens_out,
                                  int flags, void* stream) {
     LATOK_ENTER();
-    static const uint8_t empty = 0;
-    return compact_common(g, true, nullptr, byte_off, n_str, total_bytes, counts_out, spans_out, spans_cap, n_tokens_out,
-                          flags, stream, nullptr, utf8 ? utf8 : &empty);
+    return compact_common(g, true, false, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total_bytes}, true, counts_out, spans_out,
+                          nullptr, spans_cap, n_tokens_out, flags, stream);
 }
 
 /* byte-space UTF-8 entry points: the tile kernel reads the bytes (1 B/char for ASCII), all positions are byte offsets */
 int latok_split_mask_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
                                       uint64_t* mask_bits_out, int flags, void* stream) {
     LATOK_ENTER();
-    int rc = need_init(g);
-    if (rc) return rc;
-    StreamTurn turn(g, stream);
-    hipStream_t st = turn.st;
-    if (flags & LATOK_DEVICE_PTRS) {
-        if ((rc = resolve_total_device(byte_off, n_str, &total_bytes, st))) return rc;
-        if (total_bytes == 0) return LATOK_OK;
-        if (!utf8 || !mask_bits_out) return fail(LATOK_ERR_INVALID, "NULL buffer");
-        return run_pipeline(g, nullptr, byte_off, n_str, total_bytes, mask_bits_out, nullptr, latok::kModeBits, st, nullptr, nullptr,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, utf8);
-    }
-    if ((rc = check_csr_host(byte_off, n_str, &total_bytes))) return rc;
-    if (total_bytes == 0) return LATOK_OK;
-    if (!utf8 || !mask_bits_out) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    const size_t out_bytes = (size_t)((total_bytes + 63) / 64) * 8;
-    if ((rc = g.u_bytes.ensure((size_t)total_bytes + 16))) return rc;
-    if ((rc = g.u_boff.ensure((size_t)(n_str + 1) * 8))) return rc;
-    if ((rc = g.h_out.ensure(out_bytes))) return rc;
-    HIP_TRY(hipMemcpyAsync(g.u_bytes.p, utf8, (size_t)total_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(g.u_boff.p, byte_off, (size_t)(n_str + 1) * 8, hipMemcpyHostToDevice, st));
-    if ((rc = run_pipeline(g, nullptr, (const int64_t*)g.u_boff.p, n_str, total_bytes, (uint64_t*)g.h_out.p, nullptr,
-                           latok::kModeBits, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           (const uint8_t*)g.u_bytes.p)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(mask_bits_out, g.h_out.p, out_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return LATOK_OK;
+    return mask_common(g, Input{utf8, Form::Utf8}, byte_off, n_str, total_bytes, mask_bits_out, latok::kModeBits, flags, stream);
 }
 
 int latok_split_offsets_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
                                          int64_t* counts_out, int64_t* offsets_out, int64_t offsets_cap,
                                          int64_t* n_offsets_out, int flags, void* stream) {
     LATOK_ENTER();
-    static const uint8_t empty = 0;
-    return compact_common(g, false, nullptr, byte_off, n_str, total_bytes, counts_out, offsets_out, offsets_cap,
-                          n_offsets_out, flags, stream, nullptr, utf8 ? utf8 : &empty, true);
+    return compact_common(g, false, false, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total_bytes}, false, counts_out, offsets_out,
+                          nullptr, offsets_cap, n_offsets_out, flags, stream);
 }
 
 int latok_token_spans_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
                                        int64_t* counts_out, int64_t* spans_out, int64_t spans_cap, int64_t* n_tokens_out,
                                        int flags, void* stream) {
     LATOK_ENTER();
-    static const uint8_t empty = 0;
-    return compact_common(g, true, nullptr, byte_off, n_str, total_bytes, counts_out, spans_out, spans_cap, n_tokens_out,
-                          flags, stream, nullptr, utf8 ? utf8 : &empty, true);
+    return compact_common(g, true, false, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total_bytes}, false, counts_out, spans_out,
+                          nullptr, spans_cap, n_tokens_out, flags, stream);
 }
 
 /* PEP 393 buffers (the reference's own input, latok.c:53-55,79): fixed-width code units of 1, 2 or 4 bytes */
@@ -1723,88 +1651,40 @@ static int check_kind(int kind) {
 int latok_split_mask_kind_batch(const void* units, int kind, const int64_t* row_off, int64_t n_str, int64_t total_chars,
                                 uint64_t* mask_bits_out, int flags, void* stream) {
     LATOK_ENTER();
-    int rc = check_kind(kind);
+    const int rc = check_kind(kind);
     if (rc) return rc;
-    if (kind == 4) return split_common(g, (const uint32_t*)units, row_off, n_str, total_chars, mask_bits_out, latok::kModeBits, flags, stream);
-    if ((rc = need_init(g))) return rc;
-    StreamTurn turn(g, stream);
-    hipStream_t st = turn.st;
-    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0;
-    int64_t total = total_chars;
-    if (dev) {
-        if ((rc = resolve_total_device(row_off, n_str, &total, st))) return rc;
-    } else if ((rc = check_csr_host(row_off, n_str, &total))) {
-        return rc;
-    }
-    if (total == 0) return LATOK_OK;
-    if (!units || !mask_bits_out) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    const uint8_t* d_units = (const uint8_t*)units;
-    const int64_t* d_row = row_off;
-    uint64_t* d_bits = mask_bits_out;
-    const size_t out_bytes = (size_t)((total + 63) / 64) * 8;
-    if (!dev) {
-        if ((rc = g.u_bytes.ensure((size_t)total * kind + 16))) return rc;
-        if ((rc = g.u_boff.ensure((size_t)(n_str + 1) * 8))) return rc;
-        if ((rc = g.h_out.ensure(out_bytes))) return rc;
-        HIP_TRY(hipMemcpyAsync(g.u_bytes.p, units, (size_t)total * kind, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(g.u_boff.p, row_off, (size_t)(n_str + 1) * 8, hipMemcpyHostToDevice, st));
-        d_units = (const uint8_t*)g.u_bytes.p;
-        d_row = (const int64_t*)g.u_boff.p;
-        d_bits = (uint64_t*)g.h_out.p;
-    }
-    rc = run_pipeline(g, nullptr, d_row, n_str, total, d_bits, nullptr, latok::kModeBits, st, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, nullptr, d_units, kind);
-    if (rc) return rc;
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(mask_bits_out, d_bits, out_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return LATOK_OK;
+    return mask_common(g, Input{units, form_of_kind(kind)}, row_off, n_str, total_chars, mask_bits_out, latok::kModeBits, flags, stream);
 }
 
 int latok_split_offsets_kind_batch(const void* units, int kind, const int64_t* row_off, int64_t n_str, int64_t total_chars,
                                    int64_t* counts_out, int64_t* offsets_out, int64_t offsets_cap, int64_t* n_offsets_out,
                                    int flags, void* stream) {
     LATOK_ENTER();
-    int rc = check_kind(kind);
+    const int rc = check_kind(kind);
     if (rc) return rc;
-    if (kind == 4)
-        return compact_common(g, false, (const uint32_t*)units, row_off, n_str, total_chars, counts_out, offsets_out, offsets_cap,
-                              n_offsets_out, flags, stream);
-    static const uint8_t empty = 0;
-    return compact_common(g, false, nullptr, row_off, n_str, total_chars, counts_out, offsets_out, offsets_cap, n_offsets_out,
-                          flags, stream, nullptr, units ? (const uint8_t*)units : &empty, true, kind);
+    return compact_common(g, false, false, Batch{Input{units, form_of_kind(kind)}, row_off, n_str, total_chars}, false, counts_out,
+                          offsets_out, nullptr, offsets_cap, n_offsets_out, flags, stream);
 }
 
 int latok_token_spans_kind_batch(const void* units, int kind, const int64_t* row_off, int64_t n_str, int64_t total_chars,
                                  int64_t* counts_out, int64_t* spans_out, int64_t spans_cap, int64_t* n_tokens_out,
                                  int flags, void* stream) {
     LATOK_ENTER();
-    int rc = check_kind(kind);
+    const int rc = check_kind(kind);
     if (rc) return rc;
-    if (kind == 4)
-        return compact_common(g, true, (const uint32_t*)units, row_off, n_str, total_chars, counts_out, spans_out, spans_cap,
-                              n_tokens_out, flags, stream);
-    static const uint8_t empty = 0;
-    return compact_common(g, true, nullptr, row_off, n_str, total_chars, counts_out, spans_out, spans_cap, n_tokens_out, flags,
-                          stream, nullptr, units ? (const uint8_t*)units : &empty, true, kind);
+    return compact_common(g, true, false, Batch{Input{units, form_of_kind(kind)}, row_off, n_str, total_chars}, false, counts_out,
+                          spans_out, nullptr, spans_cap, n_tokens_out, flags, stream);
 }
 
 int latok_token_features_kind_batch(const void* units, int kind, const int64_t* row_off, int64_t n_str, int64_t total_chars,
                                     int64_t* counts_out, int64_t* spans4_out, int8_t* features_out, int64_t cap,
                                     int64_t* n_tokens_out, int flags, void* stream) {
     LATOK_ENTER();
-    int rc = check_kind(kind);
+    const int rc = check_kind(kind);
     if (rc) return rc;
     if (!features_out && cap > 0) return fail(LATOK_ERR_INVALID, "features_out is NULL");
-    static int8_t dummy = 0;
-    int8_t* f = features_out ? features_out : &dummy;
-    if (kind == 4)
-        return compact_common(g, true, (const uint32_t*)units, row_off, n_str, total_chars, counts_out, spans4_out, cap, n_tokens_out,
-                              flags, stream, f);
-    static const uint8_t empty = 0;
-    return compact_common(g, true, nullptr, row_off, n_str, total_chars, counts_out, spans4_out, cap, n_tokens_out, flags, stream,
-                          f, units ? (const uint8_t*)units : &empty, true, kind);
+    return compact_common(g, true, true, Batch{Input{units, form_of_kind(kind)}, row_off, n_str, total_chars}, false, counts_out,
+                          spans4_out, features_out, cap, n_tokens_out, flags, stream);
 }
 
 int latok_token_features_batch(const uint32_t* cps, const int64_t* row_off, int64_t n_str, int64_t total,
@@ -1812,9 +1692,8 @@ int latok_token_features_batch(const uint32_t* cps, const int64_t* row_off, int6
                                int64_t* n_tokens_out, int flags, void* stream) {
     LATOK_ENTER();
     if (!features_out && cap > 0) return fail(LATOK_ERR_INVALID, "features_out is NULL");
-    int8_t dummy = 0;
-    return compact_common(g, true, cps, row_off, n_str, total, counts_out, spans4_out, cap, n_tokens_out, flags, stream,
-                          features_out ? features_out : &dummy);
+    return compact_common(g, true, true, Batch{Input{cps, Form::Utf32}, row_off, n_str, total}, false, counts_out, spans4_out, features_out,
+                          cap, n_tokens_out, flags, stream);
 }
 
 int latok_parse_matrix(const uint32_t* cps, int64_t n, int8_t* matrix_out, int flags, void* stream) {
@@ -1966,11 +1845,17 @@ int latok_block_mask(const int8_t* a1, const int8_t* a2, int64_t n, int8_t* out,
         d2 = (const int8_t*)g.h_aux.p;
         dout = (int8_t*)g.h_out.p;
     }
-    int* d_flags = (int*)((char*)g.scalar.p + 16);
+    int* d_flags = (int*)((char*)g.ws.scalar.p + 16);
     HIP_TRY(latok::launch_any_nonzero(d1, d2, n, d_flags, st));
-    if ((rc = run_pipeline(g, nullptr, (const int64_t*)g.h_row.p, 1, n, nullptr, (uint8_t*)dout, latok::kModeBlockMask, st,
-                           nullptr, nullptr, d1, d2, d_flags)))
-        return rc;
+    Pipe a;
+    a.b = Batch{Input{}, (const int64_t*)g.h_row.p, 1, n};
+    a.mode = latok::kModeBlockMask;
+    a.values = (uint8_t*)dout;
+    a.bm_a1 = d1;
+    a.bm_a2 = d2;
+    a.bm_flags = d_flags;
+    a.st = st;
+    if ((rc = run_pipeline(g, g.ws, a))) return rc;
     if (!dev) {
         HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -2085,9 +1970,9 @@ int latok_utf8_bytes(const uint32_t* cps, int64_t n, int64_t* bytes_out, int fla
     LATOK_ENTER();
     int rc = need_init(g);
     if (rc) return rc;
-    HIP_TRY(latok::launch_utf8_bytes(cps, n, (unsigned long long*)g.scalar.p, g.stream));
+    HIP_TRY(latok::launch_utf8_bytes(cps, n, (unsigned long long*)g.ws.scalar.p, g.stream));
     unsigned long long t = 0;
-    HIP_TRY(hipMemcpyAsync(&t, g.scalar.p, 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(&t, g.ws.scalar.p, 8, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     *bytes_out = (int64_t)t;
     return LATOK_OK;
@@ -2097,7 +1982,7 @@ int latok_utf8_bytes(const uint32_t* cps, int64_t n, int64_t* bytes_out, int fla
  * the 18-bit epoch of k_word_counts_scan's state can be exercised without 262 144 calls */
 int latok_debug_set_scan_epoch(unsigned epoch) {
     LATOK_ENTER();
-    g.scan_epoch = epoch & 0x3FFFFu;
+    g.ws.scan_epoch = epoch & 0x3FFFFu;
     return LATOK_OK;
 }
 
@@ -2252,23 +2137,17 @@ static int flow_drain(Ctx& g) {
     return LATOK_OK;
 }
 // Reserve what a batch needs in a slot.  A buffer that has to grow is reallocated only once nothing in flight can still use it.
-struct SlotNeed {
-    DevBuf* buf;
-    size_t bytes;
-};
-static int flow_reserve(Ctx& g, std::initializer_list<SlotNeed> needs) {
+static int flow_reserve(Ctx& g, const WsNeed* needs, int n) {
     bool grow = false;
-    for (const SlotNeed& n : needs) grow = grow || n.buf->cap < n.bytes;
+    for (int i = 0; i < n; ++i) grow = grow || needs[i].buf->cap < needs[i].bytes;
     if (!grow) return LATOK_OK;
-    int rc = flow_drain(g);
-    for (const SlotNeed& n : needs)
-        if (!rc) rc = n.buf->ensure(n.bytes);
-    return rc;
+    const int rc = flow_drain(g);
+    return rc ? rc : ws_ensure(needs, n);
 }
 // Slots are used in turn -- except that a batch which touches memory a batch still in flight writes (or writes memory one
 // reads) goes to THAT batch's slot, whose stream orders the two; when batches of several slots are in its way the flow is
 // drained first (flow_hazards.h; callers that alternate buffers never hit either; an event per batch to order such pairs
-// across streams would cost every batch ~3 us).  *slot_out = the slot to enqueue on; flow_note after the batch is enqueued.
+// across streams would cost every batch ~3 us).  *slot_out = the slot to enqueue on; the caller notes the batch's ranges.
 static int flow_pick(Ctx& g, const latok::FlowRange* r, int n, int* slot_out) {
     const int turn = (int)(g.flow_seq % (unsigned)g.flow_slots);
     int s = g.flow_held.route(g.flow_slots, turn, r, n);
@@ -2290,45 +2169,50 @@ static int flow_pick(Ctx& g, const latok::FlowRange* r, int n, int* slot_out) {
     *slot_out = s;
     return LATOK_OK;
 }
-// units: UTF-32 code points (unit_kind 4), PEP 393 units (1 / 2; positions are chars) or UTF-8 bytes (0; byte space)
-static int flow_submit(Ctx& g, const void* units, int unit_kind, const int64_t* row_off, int64_t n_str, int64_t total, uint64_t* mask,
-                       int* slot_used = nullptr) {
-    int rc = flow_setup(g);
-    if (rc) return rc;
-    if (n_str <= 0 || total <= 0) return LATOK_OK;
-    if (!units || !row_off || !mask) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    if (((uintptr_t)units & 15) != 0) return fail(LATOK_ERR_INVALID, "device input pointer must be 16-byte aligned");
-    const uint32_t* cps = unit_kind == 4 ? (const uint32_t*)units : nullptr;
-    const uint8_t* u8 = unit_kind == 4 ? nullptr : (const uint8_t*)units;
-    const int64_t n_tiles = (total + latok::kTile - 1) / latok::kTile;
-    const size_t unit_bytes = unit_kind == 0 ? 1 : (size_t)unit_kind;
-    const latok::FlowRange touched[3] = {latok::flow_range(mask, (size_t)((total + 63) / 64) * 8, true),
-                                         latok::flow_range(units, (size_t)total * unit_bytes, false),
-                                         latok::flow_range(row_off, (size_t)(n_str + 1) * 8, false)};
-    int slot = 0;
-    if ((rc = flow_pick(g, touched, 3, &slot))) return rc;
-    Ctx::FlowSlot& f = g.flow[slot];
-    if ((rc = flow_reserve(g, {{&f.summ, ws_summ_bytes(n_tiles)}, {&f.seg_agg, ws_seg_bytes(n_tiles)}, {&f.tile_first, ws_first_bytes(n_tiles)},
-                               {&f.fix_count, 8}})))
-        return rc;
-    if ((rc = run_pipeline(g, cps, row_off, n_str, total, mask, nullptr, latok::kModeBits, f.st, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, u8, unit_kind == 4 ? 0 : unit_kind, 7, nullptr, latok::DoneSignal{nullptr, 0, nullptr}, &f)))
-        return rc;
-    g.flow_held.note(slot, touched, 3);
-    if (slot_used) *slot_used = slot;
+// The prologue of a flow batch (b: device pointers, n_str > 0, total > 0, checked by the caller).  r[0 .. n_out) = what the
+// batch writes; its inputs are added here.  The slot is picked, the first n_needs buffers of its workspace are reserved, and
+// the ranges are noted BEFORE anything is enqueued: a launch that fails midway cannot leave work on the caller's buffers that
+// the routing does not know of (over-noting only costs overlap).
+static int flow_begin(Ctx& g, const Batch& b, latok::FlowRange* r, int n_out, int n_needs, bool spans, bool feats, int* slot_out) {
+    r[n_out] = latok::flow_range(b.in.p, (size_t)b.total * b.in.width(), false);
+    r[n_out + 1] = latok::flow_range(b.row, (size_t)(b.n_str + 1) * 8, false);
+    const int n = n_out + 2;
+    int rc, s = 0;
+    if ((rc = flow_pick(g, r, n, &s))) return rc;
+    if ((rc = flow_reserve(g, ws_needs(g.flow[s].ws, b.total, spans, feats, feats && b.in.narrow()).data(), n_needs))) return rc;
+    g.flow_held.note(s, r, n);
     ++g.flow_seq;
+    *slot_out = s;
     return LATOK_OK;
 }
-// offsets (spans = false) or token spans of one batch: everything latok_split_offsets_batch / latok_token_spans_batch launch,
-// on the slot's stream and workspaces; the item total and the error flags land in result[0..1] when the stream gets there
-static int flow_submit_compact(Ctx& g, bool spans, const void* units, int unit_kind, const int64_t* row_off, int64_t n_str, int64_t total,
-                               void* counts, void* items, int64_t cap, int64_t* result, int flags, int8_t* feat = nullptr, bool feats = false) {
+static int flow_submit(Ctx& g, const Batch& b, uint64_t* mask, int* slot_used = nullptr) {
+    int rc = flow_setup(g);
+    if (rc) return rc;
+    if (b.n_str <= 0 || b.total <= 0) return LATOK_OK;
+    if (!b.in.p || !b.row || !mask) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (((uintptr_t)b.in.p & 15) != 0) return fail(LATOK_ERR_INVALID, "device input pointer must be 16-byte aligned");
+    latok::FlowRange touched[3] = {latok::flow_range(mask, (size_t)((b.total + 63) / 64) * 8, true)};
+    int slot = 0;
+    if ((rc = flow_begin(g, b, touched, 1, kTileNeeds, false, false, &slot))) return rc;
+    if (slot_used) *slot_used = slot;
+    Ctx::FlowSlot& f = g.flow[slot];
+    Pipe a;
+    a.b = b;
+    a.bits = mask;
+    a.st = f.st;
+    return run_pipeline(g, f.ws, a);
+}
+// offsets (spans = false), token spans or token spans + feature sums (feats) of one batch: everything the blocking calls
+// launch, on the slot's stream and workspace; the item total and the error flags land in result[0..1] when the stream gets there
+static int flow_submit_compact(Ctx& g, bool spans, bool feats, const Batch& b, void* counts, void* items, int8_t* feat, int64_t cap,
+                               int64_t* result, int flags) {
     int rc = flow_setup(g);
     if (rc) return rc;
     if (!result) return fail(LATOK_ERR_INVALID, "NULL result pointer");
     if (((uintptr_t)result & 7) != 0) return fail(LATOK_ERR_INVALID, "result pointer must be 8-byte aligned");
+    const int64_t n_str = b.n_str;
     const size_t rec = (flags & LATOK_OUT_INT32) ? 4 : 8;   // bytes of a count / of one field of a record
-    if (n_str <= 0 || total <= 0) {   // nothing to launch: counts of empty strings are zero, no items
+    if (n_str <= 0 || b.total <= 0) {   // nothing to launch: counts of empty strings are zero, no items
         const latok::FlowRange w[2] = {latok::flow_range(result, 16, true), latok::flow_range(counts, n_str > 0 ? (size_t)n_str * rec : 0, true)};
         int s0 = 0;
         if ((rc = flow_pick(g, w, 2, &s0))) return rc;
@@ -2337,41 +2221,33 @@ static int flow_submit_compact(Ctx& g, bool spans, const void* units, int unit_k
         g.flow_held.note(s0, w, 2);
         return LATOK_OK;
     }
-    if (!units || !row_off || !counts || ((!items || (feats && !feat)) && cap > 0)) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (!b.in.p || !b.row || !counts || ((!items || (feats && !feat)) && cap > 0)) return fail(LATOK_ERR_INVALID, "NULL buffer");
     if (cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
-    if (feats && unit_kind == 0) return fail(LATOK_ERR_INVALID, "featurize reads code points or PEP 393 units, not UTF-8 bytes");
-    if (((uintptr_t)units & 15) != 0) return fail(LATOK_ERR_INVALID, "device input pointer must be 16-byte aligned");
+    if (feats && b.in.form == Form::Utf8) return fail(LATOK_ERR_INVALID, "featurize reads code points or PEP 393 units, not UTF-8 bytes");
+    if (((uintptr_t)b.in.p & 15) != 0) return fail(LATOK_ERR_INVALID, "device input pointer must be 16-byte aligned");
     const bool o32 = (flags & LATOK_OUT_INT32) != 0;
     if (((uintptr_t)items & 15) != 0 || ((uintptr_t)counts & (o32 ? 3 : 7)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    const uint32_t* cps = unit_kind == 4 ? (const uint32_t*)units : nullptr;
-    const uint8_t* u8 = unit_kind == 4 ? nullptr : (const uint8_t*)units;
-    const int64_t n_tiles = (total + latok::kTile - 1) / latok::kTile;
-    const int64_t words = (total + 63) / 64, c_tiles = (words + 63) / 64;
-    // every output of the batch -- records, counts, result words, feature sums -- and its inputs
-    const size_t unit_bytes = unit_kind == 0 ? 1 : (size_t)unit_kind;
+    // every output of the batch -- records, counts, result words, feature sums -- and (flow_begin) its inputs
     const size_t fields = feats ? 4 : (spans ? 2 : 1);
-    const latok::FlowRange touched[6] = {latok::flow_range(items, (size_t)cap * fields * rec, true),
-                                         latok::flow_range(counts, (size_t)n_str * rec, true),
-                                         latok::flow_range(result, 16, true),
-                                         latok::flow_range(feat, feats ? (size_t)cap * LATOK_FEATURE_COUNT : 0, true),
-                                         latok::flow_range(units, (size_t)total * unit_bytes, false),
-                                         latok::flow_range(row_off, (size_t)(n_str + 1) * 8, false)};
+    latok::FlowRange touched[6] = {latok::flow_range(items, (size_t)cap * fields * rec, true),
+                                   latok::flow_range(counts, (size_t)n_str * rec, true),
+                                   latok::flow_range(result, 16, true),
+                                   latok::flow_range(feat, feats ? (size_t)cap * LATOK_FEATURE_COUNT : 0, true)};
     int slot = 0;
-    if ((rc = flow_pick(g, touched, 6, &slot))) return rc;
+    if ((rc = flow_begin(g, b, touched, 4, kWsNeeds, spans, feats, &slot))) return rc;
     Ctx::FlowSlot& f = g.flow[slot];
-    if ((rc = flow_reserve(g, {{&f.summ, ws_summ_bytes(n_tiles)}, {&f.seg_agg, ws_seg_bytes(n_tiles)}, {&f.tile_first, ws_first_bytes(n_tiles)},
-                               {&f.fix_count, 8}, {&f.bits, (size_t)words * 8 + 8}, {&f.space, spans ? (size_t)words * 8 + 8 : 0},
-                               {&f.kept, spans ? (size_t)words * 8 + 8 : 0}, {&f.wcnt, (size_t)c_tiles * 8 + 8}, {&f.bases, (size_t)c_tiles * 8 + 8},
-                               {&f.wpref, (size_t)words * 2 + 8}, {&f.scalar, 64}, {&f.chain, (size_t)latok::count_blocks(words) * 8 + 64},
-                               {&f.chain_ctl, 64}, {&f.codes, feats ? (size_t)total + latok::kTile + 256 : 0},
-                               {&f.widened, feats && unit_kind != 4 ? (size_t)total * 4 + 16 : 0}})))
-        return rc;
-    if ((rc = enqueue_compaction_dev(g, spans, feats, o32, cps, u8, unit_kind == 4 ? 0 : unit_kind, row_off, n_str, total, counts, items, feat,
-                                     cap, result, nullptr, f.st, latok::DoneSignal{nullptr, 0, nullptr}, &f)))
-        return rc;
-    g.flow_held.note(slot, touched, 6);
-    ++g.flow_seq;
-    return LATOK_OK;
+    Compaction k;
+    k.b = b;
+    k.spans = spans;
+    k.feats = feats;
+    k.o32 = o32;
+    k.counts = counts;
+    k.items = items;
+    k.feat = feat;
+    k.cap = cap;
+    k.p_tot = result;
+    k.st = f.st;
+    return enqueue_compaction_dev(g, f.ws, k);
 }
 
 int latok_flow_split_mask(const uint32_t* cps_dev, const int64_t* row_off_dev, int64_t n_str, int64_t total_chars,
@@ -2382,7 +2258,7 @@ int latok_flow_split_mask(const uint32_t* cps_dev, const int64_t* row_off_dev, i
     if (total_chars < 0) {
         if ((rc = resolve_total_device(row_off_dev, n_str, &total_chars, g.stream))) return rc;
     }
-    return flow_submit(g, cps_dev, 4, row_off_dev, n_str, total_chars, mask_dev);
+    return flow_submit(g, Batch{Input{cps_dev, Form::Utf32}, row_off_dev, n_str, total_chars}, mask_dev);
 }
 int latok_flow_split_mask_kind(const void* units_dev, int kind, const int64_t* row_off_dev, int64_t n_str, int64_t total_chars,
                                uint64_t* mask_dev) {
@@ -2393,7 +2269,7 @@ int latok_flow_split_mask_kind(const void* units_dev, int kind, const int64_t* r
     if (total_chars < 0) {
         if ((rc = resolve_total_device(row_off_dev, n_str, &total_chars, g.stream))) return rc;
     }
-    return flow_submit(g, units_dev, kind, row_off_dev, n_str, total_chars, mask_dev);
+    return flow_submit(g, Batch{Input{units_dev, form_of_kind(kind)}, row_off_dev, n_str, total_chars}, mask_dev);
 }
 int latok_flow_split_mask_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
                                      uint64_t* mask_dev) {
@@ -2403,40 +2279,36 @@ int latok_flow_split_mask_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byt
     if (total_bytes < 0) {
         if ((rc = resolve_total_device(byte_off_dev, n_str, &total_bytes, g.stream))) return rc;
     }
-    return flow_submit(g, utf8_dev, 0, byte_off_dev, n_str, total_bytes, mask_dev);
+    return flow_submit(g, Batch{Input{utf8_dev, Form::Utf8}, byte_off_dev, n_str, total_bytes}, mask_dev);
 }
-static int flow_compact_entry(bool spans, const void* units_dev, int kind, const int64_t* row_off_dev, int64_t n_str, int64_t total_units,
-                              void* counts_dev, void* items_dev, int64_t cap, int64_t* result_dev, int flags) {
+static int flow_compact_entry(bool spans, bool feats, const void* units_dev, int kind, const int64_t* row_off_dev, int64_t n_str,
+                              int64_t total_units, void* counts_dev, void* items_dev, int8_t* features_dev, int64_t cap, int64_t* result_dev,
+                              int flags) {
     LATOK_ENTER();
     int rc = need_init(g);
     if (rc) return rc;
-    if (kind != 0 && (rc = check_kind(kind))) return rc;
+    if ((kind != 0 || feats) && (rc = check_kind(kind))) return rc;
     if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
     if (total_units < 0) {
         if ((rc = resolve_total_device(row_off_dev, n_str, &total_units, g.stream))) return rc;
     }
-    return flow_submit_compact(g, spans, units_dev, kind, row_off_dev, n_str, total_units, counts_dev, items_dev, cap, result_dev, flags);
+    return flow_submit_compact(g, spans, feats, Batch{Input{units_dev, form_of_kind(kind)}, row_off_dev, n_str, total_units}, counts_dev,
+                               items_dev, features_dev, cap, result_dev, flags);
 }
 int latok_flow_split_offsets(const void* units_dev, int kind, const int64_t* row_off_dev, int64_t n_str, int64_t total_units,
                              void* counts_dev, void* offsets_dev, int64_t offsets_cap, int64_t* result_dev, int flags) {
-    return flow_compact_entry(false, units_dev, kind, row_off_dev, n_str, total_units, counts_dev, offsets_dev, offsets_cap, result_dev, flags);
+    return flow_compact_entry(false, false, units_dev, kind, row_off_dev, n_str, total_units, counts_dev, offsets_dev, nullptr, offsets_cap,
+                              result_dev, flags);
 }
 int latok_flow_token_spans(const void* units_dev, int kind, const int64_t* row_off_dev, int64_t n_str, int64_t total_units,
                            void* counts_dev, void* spans_dev, int64_t spans_cap, int64_t* result_dev, int flags) {
-    return flow_compact_entry(true, units_dev, kind, row_off_dev, n_str, total_units, counts_dev, spans_dev, spans_cap, result_dev, flags);
+    return flow_compact_entry(true, false, units_dev, kind, row_off_dev, n_str, total_units, counts_dev, spans_dev, nullptr, spans_cap,
+                              result_dev, flags);
 }
 int latok_flow_token_features(const void* units_dev, int kind, const int64_t* row_off_dev, int64_t n_str, int64_t total_chars,
                               void* counts_dev, void* spans4_dev, int8_t* features_dev, int64_t cap, int64_t* result_dev, int flags) {
-    LATOK_ENTER();
-    int rc = need_init(g);
-    if (rc) return rc;
-    if ((rc = check_kind(kind))) return rc;
-    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
-    if (total_chars < 0) {
-        if ((rc = resolve_total_device(row_off_dev, n_str, &total_chars, g.stream))) return rc;
-    }
-    return flow_submit_compact(g, true, units_dev, kind, row_off_dev, n_str, total_chars, counts_dev, spans4_dev, cap, result_dev, flags,
-                               features_dev, true);
+    return flow_compact_entry(true, true, units_dev, kind, row_off_dev, n_str, total_chars, counts_dev, spans4_dev, features_dev, cap,
+                              result_dev, flags);
 }
 int latok_flow_wait(void) {
     LATOK_ENTER();
@@ -2454,7 +2326,7 @@ int latok_bench_stream_read(const void* buf_dev, int64_t bytes, int warmup, int 
     if (((uintptr_t)buf_dev & 15) != 0) return fail(LATOK_ERR_INVALID, "device pointer must be 16-byte aligned");
     StreamTurn turn(g, nullptr);
     hipStream_t st = turn.st;
-    uint32_t* sink = (uint32_t*)g.scalar.p + 8;
+    uint32_t* sink = (uint32_t*)g.ws.scalar.p + 8;
     for (int i = 0; i < warmup; ++i) HIP_TRY(latok::launch_stream_read(buf_dev, bytes, sink, g.n_cu, st));
     HIP_TRY(hipEventRecord(g.ev[0], st));
     for (int i = 0; i < iters; ++i) HIP_TRY(latok::launch_stream_read(buf_dev, bytes, sink, g.n_cu, st));
@@ -2475,13 +2347,19 @@ int latok_bench_split_mask(const uint32_t* cps_dev, const int64_t* row_off_dev, 
     StreamTurn turn(g, nullptr);
     hipStream_t st = turn.st;
     if ((rc = resolve_total_device(row_off_dev, n_str, &total, st))) return rc;
+    Pipe a;
+    a.b = Batch{Input{cps_dev, Form::Utf32}, row_off_dev, n_str, total};
+    a.bits = mask_dev;
+    a.st = st;
+    Pipe tiles = a;   // stage 2 alone
+    tiles.stages = 2;
     for (int i = 0; i < warmup; ++i)
-        if ((rc = run_pipeline(g, cps_dev, row_off_dev, n_str, total, mask_dev, nullptr, latok::kModeBits, st))) return rc;
+        if ((rc = run_pipeline(g, g.ws, a))) return rc;
     // (1) whole pipeline, `iters` passes between one pair of events on the launch stream
     if (ms_total_out) {
         HIP_TRY(hipEventRecord(g.ev[0], st));
         for (int i = 0; i < iters; ++i)
-            if ((rc = run_pipeline(g, cps_dev, row_off_dev, n_str, total, mask_dev, nullptr, latok::kModeBits, st))) return rc;
+            if ((rc = run_pipeline(g, g.ws, a))) return rc;
         HIP_TRY(hipEventRecord(g.ev[1], st));
         HIP_TRY(hipEventSynchronize(g.ev[1]));
         float ms = 0.f;
@@ -2496,21 +2374,19 @@ int latok_bench_split_mask(const uint32_t* cps_dev, const int64_t* row_off_dev, 
     if (ms_tiles_out) {
         HIP_TRY(hipEventRecord(g.ev[2], st));
         for (int i = 0; i < iters; ++i)
-            if ((rc = run_pipeline(g, cps_dev, row_off_dev, n_str, total, mask_dev, nullptr, latok::kModeBits, st, nullptr, nullptr,
-                                   nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 2)))
-                return rc;
+            if ((rc = run_pipeline(g, g.ws, tiles))) return rc;
         HIP_TRY(hipEventRecord(g.ev[3], st));
         HIP_TRY(hipEventSynchronize(g.ev[3]));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, g.ev[2], g.ev[3]));
         *ms_tiles_out = ms;
         // leave a resolved mask behind
-        if ((rc = run_pipeline(g, cps_dev, row_off_dev, n_str, total, mask_dev, nullptr, latok::kModeBits, st))) return rc;
+        if ((rc = run_pipeline(g, g.ws, a))) return rc;
     }
     HIP_TRY(hipStreamSynchronize(st));
     if (n_fix_tiles_out) {
         *n_fix_tiles_out = 0;
-        if (total > 0) HIP_TRY(hipMemcpy(n_fix_tiles_out, g.fix_count.p, 8, hipMemcpyDeviceToHost));
+        if (total > 0) HIP_TRY(hipMemcpy(n_fix_tiles_out, g.ws.fix_count.p, 8, hipMemcpyDeviceToHost));
     }
     return LATOK_OK;
 }
@@ -2636,6 +2512,10 @@ int latok_bench_split_mask_gated(const uint32_t* cps_dev, const int64_t* row_off
     StreamTurn turn(g, nullptr);
     hipStream_t st = turn.st;
     if ((rc = resolve_total_device(row_off_dev, n_str, &total, st))) return rc;
+    Pipe a;
+    a.b = Batch{Input{cps_dev, Form::Utf32}, row_off_dev, n_str, total};
+    a.bits = mask_dev;
+    a.st = st;
     // LATOK_BENCH_GRAPH=1 (bench.py --launch threads, N > 1): the K passes are captured into ONE hipGraph outside the
     // timed region and replayed by one call inside it -- with N host threads of one process launching 3 kernels per 0.1 ms
     // step each, the threads would otherwise meet in the runtime's launch path.  Same kernels, same order, same stream.
@@ -2646,11 +2526,11 @@ int latok_bench_split_mask_gated(const uint32_t* cps_dev, const int64_t* row_off
         if (e && e[0] == '1') {
             // (the workspaces are sized by the caller's warm-up passes; one eager pass here makes sure of it: nothing may
             // allocate during a capture)
-            if ((rc = run_pipeline(g, cps_dev, row_off_dev, n_str, total, mask_dev, nullptr, latok::kModeBits, st))) return rc;
+            if ((rc = run_pipeline(g, g.ws, a))) return rc;
             HIP_TRY(hipStreamSynchronize(st));
             if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
                 for (int i = 0; i < iters && !rc; ++i)
-                    rc = run_pipeline(g, cps_dev, row_off_dev, n_str, total, mask_dev, nullptr, latok::kModeBits, st);
+                    rc = run_pipeline(g, g.ws, a);
                 hipError_t ce = hipStreamEndCapture(st, &graph);
                 if (!rc && ce == hipSuccess && graph) ce = hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0);
                 if (rc || ce != hipSuccess || !gexec) {      // no graph on this runtime: the eager form below
@@ -2677,7 +2557,7 @@ int latok_bench_split_mask_gated(const uint32_t* cps_dev, const int64_t* row_off
         if (hipGraphLaunch(gexec, st) != hipSuccess) rc = fail(LATOK_ERR_HIP, "hipGraphLaunch failed");
     } else {
         for (int i = 0; i < iters; ++i)
-            if ((rc = run_pipeline(g, cps_dev, row_off_dev, n_str, total, mask_dev, nullptr, latok::kModeBits, st))) break;
+            if ((rc = run_pipeline(g, g.ws, a))) break;
     }
     if (!rc) {
         hipError_t e = hipEventRecord(g.ev[1], st);
@@ -2716,8 +2596,8 @@ int latok_bench_split_mask_flow_gated(const uint32_t* cps_dev, const int64_t* ro
     const uint32_t* cps_b = g.bench_cps_b ? g.bench_cps_b : cps_dev;     // (latok_bench_set_second_input: a copy at another address)
     const int64_t* row_b = g.bench_row_b ? g.bench_row_b : row_off_dev;
     for (int i = 0; i < iters; ++i)
-        if ((rc = flow_submit(g, (i & 1) ? cps_b : cps_dev, 4, (i & 1) ? row_b : row_off_dev, n_str, total, (i & 1) ? mask_b_dev : mask_a_dev,
-                              &last_slot)))
+        if ((rc = flow_submit(g, Batch{Input{(i & 1) ? cps_b : cps_dev, Form::Utf32}, (i & 1) ? row_b : row_off_dev, n_str, total},
+                              (i & 1) ? mask_b_dev : mask_a_dev, &last_slot)))
             break;
     if (!rc) {
         hipError_t e = hipEventRecord(g.ev[1], g.flow[last_slot].st);   // ... of the last one
@@ -2759,14 +2639,19 @@ int latok_bench_tiles_flow(const uint32_t* cps_dev, const int64_t* row_off_dev, 
     const int64_t* row_b = g.bench_row_b ? g.bench_row_b : row_off_dev;
     int slot_of[2] = {0, 1};
     for (int i = 0; i < 2; ++i)
-        if ((rc = flow_submit(g, i ? cps_b : cps_dev, 4, i ? row_b : row_off_dev, n_str, total, i ? mask_b_dev : mask_a_dev, &slot_of[i]))) return rc;
+        if ((rc = flow_submit(g, Batch{Input{i ? cps_b : cps_dev, Form::Utf32}, i ? row_b : row_off_dev, n_str, total}, i ? mask_b_dev : mask_a_dev,
+                              &slot_of[i])))
+            return rc;
     if ((rc = flow_drain(g))) return rc;
     const int64_t t0 = mono_ns();
     for (int i = 0; i < iters && !rc; ++i) {
         Ctx::FlowSlot& f = g.flow[slot_of[i & 1]];
-        rc = run_pipeline(g, (i & 1) ? cps_b : cps_dev, (i & 1) ? row_b : row_off_dev, n_str, total, (i & 1) ? mask_b_dev : mask_a_dev, nullptr,
-                          latok::kModeBits, f.st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 2, nullptr,
-                          latok::DoneSignal{nullptr, 0, nullptr}, &f);
+        Pipe a;
+        a.b = Batch{Input{(i & 1) ? cps_b : cps_dev, Form::Utf32}, (i & 1) ? row_b : row_off_dev, n_str, total};
+        a.bits = (i & 1) ? mask_b_dev : mask_a_dev;
+        a.stages = 2;
+        a.st = f.st;
+        rc = run_pipeline(g, f.ws, a);
     }
     const int rc_drain = flow_drain(g);
     const int64_t t1 = mono_ns();
@@ -2775,7 +2660,7 @@ int latok_bench_tiles_flow(const uint32_t* cps_dev, const int64_t* row_off_dev, 
     *ms_out = (float)((t1 - t0) / 1e6);
     // leave resolved masks behind
     for (int i = 0; i < 2; ++i)
-        if ((rc = flow_submit(g, cps_dev, 4, row_off_dev, n_str, total, i ? mask_b_dev : mask_a_dev))) return rc;
+        if ((rc = flow_submit(g, Batch{Input{cps_dev, Form::Utf32}, row_off_dev, n_str, total}, i ? mask_b_dev : mask_a_dev))) return rc;
     return flow_drain(g);
 }
 
