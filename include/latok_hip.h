@@ -144,6 +144,14 @@ int latok_split_offsets_utf8_batch(const uint8_t* utf8, const int64_t* byte_off,
 int latok_token_spans_utf8_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
                                  int64_t* counts_out, int64_t* spans_out, int64_t spans_cap, int64_t* n_tokens_out,
                                  int flags, void* stream);
+/* featurize of the decoded text: latok_token_features_batch (below) on what latok_utf8_decode_batch would give -- spans4 in
+ * code points relative to each string, the 25 feature sums per token -- with the same flags (LATOK_OUT_INT32, LATOK_DEVICE_PTRS),
+ * total_bytes = -1 and capacity protocol; features_out NULL with cap > 0 is refused.  Large well-formed batches make no UTF-32
+ * copy: the byte-space pipeline gives the code-point masks and one kernel stores the rule code of every char at its code-point
+ * index (1 B/char) for the feature sums.  Malformed input gives what the staged decoder gives. */
+int latok_token_features_utf8_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                    int64_t* counts_out, int64_t* spans4_out, int8_t* features_out, int64_t cap,
+                                    int64_t* n_tokens_out, int flags, void* stream);
 
 /* ---- UTF-8 in BYTE space (fused ingest) -----------------------------------------------------------------------------
  * Same tokenization, but nothing is decoded to UTF-32: the tile kernel reads the UTF-8 bytes themselves (1 byte per

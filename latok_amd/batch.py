@@ -311,6 +311,31 @@ def token_spans_utf8_csr(utf8, byte_off, dtype=np.int64):
     return _compact(_lib.ensure_init().latok_token_spans_utf8_batch, [_ptr(utf8), _ptr(byte_off)], n_str, total, 2, dtype)
 
 
+def token_features_utf8_csr(utf8, byte_off, dtype=np.int64):
+    """(counts, spans[n_tokens, 4], features int8[n_tokens, 25]) like token_features_csr for a UTF-8 CSR batch: spans are
+    code-point indices, exactly what token_features_csr gives for the decoded text (no UTF-32 copy is made for large batches)."""
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    n_str = byte_off.size - 1
+    total = int(byte_off[-1]) if n_str > 0 else 0
+    return _compact(_lib.ensure_init().latok_token_features_utf8_batch, [_ptr(utf8), _ptr(byte_off)], n_str, total, 4, dtype, feats=True)
+
+
+def featurize_utf8_batch(blobs):
+    """list[bytes] (each valid UTF-8) -> list[list[LaToken]], token for token what featurize_batch gives for the decoded
+    strings: start_idx / end_idx in code points, text = the decoded string sliced at the stripped span."""
+    from .core.latok_utils import LaToken
+    if len(blobs) == 0:
+        return []
+    utf8, byte_off = pack_utf8(blobs)
+    counts, spans, feats = token_features_utf8_csr(utf8, byte_off, dtype=_record_dtype(byte_off))
+    out, k = [], 0
+    for blob, n in zip(blobs, counts.tolist()):
+        text = blob.decode("utf-8", "surrogatepass") if n else ""
+        out.append([LaToken(text[c:d], a, b, feats[k + j]) for j, (a, b, c, d) in enumerate(spans[k:k + n].tolist())])
+        k += n
+    return out
+
+
 # byte-space forms: the tile kernel reads the UTF-8 bytes itself; every position is a BYTE position in `utf8`
 def split_mask_utf8_bytes_csr(utf8, byte_off) -> np.ndarray:
     """uint64 bitmask over the BYTES of the batch: bit i set = byte i is the lead byte of a boundary char."""

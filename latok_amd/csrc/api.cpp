@@ -271,8 +271,10 @@ struct Ctx {
     hipEvent_t turn_event = nullptr;     // recorded behind the last kernel of every call (StreamTurn)
     hipStream_t turn_stream = nullptr;
     bool turn_stream_valid = false;
-    // test hooks: latok_debug_set_plan_cus (0 = the device's own CU count) and what the last run_pipeline launched
+    // test hooks: latok_debug_set_plan_cus (0 = the device's own CU count), what the last run_pipeline launched and the route the
+    // last compaction call took (latok_debug_last_route)
     int plan_cus = 0;
+    int last_route = 0;
     struct LastPlan {
         latok::LaunchPlan plan{};
         int64_t n_tiles = 0;
@@ -957,6 +959,7 @@ struct Compaction {
     latok::DoneSignal done{nullptr, 0, nullptr};
     const uint64_t* pre_bits = nullptr;    // the two bitmasks are already there (code-point masks packed from byte space:
     const uint64_t* pre_space = nullptr;   // cp_masks_via_bytes): only the string index is launched
+    const uint8_t* pre_codes = nullptr;    // featurize: the rule codes too (k_lead_codes), padded to one tile + 256 B behind `total`
     hipStream_t st = nullptr;
 };
 
@@ -994,14 +997,17 @@ static int enqueue_compaction_dev(Ctx& g, Workspace& w, const Compaction& c) {
     uint16_t* d_pref = (uint16_t*)w.wpref.p;
     int64_t* d_tile_first = (int64_t*)w.tile_first.p;
     uint8_t* d_codes = nullptr;
-    if (c.feats) {   // the tile kernel leaves the rule code of every char: 1 B/char for k_features_tiles instead of 4 B/char + tables
+    if (c.feats && c.pre_codes) {   // packed before (every char's code is there already): only the padding behind the last char
+        d_codes = const_cast<uint8_t*>(c.pre_codes);
+        HIP_TRY(hipMemsetAsync(d_codes + total, 0, (size_t)latok::kTile + 256, st));
+    } else if (c.feats) {   // the tile kernel leaves the rule code of every char: 1 B/char for k_features_tiles instead of 4 B/char + tables
         d_codes = (uint8_t*)w.codes.p;
         const size_t tail0 = (size_t)total & ~(size_t)(latok::kTile - 1);
         HIP_TRY(hipMemsetAsync(d_codes + tail0, 0, (size_t)total + latok::kTile + 256 - tail0, st));
     }
     a.bits = d_bits;
     a.space = d_space;
-    a.codes = d_codes;
+    a.codes = c.pre_codes ? nullptr : d_codes;
     a.stages = c.pre_bits ? 1 : 7;
     if ((rc = run_pipeline(g, w, a))) return rc;
     if (c.h_tot) {   // pinned pair of the context's own calls: cleared by the host
@@ -1235,14 +1241,15 @@ static bool host_decode_small(const uint8_t* u8, const int64_t* boff, int64_t n_
 // after one synchronisation.  *fallback_out = 1: the batch holds a continuation byte that the byte-space model and the
 // decoder treat differently (malformed UTF-8): the caller takes the decoder.
 //   d: the bytes on the device; d_out / d_out_space: where the packed masks go (cap_words words each; d_out_space NULL:
-//   boundaries only), d_cp_row [n_str + 1]
+//   boundaries only), d_cp_row [n_str + 1]; codes (featurize): k_lead_codes also stores the rule code of every char into the
+//   workspace's code bytes (g.ws.codes, sized by the byte count, which bounds the code-point count), as the UTF-32 tile kernel would
 static int cp_masks_via_bytes(Ctx& g, const Batch& d, uint64_t* d_out, uint64_t* d_out_space, int64_t cap_words, int64_t* d_cp_row,
-                              hipStream_t st, int64_t* total_cps_out, int* fallback_out) {
+                              hipStream_t st, int64_t* total_cps_out, int* fallback_out, bool codes = false) {
     int rc;
     *fallback_out = 0;
     Workspace& w = g.ws;
     const int64_t total_bytes = d.total, words_b = (total_bytes + 63) / 64, c_tiles = (words_b + 63) / 64;
-    if ((rc = ws_ensure(ws_needs(w, total_bytes, false, false, false).data(), kWsNeeds)) || (rc = g.u_lead.ensure((size_t)words_b * 8 + 8)) ||
+    if ((rc = ws_ensure(ws_needs(w, total_bytes, false, codes, false).data(), kWsNeeds)) || (rc = g.u_lead.ensure((size_t)words_b * 8 + 8)) ||
         (d_out_space && (rc = g.u_bspace.ensure((size_t)words_b * 8 + 8))) || (rc = g.pin_tot.ensure(64)))
         return rc;
     unsigned epoch = 0;
@@ -1270,6 +1277,9 @@ static int cp_masks_via_bytes(Ctx& g, const Batch& d, uint64_t* d_out, uint64_t*
     HIP_TRY(latok::launch_lead_compress(d_bmask, d_bspace, d_lead, (const int64_t*)w.bases.p, (const int64_t*)w.wcnt.p,
                                         (const uint16_t*)w.wpref.p, words_b, total_bytes, d.row, d.n_str, (const int64_t*)w.scalar.p, d_out,
                                         d_out_space, cap_words, d_cp_row, (int*)(p_tot + 3), st));
+    if (codes)
+        HIP_TRY(latok::launch_lead_codes((const uint8_t*)d.in.p, total_bytes, d_lead, (const int64_t*)w.bases.p, (const int64_t*)w.wcnt.p,
+                                         (const uint16_t*)w.wpref.p, words_b, (const uint8_t*)g.tb6rule.p, (uint8_t*)w.codes.p, g.n_cu, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (h_tot[1] != 0) { w.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the chained scan did not complete (flag %lld)", (long long)h_tot[1]); }
     if (h_tot[3] != 0) { *fallback_out = 1; return LATOK_OK; }
@@ -1299,10 +1309,12 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
     // Small well-formed UTF-8 host batches (one string per call is the usual C caller) are decoded by the host
     // (host_decode_small) and take the pinned small-batch path of the code-point form; byte-space results are mapped back:
     // a char position becomes the byte position of that char, relative to its string.
+    g.last_route = 0;
     if (!dev && b.in.form == Form::Utf8 && b.in.p && counts_out && n_str <= kSmallStrings && b.total > 0 && b.total <= kSmallChars &&
         host_decode_small((const uint8_t*)b.in.p, row_off, n_str, g.hd_cps, g.hd_row, g.hd_pos)) {
         const Batch cps{Input{g.hd_cps.data(), Form::Utf32}, g.hd_row.data(), n_str, (int64_t)g.hd_cps.size()};
         rc = compact_common(g, spans, feats, cps, false, counts_out, items_out, features_out, items_cap, n_items_out, flags, stream);
+        g.last_route = 1;
         if (rc != LATOK_OK || cp_units || !items_out) return rc;
         const int64_t per = spans ? 2 : 1;
         int64_t k = 0;
@@ -1332,11 +1344,12 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
         return compact_host_pipelined(g, spans, feats, o32, b, counts_out, items_out, items_cap, n_items_out, features_out, st);
     Batch d = b;   // the batch as the kernels read it
     const uint64_t *pre_bits = nullptr, *pre_space = nullptr;   // code-point masks packed from byte space (UTF-8 in code-point units)
+    const uint8_t* pre_codes = nullptr;                            // ... and featurize's rule codes
     if (cp_units) {
         bool via_bytes = false;
-        if (!feats && b.total > kSmallChars && (!dev || ((uintptr_t)b.in.p & 15) == 0)) {
+        if (b.total > kSmallChars && (!dev || ((uintptr_t)b.in.p & 15) == 0)) {
             // large batches: the byte-space kernel + the masks packed at the lead bytes (no UTF-32 copy of the batch); the compaction
-            // then runs on the code-point masks
+            // then runs on the code-point masks (featurize: and on the rule codes k_lead_codes stores at the code-point positions)
             Batch bytes;
             if ((rc = units_on_device(g, b, dev, st, &bytes))) return rc;
             const int64_t words_b = (b.total + 63) / 64;
@@ -1346,16 +1359,19 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
             int fallback = 0;
             int64_t total_cps = 0;
             if ((rc = cp_masks_via_bytes(g, bytes, (uint64_t*)g.u_cpbits.p, spans ? (uint64_t*)g.u_cpspace.p : nullptr, words_b,
-                                         (int64_t*)g.u_row.p, st, &total_cps, &fallback)))
+                                         (int64_t*)g.u_row.p, st, &total_cps, &fallback, feats)))
                 return rc;
             if (!fallback) {
                 pre_bits = (const uint64_t*)g.u_cpbits.p;
                 pre_space = spans ? (const uint64_t*)g.u_cpspace.p : nullptr;
+                pre_codes = feats ? (const uint8_t*)g.ws.codes.p : nullptr;
                 d = Batch{Input{}, (const int64_t*)g.u_row.p, n_str, total_cps};
                 via_bytes = true;
+                g.last_route = 3;
             }
         }
-        if (!via_bytes) {   // small batches, featurize (re-reads code points), malformed input: decode on the device first
+        if (!via_bytes) {   // small batches, malformed input: decode on the device first
+            g.last_route = 2;
             Batch bytes;
             int64_t total_cps = 0;
             if ((rc = decode_utf8_to_workspace(g, b, dev, st, &total_cps, feats ? nullptr : &bytes))) return rc;
@@ -1459,6 +1475,7 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
         k.h_tot = h_tot;
         k.pre_bits = pre_bits;
         k.pre_space = pre_space;
+        k.pre_codes = pre_codes;
         k.st = st;
         if ((rc = enqueue_compaction_dev(g, g.ws, k))) return rc;
         done = k.done;
@@ -1617,6 +1634,15 @@ int latok_token_spans_utf8_batch(const uint8_t* utf8, const int64_t* byte_off, i
     LATOK_ENTER();
     return compact_common(g, true, false, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total_bytes}, true, counts_out, spans_out,
                           nullptr, spans_cap, n_tokens_out, flags, stream);
+}
+
+int latok_token_features_utf8_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                    int64_t* counts_out, int64_t* spans4_out, int8_t* features_out, int64_t cap,
+                                    int64_t* n_tokens_out, int flags, void* stream) {
+    LATOK_ENTER();
+    if (!features_out && cap > 0) return fail(LATOK_ERR_INVALID, "features_out is NULL");
+    return compact_common(g, true, true, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total_bytes}, true, counts_out, spans4_out,
+                          features_out, cap, n_tokens_out, flags, stream);
 }
 
 /* byte-space UTF-8 entry points: the tile kernel reads the bytes (1 B/char for ASCII), all positions are byte offsets */
@@ -2050,6 +2076,14 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
     for (; k < 3 && k < n; ++k) out[k] = head[k];
     if (n > 3) k += put_plan(g.last.plan, g.last.n_tiles, out + 3, n - 3);
     return k;
+}
+
+/* test hook (not part of the ABI): the route the last compaction call (offsets / spans / featurize) of the current context took --
+ * 0: the batch's own units (UTF-32, PEP 393 units, UTF-8 in byte space), 1: a small UTF-8 host batch decoded by the host,
+ * 2: UTF-8 through the staged device decoder, 3: UTF-8 through byte space and the packed code-point masks (and codes) */
+extern "C" int latok_debug_last_route(void) {
+    LATOK_ENTER();
+    return g.last_route;
 }
 
 /* test hook (not part of the ABI; needs no device): the flow's routing of batches to slots (flow_hazards.h) driven without a

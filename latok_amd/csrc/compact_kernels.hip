@@ -652,6 +652,178 @@ hipError_t launch_lead_compress(const uint64_t* bmask, const uint64_t* bmask2, c
     return hipGetLastError();
 }
 
+// ---- rule code of every char from byte space (featurize of UTF-8 in code-point units) --------------------------------------
+// k_features_tiles reads the rule code of every char (FeatParams::codes, 1 B/char), which the UTF-32 tile kernel leaves as it
+// classifies.  A UTF-8 batch in code-point units has no UTF-32 copy: after the byte-space pipeline (lead-byte mask, leads per
+// word and per tile) and k_scan_chained (tile ranks), this kernel stores, for every lead byte, the rule code of its char at the
+// char's code-point index tile_rank[t] + word_pref[w] + (leads below it in the word).  It classifies as bytes_phase1 does: the
+// byte-space rule-code table (kernels.h: kB6*), an ASCII byte by one lookup, a multi-byte char through lk_lead_entry_of /
+// lk_lead_index in at most two decode slots per dword (more only in malformed input: a wave-uniform loop), U+FFFD for a sequence
+// that is cut short -- so the codes are what the UTF-32 tile kernel writes for the decoded char.
+// A group = kCompressWaves tiles (k_lead_compress's geometry), one thread per 64-byte word; a workgroup walks groups (the class
+// table is copied to LDS once per workgroup).  The codes of a group are one contiguous range [tile_rank[T0], tile_rank[T1] +
+// tile_cnt[T1]).  Per dword a thread packs its lead bytes' codes with one v_perm (selector by the dword's lead nibble) and
+// appends them to a 64-bit accumulator, which ORs every full dword into a zeroed LDS window over the range (4 pad bytes per 64:
+// an all-lead wave writes without bank conflicts; the dwords a thread shares with its neighbours merge by the OR).  The window
+// goes out with dword stores, byte stores at its two ends.  Ranges of different groups never overlap: no global atomics.
+constexpr int kLeadCodesWin = kCompressWaves * kTile + 8;                         // the range + its offset in its first dword
+constexpr int kLeadCodesLds = kLeadCodesWin + 4 * ((kLeadCodesWin + 63) / 64);
+__device__ __forceinline__ int lead_codes_slot(int i) { return i + ((i >> 6) << 2); }   // LDS byte of window byte i (i % 4 == 0)
+
+// one decode slot of a dword: the multi-byte lead that `s` marks (bit 7 of its byte; s == 0: byte 3, whatever it is) -> its code
+// ORed into `out` at its byte (a slot without a lead adds 0 or its dword's lead's own code again, bytes_phase1's argument)
+__device__ __forceinline__ void lead_codes_slot_decode(uint32_t lo, uint32_t hi, uint32_t s, const uint2* ltab, const uint8_t* t1b,
+                                                       const uint8_t* t2b, uint32_t code_fffd, uint32_t& out) {
+    const uint32_t r8 = (uint32_t)__builtin_ctz(s | 0x80000000u) & 24u;
+    const uint32_t W = __builtin_amdgcn_alignbit(hi, lo, r8);   // the 4 bytes from the slot's byte on (lo = dword Q, hi = Q + 1)
+    const uint2 q = ltab[W & 0xFFu];
+    lk_lead_entry e;
+    e.sel = q.x;
+    e.hi0 = q.y;
+    uint32_t off2, R;
+    const bool bad = lk_lead_index(e, W, &off2, &R);
+    off2 = min(off2, 2u * (uint32_t)(kB6Stage1Len - 1));
+    const uint32_t blk = *reinterpret_cast<const uint16_t*>(t1b + off2);
+    const uint32_t code = t2b[blk | (R & 0x3Fu)];
+    out = bad ? ((out & ~(0xFFu << r8)) | (code_fffd << r8)) : (out | (code << r8));
+}
+
+__global__ __launch_bounds__(kCompressWaves * 64) void k_lead_codes(
+    const uint8_t* __restrict__ u8, int64_t total_bytes, const uint64_t* __restrict__ lead, const int64_t* __restrict__ tile_rank,
+    const int64_t* __restrict__ tile_cnt, const uint16_t* __restrict__ word_pref, int64_t n_words, const uint8_t* __restrict__ tb6rule,
+    uint8_t* __restrict__ codes) {
+    __shared__ __attribute__((aligned(16))) uint8_t tab_s[kB6TablesBytes];
+    __shared__ __attribute__((aligned(16))) uint8_t win_s[kLeadCodesLds];
+    __shared__ uint2 ltab_s[256];                                  // lk_lead_entry_of of every byte value
+    __shared__ uint8_t ctab_s[256];                                // code of a byte taken as a char (0 from 0x80 on)
+    __shared__ uint32_t sel_s[16];                                 // v_perm selector that packs the lead bytes of a dword
+    const int tid = threadIdx.x;
+    constexpr int NT = kCompressWaves * 64;
+    for (int i = tid; i < kB6TablesBytes / 16; i += NT)
+        reinterpret_cast<uint4*>(tab_s)[i] = reinterpret_cast<const uint4*>(tb6rule)[i];
+    if (tid < 256) {
+        const lk_lead_entry e = lk_lead_entry_of((uint32_t)tid);
+        ltab_s[tid] = make_uint2(e.sel, e.hi0);
+        ctab_s[tid] = tid < 0x80 ? tb6rule[kB6Stage1Bytes + tid] : (uint8_t)0;   // (ASCII = stage 2's first two blocks)
+    }
+    if (tid < 16) {
+        uint32_t sel = 0x04040404u;                                // byte 4 of {0, x}: 0
+        int j = 0;
+        for (int k = 0; k < 4; ++k)
+            if ((tid >> k) & 1) { sel = (sel & ~(0xFFu << (8 * j))) | ((uint32_t)k << (8 * j)); ++j; }
+        sel_s[tid] = sel;
+    }
+    const uint8_t* t1b = tab_s;
+    const uint8_t* t2b = tab_s + kB6Stage1Bytes;
+    uint32_t* win32 = reinterpret_cast<uint32_t*>(win_s);
+    const int64_t n_tiles = (n_words + 63) >> 6;
+    const int64_t n_groups = (n_tiles + kCompressWaves - 1) / kCompressWaves;
+    for (int64_t G = blockIdx.x; G < n_groups; G += gridDim.x) {
+        const int64_t T0 = G * kCompressWaves;
+        const int64_t T1 = min(T0 + kCompressWaves, n_tiles) - 1;
+        const int64_t pos0 = tile_rank[T0];
+        const int64_t end = tile_rank[T1] + tile_cnt[T1];
+        // no lead byte at all; or ranks that cannot be (the scan failed: the host sees its flag and drops the batch) -- uniform
+        if (end == pos0 || pos0 < 0 || end < pos0 || end - pos0 > (int64_t)kCompressWaves * kTile || end > total_bytes) continue;
+        const int64_t t = min(T0 + (tid >> 6), T1);
+        const int64_t w = T0 * 64 + tid;
+        const bool in = w < n_words;
+        const int64_t wc = in ? w : n_words - 1;
+        uint64_t m = in ? lead[wc] : 0ull;
+        const int64_t pos = tile_rank[t] + word_pref[wc];          // code-point index of my word's first lead
+        if (pos < pos0 || pos + __popcll(m) > end) m = 0ull;       // (the same: every store stays inside the range)
+        // my 64 bytes (0 past the end of the batch) and the 4 after them (the next lane's first dword; lane 63: from memory)
+        uint32_t d[17];
+        const int64_t b = w * 64;
+        if (in && b + 64 <= total_bytes) {
+            const uint4* src = reinterpret_cast<const uint4*>(u8 + b);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint4 v = src[k];
+                d[4 * k] = v.x; d[4 * k + 1] = v.y; d[4 * k + 2] = v.z; d[4 * k + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                uint32_t x = 0;
+                for (int j = 0; j < 4; ++j)
+                    if (b + 4 * q + j < total_bytes) x |= (uint32_t)u8[b + 4 * q + j] << (8 * j);
+                d[q] = x;
+            }
+        }
+        d[16] = (uint32_t)__shfl_down((int)d[0], 1);
+        if ((tid & 63) == 63) {
+            uint32_t x = 0;
+            for (int j = 0; j < 4; ++j)
+                if (b + 64 + j < total_bytes) x |= (uint32_t)u8[b + 64 + j] << (8 * j);
+            d[16] = x;
+        }
+        const int64_t wb = pos0 & ~(int64_t)3;                     // window byte 0 = the first byte of the range's first dword
+        const int n_win = (int)((end - wb + 3) >> 2);              // window dwords
+        for (int i = tid; i < n_win + (n_win >> 4) + 1; i += NT) win32[i] = 0u;
+        __syncthreads();                                           // (also: the tables, for the first group)
+        const uint32_t code_fffd = t2b[*reinterpret_cast<const uint16_t*>(t1b + 2u * (0xFFFDu >> 6)) | (0xFFFDu & 63u)];
+        const int o = (int)(pos - wb);
+        int e = o >> 2, cnt = o & 3;                               // next window dword, bytes in the accumulator (the first
+        uint64_t acc = 0;                                          // `cnt` are a neighbour's: 0, merged by the OR)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const uint32_t x = d[q];
+            uint32_t out = (uint32_t)ctab_s[x & 0xFFu] | ((uint32_t)ctab_s[(x >> 8) & 0xFFu] << 8) |
+                           ((uint32_t)ctab_s[(x >> 16) & 0xFFu] << 16) | ((uint32_t)ctab_s[x >> 24] << 24);
+            const uint32_t hi = x & 0x80808080u;
+            const uint32_t m1 = hi & (x << 1);                     // multi-byte leads (11xxxxxx), "bit 7 of the byte" form
+            if (__any(m1 != 0u)) {                                 // (wave-uniform)
+                const uint32_t m2 = m1 & (m1 - 1u);
+                lead_codes_slot_decode(x, d[q + 1], m1, ltab_s, t1b, t2b, code_fffd, out);
+                if (__any(m2 != 0u)) {
+                    lead_codes_slot_decode(x, d[q + 1], m2, ltab_s, t1b, t2b, code_fffd, out);
+                    uint32_t rest = m2 & (m2 - 1u);                // leads beyond two per dword (malformed input)
+                    while (__any(rest != 0u)) {
+                        if (rest) lead_codes_slot_decode(x, d[q + 1], rest, ltab_s, t1b, t2b, code_fffd, out);
+                        rest &= rest - 1u;
+                    }
+                }
+            }
+            const uint32_t L = (uint32_t)(m >> (4 * q)) & 15u;
+            const uint32_t packed = __builtin_amdgcn_perm(0u, out, sel_s[L]);
+            acc |= (uint64_t)packed << (8 * cnt);
+            cnt += __popc(L);
+            const bool full = cnt >= 4;
+            atomicOr(&win32[e + (e >> 4)], full ? (uint32_t)acc : 0u);
+            e += full ? 1 : 0;
+            acc = full ? acc >> 32 : acc;
+            cnt -= full ? 4 : 0;
+        }
+        if (cnt > 0) atomicOr(&win32[e + (e >> 4)], (uint32_t)acc);
+        __syncthreads();
+        // out: every dword of the range, whole where the range covers it, else byte by byte (the range's first and last dword)
+        const int64_t q0 = pos0 >> 2, q1 = (end + 3) >> 2;
+        for (int64_t q = q0 + tid; q < q1; q += NT) {
+            const int i = (int)(q - q0);
+            const uint32_t v = win32[i + (i >> 4)];
+            if (4 * q >= pos0 && 4 * q + 4 <= end) {
+                *reinterpret_cast<uint32_t*>(codes + 4 * q) = v;
+            } else {
+                for (int j = 0; j < 4; ++j)
+                    if (4 * q + j >= pos0 && 4 * q + j < end) codes[4 * q + j] = (uint8_t)(v >> (8 * j));
+            }
+        }
+        __syncthreads();                                           // (the window is zeroed again for the next group)
+    }
+}
+
+hipError_t launch_lead_codes(const uint8_t* u8, int64_t total_bytes, const uint64_t* lead, const int64_t* tile_rank, const int64_t* tile_cnt,
+                             const uint16_t* word_pref, int64_t n_words, const uint8_t* tb6rule, uint8_t* codes, int n_cu, hipStream_t st) {
+    const int64_t n_tiles = (n_words + 63) / 64;
+    if (n_tiles <= 0) return hipSuccess;
+    const int64_t n_groups = (n_tiles + kCompressWaves - 1) / kCompressWaves;
+    const unsigned nb = (unsigned)min(n_groups, (int64_t)max(n_cu, 1));   // one workgroup per CU (LDS), each walks its groups
+    hipLaunchKernelGGL(k_lead_codes, dim3(nb), dim3(kCompressWaves * 64), 0, st, u8, total_bytes, lead, tile_rank, tile_cnt, word_pref,
+                       n_words, tb6rule, codes);
+    return hipGetLastError();
+}
+
 // exclusive scan of per-tile counts that some other kernel left (the byte-space tile kernel: leads per tile): k_scan_chained alone
 hipError_t launch_tile_scan(const int64_t* tile_cnt, int64_t n_tiles, int64_t* tile_rank, unsigned long long* chain, unsigned* ticket,
                             unsigned epoch, int64_t* total_dev, int64_t* total_host, int* err, hipStream_t st) {

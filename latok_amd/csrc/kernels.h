@@ -222,6 +222,10 @@ hipError_t launch_lead_compress(const uint64_t* bmask, const uint64_t* bmask2, c
                                 const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, int64_t total_bytes,
                                 const int64_t* byte_off, int64_t n_str, const int64_t* total_cps_dev, uint64_t* out_mask,
                                 uint64_t* out_mask2, int64_t cap_words, int64_t* cp_row_off, int* odd, hipStream_t st);
+// the rule code of every char of a UTF-8 batch at its code-point index (codes[tile_rank[t] + word_pref[w] + leads below it]), from
+// the bytes, the lead-byte mask and the lead ranks of the byte-space pipeline; tb6rule = the byte-space rule-code table (featurize)
+hipError_t launch_lead_codes(const uint8_t* u8, int64_t total_bytes, const uint64_t* lead, const int64_t* tile_rank, const int64_t* tile_cnt,
+                             const uint16_t* word_pref, int64_t n_words, const uint8_t* tb6rule, uint8_t* codes, int n_cu, hipStream_t st);
 hipError_t launch_tile_scan(const int64_t* tile_cnt, int64_t n_tiles, int64_t* tile_rank, unsigned long long* chain, unsigned* ticket,
                             unsigned epoch, int64_t* total_dev, int64_t* total_host, int* err, hipStream_t st);
 int64_t utf8_blocks(int64_t total_bytes);   // 4 KiB blocks of the chunk-parallel UTF-8 decoder

@@ -8,6 +8,9 @@
   utf8_mask       latok_split_mask_utf8_batch       (8f-3: UTF-8 in, code-point row offsets + mask out)
   utf8_offsets    latok_split_offsets_utf8_batch
   utf8_spans      latok_token_spans_utf8_batch
+  utf8_features32 latok_token_features_utf8_batch with LATOK_OUT_INT32 (featurize of UTF-8 in code-point units, no UTF-32 copy)
+  utf8_decode_features32   what a UTF-8 caller had to compose before: latok_utf8_decode_batch into a device buffer, then
+                  latok_token_features_batch on it (LATOK_OUT_INT32); same data, same process
   bytes_mask / bytes_offsets / bytes_spans   latok_*_utf8_bytes_batch (8f-3 fused: the tile kernel reads the bytes)
   rules_mask      latok_split_mask_batch after latok_set_rules(built-in tables)   (8f-4)
   offsets32 / spans32 / features32 / kind_offsets32 / kind_spans32   the same entry points with LATOK_OUT_INT32 records
@@ -63,7 +66,7 @@ def main():
     ap.add_argument("--strings", type=int, default=1_000_000)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--cpu", type=int, default=0, help="strings of CPU baseline (0 = skip)")
-    ap.add_argument("--paths", default="mask,mask_flow,bytes_mask_flow,kind_mask_flow,offsets32_flow,spans32_flow,features32_flow,offsets,offsets32,spans,spans32,features,features32,utf8_mask,utf8_offsets,utf8_spans,"
+    ap.add_argument("--paths", default="mask,mask_flow,bytes_mask_flow,kind_mask_flow,offsets32_flow,spans32_flow,features32_flow,offsets,offsets32,spans,spans32,features,features32,utf8_mask,utf8_offsets,utf8_spans,utf8_features32,utf8_decode_features32,"
                                        "bytes_mask,bytes_offsets,bytes_spans,rules_mask,kind_mask,kind_offsets,kind_offsets32,"
                                        "kind_spans,kind_spans32")
     args = ap.parse_args()
@@ -210,6 +213,22 @@ def main():
     if "utf8_spans" in paths:
         run("utf8_spans", lambda: lib.latok_token_spans_utf8_batch(d_u8, d_boff, n, n8, d_counts, d_items, cap, C.byref(nout), D, None),
             lambda: n8 + csr + 8 * n + 16 * nout.value, "UTF-8 bytes + 8 B/string read; 8 B/string + 16 B/token written")
+    if "utf8_features32" in paths:
+        run("utf8_features32", lambda: lib.latok_token_features_utf8_batch(d_u8, d_boff, n, n8, d_counts, d_items, d_feat, cap, C.byref(nout), D32, None),
+            lambda: n8 + csr + 4 * n + (16 + 25) * nout.value,
+            "UTF-8 bytes + 8 B/string read (the input ONCE); 4 B/string + 41 B/token written (LATOK_OUT_INT32)")
+    if "utf8_decode_features32" in paths:
+        d_dec, d_decrow = lib.latok_dev_alloc(total * 4 + 64), lib.latok_dev_alloc((n + 1) * 8)
+        if not d_dec or not d_decrow:
+            raise RuntimeError(_lib.last_error())
+
+        def decode_features():
+            rc = lib.latok_utf8_decode_batch(d_u8, d_boff, n, n8, d_dec, total, d_decrow, C.byref(tcp), D, None)
+            return rc or lib.latok_token_features_batch(d_dec, d_decrow, n, total, d_counts, d_items, d_feat, cap, C.byref(nout), D32, None)
+        run("utf8_decode_features32", decode_features, lambda: n8 + csr + 4 * n + (16 + 25) * nout.value,
+            "UTF-8 bytes + 8 B/string read; 4 B/string + 41 B/token written (LATOK_OUT_INT32); the 4 B/char UTF-32 copy is not counted")
+        lib.latok_dev_free(d_dec)
+        lib.latok_dev_free(d_decrow)
     bwords = (n8 + 63) // 64
     if "bytes_mask" in paths:
         d_bbits = lib.latok_dev_alloc(bwords * 8 + 8)
