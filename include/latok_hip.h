@@ -279,8 +279,8 @@ int latok_rules_active(void);  /* 1 while custom tables are installed */
  *     streams are polled for up to 2 ms before the call sleeps on them (a sleeping wait returns ~15 us late).
  * Ordering between batches of one flow.  Every call is independent, as the reference's calls are -- batches that touch
  * disjoint memory overlap freely.  The library tracks the byte RANGE of every buffer a batch in flight reads (units, row
- * offsets) or writes (mask; for the compaction calls: records, counts, result words, feature sums) until the flow is next
- * idle.  A new batch that writes any byte a batch still in flight reads or writes, or reads one it writes -- whole buffer or
+ * offsets) or writes (mask; for the compaction calls: records, counts, result words, feature sums; for the code-point UTF-8
+ * calls at the end of this section also the code-point row offsets and all four result words) until the flow is next idle.  A new batch that writes any byte a batch still in flight reads or writes, or reads one it writes -- whole buffer or
  * partial overlap, however many other batches were submitted in between -- is ordered behind that batch (it is enqueued on that
  * batch's slot; if batches on both slots are in its way the call first waits for the flow to drain).  So reusing an output
  * buffer is always correct, it just does not overlap; callers that want the overlap alternate their buffers.
@@ -314,6 +314,35 @@ int latok_flow_token_spans(const void* units_dev, int kind, const int64_t* row_o
 /* featurize through the flow: latok_token_features_batch / _kind_batch (kind 4 / 1 / 2) with the same result words */
 int latok_flow_token_features(const void* units_dev, int kind, const int64_t* row_off_dev, int64_t n_str, int64_t total_chars,
                               void* counts_dev, void* spans4_dev, int8_t* features_dev, int64_t cap, int64_t* result_dev, int flags);
+/* UTF-8 in CODE-POINT units through the flow: what latok_split_mask_utf8_batch, latok_split_offsets_utf8_batch,
+ * latok_token_spans_utf8_batch and latok_token_features_utf8_batch report for the same batch (positions are code points of
+ * the decoded text, as the reference reports them), bit-identical, enqueued without waiting for anything: the code-point total
+ * stays on the device, where the stages behind the lead-byte scan read it.  Every pointer is a device address; utf8_dev
+ * 16-byte aligned; total_bytes < 0: read from byte_off (one small synchronous copy); batches of every size take this route.
+ *   result_dev: int64[4], 8-byte aligned, device-writable, read after latok_flow_wait:
+ *     result[0]  number of items (offsets / tokens); 0 for the mask form
+ *     result[1]  as above: low half = a string of >= 2^31 chars under LATOK_OUT_INT32, high half = the chained scan did
+ *                not complete (safe to repeat)
+ *     result[2]  code-point total of the batch (total_cps_out of the blocking call)
+ *     result[3]  nonzero = the batch holds MALFORMED UTF-8 that the byte-space model and the staged decoder read differently
+ *                (a continuation byte without a lead byte in the 3 bytes before it, or at the start of a string).  Then NO
+ *                record, count, mask word or row offset of this batch is valid (records and feature sums are not written at
+ *                all): resubmit the batch through the blocking _utf8_batch call, which has the staged decoder.  The flow
+ *                reports such input; it does not decode it.
+ *   Capacity: when result[0] exceeds the capacity no record is written and counts are valid.  Mask form: mask_dev holds
+ *     mask_cap_words words; ceil(total_bytes / 64) always suffice; when ceil(result[2] / 64) exceeds mask_cap_words no mask
+ *     word is written (row offsets are).  Bits of the last meaningful word above the total are zero.  cp_row_off_dev[n_str + 1].
+ *   n_str == 0 or total_bytes == 0: the result words, counts and row offsets are cleared on the slot's stream.
+ * The four result words, mask, row offsets, counts, records, feature sums and the inputs take part in the ordering rule. */
+int latok_flow_split_mask_utf8(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                               uint64_t* mask_dev, int64_t mask_cap_words, int64_t* cp_row_off_dev, int64_t* result_dev);
+int latok_flow_split_offsets_utf8(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                  void* counts_dev, void* offsets_dev, int64_t offsets_cap, int64_t* result_dev, int flags);
+int latok_flow_token_spans_utf8(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                void* counts_dev, void* spans_dev, int64_t spans_cap, int64_t* result_dev, int flags);
+int latok_flow_token_features_utf8(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                   void* counts_dev, void* spans4_dev, int8_t* features_dev, int64_t cap,
+                                   int64_t* result_dev, int flags);
 int latok_flow_wait(void);
 
 /* ---- measurement ----------------------------------------------------------------------------------------------- */

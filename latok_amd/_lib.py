@@ -92,6 +92,10 @@ SIGNATURES = {
     "latok_flow_split_offsets": (ci, [vp, ci, vp, i64, i64, vp, vp, i64, vp, ci]),
     "latok_flow_token_spans": (ci, [vp, ci, vp, i64, i64, vp, vp, i64, vp, ci]),
     "latok_flow_token_features": (ci, [vp, ci, vp, i64, i64, vp, vp, vp, i64, vp, ci]),
+    "latok_flow_split_mask_utf8": (ci, [vp, vp, i64, i64, vp, i64, vp, vp]),
+    "latok_flow_split_offsets_utf8": (ci, [vp, vp, i64, i64, vp, vp, i64, vp, ci]),
+    "latok_flow_token_spans_utf8": (ci, [vp, vp, i64, i64, vp, vp, i64, vp, ci]),
+    "latok_flow_token_features_utf8": (ci, [vp, vp, i64, i64, vp, vp, vp, i64, vp, ci]),
     "latok_flow_wait": (ci, []),
     "latok_bench_split_mask_flow_gated": (ci, [vp, vp, i64, i64, vp, vp, ci, vp, C.POINTER(C.c_float), C.POINTER(i64),
                                                C.POINTER(i64)]),

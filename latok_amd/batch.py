@@ -581,6 +581,41 @@ def flow_token_features(d_units, kind, d_row_off, n_str, total_chars, d_counts, 
                                              int(cap), d_result, flag32))
 
 
+def flow_split_mask_utf8(d_utf8, d_byte_off, n_str, total_bytes, d_mask, mask_cap_words, d_cp_row_off, d_result):
+    """Split mask of one device-resident UTF-8 batch in CODE-POINT units through the flow (``latok_flow_split_mask_utf8``):
+    what ``split_mask_utf8_batch`` reports (bit k = code point k, the reference's unit, latok.c:53-55,79) without a wait.
+    ``d_result`` = int64[4] the device can write, valid after ``flow_wait()``: [0] 0, [1] error word, [2] code-point total,
+    [3] nonzero = malformed UTF-8 -- nothing of the batch is valid, resubmit it through the blocking call."""
+    lib = _lib.ensure_init()
+    _lib.check(lib.latok_flow_split_mask_utf8(d_utf8, d_byte_off, int(n_str), int(total_bytes), d_mask, int(mask_cap_words),
+                                              d_cp_row_off, d_result))
+
+
+def flow_split_offsets_utf8(d_utf8, d_byte_off, n_str, total_bytes, d_counts, d_offsets, cap, d_result, dtype=np.int64):
+    """Boundary offsets in code-point units of one device-resident UTF-8 batch through the flow
+    (``latok_flow_split_offsets_utf8``).  ``d_result`` = int64[4]: item total, error word, code-point total, malformed flag."""
+    lib = _lib.ensure_init()
+    _, flag32 = _out_dtype(dtype)
+    _lib.check(lib.latok_flow_split_offsets_utf8(d_utf8, d_byte_off, int(n_str), int(total_bytes), d_counts, d_offsets, int(cap),
+                                                 d_result, flag32))
+
+
+def flow_token_spans_utf8(d_utf8, d_byte_off, n_str, total_bytes, d_counts, d_spans, cap, d_result, dtype=np.int64):
+    """Token spans in code-point units of one device-resident UTF-8 batch through the flow (``latok_flow_token_spans_utf8``)."""
+    lib = _lib.ensure_init()
+    _, flag32 = _out_dtype(dtype)
+    _lib.check(lib.latok_flow_token_spans_utf8(d_utf8, d_byte_off, int(n_str), int(total_bytes), d_counts, d_spans, int(cap),
+                                               d_result, flag32))
+
+
+def flow_token_features_utf8(d_utf8, d_byte_off, n_str, total_bytes, d_counts, d_spans4, d_features, cap, d_result, dtype=np.int64):
+    """featurize in code-point units of one device-resident UTF-8 batch through the flow (``latok_flow_token_features_utf8``)."""
+    lib = _lib.ensure_init()
+    _, flag32 = _out_dtype(dtype)
+    _lib.check(lib.latok_flow_token_features_utf8(d_utf8, d_byte_off, int(n_str), int(total_bytes), d_counts, d_spans4, d_features,
+                                                  int(cap), d_result, flag32))
+
+
 def flow_wait():
     """Block until every batch submitted with ``flow_split_mask`` on the current context is complete."""
     _lib.check(_lib.ensure_init().latok_flow_wait())

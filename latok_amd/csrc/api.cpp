@@ -148,7 +148,7 @@ constexpr int64_t kSmallStrings = 16384;
 
 // The input form of a batch as the tile kernel reads it: UTF-32 code points, PEP 393 kind 1 / 2 code units (positions are
 // chars) or UTF-8 bytes (positions are bytes).  Code-point positions of a UTF-8 batch are not a kernel form: compact_common
-// and latok_split_mask_utf8_batch reach them through byte space or the decoder.
+// and latok_split_mask_utf8_batch reach them through byte space or the decoder, flow_submit_utf8 through byte space alone.
 enum class Form { Utf32, Latin1, Ucs2, Utf8 };
 struct Input {
     const void* p = nullptr;
@@ -171,6 +171,9 @@ struct Workspace {
     DevBuf summ, seg_agg, fix_count, tile_first;   // tile stage (run_pipeline)
     DevBuf bits, space, kept, wcnt, wpref, bases, scalar, chain, chain_ctl;   // compaction passes (enqueue_compaction_dev)
     DevBuf codes, widened;                          // featurize: rule code of every char, PEP 393 units widened to UTF-32
+    // code-point results of a UTF-8 batch in a flow (flow_submit_utf8): lead-byte mask and SPACE plane over the bytes, the packed
+    // code-point masks, the code-point row offsets (the blocking calls keep theirs in the context: Ctx::u_lead ..)
+    DevBuf lead, bspace, cpbits, cpspace, cprow;
     // the single-pass scan of k_word_counts_scan keeps its look-back state (chain: per workgroup, chain_ctl: {ticket
     // counter}) between launches: entries carry an epoch, so the array is cleared only when it is (re)allocated or when the
     // 18-bit epoch wraps (next_scan_epoch); *_seen = DevBuf::gen of the allocations it was last cleared in
@@ -178,7 +181,7 @@ struct Workspace {
     bool chain_ready = false;
     void release() {
         for (DevBuf* b : {&summ, &seg_agg, &fix_count, &tile_first, &bits, &space, &kept, &wcnt, &wpref, &bases, &scalar, &chain,
-                          &chain_ctl, &codes, &widened})
+                          &chain_ctl, &codes, &widened, &lead, &bspace, &cpbits, &cpspace, &cprow})
             b->release();
         scan_epoch = chain_seen = chain_ctl_seen = 0;
         chain_ready = false;
@@ -189,10 +192,12 @@ struct WsNeed {
     size_t bytes;   // 0: the batch does not use the buffer
 };
 constexpr int kTileNeeds = 4;   // the first entries of ws_needs: the tile stage
-constexpr int kWsNeeds = 15;
+constexpr int kWsNeeds = 20;
 // The one sizing rule of a workspace: every buffer a batch of `units` positions uses and its byte size.  token spans (spans)
 // add the SPACE and kept planes, featurize (feats) the code bytes, and narrow units read by featurize (widen) a UTF-32 copy.
-static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, bool spans, bool feats, bool widen) {
+// cp_rows > 0: `units` UTF-8 bytes whose results are reported in code points (cp_rows = n_str + 1): every buffer is sized by the
+// byte count, which bounds the code-point count.
+static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, bool spans, bool feats, bool widen, int64_t cp_rows = 0) {
     const size_t t = (size_t)std::max<int64_t>((units + latok::kTile - 1) / latok::kTile, 1);
     const size_t words = (size_t)((units + 63) / 64), c_tiles = (words + 63) / 64;
     return {{{&w.summ, t * 16},
@@ -211,7 +216,12 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, bool s
              {&w.chain, (size_t)latok::count_blocks((int64_t)words) * 8 + 64},
              {&w.chain_ctl, 64},
              {&w.codes, feats ? (size_t)units + latok::kTile + 256 : 0},   // read (never used) up to a tile behind the last char
-             {&w.widened, widen ? (size_t)units * 4 + 16 : 0}}};
+             {&w.widened, widen ? (size_t)units * 4 + 16 : 0},
+             {&w.lead, cp_rows > 0 ? words * 8 + 8 : 0},
+             {&w.bspace, cp_rows > 0 && spans ? words * 8 + 8 : 0},
+             {&w.cpbits, cp_rows > 0 ? words * 8 + 8 : 0},
+             {&w.cpspace, cp_rows > 0 && spans ? words * 8 + 8 : 0},
+             {&w.cprow, cp_rows > 0 ? (size_t)cp_rows * 8 : 0}}};
 }
 static int ws_ensure(const WsNeed* needs, int n) {
     for (int i = 0; i < n; ++i) {
@@ -906,7 +916,7 @@ static int decode_utf8_to_workspace(Ctx& g, const Batch& b, bool dev, hipStream_
 static int enqueue_features(Ctx& g, const uint8_t* d_codes, const int64_t* d_row, int64_t n_str, int64_t total, const uint64_t* d_bits,
                             const uint64_t* d_space, const uint64_t* d_kept, const int64_t* d_rank, const int64_t* d_tile_cnt,
                             const uint16_t* d_pref, const int64_t* d_tile_first, void* d_spans4, int8_t* d_feat, bool out32,
-                            const int64_t* d_n_tokens, int64_t cap, hipStream_t st, latok::DoneSignal done) {
+                            const int64_t* d_n_tokens, int64_t cap, hipStream_t st, latok::DoneSignal done, latok::DeviceTotal dt) {
     latok::FeatParams F;
     F.codes = d_codes;
     F.row_off = d_row;
@@ -926,6 +936,7 @@ static int enqueue_features(Ctx& g, const uint8_t* d_codes, const int64_t* d_row
     F.n_tokens_dev = d_n_tokens;
     F.cap = cap;
     F.done = done;
+    F.dt = dt;
     HIP_TRY(latok::launch_features_tiles(F, g.n_cu, st));
     return LATOK_OK;
 }
@@ -960,6 +971,10 @@ struct Compaction {
     const uint64_t* pre_bits = nullptr;    // the two bitmasks are already there (code-point masks packed from byte space:
     const uint64_t* pre_space = nullptr;   // cp_masks_via_bytes): only the string index is launched
     const uint8_t* pre_codes = nullptr;    // featurize: the rule codes too (k_lead_codes), padded to one tile + 256 B behind `total`
+    // a code-point batch of a flow (flow_submit_utf8): b.total is the BYTE count, an upper bound; the code-point total is the word
+    // dt.total, which the lead-byte scan writes on the same stream, and dt.gate its malformed-input flag.  The batch's result words
+    // (p_tot[0..3]) were cleared by the caller.
+    latok::DeviceTotal dt{nullptr, nullptr};
     hipStream_t st = nullptr;
 };
 
@@ -999,7 +1014,8 @@ static int enqueue_compaction_dev(Ctx& g, Workspace& w, const Compaction& c) {
     uint8_t* d_codes = nullptr;
     if (c.feats && c.pre_codes) {   // packed before (every char's code is there already): only the padding behind the last char
         d_codes = const_cast<uint8_t*>(c.pre_codes);
-        HIP_TRY(hipMemsetAsync(d_codes + total, 0, (size_t)latok::kTile + 256, st));
+        if (c.dt.total) HIP_TRY(latok::launch_pad_codes(d_codes, c.dt.total, total, st));   // (behind a total the host does not know)
+        else HIP_TRY(hipMemsetAsync(d_codes + total, 0, (size_t)latok::kTile + 256, st));
     } else if (c.feats) {   // the tile kernel leaves the rule code of every char: 1 B/char for k_features_tiles instead of 4 B/char + tables
         d_codes = (uint8_t*)w.codes.p;
         const size_t tail0 = (size_t)total & ~(size_t)(latok::kTile - 1);
@@ -1013,7 +1029,7 @@ static int enqueue_compaction_dev(Ctx& g, Workspace& w, const Compaction& c) {
     if (c.h_tot) {   // pinned pair of the context's own calls: cleared by the host
         c.h_tot[0] = 0;
         c.h_tot[1] = 0;
-    } else {         // a flow's result words live wherever the caller put them: cleared on the stream
+    } else if (!c.dt.total) {   // a flow's result words live wherever the caller put them: cleared on the stream
         HIP_TRY(hipMemsetAsync(c.p_tot, 0, 16, st));
     }
     const int64_t* d_row = c.b.row;
@@ -1021,14 +1037,14 @@ static int enqueue_compaction_dev(Ctx& g, Workspace& w, const Compaction& c) {
     int64_t* d_total = (int64_t*)w.scalar.p;
     int* d_err = (int*)(c.p_tot + 1);
     HIP_TRY(latok::launch_word_counts_scan(c.spans, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank,
-                                           (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total, c.p_tot, d_err + 1, st));   // (the scan's own flag: the upper half of the pinned word)
+                                           (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total, c.p_tot, d_err + 1, st, c.dt));   // (the scan's own flag: the upper half of the pinned word)
     if (c.feats) {   // spans and sums come from one kernel
-        HIP_TRY(latok::launch_string_counts(c.o32, d_item_mask, d_rank, d_pref, d_row, n_str, total, d_total, c.counts, d_err, st));
+        HIP_TRY(latok::launch_string_counts(c.o32, d_item_mask, d_rank, d_pref, d_row, n_str, total, d_total, c.counts, d_err, st, c.dt));
         return enqueue_features(g, d_codes, d_row, n_str, total, d_bits, d_space, d_kept, d_rank, d_tcnt, d_pref, d_tile_first, c.items,
-                                c.feat, c.o32, d_total, c.cap, st, c.done);
+                                c.feat, c.o32, d_total, c.cap, st, c.done, c.dt);
     }
     HIP_TRY(latok::launch_counts_scatter(c.spans ? 1 : 0, c.o32, d_bits, d_space, d_item_mask, d_rank, d_tcnt, d_pref, words, total, d_row,
-                                         n_str, d_tile_first, c.items, d_total, c.cap, c.counts, d_err, st, c.done));
+                                         n_str, d_tile_first, c.items, d_total, c.cap, c.counts, d_err, st, c.done, c.dt));
     return LATOK_OK;
 }
 
@@ -2343,6 +2359,213 @@ int latok_flow_token_features(const void* units_dev, int kind, const int64_t* ro
                               void* counts_dev, void* spans4_dev, int8_t* features_dev, int64_t cap, int64_t* result_dev, int flags) {
     return flow_compact_entry(true, true, units_dev, kind, row_off_dev, n_str, total_chars, counts_dev, spans4_dev, features_dev, cap,
                               result_dev, flags);
+}
+// ---- code-point results of UTF-8 batches in a flow ---------------------------------------------------------------------------
+// The blocking calls (cp_masks_via_bytes) wait for the host after the lead-byte scan: the host reads the code-point total and
+// the malformed-input flag and sizes everything downstream by value.  A flow batch may not wait, so here (shape 1 of DESIGN.md
+// section 7, "device-resident total") the launches behind the scan are sized by the BYTE count -- a batch has at most one char
+// per byte -- and read the code-point total from the word the scan wrote (latok::DeviceTotal); the malformed-input flag lands in
+// result[3], gates the records and feature sums on the device and is read by the caller after latok_flow_wait.  The lead-byte
+// mask, the byte-space SPACE plane, the packed code-point masks, the code-point row offsets and the rule codes are buffers of
+// the slot's workspace.
+enum { kU8Mask = 0, kU8Offsets = 1, kU8Spans = 2, kU8Feats = 3 };
+struct Utf8Flow {
+    int what = kU8Mask;
+    const uint8_t* u8 = nullptr;
+    const int64_t* boff = nullptr;
+    int64_t n_str = 0, total_bytes = 0;
+    uint64_t* mask = nullptr;     // kU8Mask
+    int64_t mask_cap = 0;
+    int64_t* cp_row = nullptr;
+    void* counts = nullptr;       // the others
+    void* items = nullptr;
+    int8_t* feat = nullptr;
+    int64_t cap = 0;
+    int64_t* result = nullptr;
+    bool o32 = false;
+};
+constexpr int kU8FlowRanges = 8;
+// every range of caller memory the batch touches, outputs first (what flow_hazards.h orders it by); returns their number
+static int utf8_flow_ranges(const Utf8Flow& a, latok::FlowRange* r) {
+    const size_t rec = a.o32 ? 4 : 8, fields = a.what == kU8Feats ? 4 : (a.what == kU8Spans ? 2 : 1);
+    const size_t n_str = (size_t)std::max<int64_t>(a.n_str, 0), bytes = (size_t)std::max<int64_t>(a.total_bytes, 0);
+    const size_t cap = (size_t)std::max<int64_t>(a.cap, 0);
+    int n = 0;
+    r[n++] = latok::flow_range(a.result, 32, true);
+    if (a.what == kU8Mask) {
+        const int64_t words_b = (int64_t)((bytes + 63) / 64);
+        r[n++] = latok::flow_range(a.mask, (size_t)std::max<int64_t>(std::min(a.mask_cap, words_b), 0) * 8, true);
+        r[n++] = latok::flow_range(a.cp_row, n_str ? (n_str + 1) * 8 : 0, true);
+    } else {
+        r[n++] = latok::flow_range(a.counts, n_str * rec, true);
+        r[n++] = latok::flow_range(a.items, bytes ? cap * fields * rec : 0, true);
+        if (a.what == kU8Feats) r[n++] = latok::flow_range(a.feat, bytes ? cap * LATOK_FEATURE_COUNT : 0, true);
+    }
+    r[n++] = latok::flow_range(a.u8, bytes, false);
+    r[n++] = latok::flow_range(a.boff, n_str ? (n_str + 1) * 8 : 0, false);
+    return n;
+}
+
+/* test hook (not part of the ABI; needs no device): the ranges a code-point UTF-8 flow batch notes, in the form
+ * latok_debug_flow_route takes them.  what: 0 mask, 1 offsets, 2 token spans, 3 featurize; addr[8] = {utf8, byte_off, mask or
+ * counts, cp_row_off or records, features, result, 0, 0}; cap = mask_cap_words or the record capacity.  Returns the number of
+ * ranges written to lo / bytes / is_write (at most n_max), < 0 on a bad argument. */
+extern "C" int latok_debug_flow_utf8_ranges(int what, const uint64_t* addr, int64_t n_str, int64_t total_bytes, int64_t cap, int flags,
+                                            uint64_t* lo, uint64_t* bytes, int* is_write, int n_max) {
+    if (what < kU8Mask || what > kU8Feats || !addr || !lo || !bytes || !is_write) return fail(LATOK_ERR_INVALID, "bad argument");
+    Utf8Flow a;
+    a.what = what;
+    a.u8 = (const uint8_t*)(uintptr_t)addr[0];
+    a.boff = (const int64_t*)(uintptr_t)addr[1];
+    a.n_str = n_str;
+    a.total_bytes = total_bytes;
+    if (what == kU8Mask) {
+        a.mask = (uint64_t*)(uintptr_t)addr[2];
+        a.cp_row = (int64_t*)(uintptr_t)addr[3];
+        a.mask_cap = cap;
+    } else {
+        a.counts = (void*)(uintptr_t)addr[2];
+        a.items = (void*)(uintptr_t)addr[3];
+        a.feat = (int8_t*)(uintptr_t)addr[4];
+        a.cap = cap;
+    }
+    a.result = (int64_t*)(uintptr_t)addr[5];
+    a.o32 = (flags & LATOK_OUT_INT32) != 0;
+    latok::FlowRange r[kU8FlowRanges];
+    const int n = utf8_flow_ranges(a, r);
+    if (n > n_max) return fail(LATOK_ERR_INVALID, "need room for %d ranges", n);
+    for (int i = 0; i < n; ++i) {
+        lo[i] = (uint64_t)r[i].lo;
+        bytes[i] = (uint64_t)(r[i].hi - r[i].lo);
+        is_write[i] = r[i].write ? 1 : 0;
+    }
+    return n;
+}
+
+static int flow_submit_utf8(Ctx& g, const Utf8Flow& a) {
+    int rc = flow_setup(g);
+    if (rc) return rc;
+    if (!a.result) return fail(LATOK_ERR_INVALID, "NULL result pointer");
+    if (((uintptr_t)a.result & 7) != 0) return fail(LATOK_ERR_INVALID, "result pointer must be 8-byte aligned");
+    if (a.n_str < 0) return fail(LATOK_ERR_INVALID, "n_str must be >= 0");
+    if (a.cap < 0 || a.mask_cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
+    const bool mask = a.what == kU8Mask, spans = a.what >= kU8Spans, feats = a.what == kU8Feats;
+    const int64_t n_str = a.n_str, total_bytes = a.total_bytes;
+    const size_t rec = a.o32 ? 4 : 8;
+    latok::FlowRange r[kU8FlowRanges];
+    const int n_r = utf8_flow_ranges(a, r);
+    int slot = 0;
+    if (n_str == 0 || total_bytes <= 0) {   // nothing to launch: no item, no char; counts and row offsets of empty strings are zero
+        if (n_str > 0 && (mask ? !a.cp_row : !a.counts)) return fail(LATOK_ERR_INVALID, "NULL buffer");
+        if ((rc = flow_pick(g, r, n_r, &slot))) return rc;
+        g.flow_held.note(slot, r, n_r);
+        HIP_TRY(hipMemsetAsync(a.result, 0, 32, g.flow[slot].st));
+        if (n_str > 0 && mask) HIP_TRY(hipMemsetAsync(a.cp_row, 0, (size_t)(n_str + 1) * 8, g.flow[slot].st));
+        if (n_str > 0 && !mask) HIP_TRY(hipMemsetAsync(a.counts, 0, (size_t)n_str * rec, g.flow[slot].st));
+        return LATOK_OK;
+    }
+    if (!a.u8 || !a.boff) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (((uintptr_t)a.u8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    const int64_t words_b = (total_bytes + 63) / 64, c_tiles = (words_b + 63) / 64;
+    if (mask) {
+        if (!a.cp_row || (!a.mask && a.mask_cap > 0)) return fail(LATOK_ERR_INVALID, "NULL buffer");
+        if (((uintptr_t)a.mask & 7) != 0 || ((uintptr_t)a.cp_row & 7) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    } else {
+        if (!a.counts || ((!a.items || (feats && !a.feat)) && a.cap > 0)) return fail(LATOK_ERR_INVALID, "NULL buffer");
+        if (((uintptr_t)a.items & 15) != 0 || ((uintptr_t)a.counts & (rec - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    }
+    if ((rc = flow_pick(g, r, n_r, &slot))) return rc;
+    Ctx::FlowSlot& f = g.flow[slot];
+    Workspace& w = f.ws;
+    if ((rc = flow_reserve(g, ws_needs(w, total_bytes, spans, feats, false, n_str + 1).data(), kWsNeeds))) return rc;
+    g.flow_held.note(slot, r, n_r);   // before anything is enqueued (flow_begin)
+    ++g.flow_seq;
+    const hipStream_t st = f.st;
+    HIP_TRY(hipMemsetAsync(a.result, 0, 32, st));
+    unsigned epoch = 0;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    uint64_t* d_bmask = (uint64_t*)w.bits.p;
+    uint64_t* d_lead = (uint64_t*)w.lead.p;
+    uint64_t* d_bspace = spans ? (uint64_t*)w.bspace.p : nullptr;
+    Pipe p;
+    p.b = Batch{Input{a.u8, Form::Utf8}, a.boff, n_str, total_bytes};
+    p.bits = d_bmask;
+    p.space = d_bspace;
+    p.lead = d_lead;
+    p.lead_pref = (uint16_t*)w.wpref.p;
+    p.lead_cnt = (int64_t*)w.wcnt.p;
+    p.st = st;
+    if ((rc = run_pipeline(g, w, p))) return rc;
+    // the code-point total: word 1 of the workspace's scalars (word 0 is the item total of the second scan) and result[2]
+    int64_t* d_total_cps = (int64_t*)w.scalar.p + 1;
+    int* d_err = (int*)(a.result + 1);
+    int* d_odd = (int*)(a.result + 3);
+    HIP_TRY(latok::launch_tile_scan((const int64_t*)w.wcnt.p, c_tiles, (int64_t*)w.bases.p, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p,
+                                    epoch, d_total_cps, a.result + 2, d_err + 1, st));
+    uint64_t* d_cpbits = mask ? a.mask : (uint64_t*)w.cpbits.p;
+    uint64_t* d_cpspace = spans ? (uint64_t*)w.cpspace.p : nullptr;
+    int64_t* d_cp_row = mask ? a.cp_row : (int64_t*)w.cprow.p;
+    HIP_TRY(latok::launch_lead_compress(d_bmask, d_bspace, d_lead, (const int64_t*)w.bases.p, (const int64_t*)w.wcnt.p,
+                                        (const uint16_t*)w.wpref.p, words_b, total_bytes, a.boff, n_str, d_total_cps, d_cpbits, d_cpspace,
+                                        mask ? std::min(a.mask_cap, words_b) : words_b, d_cp_row, d_odd, st));
+    if (mask) return LATOK_OK;
+    if (feats)
+        HIP_TRY(latok::launch_lead_codes(a.u8, total_bytes, d_lead, (const int64_t*)w.bases.p, (const int64_t*)w.wcnt.p,
+                                         (const uint16_t*)w.wpref.p, words_b, (const uint8_t*)g.tb6rule.p, (uint8_t*)w.codes.p, g.n_cu, st));
+    Compaction k;
+    k.b = Batch{Input{}, d_cp_row, n_str, total_bytes};   // (total: the upper bound; the stages read k.dt.total)
+    k.spans = spans;
+    k.feats = feats;
+    k.o32 = a.o32;
+    k.counts = a.counts;
+    k.items = a.items;
+    k.feat = a.feat;
+    k.cap = a.cap;
+    k.p_tot = a.result;
+    k.pre_bits = d_cpbits;
+    k.pre_space = d_cpspace;
+    k.pre_codes = feats ? (const uint8_t*)w.codes.p : nullptr;
+    k.dt = latok::DeviceTotal{d_total_cps, d_odd};
+    k.st = st;
+    return enqueue_compaction_dev(g, w, k);
+}
+static int flow_utf8_entry(Utf8Flow a, int flags) {
+    LATOK_ENTER();
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    a.o32 = (flags & LATOK_OUT_INT32) != 0;
+    if (a.total_bytes < 0 && (rc = resolve_total_device(a.boff, a.n_str, &a.total_bytes, g.stream))) return rc;
+    return flow_submit_utf8(g, a);
+}
+int latok_flow_split_mask_utf8(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                               uint64_t* mask_dev, int64_t mask_cap_words, int64_t* cp_row_off_dev, int64_t* result_dev) {
+    Utf8Flow a;
+    a.what = kU8Mask; a.u8 = utf8_dev; a.boff = byte_off_dev; a.n_str = n_str; a.total_bytes = total_bytes;
+    a.mask = mask_dev; a.mask_cap = mask_cap_words; a.cp_row = cp_row_off_dev; a.result = result_dev;
+    return flow_utf8_entry(a, 0);
+}
+static int flow_utf8_compact_entry(int what, const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                   void* counts_dev, void* items_dev, int8_t* features_dev, int64_t cap, int64_t* result_dev, int flags) {
+    Utf8Flow a;
+    a.what = what; a.u8 = utf8_dev; a.boff = byte_off_dev; a.n_str = n_str; a.total_bytes = total_bytes;
+    a.counts = counts_dev; a.items = items_dev; a.feat = features_dev; a.cap = cap; a.result = result_dev;
+    return flow_utf8_entry(a, flags);
+}
+int latok_flow_split_offsets_utf8(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                  void* counts_dev, void* offsets_dev, int64_t offsets_cap, int64_t* result_dev, int flags) {
+    return flow_utf8_compact_entry(kU8Offsets, utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, offsets_dev, nullptr, offsets_cap,
+                                   result_dev, flags);
+}
+int latok_flow_token_spans_utf8(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                void* counts_dev, void* spans_dev, int64_t spans_cap, int64_t* result_dev, int flags) {
+    return flow_utf8_compact_entry(kU8Spans, utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, spans_dev, nullptr, spans_cap, result_dev,
+                                   flags);
+}
+int latok_flow_token_features_utf8(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                   void* counts_dev, void* spans4_dev, int8_t* features_dev, int64_t cap, int64_t* result_dev, int flags) {
+    return flow_utf8_compact_entry(kU8Feats, utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, spans4_dev, features_dev, cap,
+                                   result_dev, flags);
 }
 int latok_flow_wait(void) {
     LATOK_ENTER();

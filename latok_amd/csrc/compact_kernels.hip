@@ -78,7 +78,14 @@ __device__ __forceinline__ void word_counts_tile(const uint64_t* __restrict__ bi
 template <bool SPANS>
 __global__ __launch_bounds__(256) void k_word_counts(const uint64_t* __restrict__ bits, const uint64_t* __restrict__ space,
                                                      int64_t n_words, int64_t total, uint64_t* __restrict__ kept_out,
-                                                     int64_t* __restrict__ tile_cnt, uint16_t* __restrict__ word_pref) {
+                                                     int64_t* __restrict__ tile_cnt, uint16_t* __restrict__ word_pref,
+                                                     const int64_t* __restrict__ total_dev) {
+    // total_dev (or NULL): the batch's size is a word in device memory that an earlier launch of the stream wrote; the grid was
+    // sized for an upper bound (n_words), and tiles behind the real size do nothing (DeviceTotal, kernels.h)
+    if (total_dev) {
+        total = device_total(total_dev, total);
+        n_words = (total + 63) >> 6;
+    }
     word_counts_tile<SPANS>(bits, space, n_words, total, kept_out, tile_cnt, word_pref,
                             ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, threadIdx.x & 63);
 }
@@ -105,7 +112,16 @@ __device__ __forceinline__ void chain_publish(unsigned long long* slot, unsigned
 __global__ __launch_bounds__(kChainBlock) void k_scan_chained(const int64_t* __restrict__ in, int64_t n, int64_t* __restrict__ out,
                                                               unsigned long long* __restrict__ chain, unsigned* __restrict__ ticket,
                                                               unsigned epoch, unsigned n_blocks, int64_t* __restrict__ total_out,
-                                                              int64_t* __restrict__ total_host, int* __restrict__ err) {
+                                                              int64_t* __restrict__ total_host, int* __restrict__ err,
+                                                              const int64_t* __restrict__ units_dev) {
+    // units_dev (or NULL): the number of counts is not known to the host -- it is ceil(*units_dev / kTile), at most the `n` the
+    // grid was sized for.  The chain terminates for every such size, 0 and exact multiples of kChainChunk included, because
+    // the size only decides what a workgroup READS, never whether it takes part: all n_blocks launched workgroups take a
+    // ticket, publish their aggregate BEFORE they wait for anything (a workgroup whose chunk lies behind the real size
+    // publishes 0), and look back only at smaller tickets, whose holders are therefore running or done.  No workgroup leaves
+    // without publishing and none waits for one that was not launched; the holder of ticket n_blocks - 1 -- n_blocks is the
+    // launched grid, not a function of the size -- writes the total (0 for an empty batch) and re-arms the ticket counter.
+    if (units_dev) n = min(n, (device_total(units_dev, n * kTile) + kTile - 1) / kTile);
     __shared__ unsigned s_ticket;
     __shared__ long long s_wave_tot[kChainBlock / 64];
     __shared__ long long s_prefix;
@@ -206,7 +222,9 @@ template <typename OUT>
 __global__ __launch_bounds__(256) void k_string_counts(const uint64_t* __restrict__ mask, const int64_t* __restrict__ tile_rank,
                                                        const uint16_t* __restrict__ word_pref, const int64_t* __restrict__ row_off,
                                                        int64_t n_str, int64_t total, const int64_t* __restrict__ n_items,
-                                                       OUT* __restrict__ counts, int* __restrict__ err) {
+                                                       OUT* __restrict__ counts, int* __restrict__ err,
+                                                       const int64_t* __restrict__ total_dev) {
+    if (total_dev) total = device_total(total_dev, total);
     string_counts_role<OUT>((int64_t)blockIdx.x * blockDim.x + threadIdx.x, mask, tile_rank, word_pref, row_off, n_str, total, *n_items,
                             counts, err);
 }
@@ -460,9 +478,14 @@ __global__ __launch_bounds__(scatter_waves(KIND) * 64) void k_counts_scatter(
     const int64_t* __restrict__ tile_rank, const int64_t* __restrict__ tile_cnt, const uint16_t* __restrict__ word_pref,
     int64_t n_words, int64_t total, const int64_t* __restrict__ row_off, int64_t n_str,
     const int64_t* __restrict__ tile_first, OUT* __restrict__ out, const int64_t* __restrict__ n_items_dev, int64_t cap,
-    OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, DoneSignal done) {
-    counts_scatter_block<KIND, OUT>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str, tile_first,
-                                    out, n_items_dev, cap, counts, n_scatter_blocks, err, blockIdx.x);
+    OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, DoneSignal done, DeviceTotal dt) {
+    if (dt.total) {   // (uniform) the size from device memory; the records are not written for a batch reported as malformed
+        total = device_total(dt.total, total);
+        n_words = (total + 63) >> 6;
+    }
+    if (!(dt.gate && *dt.gate != 0 && blockIdx.x < n_scatter_blocks))   // (the counts role still runs: counts may be written)
+        counts_scatter_block<KIND, OUT>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str,
+                                        tile_first, out, n_items_dev, cap, counts, n_scatter_blocks, err, blockIdx.x);
     signal_block_done(done);   // (pinned outputs of a small host batch: the host polls the completion word)
 }
 
@@ -830,7 +853,19 @@ hipError_t launch_tile_scan(const int64_t* tile_cnt, int64_t n_tiles, int64_t* t
     if (n_tiles <= 0) return hipSuccess;
     const unsigned n_blocks = (unsigned)((n_tiles + kChainChunk - 1) / kChainChunk);
     hipLaunchKernelGGL(k_scan_chained, dim3(n_blocks), dim3(kChainBlock), 0, st, tile_cnt, n_tiles, tile_rank, chain, ticket, epoch,
-                       n_blocks, total_dev, total_host, err);
+                       n_blocks, total_dev, total_host, err, (const int64_t*)nullptr);
+    return hipGetLastError();
+}
+
+// The zero padding k_features_tiles reads behind the last rule code (one tile + 256 B), for a batch whose code-point total only
+// the device knows: written at codes[*total_dev ..) by this launch instead of a memset the host would have to place.
+__global__ __launch_bounds__(256) void k_pad_codes(uint8_t* __restrict__ codes, const int64_t* __restrict__ total_dev, int64_t bound,
+                                                   int n_pad) {
+    const int64_t total = device_total(total_dev, bound);
+    for (int i = threadIdx.x; i < n_pad; i += 256) codes[total + i] = 0;
+}
+hipError_t launch_pad_codes(uint8_t* codes, const int64_t* total_dev, int64_t bound, hipStream_t st) {
+    hipLaunchKernelGGL(k_pad_codes, dim3(1), dim3(256), 0, st, codes, total_dev, bound, kTile + 256);
     return hipGetLastError();
 }
 
@@ -840,29 +875,29 @@ int64_t count_blocks(int64_t n_words) { return n_words > 0 ? ((n_words + 63) / 6
 hipError_t launch_word_counts_scan(bool spans, const uint64_t* bits, const uint64_t* space, int64_t n_words, int64_t total,
                                    uint64_t* kept, int64_t* tile_cnt, uint16_t* word_pref, int64_t* tile_rank,
                                    unsigned long long* chain, unsigned* ticket, unsigned epoch, int64_t* total_dev,
-                                   int64_t* total_host, int* err, hipStream_t st) {
+                                   int64_t* total_host, int* err, hipStream_t st, DeviceTotal dt) {
     if (n_words <= 0) return hipSuccess;
     const int64_t n_tiles = (n_words + 63) / 64;
     const dim3 grid((unsigned)((n_tiles + 3) / 4)), block(256);
-    if (spans) hipLaunchKernelGGL((k_word_counts<true>), grid, block, 0, st, bits, space, n_words, total, kept, tile_cnt, word_pref);
-    else hipLaunchKernelGGL((k_word_counts<false>), grid, block, 0, st, bits, space, n_words, total, kept, tile_cnt, word_pref);
+    if (spans) hipLaunchKernelGGL((k_word_counts<true>), grid, block, 0, st, bits, space, n_words, total, kept, tile_cnt, word_pref, dt.total);
+    else hipLaunchKernelGGL((k_word_counts<false>), grid, block, 0, st, bits, space, n_words, total, kept, tile_cnt, word_pref, dt.total);
     const unsigned n_blocks = (unsigned)count_blocks(n_words);
     hipLaunchKernelGGL(k_scan_chained, dim3(n_blocks), dim3(kChainBlock), 0, st, tile_cnt, n_tiles, tile_rank, chain, ticket, epoch,
-                       n_blocks, total_dev, total_host, err);
+                       n_blocks, total_dev, total_host, err, dt.total);
     return hipGetLastError();
 }
 
 hipError_t launch_string_counts(bool out32, const uint64_t* mask, const int64_t* tile_rank, const uint16_t* word_pref,
                                 const int64_t* row_off, int64_t n_str, int64_t total, const int64_t* n_items, void* counts, int* err,
-                                hipStream_t st) {
+                                hipStream_t st, DeviceTotal dt) {
     if (n_str <= 0) return hipSuccess;
     const dim3 grid((unsigned)((n_str + 255) / 256)), block(256);
     if (out32)
         hipLaunchKernelGGL((k_string_counts<int32_t>), grid, block, 0, st, mask, tile_rank, word_pref, row_off, n_str, total, n_items,
-                           (int32_t*)counts, err);
+                           (int32_t*)counts, err, dt.total);
     else
         hipLaunchKernelGGL((k_string_counts<int64_t>), grid, block, 0, st, mask, tile_rank, word_pref, row_off, n_str, total, n_items,
-                           (int64_t*)counts, err);
+                           (int64_t*)counts, err, dt.total);
     return hipGetLastError();
 }
 
@@ -871,14 +906,14 @@ static hipError_t launch_counts_scatter_t(const uint64_t* bits, const uint64_t* 
                                           const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref,
                                           int64_t n_words, int64_t total, const int64_t* row_off, int64_t n_str,
                                           const int64_t* tile_first, void* out, const int64_t* n_items_dev, int64_t cap,
-                                          void* counts, int* err, hipStream_t st, DoneSignal done) {
+                                          void* counts, int* err, hipStream_t st, DoneSignal done, DeviceTotal dt) {
     const int64_t per_block = (int64_t)scatter_waves(KIND) * 64;
     const unsigned nb_scatter = out ? (unsigned)((n_words + per_block - 1) / per_block) : 0u;
     const unsigned nb_counts = counts ? (unsigned)((n_str + 255) / 256) : 0u;
     if (nb_scatter + nb_counts == 0) return hipSuccess;
     hipLaunchKernelGGL((k_counts_scatter<KIND, OUT>), dim3(nb_scatter + nb_counts), dim3(scatter_waves(KIND) * 64), 0, st, bits, space,
                        item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str, tile_first, (OUT*)out, n_items_dev,
-                       cap, (OUT*)counts, nb_scatter, err, done);
+                       cap, (OUT*)counts, nb_scatter, err, done, dt);
     return hipGetLastError();
 }
 
@@ -886,10 +921,11 @@ static hipError_t launch_counts_scatter_t(const uint64_t* bits, const uint64_t* 
 hipError_t launch_counts_scatter(int kind, bool out32, const uint64_t* bits, const uint64_t* space, const uint64_t* item_mask,
                                  const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words,
                                  int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,
-                                 const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st, DoneSignal done) {
+                                 const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st, DoneSignal done,
+                                 DeviceTotal dt) {
     if (n_words <= 0) return hipSuccess;
 #define LATOK_CS(K, T) launch_counts_scatter_t<K, T>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, \
-                                                     n_str, tile_first, out, n_items_dev, cap, counts, err, st, done)
+                                                     n_str, tile_first, out, n_items_dev, cap, counts, err, st, done, dt)
     if (kind == 0) return out32 ? LATOK_CS(0, int32_t) : LATOK_CS(0, int64_t);
     return out32 ? LATOK_CS(1, int32_t) : LATOK_CS(1, int64_t);
 #undef LATOK_CS

@@ -126,6 +126,24 @@ struct SplitParams {
 };
 
 
+// A batch whose size only the device knows when its launches are enqueued (code-point results of a UTF-8 batch in a flow: the
+// code-point total is the result of the lead-byte scan).  total: the word that holds it, written earlier on the same stream; the
+// launch's own size arguments are then an UPPER BOUND (a batch has at most one char per byte) that sizes grids and buffers, and
+// tiles, words and strings behind the real size do no work.  gate: a word that is nonzero when the batch was found malformed --
+// the records and feature sums of such a batch are not written.  {NULL, NULL}: the host's size is the size.
+struct DeviceTotal {
+    const int64_t* total;
+    const int* gate;
+};
+#if defined(__HIPCC__)
+// the size a kernel works with: the device's word, held inside [0, bound] -- the buffers were sized by the bound, so whatever the
+// word holds (a scan that ended with its error flag raised leaves anything) no access leaves them
+__device__ __forceinline__ int64_t device_total(const int64_t* p, int64_t bound) {
+    const int64_t t = *p;
+    return t < 0 ? 0 : (t > bound ? bound : t);
+}
+#endif
+
 // featurize on the tile grid (split_kernels.hip: k_features_tiles)
 struct FeatParams {
     const uint8_t* codes;         // rule code of every char (SplitParams::codes_out of the tile kernel), padded by one tile + 256 B
@@ -144,6 +162,7 @@ struct FeatParams {
     const int64_t* n_tokens_dev;  // device: total tokens of the batch (k_word_counts_scan) ...
     int64_t cap;                  // ... nothing is written when it exceeds the caller's capacity
     DoneSignal done;
+    DeviceTotal dt;               // total / n_tiles above are an upper bound when dt.total is set
 };
 hipError_t launch_features_tiles(const FeatParams& P, int n_cu, hipStream_t st);
 
@@ -207,14 +226,15 @@ int64_t count_blocks(int64_t n_words);   // workgroups of launch_word_counts_sca
 hipError_t launch_word_counts_scan(bool spans, const uint64_t* bits, const uint64_t* space, int64_t n_words, int64_t total,
                                    uint64_t* kept, int64_t* tile_cnt, uint16_t* word_pref, int64_t* tile_rank,
                                    unsigned long long* chain, unsigned* ticket, unsigned epoch, int64_t* total_dev,
-                                   int64_t* total_host, int* err, hipStream_t st);
+                                   int64_t* total_host, int* err, hipStream_t st, DeviceTotal dt = DeviceTotal{nullptr, nullptr});
 hipError_t launch_string_counts(bool out32, const uint64_t* mask, const int64_t* tile_rank, const uint16_t* word_pref,
                                 const int64_t* row_off, int64_t n_str, int64_t total, const int64_t* n_items, void* counts, int* err,
-                                hipStream_t st);
+                                hipStream_t st, DeviceTotal dt = DeviceTotal{nullptr, nullptr});
 hipError_t launch_counts_scatter(int kind, bool out32, const uint64_t* bits, const uint64_t* space, const uint64_t* item_mask,
                                  const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words,
                                  int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,
-                                 const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st, DoneSignal done = DoneSignal{nullptr, 0, nullptr});
+                                 const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st, DoneSignal done = DoneSignal{nullptr, 0, nullptr},
+                                 DeviceTotal dt = DeviceTotal{nullptr, nullptr});
 constexpr int kCompressWaves = 16;   // k_lead_compress: tiles (= waves) per workgroup
 // code-point boundary mask + code-point row offsets from the byte-space mask and the lead-byte mask of a UTF-8 batch
 // (bmask2 / out_mask2: optionally a second mask -- the SPACE plane -- packed the same way, for token spans in code-point units)
@@ -228,6 +248,8 @@ hipError_t launch_lead_codes(const uint8_t* u8, int64_t total_bytes, const uint6
                              const uint16_t* word_pref, int64_t n_words, const uint8_t* tb6rule, uint8_t* codes, int n_cu, hipStream_t st);
 hipError_t launch_tile_scan(const int64_t* tile_cnt, int64_t n_tiles, int64_t* tile_rank, unsigned long long* chain, unsigned* ticket,
                             unsigned epoch, int64_t* total_dev, int64_t* total_host, int* err, hipStream_t st);
+// zeros at codes[t .. t + kTile + 256), t = *total_dev held inside [0, bound]
+hipError_t launch_pad_codes(uint8_t* codes, const int64_t* total_dev, int64_t bound, hipStream_t st);
 int64_t utf8_blocks(int64_t total_bytes);   // 4 KiB blocks of the chunk-parallel UTF-8 decoder
 hipError_t launch_utf8_block_counts(const uint8_t* u8, int64_t total, int64_t* block_cnt, hipStream_t st);
 hipError_t launch_utf8_decode(const uint8_t* u8, int64_t total, const int64_t* byte_off, int64_t n_str,

@@ -2308,8 +2308,14 @@ __global__ __launch_bounds__(kFeatWaves * 64) void k_features_tiles(FeatParams P
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    bool gated = false;
+    if (P.dt.total) {   // (uniform) the batch's size from device memory (kernels.h: DeviceTotal); a malformed batch writes nothing
+        P.total = device_total(P.dt.total, P.total);
+        P.n_tiles = (P.total + kTile - 1) / kTile;
+        gated = P.dt.gate && *P.dt.gate != 0;
+    }
     // (the caller's buffers are too small: nothing is written)
-    if (!(P.n_tokens_dev && *P.n_tokens_dev > P.cap)) {
+    if (!gated && !(P.n_tokens_dev && *P.n_tokens_dev > P.cap)) {
         TileLds L;
         L.small_bits = L.small_space = nullptr;
         L.t1 = L.t2 = L.lut = L.ctab = L.ltab = L.t1b = L.t2b = nullptr; L.tables = nullptr; L.ctl = nullptr;   // nothing is classified here: the tile kernel left the rule codes (P.codes)

@@ -9,6 +9,11 @@
   utf8_offsets    latok_split_offsets_utf8_batch
   utf8_spans      latok_token_spans_utf8_batch
   utf8_features32 latok_token_features_utf8_batch with LATOK_OUT_INT32 (featurize of UTF-8 in code-point units, no UTF-32 copy)
+  utf8_offsets32 / utf8_spans32   the same UTF-8 entry points with LATOK_OUT_INT32 records
+  utf8_mask_flow / utf8_offsets_flow / utf8_offsets32_flow / utf8_spans_flow / utf8_spans32_flow / utf8_features32_flow
+                  (the `utf8_flow` leg) UTF-8 in code-point units through the batch flow (latok_flow_*_utf8): two batches in
+                  flight with alternating output buffers and result words, nothing read by the host between the launches;
+                  the result words of the last two batches are checked after the wait (no malformed flag, the blocking item count)
   utf8_decode_features32   what a UTF-8 caller had to compose before: latok_utf8_decode_batch into a device buffer, then
                   latok_token_features_batch on it (LATOK_OUT_INT32); same data, same process
   bytes_mask / bytes_offsets / bytes_spans   latok_*_utf8_bytes_batch (8f-3 fused: the tile kernel reads the bytes)
@@ -26,7 +31,9 @@ the path's ALGORITHMIC bytes (inputs that must be read + outputs that must be wr
 as a fraction of the 8 TB/s HBM peak.  `--cpu N` adds the reference's own C functions + its Python glue (oracle/_ref,
 test infrastructure, timed here as the baseline only) on the first N strings for offsets and tokens.
 
-usage: tools/path_bench.py [--workload C2|C3] [--strings N] [--iters K] [--cpu N]
+`--repeat R` prints every line R times (R measurements in one warm process: the run-to-run spread of a path).
+
+usage: tools/path_bench.py [--workload C2|C3] [--strings N] [--iters K] [--repeat R] [--cpu N]
 """
 import argparse
 import ctypes as C
@@ -65,8 +72,10 @@ def main():
     ap.add_argument("--workload", default="C2", choices=sorted(WORKLOADS))
     ap.add_argument("--strings", type=int, default=1_000_000)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--repeat", type=int, default=1, help="measurements per path, one JSON line each")
     ap.add_argument("--cpu", type=int, default=0, help="strings of CPU baseline (0 = skip)")
-    ap.add_argument("--paths", default="mask,mask_flow,bytes_mask_flow,kind_mask_flow,offsets32_flow,spans32_flow,features32_flow,offsets,offsets32,spans,spans32,features,features32,utf8_mask,utf8_offsets,utf8_spans,utf8_features32,utf8_decode_features32,"
+    ap.add_argument("--paths", default="mask,mask_flow,bytes_mask_flow,kind_mask_flow,offsets32_flow,spans32_flow,features32_flow,offsets,offsets32,spans,spans32,features,features32,utf8_mask,utf8_offsets,utf8_offsets32,utf8_spans,utf8_spans32,utf8_features32,"
+                                       "utf8_mask_flow,utf8_offsets_flow,utf8_offsets32_flow,utf8_spans_flow,utf8_spans32_flow,utf8_features32_flow,utf8_decode_features32,"
                                        "bytes_mask,bytes_offsets,bytes_spans,rules_mask,kind_mask,kind_offsets,kind_offsets32,"
                                        "kind_spans,kind_spans32")
     args = ap.parse_args()
@@ -105,16 +114,17 @@ def main():
     def run(name, fn, alg, note):
         _lib.check(fn())
         _lib.check(lib.latok_sync())
-        t = time.perf_counter()
-        for _ in range(args.iters):
-            _lib.check(fn())
-        _lib.check(lib.latok_sync())
-        dt = (time.perf_counter() - t) / args.iters
-        a = alg()
-        print(json.dumps({"path": name, "workload": args.workload, "strings": n, "chars": total, "utf8_bytes": n8,
-                          "items": nout.value, "ms_per_call": dt * 1e3, "utf8_GBps": n8 / dt / 1e9,
-                          "alg_bytes": a, "alg_GBps": a / dt / 1e9, "frac_of_hbm_peak": a / dt / 1e9 / HBM_PEAK,
-                          "alg_bytes_are": note}), flush=True)
+        for r in range(args.repeat):
+            t = time.perf_counter()
+            for _ in range(args.iters):
+                _lib.check(fn())
+            _lib.check(lib.latok_sync())
+            dt = (time.perf_counter() - t) / args.iters
+            a = alg()
+            print(json.dumps({"path": name, "workload": args.workload, "strings": n, "chars": total, "utf8_bytes": n8,
+                              "items": nout.value, "ms_per_call": dt * 1e3, "utf8_GBps": n8 / dt / 1e9,
+                              "alg_bytes": a, "alg_GBps": a / dt / 1e9, "frac_of_hbm_peak": a / dt / 1e9 / HBM_PEAK,
+                              "alg_bytes_are": note, "repeat": r}), flush=True)
 
     paths = args.paths.split(",")
     flow_buf = {}
@@ -131,17 +141,18 @@ def main():
             _lib.check(submit(i))
         _lib.check(lib.latok_flow_wait())
         k = max(args.iters, 100)   # long enough that filling and draining the two-batch pipeline is noise
-        t = time.perf_counter()
-        for i in range(k):
-            _lib.check(submit(i))
-        _lib.check(lib.latok_flow_wait())
-        dt = (time.perf_counter() - t) / k
-        a = alg()
-        print(json.dumps({"path": name, "workload": args.workload, "strings": n, "chars": total, "utf8_bytes": n8,
-                          "items": 0, "ms_per_call": dt * 1e3, "utf8_GBps": n8 / dt / 1e9,
-                          "alg_bytes": a, "alg_GBps": a / dt / 1e9, "frac_of_hbm_peak": a / dt / 1e9 / HBM_PEAK,
-                          "alg_bytes_are": note + "; batch flow: two batches in flight, per-batch time of " + str(k) + " submissions + one wait"}),
-              flush=True)
+        for r in range(args.repeat):
+            t = time.perf_counter()
+            for i in range(k):
+                _lib.check(submit(i))
+            _lib.check(lib.latok_flow_wait())
+            dt = (time.perf_counter() - t) / k
+            a = alg()
+            print(json.dumps({"path": name, "workload": args.workload, "strings": n, "chars": total, "utf8_bytes": n8,
+                              "items": 0, "ms_per_call": dt * 1e3, "utf8_GBps": n8 / dt / 1e9,
+                              "alg_bytes": a, "alg_GBps": a / dt / 1e9, "frac_of_hbm_peak": a / dt / 1e9 / HBM_PEAK,
+                              "alg_bytes_are": note + "; batch flow: two batches in flight, per-batch time of " + str(k) + " submissions + one wait",
+                              "repeat": r}), flush=True)
 
     if "mask_flow" in paths:
         fa, fb = flow_pair(words)
@@ -213,10 +224,60 @@ def main():
     if "utf8_spans" in paths:
         run("utf8_spans", lambda: lib.latok_token_spans_utf8_batch(d_u8, d_boff, n, n8, d_counts, d_items, cap, C.byref(nout), D, None),
             lambda: n8 + csr + 8 * n + 16 * nout.value, "UTF-8 bytes + 8 B/string read; 8 B/string + 16 B/token written")
+    if "utf8_offsets32" in paths:
+        run("utf8_offsets32", lambda: lib.latok_split_offsets_utf8_batch(d_u8, d_boff, n, n8, d_counts, d_items, cap, C.byref(nout), D32, None),
+            lambda: n8 + csr + 4 * n + 4 * nout.value, "UTF-8 bytes + 8 B/string read; 4 B/string + 4 B/boundary written (LATOK_OUT_INT32)")
+    if "utf8_spans32" in paths:
+        run("utf8_spans32", lambda: lib.latok_token_spans_utf8_batch(d_u8, d_boff, n, n8, d_counts, d_items, cap, C.byref(nout), D32, None),
+            lambda: n8 + csr + 4 * n + 8 * nout.value, "UTF-8 bytes + 8 B/string read; 4 B/string + 8 B/token written (LATOK_OUT_INT32)")
     if "utf8_features32" in paths:
         run("utf8_features32", lambda: lib.latok_token_features_utf8_batch(d_u8, d_boff, n, n8, d_counts, d_items, d_feat, cap, C.byref(nout), D32, None),
             lambda: n8 + csr + 4 * n + (16 + 25) * nout.value,
             "UTF-8 bytes + 8 B/string read (the input ONCE); 4 B/string + 41 B/token written (LATOK_OUT_INT32)")
+    # the utf8_flow leg: the same code-point results through the batch flow, two batches in flight with alternating buffers
+    u8_flow = [p for p in paths if p.startswith("utf8_") and p.endswith("_flow")]
+    if u8_flow:
+        bw8 = (n8 + 63) // 64
+        fa, fb = flow_pair(bw8)
+        d_cprow2, d_items4, d_counts4, d_feat4 = (lib.latok_dev_alloc((n + 1) * 8), lib.latok_dev_alloc(cap * 32), lib.latok_dev_alloc(n * 8),
+                                                   lib.latok_dev_alloc(cap * 25))
+        d_res4 = lib.latok_dev_alloc(128)
+        if not (d_cprow2 and d_items4 and d_counts4 and d_feat4 and d_res4):
+            raise RuntimeError(_lib.last_error())
+        res_of = lambda i: C.c_void_p(d_res4 + 32 * (i & 1))  # noqa: E731
+
+        def checked(name, blocking, submit, alg, note):
+            """the blocking call once (item count), the flow measurement, then the result words of the last two batches"""
+            _lib.check(blocking())
+            items_n = 0 if name == "utf8_mask_flow" else nout.value
+            run_flow(name, submit, lambda: alg(items_n), note)
+            res = np.empty(8, np.int64)
+            _lib.check(lib.latok_memcpy_d2h(res.ctypes.data, d_res4, 64))
+            for r4 in res.reshape(2, 4):
+                assert r4[3] == 0 and r4[1] == 0 and r4[2] == total and r4[0] == items_n, (name, r4.tolist())
+
+        if "utf8_mask_flow" in u8_flow:
+            checked("utf8_mask_flow", lambda: lib.latok_split_mask_utf8_batch(d_u8, d_boff, n, n8, d_bits, words + 1, d_cprow, C.byref(tcp), D, None),
+                    lambda i: lib.latok_flow_split_mask_utf8(d_u8, d_boff, n, n8, fb if i & 1 else fa, bw8, d_cprow2 if i & 1 else d_cprow, res_of(i)),
+                    lambda _: n8 + csr + words * 8 + csr, "UTF-8 bytes + 8 B/string read; 1 bit/char + 8 B/string cp offsets written")
+        for name, fn_b, fn_f, fl, rec, per in (
+                ("utf8_offsets_flow", lib.latok_split_offsets_utf8_batch, lib.latok_flow_split_offsets_utf8, 0, 8, 1),
+                ("utf8_offsets32_flow", lib.latok_split_offsets_utf8_batch, lib.latok_flow_split_offsets_utf8, _lib.OUT_INT32, 4, 1),
+                ("utf8_spans_flow", lib.latok_token_spans_utf8_batch, lib.latok_flow_token_spans_utf8, 0, 8, 2),
+                ("utf8_spans32_flow", lib.latok_token_spans_utf8_batch, lib.latok_flow_token_spans_utf8, _lib.OUT_INT32, 4, 2)):
+            if name in u8_flow:
+                checked(name, lambda fn_b=fn_b, fl=fl: fn_b(d_u8, d_boff, n, n8, d_counts, d_items, cap, C.byref(nout), D | fl, None),
+                        lambda i, fn_f=fn_f, fl=fl: fn_f(d_u8, d_boff, n, n8, d_counts4 if i & 1 else d_counts, d_items4 if i & 1 else d_items, cap,
+                                                         res_of(i), fl),
+                        lambda k, rec=rec, per=per: n8 + csr + rec * n + rec * per * k,
+                        f"UTF-8 bytes + 8 B/string read; {rec} B/string + {rec * per} B/item written")
+        if "utf8_features32_flow" in u8_flow:
+            checked("utf8_features32_flow",
+                    lambda: lib.latok_token_features_utf8_batch(d_u8, d_boff, n, n8, d_counts, d_items, d_feat, cap, C.byref(nout), D32, None),
+                    lambda i: lib.latok_flow_token_features_utf8(d_u8, d_boff, n, n8, d_counts4 if i & 1 else d_counts, d_items4 if i & 1 else d_items,
+                                                                 d_feat4 if i & 1 else d_feat, cap, res_of(i), _lib.OUT_INT32),
+                    lambda k: n8 + csr + 4 * n + (16 + 25) * k,
+                    "UTF-8 bytes + 8 B/string read (the input ONCE); 4 B/string + 41 B/token written (LATOK_OUT_INT32)")
     if "utf8_decode_features32" in paths:
         d_dec, d_decrow = lib.latok_dev_alloc(total * 4 + 64), lib.latok_dev_alloc((n + 1) * 8)
         if not d_dec or not d_decrow:

@@ -4,7 +4,8 @@
 Worker processes build random batches from adversarial alphabets in several shape regimes (many tiny strings, tweets,
 multi-tile documents, no-whitespace documents with starts, dense starts) and compute the oracle's split values / bitmask on
 the CPU; the main process runs the same batch through the C ABI (values, bitmask, offsets, token spans, the bitmask
-under run-time rule tables, featurize sums, the UTF-8 entry points in byte space and in code-point units, and the PEP 393 kind-1 / kind-2 entry points) and compares bit for bit.  Stops after --seconds.
+under run-time rule tables, featurize sums, the UTF-8 entry points in byte space and in code-point units -- blocking and, in
+code-point units, through the batch flow (latok_flow_*_utf8) --, and the PEP 393 kind-1 / kind-2 entry points) and compares bit for bit.  Stops after --seconds.
 
 usage: tools/soak.py [--seconds 120] [--workers 12] [--seed 1]
 """
@@ -113,15 +114,17 @@ def spans_from(vals, space, row):
 
 class FlowLeg:
     """Every group of batches also goes through the batch flow (latok_flow_*: two batches in flight per context): each batch is
-    uploaded, its mask / offsets / spans are submitted back to back with the other batches' and checked after ONE wait."""
+    uploaded, its mask / offsets / spans are submitted back to back with the other batches' and checked after ONE wait.  A batch
+    that has a UTF-8 view goes through latok_flow_*_utf8 as well (code-point units: the same expectations; featurize when the
+    oracle's sums were computed), and its four result words must report a well-formed batch."""
 
     def __init__(self, lib, group=4):
-        self.lib, self.group, self.items, self.n_checked = lib, group, [], 0
+        self.lib, self.group, self.items, self.n_checked, self.n_utf8 = lib, group, [], 0, 0
 
-    def add(self, cps, row, bits, counts, offs, spans, dt, tag):
+    def add(self, cps, row, bits, counts, offs, spans, dt, tag, u8=None, boff=None, feats=None):
         if cps.size == 0:
             return
-        self.items.append((cps, row, bits, counts, offs, spans, dt, tag))
+        self.items.append((cps, row, bits, counts, offs, spans, dt, tag, u8, boff, feats))
         if len(self.items) >= self.group:
             self.run()
 
@@ -142,7 +145,7 @@ class FlowLeg:
             if a.nbytes:
                 _lib.check(lib.latok_memcpy_d2h(a.ctypes.data, p, a.nbytes))
             return a
-        for cps, row, bits, counts, offs, spans, dt, tag in self.items:
+        for cps, row, bits, counts, offs, spans, dt, tag, u8, boff, feats in self.items:
             n, total, isz = len(row) - 1, int(row[-1]), np.dtype(dt).itemsize
             d_c, d_r, d_m = dev(cps.nbytes, cps), dev(row.nbytes, row), dev(bits.nbytes)
             d_oc, d_oo, d_or = dev(n * isz), dev(max(len(offs), 1) * isz), dev(16)
@@ -152,6 +155,21 @@ class FlowLeg:
             if spans is not None:
                 job["d_sc"], job["d_ss"], job["d_sr"] = dev(n * isz), dev(max(len(spans[1]), 1) * 2 * isz), dev(16)
                 batch.flow_token_spans(d_c, 4, d_r, n, -1, job["d_sc"], job["d_ss"], len(spans[1]), job["d_sr"], dtype=dt)
+            if u8 is not None:   # the same batch as UTF-8, results in code-point units
+                n8 = int(u8.size)
+                d_u, d_b = dev(n8, u8), dev(boff.nbytes, boff)
+                u = dict(row=row, d_m=dev((n8 + 63) // 64 * 8), d_row=dev(row.nbytes), d_mr=dev(32), d_oc=dev(n * isz), d_oo=dev(max(len(offs), 1) * isz),
+                         d_or=dev(32))
+                batch.flow_split_mask_utf8(d_u, d_b, n, n8, u["d_m"], (n8 + 63) // 64, u["d_row"], u["d_mr"])
+                batch.flow_split_offsets_utf8(d_u, d_b, n, -1, u["d_oc"], u["d_oo"], len(offs), u["d_or"], dtype=dt)
+                if spans is not None:
+                    u["d_sc"], u["d_ss"], u["d_sr"] = dev(n * isz), dev(max(len(spans[1]), 1) * 2 * isz), dev(32)
+                    batch.flow_token_spans_utf8(d_u, d_b, n, n8, u["d_sc"], u["d_ss"], len(spans[1]), u["d_sr"], dtype=dt)
+                if feats is not None:
+                    nf = len(feats[1])
+                    u["feats"], u["d_fc"], u["d_fs"], u["d_ff"], u["d_fr"] = feats, dev(n * isz), dev(max(nf, 1) * 4 * isz), dev(max(nf, 1) * 25), dev(32)
+                    batch.flow_token_features_utf8(d_u, d_b, n, n8, u["d_fc"], u["d_fs"], u["d_ff"], nf, u["d_fr"], dtype=dt)
+                job["u8"] = u
             jobs.append(job)
         batch.flow_wait()
         for j in jobs:
@@ -166,6 +184,28 @@ class FlowLeg:
                 assert res[0] == len(ws) and res[1] == 0, "flow span total differs: " + j["tag"]
                 assert np.array_equal(get(j["d_sc"], j["n"], j["dt"]), wc), "flow span counts differ: " + j["tag"]
                 assert np.array_equal(get(j["d_ss"], (len(ws), 2), j["dt"]), ws), "flow spans differ: " + j["tag"]
+            u = j.get("u8")
+            if u is None:
+                continue
+            total = int(u["row"][-1])
+            res = get(u["d_mr"], 4, np.int64)
+            assert res.tolist() == [0, 0, total, 0], "flow UTF-8 mask result words: " + j["tag"]
+            assert np.array_equal(get(u["d_m"], j["bits"].shape, np.uint64), j["bits"]), "flow UTF-8 bitmask differs: " + j["tag"]
+            assert np.array_equal(get(u["d_row"], u["row"].shape, np.int64), u["row"]), "flow UTF-8 row offsets differ: " + j["tag"]
+            assert get(u["d_or"], 4, np.int64).tolist() == [len(j["offs"]), 0, total, 0], "flow UTF-8 offsets result words: " + j["tag"]
+            assert np.array_equal(get(u["d_oc"], j["n"], j["dt"]), j["counts"]), "flow UTF-8 offset counts differ: " + j["tag"]
+            assert np.array_equal(get(u["d_oo"], len(j["offs"]), j["dt"]), j["offs"]), "flow UTF-8 offsets differ: " + j["tag"]
+            if j["spans"] is not None:
+                wc, ws = j["spans"]
+                assert get(u["d_sr"], 4, np.int64).tolist() == [len(ws), 0, total, 0], "flow UTF-8 span result words: " + j["tag"]
+                assert np.array_equal(get(u["d_sc"], j["n"], j["dt"]), wc), "flow UTF-8 span counts differ: " + j["tag"]
+                assert np.array_equal(get(u["d_ss"], (len(ws), 2), j["dt"]), ws), "flow UTF-8 spans differ: " + j["tag"]
+            if "feats" in u:
+                ff, fs = u["feats"]
+                assert get(u["d_fr"], 4, np.int64).tolist() == [len(fs), 0, total, 0], "flow UTF-8 featurize result words: " + j["tag"]
+                assert np.array_equal(get(u["d_fs"], (len(fs), 4), j["dt"]), fs), "flow UTF-8 featurize span records differ: " + j["tag"]
+                assert np.array_equal(get(u["d_ff"], (len(fs), 25), np.int8), ff), "flow UTF-8 featurize sums differ: " + j["tag"]
+            self.n_utf8 += 1
         for p in live:
             lib.latok_dev_free(p)
         self.n_checked += len(jobs)
@@ -216,7 +256,7 @@ def main():
                 assert np.array_equal(gc, wc) and np.array_equal(gs, ws), "token spans differ: " + tag
                 n_spans += 1
             # (the flow leg runs on whatever context is current when its group is full: both contexts get their share)
-            flow.add(cps, row, bits, counts, offs, (wc, ws) if ws is not None else None, dt, tag)
+            flow.add(cps, row, bits, counts, offs, (wc, ws) if ws is not None else None, dt, tag, u8, boff, feats)
             if rules is not None:
                 batch.set_rules(*rules)
                 try:
@@ -296,7 +336,7 @@ def main():
         flow.run()
     _lib.load().latok_ctx_set_current(None)
     second.destroy()
-    print(f"soak passed (two contexts alternating, int32 / int64 records alternating): {n_batches} batches, {n_chars} chars, {flow.n_checked} also through the batch flow (mask + offsets + spans), {n_rules} with rule tables, {n_spans} span checks, "
+    print(f"soak passed (two contexts alternating, int32 / int64 records alternating): {n_batches} batches, {n_chars} chars, {flow.n_checked} also through the batch flow (mask + offsets + spans; {flow.n_utf8} of them as UTF-8 in code-point units too), {n_rules} with rule tables, {n_spans} span checks, "
           f"{n_u8} UTF-8 (byte space + code-point) checks, {n_feat} featurize checks, {n_kind} PEP 393 kind checks, {args.seconds:.0f} s")
 
 
