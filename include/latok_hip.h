@@ -161,6 +161,7 @@ int latok_token_features_utf8_batch(const uint8_t* utf8, const int64_t* byte_off
  *   offsets  byte offsets relative to the start of each string
  *   spans    [start, end) byte ranges of the stripped, non-empty tokens: utf8[byte_off[s] + start : byte_off[s] + end]
  *            is the UTF-8 encoding of the token the reference yields
+ *   featurize  the four positions of a token's span record as byte positions, the 25 feature sums per char
  * Input must be valid UTF-8 ("surrogatepass" forms are accepted as they decode); a truncated sequence counts as
  * U+FFFD, stray continuation bytes belong to no char.  With LATOK_DEVICE_PTRS the byte buffer must be 16-byte aligned.
  * Run-time rule tables (latok_set_rules) apply in byte space too (evaluated by the byte-space tile kernel itself). */
@@ -172,6 +173,27 @@ int latok_split_offsets_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byt
 int latok_token_spans_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
                                        int64_t* counts_out, int64_t* spans_out, int64_t spans_cap, int64_t* n_tokens_out,
                                        int flags, void* stream);
+
+/* featurize in byte space: latok_token_features_batch (below) for a caller who holds bytes and slices bytes.  Token for token
+ * (same tokens, same order, same counts) what the two calls above and latok_token_features_utf8_batch report:
+ *   spans4_out[4k + 2], [4k + 3]   the stripped BYTE range = the record of latok_token_spans_utf8_bytes_batch (LaToken.text =
+ *                                  utf8[byte_off[s] + strip_start : byte_off[s] + strip_end])
+ *   spans4_out[4k], [4k + 1]       the raw BYTE range = the two consecutive offsets of latok_split_offsets_utf8_bytes_batch (the
+ *                                  string's byte length closing the last one) that enclose it
+ *   features_out[25k .. 25k + 24]  the sums latok_token_features_utf8_batch gives for the token: one count per CHAR, not per byte
+ * i.e. the reference's featurize of the decoded string with every position mapped from a char to the first byte of that char
+ * (end positions: the byte behind the char's last byte).  Flags, total_bytes = -1, the capacity protocol (cap in tokens; too
+ * small: nothing written to records or sums, counts valid, needed count in *n_tokens_out; cap = 0 with NULL buffers = size query;
+ * features_out NULL with cap > 0 is refused) and run-time rule tables as in latok_token_features_utf8_batch; under LATOK_OUT_INT32
+ * a string of 2^31 BYTES or more fails.  Truncated sequences and lone lead bytes count as one char each, as everywhere in byte
+ * space.  A batch with a STRAY continuation byte (none of the 3 bytes before it is a lead byte, or it opens a string) has no
+ * defined feature sums here -- byte space assigns the byte to no char, the decoder makes it U+FFFD -- and is REFUSED:
+ * LATOK_ERR_INVALID ("malformed UTF-8"), no record and no sum written, *n_tokens_out = 0.  Such input can go to
+ * latok_token_features_utf8_batch (code-point results through the staged decoder) or to latok_token_spans_utf8_bytes_batch
+ * (byte ranges without sums). */
+int latok_token_features_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                          int64_t* counts_out, int64_t* spans4_out, int8_t* features_out, int64_t cap,
+                                          int64_t* n_tokens_out, int flags, void* stream);
 
 /* Token feature vectors: reference featurize() (default_tokenizer.py:163-191) for a whole batch without the n x 25
  * matrix.  Per kept token k: spans4_out[4k..4k+3] = {raw_start, raw_end, strip_start, strip_end} (LaToken.start_idx /
@@ -343,6 +365,13 @@ int latok_flow_token_spans_utf8(const uint8_t* utf8_dev, const int64_t* byte_off
 int latok_flow_token_features_utf8(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
                                    void* counts_dev, void* spans4_dev, int8_t* features_dev, int64_t cap,
                                    int64_t* result_dev, int flags);
+/* featurize in BYTE space through the flow: what latok_token_features_utf8_bytes_batch reports (span records in byte positions,
+ * sums per char), bit-identical, with the conventions of latok_flow_token_features_utf8: the same four result words (result[2] =
+ * code-point total; result[3] nonzero = malformed UTF-8: no record and no sum was written -- the blocking call refuses the same
+ * batch), the same capacity rule, every buffer in the ordering rule; under LATOK_OUT_INT32 a string of 2^31 BYTES sets result[1]. */
+int latok_flow_token_features_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                         void* counts_dev, void* spans4_dev, int8_t* features_dev, int64_t cap,
+                                         int64_t* result_dev /* int64[4] */, int flags);
 int latok_flow_wait(void);
 
 /* ---- measurement ----------------------------------------------------------------------------------------------- */

@@ -364,6 +364,34 @@ def token_spans_utf8_bytes_csr(utf8, byte_off, dtype=np.int64):
     return _compact(_lib.ensure_init().latok_token_spans_utf8_bytes_batch, [_ptr(utf8), _ptr(byte_off)], n_str, total, 2, dtype)
 
 
+def token_features_utf8_bytes_csr(utf8, byte_off, dtype=np.int64):
+    """(counts, spans4[n_tokens, 4], features int8[n_tokens, 25]): featurize in byte space.  spans4 = {raw start, raw end,
+    stripped start, stripped end} as BYTE positions relative to each string's first byte; the feature sums count chars, not
+    bytes (they are what token_features_utf8_csr gives for the same token).  Malformed UTF-8 (a continuation byte without a
+    lead byte) is refused with ValueError."""
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    _out_dtype(dtype)   # (a bad argument is a ValueError before any device is asked for)
+    n_str = byte_off.size - 1
+    total = int(byte_off[-1]) if n_str > 0 else 0
+    return _compact(_lib.ensure_init().latok_token_features_utf8_bytes_batch, [_ptr(utf8), _ptr(byte_off)], n_str, total, 4, dtype,
+                    feats=True)
+
+
+def featurize_utf8_bytes_batch(blobs):
+    """list[bytes] (each valid UTF-8) -> list[list[LaToken]] without transcoding anything: text = blob[strip_start:strip_end]
+    (bytes), start_idx / end_idx = the raw BYTE range of the token in its blob, features = the reference's 25 sums."""
+    from .core.latok_utils import LaToken
+    if len(blobs) == 0:
+        return []
+    utf8, byte_off = pack_utf8(blobs)
+    counts, spans, feats = token_features_utf8_bytes_csr(utf8, byte_off, dtype=_record_dtype(byte_off))
+    out, k = [], 0
+    for blob, n in zip(blobs, counts.tolist()):
+        out.append([LaToken(blob[c:d], a, b, feats[k + j]) for j, (a, b, c, d) in enumerate(spans[k:k + n].tolist())])
+        k += n
+    return out
+
+
 def tokenize_utf8_batch(blobs):
     """list[bytes] (UTF-8) -> list[list[bytes]]: the reference's tokens of every string, as UTF-8 slices of the input
     (byte-space path: nothing is transcoded on the host or on the device)."""
@@ -614,6 +642,16 @@ def flow_token_features_utf8(d_utf8, d_byte_off, n_str, total_bytes, d_counts, d
     _, flag32 = _out_dtype(dtype)
     _lib.check(lib.latok_flow_token_features_utf8(d_utf8, d_byte_off, int(n_str), int(total_bytes), d_counts, d_spans4, d_features,
                                                   int(cap), d_result, flag32))
+
+
+def flow_token_features_utf8_bytes(d_utf8, d_byte_off, n_str, total_bytes, d_counts, d_spans4, d_features, cap, d_result, dtype=np.int64):
+    """featurize in BYTE space of one device-resident UTF-8 batch through the flow (``latok_flow_token_features_utf8_bytes``):
+    span records in byte positions, sums per char.  ``d_result`` = int64[4]: token total, error word, code-point total,
+    malformed flag (nonzero: no record and no sum of the batch was written)."""
+    lib = _lib.ensure_init()
+    _, flag32 = _out_dtype(dtype)
+    _lib.check(lib.latok_flow_token_features_utf8_bytes(d_utf8, d_byte_off, int(n_str), int(total_bytes), d_counts, d_spans4, d_features,
+                                                        int(cap), d_result, flag32))
 
 
 def flow_wait():

@@ -1303,6 +1303,152 @@ static int cp_masks_via_bytes(Ctx& g, const Batch& d, uint64_t* d_out, uint64_t*
     return LATOK_OK;
 }
 
+// featurize of a UTF-8 batch in BYTE space (latok_token_features_utf8_bytes_batch and its flow form): span records in byte
+// positions, feature sums per CHAR.  A token has the same rank in byte space and in code-point space, so two writers share one
+// record index: k_counts_scatter<2> puts the four byte positions from the byte-space masks, k_features_tiles (without span records)
+// the sums from the packed code-point masks and the rule codes.  One stream, nothing waits for the host:
+//   tile index -> byte-space tiles -> resolve       boundary mask, SPACE plane, lead mask + lead counts over the BYTES
+//   k_scan_chained (lead counts)                    lead ranks; code-point total -> r_cps, and the workspace's scalar word 1
+//   k_lead_compress, k_lead_codes                   packed code-point masks, code-point row offsets, rule codes; malformed -> r_odd
+//   k_word_counts + k_scan_chained (byte masks)     kept mask / item ranks in byte space; THE token total -> scalar word 0, r_items
+//   k_counts_scatter<2>                             counts + byte records        (gates: total <= cap, *r_odd == 0)
+//   tile index (code-point rows), k_word_counts + k_scan_chained (code-point masks)    item ranks in code-point space
+//   k_features_tiles                                the sums                     (the same two gates)
+// The three scans share the workspace's rank arrays (bases / wcnt / wpref) and kept mask: every consumer of one scan has been
+// enqueued before the next scan overwrites them, and the stream orders them.  The token total is written once, by the byte-space
+// scan (the code-point scan's own total goes to scalar word 2 and to no result word), and gates both writers.  Sizes behind the
+// lead scan are the byte count, an upper bound (DeviceTotal).  `w` was sized by ws_needs(w, total_bytes, true, true, false, n_str + 1).
+struct Utf8BytesFeats {
+    Batch b;                      // UTF-8 bytes on the device, byte offsets, total in bytes (> 0), n_str > 0
+    bool o32 = false;
+    void* counts = nullptr;
+    void* items = nullptr;
+    int8_t* feat = nullptr;
+    int64_t cap = 0;
+    int64_t* r_items = nullptr;   // the four result words as the device sees them (cleared by the caller): token total,
+    int64_t* r_err = nullptr;     // int32-overflow flag (low half) | scan flag (high half),
+    int64_t* r_cps = nullptr;     // code-point total,
+    int64_t* r_odd = nullptr;     // malformed-input flag
+    hipStream_t st = nullptr;
+};
+static int enqueue_utf8_bytes_features(Ctx& g, Workspace& w, const Utf8BytesFeats& a) {
+    int rc;
+    const hipStream_t st = a.st;
+    const int64_t n_str = a.b.n_str, total_bytes = a.b.total, words_b = (total_bytes + 63) / 64, c_tiles = (words_b + 63) / 64;
+    uint64_t* d_bmask = (uint64_t*)w.bits.p;
+    uint64_t* d_lead = (uint64_t*)w.lead.p;
+    uint64_t* d_bspace = (uint64_t*)w.bspace.p;
+    uint64_t* d_kept = (uint64_t*)w.kept.p;
+    int64_t* d_rank = (int64_t*)w.bases.p;
+    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
+    uint16_t* d_pref = (uint16_t*)w.wpref.p;
+    int64_t* d_total = (int64_t*)w.scalar.p;        // word 0: the token total
+    int64_t* d_total_cps = d_total + 1;             // word 1: the code-point total
+    int* d_err = (int*)a.r_err;
+    const int* d_odd = (const int*)a.r_odd;
+    unsigned epoch = 0;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    Pipe p;
+    p.b = a.b;
+    p.bits = d_bmask;
+    p.space = d_bspace;
+    p.lead = d_lead;
+    p.lead_pref = d_pref;
+    p.lead_cnt = d_tcnt;
+    p.st = st;
+    if ((rc = run_pipeline(g, w, p))) return rc;
+    HIP_TRY(latok::launch_tile_scan(d_tcnt, c_tiles, d_rank, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total_cps,
+                                    a.r_cps, d_err + 1, st));
+    uint64_t* d_cpbits = (uint64_t*)w.cpbits.p;
+    uint64_t* d_cpspace = (uint64_t*)w.cpspace.p;
+    int64_t* d_cp_row = (int64_t*)w.cprow.p;
+    HIP_TRY(latok::launch_lead_compress(d_bmask, d_bspace, d_lead, d_rank, d_tcnt, d_pref, words_b, total_bytes, a.b.row, n_str, d_total_cps,
+                                        d_cpbits, d_cpspace, words_b, d_cp_row, (int*)a.r_odd, st));
+    uint8_t* d_codes = (uint8_t*)w.codes.p;
+    HIP_TRY(latok::launch_lead_codes((const uint8_t*)a.b.in.p, total_bytes, d_lead, d_rank, d_tcnt, d_pref, words_b, (const uint8_t*)g.tb6rule.p,
+                                     d_codes, g.n_cu, st));
+    HIP_TRY(latok::launch_pad_codes(d_codes, d_total_cps, total_bytes, st));
+    // byte space: kept tokens, their ranks, the total; counts and the four byte positions of every token (the lead ranks are spent)
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    HIP_TRY(latok::launch_word_counts_scan(true, d_bmask, d_bspace, words_b, total_bytes, d_kept, d_tcnt, d_pref, d_rank,
+                                           (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total, a.r_items, d_err + 1, st));
+    HIP_TRY(latok::launch_counts_scatter(2, a.o32, d_bmask, d_bspace, d_kept, d_rank, d_tcnt, d_pref, words_b, total_bytes, a.b.row, n_str,
+                                         (const int64_t*)w.tile_first.p, a.items, d_total, a.cap, a.counts, d_err, st,
+                                         latok::DoneSignal{nullptr, 0, nullptr}, latok::DeviceTotal{nullptr, d_odd}));
+    // code-point space: the same tokens on the packed masks (the byte-space ranks and kept mask are spent); sums only
+    const latok::DeviceTotal dt{d_total_cps, d_odd};
+    Pipe q;
+    q.b = Batch{Input{}, d_cp_row, n_str, total_bytes};
+    q.stages = 1;
+    q.st = st;
+    if ((rc = run_pipeline(g, w, q))) return rc;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    HIP_TRY(latok::launch_word_counts_scan(true, d_cpbits, d_cpspace, words_b, total_bytes, d_kept, d_tcnt, d_pref, d_rank,
+                                           (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 2, nullptr, d_err + 1, st, dt));
+    return enqueue_features(g, d_codes, d_cp_row, n_str, total_bytes, d_cpbits, d_cpspace, d_kept, d_rank, d_tcnt, d_pref,
+                            (const int64_t*)w.tile_first.p, nullptr, a.feat, a.o32, d_total, a.cap, st, latok::DoneSignal{nullptr, 0, nullptr}, dt);
+}
+
+// The blocking call behind compact_common's checks: b = the caller's UTF-8 batch (total resolved, n_str > 0, total > 0).  Every
+// batch that the host did not decode takes this route, whatever its size.  One synchronisation.
+static int features_utf8_bytes_route(Ctx& g, const Batch& b, bool dev, bool o32, void* counts_out, void* items_out, int8_t* features_out,
+                                     int64_t items_cap, int64_t* n_items_out, hipStream_t st) {
+    int rc;
+    const int64_t n_str = b.n_str, total_bytes = b.total;
+    if (dev && ((uintptr_t)b.in.p & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    g.last_route = 4;
+    const size_t elt = o32 ? 4 : 8;
+    Batch d;
+    if ((rc = units_on_device(g, b, dev, st, &d))) return rc;
+    if ((rc = ws_ensure(ws_needs(g.ws, total_bytes, true, true, false, n_str + 1).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+    int64_t* p_tot = (int64_t*)g.pin_tot.d;
+    Utf8BytesFeats a;
+    a.b = d;
+    a.o32 = o32;
+    a.counts = counts_out;
+    a.items = items_out;
+    a.feat = features_out;
+    // (a batch has at most one token per byte: a larger capacity gates nothing, and the staging below is sized by it)
+    a.cap = items_out ? std::min(items_cap, total_bytes) : 0;
+    if (!dev) {
+        if ((rc = g.counts.ensure((size_t)n_str * 8)) || (rc = g.h_out.ensure((size_t)a.cap * 4 * elt + 16)) ||
+            (rc = g.h_aux.ensure((size_t)a.cap * LATOK_FEATURE_COUNT + 16)))
+            return rc;
+        a.counts = g.counts.p;
+        a.items = g.h_out.p;
+        a.feat = (int8_t*)g.h_aux.p;
+    }
+    // pinned result words: 0 = tokens, 1 = flags, 3 = malformed, 4 = code points (2 is the small path's completion word)
+    h_tot[0] = h_tot[1] = h_tot[3] = h_tot[4] = 0;
+    a.r_items = p_tot;
+    a.r_err = p_tot + 1;
+    a.r_odd = p_tot + 3;
+    a.r_cps = p_tot + 4;
+    a.st = st;
+    if ((rc = enqueue_utf8_bytes_features(g, g.ws, a))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_tot[1] >> 32) { g.ws.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
+    if (h_tot[3] != 0)
+        return fail(LATOK_ERR_INVALID, "malformed UTF-8 (a continuation byte without a lead byte): no feature sums in byte space; "
+                                       "latok_token_features_utf8_batch reads such input through the decoder");
+    if (h_tot[1] & 0xFFFFFFFFll) return fail(LATOK_ERR_INVALID, "a string is too long for LATOK_OUT_INT32; use the 64-bit form");
+    const int64_t n_items = h_tot[0];
+    *n_items_out = n_items;
+    const bool fits = n_items <= items_cap && (n_items == 0 || items_out);
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(counts_out, g.counts.p, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));
+        if (fits && n_items > 0) {
+            HIP_TRY(hipMemcpyAsync(items_out, g.h_out.p, (size_t)n_items * 4 * elt, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(features_out, g.h_aux.p, (size_t)n_items * LATOK_FEATURE_COUNT, hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (n_items > items_cap) return fail(LATOK_ERR_INVALID, "output capacity too small: need %lld", (long long)n_items);
+    if (n_items > 0 && !items_out) return fail(LATOK_ERR_INVALID, "output buffer is NULL");
+    return LATOK_OK;
+}
+
 // Shared body of the compaction entry points: argument checks, staging of host-pointer batches, one synchronisation.
 // cp_units: a UTF-8 batch (b.row = byte offsets, b.total = bytes) whose results are in code-point units.
 static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units, void* counts_out, void* items_out, int8_t* features_out,
@@ -1332,7 +1478,7 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
         rc = compact_common(g, spans, feats, cps, false, counts_out, items_out, features_out, items_cap, n_items_out, flags, stream);
         g.last_route = 1;
         if (rc != LATOK_OK || cp_units || !items_out) return rc;
-        const int64_t per = spans ? 2 : 1;
+        const int64_t per = feats ? 4 : (spans ? 2 : 1);
         int64_t k = 0;
         for (int64_t s = 0; s < n_str; ++s) {
             const int64_t n = o32 ? (int64_t)((const int32_t*)counts_out)[s] : ((const int64_t*)counts_out)[s];
@@ -1356,6 +1502,14 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
     if (b.total > 0 && !b.in.p) return fail(LATOK_ERR_INVALID, "NULL buffer");
     const size_t elt = o32 ? 4 : 8;                                   // width of counts and of every record field
     const size_t item_bytes = (feats ? 4 : (spans ? 2 : 1)) * elt;
+    if (feats && b.in.form == Form::Utf8 && !cp_units) {   // featurize in byte space: a route of its own
+        if (b.total == 0) {
+            if (dev) HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)n_str * elt, st));
+            else memset(counts_out, 0, (size_t)n_str * elt);
+            return LATOK_OK;
+        }
+        return features_utf8_bytes_route(g, b, dev, o32, counts_out, items_out, features_out, items_cap, n_items_out, st);
+    }
     if (!dev && !cp_units && b.total >= kPipeMinChars)
         return compact_host_pipelined(g, spans, feats, o32, b, counts_out, items_out, items_cap, n_items_out, features_out, st);
     Batch d = b;   // the batch as the kernels read it
@@ -1682,6 +1836,16 @@ int latok_token_spans_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_
     LATOK_ENTER();
     return compact_common(g, true, false, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total_bytes}, false, counts_out, spans_out,
                           nullptr, spans_cap, n_tokens_out, flags, stream);
+}
+
+/* featurize in byte space: byte positions in the span records, feature sums per char (enqueue_utf8_bytes_features) */
+int latok_token_features_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                          int64_t* counts_out, int64_t* spans4_out, int8_t* features_out, int64_t cap,
+                                          int64_t* n_tokens_out, int flags, void* stream) {
+    LATOK_ENTER();
+    if (!features_out && cap > 0) return fail(LATOK_ERR_INVALID, "features_out is NULL");
+    return compact_common(g, true, true, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total_bytes}, false, counts_out, spans4_out,
+                          features_out, cap, n_tokens_out, flags, stream);
 }
 
 /* PEP 393 buffers (the reference's own input, latok.c:53-55,79): fixed-width code units of 1, 2 or 4 bytes */
@@ -2096,7 +2260,8 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
 
 /* test hook (not part of the ABI): the route the last compaction call (offsets / spans / featurize) of the current context took --
  * 0: the batch's own units (UTF-32, PEP 393 units, UTF-8 in byte space), 1: a small UTF-8 host batch decoded by the host,
- * 2: UTF-8 through the staged device decoder, 3: UTF-8 through byte space and the packed code-point masks (and codes) */
+ * 2: UTF-8 through the staged device decoder, 3: UTF-8 through byte space and the packed code-point masks (and codes),
+ * 4: featurize of UTF-8 in byte space (byte records from the byte-space masks, sums from the packed code-point masks) */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;
@@ -2273,7 +2438,8 @@ static int flow_submit_compact(Ctx& g, bool spans, bool feats, const Batch& b, v
     }
     if (!b.in.p || !b.row || !counts || ((!items || (feats && !feat)) && cap > 0)) return fail(LATOK_ERR_INVALID, "NULL buffer");
     if (cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
-    if (feats && b.in.form == Form::Utf8) return fail(LATOK_ERR_INVALID, "featurize reads code points or PEP 393 units, not UTF-8 bytes");
+    if (feats && b.in.form == Form::Utf8)
+        return fail(LATOK_ERR_INVALID, "featurize of UTF-8 bytes has calls of its own (latok_flow_token_features_utf8 / _utf8_bytes)");
     if (((uintptr_t)b.in.p & 15) != 0) return fail(LATOK_ERR_INVALID, "device input pointer must be 16-byte aligned");
     const bool o32 = (flags & LATOK_OUT_INT32) != 0;
     if (((uintptr_t)items & 15) != 0 || ((uintptr_t)counts & (o32 ? 3 : 7)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
@@ -2368,7 +2534,7 @@ int latok_flow_token_features(const void* units_dev, int kind, const int64_t* ro
 // result[3], gates the records and feature sums on the device and is read by the caller after latok_flow_wait.  The lead-byte
 // mask, the byte-space SPACE plane, the packed code-point masks, the code-point row offsets and the rule codes are buffers of
 // the slot's workspace.
-enum { kU8Mask = 0, kU8Offsets = 1, kU8Spans = 2, kU8Feats = 3 };
+enum { kU8Mask = 0, kU8Offsets = 1, kU8Spans = 2, kU8Feats = 3, kU8BytesFeats = 4 };   // (4: records in BYTE positions)
 struct Utf8Flow {
     int what = kU8Mask;
     const uint8_t* u8 = nullptr;
@@ -2387,9 +2553,11 @@ struct Utf8Flow {
 constexpr int kU8FlowRanges = 8;
 // every range of caller memory the batch touches, outputs first (what flow_hazards.h orders it by); returns their number
 static int utf8_flow_ranges(const Utf8Flow& a, latok::FlowRange* r) {
-    const size_t rec = a.o32 ? 4 : 8, fields = a.what == kU8Feats ? 4 : (a.what == kU8Spans ? 2 : 1);
+    const size_t rec = a.o32 ? 4 : 8, fields = a.what >= kU8Feats ? 4 : (a.what == kU8Spans ? 2 : 1);
     const size_t n_str = (size_t)std::max<int64_t>(a.n_str, 0), bytes = (size_t)std::max<int64_t>(a.total_bytes, 0);
-    const size_t cap = (size_t)std::max<int64_t>(a.cap, 0);
+    // (a batch has at most one item per byte: no more of the record buffers can be written, and a huge "unbounded" capacity
+    // cannot wrap the tracked length into an empty range)
+    const size_t cap = std::min((size_t)std::max<int64_t>(a.cap, 0), bytes);
     int n = 0;
     r[n++] = latok::flow_range(a.result, 32, true);
     if (a.what == kU8Mask) {
@@ -2399,7 +2567,7 @@ static int utf8_flow_ranges(const Utf8Flow& a, latok::FlowRange* r) {
     } else {
         r[n++] = latok::flow_range(a.counts, n_str * rec, true);
         r[n++] = latok::flow_range(a.items, bytes ? cap * fields * rec : 0, true);
-        if (a.what == kU8Feats) r[n++] = latok::flow_range(a.feat, bytes ? cap * LATOK_FEATURE_COUNT : 0, true);
+        if (a.what >= kU8Feats) r[n++] = latok::flow_range(a.feat, bytes ? cap * LATOK_FEATURE_COUNT : 0, true);
     }
     r[n++] = latok::flow_range(a.u8, bytes, false);
     r[n++] = latok::flow_range(a.boff, n_str ? (n_str + 1) * 8 : 0, false);
@@ -2407,12 +2575,12 @@ static int utf8_flow_ranges(const Utf8Flow& a, latok::FlowRange* r) {
 }
 
 /* test hook (not part of the ABI; needs no device): the ranges a code-point UTF-8 flow batch notes, in the form
- * latok_debug_flow_route takes them.  what: 0 mask, 1 offsets, 2 token spans, 3 featurize; addr[8] = {utf8, byte_off, mask or
+ * latok_debug_flow_route takes them.  what: 0 mask, 1 offsets, 2 token spans, 3 featurize, 4 featurize in byte space; addr[8] = {utf8, byte_off, mask or
  * counts, cp_row_off or records, features, result, 0, 0}; cap = mask_cap_words or the record capacity.  Returns the number of
  * ranges written to lo / bytes / is_write (at most n_max), < 0 on a bad argument. */
 extern "C" int latok_debug_flow_utf8_ranges(int what, const uint64_t* addr, int64_t n_str, int64_t total_bytes, int64_t cap, int flags,
                                             uint64_t* lo, uint64_t* bytes, int* is_write, int n_max) {
-    if (what < kU8Mask || what > kU8Feats || !addr || !lo || !bytes || !is_write) return fail(LATOK_ERR_INVALID, "bad argument");
+    if (what < kU8Mask || what > kU8BytesFeats || !addr || !lo || !bytes || !is_write) return fail(LATOK_ERR_INVALID, "bad argument");
     Utf8Flow a;
     a.what = what;
     a.u8 = (const uint8_t*)(uintptr_t)addr[0];
@@ -2449,7 +2617,7 @@ static int flow_submit_utf8(Ctx& g, const Utf8Flow& a) {
     if (((uintptr_t)a.result & 7) != 0) return fail(LATOK_ERR_INVALID, "result pointer must be 8-byte aligned");
     if (a.n_str < 0) return fail(LATOK_ERR_INVALID, "n_str must be >= 0");
     if (a.cap < 0 || a.mask_cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
-    const bool mask = a.what == kU8Mask, spans = a.what >= kU8Spans, feats = a.what == kU8Feats;
+    const bool mask = a.what == kU8Mask, spans = a.what >= kU8Spans, feats = a.what >= kU8Feats;
     const int64_t n_str = a.n_str, total_bytes = a.total_bytes;
     const size_t rec = a.o32 ? 4 : 8;
     latok::FlowRange r[kU8FlowRanges];
@@ -2482,6 +2650,21 @@ static int flow_submit_utf8(Ctx& g, const Utf8Flow& a) {
     ++g.flow_seq;
     const hipStream_t st = f.st;
     HIP_TRY(hipMemsetAsync(a.result, 0, 32, st));
+    if (a.what == kU8BytesFeats) {   // records in byte positions: the sequence the blocking call enqueues, on the slot
+        Utf8BytesFeats k;
+        k.b = Batch{Input{a.u8, Form::Utf8}, a.boff, n_str, total_bytes};
+        k.o32 = a.o32;
+        k.counts = a.counts;
+        k.items = a.items;
+        k.feat = a.feat;
+        k.cap = a.cap;
+        k.r_items = a.result;
+        k.r_err = a.result + 1;
+        k.r_cps = a.result + 2;
+        k.r_odd = a.result + 3;
+        k.st = st;
+        return enqueue_utf8_bytes_features(g, w, k);
+    }
     unsigned epoch = 0;
     if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
     uint64_t* d_bmask = (uint64_t*)w.bits.p;
@@ -2565,6 +2748,11 @@ int latok_flow_token_spans_utf8(const uint8_t* utf8_dev, const int64_t* byte_off
 int latok_flow_token_features_utf8(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
                                    void* counts_dev, void* spans4_dev, int8_t* features_dev, int64_t cap, int64_t* result_dev, int flags) {
     return flow_utf8_compact_entry(kU8Feats, utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, spans4_dev, features_dev, cap,
+                                   result_dev, flags);
+}
+int latok_flow_token_features_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                         void* counts_dev, void* spans4_dev, int8_t* features_dev, int64_t cap, int64_t* result_dev, int flags) {
+    return flow_utf8_compact_entry(kU8BytesFeats, utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, spans4_dev, features_dev, cap,
                                    result_dev, flags);
 }
 int latok_flow_wait(void) {

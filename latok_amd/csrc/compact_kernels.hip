@@ -238,7 +238,9 @@ __global__ __launch_bounds__(256) void k_string_counts(const uint64_t* __restric
 //       word's end follows the masks further) and puts the records into an LDS window at their rank inside the wave;
 //   (c) streams the window to the output: consecutive lanes write consecutive 8-byte words.
 // KIND 0: offsets[k] = p - start of its string.   KIND 1: spans[2k..] = stripped extent.
-// (featurize writes its 4-value span records from k_features_tiles, together with the sums)
+// KIND 2: spans4[4k..] = {raw start, raw end, stripped start, stripped end}: featurize's span record, for UTF-8 in BYTE space --
+// the sums of the same tokens are formed in code-point space by k_features_tiles, which then writes no records (a token has
+// the same rank in both spaces).  The other forms of featurize get their records from k_features_tiles, together with the sums.
 constexpr int scatter_waves(int kind) { return 4; }   // waves per workgroup
 
 __device__ __forceinline__ int64_t scatter_lower_bound(const int64_t* __restrict__ row_off, int64_t n_entries, int64_t c,
@@ -441,20 +443,22 @@ __device__ __forceinline__ void counts_scatter_block(
                     const uint64_t X = (o_xb >> b) | ((o_xb1 << 1) << (63 - b));     // boundaries at p, p+1, ..
                     const uint64_t N = (o_nn >> b) | ((o_nn1 << 1) << (63 - b));     // non-SPACE chars at p, p+1, ..
                     const uint64_t after = X & ~1ull;
-                    int64_t a2, e2;
+                    const int64_t p = obase + b;
+                    int64_t e, a2, e2;                              // (e: the raw end, KIND 2 only)
                     if (after) {                                    // the token ends within 64 chars (kept => seg != 0)
                         const uint64_t seg = N & (((after & (~after + 1ull)) - 1ull));
-                        const int64_t p = obase + b;
+                        e = p + __builtin_ctzll(after);
                         a2 = p + __builtin_ctzll(seg);
                         e2 = p + 64 - __builtin_clzll(seg);
                     } else if (o_xb1 & ~((1ull << b) - 1ull)) {     // (rare) longer: ends at a boundary of the next word beyond p + 63
                         const int eb = __builtin_ctzll(o_xb1 & ~((1ull << b) - 1ull));
                         const uint64_t seg0 = o_nn & (~0ull << b);
                         const uint64_t seg1 = o_nn1 & ((1ull << eb) - 1ull);
+                        e = obase + 64 + eb;
                         a2 = seg0 ? obase + __builtin_ctzll(seg0) : obase + 64 + __builtin_ctzll(seg1);
                         e2 = seg1 ? obase + 128 - __builtin_clzll(seg1) : obase + 64 - __builtin_clzll(seg0);
                     } else {                                        // (rare) no boundary up to the end of the next word
-                        const int64_t e = next_set_bit(bits, obase + 128, total);
+                        e = next_set_bit(bits, obase + 128, total);
                         const uint64_t seg = o_nn & (~0ull << b);
                         a2 = seg ? obase + __builtin_ctzll(seg) : (o_nn1 ? obase + 64 + __builtin_ctzll(o_nn1) : next_zero_bit(space, obase + 128, e));
                         e2 = prev_zero_end(space, a2, e);
@@ -463,7 +467,26 @@ __device__ __forceinline__ void counts_scatter_block(
                     out2 v;
                     v.x = (OUT)(a2 - lo);
                     v.y = (OUT)(e2 - lo);
-                    __builtin_nontemporal_store(v, reinterpret_cast<out2*>(out) + base_out + win0 + j);
+                    if (KIND == 2) {                                // the record is 16 or 32 bytes: aligned 16-byte stores
+                        if (sizeof(OUT) == 4) {
+                            typedef OUT out4 __attribute__((ext_vector_type(4)));
+                            out4 r;
+                            r.x = (OUT)(p - lo);
+                            r.y = (OUT)(e - lo);
+                            r.z = v.x;
+                            r.w = v.y;
+                            __builtin_nontemporal_store(r, reinterpret_cast<out4*>(out) + base_out + win0 + j);
+                        } else {
+                            out2 r;
+                            r.x = (OUT)(p - lo);
+                            r.y = (OUT)(e - lo);
+                            out2* rec = reinterpret_cast<out2*>(out) + 2 * (base_out + win0 + j);
+                            __builtin_nontemporal_store(r, rec);
+                            __builtin_nontemporal_store(v, rec + 1);
+                        }
+                    } else {
+                        __builtin_nontemporal_store(v, reinterpret_cast<out2*>(out) + base_out + win0 + j);
+                    }
                 }
             }
         }
@@ -927,6 +950,7 @@ hipError_t launch_counts_scatter(int kind, bool out32, const uint64_t* bits, con
 #define LATOK_CS(K, T) launch_counts_scatter_t<K, T>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, \
                                                      n_str, tile_first, out, n_items_dev, cap, counts, err, st, done, dt)
     if (kind == 0) return out32 ? LATOK_CS(0, int32_t) : LATOK_CS(0, int64_t);
+    if (kind == 2) return out32 ? LATOK_CS(2, int32_t) : LATOK_CS(2, int64_t);
     return out32 ? LATOK_CS(1, int32_t) : LATOK_CS(1, int64_t);
 #undef LATOK_CS
 }

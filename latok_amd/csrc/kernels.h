@@ -158,6 +158,7 @@ struct FeatParams {
     const uint64_t* space;        // SPACE bitmask (only walked for tokens that span more than two words)
     int8_t* features;             // [n_tokens][25]
     void* spans4;                 // [n_tokens][4] = {raw start, raw end, stripped start, stripped end}, string relative; int64 or int32
+                                  // NULL: no span records, only the sums (UTF-8 in byte space: launch_counts_scatter kind 2 writes them)
     bool out32;                   // spans4 holds int32
     const int64_t* n_tokens_dev;  // device: total tokens of the batch (k_word_counts_scan) ...
     int64_t cap;                  // ... nothing is written when it exceeds the caller's capacity
@@ -230,6 +231,7 @@ hipError_t launch_word_counts_scan(bool spans, const uint64_t* bits, const uint6
 hipError_t launch_string_counts(bool out32, const uint64_t* mask, const int64_t* tile_rank, const uint16_t* word_pref,
                                 const int64_t* row_off, int64_t n_str, int64_t total, const int64_t* n_items, void* counts, int* err,
                                 hipStream_t st, DeviceTotal dt = DeviceTotal{nullptr, nullptr});
+// kind 0 = offsets, 1 = stripped token spans, 2 = featurize's 4-field span records {raw start, raw end, stripped start, stripped end}
 hipError_t launch_counts_scatter(int kind, bool out32, const uint64_t* bits, const uint64_t* space, const uint64_t* item_mask,
                                  const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words,
                                  int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,

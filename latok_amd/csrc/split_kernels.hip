@@ -2133,8 +2133,8 @@ __device__ __forceinline__ void feature_tile(const FeatParams& P, const TileLds&
                     const uint32_t cq = (uint32_t)__shfl((int)C.v[q], owner);
                     if (!above) sum.v[q] = swar_add_u8(sum.v[q], cq);
                 }
-                if (active) {
-                    put_record(fwin + shift, j, sum);
+                if (active) put_record(fwin + shift, j, sum);
+                if (active && spans4) {   // (spans4 == NULL: the records come from another kernel, see below)
                     const lk_u64 o_nn = ~o_S & ovalid;
                     const int64_t p = obase + b;
                     const lk_u64 bl = o_B & ((2ull << b) - 1ull);
@@ -2245,6 +2245,9 @@ __device__ __forceinline__ void feature_tile(const FeatParams& P, const TileLds&
 
     // ---- the span records of the same tokens: {raw start, raw end, stripped start, stripped end}, string relative --------
     // (reference featurize: LaToken.start_idx / end_idx = the raw span, .text = text[stripped]; default_tokenizer.py:173-191)
+    // spans4 == NULL (uniform): UTF-8 in byte space -- these positions are code points, the caller wants bytes: the records of the
+    // same tokens, at the same ranks, are written by k_counts_scatter<2> from the byte-space masks (compact_kernels.hip)
+    if (!spans4) return;
     OUT* swin = reinterpret_cast<OUT*>(L.stage);
     constexpr int kSpanRound = span_round<OUT>();
     lk_u64 rest = x;

@@ -14,6 +14,12 @@
                   (the `utf8_flow` leg) UTF-8 in code-point units through the batch flow (latok_flow_*_utf8): two batches in
                   flight with alternating output buffers and result words, nothing read by the host between the launches;
                   the result words of the last two batches are checked after the wait (no malformed flag, the blocking item count)
+  utf8_bytes_features32 / utf8_bytes_features32_flow   latok_token_features_utf8_bytes_batch / latok_flow_token_features_utf8_bytes
+                  with LATOK_OUT_INT32: featurize in BYTE space (4-field byte records + the 25 sums per char)
+  pair_features32_bytes_spans32 / pair_features32_bytes_spans32_flow   what a byte-space caller had to run before that call
+                  existed: latok_token_features_utf8_batch, then latok_token_spans_utf8_bytes_batch on the same batch (their
+                  flow forms for the flow line; records of the two calls in buffers of their own).  Only symbols that older
+                  libraries have too, so the same two paths can be timed against a library built from an earlier commit
   utf8_decode_features32   what a UTF-8 caller had to compose before: latok_utf8_decode_batch into a device buffer, then
                   latok_token_features_batch on it (LATOK_OUT_INT32); same data, same process
   bytes_mask / bytes_offsets / bytes_spans   latok_*_utf8_bytes_batch (8f-3 fused: the tile kernel reads the bytes)
@@ -76,6 +82,7 @@ def main():
     ap.add_argument("--cpu", type=int, default=0, help="strings of CPU baseline (0 = skip)")
     ap.add_argument("--paths", default="mask,mask_flow,bytes_mask_flow,kind_mask_flow,offsets32_flow,spans32_flow,features32_flow,offsets,offsets32,spans,spans32,features,features32,utf8_mask,utf8_offsets,utf8_offsets32,utf8_spans,utf8_spans32,utf8_features32,"
                                        "utf8_mask_flow,utf8_offsets_flow,utf8_offsets32_flow,utf8_spans_flow,utf8_spans32_flow,utf8_features32_flow,utf8_decode_features32,"
+                                       "utf8_bytes_features32,utf8_bytes_features32_flow,pair_features32_bytes_spans32,pair_features32_bytes_spans32_flow,"
                                        "bytes_mask,bytes_offsets,bytes_spans,rules_mask,kind_mask,kind_offsets,kind_offsets32,"
                                        "kind_spans,kind_spans32")
     args = ap.parse_args()
@@ -278,6 +285,58 @@ def main():
                                                                  d_feat4 if i & 1 else d_feat, cap, res_of(i), _lib.OUT_INT32),
                     lambda k: n8 + csr + 4 * n + (16 + 25) * k,
                     "UTF-8 bytes + 8 B/string read (the input ONCE); 4 B/string + 41 B/token written (LATOK_OUT_INT32)")
+    # featurize in byte space, and the pair of calls it replaces; every line of this leg in one process run
+    bytes_leg = [p for p in paths if p.startswith("utf8_bytes_features32") or p.startswith("pair_features32_bytes_spans32")]
+    if bytes_leg:
+        bufs = [lib.latok_dev_alloc(sz) for sz in (cap * 16, n * 4, cap * 25, cap * 8, n * 4, cap * 16, n * 4, cap * 25, cap * 8, n * 4, 256)]
+        if not all(bufs):
+            raise RuntimeError(_lib.last_error())
+        (b_items, b_counts, b_feat, b_spans, b_scounts), (c_items, c_counts, c_feat, c_spans, c_scounts), d_resb = bufs[:5], bufs[5:10], bufs[10]
+        res4 = lambda i: C.c_void_p(d_resb + 32 * (i & 1))        # noqa: E731 -- four result words per batch in flight
+        res2 = lambda i: C.c_void_p(d_resb + 128 + 16 * (i & 1))  # noqa: E731 -- two for the byte-space spans of the pair
+        note41 = "UTF-8 bytes + 8 B/string read (the input ONCE); 4 B/string + 41 B/token written (LATOK_OUT_INT32)"
+        note_pair = "two calls: " + note41 + ", then UTF-8 bytes + 8 B/string read again; 4 B/string + 8 B/token written"
+
+        def pair_blocking():
+            rc = lib.latok_token_features_utf8_batch(d_u8, d_boff, n, n8, b_counts, b_items, b_feat, cap, C.byref(nout), D32, None)
+            return rc or lib.latok_token_spans_utf8_bytes_batch(d_u8, d_boff, n, n8, b_scounts, b_spans, cap, C.byref(nout), D32, None)
+
+        def pair_flow(i):
+            x = (c_items, c_counts, c_feat, c_spans, c_scounts) if i & 1 else (b_items, b_counts, b_feat, b_spans, b_scounts)
+            rc = lib.latok_flow_token_features_utf8(d_u8, d_boff, n, n8, x[1], x[0], x[2], cap, res4(i), _lib.OUT_INT32)
+            return rc or lib.latok_flow_token_spans(d_u8, 0, d_boff, n, n8, x[4], x[3], cap, res2(i), _lib.OUT_INT32)
+
+        def flow_words(name, items_n, pair):
+            res = np.empty(24, np.int64)
+            _lib.check(lib.latok_memcpy_d2h(res.ctypes.data, d_resb, 192))
+            for r4 in res[:8].reshape(2, 4):
+                assert r4[3] == 0 and r4[1] == 0 and r4[2] == total and r4[0] == items_n, (name, r4.tolist())
+            for r2 in res[16:20].reshape(2, 2) if pair else ():
+                assert r2[1] == 0 and r2[0] == items_n, (name, r2.tolist())
+
+        for name in bytes_leg:   # in the order given
+            if name == "pair_features32_bytes_spans32":
+                run(name, pair_blocking, lambda: 2 * (n8 + csr) + 8 * n + (16 + 25 + 8) * nout.value, note_pair)
+            elif name == "pair_features32_bytes_spans32_flow":
+                _lib.check(pair_blocking())
+                items_n = nout.value
+                run_flow(name, pair_flow, lambda: 2 * (n8 + csr) + 8 * n + (16 + 25 + 8) * items_n, note_pair)
+                flow_words(name, items_n, True)
+            elif name == "utf8_bytes_features32":
+                run(name, lambda: lib.latok_token_features_utf8_bytes_batch(d_u8, d_boff, n, n8, b_counts, b_items, b_feat, cap, C.byref(nout), D32, None),
+                    lambda: n8 + csr + 4 * n + (16 + 25) * nout.value, note41 + "; byte positions")
+            elif name == "utf8_bytes_features32_flow":
+                _lib.check(lib.latok_token_features_utf8_bytes_batch(d_u8, d_boff, n, n8, b_counts, b_items, b_feat, cap, C.byref(nout), D32, None))
+                items_n = nout.value
+                run_flow(name, lambda i: lib.latok_flow_token_features_utf8_bytes(d_u8, d_boff, n, n8, c_counts if i & 1 else b_counts,
+                                                                                  c_items if i & 1 else b_items, c_feat if i & 1 else b_feat, cap,
+                                                                                  res4(i), _lib.OUT_INT32),
+                         lambda: n8 + csr + 4 * n + (16 + 25) * items_n, note41 + "; byte positions")
+                flow_words(name, items_n, False)
+            else:
+                raise SystemExit("unknown path " + name)
+        for p_ in bufs:
+            lib.latok_dev_free(p_)
     if "utf8_decode_features32" in paths:
         d_dec, d_decrow = lib.latok_dev_alloc(total * 4 + 64), lib.latok_dev_alloc((n + 1) * 8)
         if not d_dec or not d_decrow:
