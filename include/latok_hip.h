@@ -195,6 +195,30 @@ int latok_token_features_utf8_bytes_batch(const uint8_t* utf8, const int64_t* by
                                           int64_t* counts_out, int64_t* spans4_out, int8_t* features_out, int64_t cap,
                                           int64_t* n_tokens_out, int flags, void* stream);
 
+/* Joined token text in byte space: the tokens themselves, not positions -- what the reference's tokenize() yields
+ * (default_tokenizer.py:149-160), one line per string.  Input as latok_token_spans_utf8_bytes_batch takes it; sep is one byte,
+ * any value 0..255 (another value is refused before any device work).  For string s let (a_k, e_k), k = 0 .. c_s - 1, be the
+ * records latok_token_spans_utf8_bytes_batch reports for it (stripped, non-empty tokens as byte ranges relative to byte_off[s]):
+ *   row(s)       = sep.join(utf8[byte_off[s] + a_k : byte_off[s] + e_k] for k in 0 .. c_s - 1)
+ *   out_off[0]   = 0
+ *   out_off[s+1] = out_off[s] + len(row(s)) = out_off[s] + sum(e_k - a_k) + max(c_s - 1, 0)
+ *   out_bytes[out_off[s] : out_off[s+1]] = row(s)
+ *   counts_out[s] = c_s                            (counts_out may be NULL; LATOK_OUT_INT32 applies to it alone, out_off is int64)
+ * Under the built-in tables, for a non-empty well-formed string, row(s) = sep.join(tokenize(text)).encode("utf-8") of the
+ * reference.  An empty and a whitespace-only string give an empty row (the reference raises on ''; batch mode, see above).  The
+ * bytes of a span are copied verbatim and the spans call defines the spans: run-time rule tables, truncated sequences, lone lead
+ * bytes and stray continuation bytes need no rule of their own, nothing is refused as malformed.  Every kept token has at least
+ * one byte and brings at most one separator, so out_off[n_str] <= 2 * total_bytes ("a,b" -> "a , b"): size buffers by it.
+ * Capacity protocol, in BYTES: out_cap too small -> nothing is written to out_bytes, out_off and counts stay valid, the needed
+ * size is in *n_out_bytes and the call returns LATOK_ERR_INVALID; out_cap = 0 with out_bytes = NULL is a size query; out_bytes =
+ * NULL with out_cap > 0 is refused.  Host pointers or LATOK_DEVICE_PTRS (device UTF-8 pointer 16-byte aligned), total_bytes = -1
+ * as in the sibling calls; a flag bit other than these two is refused.  With device pointers the call synchronises once; with
+ * host pointers a second time behind the copy of the bytes (their number is known only after the first).  Every batch size takes the
+ * same kernels and gives the same bytes. */
+int latok_join_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                       int sep, uint8_t* out_bytes, int64_t out_cap, int64_t* out_off /* int64[n_str+1] */,
+                                       void* counts_out /* may be NULL */, int64_t* n_out_bytes, int flags, void* stream);
+
 /* Token feature vectors: reference featurize() (default_tokenizer.py:163-191) for a whole batch without the n x 25
  * matrix.  Per kept token k: spans4_out[4k..4k+3] = {raw_start, raw_end, strip_start, strip_end} (LaToken.start_idx /
  * end_idx are the raw span, LaToken.text is text[strip_start:strip_end]); features_out[25k..25k+24] = sum of the 25
@@ -372,6 +396,15 @@ int latok_flow_token_features_utf8(const uint8_t* utf8_dev, const int64_t* byte_
 int latok_flow_token_features_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
                                          void* counts_dev, void* spans4_dev, int8_t* features_dev, int64_t cap,
                                          int64_t* result_dev /* int64[4] */, int flags);
+/* Joined token text through the flow: what latok_join_tokens_utf8_bytes_batch reports (sep.join of every string's tokens,
+ * reference default_tokenizer.py:149-160; the definition is at that call), byte-identical, without waiting: result[0] = output
+ * bytes (= out_off[n_str]), result[1] = error word -- bit 0: a string too long for LATOK_OUT_INT32 counts, bit 2 (value 4): the
+ * batch needs more than out_cap bytes (nothing was written to out_bytes; out_off, counts and result[0] are valid), upper half: the
+ * scan's internal flag.  Read them after latok_flow_wait.  counts_dev may be NULL.  The ordering rule covers the input bytes,
+ * byte_off, out_bytes (min(out_cap, 2 * total_bytes) bytes of it), out_off, counts and the result words. */
+int latok_flow_join_tokens_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                      int sep, uint8_t* out_bytes_dev, int64_t out_cap, int64_t* out_off_dev,
+                                      void* counts_dev, int64_t* result_dev /* int64[2]: output bytes, error word */, int flags);
 int latok_flow_wait(void);
 
 /* ---- measurement ----------------------------------------------------------------------------------------------- */

@@ -406,6 +406,63 @@ def tokenize_utf8_batch(blobs):
     return out
 
 
+# joined token text: the tokens themselves, each string's joined by one separator (what a pre-tokenized corpus holds)
+def _sep_byte(sep) -> int:
+    """the separator as one byte value; anything else is a ValueError (raised before any device is asked for)"""
+    if isinstance(sep, (bytes, bytearray)) and len(sep) == 1:
+        return sep[0]
+    if isinstance(sep, (int, np.integer)) and not isinstance(sep, bool) and 0 <= int(sep) <= 255:
+        return int(sep)
+    raise ValueError("sep must be one byte (bytes of length 1, or an int 0..255)")
+
+
+def _join_csr(utf8, byte_off, sep, dtype, want_counts):
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    sep = _sep_byte(sep)
+    dt, flags = _out_dtype(dtype)
+    n_str = byte_off.size - 1
+    total = int(byte_off[-1]) if n_str > 0 else 0
+    lib = _lib.ensure_init()
+    cap = max(2 * total, 1)                              # a kept token has >= 1 byte and brings <= 1 separator
+    out = np.empty(cap, np.uint8)
+    out_off = np.zeros(n_str + 1, np.int64)
+    counts = np.zeros(n_str, dt) if want_counts else None
+    n = C.c_int64(0)
+    _lib.check(lib.latok_join_tokens_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, sep, _ptr(out), cap, _ptr(out_off),
+                                                      _ptr(counts) if want_counts else None, C.byref(n), flags, None))
+    return out[:n.value], out_off, counts
+
+
+def join_tokens_utf8_csr(utf8, byte_off, sep=b" ", dtype=np.int64):
+    """(out_bytes uint8[], out_off int64[n+1], counts): every string's stripped, non-empty tokens -- the byte ranges
+    token_spans_utf8_bytes_csr reports -- joined by the one-byte ``sep``, all rows back to back: row s =
+    out_bytes[out_off[s]:out_off[s+1]] = sep.join(tokens of string s); counts[s] = its number of tokens (``dtype``; out_off is
+    always int64).  Cut, joined and written on the device (``latok_join_tokens_utf8_bytes_batch``)."""
+    out, out_off, counts = _join_csr(utf8, byte_off, sep, dtype, True)
+    return out.copy(), out_off, counts
+
+
+def join_tokens_utf8_batch(blobs, sep=b" "):
+    """list[bytes] (UTF-8) -> list[bytes]: ``sep.join(tokens)`` of every string -- the rows ``[sep.join(t) for t in
+    tokenize_utf8_batch(blobs)]`` gives, without a token-by-token loop on the host ('' and whitespace-only -> b'')."""
+    sep_b = _sep_byte(sep)
+    if len(blobs) == 0:
+        return []
+    utf8, byte_off = pack_utf8(blobs)
+    out, out_off, _ = _join_csr(utf8, byte_off, sep_b, np.int64, False)
+    buf, o = out.tobytes(), out_off.tolist()
+    return [buf[a:b] for a, b in zip(o[:-1], o[1:])]
+
+
+def join_tokens_batch(texts, sep=" "):
+    """list[str] -> list[str]: ``sep.join(tokenize(text))`` of every string ('' -> ''); ``sep`` is one ASCII character.  The
+    strings go through UTF-8 ("surrogatepass") and the byte-space call; rows are decoded one by one."""
+    if not isinstance(sep, str) or len(sep) != 1 or ord(sep) > 0x7F:
+        raise ValueError("sep must be one ASCII character")
+    rows = join_tokens_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], sep.encode("ascii"))
+    return [r.decode("utf-8", "surrogatepass") for r in rows]
+
+
 # ---- PEP 393 code units: 1 / 2 / 4 bytes per char, the buffer the reference itself reads (latok.c:53-55,79) -----------
 def pack_kind(texts):
     """list[str] -> (units, row_off): units uint8 / uint16 / uint32 = the narrowest PEP 393 kind that holds every char of
@@ -652,6 +709,20 @@ def flow_token_features_utf8_bytes(d_utf8, d_byte_off, n_str, total_bytes, d_cou
     _, flag32 = _out_dtype(dtype)
     _lib.check(lib.latok_flow_token_features_utf8_bytes(d_utf8, d_byte_off, int(n_str), int(total_bytes), d_counts, d_spans4, d_features,
                                                         int(cap), d_result, flag32))
+
+
+def flow_join_tokens_utf8_bytes(d_utf8, d_byte_off, n_str, total_bytes, d_out_bytes, out_cap, d_out_off, d_counts, d_result, sep=b" ",
+                                dtype=np.int64):
+    """joined token text of one device-resident UTF-8 batch through the flow (``latok_flow_join_tokens_utf8_bytes``): what
+    ``join_tokens_utf8_csr`` reports, in device buffers, without waiting.  ``d_result`` = int64[2]: output bytes, error word
+    (bit 2: the batch needs more than ``out_cap`` bytes and nothing was written to ``d_out_bytes``); ``d_counts`` may be None.
+    The arguments follow the C call, except that ``sep`` (its fifth) is a trailing keyword here and ``flags`` is ``dtype`` (the
+    width of the counts), as in the sibling wrappers."""
+    sep = _sep_byte(sep)
+    _, flag32 = _out_dtype(dtype)
+    lib = _lib.ensure_init()
+    _lib.check(lib.latok_flow_join_tokens_utf8_bytes(d_utf8, d_byte_off, int(n_str), int(total_bytes), sep, d_out_bytes, int(out_cap),
+                                                     d_out_off, d_counts, d_result, flag32))
 
 
 def flow_wait():

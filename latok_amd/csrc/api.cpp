@@ -174,6 +174,7 @@ struct Workspace {
     // code-point results of a UTF-8 batch in a flow (flow_submit_utf8): lead-byte mask and SPACE plane over the bytes, the packed
     // code-point masks, the code-point row offsets (the blocking calls keep theirs in the context: Ctx::u_lead ..)
     DevBuf lead, bspace, cpbits, cpspace, cprow;
+    DevBuf jbody, jhead;   // joined token text: the body / head planes over the bytes (k_join_counts)
     // the single-pass scan of k_word_counts_scan keeps its look-back state (chain: per workgroup, chain_ctl: {ticket
     // counter}) between launches: entries carry an epoch, so the array is cleared only when it is (re)allocated or when the
     // 18-bit epoch wraps (next_scan_epoch); *_seen = DevBuf::gen of the allocations it was last cleared in
@@ -181,7 +182,7 @@ struct Workspace {
     bool chain_ready = false;
     void release() {
         for (DevBuf* b : {&summ, &seg_agg, &fix_count, &tile_first, &bits, &space, &kept, &wcnt, &wpref, &bases, &scalar, &chain,
-                          &chain_ctl, &codes, &widened, &lead, &bspace, &cpbits, &cpspace, &cprow})
+                          &chain_ctl, &codes, &widened, &lead, &bspace, &cpbits, &cpspace, &cprow, &jbody, &jhead})
             b->release();
         scan_epoch = chain_seen = chain_ctl_seen = 0;
         chain_ready = false;
@@ -192,12 +193,13 @@ struct WsNeed {
     size_t bytes;   // 0: the batch does not use the buffer
 };
 constexpr int kTileNeeds = 4;   // the first entries of ws_needs: the tile stage
-constexpr int kWsNeeds = 20;
+constexpr int kWsNeeds = 22;
 // The one sizing rule of a workspace: every buffer a batch of `units` positions uses and its byte size.  token spans (spans)
 // add the SPACE and kept planes, featurize (feats) the code bytes, and narrow units read by featurize (widen) a UTF-32 copy.
 // cp_rows > 0: `units` UTF-8 bytes whose results are reported in code points (cp_rows = n_str + 1): every buffer is sized by the
-// byte count, which bounds the code-point count.
-static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, bool spans, bool feats, bool widen, int64_t cp_rows = 0) {
+// byte count, which bounds the code-point count.  join: the two planes of the joined token text (UTF-8 bytes, with spans).
+static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, bool spans, bool feats, bool widen, int64_t cp_rows = 0,
+                                             bool join = false) {
     const size_t t = (size_t)std::max<int64_t>((units + latok::kTile - 1) / latok::kTile, 1);
     const size_t words = (size_t)((units + 63) / 64), c_tiles = (words + 63) / 64;
     return {{{&w.summ, t * 16},
@@ -221,7 +223,9 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, bool s
              {&w.bspace, cp_rows > 0 && spans ? words * 8 + 8 : 0},
              {&w.cpbits, cp_rows > 0 ? words * 8 + 8 : 0},
              {&w.cpspace, cp_rows > 0 && spans ? words * 8 + 8 : 0},
-             {&w.cprow, cp_rows > 0 ? (size_t)cp_rows * 8 : 0}}};
+             {&w.cprow, cp_rows > 0 ? (size_t)cp_rows * 8 : 0},
+             {&w.jbody, join ? words * 8 + 8 : 0},
+             {&w.jhead, join ? words * 8 + 8 : 0}}};
 }
 static int ws_ensure(const WsNeed* needs, int n) {
     for (int i = 0; i < n; ++i) {
@@ -1389,6 +1393,66 @@ static int enqueue_utf8_bytes_features(Ctx& g, Workspace& w, const Utf8BytesFeat
                             (const int64_t*)w.tile_first.p, nullptr, a.feat, a.o32, d_total, a.cap, st, latok::DoneSignal{nullptr, 0, nullptr}, dt);
 }
 
+// Joined token text of a UTF-8 batch in BYTE space (latok_join_tokens_utf8_bytes_batch and its flow form): for every string its
+// stripped, non-empty tokens joined by one separator byte (sep.join(tokenize(text)), reference default_tokenizer.py:149-160).
+// One stream, nothing waits for the host:
+//   tile index -> byte-space tiles -> resolve          boundary mask, smeared SPACE plane over the BYTES
+//   [k_word_counts + k_scan_chained, k_counts_scatter  kept mask and token ranks, per-string token counts -- only when counts are asked for]
+//   k_join_counts                                      body / head planes, output bytes per word and per tile
+//   k_scan_chained                                     tile ranks; THE byte total -> scalar word 0, r_bytes
+//   k_join_scatter                                     the bytes (gate: total <= cap), out_off; bit 2 of the error word if the total exceeds cap
+// Every batch size takes this route: there is no one-launch form and no host decode, so a batch gives the same bytes at every size.
+// `w` was sized by ws_needs(w, total_bytes, true, false, false, 0, true).
+struct JoinTokens {
+    Batch b;                      // UTF-8 bytes on the device, byte offsets, total in bytes (> 0), n_str > 0
+    int sep = ' ';
+    uint8_t* out = nullptr;       // NULL: a size query
+    int64_t cap = 0;
+    int64_t* out_off = nullptr;   // int64[n_str + 1]
+    void* counts = nullptr;       // NULL: not asked for
+    bool o32 = false;             // width of the counts
+    int64_t* r_bytes = nullptr;   // the two result words as the device sees them (cleared by the caller): output bytes,
+    int64_t* r_err = nullptr;     // int32-overflow flag (bit 0) | capacity flag (bit 2) in the low half, scan flag in the high half
+    hipStream_t st = nullptr;
+};
+static int enqueue_join_tokens(Ctx& g, Workspace& w, const JoinTokens& a) {
+    int rc;
+    const hipStream_t st = a.st;
+    const int64_t n_str = a.b.n_str, total = a.b.total, words = (total + 63) / 64, c_tiles = (words + 63) / 64;
+    uint64_t* d_bits = (uint64_t*)w.bits.p;
+    uint64_t* d_space = (uint64_t*)w.space.p;
+    int64_t* d_rank = (int64_t*)w.bases.p;
+    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
+    uint16_t* d_pref = (uint16_t*)w.wpref.p;
+    const int64_t* d_tile_first = (const int64_t*)w.tile_first.p;
+    int64_t* d_total = (int64_t*)w.scalar.p;        // word 0: the byte total (word 2: the token total of the counts)
+    int* d_err = (int*)a.r_err;
+    unsigned epoch = 0;
+    Pipe p;
+    p.b = a.b;
+    p.bits = d_bits;
+    p.space = d_space;
+    p.st = st;
+    if ((rc = run_pipeline(g, w, p))) return rc;
+    if (a.counts) {   // the token counts of the spans call, by its own kernels (the ranks are spent once the counts are written)
+        uint64_t* d_kept = (uint64_t*)w.kept.p;
+        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+        HIP_TRY(latok::launch_word_counts_scan(true, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank, (unsigned long long*)w.chain.p,
+                                               (unsigned*)w.chain_ctl.p, epoch, d_total + 2, nullptr, d_err + 1, st));
+        HIP_TRY(latok::launch_counts_scatter(1, a.o32, d_bits, d_space, d_kept, d_rank, d_tcnt, d_pref, words, total, a.b.row, n_str, d_tile_first,
+                                             nullptr, d_total + 2, 0, a.counts, d_err, st));
+    }
+    uint64_t* d_body = (uint64_t*)w.jbody.p;
+    uint64_t* d_head = (uint64_t*)w.jhead.p;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    HIP_TRY(latok::launch_join_counts(d_bits, d_space, words, total, a.b.row, n_str, d_tile_first, d_body, d_head, d_tcnt, d_pref, st));
+    HIP_TRY(latok::launch_tile_scan(d_tcnt, c_tiles, d_rank, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total, a.r_bytes,
+                                    d_err + 1, st));
+    HIP_TRY(latok::launch_join_scatter((const uint8_t*)a.b.in.p, total, d_body, d_head, d_rank, d_tcnt, d_pref, words, a.b.row, n_str, a.sep, a.out,
+                                       a.cap, d_total, a.out_off, d_err, st));
+    return LATOK_OK;
+}
+
 // The blocking call behind compact_common's checks: b = the caller's UTF-8 batch (total resolved, n_str > 0, total > 0).  Every
 // batch that the host did not decode takes this route, whatever its size.  One synchronisation.
 static int features_utf8_bytes_route(Ctx& g, const Batch& b, bool dev, bool o32, void* counts_out, void* items_out, int8_t* features_out,
@@ -1848,6 +1912,85 @@ int latok_token_features_utf8_bytes_batch(const uint8_t* utf8, const int64_t* by
                           features_out, cap, n_tokens_out, flags, stream);
 }
 
+/* joined token text in byte space: every string's tokens joined by one separator byte (enqueue_join_tokens) */
+int latok_join_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, int sep,
+                                       uint8_t* out_bytes, int64_t out_cap, int64_t* out_off, void* counts_out, int64_t* n_out_bytes,
+                                       int flags, void* stream) {
+    LATOK_ENTER();
+    if (sep < 0 || sep > 255) return fail(LATOK_ERR_INVALID, "sep must be one byte (0..255), got %d", sep);
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (!n_out_bytes) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
+    *n_out_bytes = 0;
+    if (out_cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
+    if (!out_bytes && out_cap > 0) return fail(LATOK_ERR_INVALID, "out_bytes is NULL but out_cap > 0 (a size query passes out_cap = 0)");
+    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0, o32 = (flags & LATOK_OUT_INT32) != 0;
+    const size_t elt = o32 ? 4 : 8;   // width of the counts (out_off is int64 in every mode)
+    int64_t total = total_bytes;
+    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
+    StreamTurn turn(g, stream);
+    hipStream_t st = turn.st;
+    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
+    if (n_str > 0 && !out_off) return fail(LATOK_ERR_INVALID, "out_off is NULL");
+    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (n_str == 0 || total == 0) {   // no byte, no token: empty rows
+        if (dev) {
+            if (out_off) HIP_TRY(hipMemsetAsync(out_off, 0, (size_t)(n_str + 1) * 8, st));
+            if (counts_out && n_str > 0) HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)n_str * elt, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        } else {
+            if (out_off) memset(out_off, 0, (size_t)(n_str + 1) * 8);
+            if (counts_out && n_str > 0) memset(counts_out, 0, (size_t)n_str * elt);
+        }
+        return LATOK_OK;
+    }
+    if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    if (dev && (((uintptr_t)out_off & 7) != 0 || ((uintptr_t)counts_out & (elt - 1)) != 0)) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    g.last_route = 5;
+    Batch d;
+    if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
+    if ((rc = ws_ensure(ws_needs(g.ws, total, true, false, false, 0, true).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+    int64_t* p_tot = (int64_t*)g.pin_tot.d;
+    JoinTokens a;
+    a.b = d;
+    a.sep = sep;
+    a.out = out_bytes;
+    // (a kept token has at least one byte and brings at most one separator: a larger capacity gates nothing, and the staging is sized by it)
+    a.cap = out_bytes ? std::min(out_cap, 2 * total) : 0;
+    a.out_off = out_off;
+    a.counts = counts_out;
+    a.o32 = o32;
+    if (!dev) {
+        if ((rc = g.h_out.ensure((size_t)a.cap + 16)) || (rc = g.h_aux.ensure((size_t)(n_str + 1) * 8)) || (rc = g.counts.ensure((size_t)n_str * 8)))
+            return rc;
+        if (out_bytes) a.out = (uint8_t*)g.h_out.p;
+        a.out_off = (int64_t*)g.h_aux.p;
+        if (counts_out) a.counts = g.counts.p;
+    }
+    h_tot[0] = h_tot[1] = 0;
+    a.r_bytes = p_tot;
+    a.r_err = p_tot + 1;
+    a.st = st;
+    if ((rc = enqueue_join_tokens(g, g.ws, a))) return rc;
+    if (!dev) {   // row offsets and counts are valid whatever the capacity
+        HIP_TRY(hipMemcpyAsync(out_off, a.out_off, (size_t)(n_str + 1) * 8, hipMemcpyDeviceToHost, st));
+        if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_tot[1] >> 32) { g.ws.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
+    if (h_tot[1] & 1) return fail(LATOK_ERR_INVALID, "a string is too long for LATOK_OUT_INT32; use the 64-bit form");
+    const int64_t n = h_tot[0];
+    *n_out_bytes = n;
+    if (n > out_cap) return fail(LATOK_ERR_INVALID, "output capacity too small: need %lld bytes", (long long)n);
+    if (!dev && n > 0) {
+        HIP_TRY(hipMemcpyAsync(out_bytes, a.out, (size_t)n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return LATOK_OK;
+}
+
 /* PEP 393 buffers (the reference's own input, latok.c:53-55,79): fixed-width code units of 1, 2 or 4 bytes */
 static int check_kind(int kind) {
     if (kind != 1 && kind != 2 && kind != 4) return fail(LATOK_ERR_INVALID, "kind must be 1 (Latin-1), 2 (UCS-2) or 4 (UCS-4), got %d", kind);
@@ -2261,7 +2404,8 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
 /* test hook (not part of the ABI): the route the last compaction call (offsets / spans / featurize) of the current context took --
  * 0: the batch's own units (UTF-32, PEP 393 units, UTF-8 in byte space), 1: a small UTF-8 host batch decoded by the host,
  * 2: UTF-8 through the staged device decoder, 3: UTF-8 through byte space and the packed code-point masks (and codes),
- * 4: featurize of UTF-8 in byte space (byte records from the byte-space masks, sums from the packed code-point masks) */
+ * 4: featurize of UTF-8 in byte space (byte records from the byte-space masks, sums from the packed code-point masks),
+ * 5: joined token text of UTF-8 in byte space (every batch size; there is no small-batch route) */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;
@@ -2755,6 +2899,95 @@ int latok_flow_token_features_utf8_bytes(const uint8_t* utf8_dev, const int64_t*
     return flow_utf8_compact_entry(kU8BytesFeats, utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, spans4_dev, features_dev, cap,
                                    result_dev, flags);
 }
+// ---- joined token text in a flow -----------------------------------------------------------------------------------------------
+constexpr int kJoinFlowRanges = 6;
+// every range of caller memory the batch touches, outputs first; returns their number.  The tracked output length is what can be
+// written at most -- min(out_cap, 2 * total_bytes) --, so a huge "unbounded" capacity cannot wrap it into an empty range.
+static int join_flow_ranges(const uint8_t* u8, const int64_t* boff, int64_t n_str_in, int64_t total_bytes, uint8_t* out, int64_t cap,
+                            int64_t* out_off, void* counts, int64_t* result, bool o32, latok::FlowRange* r) {
+    const size_t n_str = (size_t)std::max<int64_t>(n_str_in, 0), bytes = (size_t)std::max<int64_t>(total_bytes, 0);
+    const size_t out_len = std::min((size_t)std::max<int64_t>(cap, 0), 2 * bytes);
+    int n = 0;
+    r[n++] = latok::flow_range(result, 16, true);
+    r[n++] = latok::flow_range(out, out_len, true);
+    r[n++] = latok::flow_range(out_off, (n_str + 1) * 8, true);
+    r[n++] = latok::flow_range(counts, n_str * (o32 ? 4 : 8), true);
+    r[n++] = latok::flow_range(u8, bytes, false);
+    r[n++] = latok::flow_range(boff, n_str ? (n_str + 1) * 8 : 0, false);
+    return n;
+}
+
+/* test hook (not part of the ABI; needs no device): the ranges a join batch of a flow notes, in the form latok_debug_flow_route
+ * takes them.  addr[6] = {utf8, byte_off, out_bytes, out_off, counts, result}.  Returns the number of ranges written to lo / bytes /
+ * is_write (at most n_max), < 0 on a bad argument. */
+extern "C" int latok_debug_flow_join_ranges(const uint64_t* addr, int64_t n_str, int64_t total_bytes, int64_t cap, int flags, uint64_t* lo,
+                                            uint64_t* bytes, int* is_write, int n_max) {
+    if (!addr || !lo || !bytes || !is_write) return fail(LATOK_ERR_INVALID, "bad argument");
+    latok::FlowRange r[kJoinFlowRanges];
+    const int n = join_flow_ranges((const uint8_t*)(uintptr_t)addr[0], (const int64_t*)(uintptr_t)addr[1], n_str, total_bytes,
+                                   (uint8_t*)(uintptr_t)addr[2], cap, (int64_t*)(uintptr_t)addr[3], (void*)(uintptr_t)addr[4],
+                                   (int64_t*)(uintptr_t)addr[5], (flags & LATOK_OUT_INT32) != 0, r);
+    if (n > n_max) return fail(LATOK_ERR_INVALID, "need room for %d ranges", n);
+    for (int i = 0; i < n; ++i) {
+        lo[i] = (uint64_t)r[i].lo;
+        bytes[i] = (uint64_t)(r[i].hi - r[i].lo);
+        is_write[i] = r[i].write ? 1 : 0;
+    }
+    return n;
+}
+
+int latok_flow_join_tokens_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes, int sep,
+                                      uint8_t* out_bytes_dev, int64_t out_cap, int64_t* out_off_dev, void* counts_dev, int64_t* result_dev,
+                                      int flags) {
+    LATOK_ENTER();
+    if (sep < 0 || sep > 255) return fail(LATOK_ERR_INVALID, "sep must be one byte (0..255), got %d", sep);
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    if (n_str < 0) return fail(LATOK_ERR_INVALID, "n_str must be >= 0");
+    if (out_cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
+    if (!out_bytes_dev && out_cap > 0) return fail(LATOK_ERR_INVALID, "out_bytes is NULL but out_cap > 0 (a size query passes out_cap = 0)");
+    if (!result_dev) return fail(LATOK_ERR_INVALID, "NULL result pointer");
+    if (((uintptr_t)result_dev & 7) != 0) return fail(LATOK_ERR_INVALID, "result pointer must be 8-byte aligned");
+    if (!out_off_dev) return fail(LATOK_ERR_INVALID, "out_off is NULL");
+    const bool o32 = (flags & LATOK_OUT_INT32) != 0;
+    const size_t rec = o32 ? 4 : 8;
+    if (((uintptr_t)out_off_dev & 7) != 0 || ((uintptr_t)counts_dev & (rec - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    if (total_bytes < 0 && (rc = resolve_total_device(byte_off_dev, n_str, &total_bytes, g.stream))) return rc;
+    if ((rc = flow_setup(g))) return rc;
+    latok::FlowRange r[kJoinFlowRanges];
+    const int n_r = join_flow_ranges(utf8_dev, byte_off_dev, n_str, total_bytes, out_bytes_dev, out_cap, out_off_dev, counts_dev, result_dev, o32, r);
+    int slot = 0;
+    if (n_str == 0 || total_bytes <= 0) {   // nothing to launch: empty rows
+        if ((rc = flow_pick(g, r, n_r, &slot))) return rc;
+        g.flow_held.note(slot, r, n_r);
+        HIP_TRY(hipMemsetAsync(result_dev, 0, 16, g.flow[slot].st));
+        HIP_TRY(hipMemsetAsync(out_off_dev, 0, (size_t)(n_str + 1) * 8, g.flow[slot].st));
+        if (counts_dev && n_str > 0) HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)n_str * rec, g.flow[slot].st));
+        return LATOK_OK;
+    }
+    if (!utf8_dev || !byte_off_dev) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (((uintptr_t)utf8_dev & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    if ((rc = flow_pick(g, r, n_r, &slot))) return rc;
+    Ctx::FlowSlot& f = g.flow[slot];
+    if ((rc = flow_reserve(g, ws_needs(f.ws, total_bytes, true, false, false, 0, true).data(), kWsNeeds))) return rc;
+    g.flow_held.note(slot, r, n_r);   // before anything is enqueued (flow_begin)
+    ++g.flow_seq;
+    HIP_TRY(hipMemsetAsync(result_dev, 0, 16, f.st));
+    JoinTokens a;
+    a.b = Batch{Input{utf8_dev, Form::Utf8}, byte_off_dev, n_str, total_bytes};
+    a.sep = sep;
+    a.out = out_bytes_dev;
+    a.cap = out_bytes_dev ? std::min(out_cap, 2 * total_bytes) : 0;
+    a.out_off = out_off_dev;
+    a.counts = counts_dev;
+    a.o32 = o32;
+    a.r_bytes = result_dev;
+    a.r_err = result_dev + 1;
+    a.st = f.st;
+    return enqueue_join_tokens(g, f.ws, a);
+}
+
 int latok_flow_wait(void) {
     LATOK_ENTER();
     int rc = need_init(g);

@@ -4,6 +4,7 @@
 //   boundary offsets   np.nonzero(splits)[0] per string                      reference default_tokenizer.py:148
 //   token spans        slice between consecutive boundaries, strip, drop ''   reference default_tokenizer.py:149-158
 //   token features     per-token sums of the 25 matrix columns (featurize)    reference default_tokenizer.py:163-191
+//   joined token text  the tokens themselves, sep.join per string, UTF-8 out  reference default_tokenizer.py:149-160   (below: "joined token text")
 //
 // Inputs are the two bitmasks the tile kernel writes (boundary bits, SPACE bits; bit i = packed char i) and row_off.
 // Because strings are contiguous and ordered in the packed buffer, "all offsets of string 0, then string 1, ..." is
@@ -889,6 +890,217 @@ __global__ __launch_bounds__(256) void k_pad_codes(uint8_t* __restrict__ codes, 
 }
 hipError_t launch_pad_codes(uint8_t* codes, const int64_t* total_dev, int64_t bound, hipStream_t st) {
     hipLaunchKernelGGL(k_pad_codes, dim3(1), dim3(256), 0, st, codes, total_dev, bound, kTile + 256);
+    return hipGetLastError();
+}
+
+// ---- joined token text: sep.join(tokenize(text)) of every string, UTF-8 out (reference default_tokenizer.py:149-160) ------
+// The tokens as text instead of positions: for every string its stripped, non-empty tokens (exactly the byte ranges
+// k_counts_scatter<1> reports) joined by one separator byte, all rows back to back in one buffer plus out_off[n_str + 1].
+// Mask-driven and parallel over the packed buffer; span records are never formed.  Two planes per 64-byte word (lane_math.h:
+// lk_join_planes): body = the byte is copied, head = a separator goes in front of it.  An output item is a body bit or a head
+// bit; the output position of body byte i is (body bits before i) + (head bits at or before i), its separator one before.
+//   k_join_counts    one wave per 4096-byte tile, lane = word: the two planes, items per word (uint16 prefix) and per tile
+//   k_scan_chained   tile ranks and the byte total (unchanged: at most 8192 items per tile, the uint16 word prefix holds them)
+//   k_join_scatter   one wave per tile: the tile's bytes, compacted with their separators into an LDS window, leave as one
+//                    contiguous run; behind them one thread per string: out_off[s] = rank of byte_off[s], O(1)
+// A token (or a string's leading whitespace) that reaches beyond the tile needs three carries into it: "a non-SPACE byte
+// earlier in my token", "... later in my token", "... earlier in my string".  Inside a tile they are carry chains over the
+// ballots of the words' summaries; from outside, the wave reads the neighbouring tiles' masks 64 words per step until the
+// question is settled -- one step in ordinary text, one step per 4096 bytes for a token or a whitespace prefix that long
+// (every step is one coalesced load per plane by the whole wave, never a per-string or per-token serial walk).
+constexpr int kJoinWaves = 4;
+constexpr int kJoinWin = 2 * kTile + 16;   // items of a tile (every byte a one-byte token with its separator: 2 per byte) + the run's offset inside its first dword
+
+__global__ __launch_bounds__(kJoinWaves * 64) void k_join_counts(
+    const uint64_t* __restrict__ bits, const uint64_t* __restrict__ space, int64_t n_words, int64_t total,
+    const int64_t* __restrict__ row_off, int64_t n_str, const int64_t* __restrict__ tile_first, uint64_t* __restrict__ body_out,
+    uint64_t* __restrict__ head_out, int64_t* __restrict__ tile_cnt, uint16_t* __restrict__ word_pref) {
+    __shared__ unsigned long long bw_s[kJoinWaves][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t t = (int64_t)blockIdx.x * kJoinWaves + wave;
+    const int64_t w0 = t * 64;
+    if (w0 >= n_words) return;                                      // whole wave (no block-wide barrier is used below)
+    const int64_t n_tiles = (n_words + 63) >> 6;
+    const int64_t w = w0 + lane;
+    const bool in = w < n_words;
+    const uint64_t x = in ? bits[w] : 0ull;
+    const uint64_t nn = in ? (~space[w] & valid_mask(w, total)) : 0ull;
+    // string starts of the tile as bits (k_counts_scatter's step (a)) and the start of the string that is open at its first byte
+    const int64_t t0 = w0 << 6;
+    int64_t idx0 = tile_first[t];
+    idx0 = idx0 < 0 ? 0 : (idx0 > n_str ? n_str : idx0);
+    const int64_t start_before = idx0 > 0 ? row_off[idx0 - 1] : 0;
+    const bool starts_here = row_off[idx0] == t0;                   // (row_off has n_str + 1 entries)
+    unsigned long long* bw = bw_s[wave];
+    bw[lane] = 0ull;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int64_t i0 = idx0; i0 < n_str; i0 += 64) {
+        const int64_t sidx = i0 + lane;
+        const int64_t ro = sidx < n_str ? row_off[sidx] : INT64_MAX;
+        const int64_t rel = ro - t0;
+        if (rel >= 0 && rel < 4096) atomicOr(&bw[rel >> 6], 1ull << (rel & 63));
+        if (__shfl(ro, 63) >= t0 + 4096) break;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const uint64_t r = bw[lane];
+    // carries from the tiles in front: the open token has a non-SPACE byte there (f_in), the open string has one (q_in)
+    int f_in = 0, q_in = 0, b_in = 0;
+    bool f_open = true, q_open = !starts_here && t0 > start_before;   // (wave-uniform)
+    for (int64_t k = t - 1; k >= 0 && (f_open || q_open); --k) {
+        const int64_t v = k * 64 + lane;                            // (a tile in front of mine lies inside the batch entirely)
+        const uint64_t xv = bits[v], nv = ~space[v];
+        if (f_open) {
+            const lk_join_sum s = lk_join_summary(xv, nv, 0ull);
+            const uint64_t G = __ballot(s.gen_f), P = __ballot(s.prop_x);
+            if (lk_seg_out(G, ~P, lk_seg_carries(G, ~P, 0))) { f_in = 1; f_open = false; }
+            else if (P != ~0ull) f_open = false;                    // a boundary with nothing but SPACE behind it
+        }
+        if (q_open) {
+            const int64_t base = v << 6;
+            uint64_t m = nv;
+            if (base + 64 <= start_before) m = 0ull;
+            else if (base < start_before) m &= ~0ull << (start_before - base);
+            if (__ballot(m != 0ull)) { q_in = 1; q_open = false; }
+            else if (k * (int64_t)kTile <= start_before) q_open = false;
+        }
+    }
+    // ... and from the tiles behind: the token that is open at my last byte has a non-SPACE byte there (b_in)
+    for (int64_t k = t + 1; k < n_tiles; ++k) {
+        const int64_t v = k * 64 + lane;
+        const bool vin = v < n_words;
+        const uint64_t xv = vin ? bits[v] : 0ull;
+        const uint64_t nv = vin ? (~space[v] & valid_mask(v, total)) : 0ull;
+        const lk_join_sum s = lk_join_summary(xv, nv, 0ull);
+        const uint64_t Gr = lk_rev(__ballot(s.gen_b)), P = __ballot(s.prop_x);
+        const uint64_t Sr = lk_rev(~P);
+        if (lk_seg_out(Gr, Sr, lk_seg_carries(Gr, Sr, 0))) { b_in = 1; break; }
+        if (P != ~0ull) break;
+    }
+    // the chains over the tile's 64 words (bit = word), then inside the word
+    const lk_join_sum s = lk_join_summary(x, nn, r);
+    const uint64_t Gf = __ballot(s.gen_f), Gb = __ballot(s.gen_b), Gq = __ballot(s.gen_q);
+    const uint64_t Sx = ~__ballot(s.prop_x), Sr = ~__ballot(s.prop_r);
+    const int cf = (int)((lk_seg_carries(Gf, Sx, f_in) >> lane) & 1ull);
+    const int cb = (int)((lk_seg_carries(lk_rev(Gb), lk_rev(Sx), b_in) >> (63 - lane)) & 1ull);
+    const int cq = (int)((lk_seg_carries(Gq, Sr, q_in) >> lane) & 1ull);
+    const lk_join_planes_t o = lk_join_planes(x, nn, r, cf, cb, cq);
+    if (in) {
+        body_out[w] = o.body;
+        head_out[w] = o.head;
+    }
+    const int cnt = __popcll(o.body) + __popcll(o.head);
+    int inc = cnt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int v = __shfl_up(inc, d);
+        if (lane >= d) inc += v;
+    }
+    if (in) word_pref[w] = (uint16_t)(inc - cnt);
+    if (lane == 63) tile_cnt[t] = inc;
+}
+
+__global__ __launch_bounds__(kJoinWaves * 64) void k_join_scatter(
+    const uint8_t* __restrict__ u8, int64_t total, const uint64_t* __restrict__ body, const uint64_t* __restrict__ head,
+    const int64_t* __restrict__ tile_rank, const int64_t* __restrict__ tile_cnt, const uint16_t* __restrict__ word_pref,
+    int64_t n_words, const int64_t* __restrict__ row_off, int64_t n_str, int sep, uint8_t* __restrict__ out, int64_t cap,
+    const int64_t* __restrict__ n_items_dev, int64_t* __restrict__ out_off, int* __restrict__ err, unsigned n_tile_blocks) {
+    if (blockIdx.x >= n_tile_blocks) {   // role 2: one thread per row offset (and the end of the batch)
+        const int64_t s = (int64_t)(blockIdx.x - n_tile_blocks) * (kJoinWaves * 64) + threadIdx.x;
+        if (s > n_str) return;
+        const int64_t n = *n_items_dev;
+        const int64_t p = row_off[s];
+        int64_t rank = n;
+        if (p < total) {
+            const int64_t w = p >> 6;
+            const uint64_t lm = low_mask((int)(p & 63));
+            rank = tile_rank[w >> 6] + word_pref[w] + __popcll(body[w] & lm) + __popcll(head[w] & lm);
+        }
+        out_off[s] = rank;
+        if (s == 0 && n > cap) *err = *err | 4;   // (plain stores: the flag may live in pinned host memory)
+        return;
+    }
+    // role 1: one wave per tile.  The caller's buffer holds `cap` bytes; when the batch needs more, nothing is written.
+    if (*n_items_dev > cap) return;
+    __shared__ __attribute__((aligned(16))) uint8_t win_s[kJoinWaves][kJoinWin];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t t = (int64_t)blockIdx.x * kJoinWaves + wave;
+    const int64_t w0 = t * 64;
+    if (w0 >= n_words) return;                                      // whole wave
+    const int n_wave = (int)tile_cnt[t];
+    if (n_wave == 0) return;
+    const int64_t w = w0 + lane;
+    const bool in = w < n_words;
+    const uint64_t bodyw = in ? body[w] : 0ull, headw = in ? head[w] : 0ull;
+    const int pref = in ? (int)word_pref[w] : 0;
+    uint8_t* dst = out + tile_rank[t];
+    const int a = (int)((uintptr_t)dst & 3u);                       // window byte j <-> dst - a + j: dwords of the two coincide
+    uint8_t* win = win_s[wave];
+    const int64_t t0 = w0 << 6;
+    const int sh = (lane & 15) * 4;
+    const uint64_t below = low_mask(sh);
+    // 256 bytes per round, one dword per lane: coalesced loads; the owner word's planes and prefix arrive through shuffles
+    for (int rd = 0; rd < 16; ++rd) {
+        const int src = 4 * rd + (lane >> 4);
+        const uint64_t bq = __shfl(bodyw, src), hq = __shfl(headw, src);
+        const int pq = __shfl(pref, src);
+        const unsigned bn = (unsigned)(bq >> sh) & 15u, hn = (unsigned)(hq >> sh) & 15u;   // (head bits are body bits)
+        if (__ballot(bn != 0u) == 0ull) continue;                   // (wave-uniform) 256 bytes of whitespace
+        if (bn != 0u) {
+            const int64_t p = t0 + 256 * rd + 4 * lane;
+            uint32_t d = 0;
+            if (p + 4 <= total) {
+                d = *reinterpret_cast<const uint32_t*>(u8 + p);
+            } else {
+                for (int k = 0; k < 4; ++k)
+                    if (p + k < total) d |= (uint32_t)u8[p + k] << (8 * k);
+            }
+            int pos = a + pq + __popcll(bq & below) + __popcll(hq & below);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if ((hn >> k) & 1u) win[pos++] = (uint8_t)sep;
+                if ((bn >> k) & 1u) win[pos++] = (uint8_t)(d >> (8 * k));
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // the run [a, a + n_wave) of the window: whole dwords, the ragged <= 3 bytes at each end as bytes -- one writer per byte
+    const int lo = a, hi = a + n_wave;
+    uint8_t* base = dst - a;
+    const int d0 = (lo + 3) & ~3, d1 = hi & ~3;
+    if (d0 >= d1) {
+        if (lo + lane < hi) base[lo + lane] = win[lo + lane];
+    } else {
+        if (lo + lane < d0) base[lo + lane] = win[lo + lane];
+        for (int j = d0 + 4 * lane; j < d1; j += 256)
+            __builtin_nontemporal_store(*reinterpret_cast<const uint32_t*>(win + j), reinterpret_cast<uint32_t*>(base + j));
+        if (d1 + lane < hi) base[d1 + lane] = win[d1 + lane];
+    }
+}
+
+hipError_t launch_join_counts(const uint64_t* bits, const uint64_t* space, int64_t n_words, int64_t total, const int64_t* row_off,
+                              int64_t n_str, const int64_t* tile_first, uint64_t* body, uint64_t* head, int64_t* tile_cnt,
+                              uint16_t* word_pref, hipStream_t st) {
+    if (n_words <= 0) return hipSuccess;
+    const int64_t n_tiles = (n_words + 63) / 64;
+    hipLaunchKernelGGL(k_join_counts, dim3((unsigned)((n_tiles + kJoinWaves - 1) / kJoinWaves)), dim3(kJoinWaves * 64), 0, st, bits, space,
+                       n_words, total, row_off, n_str, tile_first, body, head, tile_cnt, word_pref);
+    return hipGetLastError();
+}
+
+// out == NULL: the row offsets only (a size query)
+hipError_t launch_join_scatter(const uint8_t* u8, int64_t total, const uint64_t* body, const uint64_t* head, const int64_t* tile_rank,
+                               const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, const int64_t* row_off,
+                               int64_t n_str, int sep, uint8_t* out, int64_t cap, const int64_t* n_items_dev, int64_t* out_off,
+                               int* err, hipStream_t st) {
+    if (n_words <= 0) return hipSuccess;
+    const int64_t n_tiles = (n_words + 63) / 64;
+    const unsigned nb_tiles = out ? (unsigned)((n_tiles + kJoinWaves - 1) / kJoinWaves) : 0u;
+    const unsigned nb_rows = (unsigned)((n_str + 1 + kJoinWaves * 64 - 1) / (kJoinWaves * 64));
+    hipLaunchKernelGGL(k_join_scatter, dim3(nb_tiles + nb_rows), dim3(kJoinWaves * 64), 0, st, u8, total, body, head, tile_rank, tile_cnt,
+                       word_pref, n_words, row_off, n_str, sep, out, cap, n_items_dev, out_off, err, nb_tiles);
     return hipGetLastError();
 }
 

@@ -250,6 +250,16 @@ hipError_t launch_lead_codes(const uint8_t* u8, int64_t total_bytes, const uint6
                              const uint16_t* word_pref, int64_t n_words, const uint8_t* tb6rule, uint8_t* codes, int n_cu, hipStream_t st);
 hipError_t launch_tile_scan(const int64_t* tile_cnt, int64_t n_tiles, int64_t* tile_rank, unsigned long long* chain, unsigned* ticket,
                             unsigned epoch, int64_t* total_dev, int64_t* total_host, int* err, hipStream_t st);
+// joined token text of a UTF-8 batch in byte space (compact_kernels.hip: "joined token text"): the body / head planes with the
+// items (output bytes) per word and per tile; then, behind a scan of the tile counts, the output bytes (only if the total
+// fits cap; out may be NULL) and out_off[n_str + 1].  *err gets bit 2 (value 4) when the total exceeds cap.
+hipError_t launch_join_counts(const uint64_t* bits, const uint64_t* space, int64_t n_words, int64_t total, const int64_t* row_off,
+                              int64_t n_str, const int64_t* tile_first, uint64_t* body, uint64_t* head, int64_t* tile_cnt,
+                              uint16_t* word_pref, hipStream_t st);
+hipError_t launch_join_scatter(const uint8_t* u8, int64_t total, const uint64_t* body, const uint64_t* head, const int64_t* tile_rank,
+                               const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, const int64_t* row_off,
+                               int64_t n_str, int sep, uint8_t* out, int64_t cap, const int64_t* n_items_dev, int64_t* out_off,
+                               int* err, hipStream_t st);
 // zeros at codes[t .. t + kTile + 256), t = *total_dev held inside [0, bound]
 hipError_t launch_pad_codes(uint8_t* codes, const int64_t* total_dev, int64_t bound, hipStream_t st);
 int64_t utf8_blocks(int64_t total_bytes);   // 4 KiB blocks of the chunk-parallel UTF-8 decoder

@@ -990,4 +990,65 @@ LATOK_HD lk_u64 lk_backward_fill(const lk_bwd& w, int cin, lk_u64 S) {
     return lk_rev(sum ^ w.xr) & ~S;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Joined token text (sep.join(tokenize(text)), reference default_tokenizer.py:149-160) in BYTE space: which bytes of a word
+// are copied, and in front of which a separator goes.  Inputs per 64-byte word:
+//   x   boundary bits (a token starts here; every string start is one, splits[0] = 1)
+//   nn  non-SPACE bytes inside the batch (~SPACE plane & valid; the plane is smeared over continuation bytes, so a multi-byte
+//       whitespace char is SPACE in all its bytes)
+//   r   string-start bits
+// Outputs:
+//   body  byte i lies inside the stripped extent of a kept token: a non-SPACE byte at or before i AND one at or after i in
+//         i's token (interior SPACE bytes are body bytes; a token of SPACE bytes alone has none)
+//   head  byte i is the first body byte of a kept token that is not the first kept token of its string: the first non-SPACE
+//         byte of its token, with a non-SPACE byte earlier in its STRING
+// All three conditions are segmented OR-smears, F(i) = gen(i) | (~seg(i) & F(i - 1)): a carry chain, one add
+// (k_word_counts<true> uses the same trick for one of them).  The same function links the 64 words of a tile (bit = word, on
+// the ballots of the word summaries below) and, one tile per step, the tiles of a token that is longer than that.
+// ---------------------------------------------------------------------------------------------------------------
+// carry INTO every position (bit 0: cin) of F(i) = gen(i) | (~seg(i) & F(i - 1))
+LATOK_HD lk_u64 lk_seg_carries(lk_u64 gen, lk_u64 seg, int cin) {
+    const lk_u64 a = ~seg | gen;
+    return (a + gen + (lk_u64)(cin & 1)) ^ a ^ gen;
+}
+// F(63) of that chain, given the carries
+LATOK_HD int lk_seg_out(lk_u64 gen, lk_u64 seg, lk_u64 carries) { return (int)(((gen | (~seg & carries)) >> 63) & 1ull); }
+
+// What a word passes on when nothing comes in (the generate bits of the chains over words) and whether it passes a carry through
+struct lk_join_sum {
+    int gen_f;    // a non-SPACE byte at or after the word's last boundary       (forward: "earlier in my token")
+    int gen_b;    // a non-SPACE byte before the word's first boundary           (backward: "later in my token")
+    int gen_q;    // a non-SPACE byte at or after the word's last string start   (forward: "earlier in my string")
+    int prop_x;   // no boundary in the word
+    int prop_r;   // no string start in the word
+};
+LATOK_HD lk_join_sum lk_join_summary(lk_u64 x, lk_u64 nn, lk_u64 r) {
+    lk_join_sum s;
+    s.gen_f = lk_seg_out(nn, x, lk_seg_carries(nn, x, 0));
+    s.gen_b = (nn & (x ? ((x & (~x + 1ull)) - 1ull) : ~0ull)) != 0;
+    s.gen_q = lk_seg_out(nn, r, lk_seg_carries(nn, r, 0));
+    s.prop_x = x == 0;
+    s.prop_r = r == 0;
+    return s;
+}
+struct lk_join_planes_t {
+    lk_u64 body, head;
+};
+// cf: a non-SPACE byte earlier in the token that is open at bit 0; cb: the token that runs past bit 63 has a non-SPACE byte
+// behind the word; cq: a non-SPACE byte earlier in the string that is open at bit 0
+LATOK_HD lk_join_planes_t lk_join_planes(lk_u64 x, lk_u64 nn, lk_u64 r, int cf, int cb, int cq) {
+    lk_join_planes_t o;
+    const lk_u64 Cf = lk_seg_carries(nn, x, cf);
+    const lk_u64 F = nn | (~x & Cf);
+    // backward on the bit-reversed word: D(j) = ~xr(j) & (nr(j) | D(j - 1)) is "my token has a non-SPACE byte at or above me and
+    // no boundary from me up to it"; the carry into j is what lies above
+    const lk_u64 xr = lk_rev(x), nr = lk_rev(nn);
+    const lk_u64 Cb = lk_seg_carries(nr & ~xr, xr, cb);
+    const lk_u64 Bk = lk_rev(nr | Cb);
+    const lk_u64 Cq = lk_seg_carries(nn, r, cq);
+    o.body = F & Bk;
+    o.head = nn & (x | ~Cf) & ~r & Cq;
+    return o;
+}
+
 #endif

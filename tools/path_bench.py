@@ -23,6 +23,12 @@
   utf8_decode_features32   what a UTF-8 caller had to compose before: latok_utf8_decode_batch into a device buffer, then
                   latok_token_features_batch on it (LATOK_OUT_INT32); same data, same process
   bytes_mask / bytes_offsets / bytes_spans   latok_*_utf8_bytes_batch (8f-3 fused: the tile kernel reads the bytes)
+  bytes_join / bytes_join_flow   latok_join_tokens_utf8_bytes_batch / latok_flow_join_tokens_utf8_bytes: every string's tokens joined by
+                  one space, UTF-8 out (no counts asked for); beside them, in the same process run,
+  bytes_spans32 / bytes_spans32_flow   latok_token_spans_utf8_bytes_batch / latok_flow_token_spans(kind 0) with LATOK_OUT_INT32: the
+                  stage the join replaces for a caller who wants text
+  py_join        end to end in Python on host blobs (the first --py-strings strings): batch.join_tokens_utf8_batch(blobs) against the
+                  only route to the same rows without it, [b" ".join(t) for t in batch.tokenize_utf8_batch(blobs)]; one line each
   rules_mask      latok_split_mask_batch after latok_set_rules(built-in tables)   (8f-4)
   offsets32 / spans32 / features32 / kind_offsets32 / kind_spans32   the same entry points with LATOK_OUT_INT32 records
   mask_flow / bytes_mask_flow / kind_mask_flow   the same mask paths through the batch flow (latok_flow_split_mask*: two
@@ -83,8 +89,10 @@ def main():
     ap.add_argument("--paths", default="mask,mask_flow,bytes_mask_flow,kind_mask_flow,offsets32_flow,spans32_flow,features32_flow,offsets,offsets32,spans,spans32,features,features32,utf8_mask,utf8_offsets,utf8_offsets32,utf8_spans,utf8_spans32,utf8_features32,"
                                        "utf8_mask_flow,utf8_offsets_flow,utf8_offsets32_flow,utf8_spans_flow,utf8_spans32_flow,utf8_features32_flow,utf8_decode_features32,"
                                        "utf8_bytes_features32,utf8_bytes_features32_flow,pair_features32_bytes_spans32,pair_features32_bytes_spans32_flow,"
-                                       "bytes_mask,bytes_offsets,bytes_spans,rules_mask,kind_mask,kind_offsets,kind_offsets32,"
+                                       "bytes_mask,bytes_offsets,bytes_spans,bytes_spans32,bytes_spans32_flow,bytes_join,bytes_join_flow,"
+                                       "rules_mask,kind_mask,kind_offsets,kind_offsets32,"
                                        "kind_spans,kind_spans32")
+    ap.add_argument("--py-strings", type=int, default=200_000, help="strings of the py_join path (host blobs)")
     args = ap.parse_args()
     lib = _lib.ensure_init()
     model, seed, lo, hi = WORKLOADS[args.workload]
@@ -361,6 +369,63 @@ def main():
     if "bytes_spans" in paths:
         run("bytes_spans", lambda: lib.latok_token_spans_utf8_bytes_batch(d_u8, d_boff, n, n8, d_counts, d_items, cap, C.byref(nout), D, None),
             lambda: n8 + csr + 8 * n + 16 * nout.value, "UTF-8 bytes + 8 B/string read; 8 B/string + 16 B/token written (byte ranges)")
+    # joined token text and the byte-space spans beside it: every line of this leg in one process run, in the order given
+    join_leg = [p for p in paths if p in ("bytes_join", "bytes_join_flow", "bytes_spans32", "bytes_spans32_flow", "py_join")]
+    if join_leg:
+        jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64)]
+        if not all(jb):
+            raise RuntimeError(_lib.last_error())
+        j_out, j_off, k_out, k_off, s_items, s_counts, t_items, t_counts, j_res = jb
+        resj = lambda i: C.c_void_p(j_res + 16 * (i & 1))  # noqa: E731
+        note_j = "UTF-8 bytes + 8 B/string read; body / head planes 2 x 1 bit/byte written and read; 1 B/output byte + 8 B/string row offsets written"
+        note_s = "UTF-8 bytes + 8 B/string read; 4 B/string + 8 B/token written (byte ranges, LATOK_OUT_INT32)"
+        join_blocking = lambda: lib.latok_join_tokens_utf8_bytes_batch(d_u8, d_boff, n, n8, 32, j_out, 2 * n8, j_off, None, C.byref(nout), D, None)  # noqa: E731
+        spans_blocking = lambda: lib.latok_token_spans_utf8_bytes_batch(d_u8, d_boff, n, n8, s_counts, s_items, cap, C.byref(nout), D32, None)  # noqa: E731
+
+        def two_words(name, want):
+            res = np.empty(4, np.int64)
+            _lib.check(lib.latok_memcpy_d2h(res.ctypes.data, j_res, 32))
+            for r2 in res.reshape(2, 2):
+                assert r2[1] == 0 and r2[0] == want, (name, r2.tolist())
+
+        for name in join_leg:
+            if name == "bytes_join":
+                run(name, join_blocking, lambda: n8 + csr + 4 * ((n8 + 63) // 64) * 8 + nout.value + csr, note_j)
+            elif name == "bytes_join_flow":
+                _lib.check(join_blocking())
+                out_n = nout.value
+                run_flow(name, lambda i: lib.latok_flow_join_tokens_utf8_bytes(d_u8, d_boff, n, n8, 32, k_out if i & 1 else j_out, 2 * n8,
+                                                                               k_off if i & 1 else j_off, None, resj(i), 0),
+                         lambda: n8 + csr + 4 * ((n8 + 63) // 64) * 8 + out_n + csr, note_j)
+                two_words(name, out_n)
+            elif name == "bytes_spans32":
+                run(name, spans_blocking, lambda: n8 + csr + 4 * n + 8 * nout.value, note_s)
+            elif name == "bytes_spans32_flow":
+                _lib.check(spans_blocking())
+                items_n = nout.value
+                run_flow(name, lambda i: lib.latok_flow_token_spans(d_u8, 0, d_boff, n, n8, t_counts if i & 1 else s_counts,
+                                                                    t_items if i & 1 else s_items, cap, resj(i), _lib.OUT_INT32),
+                         lambda: n8 + csr + 4 * n + 8 * items_n, note_s)
+                two_words(name, items_n)
+            else:   # py_join: host blobs in, host rows out, both routes in this process
+                from latok_amd import batch
+                m = min(args.py_strings, n)
+                blob = u8[:int(boff[m])].tobytes()
+                blobs = [blob[int(a):int(b)] for a, b in zip(boff[:m], boff[1:m + 1])]
+                routes = (("py_join_tokens_utf8_batch", lambda: batch.join_tokens_utf8_batch(blobs)),
+                          ("py_tokenize_utf8_batch_then_join", lambda: [b" ".join(t) for t in batch.tokenize_utf8_batch(blobs)]))
+                assert routes[0][1]() == routes[1][1]()
+                for r in range(args.repeat):
+                    for rname, fn in routes:
+                        t = time.perf_counter()
+                        rows = fn()
+                        dt = time.perf_counter() - t
+                        print(json.dumps({"path": rname, "workload": args.workload, "strings": m, "utf8_bytes": len(blob),
+                                          "out_bytes": sum(map(len, rows)), "ms_per_call": dt * 1e3, "utf8_GBps": len(blob) / dt / 1e9,
+                                          "note": "end to end in Python: list[bytes] in, list[bytes] out, pack and host slicing included",
+                                          "repeat": r}), flush=True)
+        for p_ in jb:
+            lib.latok_dev_free(p_)
     if "rules_mask" in paths:
         from latok_amd import batch
         from latok_amd.core import default_tokenizer as dt
