@@ -2337,12 +2337,14 @@ int latok_debug_set_scan_epoch(unsigned epoch) {
 
 /* test hook (not part of the ABI; needs no device): the constants that decide the tile pipeline's plans and host paths, so that
  * tests take their thresholds from the library: out[0..8] = kTile, kWPB, kNarrowWPB, kSegMax, kOneSegTiles, kFastTailTiles,
- * kSmallChars, kSmallStrings, tiles per workgroup of k_lead_compress.  Returns the number of values written. */
+ * kSmallChars, kSmallStrings, tiles per workgroup of k_lead_compress; out[9..13] = kFeatWaves, kFeatRound, kFeatRoundTm,
+ * kFeatFormThresh, kFeatWinBytes of k_features_tiles.  Returns the number of values written. */
 extern "C" int latok_debug_limits(int64_t* out, int n) {
-    const int64_t v[9] = {latok::kTile, latok::kWPB, latok::kNarrowWPB, latok::kSegMax, latok::kOneSegTiles, latok::kFastTailTiles,
-                          kSmallChars, kSmallStrings, latok::kCompressWaves};
+    const int64_t v[14] = {latok::kTile, latok::kWPB, latok::kNarrowWPB, latok::kSegMax, latok::kOneSegTiles, latok::kFastTailTiles,
+                           kSmallChars, kSmallStrings, latok::kCompressWaves, latok::kFeatWaves, latok::kFeatRound, latok::kFeatRoundTm,
+                           latok::kFeatFormThresh, latok::kFeatWinBytes};
     if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
-    const int k = n < 9 ? n : 9;
+    const int k = n < 14 ? n : 14;
     for (int i = 0; i < k; ++i) out[i] = v[i];
     return k;
 }

@@ -237,6 +237,13 @@ hipError_t launch_counts_scatter(int kind, bool out32, const uint64_t* bits, con
                                  int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,
                                  const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st, DoneSignal done = DoneSignal{nullptr, 0, nullptr},
                                  DeviceTotal dt = DeviceTotal{nullptr, nullptr});
+// k_features_tiles (split_kernels.hip, where the measurements behind these values are told); latok_debug_limits reports them
+constexpr int kFeatWaves = 7;                                         // (6 -> 7: C2 -4.5 %, C3 -6 %; 8 would need rounds of < 800 tokens: two rounds per C2 tile)
+constexpr int kFeatRound = 896;                                       // tokens per round (word-major form)
+constexpr int kFeatRec = 25;                                          // packed records in the window, as in the output
+constexpr int kFeatRoundTm = 768;                                     // token-major form: records + 2-byte (lane, bit) codes share the window
+constexpr int kFeatWinBytes = kFeatRound * kFeatRec + 16;             // (+ 16: the records start at record_shift(dst); token-major rounds cost nothing extra)
+constexpr int kFeatFormThresh = 5;                                    // token-major when maxc * 2 * wm_rounds > ceil(n / 64) * kFeatFormThresh
 constexpr int kCompressWaves = 16;   // k_lead_compress: tiles (= waves) per workgroup
 // code-point boundary mask + code-point row offsets from the byte-space mask and the lead-byte mask of a UTF-8 batch
 // (bmask2 / out_mask2: optionally a second mask -- the SPACE plane -- packed the same way, for token spans in code-point units)

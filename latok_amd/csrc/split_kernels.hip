@@ -1829,11 +1829,7 @@ __device__ __forceinline__ uint32_t feat_row_bits1(uint32_t w, uint32_t p, uint3
 // to global memory costs +0.4 ms in scattered stores.  So this kernel trades waves for LDS: kFeatWaves waves per CU,
 // each with a window for kFeatRound tokens (a 4096-char tile of word-soup text has ~830), which doubles as the
 // code-byte staging buffer before the planes are built.
-constexpr int kFeatWaves = 7;                                         // (6 -> 7: C2 -4.5 %, C3 -6 %; 8 would need rounds of < 800 tokens: two rounds per C2 tile)
-constexpr int kFeatRound = 896;                                       // tokens per round (word-major form)
-constexpr int kFeatRec = 25;                                          // packed records in the window, as in the output
-constexpr int kFeatRoundTm = 768;                                     // token-major form: records + 2-byte (lane, bit) codes share the window
-constexpr int kFeatWinBytes = kFeatRound * kFeatRec + 16;             // (+ 16: the records start at record_shift(dst); token-major rounds cost nothing extra)
+// kFeatWaves, kFeatRound, kFeatRec, kFeatRoundTm, kFeatWinBytes and kFeatFormThresh: kernels.h (latok_debug_limits reports them)
 static_assert(kFeatRoundTm * (kFeatRec + 2) + 16 <= kFeatWinBytes, "token-major round fits the window");
 constexpr int kFeatWaveLds = kFeatWinBytes + 16 + 66 * 8;             // window | (unused) | string-start words
 constexpr int kFeatLdsTotal = kFeatWaves * kFeatWaveLds;
@@ -2084,7 +2080,6 @@ __device__ __forceinline__ void feature_tile(const FeatParams& P, const TileLds&
     // ~70 64-bit shuffles per token make it the slower form for evenly filled tiles, hence the choice per tile.
     const int maxc = wave_max(lk_popc(x), 0);
     // threshold swept on C2 (word-major 9 % faster) and C3 (token-major 15 % faster): fullest word > 1.5 x steps of 64 tokens
-    constexpr int kFeatFormThresh = 5;
     // The word-major walk below runs as long as the fullest word (maxc steps of ~160 instructions with the span records), once
     // per window round; the token-major form takes ceil(n_wave / 64) steps of ~300 whatever the spread.
     const int wm_rounds = (n_wave + kFeatRound - 1) / kFeatRound;

@@ -51,6 +51,10 @@ def lib():
         L.oracle_nonzero.argtypes = [vp, i64, vp]
         L.oracle_split_batch.restype = C.c_int
         L.oracle_split_batch.argtypes = [vp, vp, i64, vp, vp]
+        L.oracle_gen_parse_matrix_batch.restype = None
+        L.oracle_gen_parse_matrix_batch.argtypes = [vp, vp, i64, vp]
+        L.oracle_gen_block_mask_batch.restype = None
+        L.oracle_gen_block_mask_batch.argtypes = [vp, vp, vp, i64, vp]
         _lib = L
     return _lib
 
@@ -172,6 +176,33 @@ def split_batch(cps: np.ndarray, row_off: np.ndarray, want_values=True, want_bit
     if rc != 0:
         raise ValueError("bad row offsets")
     return vals, bits
+
+
+def gen_parse_matrix_batch(cps: np.ndarray, row_off: np.ndarray) -> np.ndarray:
+    """gen_parse_matrix of every string of a CSR batch, rows at the packed char index"""
+    cps = np.ascontiguousarray(cps, dtype=np.uint32)
+    row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+    out = np.empty((len(cps), FEATURE_COUNT), np.int8)
+    lib().oracle_gen_parse_matrix_batch(_p(cps), _p(row_off), len(row_off) - 1, _p(out))
+    return out
+
+
+def split_values_rules_batch(cps, row_off, c_split, c_mask, c_sym, m=None) -> np.ndarray:
+    """split_values_rules of every string of a CSR batch at the packed char index: the same composition, with the sequential
+    block mask and the forced first boundary taken string by string (combine_matrix_rows works char by char)"""
+    row_off = np.ascontiguousarray(row_off, dtype=np.int64)
+    m = gen_parse_matrix_batch(cps, row_off) if m is None else m
+    if m.shape[0] == 0:
+        return np.zeros(0, np.int8)
+    mt = m.T
+    a1 = np.ascontiguousarray(combine_matrix_rows(mt, np.asarray(c_mask, np.int8)) != 0, dtype=np.int8)
+    a2 = np.ascontiguousarray(mt[5] != 0, dtype=np.int8)
+    block = np.empty(m.shape[0], np.int8)
+    lib().oracle_gen_block_mask_batch(_p(a1), _p(a2), _p(row_off), len(row_off) - 1, _p(block))
+    splits = combine_matrix_rows(mt, np.asarray(c_split, np.int8)) * block
+    splits += combine_matrix_rows(mt, np.asarray(c_sym, np.int8))
+    splits[row_off[:-1][row_off[1:] > row_off[:-1]]] = 1
+    return splits
 
 
 # ------------------------------------------------------------------------------------------------------------------
