@@ -219,6 +219,29 @@ int latok_join_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_
                                        int sep, uint8_t* out_bytes, int64_t out_cap, int64_t* out_off /* int64[n_str+1] */,
                                        void* counts_out /* may be NULL */, int64_t* n_out_bytes, int flags, void* stream);
 
+/* Token hashes in byte space: one 32-bit id per token instead of positions or text -- what a hashing vectorizer, feature hashing
+ * or a hashed embedding table consume.  A token is what the reference's tokenize() yields (default_tokenizer.py:149-160): for
+ * string s let (a_k, e_k), k = 0 .. c_s - 1, be the records latok_token_spans_utf8_bytes_batch reports for it (stripped,
+ * non-empty tokens as byte ranges relative to byte_off[s]), and rank(s, k) = c_0 + .. + c_(s-1) + k.  Then
+ *   hashes_out[rank(s, k)] = MurmurHash3 x86_32 (murmur3_x86_32) of utf8[byte_off[s] + a_k : byte_off[s] + e_k] with `seed`
+ *   counts_out[s]          = c_s                        (may be NULL)
+ *   spans_out[2 rank(s, k)], [2 rank(s, k) + 1] = a_k, e_k   (may be NULL; the records of the spans call, byte for byte)
+ * LATOK_OUT_INT32 applies to counts and spans; a hash is always one uint32.  MurmurHash3 x86_32 is the function of scikit-learn's
+ * HashingVectorizer / FeatureHasher, Spark's HashingTF and Vowpal Wabbit: sklearn.utils.murmurhash3_32(token_bytes, seed) is this
+ * uint32 read as int32 (the same word with positive=True); bucket reduction (% n, sign) is the consumer's.  The bytes of a span are
+ * hashed verbatim and the spans call defines the spans: run-time rule tables, truncated sequences, lone lead bytes and stray
+ * continuation bytes need no rule of their own, nothing is refused as malformed.  Empty and whitespace-only strings contribute no
+ * token; n_str = 0 or total_bytes = 0 gives zero tokens with counts cleared.
+ * Capacity protocol, in TOKENS, as in the spans call: cap too small -> nothing is written to hashes or records, counts stay valid,
+ * the needed count is in *n_tokens_out and the call returns LATOK_ERR_INVALID; cap = 0 with hashes_out = NULL is a size query;
+ * hashes_out = NULL with cap > 0 is refused.  Host pointers or LATOK_DEVICE_PTRS (device UTF-8 pointer 16-byte aligned; the kernel
+ * reads the text as aligned 4-byte words, up to the word that holds the last byte), total_bytes = -1 as in the sibling calls; a
+ * flag bit other than these two is refused before any device work.  Every batch size takes the same kernels and gives the same
+ * words; the call waits for its kernels once. */
+int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                        uint32_t seed, int64_t* counts_out /* may be NULL */, int64_t* spans_out /* may be NULL */,
+                                        uint32_t* hashes_out, int64_t cap, int64_t* n_tokens_out, int flags, void* stream);
+
 /* Token feature vectors: reference featurize() (default_tokenizer.py:163-191) for a whole batch without the n x 25
  * matrix.  Per kept token k: spans4_out[4k..4k+3] = {raw_start, raw_end, strip_start, strip_end} (LaToken.start_idx /
  * end_idx are the raw span, LaToken.text is text[strip_start:strip_end]); features_out[25k..25k+24] = sum of the 25
@@ -405,6 +428,15 @@ int latok_flow_token_features_utf8_bytes(const uint8_t* utf8_dev, const int64_t*
 int latok_flow_join_tokens_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
                                       int sep, uint8_t* out_bytes_dev, int64_t out_cap, int64_t* out_off_dev,
                                       void* counts_dev, int64_t* result_dev /* int64[2]: output bytes, error word */, int flags);
+/* Token hashes through the flow: what latok_token_hashes_utf8_bytes_batch reports (MurmurHash3 x86_32 of every token of
+ * default_tokenizer.py:149-160; the definition is at that call), word for word, without waiting.  The two result words of
+ * latok_flow_token_spans: result[0] = tokens, result[1] = error word (bit 0: a string too long for LATOK_OUT_INT32, upper half:
+ * the scan's internal flag), and its capacity rule, read late: result[0] > cap means nothing was written to hashes or records
+ * (counts are valid).  Read them after latok_flow_wait.  counts_dev and spans_dev may be NULL.  The ordering rule covers the
+ * input bytes, byte_off, hashes and records (min(cap, total_bytes) tokens of each), counts and the result words. */
+int latok_flow_token_hashes_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                       uint32_t seed, void* counts_dev, void* spans_dev, uint32_t* hashes_dev, int64_t cap,
+                                       int64_t* result_dev /* int64[2]: tokens, error word */, int flags);
 int latok_flow_wait(void);
 
 /* ---- measurement ----------------------------------------------------------------------------------------------- */

@@ -463,6 +463,80 @@ def join_tokens_batch(texts, sep=" "):
     return [r.decode("utf-8", "surrogatepass") for r in rows]
 
 
+# token hashes: one 32-bit id per token (MurmurHash3 x86_32 of its UTF-8 bytes) -- what hashing vectorizers and hashed tables take
+def murmur3_32(data: bytes, seed=0) -> int:
+    """MurmurHash3 x86_32 of ``data`` (bytes) with a 32-bit ``seed``, as an unsigned int: the word the device gives for a token with
+    these bytes (``token_hashes_*``), computed on the host -- for building id tables from a vocabulary.  scikit-learn's
+    ``murmurhash3_32(data, seed, positive=True)`` is the same number."""
+    seed = _seed32(seed)
+    data = bytes(data)
+    m = 0xFFFFFFFF
+    h, n = seed, len(data)
+    for i in range(0, n & ~3, 4):
+        k = int.from_bytes(data[i:i + 4], "little") * 0xcc9e2d51 & m
+        k = ((k << 15) | (k >> 17)) * 0x1b873593 & m
+        h ^= k
+        h = (((h << 13) & m | (h >> 19)) * 5 + 0xe6546b64) & m
+    if n & 3:
+        k = int.from_bytes(data[n & ~3:], "little") * 0xcc9e2d51 & m
+        k = (((k << 15) & m) | (k >> 17)) * 0x1b873593 & m
+        h ^= k
+    h ^= n & m
+    h = (h ^ (h >> 16)) * 0x85ebca6b & m
+    h = (h ^ (h >> 13)) * 0xc2b2ae35 & m
+    return h ^ (h >> 16)
+
+
+def _seed32(seed) -> int:
+    """the seed as an int 0 .. 2**32 - 1; anything else is a ValueError (raised before any device is asked for)"""
+    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool) and 0 <= int(seed) <= 0xFFFFFFFF:
+        return int(seed)
+    raise ValueError("seed must be an int in 0 .. 2**32 - 1")
+
+
+def _hashes_csr(utf8, byte_off, seed, dtype, want_spans):
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    seed = _seed32(seed)
+    dt, flags = _out_dtype(dtype)
+    n_str = byte_off.size - 1
+    total = int(byte_off[-1]) if n_str > 0 else 0
+    lib = _lib.ensure_init()
+    cap = max(total, 1)                                  # a token has at least one byte
+    counts = np.zeros(n_str, dt)
+    hashes = np.empty(cap, np.uint32)
+    spans = np.empty((cap, 2), dt) if want_spans else None
+    n = C.c_int64(0)
+    _lib.check(lib.latok_token_hashes_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, seed, _ptr(counts),
+                                                       _ptr(spans) if want_spans else None, _ptr(hashes), cap, C.byref(n), flags, None))
+    return counts, hashes[:n.value].copy(), (spans[:n.value].copy() if want_spans else None)
+
+
+def token_hashes_utf8_csr(utf8, byte_off, seed=0, dtype=np.int64, spans=False):
+    """(counts, hashes uint32[n_tokens][, spans[n_tokens, 2]]): MurmurHash3 x86_32 (``seed``) of the UTF-8 bytes of every stripped,
+    non-empty token -- the byte ranges token_spans_utf8_bytes_csr reports, in its order: hashes[k] belongs to spans[k].  counts
+    (and spans, with ``spans=True``) in ``dtype``.  Cut and hashed on the device (``latok_token_hashes_utf8_bytes_batch``); the
+    host sees no token text.  ``murmur3_32(token_bytes, seed)`` is the same word."""
+    counts, hashes, sp = _hashes_csr(utf8, byte_off, seed, dtype, spans)
+    return (counts, hashes, sp) if spans else (counts, hashes)
+
+
+def token_hashes_utf8_batch(blobs, seed=0):
+    """list[bytes] (UTF-8) -> list of uint32 arrays: the hashes of every string's tokens ('' and whitespace-only -> empty)."""
+    seed = _seed32(seed)
+    if len(blobs) == 0:
+        return []
+    utf8, byte_off = pack_utf8(blobs)
+    counts, hashes, _ = _hashes_csr(utf8, byte_off, seed, np.int64, False)
+    return np.split(hashes, np.cumsum(counts)[:-1])
+
+
+def token_hashes_batch(texts, seed=0):
+    """list[str] -> list of uint32 arrays: ``[murmur3_32(t.encode("utf-8"), seed) for t in tokenize(text)]`` of every string.  The
+    strings go through UTF-8 ("surrogatepass") on the host and the byte-space call."""
+    seed = _seed32(seed)
+    return token_hashes_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], seed)
+
+
 # ---- PEP 393 code units: 1 / 2 / 4 bytes per char, the buffer the reference itself reads (latok.c:53-55,79) -----------
 def pack_kind(texts):
     """list[str] -> (units, row_off): units uint8 / uint16 / uint32 = the narrowest PEP 393 kind that holds every char of
@@ -723,6 +797,20 @@ def flow_join_tokens_utf8_bytes(d_utf8, d_byte_off, n_str, total_bytes, d_out_by
     lib = _lib.ensure_init()
     _lib.check(lib.latok_flow_join_tokens_utf8_bytes(d_utf8, d_byte_off, int(n_str), int(total_bytes), sep, d_out_bytes, int(out_cap),
                                                      d_out_off, d_counts, d_result, flag32))
+
+
+def flow_token_hashes_utf8_bytes(d_utf8, d_byte_off, n_str, total_bytes, d_counts, d_spans, d_hashes, cap, d_result, seed=0,
+                                 dtype=np.int64):
+    """token hashes of one device-resident UTF-8 batch through the flow (``latok_flow_token_hashes_utf8_bytes``): what
+    ``token_hashes_utf8_csr`` reports, in device buffers, without waiting.  ``d_result`` = int64[2]: tokens, error word; more
+    tokens than ``cap`` means nothing was written to ``d_hashes`` / ``d_spans``.  ``d_counts`` and ``d_spans`` may be None.  The
+    arguments follow the C call, except that ``seed`` (its fifth) is a trailing keyword here and ``flags`` is ``dtype`` (the width
+    of counts and spans), as in the sibling wrappers."""
+    seed = _seed32(seed)
+    _, flag32 = _out_dtype(dtype)
+    lib = _lib.ensure_init()
+    _lib.check(lib.latok_flow_token_hashes_utf8_bytes(d_utf8, d_byte_off, int(n_str), int(total_bytes), seed, d_counts, d_spans, d_hashes,
+                                                      int(cap), d_result, flag32))
 
 
 def flow_wait():

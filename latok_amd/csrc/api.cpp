@@ -1453,6 +1453,54 @@ static int enqueue_join_tokens(Ctx& g, Workspace& w, const JoinTokens& a) {
     return LATOK_OK;
 }
 
+// Token hashes of a UTF-8 batch in BYTE space (latok_token_hashes_utf8_bytes_batch and its flow form): one MurmurHash3 x86_32 word
+// per stripped, non-empty token (the tokens of default_tokenizer.py:149-160, as latok_token_spans_utf8_bytes_batch cuts them), at
+// the token's rank.  One stream, nothing waits for the host:
+//   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
+//   k_word_counts + k_scan_chained                kept mask, token ranks; THE token total -> scalar word 0, r_tokens
+//   k_hash_scatter                                counts, the span records (if asked for) and the hashes (gate: total <= cap)
+// Every batch size takes this route: there is no one-launch form and no host decode, so a batch gives the same words at every size.
+// `w` was sized by ws_needs(w, total_bytes, true, false, false).
+struct TokenHashes {
+    Batch b;                       // UTF-8 bytes on the device (16-byte aligned), byte offsets, total in bytes (> 0), n_str > 0
+    uint32_t seed = 0;
+    void* counts = nullptr;        // NULL: not asked for
+    void* spans = nullptr;         // NULL: not asked for
+    uint32_t* hashes = nullptr;    // NULL: a size query
+    int64_t cap = 0;               // in tokens
+    bool o32 = false;              // width of the counts and records
+    int64_t* r_tokens = nullptr;   // the two result words as the device sees them (cleared by the caller): tokens,
+    int64_t* r_err = nullptr;      // int32-overflow flag (bit 0) in the low half, scan flag in the high half
+    hipStream_t st = nullptr;
+};
+static int enqueue_token_hashes(Ctx& g, Workspace& w, const TokenHashes& a) {
+    int rc;
+    const hipStream_t st = a.st;
+    const int64_t total = a.b.total, words = (total + 63) / 64;
+    uint64_t* d_bits = (uint64_t*)w.bits.p;
+    uint64_t* d_space = (uint64_t*)w.space.p;
+    uint64_t* d_kept = (uint64_t*)w.kept.p;
+    int64_t* d_rank = (int64_t*)w.bases.p;
+    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
+    uint16_t* d_pref = (uint16_t*)w.wpref.p;
+    int64_t* d_total = (int64_t*)w.scalar.p;
+    int* d_err = (int*)a.r_err;
+    unsigned epoch = 0;
+    Pipe p;
+    p.b = a.b;
+    p.bits = d_bits;
+    p.space = d_space;
+    p.st = st;
+    if ((rc = run_pipeline(g, w, p))) return rc;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    HIP_TRY(latok::launch_word_counts_scan(true, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank, (unsigned long long*)w.chain.p,
+                                           (unsigned*)w.chain_ctl.p, epoch, d_total, a.r_tokens, d_err + 1, st));
+    HIP_TRY(latok::launch_hash_scatter(a.o32, (const uint8_t*)a.b.in.p, a.seed, d_bits, d_space, d_kept, d_rank, d_tcnt, d_pref, words, total,
+                                       a.b.row, a.b.n_str, (const int64_t*)w.tile_first.p, a.hashes ? a.spans : nullptr, a.hashes, d_total, a.cap,
+                                       a.counts, d_err, st));
+    return LATOK_OK;
+}
+
 // The blocking call behind compact_common's checks: b = the caller's UTF-8 batch (total resolved, n_str > 0, total > 0).  Every
 // batch that the host did not decode takes this route, whatever its size.  One synchronisation.
 static int features_utf8_bytes_route(Ctx& g, const Batch& b, bool dev, bool o32, void* counts_out, void* items_out, int8_t* features_out,
@@ -1991,6 +2039,81 @@ int latok_join_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_
     return LATOK_OK;
 }
 
+/* token hashes in byte space: one MurmurHash3 x86_32 word per token, rank-aligned with the span records (enqueue_token_hashes) */
+int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, uint32_t seed,
+                                        int64_t* counts_out, int64_t* spans_out, uint32_t* hashes_out, int64_t cap, int64_t* n_tokens_out,
+                                        int flags, void* stream) {
+    LATOK_ENTER();
+    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (!n_tokens_out) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
+    *n_tokens_out = 0;
+    if (cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
+    if (!hashes_out && cap > 0) return fail(LATOK_ERR_INVALID, "hashes_out is NULL but cap > 0 (a size query passes cap = 0)");
+    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0, o32 = (flags & LATOK_OUT_INT32) != 0;
+    const size_t elt = o32 ? 4 : 8;   // width of a count and of one field of a record (a hash is 4 bytes in every mode)
+    int64_t total = total_bytes;
+    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
+    StreamTurn turn(g, stream);
+    hipStream_t st = turn.st;
+    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
+    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (n_str == 0 || total == 0) {   // no byte, no token
+        if (counts_out && n_str > 0) {
+            if (dev) {
+                HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)n_str * elt, st));
+                HIP_TRY(hipStreamSynchronize(st));
+            } else {
+                memset(counts_out, 0, (size_t)n_str * elt);
+            }
+        }
+        return LATOK_OK;
+    }
+    if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    if (dev && (((uintptr_t)spans_out & (2 * elt - 1)) != 0 || ((uintptr_t)counts_out & (elt - 1)) != 0 || ((uintptr_t)hashes_out & 3) != 0))
+        return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    g.last_route = 6;
+    Batch d;
+    if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
+    if ((rc = ws_ensure(ws_needs(g.ws, total, true, false, false).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+    int64_t* p_tot = (int64_t*)g.pin_tot.d;
+    TokenHashes a;
+    a.b = d;
+    a.seed = seed;
+    a.counts = counts_out;
+    a.spans = spans_out;
+    a.hashes = hashes_out;
+    a.cap = hashes_out ? std::min(cap, total) : 0;   // (a token has at least one byte: a larger capacity gates nothing, and the staging is sized by it)
+    a.o32 = o32;
+    if (!dev) {
+        if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 2 * elt + 16)) || (rc = g.counts.ensure((size_t)n_str * 8)))
+            return rc;
+        if (hashes_out) a.hashes = (uint32_t*)g.h_aux.p;
+        if (spans_out) a.spans = g.h_out.p;
+        if (counts_out) a.counts = g.counts.p;
+    }
+    h_tot[0] = h_tot[1] = 0;
+    a.r_tokens = p_tot;
+    a.r_err = p_tot + 1;
+    a.st = st;
+    if ((rc = enqueue_token_hashes(g, g.ws, a))) return rc;
+    if (!dev && counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));   // valid whatever the capacity
+    HIP_TRY(hipStreamSynchronize(st));   // the call's one wait for the kernels
+    if (h_tot[1] >> 32) { g.ws.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
+    if (h_tot[1] & 1) return fail(LATOK_ERR_INVALID, "a string is too long for LATOK_OUT_INT32; use the 64-bit form");
+    const int64_t n = h_tot[0];
+    *n_tokens_out = n;
+    if (n > cap) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld tokens", (long long)n);
+    if (!dev && n > 0 && hashes_out) {   // (host pointers: the copies, whose size is known only now)
+        HIP_TRY(hipMemcpyAsync(hashes_out, a.hashes, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        if (spans_out) HIP_TRY(hipMemcpyAsync(spans_out, a.spans, (size_t)n * 2 * elt, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return LATOK_OK;
+}
+
 /* PEP 393 buffers (the reference's own input, latok.c:53-55,79): fixed-width code units of 1, 2 or 4 bytes */
 static int check_kind(int kind) {
     if (kind != 1 && kind != 2 && kind != 4) return fail(LATOK_ERR_INVALID, "kind must be 1 (Latin-1), 2 (UCS-2) or 4 (UCS-4), got %d", kind);
@@ -2338,13 +2461,14 @@ int latok_debug_set_scan_epoch(unsigned epoch) {
 /* test hook (not part of the ABI; needs no device): the constants that decide the tile pipeline's plans and host paths, so that
  * tests take their thresholds from the library: out[0..8] = kTile, kWPB, kNarrowWPB, kSegMax, kOneSegTiles, kFastTailTiles,
  * kSmallChars, kSmallStrings, tiles per workgroup of k_lead_compress; out[9..13] = kFeatWaves, kFeatRound, kFeatRoundTm,
- * kFeatFormThresh, kFeatWinBytes of k_features_tiles.  Returns the number of values written. */
+ * kFeatFormThresh, kFeatWinBytes of k_features_tiles; out[14] = kHashWaveBytes (a longer token is hashed by its whole wave).  Returns
+ * the number of values written. */
 extern "C" int latok_debug_limits(int64_t* out, int n) {
-    const int64_t v[14] = {latok::kTile, latok::kWPB, latok::kNarrowWPB, latok::kSegMax, latok::kOneSegTiles, latok::kFastTailTiles,
+    const int64_t v[15] = {latok::kTile, latok::kWPB, latok::kNarrowWPB, latok::kSegMax, latok::kOneSegTiles, latok::kFastTailTiles,
                            kSmallChars, kSmallStrings, latok::kCompressWaves, latok::kFeatWaves, latok::kFeatRound, latok::kFeatRoundTm,
-                           latok::kFeatFormThresh, latok::kFeatWinBytes};
+                           latok::kFeatFormThresh, latok::kFeatWinBytes, latok::kHashWaveBytes};
     if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
-    const int k = n < 14 ? n : 14;
+    const int k = n < 15 ? n : 15;
     for (int i = 0; i < k; ++i) out[i] = v[i];
     return k;
 }
@@ -2407,7 +2531,8 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
  * 0: the batch's own units (UTF-32, PEP 393 units, UTF-8 in byte space), 1: a small UTF-8 host batch decoded by the host,
  * 2: UTF-8 through the staged device decoder, 3: UTF-8 through byte space and the packed code-point masks (and codes),
  * 4: featurize of UTF-8 in byte space (byte records from the byte-space masks, sums from the packed code-point masks),
- * 5: joined token text of UTF-8 in byte space (every batch size; there is no small-batch route) */
+ * 5: joined token text of UTF-8 in byte space (every batch size; there is no small-batch route),
+ * 6: token hashes of UTF-8 in byte space (every batch size as well) */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;
@@ -2988,6 +3113,93 @@ int latok_flow_join_tokens_utf8_bytes(const uint8_t* utf8_dev, const int64_t* by
     a.r_err = result_dev + 1;
     a.st = f.st;
     return enqueue_join_tokens(g, f.ws, a);
+}
+
+// ---- token hashes in a flow ------------------------------------------------------------------------------------------------------
+constexpr int kHashFlowRanges = 6;
+// every range of caller memory the batch touches, outputs first; returns their number.  The tracked length of the hashes and of
+// the records is what can be written at most -- min(cap, total_bytes) tokens, a token has at least one byte --, so a huge
+// "unbounded" capacity cannot wrap a range into an empty one.
+static int hash_flow_ranges(const uint8_t* u8, const int64_t* boff, int64_t n_str_in, int64_t total_bytes, void* counts, void* spans,
+                            uint32_t* hashes, int64_t cap, int64_t* result, bool o32, latok::FlowRange* r) {
+    const size_t n_str = (size_t)std::max<int64_t>(n_str_in, 0), bytes = (size_t)std::max<int64_t>(total_bytes, 0);
+    const size_t tokens = std::min((size_t)std::max<int64_t>(cap, 0), bytes), rec = o32 ? 4 : 8;
+    int n = 0;
+    r[n++] = latok::flow_range(result, 16, true);
+    r[n++] = latok::flow_range(hashes, tokens * 4, true);
+    r[n++] = latok::flow_range(spans, tokens * 2 * rec, true);
+    r[n++] = latok::flow_range(counts, n_str * rec, true);
+    r[n++] = latok::flow_range(u8, bytes, false);
+    r[n++] = latok::flow_range(boff, n_str ? (n_str + 1) * 8 : 0, false);
+    return n;
+}
+
+/* test hook (not part of the ABI; needs no device): the ranges a token-hash batch of a flow notes, in the form latok_debug_flow_route
+ * takes them.  addr[6] = {utf8, byte_off, counts, spans, hashes, result}.  Returns the number of ranges written to lo / bytes /
+ * is_write (at most n_max), < 0 on a bad argument. */
+extern "C" int latok_debug_flow_hashes_ranges(const uint64_t* addr, int64_t n_str, int64_t total_bytes, int64_t cap, int flags, uint64_t* lo,
+                                              uint64_t* bytes, int* is_write, int n_max) {
+    if (!addr || !lo || !bytes || !is_write) return fail(LATOK_ERR_INVALID, "bad argument");
+    latok::FlowRange r[kHashFlowRanges];
+    const int n = hash_flow_ranges((const uint8_t*)(uintptr_t)addr[0], (const int64_t*)(uintptr_t)addr[1], n_str, total_bytes,
+                                   (void*)(uintptr_t)addr[2], (void*)(uintptr_t)addr[3], (uint32_t*)(uintptr_t)addr[4], cap,
+                                   (int64_t*)(uintptr_t)addr[5], (flags & LATOK_OUT_INT32) != 0, r);
+    if (n > n_max) return fail(LATOK_ERR_INVALID, "need room for %d ranges", n);
+    for (int i = 0; i < n; ++i) {
+        lo[i] = (uint64_t)r[i].lo;
+        bytes[i] = (uint64_t)(r[i].hi - r[i].lo);
+        is_write[i] = r[i].write ? 1 : 0;
+    }
+    return n;
+}
+
+int latok_flow_token_hashes_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes, uint32_t seed,
+                                       void* counts_dev, void* spans_dev, uint32_t* hashes_dev, int64_t cap, int64_t* result_dev, int flags) {
+    LATOK_ENTER();
+    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (n_str < 0) return fail(LATOK_ERR_INVALID, "n_str must be >= 0");
+    if (cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
+    if (!hashes_dev && cap > 0) return fail(LATOK_ERR_INVALID, "hashes is NULL but cap > 0 (a size query passes cap = 0)");
+    if (!result_dev) return fail(LATOK_ERR_INVALID, "NULL result pointer");
+    if (((uintptr_t)result_dev & 7) != 0) return fail(LATOK_ERR_INVALID, "result pointer must be 8-byte aligned");
+    const bool o32 = (flags & LATOK_OUT_INT32) != 0;
+    const size_t rec = o32 ? 4 : 8;
+    if (((uintptr_t)spans_dev & (2 * rec - 1)) != 0 || ((uintptr_t)counts_dev & (rec - 1)) != 0 || ((uintptr_t)hashes_dev & 3) != 0)
+        return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    if (total_bytes < 0 && (rc = resolve_total_device(byte_off_dev, n_str, &total_bytes, g.stream))) return rc;
+    if ((rc = flow_setup(g))) return rc;
+    latok::FlowRange r[kHashFlowRanges];
+    const int n_r = hash_flow_ranges(utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, spans_dev, hashes_dev, cap, result_dev, o32, r);
+    int slot = 0;
+    if (n_str == 0 || total_bytes <= 0) {   // nothing to launch: no token
+        if ((rc = flow_pick(g, r, n_r, &slot))) return rc;
+        g.flow_held.note(slot, r, n_r);
+        HIP_TRY(hipMemsetAsync(result_dev, 0, 16, g.flow[slot].st));
+        if (counts_dev && n_str > 0) HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)n_str * rec, g.flow[slot].st));
+        return LATOK_OK;
+    }
+    if (!utf8_dev || !byte_off_dev) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (((uintptr_t)utf8_dev & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    if ((rc = flow_pick(g, r, n_r, &slot))) return rc;
+    Ctx::FlowSlot& f = g.flow[slot];
+    if ((rc = flow_reserve(g, ws_needs(f.ws, total_bytes, true, false, false).data(), kWsNeeds))) return rc;
+    g.flow_held.note(slot, r, n_r);   // before anything is enqueued (flow_begin)
+    ++g.flow_seq;
+    HIP_TRY(hipMemsetAsync(result_dev, 0, 16, f.st));
+    TokenHashes a;
+    a.b = Batch{Input{utf8_dev, Form::Utf8}, byte_off_dev, n_str, total_bytes};
+    a.seed = seed;
+    a.counts = counts_dev;
+    a.spans = spans_dev;
+    a.hashes = hashes_dev;
+    a.cap = hashes_dev ? std::min(cap, total_bytes) : 0;
+    a.o32 = o32;
+    a.r_tokens = result_dev;
+    a.r_err = result_dev + 1;
+    a.st = f.st;
+    return enqueue_token_hashes(g, f.ws, a);
 }
 
 int latok_flow_wait(void) {

@@ -5,6 +5,7 @@
 //   token spans        slice between consecutive boundaries, strip, drop ''   reference default_tokenizer.py:149-158
 //   token features     per-token sums of the 25 matrix columns (featurize)    reference default_tokenizer.py:163-191
 //   joined token text  the tokens themselves, sep.join per string, UTF-8 out  reference default_tokenizer.py:149-160   (below: "joined token text")
+//   token hashes       MurmurHash3 x86_32 of every token's UTF-8 bytes        reference default_tokenizer.py:149-160   (KIND 3 of k_counts_scatter's body)
 //
 // Inputs are the two bitmasks the tile kernel writes (boundary bits, SPACE bits; bit i = packed char i) and row_off.
 // Because strings are contiguous and ordered in the packed buffer, "all offsets of string 0, then string 1, ..." is
@@ -23,6 +24,7 @@
 #include "bitscan.h"
 #include "kernels.h"
 #include "lane_math.h"
+#include "token_hash.h"
 
 namespace latok {
 
@@ -242,7 +244,17 @@ __global__ __launch_bounds__(256) void k_string_counts(const uint64_t* __restric
 // KIND 2: spans4[4k..] = {raw start, raw end, stripped start, stripped end}: featurize's span record, for UTF-8 in BYTE space --
 // the sums of the same tokens are formed in code-point space by k_features_tiles, which then writes no records (a token has
 // the same rank in both spaces).  The other forms of featurize get their records from k_features_tiles, together with the sums.
+// KIND 3 (k_hash_scatter): KIND 1's records (out may be NULL: none) and hashes[k] = MurmurHash3 x86_32 of the stripped token's
+// bytes (token_hash.h).  In the token-major loop lane j holds token j's byte range: it walks its own token -- neighbouring lanes
+// hold neighbouring tokens, their aligned dword loads share cache lines --, unless the token is longer than kHashWaveBytes: those
+// the wave takes one at a time behind the round, 256 bytes per step with coalesced loads, every lane mixing its own block and
+// the h chain folded in lane order, so a long token costs its length once, with the whole wave at work.
 constexpr int scatter_waves(int kind) { return 4; }   // waves per workgroup
+struct HashArgs {
+    const uint32_t* text = nullptr;   // the batch's bytes as aligned dwords (the buffer is 16-byte aligned)
+    uint32_t* hashes = nullptr;
+    uint32_t seed = 0;
+};
 
 __device__ __forceinline__ int64_t scatter_lower_bound(const int64_t* __restrict__ row_off, int64_t n_entries, int64_t c,
                                                        int lane) {
@@ -271,7 +283,8 @@ __device__ __forceinline__ void counts_scatter_block(
     const int64_t* __restrict__ tile_rank, const int64_t* __restrict__ tile_cnt, const uint16_t* __restrict__ word_pref,
     int64_t n_words, int64_t total, const int64_t* __restrict__ row_off, int64_t n_str,
     const int64_t* __restrict__ tile_first, OUT* __restrict__ out, const int64_t* __restrict__ n_items_dev, int64_t cap,
-    OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, unsigned vb) {   // vb: (virtual) workgroup index
+    OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, unsigned vb,     // vb: (virtual) workgroup index
+    const HashArgs ha = HashArgs{}) {                                                            // (KIND 3 only)
     static_assert(scatter_waves(KIND) * 64 == 256, "both roles use 256-thread workgroups");
     if (vb >= n_scatter_blocks) {   // role 2: one thread per string
         if (counts)
@@ -433,6 +446,7 @@ __device__ __forceinline__ void counts_scatter_block(
             const uint64_t* orow = rows + 6 * owner;
             const uint64_t o_xb = orow[0], o_nn = orow[1], o_xb1 = orow[2], o_nn1 = orow[3], o_Bw = orow[4];
             const int64_t o_lo_in = (int64_t)orow[5];
+            int64_t h_a = 0, h_e = 0;                                 // (KIND 3) my token's absolute byte range
             if (active) {
                 const int64_t obase = (w0 + owner) << 6;
                 const uint64_t bl = o_Bw & ((2ull << b) - 1ull);      // string starts at or before the item (b = 63: all)
@@ -485,9 +499,37 @@ __device__ __forceinline__ void counts_scatter_block(
                             __builtin_nontemporal_store(r, rec);
                             __builtin_nontemporal_store(v, rec + 1);
                         }
-                    } else {
+                    } else if (KIND != 3 || out) {
                         __builtin_nontemporal_store(v, reinterpret_cast<out2*>(out) + base_out + win0 + j);
                     }
+                    if (KIND == 3) {
+                        h_a = a2;
+                        h_e = e2;
+                        if (e2 - a2 <= kHashWaveBytes) {
+                            const uint32_t* text = ha.text;
+                            const uint32_t h = th_hash_lane([text](int64_t i) { return text[i]; }, a2, e2, ha.seed);
+                            __builtin_nontemporal_store(h, ha.hashes + base_out + win0 + j);
+                        }
+                    }
+                }
+            }
+            if (KIND == 3) {
+                // the long tokens of the round, one at a time by the whole wave (wave-uniform loop: `todo` is a ballot)
+                const uint32_t* text = ha.text;
+                auto ld = [text](int64_t i) { return text[i]; };
+                for (uint64_t todo = __ballot(h_e - h_a > kHashWaveBytes); todo; todo &= todo - 1ull) {
+                    const int src = __builtin_ctzll(todo);
+                    const int64_t a = __shfl(h_a, src), e = __shfl(h_e, src);
+                    const int64_t rounds = (((e - a) >> 2) + kThWaveBlocks - 1) / kThWaveBlocks;
+                    uint32_t h = ha.seed;
+                    uint32_t mk = th_wave_block(ld, a, e, 0, lane);
+                    for (int64_t r = 0; r < rounds; ++r) {
+                        const uint32_t cur = mk;
+                        if (r + 1 < rounds) mk = th_wave_block(ld, a, e, r + 1, lane);   // (the next round's loads fly during the fold)
+                        h = th_wave_fold(h, [cur](int l) { return (uint32_t)__builtin_amdgcn_readlane((int)cur, l); }, th_wave_count(a, e, r));
+                    }
+                    h = th_wave_tail(ld, a, e, h);
+                    if (lane == src) __builtin_nontemporal_store(h, ha.hashes + base_out + win0 + j);
                 }
             }
         }
@@ -511,6 +553,18 @@ __global__ __launch_bounds__(scatter_waves(KIND) * 64) void k_counts_scatter(
         counts_scatter_block<KIND, OUT>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str,
                                         tile_first, out, n_items_dev, cap, counts, n_scatter_blocks, err, blockIdx.x);
     signal_block_done(done);   // (pinned outputs of a small host batch: the host polls the completion word)
+}
+
+// Token hashes: KIND 3 of the body above in a kernel of its own (the three kernels above keep their arguments).
+template <typename OUT>
+__global__ __launch_bounds__(scatter_waves(3) * 64) void k_hash_scatter(
+    const uint64_t* __restrict__ bits, const uint64_t* __restrict__ space, const uint64_t* __restrict__ item_mask,
+    const int64_t* __restrict__ tile_rank, const int64_t* __restrict__ tile_cnt, const uint16_t* __restrict__ word_pref,
+    int64_t n_words, int64_t total, const int64_t* __restrict__ row_off, int64_t n_str,
+    const int64_t* __restrict__ tile_first, OUT* __restrict__ out, const int64_t* __restrict__ n_items_dev, int64_t cap,
+    OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, HashArgs ha) {
+    counts_scatter_block<3, OUT>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str, tile_first, out,
+                                 n_items_dev, cap, counts, n_scatter_blocks, err, blockIdx.x, ha);
 }
 
 // ---- code-point results of a UTF-8 batch from its BYTE-space results ------------------------------------------------------
@@ -1165,6 +1219,29 @@ hipError_t launch_counts_scatter(int kind, bool out32, const uint64_t* bits, con
     if (kind == 2) return out32 ? LATOK_CS(2, int32_t) : LATOK_CS(2, int64_t);
     return out32 ? LATOK_CS(1, int32_t) : LATOK_CS(1, int64_t);
 #undef LATOK_CS
+}
+
+// token hashes (+ the span records if out != NULL, + the counts if counts != NULL); hashes == NULL: counts only (a size query)
+hipError_t launch_hash_scatter(bool out32, const uint8_t* u8, uint32_t seed, const uint64_t* bits, const uint64_t* space,
+                               const uint64_t* kept, const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref,
+                               int64_t n_words, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,
+                               uint32_t* hashes, const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st) {
+    if (n_words <= 0) return hipSuccess;
+    const unsigned nb_scatter = hashes ? (unsigned)((n_words + 255) / 256) : 0u;
+    const unsigned nb_counts = counts ? (unsigned)((n_str + 255) / 256) : 0u;
+    if (nb_scatter + nb_counts == 0) return hipSuccess;
+    HashArgs ha;
+    ha.text = reinterpret_cast<const uint32_t*>(u8);
+    ha.hashes = hashes;
+    ha.seed = seed;
+    const dim3 grid(nb_scatter + nb_counts), block(scatter_waves(3) * 64);
+    if (out32)
+        hipLaunchKernelGGL((k_hash_scatter<int32_t>), grid, block, 0, st, bits, space, kept, tile_rank, tile_cnt, word_pref, n_words, total,
+                           row_off, n_str, tile_first, (int32_t*)out, n_items_dev, cap, (int32_t*)counts, nb_scatter, err, ha);
+    else
+        hipLaunchKernelGGL((k_hash_scatter<int64_t>), grid, block, 0, st, bits, space, kept, tile_rank, tile_cnt, word_pref, n_words, total,
+                           row_off, n_str, tile_first, (int64_t*)out, n_items_dev, cap, (int64_t*)counts, nb_scatter, err, ha);
+    return hipGetLastError();
 }
 
 }  // namespace latok

@@ -267,6 +267,14 @@ hipError_t launch_join_scatter(const uint8_t* u8, int64_t total, const uint64_t*
                                const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, const int64_t* row_off,
                                int64_t n_str, int sep, uint8_t* out, int64_t cap, const int64_t* n_items_dev, int64_t* out_off,
                                int* err, hipStream_t st);
+// token hashes of a UTF-8 batch in byte space (compact_kernels.hip: KIND 3): behind k_word_counts<true> + k_scan_chained, the
+// per-string counts (counts may be NULL), the span records of KIND 1 (out may be NULL) and one MurmurHash3 x86_32 word per token
+// at its rank, the last two only if the total fits cap.  A token of more than kHashWaveBytes bytes is hashed by its whole wave.
+constexpr int kHashWaveBytes = 256;
+hipError_t launch_hash_scatter(bool out32, const uint8_t* u8, uint32_t seed, const uint64_t* bits, const uint64_t* space,
+                               const uint64_t* kept, const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref,
+                               int64_t n_words, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,
+                               uint32_t* hashes, const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st);
 // zeros at codes[t .. t + kTile + 256), t = *total_dev held inside [0, bound]
 hipError_t launch_pad_codes(uint8_t* codes, const int64_t* total_dev, int64_t bound, hipStream_t st);
 int64_t utf8_blocks(int64_t total_bytes);   // 4 KiB blocks of the chunk-parallel UTF-8 decoder

@@ -27,6 +27,9 @@
                   one space, UTF-8 out (no counts asked for); beside them, in the same process run,
   bytes_spans32 / bytes_spans32_flow   latok_token_spans_utf8_bytes_batch / latok_flow_token_spans(kind 0) with LATOK_OUT_INT32: the
                   stage the join replaces for a caller who wants text
+  bytes_hashes32 / bytes_hashes32_flow / bytes_hashes_only / bytes_hashes_only_flow   latok_token_hashes_utf8_bytes_batch /
+                  latok_flow_token_hashes_utf8_bytes: one MurmurHash3 x86_32 word per token, with the int32 counts and records of
+                  bytes_spans32 (hashes32) or alone (hashes_only: no counts, no records); same process run as bytes_spans32
   py_join        end to end in Python on host blobs (the first --py-strings strings): batch.join_tokens_utf8_batch(blobs) against the
                   only route to the same rows without it, [b" ".join(t) for t in batch.tokenize_utf8_batch(blobs)]; one line each
   rules_mask      latok_split_mask_batch after latok_set_rules(built-in tables)   (8f-4)
@@ -90,6 +93,7 @@ def main():
                                        "utf8_mask_flow,utf8_offsets_flow,utf8_offsets32_flow,utf8_spans_flow,utf8_spans32_flow,utf8_features32_flow,utf8_decode_features32,"
                                        "utf8_bytes_features32,utf8_bytes_features32_flow,pair_features32_bytes_spans32,pair_features32_bytes_spans32_flow,"
                                        "bytes_mask,bytes_offsets,bytes_spans,bytes_spans32,bytes_spans32_flow,bytes_join,bytes_join_flow,"
+                                       "bytes_hashes32,bytes_hashes32_flow,bytes_hashes_only,bytes_hashes_only_flow,"
                                        "rules_mask,kind_mask,kind_offsets,kind_offsets32,"
                                        "kind_spans,kind_spans32")
     ap.add_argument("--py-strings", type=int, default=200_000, help="strings of the py_join path (host blobs)")
@@ -370,17 +374,25 @@ def main():
         run("bytes_spans", lambda: lib.latok_token_spans_utf8_bytes_batch(d_u8, d_boff, n, n8, d_counts, d_items, cap, C.byref(nout), D, None),
             lambda: n8 + csr + 8 * n + 16 * nout.value, "UTF-8 bytes + 8 B/string read; 8 B/string + 16 B/token written (byte ranges)")
     # joined token text and the byte-space spans beside it: every line of this leg in one process run, in the order given
-    join_leg = [p for p in paths if p in ("bytes_join", "bytes_join_flow", "bytes_spans32", "bytes_spans32_flow", "py_join")]
+    join_leg = [p for p in paths if p in ("bytes_join", "bytes_join_flow", "bytes_spans32", "bytes_spans32_flow", "bytes_hashes32",
+                                          "bytes_hashes32_flow", "bytes_hashes_only", "bytes_hashes_only_flow", "py_join")]
     if join_leg:
-        jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64)]
+        jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64, cap * 4, cap * 4)]
         if not all(jb):
             raise RuntimeError(_lib.last_error())
-        j_out, j_off, k_out, k_off, s_items, s_counts, t_items, t_counts, j_res = jb
+        j_out, j_off, k_out, k_off, s_items, s_counts, t_items, t_counts, j_res, h_a, h_b = jb
         resj = lambda i: C.c_void_p(j_res + 16 * (i & 1))  # noqa: E731
         note_j = "UTF-8 bytes + 8 B/string read; body / head planes 2 x 1 bit/byte written and read; 1 B/output byte + 8 B/string row offsets written"
         note_s = "UTF-8 bytes + 8 B/string read; 4 B/string + 8 B/token written (byte ranges, LATOK_OUT_INT32)"
         join_blocking = lambda: lib.latok_join_tokens_utf8_bytes_batch(d_u8, d_boff, n, n8, 32, j_out, 2 * n8, j_off, None, C.byref(nout), D, None)  # noqa: E731
         spans_blocking = lambda: lib.latok_token_spans_utf8_bytes_batch(d_u8, d_boff, n, n8, s_counts, s_items, cap, C.byref(nout), D32, None)  # noqa: E731
+
+        note_h = "UTF-8 bytes + 8 B/string read, the bytes of every token read once more; 4 B/token written (MurmurHash3 x86_32)"
+        SEED = 0x9747B28C
+
+        def hashes_blocking(rec):
+            return lib.latok_token_hashes_utf8_bytes_batch(d_u8, d_boff, n, n8, SEED, s_counts if rec else None, s_items if rec else None, h_a, cap,
+                                                           C.byref(nout), D32, None)
 
         def two_words(name, want):
             res = np.empty(4, np.int64)
@@ -406,6 +418,19 @@ def main():
                 run_flow(name, lambda i: lib.latok_flow_token_spans(d_u8, 0, d_boff, n, n8, t_counts if i & 1 else s_counts,
                                                                     t_items if i & 1 else s_items, cap, resj(i), _lib.OUT_INT32),
                          lambda: n8 + csr + 4 * n + 8 * items_n, note_s)
+                two_words(name, items_n)
+            elif name in ("bytes_hashes32", "bytes_hashes_only"):
+                rec = name == "bytes_hashes32"
+                run(name, lambda: hashes_blocking(rec), lambda: n8 + csr + 4 * nout.value + (4 * n + 8 * nout.value if rec else 0),
+                    note_h + (" + " + note_s if rec else ""))
+            elif name in ("bytes_hashes32_flow", "bytes_hashes_only_flow"):
+                rec = name == "bytes_hashes32_flow"
+                _lib.check(hashes_blocking(rec))
+                items_n = nout.value
+                run_flow(name, lambda i: lib.latok_flow_token_hashes_utf8_bytes(d_u8, d_boff, n, n8, SEED, (t_counts if i & 1 else s_counts) if rec else None,
+                                                                                (t_items if i & 1 else s_items) if rec else None,
+                                                                                h_b if i & 1 else h_a, cap, resj(i), _lib.OUT_INT32),
+                         lambda: n8 + csr + 4 * items_n + (4 * n + 8 * items_n if rec else 0), note_h + (" + " + note_s if rec else ""))
                 two_words(name, items_n)
             else:   # py_join: host blobs in, host rows out, both routes in this process
                 from latok_amd import batch
