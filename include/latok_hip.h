@@ -129,6 +129,8 @@ int latok_token_spans_batch(const uint32_t* cps, const int64_t* row_off, int64_t
  * A batch can also be handed over as UTF-8: `utf8` = packed bytes of all strings, `byte_off[n_str + 1]` = byte offset
  * of each string (byte_off[0] == 0).  The library decodes on the device (one code point per lead byte; input must be
  * valid UTF-8, "surrogatepass" forms decode as they are, truncated sequences give U+FFFD) and runs the same pipeline.
+ * Each string must itself be valid UTF-8: on malformed input a sequence that a string's end cuts is read on into the
+ * following string's bytes (the window of a lead byte is taken from the packed stream), never past the end of the batch.
  * All results are in CODE-POINT units, exactly what the reference would report for the decoded str.  With host
  * pointers this moves 1 byte per ASCII char over PCIe instead of 4. */
 int latok_utf8_decode_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,

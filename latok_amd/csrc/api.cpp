@@ -2461,14 +2461,16 @@ int latok_debug_set_scan_epoch(unsigned epoch) {
 /* test hook (not part of the ABI; needs no device): the constants that decide the tile pipeline's plans and host paths, so that
  * tests take their thresholds from the library: out[0..8] = kTile, kWPB, kNarrowWPB, kSegMax, kOneSegTiles, kFastTailTiles,
  * kSmallChars, kSmallStrings, tiles per workgroup of k_lead_compress; out[9..13] = kFeatWaves, kFeatRound, kFeatRoundTm,
- * kFeatFormThresh, kFeatWinBytes of k_features_tiles; out[14] = kHashWaveBytes (a longer token is hashed by its whole wave).  Returns
- * the number of values written. */
+ * kFeatFormThresh, kFeatWinBytes of k_features_tiles; out[14] = kHashWaveBytes (a longer token is hashed by its whole wave);
+ * out[15..16] = kScanSmallMax (more entries: the exclusive scan takes three launches), kU8Block (bytes per block of the staged
+ * UTF-8 decoder, one scan entry each).  Returns the number of values written. */
 extern "C" int latok_debug_limits(int64_t* out, int n) {
-    const int64_t v[15] = {latok::kTile, latok::kWPB, latok::kNarrowWPB, latok::kSegMax, latok::kOneSegTiles, latok::kFastTailTiles,
+    const int64_t v[17] = {latok::kTile, latok::kWPB, latok::kNarrowWPB, latok::kSegMax, latok::kOneSegTiles, latok::kFastTailTiles,
                            kSmallChars, kSmallStrings, latok::kCompressWaves, latok::kFeatWaves, latok::kFeatRound, latok::kFeatRoundTm,
-                           latok::kFeatFormThresh, latok::kFeatWinBytes, latok::kHashWaveBytes};
+                           latok::kFeatFormThresh, latok::kFeatWinBytes, latok::kHashWaveBytes, latok::scan_small_max(),
+                           latok::utf8_block_bytes()};
     if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
-    const int k = n < 15 ? n : 15;
+    const int k = n < 17 ? n : 17;
     for (int i = 0; i < k; ++i) out[i] = v[i];
     return k;
 }

@@ -278,6 +278,8 @@ hipError_t launch_hash_scatter(bool out32, const uint8_t* u8, uint32_t seed, con
 // zeros at codes[t .. t + kTile + 256), t = *total_dev held inside [0, bound]
 hipError_t launch_pad_codes(uint8_t* codes, const int64_t* total_dev, int64_t bound, hipStream_t st);
 int64_t utf8_blocks(int64_t total_bytes);   // 4 KiB blocks of the chunk-parallel UTF-8 decoder
+int64_t utf8_block_bytes();                 // kU8Block: bytes per block of that decoder (latok_debug_limits)
+int64_t scan_small_max();                   // kScanSmallMax: entries above which launch_exclusive_scan takes three launches
 hipError_t launch_utf8_block_counts(const uint8_t* u8, int64_t total, int64_t* block_cnt, hipStream_t st);
 hipError_t launch_utf8_decode(const uint8_t* u8, int64_t total, const int64_t* byte_off, int64_t n_str,
                               const int64_t* block_base, uint16_t* chunk_pref, int64_t total_cps, uint32_t* cps,

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import ALPHABETS, RULE_SETS, pack, random_strings
+from helpers import utf8_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -213,10 +214,13 @@ def test_malformed_input_equals_the_staged_decoder(gpu):
         blobs = body[:1500] + extra + body[1500:] + extra
         u8, boff = batch.pack_utf8(blobs)
         assert u8.size > SMALL_CHARS
+        cps, row = batch.utf8_decode_csr(u8, boff)
+        want_cps, want_row, _ = utf8_ref.decode_batch(u8, boff)        # the decoder's output is the rule's before it is the expectation
+        assert np.array_equal(cps, want_cps) and np.array_equal(row, want_row), route
         for dt in DTYPES:
             got = batch.token_features_utf8_csr(u8, boff, dtype=dt)
             assert _route() == route, (route, dt)
-            _same(got, batch.token_features_csr(*batch.utf8_decode_csr(u8, boff), dtype=dt), (route, dt))
+            _same(got, batch.token_features_csr(cps, row, dtype=dt), (route, dt))
 
 
 def test_small_and_mid_batches_keep_their_routes(gpu):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import ALPHABETS, RULE_SETS, pack, random_strings
+from helpers import utf8_ref
 from test_gpu_features_utf8 import _edge_text, _oracle_raw
 
 pytestmark = pytest.mark.gpu
@@ -458,7 +459,9 @@ def test_malformed_input_is_reported_not_decoded(gpu):
             for j in jobs:
                 j.submit()
             batch.flow_wait()
-            cps, row = batch.utf8_decode_csr(u8, boff)                  # the staged decoder
+            cps, row = batch.utf8_decode_csr(u8, boff)                  # the staged decoder, held to the rule first
+            want_cps, want_row, _ = utf8_ref.decode_batch(u8, boff)
+            assert np.array_equal(cps, want_cps) and np.array_equal(row, want_row)
             if not bad:
                 res, bits, rowo = jobs[0].mask()
                 assert res[2] == row[-1] and np.array_equal(bits, batch.split_mask_batch(cps, row)) and np.array_equal(rowo, row)
@@ -655,6 +658,8 @@ def test_c_example_flow_utf8_codepoints(gpu, oracle, tmp_path):
     want = ["batch 0: %d code points, well formed" % sum(map(len, good))]
     want += ["0.%d:" % i + "".join(" %d" % o for o in (oracle.split_offsets(t) if t else [])) for i, t in enumerate(good)]
     cps, row = batch.utf8_decode_csr(*batch.pack_utf8(bad))                       # what the staged decoder makes of the bytes
+    want_cps, want_row, _ = utf8_ref.decode_batch(*batch.pack_utf8(bad))
+    assert np.array_equal(cps, want_cps) and np.array_equal(row, want_row)
     decoded = [cps[row[i]:row[i + 1]].astype("<u4").tobytes().decode("utf-32-le", "surrogatepass") for i in range(len(bad))]
     want += ["batch 1: %d code points, malformed -> blocking call" % sum(b[0] & 0xC0 != 0x80 for b in [bytes([x]) for x in b"".join(bad)])]
     want += ["1.%d:" % i + "".join(" %d" % o for o in oracle.split_offsets(t)) for i, t in enumerate(decoded)]

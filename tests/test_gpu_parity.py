@@ -2,11 +2,13 @@
 this is integer / byte / index work."""
 import ctypes as C
 import random
+import zlib
 
 import numpy as np
 import pytest
 
 from conftest import ALPHABETS, bits_to_bool, pack, random_strings
+from helpers import utf8_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -51,7 +53,7 @@ def test_reference_main_sentence(gpu, oracle):
     ("rare_space_at", 3, 5000, 30000), ("words", 200, 0, 200), ("mixed", 3000, 0, 12), ("starts", 2000, 1, 3),
 ])
 def test_random_adversarial(gpu, oracle, kind, n, lo, hi):
-    rng = random.Random(hash((kind, n, lo, hi)) & 0xFFFF)
+    rng = random.Random(zlib.crc32(repr((kind, n, lo, hi)).encode()) & 0xFFFF)
     for _ in range(6):
         _check_batch(oracle, random_strings(rng, rng.randint(1, n), lo, hi, ALPHABETS[kind]))
 
@@ -803,6 +805,8 @@ def test_utf8_code_point_mask_without_a_utf32_copy(gpu, oracle):
         cps, row = batch.utf8_decode_csr(u8, boff)               # the staged decoder: one code point per lead byte
         is_lead = (u8 & 0xC0) != 0x80
         assert cps.size == int(is_lead.sum())
+        want_cps, want_row, _ = utf8_ref.decode_batch(u8, boff)  # ... held to the rule before it serves as the expectation
+        assert np.array_equal(cps, want_cps) and np.array_equal(row, want_row), it
         got, got_row = batch.split_mask_utf8_csr(u8, boff)
         assert np.array_equal(got_row, row), it
         assert np.array_equal(got, batch.split_mask_batch(cps, row)), it
@@ -818,6 +822,8 @@ def test_utf8_code_point_mask_without_a_utf32_copy(gpu, oracle):
         u8, boff = batch.pack_utf8(blobs)
         cps, row = batch.utf8_decode_csr(u8, boff)
         assert cps[-1] == 0xFFFD and row[-1] == cps.size == int(((u8 & 0xC0) != 0x80).sum()), tail
+        want_cps, want_row, _ = utf8_ref.decode_batch(u8, boff)
+        assert np.array_equal(cps, want_cps) and np.array_equal(row, want_row), tail
         got, got_row = batch.split_mask_utf8_csr(u8, boff)
         assert np.array_equal(got_row, row) and np.array_equal(got, batch.split_mask_batch(cps, row)), tail
 
@@ -860,7 +866,7 @@ def test_runtime_rule_tables(gpu, oracle, name):
     tables by the oracle; bitmask, offsets and token spans."""
     from conftest import RULE_SETS, oracle_rule_bits, random_rule_tables
     from latok_amd import batch
-    rng = random.Random(hash(name) & 0xFFFF)
+    rng = random.Random(zlib.crc32(name.encode()) & 0xFFFF)
     try:
         for rep in range(5 if name == "random" else 2):
             tables = random_rule_tables(rng) if name == "random" else RULE_SETS[name]
