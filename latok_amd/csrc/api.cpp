@@ -194,12 +194,18 @@ struct WsNeed {
 };
 constexpr int kTileNeeds = 4;   // the first entries of ws_needs: the tile stage
 constexpr int kWsNeeds = 22;
-// The one sizing rule of a workspace: every buffer a batch of `units` positions uses and its byte size.  token spans (spans)
-// add the SPACE and kept planes, featurize (feats) the code bytes, and narrow units read by featurize (widen) a UTF-32 copy.
-// cp_rows > 0: `units` UTF-8 bytes whose results are reported in code points (cp_rows = n_str + 1): every buffer is sized by the
-// byte count, which bounds the code-point count.  join: the two planes of the joined token text (UTF-8 bytes, with spans).
-static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, bool spans, bool feats, bool widen, int64_t cp_rows = 0,
-                                             bool join = false) {
+// What a batch asks of its workspace beyond the tile stage.  token spans (spans) add the SPACE and kept planes, featurize (feats)
+// the code bytes, and narrow units read by featurize (widen) a UTF-32 copy.  cp_rows > 0: the units are UTF-8 bytes whose results
+// are reported in code points (cp_rows = n_str + 1): every buffer is sized by the byte count, which bounds the code-point count.
+// join: the two planes of the joined token text (UTF-8 bytes, with spans).
+struct WsShape {
+    bool spans = false, feats = false, widen = false, join = false;
+    int64_t cp_rows = 0;
+};
+// The one sizing rule of a workspace: every buffer a batch of `units` positions uses and its byte size.
+static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const WsShape& shape) {
+    const bool spans = shape.spans, feats = shape.feats, widen = shape.widen, join = shape.join;
+    const int64_t cp_rows = shape.cp_rows;
     const size_t t = (size_t)std::max<int64_t>((units + latok::kTile - 1) / latok::kTile, 1);
     const size_t words = (size_t)((units + 63) / 64), c_tiles = (words + 63) / 64;
     return {{{&w.summ, t * 16},
@@ -385,7 +391,7 @@ int run_pipeline(Ctx& g, Workspace& w, const Pipe& a) {
     // run-time rule tables (latok_set_rules): the same input form, rules interpreted from the kernel arguments
     if (g.rules_on && mode != latok::kModeBlockMask) mode = latok::mode_with_rules(mode);
     const int64_t n_tiles = (total + latok::kTile - 1) / latok::kTile;
-    int rc = ws_ensure(ws_needs(w, total, false, false, false).data(), kTileNeeds);
+    int rc = ws_ensure(ws_needs(w, total, WsShape{}).data(), kTileNeeds);
     if (rc) return rc;
     latok::SplitParams P;
     P.cps = in.form == Form::Utf32 ? (const uint32_t*)in.p : nullptr;
@@ -514,6 +520,26 @@ int units_on_device(Ctx& g, const Batch& b, bool dev, hipStream_t st, Batch* d) 
     HIP_TRY(hipMemcpyAsync(g.u_boff.p, b.row, (size_t)(b.n_str + 1) * 8, hipMemcpyHostToDevice, st));
     d->in.p = g.u_bytes.p;
     d->row = (const int64_t*)g.u_boff.p;
+    return LATOK_OK;
+}
+
+// A batch without a unit has no item: all its counts (or row offsets) are zero.  Host memory is cleared in place, device memory
+// on the call's stream -- waited for when the caller returns straight away (sync).  Nothing behind a NULL pointer.
+int zero_counts(bool dev, void* p, size_t bytes, hipStream_t st, bool sync = false) {
+    if (!p || bytes == 0) return LATOK_OK;
+    if (!dev) memset(p, 0, bytes);
+    else HIP_TRY(hipMemsetAsync(p, 0, bytes, st));
+    if (dev && sync) HIP_TRY(hipStreamSynchronize(st));
+    return LATOK_OK;
+}
+int refuse_too_long() { return fail(LATOK_ERR_INVALID, "a string is too long for LATOK_OUT_INT32; use the 64-bit form"); }
+// The pinned pair of a blocking call after its one synchronisation: h[0] = the total, h[1] = the scan's own flag (high half) and
+// the int32-overflow flag (the bits `o32_mask` of the low half: all of them on the compaction routes, bit 0 for join and hashes,
+// whose low half also carries the capacity flag).  A scan that met corrupt look-back state has its state cleared by the next call.
+int finish_totals(Workspace& w, const volatile int64_t* h, int64_t o32_mask, int64_t* total_out) {
+    if (h[1] >> 32) { w.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
+    if (h[1] & o32_mask) return refuse_too_long();
+    *total_out = h[0];
     return LATOK_OK;
 }
 
@@ -808,7 +834,7 @@ int latok_reserve(int64_t max_chars, int64_t max_strings) {
     int rc = need_init(g);
     if (rc) return rc;
     if (max_chars < 0 || max_strings < 0) return fail(LATOK_ERR_INVALID, "negative size");
-    return ws_ensure(ws_needs(g.ws, max_chars, false, false, false).data(), kTileNeeds);
+    return ws_ensure(ws_needs(g.ws, max_chars, WsShape{}).data(), kTileNeeds);
 }
 
 // one rule table: row-major int8 [rows x cols] as build_combo_matrix returns it -> per-row column sets
@@ -996,7 +1022,7 @@ static int enqueue_compaction_dev(Ctx& g, Workspace& w, const Compaction& c) {
     const hipStream_t st = c.st;
     const bool widen = c.feats && c.b.in.narrow();   // featurize re-reads the code points: widen once, on the device
     if (widen && ((uintptr_t)c.b.in.p & (c.b.in.width() - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned code units");
-    if ((rc = ws_ensure(ws_needs(w, total, c.spans, c.feats, widen).data(), kWsNeeds))) return rc;
+    if ((rc = ws_ensure(ws_needs(w, total, WsShape{.spans = c.spans, .feats = c.feats, .widen = widen}).data(), kWsNeeds))) return rc;
     Pipe a;
     a.b = c.b;
     a.st = st;
@@ -1115,7 +1141,7 @@ static int compact_host_pipelined_body(Ctx& g, bool spans, bool feats, bool o32,
     }
     if ((rc = g.pipe_tot.ensure(8 * 16))) return rc;
     // size the workspace for the largest chunk now: growing a buffer later would free it under a chunk that is still running
-    if ((rc = ws_ensure(ws_needs(g.ws, max_chars, spans, feats, feats && h.in.narrow()).data(), kWsNeeds))) return rc;
+    if ((rc = ws_ensure(ws_needs(g.ws, max_chars, WsShape{.spans = spans, .feats = feats, .widen = feats && h.in.narrow()}).data(), kWsNeeds))) return rc;
     int64_t running = 0;
     bool overflow = false, too_long = false;
     std::vector<int64_t> n_of(n_chunks, 0);
@@ -1123,8 +1149,9 @@ static int compact_host_pipelined_body(Ctx& g, bool spans, bool feats, bool o32,
         const int slot = c & 1;
         HIP_TRY(hipEventSynchronize(g.ev_k_done[slot]));
         volatile int64_t* h = (volatile int64_t*)g.pipe_tot.h + 2 * (c & 7);
-        const int64_t n = h[0];
-        if (h[1] >> 32) { g.ws.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
+        int64_t n = 0;
+        // (mask 0: a chunk that overflows int32 does not end the call while later chunks are in flight: refused once, at the end)
+        if ((rc = finish_totals(g.ws, h, 0, &n))) return rc;
         if (h[1] & 0xFFFFFFFFll) too_long = true;
         n_of[c] = n;
         const int64_t s0 = cut[c], ns = cut[c + 1] - cut[c];
@@ -1191,7 +1218,7 @@ static int compact_host_pipelined_body(Ctx& g, bool spans, bool feats, bool o32,
     HIP_TRY(hipStreamSynchronize(g.s_d2h));
     HIP_TRY(hipStreamSynchronize(st));
     *n_items_out = running;
-    if (too_long) return fail(LATOK_ERR_INVALID, "a string is too long for LATOK_OUT_INT32; use the 64-bit form");
+    if (too_long) return refuse_too_long();
     if (running > items_cap) return fail(LATOK_ERR_INVALID, "output capacity too small: need %lld", (long long)running);
     if (running > 0 && !items_out) return fail(LATOK_ERR_INVALID, "output buffer is NULL");
     return LATOK_OK;
@@ -1269,7 +1296,7 @@ static int cp_masks_via_bytes(Ctx& g, const Batch& d, uint64_t* d_out, uint64_t*
     *fallback_out = 0;
     Workspace& w = g.ws;
     const int64_t total_bytes = d.total, words_b = (total_bytes + 63) / 64, c_tiles = (words_b + 63) / 64;
-    if ((rc = ws_ensure(ws_needs(w, total_bytes, false, codes, false).data(), kWsNeeds)) || (rc = g.u_lead.ensure((size_t)words_b * 8 + 8)) ||
+    if ((rc = ws_ensure(ws_needs(w, total_bytes, WsShape{.feats = codes}).data(), kWsNeeds)) || (rc = g.u_lead.ensure((size_t)words_b * 8 + 8)) ||
         (d_out_space && (rc = g.u_bspace.ensure((size_t)words_b * 8 + 8))) || (rc = g.pin_tot.ensure(64)))
         return rc;
     unsigned epoch = 0;
@@ -1321,7 +1348,7 @@ static int cp_masks_via_bytes(Ctx& g, const Batch& d, uint64_t* d_out, uint64_t*
 // The three scans share the workspace's rank arrays (bases / wcnt / wpref) and kept mask: every consumer of one scan has been
 // enqueued before the next scan overwrites them, and the stream orders them.  The token total is written once, by the byte-space
 // scan (the code-point scan's own total goes to scalar word 2 and to no result word), and gates both writers.  Sizes behind the
-// lead scan are the byte count, an upper bound (DeviceTotal).  `w` was sized by ws_needs(w, total_bytes, true, true, false, n_str + 1).
+// lead scan are the byte count, an upper bound (DeviceTotal).  `w` was sized by ws_needs with WsShape{.spans = true, .feats = true, .cp_rows = n_str + 1}.
 struct Utf8BytesFeats {
     Batch b;                      // UTF-8 bytes on the device, byte offsets, total in bytes (> 0), n_str > 0
     bool o32 = false;
@@ -1402,7 +1429,7 @@ static int enqueue_utf8_bytes_features(Ctx& g, Workspace& w, const Utf8BytesFeat
 //   k_scan_chained                                     tile ranks; THE byte total -> scalar word 0, r_bytes
 //   k_join_scatter                                     the bytes (gate: total <= cap), out_off; bit 2 of the error word if the total exceeds cap
 // Every batch size takes this route: there is no one-launch form and no host decode, so a batch gives the same bytes at every size.
-// `w` was sized by ws_needs(w, total_bytes, true, false, false, 0, true).
+// `w` was sized by ws_needs with WsShape{.spans = true, .join = true}.
 struct JoinTokens {
     Batch b;                      // UTF-8 bytes on the device, byte offsets, total in bytes (> 0), n_str > 0
     int sep = ' ';
@@ -1460,7 +1487,7 @@ static int enqueue_join_tokens(Ctx& g, Workspace& w, const JoinTokens& a) {
 //   k_word_counts + k_scan_chained                kept mask, token ranks; THE token total -> scalar word 0, r_tokens
 //   k_hash_scatter                                counts, the span records (if asked for) and the hashes (gate: total <= cap)
 // Every batch size takes this route: there is no one-launch form and no host decode, so a batch gives the same words at every size.
-// `w` was sized by ws_needs(w, total_bytes, true, false, false).
+// `w` was sized by ws_needs with WsShape{.spans = true}.
 struct TokenHashes {
     Batch b;                       // UTF-8 bytes on the device (16-byte aligned), byte offsets, total in bytes (> 0), n_str > 0
     uint32_t seed = 0;
@@ -1512,7 +1539,8 @@ static int features_utf8_bytes_route(Ctx& g, const Batch& b, bool dev, bool o32,
     const size_t elt = o32 ? 4 : 8;
     Batch d;
     if ((rc = units_on_device(g, b, dev, st, &d))) return rc;
-    if ((rc = ws_ensure(ws_needs(g.ws, total_bytes, true, true, false, n_str + 1).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+    if ((rc = ws_ensure(ws_needs(g.ws, total_bytes, WsShape{.spans = true, .feats = true, .cp_rows = n_str + 1}).data(), kWsNeeds))) return rc;
+    if ((rc = g.pin_tot.ensure(64))) return rc;
     volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
     int64_t* p_tot = (int64_t*)g.pin_tot.d;
     Utf8BytesFeats a;
@@ -1540,12 +1568,13 @@ static int features_utf8_bytes_route(Ctx& g, const Batch& b, bool dev, bool o32,
     a.st = st;
     if ((rc = enqueue_utf8_bytes_features(g, g.ws, a))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    if (h_tot[1] >> 32) { g.ws.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
+    int64_t n_items = 0;
+    // (mask 0: malformed input is refused before an int32 overflow, so the overflow flag is read behind that check)
+    if ((rc = finish_totals(g.ws, h_tot, 0, &n_items))) return rc;
     if (h_tot[3] != 0)
         return fail(LATOK_ERR_INVALID, "malformed UTF-8 (a continuation byte without a lead byte): no feature sums in byte space; "
                                        "latok_token_features_utf8_batch reads such input through the decoder");
-    if (h_tot[1] & 0xFFFFFFFFll) return fail(LATOK_ERR_INVALID, "a string is too long for LATOK_OUT_INT32; use the 64-bit form");
-    const int64_t n_items = h_tot[0];
+    if (h_tot[1] & 0xFFFFFFFFll) return refuse_too_long();
     *n_items_out = n_items;
     const bool fits = n_items <= items_cap && (n_items == 0 || items_out);
     if (!dev) {
@@ -1615,11 +1644,7 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
     const size_t elt = o32 ? 4 : 8;                                   // width of counts and of every record field
     const size_t item_bytes = (feats ? 4 : (spans ? 2 : 1)) * elt;
     if (feats && b.in.form == Form::Utf8 && !cp_units) {   // featurize in byte space: a route of its own
-        if (b.total == 0) {
-            if (dev) HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)n_str * elt, st));
-            else memset(counts_out, 0, (size_t)n_str * elt);
-            return LATOK_OK;
-        }
+        if (b.total == 0) return zero_counts(dev, counts_out, (size_t)n_str * elt, st);
         return features_utf8_bytes_route(g, b, dev, o32, counts_out, items_out, features_out, items_cap, n_items_out, st);
     }
     if (!dev && !cp_units && b.total >= kPipeMinChars)
@@ -1662,11 +1687,7 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
         }
     }
     const int64_t total = d.total;
-    if (total == 0) {   // only empty strings: all counts are 0
-        if (dev) HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)n_str * elt, st));
-        else memset(counts_out, 0, (size_t)n_str * elt);
-        return LATOK_OK;
-    }
+    if (total == 0) return zero_counts(dev, counts_out, (size_t)n_str * elt, st);   // only empty strings
     // small host batch: inputs and every output live in pinned mapped memory; nothing is copied by the runtime and the
     // call synchronises once (a string of ~100 chars: ~110 us of blocking copies otherwise)
     const bool small = !dev && (b.in.form == Form::Utf32 || b.in.narrow()) && total <= kSmallChars && n_str <= kSmallStrings;
@@ -1765,10 +1786,8 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
     // the one synchronisation: total and flag are in pinned memory now (a polled small batch has seen its completion
     // word, which the kernel stores after everything else; the launch itself retires on the stream a moment later)
     if ((rc = wait_done(g, done, st))) return rc;
-    const int64_t n_items = h_tot[0];
-    *n_items_out = n_items;
-    if (h_tot[1] >> 32) { g.ws.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
-    if (h_tot[1] & 0xFFFFFFFFll) return fail(LATOK_ERR_INVALID, "a string is too long for LATOK_OUT_INT32; use the 64-bit form");
+    int64_t n_items = *n_items_out = h_tot[0];   // (the total is reported whatever the flags say)
+    if ((rc = finish_totals(g.ws, h_tot, 0xFFFFFFFFll, &n_items))) return rc;
     const bool fits = n_items <= items_cap && (n_items == 0 || items_out);
     if (small) {
         memcpy(counts_out, (char*)g.pin.h + po_counts, (size_t)n_str * elt);
@@ -1982,15 +2001,9 @@ int latok_join_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_
     if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
     if (n_str > 0 && !out_off) return fail(LATOK_ERR_INVALID, "out_off is NULL");
     if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    if (n_str == 0 || total == 0) {   // no byte, no token: empty rows
-        if (dev) {
-            if (out_off) HIP_TRY(hipMemsetAsync(out_off, 0, (size_t)(n_str + 1) * 8, st));
-            if (counts_out && n_str > 0) HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)n_str * elt, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        } else {
-            if (out_off) memset(out_off, 0, (size_t)(n_str + 1) * 8);
-            if (counts_out && n_str > 0) memset(counts_out, 0, (size_t)n_str * elt);
-        }
+    if (n_str == 0 || total == 0) {   // no byte, no token: empty rows (device pointers: one wait, whatever was cleared)
+        if ((rc = zero_counts(dev, out_off, (size_t)(n_str + 1) * 8, st)) || (rc = zero_counts(dev, counts_out, (size_t)n_str * elt, st))) return rc;
+        if (dev) HIP_TRY(hipStreamSynchronize(st));
         return LATOK_OK;
     }
     if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
@@ -1998,7 +2011,7 @@ int latok_join_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_
     g.last_route = 5;
     Batch d;
     if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
-    if ((rc = ws_ensure(ws_needs(g.ws, total, true, false, false, 0, true).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+    if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true, .join = true}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
     volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
     int64_t* p_tot = (int64_t*)g.pin_tot.d;
     JoinTokens a;
@@ -2027,9 +2040,8 @@ int latok_join_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_
         if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
-    if (h_tot[1] >> 32) { g.ws.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
-    if (h_tot[1] & 1) return fail(LATOK_ERR_INVALID, "a string is too long for LATOK_OUT_INT32; use the 64-bit form");
-    const int64_t n = h_tot[0];
+    int64_t n = 0;
+    if ((rc = finish_totals(g.ws, h_tot, 1, &n))) return rc;
     *n_out_bytes = n;
     if (n > out_cap) return fail(LATOK_ERR_INVALID, "output capacity too small: need %lld bytes", (long long)n);
     if (!dev && n > 0) {
@@ -2059,24 +2071,14 @@ int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
     hipStream_t st = turn.st;
     if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
     if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    if (n_str == 0 || total == 0) {   // no byte, no token
-        if (counts_out && n_str > 0) {
-            if (dev) {
-                HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)n_str * elt, st));
-                HIP_TRY(hipStreamSynchronize(st));
-            } else {
-                memset(counts_out, 0, (size_t)n_str * elt);
-            }
-        }
-        return LATOK_OK;
-    }
+    if (n_str == 0 || total == 0) return zero_counts(dev, counts_out, (size_t)n_str * elt, st, true);   // no byte, no token
     if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
     if (dev && (((uintptr_t)spans_out & (2 * elt - 1)) != 0 || ((uintptr_t)counts_out & (elt - 1)) != 0 || ((uintptr_t)hashes_out & 3) != 0))
         return fail(LATOK_ERR_INVALID, "misaligned output buffer");
     g.last_route = 6;
     Batch d;
     if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
-    if ((rc = ws_ensure(ws_needs(g.ws, total, true, false, false).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+    if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
     volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
     int64_t* p_tot = (int64_t*)g.pin_tot.d;
     TokenHashes a;
@@ -2101,9 +2103,8 @@ int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
     if ((rc = enqueue_token_hashes(g, g.ws, a))) return rc;
     if (!dev && counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));   // valid whatever the capacity
     HIP_TRY(hipStreamSynchronize(st));   // the call's one wait for the kernels
-    if (h_tot[1] >> 32) { g.ws.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
-    if (h_tot[1] & 1) return fail(LATOK_ERR_INVALID, "a string is too long for LATOK_OUT_INT32; use the 64-bit form");
-    const int64_t n = h_tot[0];
+    int64_t n = 0;
+    if ((rc = finish_totals(g.ws, h_tot, 1, &n))) return rc;
     *n_tokens_out = n;
     if (n > cap) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld tokens", (long long)n);
     if (!dev && n > 0 && hashes_out) {   // (host pointers: the copies, whose size is known only now)
@@ -2657,31 +2658,68 @@ static int flow_pick(Ctx& g, const latok::FlowRange* r, int n, int* slot_out) {
     *slot_out = s;
     return LATOK_OK;
 }
-// The prologue of a flow batch (b: device pointers, n_str > 0, total > 0, checked by the caller).  r[0 .. n_out) = what the
-// batch writes; its inputs are added here.  The slot is picked, the first n_needs buffers of its workspace are reserved, and
-// the ranges are noted BEFORE anything is enqueued: a launch that fails midway cannot leave work on the caller's buffers that
-// the routing does not know of (over-noting only costs overlap).
-static int flow_begin(Ctx& g, const Batch& b, latok::FlowRange* r, int n_out, int n_needs, bool spans, bool feats, int* slot_out) {
-    r[n_out] = latok::flow_range(b.in.p, (size_t)b.total * b.in.width(), false);
-    r[n_out + 1] = latok::flow_range(b.row, (size_t)(b.n_str + 1) * 8, false);
-    const int n = n_out + 2;
+// The prologue of a flow batch, the same for every submitter: what it touches, what is cleared for it, what its slot must hold.
+struct FlowZero {
+    void* p;
+    size_t bytes;
+};
+struct FlowOpen {
+    const latok::FlowRange* r = nullptr;   // every range of caller memory the batch touches, outputs first (the *_flow_ranges)
+    int n_r = 0;
+    bool empty = false;                    // no string or no unit: nothing is launched
+    FlowZero result = {};                  // result words cleared on the slot's stream before the batch: 32 bytes (code-point UTF-8),
+                                           // 16 (join, hashes), none (there are none, or the enqueue core clears its own)
+    FlowZero zero[2] = {};                 // an empty batch: the buffers it zeroes (NULL / 0 entries are skipped)
+    int64_t units = 0;                     // a batch that launches: the slot's workspace is sized by ws_needs(units, shape),
+    WsShape shape;                         // of which the first n_needs entries are reserved (kTileNeeds: the mask alone)
+    int n_needs = kWsNeeds;
+};
+// Picks the slot, reserves its workspace and notes the ranges before anything is enqueued: a launch that fails midway cannot
+// leave work on the caller's buffers that the routing does not know of (over-noting only costs overlap).  Then the clears, on
+// the slot's stream.  Only a batch that launches counts in flow_seq, by which the slots take turns.
+static int flow_open(Ctx& g, const FlowOpen& o, int* slot_out) {
     int rc, s = 0;
-    if ((rc = flow_pick(g, r, n, &s))) return rc;
-    if ((rc = flow_reserve(g, ws_needs(g.flow[s].ws, b.total, spans, feats, feats && b.in.narrow()).data(), n_needs))) return rc;
-    g.flow_held.note(s, r, n);
-    ++g.flow_seq;
+    if ((rc = flow_setup(g)) || (rc = flow_pick(g, o.r, o.n_r, &s))) return rc;
+    Ctx::FlowSlot& f = g.flow[s];
+    if (!o.empty && (rc = flow_reserve(g, ws_needs(f.ws, o.units, o.shape).data(), o.n_needs))) return rc;
+    g.flow_held.note(s, o.r, o.n_r);
+    if (!o.empty) ++g.flow_seq;
+    if (o.result.bytes) HIP_TRY(hipMemsetAsync(o.result.p, 0, o.result.bytes, f.st));
+    if (o.empty)
+        for (const FlowZero& z : o.zero)
+            if (z.p && z.bytes) HIP_TRY(hipMemsetAsync(z.p, 0, z.bytes, f.st));
     *slot_out = s;
     return LATOK_OK;
 }
+constexpr int kMaskFlowRanges = 3, kCompactFlowRanges = 6;
+// every range of caller memory a mask batch (b: n_str > 0, total > 0) touches, outputs first; returns their number
+static int mask_flow_ranges(const Batch& b, uint64_t* mask, latok::FlowRange* r) {
+    r[0] = latok::flow_range(mask, (size_t)((b.total + 63) / 64) * 8, true);
+    r[1] = latok::flow_range(b.in.p, (size_t)b.total * b.in.width(), false);
+    r[2] = latok::flow_range(b.row, (size_t)(b.n_str + 1) * 8, false);
+    return kMaskFlowRanges;
+}
+// ... and a compaction batch: records, counts, result words, feature sums, then its inputs.  An empty batch (cap unchecked) touches
+// its result words and counts alone.
+static int compact_flow_ranges(bool spans, bool feats, const Batch& b, bool empty, void* counts, void* items, int8_t* feat, int64_t cap,
+                               int64_t* result, size_t rec, latok::FlowRange* r) {
+    const size_t n_str = (size_t)std::max<int64_t>(b.n_str, 0), n_items = empty ? 0 : (size_t)cap, fields = feats ? 4 : (spans ? 2 : 1);
+    r[0] = latok::flow_range(items, n_items * fields * rec, true);
+    r[1] = latok::flow_range(counts, n_str * rec, true);
+    r[2] = latok::flow_range(result, 16, true);
+    r[3] = latok::flow_range(feat, feats ? n_items * LATOK_FEATURE_COUNT : 0, true);
+    r[4] = latok::flow_range(b.in.p, empty ? 0 : (size_t)b.total * b.in.width(), false);
+    r[5] = latok::flow_range(b.row, empty ? 0 : (n_str + 1) * 8, false);
+    return kCompactFlowRanges;
+}
 static int flow_submit(Ctx& g, const Batch& b, uint64_t* mask, int* slot_used = nullptr) {
-    int rc = flow_setup(g);
-    if (rc) return rc;
-    if (b.n_str <= 0 || b.total <= 0) return LATOK_OK;
+    if (b.n_str <= 0 || b.total <= 0) return LATOK_OK;   // an empty mask batch touches nothing
     if (!b.in.p || !b.row || !mask) return fail(LATOK_ERR_INVALID, "NULL buffer");
     if (((uintptr_t)b.in.p & 15) != 0) return fail(LATOK_ERR_INVALID, "device input pointer must be 16-byte aligned");
-    latok::FlowRange touched[3] = {latok::flow_range(mask, (size_t)((b.total + 63) / 64) * 8, true)};
-    int slot = 0;
-    if ((rc = flow_begin(g, b, touched, 1, kTileNeeds, false, false, &slot))) return rc;
+    latok::FlowRange r[kMaskFlowRanges];
+    const FlowOpen o{.r = r, .n_r = mask_flow_ranges(b, mask, r), .units = b.total, .n_needs = kTileNeeds};
+    int rc, slot = 0;
+    if ((rc = flow_open(g, o, &slot))) return rc;
     if (slot_used) *slot_used = slot;
     Ctx::FlowSlot& f = g.flow[slot];
     Pipe a;
@@ -2694,36 +2732,26 @@ static int flow_submit(Ctx& g, const Batch& b, uint64_t* mask, int* slot_used = 
 // launch, on the slot's stream and workspace; the item total and the error flags land in result[0..1] when the stream gets there
 static int flow_submit_compact(Ctx& g, bool spans, bool feats, const Batch& b, void* counts, void* items, int8_t* feat, int64_t cap,
                                int64_t* result, int flags) {
-    int rc = flow_setup(g);
-    if (rc) return rc;
     if (!result) return fail(LATOK_ERR_INVALID, "NULL result pointer");
     if (((uintptr_t)result & 7) != 0) return fail(LATOK_ERR_INVALID, "result pointer must be 8-byte aligned");
     const int64_t n_str = b.n_str;
-    const size_t rec = (flags & LATOK_OUT_INT32) ? 4 : 8;   // bytes of a count / of one field of a record
-    if (n_str <= 0 || b.total <= 0) {   // nothing to launch: counts of empty strings are zero, no items
-        const latok::FlowRange w[2] = {latok::flow_range(result, 16, true), latok::flow_range(counts, n_str > 0 ? (size_t)n_str * rec : 0, true)};
-        int s0 = 0;
-        if ((rc = flow_pick(g, w, 2, &s0))) return rc;
-        HIP_TRY(hipMemsetAsync(result, 0, 16, g.flow[s0].st));
-        if (n_str > 0 && counts) HIP_TRY(hipMemsetAsync(counts, 0, (size_t)n_str * rec, g.flow[s0].st));
-        g.flow_held.note(s0, w, 2);
-        return LATOK_OK;
+    const bool o32 = (flags & LATOK_OUT_INT32) != 0, empty = n_str <= 0 || b.total <= 0;
+    const size_t rec = o32 ? 4 : 8;   // bytes of a count / of one field of a record
+    if (!empty) {
+        if (!b.in.p || !b.row || !counts || ((!items || (feats && !feat)) && cap > 0)) return fail(LATOK_ERR_INVALID, "NULL buffer");
+        if (cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
+        if (feats && b.in.form == Form::Utf8)
+            return fail(LATOK_ERR_INVALID, "featurize of UTF-8 bytes has calls of its own (latok_flow_token_features_utf8 / _utf8_bytes)");
+        if (((uintptr_t)b.in.p & 15) != 0) return fail(LATOK_ERR_INVALID, "device input pointer must be 16-byte aligned");
+        if (((uintptr_t)items & 15) != 0 || ((uintptr_t)counts & (rec - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
     }
-    if (!b.in.p || !b.row || !counts || ((!items || (feats && !feat)) && cap > 0)) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    if (cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
-    if (feats && b.in.form == Form::Utf8)
-        return fail(LATOK_ERR_INVALID, "featurize of UTF-8 bytes has calls of its own (latok_flow_token_features_utf8 / _utf8_bytes)");
-    if (((uintptr_t)b.in.p & 15) != 0) return fail(LATOK_ERR_INVALID, "device input pointer must be 16-byte aligned");
-    const bool o32 = (flags & LATOK_OUT_INT32) != 0;
-    if (((uintptr_t)items & 15) != 0 || ((uintptr_t)counts & (o32 ? 3 : 7)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    // every output of the batch -- records, counts, result words, feature sums -- and (flow_begin) its inputs
-    const size_t fields = feats ? 4 : (spans ? 2 : 1);
-    latok::FlowRange touched[6] = {latok::flow_range(items, (size_t)cap * fields * rec, true),
-                                   latok::flow_range(counts, (size_t)n_str * rec, true),
-                                   latok::flow_range(result, 16, true),
-                                   latok::flow_range(feat, feats ? (size_t)cap * LATOK_FEATURE_COUNT : 0, true)};
-    int slot = 0;
-    if ((rc = flow_begin(g, b, touched, 4, kWsNeeds, spans, feats, &slot))) return rc;
+    latok::FlowRange r[kCompactFlowRanges];
+    // an empty batch: counts of empty strings are zero, no items; one that launches: enqueue_compaction_dev clears its result words
+    const FlowOpen o{.r = r, .n_r = compact_flow_ranges(spans, feats, b, empty, counts, items, feat, cap, result, rec, r), .empty = empty,
+                     .zero = {{result, 16}, {counts, n_str > 0 ? (size_t)n_str * rec : 0}}, .units = b.total,
+                     .shape = {.spans = spans, .feats = feats, .widen = feats && b.in.narrow()}};
+    int rc, slot = 0;
+    if ((rc = flow_open(g, o, &slot)) || empty) return rc;
     Ctx::FlowSlot& f = g.flow[slot];
     Compaction k;
     k.b = b;
@@ -2824,6 +2852,16 @@ struct Utf8Flow {
     bool o32 = false;
 };
 constexpr int kU8FlowRanges = 8;
+// the debug hooks' view of a batch's ranges, in the form latok_debug_flow_route takes them; returns n, < 0 if n_max is too small
+static int export_flow_ranges(const latok::FlowRange* r, int n, uint64_t* lo, uint64_t* bytes, int* is_write, int n_max) {
+    if (n > n_max) return fail(LATOK_ERR_INVALID, "need room for %d ranges", n);
+    for (int i = 0; i < n; ++i) {
+        lo[i] = (uint64_t)r[i].lo;
+        bytes[i] = (uint64_t)(r[i].hi - r[i].lo);
+        is_write[i] = r[i].write ? 1 : 0;
+    }
+    return n;
+}
 // every range of caller memory the batch touches, outputs first (what flow_hazards.h orders it by); returns their number
 static int utf8_flow_ranges(const Utf8Flow& a, latok::FlowRange* r) {
     const size_t rec = a.o32 ? 4 : 8, fields = a.what >= kU8Feats ? 4 : (a.what == kU8Spans ? 2 : 1);
@@ -2873,19 +2911,10 @@ extern "C" int latok_debug_flow_utf8_ranges(int what, const uint64_t* addr, int6
     a.result = (int64_t*)(uintptr_t)addr[5];
     a.o32 = (flags & LATOK_OUT_INT32) != 0;
     latok::FlowRange r[kU8FlowRanges];
-    const int n = utf8_flow_ranges(a, r);
-    if (n > n_max) return fail(LATOK_ERR_INVALID, "need room for %d ranges", n);
-    for (int i = 0; i < n; ++i) {
-        lo[i] = (uint64_t)r[i].lo;
-        bytes[i] = (uint64_t)(r[i].hi - r[i].lo);
-        is_write[i] = r[i].write ? 1 : 0;
-    }
-    return n;
+    return export_flow_ranges(r, utf8_flow_ranges(a, r), lo, bytes, is_write, n_max);
 }
 
 static int flow_submit_utf8(Ctx& g, const Utf8Flow& a) {
-    int rc = flow_setup(g);
-    if (rc) return rc;
     if (!a.result) return fail(LATOK_ERR_INVALID, "NULL result pointer");
     if (((uintptr_t)a.result & 7) != 0) return fail(LATOK_ERR_INVALID, "result pointer must be 8-byte aligned");
     if (a.n_str < 0) return fail(LATOK_ERR_INVALID, "n_str must be >= 0");
@@ -2893,36 +2922,30 @@ static int flow_submit_utf8(Ctx& g, const Utf8Flow& a) {
     const bool mask = a.what == kU8Mask, spans = a.what >= kU8Spans, feats = a.what >= kU8Feats;
     const int64_t n_str = a.n_str, total_bytes = a.total_bytes;
     const size_t rec = a.o32 ? 4 : 8;
-    latok::FlowRange r[kU8FlowRanges];
-    const int n_r = utf8_flow_ranges(a, r);
-    int slot = 0;
-    if (n_str == 0 || total_bytes <= 0) {   // nothing to launch: no item, no char; counts and row offsets of empty strings are zero
+    const bool empty = n_str == 0 || total_bytes <= 0;   // no item, no char; counts and row offsets of empty strings are zero
+    if (empty) {
         if (n_str > 0 && (mask ? !a.cp_row : !a.counts)) return fail(LATOK_ERR_INVALID, "NULL buffer");
-        if ((rc = flow_pick(g, r, n_r, &slot))) return rc;
-        g.flow_held.note(slot, r, n_r);
-        HIP_TRY(hipMemsetAsync(a.result, 0, 32, g.flow[slot].st));
-        if (n_str > 0 && mask) HIP_TRY(hipMemsetAsync(a.cp_row, 0, (size_t)(n_str + 1) * 8, g.flow[slot].st));
-        if (n_str > 0 && !mask) HIP_TRY(hipMemsetAsync(a.counts, 0, (size_t)n_str * rec, g.flow[slot].st));
-        return LATOK_OK;
-    }
-    if (!a.u8 || !a.boff) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    if (((uintptr_t)a.u8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
-    const int64_t words_b = (total_bytes + 63) / 64, c_tiles = (words_b + 63) / 64;
-    if (mask) {
-        if (!a.cp_row || (!a.mask && a.mask_cap > 0)) return fail(LATOK_ERR_INVALID, "NULL buffer");
-        if (((uintptr_t)a.mask & 7) != 0 || ((uintptr_t)a.cp_row & 7) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
     } else {
-        if (!a.counts || ((!a.items || (feats && !a.feat)) && a.cap > 0)) return fail(LATOK_ERR_INVALID, "NULL buffer");
-        if (((uintptr_t)a.items & 15) != 0 || ((uintptr_t)a.counts & (rec - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+        if (!a.u8 || !a.boff) return fail(LATOK_ERR_INVALID, "NULL buffer");
+        if (((uintptr_t)a.u8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+        if (mask) {
+            if (!a.cp_row || (!a.mask && a.mask_cap > 0)) return fail(LATOK_ERR_INVALID, "NULL buffer");
+            if (((uintptr_t)a.mask & 7) != 0 || ((uintptr_t)a.cp_row & 7) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+        } else {
+            if (!a.counts || ((!a.items || (feats && !a.feat)) && a.cap > 0)) return fail(LATOK_ERR_INVALID, "NULL buffer");
+            if (((uintptr_t)a.items & 15) != 0 || ((uintptr_t)a.counts & (rec - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+        }
     }
-    if ((rc = flow_pick(g, r, n_r, &slot))) return rc;
+    latok::FlowRange r[kU8FlowRanges];
+    const FlowZero rows = mask ? FlowZero{a.cp_row, (size_t)(n_str + 1) * 8} : FlowZero{a.counts, (size_t)n_str * rec};
+    const FlowOpen o{.r = r, .n_r = utf8_flow_ranges(a, r), .empty = empty, .result = {a.result, 32},
+                     .zero = {n_str > 0 ? rows : FlowZero{}}, .units = total_bytes, .shape = {.spans = spans, .feats = feats, .cp_rows = n_str + 1}};
+    int rc, slot = 0;
+    if ((rc = flow_open(g, o, &slot)) || empty) return rc;
     Ctx::FlowSlot& f = g.flow[slot];
     Workspace& w = f.ws;
-    if ((rc = flow_reserve(g, ws_needs(w, total_bytes, spans, feats, false, n_str + 1).data(), kWsNeeds))) return rc;
-    g.flow_held.note(slot, r, n_r);   // before anything is enqueued (flow_begin)
-    ++g.flow_seq;
     const hipStream_t st = f.st;
-    HIP_TRY(hipMemsetAsync(a.result, 0, 32, st));
+    const int64_t words_b = (total_bytes + 63) / 64, c_tiles = (words_b + 63) / 64;
     if (a.what == kU8BytesFeats) {   // records in byte positions: the sequence the blocking call enqueues, on the slot
         Utf8BytesFeats k;
         k.b = Batch{Input{a.u8, Form::Utf8}, a.boff, n_str, total_bytes};
@@ -3056,13 +3079,7 @@ extern "C" int latok_debug_flow_join_ranges(const uint64_t* addr, int64_t n_str,
     const int n = join_flow_ranges((const uint8_t*)(uintptr_t)addr[0], (const int64_t*)(uintptr_t)addr[1], n_str, total_bytes,
                                    (uint8_t*)(uintptr_t)addr[2], cap, (int64_t*)(uintptr_t)addr[3], (void*)(uintptr_t)addr[4],
                                    (int64_t*)(uintptr_t)addr[5], (flags & LATOK_OUT_INT32) != 0, r);
-    if (n > n_max) return fail(LATOK_ERR_INVALID, "need room for %d ranges", n);
-    for (int i = 0; i < n; ++i) {
-        lo[i] = (uint64_t)r[i].lo;
-        bytes[i] = (uint64_t)(r[i].hi - r[i].lo);
-        is_write[i] = r[i].write ? 1 : 0;
-    }
-    return n;
+    return export_flow_ranges(r, n, lo, bytes, is_write, n_max);
 }
 
 int latok_flow_join_tokens_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes, int sep,
@@ -3083,26 +3100,19 @@ int latok_flow_join_tokens_utf8_bytes(const uint8_t* utf8_dev, const int64_t* by
     const size_t rec = o32 ? 4 : 8;
     if (((uintptr_t)out_off_dev & 7) != 0 || ((uintptr_t)counts_dev & (rec - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
     if (total_bytes < 0 && (rc = resolve_total_device(byte_off_dev, n_str, &total_bytes, g.stream))) return rc;
-    if ((rc = flow_setup(g))) return rc;
+    const bool empty = n_str == 0 || total_bytes <= 0;   // empty rows
+    if (!empty) {
+        if (!utf8_dev || !byte_off_dev) return fail(LATOK_ERR_INVALID, "NULL buffer");
+        if (((uintptr_t)utf8_dev & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    }
     latok::FlowRange r[kJoinFlowRanges];
     const int n_r = join_flow_ranges(utf8_dev, byte_off_dev, n_str, total_bytes, out_bytes_dev, out_cap, out_off_dev, counts_dev, result_dev, o32, r);
+    const FlowOpen o{.r = r, .n_r = n_r, .empty = empty, .result = {result_dev, 16},
+                     .zero = {{out_off_dev, (size_t)(n_str + 1) * 8}, {counts_dev, (size_t)n_str * rec}}, .units = total_bytes,
+                     .shape = {.spans = true, .join = true}};
     int slot = 0;
-    if (n_str == 0 || total_bytes <= 0) {   // nothing to launch: empty rows
-        if ((rc = flow_pick(g, r, n_r, &slot))) return rc;
-        g.flow_held.note(slot, r, n_r);
-        HIP_TRY(hipMemsetAsync(result_dev, 0, 16, g.flow[slot].st));
-        HIP_TRY(hipMemsetAsync(out_off_dev, 0, (size_t)(n_str + 1) * 8, g.flow[slot].st));
-        if (counts_dev && n_str > 0) HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)n_str * rec, g.flow[slot].st));
-        return LATOK_OK;
-    }
-    if (!utf8_dev || !byte_off_dev) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    if (((uintptr_t)utf8_dev & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
-    if ((rc = flow_pick(g, r, n_r, &slot))) return rc;
+    if ((rc = flow_open(g, o, &slot)) || empty) return rc;
     Ctx::FlowSlot& f = g.flow[slot];
-    if ((rc = flow_reserve(g, ws_needs(f.ws, total_bytes, true, false, false, 0, true).data(), kWsNeeds))) return rc;
-    g.flow_held.note(slot, r, n_r);   // before anything is enqueued (flow_begin)
-    ++g.flow_seq;
-    HIP_TRY(hipMemsetAsync(result_dev, 0, 16, f.st));
     JoinTokens a;
     a.b = Batch{Input{utf8_dev, Form::Utf8}, byte_off_dev, n_str, total_bytes};
     a.sep = sep;
@@ -3146,13 +3156,7 @@ extern "C" int latok_debug_flow_hashes_ranges(const uint64_t* addr, int64_t n_st
     const int n = hash_flow_ranges((const uint8_t*)(uintptr_t)addr[0], (const int64_t*)(uintptr_t)addr[1], n_str, total_bytes,
                                    (void*)(uintptr_t)addr[2], (void*)(uintptr_t)addr[3], (uint32_t*)(uintptr_t)addr[4], cap,
                                    (int64_t*)(uintptr_t)addr[5], (flags & LATOK_OUT_INT32) != 0, r);
-    if (n > n_max) return fail(LATOK_ERR_INVALID, "need room for %d ranges", n);
-    for (int i = 0; i < n; ++i) {
-        lo[i] = (uint64_t)r[i].lo;
-        bytes[i] = (uint64_t)(r[i].hi - r[i].lo);
-        is_write[i] = r[i].write ? 1 : 0;
-    }
-    return n;
+    return export_flow_ranges(r, n, lo, bytes, is_write, n_max);
 }
 
 int latok_flow_token_hashes_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes, uint32_t seed,
@@ -3171,25 +3175,18 @@ int latok_flow_token_hashes_utf8_bytes(const uint8_t* utf8_dev, const int64_t* b
     if (((uintptr_t)spans_dev & (2 * rec - 1)) != 0 || ((uintptr_t)counts_dev & (rec - 1)) != 0 || ((uintptr_t)hashes_dev & 3) != 0)
         return fail(LATOK_ERR_INVALID, "misaligned output buffer");
     if (total_bytes < 0 && (rc = resolve_total_device(byte_off_dev, n_str, &total_bytes, g.stream))) return rc;
-    if ((rc = flow_setup(g))) return rc;
+    const bool empty = n_str == 0 || total_bytes <= 0;   // no token
+    if (!empty) {
+        if (!utf8_dev || !byte_off_dev) return fail(LATOK_ERR_INVALID, "NULL buffer");
+        if (((uintptr_t)utf8_dev & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    }
     latok::FlowRange r[kHashFlowRanges];
     const int n_r = hash_flow_ranges(utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, spans_dev, hashes_dev, cap, result_dev, o32, r);
+    const FlowOpen o{.r = r, .n_r = n_r, .empty = empty, .result = {result_dev, 16}, .zero = {{counts_dev, (size_t)n_str * rec}},
+                     .units = total_bytes, .shape = {.spans = true}};
     int slot = 0;
-    if (n_str == 0 || total_bytes <= 0) {   // nothing to launch: no token
-        if ((rc = flow_pick(g, r, n_r, &slot))) return rc;
-        g.flow_held.note(slot, r, n_r);
-        HIP_TRY(hipMemsetAsync(result_dev, 0, 16, g.flow[slot].st));
-        if (counts_dev && n_str > 0) HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)n_str * rec, g.flow[slot].st));
-        return LATOK_OK;
-    }
-    if (!utf8_dev || !byte_off_dev) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    if (((uintptr_t)utf8_dev & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
-    if ((rc = flow_pick(g, r, n_r, &slot))) return rc;
+    if ((rc = flow_open(g, o, &slot)) || empty) return rc;
     Ctx::FlowSlot& f = g.flow[slot];
-    if ((rc = flow_reserve(g, ws_needs(f.ws, total_bytes, true, false, false).data(), kWsNeeds))) return rc;
-    g.flow_held.note(slot, r, n_r);   // before anything is enqueued (flow_begin)
-    ++g.flow_seq;
-    HIP_TRY(hipMemsetAsync(result_dev, 0, 16, f.st));
     TokenHashes a;
     a.b = Batch{Input{utf8_dev, Form::Utf8}, byte_off_dev, n_str, total_bytes};
     a.seed = seed;
