@@ -3,7 +3,7 @@
 //       _gen_parse_matrix      reference latok/core/src/latok/latok.c:31-138
 //       _combine_matrix_rows   reference latok/core/src/latok/latok.c:275-370
 //   * device-wide exclusive scan (used by the compaction passes and the UTF-8 decoder)
-//   * the staged UTF-8 decoder (code-point units; the byte-space ingest lives in split_kernels.hip)
+//   * the staged UTF-8 decoder (code-point units; the byte-space ingest lives in tile_core.h)
 //   * synthetic corpus fill, UTF-8 size reduction and the streaming-read ceiling kernel for the benchmark
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +11,7 @@
 #include "corpus_gen.h"
 #include "kernels.h"
 #include "utf8_decode.h"
+#include "wave_ops.h"
 
 namespace latok {
 
@@ -162,7 +163,7 @@ constexpr int kScanChunk = kScanBlock * kScanItems; // elements per block
 
 __device__ __forceinline__ long long block_exclusive_scan_ll(long long v, long long* total, long long* lds /*[16]*/) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long inc = v;
+    long long inc = v;   // (written out: shfl_scan_add here reorders the kernels' instructions)
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const long long o = __shfl_up(inc, d);
@@ -315,12 +316,7 @@ __device__ __forceinline__ uint32_t utf8_lead_mask16(uint4 v) {
 
 __device__ __forceinline__ int block_exclusive_scan_int(int v, int* total, int* lds /*[kU8Threads/64]*/) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
+    const int inc = shfl_scan_add(v, lane);
     __syncthreads();
     if (lane == 63) lds[wave] = inc;
     __syncthreads();
@@ -403,7 +399,7 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_decode_chunks(const uint8_t
         } else {
             // A mixed chunk.  ASCII lead bytes are their own code points; only the NON-ASCII leads are decoded -- two
             // branch-free slots per dword (well-formed UTF-8 has at most two multi-byte leads in 4 bytes; more: the loop
-            // below), as in the byte-space tile kernel (split_kernels.hip: bytes_phase1).  A lead's place in the output is
+            // below), as in the byte-space tile kernel (tile_core.h: bytes_phase1).  A lead's place in the output is
             // its rank among the chunk's leads.  (The old form decoded all 16 positions with the branchy utf8_decode_at:
             // 554 us for the 471 MB of C3.)
             // bytes p+16 .. p+18: the next thread's first dword; the last lane of a wave reads them from memory

@@ -25,6 +25,7 @@
 #include "kernels.h"
 #include "lane_math.h"
 #include "token_hash.h"
+#include "wave_ops.h"
 
 namespace latok {
 
@@ -53,27 +54,16 @@ __device__ __forceinline__ void word_counts_tile(const uint64_t* __restrict__ bi
             x1 = has ? bits[w + 1] : 0ull;
             nn1 = has ? (~space[w + 1] & valid_mask(w + 1, total)) : 0ull;
         }
-        // Which boundaries start a token with a non-SPACE char, for all boundaries of the word at once: on the bit-reversed
-        // word a boundary is the TOP of its token, so "some non-SPACE below me in my token" is a carry chain -- one add.
-        //   generate = non-SPACE chars that are not boundaries, propagate = non-boundaries, carry-in = the token that
-        //   continues into the next word(s) has a non-SPACE char there
+        // which boundaries start a token with a non-SPACE char (kept_boundaries, wave_ops.h); carry-in = the token that
+        // continues into the next word(s) has a non-SPACE char there
         bool cin;
         if (x1) cin = (nn1 & ((x1 & (~x1 + 1ull)) - 1ull)) != 0;
         else cin = nn1 != 0 || (x != 0 && w + 1 < n_words && tail_has_nonspace(bits, space, w + 1, n_words, total));
-        const uint64_t xr = __builtin_bitreverse64(x), nr = __builtin_bitreverse64(nn);
-        const uint64_t g = nr & ~xr, pr = ~xr;
-        const uint64_t a = pr | g;
-        const uint64_t carries = (a + g + (cin ? 1ull : 0ull)) ^ a ^ g;      // carry INTO every position
-        const uint64_t kept = __builtin_bitreverse64(xr & (nr | carries));
+        const uint64_t kept = kept_boundaries(x, nn, cin);
         if (w < n_words) kept_out[w] = kept;
         cnt = __popcll(kept);
     }
-    int inc = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
+    const int inc = shfl_scan_add(cnt, lane);
     if (w < n_words) word_pref[w] = (uint16_t)(inc - cnt);
     if (lane == 63) tile_cnt[t] = inc;
 }
@@ -139,12 +129,7 @@ __global__ __launch_bounds__(kChainBlock) void k_scan_chained(const int64_t* __r
         v[j] = base + j < n ? in[base + j] : 0;
         sum += v[j];
     }
-    long long inc = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
+    const long long inc = shfl_scan_add(sum, lane);
     if (lane == 63) s_wave_tot[wave] = inc;
     __syncthreads();
     long long wave_excl = 0, agg = 0;
@@ -256,27 +241,6 @@ struct HashArgs {
     uint32_t seed = 0;
 };
 
-__device__ __forceinline__ int64_t scatter_lower_bound(const int64_t* __restrict__ row_off, int64_t n_entries, int64_t c,
-                                                       int lane) {
-    int64_t lo = 0, hi = n_entries;   // smallest s with row_off[s] >= c, 64 probes per round
-    while (hi > lo) {
-        const int64_t len = hi - lo;
-        const int64_t step = (len + 63) / 64;
-        const int64_t p = lo + (int64_t)lane * step;
-        const bool pred = p < hi && row_off[p] >= c;
-        const unsigned long long m = __ballot(pred);
-        if (!m) {
-            const int64_t n_valid = (len + step - 1) / step;
-            lo = min(lo + (n_valid - 1) * step + 1, hi);
-        } else {
-            const int f = __builtin_ctzll(m);
-            hi = lo + (int64_t)f * step;
-            if (f > 0) lo = lo + (int64_t)(f - 1) * step + 1;
-        }
-    }
-    return lo;
-}
-
 template <int KIND, typename OUT>
 __device__ __forceinline__ void counts_scatter_block(
     const uint64_t* __restrict__ bits, const uint64_t* __restrict__ space, const uint64_t* __restrict__ item_mask,
@@ -324,8 +288,8 @@ __device__ __forceinline__ void counts_scatter_block(
     //     every string change stalled the whole wave on every step of its item loop.
     const int64_t t0 = w0 << 6;
     // first string starting at or after t0: published by the tile kernel (one wave = one tile), else searched
-    int64_t idx0 = tile_first ? tile_first[w0 >> 6] : scatter_lower_bound(row_off, n_str, t0, lane);
-    idx0 = idx0 < 0 ? 0 : (idx0 > n_str ? n_str : idx0);
+    int64_t idx0 = tile_first ? tile_first[w0 >> 6] : wave_lower_bound(row_off, n_str, t0, lane);
+    idx0 = idx0 < 0 ? 0 : idx0;
     if (idx0 > n_str) idx0 = n_str;
     const int64_t start_before = idx0 > 0 ? row_off[idx0 - 1] : 0;
     unsigned long long* bw = reinterpret_cast<unsigned long long*>(smax);
@@ -342,14 +306,7 @@ __device__ __forceinline__ void counts_scatter_block(
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const uint64_t Bw = bw[lane];
-    int carry = Bw ? 64 * lane + 63 - __builtin_clzll(Bw) : -1;     // tile-relative position of my word's last string start
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(carry, d);
-        if (lane >= d && o > carry) carry = o;
-    }
-    carry = __shfl_up(carry, 1);
-    if (lane == 0) carry = -1;
+    const int carry = last_start_before(Bw, lane);
     const int64_t lo_in = carry >= 0 ? t0 + carry : start_before;
 
     // (b) + (c), window by window
@@ -706,7 +663,7 @@ __global__ __launch_bounds__(kCompressWaves * 64) void k_lead_compress(
                 mb = 0ull; xb = 0ull; xb2 = 0ull;
             }
             const int cnt = __popcll(mb);
-            int inc = cnt;
+            int inc = cnt;   // (written out: shfl_scan_add here reorders the kernel's instructions)
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
                 const int o = __shfl_up(inc, d);
@@ -1045,12 +1002,7 @@ __global__ __launch_bounds__(kJoinWaves * 64) void k_join_counts(
         head_out[w] = o.head;
     }
     const int cnt = __popcll(o.body) + __popcll(o.head);
-    int inc = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(inc, d);
-        if (lane >= d) inc += v;
-    }
+    const int inc = shfl_scan_add(cnt, lane);
     if (in) word_pref[w] = (uint16_t)(inc - cnt);
     if (lane == 63) tile_cnt[t] = inc;
 }

@@ -144,7 +144,7 @@ __device__ __forceinline__ int64_t device_total(const int64_t* p, int64_t bound)
 }
 #endif
 
-// featurize on the tile grid (split_kernels.hip: k_features_tiles)
+// featurize on the tile grid (feature_kernels.hip: k_features_tiles)
 struct FeatParams {
     const uint8_t* codes;         // rule code of every char (SplitParams::codes_out of the tile kernel), padded by one tile + 256 B
     const int64_t* row_off;
@@ -174,7 +174,7 @@ constexpr int64_t kOneSegTiles = 24;
 constexpr int64_t kFastTailTiles = 256;   // k_tiles_main<.., FAST_TAIL>: batches of at most ~1 M chars (beyond, one tile's latency is noise)
 constexpr int kNarrowWPB = 16;            // Latin-1 / UCS-2 tile kernels: 4 waves per SIMD (<= 128 VGPRs)
 constexpr int kCpsPrefetchRows = 2;       // rows (1 KiB) of the wave's next UTF-32 tile requested before phase 2 of the current one
-constexpr int kCpsPrefetchRowsFlow = 6;   // the same in a batch of a flow (split_kernels.hip)
+constexpr int kCpsPrefetchRowsFlow = 6;   // the same in a batch of a flow (tile_core.h)
 // What the tile pipeline launches for a batch: the segment plan and the kernel variants.  plan_launch is the only place
 // that decides it; run_pipeline launches what it says and the test hooks (latok_debug_plan / _last_plan) report it.
 struct LaunchPlan {
@@ -237,7 +237,7 @@ hipError_t launch_counts_scatter(int kind, bool out32, const uint64_t* bits, con
                                  int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,
                                  const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st, DoneSignal done = DoneSignal{nullptr, 0, nullptr},
                                  DeviceTotal dt = DeviceTotal{nullptr, nullptr});
-// k_features_tiles (split_kernels.hip, where the measurements behind these values are told); latok_debug_limits reports them
+// k_features_tiles (feature_kernels.hip, where the measurements behind these values are told); latok_debug_limits reports them
 constexpr int kFeatWaves = 7;                                         // (6 -> 7: C2 -4.5 %, C3 -6 %; 8 would need rounds of < 800 tokens: two rounds per C2 tile)
 constexpr int kFeatRound = 896;                                       // tokens per round (word-major form)
 constexpr int kFeatRec = 25;                                          // packed records in the window, as in the output

@@ -1,6 +1,6 @@
 // fused_model.cpp -- TEST INFRASTRUCTURE ONLY.
 //
-// A CPU model of the HIP pipeline in latok_amd/csrc/split_kernels.hip: same tiling (4096-char tiles, 64 "lanes" of
+// A CPU model of the HIP pipeline in latok_amd/csrc/tile_core.h and split_kernels.hip: same tiling (4096-char tiles, 64 "lanes" of
 // one 64-bit word each), same per-lane math (it includes the product's lane_math.h and unicode_tables.inc), same
 // four stages (tile index / tiles / summary scan / fix-up), with the wavefront written as a plain loop over 64
 // lanes.  It exists to debug the *algorithm* against the reference-shaped oracle (latok_oracle.c) in a container

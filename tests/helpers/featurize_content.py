@@ -1,4 +1,4 @@
-"""Content, reference and census for the featurize kernel (k_features_tiles / feature_tile, latok_amd/csrc/split_kernels.hip).
+"""Content, reference and census for the featurize kernel (k_features_tiles / feature_tile, latok_amd/csrc/feature_kernels.hip).
 
 Three parts, none of which calls the product's kernels:
   * ``batch_reference`` / ``reference``: what featurize must return for a batch -- counts, spans4 and the 25 sums -- from the

@@ -1,4 +1,4 @@
-"""Every path of feature_tile (k_features_tiles, latok_amd/csrc/split_kernels.hip) against the oracle.
+"""Every path of feature_tile (k_features_tiles, latok_amd/csrc/feature_kernels.hip) against the oracle.
 
 tests/helpers/featurize_content.py plants, and names, what the kernel does differently from tile to tile: the word-major and the
 token-major form on both sides of the form threshold, window rounds of either form and the int64 span rounds that are out of step

@@ -1076,7 +1076,7 @@ def test_utf8_byte_space(gpu, oracle):
 
 
 def test_utf8_byte_space_tables_arrive_when_the_first_multibyte_char_does(gpu, oracle):
-    """Byte space copies its class table to LDS on demand (split_kernels.hip: tables_ensure_bytes): the launch brings in the 128
+    """Byte space copies its class table to LDS on demand (tile_core.h: tables_ensure_bytes): the launch brings in the 128
     ASCII codes, the first wave of a workgroup that meets a multi-byte char fetches the rest, waves that arrive meanwhile take a
     share or wait.  Large ASCII batches (hundreds of tiles per workgroup) whose ONLY multi-byte chars sit at chosen places -- the
     very first tile, the very last, one tile somewhere in the middle, the last byte of a tile, every 50th tile -- so that one wave
