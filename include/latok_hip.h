@@ -244,6 +244,48 @@ int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
                                         uint32_t seed, int64_t* counts_out /* may be NULL */, int64_t* spans_out /* may be NULL */,
                                         uint32_t* hashes_out, int64_t cap, int64_t* n_tokens_out, int flags, void* stream);
 
+/* Token ids in byte space: every token's id in a vocabulary -- an index into an embedding table, a count vector or a label space.
+ * A VOCABULARY is an ordered list of byte strings w_0 .. w_(V-1).  It may carry ids id_0 .. id_(V-1) (int32; word_ids = NULL means
+ * id_i = i) and it carries a 32-bit seed (of the MurmurHash3 x86_32 that places a word in the table; it does not change any id).
+ * A token is what the reference's tokenize() yields (default_tokenizer.py:149-160): for string s let (a_k, e_k), k = 0 .. c_s - 1, be
+ * the records latok_token_spans_utf8_bytes_batch reports for it, rank(s, k) = c_0 + .. + c_(s-1) + k as for the hashes call, and i
+ * the LOWEST index whose word equals the token's bytes utf8[byte_off[s] + a_k : byte_off[s] + e_k], byte for byte and of the same
+ * length.  Then
+ *   ids_out[rank(s, k)] = id_i      if such an i exists
+ *                         unk_id    otherwise (any int32, per call)
+ *   counts_out[s]       = c_s                        (may be NULL)
+ *   spans_out[2 rank(s, k)], [2 rank(s, k) + 1] = a_k, e_k   (may be NULL; the records of the spans call, byte for byte)
+ * Exact: the hash only finds the slot, equality is decided by comparing the bytes, so two different byte strings never share an id
+ * because their hashes agree.  Of a duplicate word the first occurrence wins.  The empty word is accepted and never matches (no
+ * token is empty).  V = 0 is accepted: every token gets unk_id.  Token bytes are compared verbatim and the spans call defines the
+ * spans: run-time rule tables, truncated sequences, lone lead bytes and stray continuation bytes need no rule of their own, nothing
+ * is refused as malformed.
+ * latok_vocab_create takes HOST pointers (words: the words back to back; word_off[n_words + 1]: their offsets, non-decreasing from
+ * 0), builds the table on the host and uploads it to the device of the current context.  Refused before any device work: a
+ * word_off that is not non-decreasing from 0, n_words >= 2^31, words that take 2^32 bytes or more once each is padded to 4, NULL
+ * outputs.  The object is immutable afterwards: any context of the same device may use it, concurrently; a call whose current
+ * context sits on another device returns LATOK_ERR_INVALID.  latok_vocab_destroy drains the current context (its stream and its
+ * flow) before it frees; as with latok_ctx_destroy, every OTHER context must be done with the object.  latok_vocab_info reports
+ * the word count as given, the slot count of the table (a power of two, >= 2 V and >= 64), the seed and the device; any output
+ * pointer may be NULL. */
+typedef struct latok_vocab latok_vocab;
+int latok_vocab_create(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
+                       const int32_t* word_ids /* may be NULL */, uint32_t seed, latok_vocab** vocab_out);
+int latok_vocab_destroy(latok_vocab* vocab);
+int latok_vocab_info(const latok_vocab* vocab, int64_t* n_words, int64_t* n_slots, uint32_t* seed, int* device);
+/* The ids call follows latok_token_hashes_utf8_bytes_batch in everything that is not the lookup.  LATOK_OUT_INT32 applies to
+ * counts and spans; an id is always one int32.  Empty and whitespace-only strings contribute no token; n_str = 0 or total_bytes =
+ * 0 gives zero tokens with counts cleared.  Capacity protocol, in TOKENS: cap too small -> nothing is written to ids or records,
+ * counts stay valid, the needed count is in *n_tokens_out and the call returns LATOK_ERR_INVALID; cap = 0 with ids_out = NULL is a
+ * size query; ids_out = NULL with cap > 0 is refused.  Host pointers or LATOK_DEVICE_PTRS (device UTF-8 pointer 16-byte aligned;
+ * the kernel reads the text as aligned 4-byte words, up to the word that holds the last byte), total_bytes = -1 as in the sibling
+ * calls; a flag bit other than these two is refused before any device work.  Every batch size takes the same kernels and gives the
+ * same ids; the call waits for its kernels once. */
+int latok_token_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                     const latok_vocab* vocab, int32_t unk_id, int64_t* counts_out /* may be NULL */,
+                                     int64_t* spans_out /* may be NULL */, int32_t* ids_out, int64_t cap, int64_t* n_tokens_out,
+                                     int flags, void* stream);
+
 /* Token feature vectors: reference featurize() (default_tokenizer.py:163-191) for a whole batch without the n x 25
  * matrix.  Per kept token k: spans4_out[4k..4k+3] = {raw_start, raw_end, strip_start, strip_end} (LaToken.start_idx /
  * end_idx are the raw span, LaToken.text is text[strip_start:strip_end]); features_out[25k..25k+24] = sum of the 25
@@ -439,6 +481,15 @@ int latok_flow_join_tokens_utf8_bytes(const uint8_t* utf8_dev, const int64_t* by
 int latok_flow_token_hashes_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
                                        uint32_t seed, void* counts_dev, void* spans_dev, uint32_t* hashes_dev, int64_t cap,
                                        int64_t* result_dev /* int64[2]: tokens, error word */, int flags);
+/* Token ids through the flow: what latok_token_ids_utf8_bytes_batch reports (the id of every token of default_tokenizer.py:149-160
+ * in `vocab`, unk_id where it has none; the definition is at that call), id for id, without waiting.  The two result words and the
+ * late-read capacity rule of latok_flow_token_hashes_utf8_bytes: result[0] = tokens, result[1] = error word; result[0] > cap means
+ * nothing was written to ids or records (counts are valid).  Read them after latok_flow_wait.  counts_dev and spans_dev may be
+ * NULL.  The ordering rule covers the input bytes, byte_off, ids and records (min(cap, total_bytes) tokens of each), counts and
+ * the result words; the vocabulary's table is library-owned read-only memory and takes no part in it. */
+int latok_flow_token_ids_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                    const latok_vocab* vocab, int32_t unk_id, void* counts_dev, void* spans_dev,
+                                    int32_t* ids_dev, int64_t cap, int64_t* result_dev /* int64[2]: tokens, error word */, int flags);
 int latok_flow_wait(void);
 
 /* ---- measurement ----------------------------------------------------------------------------------------------- */

@@ -51,6 +51,10 @@ SIGNATURES = {
     "latok_token_features_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, vp, vp, i64, C.POINTER(i64), ci, vp]),
     "latok_join_tokens_utf8_bytes_batch": (ci, [vp, vp, i64, i64, ci, vp, i64, vp, vp, C.POINTER(i64), ci, vp]),
     "latok_token_hashes_utf8_bytes_batch": (ci, [vp, vp, i64, i64, C.c_uint32, vp, vp, vp, i64, C.POINTER(i64), ci, vp]),
+    "latok_vocab_create": (ci, [vp, vp, i64, vp, C.c_uint32, C.POINTER(vp)]),
+    "latok_vocab_destroy": (ci, [vp]),
+    "latok_vocab_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint32), C.POINTER(ci)]),
+    "latok_token_ids_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, vp, vp, vp, i64, C.POINTER(i64), ci, vp]),
     "latok_token_features_batch": (ci, [vp, vp, i64, i64, vp, vp, vp, i64, C.POINTER(i64), ci, vp]),
     "latok_split_mask_kind_batch": (ci, [vp, ci, vp, i64, i64, vp, ci, vp]),
     "latok_split_offsets_kind_batch": (ci, [vp, ci, vp, i64, i64, vp, vp, i64, C.POINTER(i64), ci, vp]),
@@ -102,6 +106,7 @@ SIGNATURES = {
     "latok_flow_token_features_utf8_bytes": (ci, [vp, vp, i64, i64, vp, vp, vp, i64, vp, ci]),
     "latok_flow_join_tokens_utf8_bytes": (ci, [vp, vp, i64, i64, ci, vp, i64, vp, vp, vp, ci]),
     "latok_flow_token_hashes_utf8_bytes": (ci, [vp, vp, i64, i64, C.c_uint32, vp, vp, vp, i64, vp, ci]),
+    "latok_flow_token_ids_utf8_bytes": (ci, [vp, vp, i64, i64, vp, C.c_int32, vp, vp, vp, i64, vp, ci]),
     "latok_flow_wait": (ci, []),
     "latok_bench_split_mask_flow_gated": (ci, [vp, vp, i64, i64, vp, vp, ci, vp, C.POINTER(C.c_float), C.POINTER(i64),
                                                C.POINTER(i64)]),

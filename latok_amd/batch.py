@@ -537,6 +537,118 @@ def token_hashes_batch(texts, seed=0):
     return token_hashes_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], seed)
 
 
+# token ids: every token's id in a vocabulary, looked up on the device -- exact (the bytes decide, the hash only finds the slot)
+def _unk32(unk_id) -> int:
+    """unk_id as an int32; anything else is a ValueError (raised before any device is asked for)"""
+    if isinstance(unk_id, (int, np.integer)) and not isinstance(unk_id, bool) and -0x80000000 <= int(unk_id) <= 0x7FFFFFFF:
+        return int(unk_id)
+    raise ValueError("unk_id must be an int in -2**31 .. 2**31 - 1")
+
+
+class Vocab:
+    """A vocabulary on the device of the current context (``latok_vocab_create``): ``words`` is a list of ``bytes`` or ``str``
+    (``str`` is encoded as UTF-8 with surrogatepass), ``ids`` an optional int32 per word (default: its index), ``seed`` the 32-bit
+    seed of the table's hash.  Of a duplicate word the first wins; the empty word never matches.  Immutable; ``len()`` is the
+    number of words given, ``.n_slots`` the size of the table.  Freed by ``close()``, on leaving a ``with`` block, or with the
+    object."""
+
+    def __init__(self, words, ids=None, seed=0):
+        self.handle = None
+        seed = _seed32(seed)
+        blobs = [w.encode("utf-8", "surrogatepass") if isinstance(w, str) else bytes(w) for w in words]
+        off = np.zeros(len(blobs) + 1, np.int64)
+        if blobs:
+            np.cumsum([len(b) for b in blobs], out=off[1:])
+        data = np.frombuffer(b"".join(blobs), np.uint8)
+        if ids is not None:
+            raw = np.asarray(ids)
+            if raw.shape != (len(blobs),) or (raw.size and raw.dtype.kind not in "iu"):
+                raise ValueError("ids must be one integer per word")
+            if raw.size and (raw.min() < -0x80000000 or raw.max() > 0x7FFFFFFF):
+                raise ValueError("ids must fit int32")
+            ids = np.ascontiguousarray(raw, np.int32)
+        lib = _lib.ensure_init()
+        h = C.c_void_p()
+        _lib.check(lib.latok_vocab_create(_ptr(data) if data.size else None, _ptr(off), len(blobs), _ptr(ids) if ids is not None else None,
+                                          seed, C.byref(h)))
+        self._lib, self.handle, self.seed, self._n = lib, h, seed, len(blobs)
+        n_slots = C.c_int64(0)
+        _lib.check(lib.latok_vocab_info(h, None, C.byref(n_slots), None, None))
+        self.n_slots = n_slots.value
+
+    def __len__(self):
+        return self._n
+
+    def close(self):
+        if self.handle:
+            h, self.handle = self.handle, None
+            _lib.check(self._lib.latok_vocab_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _vocab_handle(vocab):
+    if not isinstance(vocab, Vocab) or not vocab.handle:
+        raise ValueError("vocab must be an open latok_amd.batch.Vocab")
+    return vocab.handle
+
+
+def _ids_csr(utf8, byte_off, vocab, unk_id, dtype, want_spans):
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    unk_id = _unk32(unk_id)
+    dt, flags = _out_dtype(dtype)
+    handle = _vocab_handle(vocab)
+    n_str = byte_off.size - 1
+    total = int(byte_off[-1]) if n_str > 0 else 0
+    lib = _lib.ensure_init()
+    cap = max(total, 1)                                  # a token has at least one byte
+    counts = np.zeros(n_str, dt)
+    ids = np.empty(cap, np.int32)
+    spans = np.empty((cap, 2), dt) if want_spans else None
+    n = C.c_int64(0)
+    _lib.check(lib.latok_token_ids_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, handle, unk_id, _ptr(counts),
+                                                    _ptr(spans) if want_spans else None, _ptr(ids), cap, C.byref(n), flags, None))
+    return counts, ids[:n.value].copy(), (spans[:n.value].copy() if want_spans else None)
+
+
+def token_ids_utf8_csr(utf8, byte_off, vocab, unk_id=-1, dtype=np.int64, spans=False):
+    """(counts, ids int32[n_tokens][, spans[n_tokens, 2]]): the id in ``vocab`` of every stripped, non-empty token -- the byte
+    ranges token_spans_utf8_bytes_csr reports, in its order: ids[k] belongs to spans[k] --, ``unk_id`` where the vocabulary does
+    not hold the token's bytes.  counts (and spans, with ``spans=True``) in ``dtype``.  Cut, hashed and looked up on the device
+    (``latok_token_ids_utf8_bytes_batch``); the host sees no token text."""
+    counts, ids, sp = _ids_csr(utf8, byte_off, vocab, unk_id, dtype, spans)
+    return (counts, ids, sp) if spans else (counts, ids)
+
+
+def token_ids_utf8_batch(blobs, vocab, unk_id=-1):
+    """list[bytes] (UTF-8) -> list of int32 arrays: the ids of every string's tokens ('' and whitespace-only -> empty)."""
+    unk_id = _unk32(unk_id)
+    _vocab_handle(vocab)
+    if len(blobs) == 0:
+        return []
+    utf8, byte_off = pack_utf8(blobs)
+    counts, ids, _ = _ids_csr(utf8, byte_off, vocab, unk_id, np.int64, False)
+    return np.split(ids, np.cumsum(counts)[:-1])
+
+
+def token_ids_batch(texts, vocab, unk_id=-1):
+    """list[str] -> list of int32 arrays: ``[d.get(t.encode("utf-8"), unk_id) for t in tokenize(text)]`` of every string, d =
+    the vocabulary as a dict.  The strings go through UTF-8 ("surrogatepass") on the host and the byte-space call."""
+    unk_id = _unk32(unk_id)
+    return token_ids_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], vocab, unk_id)
+
+
 # ---- PEP 393 code units: 1 / 2 / 4 bytes per char, the buffer the reference itself reads (latok.c:53-55,79) -----------
 def pack_kind(texts):
     """list[str] -> (units, row_off): units uint8 / uint16 / uint32 = the narrowest PEP 393 kind that holds every char of
@@ -811,6 +923,21 @@ def flow_token_hashes_utf8_bytes(d_utf8, d_byte_off, n_str, total_bytes, d_count
     lib = _lib.ensure_init()
     _lib.check(lib.latok_flow_token_hashes_utf8_bytes(d_utf8, d_byte_off, int(n_str), int(total_bytes), seed, d_counts, d_spans, d_hashes,
                                                       int(cap), d_result, flag32))
+
+
+def flow_token_ids_utf8_bytes(d_utf8, d_byte_off, n_str, total_bytes, vocab, d_counts, d_spans, d_ids, cap, d_result, unk_id=-1,
+                              dtype=np.int64):
+    """token ids of one device-resident UTF-8 batch through the flow (``latok_flow_token_ids_utf8_bytes``): what
+    ``token_ids_utf8_csr`` reports, in device buffers, without waiting.  ``d_result`` = int64[2]: tokens, error word; more tokens
+    than ``cap`` means nothing was written to ``d_ids`` / ``d_spans``.  ``d_counts`` and ``d_spans`` may be None.  The arguments
+    follow the C call, except that ``unk_id`` is a trailing keyword here and ``flags`` is ``dtype`` (the width of counts and
+    spans), as in the sibling wrappers."""
+    unk_id = _unk32(unk_id)
+    _, flag32 = _out_dtype(dtype)
+    handle = _vocab_handle(vocab)
+    lib = _lib.ensure_init()
+    _lib.check(lib.latok_flow_token_ids_utf8_bytes(d_utf8, d_byte_off, int(n_str), int(total_bytes), handle, unk_id, d_counts, d_spans, d_ids,
+                                                   int(cap), d_result, flag32))
 
 
 def flow_wait():

@@ -29,6 +29,7 @@
 #include "flow_hazards.h"
 #include "kernels.h"
 #include "unicode_tables.inc"
+#include "vocab_table.h"
 
 static_assert(LATOK_TBL_SHIFT == latok::kTblShift, "table shift");
 static_assert(LATOK_TBL_STAGE1_LEN == latok::kStage1Len, "stage-1 length");
@@ -1528,6 +1529,67 @@ static int enqueue_token_hashes(Ctx& g, Workspace& w, const TokenHashes& a) {
     return LATOK_OK;
 }
 
+// Token ids of a UTF-8 batch in BYTE space (latok_token_ids_utf8_bytes_batch and its flow form): enqueue_token_hashes' sequence with
+// k_vocab_scatter in place of k_hash_scatter -- the hash stays in its lane and finds the token's slot in the vocabulary table, the
+// bytes decide.  `w` was sized by ws_needs with WsShape{.spans = true}.
+struct Vocab {                     // latok_vocab: immutable once created
+    int device = -1;
+    int64_t n_words = 0;
+    uint64_t n_slots = 0;
+    uint32_t seed = 0;
+    void* d_slots = nullptr;       // VtSlot[n_slots]
+    void* d_blob = nullptr;        // the padded words
+};
+struct TokenIds {
+    Batch b;                       // UTF-8 bytes on the device (16-byte aligned), byte offsets, total in bytes (> 0), n_str > 0
+    const Vocab* vocab = nullptr;
+    int32_t unk = -1;
+    void* counts = nullptr;        // NULL: not asked for
+    void* spans = nullptr;         // NULL: not asked for
+    int32_t* ids = nullptr;        // NULL: a size query
+    int64_t cap = 0;               // in tokens
+    bool o32 = false;              // width of the counts and records
+    int64_t* r_tokens = nullptr;   // the two result words as the device sees them (cleared by the caller): tokens,
+    int64_t* r_err = nullptr;      // int32-overflow flag (bit 0) in the low half, scan flag in the high half
+    hipStream_t st = nullptr;
+};
+static int enqueue_token_ids(Ctx& g, Workspace& w, const TokenIds& a) {
+    int rc;
+    const hipStream_t st = a.st;
+    const int64_t total = a.b.total, words = (total + 63) / 64;
+    uint64_t* d_bits = (uint64_t*)w.bits.p;
+    uint64_t* d_space = (uint64_t*)w.space.p;
+    uint64_t* d_kept = (uint64_t*)w.kept.p;
+    int64_t* d_rank = (int64_t*)w.bases.p;
+    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
+    uint16_t* d_pref = (uint16_t*)w.wpref.p;
+    int64_t* d_total = (int64_t*)w.scalar.p;
+    int* d_err = (int*)a.r_err;
+    unsigned epoch = 0;
+    Pipe p;
+    p.b = a.b;
+    p.bits = d_bits;
+    p.space = d_space;
+    p.st = st;
+    if ((rc = run_pipeline(g, w, p))) return rc;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    HIP_TRY(latok::launch_word_counts_scan(true, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank, (unsigned long long*)w.chain.p,
+                                           (unsigned*)w.chain_ctl.p, epoch, d_total, a.r_tokens, d_err + 1, st));
+    const latok::VocabTable vt{a.vocab->d_slots, (const uint32_t*)a.vocab->d_blob, a.vocab->n_slots, a.vocab->seed};
+    HIP_TRY(latok::launch_vocab_scatter(a.o32, (const uint8_t*)a.b.in.p, vt, a.unk, d_bits, d_space, d_kept, d_rank, d_tcnt, d_pref, words, total,
+                                        a.b.row, a.b.n_str, (const int64_t*)w.tile_first.p, a.ids ? a.spans : nullptr, a.ids, d_total, a.cap,
+                                        a.counts, d_err, st));
+    return LATOK_OK;
+}
+// the vocabulary of an ids call: there is one, and it lives on the device of the context that runs the call
+static int check_vocab(const Ctx& g, const latok_vocab* vocab, const Vocab** v) {
+    *v = reinterpret_cast<const Vocab*>(vocab);
+    if (!*v) return fail(LATOK_ERR_INVALID, "vocab is NULL");
+    if ((*v)->device != g.device)
+        return fail(LATOK_ERR_INVALID, "the vocabulary lives on device %d, the current context on device %d", (*v)->device, g.device);
+    return LATOK_OK;
+}
+
 // The blocking call behind compact_common's checks: b = the caller's UTF-8 batch (total resolved, n_str > 0, total > 0).  Every
 // batch that the host did not decode takes this route, whatever its size.  One synchronisation.
 static int features_utf8_bytes_route(Ctx& g, const Batch& b, bool dev, bool o32, void* counts_out, void* items_out, int8_t* features_out,
@@ -2115,6 +2177,151 @@ int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
     return LATOK_OK;
 }
 
+/* vocabularies: built on the host (vocab_table.h), uploaded once, read only afterwards */
+static int flow_drain(Ctx& g);   // batch flow (below): its three streams
+int latok_vocab_create(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, uint32_t seed,
+                       latok_vocab** vocab_out) {
+    LATOK_ENTER();
+    // what needs no device is refused first
+    if (!vocab_out) return fail(LATOK_ERR_INVALID, "vocab_out is NULL");
+    *vocab_out = nullptr;
+    if (n_words < 0 || n_words >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "n_words must be in 0 .. 2^31 - 1");
+    if (!word_off) return fail(LATOK_ERR_INVALID, "word_off is NULL");
+    if (word_off[0] != 0) return fail(LATOK_ERR_INVALID, "word_off must start at 0");
+    uint64_t padded = 0;
+    for (int64_t i = 0; i < n_words; ++i) {
+        if (word_off[i + 1] < word_off[i]) return fail(LATOK_ERR_INVALID, "word_off must be non-decreasing (word %lld)", (long long)i);
+        padded += ((uint64_t)(word_off[i + 1] - word_off[i]) + 3u) & ~3ull;
+        if (padded >= (1ull << 32)) return fail(LATOK_ERR_INVALID, "the padded words take 2^32 bytes or more");
+    }
+    if (word_off[n_words] > 0 && !words) return fail(LATOK_ERR_INVALID, "words is NULL");
+    int rc = need_init(g);
+    if (rc) return rc;
+    VtTable t;
+    Vocab* v = nullptr;
+    try {
+        vt_build(words, word_off, n_words, word_ids, seed, &t);
+        v = new Vocab();
+    } catch (const std::bad_alloc&) {
+        return fail(LATOK_ERR_NOMEM, "out of host memory");
+    }
+    v->device = g.device;
+    v->n_words = n_words;
+    v->n_slots = t.slots.size();
+    v->seed = seed;
+    const size_t slot_bytes = t.slots.size() * sizeof(VtSlot), blob_bytes = t.blob.size() * 4;
+    hipError_t e = hipMalloc(&v->d_slots, slot_bytes);
+    if (e == hipSuccess) e = hipMalloc(&v->d_blob, blob_bytes);
+    if (e != hipSuccess) {
+        if (v->d_slots) (void)hipFree(v->d_slots);
+        delete v;
+        return fail(LATOK_ERR_NOMEM, "hipMalloc(%zu) failed: %s", slot_bytes + blob_bytes, hipGetErrorString(e));
+    }
+    e = hipMemcpyAsync(v->d_slots, t.slots.data(), slot_bytes, hipMemcpyHostToDevice, g.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(v->d_blob, t.blob.data(), blob_bytes, hipMemcpyHostToDevice, g.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);   // (the host table dies with this call, and every context may use the object at once)
+    if (e != hipSuccess) {
+        (void)hipFree(v->d_slots);
+        (void)hipFree(v->d_blob);
+        delete v;
+        return fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
+    }
+    *vocab_out = reinterpret_cast<latok_vocab*>(v);
+    return LATOK_OK;
+}
+
+int latok_vocab_destroy(latok_vocab* vocab) {
+    LATOK_ENTER();
+    Vocab* v = reinterpret_cast<Vocab*>(vocab);
+    if (!v) return LATOK_OK;
+    int rc = LATOK_OK;
+    if (g.inited) {   // the current context's own work on it: its stream and its flow
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        rc = flow_drain(g);
+    }
+    (void)hipFree(v->d_slots);
+    (void)hipFree(v->d_blob);
+    delete v;
+    return rc;
+}
+
+int latok_vocab_info(const latok_vocab* vocab, int64_t* n_words, int64_t* n_slots, uint32_t* seed, int* device) {
+    const Vocab* v = reinterpret_cast<const Vocab*>(vocab);
+    if (!v) return fail(LATOK_ERR_INVALID, "vocab is NULL");
+    if (n_words) *n_words = v->n_words;
+    if (n_slots) *n_slots = (int64_t)v->n_slots;
+    if (seed) *seed = v->seed;
+    if (device) *device = v->device;
+    return LATOK_OK;
+}
+
+/* token ids in byte space: the id of every token in a vocabulary, rank-aligned with the span records (enqueue_token_ids) */
+int latok_token_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
+                                     int32_t unk_id, int64_t* counts_out, int64_t* spans_out, int32_t* ids_out, int64_t cap,
+                                     int64_t* n_tokens_out, int flags, void* stream) {
+    LATOK_ENTER();
+    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (!n_tokens_out) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
+    *n_tokens_out = 0;
+    if (cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
+    if (!ids_out && cap > 0) return fail(LATOK_ERR_INVALID, "ids_out is NULL but cap > 0 (a size query passes cap = 0)");
+    const Vocab* v = nullptr;
+    if ((rc = check_vocab(g, vocab, &v))) return rc;
+    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0, o32 = (flags & LATOK_OUT_INT32) != 0;
+    const size_t elt = o32 ? 4 : 8;   // width of a count and of one field of a record (an id is 4 bytes in every mode)
+    int64_t total = total_bytes;
+    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
+    StreamTurn turn(g, stream);
+    hipStream_t st = turn.st;
+    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
+    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (n_str == 0 || total == 0) return zero_counts(dev, counts_out, (size_t)n_str * elt, st, true);   // no byte, no token
+    if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    if (dev && (((uintptr_t)spans_out & (2 * elt - 1)) != 0 || ((uintptr_t)counts_out & (elt - 1)) != 0 || ((uintptr_t)ids_out & 3) != 0))
+        return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    g.last_route = 7;
+    Batch d;
+    if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
+    if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+    int64_t* p_tot = (int64_t*)g.pin_tot.d;
+    TokenIds a;
+    a.b = d;
+    a.vocab = v;
+    a.unk = unk_id;
+    a.counts = counts_out;
+    a.spans = spans_out;
+    a.ids = ids_out;
+    a.cap = ids_out ? std::min(cap, total) : 0;   // (a token has at least one byte: a larger capacity gates nothing, and the staging is sized by it)
+    a.o32 = o32;
+    if (!dev) {
+        if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 2 * elt + 16)) || (rc = g.counts.ensure((size_t)n_str * 8)))
+            return rc;
+        if (ids_out) a.ids = (int32_t*)g.h_aux.p;
+        if (spans_out) a.spans = g.h_out.p;
+        if (counts_out) a.counts = g.counts.p;
+    }
+    h_tot[0] = h_tot[1] = 0;
+    a.r_tokens = p_tot;
+    a.r_err = p_tot + 1;
+    a.st = st;
+    if ((rc = enqueue_token_ids(g, g.ws, a))) return rc;
+    if (!dev && counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));   // valid whatever the capacity
+    HIP_TRY(hipStreamSynchronize(st));   // the call's one wait for the kernels
+    int64_t n = 0;
+    if ((rc = finish_totals(g.ws, h_tot, 1, &n))) return rc;
+    *n_tokens_out = n;
+    if (n > cap) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld tokens", (long long)n);
+    if (!dev && n > 0 && ids_out) {   // (host pointers: the copies, whose size is known only now)
+        HIP_TRY(hipMemcpyAsync(ids_out, a.ids, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        if (spans_out) HIP_TRY(hipMemcpyAsync(spans_out, a.spans, (size_t)n * 2 * elt, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return LATOK_OK;
+}
+
 /* PEP 393 buffers (the reference's own input, latok.c:53-55,79): fixed-width code units of 1, 2 or 4 bytes */
 static int check_kind(int kind) {
     if (kind != 1 && kind != 2 && kind != 4) return fail(LATOK_ERR_INVALID, "kind must be 1 (Latin-1), 2 (UCS-2) or 4 (UCS-4), got %d", kind);
@@ -2385,7 +2592,6 @@ int latok_memset_dev(void* d, int v, size_t n) {
     HIP_TRY(hipMemsetAsync(d, v, n, g.stream));
     return LATOK_OK;
 }
-static int flow_drain(Ctx& g);   // batch flow (below): its three streams
 int latok_sync(void) {
     LATOK_ENTER();
     int rc = need_init(g);
@@ -2535,7 +2741,7 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
  * 2: UTF-8 through the staged device decoder, 3: UTF-8 through byte space and the packed code-point masks (and codes),
  * 4: featurize of UTF-8 in byte space (byte records from the byte-space masks, sums from the packed code-point masks),
  * 5: joined token text of UTF-8 in byte space (every batch size; there is no small-batch route),
- * 6: token hashes of UTF-8 in byte space (every batch size as well) */
+ * 6: token hashes of UTF-8 in byte space (every batch size as well); 7: token ids of UTF-8 in byte space (likewise) */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;
@@ -3199,6 +3405,68 @@ int latok_flow_token_hashes_utf8_bytes(const uint8_t* utf8_dev, const int64_t* b
     a.r_err = result_dev + 1;
     a.st = f.st;
     return enqueue_token_hashes(g, f.ws, a);
+}
+
+// ---- token ids in a flow ---------------------------------------------------------------------------------------------------------
+// The ranges are those of a hash batch with the ids in the hashes' place (both are 4 bytes per token); the vocabulary table is
+// library-owned read-only memory and is not tracked.
+/* test hook (not part of the ABI; needs no device): the ranges a token-id batch of a flow notes, in the form latok_debug_flow_route
+ * takes them.  addr[6] = {utf8, byte_off, counts, spans, ids, result}.  Returns the number of ranges written to lo / bytes /
+ * is_write (at most n_max), < 0 on a bad argument. */
+extern "C" int latok_debug_flow_ids_ranges(const uint64_t* addr, int64_t n_str, int64_t total_bytes, int64_t cap, int flags, uint64_t* lo,
+                                           uint64_t* bytes, int* is_write, int n_max) {
+    if (!addr || !lo || !bytes || !is_write) return fail(LATOK_ERR_INVALID, "bad argument");
+    latok::FlowRange r[kHashFlowRanges];
+    const int n = hash_flow_ranges((const uint8_t*)(uintptr_t)addr[0], (const int64_t*)(uintptr_t)addr[1], n_str, total_bytes,
+                                   (void*)(uintptr_t)addr[2], (void*)(uintptr_t)addr[3], (uint32_t*)(uintptr_t)addr[4], cap,
+                                   (int64_t*)(uintptr_t)addr[5], (flags & LATOK_OUT_INT32) != 0, r);
+    return export_flow_ranges(r, n, lo, bytes, is_write, n_max);
+}
+
+int latok_flow_token_ids_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                    const latok_vocab* vocab, int32_t unk_id, void* counts_dev, void* spans_dev, int32_t* ids_dev, int64_t cap,
+                                    int64_t* result_dev, int flags) {
+    LATOK_ENTER();
+    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (n_str < 0) return fail(LATOK_ERR_INVALID, "n_str must be >= 0");
+    if (cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
+    if (!ids_dev && cap > 0) return fail(LATOK_ERR_INVALID, "ids is NULL but cap > 0 (a size query passes cap = 0)");
+    if (!result_dev) return fail(LATOK_ERR_INVALID, "NULL result pointer");
+    if (((uintptr_t)result_dev & 7) != 0) return fail(LATOK_ERR_INVALID, "result pointer must be 8-byte aligned");
+    const Vocab* v = nullptr;
+    if ((rc = check_vocab(g, vocab, &v))) return rc;
+    const bool o32 = (flags & LATOK_OUT_INT32) != 0;
+    const size_t rec = o32 ? 4 : 8;
+    if (((uintptr_t)spans_dev & (2 * rec - 1)) != 0 || ((uintptr_t)counts_dev & (rec - 1)) != 0 || ((uintptr_t)ids_dev & 3) != 0)
+        return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    if (total_bytes < 0 && (rc = resolve_total_device(byte_off_dev, n_str, &total_bytes, g.stream))) return rc;
+    const bool empty = n_str == 0 || total_bytes <= 0;   // no token
+    if (!empty) {
+        if (!utf8_dev || !byte_off_dev) return fail(LATOK_ERR_INVALID, "NULL buffer");
+        if (((uintptr_t)utf8_dev & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    }
+    latok::FlowRange r[kHashFlowRanges];
+    const int n_r = hash_flow_ranges(utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, spans_dev, (uint32_t*)ids_dev, cap, result_dev, o32, r);
+    const FlowOpen o{.r = r, .n_r = n_r, .empty = empty, .result = {result_dev, 16}, .zero = {{counts_dev, (size_t)n_str * rec}},
+                     .units = total_bytes, .shape = {.spans = true}};
+    int slot = 0;
+    if ((rc = flow_open(g, o, &slot)) || empty) return rc;
+    Ctx::FlowSlot& f = g.flow[slot];
+    TokenIds a;
+    a.b = Batch{Input{utf8_dev, Form::Utf8}, byte_off_dev, n_str, total_bytes};
+    a.vocab = v;
+    a.unk = unk_id;
+    a.counts = counts_dev;
+    a.spans = spans_dev;
+    a.ids = ids_dev;
+    a.cap = ids_dev ? std::min(cap, total_bytes) : 0;
+    a.o32 = o32;
+    a.r_tokens = result_dev;
+    a.r_err = result_dev + 1;
+    a.st = f.st;
+    return enqueue_token_ids(g, f.ws, a);
 }
 
 int latok_flow_wait(void) {

@@ -25,6 +25,7 @@
 #include "kernels.h"
 #include "lane_math.h"
 #include "token_hash.h"
+#include "vocab_table.h"
 #include "wave_ops.h"
 
 namespace latok {
@@ -234,11 +235,23 @@ __global__ __launch_bounds__(256) void k_string_counts(const uint64_t* __restric
 // hold neighbouring tokens, their aligned dword loads share cache lines --, unless the token is longer than kHashWaveBytes: those
 // the wave takes one at a time behind the round, 256 bytes per step with coalesced loads, every lane mixing its own block and
 // the h chain folded in lane order, so a long token costs its length once, with the whole wave at work.
+// KIND 4 (k_vocab_scatter): KIND 3 with the hash kept in its lane instead of stored: the lane that hashed a short token probes the
+// vocabulary table with it (vocab_table.h: one 16-byte slot per step, at most n_slots steps), compares the bytes where hash and
+// length agree and stores ids[k] = the word's id or unk.  A long token's hash is wave-uniform, so the wave probes in step -- every
+// lane asks for the same slot, one request -- and compares a candidate 64 dwords per step with coalesced loads; a ballot decides.
+// The table and the blob are read with ordinary cached loads (they are what is worth keeping in L2); no hash goes through memory.
 constexpr int scatter_waves(int kind) { return 4; }   // waves per workgroup
 struct HashArgs {
     const uint32_t* text = nullptr;   // the batch's bytes as aligned dwords (the buffer is 16-byte aligned)
     uint32_t* hashes = nullptr;
     uint32_t seed = 0;
+};
+struct VocabArgs {                    // (KIND 4; the text and the seed travel in HashArgs)
+    const VtSlot* slots = nullptr;
+    const uint32_t* blob = nullptr;
+    uint64_t n_slots = 0;             // a power of two
+    int32_t* ids = nullptr;
+    int32_t unk = 0;
 };
 
 template <int KIND, typename OUT>
@@ -248,7 +261,9 @@ __device__ __forceinline__ void counts_scatter_block(
     int64_t n_words, int64_t total, const int64_t* __restrict__ row_off, int64_t n_str,
     const int64_t* __restrict__ tile_first, OUT* __restrict__ out, const int64_t* __restrict__ n_items_dev, int64_t cap,
     OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, unsigned vb,     // vb: (virtual) workgroup index
-    const HashArgs ha = HashArgs{}) {                                                            // (KIND 3 only)
+    const HashArgs ha = HashArgs{},                                                              // (KIND 3 and 4 only)
+    const VocabArgs va = VocabArgs{}) {                                                          // (KIND 4 only)
+    constexpr bool kHashes = KIND == 3 || KIND == 4;                                             // records optional, tokens hashed
     static_assert(scatter_waves(KIND) * 64 == 256, "both roles use 256-thread workgroups");
     if (vb >= n_scatter_blocks) {   // role 2: one thread per string
         if (counts)
@@ -403,7 +418,7 @@ __device__ __forceinline__ void counts_scatter_block(
             const uint64_t* orow = rows + 6 * owner;
             const uint64_t o_xb = orow[0], o_nn = orow[1], o_xb1 = orow[2], o_nn1 = orow[3], o_Bw = orow[4];
             const int64_t o_lo_in = (int64_t)orow[5];
-            int64_t h_a = 0, h_e = 0;                                 // (KIND 3) my token's absolute byte range
+            int64_t h_a = 0, h_e = 0;                                 // (KIND 3, 4) my token's absolute byte range
             if (active) {
                 const int64_t obase = (w0 + owner) << 6;
                 const uint64_t bl = o_Bw & ((2ull << b) - 1ull);      // string starts at or before the item (b = 63: all)
@@ -456,21 +471,30 @@ __device__ __forceinline__ void counts_scatter_block(
                             __builtin_nontemporal_store(r, rec);
                             __builtin_nontemporal_store(v, rec + 1);
                         }
-                    } else if (KIND != 3 || out) {
+                    } else if (!kHashes || out) {
                         __builtin_nontemporal_store(v, reinterpret_cast<out2*>(out) + base_out + win0 + j);
                     }
-                    if (KIND == 3) {
+                    if (kHashes) {
                         h_a = a2;
                         h_e = e2;
                         if (e2 - a2 <= kHashWaveBytes) {
                             const uint32_t* text = ha.text;
                             const uint32_t h = th_hash_lane([text](int64_t i) { return text[i]; }, a2, e2, ha.seed);
-                            __builtin_nontemporal_store(h, ha.hashes + base_out + win0 + j);
+                            if (KIND == 3) {
+                                __builtin_nontemporal_store(h, ha.hashes + base_out + win0 + j);
+                            } else {
+                                const VtSlot* slots = va.slots;
+                                const uint32_t* blob = va.blob;
+                                const int32_t id = vt_lookup_lane([text](int64_t i) { return text[i]; }, a2, e2, h,
+                                                                  [slots](uint64_t i) { return slots[i]; },
+                                                                  [blob](uint64_t i) { return blob[i]; }, va.n_slots, va.unk);
+                                __builtin_nontemporal_store(id, va.ids + base_out + win0 + j);
+                            }
                         }
                     }
                 }
             }
-            if (KIND == 3) {
+            if (kHashes) {
                 // the long tokens of the round, one at a time by the whole wave (wave-uniform loop: `todo` is a ballot)
                 const uint32_t* text = ha.text;
                 auto ld = [text](int64_t i) { return text[i]; };
@@ -486,7 +510,30 @@ __device__ __forceinline__ void counts_scatter_block(
                         h = th_wave_fold(h, [cur](int l) { return (uint32_t)__builtin_amdgcn_readlane((int)cur, l); }, th_wave_count(a, e, r));
                     }
                     h = th_wave_tail(ld, a, e, h);
-                    if (lane == src) __builtin_nontemporal_store(h, ha.hashes + base_out + win0 + j);
+                    if (KIND == 3) {
+                        if (lane == src) __builtin_nontemporal_store(h, ha.hashes + base_out + win0 + j);
+                    } else {
+                        // every lane holds the same h: the wave walks the slots in step and compares a candidate together
+                        const VtSlot* slots = va.slots;
+                        const uint32_t* blob = va.blob;
+                        const uint32_t hu = (uint32_t)__builtin_amdgcn_readfirstlane((int)h);
+                        const int32_t id = vt_probe(
+                            [slots](uint64_t i) {
+                                const VtSlot v = slots[i];
+                                return VtSlot{(uint32_t)__builtin_amdgcn_readfirstlane((int)v.hash), __builtin_amdgcn_readfirstlane(v.id),
+                                              (uint32_t)__builtin_amdgcn_readfirstlane((int)v.off),
+                                              (uint32_t)__builtin_amdgcn_readfirstlane((int)v.len)};
+                            },
+                            va.n_slots, hu, (uint32_t)(e - a),
+                            [ld, a, e, blob, lane](uint32_t off) {
+                                const int64_t rounds_c = vt_wave_rounds(a, e);
+                                for (int64_t r = 0; r < rounds_c; ++r)
+                                    if (__ballot(vt_wave_differs(ld, a, e, [blob](uint64_t i) { return blob[i]; }, off, r, lane))) return false;
+                                return true;
+                            },
+                            va.unk);
+                        if (lane == src) __builtin_nontemporal_store(id, va.ids + base_out + win0 + j);
+                    }
                 }
             }
         }
@@ -522,6 +569,18 @@ __global__ __launch_bounds__(scatter_waves(3) * 64) void k_hash_scatter(
     OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, HashArgs ha) {
     counts_scatter_block<3, OUT>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str, tile_first, out,
                                  n_items_dev, cap, counts, n_scatter_blocks, err, blockIdx.x, ha);
+}
+
+// Token ids: KIND 4 of the body above in a kernel of its own (the kernels above keep their arguments and their code).
+template <typename OUT>
+__global__ __launch_bounds__(scatter_waves(4) * 64) void k_vocab_scatter(
+    const uint64_t* __restrict__ bits, const uint64_t* __restrict__ space, const uint64_t* __restrict__ item_mask,
+    const int64_t* __restrict__ tile_rank, const int64_t* __restrict__ tile_cnt, const uint16_t* __restrict__ word_pref,
+    int64_t n_words, int64_t total, const int64_t* __restrict__ row_off, int64_t n_str,
+    const int64_t* __restrict__ tile_first, OUT* __restrict__ out, const int64_t* __restrict__ n_items_dev, int64_t cap,
+    OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, HashArgs ha, VocabArgs va) {
+    counts_scatter_block<4, OUT>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str, tile_first, out,
+                                 n_items_dev, cap, counts, n_scatter_blocks, err, blockIdx.x, ha, va);
 }
 
 // ---- code-point results of a UTF-8 batch from its BYTE-space results ------------------------------------------------------
@@ -1193,6 +1252,35 @@ hipError_t launch_hash_scatter(bool out32, const uint8_t* u8, uint32_t seed, con
     else
         hipLaunchKernelGGL((k_hash_scatter<int64_t>), grid, block, 0, st, bits, space, kept, tile_rank, tile_cnt, word_pref, n_words, total,
                            row_off, n_str, tile_first, (int64_t*)out, n_items_dev, cap, (int64_t*)counts, nb_scatter, err, ha);
+    return hipGetLastError();
+}
+
+// token ids (+ the span records if out != NULL, + the counts if counts != NULL); ids == NULL: counts only (a size query)
+hipError_t launch_vocab_scatter(bool out32, const uint8_t* u8, const VocabTable& vt, int32_t unk_id, const uint64_t* bits,
+                                const uint64_t* space, const uint64_t* kept, const int64_t* tile_rank, const int64_t* tile_cnt,
+                                const uint16_t* word_pref, int64_t n_words, int64_t total, const int64_t* row_off, int64_t n_str,
+                                const int64_t* tile_first, void* out, int32_t* ids, const int64_t* n_items_dev, int64_t cap, void* counts,
+                                int* err, hipStream_t st) {
+    if (n_words <= 0) return hipSuccess;
+    const unsigned nb_scatter = ids ? (unsigned)((n_words + 255) / 256) : 0u;
+    const unsigned nb_counts = counts ? (unsigned)((n_str + 255) / 256) : 0u;
+    if (nb_scatter + nb_counts == 0) return hipSuccess;
+    HashArgs ha;
+    ha.text = reinterpret_cast<const uint32_t*>(u8);
+    ha.seed = vt.seed;
+    VocabArgs va;
+    va.slots = reinterpret_cast<const VtSlot*>(vt.slots);
+    va.blob = vt.blob;
+    va.n_slots = vt.n_slots;
+    va.ids = ids;
+    va.unk = unk_id;
+    const dim3 grid(nb_scatter + nb_counts), block(scatter_waves(4) * 64);
+    if (out32)
+        hipLaunchKernelGGL((k_vocab_scatter<int32_t>), grid, block, 0, st, bits, space, kept, tile_rank, tile_cnt, word_pref, n_words, total,
+                           row_off, n_str, tile_first, (int32_t*)out, n_items_dev, cap, (int32_t*)counts, nb_scatter, err, ha, va);
+    else
+        hipLaunchKernelGGL((k_vocab_scatter<int64_t>), grid, block, 0, st, bits, space, kept, tile_rank, tile_cnt, word_pref, n_words, total,
+                           row_off, n_str, tile_first, (int64_t*)out, n_items_dev, cap, (int64_t*)counts, nb_scatter, err, ha, va);
     return hipGetLastError();
 }
 

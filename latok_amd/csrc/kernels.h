@@ -275,6 +275,20 @@ hipError_t launch_hash_scatter(bool out32, const uint8_t* u8, uint32_t seed, con
                                const uint64_t* kept, const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref,
                                int64_t n_words, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,
                                uint32_t* hashes, const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st);
+// token ids of a UTF-8 batch in byte space (compact_kernels.hip: KIND 4): launch_hash_scatter's launch with the hash kept in its
+// lane and looked up in a vocabulary table (vocab_table.h) -- exact: the hash finds the slot, the bytes decide.  ids[rank] = the
+// word's id or unk_id.  The table is device memory, read only.
+struct VocabTable {
+    const void* slots = nullptr;      // VtSlot[n_slots]
+    const uint32_t* blob = nullptr;   // the padded words
+    uint64_t n_slots = 0;             // a power of two
+    uint32_t seed = 0;
+};
+hipError_t launch_vocab_scatter(bool out32, const uint8_t* u8, const VocabTable& vt, int32_t unk_id, const uint64_t* bits,
+                                const uint64_t* space, const uint64_t* kept, const int64_t* tile_rank, const int64_t* tile_cnt,
+                                const uint16_t* word_pref, int64_t n_words, int64_t total, const int64_t* row_off, int64_t n_str,
+                                const int64_t* tile_first, void* out, int32_t* ids, const int64_t* n_items_dev, int64_t cap, void* counts,
+                                int* err, hipStream_t st);
 // zeros at codes[t .. t + kTile + 256), t = *total_dev held inside [0, bound]
 hipError_t launch_pad_codes(uint8_t* codes, const int64_t* total_dev, int64_t bound, hipStream_t st);
 int64_t utf8_blocks(int64_t total_bytes);   // 4 KiB blocks of the chunk-parallel UTF-8 decoder

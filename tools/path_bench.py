@@ -30,6 +30,12 @@
   bytes_hashes32 / bytes_hashes32_flow / bytes_hashes_only / bytes_hashes_only_flow   latok_token_hashes_utf8_bytes_batch /
                   latok_flow_token_hashes_utf8_bytes: one MurmurHash3 x86_32 word per token, with the int32 counts and records of
                   bytes_spans32 (hashes32) or alone (hashes_only: no counts, no records); same process run as bytes_spans32
+  bytes_ids32 / bytes_ids32_flow / bytes_ids_only / bytes_ids_only_flow   latok_token_ids_utf8_bytes_batch /
+                  latok_flow_token_ids_utf8_bytes: every token's id in a vocabulary (--vocab all: every distinct token of the corpus,
+                  so every lookup hits; half: every second distinct token, in order of first appearance), with the int32 counts and
+                  records of bytes_spans32 (ids32) or alone (ids_only); same process run as bytes_spans32 and bytes_hashes32
+  py_ids         end to end in Python on host blobs (the first --py-strings strings): batch.token_ids_utf8_batch(blobs, vocab)
+                  against [[d.get(t, -1) for t in row] for row in batch.tokenize_utf8_batch(blobs)]; one line each
   py_join        end to end in Python on host blobs (the first --py-strings strings): batch.join_tokens_utf8_batch(blobs) against the
                   only route to the same rows without it, [b" ".join(t) for t in batch.tokenize_utf8_batch(blobs)]; one line each
   rules_mask      latok_split_mask_batch after latok_set_rules(built-in tables)   (8f-4)
@@ -94,9 +100,11 @@ def main():
                                        "utf8_bytes_features32,utf8_bytes_features32_flow,pair_features32_bytes_spans32,pair_features32_bytes_spans32_flow,"
                                        "bytes_mask,bytes_offsets,bytes_spans,bytes_spans32,bytes_spans32_flow,bytes_join,bytes_join_flow,"
                                        "bytes_hashes32,bytes_hashes32_flow,bytes_hashes_only,bytes_hashes_only_flow,"
+                                       "bytes_ids32,bytes_ids32_flow,bytes_ids_only,bytes_ids_only_flow,"
                                        "rules_mask,kind_mask,kind_offsets,kind_offsets32,"
                                        "kind_spans,kind_spans32")
-    ap.add_argument("--py-strings", type=int, default=200_000, help="strings of the py_join path (host blobs)")
+    ap.add_argument("--py-strings", type=int, default=200_000, help="strings of the py_join / py_ids paths (host blobs)")
+    ap.add_argument("--vocab", default="all", choices=("all", "half"), help="vocabulary of the ids paths: every distinct token of the corpus, or every second one")
     args = ap.parse_args()
     lib = _lib.ensure_init()
     model, seed, lo, hi = WORKLOADS[args.workload]
@@ -375,7 +383,8 @@ def main():
             lambda: n8 + csr + 8 * n + 16 * nout.value, "UTF-8 bytes + 8 B/string read; 8 B/string + 16 B/token written (byte ranges)")
     # joined token text and the byte-space spans beside it: every line of this leg in one process run, in the order given
     join_leg = [p for p in paths if p in ("bytes_join", "bytes_join_flow", "bytes_spans32", "bytes_spans32_flow", "bytes_hashes32",
-                                          "bytes_hashes32_flow", "bytes_hashes_only", "bytes_hashes_only_flow", "py_join")]
+                                          "bytes_hashes32_flow", "bytes_hashes_only", "bytes_hashes_only_flow", "bytes_ids32", "bytes_ids32_flow",
+                                          "bytes_ids_only", "bytes_ids_only_flow", "py_ids", "py_join")]
     if join_leg:
         jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64, cap * 4, cap * 4)]
         if not all(jb):
@@ -393,6 +402,42 @@ def main():
         def hashes_blocking(rec):
             return lib.latok_token_hashes_utf8_bytes_batch(d_u8, d_boff, n, n8, SEED, s_counts if rec else None, s_items if rec else None, h_a, cap,
                                                            C.byref(nout), D32, None)
+
+        note_i = ("UTF-8 bytes + 8 B/string read, the bytes of every token read once more, one 16-byte slot per probe step and the word of a "
+                  "candidate read from the table; 4 B/token written (exact id, --vocab " + args.vocab + ")")
+        vocab_box = []
+
+        def corpus_vocab():
+            """the vocabulary of the ids paths, built once: distinct tokens in order of first appearance, told apart by two hashes"""
+            if vocab_box:
+                return vocab_box[0]
+            from latok_amd import batch
+            keys = []
+            for seed in (1, 2):
+                _lib.check(lib.latok_token_hashes_utf8_bytes_batch(d_u8, d_boff, n, n8, seed, s_counts, s_items, h_a, cap, C.byref(nout), D32, None))
+                h = np.empty(nout.value, np.uint32)
+                _lib.check(lib.latok_memcpy_d2h(h.ctypes.data, h_a, h.nbytes))
+                keys.append(h.astype(np.uint64))
+            sp, cnt = np.empty((nout.value, 2), np.int32), np.empty(n, np.int32)
+            _lib.check(lib.latok_memcpy_d2h(sp.ctypes.data, s_items, sp.nbytes))
+            _lib.check(lib.latok_memcpy_d2h(cnt.ctypes.data, s_counts, cnt.nbytes))
+            first = np.sort(np.unique((keys[0] << np.uint64(32)) | keys[1], return_index=True)[1])
+            n_distinct = first.size
+            first = first[::2] if args.vocab == "half" else first
+            base = np.repeat(boff[:-1], cnt)[first]
+            raw = u8.tobytes()
+            words = [raw[a:b] for a, b in zip((base + sp[first, 0]).tolist(), (base + sp[first, 1]).tolist())]
+            t = time.perf_counter()
+            v = batch.Vocab(words, seed=SEED)
+            print(json.dumps({"vocab": args.vocab, "workload": args.workload, "distinct_tokens": int(n_distinct), "words": len(words),
+                              "n_slots": v.n_slots, "table_MiB": v.n_slots * 16 / 2**20, "word_bytes": sum(map(len, words)),
+                              "create_ms": (time.perf_counter() - t) * 1e3}), flush=True)
+            vocab_box.append(v)
+            return v
+
+        def ids_blocking(rec):
+            return lib.latok_token_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, corpus_vocab().handle, -1, s_counts if rec else None,
+                                                        s_items if rec else None, h_a, cap, C.byref(nout), D32, None)
 
         def two_words(name, want):
             res = np.empty(4, np.int64)
@@ -432,6 +477,42 @@ def main():
                                                                                 h_b if i & 1 else h_a, cap, resj(i), _lib.OUT_INT32),
                          lambda: n8 + csr + 4 * items_n + (4 * n + 8 * items_n if rec else 0), note_h + (" + " + note_s if rec else ""))
                 two_words(name, items_n)
+            elif name in ("bytes_ids32", "bytes_ids_only"):
+                rec = name == "bytes_ids32"
+                run(name, lambda: ids_blocking(rec), lambda: n8 + csr + 4 * nout.value + (4 * n + 8 * nout.value if rec else 0),
+                    note_i + (" + " + note_s if rec else ""))
+            elif name in ("bytes_ids32_flow", "bytes_ids_only_flow"):
+                rec = name == "bytes_ids32_flow"
+                _lib.check(ids_blocking(rec))
+                items_n = nout.value
+                vh = corpus_vocab().handle
+                run_flow(name, lambda i: lib.latok_flow_token_ids_utf8_bytes(d_u8, d_boff, n, n8, vh, -1, (t_counts if i & 1 else s_counts) if rec else None,
+                                                                             (t_items if i & 1 else s_items) if rec else None,
+                                                                             h_b if i & 1 else h_a, cap, resj(i), _lib.OUT_INT32),
+                         lambda: n8 + csr + 4 * items_n + (4 * n + 8 * items_n if rec else 0), note_i + (" + " + note_s if rec else ""))
+                two_words(name, items_n)
+            elif name == "py_ids":   # host blobs in, host id rows out, both routes in this process
+                from latok_amd import batch
+                m = min(args.py_strings, n)
+                blob = u8[:int(boff[m])].tobytes()
+                blobs = [blob[int(a):int(b)] for a, b in zip(boff[:m], boff[1:m + 1])]
+                distinct = list(dict.fromkeys(t for row in batch.tokenize_utf8_batch(blobs) for t in row))
+                words = distinct[::2] if args.vocab == "half" else distinct
+                d = {w: i for i, w in enumerate(words)}
+                with batch.Vocab(words, seed=SEED) as v:
+                    routes = (("py_token_ids_utf8_batch", lambda: batch.token_ids_utf8_batch(blobs, v)),
+                              ("py_tokenize_utf8_batch_then_dict_get", lambda: [[d.get(t, -1) for t in row] for row in batch.tokenize_utf8_batch(blobs)]))
+                    assert [r.tolist() for r in routes[0][1]()] == routes[1][1]()
+                    for r in range(args.repeat):
+                        for rname, fn in routes:
+                            t = time.perf_counter()
+                            rows = fn()
+                            dt = time.perf_counter() - t
+                            print(json.dumps({"path": rname, "workload": args.workload, "strings": m, "utf8_bytes": len(blob), "vocab": args.vocab,
+                                              "words": len(words), "tokens": sum(map(len, rows)), "ms_per_call": dt * 1e3,
+                                              "utf8_GBps": len(blob) / dt / 1e9,
+                                              "note": "end to end in Python: list[bytes] in, one id row per string out, pack and host work included",
+                                              "repeat": r}), flush=True)
             else:   # py_join: host blobs in, host rows out, both routes in this process
                 from latok_amd import batch
                 m = min(args.py_strings, n)
@@ -449,6 +530,8 @@ def main():
                                           "out_bytes": sum(map(len, rows)), "ms_per_call": dt * 1e3, "utf8_GBps": len(blob) / dt / 1e9,
                                           "note": "end to end in Python: list[bytes] in, list[bytes] out, pack and host slicing included",
                                           "repeat": r}), flush=True)
+        if vocab_box:
+            vocab_box[0].close()
         for p_ in jb:
             lib.latok_dev_free(p_)
     if "rules_mask" in paths:
