@@ -286,6 +286,52 @@ int latok_token_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_of
                                      int64_t* spans_out /* may be NULL */, int32_t* ids_out, int64_t cap, int64_t* n_tokens_out,
                                      int flags, void* stream);
 
+/* Token counting in byte space: the vocabulary of a corpus -- every distinct token with its frequency -- built on the device.
+ * The tokens of a batch are the byte slices latok_token_spans_utf8_bytes_batch reports for it (default_tokenizer.py:149-160);
+ * run-time rule tables and malformed bytes are taken as that call takes them, and bytes are compared verbatim.  A COUNTER is a
+ * mutable device object with three fixed properties: max_word_bytes in 1 .. 256 (another value is refused before any device work;
+ * there is no form for longer words), a table of n_slots = a power of two >= 2 max_words and >= 64 (max_words in 1 .. 2^30), and
+ * a 32-bit seed (of the MurmurHash3 x86_32 that places a word; it changes no count).  After any sequence of updates:
+ *   count[w]  = number of tokens equal to w, byte for byte, over all updates, for every word w the counter holds
+ *   tokens    = counted + long + dropped, always
+ *   long      = tokens of more than max_word_bytes bytes: tallied, never entered
+ *   dropped   = tokens that found neither their word nor a free slot within the probe bound (128 slots, or n_slots if smaller)
+ *   distinct  = words held
+ * dropped = 0 means the counter holds exactly the distinct tokens of at most max_word_bytes bytes, with exact counts; at
+ * most max_words distinct words in a table of 2 max_words slots drop only if 128 occupied slots lie in a row, which at that load
+ * has a probability of about 1e-11 per slot: not in practice, but it is the stats that say so, not the sizing.  dropped > 0 means every held count is a lower bound and
+ * no held word is missing from the text.  Exact as the ids call is: the hash finds the slot, the bytes decide.  The order in which
+ * latok_counter_read lists the words is unspecified (it depends on which thread wins a slot); everything else is deterministic.
+ * latok_counter_create makes an empty counter on the device of the current context.  latok_counter_info needs no device; any
+ * output pointer may be NULL; stats5 = {tokens, counted, long, dropped, distinct}, totals over all updates.  latok_counter_clear
+ * empties the counter.  latok_counter_destroy drains the current context (its stream and its flow) first, like latok_vocab_destroy, and
+ * frees the counter whatever the drain reports.
+ * The update call follows latok_token_ids_utf8_bytes_batch in everything that is not the counting: host pointers or
+ * LATOK_DEVICE_PTRS (device UTF-8 pointer 16-byte aligned), total_bytes = -1 accepted; any other flag bit, LATOK_OUT_INT32 included,
+ * is refused before any device work, and so are a NULL counter, a counter on another device than the current context's, a counter
+ * in the failed state and a batch of 2^39 bytes or more.  n_str = 0 or total_bytes = 0 leaves the counter untouched and zeroes
+ * stats4_out = {tokens, counted, long, dropped} of THIS call (may be NULL).  Every batch size takes the same kernels.  When the call
+ * returns, the counter holds copies of its words: the caller's text may be overwritten or freed.
+ * Calls on one counter are serialised by a lock inside it; two contexts of one device may share it.  The object is NOT immutable,
+ * so there is no flow form: two batches in flight would race on the table's state.
+ * FAILED STATE: if an update fails after its counting kernel was enqueued and before its words were copied (a HIP error, no memory
+ * for the words), the counter is marked failed: every later call on it except latok_counter_clear and latok_counter_destroy
+ * returns LATOK_ERR_INVALID.
+ * latok_counter_read takes HOST pointers and the capacity protocol of the siblings: cap = 0, bytes_cap = 0 with NULL buffers is a
+ * size query; if either capacity is too small nothing is written but *n_words_out and *n_bytes_out, and the call returns
+ * LATOK_ERR_INVALID.  words_out / word_off_out have exactly the layout latok_vocab_create takes (the words back to back,
+ * word_off_out[n_words + 1] from 0), counts_out[i] is the count of word i. */
+typedef struct latok_counter latok_counter;
+int latok_counter_create(int64_t max_words, int max_word_bytes, uint32_t seed, latok_counter** out);
+int latok_counter_destroy(latok_counter* counter);
+int latok_counter_clear(latok_counter* counter);
+int latok_counter_info(const latok_counter* counter, int64_t* max_words, int64_t* n_slots, int* max_word_bytes, uint32_t* seed,
+                       int* device, int64_t* stats5);
+int latok_count_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                        latok_counter* counter, int64_t* stats4_out /* may be NULL */, int flags, void* stream);
+int latok_counter_read(const latok_counter* counter, uint8_t* words_out, int64_t bytes_cap, int64_t* word_off_out /* [cap+1] */,
+                       uint64_t* counts_out, int64_t cap, int64_t* n_words_out, int64_t* n_bytes_out);
+
 /* Token feature vectors: reference featurize() (default_tokenizer.py:163-191) for a whole batch without the n x 25
  * matrix.  Per kept token k: spans4_out[4k..4k+3] = {raw_start, raw_end, strip_start, strip_end} (LaToken.start_idx /
  * end_idx are the raw span, LaToken.text is text[strip_start:strip_end]); features_out[25k..25k+24] = sum of the 25

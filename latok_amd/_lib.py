@@ -55,6 +55,12 @@ SIGNATURES = {
     "latok_vocab_destroy": (ci, [vp]),
     "latok_vocab_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint32), C.POINTER(ci)]),
     "latok_token_ids_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, vp, vp, vp, i64, C.POINTER(i64), ci, vp]),
+    "latok_counter_create": (ci, [i64, ci, C.c_uint32, C.POINTER(vp)]),
+    "latok_counter_destroy": (ci, [vp]),
+    "latok_counter_clear": (ci, [vp]),
+    "latok_counter_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(ci), C.POINTER(C.c_uint32), C.POINTER(ci), vp]),
+    "latok_count_tokens_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, vp, ci, vp]),
+    "latok_counter_read": (ci, [vp, vp, i64, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
     "latok_token_features_batch": (ci, [vp, vp, i64, i64, vp, vp, vp, i64, C.POINTER(i64), ci, vp]),
     "latok_split_mask_kind_batch": (ci, [vp, ci, vp, i64, i64, vp, ci, vp]),
     "latok_split_offsets_kind_batch": (ci, [vp, ci, vp, i64, i64, vp, vp, i64, C.POINTER(i64), ci, vp]),

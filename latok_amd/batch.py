@@ -649,6 +649,131 @@ def token_ids_batch(texts, vocab, unk_id=-1):
     return token_ids_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], vocab, unk_id)
 
 
+# token counts: the vocabulary of a corpus -- every distinct token with its frequency --, counted on the device, exactly
+class TokenCounter:
+    """A counting table on the device of the current context (``latok_counter_create``): at most about ``max_words`` distinct
+    tokens (the table has ``n_slots`` >= 2 * max_words slots), each of at most ``max_word_bytes`` bytes (1 .. 256; longer tokens
+    are tallied as ``long``), placed by MurmurHash3 with ``seed``.  ``update*`` count the tokens of a batch -- the byte slices
+    token_spans_utf8_bytes_csr reports -- and return that call's ``{tokens, counted, long, dropped}``; ``stats`` are the totals
+    with ``distinct``.  ``dropped == 0`` means every count is exact.  Mutable, so it has no flow form.  Freed by ``close()``, on
+    leaving a ``with`` block, or with the object."""
+
+    STATS = ("tokens", "counted", "long", "dropped", "distinct")
+
+    def __init__(self, max_words, max_word_bytes=256, seed=0):
+        self.handle = None
+        seed = _seed32(seed)
+        for name, v, hi in (("max_words", max_words, 1 << 30), ("max_word_bytes", max_word_bytes, 256)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 1 <= int(v) <= hi:
+                raise ValueError("%s must be an int in 1 .. %d" % (name, hi))
+        lib = _lib.ensure_init()
+        h = C.c_void_p()
+        _lib.check(lib.latok_counter_create(int(max_words), int(max_word_bytes), seed, C.byref(h)))
+        self._lib, self.handle, self.seed = lib, h, seed
+        self.max_words, self.max_word_bytes = int(max_words), int(max_word_bytes)
+        n_slots = C.c_int64(0)
+        _lib.check(lib.latok_counter_info(h, None, C.byref(n_slots), None, None, None, None))
+        self.n_slots = n_slots.value
+
+    def _open(self):
+        if not self.handle:
+            raise ValueError("the TokenCounter is closed")
+        return self.handle
+
+    def update_utf8_csr(self, utf8, byte_off):
+        """count the tokens of a CSR batch of UTF-8 bytes; returns this call's {tokens, counted, long, dropped}"""
+        utf8, byte_off = _csr_u8(utf8, byte_off)
+        h = self._open()
+        n_str = byte_off.size - 1
+        total = int(byte_off[-1]) if n_str > 0 else 0
+        st = np.zeros(4, np.int64)
+        _lib.check(self._lib.latok_count_tokens_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, h, _ptr(st), 0, None))
+        return dict(zip(self.STATS[:4], map(int, st)))
+
+    def update_utf8(self, blobs):
+        """list[bytes] (UTF-8)"""
+        self._open()
+        return self.update_utf8_csr(*pack_utf8(blobs))
+
+    def update(self, texts):
+        """list[str]; the strings go through UTF-8 ("surrogatepass") on the host"""
+        return self.update_utf8([t.encode("utf-8", "surrogatepass") for t in texts])
+
+    @property
+    def stats(self):
+        h = self._open()
+        st = np.zeros(5, np.int64)
+        _lib.check(self._lib.latok_counter_info(h, None, None, None, None, None, _ptr(st)))
+        return dict(zip(self.STATS, map(int, st)))
+
+    def items(self):
+        """(list[bytes], uint64 array): the words held and their counts, in no particular order"""
+        h = self._open()
+        n, nb = C.c_int64(0), C.c_int64(0)
+        rc = self._lib.latok_counter_read(h, None, 0, None, None, 0, C.byref(n), C.byref(nb))   # the size query
+        if rc != _lib.OK and not (rc == _lib.ERR_INVALID and n.value > 0):
+            _lib.check(rc)
+        if n.value == 0:
+            return [], np.zeros(0, np.uint64)
+        words, off, counts = np.empty(nb.value, np.uint8), np.empty(n.value + 1, np.int64), np.empty(n.value, np.uint64)
+        _lib.check(self._lib.latok_counter_read(h, _ptr(words), nb.value, _ptr(off), _ptr(counts), n.value, C.byref(n), C.byref(nb)))
+        raw = words.tobytes()
+        return [raw[off[i]:off[i + 1]] for i in range(n.value)], counts
+
+    def most_common(self, n=None):
+        """[(word bytes, count)] sorted by (-count, bytes): deterministic; the first ``n`` if given"""
+        words, counts = self.items()
+        ranked = sorted(zip(words, map(int, counts)), key=lambda wc: (-wc[1], wc[0]))
+        return ranked if n is None else ranked[:n]
+
+    def to_vocab(self, min_count=1, max_size=None, seed=0):
+        """a ``Vocab`` of the words counted at least ``min_count`` times, at most ``max_size`` of them; a word's id is its rank
+        in ``most_common()``"""
+        seed = _seed32(seed)
+        return Vocab([w for w, c in self.most_common(max_size) if c >= min_count], seed=seed)
+
+    def clear(self):
+        h = self._open()
+        _lib.check(self._lib.latok_counter_clear(h))
+
+    def close(self):
+        if self.handle:
+            h, self.handle = self.handle, None
+            _lib.check(self._lib.latok_counter_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def count_tokens_utf8_batch(blobs, max_words=None):
+    """list[bytes] (UTF-8) -> ``collections.Counter`` of the batch's tokens (as bytes), counted on the device.  ``max_words``
+    defaults to the byte total (at most 2**30): a token has at least one byte, so the table is at most half full and does not
+    drop in practice (a drop needs 128 occupied slots in a row, about 1e-11 per slot at that load).  That default is sized for
+    the worst case, not for text: it costs 32 bytes of device memory per input byte, rounded up to a power of two (4 GiB for a
+    100 MB batch) -- pass ``max_words`` (about the number of distinct tokens expected) for anything large, or keep a
+    ``TokenCounter`` and check ``stats["dropped"]``.  A ``dropped`` count other than 0 raises ``RuntimeError`` here, since
+    the Counter would not be exact.  Tokens of more than 256 bytes are not counted."""
+    import collections
+    total = sum(len(b) for b in blobs)
+    if max_words is None:
+        max_words = min(max(total, 1), 1 << 30)
+    with TokenCounter(max_words) as tc:
+        if total and tc.update_utf8(blobs)["dropped"]:
+            raise RuntimeError("count_tokens_utf8_batch: max_words=%d is too small for this batch, tokens were dropped" % max_words)
+        words, counts = tc.items()
+    return collections.Counter(dict(zip(words, map(int, counts))))
+
+
 # ---- PEP 393 code units: 1 / 2 / 4 bytes per char, the buffer the reference itself reads (latok.c:53-55,79) -----------
 def pack_kind(texts):
     """list[str] -> (units, row_off): units uint8 / uint16 / uint32 = the narrowest PEP 393 kind that holds every char of

@@ -30,6 +30,7 @@
 #include "kernels.h"
 #include "unicode_tables.inc"
 #include "vocab_table.h"
+#include "count_table.h"
 
 static_assert(LATOK_TBL_SHIFT == latok::kTblShift, "table shift");
 static_assert(LATOK_TBL_STAGE1_LEN == latok::kStage1Len, "stage-1 length");
@@ -2322,6 +2323,339 @@ int latok_token_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_of
     return LATOK_OK;
 }
 
+/* token counting in byte space: a mutable, exact counting table on the device (count_table.h), filled by k_count_scatter and made
+ * independent of the caller's text by the two commit launches before the call returns.  One stream:
+ *   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
+ *   k_word_counts + k_scan_chained                kept mask, token ranks; THE token total -> scalar word 0, pinned word 0
+ *   k_count_scatter                               every token found or entered (fresh slots point into the text), counted
+ *   k_count_commit_sum                            padded dwords of the fresh slots; the host waits, reads, grows the blob if needed
+ *   k_count_commit_copy                           fresh words into the blob, resident slot words
+ * `w` is sized by ws_needs with WsShape{.spans = true}: the spans shape, no buffer beyond it. */
+struct Counter {                   // latok_counter: mutable; calls on it are serialised by its own lock
+    std::mutex mu;
+    int device = -1;
+    int64_t max_words = 0;
+    uint64_t n_slots = 0;
+    int max_word_bytes = 0;
+    uint32_t seed = 0;
+    void* d_slots = nullptr;       // uint64[n_slots]
+    void* d_counts = nullptr;      // uint64[n_slots]
+    void* d_blob = nullptr;        // uint32[blob_dwords]; dword 0 is reserved
+    uint64_t blob_dwords = 0;
+    uint64_t cursor = 1;           // dwords of the blob in use
+    void* d_ctl = nullptr;         // uint64[8]: {counted, long, dropped, -, fresh dwords, cursor, distinct, overflow}
+    int64_t totals[4] = {0, 0, 0, 0};   // tokens, counted, long, dropped over all updates
+    int64_t distinct = 0;
+    int64_t grown = 0;             // times the blob was reallocated (latok_debug_counter_state)
+    bool failed = false;           // a call ended between k_count_scatter and the end of its commit: fresh slots may remain
+};
+static latok::CountTable count_table_of(const Counter& c) {
+    latok::CountTable t;
+    t.slots = (uint64_t*)c.d_slots;
+    t.counts = (unsigned long long*)c.d_counts;
+    t.blob = (uint32_t*)c.d_blob;
+    t.blob_dwords = c.blob_dwords;
+    t.n_slots = c.n_slots;
+    t.seed = c.seed;
+    t.max_word_bytes = c.max_word_bytes;
+    t.tally = (unsigned long long*)c.d_ctl;
+    t.ctl = (unsigned long long*)c.d_ctl + 4;
+    return t;
+}
+static void counter_free(Counter* c) {
+    for (void* p : {c->d_slots, c->d_counts, c->d_blob, c->d_ctl})
+        if (p) (void)hipFree(p);
+    delete c;
+}
+// empty table, empty blob, zero totals (the device part on `st`, waited for)
+static int counter_reset(Counter& c, hipStream_t st) {
+    const uint64_t ctl[8] = {0, 0, 0, 0, 0, 1, 0, 0};
+    HIP_TRY(hipMemsetAsync(c.d_slots, 0, c.n_slots * 8, st));
+    HIP_TRY(hipMemsetAsync(c.d_counts, 0, c.n_slots * 8, st));
+    HIP_TRY(hipMemsetAsync(c.d_blob, 0, 4, st));
+    HIP_TRY(hipMemcpyAsync(c.d_ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c.cursor = 1;
+    c.distinct = 0;
+    for (int64_t& t : c.totals) t = 0;
+    c.failed = false;
+    return LATOK_OK;
+}
+// the counter of a call: there is one, it lives on the device of the context that runs the call, and it is not failed
+static int check_counter(const Ctx& g, const Counter& c) {
+    if (c.device != g.device)
+        return fail(LATOK_ERR_INVALID, "the counter lives on device %d, the current context on device %d", c.device, g.device);
+    if (c.failed) return fail(LATOK_ERR_INVALID, "the counter is in the failed state (an update did not finish): latok_counter_clear it");
+    return LATOK_OK;
+}
+
+int latok_counter_create(int64_t max_words, int max_word_bytes, uint32_t seed, latok_counter** out) {
+    LATOK_ENTER();
+    // what needs no device is refused first
+    if (!out) return fail(LATOK_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (max_words < 1 || max_words > (1ll << 30)) return fail(LATOK_ERR_INVALID, "max_words must be in 1 .. 2^30");
+    if (max_word_bytes < 1 || max_word_bytes > latok::kHashWaveBytes)
+        return fail(LATOK_ERR_INVALID, "max_word_bytes must be in 1 .. %d", latok::kHashWaveBytes);
+    static_assert(latok::kHashWaveBytes <= kCtMaxWordBytes, "a slot word holds length - 1 in 8 bits");
+    int rc = need_init(g);
+    if (rc) return rc;
+    Counter* c = nullptr;
+    try {
+        c = new Counter();
+    } catch (const std::bad_alloc&) {
+        return fail(LATOK_ERR_NOMEM, "out of host memory");
+    }
+    c->device = g.device;
+    c->max_words = max_words;
+    c->n_slots = ct_slot_count(max_words);
+    c->max_word_bytes = max_word_bytes;
+    c->seed = seed;
+    // the blob starts at 8 bytes per word and grows by need (every commit knows its need before it copies)
+    c->blob_dwords = std::max<uint64_t>(64, 2 * (uint64_t)max_words);
+    hipError_t e = hipMalloc(&c->d_slots, c->n_slots * 8);
+    if (e == hipSuccess) e = hipMalloc(&c->d_counts, c->n_slots * 8);
+    if (e == hipSuccess) e = hipMalloc(&c->d_blob, c->blob_dwords * 4);
+    if (e == hipSuccess) e = hipMalloc(&c->d_ctl, 64);
+    if (e != hipSuccess) {
+        counter_free(c);
+        return fail(LATOK_ERR_NOMEM, "hipMalloc of a counter of %lld slots failed: %s", (long long)ct_slot_count(max_words), hipGetErrorString(e));
+    }
+    if ((rc = counter_reset(*c, g.stream))) {
+        counter_free(c);
+        return rc;
+    }
+    *out = reinterpret_cast<latok_counter*>(c);
+    return LATOK_OK;
+}
+
+int latok_counter_destroy(latok_counter* counter) {
+    LATOK_ENTER();
+    Counter* c = reinterpret_cast<Counter*>(counter);
+    if (!c) return LATOK_OK;
+    int rc = LATOK_OK;
+    if (g.inited) {   // the current context's own work: its stream and its flow; whatever they report, the counter is freed
+        const hipError_t e = hipStreamSynchronize(g.stream);
+        rc = flow_drain(g);
+        if (e != hipSuccess) rc = fail(LATOK_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    }
+    { std::lock_guard<std::mutex> cl(c->mu); }   // (a call of another context that still holds it has returned)
+    counter_free(c);
+    return rc;
+}
+
+int latok_counter_clear(latok_counter* counter) {
+    LATOK_ENTER();
+    Counter* c = reinterpret_cast<Counter*>(counter);
+    if (!c) return fail(LATOK_ERR_INVALID, "counter is NULL");
+    int rc = need_init(g);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> cl(c->mu);
+    if (c->device != g.device)
+        return fail(LATOK_ERR_INVALID, "the counter lives on device %d, the current context on device %d", c->device, g.device);
+    return counter_reset(*c, g.stream);
+}
+
+int latok_counter_info(const latok_counter* counter, int64_t* max_words, int64_t* n_slots, int* max_word_bytes, uint32_t* seed, int* device,
+                       int64_t* stats5) {
+    Counter* c = const_cast<Counter*>(reinterpret_cast<const Counter*>(counter));
+    if (!c) return fail(LATOK_ERR_INVALID, "counter is NULL");
+    std::lock_guard<std::mutex> cl(c->mu);
+    if (max_words) *max_words = c->max_words;
+    if (n_slots) *n_slots = (int64_t)c->n_slots;
+    if (max_word_bytes) *max_word_bytes = c->max_word_bytes;
+    if (seed) *seed = c->seed;
+    if (device) *device = c->device;
+    if (stats5) {
+        for (int i = 0; i < 4; ++i) stats5[i] = c->totals[i];
+        stats5[4] = c->distinct;
+    }
+    return LATOK_OK;
+}
+
+// everything of an update from k_count_scatter on: a failure in here leaves the counter failed (the caller sets the flag)
+static int count_scatter_and_commit(Ctx& g, Workspace& w, Counter& c, const Batch& d, int64_t* p_tot, const volatile int64_t* h_tot,
+                                    int64_t* stats4, hipStream_t st) {
+    const int64_t total = d.total, words = (total + 63) / 64;
+    uint64_t ctl[8];
+    latok::CountTable t = count_table_of(c);
+    HIP_TRY(latok::launch_count_scatter((const uint8_t*)d.in.p, t, (const uint64_t*)w.bits.p, (const uint64_t*)w.space.p, (const uint64_t*)w.kept.p,
+                                        (const int64_t*)w.bases.p, (const int64_t*)w.wcnt.p, (const uint16_t*)w.wpref.p, words, total, d.row,
+                                        d.n_str, (const int64_t*)w.tile_first.p, (const int64_t*)w.scalar.p, (int*)(p_tot + 1), st));
+    HIP_TRY(latok::launch_count_commit_sum(t, st));
+    HIP_TRY(hipMemcpyAsync(ctl, c.d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the first of the call's two waits: the commit's need is known
+    int rc;
+    int64_t n = 0;
+    if ((rc = finish_totals(w, h_tot, 0, &n))) return rc;
+    const uint64_t need = c.cursor + ctl[4];
+    if (need >= (1ull << 32)) return fail(LATOK_ERR_NOMEM, "the counter's words would take 2^34 bytes or more");
+    if (need > c.blob_dwords) {          // grow: new allocation, device copy, free
+        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(need, 2 * c.blob_dwords), (1ull << 32) - 1);
+        void* p = nullptr;
+        hipError_t e = hipMalloc(&p, want * 4);
+        if (e != hipSuccess) return fail(LATOK_ERR_NOMEM, "hipMalloc(%llu) failed: %s", (unsigned long long)(want * 4), hipGetErrorString(e));
+        e = hipMemcpyAsync(p, c.d_blob, c.cursor * 4, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return fail(LATOK_ERR_HIP, "copying the counter's words failed: %s", hipGetErrorString(e));
+        }
+        (void)hipFree(c.d_blob);
+        c.d_blob = p;
+        c.blob_dwords = want;
+        ++c.grown;
+        t = count_table_of(c);
+    }
+    if (ctl[4] > 0) {                    // (no fresh slot: nothing to copy, the table is resident already)
+        HIP_TRY(latok::launch_count_commit_copy((const uint8_t*)d.in.p, t, st));
+        HIP_TRY(hipMemcpyAsync(ctl, c.d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (ctl[7] != 0 || ctl[5] != need) return fail(LATOK_ERR_HIP, "internal: the commit of the counter's words did not add up");
+    }
+    c.cursor = need;
+    c.distinct = (int64_t)ctl[6];
+    stats4[0] = n;
+    stats4[1] = (int64_t)ctl[0];
+    stats4[2] = (int64_t)ctl[1];
+    stats4[3] = (int64_t)ctl[2];
+    for (int i = 0; i < 4; ++i) c.totals[i] += stats4[i];
+    return LATOK_OK;
+}
+
+int latok_count_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, latok_counter* counter,
+                                        int64_t* stats4_out, int flags, void* stream) {
+    LATOK_ENTER();
+    if (flags & ~LATOK_DEVICE_PTRS) return fail(LATOK_ERR_INVALID, "unknown flag (the counting call takes LATOK_DEVICE_PTRS only)");
+    Counter* c = reinterpret_cast<Counter*>(counter);
+    if (!c) return fail(LATOK_ERR_INVALID, "counter is NULL");
+    int rc = need_init(g);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> cl(c->mu);
+    if ((rc = check_counter(g, *c))) return rc;
+    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0;
+    int64_t total = total_bytes;
+    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
+    StreamTurn turn(g, stream);
+    hipStream_t st = turn.st;
+    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
+    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (total >= kCtMaxTextBytes) return fail(LATOK_ERR_INVALID, "a counting batch must be shorter than 2^39 bytes");
+    int64_t stats4[4] = {0, 0, 0, 0};
+    if (stats4_out) memcpy(stats4_out, stats4, sizeof(stats4));
+    if (n_str == 0 || total == 0) return LATOK_OK;   // no byte, no token: the counter is untouched
+    if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    g.last_route = 8;
+    Batch d;
+    if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
+    if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+    int64_t* p_tot = (int64_t*)g.pin_tot.d;
+    h_tot[0] = h_tot[1] = 0;
+    Workspace& w = g.ws;
+    unsigned epoch = 0;
+    Pipe p;
+    p.b = d;
+    p.bits = (uint64_t*)w.bits.p;
+    p.space = (uint64_t*)w.space.p;
+    p.st = st;
+    HIP_TRY(hipMemsetAsync(c->d_ctl, 0, 40, st));                    // this call's tallies and fresh dwords
+    HIP_TRY(hipMemsetAsync((uint64_t*)c->d_ctl + 7, 0, 8, st));      // ... and the overflow flag
+    if ((rc = run_pipeline(g, w, p))) return rc;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    HIP_TRY(latok::launch_word_counts_scan(true, p.bits, p.space, (total + 63) / 64, total, (uint64_t*)w.kept.p, (int64_t*)w.wcnt.p,
+                                           (uint16_t*)w.wpref.p, (int64_t*)w.bases.p, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p,
+                                           epoch, (int64_t*)w.scalar.p, p_tot, (int*)(p_tot + 1) + 1, st));
+    // from here to the end of the commit the table may hold slots that point into the caller's text
+    if ((rc = count_scatter_and_commit(g, w, *c, d, p_tot, h_tot, stats4, st))) {
+        c->failed = true;
+        (void)hipStreamSynchronize(st);   // (nothing of this call is still running when the caller gets its text back)
+        return rc;
+    }
+    if (stats4_out) memcpy(stats4_out, stats4, sizeof(stats4));
+    return LATOK_OK;
+}
+
+int latok_counter_read(const latok_counter* counter, uint8_t* words_out, int64_t bytes_cap, int64_t* word_off_out, uint64_t* counts_out,
+                       int64_t cap, int64_t* n_words_out, int64_t* n_bytes_out) {
+    LATOK_ENTER();
+    Counter* c = const_cast<Counter*>(reinterpret_cast<const Counter*>(counter));
+    if (!c) return fail(LATOK_ERR_INVALID, "counter is NULL");
+    if (!n_words_out || !n_bytes_out) return fail(LATOK_ERR_INVALID, "the total-size output pointers are NULL");
+    *n_words_out = *n_bytes_out = 0;
+    if (cap < 0 || bytes_cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
+    if (cap > 0 && (!word_off_out || !counts_out)) return fail(LATOK_ERR_INVALID, "word_off_out or counts_out is NULL but cap > 0 (a size query passes cap = 0)");
+    if (bytes_cap > 0 && !words_out) return fail(LATOK_ERR_INVALID, "words_out is NULL but bytes_cap > 0");
+    int rc = need_init(g);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> cl(c->mu);
+    if ((rc = check_counter(g, *c))) return rc;
+    // not a hot path: slots, counts and blob come to the host and are compacted here, in slot order
+    std::vector<uint64_t> slots, counts;
+    std::vector<uint32_t> blob;
+    try {
+        slots.resize(c->n_slots);
+    } catch (const std::bad_alloc&) {
+        return fail(LATOK_ERR_NOMEM, "out of host memory");
+    }
+    HIP_TRY(hipMemcpyAsync(slots.data(), c->d_slots, c->n_slots * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    int64_t n_words = 0, n_bytes = 0;
+    for (const uint64_t v : slots) {
+        if (v == kCtEmpty) continue;
+        if (ct_is_fresh(v) || ct_pos(v) + ct_padded_dwords(v) > c->cursor) return fail(LATOK_ERR_HIP, "internal: a slot of the counter is not resident");
+        ++n_words;
+        n_bytes += ct_len(v);
+    }
+    *n_words_out = n_words;
+    *n_bytes_out = n_bytes;
+    if (n_words > cap || n_bytes > bytes_cap)
+        return fail(LATOK_ERR_INVALID, "capacity too small: need %lld words and %lld bytes", (long long)n_words, (long long)n_bytes);
+    if (word_off_out) word_off_out[0] = 0;
+    if (n_words == 0) return LATOK_OK;
+    try {
+        counts.resize(c->n_slots);
+        blob.resize(c->cursor);
+    } catch (const std::bad_alloc&) {
+        return fail(LATOK_ERR_NOMEM, "out of host memory");
+    }
+    HIP_TRY(hipMemcpyAsync(counts.data(), c->d_counts, c->n_slots * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(blob.data(), c->d_blob, c->cursor * 4, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    int64_t k = 0, at = 0;
+    for (uint64_t i = 0; i < c->n_slots; ++i) {
+        const uint64_t v = slots[i];
+        if (v == kCtEmpty) continue;
+        const int64_t len = ct_len(v);
+        memcpy(words_out + at, reinterpret_cast<const uint8_t*>(blob.data() + ct_pos(v)), (size_t)len);
+        at += len;
+        counts_out[k] = counts[i];
+        word_off_out[++k] = at;
+    }
+    return LATOK_OK;
+}
+
+/* test hooks (not part of the ABI in include/latok_hip.h): out[0..3] = capacity of the counter's blob in dwords, dwords in use,
+ * times the blob was reallocated, 1 if the counter is in the failed state; and: put the counter into the failed state, as an
+ * update that did not finish its commit would */
+extern "C" int latok_debug_counter_state(const latok_counter* counter, int64_t* out4) {
+    Counter* c = const_cast<Counter*>(reinterpret_cast<const Counter*>(counter));
+    if (!c || !out4) return fail(LATOK_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> cl(c->mu);
+    out4[0] = (int64_t)c->blob_dwords;
+    out4[1] = (int64_t)c->cursor;
+    out4[2] = c->grown;
+    out4[3] = c->failed ? 1 : 0;
+    return LATOK_OK;
+}
+extern "C" int latok_debug_counter_fail(latok_counter* counter) {
+    Counter* c = reinterpret_cast<Counter*>(counter);
+    if (!c) return fail(LATOK_ERR_INVALID, "counter is NULL");
+    std::lock_guard<std::mutex> cl(c->mu);
+    c->failed = true;
+    return LATOK_OK;
+}
+
 /* PEP 393 buffers (the reference's own input, latok.c:53-55,79): fixed-width code units of 1, 2 or 4 bytes */
 static int check_kind(int kind) {
     if (kind != 1 && kind != 2 && kind != 4) return fail(LATOK_ERR_INVALID, "kind must be 1 (Latin-1), 2 (UCS-2) or 4 (UCS-4), got %d", kind);
@@ -2670,14 +3004,15 @@ int latok_debug_set_scan_epoch(unsigned epoch) {
  * kSmallChars, kSmallStrings, tiles per workgroup of k_lead_compress; out[9..13] = kFeatWaves, kFeatRound, kFeatRoundTm,
  * kFeatFormThresh, kFeatWinBytes of k_features_tiles; out[14] = kHashWaveBytes (a longer token is hashed by its whole wave);
  * out[15..16] = kScanSmallMax (more entries: the exclusive scan takes three launches), kU8Block (bytes per block of the staged
- * UTF-8 decoder, one scan entry each).  Returns the number of values written. */
+ * UTF-8 decoder, one scan entry each); out[17..18] = kCountProbeMax (steps after which a probe of a counting table gives up),
+ * kCountAccEntries (entries of a wave's count accumulator in k_count_scatter).  Returns the number of values written. */
 extern "C" int latok_debug_limits(int64_t* out, int n) {
-    const int64_t v[17] = {latok::kTile, latok::kWPB, latok::kNarrowWPB, latok::kSegMax, latok::kOneSegTiles, latok::kFastTailTiles,
+    const int64_t v[19] = {latok::kTile, latok::kWPB, latok::kNarrowWPB, latok::kSegMax, latok::kOneSegTiles, latok::kFastTailTiles,
                            kSmallChars, kSmallStrings, latok::kCompressWaves, latok::kFeatWaves, latok::kFeatRound, latok::kFeatRoundTm,
                            latok::kFeatFormThresh, latok::kFeatWinBytes, latok::kHashWaveBytes, latok::scan_small_max(),
-                           latok::utf8_block_bytes()};
+                           latok::utf8_block_bytes(), latok::kCountProbeMax, latok::kCountAccEntries};
     if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
-    const int k = n < 17 ? n : 17;
+    const int k = n < 19 ? n : 19;
     for (int i = 0; i < k; ++i) out[i] = v[i];
     return k;
 }

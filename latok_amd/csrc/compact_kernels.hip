@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "bitscan.h"
+#include "count_table.h"
 #include "kernels.h"
 #include "lane_math.h"
 #include "token_hash.h"
@@ -240,6 +241,13 @@ __global__ __launch_bounds__(256) void k_string_counts(const uint64_t* __restric
 // length agree and stores ids[k] = the word's id or unk.  A long token's hash is wave-uniform, so the wave probes in step -- every
 // lane asks for the same slot, one request -- and compares a candidate 64 dwords per step with coalesced loads; a ballot decides.
 // The table and the blob are read with ordinary cached loads (they are what is worth keeping in L2); no hash goes through memory.
+// KIND 5 (k_count_scatter): KIND 4's lane path with a counting table in the vocabulary's place (count_table.h): the lane finds its
+// token's slot or claims an empty one with one CAS -- nothing waits for another thread --, and the hit is counted in a per-wave
+// accumulator in LDS, a direct-mapped {slot + 1, count} array of kCountAccEntries entries: the tag is claimed with an LDS CAS, a
+// hit is an LDS add, a conflicting entry adds to the global count directly.  Behind the tile's last round the wave flushes its
+// entries with no-return atomic adds, so a hot word costs one global atomic per tile, not one per token.  It writes no records.
+// A token of more than max_word_bytes bytes is tallied as long and never entered: there is no whole-wave form.  The three
+// tallies (counted, long, dropped) are reduced over the wave: one atomic each per tile.
 constexpr int scatter_waves(int kind) { return 4; }   // waves per workgroup
 struct HashArgs {
     const uint32_t* text = nullptr;   // the batch's bytes as aligned dwords (the buffer is 16-byte aligned)
@@ -254,6 +262,22 @@ struct VocabArgs {                    // (KIND 4; the text and the seed travel i
     int32_t unk = 0;
 };
 
+struct CountArgs {                    // (KIND 5; the text and the seed travel in HashArgs)
+    uint64_t* slots = nullptr;        // one 8-byte word per slot (count_table.h), 0 = empty
+    unsigned long long* counts = nullptr;
+    const uint32_t* blob = nullptr;   // the resident words, stored by earlier launches
+    uint64_t n_slots = 0;             // a power of two, <= 2^31
+    unsigned long long* tally = nullptr;   // this call's {counted, long, dropped}
+    int max_word_bytes = 0;           // 1 .. kHashWaveBytes
+};
+struct CtDeviceAtomics {              // count_table.h's policy: relaxed, agent scope -- the slot word is the whole message
+    static __device__ __forceinline__ uint64_t load(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    static __device__ __forceinline__ uint64_t cas(uint64_t* p, uint64_t expect, uint64_t v) {
+        __hip_atomic_compare_exchange_strong(p, &expect, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return expect;
+    }
+};
+
 template <int KIND, typename OUT>
 __device__ __forceinline__ void counts_scatter_block(
     const uint64_t* __restrict__ bits, const uint64_t* __restrict__ space, const uint64_t* __restrict__ item_mask,
@@ -262,8 +286,9 @@ __device__ __forceinline__ void counts_scatter_block(
     const int64_t* __restrict__ tile_first, OUT* __restrict__ out, const int64_t* __restrict__ n_items_dev, int64_t cap,
     OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, unsigned vb,     // vb: (virtual) workgroup index
     const HashArgs ha = HashArgs{},                                                              // (KIND 3 and 4 only)
-    const VocabArgs va = VocabArgs{}) {                                                          // (KIND 4 only)
-    constexpr bool kHashes = KIND == 3 || KIND == 4;                                             // records optional, tokens hashed
+    const VocabArgs va = VocabArgs{},                                                            // (KIND 4 only)
+    const CountArgs ca = CountArgs{}) {                                                          // (KIND 5 only)
+    constexpr bool kHashes = KIND == 3 || KIND == 4 || KIND == 5;                                // records optional, tokens hashed
     static_assert(scatter_waves(KIND) * 64 == 256, "both roles use 256-thread workgroups");
     if (vb >= n_scatter_blocks) {   // role 2: one thread per string
         if (counts)
@@ -281,7 +306,10 @@ __device__ __forceinline__ void counts_scatter_block(
     // 0.174 -> 0.165 ms and int32 spans 0.233 -> 0.222 at 7 - 8 workgroups per CU, but int64 spans 0.247 -> 0.256 (twice
     // the store stream per token): that form keeps the footprint that holds it at 4.
     constexpr int kSpan64Buf = 6656;   // int64 spans: 5 workgroups per CU (4: C3 +2.5 %; 7: C2 +4 %)
-    constexpr int kBufBytes = KIND == 0 ? kCodes * (int)sizeof(OUT) : (sizeof(OUT) == 8 ? kSpan64Buf : kCodes * 2 + 64 * 48);
+    constexpr int kAccAt = kCodes * 2 + 64 * 48;                                   // (KIND 5, int32 form) the accumulator lies behind the rows
+    constexpr int kBufBytes = (KIND == 0 ? kCodes * (int)sizeof(OUT) : (sizeof(OUT) == 8 ? kSpan64Buf : kCodes * 2 + 64 * 48)) +
+                              (KIND == 5 ? 8 * kCountAccEntries : 0);
+    static_assert(KIND != 5 || sizeof(OUT) == 4, "the counting form is instantiated for int32 only");
     __shared__ __attribute__((aligned(16))) uint8_t buf_s[kScatterWaves][kBufBytes];
     __shared__ long long smax_s[kScatterWaves][65];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -400,6 +428,12 @@ __device__ __forceinline__ void counts_scatter_block(
         uint64_t* r = rows + 6 * lane;
         r[0] = xb; r[1] = nn; r[2] = xb1; r[3] = nn1; r[4] = Bw; r[5] = (uint64_t)lo_in;
     }
+    // (KIND 5) the wave's accumulator: tags (slot + 1, 0 = free) in the first half, counts in the second; my tallies
+    // (every other kind has neither: the names exist for the `if constexpr (KIND == 5)` blocks below and compile away)
+    [[maybe_unused]] uint32_t* const acc = KIND == 5 ? reinterpret_cast<uint32_t*>(buf_s[wave] + kAccAt) : nullptr;
+    [[maybe_unused]] unsigned n_counted = 0, n_long = 0, n_dropped = 0;
+    if constexpr (KIND == 5)
+        for (int i = lane; i < 2 * kCountAccEntries; i += 64) acc[i] = 0u;   // (visible behind the round's first wave barrier)
     for (int win0 = 0; win0 < n_wave; win0 += kCodes) {
         while (rest && k < win0 + kCodes) {
             const int b = __builtin_ctzll(rest);
@@ -477,7 +511,27 @@ __device__ __forceinline__ void counts_scatter_block(
                     if (kHashes) {
                         h_a = a2;
                         h_e = e2;
-                        if (e2 - a2 <= kHashWaveBytes) {
+                        if constexpr (KIND == 5) {
+                            if (e2 - a2 > ca.max_word_bytes) {
+                                ++n_long;
+                            } else {
+                                const uint32_t* text = ha.text;
+                                const uint32_t* blob = ca.blob;
+                                const uint32_t h = th_hash_lane([text](int64_t i) { return text[i]; }, a2, e2, ha.seed);
+                                const int64_t s = ct_find_or_insert<CtDeviceAtomics>([text](int64_t i) { return text[i]; }, a2, e2, h, ca.slots,
+                                                                                     [blob](uint64_t i) { return blob[i]; }, ca.n_slots,
+                                                                                     (uint32_t)kCountProbeMax);
+                                if (s == kCtDropped) {
+                                    ++n_dropped;
+                                } else {
+                                    ++n_counted;
+                                    const uint32_t tag = (uint32_t)s + 1u, at = (uint32_t)s & (uint32_t)(kCountAccEntries - 1);
+                                    const uint32_t was = atomicCAS(&acc[at], 0u, tag);
+                                    if (was == 0u || was == tag) atomicAdd(&acc[kCountAccEntries + at], 1u);
+                                    else (void)__hip_atomic_fetch_add(ca.counts + s, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                                }
+                            }
+                        } else if (e2 - a2 <= kHashWaveBytes) {
                             const uint32_t* text = ha.text;
                             const uint32_t h = th_hash_lane([text](int64_t i) { return text[i]; }, a2, e2, ha.seed);
                             if (KIND == 3) {
@@ -494,7 +548,7 @@ __device__ __forceinline__ void counts_scatter_block(
                     }
                 }
             }
-            if (kHashes) {
+            if (kHashes && KIND != 5) {
                 // the long tokens of the round, one at a time by the whole wave (wave-uniform loop: `todo` is a ballot)
                 const uint32_t* text = ha.text;
                 auto ld = [text](int64_t i) { return text[i]; };
@@ -540,6 +594,23 @@ __device__ __forceinline__ void counts_scatter_block(
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
+    if constexpr (KIND == 5) {   // the tile is done: flush the accumulator (no-return adds) and the three tallies
+        for (int i = lane; i < kCountAccEntries; i += 64) {
+            const uint32_t tag = acc[i];
+            if (tag) (void)__hip_atomic_fetch_add(ca.counts + (tag - 1u), (unsigned long long)acc[kCountAccEntries + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            n_counted += __shfl_xor(n_counted, d);
+            n_long += __shfl_xor(n_long, d);
+            n_dropped += __shfl_xor(n_dropped, d);
+        }
+        if (lane == 0) {
+            if (n_counted) (void)__hip_atomic_fetch_add(ca.tally + 0, (unsigned long long)n_counted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (n_long) (void)__hip_atomic_fetch_add(ca.tally + 1, (unsigned long long)n_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (n_dropped) (void)__hip_atomic_fetch_add(ca.tally + 2, (unsigned long long)n_dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
 template <int KIND, typename OUT>
@@ -581,6 +652,85 @@ __global__ __launch_bounds__(scatter_waves(4) * 64) void k_vocab_scatter(
     OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, HashArgs ha, VocabArgs va) {
     counts_scatter_block<4, OUT>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str, tile_first, out,
                                  n_items_dev, cap, counts, n_scatter_blocks, err, blockIdx.x, ha, va);
+}
+
+// Token counts: KIND 5 of the body above in a kernel of its own (the kernels above keep their arguments and their code).  No
+// records, no per-string counts: `out` only switches the tile role on, and nothing is gated by a capacity.
+struct CountScatterArgs {
+    const uint64_t* bits; const uint64_t* space; const uint64_t* item_mask;
+    const int64_t* tile_rank; const int64_t* tile_cnt; const uint16_t* word_pref;
+    int64_t n_words, total;
+    const int64_t* row_off; int64_t n_str;
+    const int64_t* tile_first; const int64_t* n_items_dev;
+    unsigned n_scatter_blocks; int* err;
+    HashArgs ha; CountArgs ca;
+};
+__global__ __launch_bounds__(scatter_waves(5) * 64) void k_count_scatter(CountScatterArgs a) {
+    counts_scatter_block<5, int32_t>(a.bits, a.space, a.item_mask, a.tile_rank, a.tile_cnt, a.word_pref, a.n_words, a.total, a.row_off, a.n_str,
+                                     a.tile_first, nullptr, a.n_items_dev, INT64_MAX, nullptr, a.n_scatter_blocks, a.err, blockIdx.x, a.ha,
+                                     VocabArgs{}, a.ca);
+}
+
+// The commit behind k_count_scatter: two launches over the slots, one thread per slot, that make the table independent of the
+// caller's text.  (a) k_count_commit_sum: the padded dwords of the fresh slots, reduced per workgroup, one atomic each -> ctl[0];
+// the host reads it and grows the blob if it has to.  (b) k_count_commit_copy: every workgroup takes its share of the blob with
+// one atomic add on the cursor ctl[1], its fresh slots copy their <= 256 bytes from the text (ct_commit_word) and store their
+// resident word; ctl[2] (distinct) advances by the workgroup's fresh slots.  A share that would leave the blob is not written and
+// raises ctl[3] (the host sized the blob from (a), so this does not happen; the host then fails the counter).
+constexpr int kCommitBlock = 256;
+__device__ __forceinline__ unsigned commit_block_scan(unsigned v, unsigned* total) {   // exclusive prefix of v over the workgroup
+    __shared__ unsigned s_wave[kCommitBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned o = __shfl_up(inc, d);
+        if (lane >= d) inc += o;
+    }
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();
+    unsigned before = 0, all = 0;
+#pragma unroll
+    for (int k = 0; k < kCommitBlock / 64; ++k) {
+        const unsigned x = s_wave[k];
+        if (k < wave) before += x;
+        all += x;
+    }
+    *total = all;
+    return before + inc - v;
+}
+__global__ __launch_bounds__(kCommitBlock) void k_count_commit_sum(const uint64_t* __restrict__ slots, uint64_t n_slots,
+                                                                   unsigned long long* __restrict__ ctl) {
+    const uint64_t i = (uint64_t)blockIdx.x * kCommitBlock + threadIdx.x;
+    const uint64_t v = i < n_slots ? slots[i] : kCtEmpty;
+    unsigned total;
+    (void)commit_block_scan(ct_is_fresh(v) ? ct_padded_dwords(v) : 0u, &total);
+    if (threadIdx.x == 0 && total) (void)__hip_atomic_fetch_add(ctl + 0, (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__global__ __launch_bounds__(kCommitBlock) void k_count_commit_copy(uint64_t* __restrict__ slots, uint64_t n_slots,
+                                                                    const uint32_t* __restrict__ text, uint32_t* __restrict__ blob,
+                                                                    uint64_t blob_dwords, unsigned long long* __restrict__ ctl) {
+    __shared__ unsigned long long s_base;
+    const uint64_t i = (uint64_t)blockIdx.x * kCommitBlock + threadIdx.x;
+    const uint64_t v = i < n_slots ? slots[i] : kCtEmpty;
+    const bool fresh = ct_is_fresh(v);
+    unsigned total, n_fresh;
+    const unsigned before = commit_block_scan(fresh ? ct_padded_dwords(v) : 0u, &total);
+    __syncthreads();                                   // (commit_block_scan's LDS words are read; the second scan writes them again)
+    (void)commit_block_scan(fresh ? 1u : 0u, &n_fresh);
+    if (total == 0) return;                            // (uniform)
+    if (threadIdx.x == 0) {
+        s_base = __hip_atomic_fetch_add(ctl + 1, (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_add(ctl + 2, (unsigned long long)n_fresh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!fresh) return;
+    const uint64_t at = s_base + before;
+    if (at + ct_padded_dwords(v) > blob_dwords) {      // never with a blob sized from k_count_commit_sum
+        ctl[3] = 1ull;
+        return;
+    }
+    slots[i] = ct_commit_word([text](int64_t k) { return text[k]; }, v, at, [blob](uint64_t k, uint32_t w) { blob[k] = w; });
 }
 
 // ---- code-point results of a UTF-8 batch from its BYTE-space results ------------------------------------------------------
@@ -1281,6 +1431,42 @@ hipError_t launch_vocab_scatter(bool out32, const uint8_t* u8, const VocabTable&
     else
         hipLaunchKernelGGL((k_vocab_scatter<int64_t>), grid, block, 0, st, bits, space, kept, tile_rank, tile_cnt, word_pref, n_words, total,
                            row_off, n_str, tile_first, (int64_t*)out, n_items_dev, cap, (int64_t*)counts, nb_scatter, err, ha, va);
+    return hipGetLastError();
+}
+
+// token counts (KIND 5): every token of the batch found or entered in the counting table and counted; no output but the table
+hipError_t launch_count_scatter(const uint8_t* u8, const CountTable& ct, const uint64_t* bits, const uint64_t* space, const uint64_t* kept,
+                                const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, int64_t total,
+                                const int64_t* row_off, int64_t n_str, const int64_t* tile_first, const int64_t* n_items_dev, int* err,
+                                hipStream_t st) {
+    if (n_words <= 0) return hipSuccess;
+    CountScatterArgs a;
+    a.bits = bits; a.space = space; a.item_mask = kept;
+    a.tile_rank = tile_rank; a.tile_cnt = tile_cnt; a.word_pref = word_pref;
+    a.n_words = n_words; a.total = total;
+    a.row_off = row_off; a.n_str = n_str;
+    a.tile_first = tile_first; a.n_items_dev = n_items_dev;
+    a.n_scatter_blocks = (unsigned)((n_words + 255) / 256);
+    a.err = err;
+    a.ha.text = reinterpret_cast<const uint32_t*>(u8);
+    a.ha.seed = ct.seed;
+    a.ca.slots = ct.slots;
+    a.ca.counts = ct.counts;
+    a.ca.blob = ct.blob;
+    a.ca.n_slots = ct.n_slots;
+    a.ca.tally = ct.tally;
+    a.ca.max_word_bytes = ct.max_word_bytes;
+    hipLaunchKernelGGL(k_count_scatter, dim3(a.n_scatter_blocks), dim3(scatter_waves(5) * 64), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t launch_count_commit_sum(const CountTable& ct, hipStream_t st) {
+    hipLaunchKernelGGL(k_count_commit_sum, dim3((unsigned)((ct.n_slots + kCommitBlock - 1) / kCommitBlock)), dim3(kCommitBlock), 0, st, ct.slots,
+                       ct.n_slots, ct.ctl);
+    return hipGetLastError();
+}
+hipError_t launch_count_commit_copy(const uint8_t* u8, const CountTable& ct, hipStream_t st) {
+    hipLaunchKernelGGL(k_count_commit_copy, dim3((unsigned)((ct.n_slots + kCommitBlock - 1) / kCommitBlock)), dim3(kCommitBlock), 0, st, ct.slots,
+                       ct.n_slots, reinterpret_cast<const uint32_t*>(u8), ct.blob, ct.blob_dwords, ct.ctl);
     return hipGetLastError();
 }
 

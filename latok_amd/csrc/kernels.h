@@ -289,6 +289,34 @@ hipError_t launch_vocab_scatter(bool out32, const uint8_t* u8, const VocabTable&
                                 const uint16_t* word_pref, int64_t n_words, int64_t total, const int64_t* row_off, int64_t n_str,
                                 const int64_t* tile_first, void* out, int32_t* ids, const int64_t* n_items_dev, int64_t cap, void* counts,
                                 int* err, hipStream_t st);
+// token counts of a UTF-8 batch in byte space (compact_kernels.hip: KIND 5): launch_vocab_scatter's launch without outputs; every
+// token of at most max_word_bytes bytes is found or entered in a counting table (count_table.h) and counted, exactly.
+// kCountProbeMax bounds a probe whatever the table holds: at load <= 0.5 a run of 128 occupied slots has probability about
+// 0.82^128 ~ 1e-11 per slot, so the bound never fires on a table sized as documented and keeps a full one from costing n_slots
+// loads per token.  kCountAccEntries: entries of a wave's direct-mapped {slot, count} accumulator in LDS (8 bytes each: 4 KiB per
+// wave, 38 944 B per workgroup -> 4 workgroups = 16 waves per CU).  A 4096-byte tile holds ~700 tokens of English text, fewer
+// than 512 of them distinct, so most of a tile's words own an entry; what conflicts adds to global memory directly.  The cost of
+// the flush atomics and the right size are unmeasured.
+constexpr int kCountProbeMax = 128;
+constexpr int kCountAccEntries = 512;   // a power of two
+struct CountTable {
+    uint64_t* slots = nullptr;              // uint64[n_slots], 0 = empty
+    unsigned long long* counts = nullptr;   // uint64[n_slots]
+    uint32_t* blob = nullptr;               // the resident words; dword 0 is reserved
+    uint64_t blob_dwords = 0;               // capacity of the blob
+    uint64_t n_slots = 0;                   // a power of two, <= 2^31
+    uint32_t seed = 0;
+    int max_word_bytes = 0;
+    unsigned long long* tally = nullptr;    // this call's {counted, long, dropped}
+    unsigned long long* ctl = nullptr;      // {fresh dwords of this call, blob cursor, distinct, overflow flag}
+};
+hipError_t launch_count_scatter(const uint8_t* u8, const CountTable& ct, const uint64_t* bits, const uint64_t* space, const uint64_t* kept,
+                                const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, int64_t total,
+                                const int64_t* row_off, int64_t n_str, const int64_t* tile_first, const int64_t* n_items_dev, int* err,
+                                hipStream_t st);
+// the commit behind it: (a) the padded dwords of the fresh slots -> ctl[0]; (b) their bytes into the blob, resident words stored
+hipError_t launch_count_commit_sum(const CountTable& ct, hipStream_t st);
+hipError_t launch_count_commit_copy(const uint8_t* u8, const CountTable& ct, hipStream_t st);
 // zeros at codes[t .. t + kTile + 256), t = *total_dev held inside [0, bound]
 hipError_t launch_pad_codes(uint8_t* codes, const int64_t* total_dev, int64_t bound, hipStream_t st);
 int64_t utf8_blocks(int64_t total_bytes);   // 4 KiB blocks of the chunk-parallel UTF-8 decoder

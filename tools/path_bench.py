@@ -34,6 +34,12 @@
                   latok_flow_token_ids_utf8_bytes: every token's id in a vocabulary (--vocab all: every distinct token of the corpus,
                   so every lookup hits; half: every second distinct token, in order of first appearance), with the int32 counts and
                   records of bytes_spans32 (ids32) or alone (ids_only); same process run as bytes_spans32 and bytes_hashes32
+  bytes_count_cold / bytes_count_warm   latok_count_tokens_utf8_bytes_batch into a counter sized for the corpus' distinct tokens
+                  (2 x distinct slots): cold -- the counter was cleared before the call (the clear is not timed), every distinct
+                  word is claimed, committed to the blob and counted; warm -- the same batch once more, every token finds its
+                  word resident and nothing is committed; same process run as bytes_spans32 and bytes_ids32
+  py_count       end to end in Python on host blobs (the first --py-strings strings): TokenCounter.update_utf8 + most_common()
+                  against collections.Counter over batch.tokenize_utf8_batch(blobs), sorted the same way; one line each
   py_ids         end to end in Python on host blobs (the first --py-strings strings): batch.token_ids_utf8_batch(blobs, vocab)
                   against [[d.get(t, -1) for t in row] for row in batch.tokenize_utf8_batch(blobs)]; one line each
   py_join        end to end in Python on host blobs (the first --py-strings strings): batch.join_tokens_utf8_batch(blobs) against the
@@ -384,7 +390,8 @@ def main():
     # joined token text and the byte-space spans beside it: every line of this leg in one process run, in the order given
     join_leg = [p for p in paths if p in ("bytes_join", "bytes_join_flow", "bytes_spans32", "bytes_spans32_flow", "bytes_hashes32",
                                           "bytes_hashes32_flow", "bytes_hashes_only", "bytes_hashes_only_flow", "bytes_ids32", "bytes_ids32_flow",
-                                          "bytes_ids_only", "bytes_ids_only_flow", "py_ids", "py_join")]
+                                          "bytes_ids_only", "bytes_ids_only_flow", "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids",
+                                          "py_join")]
     if join_leg:
         jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64, cap * 4, cap * 4)]
         if not all(jb):
@@ -439,6 +446,53 @@ def main():
             return lib.latok_token_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, corpus_vocab().handle, -1, s_counts if rec else None,
                                                         s_items if rec else None, h_a, cap, C.byref(nout), D32, None)
 
+        note_c = ("UTF-8 bytes + 8 B/string read, the bytes of every token read once more, one 8-byte slot per probe step and the word of a "
+                  "candidate read from the text or the blob; per tile and distinct word one 8-byte atomic add; two passes over the slots")
+        counter_box = []
+
+        def corpus_counter():
+            """the counter of the count paths, made once: sized for the corpus' distinct tokens (found with a first, generous one)"""
+            if counter_box:
+                return counter_box[0]
+            from latok_amd import batch
+            guess = 1 << 20
+            while True:
+                with batch.TokenCounter(guess, seed=SEED) as probe:
+                    st = np.zeros(4, np.int64)
+                    _lib.check(lib.latok_count_tokens_utf8_bytes_batch(d_u8, d_boff, n, n8, probe.handle, st.ctypes.data, D, None))
+                    distinct, dropped = probe.stats["distinct"], int(st[3])
+                if dropped == 0 and distinct <= guess:
+                    break
+                guess *= 4
+            tc = batch.TokenCounter(max(distinct, 1), seed=SEED)
+            print(json.dumps({"counter": "corpus", "workload": args.workload, "distinct_tokens": distinct, "tokens": int(st[0]), "long": int(st[2]),
+                              "n_slots": tc.n_slots, "table_MiB": tc.n_slots * 16 / 2**20}), flush=True)
+            counter_box.append(tc)
+            return tc
+
+        def run_count(name, warm):
+            tc = corpus_counter()
+            st = np.zeros(4, np.int64)
+            call = lambda: lib.latok_count_tokens_utf8_bytes_batch(d_u8, d_boff, n, n8, tc.handle, st.ctypes.data, D, None)  # noqa: E731
+            tc.clear()
+            _lib.check(call())
+            for r in range(args.repeat):
+                dt = 0.0
+                for _ in range(args.iters):
+                    if not warm:
+                        tc.clear()                   # (waits for the device; not timed)
+                    t = time.perf_counter()
+                    _lib.check(call())               # (blocking: the commit is inside)
+                    dt += time.perf_counter() - t
+                dt /= args.iters
+                assert st[3] == 0 and st[0] == st[1] + st[2], st.tolist()
+                distinct = tc.stats["distinct"]
+                a = n8 + csr + 2 * tc.n_slots * 8
+                print(json.dumps({"path": name, "workload": args.workload, "strings": n, "utf8_bytes": n8, "items": int(st[0]), "distinct": distinct,
+                                  "long": int(st[2]), "n_slots": tc.n_slots, "ms_per_call": dt * 1e3, "utf8_GBps": n8 / dt / 1e9, "alg_bytes": a,
+                                  "alg_GBps": a / dt / 1e9, "frac_of_hbm_peak": a / dt / 1e9 / HBM_PEAK, "alg_bytes_are": note_c, "repeat": r}),
+                      flush=True)
+
         def two_words(name, want):
             res = np.empty(4, np.int64)
             _lib.check(lib.latok_memcpy_d2h(res.ctypes.data, j_res, 32))
@@ -491,6 +545,35 @@ def main():
                                                                              h_b if i & 1 else h_a, cap, resj(i), _lib.OUT_INT32),
                          lambda: n8 + csr + 4 * items_n + (4 * n + 8 * items_n if rec else 0), note_i + (" + " + note_s if rec else ""))
                 two_words(name, items_n)
+            elif name in ("bytes_count_cold", "bytes_count_warm"):
+                run_count(name, name == "bytes_count_warm")
+            elif name == "py_count":   # host blobs in, a ranked vocabulary out, both routes in this process
+                import collections
+                from latok_amd import batch
+                m = min(args.py_strings, n)
+                blob = u8[:int(boff[m])].tobytes()
+                blobs = [blob[int(a):int(b)] for a, b in zip(boff[:m], boff[1:m + 1])]
+                rank = lambda items: sorted(items, key=lambda wc: (-wc[1], wc[0]))  # noqa: E731
+
+                def on_device():
+                    with batch.TokenCounter(len(blob) // 4 + 64, seed=SEED) as tc:
+                        tc.update_utf8(blobs)
+                        assert tc.stats["dropped"] == 0
+                        return tc.most_common()
+
+                routes = (("py_token_counter_most_common", on_device),
+                          ("py_tokenize_utf8_batch_then_counter", lambda: rank(collections.Counter(
+                              t for row in batch.tokenize_utf8_batch(blobs) for t in row if len(t) <= 256).items())))
+                assert routes[0][1]() == routes[1][1]()
+                for r in range(args.repeat):
+                    for rname, fn in routes:
+                        t = time.perf_counter()
+                        ranked = fn()
+                        dt = time.perf_counter() - t
+                        print(json.dumps({"path": rname, "workload": args.workload, "strings": m, "utf8_bytes": len(blob), "distinct": len(ranked),
+                                          "tokens": sum(c for _, c in ranked), "ms_per_call": dt * 1e3, "utf8_GBps": len(blob) / dt / 1e9,
+                                          "note": "end to end in Python: list[bytes] in, [(word, count)] ranked by (-count, bytes) out, pack and host work included",
+                                          "repeat": r}), flush=True)
             elif name == "py_ids":   # host blobs in, host id rows out, both routes in this process
                 from latok_amd import batch
                 m = min(args.py_strings, n)
@@ -532,6 +615,8 @@ def main():
                                           "repeat": r}), flush=True)
         if vocab_box:
             vocab_box[0].close()
+        if counter_box:
+            counter_box[0].close()
         for p_ in jb:
             lib.latok_dev_free(p_)
     if "rules_mask" in paths:
