@@ -286,6 +286,45 @@ int latok_token_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_of
                                      int64_t* spans_out /* may be NULL */, int32_t* ids_out, int64_t cap, int64_t* n_tokens_out,
                                      int flags, void* stream);
 
+/* Per-string term counts in byte space: the rows of a document-term matrix, as the three arrays of a canonical CSR matrix --
+ * what CountVectorizer(vocabulary=...).transform and HashingVectorizer(norm=None).transform return.  A token is what the spans call
+ * yields: for string s, t_0 .. t_(c_s-1) are the byte slices latok_token_spans_utf8_bytes_batch reports; run-time rule tables and
+ * malformed bytes are taken as that call takes them.  Every token gets a key and a value:
+ *   vocabulary form   key = id_i of the lowest-indexed word equal to the token, byte for byte -- exactly the id
+ *                     latok_token_ids_utf8_bytes_batch would store --, value = 1.  A token with no such word is OUT OF VOCABULARY:
+ *                     it contributes no entry and adds 1 to oov[s].  "Not found" is kept apart from every legal id (a vocabulary
+ *                     may carry any int32 as an id: there is no unk sentinel).  Two words that carry the same id count into the
+ *                     same entry.  V = 0 is accepted: every token is out of vocabulary.
+ *   hashed form       h = MurmurHash3 x86_32 of the token's bytes with `seed`, read as int32; key = |h| mod n_features, computed in
+ *                     64 bits (h = -2^31 gives 2^31 mod n_features: scikit-learn's rule in _hashing_fast.pyx); value = (h >= 0 ? +1
+ *                     : -1) if alternate_sign, else +1.  n_features must be in 1 .. 2^31 - 1; anything else is refused before
+ *                     any device work.
+ * Row s is the set of distinct keys of its tokens, ascending as signed int32, each with the sum of its values:
+ *   indptr[0] = 0, indptr[s+1] = indptr[s] + (number of distinct keys of string s)
+ *   indices[indptr[s] + j] = j-th smallest key of string s
+ *   data   [indptr[s] + j] = sum of the values of the tokens of s with that key   (int32)
+ *   oov[s]                 = number of out-of-vocabulary tokens of s             (vocabulary form; may be NULL)
+ * In the hashed form a sum may be 0: the entry is kept, as scikit-learn keeps it after sum_duplicates.  The output is fully
+ * deterministic (unlike the order of latok_counter_read).  Empty strings, whitespace-only strings and all-OOV strings give empty
+ * rows; n_str = 0 or total_bytes = 0 gives nnz = 0 with indptr cleared.
+ * Everything else follows the ids call: host pointers or LATOK_DEVICE_PTRS (device UTF-8 pointer 16-byte aligned), total_bytes =
+ * -1, check of the vocabulary's device; LATOK_OUT_INT32 applies to indptr and oov (an index and a count are always one int32); any
+ * other flag bit is refused before any device work.  Capacity protocol, in ENTRIES (nnz): cap too small -> nothing is written to
+ * indices or data, indptr and oov stay valid, the need is in *nnz_out and the call returns LATOK_ERR_INVALID; cap = 0 with both
+ * buffers NULL is a size query; exactly one of the two NULL, or both NULL with cap > 0, is refused.  A batch whose token total is
+ * 2^31 or more is refused with nothing written (data is int32).  *n_tokens_out (may be NULL) = the token total.  Every batch size
+ * takes the same kernels.  The calls are blocking and wait for their kernels TWICE -- once for the token total, which sizes the key
+ * buffers, once for nnz --, and a third time for the copy of the entries when the outputs are host pointers.  There is no flow
+ * form. */
+int latok_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                       const latok_vocab* vocab, int64_t* indptr_out /* [n_str+1] */,
+                                       int64_t* oov_out /* [n_str], may be NULL */, int32_t* indices_out, int32_t* data_out, int64_t cap,
+                                       int64_t* nnz_out, int64_t* n_tokens_out /* may be NULL */, int flags, void* stream);
+int latok_hashed_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                              uint32_t seed, int64_t n_features, int alternate_sign, int64_t* indptr_out /* [n_str+1] */,
+                                              int32_t* indices_out, int32_t* data_out, int64_t cap, int64_t* nnz_out,
+                                              int64_t* n_tokens_out /* may be NULL */, int flags, void* stream);
+
 /* Token counting in byte space: the vocabulary of a corpus -- every distinct token with its frequency -- built on the device.
  * The tokens of a batch are the byte slices latok_token_spans_utf8_bytes_batch reports for it (default_tokenizer.py:149-160);
  * run-time rule tables and malformed bytes are taken as that call takes them, and bytes are compared verbatim.  A COUNTER is a

@@ -55,6 +55,9 @@ SIGNATURES = {
     "latok_vocab_destroy": (ci, [vp]),
     "latok_vocab_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_uint32), C.POINTER(ci)]),
     "latok_token_ids_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, vp, vp, vp, i64, C.POINTER(i64), ci, vp]),
+    "latok_term_counts_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
+    "latok_hashed_term_counts_utf8_bytes_batch": (ci, [vp, vp, i64, i64, C.c_uint32, i64, ci, vp, vp, vp, i64, C.POINTER(i64),
+                                                       C.POINTER(i64), ci, vp]),
     "latok_counter_create": (ci, [i64, ci, C.c_uint32, C.POINTER(vp)]),
     "latok_counter_destroy": (ci, [vp]),
     "latok_counter_clear": (ci, [vp]),

@@ -649,6 +649,86 @@ def token_ids_batch(texts, vocab, unk_id=-1):
     return token_ids_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], vocab, unk_id)
 
 
+# term counts: every string's distinct tokens with their counts -- the CSR rows of a document-term matrix, built on the device
+def _n_features31(n_features) -> int:
+    """n_features as an int 1 .. 2**31 - 1; anything else is a ValueError (raised before any device is asked for)"""
+    if isinstance(n_features, (int, np.integer)) and not isinstance(n_features, bool) and 1 <= int(n_features) <= 0x7FFFFFFF:
+        return int(n_features)
+    raise ValueError("n_features must be an int in 1 .. 2**31 - 1")
+
+
+def _terms_csr(utf8, byte_off, vocab, hashed, dtype):
+    """the size query, then the fill -> (indptr, indices, data, oov or None)"""
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    dt, flags = _out_dtype(dtype)
+    n_str = byte_off.size - 1
+    total = int(byte_off[-1]) if n_str > 0 else 0
+    lib = _lib.ensure_init()
+    indptr = np.zeros(n_str + 1, dt)
+    oov = None if hashed else np.zeros(n_str, dt)
+    nnz = C.c_int64(0)
+
+    def call(indices, data, cap):
+        if hashed:
+            seed, n_features, alternate_sign = hashed
+            return lib.latok_hashed_term_counts_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, seed, n_features,
+                                                                 1 if alternate_sign else 0, _ptr(indptr), indices, data, cap,
+                                                                 C.byref(nnz), None, flags, None)
+        return lib.latok_term_counts_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, vocab, _ptr(indptr), _ptr(oov), indices, data,
+                                                      cap, C.byref(nnz), None, flags, None)
+
+    rc = call(None, None, 0)
+    if rc != _lib.OK and not (rc == _lib.ERR_INVALID and nnz.value > 0):
+        _lib.check(rc)
+    indices, data = np.empty(nnz.value, np.int32), np.empty(nnz.value, np.int32)
+    if nnz.value > 0:
+        _lib.check(call(_ptr(indices), _ptr(data), nnz.value))
+    return indptr, indices, data, oov
+
+
+def term_counts_utf8_csr(utf8, byte_off, vocab, dtype=np.int64):
+    """(indptr[n + 1], indices int32[nnz], data int32[nnz], oov[n]): the term counts of every string against ``vocab`` as a
+    canonical CSR matrix -- row s holds the distinct vocabulary ids of its tokens (the byte slices token_spans_utf8_bytes_csr
+    reports), ascending, each with its count; ``oov[s]`` counts the tokens the vocabulary does not hold.  What
+    ``CountVectorizer(vocabulary=...).transform`` returns: ``scipy.sparse.csr_matrix((data, indices, indptr), shape=(n, n_cols))``.
+    indptr and oov in ``dtype``.  Cut, looked up, sorted and reduced on the device (``latok_term_counts_utf8_bytes_batch``)."""
+    return _terms_csr(utf8, byte_off, _vocab_handle(vocab), None, dtype)
+
+
+def term_counts_utf8_batch(blobs, vocab):
+    """list[bytes] (UTF-8) -> (indptr, indices, data, oov) of term_counts_utf8_csr, int64 ('' and whitespace-only -> empty rows)."""
+    handle = _vocab_handle(vocab)
+    utf8, byte_off = pack_utf8(blobs)
+    return _terms_csr(utf8, byte_off, handle, None, np.int64)
+
+
+def term_counts_batch(texts, vocab):
+    """list[str] -> (indptr, indices, data, oov): per string ``Counter(d[t] for t in tokenize(text) if t in d)`` with sorted keys,
+    d = the vocabulary as a dict; oov = the tokens not in d.  The strings go through UTF-8 ("surrogatepass") on the host."""
+    return term_counts_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], vocab)
+
+
+def hashed_term_counts_utf8_csr(utf8, byte_off, n_features=1 << 20, seed=0, alternate_sign=True, dtype=np.int64):
+    """(indptr[n + 1], indices int32[nnz], data int32[nnz]): the hashed term counts of every string as a canonical CSR matrix --
+    column = ``abs(h) % n_features``, value = ``+1`` or (``alternate_sign`` and h < 0) ``-1``, h = MurmurHash3 x86_32 of the token's
+    bytes with ``seed`` as int32; a row's columns ascend and a sum may be an explicit 0.  What ``HashingVectorizer(norm=None)
+    .transform`` returns: ``scipy.sparse.csr_matrix((data, indices, indptr), shape=(n, n_features))``.  indptr in ``dtype``.  Cut,
+    hashed, sorted and reduced on the device (``latok_hashed_term_counts_utf8_bytes_batch``)."""
+    return _terms_csr(utf8, byte_off, None, (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), dtype)[:3]
+
+
+def hashed_term_counts_utf8_batch(blobs, n_features=1 << 20, seed=0, alternate_sign=True):
+    """list[bytes] (UTF-8) -> (indptr, indices, data) of hashed_term_counts_utf8_csr, int64."""
+    hashed = (_seed32(seed), _n_features31(n_features), bool(alternate_sign))
+    utf8, byte_off = pack_utf8(blobs)
+    return _terms_csr(utf8, byte_off, None, hashed, np.int64)[:3]
+
+
+def hashed_term_counts_batch(texts, n_features=1 << 20, seed=0, alternate_sign=True):
+    """list[str] -> (indptr, indices, data): hashed_term_counts_utf8_batch of the strings' UTF-8 ("surrogatepass")."""
+    return hashed_term_counts_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], n_features, seed, alternate_sign)
+
+
 # token counts: the vocabulary of a corpus -- every distinct token with its frequency --, counted on the device, exactly
 class TokenCounter:
     """A counting table on the device of the current context (``latok_counter_create``): at most about ``max_words`` distinct

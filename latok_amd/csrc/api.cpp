@@ -177,6 +177,7 @@ struct Workspace {
     // code-point masks, the code-point row offsets (the blocking calls keep theirs in the context: Ctx::u_lead ..)
     DevBuf lead, bspace, cpbits, cpspace, cprow;
     DevBuf jbody, jhead;   // joined token text: the body / head planes over the bytes (k_join_counts)
+    DevBuf tkeys, tkeys2, trows;   // term counts: one key per token, the long rows' second buffer, five int64 arrays over the rows
     // the single-pass scan of k_word_counts_scan keeps its look-back state (chain: per workgroup, chain_ctl: {ticket
     // counter}) between launches: entries carry an epoch, so the array is cleared only when it is (re)allocated or when the
     // 18-bit epoch wraps (next_scan_epoch); *_seen = DevBuf::gen of the allocations it was last cleared in
@@ -184,7 +185,8 @@ struct Workspace {
     bool chain_ready = false;
     void release() {
         for (DevBuf* b : {&summ, &seg_agg, &fix_count, &tile_first, &bits, &space, &kept, &wcnt, &wpref, &bases, &scalar, &chain,
-                          &chain_ctl, &codes, &widened, &lead, &bspace, &cpbits, &cpspace, &cprow, &jbody, &jhead})
+                          &chain_ctl, &codes, &widened, &lead, &bspace, &cpbits, &cpspace, &cprow, &jbody, &jhead, &tkeys,
+                          &tkeys2, &trows})
             b->release();
         scan_epoch = chain_seen = chain_ctl_seen = 0;
         chain_ready = false;
@@ -195,14 +197,18 @@ struct WsNeed {
     size_t bytes;   // 0: the batch does not use the buffer
 };
 constexpr int kTileNeeds = 4;   // the first entries of ws_needs: the tile stage
-constexpr int kWsNeeds = 22;
+constexpr int kWsNeeds = 25;
 // What a batch asks of its workspace beyond the tile stage.  token spans (spans) add the SPACE and kept planes, featurize (feats)
 // the code bytes, and narrow units read by featurize (widen) a UTF-32 copy.  cp_rows > 0: the units are UTF-8 bytes whose results
 // are reported in code points (cp_rows = n_str + 1): every buffer is sized by the byte count, which bounds the code-point count.
-// join: the two planes of the joined token text (UTF-8 bytes, with spans).
+// join: the two planes of the joined token text (UTF-8 bytes, with spans).  term_rows > 0 (= n_str + 1): term counts -- the row
+// arrays and a scan state that also serves a scan over the rows; term_tokens: the batch's token total, which the term-count call
+// waits for before it sizes the two key buffers.
+constexpr int kTermRowArrays = 5;   // token counts, row starts, distinct counts, indptr, OOV counts
 struct WsShape {
     bool spans = false, feats = false, widen = false, join = false;
     int64_t cp_rows = 0;
+    int64_t term_rows = 0, term_tokens = 0;
 };
 // The one sizing rule of a workspace: every buffer a batch of `units` positions uses and its byte size.
 static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const WsShape& shape) {
@@ -223,7 +229,7 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const 
              {&w.wpref, words * 2 + 8},     // items of the tile before each word
              {&w.bases, c_tiles * 8 + 8},   // rank of each tile's first item
              {&w.scalar, 64},
-             {&w.chain, (size_t)latok::count_blocks((int64_t)words) * 8 + 64},
+             {&w.chain, (size_t)std::max(latok::count_blocks((int64_t)words), latok::count_blocks(shape.term_rows * 64)) * 8 + 64},
              {&w.chain_ctl, 64},
              {&w.codes, feats ? (size_t)units + latok::kTile + 256 : 0},   // read (never used) up to a tile behind the last char
              {&w.widened, widen ? (size_t)units * 4 + 16 : 0},
@@ -233,7 +239,10 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const 
              {&w.cpspace, cp_rows > 0 && spans ? words * 8 + 8 : 0},
              {&w.cprow, cp_rows > 0 ? (size_t)cp_rows * 8 : 0},
              {&w.jbody, join ? words * 8 + 8 : 0},
-             {&w.jhead, join ? words * 8 + 8 : 0}}};
+             {&w.jhead, join ? words * 8 + 8 : 0},
+             {&w.tkeys, shape.term_tokens > 0 ? (size_t)shape.term_tokens * 8 : 0},
+             {&w.tkeys2, shape.term_tokens > 0 ? (size_t)shape.term_tokens * 8 : 0},
+             {&w.trows, shape.term_rows > 0 ? (size_t)shape.term_rows * 8 * kTermRowArrays : 0}}};
 }
 static int ws_ensure(const WsNeed* needs, int n) {
     for (int i = 0; i < n; ++i) {
@@ -2323,6 +2332,189 @@ int latok_token_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_of
     return LATOK_OK;
 }
 
+/* Per-string term counts of a UTF-8 batch in BYTE space (latok_term_counts_utf8_bytes_batch, latok_hashed_term_counts_utf8_bytes_batch):
+ * the CSR rows of a document-term matrix.  One stream, every batch size the same kernels:
+ *   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
+ *   k_word_counts + k_scan_chained                kept mask, token ranks; THE token total -> scalar word 0, pinned word 0
+ *   (wait 1)                                      the host reads the token total: 2^31 or more is refused, the key buffers are sized
+ *   k_term_scatter                                one term key per token at its rank (term_key.h), int64 token count per string
+ *   k_scan_chained                                the row starts in token space
+ *   k_terms_tile, k_terms_long                    sort and reduce inside every string: distinct and OOV counts, the entries
+ *   k_scan_chained                                indptr, nnz -> pinned word 3
+ *   k_terms_finish, k_terms_emit                  indptr / oov in the caller's width; indices / data if nnz fits the capacity
+ *   (wait 2)                                      nnz; host pointers then copy nnz entries (wait 3)
+ * `w` was sized by ws_needs with WsShape{.spans = true, .term_rows = n_str + 1}; the call sizes the key buffers itself. */
+struct TermCounts {
+    Batch b;                       // UTF-8 bytes on the device (16-byte aligned), byte offsets, total in bytes (> 0), n_str > 0
+    const Vocab* vocab = nullptr;  // NULL: the hashed form
+    uint32_t seed = 0, n_features = 0;
+    bool alternate_sign = false;
+    void* indptr = nullptr;        // [n_str + 1]
+    void* oov = nullptr;           // [n_str]; NULL: not asked for
+    int32_t* indices = nullptr;    // NULL (both): a size query
+    int32_t* data = nullptr;
+    int64_t cap = 0;               // in entries
+    bool o32 = false;              // width of indptr and oov
+    int64_t* p_tot = nullptr;      // the pinned words as the device sees them (cleared by the caller): 0 tokens, 1 flags, 3 nnz
+    volatile int64_t* h_tot = nullptr;
+    int64_t n_tokens = 0;          // (out) the token total
+    hipStream_t st = nullptr;
+};
+static int enqueue_term_counts(Ctx& g, Workspace& w, TermCounts& a) {
+    int rc;
+    const hipStream_t st = a.st;
+    const int64_t total = a.b.total, words = (total + 63) / 64, n_str = a.b.n_str;
+    uint64_t* d_bits = (uint64_t*)w.bits.p;
+    uint64_t* d_space = (uint64_t*)w.space.p;
+    uint64_t* d_kept = (uint64_t*)w.kept.p;
+    int64_t* d_rank = (int64_t*)w.bases.p;
+    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
+    uint16_t* d_pref = (uint16_t*)w.wpref.p;
+    int64_t* d_total = (int64_t*)w.scalar.p;
+    int* d_err = (int*)(a.p_tot + 1);
+    unsigned epoch = 0;
+    Pipe p;
+    p.b = a.b;
+    p.bits = d_bits;
+    p.space = d_space;
+    p.st = st;
+    if ((rc = run_pipeline(g, w, p))) return rc;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    HIP_TRY(latok::launch_word_counts_scan(true, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank, (unsigned long long*)w.chain.p,
+                                           (unsigned*)w.chain_ctl.p, epoch, d_total, a.p_tot, d_err + 1, st));
+    HIP_TRY(hipStreamSynchronize(st));   // wait 1: the token total decides whether the call goes on and what the keys take
+    if ((rc = finish_totals(w, a.h_tot, 0, &a.n_tokens))) return rc;
+    const int64_t n_tok = a.n_tokens;
+    if (n_tok >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld tokens: term counts are int32 (fewer than 2^31 tokens a call)", (long long)n_tok);
+    if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .term_tokens = n_tok}).data(), kWsNeeds)))
+        return rc;
+    int64_t* rows = (int64_t*)w.trows.p;
+    int64_t* d_cnt = rows;
+    int64_t* d_start = rows + (n_str + 1);
+    int64_t* d_distinct = rows + 2 * (n_str + 1);
+    int64_t* d_indptr = rows + 3 * (n_str + 1);
+    int64_t* d_oov = rows + 4 * (n_str + 1);
+    HIP_TRY(hipMemsetAsync(rows, 0, (size_t)(n_str + 1) * 8 * kTermRowArrays, st));   // (no token: every row is empty, nnz = 0)
+    if (n_tok > 0) {
+        uint64_t* d_keys = (uint64_t*)w.tkeys.p;
+        latok::VocabTable vt;
+        if (a.vocab) vt = latok::VocabTable{a.vocab->d_slots, (const uint32_t*)a.vocab->d_blob, a.vocab->n_slots, a.vocab->seed};
+        HIP_TRY(latok::launch_term_scatter((const uint8_t*)a.b.in.p, a.vocab ? &vt : nullptr, a.seed, a.n_features, a.alternate_sign, d_bits, d_space,
+                                           d_kept, d_rank, d_tcnt, d_pref, words, total, a.b.row, n_str, (const int64_t*)w.tile_first.p, d_total,
+                                           d_keys, d_cnt, d_err, st));
+        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+        HIP_TRY(latok::launch_tile_scan(d_cnt, n_str + 1, d_start, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 4,
+                                        nullptr, d_err + 1, st));
+        HIP_TRY(latok::launch_terms_reduce(d_keys, (uint64_t*)w.tkeys2.p, d_start, n_str, n_tok, a.vocab != nullptr, d_distinct, d_oov, st));
+        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+        HIP_TRY(latok::launch_tile_scan(d_distinct, n_str + 1, d_indptr, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch,
+                                        d_total + 5, a.p_tot + 3, d_err + 1, st));
+        if (a.indices)
+            HIP_TRY(latok::launch_terms_emit(d_keys, d_start, n_str, n_tok, d_distinct, d_indptr, d_total + 5, a.cap, a.indices, a.data, st));
+    }
+    HIP_TRY(latok::launch_terms_finish(a.o32, d_indptr, d_oov, n_str, a.indptr, a.oov, st));
+    return LATOK_OK;
+}
+
+// the two blocking entry points' shared body: the checks of the ids call, the capacity protocol in entries
+static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
+                              bool hashed, uint32_t seed, int64_t n_features, int alternate_sign, void* indptr_out, void* oov_out,
+                              int32_t* indices_out, int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_tokens_out, int flags,
+                              void* stream) {
+    LATOK_ENTER();
+    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (!nnz_out) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
+    *nnz_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!indptr_out) return fail(LATOK_ERR_INVALID, "indptr_out is NULL");
+    if (cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
+    if ((indices_out == nullptr) != (data_out == nullptr)) return fail(LATOK_ERR_INVALID, "indices_out and data_out go together: one of them is NULL");
+    if (!indices_out && cap > 0) return fail(LATOK_ERR_INVALID, "indices_out and data_out are NULL but cap > 0 (a size query passes cap = 0)");
+    if (hashed && (n_features < 1 || n_features > 0x7FFFFFFFll)) return fail(LATOK_ERR_INVALID, "n_features must be in 1 .. 2^31 - 1");
+    const Vocab* v = nullptr;
+    if (!hashed && (rc = check_vocab(g, vocab, &v))) return rc;
+    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0, o32 = (flags & LATOK_OUT_INT32) != 0;
+    const size_t elt = o32 ? 4 : 8;   // width of indptr and oov (an index and a count are 4 bytes in every mode)
+    int64_t total = total_bytes;
+    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
+    StreamTurn turn(g, stream);
+    hipStream_t st = turn.st;
+    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
+    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (dev && ((uintptr_t)indptr_out & (elt - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    if (n_str == 0 || total == 0) {   // no byte, no token: every row is empty
+        if ((rc = zero_counts(dev, indptr_out, (size_t)(n_str + 1) * elt, st))) return rc;
+        return zero_counts(dev, oov_out, (size_t)n_str * elt, st, true);
+    }
+    if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    if (dev && (((uintptr_t)oov_out & (elt - 1)) != 0 || ((uintptr_t)indices_out & 3) != 0 || ((uintptr_t)data_out & 3) != 0))
+        return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    g.last_route = hashed ? 10 : 9;
+    Batch d;
+    if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
+    if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true, .term_rows = n_str + 1}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+    TermCounts a;
+    a.b = d;
+    a.vocab = v;
+    a.seed = seed;
+    a.n_features = (uint32_t)n_features;
+    a.alternate_sign = alternate_sign != 0;
+    a.indptr = indptr_out;
+    a.oov = oov_out;
+    a.indices = indices_out;
+    a.data = data_out;
+    a.cap = indices_out ? std::min(cap, total) : 0;   // (an entry has at least one token, a token one byte: the staging is sized by it)
+    a.o32 = o32;
+    if (!dev) {
+        if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 4 + 16)) ||
+            (rc = g.counts.ensure((size_t)(2 * n_str + 2) * 8)))
+            return rc;
+        if (indices_out) {
+            a.indices = (int32_t*)g.h_aux.p;
+            a.data = (int32_t*)g.h_out.p;
+        }
+        a.indptr = g.counts.p;
+        if (oov_out) a.oov = (uint8_t*)g.counts.p + (size_t)(n_str + 1) * 8;
+    }
+    h_tot[0] = h_tot[1] = h_tot[3] = 0;
+    a.p_tot = (int64_t*)g.pin_tot.d;
+    a.h_tot = h_tot;
+    a.st = st;
+    if ((rc = enqueue_term_counts(g, g.ws, a))) return rc;
+    if (!dev) {   // valid whatever the capacity
+        HIP_TRY(hipMemcpyAsync(indptr_out, a.indptr, (size_t)(n_str + 1) * elt, hipMemcpyDeviceToHost, st));
+        if (oov_out) HIP_TRY(hipMemcpyAsync(oov_out, a.oov, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // wait 2
+    int64_t n_tok = 0;
+    if ((rc = finish_totals(g.ws, h_tot, 0, &n_tok))) return rc;
+    if (n_tokens_out) *n_tokens_out = n_tok;
+    const int64_t nnz = h_tot[3];
+    *nnz_out = nnz;
+    if (nnz > cap) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld entries", (long long)nnz);
+    if (!dev && nnz > 0 && indices_out) {   // (host pointers: the copies, whose size is known only now)
+        HIP_TRY(hipMemcpyAsync(indices_out, a.indices, (size_t)nnz * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(data_out, a.data, (size_t)nnz * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));   // wait 3
+    }
+    return LATOK_OK;
+}
+int latok_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
+                                       int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out, int32_t* data_out, int64_t cap,
+                                       int64_t* nnz_out, int64_t* n_tokens_out, int flags, void* stream) {
+    return term_counts_common(utf8, byte_off, n_str, total_bytes, vocab, false, 0, 0, 0, indptr_out, oov_out, indices_out, data_out, cap, nnz_out,
+                              n_tokens_out, flags, stream);
+}
+int latok_hashed_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, uint32_t seed,
+                                              int64_t n_features, int alternate_sign, int64_t* indptr_out, int32_t* indices_out,
+                                              int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_tokens_out, int flags, void* stream) {
+    return term_counts_common(utf8, byte_off, n_str, total_bytes, nullptr, true, seed, n_features, alternate_sign, indptr_out, nullptr, indices_out,
+                              data_out, cap, nnz_out, n_tokens_out, flags, stream);
+}
+
 /* token counting in byte space: a mutable, exact counting table on the device (count_table.h), filled by k_count_scatter and made
  * independent of the caller's text by the two commit launches before the call returns.  One stream:
  *   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
@@ -3005,7 +3197,8 @@ int latok_debug_set_scan_epoch(unsigned epoch) {
  * kFeatFormThresh, kFeatWinBytes of k_features_tiles; out[14] = kHashWaveBytes (a longer token is hashed by its whole wave);
  * out[15..16] = kScanSmallMax (more entries: the exclusive scan takes three launches), kU8Block (bytes per block of the staged
  * UTF-8 decoder, one scan entry each); out[17..18] = kCountProbeMax (steps after which a probe of a counting table gives up),
- * kCountAccEntries (entries of a wave's count accumulator in k_count_scatter).  Returns the number of values written. */
+ * kCountAccEntries (entries of a wave's count accumulator in k_count_scatter).  Returns the number of values written.  The list is
+ * closed at these 19 entries (tests/test_count_table_host.py pins the count); later constants have hooks of their own. */
 extern "C" int latok_debug_limits(int64_t* out, int n) {
     const int64_t v[19] = {latok::kTile, latok::kWPB, latok::kNarrowWPB, latok::kSegMax, latok::kOneSegTiles, latok::kFastTailTiles,
                            kSmallChars, kSmallStrings, latok::kCompressWaves, latok::kFeatWaves, latok::kFeatRound, latok::kFeatRoundTm,
@@ -3013,6 +3206,17 @@ extern "C" int latok_debug_limits(int64_t* out, int n) {
                            latok::utf8_block_bytes(), latok::kCountProbeMax, latok::kCountAccEntries};
     if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
     const int k = n < 19 ? n : 19;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
+/* test hook (not part of the ABI; needs no device): the constants of the term-count kernels (terms_kernels.hip): out[0] = kTermsTile
+ * (tokens per tile: a workgroup owns the rows that start in its tile), out[1] = kTermsRowMax (a row of more tokens is sorted by a
+ * workgroup of its own).  Returns the number of values written. */
+extern "C" int latok_debug_terms_limits(int64_t* out, int n) {
+    const int64_t v[2] = {latok::kTermsTile, latok::kTermsRowMax};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 2 ? n : 2;
     for (int i = 0; i < k; ++i) out[i] = v[i];
     return k;
 }
@@ -3076,7 +3280,8 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
  * 2: UTF-8 through the staged device decoder, 3: UTF-8 through byte space and the packed code-point masks (and codes),
  * 4: featurize of UTF-8 in byte space (byte records from the byte-space masks, sums from the packed code-point masks),
  * 5: joined token text of UTF-8 in byte space (every batch size; there is no small-batch route),
- * 6: token hashes of UTF-8 in byte space (every batch size as well); 7: token ids of UTF-8 in byte space (likewise) */
+ * 6: token hashes of UTF-8 in byte space (every batch size as well); 7: token ids of UTF-8 in byte space (likewise);
+ * 9 / 10: term counts of UTF-8 in byte space, vocabulary form / hashed form (likewise) */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;

@@ -25,6 +25,7 @@
 #include "count_table.h"
 #include "kernels.h"
 #include "lane_math.h"
+#include "term_key.h"
 #include "token_hash.h"
 #include "vocab_table.h"
 #include "wave_ops.h"
@@ -248,6 +249,9 @@ __global__ __launch_bounds__(256) void k_string_counts(const uint64_t* __restric
 // entries with no-return atomic adds, so a hot word costs one global atomic per tile, not one per token.  It writes no records.
 // A token of more than max_word_bytes bytes is tallied as long and never entered: there is no whole-wave form.  The three
 // tallies (counted, long, dropped) are reduced over the wave: one atomic each per tile.
+// KIND 6 (k_term_scatter): KIND 4's two paths with a term key (term_key.h) stored at the token's rank in the workspace instead of an
+// id in caller memory: the id with a found bit of its own, or -- with no table, n_features > 0 -- the hash bucket and the sign.
+// terms_kernels.hip sorts and reduces the keys inside every string.  It writes no records.
 constexpr int scatter_waves(int kind) { return 4; }   // waves per workgroup
 struct HashArgs {
     const uint32_t* text = nullptr;   // the batch's bytes as aligned dwords (the buffer is 16-byte aligned)
@@ -270,6 +274,11 @@ struct CountArgs {                    // (KIND 5; the text and the seed travel i
     unsigned long long* tally = nullptr;   // this call's {counted, long, dropped}
     int max_word_bytes = 0;           // 1 .. kHashWaveBytes
 };
+struct TermArgs {                     // (KIND 6; the text and the seed travel in HashArgs, the table in VocabArgs)
+    uint64_t* keys = nullptr;         // one term_key.h key per token, at its rank
+    uint32_t n_features = 0;          // 0: the vocabulary form
+    bool alternate_sign = false;
+};
 struct CtDeviceAtomics {              // count_table.h's policy: relaxed, agent scope -- the slot word is the whole message
     static __device__ __forceinline__ uint64_t load(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     static __device__ __forceinline__ uint64_t cas(uint64_t* p, uint64_t expect, uint64_t v) {
@@ -287,8 +296,9 @@ __device__ __forceinline__ void counts_scatter_block(
     OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, unsigned vb,     // vb: (virtual) workgroup index
     const HashArgs ha = HashArgs{},                                                              // (KIND 3 and 4 only)
     const VocabArgs va = VocabArgs{},                                                            // (KIND 4 only)
-    const CountArgs ca = CountArgs{}) {                                                          // (KIND 5 only)
-    constexpr bool kHashes = KIND == 3 || KIND == 4 || KIND == 5;                                // records optional, tokens hashed
+    const CountArgs ca = CountArgs{},                                                            // (KIND 5 only)
+    const TermArgs ta = TermArgs{}) {                                                            // (KIND 6 only)
+    constexpr bool kHashes = KIND == 3 || KIND == 4 || KIND == 5 || KIND == 6;                   // records optional, tokens hashed
     static_assert(scatter_waves(KIND) * 64 == 256, "both roles use 256-thread workgroups");
     if (vb >= n_scatter_blocks) {   // role 2: one thread per string
         if (counts)
@@ -536,6 +546,20 @@ __device__ __forceinline__ void counts_scatter_block(
                             const uint32_t h = th_hash_lane([text](int64_t i) { return text[i]; }, a2, e2, ha.seed);
                             if (KIND == 3) {
                                 __builtin_nontemporal_store(h, ha.hashes + base_out + win0 + j);
+                            } else if constexpr (KIND == 6) {
+                                uint64_t key;
+                                if (ta.n_features) {
+                                    key = tk_hashed_key(h, ta.n_features, ta.alternate_sign);
+                                } else {
+                                    const VtSlot* slots = va.slots;
+                                    const uint32_t* blob = va.blob;
+                                    key = tk_vocab_probe([slots](uint64_t i) { return slots[i]; }, va.n_slots, h, (uint32_t)(e2 - a2),
+                                                         [text, a2, e2, blob](uint32_t off) {
+                                                             return vt_equal_lane([text](int64_t i) { return text[i]; }, a2, e2,
+                                                                                  [blob](uint64_t i) { return blob[i]; }, off);
+                                                         });
+                                }
+                                ta.keys[base_out + win0 + j] = key;
                             } else {
                                 const VtSlot* slots = va.slots;
                                 const uint32_t* blob = va.blob;
@@ -566,6 +590,29 @@ __device__ __forceinline__ void counts_scatter_block(
                     h = th_wave_tail(ld, a, e, h);
                     if (KIND == 3) {
                         if (lane == src) __builtin_nontemporal_store(h, ha.hashes + base_out + win0 + j);
+                    } else if constexpr (KIND == 6) {
+                        const uint32_t hu = (uint32_t)__builtin_amdgcn_readfirstlane((int)h);
+                        uint64_t key;
+                        if (ta.n_features) {
+                            key = tk_hashed_key(hu, ta.n_features, ta.alternate_sign);
+                        } else {   // the wave probes in step, as KIND 4 does
+                            const VtSlot* slots = va.slots;
+                            const uint32_t* blob = va.blob;
+                            key = tk_vocab_probe(
+                                [slots](uint64_t i) {
+                                    const VtSlot v = slots[i];
+                                    return VtSlot{(uint32_t)__builtin_amdgcn_readfirstlane((int)v.hash), __builtin_amdgcn_readfirstlane(v.id),
+                                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)v.off),
+                                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)v.len)};
+                                },
+                                va.n_slots, hu, (uint32_t)(e - a), [ld, a, e, blob, lane](uint32_t off) {
+                                    const int64_t rounds_c = vt_wave_rounds(a, e);
+                                    for (int64_t r = 0; r < rounds_c; ++r)
+                                        if (__ballot(vt_wave_differs(ld, a, e, [blob](uint64_t i) { return blob[i]; }, off, r, lane))) return false;
+                                    return true;
+                                });
+                        }
+                        if (lane == src) ta.keys[base_out + win0 + j] = key;
                     } else {
                         // every lane holds the same h: the wave walks the slots in step and compares a candidate together
                         const VtSlot* slots = va.slots;
@@ -669,6 +716,23 @@ __global__ __launch_bounds__(scatter_waves(5) * 64) void k_count_scatter(CountSc
     counts_scatter_block<5, int32_t>(a.bits, a.space, a.item_mask, a.tile_rank, a.tile_cnt, a.word_pref, a.n_words, a.total, a.row_off, a.n_str,
                                      a.tile_first, nullptr, a.n_items_dev, INT64_MAX, nullptr, a.n_scatter_blocks, a.err, blockIdx.x, a.ha,
                                      VocabArgs{}, a.ca);
+}
+
+// Term keys: KIND 6 of the body above in a kernel of its own (the kernels above keep their arguments and their code).  No records;
+// the per-string token counts are int64 (they feed the row scan of the term-count calls) and nothing is gated by a capacity.
+struct TermScatterArgs {
+    const uint64_t* bits; const uint64_t* space; const uint64_t* item_mask;
+    const int64_t* tile_rank; const int64_t* tile_cnt; const uint16_t* word_pref;
+    int64_t n_words, total;
+    const int64_t* row_off; int64_t n_str;
+    const int64_t* tile_first; const int64_t* n_items_dev; int64_t* counts;
+    unsigned n_scatter_blocks; int* err;
+    HashArgs ha; VocabArgs va; TermArgs ta;
+};
+__global__ __launch_bounds__(scatter_waves(6) * 64) void k_term_scatter(TermScatterArgs a) {
+    counts_scatter_block<6, int64_t>(a.bits, a.space, a.item_mask, a.tile_rank, a.tile_cnt, a.word_pref, a.n_words, a.total, a.row_off, a.n_str,
+                                     a.tile_first, nullptr, a.n_items_dev, INT64_MAX, a.counts, a.n_scatter_blocks, a.err, blockIdx.x, a.ha,
+                                     a.va, CountArgs{}, a.ta);
 }
 
 // The commit behind k_count_scatter: two launches over the slots, one thread per slot, that make the table independent of the
@@ -1459,6 +1523,35 @@ hipError_t launch_count_scatter(const uint8_t* u8, const CountTable& ct, const u
     hipLaunchKernelGGL(k_count_scatter, dim3(a.n_scatter_blocks), dim3(scatter_waves(5) * 64), 0, st, a);
     return hipGetLastError();
 }
+// term keys (KIND 6): keys[rank] of every token and the int64 token count of every string (vt == NULL: the hashed form)
+hipError_t launch_term_scatter(const uint8_t* u8, const VocabTable* vt, uint32_t seed, uint32_t n_features, bool alternate_sign,
+                               const uint64_t* bits, const uint64_t* space, const uint64_t* kept, const int64_t* tile_rank,
+                               const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, int64_t total, const int64_t* row_off,
+                               int64_t n_str, const int64_t* tile_first, const int64_t* n_items_dev, uint64_t* keys, int64_t* counts, int* err,
+                               hipStream_t st) {
+    if (n_words <= 0) return hipSuccess;
+    TermScatterArgs a{};
+    a.bits = bits; a.space = space; a.item_mask = kept;
+    a.tile_rank = tile_rank; a.tile_cnt = tile_cnt; a.word_pref = word_pref;
+    a.n_words = n_words; a.total = total;
+    a.row_off = row_off; a.n_str = n_str;
+    a.tile_first = tile_first; a.n_items_dev = n_items_dev; a.counts = counts;
+    a.n_scatter_blocks = (unsigned)((n_words + 255) / 256);
+    a.err = err;
+    a.ha.text = reinterpret_cast<const uint32_t*>(u8);
+    a.ha.seed = vt ? vt->seed : seed;
+    if (vt) {
+        a.va.slots = reinterpret_cast<const VtSlot*>(vt->slots);
+        a.va.blob = vt->blob;
+        a.va.n_slots = vt->n_slots;
+    }
+    a.ta.keys = keys;
+    a.ta.n_features = vt ? 0u : n_features;
+    a.ta.alternate_sign = alternate_sign;
+    hipLaunchKernelGGL(k_term_scatter, dim3(a.n_scatter_blocks + (unsigned)((n_str + 255) / 256)), dim3(scatter_waves(6) * 64), 0, st, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_count_commit_sum(const CountTable& ct, hipStream_t st) {
     hipLaunchKernelGGL(k_count_commit_sum, dim3((unsigned)((ct.n_slots + kCommitBlock - 1) / kCommitBlock)), dim3(kCommitBlock), 0, st, ct.slots,
                        ct.n_slots, ct.ctl);

@@ -314,6 +314,28 @@ hipError_t launch_count_scatter(const uint8_t* u8, const CountTable& ct, const u
                                 const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, int64_t total,
                                 const int64_t* row_off, int64_t n_str, const int64_t* tile_first, const int64_t* n_items_dev, int* err,
                                 hipStream_t st);
+// term keys of a UTF-8 batch in byte space (compact_kernels.hip: KIND 6): launch_vocab_scatter's launch with one term key
+// (term_key.h) per token at its rank in `keys` and the int64 token count of every string in `counts`; vt == NULL: the hashed form
+// (bucket = |h| mod n_features, sign).  No records, no capacity.
+hipError_t launch_term_scatter(const uint8_t* u8, const VocabTable* vt, uint32_t seed, uint32_t n_features, bool alternate_sign,
+                               const uint64_t* bits, const uint64_t* space, const uint64_t* kept, const int64_t* tile_rank,
+                               const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, int64_t total, const int64_t* row_off,
+                               int64_t n_str, const int64_t* tile_first, const int64_t* n_items_dev, uint64_t* keys, int64_t* counts, int* err,
+                               hipStream_t st);
+// per-string term counts (terms_kernels.hip): the segmented sort-and-reduce of the term keys.  A workgroup owns the rows that start
+// in its tile of kTermsTile tokens; a row of more than kTermsRowMax tokens is sorted by a workgroup of its own through `alt`
+// (as large as `keys`).  row_start[n_str + 1] = the exclusive scan of the per-string token counts.  launch_terms_reduce leaves
+// distinct[row], oov[row] and the row's entries over the row's first keys; launch_terms_emit, behind the scan of distinct[] into
+// indptr[] and *nnz_dev, stores indices / data if nnz fits cap; launch_terms_finish types indptr[n_str + 1] and oov[n_str] (may be
+// NULL) for the caller.  latok_debug_terms_limits reports the two constants.
+constexpr int kTermsTile = 1024;
+constexpr int kTermsRowMax = 1024;
+hipError_t launch_terms_reduce(uint64_t* keys, uint64_t* alt, const int64_t* row_start, int64_t n_str, int64_t n_tok, bool vocab_form,
+                               int64_t* distinct, int64_t* oov, hipStream_t st);
+hipError_t launch_terms_emit(const uint64_t* keys, const int64_t* row_start, int64_t n_str, int64_t n_tok, const int64_t* distinct,
+                             const int64_t* indptr, const int64_t* nnz_dev, int64_t cap, int32_t* indices, int32_t* data, hipStream_t st);
+hipError_t launch_terms_finish(bool out32, const int64_t* indptr, const int64_t* oov, int64_t n_str, void* indptr_out, void* oov_out,
+                               hipStream_t st);
 // the commit behind it: (a) the padded dwords of the fresh slots -> ctl[0]; (b) their bytes into the blob, resident words stored
 hipError_t launch_count_commit_sum(const CountTable& ct, hipStream_t st);
 hipError_t launch_count_commit_copy(const uint8_t* u8, const CountTable& ct, hipStream_t st);

@@ -38,6 +38,11 @@
                   (2 x distinct slots): cold -- the counter was cleared before the call (the clear is not timed), every distinct
                   word is claimed, committed to the blob and counted; warm -- the same batch once more, every token finds its
                   word resident and nothing is committed; same process run as bytes_spans32 and bytes_ids32
+  bytes_terms32 / bytes_terms_hashed   latok_term_counts_utf8_bytes_batch (the vocabulary of the ids paths, --vocab all|half) /
+                  latok_hashed_term_counts_utf8_bytes_batch (2^20 features, alternating signs): the CSR rows of the document-term
+                  matrix with int32 indptr (and oov), capacity = the token total; same process run as bytes_ids32 and bytes_hashes32
+  py_terms       end to end in Python on host blobs (the first --py-strings strings): batch.term_counts_utf8_batch(blobs, vocab)
+                  against batch.tokenize_utf8_batch(blobs) + a dict and collections.Counter per row; one line each
   py_count       end to end in Python on host blobs (the first --py-strings strings): TokenCounter.update_utf8 + most_common()
                   against collections.Counter over batch.tokenize_utf8_batch(blobs), sorted the same way; one line each
   py_ids         end to end in Python on host blobs (the first --py-strings strings): batch.token_ids_utf8_batch(blobs, vocab)
@@ -106,10 +111,10 @@ def main():
                                        "utf8_bytes_features32,utf8_bytes_features32_flow,pair_features32_bytes_spans32,pair_features32_bytes_spans32_flow,"
                                        "bytes_mask,bytes_offsets,bytes_spans,bytes_spans32,bytes_spans32_flow,bytes_join,bytes_join_flow,"
                                        "bytes_hashes32,bytes_hashes32_flow,bytes_hashes_only,bytes_hashes_only_flow,"
-                                       "bytes_ids32,bytes_ids32_flow,bytes_ids_only,bytes_ids_only_flow,"
+                                       "bytes_ids32,bytes_ids32_flow,bytes_ids_only,bytes_ids_only_flow,bytes_terms32,bytes_terms_hashed,"
                                        "rules_mask,kind_mask,kind_offsets,kind_offsets32,"
                                        "kind_spans,kind_spans32")
-    ap.add_argument("--py-strings", type=int, default=200_000, help="strings of the py_join / py_ids paths (host blobs)")
+    ap.add_argument("--py-strings", type=int, default=200_000, help="strings of the py_join / py_ids / py_terms paths (host blobs)")
     ap.add_argument("--vocab", default="all", choices=("all", "half"), help="vocabulary of the ids paths: every distinct token of the corpus, or every second one")
     args = ap.parse_args()
     lib = _lib.ensure_init()
@@ -390,8 +395,8 @@ def main():
     # joined token text and the byte-space spans beside it: every line of this leg in one process run, in the order given
     join_leg = [p for p in paths if p in ("bytes_join", "bytes_join_flow", "bytes_spans32", "bytes_spans32_flow", "bytes_hashes32",
                                           "bytes_hashes32_flow", "bytes_hashes_only", "bytes_hashes_only_flow", "bytes_ids32", "bytes_ids32_flow",
-                                          "bytes_ids_only", "bytes_ids_only_flow", "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids",
-                                          "py_join")]
+                                          "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "py_terms",
+                                          "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join")]
     if join_leg:
         jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64, cap * 4, cap * 4)]
         if not all(jb):
@@ -445,6 +450,23 @@ def main():
         def ids_blocking(rec):
             return lib.latok_token_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, corpus_vocab().handle, -1, s_counts if rec else None,
                                                         s_items if rec else None, h_a, cap, C.byref(nout), D32, None)
+
+        note_t = ("as the ids / hashes path up to the key; 8 B/token keys written, read by the sort and written back; 4 B/string indptr "
+                  "(+ 4 B/string oov) and 8 B/entry written (--vocab " + args.vocab + " / 2^20 features)")
+        terms_box = []
+
+        def terms_blocking(hashed):
+            if not terms_box:
+                tb = [lib.latok_dev_alloc(sz) for sz in ((n + 1) * 4 + 64, n * 4 + 64)]
+                if not all(tb):
+                    raise RuntimeError(_lib.last_error())
+                terms_box.extend(tb)
+            t_indptr, t_oov = terms_box
+            if hashed:
+                return lib.latok_hashed_term_counts_utf8_bytes_batch(d_u8, d_boff, n, n8, SEED, 1 << 20, 1, t_indptr, h_a, h_b, cap, C.byref(nout),
+                                                                     None, D32, None)
+            return lib.latok_term_counts_utf8_bytes_batch(d_u8, d_boff, n, n8, corpus_vocab().handle, t_indptr, t_oov, h_a, h_b, cap, C.byref(nout),
+                                                          None, D32, None)
 
         note_c = ("UTF-8 bytes + 8 B/string read, the bytes of every token read once more, one 8-byte slot per probe step and the word of a "
                   "candidate read from the text or the blob; per tile and distinct word one 8-byte atomic add; two passes over the slots")
@@ -545,6 +567,44 @@ def main():
                                                                              h_b if i & 1 else h_a, cap, resj(i), _lib.OUT_INT32),
                          lambda: n8 + csr + 4 * items_n + (4 * n + 8 * items_n if rec else 0), note_i + (" + " + note_s if rec else ""))
                 two_words(name, items_n)
+            elif name in ("bytes_terms32", "bytes_terms_hashed"):   # (items = nnz; the keys are sized by the token total)
+                hashed = name == "bytes_terms_hashed"
+                run(name, lambda: terms_blocking(hashed), lambda: n8 + csr + 4 * n + (0 if hashed else 4 * n) + 8 * nout.value, note_t)
+            elif name == "py_terms":   # host blobs in, the CSR arrays out, both routes in this process
+                import collections
+                from latok_amd import batch
+                m = min(args.py_strings, n)
+                blob = u8[:int(boff[m])].tobytes()
+                blobs = [blob[int(a):int(b)] for a, b in zip(boff[:m], boff[1:m + 1])]
+                distinct = list(dict.fromkeys(t for row in batch.tokenize_utf8_batch(blobs) for t in row))
+                words = distinct[::2] if args.vocab == "half" else distinct
+                d = {w: i for i, w in enumerate(words)}
+
+                def on_host():
+                    indptr, indices, data, oov = [0], [], [], []
+                    for row in batch.tokenize_utf8_batch(blobs):
+                        c = collections.Counter(d[t] for t in row if t in d)
+                        keys = sorted(c)
+                        indices.extend(keys)
+                        data.extend(c[k] for k in keys)
+                        indptr.append(len(indices))
+                        oov.append(len(row) - sum(c.values()))
+                    return np.array(indptr, np.int64), np.array(indices, np.int32), np.array(data, np.int32), np.array(oov, np.int64)
+
+                with batch.Vocab(words, seed=SEED) as v:
+                    routes = (("py_term_counts_utf8_batch", lambda: batch.term_counts_utf8_batch(blobs, v)),
+                              ("py_tokenize_utf8_batch_then_dict_counter", on_host))
+                    assert all(np.array_equal(a, b) for a, b in zip(routes[0][1](), routes[1][1]()))
+                    for r in range(args.repeat):
+                        for rname, fn in routes:
+                            t = time.perf_counter()
+                            got = fn()
+                            dt = time.perf_counter() - t
+                            print(json.dumps({"path": rname, "workload": args.workload, "strings": m, "utf8_bytes": len(blob), "vocab": args.vocab,
+                                              "words": len(words), "nnz": int(got[1].size), "oov": int(got[3].sum()), "ms_per_call": dt * 1e3,
+                                              "utf8_GBps": len(blob) / dt / 1e9,
+                                              "note": "end to end in Python: list[bytes] in, (indptr, indices, data, oov) out, pack and host work included",
+                                              "repeat": r}), flush=True)
             elif name in ("bytes_count_cold", "bytes_count_warm"):
                 run_count(name, name == "bytes_count_warm")
             elif name == "py_count":   # host blobs in, a ranked vocabulary out, both routes in this process
@@ -617,6 +677,8 @@ def main():
             vocab_box[0].close()
         if counter_box:
             counter_box[0].close()
+        for p_ in terms_box:
+            lib.latok_dev_free(p_)
         for p_ in jb:
             lib.latok_dev_free(p_)
     if "rules_mask" in paths:
