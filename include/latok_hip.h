@@ -325,6 +325,67 @@ int latok_hashed_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t
                                               int32_t* indices_out, int32_t* data_out, int64_t cap, int64_t* nnz_out,
                                               int64_t* n_tokens_out /* may be NULL */, int flags, void* stream);
 
+/* WordPiece in byte space: the subword ids a BERT-family model takes, for every token of a batch.
+ * A WORDPIECE VOCABULARY is an ordered list of byte strings w_0 .. w_(V-1) with optional int32 ids (word_ids = NULL means id_i = i),
+ * a continuation prefix P of 0 .. 8 bytes ("##" in BERT's files; an empty P is legal: every word is then also a continuation word),
+ * a 32-bit seed (of the MurmurHash3 x86_32 that places a word; it changes no id) and max_chars in 1 .. 1024 (BERT's
+ * max_input_chars_per_word).  It is one immutable device object that holds two tables of the kind latok_vocab holds: the INITIAL
+ * table holds every word; the CONTINUATION table holds every word that starts with P and is longer than P, stored without P, with
+ * the same id.  Of duplicate words the first wins.  These are exactly the lookups of one dictionary that gets `piece` at a token's
+ * start and P + piece elsewhere.  Each table records the byte length of its longest word.
+ * A token is what the spans call yields: bytes [a, e) of string s from latok_token_spans_utf8_bytes_batch; run-time rule tables and
+ * malformed bytes are taken as that call takes them.  A CHAR START is the token's first byte, and any later byte b with
+ * (b & 0xC0) != 0x80; chars(token) is the number of char starts.  The cut, per token:
+ *   1. chars(token) > max_chars: the token is ONE piece (unk_id, a, e).
+ *   2. otherwise start = a; while start < e:
+ *        among the ends p in (start, e] where p == e or p is a char start, take the LARGEST p such that bytes[start:p] is a word of
+ *        the initial table (if start == a) or of the continuation table (otherwise), compared byte for byte;
+ *        no end matches: the WHOLE token is one piece (unk_id, a, e), pieces found so far are discarded;
+ *        otherwise emit (id, start, p) and set start = p.
+ * Exact as the ids call is: the hash finds the slot, the bytes decide.  V = 0 is accepted: every token is one unk piece.  A token
+ * that is itself a word gives one piece with the id latok_token_ids_utf8_bytes_batch would give.
+ * With c_s tokens in string s and the pieces of a batch numbered in the order of strings, tokens and pieces:
+ *   indptr[0] = 0, indptr[s+1] = indptr[s] + (pieces of the tokens of string s)
+ *   ids_out[r]                            = the id of piece r (int32)
+ *   spans_out[2 r], spans_out[2 r + 1]    = its byte range, relative to its string's first byte (may be NULL)
+ * latok_wordpiece_create takes HOST pointers as latok_vocab_create does and refuses, before any device work, what that call refuses
+ * and a prefix_len outside 0 .. 8 or a max_chars outside 1 .. 1024.  The object may be used by any context of its device,
+ * concurrently; latok_wordpiece_destroy drains the current context first, like latok_vocab_destroy.  latok_wordpiece_info reports the
+ * word count as given, the slots and the longest word of both tables, the prefix (8 bytes are written), max_chars, the seed and the
+ * device; any output pointer may be NULL.
+ * The calls follow the term-counts call: host pointers or LATOK_DEVICE_PTRS (device UTF-8 pointer 16-byte aligned), total_bytes =
+ * -1, check of the vocabulary's device; LATOK_OUT_INT32 applies to indptr and spans (an id is always one int32); any other flag bit
+ * is refused before any device work.  Capacity protocol, in PIECES: cap too small -> nothing is written to ids or spans, indptr
+ * stays valid, the need is in *n_pieces_out and the call returns LATOK_ERR_INVALID; cap = 0 with ids_out = NULL is a size query;
+ * ids_out = NULL with cap > 0 is refused.  A batch with 2^31 pieces or more is refused.  *n_tokens_out (may be NULL) = the token
+ * total.  n_str = 0 or total_bytes = 0 gives zero pieces with indptr cleared.  Every batch size takes the same kernels.  The
+ * calls are blocking: they wait once for the token total, which sizes the token buffers, once for the piece total, and once more
+ * for the copy of the pieces when the outputs are host pointers.
+ * The PADDED form writes what a model takes: input_ids_out is an [n_str, max_length] block of int32, row s = cls_id (if
+ * add_special), the first max_length - 2 add_special pieces of string s, sep_id (if add_special), then pad_id; lengths_out[s]
+ * (int32 in every mode) = the cells of row s in front of the padding.  max_length must be >= 1 + 2 add_special, else the call is
+ * refused; *n_pieces_out (may be NULL) = the untruncated piece total.  n_str = 0 writes nothing; total_bytes = 0 gives rows of
+ * specials and padding.  It waits for the piece total before it sizes its ids, so it waits three times.
+ * Out of scope: lower-casing, accent stripping and CJK spacing (BERT's BasicTokenizer) -- tokens are latok's, bytes are verbatim, an
+ * uncased vocabulary needs the caller to fold case first --, BPE and Unigram models, a flow form, sentence pairs. */
+typedef struct latok_wordpiece latok_wordpiece;
+int latok_wordpiece_create(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
+                           const int32_t* word_ids /* may be NULL */, const uint8_t* prefix, int prefix_len, int max_chars, uint32_t seed,
+                           latok_wordpiece** wp_out);
+int latok_wordpiece_destroy(latok_wordpiece* wp);
+int latok_wordpiece_info(const latok_wordpiece* wp, int64_t* n_words, int64_t* n_slots_initial, int64_t* n_slots_cont,
+                         int64_t* max_len_initial, int64_t* max_len_cont, uint8_t* prefix_out /* [8] */, int* prefix_len, int* max_chars,
+                         uint32_t* seed, int* device);
+int latok_wordpiece_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                         const latok_wordpiece* wp, int32_t unk_id, int64_t* indptr_out /* [n_str+1] */, int32_t* ids_out,
+                                         int64_t* spans_out /* may be NULL */, int64_t cap, int64_t* n_pieces_out,
+                                         int64_t* n_tokens_out /* may be NULL */, int flags, void* stream);
+int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                            const latok_wordpiece* wp, int32_t unk_id, int64_t max_length, int add_special, int32_t cls_id,
+                                            int32_t sep_id, int32_t pad_id, int32_t* input_ids_out /* [n_str*max_length] */,
+                                            int32_t* lengths_out /* [n_str] */, int64_t* n_pieces_out /* may be NULL */, int flags,
+                                            void* stream);
+
 /* Token counting in byte space: the vocabulary of a corpus -- every distinct token with its frequency -- built on the device.
  * The tokens of a batch are the byte slices latok_token_spans_utf8_bytes_batch reports for it (default_tokenizer.py:149-160);
  * run-time rule tables and malformed bytes are taken as that call takes them, and bytes are compared verbatim.  A COUNTER is a

@@ -729,6 +729,158 @@ def hashed_term_counts_batch(texts, n_features=1 << 20, seed=0, alternate_sign=T
     return hashed_term_counts_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], n_features, seed, alternate_sign)
 
 
+# WordPiece: every token cut greedily into the longest vocabulary prefix and ##-continuations, on the device -- the subword ids a
+# BERT-family model takes, as CSR rows or as the padded [n, L] block
+class WordPiece:
+    """A WordPiece vocabulary on the device of the current context (``latok_wordpiece_create``): ``words`` is a list of ``bytes`` or
+    ``str`` (``str`` is encoded as UTF-8 with surrogatepass), ``ids`` an optional int32 per word (default: its index), ``prefix``
+    the continuation prefix (0 .. 8 bytes, ``##`` in BERT's files), ``max_chars`` BERT's ``max_input_chars_per_word`` (1 .. 1024:
+    a token of more chars is one unknown piece), ``seed`` the 32-bit seed of the tables' hash.  Of a duplicate word the first wins.
+    Bytes are compared verbatim: there is no lower-casing and no accent stripping.  Immutable; ``len()`` is the number of words
+    given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
+
+    def __init__(self, words, ids=None, prefix=b"##", max_chars=100, seed=0):
+        self.handle = None
+        seed = _seed32(seed)
+        prefix = prefix.encode("utf-8") if isinstance(prefix, str) else bytes(prefix)
+        if len(prefix) > 8:
+            raise ValueError("prefix must be 0 .. 8 bytes")
+        if not isinstance(max_chars, (int, np.integer)) or isinstance(max_chars, bool) or not 1 <= int(max_chars) <= 1024:
+            raise ValueError("max_chars must be an int in 1 .. 1024")
+        blobs = [w.encode("utf-8", "surrogatepass") if isinstance(w, str) else bytes(w) for w in words]
+        off = np.zeros(len(blobs) + 1, np.int64)
+        if blobs:
+            np.cumsum([len(b) for b in blobs], out=off[1:])
+        data = np.frombuffer(b"".join(blobs), np.uint8)
+        if ids is not None:
+            raw = np.asarray(ids)
+            if raw.shape != (len(blobs),) or (raw.size and raw.dtype.kind not in "iu"):
+                raise ValueError("ids must be one integer per word")
+            if raw.size and (raw.min() < -0x80000000 or raw.max() > 0x7FFFFFFF):
+                raise ValueError("ids must fit int32")
+            ids = np.ascontiguousarray(raw, np.int32)
+        lib = _lib.ensure_init()
+        h = C.c_void_p()
+        pre = np.frombuffer(prefix + b"\x00", np.uint8)
+        _lib.check(lib.latok_wordpiece_create(_ptr(data) if data.size else None, _ptr(off), len(blobs), _ptr(ids) if ids is not None else None,
+                                              _ptr(pre), len(prefix), int(max_chars), seed, C.byref(h)))
+        self._lib, self.handle, self.seed, self._n = lib, h, seed, len(blobs)
+        self.prefix, self.max_chars = prefix, int(max_chars)
+
+    @classmethod
+    def from_vocab_file(cls, path, **kw):
+        """a BERT ``vocab.txt``: one word per line (UTF-8), id = line number from 0"""
+        with open(path, "rb") as f:
+            words = [line.rstrip(b"\r\n") for line in f.read().split(b"\n")]
+        if words and words[-1] == b"":
+            words.pop()                                   # (the file's last newline ends the last word, it starts none)
+        return cls(words, **kw)
+
+    def info(self):
+        """dict of what ``latok_wordpiece_info`` reports"""
+        v = [C.c_int64(0) for _ in range(5)]
+        pre, plen, mc, seed, dev = np.zeros(8, np.uint8), C.c_int(0), C.c_int(0), C.c_uint32(0), C.c_int(0)
+        _lib.check(self._lib.latok_wordpiece_info(_wordpiece_handle(self), *[C.byref(x) for x in v], _ptr(pre), C.byref(plen), C.byref(mc),
+                                                  C.byref(seed), C.byref(dev)))
+        return dict(n_words=v[0].value, n_slots_initial=v[1].value, n_slots_cont=v[2].value, max_len_initial=v[3].value,
+                    max_len_cont=v[4].value, prefix=pre[:plen.value].tobytes(), max_chars=mc.value, seed=seed.value, device=dev.value)
+
+    def __len__(self):
+        return self._n
+
+    def close(self):
+        if self.handle:
+            h, self.handle = self.handle, None
+            _lib.check(self._lib.latok_wordpiece_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _wordpiece_handle(wp):
+    if not isinstance(wp, WordPiece) or not wp.handle:
+        raise ValueError("wp must be an open latok_amd.batch.WordPiece")
+    return wp.handle
+
+
+def wordpiece_ids_utf8_csr(utf8, byte_off, wp, unk_id=-1, dtype=np.int64, spans=True):
+    """(indptr[n + 1], ids int32[n_pieces], spans[n_pieces, 2] or None): the WordPiece ids of every string -- each token (the byte
+    slices token_spans_utf8_bytes_csr reports) cut greedily into the longest word of ``wp`` and ``prefix``-continuations, or ONE
+    ``unk_id`` piece when a part of it matches nothing or it has more than ``max_chars`` chars.  spans[r] = piece r's byte range
+    inside its string.  indptr and spans in ``dtype``.  Cut and looked up on the device (``latok_wordpiece_ids_utf8_bytes_batch``):
+    the size query, then the fill."""
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    unk_id = _unk32(unk_id)
+    dt, flags = _out_dtype(dtype)
+    handle = _wordpiece_handle(wp)
+    n_str = byte_off.size - 1
+    total = int(byte_off[-1]) if n_str > 0 else 0
+    lib = _lib.ensure_init()
+    indptr = np.zeros(n_str + 1, dt)
+    n = C.c_int64(0)
+
+    def call(ids, sp, cap):
+        return lib.latok_wordpiece_ids_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, handle, unk_id, _ptr(indptr), ids, sp, cap,
+                                                        C.byref(n), None, flags, None)
+
+    rc = call(None, None, 0)
+    if rc != _lib.OK and not (rc == _lib.ERR_INVALID and n.value > 0):
+        _lib.check(rc)
+    ids = np.empty(n.value, np.int32)
+    sp = np.empty((n.value, 2), dt) if spans else None
+    if n.value > 0:
+        _lib.check(call(_ptr(ids), _ptr(sp) if spans else None, n.value))
+    return indptr, ids, sp
+
+
+def wordpiece_ids_utf8_batch(blobs, wp, unk_id=-1):
+    """list[bytes] (UTF-8) -> (indptr, ids, spans) of wordpiece_ids_utf8_csr, int64 ('' and whitespace-only -> empty rows)."""
+    unk_id = _unk32(unk_id)
+    _wordpiece_handle(wp)
+    utf8, byte_off = pack_utf8(blobs)
+    return wordpiece_ids_utf8_csr(utf8, byte_off, wp, unk_id)
+
+
+def wordpiece_ids_batch(texts, wp, unk_id=-1):
+    """list[str] -> (indptr, ids, spans): wordpiece_ids_utf8_batch of the strings' UTF-8 ("surrogatepass"); the spans are in bytes."""
+    return wordpiece_ids_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], wp, unk_id)
+
+
+def wordpiece_encode_utf8_batch(blobs, wp, max_length, cls_id=None, sep_id=None, pad_id=0, unk_id=-1):
+    """list[bytes] (UTF-8) -> (input_ids int32[n, max_length], attention_mask int32[n, max_length]): what a BERT-family model takes.
+    Row s = ``cls_id``, the first pieces of string s, ``sep_id``, then ``pad_id``; the two specials are added when BOTH are given
+    and omitted when both are None.  A longer row is truncated to ``max_length`` cells, specials included.  attention_mask is 1 on
+    the cells in front of the padding.  One call of ``latok_wordpiece_padded_utf8_bytes_batch``."""
+    unk_id, pad_id = _unk32(unk_id), _unk32(pad_id)
+    if (cls_id is None) != (sep_id is None):
+        raise ValueError("cls_id and sep_id go together: give both or neither")
+    special = cls_id is not None
+    cls_id, sep_id = (_unk32(cls_id), _unk32(sep_id)) if special else (0, 0)
+    if not isinstance(max_length, (int, np.integer)) or isinstance(max_length, bool) or not 1 + 2 * special <= int(max_length) <= 0x7FFFFFFF:
+        raise ValueError("max_length must be an int >= %d" % (1 + 2 * special))
+    handle = _wordpiece_handle(wp)
+    utf8, byte_off = pack_utf8(blobs)
+    n_str, total = len(blobs), int(byte_off[-1])
+    lib = _lib.ensure_init()
+    input_ids = np.empty((n_str, int(max_length)), np.int32)
+    lengths = np.zeros(n_str, np.int32)
+    _lib.check(lib.latok_wordpiece_padded_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, handle, unk_id, int(max_length),
+                                                           1 if special else 0, cls_id, sep_id, pad_id, _ptr(input_ids), _ptr(lengths), None,
+                                                           0, None))
+    mask = (np.arange(int(max_length), dtype=np.int32)[None, :] < lengths[:, None]).astype(np.int32)
+    return input_ids, mask
+
+
 # token counts: the vocabulary of a corpus -- every distinct token with its frequency --, counted on the device, exactly
 class TokenCounter:
     """A counting table on the device of the current context (``latok_counter_create``): at most about ``max_words`` distinct

@@ -31,6 +31,7 @@
 #include "unicode_tables.inc"
 #include "vocab_table.h"
 #include "count_table.h"
+#include "wordpiece.h"
 
 static_assert(LATOK_TBL_SHIFT == latok::kTblShift, "table shift");
 static_assert(LATOK_TBL_STAGE1_LEN == latok::kStage1Len, "stage-1 length");
@@ -178,6 +179,7 @@ struct Workspace {
     DevBuf lead, bspace, cpbits, cpspace, cprow;
     DevBuf jbody, jhead;   // joined token text: the body / head planes over the bytes (k_join_counts)
     DevBuf tkeys, tkeys2, trows;   // term counts: one key per token, the long rows' second buffer, five int64 arrays over the rows
+    DevBuf wpspans, wpcnt, wprank, wpids;   // WordPiece: per token its span record, piece count and piece rank; the padded form's ids
     // the single-pass scan of k_word_counts_scan keeps its look-back state (chain: per workgroup, chain_ctl: {ticket
     // counter}) between launches: entries carry an epoch, so the array is cleared only when it is (re)allocated or when the
     // 18-bit epoch wraps (next_scan_epoch); *_seen = DevBuf::gen of the allocations it was last cleared in
@@ -186,7 +188,7 @@ struct Workspace {
     void release() {
         for (DevBuf* b : {&summ, &seg_agg, &fix_count, &tile_first, &bits, &space, &kept, &wcnt, &wpref, &bases, &scalar, &chain,
                           &chain_ctl, &codes, &widened, &lead, &bspace, &cpbits, &cpspace, &cprow, &jbody, &jhead, &tkeys,
-                          &tkeys2, &trows})
+                          &tkeys2, &trows, &wpspans, &wpcnt, &wprank, &wpids})
             b->release();
         scan_epoch = chain_seen = chain_ctl_seen = 0;
         chain_ready = false;
@@ -197,18 +199,21 @@ struct WsNeed {
     size_t bytes;   // 0: the batch does not use the buffer
 };
 constexpr int kTileNeeds = 4;   // the first entries of ws_needs: the tile stage
-constexpr int kWsNeeds = 25;
+constexpr int kWsNeeds = 29;
 // What a batch asks of its workspace beyond the tile stage.  token spans (spans) add the SPACE and kept planes, featurize (feats)
 // the code bytes, and narrow units read by featurize (widen) a UTF-32 copy.  cp_rows > 0: the units are UTF-8 bytes whose results
 // are reported in code points (cp_rows = n_str + 1): every buffer is sized by the byte count, which bounds the code-point count.
 // join: the two planes of the joined token text (UTF-8 bytes, with spans).  term_rows > 0 (= n_str + 1): term counts -- the row
 // arrays and a scan state that also serves a scan over the rows; term_tokens: the batch's token total, which the term-count call
-// waits for before it sizes the two key buffers.
+// waits for before it sizes the two key buffers.  wp_tokens: the token total again, for the WordPiece calls (which use the first two
+// row arrays of term_rows): 16 bytes of span record, 8 of piece count and 8 of piece rank per token, one entry more in the last two,
+// and a scan state for that many entries; wp_pieces: the piece total, which the padded form waits for before it sizes its ids.
 constexpr int kTermRowArrays = 5;   // token counts, row starts, distinct counts, indptr, OOV counts
 struct WsShape {
     bool spans = false, feats = false, widen = false, join = false;
     int64_t cp_rows = 0;
     int64_t term_rows = 0, term_tokens = 0;
+    int64_t wp_tokens = 0, wp_pieces = 0;
 };
 // The one sizing rule of a workspace: every buffer a batch of `units` positions uses and its byte size.
 static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const WsShape& shape) {
@@ -229,7 +234,8 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const 
              {&w.wpref, words * 2 + 8},     // items of the tile before each word
              {&w.bases, c_tiles * 8 + 8},   // rank of each tile's first item
              {&w.scalar, 64},
-             {&w.chain, (size_t)std::max(latok::count_blocks((int64_t)words), latok::count_blocks(shape.term_rows * 64)) * 8 + 64},
+             {&w.chain, (size_t)std::max({latok::count_blocks((int64_t)words), latok::count_blocks(shape.term_rows * 64),
+                                            latok::count_blocks(shape.wp_tokens > 0 ? (shape.wp_tokens + 1) * 64 : 0)}) * 8 + 64},
              {&w.chain_ctl, 64},
              {&w.codes, feats ? (size_t)units + latok::kTile + 256 : 0},   // read (never used) up to a tile behind the last char
              {&w.widened, widen ? (size_t)units * 4 + 16 : 0},
@@ -242,7 +248,11 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const 
              {&w.jhead, join ? words * 8 + 8 : 0},
              {&w.tkeys, shape.term_tokens > 0 ? (size_t)shape.term_tokens * 8 : 0},
              {&w.tkeys2, shape.term_tokens > 0 ? (size_t)shape.term_tokens * 8 : 0},
-             {&w.trows, shape.term_rows > 0 ? (size_t)shape.term_rows * 8 * kTermRowArrays : 0}}};
+             {&w.trows, shape.term_rows > 0 ? (size_t)shape.term_rows * 8 * kTermRowArrays : 0},
+             {&w.wpspans, shape.wp_tokens > 0 ? (size_t)shape.wp_tokens * 16 : 0},
+             {&w.wpcnt, shape.wp_tokens > 0 ? (size_t)(shape.wp_tokens + 1) * 8 : 0},
+             {&w.wprank, shape.wp_tokens > 0 ? (size_t)(shape.wp_tokens + 1) * 8 : 0},
+             {&w.wpids, shape.wp_pieces > 0 ? (size_t)shape.wp_pieces * 4 : 0}}};
 }
 static int ws_ensure(const WsNeed* needs, int n) {
     for (int i = 0; i < n; ++i) {
@@ -2515,6 +2525,387 @@ int latok_hashed_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t
                               data_out, cap, nnz_out, n_tokens_out, flags, stream);
 }
 
+/* WordPiece in byte space (latok_wordpiece_ids_utf8_bytes_batch, latok_wordpiece_padded_utf8_bytes_batch): the subword ids of every
+ * token.  The vocabulary object holds two vocab_table.h tables (wordpiece.h: initial and continuation), built on the host, uploaded
+ * once, read only afterwards.  One stream, every batch size the same kernels:
+ *   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
+ *   k_word_counts + k_scan_chained                kept mask, token ranks; THE token total -> scalar word 0, pinned word 0
+ *   (wait 1)                                      the host reads the token total: 2^31 or more is refused, the token buffers are sized
+ *   k_counts_scatter (KIND 1, int64)              the span record of every token at its rank in the workspace, token count per string
+ *   k_scan_chained                                the row starts in token space
+ *   k_wp_count                                    pieces per token
+ *   k_scan_chained                                piece ranks; the piece total -> scalar word 5, pinned word 3
+ *   (padded form: wait 2)                         the piece total sizes the ids of the workspace
+ *   k_wp_emit                                     ids (and spans) at the piece rank, if the total fits the capacity
+ *   k_wp_rows / k_wp_pad                          indptr in the caller's width / the padded block and the lengths
+ *   (last wait)                                   the piece total; host pointers then copy that many pieces (one wait more)
+ * `w` was sized by ws_needs with WsShape{.spans = true, .term_rows = n_str + 1}; the call sizes the token buffers itself. */
+struct WordPiece {                 // latok_wordpiece: immutable once created
+    int device = -1;
+    int64_t n_words = 0;
+    uint64_t n_slots0 = 0, n_slots1 = 0;
+    uint32_t max_len0 = 0, max_len1 = 0;
+    uint8_t prefix[kWpMaxPrefix] = {0};
+    int prefix_len = 0, max_chars = 0;
+    uint32_t seed = 0;
+    void* d_slots0 = nullptr;      // VtSlot[n_slots0]: the initial table
+    void* d_blob0 = nullptr;
+    void* d_slots1 = nullptr;      // VtSlot[n_slots1]: the continuation table
+    void* d_blob1 = nullptr;
+    void free_device() {
+        for (void* p : {d_slots0, d_blob0, d_slots1, d_blob1})
+            if (p) (void)hipFree(p);
+        d_slots0 = d_blob0 = d_slots1 = d_blob1 = nullptr;
+    }
+};
+int latok_wordpiece_create(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, const uint8_t* prefix,
+                           int prefix_len, int max_chars, uint32_t seed, latok_wordpiece** wp_out) {
+    LATOK_ENTER();
+    // what needs no device is refused first
+    if (!wp_out) return fail(LATOK_ERR_INVALID, "wp_out is NULL");
+    *wp_out = nullptr;
+    if (n_words < 0 || n_words >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "n_words must be in 0 .. 2^31 - 1");
+    if (prefix_len < 0 || prefix_len > kWpMaxPrefix) return fail(LATOK_ERR_INVALID, "prefix_len must be in 0 .. %d", kWpMaxPrefix);
+    if (prefix_len > 0 && !prefix) return fail(LATOK_ERR_INVALID, "prefix is NULL");
+    if (max_chars < 1 || max_chars > kWpMaxChars) return fail(LATOK_ERR_INVALID, "max_chars must be in 1 .. %d", kWpMaxChars);
+    if (!word_off) return fail(LATOK_ERR_INVALID, "word_off is NULL");
+    if (word_off[0] != 0) return fail(LATOK_ERR_INVALID, "word_off must start at 0");
+    uint64_t padded = 0;
+    for (int64_t i = 0; i < n_words; ++i) {
+        if (word_off[i + 1] < word_off[i]) return fail(LATOK_ERR_INVALID, "word_off must be non-decreasing (word %lld)", (long long)i);
+        padded += ((uint64_t)(word_off[i + 1] - word_off[i]) + 3u) & ~3ull;
+        if (padded >= (1ull << 32)) return fail(LATOK_ERR_INVALID, "the padded words take 2^32 bytes or more");
+    }
+    if (word_off[n_words] > 0 && !words) return fail(LATOK_ERR_INVALID, "words is NULL");
+    int rc = need_init(g);
+    if (rc) return rc;
+    WpTables t;
+    WordPiece* v = nullptr;
+    try {
+        wp_build(words, word_off, n_words, word_ids, prefix, prefix_len, seed, &t);
+        v = new WordPiece();
+    } catch (const std::bad_alloc&) {
+        return fail(LATOK_ERR_NOMEM, "out of host memory");
+    }
+    v->device = g.device;
+    v->n_words = n_words;
+    v->n_slots0 = t.initial.slots.size();
+    v->n_slots1 = t.cont.slots.size();
+    v->max_len0 = t.max_len0;
+    v->max_len1 = t.max_len1;
+    for (int i = 0; i < prefix_len; ++i) v->prefix[i] = prefix[i];
+    v->prefix_len = prefix_len;
+    v->max_chars = max_chars;
+    v->seed = seed;
+    const size_t sb0 = t.initial.slots.size() * sizeof(VtSlot), bb0 = t.initial.blob.size() * 4;
+    const size_t sb1 = t.cont.slots.size() * sizeof(VtSlot), bb1 = t.cont.blob.size() * 4;
+    hipError_t e = hipMalloc(&v->d_slots0, sb0);
+    if (e == hipSuccess) e = hipMalloc(&v->d_blob0, bb0);
+    if (e == hipSuccess) e = hipMalloc(&v->d_slots1, sb1);
+    if (e == hipSuccess) e = hipMalloc(&v->d_blob1, bb1);
+    if (e != hipSuccess) {
+        v->free_device();
+        delete v;
+        return fail(LATOK_ERR_NOMEM, "hipMalloc(%zu) failed: %s", sb0 + bb0 + sb1 + bb1, hipGetErrorString(e));
+    }
+    e = hipMemcpyAsync(v->d_slots0, t.initial.slots.data(), sb0, hipMemcpyHostToDevice, g.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(v->d_blob0, t.initial.blob.data(), bb0, hipMemcpyHostToDevice, g.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(v->d_slots1, t.cont.slots.data(), sb1, hipMemcpyHostToDevice, g.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(v->d_blob1, t.cont.blob.data(), bb1, hipMemcpyHostToDevice, g.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);   // (the host tables die with this call, and every context may use the object at once)
+    if (e != hipSuccess) {
+        v->free_device();
+        delete v;
+        return fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
+    }
+    *wp_out = reinterpret_cast<latok_wordpiece*>(v);
+    return LATOK_OK;
+}
+
+int latok_wordpiece_destroy(latok_wordpiece* wp) {
+    LATOK_ENTER();
+    WordPiece* v = reinterpret_cast<WordPiece*>(wp);
+    if (!v) return LATOK_OK;
+    int rc = LATOK_OK;
+    if (g.inited) {   // the current context's own work on it: its stream and its flow
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        rc = flow_drain(g);
+    }
+    v->free_device();
+    delete v;
+    return rc;
+}
+
+int latok_wordpiece_info(const latok_wordpiece* wp, int64_t* n_words, int64_t* n_slots_initial, int64_t* n_slots_cont, int64_t* max_len_initial,
+                         int64_t* max_len_cont, uint8_t* prefix_out, int* prefix_len, int* max_chars, uint32_t* seed, int* device) {
+    const WordPiece* v = reinterpret_cast<const WordPiece*>(wp);
+    if (!v) return fail(LATOK_ERR_INVALID, "wp is NULL");
+    if (n_words) *n_words = v->n_words;
+    if (n_slots_initial) *n_slots_initial = (int64_t)v->n_slots0;
+    if (n_slots_cont) *n_slots_cont = (int64_t)v->n_slots1;
+    if (max_len_initial) *max_len_initial = v->max_len0;
+    if (max_len_cont) *max_len_cont = v->max_len1;
+    if (prefix_out) memcpy(prefix_out, v->prefix, kWpMaxPrefix);
+    if (prefix_len) *prefix_len = v->prefix_len;
+    if (max_chars) *max_chars = v->max_chars;
+    if (seed) *seed = v->seed;
+    if (device) *device = v->device;
+    return LATOK_OK;
+}
+
+struct WordPieceCall {
+    Batch b;                       // UTF-8 bytes on the device (16-byte aligned), byte offsets, total in bytes (> 0), n_str > 0
+    const WordPiece* wp = nullptr;
+    int32_t unk = 0;
+    void* indptr = nullptr;        // [n_str + 1]; NULL: the padded form
+    int32_t* ids = nullptr;        // NULL: a size query (ids form)
+    void* spans = nullptr;         // NULL: not asked for
+    int64_t cap = 0;               // in pieces
+    bool o32 = false;              // width of indptr and spans
+    bool padded = false;           // the padded form: the ids go to the workspace, then k_wp_pad
+    int64_t max_length = 0;
+    int add_special = 0;
+    int32_t cls_id = 0, sep_id = 0, pad_id = 0;
+    int32_t* input_ids = nullptr;  // [n_str * max_length]
+    int32_t* lengths = nullptr;    // [n_str]
+    int64_t* p_tot = nullptr;      // the pinned words as the device sees them (cleared by the caller): 0 tokens, 1 flags, 3 pieces
+    volatile int64_t* h_tot = nullptr;
+    int64_t n_tokens = 0;          // (out) the token total
+    hipStream_t st = nullptr;
+};
+static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
+    int rc;
+    const hipStream_t st = a.st;
+    const int64_t total = a.b.total, words = (total + 63) / 64, n_str = a.b.n_str;
+    uint64_t* d_bits = (uint64_t*)w.bits.p;
+    uint64_t* d_space = (uint64_t*)w.space.p;
+    uint64_t* d_kept = (uint64_t*)w.kept.p;
+    int64_t* d_rank = (int64_t*)w.bases.p;
+    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
+    uint16_t* d_pref = (uint16_t*)w.wpref.p;
+    int64_t* d_total = (int64_t*)w.scalar.p;
+    int* d_err = (int*)(a.p_tot + 1);
+    unsigned epoch = 0;
+    Pipe p;
+    p.b = a.b;
+    p.bits = d_bits;
+    p.space = d_space;
+    p.st = st;
+    if ((rc = run_pipeline(g, w, p))) return rc;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    HIP_TRY(latok::launch_word_counts_scan(true, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank, (unsigned long long*)w.chain.p,
+                                           (unsigned*)w.chain_ctl.p, epoch, d_total, a.p_tot, d_err + 1, st));
+    HIP_TRY(hipStreamSynchronize(st));   // wait 1: the token total decides whether the call goes on and what the token buffers take
+    if ((rc = finish_totals(w, a.h_tot, 0, &a.n_tokens))) return rc;
+    const int64_t n_tok = a.n_tokens;
+    if (n_tok >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld tokens: a call takes fewer than 2^31 pieces", (long long)n_tok);
+    if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok}).data(), kWsNeeds)))
+        return rc;
+    int64_t* d_cnt = (int64_t*)w.trows.p;       // token count of every string, one zero entry behind them
+    int64_t* d_start = d_cnt + (n_str + 1);     // their exclusive scan: d_start[n_str] = the token total
+    int64_t* d_pcnt = (int64_t*)w.wpcnt.p;
+    int64_t* d_prank = (int64_t*)w.wprank.p;
+    const int32_t* d_ids = a.ids;
+    if (n_tok > 0) {
+        HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)(n_str + 1) * 8, st));
+        int64_t* d_tspans = (int64_t*)w.wpspans.p;
+        HIP_TRY(latok::launch_counts_scatter(1, false, d_bits, d_space, d_kept, d_rank, d_tcnt, d_pref, words, total, a.b.row, n_str,
+                                             (const int64_t*)w.tile_first.p, d_tspans, d_total, n_tok, d_cnt, d_err, st));
+        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+        HIP_TRY(latok::launch_tile_scan(d_cnt, n_str + 1, d_start, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 4,
+                                        nullptr, d_err + 1, st));
+        latok::WordPieceTables wt;
+        wt.initial = latok::VocabTable{a.wp->d_slots0, (const uint32_t*)a.wp->d_blob0, a.wp->n_slots0, a.wp->seed};
+        wt.cont = latok::VocabTable{a.wp->d_slots1, (const uint32_t*)a.wp->d_blob1, a.wp->n_slots1, a.wp->seed};
+        wt.max_len0 = a.wp->max_len0;
+        wt.max_len1 = a.wp->max_len1;
+        wt.max_chars = a.wp->max_chars;
+        const uint8_t* u8 = (const uint8_t*)a.b.in.p;
+        HIP_TRY(latok::launch_wp_count(u8, total, a.b.row, n_str, d_start, d_tspans, n_tok, wt, d_pcnt, st));
+        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+        HIP_TRY(latok::launch_tile_scan(d_pcnt, n_tok + 1, d_prank, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 5,
+                                        a.p_tot + 3, d_err + 1, st));
+        int32_t* ids = a.ids;
+        int64_t cap = a.cap;
+        if (a.padded) {
+            HIP_TRY(hipStreamSynchronize(st));   // wait 2 (padded form): the piece total sizes the ids
+            int64_t n_tok_again = 0;
+            if ((rc = finish_totals(w, a.h_tot, 0, &n_tok_again))) return rc;
+            cap = a.h_tot[3];
+            if (cap >= (1ll << 31)) return LATOK_OK;   // (the caller refuses it)
+            if ((rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok, .wp_pieces = cap}).data(),
+                                kWsNeeds)))
+                return rc;
+            ids = (int32_t*)w.wpids.p;
+            d_ids = ids;
+        }
+        if (ids)
+            HIP_TRY(latok::launch_wp_emit(a.o32, u8, total, a.b.row, n_str, d_start, d_tspans, n_tok, wt, a.unk, d_prank, d_total + 5, cap, ids,
+                                          a.spans, st));
+        if (a.indptr) HIP_TRY(latok::launch_wp_rows(a.o32, d_start, d_prank, n_str, n_tok, a.indptr, st));
+    } else if (a.indptr) {
+        HIP_TRY(hipMemsetAsync(a.indptr, 0, (size_t)(n_str + 1) * (a.o32 ? 4 : 8), st));   // (no token: every row is empty)
+    }
+    if (a.padded)
+        HIP_TRY(latok::launch_wp_pad(d_ids, d_start, n_tok > 0 ? d_prank : nullptr, n_str, n_tok, a.max_length, a.add_special, a.cls_id, a.sep_id, a.pad_id,
+                                     a.input_ids, a.lengths, st));
+    return LATOK_OK;
+}
+// the WordPiece object of a call: there is one, and it lives on the device of the context that runs the call
+static int check_wordpiece(const Ctx& g, const latok_wordpiece* wp, const WordPiece** v) {
+    *v = reinterpret_cast<const WordPiece*>(wp);
+    if (!*v) return fail(LATOK_ERR_INVALID, "wp is NULL");
+    if ((*v)->device != g.device)
+        return fail(LATOK_ERR_INVALID, "the vocabulary lives on device %d, the current context on device %d", (*v)->device, g.device);
+    return LATOK_OK;
+}
+
+int latok_wordpiece_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                         const latok_wordpiece* wp, int32_t unk_id, int64_t* indptr_out, int32_t* ids_out, int64_t* spans_out,
+                                         int64_t cap, int64_t* n_pieces_out, int64_t* n_tokens_out, int flags, void* stream) {
+    LATOK_ENTER();
+    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (!n_pieces_out) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
+    *n_pieces_out = 0;
+    if (n_tokens_out) *n_tokens_out = 0;
+    if (!indptr_out) return fail(LATOK_ERR_INVALID, "indptr_out is NULL");
+    if (cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
+    if (!ids_out && cap > 0) return fail(LATOK_ERR_INVALID, "ids_out is NULL but cap > 0 (a size query passes cap = 0)");
+    const WordPiece* v = nullptr;
+    if ((rc = check_wordpiece(g, wp, &v))) return rc;
+    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0, o32 = (flags & LATOK_OUT_INT32) != 0;
+    const size_t elt = o32 ? 4 : 8;   // width of indptr and of one field of a span (an id is 4 bytes in every mode)
+    int64_t total = total_bytes;
+    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
+    StreamTurn turn(g, stream);
+    hipStream_t st = turn.st;
+    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
+    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (dev && ((uintptr_t)indptr_out & (elt - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    if (n_str == 0 || total == 0) return zero_counts(dev, indptr_out, (size_t)(n_str + 1) * elt, st, true);   // no byte, no piece
+    if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    if (dev && (((uintptr_t)spans_out & (2 * elt - 1)) != 0 || ((uintptr_t)ids_out & 3) != 0)) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    g.last_route = 11;
+    Batch d;
+    if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
+    if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true, .term_rows = n_str + 1}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+    WordPieceCall a;
+    a.b = d;
+    a.wp = v;
+    a.unk = unk_id;
+    a.indptr = indptr_out;
+    a.ids = ids_out;
+    a.spans = ids_out ? spans_out : nullptr;
+    // (a piece has at least one byte: a larger capacity gates nothing, and the staging is sized by it; 2^31 pieces or more are refused)
+    a.cap = ids_out ? std::min({cap, total, (int64_t)0x7FFFFFFF}) : 0;
+    a.o32 = o32;
+    if (!dev) {
+        if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 2 * elt + 16)) || (rc = g.counts.ensure((size_t)(n_str + 1) * 8)))
+            return rc;
+        if (ids_out) a.ids = (int32_t*)g.h_aux.p;
+        if (a.spans) a.spans = g.h_out.p;
+        a.indptr = g.counts.p;
+    }
+    h_tot[0] = h_tot[1] = h_tot[3] = 0;
+    a.p_tot = (int64_t*)g.pin_tot.d;
+    a.h_tot = h_tot;
+    a.st = st;
+    if ((rc = enqueue_wordpiece(g, g.ws, a))) return rc;
+    if (!dev) HIP_TRY(hipMemcpyAsync(indptr_out, a.indptr, (size_t)(n_str + 1) * elt, hipMemcpyDeviceToHost, st));   // valid whatever the capacity
+    HIP_TRY(hipStreamSynchronize(st));   // wait 2
+    int64_t n_tok = 0;
+    if ((rc = finish_totals(g.ws, h_tot, 0, &n_tok))) return rc;
+    if (n_tokens_out) *n_tokens_out = n_tok;
+    const int64_t n = h_tot[3];
+    *n_pieces_out = n;
+    if (n >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld pieces: a call takes fewer than 2^31", (long long)n);
+    if (n > cap) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld pieces", (long long)n);
+    if (!dev && n > 0 && ids_out) {   // (host pointers: the copies, whose size is known only now)
+        HIP_TRY(hipMemcpyAsync(ids_out, a.ids, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        if (spans_out) HIP_TRY(hipMemcpyAsync(spans_out, a.spans, (size_t)n * 2 * elt, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));   // wait 3
+    }
+    return LATOK_OK;
+}
+
+int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                            const latok_wordpiece* wp, int32_t unk_id, int64_t max_length, int add_special, int32_t cls_id,
+                                            int32_t sep_id, int32_t pad_id, int32_t* input_ids_out, int32_t* lengths_out, int64_t* n_pieces_out,
+                                            int flags, void* stream) {
+    LATOK_ENTER();
+    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (n_pieces_out) *n_pieces_out = 0;
+    const int sp = add_special ? 1 : 0;
+    if (max_length < 1 + 2 * sp || max_length > 0x7FFFFFFF) return fail(LATOK_ERR_INVALID, "max_length must be in %d .. 2^31 - 1", 1 + 2 * sp);
+    const WordPiece* v = nullptr;
+    if ((rc = check_wordpiece(g, wp, &v))) return rc;
+    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0;
+    int64_t total = total_bytes;
+    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
+    StreamTurn turn(g, stream);
+    hipStream_t st = turn.st;
+    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
+    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (n_str == 0) return LATOK_OK;
+    if (n_str > (1ll << 40) / max_length) return fail(LATOK_ERR_INVALID, "n_str * max_length must not exceed 2^40");
+    if (!input_ids_out || !lengths_out) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (dev && ((((uintptr_t)input_ids_out | (uintptr_t)lengths_out) & 3) != 0)) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    if (dev && total > 0 && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    g.last_route = 12;
+    const size_t cells = (size_t)n_str * (size_t)max_length;
+    int32_t* d_block = input_ids_out;
+    int32_t* d_len = lengths_out;
+    if (!dev) {
+        if ((rc = g.h_out.ensure(cells * 4 + 16)) || (rc = g.counts.ensure((size_t)(n_str + 1) * 8))) return rc;
+        d_block = (int32_t*)g.h_out.p;
+        d_len = (int32_t*)g.counts.p;
+    }
+    int64_t n = 0;
+    if (total == 0) {   // no byte, no piece: every row is its specials and padding
+        HIP_TRY(latok::launch_wp_pad(nullptr, nullptr, nullptr, n_str, 0, max_length, sp, cls_id, sep_id, pad_id, d_block, d_len, st));
+    } else {
+        Batch d;
+        if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
+        if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true, .term_rows = n_str + 1}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+        volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+        WordPieceCall a;
+        a.b = d;
+        a.wp = v;
+        a.unk = unk_id;
+        a.padded = true;
+        a.max_length = max_length;
+        a.add_special = sp;
+        a.cls_id = cls_id;
+        a.sep_id = sep_id;
+        a.pad_id = pad_id;
+        a.input_ids = d_block;
+        a.lengths = d_len;
+        h_tot[0] = h_tot[1] = h_tot[3] = 0;
+        a.p_tot = (int64_t*)g.pin_tot.d;
+        a.h_tot = h_tot;
+        a.st = st;
+        if ((rc = enqueue_wordpiece(g, g.ws, a))) return rc;
+        n = h_tot[3];   // (read behind wait 2 of the padded form; 0 when the batch has no token)
+        if (n_pieces_out) *n_pieces_out = n;
+        if (n >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld pieces: a call takes fewer than 2^31", (long long)n);
+    }
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(input_ids_out, d_block, cells * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(lengths_out, d_len, (size_t)n_str * 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // the last wait
+    if (total > 0) {
+        int64_t n_tok = 0;
+        if ((rc = finish_totals(g.ws, (volatile int64_t*)g.pin_tot.h, 0, &n_tok))) return rc;
+    }
+    return LATOK_OK;
+}
+
 /* token counting in byte space: a mutable, exact counting table on the device (count_table.h), filled by k_count_scatter and made
  * independent of the caller's text by the two commit launches before the call returns.  One stream:
  *   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
@@ -3221,6 +3612,17 @@ extern "C" int latok_debug_terms_limits(int64_t* out, int n) {
     return k;
 }
 
+/* test hook (not part of the ABI; needs no device): the constants of the WordPiece calls: out[0] = kWpBlock (tokens per workgroup of
+ * k_wp_count / k_wp_emit), out[1] = entries per workgroup of the chained scan over the piece counts (one scan block), out[2] =
+ * kWpMaxPrefix, out[3] = kWpMaxChars.  Returns the number of values written. */
+extern "C" int latok_debug_wordpiece_limits(int64_t* out, int n) {
+    const int64_t v[4] = {latok::kWpBlock, latok::scan_chunk(), kWpMaxPrefix, kWpMaxChars};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 4 ? n : 4;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
 // LaunchPlan as the hooks report it: out[0..11] = n_cu_eff, seg_tiles, n_segs, rounds, grid of k_tiles_main, grid of
 // k_resolve_fix, fast_tail, pf, wpb, nw, one_launch, n_tiles
 static int put_plan(const latok::LaunchPlan& L, int64_t n_tiles, int64_t* out, int n) {
@@ -3281,7 +3683,8 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
  * 4: featurize of UTF-8 in byte space (byte records from the byte-space masks, sums from the packed code-point masks),
  * 5: joined token text of UTF-8 in byte space (every batch size; there is no small-batch route),
  * 6: token hashes of UTF-8 in byte space (every batch size as well); 7: token ids of UTF-8 in byte space (likewise);
- * 9 / 10: term counts of UTF-8 in byte space, vocabulary form / hashed form (likewise) */
+ * 9 / 10: term counts of UTF-8 in byte space, vocabulary form / hashed form (likewise);
+ * 11 / 12: WordPiece ids of UTF-8 in byte space, CSR form / padded form (likewise) */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;

@@ -1384,6 +1384,7 @@ hipError_t launch_join_scatter(const uint8_t* u8, int64_t total, const uint64_t*
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
+int64_t scan_chunk() { return kChainChunk; }
 int64_t count_blocks(int64_t n_words) { return n_words > 0 ? ((n_words + 63) / 64 + kChainChunk - 1) / kChainChunk : 0; }
 
 hipError_t launch_word_counts_scan(bool spans, const uint64_t* bits, const uint64_t* space, int64_t n_words, int64_t total,

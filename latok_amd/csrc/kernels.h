@@ -224,6 +224,7 @@ hipError_t launch_exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int
                                  hipStream_t st, int64_t* total_host = nullptr);
 // compact_kernels.hip: word-parallel compaction (offsets / token spans / featurize spans)
 int64_t count_blocks(int64_t n_words);   // workgroups of launch_word_counts_scan = entries of its `chain` state
+int64_t scan_chunk();                  // kChainChunk: entries one workgroup of the chained scan takes (latok_debug_wordpiece_limits)
 hipError_t launch_word_counts_scan(bool spans, const uint64_t* bits, const uint64_t* space, int64_t n_words, int64_t total,
                                    uint64_t* kept, int64_t* tile_cnt, uint16_t* word_pref, int64_t* tile_rank,
                                    unsigned long long* chain, unsigned* ticket, unsigned epoch, int64_t* total_dev,
@@ -336,6 +337,28 @@ hipError_t launch_terms_emit(const uint64_t* keys, const int64_t* row_start, int
                              const int64_t* indptr, const int64_t* nnz_dev, int64_t cap, int32_t* indices, int32_t* data, hipStream_t st);
 hipError_t launch_terms_finish(bool out32, const int64_t* indptr, const int64_t* oov, int64_t n_str, void* indptr_out, void* oov_out,
                                hipStream_t st);
+// WordPiece ids of a UTF-8 batch in byte space (wordpiece_kernels.hip), in token space, one lane per token: behind KIND 1 of
+// launch_counts_scatter (int64 span records at rank in the workspace, int64 token count per string) and the scan of those counts
+// (row_start[n_str + 1]).  launch_wp_count leaves the pieces of every token in cnt[0 .. n_tok) and 0 in cnt[n_tok]; the caller scans
+// the n_tok + 1 entries into rank[] (rank[n_tok] = the piece total); launch_wp_emit walks every token again and stores ids, and
+// string-relative spans if asked for, at the piece rank, only if the total fits cap; launch_wp_rows types indptr[s] =
+// rank[row_start[s]], s = 0 .. n_str.  launch_wp_pad fills an [n_str, max_length] int32 block from the ids: cls (if add_special),
+// the first max_length - 2 add_special pieces of the row, sep (if add_special), pad; lengths[s] = cells used.  rank == NULL there:
+// a batch without a token, every row is empty.  The tables are device memory, read only.
+constexpr int kWpBlock = 256;   // tokens per workgroup of k_wp_count / k_wp_emit (latok_debug_wordpiece_limits)
+struct WordPieceTables {
+    VocabTable initial, cont;         // (the seed is the same in both)
+    uint32_t max_len0 = 0, max_len1 = 0;
+    int max_chars = 0;
+};
+hipError_t launch_wp_count(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
+                           const int64_t* tok_spans, int64_t n_tok, const WordPieceTables& wt, int64_t* cnt, hipStream_t st);
+hipError_t launch_wp_emit(bool out32, const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
+                          const int64_t* tok_spans, int64_t n_tok, const WordPieceTables& wt, int32_t unk_id, const int64_t* rank,
+                          const int64_t* n_pieces_dev, int64_t cap, int32_t* ids, void* spans, hipStream_t st);
+hipError_t launch_wp_rows(bool out32, const int64_t* row_start, const int64_t* rank, int64_t n_str, int64_t n_tok, void* indptr_out, hipStream_t st);
+hipError_t launch_wp_pad(const int32_t* ids, const int64_t* row_start, const int64_t* rank, int64_t n_str, int64_t n_tok, int64_t max_length, int add_special,
+                         int32_t cls_id, int32_t sep_id, int32_t pad_id, int32_t* input_ids, int32_t* lengths, hipStream_t st);
 // the commit behind it: (a) the padded dwords of the fresh slots -> ctl[0]; (b) their bytes into the blob, resident words stored
 hipError_t launch_count_commit_sum(const CountTable& ct, hipStream_t st);
 hipError_t launch_count_commit_copy(const uint8_t* u8, const CountTable& ct, hipStream_t st);

@@ -41,6 +41,13 @@
   bytes_terms32 / bytes_terms_hashed   latok_term_counts_utf8_bytes_batch (the vocabulary of the ids paths, --vocab all|half) /
                   latok_hashed_term_counts_utf8_bytes_batch (2^20 features, alternating signs): the CSR rows of the document-term
                   matrix with int32 indptr (and oov), capacity = the token total; same process run as bytes_ids32 and bytes_hashes32
+  bytes_wp32 / bytes_wp_padded   latok_wordpiece_ids_utf8_bytes_batch (int32 indptr and spans, capacity = the token bound) /
+                  latok_wordpiece_padded_utf8_bytes_batch ([n, 64] block with [CLS] / [SEP]) against a WordPiece vocabulary of the words
+                  of the ids paths (--vocab all|half; no continuation words, so a token is one piece: with `all` its id, with `half`
+                  every second distinct token misses at every candidate end); same process run as bytes_ids32 and bytes_spans32
+  py_wp          end to end in Python on host blobs (the first --py-strings strings): batch.wordpiece_ids_utf8_batch(blobs, wp) against
+                  batch.tokenize_utf8_batch(blobs) + the greedy longest-match loop over a dict; the vocabulary there also holds 2-byte
+                  stems and ##-suffixes, so tokens do split; one line each
   py_terms       end to end in Python on host blobs (the first --py-strings strings): batch.term_counts_utf8_batch(blobs, vocab)
                   against batch.tokenize_utf8_batch(blobs) + a dict and collections.Counter per row; one line each
   py_count       end to end in Python on host blobs (the first --py-strings strings): TokenCounter.update_utf8 + most_common()
@@ -396,7 +403,7 @@ def main():
     join_leg = [p for p in paths if p in ("bytes_join", "bytes_join_flow", "bytes_spans32", "bytes_spans32_flow", "bytes_hashes32",
                                           "bytes_hashes32_flow", "bytes_hashes_only", "bytes_hashes_only_flow", "bytes_ids32", "bytes_ids32_flow",
                                           "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "py_terms",
-                                          "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join")]
+                                          "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join", "bytes_wp32", "bytes_wp_padded", "py_wp")]
     if join_leg:
         jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64, cap * 4, cap * 4)]
         if not all(jb):
@@ -417,7 +424,7 @@ def main():
 
         note_i = ("UTF-8 bytes + 8 B/string read, the bytes of every token read once more, one 16-byte slot per probe step and the word of a "
                   "candidate read from the table; 4 B/token written (exact id, --vocab " + args.vocab + ")")
-        vocab_box = []
+        vocab_box, words_box = [], []
 
         def corpus_vocab():
             """the vocabulary of the ids paths, built once: distinct tokens in order of first appearance, told apart by two hashes"""
@@ -445,6 +452,7 @@ def main():
                               "n_slots": v.n_slots, "table_MiB": v.n_slots * 16 / 2**20, "word_bytes": sum(map(len, words)),
                               "create_ms": (time.perf_counter() - t) * 1e3}), flush=True)
             vocab_box.append(v)
+            words_box.append(words)
             return v
 
         def ids_blocking(rec):
@@ -467,6 +475,38 @@ def main():
                                                                      None, D32, None)
             return lib.latok_term_counts_utf8_bytes_batch(d_u8, d_boff, n, n8, corpus_vocab().handle, t_indptr, t_oov, h_a, h_b, cap, C.byref(nout),
                                                           None, D32, None)
+
+        note_w = ("UTF-8 bytes + 8 B/string read; 4 B/string indptr + 4 B/piece ids + 8 B/piece spans written (--vocab " + args.vocab + "). NOT "
+                  "counted: the workspace traffic (16 B/token span records, 8 B/token piece counts, 8 B/token piece ranks, each written "
+                  "once and read once or twice), the two walks of every token's bytes and the table reads of every candidate end")
+        WP_LEN = 64
+        wp_box = []
+
+        def corpus_wordpiece():
+            """the WordPiece vocabulary of the wp paths, built once: the words of the ids paths (no continuation words: a token is one
+            piece, its own id or unk -- with --vocab half every second distinct token misses at every candidate end)"""
+            if not wp_box:
+                from latok_amd import batch
+                corpus_vocab()
+                t = time.perf_counter()
+                w = batch.WordPiece(words_box[0], max_chars=100, seed=SEED)
+                print(json.dumps(dict(w.info(), prefix="##", wordpiece=args.vocab, workload=args.workload,
+                                      create_ms=(time.perf_counter() - t) * 1e3)), flush=True)
+                bufs = [lib.latok_dev_alloc(sz) for sz in ((n + 1) * 4 + 64, n * WP_LEN * 4 + 64, n * 4 + 64)]
+                if not all(bufs):
+                    raise RuntimeError(_lib.last_error())
+                wp_box.extend([w] + bufs)
+            return wp_box
+
+        def wp_blocking():
+            w, w_indptr, _, _ = corpus_wordpiece()
+            return lib.latok_wordpiece_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, w.handle, -1, w_indptr, h_a, s_items, cap, C.byref(nout), None,
+                                                            D32, None)
+
+        def wp_padded_blocking():
+            w, _, w_block, w_len = corpus_wordpiece()
+            return lib.latok_wordpiece_padded_utf8_bytes_batch(d_u8, d_boff, n, n8, w.handle, -1, WP_LEN, 1, 101, 102, 0, w_block, w_len,
+                                                               C.byref(nout), D, None)
 
         note_c = ("UTF-8 bytes + 8 B/string read, the bytes of every token read once more, one 8-byte slot per probe step and the word of a "
                   "candidate read from the text or the blob; per tile and distinct word one 8-byte atomic add; two passes over the slots")
@@ -567,6 +607,62 @@ def main():
                                                                              h_b if i & 1 else h_a, cap, resj(i), _lib.OUT_INT32),
                          lambda: n8 + csr + 4 * items_n + (4 * n + 8 * items_n if rec else 0), note_i + (" + " + note_s if rec else ""))
                 two_words(name, items_n)
+            elif name == "bytes_wp32":   # (items = pieces)
+                run(name, wp_blocking, lambda: n8 + csr + 4 * n + 12 * nout.value, note_w)
+            elif name == "bytes_wp_padded":   # (items = the untruncated piece total; the block is [n, WP_LEN] with [CLS] / [SEP])
+                run(name, wp_padded_blocking, lambda: n8 + csr + 4 * n + 4 * n * WP_LEN,
+                    note_w.replace("4 B/string indptr + 4 B/piece ids + 8 B/piece spans", "4 B/string lengths + 4 B/cell of the [n, %d] block" % WP_LEN))
+            elif name == "py_wp":   # host blobs in, the CSR arrays out, both routes in this process
+                from latok_amd import batch
+                m = min(args.py_strings, n)
+                blob = u8[:int(boff[m])].tobytes()
+                blobs = [blob[int(a):int(b)] for a, b in zip(boff[:m], boff[1:m + 1])]
+                distinct = list(dict.fromkeys(t for row in batch.tokenize_utf8_batch(blobs) for t in row))
+                words = distinct[::2] if args.vocab == "half" else distinct
+                words = words + [b"##" + w[2:] for w in words[::3] if len(w) > 3] + list(dict.fromkeys(w[:2] for w in words))
+                d = {}
+                for i, w in enumerate(words):
+                    d.setdefault(w, i)
+
+                def cut(tok):
+                    if sum((b & 0xC0) != 0x80 for b in tok[1:]) + 1 > 100:
+                        return [-1]
+                    out, start, n_tok = [], 0, len(tok)
+                    while start < n_tok:
+                        for e in range(n_tok, start, -1):
+                            if e < n_tok and (tok[e] & 0xC0) == 0x80:
+                                continue
+                            pid = d.get(tok[start:e] if start == 0 else b"##" + tok[start:e])
+                            if pid is not None:
+                                break
+                        else:
+                            return [-1]
+                        out.append(pid)
+                        start = e
+                    return out
+
+                def on_host():
+                    indptr, ids = [0], []
+                    for row in batch.tokenize_utf8_batch(blobs):
+                        for tok in row:
+                            ids.extend(cut(tok))
+                        indptr.append(len(ids))
+                    return np.array(indptr, np.int64), np.array(ids, np.int32)
+
+                with batch.WordPiece(words, seed=SEED) as w:
+                    routes = (("py_wordpiece_ids_utf8_batch", lambda: batch.wordpiece_ids_utf8_batch(blobs, w)[:2]),
+                              ("py_tokenize_utf8_batch_then_wordpiece_loop", on_host))
+                    assert all(np.array_equal(a, b) for a, b in zip(routes[0][1](), routes[1][1]()))
+                    for r in range(args.repeat):
+                        for rname, fn in routes:
+                            t = time.perf_counter()
+                            got = fn()
+                            dt = time.perf_counter() - t
+                            print(json.dumps({"path": rname, "workload": args.workload, "strings": m, "utf8_bytes": len(blob), "vocab": args.vocab,
+                                              "words": len(words), "pieces": int(got[1].size), "unk": int((got[1] == -1).sum()), "ms_per_call": dt * 1e3,
+                                              "utf8_GBps": len(blob) / dt / 1e9,
+                                              "note": "end to end in Python: list[bytes] in, (indptr, ids) out, pack and host work included",
+                                              "repeat": r}), flush=True)
             elif name in ("bytes_terms32", "bytes_terms_hashed"):   # (items = nnz; the keys are sized by the token total)
                 hashed = name == "bytes_terms_hashed"
                 run(name, lambda: terms_blocking(hashed), lambda: n8 + csr + 4 * n + (0 if hashed else 4 * n) + 8 * nout.value, note_t)
@@ -677,6 +773,10 @@ def main():
             vocab_box[0].close()
         if counter_box:
             counter_box[0].close()
+        if wp_box:
+            wp_box[0].close()
+            for p_ in wp_box[1:]:
+                lib.latok_dev_free(p_)
         for p_ in terms_box:
             lib.latok_dev_free(p_)
         for p_ in jb:
