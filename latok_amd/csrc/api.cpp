@@ -18,8 +18,10 @@
 #include <array>
 #include <atomic>
 #include <chrono>
+#include <initializer_list>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -561,6 +563,88 @@ int finish_totals(Workspace& w, const volatile int64_t* h, int64_t o32_mask, int
     if (h[1] >> 32) { w.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the scan's look-back state was corrupt (the call is safe to repeat)"); }
     if (h[1] & o32_mask) return refuse_too_long();
     *total_out = h[0];
+    return LATOK_OK;
+}
+
+// The frame of a blocking byte-space call on a UTF-8 batch, in two steps with the entry's own checks between them.  The entry keeps
+// its flag check, need_init and argument checks ahead of open(), answers the empty batch itself and checks its outputs' alignment
+// ahead of stage().  The StreamTurn lives as long as the frame: declare it behind every lock the call takes.
+struct BytesCall {
+    bool dev = false, o32 = false;
+    size_t elt = 8;                       // width of the outputs that follow LATOK_OUT_INT32
+    std::optional<StreamTurn> turn;
+    hipStream_t st = nullptr;
+    int64_t total = 0;                    // the batch's bytes, resolved
+    bool empty = true;                    // no string or no byte: nothing is launched
+    Batch b;                              // the caller's batch ...
+    Batch d;                              // ... and the same on the device (stage)
+    volatile int64_t* h_tot = nullptr;    // the context's pinned words as the host sees them (stage) ...
+    int64_t* p_tot = nullptr;             // ... and the device
+    // host row offsets are checked before the call takes its turn on the stream, device row offsets resolved on it
+    int open(Ctx& g, const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, int flags, void* stream) {
+        int rc;
+        const bool dev_ptrs = (flags & LATOK_DEVICE_PTRS) != 0;
+        if (!dev_ptrs && (rc = check_csr_host(byte_off, n_str, &total_bytes))) return rc;
+        turn.emplace(g, stream);
+        if (dev_ptrs && (rc = resolve_total_device(byte_off, n_str, &total_bytes, turn->st))) return rc;
+        if (total_bytes > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
+        adopt(Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total_bytes}, dev_ptrs, (flags & LATOK_OUT_INT32) != 0, turn->st);
+        return LATOK_OK;
+    }
+    // a batch that was checked and resolved elsewhere (compact_common), on that call's turn
+    void adopt(const Batch& batch, bool dev_ptrs, bool out32, hipStream_t stream) {
+        dev = dev_ptrs;
+        o32 = out32;
+        elt = o32 ? 4 : 8;
+        st = stream;
+        b = batch;
+        total = batch.total;
+        empty = batch.n_str == 0 || batch.total == 0;
+    }
+    // a batch that launches: the batch on the device, the context's workspace sized for `shape`, the pinned words of `clear_mask` zero
+    int stage(Ctx& g, int route, const WsShape& shape, unsigned clear_mask) {
+        int rc;
+        if (dev && ((uintptr_t)b.in.p & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+        g.last_route = route;
+        if ((rc = units_on_device(g, b, dev, st, &d))) return rc;
+        if ((rc = ws_ensure(ws_needs(g.ws, total, shape).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+        h_tot = (volatile int64_t*)g.pin_tot.h;
+        p_tot = (int64_t*)g.pin_tot.d;
+        for (int i = 0; i < 8; ++i)
+            if (clear_mask >> i & 1) h_tot[i] = 0;
+        return LATOK_OK;
+    }
+    // the call's wait for its kernels, then the pinned pair (finish_totals)
+    int wait_totals(Ctx& g, int64_t o32_mask, int64_t* total_out) {
+        HIP_TRY(hipStreamSynchronize(st));
+        return finish_totals(g.ws, h_tot, o32_mask, total_out);
+    }
+};
+constexpr unsigned kClearPair = 0x3, kClearSized = 0xB, kClearBytesFeats = 0x1B;   // pinned words {0, 1}, {0, 1, 3}, {0, 1, 3, 4}
+
+// The end of a call whose payload has a size known only now (`n` items, read behind wait_totals): more than the caller's capacity
+// is refused with `need_fmt`; host pointers then get `n` items of every array (a NULL dst was not asked for) and a last wait.
+struct SizedCopy {
+    void* dst;
+    const void* src;
+    size_t width;   // bytes per item
+};
+int deliver_sized(const BytesCall& c, int64_t n, int64_t cap, const char* need_fmt, std::initializer_list<SizedCopy> copies) {
+    if (n > cap) return fail(LATOK_ERR_INVALID, need_fmt, (long long)n);
+    if (c.dev || n == 0) return LATOK_OK;
+    for (const SizedCopy& k : copies)
+        if (k.dst) HIP_TRY(hipMemcpyAsync(k.dst, k.src, (size_t)n * k.width, hipMemcpyDeviceToHost, c.st));
+    HIP_TRY(hipStreamSynchronize(c.st));
+    return LATOK_OK;
+}
+
+// the vocabulary (or WordPiece object) of a call: there is one, and it lives on the device of the context that runs the call
+template <class Obj, class Handle>
+int check_object(const Ctx& g, const Handle* handle, const char* null_msg, const Obj** v) {
+    *v = reinterpret_cast<const Obj*>(handle);
+    if (!*v) return fail(LATOK_ERR_INVALID, "%s", null_msg);
+    if ((*v)->device != g.device)
+        return fail(LATOK_ERR_INVALID, "the vocabulary lives on device %d, the current context on device %d", (*v)->device, g.device);
     return LATOK_OK;
 }
 
@@ -1501,57 +1585,54 @@ static int enqueue_join_tokens(Ctx& g, Workspace& w, const JoinTokens& a) {
     return LATOK_OK;
 }
 
-// Token hashes of a UTF-8 batch in BYTE space (latok_token_hashes_utf8_bytes_batch and its flow form): one MurmurHash3 x86_32 word
-// per stripped, non-empty token (the tokens of default_tokenizer.py:149-160, as latok_token_spans_utf8_bytes_batch cuts them), at
-// the token's rank.  One stream, nothing waits for the host:
+// The front of the byte-space token calls (hashes and ids, term counts, WordPiece, counting): the two bitmasks over the BYTES, then the
+// kept tokens, their ranks and their total.  One stream, nothing waits for the host:
 //   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
 //   k_word_counts + k_scan_chained                kept mask, token ranks; THE token total -> scalar word 0, r_tokens
-//   k_hash_scatter                                counts, the span records (if asked for) and the hashes (gate: total <= cap)
-// Every batch size takes this route: there is no one-launch form and no host decode, so a batch gives the same words at every size.
-// `w` was sized by ws_needs with WsShape{.spans = true}.
-struct TokenHashes {
-    Batch b;                       // UTF-8 bytes on the device (16-byte aligned), byte offsets, total in bytes (> 0), n_str > 0
-    uint32_t seed = 0;
-    void* counts = nullptr;        // NULL: not asked for
-    void* spans = nullptr;         // NULL: not asked for
-    uint32_t* hashes = nullptr;    // NULL: a size query
-    int64_t cap = 0;               // in tokens
-    bool o32 = false;              // width of the counts and records
-    int64_t* r_tokens = nullptr;   // the two result words as the device sees them (cleared by the caller): tokens,
-    int64_t* r_err = nullptr;      // int32-overflow flag (bit 0) in the low half, scan flag in the high half
-    hipStream_t st = nullptr;
+// d_err = the call's error word; the scan's own flag goes to its high half.  `w` was sized by ws_needs with a shape that has
+// .spans = true.  What comes back are the workspace's planes, for the launches that follow.
+struct TokenPlanes {
+    uint64_t *bits = nullptr, *space = nullptr, *kept = nullptr;
+    int64_t *rank = nullptr, *tcnt = nullptr;
+    uint16_t* pref = nullptr;
+    const int64_t* tile_first = nullptr;
+    int64_t* total = nullptr;      // the workspace's scalar words: word 0 is the token total
+    int64_t words = 0;             // 64-bit words of one plane
 };
-static int enqueue_token_hashes(Ctx& g, Workspace& w, const TokenHashes& a) {
+static int enqueue_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* r_tokens, int* d_err, hipStream_t st, TokenPlanes* out) {
     int rc;
-    const hipStream_t st = a.st;
-    const int64_t total = a.b.total, words = (total + 63) / 64;
-    uint64_t* d_bits = (uint64_t*)w.bits.p;
-    uint64_t* d_space = (uint64_t*)w.space.p;
-    uint64_t* d_kept = (uint64_t*)w.kept.p;
-    int64_t* d_rank = (int64_t*)w.bases.p;
-    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
-    uint16_t* d_pref = (uint16_t*)w.wpref.p;
-    int64_t* d_total = (int64_t*)w.scalar.p;
-    int* d_err = (int*)a.r_err;
+    TokenPlanes& t = *out;
+    t.bits = (uint64_t*)w.bits.p;
+    t.space = (uint64_t*)w.space.p;
+    t.kept = (uint64_t*)w.kept.p;
+    t.rank = (int64_t*)w.bases.p;
+    t.tcnt = (int64_t*)w.wcnt.p;
+    t.pref = (uint16_t*)w.wpref.p;
+    t.tile_first = (const int64_t*)w.tile_first.p;
+    t.total = (int64_t*)w.scalar.p;
+    t.words = (b.total + 63) / 64;
     unsigned epoch = 0;
     Pipe p;
-    p.b = a.b;
-    p.bits = d_bits;
-    p.space = d_space;
+    p.b = b;
+    p.bits = t.bits;
+    p.space = t.space;
     p.st = st;
     if ((rc = run_pipeline(g, w, p))) return rc;
     if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    HIP_TRY(latok::launch_word_counts_scan(true, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank, (unsigned long long*)w.chain.p,
-                                           (unsigned*)w.chain_ctl.p, epoch, d_total, a.r_tokens, d_err + 1, st));
-    HIP_TRY(latok::launch_hash_scatter(a.o32, (const uint8_t*)a.b.in.p, a.seed, d_bits, d_space, d_kept, d_rank, d_tcnt, d_pref, words, total,
-                                       a.b.row, a.b.n_str, (const int64_t*)w.tile_first.p, a.hashes ? a.spans : nullptr, a.hashes, d_total, a.cap,
-                                       a.counts, d_err, st));
+    HIP_TRY(latok::launch_word_counts_scan(true, t.bits, t.space, t.words, b.total, t.kept, t.tcnt, t.pref, t.rank, (unsigned long long*)w.chain.p,
+                                           (unsigned*)w.chain_ctl.p, epoch, t.total, r_tokens, d_err + 1, st));
     return LATOK_OK;
 }
 
-// Token ids of a UTF-8 batch in BYTE space (latok_token_ids_utf8_bytes_batch and its flow form): enqueue_token_hashes' sequence with
-// k_vocab_scatter in place of k_hash_scatter -- the hash stays in its lane and finds the token's slot in the vocabulary table, the
-// bytes decide.  `w` was sized by ws_needs with WsShape{.spans = true}.
+// Token hashes and token ids of a UTF-8 batch in BYTE space (latok_token_hashes_utf8_bytes_batch, latok_token_ids_utf8_bytes_batch and
+// their flow forms): one 32-bit word per stripped, non-empty token (the tokens of default_tokenizer.py:149-160, as
+// latok_token_spans_utf8_bytes_batch cuts them), at the token's rank.  The hashed form stores the token's MurmurHash3 x86_32; the ids
+// form keeps the hash in its lane and finds the token's slot in the vocabulary table, the bytes decide.  One stream, nothing waits
+// for the host:
+//   enqueue_token_front                           kept mask, token ranks; THE token total -> scalar word 0, r_tokens
+//   k_hash_scatter / k_vocab_scatter              counts, the span records (if asked for) and the words (gate: total <= cap)
+// Every batch size takes this route: there is no one-launch form and no host decode, so a batch gives the same words at every size.
+// `w` was sized by ws_needs with WsShape{.spans = true}.
 struct Vocab {                     // latok_vocab: immutable once created
     int device = -1;
     int64_t n_words = 0;
@@ -1560,73 +1641,49 @@ struct Vocab {                     // latok_vocab: immutable once created
     void* d_slots = nullptr;       // VtSlot[n_slots]
     void* d_blob = nullptr;        // the padded words
 };
-struct TokenIds {
+struct TokenWords {
     Batch b;                       // UTF-8 bytes on the device (16-byte aligned), byte offsets, total in bytes (> 0), n_str > 0
-    const Vocab* vocab = nullptr;
-    int32_t unk = -1;
+    const Vocab* vocab = nullptr;  // NULL: the hashed form
+    uint32_t seed = 0;             // of the hashed form (the ids form hashes with its vocabulary's)
+    int32_t unk = -1;              // ids form: the id of a token that is not in the vocabulary
     void* counts = nullptr;        // NULL: not asked for
     void* spans = nullptr;         // NULL: not asked for
-    int32_t* ids = nullptr;        // NULL: a size query
+    void* words = nullptr;         // uint32 hashes / int32 ids; NULL: a size query
     int64_t cap = 0;               // in tokens
     bool o32 = false;              // width of the counts and records
     int64_t* r_tokens = nullptr;   // the two result words as the device sees them (cleared by the caller): tokens,
     int64_t* r_err = nullptr;      // int32-overflow flag (bit 0) in the low half, scan flag in the high half
     hipStream_t st = nullptr;
 };
-static int enqueue_token_ids(Ctx& g, Workspace& w, const TokenIds& a) {
+static int enqueue_token_words(Ctx& g, Workspace& w, const TokenWords& a) {
     int rc;
-    const hipStream_t st = a.st;
-    const int64_t total = a.b.total, words = (total + 63) / 64;
-    uint64_t* d_bits = (uint64_t*)w.bits.p;
-    uint64_t* d_space = (uint64_t*)w.space.p;
-    uint64_t* d_kept = (uint64_t*)w.kept.p;
-    int64_t* d_rank = (int64_t*)w.bases.p;
-    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
-    uint16_t* d_pref = (uint16_t*)w.wpref.p;
-    int64_t* d_total = (int64_t*)w.scalar.p;
     int* d_err = (int*)a.r_err;
-    unsigned epoch = 0;
-    Pipe p;
-    p.b = a.b;
-    p.bits = d_bits;
-    p.space = d_space;
-    p.st = st;
-    if ((rc = run_pipeline(g, w, p))) return rc;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    HIP_TRY(latok::launch_word_counts_scan(true, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank, (unsigned long long*)w.chain.p,
-                                           (unsigned*)w.chain_ctl.p, epoch, d_total, a.r_tokens, d_err + 1, st));
+    TokenPlanes t;
+    if ((rc = enqueue_token_front(g, w, a.b, a.r_tokens, d_err, a.st, &t))) return rc;
+    const uint8_t* u8 = (const uint8_t*)a.b.in.p;
+    void* spans = a.words ? a.spans : nullptr;   // the records are written only when the words are
+    if (!a.vocab) {
+        HIP_TRY(latok::launch_hash_scatter(a.o32, u8, a.seed, t.bits, t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, a.b.total, a.b.row, a.b.n_str,
+                                           t.tile_first, spans, (uint32_t*)a.words, t.total, a.cap, a.counts, d_err, a.st));
+        return LATOK_OK;
+    }
     const latok::VocabTable vt{a.vocab->d_slots, (const uint32_t*)a.vocab->d_blob, a.vocab->n_slots, a.vocab->seed};
-    HIP_TRY(latok::launch_vocab_scatter(a.o32, (const uint8_t*)a.b.in.p, vt, a.unk, d_bits, d_space, d_kept, d_rank, d_tcnt, d_pref, words, total,
-                                        a.b.row, a.b.n_str, (const int64_t*)w.tile_first.p, a.ids ? a.spans : nullptr, a.ids, d_total, a.cap,
-                                        a.counts, d_err, st));
+    HIP_TRY(latok::launch_vocab_scatter(a.o32, u8, vt, a.unk, t.bits, t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, a.b.total, a.b.row, a.b.n_str,
+                                        t.tile_first, spans, (int32_t*)a.words, t.total, a.cap, a.counts, d_err, a.st));
     return LATOK_OK;
 }
-// the vocabulary of an ids call: there is one, and it lives on the device of the context that runs the call
-static int check_vocab(const Ctx& g, const latok_vocab* vocab, const Vocab** v) {
-    *v = reinterpret_cast<const Vocab*>(vocab);
-    if (!*v) return fail(LATOK_ERR_INVALID, "vocab is NULL");
-    if ((*v)->device != g.device)
-        return fail(LATOK_ERR_INVALID, "the vocabulary lives on device %d, the current context on device %d", (*v)->device, g.device);
-    return LATOK_OK;
-}
-
 // The blocking call behind compact_common's checks: b = the caller's UTF-8 batch (total resolved, n_str > 0, total > 0).  Every
 // batch that the host did not decode takes this route, whatever its size.  One synchronisation.
 static int features_utf8_bytes_route(Ctx& g, const Batch& b, bool dev, bool o32, void* counts_out, void* items_out, int8_t* features_out,
                                      int64_t items_cap, int64_t* n_items_out, hipStream_t st) {
     int rc;
     const int64_t n_str = b.n_str, total_bytes = b.total;
-    if (dev && ((uintptr_t)b.in.p & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
-    g.last_route = 4;
-    const size_t elt = o32 ? 4 : 8;
-    Batch d;
-    if ((rc = units_on_device(g, b, dev, st, &d))) return rc;
-    if ((rc = ws_ensure(ws_needs(g.ws, total_bytes, WsShape{.spans = true, .feats = true, .cp_rows = n_str + 1}).data(), kWsNeeds))) return rc;
-    if ((rc = g.pin_tot.ensure(64))) return rc;
-    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
-    int64_t* p_tot = (int64_t*)g.pin_tot.d;
+    BytesCall c;
+    c.adopt(b, dev, o32, st);
+    // pinned result words: 0 = tokens, 1 = flags, 3 = malformed, 4 = code points (2 is the small path's completion word)
+    if ((rc = c.stage(g, 4, WsShape{.spans = true, .feats = true, .cp_rows = n_str + 1}, kClearBytesFeats))) return rc;
     Utf8BytesFeats a;
-    a.b = d;
+    a.b = c.d;
     a.o32 = o32;
     a.counts = counts_out;
     a.items = items_out;
@@ -1634,35 +1691,32 @@ static int features_utf8_bytes_route(Ctx& g, const Batch& b, bool dev, bool o32,
     // (a batch has at most one token per byte: a larger capacity gates nothing, and the staging below is sized by it)
     a.cap = items_out ? std::min(items_cap, total_bytes) : 0;
     if (!dev) {
-        if ((rc = g.counts.ensure((size_t)n_str * 8)) || (rc = g.h_out.ensure((size_t)a.cap * 4 * elt + 16)) ||
+        if ((rc = g.counts.ensure((size_t)n_str * 8)) || (rc = g.h_out.ensure((size_t)a.cap * 4 * c.elt + 16)) ||
             (rc = g.h_aux.ensure((size_t)a.cap * LATOK_FEATURE_COUNT + 16)))
             return rc;
         a.counts = g.counts.p;
         a.items = g.h_out.p;
         a.feat = (int8_t*)g.h_aux.p;
     }
-    // pinned result words: 0 = tokens, 1 = flags, 3 = malformed, 4 = code points (2 is the small path's completion word)
-    h_tot[0] = h_tot[1] = h_tot[3] = h_tot[4] = 0;
-    a.r_items = p_tot;
-    a.r_err = p_tot + 1;
-    a.r_odd = p_tot + 3;
-    a.r_cps = p_tot + 4;
+    a.r_items = c.p_tot;
+    a.r_err = c.p_tot + 1;
+    a.r_odd = c.p_tot + 3;
+    a.r_cps = c.p_tot + 4;
     a.st = st;
     if ((rc = enqueue_utf8_bytes_features(g, g.ws, a))) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
     int64_t n_items = 0;
     // (mask 0: malformed input is refused before an int32 overflow, so the overflow flag is read behind that check)
-    if ((rc = finish_totals(g.ws, h_tot, 0, &n_items))) return rc;
-    if (h_tot[3] != 0)
+    if ((rc = c.wait_totals(g, 0, &n_items))) return rc;
+    if (c.h_tot[3] != 0)
         return fail(LATOK_ERR_INVALID, "malformed UTF-8 (a continuation byte without a lead byte): no feature sums in byte space; "
                                        "latok_token_features_utf8_batch reads such input through the decoder");
-    if (h_tot[1] & 0xFFFFFFFFll) return refuse_too_long();
+    if (c.h_tot[1] & 0xFFFFFFFFll) return refuse_too_long();
     *n_items_out = n_items;
     const bool fits = n_items <= items_cap && (n_items == 0 || items_out);
     if (!dev) {
-        HIP_TRY(hipMemcpyAsync(counts_out, g.counts.p, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(counts_out, g.counts.p, (size_t)n_str * c.elt, hipMemcpyDeviceToHost, st));
         if (fits && n_items > 0) {
-            HIP_TRY(hipMemcpyAsync(items_out, g.h_out.p, (size_t)n_items * 4 * elt, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(items_out, g.h_out.p, (size_t)n_items * 4 * c.elt, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(features_out, g.h_aux.p, (size_t)n_items * LATOK_FEATURE_COUNT, hipMemcpyDeviceToHost, st));
         }
         HIP_TRY(hipStreamSynchronize(st));
@@ -2074,37 +2128,27 @@ int latok_join_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_
     if (out_cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
     if (!out_bytes && out_cap > 0) return fail(LATOK_ERR_INVALID, "out_bytes is NULL but out_cap > 0 (a size query passes out_cap = 0)");
     if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
-    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0, o32 = (flags & LATOK_OUT_INT32) != 0;
-    const size_t elt = o32 ? 4 : 8;   // width of the counts (out_off is int64 in every mode)
-    int64_t total = total_bytes;
-    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
-    StreamTurn turn(g, stream);
-    hipStream_t st = turn.st;
-    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
+    BytesCall c;   // (elt: the width of the counts; out_off is int64 in every mode)
+    if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
+    const bool dev = c.dev;
+    const hipStream_t st = c.st;
     if (n_str > 0 && !out_off) return fail(LATOK_ERR_INVALID, "out_off is NULL");
-    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    if (n_str == 0 || total == 0) {   // no byte, no token: empty rows (device pointers: one wait, whatever was cleared)
-        if ((rc = zero_counts(dev, out_off, (size_t)(n_str + 1) * 8, st)) || (rc = zero_counts(dev, counts_out, (size_t)n_str * elt, st))) return rc;
+    if (c.empty) {   // no byte, no token: empty rows (device pointers: one wait, whatever was cleared)
+        if ((rc = zero_counts(dev, out_off, (size_t)(n_str + 1) * 8, st)) || (rc = zero_counts(dev, counts_out, (size_t)n_str * c.elt, st))) return rc;
         if (dev) HIP_TRY(hipStreamSynchronize(st));
         return LATOK_OK;
     }
-    if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
-    if (dev && (((uintptr_t)out_off & 7) != 0 || ((uintptr_t)counts_out & (elt - 1)) != 0)) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    g.last_route = 5;
-    Batch d;
-    if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
-    if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true, .join = true}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
-    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
-    int64_t* p_tot = (int64_t*)g.pin_tot.d;
+    if (dev && (((uintptr_t)out_off & 7) != 0 || ((uintptr_t)counts_out & (c.elt - 1)) != 0)) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    if ((rc = c.stage(g, 5, WsShape{.spans = true, .join = true}, kClearPair))) return rc;
     JoinTokens a;
-    a.b = d;
+    a.b = c.d;
     a.sep = sep;
     a.out = out_bytes;
     // (a kept token has at least one byte and brings at most one separator: a larger capacity gates nothing, and the staging is sized by it)
-    a.cap = out_bytes ? std::min(out_cap, 2 * total) : 0;
+    a.cap = out_bytes ? std::min(out_cap, 2 * c.total) : 0;
     a.out_off = out_off;
     a.counts = counts_out;
-    a.o32 = o32;
+    a.o32 = c.o32;
     if (!dev) {
         if ((rc = g.h_out.ensure((size_t)a.cap + 16)) || (rc = g.h_aux.ensure((size_t)(n_str + 1) * 8)) || (rc = g.counts.ensure((size_t)n_str * 8)))
             return rc;
@@ -2112,31 +2156,25 @@ int latok_join_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_
         a.out_off = (int64_t*)g.h_aux.p;
         if (counts_out) a.counts = g.counts.p;
     }
-    h_tot[0] = h_tot[1] = 0;
-    a.r_bytes = p_tot;
-    a.r_err = p_tot + 1;
+    a.r_bytes = c.p_tot;
+    a.r_err = c.p_tot + 1;
     a.st = st;
     if ((rc = enqueue_join_tokens(g, g.ws, a))) return rc;
     if (!dev) {   // row offsets and counts are valid whatever the capacity
         HIP_TRY(hipMemcpyAsync(out_off, a.out_off, (size_t)(n_str + 1) * 8, hipMemcpyDeviceToHost, st));
-        if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));
+        if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_str * c.elt, hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(hipStreamSynchronize(st));
     int64_t n = 0;
-    if ((rc = finish_totals(g.ws, h_tot, 1, &n))) return rc;
+    if ((rc = c.wait_totals(g, 1, &n))) return rc;
     *n_out_bytes = n;
-    if (n > out_cap) return fail(LATOK_ERR_INVALID, "output capacity too small: need %lld bytes", (long long)n);
-    if (!dev && n > 0) {
-        HIP_TRY(hipMemcpyAsync(out_bytes, a.out, (size_t)n, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return LATOK_OK;
+    return deliver_sized(c, n, out_cap, "output capacity too small: need %lld bytes", {{out_bytes, a.out, 1}});
 }
 
-/* token hashes in byte space: one MurmurHash3 x86_32 word per token, rank-aligned with the span records (enqueue_token_hashes) */
-int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, uint32_t seed,
-                                        int64_t* counts_out, int64_t* spans_out, uint32_t* hashes_out, int64_t cap, int64_t* n_tokens_out,
-                                        int flags, void* stream) {
+/* token hashes and token ids in byte space: one MurmurHash3 x86_32 word per token, or its id in a vocabulary, rank-aligned with the
+ * span records (enqueue_token_words).  The two blocking entry points' shared body: ids = the call takes a vocabulary. */
+static int token_words_common(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, bool ids, const latok_vocab* vocab,
+                              uint32_t seed, int32_t unk_id, void* counts_out, void* spans_out, void* words_out, int64_t cap,
+                              int64_t* n_tokens_out, int flags, void* stream) {
     LATOK_ENTER();
     if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
     int rc = need_init(g);
@@ -2144,57 +2182,49 @@ int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
     if (!n_tokens_out) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
     *n_tokens_out = 0;
     if (cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
-    if (!hashes_out && cap > 0) return fail(LATOK_ERR_INVALID, "hashes_out is NULL but cap > 0 (a size query passes cap = 0)");
-    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0, o32 = (flags & LATOK_OUT_INT32) != 0;
-    const size_t elt = o32 ? 4 : 8;   // width of a count and of one field of a record (a hash is 4 bytes in every mode)
-    int64_t total = total_bytes;
-    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
-    StreamTurn turn(g, stream);
-    hipStream_t st = turn.st;
-    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
-    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    if (n_str == 0 || total == 0) return zero_counts(dev, counts_out, (size_t)n_str * elt, st, true);   // no byte, no token
-    if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
-    if (dev && (((uintptr_t)spans_out & (2 * elt - 1)) != 0 || ((uintptr_t)counts_out & (elt - 1)) != 0 || ((uintptr_t)hashes_out & 3) != 0))
+    if (!words_out && cap > 0) return fail(LATOK_ERR_INVALID, "%s_out is NULL but cap > 0 (a size query passes cap = 0)", ids ? "ids" : "hashes");
+    const Vocab* v = nullptr;
+    if (ids && (rc = check_object(g, vocab, "vocab is NULL", &v))) return rc;
+    BytesCall c;   // (elt: the width of a count and of one field of a record; a hash or an id is 4 bytes in every mode)
+    if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
+    const bool dev = c.dev;
+    const size_t elt = c.elt;
+    if (c.empty) return zero_counts(dev, counts_out, (size_t)n_str * elt, c.st, true);   // no byte, no token
+    if (dev && (((uintptr_t)spans_out & (2 * elt - 1)) != 0 || ((uintptr_t)counts_out & (elt - 1)) != 0 || ((uintptr_t)words_out & 3) != 0))
         return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    g.last_route = 6;
-    Batch d;
-    if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
-    if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
-    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
-    int64_t* p_tot = (int64_t*)g.pin_tot.d;
-    TokenHashes a;
-    a.b = d;
+    if ((rc = c.stage(g, ids ? 7 : 6, WsShape{.spans = true}, kClearPair))) return rc;
+    TokenWords a;
+    a.b = c.d;
+    a.vocab = v;
     a.seed = seed;
+    a.unk = unk_id;
     a.counts = counts_out;
     a.spans = spans_out;
-    a.hashes = hashes_out;
-    a.cap = hashes_out ? std::min(cap, total) : 0;   // (a token has at least one byte: a larger capacity gates nothing, and the staging is sized by it)
-    a.o32 = o32;
+    a.words = words_out;
+    a.cap = words_out ? std::min(cap, c.total) : 0;   // (a token has at least one byte: a larger capacity gates nothing, and the staging is sized by it)
+    a.o32 = c.o32;
     if (!dev) {
         if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 2 * elt + 16)) || (rc = g.counts.ensure((size_t)n_str * 8)))
             return rc;
-        if (hashes_out) a.hashes = (uint32_t*)g.h_aux.p;
+        if (words_out) a.words = g.h_aux.p;
         if (spans_out) a.spans = g.h_out.p;
         if (counts_out) a.counts = g.counts.p;
     }
-    h_tot[0] = h_tot[1] = 0;
-    a.r_tokens = p_tot;
-    a.r_err = p_tot + 1;
-    a.st = st;
-    if ((rc = enqueue_token_hashes(g, g.ws, a))) return rc;
-    if (!dev && counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));   // valid whatever the capacity
-    HIP_TRY(hipStreamSynchronize(st));   // the call's one wait for the kernels
+    a.r_tokens = c.p_tot;
+    a.r_err = c.p_tot + 1;
+    a.st = c.st;
+    if ((rc = enqueue_token_words(g, g.ws, a))) return rc;
+    if (!dev && counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_str * elt, hipMemcpyDeviceToHost, c.st));   // valid whatever the capacity
     int64_t n = 0;
-    if ((rc = finish_totals(g.ws, h_tot, 1, &n))) return rc;
+    if ((rc = c.wait_totals(g, 1, &n))) return rc;   // the call's one wait for the kernels
     *n_tokens_out = n;
-    if (n > cap) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld tokens", (long long)n);
-    if (!dev && n > 0 && hashes_out) {   // (host pointers: the copies, whose size is known only now)
-        HIP_TRY(hipMemcpyAsync(hashes_out, a.hashes, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        if (spans_out) HIP_TRY(hipMemcpyAsync(spans_out, a.spans, (size_t)n * 2 * elt, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return LATOK_OK;
+    return deliver_sized(c, n, cap, "capacity too small: need %lld tokens", {{words_out, a.words, 4}, {spans_out, a.spans, 2 * elt}});
+}
+int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, uint32_t seed,
+                                        int64_t* counts_out, int64_t* spans_out, uint32_t* hashes_out, int64_t cap, int64_t* n_tokens_out,
+                                        int flags, void* stream) {
+    return token_words_common(utf8, byte_off, n_str, total_bytes, false, nullptr, seed, -1, counts_out, spans_out, hashes_out, cap, n_tokens_out, flags,
+                              stream);
 }
 
 /* vocabularies: built on the host (vocab_table.h), uploaded once, read only afterwards */
@@ -2275,71 +2305,11 @@ int latok_vocab_info(const latok_vocab* vocab, int64_t* n_words, int64_t* n_slot
     return LATOK_OK;
 }
 
-/* token ids in byte space: the id of every token in a vocabulary, rank-aligned with the span records (enqueue_token_ids) */
+/* token ids in byte space: the id of every token in a vocabulary, rank-aligned with the span records (token_words_common) */
 int latok_token_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
                                      int32_t unk_id, int64_t* counts_out, int64_t* spans_out, int32_t* ids_out, int64_t cap,
                                      int64_t* n_tokens_out, int flags, void* stream) {
-    LATOK_ENTER();
-    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
-    int rc = need_init(g);
-    if (rc) return rc;
-    if (!n_tokens_out) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
-    *n_tokens_out = 0;
-    if (cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
-    if (!ids_out && cap > 0) return fail(LATOK_ERR_INVALID, "ids_out is NULL but cap > 0 (a size query passes cap = 0)");
-    const Vocab* v = nullptr;
-    if ((rc = check_vocab(g, vocab, &v))) return rc;
-    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0, o32 = (flags & LATOK_OUT_INT32) != 0;
-    const size_t elt = o32 ? 4 : 8;   // width of a count and of one field of a record (an id is 4 bytes in every mode)
-    int64_t total = total_bytes;
-    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
-    StreamTurn turn(g, stream);
-    hipStream_t st = turn.st;
-    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
-    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    if (n_str == 0 || total == 0) return zero_counts(dev, counts_out, (size_t)n_str * elt, st, true);   // no byte, no token
-    if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
-    if (dev && (((uintptr_t)spans_out & (2 * elt - 1)) != 0 || ((uintptr_t)counts_out & (elt - 1)) != 0 || ((uintptr_t)ids_out & 3) != 0))
-        return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    g.last_route = 7;
-    Batch d;
-    if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
-    if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
-    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
-    int64_t* p_tot = (int64_t*)g.pin_tot.d;
-    TokenIds a;
-    a.b = d;
-    a.vocab = v;
-    a.unk = unk_id;
-    a.counts = counts_out;
-    a.spans = spans_out;
-    a.ids = ids_out;
-    a.cap = ids_out ? std::min(cap, total) : 0;   // (a token has at least one byte: a larger capacity gates nothing, and the staging is sized by it)
-    a.o32 = o32;
-    if (!dev) {
-        if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 2 * elt + 16)) || (rc = g.counts.ensure((size_t)n_str * 8)))
-            return rc;
-        if (ids_out) a.ids = (int32_t*)g.h_aux.p;
-        if (spans_out) a.spans = g.h_out.p;
-        if (counts_out) a.counts = g.counts.p;
-    }
-    h_tot[0] = h_tot[1] = 0;
-    a.r_tokens = p_tot;
-    a.r_err = p_tot + 1;
-    a.st = st;
-    if ((rc = enqueue_token_ids(g, g.ws, a))) return rc;
-    if (!dev && counts_out) HIP_TRY(hipMemcpyAsync(counts_out, a.counts, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));   // valid whatever the capacity
-    HIP_TRY(hipStreamSynchronize(st));   // the call's one wait for the kernels
-    int64_t n = 0;
-    if ((rc = finish_totals(g.ws, h_tot, 1, &n))) return rc;
-    *n_tokens_out = n;
-    if (n > cap) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld tokens", (long long)n);
-    if (!dev && n > 0 && ids_out) {   // (host pointers: the copies, whose size is known only now)
-        HIP_TRY(hipMemcpyAsync(ids_out, a.ids, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        if (spans_out) HIP_TRY(hipMemcpyAsync(spans_out, a.spans, (size_t)n * 2 * elt, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return LATOK_OK;
+    return token_words_common(utf8, byte_off, n_str, total_bytes, true, vocab, 0, unk_id, counts_out, spans_out, ids_out, cap, n_tokens_out, flags, stream);
 }
 
 /* Per-string term counts of a UTF-8 batch in BYTE space (latok_term_counts_utf8_bytes_batch, latok_hashed_term_counts_utf8_bytes_batch):
@@ -2373,25 +2343,12 @@ struct TermCounts {
 static int enqueue_term_counts(Ctx& g, Workspace& w, TermCounts& a) {
     int rc;
     const hipStream_t st = a.st;
-    const int64_t total = a.b.total, words = (total + 63) / 64, n_str = a.b.n_str;
-    uint64_t* d_bits = (uint64_t*)w.bits.p;
-    uint64_t* d_space = (uint64_t*)w.space.p;
-    uint64_t* d_kept = (uint64_t*)w.kept.p;
-    int64_t* d_rank = (int64_t*)w.bases.p;
-    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
-    uint16_t* d_pref = (uint16_t*)w.wpref.p;
-    int64_t* d_total = (int64_t*)w.scalar.p;
+    const int64_t total = a.b.total, n_str = a.b.n_str;
     int* d_err = (int*)(a.p_tot + 1);
     unsigned epoch = 0;
-    Pipe p;
-    p.b = a.b;
-    p.bits = d_bits;
-    p.space = d_space;
-    p.st = st;
-    if ((rc = run_pipeline(g, w, p))) return rc;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    HIP_TRY(latok::launch_word_counts_scan(true, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank, (unsigned long long*)w.chain.p,
-                                           (unsigned*)w.chain_ctl.p, epoch, d_total, a.p_tot, d_err + 1, st));
+    TokenPlanes t;
+    if ((rc = enqueue_token_front(g, w, a.b, a.p_tot, d_err, st, &t))) return rc;
+    int64_t* d_total = t.total;
     HIP_TRY(hipStreamSynchronize(st));   // wait 1: the token total decides whether the call goes on and what the keys take
     if ((rc = finish_totals(w, a.h_tot, 0, &a.n_tokens))) return rc;
     const int64_t n_tok = a.n_tokens;
@@ -2409,9 +2366,9 @@ static int enqueue_term_counts(Ctx& g, Workspace& w, TermCounts& a) {
         uint64_t* d_keys = (uint64_t*)w.tkeys.p;
         latok::VocabTable vt;
         if (a.vocab) vt = latok::VocabTable{a.vocab->d_slots, (const uint32_t*)a.vocab->d_blob, a.vocab->n_slots, a.vocab->seed};
-        HIP_TRY(latok::launch_term_scatter((const uint8_t*)a.b.in.p, a.vocab ? &vt : nullptr, a.seed, a.n_features, a.alternate_sign, d_bits, d_space,
-                                           d_kept, d_rank, d_tcnt, d_pref, words, total, a.b.row, n_str, (const int64_t*)w.tile_first.p, d_total,
-                                           d_keys, d_cnt, d_err, st));
+        HIP_TRY(latok::launch_term_scatter((const uint8_t*)a.b.in.p, a.vocab ? &vt : nullptr, a.seed, a.n_features, a.alternate_sign, t.bits, t.space,
+                                           t.kept, t.rank, t.tcnt, t.pref, t.words, total, a.b.row, n_str, t.tile_first, d_total, d_keys, d_cnt,
+                                           d_err, st));
         if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
         HIP_TRY(latok::launch_tile_scan(d_cnt, n_str + 1, d_start, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 4,
                                         nullptr, d_err + 1, st));
@@ -2444,30 +2401,22 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
     if (!indices_out && cap > 0) return fail(LATOK_ERR_INVALID, "indices_out and data_out are NULL but cap > 0 (a size query passes cap = 0)");
     if (hashed && (n_features < 1 || n_features > 0x7FFFFFFFll)) return fail(LATOK_ERR_INVALID, "n_features must be in 1 .. 2^31 - 1");
     const Vocab* v = nullptr;
-    if (!hashed && (rc = check_vocab(g, vocab, &v))) return rc;
-    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0, o32 = (flags & LATOK_OUT_INT32) != 0;
-    const size_t elt = o32 ? 4 : 8;   // width of indptr and oov (an index and a count are 4 bytes in every mode)
-    int64_t total = total_bytes;
-    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
-    StreamTurn turn(g, stream);
-    hipStream_t st = turn.st;
-    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
-    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if (!hashed && (rc = check_object(g, vocab, "vocab is NULL", &v))) return rc;
+    BytesCall c;   // (elt: the width of indptr and oov; an index and a count are 4 bytes in every mode)
+    if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
+    const bool dev = c.dev;
+    const size_t elt = c.elt;
+    const hipStream_t st = c.st;
     if (dev && ((uintptr_t)indptr_out & (elt - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    if (n_str == 0 || total == 0) {   // no byte, no token: every row is empty
+    if (c.empty) {   // no byte, no token: every row is empty
         if ((rc = zero_counts(dev, indptr_out, (size_t)(n_str + 1) * elt, st))) return rc;
         return zero_counts(dev, oov_out, (size_t)n_str * elt, st, true);
     }
-    if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
     if (dev && (((uintptr_t)oov_out & (elt - 1)) != 0 || ((uintptr_t)indices_out & 3) != 0 || ((uintptr_t)data_out & 3) != 0))
         return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    g.last_route = hashed ? 10 : 9;
-    Batch d;
-    if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
-    if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true, .term_rows = n_str + 1}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
-    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+    if ((rc = c.stage(g, hashed ? 10 : 9, WsShape{.spans = true, .term_rows = n_str + 1}, kClearSized))) return rc;
     TermCounts a;
-    a.b = d;
+    a.b = c.d;
     a.vocab = v;
     a.seed = seed;
     a.n_features = (uint32_t)n_features;
@@ -2476,8 +2425,8 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
     a.oov = oov_out;
     a.indices = indices_out;
     a.data = data_out;
-    a.cap = indices_out ? std::min(cap, total) : 0;   // (an entry has at least one token, a token one byte: the staging is sized by it)
-    a.o32 = o32;
+    a.cap = indices_out ? std::min(cap, c.total) : 0;   // (an entry has at least one token, a token one byte: the staging is sized by it)
+    a.o32 = c.o32;
     if (!dev) {
         if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 4 + 16)) ||
             (rc = g.counts.ensure((size_t)(2 * n_str + 2) * 8)))
@@ -2489,28 +2438,20 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
         a.indptr = g.counts.p;
         if (oov_out) a.oov = (uint8_t*)g.counts.p + (size_t)(n_str + 1) * 8;
     }
-    h_tot[0] = h_tot[1] = h_tot[3] = 0;
-    a.p_tot = (int64_t*)g.pin_tot.d;
-    a.h_tot = h_tot;
+    a.p_tot = c.p_tot;
+    a.h_tot = c.h_tot;
     a.st = st;
     if ((rc = enqueue_term_counts(g, g.ws, a))) return rc;
     if (!dev) {   // valid whatever the capacity
         HIP_TRY(hipMemcpyAsync(indptr_out, a.indptr, (size_t)(n_str + 1) * elt, hipMemcpyDeviceToHost, st));
         if (oov_out) HIP_TRY(hipMemcpyAsync(oov_out, a.oov, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(hipStreamSynchronize(st));   // wait 2
     int64_t n_tok = 0;
-    if ((rc = finish_totals(g.ws, h_tot, 0, &n_tok))) return rc;
+    if ((rc = c.wait_totals(g, 0, &n_tok))) return rc;   // wait 2
     if (n_tokens_out) *n_tokens_out = n_tok;
-    const int64_t nnz = h_tot[3];
+    const int64_t nnz = c.h_tot[3];
     *nnz_out = nnz;
-    if (nnz > cap) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld entries", (long long)nnz);
-    if (!dev && nnz > 0 && indices_out) {   // (host pointers: the copies, whose size is known only now)
-        HIP_TRY(hipMemcpyAsync(indices_out, a.indices, (size_t)nnz * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(data_out, a.data, (size_t)nnz * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));   // wait 3
-    }
-    return LATOK_OK;
+    return deliver_sized(c, nnz, cap, "capacity too small: need %lld entries", {{indices_out, a.indices, 4}, {data_out, a.data, 4}});   // (wait 3)
 }
 int latok_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
                                        int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out, int32_t* data_out, int64_t cap,
@@ -2676,25 +2617,12 @@ struct WordPieceCall {
 static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
     int rc;
     const hipStream_t st = a.st;
-    const int64_t total = a.b.total, words = (total + 63) / 64, n_str = a.b.n_str;
-    uint64_t* d_bits = (uint64_t*)w.bits.p;
-    uint64_t* d_space = (uint64_t*)w.space.p;
-    uint64_t* d_kept = (uint64_t*)w.kept.p;
-    int64_t* d_rank = (int64_t*)w.bases.p;
-    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
-    uint16_t* d_pref = (uint16_t*)w.wpref.p;
-    int64_t* d_total = (int64_t*)w.scalar.p;
+    const int64_t total = a.b.total, n_str = a.b.n_str;
     int* d_err = (int*)(a.p_tot + 1);
     unsigned epoch = 0;
-    Pipe p;
-    p.b = a.b;
-    p.bits = d_bits;
-    p.space = d_space;
-    p.st = st;
-    if ((rc = run_pipeline(g, w, p))) return rc;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    HIP_TRY(latok::launch_word_counts_scan(true, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank, (unsigned long long*)w.chain.p,
-                                           (unsigned*)w.chain_ctl.p, epoch, d_total, a.p_tot, d_err + 1, st));
+    TokenPlanes t;
+    if ((rc = enqueue_token_front(g, w, a.b, a.p_tot, d_err, st, &t))) return rc;
+    int64_t* d_total = t.total;
     HIP_TRY(hipStreamSynchronize(st));   // wait 1: the token total decides whether the call goes on and what the token buffers take
     if ((rc = finish_totals(w, a.h_tot, 0, &a.n_tokens))) return rc;
     const int64_t n_tok = a.n_tokens;
@@ -2709,8 +2637,8 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
     if (n_tok > 0) {
         HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)(n_str + 1) * 8, st));
         int64_t* d_tspans = (int64_t*)w.wpspans.p;
-        HIP_TRY(latok::launch_counts_scatter(1, false, d_bits, d_space, d_kept, d_rank, d_tcnt, d_pref, words, total, a.b.row, n_str,
-                                             (const int64_t*)w.tile_first.p, d_tspans, d_total, n_tok, d_cnt, d_err, st));
+        HIP_TRY(latok::launch_counts_scatter(1, false, t.bits, t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, total, a.b.row, n_str, t.tile_first,
+                                             d_tspans, d_total, n_tok, d_cnt, d_err, st));
         if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
         HIP_TRY(latok::launch_tile_scan(d_cnt, n_str + 1, d_start, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 4,
                                         nullptr, d_err + 1, st));
@@ -2751,15 +2679,6 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
                                      a.input_ids, a.lengths, st));
     return LATOK_OK;
 }
-// the WordPiece object of a call: there is one, and it lives on the device of the context that runs the call
-static int check_wordpiece(const Ctx& g, const latok_wordpiece* wp, const WordPiece** v) {
-    *v = reinterpret_cast<const WordPiece*>(wp);
-    if (!*v) return fail(LATOK_ERR_INVALID, "wp is NULL");
-    if ((*v)->device != g.device)
-        return fail(LATOK_ERR_INVALID, "the vocabulary lives on device %d, the current context on device %d", (*v)->device, g.device);
-    return LATOK_OK;
-}
-
 int latok_wordpiece_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
                                          const latok_wordpiece* wp, int32_t unk_id, int64_t* indptr_out, int32_t* ids_out, int64_t* spans_out,
                                          int64_t cap, int64_t* n_pieces_out, int64_t* n_tokens_out, int flags, void* stream) {
@@ -2774,34 +2693,25 @@ int latok_wordpiece_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byt
     if (cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
     if (!ids_out && cap > 0) return fail(LATOK_ERR_INVALID, "ids_out is NULL but cap > 0 (a size query passes cap = 0)");
     const WordPiece* v = nullptr;
-    if ((rc = check_wordpiece(g, wp, &v))) return rc;
-    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0, o32 = (flags & LATOK_OUT_INT32) != 0;
-    const size_t elt = o32 ? 4 : 8;   // width of indptr and of one field of a span (an id is 4 bytes in every mode)
-    int64_t total = total_bytes;
-    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
-    StreamTurn turn(g, stream);
-    hipStream_t st = turn.st;
-    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
-    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if ((rc = check_object(g, wp, "wp is NULL", &v))) return rc;
+    BytesCall c;   // (elt: the width of indptr and of one field of a span; an id is 4 bytes in every mode)
+    if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
+    const bool dev = c.dev;
+    const size_t elt = c.elt;
     if (dev && ((uintptr_t)indptr_out & (elt - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    if (n_str == 0 || total == 0) return zero_counts(dev, indptr_out, (size_t)(n_str + 1) * elt, st, true);   // no byte, no piece
-    if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    if (c.empty) return zero_counts(dev, indptr_out, (size_t)(n_str + 1) * elt, c.st, true);   // no byte, no piece
     if (dev && (((uintptr_t)spans_out & (2 * elt - 1)) != 0 || ((uintptr_t)ids_out & 3) != 0)) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    g.last_route = 11;
-    Batch d;
-    if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
-    if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true, .term_rows = n_str + 1}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
-    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+    if ((rc = c.stage(g, 11, WsShape{.spans = true, .term_rows = n_str + 1}, kClearSized))) return rc;
     WordPieceCall a;
-    a.b = d;
+    a.b = c.d;
     a.wp = v;
     a.unk = unk_id;
     a.indptr = indptr_out;
     a.ids = ids_out;
     a.spans = ids_out ? spans_out : nullptr;
     // (a piece has at least one byte: a larger capacity gates nothing, and the staging is sized by it; 2^31 pieces or more are refused)
-    a.cap = ids_out ? std::min({cap, total, (int64_t)0x7FFFFFFF}) : 0;
-    a.o32 = o32;
+    a.cap = ids_out ? std::min({cap, c.total, (int64_t)0x7FFFFFFF}) : 0;
+    a.o32 = c.o32;
     if (!dev) {
         if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 2 * elt + 16)) || (rc = g.counts.ensure((size_t)(n_str + 1) * 8)))
             return rc;
@@ -2809,26 +2719,18 @@ int latok_wordpiece_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byt
         if (a.spans) a.spans = g.h_out.p;
         a.indptr = g.counts.p;
     }
-    h_tot[0] = h_tot[1] = h_tot[3] = 0;
-    a.p_tot = (int64_t*)g.pin_tot.d;
-    a.h_tot = h_tot;
-    a.st = st;
+    a.p_tot = c.p_tot;
+    a.h_tot = c.h_tot;
+    a.st = c.st;
     if ((rc = enqueue_wordpiece(g, g.ws, a))) return rc;
-    if (!dev) HIP_TRY(hipMemcpyAsync(indptr_out, a.indptr, (size_t)(n_str + 1) * elt, hipMemcpyDeviceToHost, st));   // valid whatever the capacity
-    HIP_TRY(hipStreamSynchronize(st));   // wait 2
+    if (!dev) HIP_TRY(hipMemcpyAsync(indptr_out, a.indptr, (size_t)(n_str + 1) * elt, hipMemcpyDeviceToHost, c.st));   // valid whatever the capacity
     int64_t n_tok = 0;
-    if ((rc = finish_totals(g.ws, h_tot, 0, &n_tok))) return rc;
+    if ((rc = c.wait_totals(g, 0, &n_tok))) return rc;   // wait 2
     if (n_tokens_out) *n_tokens_out = n_tok;
-    const int64_t n = h_tot[3];
+    const int64_t n = c.h_tot[3];
     *n_pieces_out = n;
     if (n >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld pieces: a call takes fewer than 2^31", (long long)n);
-    if (n > cap) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld pieces", (long long)n);
-    if (!dev && n > 0 && ids_out) {   // (host pointers: the copies, whose size is known only now)
-        HIP_TRY(hipMemcpyAsync(ids_out, a.ids, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        if (spans_out) HIP_TRY(hipMemcpyAsync(spans_out, a.spans, (size_t)n * 2 * elt, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));   // wait 3
-    }
-    return LATOK_OK;
+    return deliver_sized(c, n, cap, "capacity too small: need %lld pieces", {{ids_out, a.ids, 4}, {spans_out, a.spans, 2 * elt}});   // (wait 3)
 }
 
 int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
@@ -2843,20 +2745,15 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
     const int sp = add_special ? 1 : 0;
     if (max_length < 1 + 2 * sp || max_length > 0x7FFFFFFF) return fail(LATOK_ERR_INVALID, "max_length must be in %d .. 2^31 - 1", 1 + 2 * sp);
     const WordPiece* v = nullptr;
-    if ((rc = check_wordpiece(g, wp, &v))) return rc;
-    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0;
-    int64_t total = total_bytes;
-    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
-    StreamTurn turn(g, stream);
-    hipStream_t st = turn.st;
-    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
-    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
+    if ((rc = check_object(g, wp, "wp is NULL", &v))) return rc;
+    BytesCall c;
+    if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
+    const bool dev = c.dev;
+    const hipStream_t st = c.st;
     if (n_str == 0) return LATOK_OK;
     if (n_str > (1ll << 40) / max_length) return fail(LATOK_ERR_INVALID, "n_str * max_length must not exceed 2^40");
     if (!input_ids_out || !lengths_out) return fail(LATOK_ERR_INVALID, "NULL buffer");
     if (dev && ((((uintptr_t)input_ids_out | (uintptr_t)lengths_out) & 3) != 0)) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    if (dev && total > 0 && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
-    g.last_route = 12;
     const size_t cells = (size_t)n_str * (size_t)max_length;
     int32_t* d_block = input_ids_out;
     int32_t* d_len = lengths_out;
@@ -2865,16 +2762,13 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
         d_block = (int32_t*)g.h_out.p;
         d_len = (int32_t*)g.counts.p;
     }
-    int64_t n = 0;
-    if (total == 0) {   // no byte, no piece: every row is its specials and padding
+    if (c.empty) {   // no byte, no piece: every row is its specials and padding
+        g.last_route = 12;
         HIP_TRY(latok::launch_wp_pad(nullptr, nullptr, nullptr, n_str, 0, max_length, sp, cls_id, sep_id, pad_id, d_block, d_len, st));
     } else {
-        Batch d;
-        if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
-        if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true, .term_rows = n_str + 1}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
-        volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+        if ((rc = c.stage(g, 12, WsShape{.spans = true, .term_rows = n_str + 1}, kClearSized))) return rc;
         WordPieceCall a;
-        a.b = d;
+        a.b = c.d;
         a.wp = v;
         a.unk = unk_id;
         a.padded = true;
@@ -2885,12 +2779,11 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
         a.pad_id = pad_id;
         a.input_ids = d_block;
         a.lengths = d_len;
-        h_tot[0] = h_tot[1] = h_tot[3] = 0;
-        a.p_tot = (int64_t*)g.pin_tot.d;
-        a.h_tot = h_tot;
+        a.p_tot = c.p_tot;
+        a.h_tot = c.h_tot;
         a.st = st;
         if ((rc = enqueue_wordpiece(g, g.ws, a))) return rc;
-        n = h_tot[3];   // (read behind wait 2 of the padded form; 0 when the batch has no token)
+        const int64_t n = c.h_tot[3];   // (read behind wait 2 of the padded form; 0 when the batch has no token)
         if (n_pieces_out) *n_pieces_out = n;
         if (n >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld pieces: a call takes fewer than 2^31", (long long)n);
     }
@@ -2898,11 +2791,9 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
         HIP_TRY(hipMemcpyAsync(input_ids_out, d_block, cells * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(lengths_out, d_len, (size_t)n_str * 4, hipMemcpyDeviceToHost, st));
     }
-    HIP_TRY(hipStreamSynchronize(st));   // the last wait
-    if (total > 0) {
-        int64_t n_tok = 0;
-        if ((rc = finish_totals(g.ws, (volatile int64_t*)g.pin_tot.h, 0, &n_tok))) return rc;
-    }
+    int64_t n_tok = 0;
+    if (!c.empty) return c.wait_totals(g, 0, &n_tok);   // the last wait
+    HIP_TRY(hipStreamSynchronize(st));
     return LATOK_OK;
 }
 
@@ -3057,14 +2948,12 @@ int latok_counter_info(const latok_counter* counter, int64_t* max_words, int64_t
 }
 
 // everything of an update from k_count_scatter on: a failure in here leaves the counter failed (the caller sets the flag)
-static int count_scatter_and_commit(Ctx& g, Workspace& w, Counter& c, const Batch& d, int64_t* p_tot, const volatile int64_t* h_tot,
-                                    int64_t* stats4, hipStream_t st) {
-    const int64_t total = d.total, words = (total + 63) / 64;
+static int count_scatter_and_commit(Ctx& g, Workspace& w, Counter& c, const Batch& d, const TokenPlanes& tp, int64_t* p_tot,
+                                    const volatile int64_t* h_tot, int64_t* stats4, hipStream_t st) {
     uint64_t ctl[8];
     latok::CountTable t = count_table_of(c);
-    HIP_TRY(latok::launch_count_scatter((const uint8_t*)d.in.p, t, (const uint64_t*)w.bits.p, (const uint64_t*)w.space.p, (const uint64_t*)w.kept.p,
-                                        (const int64_t*)w.bases.p, (const int64_t*)w.wcnt.p, (const uint16_t*)w.wpref.p, words, total, d.row,
-                                        d.n_str, (const int64_t*)w.tile_first.p, (const int64_t*)w.scalar.p, (int*)(p_tot + 1), st));
+    HIP_TRY(latok::launch_count_scatter((const uint8_t*)d.in.p, t, tp.bits, tp.space, tp.kept, tp.rank, tp.tcnt, tp.pref, tp.words, d.total, d.row,
+                                        d.n_str, tp.tile_first, tp.total, (int*)(p_tot + 1), st));
     HIP_TRY(latok::launch_count_commit_sum(t, st));
     HIP_TRY(hipMemcpyAsync(ctl, c.d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));   // the first of the call's two waits: the commit's need is known
@@ -3116,41 +3005,23 @@ int latok_count_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
     if (rc) return rc;
     std::lock_guard<std::mutex> cl(c->mu);
     if ((rc = check_counter(g, *c))) return rc;
-    const bool dev = (flags & LATOK_DEVICE_PTRS) != 0;
-    int64_t total = total_bytes;
-    if (!dev && (rc = check_csr_host(byte_off, n_str, &total))) return rc;
-    StreamTurn turn(g, stream);
-    hipStream_t st = turn.st;
-    if (dev && (rc = resolve_total_device(byte_off, n_str, &total, st))) return rc;
-    if (total > 0 && !utf8) return fail(LATOK_ERR_INVALID, "NULL buffer");
-    if (total >= kCtMaxTextBytes) return fail(LATOK_ERR_INVALID, "a counting batch must be shorter than 2^39 bytes");
+    BytesCall call;
+    if ((rc = call.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
+    const hipStream_t st = call.st;
+    if (call.total >= kCtMaxTextBytes) return fail(LATOK_ERR_INVALID, "a counting batch must be shorter than 2^39 bytes");
     int64_t stats4[4] = {0, 0, 0, 0};
     if (stats4_out) memcpy(stats4_out, stats4, sizeof(stats4));
-    if (n_str == 0 || total == 0) return LATOK_OK;   // no byte, no token: the counter is untouched
-    if (dev && ((uintptr_t)utf8 & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
-    g.last_route = 8;
-    Batch d;
-    if ((rc = units_on_device(g, Batch{Input{utf8, Form::Utf8}, byte_off, n_str, total}, dev, st, &d))) return rc;
-    if ((rc = ws_ensure(ws_needs(g.ws, total, WsShape{.spans = true}).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
-    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
-    int64_t* p_tot = (int64_t*)g.pin_tot.d;
-    h_tot[0] = h_tot[1] = 0;
+    if (call.empty) return LATOK_OK;   // no byte, no token: the counter is untouched
+    if ((rc = call.stage(g, 8, WsShape{.spans = true}, kClearPair))) return rc;
+    const Batch& d = call.d;
+    int64_t* p_tot = call.p_tot;
     Workspace& w = g.ws;
-    unsigned epoch = 0;
-    Pipe p;
-    p.b = d;
-    p.bits = (uint64_t*)w.bits.p;
-    p.space = (uint64_t*)w.space.p;
-    p.st = st;
     HIP_TRY(hipMemsetAsync(c->d_ctl, 0, 40, st));                    // this call's tallies and fresh dwords
     HIP_TRY(hipMemsetAsync((uint64_t*)c->d_ctl + 7, 0, 8, st));      // ... and the overflow flag
-    if ((rc = run_pipeline(g, w, p))) return rc;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    HIP_TRY(latok::launch_word_counts_scan(true, p.bits, p.space, (total + 63) / 64, total, (uint64_t*)w.kept.p, (int64_t*)w.wcnt.p,
-                                           (uint16_t*)w.wpref.p, (int64_t*)w.bases.p, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p,
-                                           epoch, (int64_t*)w.scalar.p, p_tot, (int*)(p_tot + 1) + 1, st));
+    TokenPlanes t;
+    if ((rc = enqueue_token_front(g, w, d, p_tot, (int*)(p_tot + 1), st, &t))) return rc;
     // from here to the end of the commit the table may hold slots that point into the caller's text
-    if ((rc = count_scatter_and_commit(g, w, *c, d, p_tot, h_tot, stats4, st))) {
+    if ((rc = count_scatter_and_commit(g, w, *c, d, t, p_tot, call.h_tot, stats4, st))) {
         c->failed = true;
         (void)hipStreamSynchronize(st);   // (nothing of this call is still running when the caller gets its text back)
         return rc;
@@ -4200,6 +4071,35 @@ int latok_flow_token_features_utf8_bytes(const uint8_t* utf8_dev, const int64_t*
     return flow_utf8_compact_entry(kU8BytesFeats, utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, spans4_dev, features_dev, cap,
                                    result_dev, flags);
 }
+// ---- byte-space token batches in a flow: the checks ahead of flow_open ---------------------------------------------------------
+// What the join entry and the hash / id entry check alike once their own flag check, need_init and object checks are done (each
+// keeps those, in its own order): the counts, the payload pointer `out` against its capacity (named in the message), the result
+// pointer, the outputs' alignment ({pointer, mask} pairs; a NULL pointer is aligned), then the total -- read on the context's
+// stream when the caller passed a negative one -- and, for a batch that is not empty, its two inputs.
+struct PtrMask {
+    const void* p;
+    size_t mask;
+};
+static int flow_bytes_checks(Ctx& g, const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t* total_io, const void* out,
+                             int64_t cap, const char* out_name, const char* cap_name, const int64_t* result_dev,
+                             std::initializer_list<PtrMask> outputs, bool* empty) {
+    int rc;
+    if (n_str < 0) return fail(LATOK_ERR_INVALID, "n_str must be >= 0");
+    if (cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
+    if (!out && cap > 0) return fail(LATOK_ERR_INVALID, "%s is NULL but %s > 0 (a size query passes %s = 0)", out_name, cap_name, cap_name);
+    if (!result_dev) return fail(LATOK_ERR_INVALID, "NULL result pointer");
+    if (((uintptr_t)result_dev & 7) != 0) return fail(LATOK_ERR_INVALID, "result pointer must be 8-byte aligned");
+    for (const PtrMask& o : outputs)
+        if (((uintptr_t)o.p & o.mask) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    if (*total_io < 0 && (rc = resolve_total_device(byte_off_dev, n_str, total_io, g.stream))) return rc;
+    *empty = n_str == 0 || *total_io <= 0;
+    if (!*empty) {
+        if (!utf8_dev || !byte_off_dev) return fail(LATOK_ERR_INVALID, "NULL buffer");
+        if (((uintptr_t)utf8_dev & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
+    }
+    return LATOK_OK;
+}
+
 // ---- joined token text in a flow -----------------------------------------------------------------------------------------------
 constexpr int kJoinFlowRanges = 6;
 // every range of caller memory the batch touches, outputs first; returns their number.  The tracked output length is what can be
@@ -4239,21 +4139,13 @@ int latok_flow_join_tokens_utf8_bytes(const uint8_t* utf8_dev, const int64_t* by
     int rc = need_init(g);
     if (rc) return rc;
     if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
-    if (n_str < 0) return fail(LATOK_ERR_INVALID, "n_str must be >= 0");
-    if (out_cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
-    if (!out_bytes_dev && out_cap > 0) return fail(LATOK_ERR_INVALID, "out_bytes is NULL but out_cap > 0 (a size query passes out_cap = 0)");
-    if (!result_dev) return fail(LATOK_ERR_INVALID, "NULL result pointer");
-    if (((uintptr_t)result_dev & 7) != 0) return fail(LATOK_ERR_INVALID, "result pointer must be 8-byte aligned");
     if (!out_off_dev) return fail(LATOK_ERR_INVALID, "out_off is NULL");
     const bool o32 = (flags & LATOK_OUT_INT32) != 0;
     const size_t rec = o32 ? 4 : 8;
-    if (((uintptr_t)out_off_dev & 7) != 0 || ((uintptr_t)counts_dev & (rec - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    if (total_bytes < 0 && (rc = resolve_total_device(byte_off_dev, n_str, &total_bytes, g.stream))) return rc;
-    const bool empty = n_str == 0 || total_bytes <= 0;   // empty rows
-    if (!empty) {
-        if (!utf8_dev || !byte_off_dev) return fail(LATOK_ERR_INVALID, "NULL buffer");
-        if (((uintptr_t)utf8_dev & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
-    }
+    bool empty = false;   // empty rows
+    if ((rc = flow_bytes_checks(g, utf8_dev, byte_off_dev, n_str, &total_bytes, out_bytes_dev, out_cap, "out_bytes", "out_cap", result_dev,
+                                {{out_off_dev, 7}, {counts_dev, rec - 1}}, &empty)))
+        return rc;
     latok::FlowRange r[kJoinFlowRanges];
     const int n_r = join_flow_ranges(utf8_dev, byte_off_dev, n_str, total_bytes, out_bytes_dev, out_cap, out_off_dev, counts_dev, result_dev, o32, r);
     const FlowOpen o{.r = r, .n_r = n_r, .empty = empty, .result = {result_dev, 16},
@@ -4276,13 +4168,13 @@ int latok_flow_join_tokens_utf8_bytes(const uint8_t* utf8_dev, const int64_t* by
     return enqueue_join_tokens(g, f.ws, a);
 }
 
-// ---- token hashes in a flow ------------------------------------------------------------------------------------------------------
+// ---- token hashes and token ids in a flow -------------------------------------------------------------------------------------
 constexpr int kHashFlowRanges = 6;
 // every range of caller memory the batch touches, outputs first; returns their number.  The tracked length of the hashes and of
 // the records is what can be written at most -- min(cap, total_bytes) tokens, a token has at least one byte --, so a huge
 // "unbounded" capacity cannot wrap a range into an empty one.
 static int hash_flow_ranges(const uint8_t* u8, const int64_t* boff, int64_t n_str_in, int64_t total_bytes, void* counts, void* spans,
-                            uint32_t* hashes, int64_t cap, int64_t* result, bool o32, latok::FlowRange* r) {
+                            void* hashes, int64_t cap, int64_t* result, bool o32, latok::FlowRange* r) {
     const size_t n_str = (size_t)std::max<int64_t>(n_str_in, 0), bytes = (size_t)std::max<int64_t>(total_bytes, 0);
     const size_t tokens = std::min((size_t)std::max<int64_t>(cap, 0), bytes), rec = o32 ? 4 : 8;
     int n = 0;
@@ -4295,121 +4187,71 @@ static int hash_flow_ranges(const uint8_t* u8, const int64_t* boff, int64_t n_st
     return n;
 }
 
-/* test hook (not part of the ABI; needs no device): the ranges a token-hash batch of a flow notes, in the form latok_debug_flow_route
- * takes them.  addr[6] = {utf8, byte_off, counts, spans, hashes, result}.  Returns the number of ranges written to lo / bytes /
- * is_write (at most n_max), < 0 on a bad argument. */
+/* test hooks (not part of the ABI; need no device): the ranges a token-hash or token-id batch of a flow notes, in the form
+ * latok_debug_flow_route takes them.  addr[6] = {utf8, byte_off, counts, spans, hashes or ids, result}: the ranges are the same with
+ * the ids in the hashes' place (both are 4 bytes per token); the vocabulary table is library-owned read-only memory and is not
+ * tracked.  Returns the number of ranges written to lo / bytes / is_write (at most n_max), < 0 on a bad argument. */
 extern "C" int latok_debug_flow_hashes_ranges(const uint64_t* addr, int64_t n_str, int64_t total_bytes, int64_t cap, int flags, uint64_t* lo,
                                               uint64_t* bytes, int* is_write, int n_max) {
     if (!addr || !lo || !bytes || !is_write) return fail(LATOK_ERR_INVALID, "bad argument");
     latok::FlowRange r[kHashFlowRanges];
     const int n = hash_flow_ranges((const uint8_t*)(uintptr_t)addr[0], (const int64_t*)(uintptr_t)addr[1], n_str, total_bytes,
-                                   (void*)(uintptr_t)addr[2], (void*)(uintptr_t)addr[3], (uint32_t*)(uintptr_t)addr[4], cap,
+                                   (void*)(uintptr_t)addr[2], (void*)(uintptr_t)addr[3], (void*)(uintptr_t)addr[4], cap,
                                    (int64_t*)(uintptr_t)addr[5], (flags & LATOK_OUT_INT32) != 0, r);
     return export_flow_ranges(r, n, lo, bytes, is_write, n_max);
 }
-
-int latok_flow_token_hashes_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes, uint32_t seed,
-                                       void* counts_dev, void* spans_dev, uint32_t* hashes_dev, int64_t cap, int64_t* result_dev, int flags) {
-    LATOK_ENTER();
-    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
-    int rc = need_init(g);
-    if (rc) return rc;
-    if (n_str < 0) return fail(LATOK_ERR_INVALID, "n_str must be >= 0");
-    if (cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
-    if (!hashes_dev && cap > 0) return fail(LATOK_ERR_INVALID, "hashes is NULL but cap > 0 (a size query passes cap = 0)");
-    if (!result_dev) return fail(LATOK_ERR_INVALID, "NULL result pointer");
-    if (((uintptr_t)result_dev & 7) != 0) return fail(LATOK_ERR_INVALID, "result pointer must be 8-byte aligned");
-    const bool o32 = (flags & LATOK_OUT_INT32) != 0;
-    const size_t rec = o32 ? 4 : 8;
-    if (((uintptr_t)spans_dev & (2 * rec - 1)) != 0 || ((uintptr_t)counts_dev & (rec - 1)) != 0 || ((uintptr_t)hashes_dev & 3) != 0)
-        return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    if (total_bytes < 0 && (rc = resolve_total_device(byte_off_dev, n_str, &total_bytes, g.stream))) return rc;
-    const bool empty = n_str == 0 || total_bytes <= 0;   // no token
-    if (!empty) {
-        if (!utf8_dev || !byte_off_dev) return fail(LATOK_ERR_INVALID, "NULL buffer");
-        if (((uintptr_t)utf8_dev & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
-    }
-    latok::FlowRange r[kHashFlowRanges];
-    const int n_r = hash_flow_ranges(utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, spans_dev, hashes_dev, cap, result_dev, o32, r);
-    const FlowOpen o{.r = r, .n_r = n_r, .empty = empty, .result = {result_dev, 16}, .zero = {{counts_dev, (size_t)n_str * rec}},
-                     .units = total_bytes, .shape = {.spans = true}};
-    int slot = 0;
-    if ((rc = flow_open(g, o, &slot)) || empty) return rc;
-    Ctx::FlowSlot& f = g.flow[slot];
-    TokenHashes a;
-    a.b = Batch{Input{utf8_dev, Form::Utf8}, byte_off_dev, n_str, total_bytes};
-    a.seed = seed;
-    a.counts = counts_dev;
-    a.spans = spans_dev;
-    a.hashes = hashes_dev;
-    a.cap = hashes_dev ? std::min(cap, total_bytes) : 0;
-    a.o32 = o32;
-    a.r_tokens = result_dev;
-    a.r_err = result_dev + 1;
-    a.st = f.st;
-    return enqueue_token_hashes(g, f.ws, a);
-}
-
-// ---- token ids in a flow ---------------------------------------------------------------------------------------------------------
-// The ranges are those of a hash batch with the ids in the hashes' place (both are 4 bytes per token); the vocabulary table is
-// library-owned read-only memory and is not tracked.
-/* test hook (not part of the ABI; needs no device): the ranges a token-id batch of a flow notes, in the form latok_debug_flow_route
- * takes them.  addr[6] = {utf8, byte_off, counts, spans, ids, result}.  Returns the number of ranges written to lo / bytes /
- * is_write (at most n_max), < 0 on a bad argument. */
 extern "C" int latok_debug_flow_ids_ranges(const uint64_t* addr, int64_t n_str, int64_t total_bytes, int64_t cap, int flags, uint64_t* lo,
                                            uint64_t* bytes, int* is_write, int n_max) {
-    if (!addr || !lo || !bytes || !is_write) return fail(LATOK_ERR_INVALID, "bad argument");
-    latok::FlowRange r[kHashFlowRanges];
-    const int n = hash_flow_ranges((const uint8_t*)(uintptr_t)addr[0], (const int64_t*)(uintptr_t)addr[1], n_str, total_bytes,
-                                   (void*)(uintptr_t)addr[2], (void*)(uintptr_t)addr[3], (uint32_t*)(uintptr_t)addr[4], cap,
-                                   (int64_t*)(uintptr_t)addr[5], (flags & LATOK_OUT_INT32) != 0, r);
-    return export_flow_ranges(r, n, lo, bytes, is_write, n_max);
+    return latok_debug_flow_hashes_ranges(addr, n_str, total_bytes, cap, flags, lo, bytes, is_write, n_max);
 }
 
-int latok_flow_token_ids_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
-                                    const latok_vocab* vocab, int32_t unk_id, void* counts_dev, void* spans_dev, int32_t* ids_dev, int64_t cap,
-                                    int64_t* result_dev, int flags) {
+// the two flow entry points' shared body: ids = the batch takes a vocabulary
+static int flow_token_words(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes, bool ids,
+                            const latok_vocab* vocab, uint32_t seed, int32_t unk_id, void* counts_dev, void* spans_dev, void* words_dev, int64_t cap,
+                            int64_t* result_dev, int flags) {
     LATOK_ENTER();
     if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
     int rc = need_init(g);
     if (rc) return rc;
-    if (n_str < 0) return fail(LATOK_ERR_INVALID, "n_str must be >= 0");
-    if (cap < 0) return fail(LATOK_ERR_INVALID, "capacity must be >= 0");
-    if (!ids_dev && cap > 0) return fail(LATOK_ERR_INVALID, "ids is NULL but cap > 0 (a size query passes cap = 0)");
-    if (!result_dev) return fail(LATOK_ERR_INVALID, "NULL result pointer");
-    if (((uintptr_t)result_dev & 7) != 0) return fail(LATOK_ERR_INVALID, "result pointer must be 8-byte aligned");
     const Vocab* v = nullptr;
-    if ((rc = check_vocab(g, vocab, &v))) return rc;
+    if (ids && (rc = check_object(g, vocab, "vocab is NULL", &v))) return rc;
     const bool o32 = (flags & LATOK_OUT_INT32) != 0;
     const size_t rec = o32 ? 4 : 8;
-    if (((uintptr_t)spans_dev & (2 * rec - 1)) != 0 || ((uintptr_t)counts_dev & (rec - 1)) != 0 || ((uintptr_t)ids_dev & 3) != 0)
-        return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    if (total_bytes < 0 && (rc = resolve_total_device(byte_off_dev, n_str, &total_bytes, g.stream))) return rc;
-    const bool empty = n_str == 0 || total_bytes <= 0;   // no token
-    if (!empty) {
-        if (!utf8_dev || !byte_off_dev) return fail(LATOK_ERR_INVALID, "NULL buffer");
-        if (((uintptr_t)utf8_dev & 15) != 0) return fail(LATOK_ERR_INVALID, "device UTF-8 pointer must be 16-byte aligned");
-    }
+    bool empty = false;   // no token
+    if ((rc = flow_bytes_checks(g, utf8_dev, byte_off_dev, n_str, &total_bytes, words_dev, cap, ids ? "ids" : "hashes", "cap", result_dev,
+                                {{spans_dev, 2 * rec - 1}, {counts_dev, rec - 1}, {words_dev, 3}}, &empty)))
+        return rc;
     latok::FlowRange r[kHashFlowRanges];
-    const int n_r = hash_flow_ranges(utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, spans_dev, (uint32_t*)ids_dev, cap, result_dev, o32, r);
+    const int n_r = hash_flow_ranges(utf8_dev, byte_off_dev, n_str, total_bytes, counts_dev, spans_dev, words_dev, cap, result_dev, o32, r);
     const FlowOpen o{.r = r, .n_r = n_r, .empty = empty, .result = {result_dev, 16}, .zero = {{counts_dev, (size_t)n_str * rec}},
                      .units = total_bytes, .shape = {.spans = true}};
     int slot = 0;
     if ((rc = flow_open(g, o, &slot)) || empty) return rc;
     Ctx::FlowSlot& f = g.flow[slot];
-    TokenIds a;
+    TokenWords a;
     a.b = Batch{Input{utf8_dev, Form::Utf8}, byte_off_dev, n_str, total_bytes};
     a.vocab = v;
+    a.seed = seed;
     a.unk = unk_id;
     a.counts = counts_dev;
     a.spans = spans_dev;
-    a.ids = ids_dev;
-    a.cap = ids_dev ? std::min(cap, total_bytes) : 0;
+    a.words = words_dev;
+    a.cap = words_dev ? std::min(cap, total_bytes) : 0;
     a.o32 = o32;
     a.r_tokens = result_dev;
     a.r_err = result_dev + 1;
     a.st = f.st;
-    return enqueue_token_ids(g, f.ws, a);
+    return enqueue_token_words(g, f.ws, a);
+}
+int latok_flow_token_hashes_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes, uint32_t seed,
+                                       void* counts_dev, void* spans_dev, uint32_t* hashes_dev, int64_t cap, int64_t* result_dev, int flags) {
+    return flow_token_words(utf8_dev, byte_off_dev, n_str, total_bytes, false, nullptr, seed, -1, counts_dev, spans_dev, hashes_dev, cap, result_dev,
+                            flags);
+}
+int latok_flow_token_ids_utf8_bytes(const uint8_t* utf8_dev, const int64_t* byte_off_dev, int64_t n_str, int64_t total_bytes,
+                                    const latok_vocab* vocab, int32_t unk_id, void* counts_dev, void* spans_dev, int32_t* ids_dev, int64_t cap,
+                                    int64_t* result_dev, int flags) {
+    return flow_token_words(utf8_dev, byte_off_dev, n_str, total_bytes, true, vocab, 0, unk_id, counts_dev, spans_dev, ids_dev, cap, result_dev, flags);
 }
 
 int latok_flow_wait(void) {
