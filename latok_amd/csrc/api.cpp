@@ -152,8 +152,9 @@ constexpr int64_t kSmallChars = 262144;
 constexpr int64_t kSmallStrings = 16384;
 
 // The input form of a batch as the tile kernel reads it: UTF-32 code points, PEP 393 kind 1 / 2 code units (positions are
-// chars) or UTF-8 bytes (positions are bytes).  Code-point positions of a UTF-8 batch are not a kernel form: compact_common
-// and latok_split_mask_utf8_batch reach them through byte space or the decoder, flow_submit_utf8 through byte space alone.
+// chars) or UTF-8 bytes (positions are bytes).  Code-point positions of a UTF-8 batch are not a kernel form: the blocking calls
+// (cp_units_route, latok_split_mask_utf8_batch) reach them through byte space (enqueue_lead_front) or the decoder, flow_submit_utf8
+// through byte space alone.
 enum class Form { Utf32, Latin1, Ucs2, Utf8 };
 struct Input {
     const void* p = nullptr;
@@ -176,8 +177,8 @@ struct Workspace {
     DevBuf summ, seg_agg, fix_count, tile_first;   // tile stage (run_pipeline)
     DevBuf bits, space, kept, wcnt, wpref, bases, scalar, chain, chain_ctl;   // compaction passes (enqueue_compaction_dev)
     DevBuf codes, widened;                          // featurize: rule code of every char, PEP 393 units widened to UTF-32
-    // code-point results of a UTF-8 batch in a flow (flow_submit_utf8): lead-byte mask and SPACE plane over the bytes, the packed
-    // code-point masks, the code-point row offsets (the blocking calls keep theirs in the context: Ctx::u_lead ..)
+    // code-point results of a UTF-8 batch from byte space (enqueue_lead_front, blocking calls and flow alike): lead-byte mask and
+    // SPACE plane over the bytes, the packed code-point masks, the code-point row offsets
     DevBuf lead, bspace, cpbits, cpspace, cprow;
     DevBuf jbody, jhead;   // joined token text: the body / head planes over the bytes (k_join_counts)
     DevBuf tkeys, tkeys2, trows;   // term counts: one key per token, the long rows' second buffer, five int64 arrays over the rows
@@ -290,8 +291,6 @@ struct Ctx {
     std::vector<int64_t> hd_row, hd_pos;
     unsigned done_ctr_seen = 0;
     DevBuf u_bytes, u_boff, u_cnt, u_row, u_pref;   // UTF-8 ingest: uploaded bytes / byte offsets, per-string cp counts, cp offsets
-    DevBuf u_lead, u_bspace, u_cpbits, u_cpspace;   // code-point results from byte space (cp_masks_via_bytes): lead-byte mask, byte-space
-                                                    // SPACE plane, the packed code-point masks
     // chunked host pipeline (compact_host_pipelined): copy streams, events and double buffers
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     hipEvent_t ev_in_ready[2] = {nullptr, nullptr}, ev_k_done[2] = {nullptr, nullptr}, ev_d2h_done[2] = {nullptr, nullptr};
@@ -387,7 +386,7 @@ struct Pipe {
     uint8_t* values = nullptr;
     uint64_t* space = nullptr;        // also the SPACE plane (token spans)
     uint64_t* lead = nullptr;         // byte space: also the lead-byte mask, the leads of a tile before each word and the leads
-    uint16_t* lead_pref = nullptr;    // per tile (code-point results, cp_masks_via_bytes)
+    uint16_t* lead_pref = nullptr;    // per tile (code-point results, enqueue_lead_front)
     int64_t* lead_cnt = nullptr;
     uint8_t* codes = nullptr;         // also the rule code of every char (featurize)
     const int8_t* bm_a1 = nullptr;    // kModeBlockMask: the two planes and {any(a1), any(a2)}
@@ -566,6 +565,36 @@ int finish_totals(Workspace& w, const volatile int64_t* h, int64_t o32_mask, int
     return LATOK_OK;
 }
 
+// The end of a blocking compaction call (offsets, token spans, featurize), behind its totals: `n_items` items were counted.  The
+// counts are delivered even when the records do not fit; the records and the feature sums (src_feat NULL: there are none) only
+// when they do; the capacity is refused after the copies and their wait.  src_*: where the kernels left them -- pinned memory that the
+// host reads (`pinned`: the small path), device staging that is copied down and waited for, or NULL: the caller's device buffers.
+int refuse_no_room(int64_t n_items, int64_t items_cap, const void* items_out) {
+    if (n_items > items_cap) return fail(LATOK_ERR_INVALID, "output capacity too small: need %lld", (long long)n_items);
+    if (n_items > 0 && !items_out) return fail(LATOK_ERR_INVALID, "output buffer is NULL");
+    return LATOK_OK;
+}
+int deliver_records(bool pinned, const void* src_counts, const void* src_items, const void* src_feat, void* counts_out, void* items_out,
+                    int8_t* features_out, int64_t n_str, size_t elt, size_t item_bytes, int64_t n_items, int64_t items_cap, hipStream_t st) {
+    const bool fits = n_items <= items_cap && (n_items == 0 || items_out);
+    const size_t n = fits ? (size_t)n_items : 0;
+    if (src_counts && pinned) {
+        memcpy(counts_out, src_counts, (size_t)n_str * elt);
+        if (n > 0) {
+            memcpy(items_out, src_items, n * item_bytes);
+            if (src_feat) memcpy(features_out, src_feat, n * LATOK_FEATURE_COUNT);
+        }
+    } else if (src_counts) {
+        HIP_TRY(hipMemcpyAsync(counts_out, src_counts, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));
+        if (n > 0) {
+            HIP_TRY(hipMemcpyAsync(items_out, src_items, n * item_bytes, hipMemcpyDeviceToHost, st));
+            if (src_feat) HIP_TRY(hipMemcpyAsync(features_out, src_feat, n * LATOK_FEATURE_COUNT, hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return refuse_no_room(n_items, items_cap, items_out);
+}
+
 // The frame of a blocking byte-space call on a UTF-8 batch, in two steps with the entry's own checks between them.  The entry keeps
 // its flag check, need_init and argument checks ahead of open(), answers the empty batch itself and checks its outputs' alignment
 // ahead of stage().  The StreamTurn lives as long as the frame: declare it behind every lock the call takes.
@@ -727,7 +756,7 @@ static void ctx_release(Ctx& g) {   // caller holds g.mu (or owns g exclusively)
     g.plan_cus = 0;
     g.last = Ctx::LastPlan{};
     for (DevBuf* b : {&g.t1, &g.t1rule, &g.tb6, &g.tb6rule, &g.t2code, &g.t2cls, &g.cw, &g.h_row, &g.h_out, &g.counts, &g.scan_tot, &g.u_bytes,
-                      &g.u_boff, &g.u_cnt, &g.u_row, &g.u_pref, &g.u_lead, &g.u_bspace, &g.u_cpbits, &g.u_cpspace, &g.h_aux})
+                      &g.u_boff, &g.u_cnt, &g.u_row, &g.u_pref, &g.h_aux})
         b->release();
     g.ws.release();
     for (auto& e : g.ev) {
@@ -1104,7 +1133,7 @@ struct Compaction {
     volatile int64_t* h_tot = nullptr;   // ... and the host (the context's pinned pair; NULL: a flow's result words)
     latok::DoneSignal done{nullptr, 0, nullptr};
     const uint64_t* pre_bits = nullptr;    // the two bitmasks are already there (code-point masks packed from byte space:
-    const uint64_t* pre_space = nullptr;   // cp_masks_via_bytes): only the string index is launched
+    const uint64_t* pre_space = nullptr;   // enqueue_lead_front): only the string index is launched
     const uint8_t* pre_codes = nullptr;    // featurize: the rule codes too (k_lead_codes), padded to one tile + 256 B behind `total`
     // a code-point batch of a flow (flow_submit_utf8): b.total is the BYTE count, an upper bound; the code-point total is the word
     // dt.total, which the lead-byte scan writes on the same stream, and dt.gate its malformed-input flag.  The batch's result words
@@ -1324,9 +1353,7 @@ static int compact_host_pipelined_body(Ctx& g, bool spans, bool feats, bool o32,
     HIP_TRY(hipStreamSynchronize(st));
     *n_items_out = running;
     if (too_long) return refuse_too_long();
-    if (running > items_cap) return fail(LATOK_ERR_INVALID, "output capacity too small: need %lld", (long long)running);
-    if (running > 0 && !items_out) return fail(LATOK_ERR_INVALID, "output buffer is NULL");
-    return LATOK_OK;
+    return refuse_no_room(running, items_cap, items_out);
 }
 
 // h: a host batch of at least kPipeMinChars units, checked
@@ -1388,51 +1415,94 @@ static bool host_decode_small(const uint8_t* u8, const int64_t* boff, int64_t n_
 // caller has bytes): the byte-space tile kernel on the bytes, which also leaves the lead-byte mask and the lead counts per word
 // and per tile; one scan of the tile counts (k_scan_chained); then k_lead_compress packs the boundary bits at lead bytes (and,
 // for token spans, the SPACE plane) and turns the byte offsets into code-point offsets.  HBM traffic: the bytes once + ~5 bits per
-// byte of masks and ranks, against 1 + 4 + 4 bytes per char through the staged decoder.  Everything is on the device; nothing
-// waits for the host between the launches; the code-point total, the capacity check and the malformed-input flag are read
-// after one synchronisation.  *fallback_out = 1: the batch holds a continuation byte that the byte-space model and the
-// decoder treat differently (malformed UTF-8): the caller takes the decoder.
-//   d: the bytes on the device; d_out / d_out_space: where the packed masks go (cap_words words each; d_out_space NULL:
-//   boundaries only), d_cp_row [n_str + 1]; codes (featurize): k_lead_codes also stores the rule code of every char into the
-//   workspace's code bytes (g.ws.codes, sized by the byte count, which bounds the code-point count), as the UTF-32 tile kernel would
-static int cp_masks_via_bytes(Ctx& g, const Batch& d, uint64_t* d_out, uint64_t* d_out_space, int64_t cap_words, int64_t* d_cp_row,
-                              hipStream_t st, int64_t* total_cps_out, int* fallback_out, bool codes = false) {
+// byte of masks and ranks, against 1 + 4 + 4 bytes per char through the staged decoder.
+// This front is the same for the blocking calls (cp_masks_via_bytes), the flow (flow_submit_utf8) and featurize in byte space
+// (enqueue_utf8_bytes_features).  One stream, nothing waits for the host:
+//   tile index -> byte-space tiles -> resolve       boundary mask, SPACE plane, lead mask + lead counts over the BYTES
+//   k_scan_chained (lead counts)                    lead ranks; the code-point total -> scalar word 1 (word 0 is the item total of the
+//                                                   scan that follows), r_cps; the scan's own flag -> the high half of r_err
+//   k_lead_compress                                 packed code-point masks, code-point row offsets; malformed -> r_odd
+//   k_lead_codes (codes)                            the rule code of every char at its code-point position, as the UTF-32 tile kernel
+//                                                   would leave it
+// `w` was sized by ws_needs at the byte count (which bounds the code-point count) with a shape that has cp_rows = n_str + 1, .spans
+// if `space` and .feats if `codes`.  What comes back are the planes, for the launches that follow.
+struct LeadFront {
+    Batch b;                       // UTF-8 bytes on the device (16-byte aligned), byte offsets, total in bytes (> 0), n_str > 0
+    bool space = false, codes = false;   // also the SPACE plane (token spans) / the rule codes (featurize)
+    uint64_t* cpbits = nullptr;    // where the packed code-point mask goes: a caller's buffer of cap_words words (a smaller mask is
+    int64_t cap_words = 0;         // not written), or NULL: the workspace's cpbits, a whole plane
+    int64_t* cp_row = nullptr;     // the code-point row offsets [n_str + 1]: a caller's buffer, or NULL: the workspace's cprow
+    int64_t* r_cps = nullptr;      // the three result words as the device sees them (cleared by the caller): code-point total,
+    int* r_err = nullptr;          // the call's error word,
+    int* r_odd = nullptr;          // malformed-input flag
+    hipStream_t st = nullptr;
+};
+struct LeadPlanes {
+    uint64_t *bmask = nullptr, *bspace = nullptr, *lead = nullptr;   // over the bytes
+    uint64_t *cpbits = nullptr, *cpspace = nullptr;                  // packed at the lead bytes
+    int64_t* cp_row = nullptr;
+    uint8_t* codes = nullptr;
+    int64_t* total_cps = nullptr;                                    // the device word that holds the code-point total
+};
+static int enqueue_lead_front(Ctx& g, Workspace& w, const LeadFront& a, LeadPlanes* out) {
+    int rc;
+    const int64_t total_bytes = a.b.total, words_b = (total_bytes + 63) / 64, c_tiles = (words_b + 63) / 64;
+    LeadPlanes& t = *out;   // (a plane that was not asked for: NULL)
+    t.bmask = (uint64_t*)w.bits.p;
+    t.bspace = a.space ? (uint64_t*)w.bspace.p : nullptr;
+    t.lead = (uint64_t*)w.lead.p;
+    t.cpbits = a.cpbits ? a.cpbits : (uint64_t*)w.cpbits.p;
+    t.cpspace = a.space ? (uint64_t*)w.cpspace.p : nullptr;
+    t.cp_row = a.cp_row ? a.cp_row : (int64_t*)w.cprow.p;
+    t.codes = a.codes ? (uint8_t*)w.codes.p : nullptr;
+    t.total_cps = (int64_t*)w.scalar.p + 1;
+    int64_t* d_rank = (int64_t*)w.bases.p;
+    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
+    uint16_t* d_pref = (uint16_t*)w.wpref.p;
+    unsigned epoch = 0;
+    if ((rc = next_scan_epoch(w, a.st, &epoch))) return rc;
+    Pipe p;
+    p.b = a.b;
+    p.bits = t.bmask;
+    p.space = t.bspace;
+    p.lead = t.lead;
+    p.lead_pref = d_pref;
+    p.lead_cnt = d_tcnt;
+    p.st = a.st;
+    if ((rc = run_pipeline(g, w, p))) return rc;
+    HIP_TRY(latok::launch_tile_scan(d_tcnt, c_tiles, d_rank, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, t.total_cps,
+                                    a.r_cps, a.r_err + 1, a.st));
+    HIP_TRY(latok::launch_lead_compress(t.bmask, t.bspace, t.lead, d_rank, d_tcnt, d_pref, words_b, total_bytes, a.b.row, a.b.n_str, t.total_cps,
+                                        t.cpbits, t.cpspace, a.cpbits ? a.cap_words : words_b, t.cp_row, a.r_odd, a.st));
+    if (a.codes)
+        HIP_TRY(latok::launch_lead_codes((const uint8_t*)a.b.in.p, total_bytes, t.lead, d_rank, d_tcnt, d_pref, words_b, (const uint8_t*)g.tb6rule.p,
+                                         t.codes, g.n_cu, a.st));
+    return LATOK_OK;
+}
+
+// The front on the context's own workspace, for the blocking calls (a: everything but the result words, which are the pinned words
+// 0, 1 and 3): the code-point total and the malformed-input flag are read after one synchronisation.  *fallback_out = 1: the batch
+// holds a continuation byte that the byte-space model and the decoder treat differently (malformed UTF-8): the caller takes the decoder.
+static int cp_masks_via_bytes(Ctx& g, LeadFront a, LeadPlanes* planes, int64_t* total_cps_out, int* fallback_out) {
     int rc;
     *fallback_out = 0;
     Workspace& w = g.ws;
-    const int64_t total_bytes = d.total, words_b = (total_bytes + 63) / 64, c_tiles = (words_b + 63) / 64;
-    if ((rc = ws_ensure(ws_needs(w, total_bytes, WsShape{.feats = codes}).data(), kWsNeeds)) || (rc = g.u_lead.ensure((size_t)words_b * 8 + 8)) ||
-        (d_out_space && (rc = g.u_bspace.ensure((size_t)words_b * 8 + 8))) || (rc = g.pin_tot.ensure(64)))
+    // DevBuf::ensure frees on growth, and the planes of this front stay live through the compaction that follows: the workspace is
+    // sized here, once, with everything that compaction will ask for, at the byte count.  enqueue_compaction_dev's own ws_ensure (a
+    // sub-shape at the code-point count, which is no larger) then finds nothing to grow.  flow_reserve does the same for a slot.
+    if ((rc = ws_ensure(ws_needs(w, a.b.total, WsShape{.spans = a.space, .feats = a.codes, .cp_rows = a.b.n_str + 1}).data(), kWsNeeds)) ||
+        (rc = g.pin_tot.ensure(64)))
         return rc;
-    unsigned epoch = 0;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    uint64_t* d_bmask = (uint64_t*)w.bits.p;
-    uint64_t* d_lead = (uint64_t*)g.u_lead.p;
-    uint64_t* d_bspace = d_out_space ? (uint64_t*)g.u_bspace.p : nullptr;
-    Pipe a;
-    a.b = d;
-    a.bits = d_bmask;
-    a.space = d_bspace;
-    a.lead = d_lead;
-    a.lead_pref = (uint16_t*)w.wpref.p;
-    a.lead_cnt = (int64_t*)w.wcnt.p;
-    a.st = st;
-    if ((rc = run_pipeline(g, w, a))) return rc;
     volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
     int64_t* p_tot = (int64_t*)g.pin_tot.d;
     h_tot[0] = 0;
     h_tot[1] = 0;
     h_tot[3] = 0;
-    int* d_err = (int*)(p_tot + 1);
-    HIP_TRY(latok::launch_tile_scan((const int64_t*)w.wcnt.p, c_tiles, (int64_t*)w.bases.p, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p,
-                                    epoch, (int64_t*)w.scalar.p, p_tot, d_err + 1, st));
-    HIP_TRY(latok::launch_lead_compress(d_bmask, d_bspace, d_lead, (const int64_t*)w.bases.p, (const int64_t*)w.wcnt.p,
-                                        (const uint16_t*)w.wpref.p, words_b, total_bytes, d.row, d.n_str, (const int64_t*)w.scalar.p, d_out,
-                                        d_out_space, cap_words, d_cp_row, (int*)(p_tot + 3), st));
-    if (codes)
-        HIP_TRY(latok::launch_lead_codes((const uint8_t*)d.in.p, total_bytes, d_lead, (const int64_t*)w.bases.p, (const int64_t*)w.wcnt.p,
-                                         (const uint16_t*)w.wpref.p, words_b, (const uint8_t*)g.tb6rule.p, (uint8_t*)w.codes.p, g.n_cu, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    a.r_cps = p_tot;
+    a.r_err = (int*)(p_tot + 1);
+    a.r_odd = (int*)(p_tot + 3);
+    if ((rc = enqueue_lead_front(g, w, a, planes))) return rc;
+    HIP_TRY(hipStreamSynchronize(a.st));
     if (h_tot[1] != 0) { w.chain_ready = false; return fail(LATOK_ERR_HIP, "internal: the chained scan did not complete (flag %lld)", (long long)h_tot[1]); }
     if (h_tot[3] != 0) { *fallback_out = 1; return LATOK_OK; }
     *total_cps_out = h_tot[0];
@@ -1443,9 +1513,8 @@ static int cp_masks_via_bytes(Ctx& g, const Batch& d, uint64_t* d_out, uint64_t*
 // positions, feature sums per CHAR.  A token has the same rank in byte space and in code-point space, so two writers share one
 // record index: k_counts_scatter<2> puts the four byte positions from the byte-space masks, k_features_tiles (without span records)
 // the sums from the packed code-point masks and the rule codes.  One stream, nothing waits for the host:
-//   tile index -> byte-space tiles -> resolve       boundary mask, SPACE plane, lead mask + lead counts over the BYTES
-//   k_scan_chained (lead counts)                    lead ranks; code-point total -> r_cps, and the workspace's scalar word 1
-//   k_lead_compress, k_lead_codes                   packed code-point masks, code-point row offsets, rule codes; malformed -> r_odd
+//   enqueue_lead_front (SPACE plane, codes)         byte-space masks, packed code-point masks, code-point row offsets, rule codes;
+//                                                   code-point total -> r_cps and the workspace's scalar word 1; malformed -> r_odd
 //   k_word_counts + k_scan_chained (byte masks)     kept mask / item ranks in byte space; THE token total -> scalar word 0, r_items
 //   k_counts_scatter<2>                             counts + byte records        (gates: total <= cap, *r_odd == 0)
 //   tile index (code-point rows), k_word_counts + k_scan_chained (code-point masks)    item ranks in code-point space
@@ -1470,58 +1539,37 @@ struct Utf8BytesFeats {
 static int enqueue_utf8_bytes_features(Ctx& g, Workspace& w, const Utf8BytesFeats& a) {
     int rc;
     const hipStream_t st = a.st;
-    const int64_t n_str = a.b.n_str, total_bytes = a.b.total, words_b = (total_bytes + 63) / 64, c_tiles = (words_b + 63) / 64;
-    uint64_t* d_bmask = (uint64_t*)w.bits.p;
-    uint64_t* d_lead = (uint64_t*)w.lead.p;
-    uint64_t* d_bspace = (uint64_t*)w.bspace.p;
+    const int64_t n_str = a.b.n_str, total_bytes = a.b.total, words_b = (total_bytes + 63) / 64;
+    int* d_err = (int*)a.r_err;
+    const int* d_odd = (const int*)a.r_odd;
+    const LeadFront f{.b = a.b, .space = true, .codes = true, .r_cps = a.r_cps, .r_err = d_err, .r_odd = (int*)a.r_odd, .st = st};
+    LeadPlanes t;
+    if ((rc = enqueue_lead_front(g, w, f, &t))) return rc;
+    HIP_TRY(latok::launch_pad_codes(t.codes, t.total_cps, total_bytes, st));
     uint64_t* d_kept = (uint64_t*)w.kept.p;
     int64_t* d_rank = (int64_t*)w.bases.p;
     int64_t* d_tcnt = (int64_t*)w.wcnt.p;
     uint16_t* d_pref = (uint16_t*)w.wpref.p;
     int64_t* d_total = (int64_t*)w.scalar.p;        // word 0: the token total
-    int64_t* d_total_cps = d_total + 1;             // word 1: the code-point total
-    int* d_err = (int*)a.r_err;
-    const int* d_odd = (const int*)a.r_odd;
     unsigned epoch = 0;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    Pipe p;
-    p.b = a.b;
-    p.bits = d_bmask;
-    p.space = d_bspace;
-    p.lead = d_lead;
-    p.lead_pref = d_pref;
-    p.lead_cnt = d_tcnt;
-    p.st = st;
-    if ((rc = run_pipeline(g, w, p))) return rc;
-    HIP_TRY(latok::launch_tile_scan(d_tcnt, c_tiles, d_rank, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total_cps,
-                                    a.r_cps, d_err + 1, st));
-    uint64_t* d_cpbits = (uint64_t*)w.cpbits.p;
-    uint64_t* d_cpspace = (uint64_t*)w.cpspace.p;
-    int64_t* d_cp_row = (int64_t*)w.cprow.p;
-    HIP_TRY(latok::launch_lead_compress(d_bmask, d_bspace, d_lead, d_rank, d_tcnt, d_pref, words_b, total_bytes, a.b.row, n_str, d_total_cps,
-                                        d_cpbits, d_cpspace, words_b, d_cp_row, (int*)a.r_odd, st));
-    uint8_t* d_codes = (uint8_t*)w.codes.p;
-    HIP_TRY(latok::launch_lead_codes((const uint8_t*)a.b.in.p, total_bytes, d_lead, d_rank, d_tcnt, d_pref, words_b, (const uint8_t*)g.tb6rule.p,
-                                     d_codes, g.n_cu, st));
-    HIP_TRY(latok::launch_pad_codes(d_codes, d_total_cps, total_bytes, st));
     // byte space: kept tokens, their ranks, the total; counts and the four byte positions of every token (the lead ranks are spent)
     if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    HIP_TRY(latok::launch_word_counts_scan(true, d_bmask, d_bspace, words_b, total_bytes, d_kept, d_tcnt, d_pref, d_rank,
+    HIP_TRY(latok::launch_word_counts_scan(true, t.bmask, t.bspace, words_b, total_bytes, d_kept, d_tcnt, d_pref, d_rank,
                                            (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total, a.r_items, d_err + 1, st));
-    HIP_TRY(latok::launch_counts_scatter(2, a.o32, d_bmask, d_bspace, d_kept, d_rank, d_tcnt, d_pref, words_b, total_bytes, a.b.row, n_str,
+    HIP_TRY(latok::launch_counts_scatter(2, a.o32, t.bmask, t.bspace, d_kept, d_rank, d_tcnt, d_pref, words_b, total_bytes, a.b.row, n_str,
                                          (const int64_t*)w.tile_first.p, a.items, d_total, a.cap, a.counts, d_err, st,
                                          latok::DoneSignal{nullptr, 0, nullptr}, latok::DeviceTotal{nullptr, d_odd}));
     // code-point space: the same tokens on the packed masks (the byte-space ranks and kept mask are spent); sums only
-    const latok::DeviceTotal dt{d_total_cps, d_odd};
+    const latok::DeviceTotal dt{t.total_cps, d_odd};
     Pipe q;
-    q.b = Batch{Input{}, d_cp_row, n_str, total_bytes};
+    q.b = Batch{Input{}, t.cp_row, n_str, total_bytes};
     q.stages = 1;
     q.st = st;
     if ((rc = run_pipeline(g, w, q))) return rc;
     if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    HIP_TRY(latok::launch_word_counts_scan(true, d_cpbits, d_cpspace, words_b, total_bytes, d_kept, d_tcnt, d_pref, d_rank,
+    HIP_TRY(latok::launch_word_counts_scan(true, t.cpbits, t.cpspace, words_b, total_bytes, d_kept, d_tcnt, d_pref, d_rank,
                                            (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 2, nullptr, d_err + 1, st, dt));
-    return enqueue_features(g, d_codes, d_cp_row, n_str, total_bytes, d_cpbits, d_cpspace, d_kept, d_rank, d_tcnt, d_pref,
+    return enqueue_features(g, t.codes, t.cp_row, n_str, total_bytes, t.cpbits, t.cpspace, d_kept, d_rank, d_tcnt, d_pref,
                             (const int64_t*)w.tile_first.p, nullptr, a.feat, a.o32, d_total, a.cap, st, latok::DoneSignal{nullptr, 0, nullptr}, dt);
 }
 
@@ -1712,17 +1760,38 @@ static int features_utf8_bytes_route(Ctx& g, const Batch& b, bool dev, bool o32,
                                        "latok_token_features_utf8_batch reads such input through the decoder");
     if (c.h_tot[1] & 0xFFFFFFFFll) return refuse_too_long();
     *n_items_out = n_items;
-    const bool fits = n_items <= items_cap && (n_items == 0 || items_out);
-    if (!dev) {
-        HIP_TRY(hipMemcpyAsync(counts_out, g.counts.p, (size_t)n_str * c.elt, hipMemcpyDeviceToHost, st));
-        if (fits && n_items > 0) {
-            HIP_TRY(hipMemcpyAsync(items_out, g.h_out.p, (size_t)n_items * 4 * c.elt, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(features_out, g.h_aux.p, (size_t)n_items * LATOK_FEATURE_COUNT, hipMemcpyDeviceToHost, st));
+    return deliver_records(false, dev ? nullptr : g.counts.p, g.h_out.p, g.h_aux.p, counts_out, items_out, features_out, n_str, c.elt, 4 * c.elt,
+                           n_items, items_cap, st);
+}
+
+// Code-point results of a UTF-8 batch in a blocking compaction call (b: n_str > 0, total resolved): what the kernels read instead of
+// the bytes, in k->b and k->pre_*, and the route in g.last_route.  Route 3, large batches: the byte-space kernel + the masks packed at
+// the lead bytes (no UTF-32 copy of the batch); the compaction then runs on the code-point masks (featurize: and on the rule codes
+// k_lead_codes stores at the code-point positions), sized by the code-point total the host has read.  Route 2, small batches and
+// malformed input: the decoder first -- or, with no multi-byte char in the batch, the bytes themselves: byte space == code-point space.
+static int cp_units_route(Ctx& g, const Batch& b, bool dev, bool spans, bool feats, hipStream_t st, Compaction* k) {
+    int rc;
+    int64_t total_cps = 0;
+    if (b.total > kSmallChars && (!dev || ((uintptr_t)b.in.p & 15) == 0)) {
+        Batch bytes;
+        int fallback = 0;
+        LeadPlanes t;
+        if ((rc = units_on_device(g, b, dev, st, &bytes)) ||
+            (rc = cp_masks_via_bytes(g, LeadFront{.b = bytes, .space = spans, .codes = feats, .st = st}, &t, &total_cps, &fallback)))
+            return rc;
+        if (!fallback) {
+            g.last_route = 3;
+            k->b = Batch{Input{}, t.cp_row, b.n_str, total_cps};
+            k->pre_bits = t.cpbits;
+            k->pre_space = t.cpspace;
+            k->pre_codes = t.codes;
+            return LATOK_OK;
         }
-        HIP_TRY(hipStreamSynchronize(st));
     }
-    if (n_items > items_cap) return fail(LATOK_ERR_INVALID, "output capacity too small: need %lld", (long long)n_items);
-    if (n_items > 0 && !items_out) return fail(LATOK_ERR_INVALID, "output buffer is NULL");
+    g.last_route = 2;
+    Batch ascii;   // (featurize needs the rule codes of the UTF-32 tile kernel: it always decodes)
+    if ((rc = decode_utf8_to_workspace(g, b, dev, st, &total_cps, feats ? nullptr : &ascii))) return rc;
+    k->b = ascii.in.p ? ascii : Batch{Input{g.h_cps.p, Form::Utf32}, (const int64_t*)g.u_row.p, b.n_str, total_cps};
     return LATOK_OK;
 }
 
@@ -1785,43 +1854,10 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
     }
     if (!dev && !cp_units && b.total >= kPipeMinChars)
         return compact_host_pipelined(g, spans, feats, o32, b, counts_out, items_out, items_cap, n_items_out, features_out, st);
-    Batch d = b;   // the batch as the kernels read it
-    const uint64_t *pre_bits = nullptr, *pre_space = nullptr;   // code-point masks packed from byte space (UTF-8 in code-point units)
-    const uint8_t* pre_codes = nullptr;                            // ... and featurize's rule codes
-    if (cp_units) {
-        bool via_bytes = false;
-        if (b.total > kSmallChars && (!dev || ((uintptr_t)b.in.p & 15) == 0)) {
-            // large batches: the byte-space kernel + the masks packed at the lead bytes (no UTF-32 copy of the batch); the compaction
-            // then runs on the code-point masks (featurize: and on the rule codes k_lead_codes stores at the code-point positions)
-            Batch bytes;
-            if ((rc = units_on_device(g, b, dev, st, &bytes))) return rc;
-            const int64_t words_b = (b.total + 63) / 64;
-            if ((rc = g.u_cpbits.ensure((size_t)words_b * 8 + 8)) || (spans && (rc = g.u_cpspace.ensure((size_t)words_b * 8 + 8))) ||
-                (rc = g.u_row.ensure((size_t)(n_str + 1) * 8)))
-                return rc;
-            int fallback = 0;
-            int64_t total_cps = 0;
-            if ((rc = cp_masks_via_bytes(g, bytes, (uint64_t*)g.u_cpbits.p, spans ? (uint64_t*)g.u_cpspace.p : nullptr, words_b,
-                                         (int64_t*)g.u_row.p, st, &total_cps, &fallback, feats)))
-                return rc;
-            if (!fallback) {
-                pre_bits = (const uint64_t*)g.u_cpbits.p;
-                pre_space = spans ? (const uint64_t*)g.u_cpspace.p : nullptr;
-                pre_codes = feats ? (const uint8_t*)g.ws.codes.p : nullptr;
-                d = Batch{Input{}, (const int64_t*)g.u_row.p, n_str, total_cps};
-                via_bytes = true;
-                g.last_route = 3;
-            }
-        }
-        if (!via_bytes) {   // small batches, malformed input: decode on the device first
-            g.last_route = 2;
-            Batch bytes;
-            int64_t total_cps = 0;
-            if ((rc = decode_utf8_to_workspace(g, b, dev, st, &total_cps, feats ? nullptr : &bytes))) return rc;
-            // (no multi-byte char in the batch: byte space == code-point space, the decode was skipped)
-            d = bytes.in.p ? bytes : Batch{Input{g.h_cps.p, Form::Utf32}, (const int64_t*)g.u_row.p, n_str, total_cps};
-        }
-    }
+    Compaction k;
+    k.b = b;
+    if (cp_units && (rc = cp_units_route(g, b, dev, spans, feats, st, &k))) return rc;
+    Batch& d = k.b;   // the batch as the kernels read it (UTF-8 in code-point units: the route's, with its masks and codes in k.pre_*)
     const int64_t total = d.total;
     if (total == 0) return zero_counts(dev, counts_out, (size_t)n_str * elt, st);   // only empty strings
     // small host batch: inputs and every output live in pinned mapped memory; nothing is copied by the runtime and the
@@ -1863,8 +1899,6 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
     int64_t* p_tot = (int64_t*)g.pin_tot.d;
     // where the records go: the caller's device buffers, the pinned area, or (host pointers, mid-size batch) device staging
     // sized for the worst case of one item per char
-    Compaction k;
-    k.b = d;
     k.spans = spans;
     k.feats = feats;
     k.o32 = o32;
@@ -1912,9 +1946,6 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
         if (small && (rc = arm_done(g, st, &k.done))) return rc;
         k.p_tot = p_tot;
         k.h_tot = h_tot;
-        k.pre_bits = pre_bits;
-        k.pre_space = pre_space;
-        k.pre_codes = pre_codes;
         k.st = st;
         if ((rc = enqueue_compaction_dev(g, g.ws, k))) return rc;
         done = k.done;
@@ -1924,24 +1955,11 @@ static int compact_common(Ctx& g, bool spans, bool feats, Batch b, bool cp_units
     if ((rc = wait_done(g, done, st))) return rc;
     int64_t n_items = *n_items_out = h_tot[0];   // (the total is reported whatever the flags say)
     if ((rc = finish_totals(g.ws, h_tot, 0xFFFFFFFFll, &n_items))) return rc;
-    const bool fits = n_items <= items_cap && (n_items == 0 || items_out);
-    if (small) {
-        memcpy(counts_out, (char*)g.pin.h + po_counts, (size_t)n_str * elt);
-        if (fits && n_items > 0) {
-            memcpy(items_out, (char*)g.pin.h + po_items, (size_t)n_items * item_bytes);
-            if (feats) memcpy(features_out, (char*)g.pin.h + po_feat, (size_t)n_items * LATOK_FEATURE_COUNT);
-        }
-    } else if (!dev) {
-        HIP_TRY(hipMemcpyAsync(counts_out, g.counts.p, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));
-        if (fits && n_items > 0) {
-            HIP_TRY(hipMemcpyAsync(items_out, g.h_out.p, (size_t)n_items * item_bytes, hipMemcpyDeviceToHost, st));
-            if (feats) HIP_TRY(hipMemcpyAsync(features_out, g.h_aux.p, (size_t)n_items * LATOK_FEATURE_COUNT, hipMemcpyDeviceToHost, st));
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    if (n_items > items_cap) return fail(LATOK_ERR_INVALID, "output capacity too small: need %lld", (long long)n_items);
-    if (n_items > 0 && !items_out) return fail(LATOK_ERR_INVALID, "output buffer is NULL");
-    return LATOK_OK;
+    const char* pin = (const char*)g.pin.h;
+    if (small) return deliver_records(true, pin + po_counts, pin + po_items, feats ? pin + po_feat : nullptr, counts_out, items_out, features_out,
+                                      n_str, elt, item_bytes, n_items, items_cap, st);
+    return deliver_records(false, dev ? nullptr : g.counts.p, g.h_out.p, feats ? g.h_aux.p : nullptr, counts_out, items_out, features_out, n_str,
+                           elt, item_bytes, n_items, items_cap, st);
 }
 
 int latok_split_offsets_batch(const uint32_t* cps, const int64_t* row_off, int64_t n_str, int64_t total,
@@ -1993,21 +2011,21 @@ static int mask_utf8_via_bytes(Ctx& g, const Batch& b, bool dev, uint64_t* mask_
     const int64_t words_b = (b.total + 63) / 64;
     const int64_t out_words = mask_cap_words < words_b ? mask_cap_words : words_b;   // (a batch has at most one char per byte)
     uint64_t* d_out = mask_bits_out;
-    int64_t* d_cp_row = cp_row_off_out;
-    if (!dev) {
-        if ((rc = g.h_out.ensure((size_t)out_words * 8 + 8)) || (rc = g.u_row.ensure((size_t)(b.n_str + 1) * 8))) return rc;
+    if (!dev) {   // (the row offsets of a host call: the workspace's)
+        if ((rc = g.h_out.ensure((size_t)out_words * 8 + 8))) return rc;
         d_out = (uint64_t*)g.h_out.p;
-        d_cp_row = (int64_t*)g.u_row.p;
     }
     int64_t total_cps = 0;
-    if ((rc = cp_masks_via_bytes(g, d, d_out, nullptr, out_words, d_cp_row, st, &total_cps, fallback_out))) return rc;
+    LeadPlanes t;
+    const LeadFront a{.b = d, .cpbits = d_out, .cap_words = out_words, .cp_row = dev ? cp_row_off_out : nullptr, .st = st};
+    if ((rc = cp_masks_via_bytes(g, a, &t, &total_cps, fallback_out))) return rc;
     if (*fallback_out) return LATOK_OK;
     *total_cps_out = total_cps;
     const int64_t words = (total_cps + 63) / 64;
     if (words > mask_cap_words) return fail(LATOK_ERR_INVALID, "mask_cap_words too small: need %lld", (long long)words);
     if (!dev) {
         if (words > 0) HIP_TRY(hipMemcpyAsync(mask_bits_out, d_out, (size_t)words * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(cp_row_off_out, d_cp_row, (size_t)(b.n_str + 1) * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(cp_row_off_out, t.cp_row, (size_t)(b.n_str + 1) * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     return LATOK_OK;
@@ -3965,7 +3983,7 @@ static int flow_submit_utf8(Ctx& g, const Utf8Flow& a) {
     Ctx::FlowSlot& f = g.flow[slot];
     Workspace& w = f.ws;
     const hipStream_t st = f.st;
-    const int64_t words_b = (total_bytes + 63) / 64, c_tiles = (words_b + 63) / 64;
+    const int64_t words_b = (total_bytes + 63) / 64;
     if (a.what == kU8BytesFeats) {   // records in byte positions: the sequence the blocking call enqueues, on the slot
         Utf8BytesFeats k;
         k.b = Batch{Input{a.u8, Form::Utf8}, a.boff, n_str, total_bytes};
@@ -3981,38 +3999,18 @@ static int flow_submit_utf8(Ctx& g, const Utf8Flow& a) {
         k.st = st;
         return enqueue_utf8_bytes_features(g, w, k);
     }
-    unsigned epoch = 0;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    uint64_t* d_bmask = (uint64_t*)w.bits.p;
-    uint64_t* d_lead = (uint64_t*)w.lead.p;
-    uint64_t* d_bspace = spans ? (uint64_t*)w.bspace.p : nullptr;
-    Pipe p;
-    p.b = Batch{Input{a.u8, Form::Utf8}, a.boff, n_str, total_bytes};
-    p.bits = d_bmask;
-    p.space = d_bspace;
-    p.lead = d_lead;
-    p.lead_pref = (uint16_t*)w.wpref.p;
-    p.lead_cnt = (int64_t*)w.wcnt.p;
-    p.st = st;
-    if ((rc = run_pipeline(g, w, p))) return rc;
     // the code-point total: word 1 of the workspace's scalars (word 0 is the item total of the second scan) and result[2]
-    int64_t* d_total_cps = (int64_t*)w.scalar.p + 1;
-    int* d_err = (int*)(a.result + 1);
-    int* d_odd = (int*)(a.result + 3);
-    HIP_TRY(latok::launch_tile_scan((const int64_t*)w.wcnt.p, c_tiles, (int64_t*)w.bases.p, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p,
-                                    epoch, d_total_cps, a.result + 2, d_err + 1, st));
-    uint64_t* d_cpbits = mask ? a.mask : (uint64_t*)w.cpbits.p;
-    uint64_t* d_cpspace = spans ? (uint64_t*)w.cpspace.p : nullptr;
-    int64_t* d_cp_row = mask ? a.cp_row : (int64_t*)w.cprow.p;
-    HIP_TRY(latok::launch_lead_compress(d_bmask, d_bspace, d_lead, (const int64_t*)w.bases.p, (const int64_t*)w.wcnt.p,
-                                        (const uint16_t*)w.wpref.p, words_b, total_bytes, a.boff, n_str, d_total_cps, d_cpbits, d_cpspace,
-                                        mask ? std::min(a.mask_cap, words_b) : words_b, d_cp_row, d_odd, st));
-    if (mask) return LATOK_OK;
-    if (feats)
-        HIP_TRY(latok::launch_lead_codes(a.u8, total_bytes, d_lead, (const int64_t*)w.bases.p, (const int64_t*)w.wcnt.p,
-                                         (const uint16_t*)w.wpref.p, words_b, (const uint8_t*)g.tb6rule.p, (uint8_t*)w.codes.p, g.n_cu, st));
+    LeadFront p{.b = Batch{Input{a.u8, Form::Utf8}, a.boff, n_str, total_bytes}, .space = spans, .codes = feats, .r_cps = a.result + 2,
+                .r_err = (int*)(a.result + 1), .r_odd = (int*)(a.result + 3), .st = st};
+    if (mask) {   // straight into the caller's buffers (no mask buffer, capacity 0: the workspace's plane takes it)
+        p.cpbits = a.mask;
+        p.cap_words = std::min(a.mask_cap, words_b);
+        p.cp_row = a.cp_row;
+    }
+    LeadPlanes t;
+    if ((rc = enqueue_lead_front(g, w, p, &t)) || mask) return rc;
     Compaction k;
-    k.b = Batch{Input{}, d_cp_row, n_str, total_bytes};   // (total: the upper bound; the stages read k.dt.total)
+    k.b = Batch{Input{}, t.cp_row, n_str, total_bytes};   // (total: the upper bound; the stages read k.dt.total)
     k.spans = spans;
     k.feats = feats;
     k.o32 = a.o32;
@@ -4021,10 +4019,10 @@ static int flow_submit_utf8(Ctx& g, const Utf8Flow& a) {
     k.feat = a.feat;
     k.cap = a.cap;
     k.p_tot = a.result;
-    k.pre_bits = d_cpbits;
-    k.pre_space = d_cpspace;
-    k.pre_codes = feats ? (const uint8_t*)w.codes.p : nullptr;
-    k.dt = latok::DeviceTotal{d_total_cps, d_odd};
+    k.pre_bits = t.cpbits;
+    k.pre_space = t.cpspace;
+    k.pre_codes = t.codes;
+    k.dt = latok::DeviceTotal{t.total_cps, p.r_odd};
     k.st = st;
     return enqueue_compaction_dev(g, w, k);
 }

@@ -224,19 +224,23 @@ def test_capacity(gpu, dev):
 
 
 # ---- (g) the calls that delegate -------------------------------------------------------------------------------------------
-def _host_calls(u8, boff, dt):
+CALLS = ("mask", "offsets", "spans", "features")
+
+
+def _host_calls(u8, boff, dt, names=CALLS):
     from latok_amd import batch
     out, routes = {}, []
-    bits, row = batch.split_mask_utf8_csr(u8, boff)
-    out["mask"] = (bits, row)
+    if "mask" in names:
+        out["mask"] = batch.split_mask_utf8_csr(u8, boff)
     for name, fn in (("offsets", batch.split_offsets_utf8_csr), ("spans", batch.token_spans_utf8_csr), ("features", batch.token_features_utf8_csr)):
-        out[name] = fn(u8, boff, dtype=dt)
-        routes.append(_route())
+        if name in names:
+            out[name] = fn(u8, boff, dtype=dt)
+            routes.append(_route())
     return out, routes
 
 
-def _dev_calls(lib, u8, boff, dt, shift=0):
-    """the four calls with device pointers, the bytes at an aligned address + shift"""
+def _dev_calls(lib, u8, boff, dt, shift=0, names=CALLS):
+    """the four calls (or those of `names`) with device pointers, the bytes at an aligned address + shift"""
     from latok_amd import _lib
     u8 = np.ascontiguousarray(u8, np.uint8)
     n_str, nbytes = boff.size - 1, int(boff[-1])
@@ -253,14 +257,17 @@ def _dev_calls(lib, u8, boff, dt, shift=0):
         _lib.check(lib.latok_memcpy_h2d(d["u8"] + shift, u8.ctypes.data, nbytes))
         _lib.check(lib.latok_memcpy_h2d(d["boff"], boff.ctypes.data, boff.nbytes))
         n = C.c_int64(-1)
-        _lib.check(lib.latok_split_mask_utf8_batch(d["u8"] + shift, d["boff"], n_str, -1, d["bits"], words, d["row"], C.byref(n), _lib.DEVICE_PTRS, None))
-        bits, row = np.zeros((n.value + 63) // 64, np.uint64), np.zeros(n_str + 1, np.int64)
-        if bits.size:
-            _lib.check(lib.latok_memcpy_d2h(bits.ctypes.data, d["bits"], bits.nbytes))
-        _lib.check(lib.latok_memcpy_d2h(row.ctypes.data, d["row"], row.nbytes))
-        out["mask"] = (bits, row)
+        if "mask" in names:
+            _lib.check(lib.latok_split_mask_utf8_batch(d["u8"] + shift, d["boff"], n_str, -1, d["bits"], words, d["row"], C.byref(n), _lib.DEVICE_PTRS, None))
+            bits, row = np.zeros((n.value + 63) // 64, np.uint64), np.zeros(n_str + 1, np.int64)
+            if bits.size:
+                _lib.check(lib.latok_memcpy_d2h(bits.ctypes.data, d["bits"], bits.nbytes))
+            _lib.check(lib.latok_memcpy_d2h(row.ctypes.data, d["row"], row.nbytes))
+            out["mask"] = (bits, row)
         for name, fn, width in (("offsets", lib.latok_split_offsets_utf8_batch, 1), ("spans", lib.latok_token_spans_utf8_batch, 2),
                                 ("features", lib.latok_token_features_utf8_batch, 4)):
+            if name not in names:
+                continue
             args = [d["u8"] + shift, d["boff"], n_str, -1, d["counts"], d["items"]] + ([d["feats"]] if width == 4 else []) + [cap, C.byref(n), flags, None]
             _lib.check(fn(*args))
             routes.append(_route())
@@ -290,8 +297,8 @@ def _utf32_calls(cps, row, dt):
             "spans": batch.token_spans_csr(cps, row, dtype=dt), "features": batch.token_features_csr(cps, row, dtype=dt)}
 
 
-def _same_results(got, want, what):
-    for name in ("mask", "offsets", "spans", "features"):
+def _same_results(got, want, what, names=CALLS):
+    for name in names:
         assert len(got[name]) == len(want[name]), (what, name)
         for k, (g, w) in enumerate(zip(got[name], want[name])):
             assert g.shape == w.shape and np.array_equal(g, w), (what, name, k)
@@ -371,6 +378,68 @@ def test_large_batches_route_by_route(gpu, case, route):
             got, routes = _dev_calls(gpu, u8, boff, dt, shift=4 if "shifted" in case else 0)
         assert routes == [route] * 3, (case, routes)
         _same_results(got, _utf32_calls(cps, row, dt), (case, dt))
+
+
+@functools.lru_cache(maxsize=None)
+def _growing_pair():
+    """two seeded batches with multi-byte chars -- A: the smallest above kSmallChars bytes (the first that takes route 3), B: about
+    twice A -- and A with one stray continuation byte; with every expectation: the UTF-32 calls on the reference's decode"""
+    from latok_amd import batch
+    from test_gpu_features_utf8_bytes import _to_bytes
+    rng = random.Random(0x9A0B)
+    blobs = _blobs(random_strings(rng, 12000, 0, 90, ALPHABETS["mixed"] + EXTRA))
+    ends = np.cumsum([len(b) for b in blobs])
+    n_a, n_b = (int(np.searchsorted(ends, k * _small_chars(), side="right")) + 1 for k in (1, 2))
+    assert n_b <= len(blobs)
+    odd = blobs[:n_a]
+    odd[n_a // 2] = b"\x80" + odd[n_a // 2]
+    case = {}
+    for key, part in (("A", blobs[:n_a]), ("B", blobs[:n_b]), ("A_odd", odd)):
+        u8, boff = _pack(part)
+        assert u8.size > _small_chars() and (u8 >= 0x80).any()
+        cps, row, _ = ref.decode_batch(u8, boff)
+        case[key] = dict(u8=u8, boff=boff, cps=np.ascontiguousarray(cps, np.uint32), row=row)
+    assert case["A"]["u8"].size - len(blobs[n_a - 1]) <= _small_chars() and case["B"]["u8"].size < 2 * _small_chars() + 400
+    a, b, o = case["A"], case["B"], case["A_odd"]
+    want = {("A", "spans"): batch.token_spans_csr(a["cps"], a["row"]), ("A", "mask"): (batch.split_mask_batch(a["cps"], a["row"]), a["row"]),
+            ("A", "offsets"): batch.split_offsets_csr(a["cps"], a["row"]), ("B", "features"): batch.token_features_csr(b["cps"], b["row"]),
+            ("B", "spans"): batch.token_spans_csr(b["cps"], b["row"], dtype=np.int32), ("A_odd", "spans"): batch.token_spans_csr(o["cps"], o["row"])}
+    # featurize in byte space: the same tokens and sums, the records as byte positions (B is well formed: a char's bytes follow from its value)
+    counts, spans4, feats = want["B", "features"]
+    pos = np.zeros(b["cps"].size + 1, np.int64)
+    np.cumsum(1 + (b["cps"] >= 0x80).astype(np.int64) + (b["cps"] >= 0x800) + (b["cps"] >= 0x10000), out=pos[1:])
+    assert pos[-1] == b["u8"].size
+    want["B", "bytes_features"] = (counts, _to_bytes(spans4, counts, b["row"], pos), feats)
+    return case, want
+
+
+@pytest.mark.parametrize("pointers", ["host", "device"])
+def test_calls_of_different_shape_share_one_growing_workspace(gpu, pointers):
+    """the blocking code-point calls keep the planes of their byte-space front in the context's workspace, which the compaction
+    behind the front sizes again: on a fresh context, calls of different kind and size in turn -- every plane is allocated by one
+    call, grown by the next and reused by the one after -- and each result is the UTF-32 call's on the reference's decode"""
+    from latok_amd import _lib, batch
+    from test_gpu_features_utf8_bytes import _dev_features
+    case, want = _growing_pair()
+    steps = [("A", "spans", np.int64, 3), ("B", "features", np.int64, 3), ("A", "mask", np.int64, None), ("B", "bytes_features", np.int64, 4),
+             ("A", "offsets", np.int64, 3), ("B", "spans", np.int32, 3), ("A_odd", "spans", np.int64, 2), ("A", "spans", np.int64, 3)]
+    with _lib.Context(_lib.default_device()):
+        for k, (key, name, dt, route) in enumerate(steps):
+            u8, boff = case[key]["u8"], case[key]["boff"]
+            if name == "bytes_features":
+                if pointers == "host":
+                    got = {name: batch.token_features_utf8_bytes_csr(u8, boff, dtype=dt)}
+                else:
+                    rc, n, res, _ = _dev_features(gpu, u8, boff, dt)
+                    assert rc == 0 and n == res[1].shape[0], (k, _lib.last_error())
+                    got = {name: res}
+                routes = [_route()]
+            elif pointers == "host":
+                got, routes = _host_calls(u8, boff, dt, names=(name,))
+            else:
+                got, routes = _dev_calls(gpu, u8, boff, dt, names=(name,))
+            assert routes == ([] if route is None else [route]), (k, key, name, routes)
+            _same_results(got, {name: want[key, name]}, (pointers, k, key, name), names=(name,))
 
 
 @pytest.mark.parametrize("rules", ["default", "all_columns"])
