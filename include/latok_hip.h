@@ -366,8 +366,10 @@ int latok_hashed_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t
  * (int32 in every mode) = the cells of row s in front of the padding.  max_length must be >= 1 + 2 add_special, else the call is
  * refused; *n_pieces_out (may be NULL) = the untruncated piece total.  n_str = 0 writes nothing; total_bytes = 0 gives rows of
  * specials and padding.  It waits for the piece total before it sizes its ids, so it waits three times.
- * Out of scope: lower-casing, accent stripping and CJK spacing (BERT's BasicTokenizer) -- tokens are latok's, bytes are verbatim, an
- * uncased vocabulary needs the caller to fold case first --, BPE and Unigram models, a flow form, sentence pairs. */
+ * Lower-casing, accent stripping, control-character cleaning and CJK spacing (the normalizer of BERT's BasicTokenizer) are a call of
+ * their own, latok_fold_utf8_bytes_batch below: its output, left on the device, is this call's input, and an uncased vocabulary is
+ * served by folding first.  Out of scope: the punctuation split of BERT's BasicTokenizer -- tokens are latok's --, the final-sigma
+ * rule of lower-casing, BPE and Unigram models, a flow form, sentence pairs. */
 typedef struct latok_wordpiece latok_wordpiece;
 int latok_wordpiece_create(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
                            const int32_t* word_ids /* may be NULL */, const uint8_t* prefix, int prefix_len, int max_chars, uint32_t seed,
@@ -385,6 +387,50 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
                                             int32_t sep_id, int32_t pad_id, int32_t* input_ids_out /* [n_str*max_length] */,
                                             int32_t* lengths_out /* [n_str] */, int64_t* n_pieces_out /* may be NULL */, int flags,
                                             void* stream);
+
+/* Case folding and accent stripping in byte space: UTF-8 in, folded UTF-8 out, what an uncased vocabulary (bert-base-uncased and its
+ * relatives) or a lower-casing vectorizer needs in front of the token calls above.  `fold` is a set of LATOK_FOLD_* bits in an
+ * argument of its own; any other bit is refused before any device work.
+ * THE MAP F_fold(c) takes one code point to 0 .. 3 code points; nothing depends on neighbouring characters.  Its data is Python's
+ * str.lower() and unicodedata of the interpreter that built the library; latok_amd/csrc/fold_tables.inc, generated by the build,
+ * records the UCD version in its first line (13.0.0 under Python 3.10, which is what the tests' fixture holds).
+ *   1. CLEAN (the _clean_text rule of BERT): c == 0, c == U+FFFD, or a category in {Cc, Cf} other than U+0009 / U+000A / U+000D maps to
+ *      the empty sequence; U+0009, U+000A, U+000D, U+0020 and category Zs map to [U+0020]; in both cases the map is done.
+ *   2. seq = [c].  LOWER: seq = the code points of chr(c).lower() (U+0130 gives two; no final-sigma rule: U+03A3 always gives
+ *      U+03C3).  STRIP_MARKS: every x of seq is replaced by the code points of its canonical decomposition (NFD) whose category is
+ *      not Mn; Hangul syllables become 2 .. 3 jamo by the arithmetic rule, the Mn code points map to nothing.
+ *   3. CJK_SPACE: c in 4E00-9FFF, 3400-4DBF, 20000-2A6DF, 2A700-2B73F, 2B740-2B81F, 2B820-2CEAF, F900-FAFF or 2F800-2FA1F gives
+ *      [U+0020] + seq + [U+0020].
+ *   4. Surrogates D800-DFFF and values above 0x10FFFF are their own image.
+ * The longest image has 3 code points and 12 bytes; the largest growth in bytes is 3x (a Hangul LVT syllable: 3 -> 9, U+1D160: 4 ->
+ * 12), the smallest image is empty.  So out_off[n_str] <= 3 * total_bytes: size buffers by it.
+ * THE BYTE RULE: the result for string s depends on the bytes of string s alone.  With k(b0) = 0 below 0x80 and for 0x80 .. 0xBF, 1
+ * for 0xC0 .. 0xDF, 2 for 0xE0 .. 0xEF, 3 for 0xF0 .. 0xFF, a byte b0 at i with k(b0) > 0 opens a SEQUENCE iff bytes i+1 .. i+k lie
+ * inside the same string and are all 10xxxxxx; a byte below 0x80 is a sequence of its own.  The sequence's value c is its payload
+ * bits put together (overlong, surrogate and too-large forms decode as they are; 0xF8 .. 0xFF carry 3 payload bits).  A sequence with
+ * F_fold(c) == [c] is copied verbatim, source bytes unchanged -- overlong forms survive --; any other sequence is replaced by the
+ * shortest-form UTF-8 of its image.  Every byte that belongs to no sequence (a lead with a truncated tail, a stray continuation
+ * byte) is copied verbatim: it is never taken for U+FFFD, and CLEAN does not drop it.  fold == 0 is the identity copy.  Nothing is
+ * invented and nothing is lost on malformed bytes, and for well-formed text t the output is "".join(F_fold(c) for c in t) in UTF-8.
+ * Relation to BERT: for text without U+03A3 and without the 23 code points that are not Mn and have a nonzero combining class,
+ * LOWER | STRIP_MARKS equals "".join(ch for ch in NFD(t.lower()) if category(ch) != "Mn"); the differences are the final sigma and
+ * the canonical reordering of surviving marks.
+ *   out_off[0] = 0, out_off[s+1] = out_off[s] + len(fold(string s)),  out_bytes[out_off[s] : out_off[s+1]] = fold(string s)
+ * Capacity protocol, in BYTES: out_cap too small -> nothing is written to out_bytes, out_off stays valid, the needed size is in
+ * *n_out_bytes and the call returns LATOK_ERR_INVALID; out_cap = 0 with out_bytes = NULL is a size query; out_bytes = NULL with
+ * out_cap > 0 is refused.  Host pointers or LATOK_DEVICE_PTRS (device UTF-8 pointer 16-byte aligned; the output then starts wherever
+ * the caller says and is a valid input of every byte-space call if that is 16-byte aligned), total_bytes = -1 as in the sibling
+ * calls; any other flag bit is refused.  n_str = 0 or total_bytes = 0 gives zero bytes with out_off cleared.  With device pointers the
+ * call synchronises once; with host pointers a second time behind the copy of the bytes.  Every batch size takes the same kernels and
+ * gives the same bytes.  Run-time rule tables (latok_set_rules) have no bearing on it.  The tables of the map reach the device with
+ * the first fold call of a context, not in latok_init. */
+#define LATOK_FOLD_LOWER 1
+#define LATOK_FOLD_STRIP_MARKS 2
+#define LATOK_FOLD_CLEAN 4
+#define LATOK_FOLD_CJK_SPACE 8
+int latok_fold_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, int fold,
+                                uint8_t* out_bytes, int64_t out_cap, int64_t* out_off /* int64[n_str+1] */,
+                                int64_t* n_out_bytes, int flags, void* stream);
 
 /* Token counting in byte space: the vocabulary of a corpus -- every distinct token with its frequency -- built on the device.
  * The tokens of a batch are the byte slices latok_token_spans_utf8_bytes_batch reports for it (default_tokenizer.py:149-160);

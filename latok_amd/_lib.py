@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("LATOK_HIP_LIB", os.path.join(_HERE, "liblatok_hip.so"
 OK, ERR_INVALID, ERR_HIP, ERR_NOT_INIT, ERR_NOMEM = 0, -1, -2, -3, -4
 DEVICE_PTRS = 1
 OUT_INT32 = 2
+FOLD_LOWER, FOLD_STRIP_MARKS, FOLD_CLEAN, FOLD_CJK_SPACE = 1, 2, 4, 8     # LATOK_FOLD_* (latok_fold_utf8_bytes_batch)
 FEATURE_COUNT = 25
 TILE_CHARS = 4096
 CORPUS_ASCII, CORPUS_UNICODE = 0, 1
@@ -65,6 +66,7 @@ SIGNATURES = {
     "latok_wordpiece_ids_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
     "latok_wordpiece_padded_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, i64, ci, C.c_int32, C.c_int32, C.c_int32, vp, vp,
                                                      C.POINTER(i64), ci, vp]),
+    "latok_fold_utf8_bytes_batch": (ci, [vp, vp, i64, i64, ci, vp, i64, vp, C.POINTER(i64), ci, vp]),
     "latok_counter_create": (ci, [i64, ci, C.c_uint32, C.POINTER(vp)]),
     "latok_counter_destroy": (ci, [vp]),
     "latok_counter_clear": (ci, [vp]),

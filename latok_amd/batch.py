@@ -463,6 +463,111 @@ def join_tokens_batch(texts, sep=" "):
     return [r.decode("utf-8", "surrogatepass") for r in rows]
 
 
+# case folding and accent stripping: UTF-8 in, folded UTF-8 out -- what an uncased vocabulary or a lower-casing vectorizer needs in
+# front of the token calls (the definition: include/latok_hip.h, latok_fold_utf8_bytes_batch)
+FOLD_LOWER, FOLD_STRIP_MARKS, FOLD_CLEAN, FOLD_CJK_SPACE = _lib.FOLD_LOWER, _lib.FOLD_STRIP_MARKS, _lib.FOLD_CLEAN, _lib.FOLD_CJK_SPACE
+FOLD_UNCASED = FOLD_LOWER | FOLD_STRIP_MARKS
+
+
+def _fold_bits(fold) -> int:
+    """the fold flags as an int 0 .. 15; anything else is a ValueError (raised before any device is asked for)"""
+    if isinstance(fold, (int, np.integer)) and not isinstance(fold, bool) and 0 <= int(fold) <= 15:
+        return int(fold)
+    raise ValueError("fold must be a combination of the FOLD_* flags (0 .. 15)")
+
+
+def _fold_csr(utf8, byte_off, fold):
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    fold = _fold_bits(fold)
+    n_str = byte_off.size - 1
+    total = int(byte_off[-1]) if n_str > 0 else 0
+    lib = _lib.ensure_init()
+    cap = max(3 * total, 1)                              # an image has at most three times the bytes of its sequence
+    out = np.empty(cap, np.uint8)
+    out_off = np.zeros(n_str + 1, np.int64)
+    n = C.c_int64(0)
+    _lib.check(lib.latok_fold_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, fold, _ptr(out), cap, _ptr(out_off), C.byref(n), 0, None))
+    return out[:n.value], out_off
+
+
+def fold_utf8_csr(utf8, byte_off, fold=FOLD_UNCASED):
+    """(out_bytes uint8[], out_off int64[n + 1]): every string folded -- lower-cased (``FOLD_LOWER``), canonically decomposed with
+    the nonspacing marks dropped (``FOLD_STRIP_MARKS``), control characters dropped and whitespace turned into U+0020
+    (``FOLD_CLEAN``), CJK ideographs set between spaces (``FOLD_CJK_SPACE``); row s = out_bytes[out_off[s]:out_off[s+1]].  Malformed
+    bytes and characters that are their own image are copied verbatim.  Folded on the device (``latok_fold_utf8_bytes_batch``)."""
+    out, out_off = _fold_csr(utf8, byte_off, fold)
+    return out.copy(), out_off
+
+
+def fold_utf8_batch(blobs, fold=FOLD_UNCASED):
+    """list[bytes] (UTF-8) -> list[bytes]: every string folded (fold_utf8_csr) -- with ``FOLD_UNCASED``, for text without a capital
+    sigma, ``"".join(c for c in unicodedata.normalize("NFD", t.lower()) if unicodedata.category(c) != "Mn")``."""
+    fold = _fold_bits(fold)
+    if len(blobs) == 0:
+        return []
+    utf8, byte_off = pack_utf8(blobs)
+    out, out_off = _fold_csr(utf8, byte_off, fold)
+    buf, o = out.tobytes(), out_off.tolist()
+    return [buf[a:b] for a, b in zip(o[:-1], o[1:])]
+
+
+def fold_batch(texts, fold=FOLD_UNCASED):
+    """list[str] -> list[str]: fold_utf8_batch of the strings' UTF-8 ("surrogatepass"), decoded row by row."""
+    rows = fold_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], fold)
+    return [r.decode("utf-8", "surrogatepass") for r in rows]
+
+
+class _DeviceFolded:
+    """A host batch folded into device memory, and the device buffers of the call that reads it: the batch is uploaded once and
+    folded there (``latok_fold_utf8_bytes_batch`` with device pointers); ``u8`` / ``off`` / ``n_str`` / ``total`` describe the folded
+    batch for a ``LATOK_DEVICE_PTRS`` call, whose outputs come from ``alloc`` and reach the host through ``fetch``.  No folded byte
+    visits the host.  Everything is freed on leaving the ``with`` block."""
+
+    def __init__(self, utf8, byte_off, fold):
+        utf8, byte_off = _csr_u8(utf8, byte_off)
+        self.lib, self._bufs = _lib.ensure_init(), []
+        self.n_str = byte_off.size - 1
+        total = int(byte_off[-1]) if self.n_str > 0 else 0
+        try:
+            src, src_off = self.alloc(total), self.alloc(byte_off.nbytes)
+            self.u8, self.off = self.alloc(3 * total), self.alloc(byte_off.nbytes)
+            if total > 0:
+                _lib.check(self.lib.latok_memcpy_h2d(src, _ptr(utf8), total))
+            _lib.check(self.lib.latok_memcpy_h2d(src_off, _ptr(byte_off), byte_off.nbytes))
+            n = C.c_int64(0)
+            _lib.check(self.lib.latok_fold_utf8_bytes_batch(src, src_off, self.n_str, total, fold, self.u8, max(3 * total, 1), self.off, C.byref(n),
+                                                            _lib.DEVICE_PTRS, None))
+            self.total = n.value
+        except Exception:
+            self.close()
+            raise
+
+    def alloc(self, nbytes):
+        p = self.lib.latok_dev_alloc(int(nbytes) + 64)
+        if not p:
+            raise MemoryError(_lib.last_error())
+        self._bufs.append(p)
+        return p
+
+    def fetch(self, ptr, shape, dtype):
+        out = np.empty(shape, dtype)
+        if out.nbytes > 0:
+            _lib.check(self.lib.latok_memcpy_d2h(_ptr(out), ptr, out.nbytes))
+        return out
+
+    def close(self):
+        bufs, self._bufs = self._bufs, []
+        for p in bufs:
+            self.lib.latok_dev_free(p)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 # token hashes: one 32-bit id per token (MurmurHash3 x86_32 of its UTF-8 bytes) -- what hashing vectorizers and hashed tables take
 def murmur3_32(data: bytes, seed=0) -> int:
     """MurmurHash3 x86_32 of ``data`` (bytes) with a 32-bit ``seed``, as an unsigned int: the word the device gives for a token with
@@ -631,14 +736,27 @@ def token_ids_utf8_csr(utf8, byte_off, vocab, unk_id=-1, dtype=np.int64, spans=F
     return (counts, ids, sp) if spans else (counts, ids)
 
 
-def token_ids_utf8_batch(blobs, vocab, unk_id=-1):
-    """list[bytes] (UTF-8) -> list of int32 arrays: the ids of every string's tokens ('' and whitespace-only -> empty)."""
-    unk_id = _unk32(unk_id)
+def _ids_csr_folded(utf8, byte_off, vocab, unk_id, fold):
+    """_ids_csr (int64, no spans) of the batch folded on the device"""
+    handle = _vocab_handle(vocab)
+    with _DeviceFolded(utf8, byte_off, fold) as d:
+        cap = max(d.total, 1)
+        counts, ids = d.alloc(d.n_str * 8), d.alloc(cap * 4)
+        n = C.c_int64(0)
+        _lib.check(d.lib.latok_token_ids_utf8_bytes_batch(d.u8, d.off, d.n_str, d.total, handle, unk_id, counts, None, ids, cap, C.byref(n),
+                                                          _lib.DEVICE_PTRS, None))
+        return d.fetch(counts, d.n_str, np.int64), d.fetch(ids, n.value, np.int32), None
+
+
+def token_ids_utf8_batch(blobs, vocab, unk_id=-1, fold=0):
+    """list[bytes] (UTF-8) -> list of int32 arrays: the ids of every string's tokens ('' and whitespace-only -> empty).  ``fold``
+    (FOLD_* flags): the batch is folded on the device first (fold_utf8_batch) and the tokens are those of the folded strings."""
+    unk_id, fold = _unk32(unk_id), _fold_bits(fold)
     _vocab_handle(vocab)
     if len(blobs) == 0:
         return []
     utf8, byte_off = pack_utf8(blobs)
-    counts, ids, _ = _ids_csr(utf8, byte_off, vocab, unk_id, np.int64, False)
+    counts, ids, _ = _ids_csr_folded(utf8, byte_off, vocab, unk_id, fold) if fold else _ids_csr(utf8, byte_off, vocab, unk_id, np.int64, False)
     return np.split(ids, np.cumsum(counts)[:-1])
 
 
@@ -655,6 +773,33 @@ def _n_features31(n_features) -> int:
     if isinstance(n_features, (int, np.integer)) and not isinstance(n_features, bool) and 1 <= int(n_features) <= 0x7FFFFFFF:
         return int(n_features)
     raise ValueError("n_features must be an int in 1 .. 2**31 - 1")
+
+
+def _terms_csr_folded(utf8, byte_off, vocab, hashed, fold):
+    """_terms_csr (int64) of the batch folded on the device: the size query, then the fill, on device buffers"""
+    with _DeviceFolded(utf8, byte_off, fold) as d:
+        lib, n_str = d.lib, d.n_str
+        indptr = d.alloc((n_str + 1) * 8)
+        oov = None if hashed else d.alloc(n_str * 8)
+        nnz = C.c_int64(0)
+
+        def call(indices, data, cap):
+            if hashed:
+                seed, n_features, alternate_sign = hashed
+                return lib.latok_hashed_term_counts_utf8_bytes_batch(d.u8, d.off, n_str, d.total, seed, n_features, 1 if alternate_sign else 0,
+                                                                     indptr, indices, data, cap, C.byref(nnz), None, _lib.DEVICE_PTRS, None)
+            return lib.latok_term_counts_utf8_bytes_batch(d.u8, d.off, n_str, d.total, vocab, indptr, oov, indices, data, cap, C.byref(nnz), None,
+                                                          _lib.DEVICE_PTRS, None)
+
+        rc = call(None, None, 0)
+        if rc != _lib.OK and not (rc == _lib.ERR_INVALID and nnz.value > 0):
+            _lib.check(rc)
+        need = nnz.value
+        if need > 0:
+            indices, data = d.alloc(need * 4), d.alloc(need * 4)
+            _lib.check(call(indices, data, need))
+        return (d.fetch(indptr, n_str + 1, np.int64), d.fetch(indices, need, np.int32) if need else np.empty(0, np.int32),
+                d.fetch(data, need, np.int32) if need else np.empty(0, np.int32), None if hashed else d.fetch(oov, n_str, np.int64))
 
 
 def _terms_csr(utf8, byte_off, vocab, hashed, dtype):
@@ -695,10 +840,14 @@ def term_counts_utf8_csr(utf8, byte_off, vocab, dtype=np.int64):
     return _terms_csr(utf8, byte_off, _vocab_handle(vocab), None, dtype)
 
 
-def term_counts_utf8_batch(blobs, vocab):
-    """list[bytes] (UTF-8) -> (indptr, indices, data, oov) of term_counts_utf8_csr, int64 ('' and whitespace-only -> empty rows)."""
-    handle = _vocab_handle(vocab)
+def term_counts_utf8_batch(blobs, vocab, fold=0):
+    """list[bytes] (UTF-8) -> (indptr, indices, data, oov) of term_counts_utf8_csr, int64 ('' and whitespace-only -> empty rows).
+    ``fold`` (FOLD_* flags): the batch is folded on the device first (fold_utf8_batch) -- ``CountVectorizer(lowercase=True)`` is
+    ``FOLD_LOWER``, ``strip_accents="unicode"`` adds ``FOLD_STRIP_MARKS``."""
+    handle, fold = _vocab_handle(vocab), _fold_bits(fold)
     utf8, byte_off = pack_utf8(blobs)
+    if fold:
+        return _terms_csr_folded(utf8, byte_off, handle, None, fold)
     return _terms_csr(utf8, byte_off, handle, None, np.int64)
 
 
@@ -717,10 +866,13 @@ def hashed_term_counts_utf8_csr(utf8, byte_off, n_features=1 << 20, seed=0, alte
     return _terms_csr(utf8, byte_off, None, (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), dtype)[:3]
 
 
-def hashed_term_counts_utf8_batch(blobs, n_features=1 << 20, seed=0, alternate_sign=True):
-    """list[bytes] (UTF-8) -> (indptr, indices, data) of hashed_term_counts_utf8_csr, int64."""
-    hashed = (_seed32(seed), _n_features31(n_features), bool(alternate_sign))
+def hashed_term_counts_utf8_batch(blobs, n_features=1 << 20, seed=0, alternate_sign=True, fold=0):
+    """list[bytes] (UTF-8) -> (indptr, indices, data) of hashed_term_counts_utf8_csr, int64.  ``fold`` (FOLD_* flags): the batch is
+    folded on the device first (fold_utf8_batch); ``HashingVectorizer`` lower-cases by default: ``FOLD_LOWER``."""
+    hashed, fold = (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), _fold_bits(fold)
     utf8, byte_off = pack_utf8(blobs)
+    if fold:
+        return _terms_csr_folded(utf8, byte_off, None, hashed, fold)[:3]
     return _terms_csr(utf8, byte_off, None, hashed, np.int64)[:3]
 
 
@@ -736,8 +888,11 @@ class WordPiece:
     ``str`` (``str`` is encoded as UTF-8 with surrogatepass), ``ids`` an optional int32 per word (default: its index), ``prefix``
     the continuation prefix (0 .. 8 bytes, ``##`` in BERT's files), ``max_chars`` BERT's ``max_input_chars_per_word`` (1 .. 1024:
     a token of more chars is one unknown piece), ``seed`` the 32-bit seed of the tables' hash.  Of a duplicate word the first wins.
-    Bytes are compared verbatim: there is no lower-casing and no accent stripping.  Immutable; ``len()`` is the number of words
-    given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
+    Bytes are compared verbatim: the object itself does no lower-casing and no accent stripping.  An uncased vocabulary
+    (``bert-base-uncased``) is served by the ``fold=FOLD_UNCASED`` keyword of the ``wordpiece_*`` calls, which folds the batch on the
+    device first (``fold_utf8_batch``; fold the words the same way if the file is not folded already).  Still out of scope: the
+    punctuation split of BERT's BasicTokenizer (tokens are latok's), the final-sigma rule, BPE and Unigram models, a flow form and
+    sentence pairs.  Immutable; ``len()`` is the number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
 
     def __init__(self, words, ids=None, prefix=b"##", max_chars=100, seed=0):
         self.handle = None
@@ -843,25 +998,53 @@ def wordpiece_ids_utf8_csr(utf8, byte_off, wp, unk_id=-1, dtype=np.int64, spans=
     return indptr, ids, sp
 
 
-def wordpiece_ids_utf8_batch(blobs, wp, unk_id=-1):
-    """list[bytes] (UTF-8) -> (indptr, ids, spans) of wordpiece_ids_utf8_csr, int64 ('' and whitespace-only -> empty rows)."""
-    unk_id = _unk32(unk_id)
+def _wordpiece_ids_folded(utf8, byte_off, wp, unk_id, fold):
+    """wordpiece_ids_utf8_csr (int64, with spans) of the batch folded on the device: the size query, then the fill, on device buffers"""
+    handle = _wordpiece_handle(wp)
+    with _DeviceFolded(utf8, byte_off, fold) as d:
+        indptr = d.alloc((d.n_str + 1) * 8)
+        n = C.c_int64(0)
+
+        def call(ids, sp, cap):
+            return d.lib.latok_wordpiece_ids_utf8_bytes_batch(d.u8, d.off, d.n_str, d.total, handle, unk_id, indptr, ids, sp, cap, C.byref(n), None,
+                                                              _lib.DEVICE_PTRS, None)
+
+        rc = call(None, None, 0)
+        if rc != _lib.OK and not (rc == _lib.ERR_INVALID and n.value > 0):
+            _lib.check(rc)
+        need = n.value
+        if need > 0:
+            ids, sp = d.alloc(need * 4), d.alloc(need * 16)
+            _lib.check(call(ids, sp, need))
+        return (d.fetch(indptr, d.n_str + 1, np.int64), d.fetch(ids, need, np.int32) if need else np.empty(0, np.int32),
+                d.fetch(sp, (need, 2), np.int64) if need else np.empty((0, 2), np.int64))
+
+
+def wordpiece_ids_utf8_batch(blobs, wp, unk_id=-1, fold=0):
+    """list[bytes] (UTF-8) -> (indptr, ids, spans) of wordpiece_ids_utf8_csr, int64 ('' and whitespace-only -> empty rows).  ``fold``
+    (FOLD_* flags, ``FOLD_UNCASED`` for an uncased vocabulary): the batch is uploaded once, folded on the device
+    (fold_utf8_batch) and cut there; the spans are then byte ranges of the FOLDED string, not of the input."""
+    unk_id, fold = _unk32(unk_id), _fold_bits(fold)
     _wordpiece_handle(wp)
     utf8, byte_off = pack_utf8(blobs)
+    if fold:
+        return _wordpiece_ids_folded(utf8, byte_off, wp, unk_id, fold)
     return wordpiece_ids_utf8_csr(utf8, byte_off, wp, unk_id)
 
 
-def wordpiece_ids_batch(texts, wp, unk_id=-1):
-    """list[str] -> (indptr, ids, spans): wordpiece_ids_utf8_batch of the strings' UTF-8 ("surrogatepass"); the spans are in bytes."""
-    return wordpiece_ids_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], wp, unk_id)
+def wordpiece_ids_batch(texts, wp, unk_id=-1, fold=0):
+    """list[str] -> (indptr, ids, spans): wordpiece_ids_utf8_batch of the strings' UTF-8 ("surrogatepass"); the spans are in bytes
+    (with ``fold``: bytes of the folded string)."""
+    return wordpiece_ids_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], wp, unk_id, fold)
 
 
-def wordpiece_encode_utf8_batch(blobs, wp, max_length, cls_id=None, sep_id=None, pad_id=0, unk_id=-1):
+def wordpiece_encode_utf8_batch(blobs, wp, max_length, cls_id=None, sep_id=None, pad_id=0, unk_id=-1, fold=0):
     """list[bytes] (UTF-8) -> (input_ids int32[n, max_length], attention_mask int32[n, max_length]): what a BERT-family model takes.
     Row s = ``cls_id``, the first pieces of string s, ``sep_id``, then ``pad_id``; the two specials are added when BOTH are given
     and omitted when both are None.  A longer row is truncated to ``max_length`` cells, specials included.  attention_mask is 1 on
-    the cells in front of the padding.  One call of ``latok_wordpiece_padded_utf8_bytes_batch``."""
-    unk_id, pad_id = _unk32(unk_id), _unk32(pad_id)
+    the cells in front of the padding.  One call of ``latok_wordpiece_padded_utf8_bytes_batch``; with ``fold`` (FOLD_* flags,
+    ``FOLD_UNCASED`` for an uncased vocabulary) behind one call of ``latok_fold_utf8_bytes_batch``, both on device memory."""
+    unk_id, pad_id, fold = _unk32(unk_id), _unk32(pad_id), _fold_bits(fold)
     if (cls_id is None) != (sep_id is None):
         raise ValueError("cls_id and sep_id go together: give both or neither")
     special = cls_id is not None
@@ -872,6 +1055,14 @@ def wordpiece_encode_utf8_batch(blobs, wp, max_length, cls_id=None, sep_id=None,
     utf8, byte_off = pack_utf8(blobs)
     n_str, total = len(blobs), int(byte_off[-1])
     lib = _lib.ensure_init()
+    if fold and n_str > 0:
+        with _DeviceFolded(utf8, byte_off, fold) as d:
+            d_ids, d_len = d.alloc(n_str * int(max_length) * 4), d.alloc(n_str * 4)
+            _lib.check(lib.latok_wordpiece_padded_utf8_bytes_batch(d.u8, d.off, n_str, d.total, handle, unk_id, int(max_length), 1 if special else 0,
+                                                                   cls_id, sep_id, pad_id, d_ids, d_len, None, _lib.DEVICE_PTRS, None))
+            input_ids, lengths = d.fetch(d_ids, (n_str, int(max_length)), np.int32), d.fetch(d_len, n_str, np.int32)
+        mask = (np.arange(int(max_length), dtype=np.int32)[None, :] < lengths[:, None]).astype(np.int32)
+        return input_ids, mask
     input_ids = np.empty((n_str, int(max_length)), np.int32)
     lengths = np.zeros(n_str, np.int32)
     _lib.check(lib.latok_wordpiece_padded_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, handle, unk_id, int(max_length),

@@ -34,6 +34,8 @@
 #include "vocab_table.h"
 #include "count_table.h"
 #include "wordpiece.h"
+#include "fold_map.h"
+#include "fold_tables.inc"
 
 static_assert(LATOK_TBL_SHIFT == latok::kTblShift, "table shift");
 static_assert(LATOK_TBL_STAGE1_LEN == latok::kStage1Len, "stage-1 length");
@@ -277,6 +279,11 @@ struct Ctx {
     // tables
     DevBuf t1, t1rule, t2code, t2cls, cw;
     DevBuf tb6, tb6rule;   // byte space: its own class table, split codes / rule codes (build_byte_tables)
+    // case folding (latok_fold_utf8_bytes_batch): the tables of fold_map.h, uploaded by the context's first fold call; the string-end
+    // bitmap and the group prefixes of the batch in hand
+    DevBuf fold_tab, fold_start, fold_pref;
+    FoldTables fold_t;
+    bool fold_ready = false;
     // runtime rule tables (latok_set_rules); off = the built-in default_tokenizer.py tables
     bool rules_on = false;
     lk_rule_tables rules;
@@ -756,8 +763,10 @@ static void ctx_release(Ctx& g) {   // caller holds g.mu (or owns g exclusively)
     g.plan_cus = 0;
     g.last = Ctx::LastPlan{};
     for (DevBuf* b : {&g.t1, &g.t1rule, &g.tb6, &g.tb6rule, &g.t2code, &g.t2cls, &g.cw, &g.h_row, &g.h_out, &g.counts, &g.scan_tot, &g.u_bytes,
-                      &g.u_boff, &g.u_cnt, &g.u_row, &g.u_pref, &g.h_aux})
+                      &g.u_boff, &g.u_cnt, &g.u_row, &g.u_pref, &g.h_aux, &g.fold_tab, &g.fold_start, &g.fold_pref})
         b->release();
+    g.fold_ready = false;
+    g.fold_t = FoldTables{};
     g.ws.release();
     for (auto& e : g.ev) {
         if (e) (void)hipEventDestroy(e);
@@ -2188,6 +2197,88 @@ int latok_join_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_
     return deliver_sized(c, n, out_cap, "output capacity too small: need %lld bytes", {{out_bytes, a.out, 1}});
 }
 
+/* case folding and accent stripping in byte space: UTF-8 in, folded UTF-8 out (fold_kernels.hip; the map: fold_map.h).  One stream:
+ *   k_fold_starts     the string-end bitmap over the bytes
+ *   k_fold_counts     output bytes per 16-byte group (prefix inside its tile) and per tile
+ *   k_scan_chained    tile ranks; THE byte total -> scalar word 0 and the pinned pair
+ *   k_fold_write      the bytes (gate: total <= cap), out_off
+ * The tables reach the device with the context's first fold call. */
+static int ensure_fold_tables(Ctx& g, hipStream_t st) {
+    if (g.fold_ready) return LATOK_OK;
+    int rc;
+    const size_t b1 = align16(sizeof(kFoldStage1)), b2 = align16(sizeof(kFoldStage2)), b3 = align16(sizeof(kFoldRec)), b4 = align16(sizeof(kFoldHigh));
+    if ((rc = g.fold_tab.ensure(b1 + b2 + b3 + b4))) return rc;
+    uint8_t* p = (uint8_t*)g.fold_tab.p;
+    HIP_TRY(hipMemcpyAsync(p, kFoldStage1, sizeof(kFoldStage1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p + b1, kFoldStage2, sizeof(kFoldStage2), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p + b1 + b2, kFoldRec, sizeof(kFoldRec), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p + b1 + b2 + b3, kFoldHigh, sizeof(kFoldHigh), hipMemcpyHostToDevice, st));
+    g.fold_t.stage1 = (const uint16_t*)p;
+    g.fold_t.stage2 = (const uint16_t*)(p + b1);
+    g.fold_t.rec = (const uint32_t*)(p + b1 + b2);
+    g.fold_t.high = (const uint32_t*)(p + b1 + b2 + b3);
+    g.fold_t.n_high = (int)kFoldHighN;
+    g.fold_ready = true;
+    return LATOK_OK;
+}
+int latok_fold_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, int fold,
+                                uint8_t* out_bytes, int64_t out_cap, int64_t* out_off, int64_t* n_out_bytes, int flags, void* stream) {
+    LATOK_ENTER();
+    if (fold & ~(LATOK_FOLD_LOWER | LATOK_FOLD_STRIP_MARKS | LATOK_FOLD_CLEAN | LATOK_FOLD_CJK_SPACE))
+        return fail(LATOK_ERR_INVALID, "unknown fold bit in %d", fold);
+    if (flags & ~LATOK_DEVICE_PTRS) return fail(LATOK_ERR_INVALID, "unknown flag");
+    if (!n_out_bytes) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
+    *n_out_bytes = 0;
+    if (out_cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
+    if (!out_bytes && out_cap > 0) return fail(LATOK_ERR_INVALID, "out_bytes is NULL but out_cap > 0 (a size query passes out_cap = 0)");
+    if (n_str > 0 && !out_off) return fail(LATOK_ERR_INVALID, "out_off is NULL");
+    int rc = need_init(g);
+    if (rc) return rc;
+    BytesCall c;
+    if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
+    const bool dev = c.dev;
+    const hipStream_t st = c.st;
+    if (c.empty) {   // no byte: empty rows (device pointers: one wait, whatever was cleared)
+        if ((rc = zero_counts(dev, out_off, (size_t)(n_str + 1) * 8, st))) return rc;
+        if (dev) HIP_TRY(hipStreamSynchronize(st));
+        return LATOK_OK;
+    }
+    if (dev && ((uintptr_t)out_off & 7) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    if ((rc = c.stage(g, 13, WsShape{}, kClearPair))) return rc;
+    const int64_t total = c.total;
+    if ((rc = ensure_fold_tables(g, st)) || (rc = g.fold_start.ensure((size_t)latok::fold_start_words(total) * 4)) ||
+        (rc = g.fold_pref.ensure((size_t)latok::fold_groups(total) * 2)))
+        return rc;
+    // (an image has at most three times the bytes of its sequence: a larger capacity gates nothing, and the staging is sized by it)
+    const int64_t cap = out_bytes ? std::min(out_cap, 3 * total) : 0;
+    uint8_t* d_out = out_bytes;
+    int64_t* d_out_off = out_off;
+    if (!dev) {
+        if ((rc = g.h_out.ensure((size_t)cap + 16)) || (rc = g.h_aux.ensure((size_t)(n_str + 1) * 8))) return rc;
+        if (out_bytes) d_out = (uint8_t*)g.h_out.p;
+        d_out_off = (int64_t*)g.h_aux.p;
+    }
+    Workspace& w = g.ws;
+    uint32_t* d_start = (uint32_t*)g.fold_start.p;
+    uint16_t* d_pref = (uint16_t*)g.fold_pref.p;
+    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
+    int64_t* d_rank = (int64_t*)w.bases.p;
+    int64_t* d_total = (int64_t*)w.scalar.p;
+    const uint8_t* d_u8 = (const uint8_t*)c.d.in.p;
+    unsigned epoch = 0;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    HIP_TRY(latok::launch_fold_starts(c.d.row, n_str, total, d_start, st));
+    HIP_TRY(latok::launch_fold_counts(d_u8, total, d_start, fold, g.fold_t, d_pref, d_tcnt, st));
+    HIP_TRY(latok::launch_tile_scan(d_tcnt, latok::fold_tiles(total), d_rank, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total,
+                                    c.p_tot, (int*)(c.p_tot + 1) + 1, st));
+    HIP_TRY(latok::launch_fold_write(d_u8, total, d_start, fold, g.fold_t, d_pref, d_rank, d_tcnt, c.d.row, n_str, d_out, cap, d_total, d_out_off, st));
+    if (!dev) HIP_TRY(hipMemcpyAsync(out_off, d_out_off, (size_t)(n_str + 1) * 8, hipMemcpyDeviceToHost, st));   // valid whatever the capacity
+    int64_t n = 0;
+    if ((rc = c.wait_totals(g, 0, &n))) return rc;
+    *n_out_bytes = n;
+    return deliver_sized(c, n, out_cap, "output capacity too small: need %lld bytes", {{out_bytes, d_out, 1}});
+}
+
 /* token hashes and token ids in byte space: one MurmurHash3 x86_32 word per token, or its id in a vocabulary, rank-aligned with the
  * span records (enqueue_token_words).  The two blocking entry points' shared body: ids = the call takes a vocabulary. */
 static int token_words_common(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, bool ids, const latok_vocab* vocab,
@@ -3501,6 +3592,16 @@ extern "C" int latok_debug_terms_limits(int64_t* out, int n) {
     return k;
 }
 
+/* test hook (not part of the ABI; needs no device): the constants of the fold call: out[0] = kFoldTile (bytes per wave of
+ * k_fold_counts / k_fold_write), out[1] = bytes per lane and load (16), out[2] = the largest growth in bytes (3) */
+extern "C" int latok_debug_fold_limits(int64_t* out, int n) {
+    const int64_t v[3] = {latok::kFoldTile, 16, 3};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 3 ? n : 3;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
 /* test hook (not part of the ABI; needs no device): the constants of the WordPiece calls: out[0] = kWpBlock (tokens per workgroup of
  * k_wp_count / k_wp_emit), out[1] = entries per workgroup of the chained scan over the piece counts (one scan block), out[2] =
  * kWpMaxPrefix, out[3] = kWpMaxChars.  Returns the number of values written. */
@@ -3573,7 +3674,8 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
  * 5: joined token text of UTF-8 in byte space (every batch size; there is no small-batch route),
  * 6: token hashes of UTF-8 in byte space (every batch size as well); 7: token ids of UTF-8 in byte space (likewise);
  * 9 / 10: term counts of UTF-8 in byte space, vocabulary form / hashed form (likewise);
- * 11 / 12: WordPiece ids of UTF-8 in byte space, CSR form / padded form (likewise) */
+ * 11 / 12: WordPiece ids of UTF-8 in byte space, CSR form / padded form (likewise);
+ * 13: case folding of UTF-8 in byte space (likewise) */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;

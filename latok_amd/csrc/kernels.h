@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fold_map.h"
 #include "split_code.h"
 
 namespace latok {
@@ -376,6 +377,19 @@ hipError_t launch_corpus_fill(uint64_t seed, int model, uint64_t sid0, int64_t n
                               uint32_t* cps, hipStream_t st);
 hipError_t launch_stream_read(const void* src, int64_t bytes, uint32_t* sink, int n_cu, hipStream_t st);
 hipError_t launch_utf8_bytes(const uint32_t* cps, int64_t n, unsigned long long* total, hipStream_t st);
+// fold_kernels.hip: case folding and accent stripping of a UTF-8 batch (fold_map.h).  start32 = fold_start_words(total) dwords,
+// group_pref = fold_groups(total) entries, tile_cnt / tile_rank = fold_tiles(total) entries, scanned by launch_tile_scan between the
+// two passes.  launch_fold_write stores the bytes only if the total fits cap (out may be NULL) and out_off[n_str + 1] always.
+constexpr int kFoldTile = 4096;   // bytes per wave of k_fold_counts / k_fold_write (latok_debug_fold_limits)
+int64_t fold_start_words(int64_t total);
+int64_t fold_groups(int64_t total);
+int64_t fold_tiles(int64_t total);
+hipError_t launch_fold_starts(const int64_t* byte_off, int64_t n_str, int64_t total, uint32_t* start32, hipStream_t st);
+hipError_t launch_fold_counts(const uint8_t* u8, int64_t total, const uint32_t* start32, int fold, const FoldTables& T, uint16_t* group_pref,
+                              int64_t* tile_cnt, hipStream_t st);
+hipError_t launch_fold_write(const uint8_t* u8, int64_t total, const uint32_t* start32, int fold, const FoldTables& T, const uint16_t* group_pref,
+                             const int64_t* tile_rank, const int64_t* tile_cnt, const int64_t* row_off, int64_t n_str, uint8_t* out, int64_t cap,
+                             const int64_t* n_items_dev, int64_t* out_off, hipStream_t st);
 
 }  // namespace latok
 #endif

@@ -54,6 +54,9 @@
                   against collections.Counter over batch.tokenize_utf8_batch(blobs), sorted the same way; one line each
   py_ids         end to end in Python on host blobs (the first --py-strings strings): batch.token_ids_utf8_batch(blobs, vocab)
                   against [[d.get(t, -1) for t in row] for row in batch.tokenize_utf8_batch(blobs)]; one line each
+  bytes_fold / bytes_fold_wp   latok_fold_utf8_bytes_batch (LOWER | STRIP_MARKS, device pointers; yardstick: bytes_join of the same run) /
+                 the same, then latok_wordpiece_padded_utf8_bytes_batch on the folded bytes (yardstick: bytes_wp_padded alone)
+  py_fold        end to end in Python on host blobs: batch.fold_utf8_batch(blobs) against NFD(t.lower()) without Mn on the host
   py_join        end to end in Python on host blobs (the first --py-strings strings): batch.join_tokens_utf8_batch(blobs) against the
                   only route to the same rows without it, [b" ".join(t) for t in batch.tokenize_utf8_batch(blobs)]; one line each
   rules_mask      latok_split_mask_batch after latok_set_rules(built-in tables)   (8f-4)
@@ -403,7 +406,8 @@ def main():
     join_leg = [p for p in paths if p in ("bytes_join", "bytes_join_flow", "bytes_spans32", "bytes_spans32_flow", "bytes_hashes32",
                                           "bytes_hashes32_flow", "bytes_hashes_only", "bytes_hashes_only_flow", "bytes_ids32", "bytes_ids32_flow",
                                           "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "py_terms",
-                                          "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join", "bytes_wp32", "bytes_wp_padded", "py_wp")]
+                                          "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join", "bytes_wp32", "bytes_wp_padded", "py_wp",
+                                          "bytes_fold", "bytes_fold_wp", "py_fold")]
     if join_leg:
         jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64, cap * 4, cap * 4)]
         if not all(jb):
@@ -507,6 +511,42 @@ def main():
             w, _, w_block, w_len = corpus_wordpiece()
             return lib.latok_wordpiece_padded_utf8_bytes_batch(d_u8, d_boff, n, n8, w.handle, -1, WP_LEN, 1, 101, 102, 0, w_block, w_len,
                                                                C.byref(nout), D, None)
+
+        note_f = ("UTF-8 bytes + 8 B/string read twice (count pass, write pass); 1 bit/byte string-end bitmap written and read; 2 B per 16 bytes "
+                  "group prefixes written and read; 1 B/output byte + 8 B/string row offsets written (LOWER | STRIP_MARKS)")
+        FOLD = _lib.FOLD_LOWER | _lib.FOLD_STRIP_MARKS
+        fold_box, fold_wp_box = [], []
+
+        def fold_bufs():
+            if not fold_box:
+                fb = [lib.latok_dev_alloc(sz) for sz in (3 * n8 + 64, (n + 1) * 8 + 64)]
+                if not all(fb):
+                    raise RuntimeError(_lib.last_error())
+                fold_box.extend(fb)
+            return fold_box
+
+        def fold_blocking():
+            f_out, f_off = fold_bufs()
+            return lib.latok_fold_utf8_bytes_batch(d_u8, d_boff, n, n8, FOLD, f_out, 3 * n8, f_off, C.byref(nout), D, None)
+
+        def folded_wordpiece():
+            """the WordPiece vocabulary of bytes_fold_wp, built once: the words of bytes_wp_padded, folded (of words that fold alike the first wins)"""
+            if not fold_wp_box:
+                from latok_amd import batch
+                corpus_wordpiece()
+                fold_wp_box.append(batch.WordPiece(batch.fold_utf8_batch(words_box[0], FOLD), max_chars=100, seed=SEED))
+            return fold_wp_box[0]
+
+        def fold_wp_blocking():
+            """fold, then the padded WordPiece call on the folded bytes, both with device pointers"""
+            f_out, f_off = fold_bufs()
+            _, _, w_block, w_len = corpus_wordpiece()
+            folded = C.c_int64(0)
+            rc = lib.latok_fold_utf8_bytes_batch(d_u8, d_boff, n, n8, FOLD, f_out, 3 * n8, f_off, C.byref(folded), D, None)
+            if rc:
+                return rc
+            return lib.latok_wordpiece_padded_utf8_bytes_batch(f_out, f_off, n, folded.value, folded_wordpiece().handle, -1, WP_LEN, 1, 101, 102, 0,
+                                                               w_block, w_len, C.byref(nout), D, None)
 
         note_c = ("UTF-8 bytes + 8 B/string read, the bytes of every token read once more, one 8-byte slot per probe step and the word of a "
                   "candidate read from the text or the blob; per tile and distinct word one 8-byte atomic add; two passes over the slots")
@@ -612,6 +652,38 @@ def main():
             elif name == "bytes_wp_padded":   # (items = the untruncated piece total; the block is [n, WP_LEN] with [CLS] / [SEP])
                 run(name, wp_padded_blocking, lambda: n8 + csr + 4 * n + 4 * n * WP_LEN,
                     note_w.replace("4 B/string indptr + 4 B/piece ids + 8 B/piece spans", "4 B/string lengths + 4 B/cell of the [n, %d] block" % WP_LEN))
+            elif name == "bytes_fold":   # (items = output bytes)
+                run(name, fold_blocking, lambda: 2 * (n8 + csr) + 2 * (n8 // 8) + 2 * (n8 // 8) + nout.value + csr, note_f)
+            elif name == "bytes_fold_wp":   # (items = the untruncated piece total of the folded batch)
+                run(name, fold_wp_blocking, lambda: n8 + csr + 4 * n + 4 * n * WP_LEN,
+                    "bytes_fold, then bytes_wp_padded on the folded bytes (vocabulary folded alike); alg_bytes are those of bytes_wp_padded alone")
+            elif name == "py_fold":   # host blobs in, host rows out, against the host expression
+                import unicodedata
+                from latok_amd import batch
+                m = min(args.py_strings, n)
+                blob = u8[:int(boff[m])].tobytes()
+                blobs = [blob[int(a):int(b)] for a, b in zip(boff[:m], boff[1:m + 1])]
+
+                def on_host():
+                    out = []
+                    for b in blobs:
+                        t = unicodedata.normalize("NFD", b.decode("utf-8", "surrogatepass").lower())
+                        out.append("".join(ch for ch in t if unicodedata.category(ch) != "Mn").encode("utf-8", "surrogatepass"))
+                    return out
+
+                routes = (("py_fold_utf8_batch", lambda: batch.fold_utf8_batch(blobs, FOLD)), ("py_lower_nfd_strip_mn", on_host))
+                a_rows, b_rows = routes[0][1](), routes[1][1]()
+                differ = sum(x != y for x, y in zip(a_rows, b_rows))   # (final sigma, reordered marks: out of scope of the device call)
+                for r in range(args.repeat):
+                    for rname, fn in routes:
+                        t = time.perf_counter()
+                        rows = fn()
+                        dt = time.perf_counter() - t
+                        print(json.dumps({"path": rname, "workload": args.workload, "strings": m, "utf8_bytes": len(blob),
+                                          "out_bytes": sum(map(len, rows)), "rows_that_differ": differ, "ms_per_call": dt * 1e3,
+                                          "utf8_GBps": len(blob) / dt / 1e9,
+                                          "note": "end to end in Python: list[bytes] in, list[bytes] out, pack and host slicing included",
+                                          "repeat": r}), flush=True)
             elif name == "py_wp":   # host blobs in, the CSR arrays out, both routes in this process
                 from latok_amd import batch
                 m = min(args.py_strings, n)
@@ -773,6 +845,10 @@ def main():
             vocab_box[0].close()
         if counter_box:
             counter_box[0].close()
+        if fold_wp_box:
+            fold_wp_box[0].close()
+        for p_ in fold_box:
+            lib.latok_dev_free(p_)
         if wp_box:
             wp_box[0].close()
             for p_ in wp_box[1:]:
