@@ -323,6 +323,7 @@ struct Ctx {
     // test hooks: latok_debug_set_plan_cus (0 = the device's own CU count), what the last run_pipeline launched and the route the
     // last compaction call took (latok_debug_last_route)
     int plan_cus = 0;
+    latok::PlanForce plan_force;         // latok_debug_set_tile_plan
     int last_route = 0;
     struct LastPlan {
         latok::LaunchPlan plan{};
@@ -433,7 +434,7 @@ int run_pipeline(Ctx& g, Workspace& w, const Pipe& a) {
     const int n_cu = g.plan_cus > 0 ? g.plan_cus : g.n_cu;   // latok_debug_set_plan_cus: plan and launch as if the chip had n_cu CUs
     const bool one_launch_ok = a.stages == 7 && in.form == Form::Utf32 && !a.tiles_begin && !a.tiles_end && one_segment_enabled();
     latok::LaunchPlan L;
-    latok::plan_launch(n_tiles, n_cu, &w != &g.ws, mode, one_launch_ok, &L);
+    latok::plan_launch(n_tiles, n_cu, &w != &g.ws, mode, one_launch_ok, &L, &g.plan_force);
     P.seg_tiles = L.seg_tiles;
     P.n_segs = L.n_segs;
     const bool one_launch = L.one_launch != 0;
@@ -3647,9 +3648,39 @@ extern "C" int latok_debug_set_plan_cus(int n_cu) {
     return LATOK_OK;
 }
 
+/* test hook (not part of the ABI; needs no device): the constants of the tile kernel's held segments (kernels.h): out[0] =
+ * kSegHoldTiles (a segment of at most that many tiles of a UTF-32 bitmask batch stores its mask words as one run at its end),
+ * out[1] = kSegHoldLdsRounds (tiles per wave whose words wait in LDS; the others wait in registers).  Returns the number of values
+ * written. */
+extern "C" int latok_debug_tile_limits(int64_t* out, int n) {
+    const int64_t v[2] = {latok::kSegHoldTiles, latok::kSegHoldLdsRounds};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 2 ? n : 2;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
+/* test hook (not part of the ABI): the tile pipeline of the current context plans with a segment length of seg_tiles tiles (0 = the
+ * plan's own; kWPB .. kSegMax, and the one-launch path is then not taken), launches at most `grid` workgroups (0 = the plan's own: a
+ * smaller grid makes each persistent workgroup walk more segments) and, with hold = 0, never holds a segment's mask words for the
+ * write-out at its end (-1 = the plan's own: segments of at most kSegHoldTiles tiles are held).  (0, 0, -1) restores the plan. */
+extern "C" int latok_debug_set_tile_plan(int seg_tiles, int grid, int hold) {
+    LATOK_ENTER();
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (seg_tiles != 0 && (seg_tiles < latok::kWPB || seg_tiles > latok::kSegMax))
+        return fail(LATOK_ERR_INVALID, "segment length must be 0 or %d..%d", latok::kWPB, latok::kSegMax);
+    if (grid < 0 || (hold != 0 && hold != -1)) return fail(LATOK_ERR_INVALID, "grid >= 0, hold 0 or -1");
+    g.plan_force.seg_tiles = seg_tiles;
+    g.plan_force.grid = grid;
+    g.plan_force.hold = hold;
+    return LATOK_OK;
+}
+
 /* test hook (not part of the ABI): what the last run_pipeline of the current context launched.  out[0] = mode (after the
  * rules), out[1] = 1 if a host batch ran in place on pinned memory (small-batch path), out[2] = tiles recomputed by the
- * resolve stage (read after a synchronisation of the call's stream), out[3..14] = the plan as latok_debug_plan reports it.
+ * resolve stage (read after a synchronisation of the call's stream), out[3..14] = the plan as latok_debug_plan reports it,
+ * out[15] = 1 if the tile kernel held its segments' mask words for one write-out per segment (LaunchPlan::hold).
  * Returns the number of values written, 0 when nothing has run. */
 extern "C" int latok_debug_last_plan(int64_t* out, int n) {
     LATOK_ENTER();
@@ -3664,6 +3695,7 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
     int k = 0;
     for (; k < 3 && k < n; ++k) out[k] = head[k];
     if (n > 3) k += put_plan(g.last.plan, g.last.n_tiles, out + 3, n - 3);
+    if (n > 15 && k == 15) out[k++] = g.last.plan.hold;   // out[15] = the tile kernel held its segments' mask words (latok_debug_set_tile_plan)
     return k;
 }
 

@@ -59,6 +59,12 @@ constexpr bool mode_writes_bits(int mode) { return mode_base(mode) == kModeBits 
 constexpr long long kNegInf64 = -(1ll << 60);
 constexpr int kWPB = 12;                 // waves per workgroup: 768 threads -> 168 VGPRs per lane, one workgroup per CU
 constexpr int kSegMax = kWPB * 64;       // tiles per segment = threads of the block-wide scans
+// k_tiles_main<.., HOLD> (UTF-32 bitmask modes): a segment of at most kSegHoldTiles tiles (kSegHoldRounds tiles per wave) stores its mask
+// words as one contiguous run at its end; the words of a wave's first kSegHoldLdsRounds tiles wait in LDS, the others in its
+// registers (split_kernels.hip: run_segment).  latok_debug_tile_limits reports them.
+constexpr int kSegHoldRounds = 12;
+constexpr int kSegHoldTiles = kSegHoldRounds * kWPB;   // 144
+constexpr int kSegHoldLdsRounds = 4;
 
 struct Fn64 {        // q transfer function of a run of tiles: f(q) = max(q + a, b); a <= kNegInf64 means constant b
     long long a, b;
@@ -189,10 +195,17 @@ struct LaunchPlan {
     int wpb;             // waves per workgroup of the tile kernel
     int nw;              // waves per workgroup of the resolve stage: nw * 64 >= seg_tiles
     int one_launch;      // k_one_segment: the three stages in one launch
+    int hold;            // k_tiles_main<.., HOLD>: a segment's mask words leave as one run (UTF-32 bitmask modes, seg_tiles <= kSegHoldTiles)
+};
+// test hook (latok_debug_set_tile_plan): what plan_launch decides by itself unless told otherwise -- the segment length (0 = the
+// plan's own; a forced length also rules the one-launch path out), the most workgroups (0 = the plan's own) and whether short
+// segments are held (-1 = the plan's own, 0 = never)
+struct PlanForce {
+    int seg_tiles = 0, grid = 0, hold = -1;
 };
 // n_cu: CUs of the device (or the context's test cap); one_launch_ok: the call may take k_one_segment (all three stages,
 // no timing events between them)
-void plan_launch(int64_t n_tiles, int n_cu, bool in_flow, int mode, bool one_launch_ok, LaunchPlan* L);
+void plan_launch(int64_t n_tiles, int n_cu, bool in_flow, int mode, bool one_launch_ok, LaunchPlan* L, const PlanForce* force = nullptr);
 hipError_t launch_tile_index(const SplitParams& P, hipStream_t st);   // stage 0: P.tile_first (must be set)
 hipError_t launch_split_tiles(const SplitParams& P, int mode, const LaunchPlan& L, hipStream_t st);
 hipError_t launch_resolve_fix(const SplitParams& P, int mode, const LaunchPlan& L, hipStream_t st);

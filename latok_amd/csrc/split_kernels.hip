@@ -13,6 +13,14 @@
 
 namespace latok {
 
+// diagnostic build (`make ablate`): k_tiles_main computes every mask word and stores none of them -- the stores hang on a
+// condition that never holds and that the compiler cannot see through.  What the mask stores cost = normal - ablated.
+#ifdef LATOK_ABLATE_MASK_STORES
+#define LATOK_MASK_STORE_GATE && P.total < 0
+#else
+#define LATOK_MASK_STORE_GATE
+#endif
+
 #ifdef LATOK_STAMPS
 __device__ unsigned long long g_stamp_sum[16];
 __device__ unsigned long long g_stamp_cnt;
@@ -165,6 +173,22 @@ static_assert(sizeof(ScanLds) <= 512, "scan scratch");
 static_assert(kSegMax == kWPB * 64, "one tile per thread in the block-wide scans");
 static_assert(kLdsTotal <= 160 * 1024, "LDS budget of one CU");
 static_assert(kLdsSumm % 16 == 0 && kLdsScan % 16 == 0 && kLdsSlice % 16 == 0, "alignment");
+// k_tiles_main<.., HOLD>, the tile kernel of the UTF-32 bitmask modes (no lds_shift there) for plans with short segments: a segment of at most kSegHoldTiles tiles keeps its mask words in the
+// workgroup and stores them as ONE contiguous run at its end (run_segment).  The words of a wave's first kSegHoldLdsRounds tiles go
+// straight to a region of their own behind the map, the rest wait in the wave's registers (obuf) and are dropped, once the segment's
+// last tile is done, over what is dead by then: the staging buffers and the resolve list area, [kLdsWaves, kLdsSumm).
+constexpr bool tile_holds(int mode) { return mode_writes_bits(mode) && !mode_is_bytes(mode); }
+constexpr int kTileMaskBytes = kTile / 8;                                       // 512: a tile's 64 mask words
+constexpr int kSegHoldLdsTiles = kSegHoldLdsRounds * kWPB;                      // 48
+constexpr int kLdsHold = kLdsSlice;                                             // lk_u64[kSegHoldLdsTiles][64]
+constexpr int kSegHoldLdsBytes = kSegHoldLdsTiles * kTileMaskBytes;             // 24 576
+constexpr int lds_total_main(int mode) { return lds_total_tiles(mode) + (tile_holds(mode) ? kSegHoldLdsBytes : 0); }
+static_assert(kSegHoldTiles == kSegHoldRounds * kWPB && kSegHoldRounds - kSegHoldLdsRounds <= 8, "what is not in LDS fits obuf[8]");
+static_assert((kSegHoldTiles - kSegHoldLdsTiles) * kTileMaskBytes <= kLdsSumm - kLdsWaves, "the rest of the run fits the dead regions");
+static_assert(lds_shift(kModeBits) == 0 && lds_shift(kModeRules) == 0 && lds_total_tiles(kModeBits) == kLdsHold && lds_total_tiles(kModeRules) == kLdsHold,
+              "the hold region sits right behind the map");
+static_assert(kLdsWaves % 16 == 0 && kLdsHold % 16 == 0 && lds_total_main(kModeBits) <= 160 * 1024 && lds_total_main(kModeRules) <= 160 * 1024,
+              "16-byte LDS reads of the write-out; LDS budget of one CU");
 
 // byte space: code[256] of a byte taken as a char of its own -- the 128 ASCII codes (stage-2 blocks 0 and 1), 0 from 0x80 on: the
 // lookups of phase 1 then need no masking of the non-ASCII positions (threads 0..15)
@@ -304,7 +328,9 @@ __device__ __forceinline__ TileLds wave_lds(uint8_t* lds, int wave) {
 //   (b) runs the tiles, each publishing its 16-byte summary to LDS and to global memory,
 //   (c) composes the segment's transfer function / head descriptor with a block-wide scan -> one aggregate per segment.
 // ---------------------------------------------------------------------------------------------------------------
-template <int MODE, bool FAST_TAIL = false, int WPB = kWPB, int PF = kCpsPrefetchRows>
+//   (d) HOLD (k_tiles_main<.., HOLD>: UTF-32 bitmask modes, segments of at most kSegHoldTiles tiles): stores the segment's mask words, which
+//       no wave has stored until now, as one run of n_seg x 512 consecutive bytes.
+template <int MODE, bool FAST_TAIL = false, int WPB = kWPB, int PF = kCpsPrefetchRows, bool HOLD = false>
 __device__ __forceinline__ void run_segment(const SplitParams& P, uint8_t* lds, int64_t seg, int tid, int lane,
                                             int wave, bool tables LATOK_STAMP_PARAM) {
     const int S = P.seg_tiles;
@@ -327,7 +353,12 @@ __device__ __forceinline__ void run_segment(const SplitParams& P, uint8_t* lds, 
     // UTF-32 input only: that kernel is HBM bound.  The narrow-input kernels are bound by instruction issue and registers: without
     // the 16 VGPRs of the buffer Latin-1 104 VGPRs (was 121), UCS-2 123 + 64 B scratch (128 + 96), byte space 128 B scratch (192);
     // C3 byte space 0.538 -> 0.506 ms, UCS-2 0.157 -> 0.142, C2 byte space 0.085 -> 0.073, Latin-1 0.069 -> 0.067.
+    // A segment of at most kSegHoldTiles tiles (C2 under both plans) stores nothing here: eight 512-byte pieces 6 KiB apart are
+    // still eight bursts.  Its words wait -- rounds 0 .. kSegHoldLdsRounds - 1 in LDS, the others in obuf -- for step (d).
     constexpr bool kDefer = mode_writes_bits(MODE) && !mode_is_bytes(MODE);
+    static_assert(!HOLD || (kDefer && WPB == kWPB), "held segments: UTF-32 bitmask modes");
+    lk_u64* const hold_lo = reinterpret_cast<lk_u64*>(lds + kLdsHold);     // words of tiles 0 .. kSegHoldLdsTiles - 1 of the segment
+    lk_u64* const hold_hi = reinterpret_cast<lk_u64*>(lds + kLdsWaves);    // ... of the tiles behind them (valid in step (d) only)
     lk_u64 obuf[8];
     int slot = 0, k_first = wave;   // buffered tiles are k_first, k_first + kWPB, ...
     const int64_t n_words = (P.total + 63) >> 6;
@@ -336,16 +367,17 @@ __device__ __forceinline__ void run_segment(const SplitParams& P, uint8_t* lds, 
         for (int j = 0; j < 8; ++j) {
             if (j < slot) {
                 const int64_t w = (T0 + k_first + j * WPB) * 64 + lane;
-                if (w < n_words) P.bits_out[w] = obuf[j];
+                if (w < n_words LATOK_MASK_STORE_GATE) P.bits_out[w] = obuf[j];
             }
         }
         slot = 0;
     };
-    auto put = [&](lk_u64 w, int k) {
-        if (slot == 0) k_first = k;
+    auto put = [&](lk_u64 w, int k, bool keep) {   // keep = false: the word is in LDS already (the selects run all the same: no branch around obuf)
+        if (slot == 0 && keep) k_first = k;
+        const int sel = keep ? slot : -1;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) obuf[j] = (j == slot) ? w : obuf[j];
-        if (++slot == 8) flush();
+        for (int j = 0; j < 8; ++j) obuf[j] = (j == sel) ? w : obuf[j];
+        if (keep && ++slot == 8 && !HOLD) flush();   // (held: at most 8 rounds come here)
     };
     CpsPrefetch pf;
     pf.valid = false;
@@ -353,13 +385,25 @@ __device__ __forceinline__ void run_segment(const SplitParams& P, uint8_t* lds, 
         const lk_u64 w = process_tile<MODE, kDefer, false, FAST_TAIL, PF>(P, L, T0 + k, lane_read64(tfv, j), 0, -1, true, &sm[k], lane LATOK_STAMP_ARG
                                                                       , MODE == kModeBits && !FAST_TAIL ? &pf : nullptr, k + WPB < n_seg ? T0 + k + WPB : (int64_t)-1
                                                                       );
-        if (kDefer) put(w, k);
+        if (kDefer) {
+            const bool to_lds = HOLD && j < kSegHoldLdsRounds;
+            if (to_lds) hold_lo[k * 64 + lane] = w;
+            put(w, k, !to_lds);
+        }
 #ifdef LATOK_STAMPS
         stamp_acc[0] += 1;
 #endif
     }
-    if (kDefer) flush();
+    if (kDefer && !HOLD) flush();
     __syncthreads();
+    // (held segments: every tile is done, so the staging buffers are dead, and this kernel never uses the list area: each wave drops
+    // its registers' words at its tiles' places over them; the summaries behind them are still needed.  The barriers of the scan
+    // below publish the words.)
+    if (HOLD) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (j < slot) hold_hi[(k_first + j * WPB - kSegHoldLdsTiles) * 64 + lane] = obuf[j];
+    }
     // (c) segment aggregate
     {
         Fn64 f = fn_identity();
@@ -374,16 +418,39 @@ __device__ __forceinline__ void run_segment(const SplitParams& P, uint8_t* lds, 
         block_scan<WPB>(f, h, scan, &ef, &eh, &tfn, &th);
         if (tid == 0) { P.seg_fn[seg] = tfn; P.seg_hd[seg] = th; }
     }
-    __syncthreads();
+    // (d) the held mask words: every thread is past the scan's barriers, so all of them are in LDS.  All threads store the run in
+    //     address order, 16 B per lane: 1 KiB per wave instruction, 12 KiB per sweep.
+    if (HOLD) {
+        const int64_t w0 = T0 * 64;                                                  // first word of the run
+        int n_run = (int)min((int64_t)n_seg * 64, n_words - w0);                     // the batch ends inside its last tile
+#ifdef LATOK_ABLATE_MASK_STORES
+        if (P.total >= 0) n_run = 0;
+#endif
+        uint64_t* const dst = P.bits_out + w0;
+        auto held = [&](int w) -> const lk_u64* {
+            return w < kSegHoldLdsTiles * 64 ? hold_lo + w : hold_hi + (w - kSegHoldLdsTiles * 64);
+        };
+        if ((reinterpret_cast<uintptr_t>(P.bits_out) & 15u) == 0) {                  // (w0 is even: the pairs are 16-byte aligned)
+            for (int w = 2 * tid; w < n_run; w += 2 * WPB * 64) {
+                if (w + 1 < n_run) *reinterpret_cast<uint4*>(dst + w) = *reinterpret_cast<const uint4*>(held(w));
+                else dst[w] = *held(w);                                              // the batch's last word, alone
+            }
+        } else {                                                                     // a mask that is only 8-byte aligned
+            for (int w = tid; w < n_run; w += WPB * 64) dst[w] = *held(w);
+        }
+    }
+    __syncthreads();   // (the LDS is the next segment's)
 }
 
 // FAST_TAIL: the batch's last, partial tile requests all its rows before the first lookup (process_tile).  Chosen for small
 // batches, where that tile's latency is a visible share of the call (a 4-tile batch in pinned host memory: 31 -> 16 us);
 // the large-batch instantiation keeps the serial tail: the unified form costs its full-tile loop 16 VGPRs and 4 % on C2.
-template <int MODE, bool FAST_TAIL = false, int PF = kCpsPrefetchRows>
+// HOLD: the same with held segments (UTF-32 bitmask modes, plans whose segments have at most kSegHoldTiles tiles: LaunchPlan::hold)
+template <int MODE, bool FAST_TAIL = false, int PF = kCpsPrefetchRows, bool HOLD = false>
 __global__ __launch_bounds__(tile_wpb(MODE) * 64) void k_tiles_main(SplitParams P) {
     constexpr int WPB = tile_wpb(MODE);
-    __shared__ __attribute__((aligned(16))) uint8_t lds[lds_total_tiles(MODE)];
+    static_assert(!HOLD || tile_holds(MODE), "UTF-32 bitmask modes");
+    __shared__ __attribute__((aligned(16))) uint8_t lds[HOLD ? lds_total_main(MODE) : lds_total_tiles(MODE)];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform -> scalar tile arithmetic
@@ -400,7 +467,7 @@ __global__ __launch_bounds__(tile_wpb(MODE) * 64) void k_tiles_main(SplitParams 
     for (int i = 0; i < 16; ++i) stamp_acc[i] = 0;
 #endif
     for (int64_t seg = blockIdx.x; seg < P.n_segs; seg += gridDim.x) {
-        run_segment<MODE, FAST_TAIL, WPB, PF>(P, lds, seg, tid, lane, wave, tables LATOK_STAMP_ARG);
+        run_segment<MODE, FAST_TAIL, WPB, PF, HOLD>(P, lds, seg, tid, lane, wave, tables LATOK_STAMP_ARG);
         tables = false;
     }
 #ifdef LATOK_STAMPS
@@ -910,7 +977,7 @@ void plan_segments(int64_t n_tiles, int n_cu, int* seg_tiles, int64_t* n_segs) {
     *n_segs = (n_tiles + s - 1) / s;
 }
 
-void plan_launch(int64_t n_tiles, int n_cu, bool in_flow, int mode, bool one_launch_ok, LaunchPlan* L) {
+void plan_launch(int64_t n_tiles, int n_cu, bool in_flow, int mode, bool one_launch_ok, LaunchPlan* L, const PlanForce* force) {
     const int wpb = tile_wpb(mode);
     // A batch of a FLOW leaves part of the chip to the other batch in flight: its persistent tile kernel is planned for 7/8 of
     // the CUs (4 free per XCD on MI355X), so the first workgroups of the NEXT batch's tile kernel start on the free CUs while
@@ -938,6 +1005,12 @@ void plan_launch(int64_t n_tiles, int n_cu, bool in_flow, int mode, bool one_lau
     if (n_cu_eff < 8) n_cu_eff = n_cu < 8 ? n_cu : 8;
     L->n_cu_eff = n_cu_eff;
     plan_segments(n_tiles, n_cu_eff, &L->seg_tiles, &L->n_segs);
+    if (force && force->seg_tiles > 0) {
+        const int s = force->seg_tiles < kWPB ? kWPB : (force->seg_tiles > kSegMax ? kSegMax : force->seg_tiles);
+        L->seg_tiles = s;
+        L->n_segs = (n_tiles + s - 1) / s;
+        one_launch_ok = false;
+    }
     // a small UTF-32 batch: one segment, and one launch for the three stages
     L->one_launch = one_launch_ok && n_tiles <= kOneSegTiles && (mode == kModeBits || mode == kModeRules);
     if (L->one_launch) {
@@ -946,10 +1019,12 @@ void plan_launch(int64_t n_tiles, int n_cu, bool in_flow, int mode, bool one_lau
     }
     // (the plan may leave CUs free; the grid never exceeds the chip)
     L->grid = L->one_launch ? 1 : (int)(L->n_segs < n_cu ? (L->n_segs < 1 ? 1 : L->n_segs) : n_cu);
+    if (force && force->grid > 0 && force->grid < L->grid) L->grid = force->grid;
     L->rounds = (L->n_segs + L->grid - 1) / L->grid;
     L->fast_tail = !L->one_launch && n_tiles <= kFastTailTiles && (mode == kModeBits || mode == kModeRules);
     L->pf = mode == kModeBits && in_flow && !L->fast_tail && !L->one_launch ? kCpsPrefetchRowsFlow : kCpsPrefetchRows;
     L->wpb = L->one_launch ? kWPB : wpb;
+    L->hold = !L->one_launch && tile_holds(mode) && L->seg_tiles <= kSegHoldTiles && !(force && force->hold == 0);
     // The bitmask modes repair almost everything in place, so their resolve stage is pure latency and runs with as few
     // waves as cover a segment; the modes that recompute tiles keep all 12 waves for that.
     const bool narrow_resolve = mode == kModeBits || mode == kModeBytes || mode == kModeLatin1 || mode == kModeUcs2;
@@ -958,6 +1033,15 @@ void plan_launch(int64_t n_tiles, int n_cu, bool in_flow, int mode, bool one_lau
 
 hipError_t launch_split_tiles(const SplitParams& P, int mode, const LaunchPlan& L, hipStream_t st) {
     const dim3 grid(L.grid), block(kWPB * 64);
+    if (L.hold) {
+        if (!tile_holds(mode) || P.seg_tiles > kSegHoldTiles) return hipErrorInvalidValue;
+        if (mode == kModeBits && L.pf == kCpsPrefetchRowsFlow) hipLaunchKernelGGL((k_tiles_main<kModeBits, false, kCpsPrefetchRowsFlow, true>), grid, block, 0, st, P);
+        else if (mode == kModeBits && L.fast_tail) hipLaunchKernelGGL((k_tiles_main<kModeBits, true, kCpsPrefetchRows, true>), grid, block, 0, st, P);
+        else if (mode == kModeRules && L.fast_tail) hipLaunchKernelGGL((k_tiles_main<kModeRules, true, kCpsPrefetchRows, true>), grid, block, 0, st, P);
+        else if (mode == kModeBits) hipLaunchKernelGGL((k_tiles_main<kModeBits, false, kCpsPrefetchRows, true>), grid, block, 0, st, P);
+        else hipLaunchKernelGGL((k_tiles_main<kModeRules, false, kCpsPrefetchRows, true>), grid, block, 0, st, P);
+        return hipGetLastError();
+    }
     if (mode == kModeBits && L.pf == kCpsPrefetchRowsFlow) hipLaunchKernelGGL((k_tiles_main<kModeBits, false, kCpsPrefetchRowsFlow>), grid, block, 0, st, P);
     else if (mode == kModeBits && L.fast_tail) hipLaunchKernelGGL((k_tiles_main<kModeBits, true>), grid, block, 0, st, P);
     else if (mode == kModeRules && L.fast_tail) hipLaunchKernelGGL((k_tiles_main<kModeRules, true>), grid, block, 0, st, P);
