@@ -325,6 +325,36 @@ int latok_hashed_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t
                                               int32_t* indices_out, int32_t* data_out, int64_t cap, int64_t* nnz_out,
                                               int64_t* n_tokens_out /* may be NULL */, int flags, void* stream);
 
+/* Word n-grams in the term counts: the same CSR rows with one term per GRAM -- what CountVectorizer(vocabulary=...,
+ * ngram_range=(min_n, max_n)) and HashingVectorizer(norm=None, ngram_range=(min_n, max_n)) return; scikit-learn's _word_ngrams
+ * feeds exactly these strings to its vocabulary or hasher.  For string s the tokens t_0 .. t_(c-1) are the byte slices
+ * latok_token_spans_utf8_bytes_batch reports; run-time rule tables and malformed bytes are taken as that call takes them.  The GRAMS
+ * of s, for 1 <= min_n <= max_n <= 8 and a one-byte separator sep (0 .. 255; scikit-learn joins with 0x20), are
+ *   g(n, i) = t_i + sep + t_(i+1) + sep + ... + t_(i+n-1)     for every n in [min_n, max_n] and every i in 0 .. c - n
+ * -- a string with fewer than n tokens has no gram of order n; a string of c tokens has sum over n of max(0, c - n + 1) grams.
+ * Every gram gets a key and a value by exactly the rules of the term-counts comment above, applied to the BYTES OF THE GRAM:
+ *   vocabulary form   the gram is looked up byte for byte in the latok_vocab; a vocabulary word may contain the separator
+ *                     ("new york").  A found gram contributes its id with value 1; a gram that is not found adds 1 to oov[s].
+ *   hashed form       h = MurmurHash3 x86_32 of the gram's bytes with `seed`; column = |h| mod n_features in 64 bits; the sign follows
+ *                     alternate_sign; the gram's byte length enters the hash as 32 bits.
+ * Row s is the set of distinct keys ascending as signed int32, each with the sum of its values, in the CSR layout above.  With min_n
+ * = max_n = 1 the result equals latok_term_counts_utf8_bytes_batch / latok_hashed_term_counts_utf8_bytes_batch entry for entry.
+ * Everything else carries over from those calls unchanged: flags, host pointers or LATOK_DEVICE_PTRS, total_bytes = -1, the check
+ * of the vocabulary's device, the capacity protocol in ENTRIES, the size query, the empty batch.  min_n < 1, max_n < min_n, max_n >
+ * 8 and sep outside 0 .. 255 are refused with LATOK_ERR_INVALID before any device work, with nothing written.  A batch whose token
+ * total, or whose gram total K, is 2^31 or more is refused with nothing written to indices or data.  *n_grams_out (may be NULL) = K.
+ * The calls are blocking and wait for their kernels THREE times -- for the token total, which sizes the token records; for K,
+ * which sizes the key buffers; for nnz -- and a fourth time for the copy of the entries when the outputs are host pointers.  A
+ * gram is hashed by one lane: a batch of very long tokens runs at the speed of its longest.  There is no flow form. */
+int latok_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                        const latok_vocab* vocab, int min_n, int max_n, int sep, int64_t* indptr_out /* [n_str+1] */,
+                                        int64_t* oov_out /* [n_str], may be NULL */, int32_t* indices_out, int32_t* data_out, int64_t cap,
+                                        int64_t* nnz_out, int64_t* n_grams_out /* may be NULL */, int flags, void* stream);
+int latok_hashed_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                               uint32_t seed, int64_t n_features, int alternate_sign, int min_n, int max_n, int sep,
+                                               int64_t* indptr_out /* [n_str+1] */, int32_t* indices_out, int32_t* data_out, int64_t cap,
+                                               int64_t* nnz_out, int64_t* n_grams_out /* may be NULL */, int flags, void* stream);
+
 /* WordPiece in byte space: the subword ids a BERT-family model takes, for every token of a batch.
  * A WORDPIECE VOCABULARY is an ordered list of byte strings w_0 .. w_(V-1) with optional int32 ids (word_ids = NULL means id_i = i),
  * a continuation prefix P of 0 .. 8 bytes ("##" in BERT's files; an empty P is legal: every word is then also a continuation word),

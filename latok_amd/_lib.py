@@ -59,6 +59,9 @@ SIGNATURES = {
     "latok_term_counts_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
     "latok_hashed_term_counts_utf8_bytes_batch": (ci, [vp, vp, i64, i64, C.c_uint32, i64, ci, vp, vp, vp, i64, C.POINTER(i64),
                                                        C.POINTER(i64), ci, vp]),
+    "latok_ngram_counts_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, ci, ci, ci, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
+    "latok_hashed_ngram_counts_utf8_bytes_batch": (ci, [vp, vp, i64, i64, C.c_uint32, i64, ci, ci, ci, ci, vp, vp, vp, i64, C.POINTER(i64),
+                                                        C.POINTER(i64), ci, vp]),
     "latok_wordpiece_create": (ci, [vp, vp, i64, vp, vp, ci, ci, C.c_uint32, C.POINTER(vp)]),
     "latok_wordpiece_destroy": (ci, [vp]),
     "latok_wordpiece_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, C.POINTER(ci),

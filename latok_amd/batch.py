@@ -775,7 +775,37 @@ def _n_features31(n_features) -> int:
     raise ValueError("n_features must be an int in 1 .. 2**31 - 1")
 
 
-def _terms_csr_folded(utf8, byte_off, vocab, hashed, fold):
+NGRAM_MAX = 8   # kNgMax of the library: the highest order of a word n-gram
+
+
+def _ngram_spec(ngram_range, sep):
+    """(min_n, max_n, sep byte) of a call that counts word n-grams, None for ngram_range (1, 1): the plain term counts.  Anything but
+    two ints 1 <= min_n <= max_n <= NGRAM_MAX and a one-byte separator is a ValueError (raised before any device is asked for)."""
+    sep = _sep_byte(sep)
+    ok = isinstance(ngram_range, (tuple, list)) and len(ngram_range) == 2 and all(
+        isinstance(n, (int, np.integer)) and not isinstance(n, bool) for n in ngram_range)
+    if not ok or not 1 <= int(ngram_range[0]) <= int(ngram_range[1]) <= NGRAM_MAX:
+        raise ValueError("ngram_range must be (min_n, max_n) with 1 <= min_n <= max_n <= %d" % NGRAM_MAX)
+    min_n, max_n = int(ngram_range[0]), int(ngram_range[1])
+    return None if (min_n, max_n) == (1, 1) else (min_n, max_n, sep)
+
+
+def _terms_call(lib, ng, hashed, u8, off, n_str, total, vocab, indptr, oov, indices, data, cap, nnz, flags):
+    """one call of the term counts: the n-gram entry points when ``ng`` is set, else the existing ones exactly as they were"""
+    if hashed:
+        seed, n_features, alternate_sign = hashed
+        if ng:
+            return lib.latok_hashed_ngram_counts_utf8_bytes_batch(u8, off, n_str, total, seed, n_features, 1 if alternate_sign else 0, ng[0], ng[1],
+                                                                  ng[2], indptr, indices, data, cap, C.byref(nnz), None, flags, None)
+        return lib.latok_hashed_term_counts_utf8_bytes_batch(u8, off, n_str, total, seed, n_features, 1 if alternate_sign else 0, indptr, indices,
+                                                             data, cap, C.byref(nnz), None, flags, None)
+    if ng:
+        return lib.latok_ngram_counts_utf8_bytes_batch(u8, off, n_str, total, vocab, ng[0], ng[1], ng[2], indptr, oov, indices, data, cap,
+                                                       C.byref(nnz), None, flags, None)
+    return lib.latok_term_counts_utf8_bytes_batch(u8, off, n_str, total, vocab, indptr, oov, indices, data, cap, C.byref(nnz), None, flags, None)
+
+
+def _terms_csr_folded(utf8, byte_off, vocab, hashed, fold, ng=None):
     """_terms_csr (int64) of the batch folded on the device: the size query, then the fill, on device buffers"""
     with _DeviceFolded(utf8, byte_off, fold) as d:
         lib, n_str = d.lib, d.n_str
@@ -784,12 +814,7 @@ def _terms_csr_folded(utf8, byte_off, vocab, hashed, fold):
         nnz = C.c_int64(0)
 
         def call(indices, data, cap):
-            if hashed:
-                seed, n_features, alternate_sign = hashed
-                return lib.latok_hashed_term_counts_utf8_bytes_batch(d.u8, d.off, n_str, d.total, seed, n_features, 1 if alternate_sign else 0,
-                                                                     indptr, indices, data, cap, C.byref(nnz), None, _lib.DEVICE_PTRS, None)
-            return lib.latok_term_counts_utf8_bytes_batch(d.u8, d.off, n_str, d.total, vocab, indptr, oov, indices, data, cap, C.byref(nnz), None,
-                                                          _lib.DEVICE_PTRS, None)
+            return _terms_call(lib, ng, hashed, d.u8, d.off, n_str, d.total, vocab, indptr, oov, indices, data, cap, nnz, _lib.DEVICE_PTRS)
 
         rc = call(None, None, 0)
         if rc != _lib.OK and not (rc == _lib.ERR_INVALID and nnz.value > 0):
@@ -802,7 +827,7 @@ def _terms_csr_folded(utf8, byte_off, vocab, hashed, fold):
                 d.fetch(data, need, np.int32) if need else np.empty(0, np.int32), None if hashed else d.fetch(oov, n_str, np.int64))
 
 
-def _terms_csr(utf8, byte_off, vocab, hashed, dtype):
+def _terms_csr(utf8, byte_off, vocab, hashed, dtype, ng=None):
     """the size query, then the fill -> (indptr, indices, data, oov or None)"""
     utf8, byte_off = _csr_u8(utf8, byte_off)
     dt, flags = _out_dtype(dtype)
@@ -814,13 +839,8 @@ def _terms_csr(utf8, byte_off, vocab, hashed, dtype):
     nnz = C.c_int64(0)
 
     def call(indices, data, cap):
-        if hashed:
-            seed, n_features, alternate_sign = hashed
-            return lib.latok_hashed_term_counts_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, seed, n_features,
-                                                                 1 if alternate_sign else 0, _ptr(indptr), indices, data, cap,
-                                                                 C.byref(nnz), None, flags, None)
-        return lib.latok_term_counts_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, vocab, _ptr(indptr), _ptr(oov), indices, data,
-                                                      cap, C.byref(nnz), None, flags, None)
+        return _terms_call(lib, ng, hashed, _ptr(utf8), _ptr(byte_off), n_str, total, vocab, _ptr(indptr), None if hashed else _ptr(oov), indices,
+                           data, cap, nnz, flags)
 
     rc = call(None, None, 0)
     if rc != _lib.OK and not (rc == _lib.ERR_INVALID and nnz.value > 0):
@@ -831,54 +851,65 @@ def _terms_csr(utf8, byte_off, vocab, hashed, dtype):
     return indptr, indices, data, oov
 
 
-def term_counts_utf8_csr(utf8, byte_off, vocab, dtype=np.int64):
+def term_counts_utf8_csr(utf8, byte_off, vocab, dtype=np.int64, ngram_range=(1, 1), sep=b" "):
     """(indptr[n + 1], indices int32[nnz], data int32[nnz], oov[n]): the term counts of every string against ``vocab`` as a
     canonical CSR matrix -- row s holds the distinct vocabulary ids of its tokens (the byte slices token_spans_utf8_bytes_csr
     reports), ascending, each with its count; ``oov[s]`` counts the tokens the vocabulary does not hold.  What
     ``CountVectorizer(vocabulary=...).transform`` returns: ``scipy.sparse.csr_matrix((data, indices, indptr), shape=(n, n_cols))``.
-    indptr and oov in ``dtype``.  Cut, looked up, sorted and reduced on the device (``latok_term_counts_utf8_bytes_batch``)."""
-    return _terms_csr(utf8, byte_off, _vocab_handle(vocab), None, dtype)
+    indptr and oov in ``dtype``.  Cut, looked up, sorted and reduced on the device (``latok_term_counts_utf8_bytes_batch``).  ``ngram_range=(min_n, max_n)`` (up to
+    (8, 8)) counts word n-grams instead: every run of n neighbouring tokens of a string joined by the one-byte ``sep``, for every n
+    in the range, looked up or hashed as one term -- scikit-learn's ``ngram_range`` (``latok_ngram_counts_utf8_bytes_batch`` /
+    ``latok_hashed_ngram_counts_utf8_bytes_batch``); (1, 1) takes the plain calls.
+    A vocabulary word may hold the separator (``b"new york"``)."""
+    return _terms_csr(utf8, byte_off, _vocab_handle(vocab), None, dtype, _ngram_spec(ngram_range, sep))
 
 
-def term_counts_utf8_batch(blobs, vocab, fold=0):
+def term_counts_utf8_batch(blobs, vocab, fold=0, ngram_range=(1, 1), sep=b" "):
     """list[bytes] (UTF-8) -> (indptr, indices, data, oov) of term_counts_utf8_csr, int64 ('' and whitespace-only -> empty rows).
     ``fold`` (FOLD_* flags): the batch is folded on the device first (fold_utf8_batch) -- ``CountVectorizer(lowercase=True)`` is
-    ``FOLD_LOWER``, ``strip_accents="unicode"`` adds ``FOLD_STRIP_MARKS``."""
-    handle, fold = _vocab_handle(vocab), _fold_bits(fold)
+    ``FOLD_LOWER``, ``strip_accents="unicode"`` adds ``FOLD_STRIP_MARKS``.  ``ngram_range``, ``sep``: as in term_counts_utf8_csr; the
+    grams are those of the folded strings."""
+    handle, fold, ng = _vocab_handle(vocab), _fold_bits(fold), _ngram_spec(ngram_range, sep)
     utf8, byte_off = pack_utf8(blobs)
     if fold:
-        return _terms_csr_folded(utf8, byte_off, handle, None, fold)
-    return _terms_csr(utf8, byte_off, handle, None, np.int64)
+        return _terms_csr_folded(utf8, byte_off, handle, None, fold, ng)
+    return _terms_csr(utf8, byte_off, handle, None, np.int64, ng)
 
 
-def term_counts_batch(texts, vocab):
+def term_counts_batch(texts, vocab, ngram_range=(1, 1), sep=b" "):
     """list[str] -> (indptr, indices, data, oov): per string ``Counter(d[t] for t in tokenize(text) if t in d)`` with sorted keys,
-    d = the vocabulary as a dict; oov = the tokens not in d.  The strings go through UTF-8 ("surrogatepass") on the host."""
-    return term_counts_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], vocab)
+    d = the vocabulary as a dict; oov = the tokens not in d.  The strings go through UTF-8 ("surrogatepass") on the host.
+    ``ngram_range``, ``sep``: as in term_counts_utf8_csr."""
+    return term_counts_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], vocab, ngram_range=ngram_range, sep=sep)
 
 
-def hashed_term_counts_utf8_csr(utf8, byte_off, n_features=1 << 20, seed=0, alternate_sign=True, dtype=np.int64):
+def hashed_term_counts_utf8_csr(utf8, byte_off, n_features=1 << 20, seed=0, alternate_sign=True, dtype=np.int64, ngram_range=(1, 1), sep=b" "):
     """(indptr[n + 1], indices int32[nnz], data int32[nnz]): the hashed term counts of every string as a canonical CSR matrix --
     column = ``abs(h) % n_features``, value = ``+1`` or (``alternate_sign`` and h < 0) ``-1``, h = MurmurHash3 x86_32 of the token's
     bytes with ``seed`` as int32; a row's columns ascend and a sum may be an explicit 0.  What ``HashingVectorizer(norm=None)
     .transform`` returns: ``scipy.sparse.csr_matrix((data, indices, indptr), shape=(n, n_features))``.  indptr in ``dtype``.  Cut,
-    hashed, sorted and reduced on the device (``latok_hashed_term_counts_utf8_bytes_batch``)."""
-    return _terms_csr(utf8, byte_off, None, (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), dtype)[:3]
+    hashed, sorted and reduced on the device (``latok_hashed_term_counts_utf8_bytes_batch``).  ``ngram_range=(min_n, max_n)`` (up to
+    (8, 8)) counts word n-grams instead: every run of n neighbouring tokens of a string joined by the one-byte ``sep``, for every n
+    in the range, looked up or hashed as one term -- scikit-learn's ``ngram_range`` (``latok_ngram_counts_utf8_bytes_batch`` /
+    ``latok_hashed_ngram_counts_utf8_bytes_batch``); (1, 1) takes the plain calls."""
+    return _terms_csr(utf8, byte_off, None, (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), dtype, _ngram_spec(ngram_range, sep))[:3]
 
 
-def hashed_term_counts_utf8_batch(blobs, n_features=1 << 20, seed=0, alternate_sign=True, fold=0):
+def hashed_term_counts_utf8_batch(blobs, n_features=1 << 20, seed=0, alternate_sign=True, fold=0, ngram_range=(1, 1), sep=b" "):
     """list[bytes] (UTF-8) -> (indptr, indices, data) of hashed_term_counts_utf8_csr, int64.  ``fold`` (FOLD_* flags): the batch is
-    folded on the device first (fold_utf8_batch); ``HashingVectorizer`` lower-cases by default: ``FOLD_LOWER``."""
-    hashed, fold = (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), _fold_bits(fold)
+    folded on the device first (fold_utf8_batch); ``HashingVectorizer`` lower-cases by default: ``FOLD_LOWER``.  ``ngram_range``, ``sep``:
+    as in hashed_term_counts_utf8_csr; the grams are those of the folded strings."""
+    hashed, fold, ng = (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), _fold_bits(fold), _ngram_spec(ngram_range, sep)
     utf8, byte_off = pack_utf8(blobs)
     if fold:
-        return _terms_csr_folded(utf8, byte_off, None, hashed, fold)[:3]
-    return _terms_csr(utf8, byte_off, None, hashed, np.int64)[:3]
+        return _terms_csr_folded(utf8, byte_off, None, hashed, fold, ng)[:3]
+    return _terms_csr(utf8, byte_off, None, hashed, np.int64, ng)[:3]
 
 
-def hashed_term_counts_batch(texts, n_features=1 << 20, seed=0, alternate_sign=True):
+def hashed_term_counts_batch(texts, n_features=1 << 20, seed=0, alternate_sign=True, ngram_range=(1, 1), sep=b" "):
     """list[str] -> (indptr, indices, data): hashed_term_counts_utf8_batch of the strings' UTF-8 ("surrogatepass")."""
-    return hashed_term_counts_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], n_features, seed, alternate_sign)
+    return hashed_term_counts_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], n_features, seed, alternate_sign, ngram_range=ngram_range,
+                                         sep=sep)
 
 
 # WordPiece: every token cut greedily into the longest vocabulary prefix and ##-continuations, on the device -- the subword ids a

@@ -32,6 +32,7 @@
 #include "kernels.h"
 #include "unicode_tables.inc"
 #include "vocab_table.h"
+#include "ngram_text.h"
 #include "count_table.h"
 #include "wordpiece.h"
 #include "fold_map.h"
@@ -185,6 +186,7 @@ struct Workspace {
     DevBuf jbody, jhead;   // joined token text: the body / head planes over the bytes (k_join_counts)
     DevBuf tkeys, tkeys2, trows;   // term counts: one key per token, the long rows' second buffer, five int64 arrays over the rows
     DevBuf wpspans, wpcnt, wprank, wpids;   // WordPiece: per token its span record, piece count and piece rank; the padded form's ids
+    DevBuf ngrows;   // word n-grams: gram counts and row starts in key space (the span records share wpspans, the keys tkeys / tkeys2)
     // the single-pass scan of k_word_counts_scan keeps its look-back state (chain: per workgroup, chain_ctl: {ticket
     // counter}) between launches: entries carry an epoch, so the array is cleared only when it is (re)allocated or when the
     // 18-bit epoch wraps (next_scan_epoch); *_seen = DevBuf::gen of the allocations it was last cleared in
@@ -193,7 +195,7 @@ struct Workspace {
     void release() {
         for (DevBuf* b : {&summ, &seg_agg, &fix_count, &tile_first, &bits, &space, &kept, &wcnt, &wpref, &bases, &scalar, &chain,
                           &chain_ctl, &codes, &widened, &lead, &bspace, &cpbits, &cpspace, &cprow, &jbody, &jhead, &tkeys,
-                          &tkeys2, &trows, &wpspans, &wpcnt, &wprank, &wpids})
+                          &tkeys2, &trows, &wpspans, &wpcnt, &wprank, &wpids, &ngrows})
             b->release();
         scan_epoch = chain_seen = chain_ctl_seen = 0;
         chain_ready = false;
@@ -204,7 +206,7 @@ struct WsNeed {
     size_t bytes;   // 0: the batch does not use the buffer
 };
 constexpr int kTileNeeds = 4;   // the first entries of ws_needs: the tile stage
-constexpr int kWsNeeds = 29;
+constexpr int kWsNeeds = 30;
 // What a batch asks of its workspace beyond the tile stage.  token spans (spans) add the SPACE and kept planes, featurize (feats)
 // the code bytes, and narrow units read by featurize (widen) a UTF-32 copy.  cp_rows > 0: the units are UTF-8 bytes whose results
 // are reported in code points (cp_rows = n_str + 1): every buffer is sized by the byte count, which bounds the code-point count.
@@ -213,12 +215,16 @@ constexpr int kWsNeeds = 29;
 // waits for before it sizes the two key buffers.  wp_tokens: the token total again, for the WordPiece calls (which use the first two
 // row arrays of term_rows): 16 bytes of span record, 8 of piece count and 8 of piece rank per token, one entry more in the last two,
 // and a scan state for that many entries; wp_pieces: the piece total, which the padded form waits for before it sizes its ids.
+// Word n-grams (which use the row arrays of term_rows as well): ng_tokens, the token total: 16 bytes of span record per token, in the
+// buffer the WordPiece calls keep theirs in; ng_rows > 0 (= n_str + 1): the gram counts and the row starts in key space; ng_keys:
+// the key total, which the n-gram call waits for before it sizes the two key buffers -- the term counts' own, one key per gram.
 constexpr int kTermRowArrays = 5;   // token counts, row starts, distinct counts, indptr, OOV counts
 struct WsShape {
     bool spans = false, feats = false, widen = false, join = false;
     int64_t cp_rows = 0;
     int64_t term_rows = 0, term_tokens = 0;
     int64_t wp_tokens = 0, wp_pieces = 0;
+    int64_t ng_tokens = 0, ng_rows = 0, ng_keys = 0;
 };
 // The one sizing rule of a workspace: every buffer a batch of `units` positions uses and its byte size.
 static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const WsShape& shape) {
@@ -251,10 +257,11 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const 
              {&w.cprow, cp_rows > 0 ? (size_t)cp_rows * 8 : 0},
              {&w.jbody, join ? words * 8 + 8 : 0},
              {&w.jhead, join ? words * 8 + 8 : 0},
-             {&w.tkeys, shape.term_tokens > 0 ? (size_t)shape.term_tokens * 8 : 0},
-             {&w.tkeys2, shape.term_tokens > 0 ? (size_t)shape.term_tokens * 8 : 0},
+             {&w.tkeys, (size_t)std::max<int64_t>({shape.term_tokens, shape.ng_keys, 0}) * 8},
+             {&w.tkeys2, (size_t)std::max<int64_t>({shape.term_tokens, shape.ng_keys, 0}) * 8},
              {&w.trows, shape.term_rows > 0 ? (size_t)shape.term_rows * 8 * kTermRowArrays : 0},
-             {&w.wpspans, shape.wp_tokens > 0 ? (size_t)shape.wp_tokens * 16 : 0},
+             {&w.wpspans, (size_t)std::max<int64_t>({shape.wp_tokens, shape.ng_tokens, 0}) * 16},
+             {&w.ngrows, shape.ng_rows > 0 ? (size_t)shape.ng_rows * 8 * 2 : 0},
              {&w.wpcnt, shape.wp_tokens > 0 ? (size_t)(shape.wp_tokens + 1) * 8 : 0},
              {&w.wprank, shape.wp_tokens > 0 ? (size_t)(shape.wp_tokens + 1) * 8 : 0},
              {&w.wpids, shape.wp_pieces > 0 ? (size_t)shape.wp_pieces * 4 : 0}}};
@@ -658,6 +665,7 @@ struct BytesCall {
     }
 };
 constexpr unsigned kClearPair = 0x3, kClearSized = 0xB, kClearBytesFeats = 0x1B;   // pinned words {0, 1}, {0, 1, 3}, {0, 1, 3, 4}
+constexpr unsigned kClearNgrams = 0x2B;                                               // {0, 1, 3, 5}
 
 // The end of a call whose payload has a size known only now (`n` items, read behind wait_totals): more than the caller's capacity
 // is refused with `need_fmt`; host pointers then get `n` items of every array (a NULL dst was not asked for) and a last wait.
@@ -2448,6 +2456,8 @@ struct TermCounts {
     int64_t* p_tot = nullptr;      // the pinned words as the device sees them (cleared by the caller): 0 tokens, 1 flags, 3 nnz
     volatile int64_t* h_tot = nullptr;
     int64_t n_tokens = 0;          // (out) the token total
+    int min_n = 1, max_n = 1, sep = 0x20;   // word n-grams (enqueue_ngram_counts): the orders and the separator byte; pinned word 5 = K
+    int64_t n_grams = 0;           // (out) the key total K of the n-gram calls
     hipStream_t st = nullptr;
 };
 static int enqueue_term_counts(Ctx& g, Workspace& w, TermCounts& a) {
@@ -2493,18 +2503,106 @@ static int enqueue_term_counts(Ctx& g, Workspace& w, TermCounts& a) {
     return LATOK_OK;
 }
 
-// the two blocking entry points' shared body: the checks of the ids call, the capacity protocol in entries
+/* Word n-grams of the term counts (latok_ngram_counts_utf8_bytes_batch, latok_hashed_ngram_counts_utf8_bytes_batch): one key per gram
+ * instead of one per token, then the term counts' own sort and reduce with the row starts in KEY space.  One stream:
+ *   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
+ *   k_word_counts + k_scan_chained                kept mask, token ranks; THE token total -> scalar word 0, pinned word 0
+ *   (wait 1)                                      the host reads the token total: 2^31 or more is refused, the span records are sized
+ *   k_counts_scatter (KIND 1, int64)              the span record of every token at its rank in the workspace, token count per string
+ *   k_scan_chained                                the row starts in token space
+ *   k_ngram_rows + k_scan_chained                 grams per string, the row starts in key space; the key total K -> pinned word 5
+ *   (wait 2)                                      the host reads K: 2^31 or more is refused, the two key buffers are sized
+ *   k_ngram_keys                                  one term key per gram inside its row's range of keys
+ *   k_terms_tile, k_terms_long ... k_terms_emit   as enqueue_term_counts, with the key rows and K in the place of the token rows
+ *   (wait 3)                                      nnz; host pointers then copy nnz entries (wait 4)
+ * `w` was sized by ws_needs with WsShape{.spans = true, .term_rows = n_str + 1, .ng_rows = n_str + 1}; the call sizes the rest. */
+static int enqueue_ngram_counts(Ctx& g, Workspace& w, TermCounts& a) {
+    int rc;
+    const hipStream_t st = a.st;
+    const int64_t total = a.b.total, n_str = a.b.n_str;
+    int* d_err = (int*)(a.p_tot + 1);
+    unsigned epoch = 0;
+    TokenPlanes t;
+    if ((rc = enqueue_token_front(g, w, a.b, a.p_tot, d_err, st, &t))) return rc;
+    int64_t* d_total = t.total;
+    HIP_TRY(hipStreamSynchronize(st));   // wait 1: the token total decides whether the call goes on and what the records take
+    if ((rc = finish_totals(w, a.h_tot, 0, &a.n_tokens))) return rc;
+    const int64_t n_tok = a.n_tokens;
+    if (n_tok >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld tokens: term counts are int32 (fewer than 2^31 tokens a call)", (long long)n_tok);
+    WsShape shape{.spans = true, .term_rows = n_str + 1};
+    shape.ng_rows = n_str + 1;
+    shape.ng_tokens = n_tok;
+    if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, shape).data(), kWsNeeds))) return rc;
+    int64_t* rows = (int64_t*)w.trows.p;
+    int64_t* d_cnt = rows;                       // token space: counts, row starts
+    int64_t* d_start = rows + (n_str + 1);
+    int64_t* d_distinct = rows + 2 * (n_str + 1);
+    int64_t* d_indptr = rows + 3 * (n_str + 1);
+    int64_t* d_oov = rows + 4 * (n_str + 1);
+    int64_t* d_kcnt = (int64_t*)w.ngrows.p;      // key space: counts, row starts
+    int64_t* d_kstart = d_kcnt + (n_str + 1);
+    HIP_TRY(hipMemsetAsync(rows, 0, (size_t)(n_str + 1) * 8 * kTermRowArrays, st));   // (no gram: every row is empty, nnz = 0)
+    if (n_tok > 0) {
+        int64_t* d_tspans = (int64_t*)w.wpspans.p;
+        HIP_TRY(latok::launch_counts_scatter(1, false, t.bits, t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, total, a.b.row, n_str, t.tile_first,
+                                             d_tspans, d_total, n_tok, d_cnt, d_err, st));
+        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+        HIP_TRY(latok::launch_tile_scan(d_cnt, n_str + 1, d_start, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 4,
+                                        nullptr, d_err + 1, st));
+        HIP_TRY(latok::launch_ngram_rows(d_cnt, n_str, a.min_n, a.max_n, d_kcnt, st));
+        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+        HIP_TRY(latok::launch_tile_scan(d_kcnt, n_str + 1, d_kstart, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 6,
+                                        a.p_tot + 5, d_err + 1, st));
+        HIP_TRY(hipStreamSynchronize(st));   // wait 2: the key total decides whether the call goes on and what the keys take
+        int64_t n_tok_again = 0;
+        if ((rc = finish_totals(w, a.h_tot, 0, &n_tok_again))) return rc;
+        const int64_t n_keys = a.h_tot[5];
+        a.n_grams = n_keys;
+        if (n_keys >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld n-grams: term counts are int32 (fewer than 2^31 grams a call)", (long long)n_keys);
+        if (n_keys > 0) {
+            shape.ng_keys = n_keys;
+            if ((rc = ws_ensure(ws_needs(w, total, shape).data(), kWsNeeds))) return rc;   // (only the key buffers grow)
+            uint64_t* d_keys = (uint64_t*)w.tkeys.p;
+            latok::VocabTable vt;
+            if (a.vocab) vt = latok::VocabTable{a.vocab->d_slots, (const uint32_t*)a.vocab->d_blob, a.vocab->n_slots, a.vocab->seed};
+            HIP_TRY(latok::launch_ngram_keys((const uint8_t*)a.b.in.p, total, a.b.row, n_str, d_start, d_kstart, d_tspans, n_tok, n_keys, a.min_n, a.max_n,
+                                             a.sep, a.vocab ? &vt : nullptr, a.seed, a.n_features, a.alternate_sign, d_keys, st));
+            HIP_TRY(latok::launch_terms_reduce(d_keys, (uint64_t*)w.tkeys2.p, d_kstart, n_str, n_keys, a.vocab != nullptr, d_distinct, d_oov, st));
+            if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+            HIP_TRY(latok::launch_tile_scan(d_distinct, n_str + 1, d_indptr, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch,
+                                            d_total + 5, a.p_tot + 3, d_err + 1, st));
+            if (a.indices)
+                HIP_TRY(latok::launch_terms_emit(d_keys, d_kstart, n_str, n_keys, d_distinct, d_indptr, d_total + 5, a.cap, a.indices, a.data, st));
+        }
+    }
+    HIP_TRY(latok::launch_terms_finish(a.o32, d_indptr, d_oov, n_str, a.indptr, a.oov, st));
+    return LATOK_OK;
+}
+
+// the n-gram arguments of the two n-gram entry points; NULL: the plain term counts
+struct NgramArgs {
+    int min_n, max_n, sep;
+    int64_t* n_grams_out;
+};
+// the four blocking entry points' shared body: the checks of the ids call, the capacity protocol in entries
 static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
                               bool hashed, uint32_t seed, int64_t n_features, int alternate_sign, void* indptr_out, void* oov_out,
                               int32_t* indices_out, int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_tokens_out, int flags,
-                              void* stream) {
+                              void* stream, const NgramArgs* ng = nullptr) {
     LATOK_ENTER();
     if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    if (ng) {   // refused before any device work, with nothing written
+        if (ng->min_n < 1) return fail(LATOK_ERR_INVALID, "min_n must be at least 1");
+        if (ng->max_n < ng->min_n) return fail(LATOK_ERR_INVALID, "max_n must not be below min_n");
+        if (ng->max_n > kNgMax) return fail(LATOK_ERR_INVALID, "max_n must not exceed %d", kNgMax);
+        if (ng->sep < 0 || ng->sep > 255) return fail(LATOK_ERR_INVALID, "sep must be one byte: 0 .. 255");
+    }
     int rc = need_init(g);
     if (rc) return rc;
     if (!nnz_out) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
     *nnz_out = 0;
     if (n_tokens_out) *n_tokens_out = 0;
+    if (ng && ng->n_grams_out) *ng->n_grams_out = 0;
     if (!indptr_out) return fail(LATOK_ERR_INVALID, "indptr_out is NULL");
     if (cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
     if ((indices_out == nullptr) != (data_out == nullptr)) return fail(LATOK_ERR_INVALID, "indices_out and data_out go together: one of them is NULL");
@@ -2524,7 +2622,9 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
     }
     if (dev && (((uintptr_t)oov_out & (elt - 1)) != 0 || ((uintptr_t)indices_out & 3) != 0 || ((uintptr_t)data_out & 3) != 0))
         return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    if ((rc = c.stage(g, hashed ? 10 : 9, WsShape{.spans = true, .term_rows = n_str + 1}, kClearSized))) return rc;
+    WsShape shape{.spans = true, .term_rows = n_str + 1};
+    if (ng) shape.ng_rows = n_str + 1;
+    if ((rc = c.stage(g, ng ? (hashed ? 15 : 14) : (hashed ? 10 : 9), shape, ng ? kClearNgrams : kClearSized))) return rc;
     TermCounts a;
     a.b = c.d;
     a.vocab = v;
@@ -2535,7 +2635,13 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
     a.oov = oov_out;
     a.indices = indices_out;
     a.data = data_out;
-    a.cap = indices_out ? std::min(cap, c.total) : 0;   // (an entry has at least one token, a token one byte: the staging is sized by it)
+    // (an entry has at least one token, a token one byte: the staging is sized by it; a token starts one gram of every order at most)
+    a.cap = indices_out ? std::min(cap, c.total * (ng ? ng->max_n - ng->min_n + 1 : 1)) : 0;
+    if (ng) {
+        a.min_n = ng->min_n;
+        a.max_n = ng->max_n;
+        a.sep = ng->sep;
+    }
     a.o32 = c.o32;
     if (!dev) {
         if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 4 + 16)) ||
@@ -2551,7 +2657,7 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
     a.p_tot = c.p_tot;
     a.h_tot = c.h_tot;
     a.st = st;
-    if ((rc = enqueue_term_counts(g, g.ws, a))) return rc;
+    if ((rc = ng ? enqueue_ngram_counts(g, g.ws, a) : enqueue_term_counts(g, g.ws, a))) return rc;
     if (!dev) {   // valid whatever the capacity
         HIP_TRY(hipMemcpyAsync(indptr_out, a.indptr, (size_t)(n_str + 1) * elt, hipMemcpyDeviceToHost, st));
         if (oov_out) HIP_TRY(hipMemcpyAsync(oov_out, a.oov, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));
@@ -2559,9 +2665,25 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
     int64_t n_tok = 0;
     if ((rc = c.wait_totals(g, 0, &n_tok))) return rc;   // wait 2
     if (n_tokens_out) *n_tokens_out = n_tok;
+    if (ng && ng->n_grams_out) *ng->n_grams_out = a.n_grams;
     const int64_t nnz = c.h_tot[3];
     *nnz_out = nnz;
     return deliver_sized(c, nnz, cap, "capacity too small: need %lld entries", {{indices_out, a.indices, 4}, {data_out, a.data, 4}});   // (wait 3)
+}
+int latok_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
+                                        int min_n, int max_n, int sep, int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out,
+                                        int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_grams_out, int flags, void* stream) {
+    const NgramArgs ng{min_n, max_n, sep, n_grams_out};
+    return term_counts_common(utf8, byte_off, n_str, total_bytes, vocab, false, 0, 0, 0, indptr_out, oov_out, indices_out, data_out, cap, nnz_out,
+                              nullptr, flags, stream, &ng);
+}
+int latok_hashed_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, uint32_t seed,
+                                               int64_t n_features, int alternate_sign, int min_n, int max_n, int sep, int64_t* indptr_out,
+                                               int32_t* indices_out, int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_grams_out,
+                                               int flags, void* stream) {
+    const NgramArgs ng{min_n, max_n, sep, n_grams_out};
+    return term_counts_common(utf8, byte_off, n_str, total_bytes, nullptr, true, seed, n_features, alternate_sign, indptr_out, nullptr, indices_out,
+                              data_out, cap, nnz_out, nullptr, flags, stream, &ng);
 }
 int latok_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
                                        int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out, int32_t* data_out, int64_t cap,
@@ -3587,6 +3709,16 @@ extern "C" int latok_debug_limits(int64_t* out, int n) {
  * workgroup of its own).  Returns the number of values written. */
 extern "C" int latok_debug_terms_limits(int64_t* out, int n) {
     const int64_t v[2] = {latok::kTermsTile, latok::kTermsRowMax};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 2 ? n : 2;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
+/* test hook (not part of the ABI; needs no device): the constants of the n-gram calls: out[0] = kNgBlock (tokens per workgroup of
+ * k_ngram_keys), out[1] = kNgMax (the highest order).  Returns the number of values written. */
+extern "C" int latok_debug_ngram_limits(int64_t* out, int n) {
+    const int64_t v[2] = {latok::kNgBlock, kNgMax};
     if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
     const int k = n < 2 ? n : 2;
     for (int i = 0; i < k; ++i) out[i] = v[i];

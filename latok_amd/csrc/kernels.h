@@ -373,6 +373,17 @@ hipError_t launch_wp_emit(bool out32, const uint8_t* u8, int64_t total, const in
 hipError_t launch_wp_rows(bool out32, const int64_t* row_start, const int64_t* rank, int64_t n_str, int64_t n_tok, void* indptr_out, hipStream_t st);
 hipError_t launch_wp_pad(const int32_t* ids, const int64_t* row_start, const int64_t* rank, int64_t n_str, int64_t n_tok, int64_t max_length, int add_special,
                          int32_t cls_id, int32_t sep_id, int32_t pad_id, int32_t* input_ids, int32_t* lengths, hipStream_t st);
+// word n-grams of a UTF-8 batch in byte space (ngram_kernels.hip), in token space, one lane per token: behind KIND 1 of
+// launch_counts_scatter and the scan of the token counts, as WordPiece.  launch_ngram_rows leaves the grams of every string in
+// key_cnt[0 .. n_str) and 0 in key_cnt[n_str]; the caller scans the n_str + 1 entries into key_start[] (key_start[n_str] = the key
+// total).  launch_ngram_keys stores one term key (term_key.h) per gram of the orders min_n .. max_n inside its row's range of
+// `keys`, which holds n_keys keys: vt == NULL the hashed form, else the lookup of the gram's bytes (tokens joined by `sep`) in the
+// table.  launch_terms_reduce / _emit / _finish then take keys and key_start as they take the token keys and the token rows.
+constexpr int kNgBlock = 256;   // tokens per workgroup of k_ngram_keys (latok_debug_ngram_limits); the highest order: kNgMax of ngram_text.h
+hipError_t launch_ngram_rows(const int64_t* tok_cnt, int64_t n_str, int min_n, int max_n, int64_t* key_cnt, hipStream_t st);
+hipError_t launch_ngram_keys(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
+                             const int64_t* key_start, const int64_t* tok_spans, int64_t n_tok, int64_t n_keys, int min_n, int max_n, int sep,
+                             const VocabTable* vt, uint32_t seed, uint32_t n_features, bool alternate_sign, uint64_t* keys, hipStream_t st);
 // the commit behind it: (a) the padded dwords of the fresh slots -> ctl[0]; (b) their bytes into the blob, resident words stored
 hipError_t launch_count_commit_sum(const CountTable& ct, hipStream_t st);
 hipError_t launch_count_commit_copy(const uint8_t* u8, const CountTable& ct, hipStream_t st);

@@ -41,6 +41,10 @@
   bytes_terms32 / bytes_terms_hashed   latok_term_counts_utf8_bytes_batch (the vocabulary of the ids paths, --vocab all|half) /
                   latok_hashed_term_counts_utf8_bytes_batch (2^20 features, alternating signs): the CSR rows of the document-term
                   matrix with int32 indptr (and oov), capacity = the token total; same process run as bytes_ids32 and bytes_hashes32
+  bytes_ngrams32 / bytes_ngrams_hashed   latok_ngram_counts_utf8_bytes_batch / latok_hashed_ngram_counts_utf8_bytes_batch with the
+                  range (1, 2) and the separator 0x20, everything else as bytes_terms32 / bytes_terms_hashed (the vocabulary of the ids
+                  paths holds single tokens only, so every bigram's probe ends in a miss); capacity = twice the token bound; same
+                  process run as bytes_terms32, bytes_terms_hashed and bytes_spans32
   bytes_wp32 / bytes_wp_padded   latok_wordpiece_ids_utf8_bytes_batch (int32 indptr and spans, capacity = the token bound) /
                   latok_wordpiece_padded_utf8_bytes_batch ([n, 64] block with [CLS] / [SEP]) against a WordPiece vocabulary of the words
                   of the ids paths (--vocab all|half; no continuation words, so a token is one piece: with `all` its id, with `half`
@@ -405,7 +409,7 @@ def main():
     # joined token text and the byte-space spans beside it: every line of this leg in one process run, in the order given
     join_leg = [p for p in paths if p in ("bytes_join", "bytes_join_flow", "bytes_spans32", "bytes_spans32_flow", "bytes_hashes32",
                                           "bytes_hashes32_flow", "bytes_hashes_only", "bytes_hashes_only_flow", "bytes_ids32", "bytes_ids32_flow",
-                                          "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "py_terms",
+                                          "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "bytes_ngrams32", "bytes_ngrams_hashed", "py_terms",
                                           "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join", "bytes_wp32", "bytes_wp_padded", "py_wp",
                                           "bytes_fold", "bytes_fold_wp", "py_fold")]
     if join_leg:
@@ -479,6 +483,24 @@ def main():
                                                                      None, D32, None)
             return lib.latok_term_counts_utf8_bytes_batch(d_u8, d_boff, n, n8, corpus_vocab().handle, t_indptr, t_oov, h_a, h_b, cap, C.byref(nout),
                                                           None, D32, None)
+
+        note_g = ("as bytes_terms32 / bytes_terms_hashed with one key per unigram and bigram: 16 B/token span records written and read, the "
+                  "bytes of every token read by the walks of two tokens; 8 B/gram keys written, read by the sort and written back; 4 B/string "
+                  "indptr (+ 4 B/string oov) and 8 B/entry written (--vocab " + args.vocab + " / 2^20 features)")
+        ngrams_box = []
+
+        def ngrams_blocking(hashed):
+            if not ngrams_box:
+                nb = [lib.latok_dev_alloc(sz) for sz in ((n + 1) * 4 + 64, n * 4 + 64, 2 * cap * 4, 2 * cap * 4)]
+                if not all(nb):
+                    raise RuntimeError(_lib.last_error())
+                ngrams_box.extend(nb)
+            g_indptr, g_oov, g_a, g_b = ngrams_box
+            if hashed:
+                return lib.latok_hashed_ngram_counts_utf8_bytes_batch(d_u8, d_boff, n, n8, SEED, 1 << 20, 1, 1, 2, 32, g_indptr, g_a, g_b, 2 * cap,
+                                                                      C.byref(nout), None, D32, None)
+            return lib.latok_ngram_counts_utf8_bytes_batch(d_u8, d_boff, n, n8, corpus_vocab().handle, 1, 2, 32, g_indptr, g_oov, g_a, g_b, 2 * cap,
+                                                           C.byref(nout), None, D32, None)
 
         note_w = ("UTF-8 bytes + 8 B/string read; 4 B/string indptr + 4 B/piece ids + 8 B/piece spans written (--vocab " + args.vocab + "). NOT "
                   "counted: the workspace traffic (16 B/token span records, 8 B/token piece counts, 8 B/token piece ranks, each written "
@@ -738,6 +760,9 @@ def main():
             elif name in ("bytes_terms32", "bytes_terms_hashed"):   # (items = nnz; the keys are sized by the token total)
                 hashed = name == "bytes_terms_hashed"
                 run(name, lambda: terms_blocking(hashed), lambda: n8 + csr + 4 * n + (0 if hashed else 4 * n) + 8 * nout.value, note_t)
+            elif name in ("bytes_ngrams32", "bytes_ngrams_hashed"):   # (items = nnz; the keys are sized by the gram total)
+                hashed = name == "bytes_ngrams_hashed"
+                run(name, lambda: ngrams_blocking(hashed), lambda: n8 + csr + 4 * n + (0 if hashed else 4 * n) + 8 * nout.value, note_g)
             elif name == "py_terms":   # host blobs in, the CSR arrays out, both routes in this process
                 import collections
                 from latok_amd import batch
@@ -853,7 +878,7 @@ def main():
             wp_box[0].close()
             for p_ in wp_box[1:]:
                 lib.latok_dev_free(p_)
-        for p_ in terms_box:
+        for p_ in terms_box + ngrams_box:
             lib.latok_dev_free(p_)
         for p_ in jb:
             lib.latok_dev_free(p_)
