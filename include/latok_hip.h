@@ -355,6 +355,93 @@ int latok_hashed_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_
                                                int64_t* indptr_out /* [n_str+1] */, int32_t* indices_out, int32_t* data_out, int64_t cap,
                                                int64_t* nnz_out, int64_t* n_grams_out /* may be NULL */, int flags, void* stream);
 
+/* TF-IDF on the device: document frequencies over many batches, and the float32 weighting of CSR rows -- what TfidfTransformer /
+ * TfidfVectorizer add to the term counts above, and the norm="l2" / "l1" of HashingVectorizer.
+ * A latok_idf is a mutable device object like latok_counter: int32 df[n_cols] (in how many rows a column was stored) and int64 n_docs
+ * (rows seen), on the device of the context that created it; every call checks that device against the current context's.  Calls on
+ * one object are serialised by a lock inside it.  latok_idf_create: n_cols in 1 .. 2^28, anything else is refused before any device
+ * work; df and n_docs start at zero.  latok_idf_info needs no device call; any output pointer may be NULL.  latok_idf_clear zeroes
+ * df and n_docs.  latok_idf_destroy drains the current context (its stream and its flow) first, like latok_vocab_destroy.
+ *   latok_idf_update_csr   df[c] += 1 for every STORED entry with column c, n_docs += n_rows: np.bincount(X.indices, minlength=n_cols)
+ *                          of a CSR matrix, scikit-learn's _document_frequency.  Explicit zeros count (the hashed rows keep them, as
+ *                          scikit-learn does).  A row's columns are taken as distinct, as every CSR of this library has them; the call
+ *                          does not check that.  Host pointers or LATOK_DEVICE_PTRS; LATOK_OUT_INT32: indptr is int32, else int64; any
+ *                          other flag bit is refused.  The CSR is validated on the device before df is touched: indptr[0] = 0,
+ *                          non-decreasing, indptr[n_rows] = nnz, every index in [0, n_cols) -- a vocabulary may carry any int32 as an
+ *                          id, so an out-of-range column is a real case.  A refused call leaves df and n_docs exactly as they were.
+ *                          The call is refused when n_docs + n_rows would reach 2^31 (df is int32).  Blocking.
+ *   latok_idf_update_utf8_bytes_batch
+ *                          the same update straight from text: the term-count pipeline of the calls above (vocab, or vocab = NULL:
+ *                          the hashed form with seed and n_features; min_n = max_n = 1: the plain term counts, else word n-grams
+ *                          joined by sep) runs into the context's own buffers and its indptr / indices feed the update; no entry
+ *                          visits the host.  Hashed form: n_features must equal n_cols, else the call is refused before any device work
+ *                          (alternate_sign has no bearing on which entries exist and is not an argument).  Vocabulary form: an id
+ *                          outside [0, n_cols) refuses the call with df and n_docs unchanged.  n_docs += n_str, empty strings
+ *                          included.  Flags: LATOK_DEVICE_PTRS only.  *nnz_out, *n_tokens_out (may be NULL) as in the count calls.
+ *   latok_idf_read         df to HOST pointers with the size-query protocol of latok_counter_read: *n_docs_out (may be NULL) is always
+ *                          set; cap = 0 with df_out NULL is a size query that returns LATOK_OK; 0 < cap < n_cols writes nothing and
+ *                          returns LATOK_ERR_INVALID (the need is n_cols: latok_idf_info).
+ *   latok_idf_load         sets df[n_cols] and n_docs from HOST pointers, for an idf that was fitted elsewhere; refused with nothing
+ *                          changed if n_docs is negative or 2^31 or more, or any df[c] lies outside [0, n_docs].
+ *   latok_idf_weights      the idf vector to HOST pointers (cap >= n_cols floats):
+ *                            idf[c] = ln((n_docs + s) / (df[c] + s)) + 1,  s = 1 if smooth else 0
+ *                          evaluated in double on the device and rounded once to float32.  WITHOUT smoothing a column with df[c] = 0
+ *                          gets idf[c] = 0, where scikit-learn divides by zero.  The vector is computed once per smoothing mode and
+ *                          kept until the next update, load or clear.
+ * Multi-device: there is no merge call; latok_idf_read on every device, a sum on the host and latok_idf_load is the route.
+ *
+ * latok_tfidf_csr is TfidfTransformer.transform on a CSR in host or device memory (flags as latok_idf_update_csr): int32 counts in,
+ * float32 weights out; data_out may be `data` itself.  idf = NULL: no idf.  opts is an OR of LATOK_TFIDF_*; both norm bits together,
+ * or an unknown bit, are refused before any device work.  For entry j of row r with count t and column c:
+ *   tf  = t; with LATOK_TFIDF_SUBLINEAR_TF: sign(t) * (1 + ln|t|) for t != 0, and 0 for t = 0.  (scikit-learn takes ln of the stored
+ *         value and gives NaN for the negative and zero sums of alternate_sign; this definition agrees with it wherever it is defined.)
+ *   w   = tf * idf[c] (LATOK_TFIDF_SMOOTH_IDF picks the smoothing mode), or tf without an idf
+ *   out = w / N_r,  N_r = sqrt(sum of w^2) with LATOK_TFIDF_NORM_L2, sum of |w| with LATOK_TFIDF_NORM_L1, 1 with neither
+ * A row whose norm is 0 keeps its zeros; an entry with t = 0 is exactly 0.0f; no NaN or infinity comes from finite input.  A row's
+ * output bits depend on that row alone -- its (indices, data) in order, the idf of its columns, opts -- not on its place in the
+ * batch, its neighbours, the batch size or host versus device pointers: a fixed group of lanes chosen by the row's length sums in a
+ * fixed order, and there is no floating-point atomic.  Every output lies within (k + 16) * 2^-23 relative of the exact value for a
+ * normalised row of k stored entries and within 8 * 2^-23 without a norm; a single-entry row under L2 with a nonzero weight is exactly
+ * +-1.0f.  The CSR is validated as in latok_idf_update_csr, the columns only when idf is given; a refused call writes nothing to
+ * data_out.  Blocking.
+ *
+ * latok_tfidf_utf8_bytes_batch / latok_hashed_tfidf_utf8_bytes_batch: text to TF-IDF rows in one call.  indptr, indices and oov are
+ * entry for entry those of latok_ngram_counts_utf8_bytes_batch / latok_hashed_ngram_counts_utf8_bytes_batch with the same arguments
+ * (min_n = max_n = 1 takes the plain term counts' kernels); data_out is the weighting of their data, bit for bit what
+ * latok_tfidf_csr gives on that CSR.  The weighting runs on the device behind the counts, in place, and adds no wait to theirs.
+ * Everything else carries over: the capacity protocol in ENTRIES with its size query, LATOK_OUT_INT32, LATOK_DEVICE_PTRS,
+ * total_bytes = -1, the empty batch, the refusal of 2^31 tokens or grams, the n-gram argument checks.  idf may be NULL.  Hashed form
+ * with an idf: n_features != n_cols is refused before any device work.  Vocabulary form with an idf: an id outside [0, n_cols)
+ * refuses the call behind its kernels; host output buffers are then untouched, device output buffers hold the unweighted counts. */
+#define LATOK_TFIDF_SMOOTH_IDF 1
+#define LATOK_TFIDF_SUBLINEAR_TF 2
+#define LATOK_TFIDF_NORM_L1 4
+#define LATOK_TFIDF_NORM_L2 8
+typedef struct latok_idf latok_idf;
+int latok_idf_create(int64_t n_cols, latok_idf** out);
+int latok_idf_destroy(latok_idf* idf);
+int latok_idf_clear(latok_idf* idf);
+int latok_idf_info(const latok_idf* idf, int64_t* n_cols, int64_t* n_docs, int* device);
+int latok_idf_update_csr(latok_idf* idf, const void* indptr /* [n_rows+1] */, const int32_t* indices, int64_t n_rows, int64_t nnz,
+                         int flags, void* stream);
+int latok_idf_update_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                      const latok_vocab* vocab /* NULL: hashed */, uint32_t seed, int64_t n_features, int min_n, int max_n,
+                                      int sep, latok_idf* idf, int64_t* nnz_out /* may be NULL */, int64_t* n_tokens_out /* may be NULL */,
+                                      int flags, void* stream);
+int latok_idf_read(const latok_idf* idf, int32_t* df_out, int64_t cap, int64_t* n_docs_out);
+int latok_idf_load(latok_idf* idf, const int32_t* df /* [n_cols] */, int64_t n_docs);
+int latok_idf_weights(const latok_idf* idf, int smooth, float* out, int64_t cap);
+int latok_tfidf_csr(const void* indptr /* [n_rows+1] */, const int32_t* indices, const int32_t* data, int64_t n_rows, int64_t nnz,
+                    const latok_idf* idf /* NULL: no idf */, int opts, float* data_out, int flags, void* stream);
+int latok_tfidf_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                 const latok_vocab* vocab, int min_n, int max_n, int sep, const latok_idf* idf /* may be NULL */, int opts,
+                                 int64_t* indptr_out /* [n_str+1] */, int64_t* oov_out /* [n_str], may be NULL */, int32_t* indices_out,
+                                 float* data_out, int64_t cap, int64_t* nnz_out, int flags, void* stream);
+int latok_hashed_tfidf_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, uint32_t seed,
+                                        int64_t n_features, int alternate_sign, int min_n, int max_n, int sep,
+                                        const latok_idf* idf /* may be NULL */, int opts, int64_t* indptr_out /* [n_str+1] */,
+                                        int32_t* indices_out, float* data_out, int64_t cap, int64_t* nnz_out, int flags, void* stream);
+
 /* WordPiece in byte space: the subword ids a BERT-family model takes, for every token of a batch.
  * A WORDPIECE VOCABULARY is an ordered list of byte strings w_0 .. w_(V-1) with optional int32 ids (word_ids = NULL means id_i = i),
  * a continuation prefix P of 0 .. 8 bytes ("##" in BERT's files; an empty P is legal: every word is then also a continuation word),

@@ -14,6 +14,7 @@ OK, ERR_INVALID, ERR_HIP, ERR_NOT_INIT, ERR_NOMEM = 0, -1, -2, -3, -4
 DEVICE_PTRS = 1
 OUT_INT32 = 2
 FOLD_LOWER, FOLD_STRIP_MARKS, FOLD_CLEAN, FOLD_CJK_SPACE = 1, 2, 4, 8     # LATOK_FOLD_* (latok_fold_utf8_bytes_batch)
+TFIDF_SMOOTH_IDF, TFIDF_SUBLINEAR_TF, TFIDF_NORM_L1, TFIDF_NORM_L2 = 1, 2, 4, 8   # LATOK_TFIDF_* (latok_tfidf_csr)
 FEATURE_COUNT = 25
 TILE_CHARS = 4096
 CORPUS_ASCII, CORPUS_UNICODE = 0, 1
@@ -62,6 +63,19 @@ SIGNATURES = {
     "latok_ngram_counts_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, ci, ci, ci, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
     "latok_hashed_ngram_counts_utf8_bytes_batch": (ci, [vp, vp, i64, i64, C.c_uint32, i64, ci, ci, ci, ci, vp, vp, vp, i64, C.POINTER(i64),
                                                         C.POINTER(i64), ci, vp]),
+    "latok_idf_create": (ci, [i64, C.POINTER(vp)]),
+    "latok_idf_destroy": (ci, [vp]),
+    "latok_idf_clear": (ci, [vp]),
+    "latok_idf_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(ci)]),
+    "latok_idf_update_csr": (ci, [vp, vp, vp, i64, i64, ci, vp]),
+    "latok_idf_update_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_uint32, i64, ci, ci, ci, vp, C.POINTER(i64), C.POINTER(i64), ci, vp]),
+    "latok_idf_read": (ci, [vp, vp, i64, C.POINTER(i64)]),
+    "latok_idf_load": (ci, [vp, vp, i64]),
+    "latok_idf_weights": (ci, [vp, ci, vp, i64]),
+    "latok_tfidf_csr": (ci, [vp, vp, vp, i64, i64, vp, ci, vp, ci, vp]),
+    "latok_tfidf_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, i64, C.POINTER(i64), ci, vp]),
+    "latok_hashed_tfidf_utf8_bytes_batch": (ci, [vp, vp, i64, i64, C.c_uint32, i64, ci, ci, ci, ci, vp, ci, vp, vp, vp, i64, C.POINTER(i64),
+                                                 ci, vp]),
     "latok_wordpiece_create": (ci, [vp, vp, i64, vp, vp, ci, ci, C.c_uint32, C.POINTER(vp)]),
     "latok_wordpiece_destroy": (ci, [vp]),
     "latok_wordpiece_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, C.POINTER(ci),

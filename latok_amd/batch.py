@@ -912,6 +912,253 @@ def hashed_term_counts_batch(texts, n_features=1 << 20, seed=0, alternate_sign=T
                                          sep=sep)
 
 
+# TF-IDF: document frequencies over many batches and the float32 weighting of the CSR rows, on the device -- TfidfVectorizer's last step
+def _tfidf_opts(smooth_idf, sublinear_tf, norm) -> int:
+    """the LATOK_TFIDF_* bits of a call; ``norm`` is "l1", "l2" or None, anything else a ValueError (before any device is asked for)"""
+    if norm not in ("l1", "l2", None):
+        raise ValueError('norm must be "l1", "l2" or None')
+    return ((_lib.TFIDF_SMOOTH_IDF if smooth_idf else 0) | (_lib.TFIDF_SUBLINEAR_TF if sublinear_tf else 0) |
+            (_lib.TFIDF_NORM_L1 if norm == "l1" else _lib.TFIDF_NORM_L2 if norm == "l2" else 0))
+
+
+def _csr_arrays(indptr, indices, data=None):
+    """(indptr int32 or int64, indices int32[, data int32], flags): contiguous copies where needed; the width of indptr picks the flag"""
+    indptr = np.asarray(indptr)
+    if indptr.ndim != 1 or indptr.size < 1 or indptr.dtype.kind not in "iu":
+        raise ValueError("indptr must be a 1-d integer array of n_rows + 1 entries")
+    indptr = np.ascontiguousarray(indptr, np.int32 if indptr.dtype == np.int32 else np.int64)
+    indices = np.ascontiguousarray(indices, np.int32)
+    flags = _lib.OUT_INT32 if indptr.dtype == np.int32 else 0
+    if data is None:
+        return indptr, indices, flags
+    data = np.ascontiguousarray(data, np.int32)
+    if data.shape != indices.shape or data.ndim != 1:
+        raise ValueError("indices and data must be 1-d arrays of one length")
+    return indptr, indices, data, flags
+
+
+class Idf:
+    """Document frequencies on the device of the current context (``latok_idf_create``): ``df[n_cols]`` -- in how many rows a column
+    was stored -- and ``n_docs``, accumulated over any number of batches; ``weights()`` is the idf vector ``ln((n_docs + s) / (df + s)) +
+    1`` (s = 1 if smooth), float32, what ``TfidfTransformer.idf_`` holds after ``fit``.  ``df()`` hands a caller what ``min_df`` /
+    ``max_df`` pruning needs.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
+
+    def __init__(self, n_cols):
+        self.handle = None
+        if not isinstance(n_cols, (int, np.integer)) or isinstance(n_cols, bool):
+            raise ValueError("n_cols must be an int in 1 .. 2**28")
+        lib = _lib.ensure_init()
+        h = C.c_void_p()
+        _lib.check(lib.latok_idf_create(int(n_cols), C.byref(h)))
+        self._lib, self.handle, self.n_cols = lib, h, int(n_cols)
+
+    def _open(self):
+        if not self.handle:
+            raise ValueError("the idf is closed")
+        return self.handle
+
+    def update_csr(self, indptr, indices):
+        """df[c] += 1 for every stored entry of the CSR (explicit zeros count), n_docs += n_rows: ``np.bincount(indices)``"""
+        indptr, indices, flags = _csr_arrays(indptr, indices)
+        _lib.check(self._lib.latok_idf_update_csr(self._open(), _ptr(indptr), _ptr(indices) if indices.size else None, indptr.size - 1,
+                                                  indices.size, flags, None))
+
+    def update_utf8(self, blobs, vocab=None, n_features=None, seed=0, fold=0, ngram_range=(1, 1), sep=b" "):
+        """The same update straight from text, list[bytes] (UTF-8): the rows of term_counts_utf8_batch (``vocab``) or of
+        hashed_term_counts_utf8_batch (``n_features``, ``seed``) -- exactly one of the two -- are counted on the device and never
+        visit the host.  Returns nnz, the entries the batch stored."""
+        if (vocab is None) == (n_features is None):
+            raise ValueError("exactly one of vocab and n_features must be given")
+        handle = None if vocab is None else _vocab_handle(vocab)
+        n_feat, seed = (0 if n_features is None else _n_features31(n_features)), _seed32(seed)
+        fold, ng = _fold_bits(fold), _ngram_spec(ngram_range, sep) or (1, 1, _sep_byte(sep))
+        h, nnz = self._open(), C.c_int64(0)
+        utf8, byte_off = pack_utf8(blobs)
+        if fold:
+            with _DeviceFolded(utf8, byte_off, fold) as d:
+                _lib.check(d.lib.latok_idf_update_utf8_bytes_batch(d.u8, d.off, d.n_str, d.total, handle, seed, n_feat, ng[0], ng[1], ng[2], h,
+                                                                   C.byref(nnz), None, _lib.DEVICE_PTRS, None))
+            return nnz.value
+        utf8, byte_off = _csr_u8(utf8, byte_off)
+        n_str = byte_off.size - 1
+        _lib.check(self._lib.latok_idf_update_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, int(byte_off[-1]) if n_str > 0 else 0, handle,
+                                                               seed, n_feat, ng[0], ng[1], ng[2], h, C.byref(nnz), None, 0, None))
+        return nnz.value
+
+    def update(self, texts, **kw):
+        """list[str]: update_utf8 of the strings' UTF-8 ("surrogatepass")"""
+        return self.update_utf8([t.encode("utf-8", "surrogatepass") for t in texts], **kw)
+
+    def df(self):
+        """int32[n_cols]: the document frequencies"""
+        out = np.empty(self.n_cols, np.int32)
+        _lib.check(self._lib.latok_idf_read(self._open(), _ptr(out), out.size, None))
+        return out
+
+    @property
+    def n_docs(self):
+        n = C.c_int64(0)
+        _lib.check(self._lib.latok_idf_info(self._open(), None, C.byref(n), None))
+        return n.value
+
+    def weights(self, smooth=True):
+        """float32[n_cols]: the idf vector; without smoothing a column with df = 0 gets 0"""
+        out = np.empty(self.n_cols, np.float32)
+        _lib.check(self._lib.latok_idf_weights(self._open(), 1 if smooth else 0, _ptr(out), out.size))
+        return out
+
+    def load(self, df, n_docs):
+        """set df and n_docs, for an idf that was fitted elsewhere (or summed over devices); every df[c] must lie in [0, n_docs]"""
+        raw = np.asarray(df)
+        if raw.shape != (self.n_cols,) or raw.dtype.kind not in "iu":
+            raise ValueError("df must be one integer per column")
+        if raw.size and (raw.min() < -0x80000000 or raw.max() > 0x7FFFFFFF):
+            raise ValueError("df must fit int32")
+        raw = np.ascontiguousarray(raw, np.int32)
+        _lib.check(self._lib.latok_idf_load(self._open(), _ptr(raw), int(n_docs)))
+
+    def clear(self):
+        _lib.check(self._lib.latok_idf_clear(self._open()))
+
+    def close(self):
+        if self.handle:
+            h, self.handle = self.handle, None
+            _lib.check(self._lib.latok_idf_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _idf_handle(idf):
+    if idf is None:
+        return None
+    if not isinstance(idf, Idf) or not idf.handle:
+        raise ValueError("idf must be an open latok_amd.batch.Idf or None")
+    return idf.handle
+
+
+def tfidf_csr(indptr, indices, data, idf=None, smooth_idf=True, sublinear_tf=False, norm="l2"):
+    """float32[nnz]: ``TfidfTransformer(norm, use_idf=idf is not None, smooth_idf, sublinear_tf).transform`` of the int32 CSR, weighted
+    on the device (``latok_tfidf_csr``): tf (or sign(t)(1 + ln|t|)) times ``idf.weights(smooth_idf)``, over the row's L2 / L1 norm.  A
+    row's output bits depend on that row alone."""
+    opts, handle = _tfidf_opts(smooth_idf, sublinear_tf, norm), _idf_handle(idf)
+    indptr, indices, data, flags = _csr_arrays(indptr, indices, data)
+    out = np.empty(data.size, np.float32)
+    lib = _lib.ensure_init()
+    _lib.check(lib.latok_tfidf_csr(_ptr(indptr), _ptr(indices) if data.size else None, _ptr(data) if data.size else None, indptr.size - 1,
+                                   data.size, handle, opts, _ptr(out) if data.size else None, flags, None))
+    return out
+
+
+def _tfidf_call(lib, hashed, u8, off, n_str, total, vocab, ng, idf, opts, indptr, oov, indices, data, cap, nnz, flags):
+    if hashed:
+        seed, n_features, alternate_sign = hashed
+        return lib.latok_hashed_tfidf_utf8_bytes_batch(u8, off, n_str, total, seed, n_features, 1 if alternate_sign else 0, ng[0], ng[1], ng[2], idf,
+                                                       opts, indptr, indices, data, cap, C.byref(nnz), flags, None)
+    return lib.latok_tfidf_utf8_bytes_batch(u8, off, n_str, total, vocab, ng[0], ng[1], ng[2], idf, opts, indptr, oov, indices, data, cap,
+                                            C.byref(nnz), flags, None)
+
+
+def _tfidf_rows(utf8, byte_off, vocab, hashed, idf, opts, fold, ng, dtype):
+    """the size query, then the fill -> (indptr, indices, data float32, oov or None); folded batches run on device buffers"""
+    dt, flags = _out_dtype(dtype)
+    nnz = C.c_int64(0)
+    if fold:
+        with _DeviceFolded(utf8, byte_off, fold) as d:
+            n_str = d.n_str
+            indptr, oov = d.alloc((n_str + 1) * dt.itemsize), None if hashed else d.alloc(n_str * dt.itemsize)
+
+            def call(indices, data, cap):
+                return _tfidf_call(d.lib, hashed, d.u8, d.off, n_str, d.total, vocab, ng, idf, opts, indptr, oov, indices, data, cap, nnz,
+                                   flags | _lib.DEVICE_PTRS)
+
+            rc = call(None, None, 0)
+            if rc != _lib.OK and not (rc == _lib.ERR_INVALID and nnz.value > 0):
+                _lib.check(rc)
+            need = nnz.value
+            if need > 0:
+                indices, data = d.alloc(need * 4), d.alloc(need * 4)
+                _lib.check(call(indices, data, need))
+            return (d.fetch(indptr, n_str + 1, dt), d.fetch(indices, need, np.int32) if need else np.empty(0, np.int32),
+                    d.fetch(data, need, np.float32) if need else np.empty(0, np.float32), None if hashed else d.fetch(oov, n_str, dt))
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    n_str = byte_off.size - 1
+    total = int(byte_off[-1]) if n_str > 0 else 0
+    lib = _lib.ensure_init()
+    indptr = np.zeros(n_str + 1, dt)
+    oov = None if hashed else np.zeros(n_str, dt)
+
+    def call(indices, data, cap):
+        return _tfidf_call(lib, hashed, _ptr(utf8), _ptr(byte_off), n_str, total, vocab, ng, idf, opts, _ptr(indptr),
+                           None if hashed else _ptr(oov), indices, data, cap, nnz, flags)
+
+    rc = call(None, None, 0)
+    if rc != _lib.OK and not (rc == _lib.ERR_INVALID and nnz.value > 0):
+        _lib.check(rc)
+    indices, data = np.empty(nnz.value, np.int32), np.empty(nnz.value, np.float32)
+    if nnz.value > 0:
+        _lib.check(call(_ptr(indices), _ptr(data), nnz.value))
+    return indptr, indices, data, oov
+
+
+def _tfidf_ng(ngram_range, sep):
+    return _ngram_spec(ngram_range, sep) or (1, 1, _sep_byte(sep))
+
+
+def tfidf_utf8_csr(utf8, byte_off, vocab, idf=None, smooth_idf=True, sublinear_tf=False, norm="l2", fold=0, ngram_range=(1, 1), sep=b" ",
+                   dtype=np.int64):
+    """(indptr, indices int32, data float32, oov): the rows of term_counts_utf8_csr with the same ``vocab`` / ``ngram_range`` / ``sep``,
+    their data weighted as tfidf_csr weights it, in one call on the device (``latok_tfidf_utf8_bytes_batch``) -- what
+    ``TfidfVectorizer(vocabulary=...).transform`` returns.  ``idf``: an Idf or None (no idf); ``fold``: FOLD_* flags, folded on the device
+    first."""
+    opts = _tfidf_opts(smooth_idf, sublinear_tf, norm)
+    return _tfidf_rows(utf8, byte_off, _vocab_handle(vocab), None, _idf_handle(idf), opts, _fold_bits(fold), _tfidf_ng(ngram_range, sep), dtype)
+
+
+def tfidf_utf8_batch(blobs, vocab, idf=None, smooth_idf=True, sublinear_tf=False, norm="l2", fold=0, ngram_range=(1, 1), sep=b" "):
+    """list[bytes] (UTF-8) -> (indptr, indices, data float32, oov) of tfidf_utf8_csr, int64"""
+    utf8, byte_off = pack_utf8(blobs)
+    return tfidf_utf8_csr(utf8, byte_off, vocab, idf, smooth_idf, sublinear_tf, norm, fold, ngram_range, sep)
+
+
+def tfidf_batch(texts, vocab, idf=None, smooth_idf=True, sublinear_tf=False, norm="l2", fold=0, ngram_range=(1, 1), sep=b" "):
+    """list[str] -> (indptr, indices, data float32, oov): tfidf_utf8_batch of the strings' UTF-8 ("surrogatepass")"""
+    return tfidf_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], vocab, idf, smooth_idf, sublinear_tf, norm, fold, ngram_range, sep)
+
+
+def hashed_tfidf_utf8_csr(utf8, byte_off, n_features=1 << 20, seed=0, alternate_sign=True, idf=None, smooth_idf=True, sublinear_tf=False,
+                          norm="l2", fold=0, ngram_range=(1, 1), sep=b" ", dtype=np.int64):
+    """(indptr, indices int32, data float32): the rows of hashed_term_counts_utf8_csr, weighted as tfidf_csr weights them, in one call
+    on the device (``latok_hashed_tfidf_utf8_bytes_batch``); without an idf and with norm="l2" this is ``HashingVectorizer``'s own
+    default.  An ``idf`` must have ``n_features`` columns."""
+    opts, hashed = _tfidf_opts(smooth_idf, sublinear_tf, norm), (_seed32(seed), _n_features31(n_features), bool(alternate_sign))
+    return _tfidf_rows(utf8, byte_off, None, hashed, _idf_handle(idf), opts, _fold_bits(fold), _tfidf_ng(ngram_range, sep), dtype)[:3]
+
+
+def hashed_tfidf_utf8_batch(blobs, n_features=1 << 20, seed=0, alternate_sign=True, idf=None, smooth_idf=True, sublinear_tf=False, norm="l2",
+                            fold=0, ngram_range=(1, 1), sep=b" "):
+    """list[bytes] (UTF-8) -> (indptr, indices, data float32) of hashed_tfidf_utf8_csr, int64"""
+    utf8, byte_off = pack_utf8(blobs)
+    return hashed_tfidf_utf8_csr(utf8, byte_off, n_features, seed, alternate_sign, idf, smooth_idf, sublinear_tf, norm, fold, ngram_range, sep)
+
+
+def hashed_tfidf_batch(texts, n_features=1 << 20, seed=0, alternate_sign=True, idf=None, smooth_idf=True, sublinear_tf=False, norm="l2", fold=0,
+                       ngram_range=(1, 1), sep=b" "):
+    """list[str] -> (indptr, indices, data float32): hashed_tfidf_utf8_batch of the strings' UTF-8 ("surrogatepass")"""
+    return hashed_tfidf_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], n_features, seed, alternate_sign, idf, smooth_idf,
+                                   sublinear_tf, norm, fold, ngram_range, sep)
+
+
 # WordPiece: every token cut greedily into the longest vocabulary prefix and ##-continuations, on the device -- the subword ids a
 # BERT-family model takes, as CSR rows or as the padded [n, L] block
 class WordPiece:

@@ -37,6 +37,7 @@
 #include "wordpiece.h"
 #include "fold_map.h"
 #include "fold_tables.inc"
+#include "tfidf_weight.h"
 
 static_assert(LATOK_TBL_SHIFT == latok::kTblShift, "table shift");
 static_assert(LATOK_TBL_STAGE1_LEN == latok::kStage1Len, "stage-1 length");
@@ -187,6 +188,7 @@ struct Workspace {
     DevBuf tkeys, tkeys2, trows;   // term counts: one key per token, the long rows' second buffer, five int64 arrays over the rows
     DevBuf wpspans, wpcnt, wprank, wpids;   // WordPiece: per token its span record, piece count and piece rank; the padded form's ids
     DevBuf ngrows;   // word n-grams: gram counts and row starts in key space (the span records share wpspans, the keys tkeys / tkeys2)
+    DevBuf tfptr, tfidx, tfval, tfctl;   // TF-IDF: a host caller's CSR on the device (indptr, indices, data) and the error word of k_csr_check
     // the single-pass scan of k_word_counts_scan keeps its look-back state (chain: per workgroup, chain_ctl: {ticket
     // counter}) between launches: entries carry an epoch, so the array is cleared only when it is (re)allocated or when the
     // 18-bit epoch wraps (next_scan_epoch); *_seen = DevBuf::gen of the allocations it was last cleared in
@@ -195,7 +197,7 @@ struct Workspace {
     void release() {
         for (DevBuf* b : {&summ, &seg_agg, &fix_count, &tile_first, &bits, &space, &kept, &wcnt, &wpref, &bases, &scalar, &chain,
                           &chain_ctl, &codes, &widened, &lead, &bspace, &cpbits, &cpspace, &cprow, &jbody, &jhead, &tkeys,
-                          &tkeys2, &trows, &wpspans, &wpcnt, &wprank, &wpids, &ngrows})
+                          &tkeys2, &trows, &wpspans, &wpcnt, &wprank, &wpids, &ngrows, &tfptr, &tfidx, &tfval, &tfctl})
             b->release();
         scan_epoch = chain_seen = chain_ctl_seen = 0;
         chain_ready = false;
@@ -206,7 +208,7 @@ struct WsNeed {
     size_t bytes;   // 0: the batch does not use the buffer
 };
 constexpr int kTileNeeds = 4;   // the first entries of ws_needs: the tile stage
-constexpr int kWsNeeds = 30;
+constexpr int kWsNeeds = 34;
 // What a batch asks of its workspace beyond the tile stage.  token spans (spans) add the SPACE and kept planes, featurize (feats)
 // the code bytes, and narrow units read by featurize (widen) a UTF-32 copy.  cp_rows > 0: the units are UTF-8 bytes whose results
 // are reported in code points (cp_rows = n_str + 1): every buffer is sized by the byte count, which bounds the code-point count.
@@ -218,6 +220,8 @@ constexpr int kWsNeeds = 30;
 // Word n-grams (which use the row arrays of term_rows as well): ng_tokens, the token total: 16 bytes of span record per token, in the
 // buffer the WordPiece calls keep theirs in; ng_rows > 0 (= n_str + 1): the gram counts and the row starts in key space; ng_keys:
 // the key total, which the n-gram call waits for before it sizes the two key buffers -- the term counts' own, one key per gram.
+// TF-IDF: tf_ctl, the error word of the CSR check; tf_ptr_bytes / tf_entries: the staging of a host caller's CSR (latok_idf_update_csr,
+// latok_tfidf_csr) -- its indptr in the caller's width, one int32 index and one 4-byte value per entry.
 constexpr int kTermRowArrays = 5;   // token counts, row starts, distinct counts, indptr, OOV counts
 struct WsShape {
     bool spans = false, feats = false, widen = false, join = false;
@@ -225,6 +229,8 @@ struct WsShape {
     int64_t term_rows = 0, term_tokens = 0;
     int64_t wp_tokens = 0, wp_pieces = 0;
     int64_t ng_tokens = 0, ng_rows = 0, ng_keys = 0;
+    bool tf_ctl = false;
+    int64_t tf_ptr_bytes = 0, tf_entries = 0;
 };
 // The one sizing rule of a workspace: every buffer a batch of `units` positions uses and its byte size.
 static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const WsShape& shape) {
@@ -264,7 +270,11 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const 
              {&w.ngrows, shape.ng_rows > 0 ? (size_t)shape.ng_rows * 8 * 2 : 0},
              {&w.wpcnt, shape.wp_tokens > 0 ? (size_t)(shape.wp_tokens + 1) * 8 : 0},
              {&w.wprank, shape.wp_tokens > 0 ? (size_t)(shape.wp_tokens + 1) * 8 : 0},
-             {&w.wpids, shape.wp_pieces > 0 ? (size_t)shape.wp_pieces * 4 : 0}}};
+             {&w.wpids, shape.wp_pieces > 0 ? (size_t)shape.wp_pieces * 4 : 0},
+             {&w.tfptr, (size_t)shape.tf_ptr_bytes},
+             {&w.tfidx, shape.tf_entries > 0 ? (size_t)shape.tf_entries * 4 + 16 : 0},
+             {&w.tfval, shape.tf_entries > 0 ? (size_t)shape.tf_entries * 4 + 16 : 0},
+             {&w.tfctl, shape.tf_ctl ? (size_t)64 : 0}}};
 }
 static int ws_ensure(const WsNeed* needs, int n) {
     for (int i = 0; i < n; ++i) {
@@ -666,6 +676,7 @@ struct BytesCall {
 };
 constexpr unsigned kClearPair = 0x3, kClearSized = 0xB, kClearBytesFeats = 0x1B;   // pinned words {0, 1}, {0, 1, 3}, {0, 1, 3, 4}
 constexpr unsigned kClearNgrams = 0x2B;                                               // {0, 1, 3, 5}
+constexpr unsigned kClearTfidfErr = 0x80;                                             // word 7: the error word of the TF-IDF tail
 
 // The end of a call whose payload has a size known only now (`n` items, read behind wait_totals): more than the caller's capacity
 // is refused with `need_fmt`; host pointers then get `n` items of every array (a NULL dst was not asked for) and a last wait.
@@ -2430,6 +2441,72 @@ int latok_token_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_of
     return token_words_common(utf8, byte_off, n_str, total_bytes, true, vocab, 0, unk_id, counts_out, spans_out, ids_out, cap, n_tokens_out, flags, stream);
 }
 
+/* TF-IDF (latok_idf_*, latok_tfidf_*; tfidf_kernels.hip, tfidf_weight.h).  The object: df and n_docs, and per smoothing mode the float32
+ * idf vector, computed by the first call that asks (k_idf_weights) and dropped by every update, load and clear.  A consumer on another
+ * stream than the one that computed the vector waits for its event on the device. */
+struct Idf {                       // latok_idf: mutable; calls on it are serialised by its own lock
+    std::mutex mu;
+    int device = -1;
+    int64_t n_cols = 0;            // (never changes)
+    int64_t n_docs = 0;
+    int32_t* d_df = nullptr;       // int32[n_cols]
+    float* d_idf[2] = {nullptr, nullptr};          // [smooth]: float[n_cols], allocated on first use
+    bool idf_valid[2] = {false, false};
+    hipEvent_t idf_ready[2] = {nullptr, nullptr};
+};
+static void idf_free(Idf* f) {
+    for (void* p : {(void*)f->d_df, (void*)f->d_idf[0], (void*)f->d_idf[1]})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t e : f->idf_ready)
+        if (e) (void)hipEventDestroy(e);
+    delete f;
+}
+static void idf_drop_weights(Idf& f) { f.idf_valid[0] = f.idf_valid[1] = false; }
+static int check_idf(const Ctx& g, const Idf& f) {
+    if (f.device != g.device) return fail(LATOK_ERR_INVALID, "the idf lives on device %d, the current context on device %d", f.device, g.device);
+    return LATOK_OK;
+}
+// the idf vector of one smoothing mode, valid on `st` (caller holds f.mu)
+static int idf_weights_on(Idf& f, bool smooth, hipStream_t st, const float** out) {
+    const int m = smooth ? 1 : 0;
+    if (!f.d_idf[m]) {
+        const hipError_t e = hipMalloc((void**)&f.d_idf[m], (size_t)f.n_cols * 4);
+        if (e != hipSuccess) {
+            f.d_idf[m] = nullptr;
+            return fail(LATOK_ERR_NOMEM, "hipMalloc of %lld idf weights failed: %s", (long long)f.n_cols, hipGetErrorString(e));
+        }
+    }
+    if (!f.idf_ready[m]) HIP_TRY(hipEventCreateWithFlags(&f.idf_ready[m], hipEventDisableTiming));
+    if (!f.idf_valid[m]) {
+        HIP_TRY(latok::launch_idf_weights(f.d_df, f.n_cols, f.n_docs, smooth, f.d_idf[m], st));
+        HIP_TRY(hipEventRecord(f.idf_ready[m], st));
+        f.idf_valid[m] = true;
+    } else {
+        HIP_TRY(hipStreamWaitEvent(st, f.idf_ready[m], 0));
+    }
+    *out = f.d_idf[m];
+    return LATOK_OK;
+}
+static int tfidf_check_opts(int opts) {
+    if (opts & ~kTwAllOpts) return fail(LATOK_ERR_INVALID, "unknown opts bit");
+    if ((opts & kTwNormL1) && (opts & kTwNormL2)) return fail(LATOK_ERR_INVALID, "LATOK_TFIDF_NORM_L1 and LATOK_TFIDF_NORM_L2 exclude each other");
+    return LATOK_OK;
+}
+static int csr_refusal(int err) {
+    if (err & latok::kCsrBadStart) return fail(LATOK_ERR_INVALID, "indptr[0] must be 0");
+    if (err & latok::kCsrBadOrder) return fail(LATOK_ERR_INVALID, "indptr must be non-decreasing");
+    if (err & latok::kCsrBadTotal) return fail(LATOK_ERR_INVALID, "indptr[n_rows] does not match nnz");
+    if (err & latok::kCsrBadColumn) return fail(LATOK_ERR_INVALID, "a column index lies outside [0, n_cols) of the idf");
+    return LATOK_OK;
+}
+static int g_df_add_cached = 1;   // latok_debug_set_df_add: 0 = the plain k_df_add_plain (tools/path_bench.py measures both)
+// what the TF-IDF entry points add to term_counts_common: the update of an idf (update) or the weighting of the rows
+struct TfidfTail {
+    Idf* idf;      // may be NULL (weighting without idf)
+    int opts;
+    bool update;
+};
+
 /* Per-string term counts of a UTF-8 batch in BYTE space (latok_term_counts_utf8_bytes_batch, latok_hashed_term_counts_utf8_bytes_batch):
  * the CSR rows of a document-term matrix.  One stream, every batch size the same kernels:
  *   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
@@ -2584,13 +2661,26 @@ struct NgramArgs {
     int min_n, max_n, sep;
     int64_t* n_grams_out;
 };
-// the four blocking entry points' shared body: the checks of the ids call, the capacity protocol in entries
+// the four blocking entry points' shared body: the checks of the ids call, the capacity protocol in entries.  tf: the TF-IDF entry
+// points -- behind the entries that launch_terms_emit wrote, the column check (vocabulary form with an idf), then the update of df
+// from the context's own buffers (tf->update: the caller has no output buffers) or the weighting of data in place; the error word
+// travels to pinned word 7 on the stream and is read behind the counts' own wait.
 static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
                               bool hashed, uint32_t seed, int64_t n_features, int alternate_sign, void* indptr_out, void* oov_out,
                               int32_t* indices_out, int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_tokens_out, int flags,
-                              void* stream, const NgramArgs* ng = nullptr) {
+                              void* stream, const NgramArgs* ng = nullptr, const TfidfTail* tf = nullptr) {
     LATOK_ENTER();
     if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    const bool upd = tf && tf->update;
+    Idf* const f = tf ? tf->idf : nullptr;
+    if (tf) {   // refused before any device work, with nothing written
+        int trc;
+        if (upd && (flags & LATOK_OUT_INT32)) return fail(LATOK_ERR_INVALID, "unknown flag");
+        if ((trc = tfidf_check_opts(tf->opts))) return trc;
+        if (upd && !f) return fail(LATOK_ERR_INVALID, "idf is NULL");
+        if (f && hashed && n_features != f->n_cols)
+            return fail(LATOK_ERR_INVALID, "n_features is %lld, the idf has %lld columns", (long long)n_features, (long long)f->n_cols);
+    }
     if (ng) {   // refused before any device work, with nothing written
         if (ng->min_n < 1) return fail(LATOK_ERR_INVALID, "min_n must be at least 1");
         if (ng->max_n < ng->min_n) return fail(LATOK_ERR_INVALID, "max_n must not be below min_n");
@@ -2603,19 +2693,31 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
     *nnz_out = 0;
     if (n_tokens_out) *n_tokens_out = 0;
     if (ng && ng->n_grams_out) *ng->n_grams_out = 0;
-    if (!indptr_out) return fail(LATOK_ERR_INVALID, "indptr_out is NULL");
+    if (!indptr_out && !upd) return fail(LATOK_ERR_INVALID, "indptr_out is NULL");
     if (cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
     if ((indices_out == nullptr) != (data_out == nullptr)) return fail(LATOK_ERR_INVALID, "indices_out and data_out go together: one of them is NULL");
     if (!indices_out && cap > 0) return fail(LATOK_ERR_INVALID, "indices_out and data_out are NULL but cap > 0 (a size query passes cap = 0)");
     if (hashed && (n_features < 1 || n_features > 0x7FFFFFFFll)) return fail(LATOK_ERR_INVALID, "n_features must be in 1 .. 2^31 - 1");
     const Vocab* v = nullptr;
     if (!hashed && (rc = check_object(g, vocab, "vocab is NULL", &v))) return rc;
+    std::unique_lock<std::mutex> idf_lock;
+    if (f) {
+        idf_lock = std::unique_lock<std::mutex>(f->mu);
+        if ((rc = check_idf(g, *f))) return rc;
+        if (upd && f->n_docs + std::max<int64_t>(n_str, 0) >= (1ll << 31))
+            return fail(LATOK_ERR_INVALID, "the idf would hold %lld documents: df is int32 (fewer than 2^31)", (long long)(f->n_docs + n_str));
+    }
     BytesCall c;   // (elt: the width of indptr and oov; an index and a count are 4 bytes in every mode)
     if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
     const bool dev = c.dev;
     const size_t elt = c.elt;
     const hipStream_t st = c.st;
     if (dev && ((uintptr_t)indptr_out & (elt - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    if (c.empty && upd) {   // rows without an entry: documents all the same
+        f->n_docs += n_str;
+        if (n_str > 0) idf_drop_weights(*f);
+        return LATOK_OK;
+    }
     if (c.empty) {   // no byte, no token: every row is empty
         if ((rc = zero_counts(dev, indptr_out, (size_t)(n_str + 1) * elt, st))) return rc;
         return zero_counts(dev, oov_out, (size_t)n_str * elt, st, true);
@@ -2624,7 +2726,8 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
         return fail(LATOK_ERR_INVALID, "misaligned output buffer");
     WsShape shape{.spans = true, .term_rows = n_str + 1};
     if (ng) shape.ng_rows = n_str + 1;
-    if ((rc = c.stage(g, ng ? (hashed ? 15 : 14) : (hashed ? 10 : 9), shape, ng ? kClearNgrams : kClearSized))) return rc;
+    shape.tf_ctl = tf != nullptr;
+    if ((rc = c.stage(g, ng ? (hashed ? 15 : 14) : (hashed ? 10 : 9), shape, (ng ? kClearNgrams : kClearSized) | (tf ? kClearTfidfErr : 0u)))) return rc;
     TermCounts a;
     a.b = c.d;
     a.vocab = v;
@@ -2636,18 +2739,19 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
     a.indices = indices_out;
     a.data = data_out;
     // (an entry has at least one token, a token one byte: the staging is sized by it; a token starts one gram of every order at most)
-    a.cap = indices_out ? std::min(cap, c.total * (ng ? ng->max_n - ng->min_n + 1 : 1)) : 0;
+    const int64_t most = c.total * (ng ? ng->max_n - ng->min_n + 1 : 1);
+    a.cap = upd ? most : indices_out ? std::min(cap, most) : 0;
     if (ng) {
         a.min_n = ng->min_n;
         a.max_n = ng->max_n;
         a.sep = ng->sep;
     }
     a.o32 = c.o32;
-    if (!dev) {
+    if (!dev || upd) {   // the outputs land in the context's own buffers
         if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 4 + 16)) ||
             (rc = g.counts.ensure((size_t)(2 * n_str + 2) * 8)))
             return rc;
-        if (indices_out) {
+        if (indices_out || upd) {
             a.indices = (int32_t*)g.h_aux.p;
             a.data = (int32_t*)g.h_out.p;
         }
@@ -2658,7 +2762,22 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
     a.h_tot = c.h_tot;
     a.st = st;
     if ((rc = ng ? enqueue_ngram_counts(g, g.ws, a) : enqueue_term_counts(g, g.ws, a))) return rc;
-    if (!dev) {   // valid whatever the capacity
+    if (tf && a.indices && (ng ? a.n_grams : a.n_tokens) > 0) {   // (no key: the scan did not run and nnz = 0)
+        const int64_t* d_indptr = (const int64_t*)g.ws.trows.p + 3 * (n_str + 1);   // the scan's own rows and total, as the enqueue left them
+        const int64_t* d_nnz = (const int64_t*)g.ws.scalar.p + 5;
+        int* d_err = (int*)g.ws.tfctl.p;
+        HIP_TRY(hipMemsetAsync(d_err, 0, 4, st));
+        if (f && !hashed) HIP_TRY(latok::launch_csr_check(false, nullptr, a.indices, n_str, 0, d_nnz, a.cap, f->n_cols, d_err, st));
+        if (upd) {
+            HIP_TRY(latok::launch_df_add(g_df_add_cached != 0, a.indices, 0, d_nnz, a.cap, d_err, f->d_df, st));
+        } else {
+            const float* weights = nullptr;
+            if (f && (rc = idf_weights_on(*f, (tf->opts & kTwSmoothIdf) != 0, st, &weights))) return rc;
+            HIP_TRY(latok::launch_tfidf_rows(false, d_indptr, a.indices, a.data, n_str, 0, d_nnz, a.cap, weights, tf->opts, d_err, (float*)a.data, st));
+        }
+        HIP_TRY(hipMemcpyAsync((void*)(c.h_tot + 7), d_err, 4, hipMemcpyDeviceToHost, st));
+    }
+    if (!dev && !upd) {   // valid whatever the capacity
         HIP_TRY(hipMemcpyAsync(indptr_out, a.indptr, (size_t)(n_str + 1) * elt, hipMemcpyDeviceToHost, st));
         if (oov_out) HIP_TRY(hipMemcpyAsync(oov_out, a.oov, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));
     }
@@ -2668,6 +2787,12 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
     if (ng && ng->n_grams_out) *ng->n_grams_out = a.n_grams;
     const int64_t nnz = c.h_tot[3];
     *nnz_out = nnz;
+    if (tf && c.h_tot[7]) return csr_refusal((int)c.h_tot[7]);
+    if (upd) {
+        f->n_docs += n_str;
+        idf_drop_weights(*f);
+        return LATOK_OK;
+    }
     return deliver_sized(c, nnz, cap, "capacity too small: need %lld entries", {{indices_out, a.indices, 4}, {data_out, a.data, 4}});   // (wait 3)
 }
 int latok_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
@@ -2696,6 +2821,292 @@ int latok_hashed_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t
                                               int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_tokens_out, int flags, void* stream) {
     return term_counts_common(utf8, byte_off, n_str, total_bytes, nullptr, true, seed, n_features, alternate_sign, indptr_out, nullptr, indices_out,
                               data_out, cap, nnz_out, n_tokens_out, flags, stream);
+}
+
+/* the TF-IDF entry points over text: term_counts_common with a tail (min_n = max_n = 1: the plain term counts' kernels) */
+static int tfidf_text_common(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab, bool hashed,
+                             uint32_t seed, int64_t n_features, int alternate_sign, int min_n, int max_n, int sep, const TfidfTail& tf,
+                             void* indptr_out, void* oov_out, int32_t* indices_out, float* data_out, int64_t cap, int64_t* nnz_out,
+                             int64_t* n_tokens_out, int flags, void* stream) {
+    const NgramArgs ng{min_n, max_n, sep, nullptr};
+    const bool plain = min_n == 1 && max_n == 1 && sep >= 0 && sep <= 255;   // (the n-gram route checks its arguments itself)
+    return term_counts_common(utf8, byte_off, n_str, total_bytes, vocab, hashed, seed, n_features, alternate_sign, indptr_out, oov_out, indices_out,
+                              (int32_t*)data_out, cap, nnz_out, n_tokens_out, flags, stream, plain ? nullptr : &ng, &tf);
+}
+int latok_tfidf_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab, int min_n,
+                                 int max_n, int sep, const latok_idf* idf, int opts, int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out,
+                                 float* data_out, int64_t cap, int64_t* nnz_out, int flags, void* stream) {
+    const TfidfTail tf{const_cast<Idf*>(reinterpret_cast<const Idf*>(idf)), opts, false};
+    return tfidf_text_common(utf8, byte_off, n_str, total_bytes, vocab, false, 0, 0, 0, min_n, max_n, sep, tf, indptr_out, oov_out, indices_out, data_out,
+                             cap, nnz_out, nullptr, flags, stream);
+}
+int latok_hashed_tfidf_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, uint32_t seed,
+                                        int64_t n_features, int alternate_sign, int min_n, int max_n, int sep, const latok_idf* idf, int opts,
+                                        int64_t* indptr_out, int32_t* indices_out, float* data_out, int64_t cap, int64_t* nnz_out, int flags,
+                                        void* stream) {
+    const TfidfTail tf{const_cast<Idf*>(reinterpret_cast<const Idf*>(idf)), opts, false};
+    return tfidf_text_common(utf8, byte_off, n_str, total_bytes, nullptr, true, seed, n_features, alternate_sign, min_n, max_n, sep, tf, indptr_out,
+                             nullptr, indices_out, data_out, cap, nnz_out, nullptr, flags, stream);
+}
+int latok_idf_update_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
+                                      uint32_t seed, int64_t n_features, int min_n, int max_n, int sep, latok_idf* idf, int64_t* nnz_out,
+                                      int64_t* n_tokens_out, int flags, void* stream) {
+    const TfidfTail tf{reinterpret_cast<Idf*>(idf), 0, true};
+    int64_t nnz = 0;
+    return tfidf_text_common(utf8, byte_off, n_str, total_bytes, vocab, vocab == nullptr, seed, n_features, 0, min_n, max_n, sep, tf, nullptr, nullptr,
+                             nullptr, nullptr, 0, nnz_out ? nnz_out : &nnz, n_tokens_out, flags, stream);
+}
+
+int latok_idf_create(int64_t n_cols, latok_idf** out) {
+    LATOK_ENTER();
+    if (!out) return fail(LATOK_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (n_cols < 1 || n_cols > (1ll << 28)) return fail(LATOK_ERR_INVALID, "n_cols must be in 1 .. 2^28");
+    int rc = need_init(g);
+    if (rc) return rc;
+    Idf* f = nullptr;
+    try {
+        f = new Idf();
+    } catch (const std::bad_alloc&) {
+        return fail(LATOK_ERR_NOMEM, "out of host memory");
+    }
+    f->device = g.device;
+    f->n_cols = n_cols;
+    hipError_t e = hipMalloc((void**)&f->d_df, (size_t)n_cols * 4);
+    if (e != hipSuccess) {
+        f->d_df = nullptr;
+        idf_free(f);
+        return fail(LATOK_ERR_NOMEM, "hipMalloc of %lld document frequencies failed: %s", (long long)n_cols, hipGetErrorString(e));
+    }
+    e = hipMemsetAsync(f->d_df, 0, (size_t)n_cols * 4, g.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
+    if (e != hipSuccess) {
+        idf_free(f);
+        return fail(LATOK_ERR_HIP, "clearing the document frequencies failed: %s", hipGetErrorString(e));
+    }
+    *out = reinterpret_cast<latok_idf*>(f);
+    return LATOK_OK;
+}
+
+int latok_idf_destroy(latok_idf* idf) {
+    LATOK_ENTER();
+    Idf* f = reinterpret_cast<Idf*>(idf);
+    if (!f) return LATOK_OK;
+    int rc = LATOK_OK;
+    if (g.inited) {   // the current context's own work: its stream and its flow; whatever they report, the object is freed
+        const hipError_t e = hipStreamSynchronize(g.stream);
+        rc = flow_drain(g);
+        if (e != hipSuccess) rc = fail(LATOK_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    }
+    { std::lock_guard<std::mutex> il(f->mu); }   // (a call of another context that still holds it has returned)
+    idf_free(f);
+    return rc;
+}
+
+int latok_idf_clear(latok_idf* idf) {
+    LATOK_ENTER();
+    Idf* f = reinterpret_cast<Idf*>(idf);
+    if (!f) return fail(LATOK_ERR_INVALID, "idf is NULL");
+    int rc = need_init(g);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> il(f->mu);
+    if ((rc = check_idf(g, *f))) return rc;
+    HIP_TRY(hipMemsetAsync(f->d_df, 0, (size_t)f->n_cols * 4, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    f->n_docs = 0;
+    idf_drop_weights(*f);
+    return LATOK_OK;
+}
+
+int latok_idf_info(const latok_idf* idf, int64_t* n_cols, int64_t* n_docs, int* device) {
+    Idf* f = const_cast<Idf*>(reinterpret_cast<const Idf*>(idf));
+    if (!f) return fail(LATOK_ERR_INVALID, "idf is NULL");
+    std::lock_guard<std::mutex> il(f->mu);
+    if (n_cols) *n_cols = f->n_cols;
+    if (n_docs) *n_docs = f->n_docs;
+    if (device) *device = f->device;
+    return LATOK_OK;
+}
+
+int latok_idf_read(const latok_idf* idf, int32_t* df_out, int64_t cap, int64_t* n_docs_out) {
+    LATOK_ENTER();
+    Idf* f = const_cast<Idf*>(reinterpret_cast<const Idf*>(idf));
+    if (!f) return fail(LATOK_ERR_INVALID, "idf is NULL");
+    if (n_docs_out) *n_docs_out = 0;
+    if (cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
+    if (cap > 0 && !df_out) return fail(LATOK_ERR_INVALID, "df_out is NULL but cap > 0 (a size query passes cap = 0)");
+    int rc = need_init(g);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> il(f->mu);
+    if ((rc = check_idf(g, *f))) return rc;
+    if (n_docs_out) *n_docs_out = f->n_docs;
+    if (cap == 0 && !df_out) return LATOK_OK;
+    if (cap < f->n_cols) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld columns", (long long)f->n_cols);
+    HIP_TRY(hipMemcpyAsync(df_out, f->d_df, (size_t)f->n_cols * 4, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return LATOK_OK;
+}
+
+int latok_idf_load(latok_idf* idf, const int32_t* df, int64_t n_docs) {
+    LATOK_ENTER();
+    Idf* f = reinterpret_cast<Idf*>(idf);
+    if (!f) return fail(LATOK_ERR_INVALID, "idf is NULL");
+    if (!df) return fail(LATOK_ERR_INVALID, "df is NULL");
+    if (n_docs < 0 || n_docs >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "n_docs must be in 0 .. 2^31 - 1");
+    int rc = need_init(g);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> il(f->mu);
+    if ((rc = check_idf(g, *f))) return rc;
+    for (int64_t c = 0; c < f->n_cols; ++c)
+        if (df[c] < 0 || (int64_t)df[c] > n_docs) return fail(LATOK_ERR_INVALID, "df[%lld] = %d lies outside [0, n_docs]", (long long)c, (int)df[c]);
+    HIP_TRY(hipMemcpyAsync(f->d_df, df, (size_t)f->n_cols * 4, hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    f->n_docs = n_docs;
+    idf_drop_weights(*f);
+    return LATOK_OK;
+}
+
+int latok_idf_weights(const latok_idf* idf, int smooth, float* out, int64_t cap) {
+    LATOK_ENTER();
+    Idf* f = const_cast<Idf*>(reinterpret_cast<const Idf*>(idf));
+    if (!f) return fail(LATOK_ERR_INVALID, "idf is NULL");
+    if (!out) return fail(LATOK_ERR_INVALID, "out is NULL");
+    int rc = need_init(g);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> il(f->mu);
+    if ((rc = check_idf(g, *f))) return rc;
+    if (cap < f->n_cols) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld columns", (long long)f->n_cols);
+    const float* w = nullptr;
+    if ((rc = idf_weights_on(*f, smooth != 0, g.stream, &w))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, w, (size_t)f->n_cols * 4, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return LATOK_OK;
+}
+
+// A caller's CSR for the device: device pointers as they are, host arrays copied into the workspace; then the check.  finish() waits
+// for the call's kernels and turns the error word into the refusal.
+struct CsrCall {
+    bool dev = false, o32 = false;
+    std::optional<StreamTurn> turn;
+    hipStream_t st = nullptr;
+    const void* indptr = nullptr;
+    const int32_t* indices = nullptr;
+    int32_t* data = nullptr;       // host callers: the staged copy, which the weighting overwrites in place
+    int* d_err = nullptr;
+    int open(Ctx& g, const void* indptr_in, const int32_t* indices_in, const int32_t* data_in, int64_t n_rows, int64_t nnz, int64_t n_cols, int flags,
+             void* stream) {
+        int rc;
+        dev = (flags & LATOK_DEVICE_PTRS) != 0;
+        o32 = (flags & LATOK_OUT_INT32) != 0;
+        const size_t elt = o32 ? 4 : 8;
+        if (dev && (((uintptr_t)indptr_in & (elt - 1)) != 0 || ((uintptr_t)indices_in & 3) != 0 || ((uintptr_t)data_in & 3) != 0))
+            return fail(LATOK_ERR_INVALID, "misaligned buffer");
+        turn.emplace(g, stream);
+        st = turn->st;
+        WsShape shape;
+        shape.tf_ctl = true;
+        if (!dev) {
+            shape.tf_ptr_bytes = (int64_t)((size_t)(n_rows + 1) * elt);
+            shape.tf_entries = nnz;
+        }
+        if ((rc = ws_ensure(ws_needs(g.ws, 0, shape).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+        indptr = indptr_in;
+        indices = indices_in;
+        data = const_cast<int32_t*>(data_in);
+        if (!dev) {
+            HIP_TRY(hipMemcpyAsync(g.ws.tfptr.p, indptr_in, (size_t)(n_rows + 1) * elt, hipMemcpyHostToDevice, st));
+            indptr = g.ws.tfptr.p;
+            if (nnz > 0) HIP_TRY(hipMemcpyAsync(g.ws.tfidx.p, indices_in, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+            indices = (const int32_t*)g.ws.tfidx.p;
+            if (data_in && nnz > 0) HIP_TRY(hipMemcpyAsync(g.ws.tfval.p, data_in, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+            data = (int32_t*)g.ws.tfval.p;
+        }
+        d_err = (int*)g.ws.tfctl.p;
+        HIP_TRY(hipMemsetAsync(d_err, 0, 4, st));
+        HIP_TRY(latok::launch_csr_check(o32, indptr, indices, n_rows, nnz, nullptr, 0, n_cols, d_err, st));
+        return LATOK_OK;
+    }
+    int finish(Ctx& g) {
+        volatile int64_t* h = (volatile int64_t*)g.pin_tot.h;
+        h[7] = 0;
+        HIP_TRY(hipMemcpyAsync((void*)(h + 7), d_err, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return csr_refusal((int)h[7]);
+    }
+};
+static int csr_args(const void* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int flags) {
+    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    if (n_rows < 0) return fail(LATOK_ERR_INVALID, "n_rows must be >= 0");
+    if (nnz < 0) return fail(LATOK_ERR_INVALID, "nnz must be >= 0");
+    if ((flags & LATOK_OUT_INT32) && (nnz > 0x7FFFFFFFll || n_rows >= 0x7FFFFFFFll)) return fail(LATOK_ERR_INVALID, "nnz does not fit an int32 indptr");
+    if (n_rows == 0 && nnz != 0) return fail(LATOK_ERR_INVALID, "indptr[n_rows] does not match nnz");
+    if (n_rows > 0 && !indptr) return fail(LATOK_ERR_INVALID, "indptr is NULL");
+    if (nnz > 0 && !indices) return fail(LATOK_ERR_INVALID, "indices is NULL");
+    return LATOK_OK;
+}
+
+int latok_idf_update_csr(latok_idf* idf, const void* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int flags, void* stream) {
+    LATOK_ENTER();
+    Idf* f = reinterpret_cast<Idf*>(idf);
+    if (!f) return fail(LATOK_ERR_INVALID, "idf is NULL");
+    int rc = csr_args(indptr, indices, n_rows, nnz, flags);
+    if (rc || (rc = need_init(g))) return rc;
+    std::lock_guard<std::mutex> il(f->mu);
+    if ((rc = check_idf(g, *f))) return rc;
+    if (f->n_docs + n_rows >= (1ll << 31))
+        return fail(LATOK_ERR_INVALID, "the idf would hold %lld documents: df is int32 (fewer than 2^31)", (long long)(f->n_docs + n_rows));
+    if (n_rows == 0) return LATOK_OK;
+    CsrCall c;
+    if ((rc = c.open(g, indptr, indices, nullptr, n_rows, nnz, f->n_cols, flags, stream))) return rc;
+    HIP_TRY(latok::launch_df_add(g_df_add_cached != 0, c.indices, nnz, nullptr, 0, c.d_err, f->d_df, c.st));
+    if ((rc = c.finish(g))) return rc;
+    f->n_docs += n_rows;
+    idf_drop_weights(*f);
+    return LATOK_OK;
+}
+
+int latok_tfidf_csr(const void* indptr, const int32_t* indices, const int32_t* data, int64_t n_rows, int64_t nnz, const latok_idf* idf, int opts,
+                    float* data_out, int flags, void* stream) {
+    LATOK_ENTER();
+    Idf* f = const_cast<Idf*>(reinterpret_cast<const Idf*>(idf));
+    int rc = csr_args(indptr, indices, n_rows, nnz, flags);
+    if (rc || (rc = tfidf_check_opts(opts))) return rc;
+    if (nnz > 0 && (!data || !data_out)) return fail(LATOK_ERR_INVALID, "data or data_out is NULL");
+    if ((rc = need_init(g))) return rc;
+    std::unique_lock<std::mutex> il;
+    if (f) {
+        il = std::unique_lock<std::mutex>(f->mu);
+        if ((rc = check_idf(g, *f))) return rc;
+    }
+    if (n_rows == 0) return LATOK_OK;
+    CsrCall c;
+    if ((flags & LATOK_DEVICE_PTRS) && ((uintptr_t)data_out & 3) != 0) return fail(LATOK_ERR_INVALID, "misaligned buffer");
+    if ((rc = c.open(g, indptr, indices, data, n_rows, nnz, f ? f->n_cols : 0, flags, stream))) return rc;
+    const float* weights = nullptr;
+    if (f && (rc = idf_weights_on(*f, (opts & kTwSmoothIdf) != 0, c.st, &weights))) return rc;
+    float* out = c.dev ? data_out : (float*)c.data;
+    HIP_TRY(latok::launch_tfidf_rows(c.o32, c.indptr, c.indices, c.data, n_rows, nnz, nullptr, 0, weights, opts, c.d_err, out, c.st));
+    if ((rc = c.finish(g))) return rc;
+    if (!c.dev && nnz > 0) {
+        HIP_TRY(hipMemcpyAsync(data_out, out, (size_t)nnz * 4, hipMemcpyDeviceToHost, c.st));
+        HIP_TRY(hipStreamSynchronize(c.st));
+    }
+    return LATOK_OK;
+}
+
+/* test hooks (not part of the ABI in include/latok_hip.h).  latok_debug_tfidf_limits: out[0] = kTfidfSubMax, the longest row that 16
+ * lanes take; out[1] = kTfidfWaveMax, the longest row that a wave takes (a longer one gets a workgroup of the second launch); out[2] =
+ * kDfSlots, the columns a workgroup of k_df_add caches.  latok_debug_set_df_add: 1 = k_df_add with its LDS table (the default), 0 = the
+ * plain form; returns the mode that was set before. */
+extern "C" int latok_debug_tfidf_limits(int64_t* out, int n) {
+    const int64_t v[3] = {latok::kTfidfSubMax, latok::kTfidfWaveMax, latok::kDfSlots};
+    for (int i = 0; i < n && i < 3; ++i) out[i] = v[i];
+    return 3;
+}
+extern "C" int latok_debug_set_df_add(int cached) {
+    const int before = g_df_add_cached;
+    g_df_add_cached = cached ? 1 : 0;
+    return before;
 }
 
 /* WordPiece in byte space (latok_wordpiece_ids_utf8_bytes_batch, latok_wordpiece_padded_utf8_bytes_batch): the subword ids of every

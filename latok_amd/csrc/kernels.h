@@ -384,6 +384,23 @@ hipError_t launch_ngram_rows(const int64_t* tok_cnt, int64_t n_str, int min_n, i
 hipError_t launch_ngram_keys(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
                              const int64_t* key_start, const int64_t* tok_spans, int64_t n_tok, int64_t n_keys, int min_n, int max_n, int sep,
                              const VocabTable* vt, uint32_t seed, uint32_t n_features, bool alternate_sign, uint64_t* keys, hipStream_t st);
+// tfidf_kernels.hip: TF-IDF on a CSR in device memory (tfidf_weight.h).  indptr is int32 (ip32) or int64; nnz_dev != NULL: the entry
+// count is the scan's own word, not yet read by the host -- the kernels then do nothing when it exceeds `cap`, what the buffers hold
+// (launch_terms_emit's rule), and `nnz` is ignored.  launch_csr_check ORs kCsrBad* bits into *err (indptr == NULL: the columns alone;
+// n_cols == 0: the indptr alone); the launches behind it return at once when *err is set.  launch_df_add: df[c] += 1 per entry, with the
+// workgroup's LDS table of kDfSlots hot columns (cached) or one global atomic per entry.  launch_tfidf_rows: out[j] = the weight of
+// entry j over its row's norm (idf == NULL: no idf; err == NULL: nothing was checked); out may be `data` itself.  A row of at most
+// kTfidfSubMax entries is taken by 16 lanes, one of at most kTfidfWaveMax by a wave, a longer one by a workgroup of a second launch
+// (latok_debug_tfidf_limits).
+constexpr int kTfidfSubMax = 64, kTfidfWaveMax = 1024, kDfSlots = 1024;
+constexpr int kCsrBadStart = 1, kCsrBadOrder = 2, kCsrBadTotal = 4, kCsrBadColumn = 8;
+hipError_t launch_csr_check(bool ip32, const void* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const int64_t* nnz_dev, int64_t cap,
+                            int64_t n_cols, int* err, hipStream_t st);
+hipError_t launch_df_add(bool cached, const int32_t* indices, int64_t nnz, const int64_t* nnz_dev, int64_t cap, const int* err, int32_t* df,
+                         hipStream_t st);
+hipError_t launch_idf_weights(const int32_t* df, int64_t n_cols, int64_t n_docs, bool smooth, float* idf, hipStream_t st);
+hipError_t launch_tfidf_rows(bool ip32, const void* indptr, const int32_t* indices, const int32_t* data, int64_t n_rows, int64_t nnz,
+                             const int64_t* nnz_dev, int64_t cap, const float* idf, int opts, const int* err, float* out, hipStream_t st);
 // the commit behind it: (a) the padded dwords of the fresh slots -> ctl[0]; (b) their bytes into the blob, resident words stored
 hipError_t launch_count_commit_sum(const CountTable& ct, hipStream_t st);
 hipError_t launch_count_commit_copy(const uint8_t* u8, const CountTable& ct, hipStream_t st);

@@ -48,6 +48,27 @@ __device__ __forceinline__ int wave_sum(int v) {
     return lane_read(v, 15) + lane_read(v, 31) + lane_read(v, 47) + lane_read(v, 63);
 }
 
+// float32 sum over every DPP row (16 lanes) of the wave, in every lane of the row: a butterfly of mirrors, so that each step adds
+// the same two values in both lanes of a pair (a + b = b + a bit for bit) and all 16 lanes end with the same bits.  The order of the
+// additions is fixed by the lane numbers inside the row alone.
+constexpr int kDppRowMirror = 0x140, kDppRowHalfMirror = 0x141, kDppQuadMirror = 0x1B, kDppQuadSwap = 0xB1;
+template <int CTRL>
+__device__ __forceinline__ float dpp_movf(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
+}
+__device__ __forceinline__ float row16_sum_f32(float v) {
+    v += dpp_movf<kDppRowMirror>(v);       // lane i with lane 15 - i
+    v += dpp_movf<kDppRowHalfMirror>(v);   // lane i with lane 7 - i of its half
+    v += dpp_movf<kDppQuadMirror>(v);      // lane i with lane 3 - i of its quad
+    v += dpp_movf<kDppQuadSwap>(v);        // lanes 0 <-> 1, 2 <-> 3
+    return v;
+}
+// ... and over the whole wave, wave-uniform: the four row sums in the fixed order (r0 + r1) + (r2 + r3)
+__device__ __forceinline__ float wave_sum_f32(float v) {
+    const int r = __float_as_int(row16_sum_f32(v));
+    return (__int_as_float(lane_read(r, 0)) + __int_as_float(lane_read(r, 16))) + (__int_as_float(lane_read(r, 32)) + __int_as_float(lane_read(r, 48)));
+}
+
 // inclusive prefix maximum over the 64 lanes of values >= `floor` (six DPP steps; the __shfl_up form is six dependent
 // ds_bpermute round trips through the LDS pipe, ~0.7 us per call at the occupancy of the featurize kernel)
 __device__ __forceinline__ int wave_scan_max(int v, int floor) {

@@ -45,6 +45,14 @@
                   range (1, 2) and the separator 0x20, everything else as bytes_terms32 / bytes_terms_hashed (the vocabulary of the ids
                   paths holds single tokens only, so every bigram's probe ends in a miss); capacity = twice the token bound; same
                   process run as bytes_terms32, bytes_terms_hashed and bytes_spans32
+  bytes_tfidf32 / bytes_tfidf_hashed   latok_tfidf_utf8_bytes_batch / latok_hashed_tfidf_utf8_bytes_batch with range (1, 1), L2, smooth
+                  idf and an idf fitted on the corpus by one update call; everything else as bytes_terms32 / bytes_terms_hashed -- run
+                  them in the same process: the ratio of the two times is what the weighting costs
+  bytes_df_update   latok_idf_update_utf8_bytes_batch (vocabulary form) into an idf that is cleared before every call
+  csr_tfidf / csr_df   latok_tfidf_csr / latok_idf_update_csr alone on the device-resident CSR that bytes_terms32's call has left;
+                  csr_df prints csr_df_cached and csr_df_plain: k_df_add with its LDS table and the plain form (latok_debug_set_df_add)
+  py_tfidf        batch.tfidf_utf8_batch end to end against batch.term_counts_utf8_batch plus scikit-learn's TfidfTransformer on the
+                  host (numpy where scikit-learn is absent)
   bytes_wp32 / bytes_wp_padded   latok_wordpiece_ids_utf8_bytes_batch (int32 indptr and spans, capacity = the token bound) /
                   latok_wordpiece_padded_utf8_bytes_batch ([n, 64] block with [CLS] / [SEP]) against a WordPiece vocabulary of the words
                   of the ids paths (--vocab all|half; no continuation words, so a token is one piece: with `all` its id, with `half`
@@ -410,6 +418,7 @@ def main():
     join_leg = [p for p in paths if p in ("bytes_join", "bytes_join_flow", "bytes_spans32", "bytes_spans32_flow", "bytes_hashes32",
                                           "bytes_hashes32_flow", "bytes_hashes_only", "bytes_hashes_only_flow", "bytes_ids32", "bytes_ids32_flow",
                                           "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "bytes_ngrams32", "bytes_ngrams_hashed", "py_terms",
+                                          "bytes_tfidf32", "bytes_tfidf_hashed", "bytes_df_update", "csr_tfidf", "csr_df", "py_tfidf",
                                           "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join", "bytes_wp32", "bytes_wp_padded", "py_wp",
                                           "bytes_fold", "bytes_fold_wp", "py_fold")]
     if join_leg:
@@ -483,6 +492,38 @@ def main():
                                                                      None, D32, None)
             return lib.latok_term_counts_utf8_bytes_batch(d_u8, d_boff, n, n8, corpus_vocab().handle, t_indptr, t_oov, h_a, h_b, cap, C.byref(nout),
                                                           None, D32, None)
+
+        # TF-IDF: the idf of the leg is fitted on the corpus itself by one update call; L2, smooth idf
+        TFIDF_OPTS = _lib.TFIDF_SMOOTH_IDF | _lib.TFIDF_NORM_L2
+        tfidf_box, tfidf_bufs = {}, []
+
+        def tfidf_idf(hashed, fitted=True):
+            """the fitted idf of the vocabulary / hashed form, or (fitted=False) an empty one of that size for the update legs"""
+            from latok_amd import batch
+            key = (hashed, fitted)
+            if key not in tfidf_box:
+                vh = None if hashed else corpus_vocab().handle
+                f = batch.Idf((1 << 20) if hashed else len(words_box[0]))
+                if fitted:
+                    _lib.check(lib.latok_idf_update_utf8_bytes_batch(d_u8, d_boff, n, n8, vh, SEED, (1 << 20) if hashed else 0, 1, 1, 32, f.handle,
+                                                                     C.byref(nout), None, D, None))
+                tfidf_box[key] = f
+            return tfidf_box[key]
+
+        def tfidf_blocking(hashed):
+            t_indptr, t_oov = terms_box
+            f = tfidf_idf(hashed)
+            if hashed:
+                return lib.latok_hashed_tfidf_utf8_bytes_batch(d_u8, d_boff, n, n8, SEED, 1 << 20, 1, 1, 1, 32, f.handle, TFIDF_OPTS, t_indptr, h_a, h_b,
+                                                               cap, C.byref(nout), D32, None)
+            return lib.latok_tfidf_utf8_bytes_batch(d_u8, d_boff, n, n8, corpus_vocab().handle, 1, 1, 32, f.handle, TFIDF_OPTS, t_indptr, t_oov, h_a,
+                                                    h_b, cap, C.byref(nout), D32, None)
+
+        def df_update_blocking():
+            f = tfidf_idf(False, fitted=False)
+            _lib.check(lib.latok_idf_clear(f.handle))   # (n_docs stays below 2^31 whatever --iters is)
+            return lib.latok_idf_update_utf8_bytes_batch(d_u8, d_boff, n, n8, corpus_vocab().handle, SEED, 0, 1, 1, 32, f.handle, C.byref(nout), None,
+                                                         D, None)
 
         note_g = ("as bytes_terms32 / bytes_terms_hashed with one key per unigram and bigram: 16 B/token span records written and read, the "
                   "bytes of every token read by the walks of two tokens; 8 B/gram keys written, read by the sort and written back; 4 B/string "
@@ -760,6 +801,84 @@ def main():
             elif name in ("bytes_terms32", "bytes_terms_hashed"):   # (items = nnz; the keys are sized by the token total)
                 hashed = name == "bytes_terms_hashed"
                 run(name, lambda: terms_blocking(hashed), lambda: n8 + csr + 4 * n + (0 if hashed else 4 * n) + 8 * nout.value, note_t)
+            elif name in ("bytes_tfidf32", "bytes_tfidf_hashed"):   # (items = nnz) the count call plus the weighting behind it, in place
+                hashed = name == "bytes_tfidf_hashed"
+                _lib.check(terms_blocking(hashed))
+                run(name, lambda: tfidf_blocking(hashed), lambda: n8 + csr + 4 * n + (0 if hashed else 4 * n) + 8 * nout.value + 12 * nout.value,
+                    note_t + "; then 8 B/entry read, 4 B/entry written and the idf gathered (L2, smooth idf, an idf fitted on the corpus)")
+            elif name == "bytes_df_update":   # (items = nnz) the count call into the context's own buffers plus k_csr_check and k_df_add
+                run(name, df_update_blocking, lambda: n8 + csr + 8 * nout.value + 8 * nout.value,
+                    note_t + "; then the indices read twice (check, df); timed with the latok_idf_clear in front of every call")
+            elif name in ("csr_tfidf", "csr_df"):   # on the device-resident CSR the count call has left: (t_indptr, h_a, h_b)
+                _lib.check(terms_blocking(False))
+                nnz = nout.value
+                t_indptr = terms_box[0]
+                if name == "csr_tfidf":
+                    if not tfidf_bufs:
+                        tfidf_bufs.append(lib.latok_dev_alloc(cap * 4 + 64))
+                    f, d_w = tfidf_idf(False), tfidf_bufs[0]
+                    run(name, lambda: lib.latok_tfidf_csr(t_indptr, h_a, h_b, n, nnz, f.handle, TFIDF_OPTS, d_w, D32, None),
+                        lambda: 12 * nnz + 8 * n, "4 B index + 4 B count read, 4 B weight written per entry; 2 x 4 B/row indptr; the idf gather, "
+                        "k_csr_check's pass over the indices and the call's one wait are not counted")
+                else:
+                    f = tfidf_idf(False, fitted=False)
+                    fn_mode = lib.latok_debug_set_df_add
+                    fn_mode.restype, fn_mode.argtypes = C.c_int, [C.c_int]
+                    for mode, label in ((1, "csr_df_cached"), (0, "csr_df_plain")):
+                        fn_mode(mode)
+
+                        def one():
+                            _lib.check(lib.latok_idf_clear(f.handle))
+                            return lib.latok_idf_update_csr(f.handle, t_indptr, h_a, n, nnz, D32, None)
+
+                        run(label, one, lambda: 8 * nnz + 4 * n, "the indices read twice (k_csr_check, k_df_add), 4 B/row indptr; one global "
+                            "atomic per entry (plain) or per occupied LDS slot (cached); timed with the latok_idf_clear in front of every call")
+                    fn_mode(1)
+            elif name == "py_tfidf":   # host blobs in, the CSR arrays out: the fused call against the count call plus the host transform
+                from latok_amd import batch
+                m = min(args.py_strings, n)
+                blob = u8[:int(boff[m])].tobytes()
+                blobs = [blob[int(a):int(b)] for a, b in zip(boff[:m], boff[1:m + 1])]
+                words = list(dict.fromkeys(t for row in batch.tokenize_utf8_batch(blobs) for t in row))
+                words = words[::2] if args.vocab == "half" else words
+                try:
+                    import scipy.sparse as sp
+                    from sklearn.feature_extraction.text import TfidfTransformer
+                    host_name = "py_term_counts_utf8_batch_then_TfidfTransformer"
+                except ImportError:
+                    sp = None
+                    host_name = "py_term_counts_utf8_batch_then_numpy"
+                with batch.Vocab(words, seed=SEED) as v, batch.Idf(len(words)) as f:
+                    f.update_utf8(blobs, vocab=v)
+                    df, n_docs = f.df().astype(np.float64), f.n_docs
+                    idf_vec = np.log((n_docs + 1.0) / (df + 1.0)) + 1.0
+                    tr = None
+                    if sp is not None:
+                        tr = TfidfTransformer()
+                        tr.idf_ = idf_vec
+
+                    def on_host():
+                        indptr, indices, data, oov = batch.term_counts_utf8_batch(blobs, v)
+                        if tr is not None:
+                            x = tr.transform(sp.csr_matrix((data.astype(np.float64), indices, indptr), shape=(m, len(words))))
+                            return indptr, indices, x.data.astype(np.float32), oov
+                        w = data * idf_vec[indices]
+                        norms = np.sqrt(np.add.reduceat(np.append(w * w, 0.0), np.minimum(indptr[:-1], w.size))) if w.size else np.zeros(m)
+                        norms = np.where(np.diff(indptr) > 0, norms, 1.0)
+                        return indptr, indices, (w / np.repeat(norms, np.diff(indptr))).astype(np.float32), oov
+
+                    routes = (("py_tfidf_utf8_batch", lambda: batch.tfidf_utf8_batch(blobs, v, f)), (host_name, on_host))
+                    a_, b_ = routes[0][1](), routes[1][1]()
+                    assert np.array_equal(a_[0], b_[0]) and np.array_equal(a_[1], b_[1]) and np.allclose(a_[2], b_[2], rtol=1e-5, atol=0)
+                    for r in range(args.repeat):
+                        for rname, fn in routes:
+                            t = time.perf_counter()
+                            got = fn()
+                            dt = time.perf_counter() - t
+                            print(json.dumps({"path": rname, "workload": args.workload, "strings": m, "utf8_bytes": len(blob), "vocab": args.vocab,
+                                              "words": len(words), "nnz": int(got[1].size), "ms_per_call": dt * 1e3, "utf8_GBps": len(blob) / dt / 1e9,
+                                              "note": "end to end in Python: list[bytes] in, (indptr, indices, data float32, oov) out, L2 and smooth "
+                                                      "idf, pack and host work included", "repeat": r}), flush=True)
             elif name in ("bytes_ngrams32", "bytes_ngrams_hashed"):   # (items = nnz; the keys are sized by the gram total)
                 hashed = name == "bytes_ngrams_hashed"
                 run(name, lambda: ngrams_blocking(hashed), lambda: n8 + csr + 4 * n + (0 if hashed else 4 * n) + 8 * nout.value, note_g)
@@ -878,7 +997,9 @@ def main():
             wp_box[0].close()
             for p_ in wp_box[1:]:
                 lib.latok_dev_free(p_)
-        for p_ in terms_box + ngrams_box:
+        for f_ in tfidf_box.values():
+            f_.close()
+        for p_ in terms_box + ngrams_box + tfidf_bufs:
             lib.latok_dev_free(p_)
         for p_ in jb:
             lib.latok_dev_free(p_)
