@@ -1408,18 +1408,24 @@ class TokenCounter:
         return dict(zip(self.STATS, map(int, st)))
 
     def items(self):
-        """(list[bytes], uint64 array): the words held and their counts, in no particular order"""
+        """(list[bytes], uint64 array): the words held and their counts, in no particular order.  One state of the counter: when another
+        thread's update lands between the size query and the read, the read reports the larger need and is made again with it."""
         h = self._open()
         n, nb = C.c_int64(0), C.c_int64(0)
         rc = self._lib.latok_counter_read(h, None, 0, None, None, 0, C.byref(n), C.byref(nb))   # the size query
-        if rc != _lib.OK and not (rc == _lib.ERR_INVALID and n.value > 0):
+        while True:
+            if rc != _lib.OK and not (rc == _lib.ERR_INVALID and n.value > 0):
+                _lib.check(rc)
+            if n.value == 0:
+                return [], np.zeros(0, np.uint64)
+            cap, bytes_cap = n.value, nb.value
+            words, off, counts = np.empty(bytes_cap, np.uint8), np.empty(cap + 1, np.int64), np.empty(cap, np.uint64)
+            rc = self._lib.latok_counter_read(h, _ptr(words), bytes_cap, _ptr(off), _ptr(counts), cap, C.byref(n), C.byref(nb))
+            if rc == _lib.ERR_INVALID and (n.value > cap or nb.value > bytes_cap):
+                continue                                      # the counter grew in between: again, with the sizes this read reported
             _lib.check(rc)
-        if n.value == 0:
-            return [], np.zeros(0, np.uint64)
-        words, off, counts = np.empty(nb.value, np.uint8), np.empty(n.value + 1, np.int64), np.empty(n.value, np.uint64)
-        _lib.check(self._lib.latok_counter_read(h, _ptr(words), nb.value, _ptr(off), _ptr(counts), n.value, C.byref(n), C.byref(nb)))
-        raw = words.tobytes()
-        return [raw[off[i]:off[i + 1]] for i in range(n.value)], counts
+            raw = words.tobytes()
+            return [raw[off[i]:off[i + 1]] for i in range(n.value)], counts[:n.value].copy()
 
     def most_common(self, n=None):
         """[(word bytes, count)] sorted by (-count, bytes): deterministic; the first ``n`` if given"""

@@ -1,0 +1,674 @@
+"""The threading contract of the device objects (include/latok_hip.h), under the serving pattern of INTEGRATION.md: several threads, each
+in a context of its own on ONE device, sharing the objects.
+
+  latok_vocab, latok_wordpiece   "any context of the same device may use it, concurrently"
+  latok_counter                  "calls on one counter are serialised by a lock inside it; two contexts of one device may share it"
+  latok_idf                      "calls on one object are serialised by a lock inside it", and the float32 idf vector it keeps per smoothing
+                                 mode, computed on one context's stream and handed to the others through an event, dropped by every
+                                 update, load and clear
+  latok_last_error               the message of the last failure ON THIS THREAD
+
+Every test has the same shape: at most 4 workers, each inside its own _lib.Context(device of the object), released together by a
+threading.Barrier; a fixed number of rounds; a worker that raises records the exception and breaks the barrier; the main thread joins with
+a timeout and raises the first error; the contexts are destroyed in a finally.
+
+The expected values are plain Python, computed before any thread starts and never by the library under load.  Every document is words
+joined by single spaces and tabs, the words hold nothing the default rules split on, so ``blob.split()`` is the tokenisation -- the spans
+call confirms that once, from one thread.  Then: ids are a dict lookup; term counts, word n-grams and the counter are collections.Counter
+over tokens and over sep.join windows; hashed columns are helpers/murmur3_ref.py under the key rule of the header; WordPiece is
+helpers/wordpiece_ref.py; fold is helpers/fold_ref.py; TF-IDF is helpers/tfidf_ref.py under the header's bound ((k + 16) * 2^-23 for a
+normalised row of k entries, 8 * 2^-23 without a norm); idf vectors are held to 2^-24 of their largest weight, as tests/test_gpu_tfidf.py
+holds them.  Which state of an idf a call saw is decided by helpers/shared_state.py (tests/test_shared_objects_host.py shows what that
+judge refuses).  Batch sizes change from round to round (60, 1500 and 300 strings of 0 .. 40 tokens), so that every context's workspaces
+and pinned buffers grow and are reused while the other contexts run; a row longer than kTermsRowMax tokens, a row of more than
+kTfidfWaveMax distinct entries, runs of empty strings and an all-OOV row sit in the rotation."""
+import collections
+import ctypes as C
+import functools
+import threading
+
+import numpy as np
+import pytest
+
+from helpers import fold_ref
+from helpers import shared_state as ss
+from helpers import tfidf_ref as ref
+from helpers import wordpiece_ref as wpr
+from helpers.murmur3_ref import murmur3_ref
+
+pytestmark = pytest.mark.gpu
+
+N_WORDS, IN_VOCAB, N_GRAM_WORDS = 3000, 2600, 300
+N_FEATURES, SEED = 1 << 12, 0
+SIZES = (60, 1500, 300)                  # strings per batch; round r of a worker takes batch r % 3: grow, reuse, shrink
+ROUNDS = 6                               # two turns through the sizes
+IDS_ROUTE, TERMS_ROUTE, HASHED_ROUTE, WP_ROUTE, WP_PADDED_ROUTE, NGRAM_ROUTE = 7, 9, 10, 11, 12, 14
+WP_UNK, WP_CLS, WP_SEP, WP_PAD, WP_LEN = 1, 2, 3, 0, 12
+BARRIER_S, JOIN_S = 60, 180
+
+
+def _word(i):
+    return bytes(97 + (i // 26 ** k) % 26 for k in (2, 1, 0)) + b"q"
+
+
+WORDS = [_word(i) for i in range(N_WORDS)]
+GRAMS = [WORDS[i] + b" " + WORDS[i + 1] for i in range(0, 2 * N_GRAM_WORDS, 2)]     # vocabulary words that hold the separator
+VOCAB_WORDS = WORDS[:IN_VOCAB] + GRAMS                                              # WORDS[IN_VOCAB:] are out of vocabulary
+VOCAB = {w: i for i, w in enumerate(VOCAB_WORDS)}
+LETTERS = range(97, 123)
+WP_WORDS = ([b"[PAD]", b"[UNK]", b"[CLS]", b"[SEP]"] + WORDS[:400] + [bytes([x, y]) for x in LETTERS for y in LETTERS if (x * 26 + y) % 5] +
+            [b"##" + bytes([y]) + b"q" for y in LETTERS if y % 4] + [b"##q"] + [b"##" + bytes([y]) for y in range(103, 110)])
+WP_DICT = wpr.vocab_dict(WP_WORDS)
+
+
+@functools.lru_cache(maxsize=1)
+def _limits():
+    """(kTermsRowMax, kTfidfWaveMax)"""
+    from latok_amd import _lib
+    lib = _lib.load()
+    out = np.zeros(4, np.int64)
+    for fn in (lib.latok_debug_tfidf_limits, lib.latok_debug_terms_limits):
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int]
+    assert lib.latok_debug_tfidf_limits(out.ctypes.data, 3) == 3
+    wave = int(out[1])
+    assert lib.latok_debug_terms_limits(out.ctypes.data, 2) == 2
+    row_max = int(out[1])
+    assert max(wave, row_max) + 8 < IN_VOCAB
+    return row_max, wave
+
+
+# ---- the runner every test uses -------------------------------------------------------------------------------------------------------
+def _run_workers(jobs, own_context=True, device=0):
+    """jobs[k](k, gate) on a thread of its own, inside a context of its own (or, own_context=False, on the default context); all are
+    released together by ``gate``, which a job may use again between its rounds"""
+    from latok_amd import _lib
+    errors = []
+    gate = threading.Barrier(len(jobs), timeout=BARRIER_S)
+    ctxs = [_lib.Context(device) for _ in jobs] if own_context else []
+
+    def run(k):
+        try:
+            if own_context:
+                with ctxs[k]:
+                    gate.wait()
+                    jobs[k](k, gate)
+            else:
+                gate.wait()
+                jobs[k](k, gate)
+        except BaseException as exc:   # noqa: BLE001 - reported to the main thread
+            errors.append(exc)
+            try:
+                gate.abort()
+            except Exception:
+                pass
+
+    ths = [threading.Thread(target=run, args=(k,)) for k in range(len(jobs))]
+    try:
+        for t in ths:
+            t.start()
+        for t in ths:
+            t.join(JOIN_S)
+        alive = [t.is_alive() for t in ths]
+    finally:
+        for ctx, t in zip(ctxs, ths):
+            if not t.is_alive():
+                ctx.destroy()
+    if errors:
+        raise errors[0]
+    assert not any(alive), "a worker did not finish"
+
+
+# ---- documents and their references ---------------------------------------------------------------------------------------------------
+def _join(words, rng):
+    """the words joined by single spaces and (one in four) tabs"""
+    if not words:
+        return b""
+    out = bytearray()
+    for w, tab in zip(words, rng.random(len(words)) < 0.25):
+        out += w
+        out.append(9 if tab else 32)
+    return bytes(out[:-1])
+
+
+def _doc(rng, n_tok, lo=0, hi=N_WORDS):
+    """n_tok words of WORDS[lo:hi], skewed to the low ones; every third is followed by its successor, so that the bigram words occur"""
+    idx = (rng.random(n_tok) ** 2 * (hi - lo)).astype(np.int64) + lo
+    idx[1::3] = np.minimum(idx[0::3][:idx[1::3].size] + 1, hi - 1)
+    return _join([WORDS[i] for i in idx], rng)
+
+
+def _specials(rng):
+    """the shapes that matter: a row of more than kTermsRowMax tokens (with repeats), a row of more than kTfidfWaveMax distinct entries, an
+    all-OOV row, a run of empty strings"""
+    row_max, wave = _limits()
+    return [_doc(rng, row_max + 7, 0, 300), _join([WORDS[i] for i in rng.permutation(wave + 9)], rng),
+            _join([WORDS[i] for i in rng.integers(IN_VOCAB, N_WORDS, 9)], rng), b"", b"", b"", b"", b""]
+
+
+def _docs(rng, n_str, special):
+    docs = [_doc(rng, int(k)) for k in rng.integers(0, 41, n_str)]
+    if special:
+        at = n_str // 3
+        docs[at:at] = _specials(rng)
+    return docs
+
+
+def _ref_spans(toks):
+    """counts and byte spans of the tokens of documents built by _join: one separator byte between two words, none at the ends"""
+    spans = []
+    for t in toks:
+        a = 0
+        for w in t:
+            spans.append((a, a + len(w)))
+            a += len(w) + 1
+    return np.array([len(t) for t in toks], np.int64), np.array(spans, np.int64).reshape(-1, 2)
+
+
+def _ref_csr(rows):
+    """rows of (key, value) pairs -> the canonical CSR: distinct keys ascending, values summed (a sum of 0 is kept)"""
+    indptr, indices, data = [0], [], []
+    for row in rows:
+        c = collections.Counter()
+        for key, v in row:
+            c[key] += v
+        for key in sorted(c):
+            indices.append(key)
+            data.append(c[key])
+        indptr.append(len(indices))
+    return np.array(indptr, np.int64), np.array(indices, np.int32), np.array(data, np.int32)
+
+
+def _ref_terms(toks, bigrams=False):
+    """(indptr, indices, data, oov) against VOCAB; with bigrams: the grams of orders 1 and 2, joined by one space"""
+    rows, oov = [], []
+    for t in toks:
+        grams = t + [a + b" " + b for a, b in zip(t, t[1:])] if bigrams else t
+        rows.append([(VOCAB[g], 1) for g in grams if g in VOCAB])
+        oov.append(len(grams) - len(rows[-1]))
+    return _ref_csr(rows) + (np.array(oov, np.int64),)
+
+
+@functools.lru_cache(maxsize=None)
+def _hash_key(word):
+    """(column, sign) of the header's key rule: h = MurmurHash3 as int32, column = |h| mod n_features, sign = -1 for h < 0"""
+    h = murmur3_ref(word, SEED)
+    h = h - (1 << 32) if h >= (1 << 31) else h
+    return abs(h) % N_FEATURES, (1 if h >= 0 else -1)
+
+
+def _ref_hashed(toks, alternate_sign=True):
+    return _ref_csr([[(_hash_key(w)[0], _hash_key(w)[1] if alternate_sign else 1) for w in t] for t in toks])
+
+
+@functools.lru_cache(maxsize=None)
+def _pieces(word):
+    return tuple(wpr.cut(word, WP_DICT, b"##", 100, WP_UNK))
+
+
+def _ref_wordpiece(toks):
+    """(indptr, ids, spans) and the padded block with its attention mask"""
+    indptr, ids, spans = [0], [], []
+    block = np.full((len(toks), WP_LEN), WP_PAD, np.int32)
+    mask = np.zeros((len(toks), WP_LEN), np.int32)
+    for s, t in enumerate(toks):
+        a, row = 0, []
+        for w in t:
+            for pid, p0, p1 in _pieces(w):
+                row.append(pid)
+                spans.append((a + p0, a + p1))
+            a += len(w) + 1
+        ids += row
+        indptr.append(len(ids))
+        cells = [WP_CLS] + row[:WP_LEN - 2] + [WP_SEP]
+        block[s, :len(cells)] = cells
+        mask[s, :len(cells)] = 1
+    return (np.array(indptr, np.int64), np.array(ids, np.int32), np.array(spans, np.int64).reshape(-1, 2)), (block, mask)
+
+
+def _upper(docs):
+    """upper-cased text; in every fifth document E carries an acute accent, which FOLD_UNCASED strips"""
+    return [d.upper().replace(b"E", "É".encode()) if i % 5 == 0 else d.upper() for i, d in enumerate(docs)]
+
+
+def _same(got, want, what):
+    assert len(got) == len(want), what
+    for i, (g, w) in enumerate(zip(got, want)):
+        if w is None:
+            assert g is None, (what, i)
+            continue
+        g, w = np.asarray(g), np.asarray(w)
+        assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w), (what, "array %d" % i, g.shape, w.shape)
+
+
+class Family:
+    """One call family on one batch: ``expect`` (Python, made before any thread starts) and ``check`` (the calls, held to it exactly)"""
+
+    def __init__(self, kind, docs):
+        from latok_amd import batch
+        self.kind, self.docs = kind, docs
+        self.u8, self.off = batch.pack_utf8(docs)
+        if kind == 3:
+            self.text = _upper(docs)
+            fu8, foff = fold_ref.fold_batch(*batch.pack_utf8(self.text), fold_ref.UNCASED)
+            raw = bytes(bytearray(fu8))
+            self.tok_text = [raw[int(a):int(b)] for a, b in zip(foff[:-1], foff[1:])]       # the tokens are those of the folded strings
+            assert self.tok_text != self.text and any(b"\xc3\x89" in t for t in self.text)
+        else:
+            self.text = self.tok_text = docs
+        toks = self.toks = [d.split() for d in self.tok_text]
+        self.spans = _ref_spans(toks)
+        if kind == 0:
+            ids = np.array([VOCAB.get(w, -1) for t in toks for w in t], np.int32)
+            self.expect = ((self.spans[0], ids, self.spans[1]), _ref_terms(toks))
+        elif kind == 1:
+            self.expect = (_ref_terms(toks, bigrams=True), _ref_hashed(toks))
+        elif kind == 2:
+            self.expect = _ref_wordpiece(toks)
+        else:
+            self.expect = ([np.array([VOCAB.get(w, -1) for w in t], np.int32) for t in toks], _ref_terms(toks))
+
+    def confirm_tokenisation(self):
+        """once, from one thread: the spans call cuts the text the tokens come from exactly where ``split()`` does"""
+        from latok_amd import batch
+        counts, spans = batch.token_spans_utf8_bytes_csr(*batch.pack_utf8(self.tok_text))
+        _same((counts, spans), self.spans, ("spans", self.kind))
+
+    def check(self, objects, route=None):
+        """the family's calls against ``expect``; route: the library's debug hook, asked where the context is the thread's own"""
+        from latok_amd import batch
+        vocab, wp = objects
+        if self.kind == 0:
+            _same(batch.token_ids_utf8_csr(self.u8, self.off, vocab, -1, spans=True), self.expect[0], "ids with spans")
+            assert route is None or route() == IDS_ROUTE
+            _same(batch.term_counts_utf8_csr(self.u8, self.off, vocab), self.expect[1], "term counts")
+            assert route is None or route() == TERMS_ROUTE
+        elif self.kind == 1:
+            _same(batch.term_counts_utf8_batch(self.docs, vocab, ngram_range=(1, 2)), self.expect[0], "n-gram counts (1, 2)")
+            assert route is None or route() == NGRAM_ROUTE
+            _same(batch.hashed_term_counts_utf8_batch(self.docs, N_FEATURES, SEED, alternate_sign=True), self.expect[1], "hashed term counts")
+            assert route is None or route() == HASHED_ROUTE
+        elif self.kind == 2:
+            _same(batch.wordpiece_ids_utf8_batch(self.docs, wp, WP_UNK), self.expect[0], "wordpiece ids")
+            assert route is None or route() == WP_ROUTE
+            _same(batch.wordpiece_encode_utf8_batch(self.docs, wp, WP_LEN, WP_CLS, WP_SEP, WP_PAD, WP_UNK), self.expect[1], "wordpiece padded")
+            assert route is None or route() == WP_PADDED_ROUTE
+        else:
+            _same(batch.token_ids_utf8_batch(self.text, vocab, -1, fold=batch.FOLD_UNCASED), self.expect[0], "folded ids")
+            assert route is None or route() == IDS_ROUTE
+            _same(batch.term_counts_utf8_batch(self.text, vocab, fold=batch.FOLD_UNCASED), self.expect[1], "folded term counts")
+            assert route is None or route() == TERMS_ROUTE
+
+
+@pytest.fixture(scope="module")
+def shared(gpu):
+    """the two immutable objects and, per family, its three batches with their references (made once, never changed)"""
+    from latok_amd import batch
+    rng = np.random.default_rng(20240)
+    families = [[Family(k, _docs(rng, n, special=(n == SIZES[2]))) for n in SIZES] for k in range(4)]
+    for fam in families:
+        for f in fam:
+            f.confirm_tokenisation()
+    row_max, wave = _limits()
+    long_terms = families[0][2].expect[1]
+    assert families[0][2].spans[0].max() > row_max and (families[0][2].spans[0] == 0).sum() >= 5   # a row of more than kTermsRowMax tokens,
+    assert np.diff(long_terms[0]).max() > wave and (long_terms[3] > 0).any()                       # one of more than kTfidfWaveMax entries,
+    assert ((np.diff(long_terms[0]) == 0) & (long_terms[3] > 0)).any()                             # an all-OOV row
+    assert len(families[1][1].expect[0][1]) and (families[1][1].expect[0][1] >= IN_VOCAB).any()    # bigram words are found
+    assert (families[1][1].expect[1][2] < 0).any() and (families[2][1].expect[0][1] == WP_UNK).any()
+    with batch.Vocab(VOCAB_WORDS) as vocab, batch.WordPiece(WP_WORDS) as wp:
+        yield (vocab, wp), families
+
+
+def _device_of(gpu):
+    return gpu.latok_ctx_device(None)
+
+
+def test_immutable_objects_serve_four_contexts_with_different_families_at_once(gpu, shared):
+    """latok_vocab / latok_wordpiece: "any context of the same device may use it, concurrently".  Worker k runs family k -- 0: ids with
+    spans and term counts; 1: word n-grams (1, 2) and hashed counts with alternate_sign; 2: WordPiece CSR and padded; 3: fold chained in
+    front of ids and term counts, on upper-cased text -- ROUNDS times, on batches of changing size; every array equals the reference."""
+    objects, families = shared
+
+    def job(k, gate):
+        for r in range(ROUNDS):
+            families[k][r % len(SIZES)].check(objects, route=gpu.latok_debug_last_route)
+
+    _run_workers([job] * 4, device=_device_of(gpu))
+    assert gpu.latok_ctx_get_current() is None
+    for k in range(4):                                               # the default context, from this thread: the same answers
+        families[k][2].check(objects, route=gpu.latok_debug_last_route)
+
+
+def test_three_threads_share_the_default_context_with_different_families(gpu, shared):
+    """the same calls where the CONTEXT is shared: its lock serialises the threads, and a call's staging, workspaces and pinned words are
+    not touched by the call of another thread that runs in between"""
+    objects, families = shared
+
+    def job(k, gate):
+        for r in range(3):
+            families[(0, 2, 3)[k]][r % len(SIZES)].check(objects)
+
+    _run_workers([job] * 3, own_context=False)
+
+
+# ---- the counter ----------------------------------------------------------------------------------------------------------------------
+COUNTER_MAX_BYTES = 6
+
+
+def _counter_corpus():
+    """[worker][round] -> documents over 1200 short words (5 bytes) and 150 long ones (9 bytes, beyond max_word_bytes)"""
+    rng = np.random.default_rng(77)
+    short = [bytes(97 + (i // 26 ** k) % 26 for k in (2, 1, 0)) + b"cw" for i in range(1200)]
+    long_ = [w[:3] + b"toolong" for w in short[:150]]
+    words = short + long_
+    slices = []
+    for k in range(4):
+        slices.append([])
+        for r in range(ROUNDS):
+            docs = [_join([words[i] for i in (rng.random(int(n)) ** 2 * len(words)).astype(np.int64)], rng) for n in rng.integers(0, 31, 150 + 60 * r)]
+            docs[5:5] = [b""] * 3
+            slices[k].append(docs)
+    return slices
+
+
+def test_counter_shared_by_four_contexts_counts_exactly(gpu):
+    """latok_counter: "calls on one counter are serialised by a lock inside it; two contexts of one device may share it".  Four contexts
+    update one counter with disjoint slices, host pointers and LATOK_DEVICE_PTRS in turn, and read it between their rounds."""
+    from latok_amd import _lib, batch
+    slices = _counter_corpus()
+    per_slice = [[collections.Counter(w for d in docs for w in d.split()) for docs in rounds] for rounds in slices]
+    total = sum((c for rounds in per_slice for c in rounds), collections.Counter())
+    want = collections.Counter({w: c for w, c in total.items() if len(w) <= COUNTER_MAX_BYTES})
+    want_long = sum(c for w, c in total.items() if len(w) > COUNTER_MAX_BYTES)
+    max_words = 2048
+    assert 0 < want_long and len(want) <= max_words and len(want) > 1000
+    Family(0, slices[0][0]).confirm_tokenisation()
+    snapshots = [[] for _ in slices]
+
+    with batch.TokenCounter(max_words, COUNTER_MAX_BYTES) as tc:
+        def job(k, gate):
+            lib = _lib.load()
+            own = collections.Counter()
+            for r, docs in enumerate(slices[k]):
+                mine = per_slice[k][r]
+                if (k + r) % 2 == 0:
+                    st = tc.update_utf8(docs)
+                else:
+                    u8, off = batch.pack_utf8(docs)
+                    d_u8, d_off = lib.latok_dev_alloc(u8.nbytes + 256), lib.latok_dev_alloc(off.nbytes)
+                    try:
+                        assert d_u8 and d_off and d_u8 % 16 == 0
+                        _lib.check(lib.latok_memset_dev(d_u8, 0, u8.nbytes + 256))
+                        _lib.check(lib.latok_memcpy_h2d(d_u8, u8.ctypes.data, u8.nbytes))
+                        _lib.check(lib.latok_memcpy_h2d(d_off, off.ctypes.data, off.nbytes))
+                        _lib.check(lib.latok_sync())
+                        out = np.full(4, -7, np.int64)
+                        _lib.check(lib.latok_count_tokens_utf8_bytes_batch(d_u8, d_off, len(docs), -1, tc.handle, out.ctypes.data, _lib.DEVICE_PTRS, None))
+                        st = dict(zip(tc.STATS[:4], map(int, out)))
+                    finally:
+                        lib.latok_dev_free(d_u8)
+                        lib.latok_dev_free(d_off)
+                n_long = sum(c for w, c in mine.items() if len(w) > COUNTER_MAX_BYTES)
+                assert st == dict(tokens=sum(mine.values()), counted=sum(mine.values()) - n_long, long=n_long, dropped=0), (k, r, st)
+                own += mine
+                snap = tc.stats
+                words, counts = tc.items()
+                snapshots[k].append((snap, dict(zip(words, map(int, counts))), len(words), sum(own.values())))
+
+        _run_workers([job] * 4, device=_device_of(gpu))
+        for k, snaps in enumerate(snapshots):                        # every snapshot is one state of the counter
+            assert len(snaps) == ROUNDS
+            own = collections.Counter()
+            for r, (snap, held, n_listed, own_tokens) in enumerate(snaps):
+                own += per_slice[k][r]
+                assert snap["tokens"] == snap["counted"] + snap["long"] + snap["dropped"] and snap["dropped"] == 0, (k, r, snap)
+                assert own_tokens <= snap["tokens"] <= sum(total.values()) and (r == 0 or snap["tokens"] >= snaps[r - 1][0]["tokens"]), (k, r, snap)
+                assert len(held) == n_listed, "a word sits in two slots"
+                assert all(c <= want.get(w, 0) for w, c in held.items()), (k, r, [w for w, c in held.items() if c > want.get(w, 0)][:5])
+                assert all(held.get(w, 0) >= c for w, c in own.items() if len(w) <= COUNTER_MAX_BYTES), (k, r)   # its own updates are in
+                assert sum(held.values()) >= snap["counted"] and len(held) >= snap["distinct"]                   # (items() came after stats)
+        st = tc.stats
+        assert st == dict(tokens=sum(total.values()), counted=sum(want.values()), long=want_long, dropped=0, distinct=len(want)), st
+        words, counts = tc.items()
+        assert len(set(words)) == len(words) and dict(zip(words, map(int, counts))) == dict(want)
+        ranked = [w for w, _ in tc.most_common()]
+        assert ranked == [w for w, _ in sorted(want.items(), key=lambda wc: (-wc[1], wc[0]))]
+        with tc.to_vocab() as v:                                      # the round trip: a held word's id is its rank, a long word has none
+            a_long = next(w for w in total if len(w) > COUNTER_MAX_BYTES)
+            ids = batch.token_ids_utf8_batch([b" ".join(ranked), a_long + b"\t" + ranked[7]], v)
+            assert ids[0].tolist() == list(range(len(ranked))) and ids[1].tolist() == [-1, 7]
+
+
+# ---- the idf --------------------------------------------------------------------------------------------------------------------------
+def _idf_slices(rng, n_workers, n_rounds):
+    slices = [[_docs(rng, 120 + 40 * r, special=(k == 1 and r == 1)) for r in range(n_rounds)] for k in range(n_workers)]
+    slices[0][0][3:3] = [b"", b"\t", b" "]
+    return slices
+
+
+@pytest.mark.parametrize("form", ["vocabulary", "hashed"])
+def test_idf_updates_from_three_contexts_add_up(gpu, shared, form):
+    """latok_idf: "calls on one object are serialised by a lock inside it".  Three contexts update one idf with disjoint slices through
+    update_utf8 on text, update_csr with int64 indptr and update_csr with int32 indptr, each worker every route once; df is the reference's
+    document frequency over all slices and n_docs counts every string, the empty ones included."""
+    from latok_amd import batch
+    (vocab, _), _ = shared
+    hashed = form == "hashed"
+    n_cols = N_FEATURES if hashed else len(VOCAB_WORDS)
+    rng = np.random.default_rng(5 + hashed)
+    slices = _idf_slices(rng, 3, 3)
+    rows = [[(_ref_hashed if hashed else _ref_terms)([d.split() for d in docs]) for docs in rounds] for rounds in slices]
+    want_df = sum(ref.document_frequency(c[1], n_cols) for rounds in rows for c in rounds)
+    n_docs = sum(len(docs) for rounds in slices for docs in rounds)
+    assert want_df.max() > 1 and (want_df == 0).any() and any(d.strip() == b"" for d in slices[0][0])
+
+    with batch.Idf(n_cols) as idf:
+        def job(k, gate):
+            seen = 0
+            for r, docs in enumerate(slices[k]):
+                indptr, indices = rows[k][r][:2]
+                route = (k + r) % 3
+                if route == 0:
+                    nnz = idf.update_utf8(docs, n_features=N_FEATURES, seed=SEED) if hashed else idf.update_utf8(docs, vocab=vocab)
+                    assert nnz == indices.size, (k, r, nnz, indices.size)
+                else:
+                    idf.update_csr(indptr if route == 1 else indptr.astype(np.int32), indices)
+                seen += len(docs)
+                assert seen <= idf.n_docs <= n_docs
+
+        _run_workers([job] * 3, device=_device_of(gpu))
+        got = idf.df()
+        assert idf.n_docs == n_docs
+        assert np.array_equal(got, want_df), np.flatnonzero(got != want_df)[:8]
+
+
+def _tfidf_batch(rng):
+    """the batch the idf tests transform, with the reference's counts"""
+    docs = _docs(rng, 200, special=True)
+    counts = _ref_terms([d.split() for d in docs])
+    return docs, counts
+
+
+CALLS = [("text", True), ("csr", False), ("weights", True), ("text", False), ("csr", True), ("weights", False)]     # (call, smooth_idf)
+
+
+def _tfidf_call(call, smooth, docs, counts, vocab, idf):
+    from latok_amd import batch
+    if call == "text":
+        got = batch.tfidf_utf8_batch(docs, vocab, idf, smooth, False, "l2")
+        _same((got[0], got[1], got[3]), (counts[0], counts[1], counts[3]), "the rows of the fused call")
+        return got[2]
+    if call == "csr":
+        return batch.tfidf_csr(counts[0], counts[1], counts[2], idf, smooth, False, "l2")
+    return idf.weights(smooth)
+
+
+def _cold_start(gpu, idf, vocab, docs, counts, df, n_docs):
+    """one invalidation of the cached vectors, then four contexts at once; returns the largest error over its bound"""
+    idf.load(df, n_docs)                                              # drops both cached vectors
+    results = [dict() for _ in range(4)]
+
+    def job(k, gate):
+        for i in range(len(CALLS)):
+            call, smooth = CALLS[(i + (0, 3, 1, 4)[k]) % len(CALLS)]    # the first arrivals ask for different modes through different calls
+            results[k][(call, smooth)] = _tfidf_call(call, smooth, docs, counts, vocab, idf)
+
+    _run_workers([job] * 4, device=_device_of(gpu))
+    worst = 0.0
+    for call, smooth in CALLS:
+        vec = ref.idf(df, n_docs, smooth)
+        mine = _tfidf_call(call, smooth, docs, counts, vocab, idf)    # the main thread, afterwards, on the default context
+        for k in range(4):
+            got = results[k][(call, smooth)]
+            assert got.dtype == np.float32
+            if call == "weights":
+                assert ss.match_vector(got, [vec]) == 0, (k, call, smooth)
+            else:
+                w, i = ref.worst(got, ref.weigh(counts[0], counts[1], counts[2], vec, False, "l2"), counts[0], "l2")
+                assert w <= 1, (k, call, smooth, "entry %d, %.2f of the bound" % (i, w))
+                worst = max(worst, w)
+            assert np.array_equal(got.view(np.uint32), mine.view(np.uint32)), (k, call, smooth, "bits differ from the main thread's")
+    for smooth in (True, False):                                      # the fused call is tfidf_csr on the counts, bit for bit
+        assert np.array_equal(results[0][("text", smooth)].view(np.uint32), results[3][("csr", smooth)].view(np.uint32))
+    return worst
+
+
+def test_idf_cached_vector_under_a_cold_concurrent_start(gpu, shared):
+    """The float32 idf vector is computed once per smoothing mode by the first call that asks, on ITS stream; a call of another context
+    waits for that vector's event.  After a load() has dropped both vectors, four contexts ask at once, for both modes in different
+    orders, through the fused text call, tfidf_csr and weights().  Every result lies within the header's bound of the reference and has
+    the bits the main thread gets afterwards ("a row's output bits depend on that row alone").  Two invalidations, with different df
+    and n_docs: a vector that survived the second load would miss the second reference."""
+    from latok_amd import batch
+    (vocab, _), _ = shared
+    rng = np.random.default_rng(404)
+    docs, counts = _tfidf_batch(rng)
+    n_cols = len(VOCAB_WORDS)
+    assert np.diff(counts[0]).max() > _limits()[1]
+    fit = [_ref_terms([d.split() for d in _docs(rng, n, special=False)]) for n in (300, 500)]
+    states = [(ref.document_frequency(fit[0][1], n_cols), 300),
+              (ref.document_frequency(fit[0][1], n_cols) + ref.document_frequency(fit[1][1], n_cols), 800)]
+    both = [ref.idf(df, n, True) for df, n in states]
+    assert ss.assert_vectors_separable(both) >= 64                   # the two loads cannot be taken for one another
+    with batch.Idf(n_cols) as idf:
+        first = _cold_start(gpu, idf, vocab, docs, counts, *states[0])
+        second = _cold_start(gpu, idf, vocab, docs, counts, *states[1])
+        print("cold start: worst error %.2f and %.2f of the bound" % (first, second))
+
+
+def test_every_transform_sees_one_whole_state_of_the_idf(gpu):
+    """One updater takes an idf through J = 6 updates that each double n_docs, over columns the probe rows do not hold (df of the probe
+    columns stands still while k_df_add runs); three readers transform the probe batch meanwhile, with and without the L2 norm, in both
+    smoothing modes, and read weights().  Every output lies within the bound of exactly one of the J + 1 references, as a whole; in round
+    r, between the barrier behind update r - 1 and the one behind update r, that state is r or r + 1; a reader's states never go backwards;
+    behind the last update every reader sees state J."""
+    from latok_amd import batch
+    corpus = ss.StateCorpus()
+    J = corpus.n_updates
+    words = WORDS[:corpus.n_cols]
+    modes = [(True, None), (True, "l2"), (False, None), (False, "l2")]
+    indptr, indices, data = corpus.csr
+    # on the CPU, before any device work: the states can be told apart
+    expected = {m: corpus.expected(*m) for m in modes}
+    margins = {m: ss.assert_separable(expected[m], indptr, m[1]) for m in modes}
+    vectors = {s: corpus.idf_vectors(s) for s in (True, False)}
+    vec_margin = min(ss.assert_vectors_separable(vectors[s]) for s in (True, False))
+    print("separation: %s; idf vectors %.0f bounds" % (", ".join("%r %.0f" % (m, v) for m, v in margins.items()), vec_margin))
+    rng = np.random.default_rng(1)
+    spell = lambda docs: [_join([words[c] for c in doc], rng) for doc in docs]      # noqa: E731
+    probe, base, updates = spell(corpus.probe), spell(corpus.base), [spell(u) for u in corpus.updates]
+    update_csr = [ss.rows_csr(u)[:2] for u in corpus.updates]
+    Family(0, probe + updates[0]).confirm_tokenisation()
+    reader_calls = [modes[0], modes[1], "weights", modes[2], modes[3]]
+    seen = [[] for _ in range(3)]
+
+    with batch.Vocab(words) as vocab, batch.Idf(corpus.n_cols) as idf:
+        assert idf.update_utf8(base, vocab=vocab) == ss.rows_csr(corpus.base)[1].size
+        assert np.array_equal(idf.df(), corpus.df[0]) and idf.n_docs == corpus.n_docs[0]
+        got = batch.term_counts_utf8_batch(probe, vocab)
+        _same(got[:3], corpus.csr, "the probe rows")
+        assert not got[3].any()
+
+        def observe(call, n_call):
+            if call == "weights":
+                smooth = n_call % 2 == 0
+                return ss.match_vector(idf.weights(smooth), vectors[smooth])
+            smooth, norm = call
+            out = batch.tfidf_utf8_batch(probe, vocab, idf, smooth, False, norm)
+            _same((out[0], out[1]), (indptr, indices), "the probe rows under load")
+            return ss.match_state(out[2], expected[call], indptr, norm)
+
+        def updater(k, gate):
+            for j in range(J):
+                if j % 3 == 0:
+                    assert idf.update_utf8(updates[j], vocab=vocab) == update_csr[j][1].size
+                else:
+                    idf.update_csr(update_csr[j][0] if j % 3 == 1 else update_csr[j][0].astype(np.int32), update_csr[j][1])
+                gate.wait()                                            # update j has returned
+
+        def reader(k, gate):
+            n_call = 0
+            for r in range(J):
+                for i in range(len(reader_calls)):
+                    call = reader_calls[(i + k) % len(reader_calls)]
+                    seen[k - 1].append(ss.check_window(observe(call, n_call), r, r + 1))
+                    n_call += 1
+                gate.wait()
+            for call in reader_calls:                                  # behind the last update: state J, whatever is asked
+                seen[k - 1].append(ss.check_window(observe(call, n_call), J, J))
+                n_call += 1
+
+        _run_workers([updater, reader, reader, reader], device=_device_of(gpu))
+        for states in seen:
+            assert len(states) == (J + 1) * len(reader_calls)
+            ss.check_order(states)
+        assert np.array_equal(idf.df(), corpus.df[J]) and idf.n_docs == corpus.n_docs[J]
+        print("states seen per reader: %s" % [sorted(set(s)) for s in seen])
+
+
+# ---- the error text -------------------------------------------------------------------------------------------------------------------
+THEIR_TEXTS = ("unknown opts bit", "max_n must not exceed", "n_features must be in", "the idf has")
+
+
+def test_the_error_text_is_the_threads_own(gpu, shared):
+    """latok_last_error: "message of the last failure on this thread".  Two workers run exact calls while a third provokes argument
+    refusals only -- an unknown opts bit, max_n = 9, n_features = 0, a hashed n_features that is not n_cols: all refused before any device
+    work -- and reads its own message each time; the other two never see a word of it."""
+    from latok_amd import _lib, batch
+    objects, families = shared
+    vocab = objects[0]
+    lib = _lib.load()
+    u8, off = families[0][0].u8, families[0][0].off
+    n_str, total = off.size - 1, int(off[-1])
+    indptr, indices, data = (np.ascontiguousarray(a) for a in families[0][0].expect[1][:3])
+    n_cols = 64
+    rounds = 3
+
+    with batch.Idf(n_cols) as idf:
+        def exact(k, gate):
+            for r in range(rounds):
+                families[(0, 2)[k]][r % 2].check(objects, route=gpu.latok_debug_last_route)
+                text = _lib.last_error()
+                assert not any(t in text for t in THEIR_TEXTS), (k, r, text)
+
+        def refused(k, gate):
+            out_ptr, nnz = np.full(n_str + 1, -7, np.int64), C.c_int64(-7)
+            out = np.full(data.size, 7.0, np.float32)
+            for r in range(rounds * 8):
+                rc = lib.latok_tfidf_csr(indptr.ctypes.data, indices.ctypes.data, data.ctypes.data, n_str, data.size, None, 16, out.ctypes.data, 0, None)
+                assert rc == _lib.ERR_INVALID and _lib.last_error() == "unknown opts bit"
+                rc = lib.latok_ngram_counts_utf8_bytes_batch(u8.ctypes.data, off.ctypes.data, n_str, total, vocab.handle, 1, 9, 32, out_ptr.ctypes.data,
+                                                             None, None, None, 0, C.byref(nnz), None, 0, None)
+                assert rc == _lib.ERR_INVALID and _lib.last_error() == "max_n must not exceed 8"
+                rc = lib.latok_hashed_term_counts_utf8_bytes_batch(u8.ctypes.data, off.ctypes.data, n_str, total, SEED, 0, 1, out_ptr.ctypes.data, None,
+                                                                   None, 0, C.byref(nnz), None, 0, None)
+                assert rc == _lib.ERR_INVALID and _lib.last_error() == "n_features must be in 1 .. 2^31 - 1"
+                rc = lib.latok_idf_update_utf8_bytes_batch(u8.ctypes.data, off.ctypes.data, n_str, total, None, SEED, n_cols + 1, 1, 1, 32, idf.handle,
+                                                           C.byref(nnz), None, 0, None)
+                assert rc == _lib.ERR_INVALID and _lib.last_error() == "n_features is %d, the idf has %d columns" % (n_cols + 1, n_cols)
+                with pytest.raises(ValueError, match="the idf has %d columns" % n_cols):
+                    idf.update_utf8(families[0][0].docs, n_features=n_cols + 1)
+            assert (out == 7.0).all() and (out_ptr == -7).all()           # nothing was written
+
+        _run_workers([exact, exact, refused], device=_device_of(gpu))
+        assert idf.n_docs == 0 and not idf.df().any()
