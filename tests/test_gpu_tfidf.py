@@ -294,7 +294,7 @@ def test_hot_column_and_both_forms_of_df_add(gpu):
             lib.latok_debug_set_df_add(cached)
             with batch.Idf(n + 1) as idf:
                 idf.update_csr(indptr, indices)
-                idf.update_csr(indptr[:-3], indices[3:-3])                               # a misaligned start, an odd length
+                idf.update_csr(indptr[:-3], indices[3:-3])                               # an odd length (host arrays are staged: an aligned start)
                 assert np.array_equal(idf.df(), want + np.bincount(indices[3:-3], minlength=n + 1)) and idf.n_docs == 2 * n - 3
     finally:
         lib.latok_debug_set_df_add(1)
