@@ -265,7 +265,7 @@ int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
  * word_off that is not non-decreasing from 0, n_words >= 2^31, words that take 2^32 bytes or more once each is padded to 4, NULL
  * outputs.  The object is immutable afterwards: any context of the same device may use it, concurrently; a call whose current
  * context sits on another device returns LATOK_ERR_INVALID.  latok_vocab_destroy drains the current context (its stream and its
- * flow) before it frees; as with latok_ctx_destroy, every OTHER context must be done with the object.  latok_vocab_info reports
+ * flow) before it frees -- whatever they report, the object is freed --; as with latok_ctx_destroy, every OTHER context must be done with the object.  latok_vocab_info reports
  * the word count as given, the slot count of the table (a power of two, >= 2 V and >= 64), the seed and the device; any output
  * pointer may be NULL. */
 typedef struct latok_vocab latok_vocab;
@@ -467,7 +467,8 @@ int latok_hashed_tfidf_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
  *   spans_out[2 r], spans_out[2 r + 1]    = its byte range, relative to its string's first byte (may be NULL)
  * latok_wordpiece_create takes HOST pointers as latok_vocab_create does and refuses, before any device work, what that call refuses
  * and a prefix_len outside 0 .. 8 or a max_chars outside 1 .. 1024.  The object may be used by any context of its device,
- * concurrently; latok_wordpiece_destroy drains the current context first, like latok_vocab_destroy.  latok_wordpiece_info reports the
+ * concurrently; latok_wordpiece_destroy drains the current context first, like latok_vocab_destroy: whatever its stream and
+ * its flow report, the object is freed.  latok_wordpiece_info reports the
  * word count as given, the slots and the longest word of both tables, the prefix (8 bytes are written), max_chars, the seed and the
  * device; any output pointer may be NULL.
  * The calls follow the term-counts call: host pointers or LATOK_DEVICE_PTRS (device UTF-8 pointer 16-byte aligned), total_bytes =

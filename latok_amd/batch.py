@@ -568,6 +568,77 @@ class _DeviceFolded:
         return False
 
 
+def _size_then_fill(call, n, alloc):
+    """The capacity protocol of the sized calls.  ``call()`` is the size query (no buffer, cap = 0): it reports its need into ``n``, a
+    c_int64, and may refuse the capacity.  ``alloc(need)`` then makes the payload buffers -- numpy arrays, ``_DeviceFolded.alloc``
+    pointers or None -- and ``call(*buffers, need)`` fills them, unless nothing is needed.  Returns (need, buffers)."""
+    rc = call()
+    if rc != _lib.OK and not (rc == _lib.ERR_INVALID and n.value > 0):
+        _lib.check(rc)
+    need = n.value
+    bufs = alloc(need)
+    if need > 0:
+        _lib.check(call(*[_ptr(b) if isinstance(b, np.ndarray) else b for b in bufs], need))
+    return need, bufs
+
+
+class _DeviceObject:
+    """What Vocab, WordPiece, Idf and TokenCounter share: ``handle`` (None once closed) of an object that ``_lib`` made and its call
+    named ``_destroy`` frees -- by ``close()``, on leaving a ``with`` block, or with the object.  ``_closed``: what ``_open()`` says."""
+
+    handle = _destroy = _closed = None
+
+    def _open(self):
+        if not self.handle:
+            raise ValueError(self._closed)
+        return self.handle
+
+    def close(self):
+        if self.handle:
+            h, self.handle = self.handle, None
+            _lib.check(getattr(self._lib, self._destroy)(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _handle_of(cls, obj, name, or_none=False):
+    """the handle of an open ``cls`` passed as argument ``name``; None for None where the call takes that"""
+    if obj is None and or_none:
+        return None
+    if not isinstance(obj, cls) or not obj.handle:
+        raise ValueError("%s must be an open latok_amd.batch.%s%s" % (name, cls.__name__, " or None" if or_none else ""))
+    return obj.handle
+
+
+def _int32_each(values, n, name, per):
+    """``values`` as int32[n]; anything but one integer per ``per`` that fits int32 is a ValueError"""
+    raw = np.asarray(values)
+    if raw.shape != (n,) or (raw.size and raw.dtype.kind not in "iu"):
+        raise ValueError("%s must be one integer per %s" % (name, per))
+    if raw.size and (raw.min() < -0x80000000 or raw.max() > 0x7FFFFFFF):
+        raise ValueError("%s must fit int32" % name)
+    return np.ascontiguousarray(raw, np.int32)
+
+
+def _pack_words(words, ids):
+    """the words of a Vocab or WordPiece (``bytes``, or ``str`` as UTF-8 with surrogatepass) and their optional ids ->
+    (data uint8[total], off int64[n + 1], ids int32[n] or None)"""
+    blobs = [w.encode("utf-8", "surrogatepass") if isinstance(w, str) else bytes(w) for w in words]
+    data, off = pack_utf8(blobs)
+    return data, off, None if ids is None else _int32_each(ids, len(blobs), "ids", "word")
+
+
 # token hashes: one 32-bit id per token (MurmurHash3 x86_32 of its UTF-8 bytes) -- what hashing vectorizers and hashed tables take
 def murmur3_32(data: bytes, seed=0) -> int:
     """MurmurHash3 x86_32 of ``data`` (bytes) with a 32-bit ``seed``, as an unsigned int: the word the device gives for a token with
@@ -650,33 +721,23 @@ def _unk32(unk_id) -> int:
     raise ValueError("unk_id must be an int in -2**31 .. 2**31 - 1")
 
 
-class Vocab:
+class Vocab(_DeviceObject):
     """A vocabulary on the device of the current context (``latok_vocab_create``): ``words`` is a list of ``bytes`` or ``str``
     (``str`` is encoded as UTF-8 with surrogatepass), ``ids`` an optional int32 per word (default: its index), ``seed`` the 32-bit
     seed of the table's hash.  Of a duplicate word the first wins; the empty word never matches.  Immutable; ``len()`` is the
     number of words given, ``.n_slots`` the size of the table.  Freed by ``close()``, on leaving a ``with`` block, or with the
     object."""
 
+    _destroy, _closed = "latok_vocab_destroy", "vocab must be an open latok_amd.batch.Vocab"
+
     def __init__(self, words, ids=None, seed=0):
-        self.handle = None
         seed = _seed32(seed)
-        blobs = [w.encode("utf-8", "surrogatepass") if isinstance(w, str) else bytes(w) for w in words]
-        off = np.zeros(len(blobs) + 1, np.int64)
-        if blobs:
-            np.cumsum([len(b) for b in blobs], out=off[1:])
-        data = np.frombuffer(b"".join(blobs), np.uint8)
-        if ids is not None:
-            raw = np.asarray(ids)
-            if raw.shape != (len(blobs),) or (raw.size and raw.dtype.kind not in "iu"):
-                raise ValueError("ids must be one integer per word")
-            if raw.size and (raw.min() < -0x80000000 or raw.max() > 0x7FFFFFFF):
-                raise ValueError("ids must fit int32")
-            ids = np.ascontiguousarray(raw, np.int32)
+        data, off, ids = _pack_words(words, ids)
         lib = _lib.ensure_init()
         h = C.c_void_p()
-        _lib.check(lib.latok_vocab_create(_ptr(data) if data.size else None, _ptr(off), len(blobs), _ptr(ids) if ids is not None else None,
+        _lib.check(lib.latok_vocab_create(_ptr(data) if data.size else None, _ptr(off), off.size - 1, _ptr(ids) if ids is not None else None,
                                           seed, C.byref(h)))
-        self._lib, self.handle, self.seed, self._n = lib, h, seed, len(blobs)
+        self._lib, self.handle, self.seed, self._n = lib, h, seed, off.size - 1
         n_slots = C.c_int64(0)
         _lib.check(lib.latok_vocab_info(h, None, C.byref(n_slots), None, None))
         self.n_slots = n_slots.value
@@ -684,36 +745,12 @@ class Vocab:
     def __len__(self):
         return self._n
 
-    def close(self):
-        if self.handle:
-            h, self.handle = self.handle, None
-            _lib.check(self._lib.latok_vocab_destroy(h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _vocab_handle(vocab):
-    if not isinstance(vocab, Vocab) or not vocab.handle:
-        raise ValueError("vocab must be an open latok_amd.batch.Vocab")
-    return vocab.handle
-
 
 def _ids_csr(utf8, byte_off, vocab, unk_id, dtype, want_spans):
     utf8, byte_off = _csr_u8(utf8, byte_off)
     unk_id = _unk32(unk_id)
     dt, flags = _out_dtype(dtype)
-    handle = _vocab_handle(vocab)
+    handle = _handle_of(Vocab, vocab, "vocab")
     n_str = byte_off.size - 1
     total = int(byte_off[-1]) if n_str > 0 else 0
     lib = _lib.ensure_init()
@@ -738,7 +775,7 @@ def token_ids_utf8_csr(utf8, byte_off, vocab, unk_id=-1, dtype=np.int64, spans=F
 
 def _ids_csr_folded(utf8, byte_off, vocab, unk_id, fold):
     """_ids_csr (int64, no spans) of the batch folded on the device"""
-    handle = _vocab_handle(vocab)
+    handle = _handle_of(Vocab, vocab, "vocab")
     with _DeviceFolded(utf8, byte_off, fold) as d:
         cap = max(d.total, 1)
         counts, ids = d.alloc(d.n_str * 8), d.alloc(cap * 4)
@@ -752,7 +789,7 @@ def token_ids_utf8_batch(blobs, vocab, unk_id=-1, fold=0):
     """list[bytes] (UTF-8) -> list of int32 arrays: the ids of every string's tokens ('' and whitespace-only -> empty).  ``fold``
     (FOLD_* flags): the batch is folded on the device first (fold_utf8_batch) and the tokens are those of the folded strings."""
     unk_id, fold = _unk32(unk_id), _fold_bits(fold)
-    _vocab_handle(vocab)
+    _handle_of(Vocab, vocab, "vocab")
     if len(blobs) == 0:
         return []
     utf8, byte_off = pack_utf8(blobs)
@@ -813,18 +850,12 @@ def _terms_csr_folded(utf8, byte_off, vocab, hashed, fold, ng=None):
         oov = None if hashed else d.alloc(n_str * 8)
         nnz = C.c_int64(0)
 
-        def call(indices, data, cap):
+        def call(indices=None, data=None, cap=0):
             return _terms_call(lib, ng, hashed, d.u8, d.off, n_str, d.total, vocab, indptr, oov, indices, data, cap, nnz, _lib.DEVICE_PTRS)
 
-        rc = call(None, None, 0)
-        if rc != _lib.OK and not (rc == _lib.ERR_INVALID and nnz.value > 0):
-            _lib.check(rc)
-        need = nnz.value
-        if need > 0:
-            indices, data = d.alloc(need * 4), d.alloc(need * 4)
-            _lib.check(call(indices, data, need))
-        return (d.fetch(indptr, n_str + 1, np.int64), d.fetch(indices, need, np.int32) if need else np.empty(0, np.int32),
-                d.fetch(data, need, np.int32) if need else np.empty(0, np.int32), None if hashed else d.fetch(oov, n_str, np.int64))
+        need, (indices, data) = _size_then_fill(call, nnz, lambda k: (d.alloc(k * 4), d.alloc(k * 4)))
+        return (d.fetch(indptr, n_str + 1, np.int64), d.fetch(indices, need, np.int32), d.fetch(data, need, np.int32),
+                None if hashed else d.fetch(oov, n_str, np.int64))
 
 
 def _terms_csr(utf8, byte_off, vocab, hashed, dtype, ng=None):
@@ -838,16 +869,11 @@ def _terms_csr(utf8, byte_off, vocab, hashed, dtype, ng=None):
     oov = None if hashed else np.zeros(n_str, dt)
     nnz = C.c_int64(0)
 
-    def call(indices, data, cap):
+    def call(indices=None, data=None, cap=0):
         return _terms_call(lib, ng, hashed, _ptr(utf8), _ptr(byte_off), n_str, total, vocab, _ptr(indptr), None if hashed else _ptr(oov), indices,
                            data, cap, nnz, flags)
 
-    rc = call(None, None, 0)
-    if rc != _lib.OK and not (rc == _lib.ERR_INVALID and nnz.value > 0):
-        _lib.check(rc)
-    indices, data = np.empty(nnz.value, np.int32), np.empty(nnz.value, np.int32)
-    if nnz.value > 0:
-        _lib.check(call(_ptr(indices), _ptr(data), nnz.value))
+    _, (indices, data) = _size_then_fill(call, nnz, lambda k: (np.empty(k, np.int32), np.empty(k, np.int32)))
     return indptr, indices, data, oov
 
 
@@ -861,7 +887,7 @@ def term_counts_utf8_csr(utf8, byte_off, vocab, dtype=np.int64, ngram_range=(1, 
     in the range, looked up or hashed as one term -- scikit-learn's ``ngram_range`` (``latok_ngram_counts_utf8_bytes_batch`` /
     ``latok_hashed_ngram_counts_utf8_bytes_batch``); (1, 1) takes the plain calls.
     A vocabulary word may hold the separator (``b"new york"``)."""
-    return _terms_csr(utf8, byte_off, _vocab_handle(vocab), None, dtype, _ngram_spec(ngram_range, sep))
+    return _terms_csr(utf8, byte_off, _handle_of(Vocab, vocab, "vocab"), None, dtype, _ngram_spec(ngram_range, sep))
 
 
 def term_counts_utf8_batch(blobs, vocab, fold=0, ngram_range=(1, 1), sep=b" "):
@@ -869,7 +895,7 @@ def term_counts_utf8_batch(blobs, vocab, fold=0, ngram_range=(1, 1), sep=b" "):
     ``fold`` (FOLD_* flags): the batch is folded on the device first (fold_utf8_batch) -- ``CountVectorizer(lowercase=True)`` is
     ``FOLD_LOWER``, ``strip_accents="unicode"`` adds ``FOLD_STRIP_MARKS``.  ``ngram_range``, ``sep``: as in term_counts_utf8_csr; the
     grams are those of the folded strings."""
-    handle, fold, ng = _vocab_handle(vocab), _fold_bits(fold), _ngram_spec(ngram_range, sep)
+    handle, fold, ng = _handle_of(Vocab, vocab, "vocab"), _fold_bits(fold), _ngram_spec(ngram_range, sep)
     utf8, byte_off = pack_utf8(blobs)
     if fold:
         return _terms_csr_folded(utf8, byte_off, handle, None, fold, ng)
@@ -937,25 +963,21 @@ def _csr_arrays(indptr, indices, data=None):
     return indptr, indices, data, flags
 
 
-class Idf:
+class Idf(_DeviceObject):
     """Document frequencies on the device of the current context (``latok_idf_create``): ``df[n_cols]`` -- in how many rows a column
     was stored -- and ``n_docs``, accumulated over any number of batches; ``weights()`` is the idf vector ``ln((n_docs + s) / (df + s)) +
     1`` (s = 1 if smooth), float32, what ``TfidfTransformer.idf_`` holds after ``fit``.  ``df()`` hands a caller what ``min_df`` /
     ``max_df`` pruning needs.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
 
+    _destroy, _closed = "latok_idf_destroy", "the idf is closed"
+
     def __init__(self, n_cols):
-        self.handle = None
         if not isinstance(n_cols, (int, np.integer)) or isinstance(n_cols, bool):
             raise ValueError("n_cols must be an int in 1 .. 2**28")
         lib = _lib.ensure_init()
         h = C.c_void_p()
         _lib.check(lib.latok_idf_create(int(n_cols), C.byref(h)))
         self._lib, self.handle, self.n_cols = lib, h, int(n_cols)
-
-    def _open(self):
-        if not self.handle:
-            raise ValueError("the idf is closed")
-        return self.handle
 
     def update_csr(self, indptr, indices):
         """df[c] += 1 for every stored entry of the CSR (explicit zeros count), n_docs += n_rows: ``np.bincount(indices)``"""
@@ -969,7 +991,7 @@ class Idf:
         visit the host.  Returns nnz, the entries the batch stored."""
         if (vocab is None) == (n_features is None):
             raise ValueError("exactly one of vocab and n_features must be given")
-        handle = None if vocab is None else _vocab_handle(vocab)
+        handle = None if vocab is None else _handle_of(Vocab, vocab, "vocab")
         n_feat, seed = (0 if n_features is None else _n_features31(n_features)), _seed32(seed)
         fold, ng = _fold_bits(fold), _ngram_spec(ngram_range, sep) or (1, 1, _sep_byte(sep))
         h, nnz = self._open(), C.c_int64(0)
@@ -1009,49 +1031,18 @@ class Idf:
 
     def load(self, df, n_docs):
         """set df and n_docs, for an idf that was fitted elsewhere (or summed over devices); every df[c] must lie in [0, n_docs]"""
-        raw = np.asarray(df)
-        if raw.shape != (self.n_cols,) or raw.dtype.kind not in "iu":
-            raise ValueError("df must be one integer per column")
-        if raw.size and (raw.min() < -0x80000000 or raw.max() > 0x7FFFFFFF):
-            raise ValueError("df must fit int32")
-        raw = np.ascontiguousarray(raw, np.int32)
+        raw = _int32_each(df, self.n_cols, "df", "column")
         _lib.check(self._lib.latok_idf_load(self._open(), _ptr(raw), int(n_docs)))
 
     def clear(self):
         _lib.check(self._lib.latok_idf_clear(self._open()))
-
-    def close(self):
-        if self.handle:
-            h, self.handle = self.handle, None
-            _lib.check(self._lib.latok_idf_destroy(h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _idf_handle(idf):
-    if idf is None:
-        return None
-    if not isinstance(idf, Idf) or not idf.handle:
-        raise ValueError("idf must be an open latok_amd.batch.Idf or None")
-    return idf.handle
 
 
 def tfidf_csr(indptr, indices, data, idf=None, smooth_idf=True, sublinear_tf=False, norm="l2"):
     """float32[nnz]: ``TfidfTransformer(norm, use_idf=idf is not None, smooth_idf, sublinear_tf).transform`` of the int32 CSR, weighted
     on the device (``latok_tfidf_csr``): tf (or sign(t)(1 + ln|t|)) times ``idf.weights(smooth_idf)``, over the row's L2 / L1 norm.  A
     row's output bits depend on that row alone."""
-    opts, handle = _tfidf_opts(smooth_idf, sublinear_tf, norm), _idf_handle(idf)
+    opts, handle = _tfidf_opts(smooth_idf, sublinear_tf, norm), _handle_of(Idf, idf, "idf", True)
     indptr, indices, data, flags = _csr_arrays(indptr, indices, data)
     out = np.empty(data.size, np.float32)
     lib = _lib.ensure_init()
@@ -1078,19 +1069,13 @@ def _tfidf_rows(utf8, byte_off, vocab, hashed, idf, opts, fold, ng, dtype):
             n_str = d.n_str
             indptr, oov = d.alloc((n_str + 1) * dt.itemsize), None if hashed else d.alloc(n_str * dt.itemsize)
 
-            def call(indices, data, cap):
+            def call(indices=None, data=None, cap=0):
                 return _tfidf_call(d.lib, hashed, d.u8, d.off, n_str, d.total, vocab, ng, idf, opts, indptr, oov, indices, data, cap, nnz,
                                    flags | _lib.DEVICE_PTRS)
 
-            rc = call(None, None, 0)
-            if rc != _lib.OK and not (rc == _lib.ERR_INVALID and nnz.value > 0):
-                _lib.check(rc)
-            need = nnz.value
-            if need > 0:
-                indices, data = d.alloc(need * 4), d.alloc(need * 4)
-                _lib.check(call(indices, data, need))
-            return (d.fetch(indptr, n_str + 1, dt), d.fetch(indices, need, np.int32) if need else np.empty(0, np.int32),
-                    d.fetch(data, need, np.float32) if need else np.empty(0, np.float32), None if hashed else d.fetch(oov, n_str, dt))
+            need, (indices, data) = _size_then_fill(call, nnz, lambda k: (d.alloc(k * 4), d.alloc(k * 4)))
+            return (d.fetch(indptr, n_str + 1, dt), d.fetch(indices, need, np.int32), d.fetch(data, need, np.float32),
+                    None if hashed else d.fetch(oov, n_str, dt))
     utf8, byte_off = _csr_u8(utf8, byte_off)
     n_str = byte_off.size - 1
     total = int(byte_off[-1]) if n_str > 0 else 0
@@ -1098,16 +1083,11 @@ def _tfidf_rows(utf8, byte_off, vocab, hashed, idf, opts, fold, ng, dtype):
     indptr = np.zeros(n_str + 1, dt)
     oov = None if hashed else np.zeros(n_str, dt)
 
-    def call(indices, data, cap):
+    def call(indices=None, data=None, cap=0):
         return _tfidf_call(lib, hashed, _ptr(utf8), _ptr(byte_off), n_str, total, vocab, ng, idf, opts, _ptr(indptr),
                            None if hashed else _ptr(oov), indices, data, cap, nnz, flags)
 
-    rc = call(None, None, 0)
-    if rc != _lib.OK and not (rc == _lib.ERR_INVALID and nnz.value > 0):
-        _lib.check(rc)
-    indices, data = np.empty(nnz.value, np.int32), np.empty(nnz.value, np.float32)
-    if nnz.value > 0:
-        _lib.check(call(_ptr(indices), _ptr(data), nnz.value))
+    _, (indices, data) = _size_then_fill(call, nnz, lambda k: (np.empty(k, np.int32), np.empty(k, np.float32)))
     return indptr, indices, data, oov
 
 
@@ -1122,7 +1102,8 @@ def tfidf_utf8_csr(utf8, byte_off, vocab, idf=None, smooth_idf=True, sublinear_t
     ``TfidfVectorizer(vocabulary=...).transform`` returns.  ``idf``: an Idf or None (no idf); ``fold``: FOLD_* flags, folded on the device
     first."""
     opts = _tfidf_opts(smooth_idf, sublinear_tf, norm)
-    return _tfidf_rows(utf8, byte_off, _vocab_handle(vocab), None, _idf_handle(idf), opts, _fold_bits(fold), _tfidf_ng(ngram_range, sep), dtype)
+    return _tfidf_rows(utf8, byte_off, _handle_of(Vocab, vocab, "vocab"), None, _handle_of(Idf, idf, "idf", True), opts, _fold_bits(fold),
+                       _tfidf_ng(ngram_range, sep), dtype)
 
 
 def tfidf_utf8_batch(blobs, vocab, idf=None, smooth_idf=True, sublinear_tf=False, norm="l2", fold=0, ngram_range=(1, 1), sep=b" "):
@@ -1142,7 +1123,7 @@ def hashed_tfidf_utf8_csr(utf8, byte_off, n_features=1 << 20, seed=0, alternate_
     on the device (``latok_hashed_tfidf_utf8_bytes_batch``); without an idf and with norm="l2" this is ``HashingVectorizer``'s own
     default.  An ``idf`` must have ``n_features`` columns."""
     opts, hashed = _tfidf_opts(smooth_idf, sublinear_tf, norm), (_seed32(seed), _n_features31(n_features), bool(alternate_sign))
-    return _tfidf_rows(utf8, byte_off, None, hashed, _idf_handle(idf), opts, _fold_bits(fold), _tfidf_ng(ngram_range, sep), dtype)[:3]
+    return _tfidf_rows(utf8, byte_off, None, hashed, _handle_of(Idf, idf, "idf", True), opts, _fold_bits(fold), _tfidf_ng(ngram_range, sep), dtype)[:3]
 
 
 def hashed_tfidf_utf8_batch(blobs, n_features=1 << 20, seed=0, alternate_sign=True, idf=None, smooth_idf=True, sublinear_tf=False, norm="l2",
@@ -1161,7 +1142,7 @@ def hashed_tfidf_batch(texts, n_features=1 << 20, seed=0, alternate_sign=True, i
 
 # WordPiece: every token cut greedily into the longest vocabulary prefix and ##-continuations, on the device -- the subword ids a
 # BERT-family model takes, as CSR rows or as the padded [n, L] block
-class WordPiece:
+class WordPiece(_DeviceObject):
     """A WordPiece vocabulary on the device of the current context (``latok_wordpiece_create``): ``words`` is a list of ``bytes`` or
     ``str`` (``str`` is encoded as UTF-8 with surrogatepass), ``ids`` an optional int32 per word (default: its index), ``prefix``
     the continuation prefix (0 .. 8 bytes, ``##`` in BERT's files), ``max_chars`` BERT's ``max_input_chars_per_word`` (1 .. 1024:
@@ -1172,32 +1153,22 @@ class WordPiece:
     punctuation split of BERT's BasicTokenizer (tokens are latok's), the final-sigma rule, BPE and Unigram models, a flow form and
     sentence pairs.  Immutable; ``len()`` is the number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
 
+    _destroy, _closed = "latok_wordpiece_destroy", "wp must be an open latok_amd.batch.WordPiece"
+
     def __init__(self, words, ids=None, prefix=b"##", max_chars=100, seed=0):
-        self.handle = None
         seed = _seed32(seed)
         prefix = prefix.encode("utf-8") if isinstance(prefix, str) else bytes(prefix)
         if len(prefix) > 8:
             raise ValueError("prefix must be 0 .. 8 bytes")
         if not isinstance(max_chars, (int, np.integer)) or isinstance(max_chars, bool) or not 1 <= int(max_chars) <= 1024:
             raise ValueError("max_chars must be an int in 1 .. 1024")
-        blobs = [w.encode("utf-8", "surrogatepass") if isinstance(w, str) else bytes(w) for w in words]
-        off = np.zeros(len(blobs) + 1, np.int64)
-        if blobs:
-            np.cumsum([len(b) for b in blobs], out=off[1:])
-        data = np.frombuffer(b"".join(blobs), np.uint8)
-        if ids is not None:
-            raw = np.asarray(ids)
-            if raw.shape != (len(blobs),) or (raw.size and raw.dtype.kind not in "iu"):
-                raise ValueError("ids must be one integer per word")
-            if raw.size and (raw.min() < -0x80000000 or raw.max() > 0x7FFFFFFF):
-                raise ValueError("ids must fit int32")
-            ids = np.ascontiguousarray(raw, np.int32)
+        data, off, ids = _pack_words(words, ids)
         lib = _lib.ensure_init()
         h = C.c_void_p()
         pre = np.frombuffer(prefix + b"\x00", np.uint8)
-        _lib.check(lib.latok_wordpiece_create(_ptr(data) if data.size else None, _ptr(off), len(blobs), _ptr(ids) if ids is not None else None,
+        _lib.check(lib.latok_wordpiece_create(_ptr(data) if data.size else None, _ptr(off), off.size - 1, _ptr(ids) if ids is not None else None,
                                               _ptr(pre), len(prefix), int(max_chars), seed, C.byref(h)))
-        self._lib, self.handle, self.seed, self._n = lib, h, seed, len(blobs)
+        self._lib, self.handle, self.seed, self._n = lib, h, seed, off.size - 1
         self.prefix, self.max_chars = prefix, int(max_chars)
 
     @classmethod
@@ -1213,37 +1184,13 @@ class WordPiece:
         """dict of what ``latok_wordpiece_info`` reports"""
         v = [C.c_int64(0) for _ in range(5)]
         pre, plen, mc, seed, dev = np.zeros(8, np.uint8), C.c_int(0), C.c_int(0), C.c_uint32(0), C.c_int(0)
-        _lib.check(self._lib.latok_wordpiece_info(_wordpiece_handle(self), *[C.byref(x) for x in v], _ptr(pre), C.byref(plen), C.byref(mc),
+        _lib.check(self._lib.latok_wordpiece_info(self._open(), *[C.byref(x) for x in v], _ptr(pre), C.byref(plen), C.byref(mc),
                                                   C.byref(seed), C.byref(dev)))
         return dict(n_words=v[0].value, n_slots_initial=v[1].value, n_slots_cont=v[2].value, max_len_initial=v[3].value,
                     max_len_cont=v[4].value, prefix=pre[:plen.value].tobytes(), max_chars=mc.value, seed=seed.value, device=dev.value)
 
     def __len__(self):
         return self._n
-
-    def close(self):
-        if self.handle:
-            h, self.handle = self.handle, None
-            _lib.check(self._lib.latok_wordpiece_destroy(h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _wordpiece_handle(wp):
-    if not isinstance(wp, WordPiece) or not wp.handle:
-        raise ValueError("wp must be an open latok_amd.batch.WordPiece")
-    return wp.handle
 
 
 def wordpiece_ids_utf8_csr(utf8, byte_off, wp, unk_id=-1, dtype=np.int64, spans=True):
@@ -1255,47 +1202,34 @@ def wordpiece_ids_utf8_csr(utf8, byte_off, wp, unk_id=-1, dtype=np.int64, spans=
     utf8, byte_off = _csr_u8(utf8, byte_off)
     unk_id = _unk32(unk_id)
     dt, flags = _out_dtype(dtype)
-    handle = _wordpiece_handle(wp)
+    handle = _handle_of(WordPiece, wp, "wp")
     n_str = byte_off.size - 1
     total = int(byte_off[-1]) if n_str > 0 else 0
     lib = _lib.ensure_init()
     indptr = np.zeros(n_str + 1, dt)
     n = C.c_int64(0)
 
-    def call(ids, sp, cap):
+    def call(ids=None, sp=None, cap=0):
         return lib.latok_wordpiece_ids_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, handle, unk_id, _ptr(indptr), ids, sp, cap,
                                                         C.byref(n), None, flags, None)
 
-    rc = call(None, None, 0)
-    if rc != _lib.OK and not (rc == _lib.ERR_INVALID and n.value > 0):
-        _lib.check(rc)
-    ids = np.empty(n.value, np.int32)
-    sp = np.empty((n.value, 2), dt) if spans else None
-    if n.value > 0:
-        _lib.check(call(_ptr(ids), _ptr(sp) if spans else None, n.value))
+    _, (ids, sp) = _size_then_fill(call, n, lambda k: (np.empty(k, np.int32), np.empty((k, 2), dt) if spans else None))
     return indptr, ids, sp
 
 
 def _wordpiece_ids_folded(utf8, byte_off, wp, unk_id, fold):
     """wordpiece_ids_utf8_csr (int64, with spans) of the batch folded on the device: the size query, then the fill, on device buffers"""
-    handle = _wordpiece_handle(wp)
+    handle = _handle_of(WordPiece, wp, "wp")
     with _DeviceFolded(utf8, byte_off, fold) as d:
         indptr = d.alloc((d.n_str + 1) * 8)
         n = C.c_int64(0)
 
-        def call(ids, sp, cap):
+        def call(ids=None, sp=None, cap=0):
             return d.lib.latok_wordpiece_ids_utf8_bytes_batch(d.u8, d.off, d.n_str, d.total, handle, unk_id, indptr, ids, sp, cap, C.byref(n), None,
                                                               _lib.DEVICE_PTRS, None)
 
-        rc = call(None, None, 0)
-        if rc != _lib.OK and not (rc == _lib.ERR_INVALID and n.value > 0):
-            _lib.check(rc)
-        need = n.value
-        if need > 0:
-            ids, sp = d.alloc(need * 4), d.alloc(need * 16)
-            _lib.check(call(ids, sp, need))
-        return (d.fetch(indptr, d.n_str + 1, np.int64), d.fetch(ids, need, np.int32) if need else np.empty(0, np.int32),
-                d.fetch(sp, (need, 2), np.int64) if need else np.empty((0, 2), np.int64))
+        need, (ids, sp) = _size_then_fill(call, n, lambda k: (d.alloc(k * 4), d.alloc(k * 16)))
+        return d.fetch(indptr, d.n_str + 1, np.int64), d.fetch(ids, need, np.int32), d.fetch(sp, (need, 2), np.int64)
 
 
 def wordpiece_ids_utf8_batch(blobs, wp, unk_id=-1, fold=0):
@@ -1303,7 +1237,7 @@ def wordpiece_ids_utf8_batch(blobs, wp, unk_id=-1, fold=0):
     (FOLD_* flags, ``FOLD_UNCASED`` for an uncased vocabulary): the batch is uploaded once, folded on the device
     (fold_utf8_batch) and cut there; the spans are then byte ranges of the FOLDED string, not of the input."""
     unk_id, fold = _unk32(unk_id), _fold_bits(fold)
-    _wordpiece_handle(wp)
+    _handle_of(WordPiece, wp, "wp")
     utf8, byte_off = pack_utf8(blobs)
     if fold:
         return _wordpiece_ids_folded(utf8, byte_off, wp, unk_id, fold)
@@ -1329,7 +1263,7 @@ def wordpiece_encode_utf8_batch(blobs, wp, max_length, cls_id=None, sep_id=None,
     cls_id, sep_id = (_unk32(cls_id), _unk32(sep_id)) if special else (0, 0)
     if not isinstance(max_length, (int, np.integer)) or isinstance(max_length, bool) or not 1 + 2 * special <= int(max_length) <= 0x7FFFFFFF:
         raise ValueError("max_length must be an int >= %d" % (1 + 2 * special))
-    handle = _wordpiece_handle(wp)
+    handle = _handle_of(WordPiece, wp, "wp")
     utf8, byte_off = pack_utf8(blobs)
     n_str, total = len(blobs), int(byte_off[-1])
     lib = _lib.ensure_init()
@@ -1351,7 +1285,7 @@ def wordpiece_encode_utf8_batch(blobs, wp, max_length, cls_id=None, sep_id=None,
 
 
 # token counts: the vocabulary of a corpus -- every distinct token with its frequency --, counted on the device, exactly
-class TokenCounter:
+class TokenCounter(_DeviceObject):
     """A counting table on the device of the current context (``latok_counter_create``): at most about ``max_words`` distinct
     tokens (the table has ``n_slots`` >= 2 * max_words slots), each of at most ``max_word_bytes`` bytes (1 .. 256; longer tokens
     are tallied as ``long``), placed by MurmurHash3 with ``seed``.  ``update*`` count the tokens of a batch -- the byte slices
@@ -1360,9 +1294,9 @@ class TokenCounter:
     leaving a ``with`` block, or with the object."""
 
     STATS = ("tokens", "counted", "long", "dropped", "distinct")
+    _destroy, _closed = "latok_counter_destroy", "the TokenCounter is closed"
 
     def __init__(self, max_words, max_word_bytes=256, seed=0):
-        self.handle = None
         seed = _seed32(seed)
         for name, v, hi in (("max_words", max_words, 1 << 30), ("max_word_bytes", max_word_bytes, 256)):
             if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 1 <= int(v) <= hi:
@@ -1375,11 +1309,6 @@ class TokenCounter:
         n_slots = C.c_int64(0)
         _lib.check(lib.latok_counter_info(h, None, C.byref(n_slots), None, None, None, None))
         self.n_slots = n_slots.value
-
-    def _open(self):
-        if not self.handle:
-            raise ValueError("the TokenCounter is closed")
-        return self.handle
 
     def update_utf8_csr(self, utf8, byte_off):
         """count the tokens of a CSR batch of UTF-8 bytes; returns this call's {tokens, counted, long, dropped}"""
@@ -1409,7 +1338,8 @@ class TokenCounter:
 
     def items(self):
         """(list[bytes], uint64 array): the words held and their counts, in no particular order.  One state of the counter: when another
-        thread's update lands between the size query and the read, the read reports the larger need and is made again with it."""
+        thread's update lands between the size query and the read, the read reports the larger need and is made again with it (which
+        is why this is not _size_then_fill: there a refused fill is an error)."""
         h = self._open()
         n, nb = C.c_int64(0), C.c_int64(0)
         rc = self._lib.latok_counter_read(h, None, 0, None, None, 0, C.byref(n), C.byref(nb))   # the size query
@@ -1442,24 +1372,6 @@ class TokenCounter:
     def clear(self):
         h = self._open()
         _lib.check(self._lib.latok_counter_clear(h))
-
-    def close(self):
-        if self.handle:
-            h, self.handle = self.handle, None
-            _lib.check(self._lib.latok_counter_destroy(h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def count_tokens_utf8_batch(blobs, max_words=None):
@@ -1766,7 +1678,7 @@ def flow_token_ids_utf8_bytes(d_utf8, d_byte_off, n_str, total_bytes, vocab, d_c
     spans), as in the sibling wrappers."""
     unk_id = _unk32(unk_id)
     _, flag32 = _out_dtype(dtype)
-    handle = _vocab_handle(vocab)
+    handle = _handle_of(Vocab, vocab, "vocab")
     lib = _lib.ensure_init()
     _lib.check(lib.latok_flow_token_ids_utf8_bytes(d_utf8, d_byte_off, int(n_str), int(total_bytes), handle, unk_id, d_counts, d_spans, d_ids,
                                                    int(cap), d_result, flag32))

@@ -89,6 +89,49 @@ struct DevBuf {
     }
 };
 
+// an exact-size device allocation with one owner, freed with it: what the long-lived objects (vocab, WordPiece, idf, counter) hold
+struct DevMem {
+    void* p = nullptr;
+    DevMem() = default;
+    DevMem(DevMem&& o) noexcept : p(std::exchange(o.p, nullptr)) {}
+    DevMem& operator=(DevMem&& o) noexcept {
+        if (p && p != o.p) (void)hipFree(p);
+        p = std::exchange(o.p, nullptr);
+        return *this;
+    }
+    ~DevMem() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) {   // of an empty one
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    template <class T>
+    T* as() const {
+        return static_cast<T*>(p);
+    }
+};
+
+// slots + padded words of one vocab_table.h table on the device
+struct DevTable {
+    DevMem slots, blob;   // VtSlot[n_slots], the padded words
+    uint64_t n_slots = 0;
+    // allocates, then enqueues the two copies on `st`: the caller waits for `st` before `t` dies
+    int upload(const VtTable& t, hipStream_t st) {
+        const size_t slot_bytes = t.slots.size() * sizeof(VtSlot), blob_bytes = t.blob.size() * 4;
+        n_slots = t.slots.size();
+        hipError_t e = slots.alloc(slot_bytes);
+        if (e == hipSuccess) e = blob.alloc(blob_bytes);
+        if (e != hipSuccess) return fail(LATOK_ERR_NOMEM, "hipMalloc(%zu) failed: %s", slot_bytes + blob_bytes, hipGetErrorString(e));
+        e = hipMemcpyAsync(slots.p, t.slots.data(), slot_bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(blob.p, t.blob.data(), blob_bytes, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
+        return LATOK_OK;
+    }
+    latok::VocabTable view(uint32_t seed) const { return latok::VocabTable{slots.p, blob.as<const uint32_t>(), n_slots, seed}; }
+};
+
 // pinned, device-mapped host memory: small host-pointer calls stage their inputs here and have the kernels read and
 // write it in place over the bus, so that a call costs launches + ONE synchronisation instead of five blocking copies
 struct PinBuf {
@@ -694,13 +737,32 @@ int deliver_sized(const BytesCall& c, int64_t n, int64_t cap, const char* need_f
     return LATOK_OK;
 }
 
-// the vocabulary (or WordPiece object) of a call: there is one, and it lives on the device of the context that runs the call
+// the shared object of a call (`noun`: vocabulary, idf, counter) lives on the device of the context that runs the call; a counter
+// passes `failed`, and is refused when an update of it did not finish
+int check_device(const Ctx& g, const char* noun, int device, bool failed = false) {
+    if (device != g.device) return fail(LATOK_ERR_INVALID, "the %s lives on device %d, the current context on device %d", noun, device, g.device);
+    if (failed) return fail(LATOK_ERR_INVALID, "the %s is in the failed state (an update did not finish): latok_%s_clear it", noun, noun);
+    return LATOK_OK;
+}
+// the vocabulary (or WordPiece object) of a call: there is one, and it passes check_device
 template <class Obj, class Handle>
 int check_object(const Ctx& g, const Handle* handle, const char* null_msg, const Obj** v) {
     *v = reinterpret_cast<const Obj*>(handle);
     if (!*v) return fail(LATOK_ERR_INVALID, "%s", null_msg);
-    if ((*v)->device != g.device)
-        return fail(LATOK_ERR_INVALID, "the vocabulary lives on device %d, the current context on device %d", (*v)->device, g.device);
+    return check_device(g, "vocabulary", (*v)->device);
+}
+// the word list of latok_vocab_create and latok_wordpiece_create; needs no device
+int check_word_list(const uint8_t* words, const int64_t* word_off, int64_t n_words) {
+    if (n_words < 0 || n_words >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "n_words must be in 0 .. 2^31 - 1");
+    if (!word_off) return fail(LATOK_ERR_INVALID, "word_off is NULL");
+    if (word_off[0] != 0) return fail(LATOK_ERR_INVALID, "word_off must start at 0");
+    uint64_t padded = 0;
+    for (int64_t i = 0; i < n_words; ++i) {
+        if (word_off[i + 1] < word_off[i]) return fail(LATOK_ERR_INVALID, "word_off must be non-decreasing (word %lld)", (long long)i);
+        padded += ((uint64_t)(word_off[i + 1] - word_off[i]) + 3u) & ~3ull;
+        if (padded >= (1ull << 32)) return fail(LATOK_ERR_INVALID, "the padded words take 2^32 bytes or more");
+    }
+    if (word_off[n_words] > 0 && !words) return fail(LATOK_ERR_INVALID, "words is NULL");
     return LATOK_OK;
 }
 
@@ -1713,10 +1775,8 @@ static int enqueue_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* r_
 struct Vocab {                     // latok_vocab: immutable once created
     int device = -1;
     int64_t n_words = 0;
-    uint64_t n_slots = 0;
     uint32_t seed = 0;
-    void* d_slots = nullptr;       // VtSlot[n_slots]
-    void* d_blob = nullptr;        // the padded words
+    DevTable table;
 };
 struct TokenWords {
     Batch b;                       // UTF-8 bytes on the device (16-byte aligned), byte offsets, total in bytes (> 0), n_str > 0
@@ -1744,7 +1804,7 @@ static int enqueue_token_words(Ctx& g, Workspace& w, const TokenWords& a) {
                                            t.tile_first, spans, (uint32_t*)a.words, t.total, a.cap, a.counts, d_err, a.st));
         return LATOK_OK;
     }
-    const latok::VocabTable vt{a.vocab->d_slots, (const uint32_t*)a.vocab->d_blob, a.vocab->n_slots, a.vocab->seed};
+    const latok::VocabTable vt = a.vocab->table.view(a.vocab->seed);
     HIP_TRY(latok::launch_vocab_scatter(a.o32, u8, vt, a.unk, t.bits, t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, a.b.total, a.b.row, a.b.n_str,
                                         t.tile_first, spans, (int32_t*)a.words, t.total, a.cap, a.counts, d_err, a.st));
     return LATOK_OK;
@@ -2358,24 +2418,30 @@ int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
 
 /* vocabularies: built on the host (vocab_table.h), uploaded once, read only afterwards */
 static int flow_drain(Ctx& g);   // batch flow (below): its three streams
+// The end of a shared object (latok_vocab, latok_wordpiece, latok_idf, latok_counter; `mu`: the lock of a mutable one).  The current
+// context's own work on it is waited for first: its stream and its flow; whatever they report, the object is freed.
+extern "C++" template <class Obj>
+static int destroy_object(Ctx& g, Obj* obj, std::mutex Obj::*mu = nullptr) {
+    if (!obj) return LATOK_OK;
+    int rc = LATOK_OK;
+    if (g.inited) {
+        const hipError_t e = hipStreamSynchronize(g.stream);
+        rc = flow_drain(g);
+        if (e != hipSuccess) rc = fail(LATOK_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    }
+    if (mu) { std::lock_guard<std::mutex> ol(obj->*mu); }   // (a call of another context that still holds it has returned)
+    delete obj;
+    return rc;
+}
+
 int latok_vocab_create(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, uint32_t seed,
                        latok_vocab** vocab_out) {
     LATOK_ENTER();
     // what needs no device is refused first
     if (!vocab_out) return fail(LATOK_ERR_INVALID, "vocab_out is NULL");
     *vocab_out = nullptr;
-    if (n_words < 0 || n_words >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "n_words must be in 0 .. 2^31 - 1");
-    if (!word_off) return fail(LATOK_ERR_INVALID, "word_off is NULL");
-    if (word_off[0] != 0) return fail(LATOK_ERR_INVALID, "word_off must start at 0");
-    uint64_t padded = 0;
-    for (int64_t i = 0; i < n_words; ++i) {
-        if (word_off[i + 1] < word_off[i]) return fail(LATOK_ERR_INVALID, "word_off must be non-decreasing (word %lld)", (long long)i);
-        padded += ((uint64_t)(word_off[i + 1] - word_off[i]) + 3u) & ~3ull;
-        if (padded >= (1ull << 32)) return fail(LATOK_ERR_INVALID, "the padded words take 2^32 bytes or more");
-    }
-    if (word_off[n_words] > 0 && !words) return fail(LATOK_ERR_INVALID, "words is NULL");
-    int rc = need_init(g);
-    if (rc) return rc;
+    int rc = check_word_list(words, word_off, n_words);
+    if (rc || (rc = need_init(g))) return rc;
     VtTable t;
     Vocab* v = nullptr;
     try {
@@ -2386,24 +2452,13 @@ int latok_vocab_create(const uint8_t* words, const int64_t* word_off, int64_t n_
     }
     v->device = g.device;
     v->n_words = n_words;
-    v->n_slots = t.slots.size();
     v->seed = seed;
-    const size_t slot_bytes = t.slots.size() * sizeof(VtSlot), blob_bytes = t.blob.size() * 4;
-    hipError_t e = hipMalloc(&v->d_slots, slot_bytes);
-    if (e == hipSuccess) e = hipMalloc(&v->d_blob, blob_bytes);
-    if (e != hipSuccess) {
-        if (v->d_slots) (void)hipFree(v->d_slots);
+    rc = v->table.upload(t, g.stream);
+    const hipError_t e = hipStreamSynchronize(g.stream);   // (the host table dies with this call, and every context may use the object at once)
+    if (!rc && e != hipSuccess) rc = fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
+    if (rc) {
         delete v;
-        return fail(LATOK_ERR_NOMEM, "hipMalloc(%zu) failed: %s", slot_bytes + blob_bytes, hipGetErrorString(e));
-    }
-    e = hipMemcpyAsync(v->d_slots, t.slots.data(), slot_bytes, hipMemcpyHostToDevice, g.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(v->d_blob, t.blob.data(), blob_bytes, hipMemcpyHostToDevice, g.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);   // (the host table dies with this call, and every context may use the object at once)
-    if (e != hipSuccess) {
-        (void)hipFree(v->d_slots);
-        (void)hipFree(v->d_blob);
-        delete v;
-        return fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
+        return rc;
     }
     *vocab_out = reinterpret_cast<latok_vocab*>(v);
     return LATOK_OK;
@@ -2411,24 +2466,14 @@ int latok_vocab_create(const uint8_t* words, const int64_t* word_off, int64_t n_
 
 int latok_vocab_destroy(latok_vocab* vocab) {
     LATOK_ENTER();
-    Vocab* v = reinterpret_cast<Vocab*>(vocab);
-    if (!v) return LATOK_OK;
-    int rc = LATOK_OK;
-    if (g.inited) {   // the current context's own work on it: its stream and its flow
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        rc = flow_drain(g);
-    }
-    (void)hipFree(v->d_slots);
-    (void)hipFree(v->d_blob);
-    delete v;
-    return rc;
+    return destroy_object(g, reinterpret_cast<Vocab*>(vocab));
 }
 
 int latok_vocab_info(const latok_vocab* vocab, int64_t* n_words, int64_t* n_slots, uint32_t* seed, int* device) {
     const Vocab* v = reinterpret_cast<const Vocab*>(vocab);
     if (!v) return fail(LATOK_ERR_INVALID, "vocab is NULL");
     if (n_words) *n_words = v->n_words;
-    if (n_slots) *n_slots = (int64_t)v->n_slots;
+    if (n_slots) *n_slots = (int64_t)v->table.n_slots;
     if (seed) *seed = v->seed;
     if (device) *device = v->device;
     return LATOK_OK;
@@ -2449,42 +2494,32 @@ struct Idf {                       // latok_idf: mutable; calls on it are serial
     int device = -1;
     int64_t n_cols = 0;            // (never changes)
     int64_t n_docs = 0;
-    int32_t* d_df = nullptr;       // int32[n_cols]
-    float* d_idf[2] = {nullptr, nullptr};          // [smooth]: float[n_cols], allocated on first use
+    DevMem df;                     // int32[n_cols]
+    DevMem idf[2];                 // [smooth]: float[n_cols], allocated on first use
     bool idf_valid[2] = {false, false};
     hipEvent_t idf_ready[2] = {nullptr, nullptr};
+    ~Idf() {
+        for (hipEvent_t e : idf_ready)
+            if (e) (void)hipEventDestroy(e);
+    }
 };
-static void idf_free(Idf* f) {
-    for (void* p : {(void*)f->d_df, (void*)f->d_idf[0], (void*)f->d_idf[1]})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : f->idf_ready)
-        if (e) (void)hipEventDestroy(e);
-    delete f;
-}
 static void idf_drop_weights(Idf& f) { f.idf_valid[0] = f.idf_valid[1] = false; }
-static int check_idf(const Ctx& g, const Idf& f) {
-    if (f.device != g.device) return fail(LATOK_ERR_INVALID, "the idf lives on device %d, the current context on device %d", f.device, g.device);
-    return LATOK_OK;
-}
 // the idf vector of one smoothing mode, valid on `st` (caller holds f.mu)
 static int idf_weights_on(Idf& f, bool smooth, hipStream_t st, const float** out) {
     const int m = smooth ? 1 : 0;
-    if (!f.d_idf[m]) {
-        const hipError_t e = hipMalloc((void**)&f.d_idf[m], (size_t)f.n_cols * 4);
-        if (e != hipSuccess) {
-            f.d_idf[m] = nullptr;
-            return fail(LATOK_ERR_NOMEM, "hipMalloc of %lld idf weights failed: %s", (long long)f.n_cols, hipGetErrorString(e));
-        }
+    if (!f.idf[m].p) {
+        const hipError_t e = f.idf[m].alloc((size_t)f.n_cols * 4);
+        if (e != hipSuccess) return fail(LATOK_ERR_NOMEM, "hipMalloc of %lld idf weights failed: %s", (long long)f.n_cols, hipGetErrorString(e));
     }
     if (!f.idf_ready[m]) HIP_TRY(hipEventCreateWithFlags(&f.idf_ready[m], hipEventDisableTiming));
     if (!f.idf_valid[m]) {
-        HIP_TRY(latok::launch_idf_weights(f.d_df, f.n_cols, f.n_docs, smooth, f.d_idf[m], st));
+        HIP_TRY(latok::launch_idf_weights(f.df.as<int32_t>(), f.n_cols, f.n_docs, smooth, f.idf[m].as<float>(), st));
         HIP_TRY(hipEventRecord(f.idf_ready[m], st));
         f.idf_valid[m] = true;
     } else {
         HIP_TRY(hipStreamWaitEvent(st, f.idf_ready[m], 0));
     }
-    *out = f.d_idf[m];
+    *out = f.idf[m].as<float>();
     return LATOK_OK;
 }
 static int tfidf_check_opts(int opts) {
@@ -2562,7 +2597,7 @@ static int enqueue_term_counts(Ctx& g, Workspace& w, TermCounts& a) {
     if (n_tok > 0) {
         uint64_t* d_keys = (uint64_t*)w.tkeys.p;
         latok::VocabTable vt;
-        if (a.vocab) vt = latok::VocabTable{a.vocab->d_slots, (const uint32_t*)a.vocab->d_blob, a.vocab->n_slots, a.vocab->seed};
+        if (a.vocab) vt = a.vocab->table.view(a.vocab->seed);
         HIP_TRY(latok::launch_term_scatter((const uint8_t*)a.b.in.p, a.vocab ? &vt : nullptr, a.seed, a.n_features, a.alternate_sign, t.bits, t.space,
                                            t.kept, t.rank, t.tcnt, t.pref, t.words, total, a.b.row, n_str, t.tile_first, d_total, d_keys, d_cnt,
                                            d_err, st));
@@ -2641,7 +2676,7 @@ static int enqueue_ngram_counts(Ctx& g, Workspace& w, TermCounts& a) {
             if ((rc = ws_ensure(ws_needs(w, total, shape).data(), kWsNeeds))) return rc;   // (only the key buffers grow)
             uint64_t* d_keys = (uint64_t*)w.tkeys.p;
             latok::VocabTable vt;
-            if (a.vocab) vt = latok::VocabTable{a.vocab->d_slots, (const uint32_t*)a.vocab->d_blob, a.vocab->n_slots, a.vocab->seed};
+            if (a.vocab) vt = a.vocab->table.view(a.vocab->seed);
             HIP_TRY(latok::launch_ngram_keys((const uint8_t*)a.b.in.p, total, a.b.row, n_str, d_start, d_kstart, d_tspans, n_tok, n_keys, a.min_n, a.max_n,
                                              a.sep, a.vocab ? &vt : nullptr, a.seed, a.n_features, a.alternate_sign, d_keys, st));
             HIP_TRY(latok::launch_terms_reduce(d_keys, (uint64_t*)w.tkeys2.p, d_kstart, n_str, n_keys, a.vocab != nullptr, d_distinct, d_oov, st));
@@ -2703,7 +2738,7 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
     std::unique_lock<std::mutex> idf_lock;
     if (f) {
         idf_lock = std::unique_lock<std::mutex>(f->mu);
-        if ((rc = check_idf(g, *f))) return rc;
+        if ((rc = check_device(g, "idf", f->device))) return rc;
         if (upd && f->n_docs + std::max<int64_t>(n_str, 0) >= (1ll << 31))
             return fail(LATOK_ERR_INVALID, "the idf would hold %lld documents: df is int32 (fewer than 2^31)", (long long)(f->n_docs + n_str));
     }
@@ -2769,7 +2804,7 @@ static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int6
         HIP_TRY(hipMemsetAsync(d_err, 0, 4, st));
         if (f && !hashed) HIP_TRY(latok::launch_csr_check(false, nullptr, a.indices, n_str, 0, d_nnz, a.cap, f->n_cols, d_err, st));
         if (upd) {
-            HIP_TRY(latok::launch_df_add(g_df_add_cached != 0, a.indices, 0, d_nnz, a.cap, d_err, f->d_df, st));
+            HIP_TRY(latok::launch_df_add(g_df_add_cached != 0, a.indices, 0, d_nnz, a.cap, d_err, f->df.as<int32_t>(), st));
         } else {
             const float* weights = nullptr;
             if (f && (rc = idf_weights_on(*f, (tf->opts & kTwSmoothIdf) != 0, st, &weights))) return rc;
@@ -2872,16 +2907,15 @@ int latok_idf_create(int64_t n_cols, latok_idf** out) {
     }
     f->device = g.device;
     f->n_cols = n_cols;
-    hipError_t e = hipMalloc((void**)&f->d_df, (size_t)n_cols * 4);
+    hipError_t e = f->df.alloc((size_t)n_cols * 4);
     if (e != hipSuccess) {
-        f->d_df = nullptr;
-        idf_free(f);
+        delete f;
         return fail(LATOK_ERR_NOMEM, "hipMalloc of %lld document frequencies failed: %s", (long long)n_cols, hipGetErrorString(e));
     }
-    e = hipMemsetAsync(f->d_df, 0, (size_t)n_cols * 4, g.stream);
+    e = hipMemsetAsync(f->df.p, 0, (size_t)n_cols * 4, g.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g.stream);
     if (e != hipSuccess) {
-        idf_free(f);
+        delete f;
         return fail(LATOK_ERR_HIP, "clearing the document frequencies failed: %s", hipGetErrorString(e));
     }
     *out = reinterpret_cast<latok_idf*>(f);
@@ -2890,17 +2924,7 @@ int latok_idf_create(int64_t n_cols, latok_idf** out) {
 
 int latok_idf_destroy(latok_idf* idf) {
     LATOK_ENTER();
-    Idf* f = reinterpret_cast<Idf*>(idf);
-    if (!f) return LATOK_OK;
-    int rc = LATOK_OK;
-    if (g.inited) {   // the current context's own work: its stream and its flow; whatever they report, the object is freed
-        const hipError_t e = hipStreamSynchronize(g.stream);
-        rc = flow_drain(g);
-        if (e != hipSuccess) rc = fail(LATOK_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
-    }
-    { std::lock_guard<std::mutex> il(f->mu); }   // (a call of another context that still holds it has returned)
-    idf_free(f);
-    return rc;
+    return destroy_object(g, reinterpret_cast<Idf*>(idf), &Idf::mu);
 }
 
 int latok_idf_clear(latok_idf* idf) {
@@ -2910,8 +2934,8 @@ int latok_idf_clear(latok_idf* idf) {
     int rc = need_init(g);
     if (rc) return rc;
     std::lock_guard<std::mutex> il(f->mu);
-    if ((rc = check_idf(g, *f))) return rc;
-    HIP_TRY(hipMemsetAsync(f->d_df, 0, (size_t)f->n_cols * 4, g.stream));
+    if ((rc = check_device(g, "idf", f->device))) return rc;
+    HIP_TRY(hipMemsetAsync(f->df.p, 0, (size_t)f->n_cols * 4, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     f->n_docs = 0;
     idf_drop_weights(*f);
@@ -2938,11 +2962,11 @@ int latok_idf_read(const latok_idf* idf, int32_t* df_out, int64_t cap, int64_t* 
     int rc = need_init(g);
     if (rc) return rc;
     std::lock_guard<std::mutex> il(f->mu);
-    if ((rc = check_idf(g, *f))) return rc;
+    if ((rc = check_device(g, "idf", f->device))) return rc;
     if (n_docs_out) *n_docs_out = f->n_docs;
     if (cap == 0 && !df_out) return LATOK_OK;
     if (cap < f->n_cols) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld columns", (long long)f->n_cols);
-    HIP_TRY(hipMemcpyAsync(df_out, f->d_df, (size_t)f->n_cols * 4, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(df_out, f->df.p, (size_t)f->n_cols * 4, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     return LATOK_OK;
 }
@@ -2956,10 +2980,10 @@ int latok_idf_load(latok_idf* idf, const int32_t* df, int64_t n_docs) {
     int rc = need_init(g);
     if (rc) return rc;
     std::lock_guard<std::mutex> il(f->mu);
-    if ((rc = check_idf(g, *f))) return rc;
+    if ((rc = check_device(g, "idf", f->device))) return rc;
     for (int64_t c = 0; c < f->n_cols; ++c)
         if (df[c] < 0 || (int64_t)df[c] > n_docs) return fail(LATOK_ERR_INVALID, "df[%lld] = %d lies outside [0, n_docs]", (long long)c, (int)df[c]);
-    HIP_TRY(hipMemcpyAsync(f->d_df, df, (size_t)f->n_cols * 4, hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(hipMemcpyAsync(f->df.p, df, (size_t)f->n_cols * 4, hipMemcpyHostToDevice, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     f->n_docs = n_docs;
     idf_drop_weights(*f);
@@ -2974,7 +2998,7 @@ int latok_idf_weights(const latok_idf* idf, int smooth, float* out, int64_t cap)
     int rc = need_init(g);
     if (rc) return rc;
     std::lock_guard<std::mutex> il(f->mu);
-    if ((rc = check_idf(g, *f))) return rc;
+    if ((rc = check_device(g, "idf", f->device))) return rc;
     if (cap < f->n_cols) return fail(LATOK_ERR_INVALID, "capacity too small: need %lld columns", (long long)f->n_cols);
     const float* w = nullptr;
     if ((rc = idf_weights_on(*f, smooth != 0, g.stream, &w))) return rc;
@@ -3052,13 +3076,13 @@ int latok_idf_update_csr(latok_idf* idf, const void* indptr, const int32_t* indi
     int rc = csr_args(indptr, indices, n_rows, nnz, flags);
     if (rc || (rc = need_init(g))) return rc;
     std::lock_guard<std::mutex> il(f->mu);
-    if ((rc = check_idf(g, *f))) return rc;
+    if ((rc = check_device(g, "idf", f->device))) return rc;
     if (f->n_docs + n_rows >= (1ll << 31))
         return fail(LATOK_ERR_INVALID, "the idf would hold %lld documents: df is int32 (fewer than 2^31)", (long long)(f->n_docs + n_rows));
     if (n_rows == 0) return LATOK_OK;
     CsrCall c;
     if ((rc = c.open(g, indptr, indices, nullptr, n_rows, nnz, f->n_cols, flags, stream))) return rc;
-    HIP_TRY(latok::launch_df_add(g_df_add_cached != 0, c.indices, nnz, nullptr, 0, c.d_err, f->d_df, c.st));
+    HIP_TRY(latok::launch_df_add(g_df_add_cached != 0, c.indices, nnz, nullptr, 0, c.d_err, f->df.as<int32_t>(), c.st));
     if ((rc = c.finish(g))) return rc;
     f->n_docs += n_rows;
     idf_drop_weights(*f);
@@ -3076,7 +3100,7 @@ int latok_tfidf_csr(const void* indptr, const int32_t* indices, const int32_t* d
     std::unique_lock<std::mutex> il;
     if (f) {
         il = std::unique_lock<std::mutex>(f->mu);
-        if ((rc = check_idf(g, *f))) return rc;
+        if ((rc = check_device(g, "idf", f->device))) return rc;
     }
     if (n_rows == 0) return LATOK_OK;
     CsrCall c;
@@ -3127,20 +3151,11 @@ extern "C" int latok_debug_set_df_add(int cached) {
 struct WordPiece {                 // latok_wordpiece: immutable once created
     int device = -1;
     int64_t n_words = 0;
-    uint64_t n_slots0 = 0, n_slots1 = 0;
     uint32_t max_len0 = 0, max_len1 = 0;
     uint8_t prefix[kWpMaxPrefix] = {0};
     int prefix_len = 0, max_chars = 0;
     uint32_t seed = 0;
-    void* d_slots0 = nullptr;      // VtSlot[n_slots0]: the initial table
-    void* d_blob0 = nullptr;
-    void* d_slots1 = nullptr;      // VtSlot[n_slots1]: the continuation table
-    void* d_blob1 = nullptr;
-    void free_device() {
-        for (void* p : {d_slots0, d_blob0, d_slots1, d_blob1})
-            if (p) (void)hipFree(p);
-        d_slots0 = d_blob0 = d_slots1 = d_blob1 = nullptr;
-    }
+    DevTable initial, cont;
 };
 int latok_wordpiece_create(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, const uint8_t* prefix,
                            int prefix_len, int max_chars, uint32_t seed, latok_wordpiece** wp_out) {
@@ -3148,21 +3163,11 @@ int latok_wordpiece_create(const uint8_t* words, const int64_t* word_off, int64_
     // what needs no device is refused first
     if (!wp_out) return fail(LATOK_ERR_INVALID, "wp_out is NULL");
     *wp_out = nullptr;
-    if (n_words < 0 || n_words >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "n_words must be in 0 .. 2^31 - 1");
     if (prefix_len < 0 || prefix_len > kWpMaxPrefix) return fail(LATOK_ERR_INVALID, "prefix_len must be in 0 .. %d", kWpMaxPrefix);
     if (prefix_len > 0 && !prefix) return fail(LATOK_ERR_INVALID, "prefix is NULL");
     if (max_chars < 1 || max_chars > kWpMaxChars) return fail(LATOK_ERR_INVALID, "max_chars must be in 1 .. %d", kWpMaxChars);
-    if (!word_off) return fail(LATOK_ERR_INVALID, "word_off is NULL");
-    if (word_off[0] != 0) return fail(LATOK_ERR_INVALID, "word_off must start at 0");
-    uint64_t padded = 0;
-    for (int64_t i = 0; i < n_words; ++i) {
-        if (word_off[i + 1] < word_off[i]) return fail(LATOK_ERR_INVALID, "word_off must be non-decreasing (word %lld)", (long long)i);
-        padded += ((uint64_t)(word_off[i + 1] - word_off[i]) + 3u) & ~3ull;
-        if (padded >= (1ull << 32)) return fail(LATOK_ERR_INVALID, "the padded words take 2^32 bytes or more");
-    }
-    if (word_off[n_words] > 0 && !words) return fail(LATOK_ERR_INVALID, "words is NULL");
-    int rc = need_init(g);
-    if (rc) return rc;
+    int rc = check_word_list(words, word_off, n_words);
+    if (rc || (rc = need_init(g))) return rc;
     WpTables t;
     WordPiece* v = nullptr;
     try {
@@ -3173,34 +3178,18 @@ int latok_wordpiece_create(const uint8_t* words, const int64_t* word_off, int64_
     }
     v->device = g.device;
     v->n_words = n_words;
-    v->n_slots0 = t.initial.slots.size();
-    v->n_slots1 = t.cont.slots.size();
     v->max_len0 = t.max_len0;
     v->max_len1 = t.max_len1;
     for (int i = 0; i < prefix_len; ++i) v->prefix[i] = prefix[i];
     v->prefix_len = prefix_len;
     v->max_chars = max_chars;
     v->seed = seed;
-    const size_t sb0 = t.initial.slots.size() * sizeof(VtSlot), bb0 = t.initial.blob.size() * 4;
-    const size_t sb1 = t.cont.slots.size() * sizeof(VtSlot), bb1 = t.cont.blob.size() * 4;
-    hipError_t e = hipMalloc(&v->d_slots0, sb0);
-    if (e == hipSuccess) e = hipMalloc(&v->d_blob0, bb0);
-    if (e == hipSuccess) e = hipMalloc(&v->d_slots1, sb1);
-    if (e == hipSuccess) e = hipMalloc(&v->d_blob1, bb1);
-    if (e != hipSuccess) {
-        v->free_device();
+    if ((rc = v->initial.upload(t.initial, g.stream)) == LATOK_OK) rc = v->cont.upload(t.cont, g.stream);
+    const hipError_t e = hipStreamSynchronize(g.stream);   // (the host tables die with this call, and every context may use the object at once)
+    if (!rc && e != hipSuccess) rc = fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
+    if (rc) {
         delete v;
-        return fail(LATOK_ERR_NOMEM, "hipMalloc(%zu) failed: %s", sb0 + bb0 + sb1 + bb1, hipGetErrorString(e));
-    }
-    e = hipMemcpyAsync(v->d_slots0, t.initial.slots.data(), sb0, hipMemcpyHostToDevice, g.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(v->d_blob0, t.initial.blob.data(), bb0, hipMemcpyHostToDevice, g.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(v->d_slots1, t.cont.slots.data(), sb1, hipMemcpyHostToDevice, g.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(v->d_blob1, t.cont.blob.data(), bb1, hipMemcpyHostToDevice, g.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g.stream);   // (the host tables die with this call, and every context may use the object at once)
-    if (e != hipSuccess) {
-        v->free_device();
-        delete v;
-        return fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
+        return rc;
     }
     *wp_out = reinterpret_cast<latok_wordpiece*>(v);
     return LATOK_OK;
@@ -3208,16 +3197,7 @@ int latok_wordpiece_create(const uint8_t* words, const int64_t* word_off, int64_
 
 int latok_wordpiece_destroy(latok_wordpiece* wp) {
     LATOK_ENTER();
-    WordPiece* v = reinterpret_cast<WordPiece*>(wp);
-    if (!v) return LATOK_OK;
-    int rc = LATOK_OK;
-    if (g.inited) {   // the current context's own work on it: its stream and its flow
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        rc = flow_drain(g);
-    }
-    v->free_device();
-    delete v;
-    return rc;
+    return destroy_object(g, reinterpret_cast<WordPiece*>(wp));
 }
 
 int latok_wordpiece_info(const latok_wordpiece* wp, int64_t* n_words, int64_t* n_slots_initial, int64_t* n_slots_cont, int64_t* max_len_initial,
@@ -3225,8 +3205,8 @@ int latok_wordpiece_info(const latok_wordpiece* wp, int64_t* n_words, int64_t* n
     const WordPiece* v = reinterpret_cast<const WordPiece*>(wp);
     if (!v) return fail(LATOK_ERR_INVALID, "wp is NULL");
     if (n_words) *n_words = v->n_words;
-    if (n_slots_initial) *n_slots_initial = (int64_t)v->n_slots0;
-    if (n_slots_cont) *n_slots_cont = (int64_t)v->n_slots1;
+    if (n_slots_initial) *n_slots_initial = (int64_t)v->initial.n_slots;
+    if (n_slots_cont) *n_slots_cont = (int64_t)v->cont.n_slots;
     if (max_len_initial) *max_len_initial = v->max_len0;
     if (max_len_cont) *max_len_cont = v->max_len1;
     if (prefix_out) memcpy(prefix_out, v->prefix, kWpMaxPrefix);
@@ -3286,8 +3266,8 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
         HIP_TRY(latok::launch_tile_scan(d_cnt, n_str + 1, d_start, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 4,
                                         nullptr, d_err + 1, st));
         latok::WordPieceTables wt;
-        wt.initial = latok::VocabTable{a.wp->d_slots0, (const uint32_t*)a.wp->d_blob0, a.wp->n_slots0, a.wp->seed};
-        wt.cont = latok::VocabTable{a.wp->d_slots1, (const uint32_t*)a.wp->d_blob1, a.wp->n_slots1, a.wp->seed};
+        wt.initial = a.wp->initial.view(a.wp->seed);
+        wt.cont = a.wp->cont.view(a.wp->seed);
         wt.max_len0 = a.wp->max_len0;
         wt.max_len1 = a.wp->max_len1;
         wt.max_chars = a.wp->max_chars;
@@ -3455,12 +3435,12 @@ struct Counter {                   // latok_counter: mutable; calls on it are se
     uint64_t n_slots = 0;
     int max_word_bytes = 0;
     uint32_t seed = 0;
-    void* d_slots = nullptr;       // uint64[n_slots]
-    void* d_counts = nullptr;      // uint64[n_slots]
-    void* d_blob = nullptr;        // uint32[blob_dwords]; dword 0 is reserved
+    DevMem slots;                  // uint64[n_slots]
+    DevMem counts;                 // uint64[n_slots]
+    DevMem blob;                   // uint32[blob_dwords]; dword 0 is reserved
     uint64_t blob_dwords = 0;
     uint64_t cursor = 1;           // dwords of the blob in use
-    void* d_ctl = nullptr;         // uint64[8]: {counted, long, dropped, -, fresh dwords, cursor, distinct, overflow}
+    DevMem ctl;                    // uint64[8]: {counted, long, dropped, -, fresh dwords, cursor, distinct, overflow}
     int64_t totals[4] = {0, 0, 0, 0};   // tokens, counted, long, dropped over all updates
     int64_t distinct = 0;
     int64_t grown = 0;             // times the blob was reallocated (latok_debug_counter_state)
@@ -3468,41 +3448,29 @@ struct Counter {                   // latok_counter: mutable; calls on it are se
 };
 static latok::CountTable count_table_of(const Counter& c) {
     latok::CountTable t;
-    t.slots = (uint64_t*)c.d_slots;
-    t.counts = (unsigned long long*)c.d_counts;
-    t.blob = (uint32_t*)c.d_blob;
+    t.slots = c.slots.as<uint64_t>();
+    t.counts = c.counts.as<unsigned long long>();
+    t.blob = c.blob.as<uint32_t>();
     t.blob_dwords = c.blob_dwords;
     t.n_slots = c.n_slots;
     t.seed = c.seed;
     t.max_word_bytes = c.max_word_bytes;
-    t.tally = (unsigned long long*)c.d_ctl;
-    t.ctl = (unsigned long long*)c.d_ctl + 4;
+    t.tally = c.ctl.as<unsigned long long>();
+    t.ctl = c.ctl.as<unsigned long long>() + 4;
     return t;
-}
-static void counter_free(Counter* c) {
-    for (void* p : {c->d_slots, c->d_counts, c->d_blob, c->d_ctl})
-        if (p) (void)hipFree(p);
-    delete c;
 }
 // empty table, empty blob, zero totals (the device part on `st`, waited for)
 static int counter_reset(Counter& c, hipStream_t st) {
     const uint64_t ctl[8] = {0, 0, 0, 0, 0, 1, 0, 0};
-    HIP_TRY(hipMemsetAsync(c.d_slots, 0, c.n_slots * 8, st));
-    HIP_TRY(hipMemsetAsync(c.d_counts, 0, c.n_slots * 8, st));
-    HIP_TRY(hipMemsetAsync(c.d_blob, 0, 4, st));
-    HIP_TRY(hipMemcpyAsync(c.d_ctl, ctl, sizeof(ctl), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(c.slots.p, 0, c.n_slots * 8, st));
+    HIP_TRY(hipMemsetAsync(c.counts.p, 0, c.n_slots * 8, st));
+    HIP_TRY(hipMemsetAsync(c.blob.p, 0, 4, st));
+    HIP_TRY(hipMemcpyAsync(c.ctl.p, ctl, sizeof(ctl), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
     c.cursor = 1;
     c.distinct = 0;
     for (int64_t& t : c.totals) t = 0;
     c.failed = false;
-    return LATOK_OK;
-}
-// the counter of a call: there is one, it lives on the device of the context that runs the call, and it is not failed
-static int check_counter(const Ctx& g, const Counter& c) {
-    if (c.device != g.device)
-        return fail(LATOK_ERR_INVALID, "the counter lives on device %d, the current context on device %d", c.device, g.device);
-    if (c.failed) return fail(LATOK_ERR_INVALID, "the counter is in the failed state (an update did not finish): latok_counter_clear it");
     return LATOK_OK;
 }
 
@@ -3530,16 +3498,16 @@ int latok_counter_create(int64_t max_words, int max_word_bytes, uint32_t seed, l
     c->seed = seed;
     // the blob starts at 8 bytes per word and grows by need (every commit knows its need before it copies)
     c->blob_dwords = std::max<uint64_t>(64, 2 * (uint64_t)max_words);
-    hipError_t e = hipMalloc(&c->d_slots, c->n_slots * 8);
-    if (e == hipSuccess) e = hipMalloc(&c->d_counts, c->n_slots * 8);
-    if (e == hipSuccess) e = hipMalloc(&c->d_blob, c->blob_dwords * 4);
-    if (e == hipSuccess) e = hipMalloc(&c->d_ctl, 64);
+    hipError_t e = c->slots.alloc(c->n_slots * 8);
+    if (e == hipSuccess) e = c->counts.alloc(c->n_slots * 8);
+    if (e == hipSuccess) e = c->blob.alloc(c->blob_dwords * 4);
+    if (e == hipSuccess) e = c->ctl.alloc(64);
     if (e != hipSuccess) {
-        counter_free(c);
+        delete c;
         return fail(LATOK_ERR_NOMEM, "hipMalloc of a counter of %lld slots failed: %s", (long long)ct_slot_count(max_words), hipGetErrorString(e));
     }
     if ((rc = counter_reset(*c, g.stream))) {
-        counter_free(c);
+        delete c;
         return rc;
     }
     *out = reinterpret_cast<latok_counter*>(c);
@@ -3548,17 +3516,7 @@ int latok_counter_create(int64_t max_words, int max_word_bytes, uint32_t seed, l
 
 int latok_counter_destroy(latok_counter* counter) {
     LATOK_ENTER();
-    Counter* c = reinterpret_cast<Counter*>(counter);
-    if (!c) return LATOK_OK;
-    int rc = LATOK_OK;
-    if (g.inited) {   // the current context's own work: its stream and its flow; whatever they report, the counter is freed
-        const hipError_t e = hipStreamSynchronize(g.stream);
-        rc = flow_drain(g);
-        if (e != hipSuccess) rc = fail(LATOK_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
-    }
-    { std::lock_guard<std::mutex> cl(c->mu); }   // (a call of another context that still holds it has returned)
-    counter_free(c);
-    return rc;
+    return destroy_object(g, reinterpret_cast<Counter*>(counter), &Counter::mu);
 }
 
 int latok_counter_clear(latok_counter* counter) {
@@ -3568,8 +3526,7 @@ int latok_counter_clear(latok_counter* counter) {
     int rc = need_init(g);
     if (rc) return rc;
     std::lock_guard<std::mutex> cl(c->mu);
-    if (c->device != g.device)
-        return fail(LATOK_ERR_INVALID, "the counter lives on device %d, the current context on device %d", c->device, g.device);
+    if ((rc = check_device(g, "counter", c->device))) return rc;
     return counter_reset(*c, g.stream);
 }
 
@@ -3598,7 +3555,7 @@ static int count_scatter_and_commit(Ctx& g, Workspace& w, Counter& c, const Batc
     HIP_TRY(latok::launch_count_scatter((const uint8_t*)d.in.p, t, tp.bits, tp.space, tp.kept, tp.rank, tp.tcnt, tp.pref, tp.words, d.total, d.row,
                                         d.n_str, tp.tile_first, tp.total, (int*)(p_tot + 1), st));
     HIP_TRY(latok::launch_count_commit_sum(t, st));
-    HIP_TRY(hipMemcpyAsync(ctl, c.d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ctl, c.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));   // the first of the call's two waits: the commit's need is known
     int rc;
     int64_t n = 0;
@@ -3607,24 +3564,20 @@ static int count_scatter_and_commit(Ctx& g, Workspace& w, Counter& c, const Batc
     if (need >= (1ull << 32)) return fail(LATOK_ERR_NOMEM, "the counter's words would take 2^34 bytes or more");
     if (need > c.blob_dwords) {          // grow: new allocation, device copy, free
         const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(need, 2 * c.blob_dwords), (1ull << 32) - 1);
-        void* p = nullptr;
-        hipError_t e = hipMalloc(&p, want * 4);
+        DevMem grown;
+        hipError_t e = grown.alloc(want * 4);
         if (e != hipSuccess) return fail(LATOK_ERR_NOMEM, "hipMalloc(%llu) failed: %s", (unsigned long long)(want * 4), hipGetErrorString(e));
-        e = hipMemcpyAsync(p, c.d_blob, c.cursor * 4, hipMemcpyDeviceToDevice, st);
+        e = hipMemcpyAsync(grown.p, c.blob.p, c.cursor * 4, hipMemcpyDeviceToDevice, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            (void)hipFree(p);
-            return fail(LATOK_ERR_HIP, "copying the counter's words failed: %s", hipGetErrorString(e));
-        }
-        (void)hipFree(c.d_blob);
-        c.d_blob = p;
+        if (e != hipSuccess) return fail(LATOK_ERR_HIP, "copying the counter's words failed: %s", hipGetErrorString(e));
+        c.blob = std::move(grown);
         c.blob_dwords = want;
         ++c.grown;
         t = count_table_of(c);
     }
     if (ctl[4] > 0) {                    // (no fresh slot: nothing to copy, the table is resident already)
         HIP_TRY(latok::launch_count_commit_copy((const uint8_t*)d.in.p, t, st));
-        HIP_TRY(hipMemcpyAsync(ctl, c.d_ctl, sizeof(ctl), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ctl, c.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (ctl[7] != 0 || ctl[5] != need) return fail(LATOK_ERR_HIP, "internal: the commit of the counter's words did not add up");
     }
@@ -3647,7 +3600,7 @@ int latok_count_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
     int rc = need_init(g);
     if (rc) return rc;
     std::lock_guard<std::mutex> cl(c->mu);
-    if ((rc = check_counter(g, *c))) return rc;
+    if ((rc = check_device(g, "counter", c->device, c->failed))) return rc;
     BytesCall call;
     if ((rc = call.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
     const hipStream_t st = call.st;
@@ -3659,8 +3612,8 @@ int latok_count_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
     const Batch& d = call.d;
     int64_t* p_tot = call.p_tot;
     Workspace& w = g.ws;
-    HIP_TRY(hipMemsetAsync(c->d_ctl, 0, 40, st));                    // this call's tallies and fresh dwords
-    HIP_TRY(hipMemsetAsync((uint64_t*)c->d_ctl + 7, 0, 8, st));      // ... and the overflow flag
+    HIP_TRY(hipMemsetAsync(c->ctl.p, 0, 40, st));                    // this call's tallies and fresh dwords
+    HIP_TRY(hipMemsetAsync(c->ctl.as<uint64_t>() + 7, 0, 8, st));      // ... and the overflow flag
     TokenPlanes t;
     if ((rc = enqueue_token_front(g, w, d, p_tot, (int*)(p_tot + 1), st, &t))) return rc;
     // from here to the end of the commit the table may hold slots that point into the caller's text
@@ -3686,7 +3639,7 @@ int latok_counter_read(const latok_counter* counter, uint8_t* words_out, int64_t
     int rc = need_init(g);
     if (rc) return rc;
     std::lock_guard<std::mutex> cl(c->mu);
-    if ((rc = check_counter(g, *c))) return rc;
+    if ((rc = check_device(g, "counter", c->device, c->failed))) return rc;
     // not a hot path: slots, counts and blob come to the host and are compacted here, in slot order
     std::vector<uint64_t> slots, counts;
     std::vector<uint32_t> blob;
@@ -3695,7 +3648,7 @@ int latok_counter_read(const latok_counter* counter, uint8_t* words_out, int64_t
     } catch (const std::bad_alloc&) {
         return fail(LATOK_ERR_NOMEM, "out of host memory");
     }
-    HIP_TRY(hipMemcpyAsync(slots.data(), c->d_slots, c->n_slots * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(slots.data(), c->slots.p, c->n_slots * 8, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     int64_t n_words = 0, n_bytes = 0;
     for (const uint64_t v : slots) {
@@ -3716,8 +3669,8 @@ int latok_counter_read(const latok_counter* counter, uint8_t* words_out, int64_t
     } catch (const std::bad_alloc&) {
         return fail(LATOK_ERR_NOMEM, "out of host memory");
     }
-    HIP_TRY(hipMemcpyAsync(counts.data(), c->d_counts, c->n_slots * 8, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipMemcpyAsync(blob.data(), c->d_blob, c->cursor * 4, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(counts.data(), c->counts.p, c->n_slots * 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(blob.data(), c->blob.p, c->cursor * 4, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     int64_t k = 0, at = 0;
     for (uint64_t i = 0; i < c->n_slots; ++i) {

@@ -672,3 +672,74 @@ def test_the_error_text_is_the_threads_own(gpu, shared):
 
         _run_workers([exact, exact, refused], device=_device_of(gpu))
         assert idf.n_docs == 0 and not idf.df().any()
+
+
+# ---- one lifecycle ----------------------------------------------------------------------------------------------------------------------
+LIFE_BLOBS = [b"ab cd ab", b""]                                    # the smallest batch that reaches every object's tables
+LIFE_VOCAB = [b"ab", b"cd", b"ef"]
+LIFE_WP = [b"[UNK]", b"a", b"##b", b"cd", b"##d"]                  # ab -> a ##b, cd -> cd
+
+
+def _life_round(lib, device):
+    """create, one call that reads the object's device memory, info, close, close again -- for each of the four objects; returns what the
+    calls gave, as plain Python"""
+    from latok_amd import batch
+    i64, u32, ci = C.c_int64, C.c_uint32, C.c_int
+    got = {}
+
+    vocab = batch.Vocab(LIFE_VOCAB)
+    got["ids"] = [a.tolist() for a in batch.token_ids_utf8_batch(LIFE_BLOBS, vocab)]
+    n_words, n_slots, seed, dev = i64(-1), i64(-1), u32(7), ci(-1)
+    assert lib.latok_vocab_info(vocab.handle, C.byref(n_words), C.byref(n_slots), C.byref(seed), C.byref(dev)) == 0
+    got["vocab"] = (len(vocab), vocab.n_slots, n_words.value, n_slots.value, seed.value, dev.value)
+
+    wp = batch.WordPiece(LIFE_WP)
+    indptr, ids, spans = batch.wordpiece_ids_utf8_batch(LIFE_BLOBS, wp, unk_id=0)
+    got["wp"] = (indptr.tolist(), ids.tolist(), spans.tolist())
+    got["wp_info"] = wp.info()
+
+    idf = batch.Idf(3)
+    got["nnz"] = idf.update_utf8(LIFE_BLOBS, vocab=vocab)
+    got["df"], got["weights"] = idf.df().tolist(), idf.weights().tolist()
+    n_cols, n_docs = i64(-1), i64(-1)
+    assert lib.latok_idf_info(idf.handle, C.byref(n_cols), C.byref(n_docs), C.byref(dev)) == 0
+    got["idf"] = (n_cols.value, n_docs.value, idf.n_docs, dev.value)
+
+    counter = batch.TokenCounter(4)
+    got["update"] = counter.update_utf8(LIFE_BLOBS)
+    words, counts = counter.items()
+    got["items"] = sorted(zip(words, counts.tolist()))
+    max_words, max_bytes = i64(-1), ci(-1)
+    assert lib.latok_counter_info(counter.handle, C.byref(max_words), C.byref(n_slots), C.byref(max_bytes), C.byref(seed), C.byref(dev), None) == 0
+    got["counter"] = (max_words.value, max_bytes.value, seed.value, dev.value, n_slots.value == counter.n_slots, counter.stats)
+
+    for obj in (counter, idf, wp, vocab):
+        obj.close()
+        assert obj.handle is None
+        obj.close()                                                  # the second close is no call at all
+    assert got["vocab"][5] == got["idf"][3] == got["counter"][3] == got["wp_info"]["device"] == device
+    return got
+
+
+def test_the_four_objects_share_one_lifecycle(gpu):
+    """Vocab, WordPiece, Idf and TokenCounter on the two-string batch: every value is written out here.  The idf weights are
+    ln((n_docs + 1) / (df + 1)) + 1 with n_docs = 2 and df = [1, 1, 0], held to 2^-24 of the largest weight as everywhere in this file.
+    Then the NULL handle, and 32 more rounds on the same context that must give the first round's values bit for bit (the library
+    exposes no free-memory figure: latok_device_props reports the device's total)."""
+    device = _device_of(gpu)
+    first = _life_round(gpu, device)
+    assert first["ids"] == [[0, 1, 0], []]
+    assert first["vocab"] == (3, 64, 3, 64, 0, device)
+    assert first["wp"] == ([0, 5, 5], [1, 2, 3, 1, 2], [[0, 1], [1, 2], [3, 5], [6, 7], [7, 8]])
+    assert first["wp_info"] == dict(n_words=5, n_slots_initial=64, n_slots_cont=64, max_len_initial=5, max_len_cont=1, prefix=b"##", max_chars=100,
+                                    seed=0, device=device)
+    assert first["nnz"] == 2 and first["df"] == [1, 1, 0] and first["idf"] == (3, 2, 2, device)
+    want = np.array([1.4054651081081644, 1.4054651081081644, 2.09861228866811])
+    assert np.abs(np.array(first["weights"]) - want).max() <= 2.0 ** -24 * want.max(), first["weights"]
+    assert first["update"] == dict(tokens=3, counted=3, long=0, dropped=0)
+    assert first["items"] == [(b"ab", 2), (b"cd", 1)]
+    assert first["counter"] == (4, 256, 0, device, True, dict(tokens=3, counted=3, long=0, dropped=0, distinct=2))
+    for destroy in (gpu.latok_vocab_destroy, gpu.latok_wordpiece_destroy, gpu.latok_idf_destroy, gpu.latok_counter_destroy):
+        assert destroy(None) == 0
+    for r in range(32):
+        assert _life_round(gpu, device) == first, r

@@ -1,6 +1,8 @@
 """The judge of tests/test_gpu_shared_objects.py (tests/helpers/shared_state.py) on the CPU: it names the right state for outputs the
 reference made, and it refuses a torn output, an output beyond the bound, a sequence that goes backwards and a corpus whose states cannot
-be told apart.  The corpus is the one the GPU test transforms, so its separability is established here as well."""
+be told apart.  The corpus is the one the GPU test transforms, so its separability is established here as well.  And what the four handle
+classes of latok_amd/batch.py share, without a device: close / with / __del__ over a library that only counts its destroy calls, the
+handle lookup, and the packing of a word list."""
 import itertools
 
 import numpy as np
@@ -168,6 +170,119 @@ def test_counter_items_follows_a_counter_that_grows_between_size_query_and_read(
     assert got == words and counts.tolist() == list(range(1, len(words) + 1)) and counts.dtype == np.uint64     # what the last read saw
     assert fake.calls[0] == (0, 0) and len(fake.calls) == 2 + grow
     assert all(b[0] > a[0] for a, b in zip(fake.calls[1:], fake.calls[2:]))      # every repeat asked with the larger need
+
+
+class _CountingLib:
+    """a library that has nothing but one destroy call: it counts, and fails when told to"""
+
+    def __init__(self, destroy, fail=False):
+        self.destroyed, self.fail = [], fail
+        setattr(self, destroy, self._destroy)
+
+    def _destroy(self, handle):
+        self.destroyed.append(handle)
+        if self.fail:
+            raise RuntimeError("destroy failed")
+        return 0
+
+
+# class, its destroy call, the argument name of its handle lookup (None: it has none), the text of _open() after close()
+HANDLE_CLASSES = [("Vocab", "latok_vocab_destroy", "vocab", "vocab must be an open latok_amd.batch.Vocab"),
+                  ("WordPiece", "latok_wordpiece_destroy", "wp", "wp must be an open latok_amd.batch.WordPiece"),
+                  ("Idf", "latok_idf_destroy", "idf", "the idf is closed"),
+                  ("TokenCounter", "latok_counter_destroy", None, "the TokenCounter is closed")]
+LOOKUP_TEXTS = {"vocab": "vocab must be an open latok_amd.batch.Vocab", "wp": "wp must be an open latok_amd.batch.WordPiece",
+                "idf": "idf must be an open latok_amd.batch.Idf or None"}
+
+
+def _fake(name, destroy, fail=False):
+    from latok_amd import batch
+    cls = getattr(batch, name)
+    obj = cls.__new__(cls)
+    obj._lib, obj.handle = _CountingLib(destroy, fail), 41
+    return obj, obj._lib
+
+
+@pytest.mark.parametrize("name,destroy,arg,closed_text", HANDLE_CLASSES)
+def test_the_four_handle_classes_share_one_lifecycle(name, destroy, arg, closed_text):
+    import re
+    from latok_amd import batch
+    cls = getattr(batch, name)
+    obj, lib = _fake(name, destroy)
+    assert obj._open() == 41
+    if arg:
+        assert batch._handle_of(cls, obj, arg, arg == "idf") == 41
+    obj.close()
+    assert obj.handle is None and lib.destroyed == [41]
+    obj.close()
+    assert lib.destroyed == [41]                                    # close() twice destroys once
+    obj.__del__()
+    assert lib.destroyed == [41]                                    # ... and __del__ after close() destroys nothing
+    with pytest.raises(ValueError, match="^%s$" % re.escape(closed_text)):
+        obj._open()
+    if arg:
+        for bad in (obj, object(), 41) + (() if arg == "idf" else (None,)):
+            with pytest.raises(ValueError, match="^%s$" % re.escape(LOOKUP_TEXTS[arg])):
+                batch._handle_of(cls, bad, arg, arg == "idf")
+
+    obj, lib = _fake(name, destroy)
+    with obj as entered:
+        assert entered is obj and lib.destroyed == []
+    assert lib.destroyed == [41] and obj.handle is None             # leaving the block destroys once
+    assert obj.__exit__(None, None, None) is False and lib.destroyed == [41]
+
+    obj, lib = _fake(name, destroy, fail=True)
+    obj.__del__()                                                   # swallows what destroy raises
+    assert lib.destroyed == [41] and obj.handle is None
+    obj, lib = _fake(name, destroy, fail=True)
+    with pytest.raises(RuntimeError, match="destroy failed"):
+        obj.close()                                                 # ... close() itself does not; the handle is gone all the same
+    assert obj.handle is None
+
+    bare = cls.__new__(cls)                                         # what the host tests build: nothing but a handle
+    bare.handle = None
+    bare.close()
+    bare.__del__()
+    with pytest.raises(ValueError, match="^%s$" % re.escape(closed_text)):
+        bare._open()
+
+
+def test_the_idf_lookup_takes_none():
+    from latok_amd import batch
+    assert batch._handle_of(batch.Idf, None, "idf", True) is None
+
+
+def _same_array(got, want, dtype):
+    assert isinstance(got, np.ndarray) and got.dtype == dtype and got.flags.c_contiguous and got.tolist() == want, (got, want)
+
+
+def test_the_word_packer_yields_the_arrays_the_create_calls_take():
+    from latok_amd import batch
+    data, off, ids = batch._pack_words([], None)
+    _same_array(data, [], np.uint8), _same_array(off, [0], np.int64)
+    assert ids is None
+    data, off, ids = batch._pack_words([], [])                      # (no word: an empty float array is no wrong dtype)
+    _same_array(ids, [], np.int32)
+    data, off, ids = batch._pack_words([b""], [7])
+    _same_array(data, [], np.uint8), _same_array(off, [0, 0], np.int64), _same_array(ids, [7], np.int32)
+    # str goes through UTF-8 with surrogatepass, bytes stay as they are (valid or not)
+    data, off, ids = batch._pack_words(["a\ud800", b"\xffz", bytearray(b""), "é"], np.array([5, -1, -2 ** 31, 2 ** 31 - 1], np.int64))
+    _same_array(data, [0x61, 0xED, 0xA0, 0x80, 0xFF, 0x7A, 0xC3, 0xA9], np.uint8)
+    _same_array(off, [0, 4, 6, 6, 8], np.int64)
+    _same_array(ids, [5, -1, -2 ** 31, 2 ** 31 - 1], np.int32)
+    _same_array(batch._pack_words(iter([b"x", b"y"]), np.arange(4, dtype=np.uint16)[::2])[2], [0, 2], np.int32)    # a generator; strided ids
+    for bad in ([1], [1, 2, 3], [[1, 2]], [1.0, 2.0], ["1", "2"], [None, 1]):
+        with pytest.raises(ValueError, match="^ids must be one integer per word$"):
+            batch._pack_words([b"x", b"y"], bad)
+    for bad in ([0, 2 ** 31], [-2 ** 31 - 1, 0], np.array([0, 2 ** 31], np.uint32)):
+        with pytest.raises(ValueError, match="^ids must fit int32$"):
+            batch._pack_words([b"x", b"y"], bad)
+    # Idf.load shares the range check, with its own words
+    _same_array(batch._int32_each(np.array([3, 0], np.int64), 2, "df", "column"), [3, 0], np.int32)
+    with pytest.raises(ValueError, match="^df must be one integer per column$"):
+        batch._int32_each([1.0, 2.0], 2, "df", "column")
+    with pytest.raises(ValueError, match="^df must fit int32$"):
+        batch._int32_each([0, 2 ** 31], 2, "df", "column")
 
 
 def test_a_corpus_that_cannot_tell_its_states_apart_fires_the_precondition(corpus):
