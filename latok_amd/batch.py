@@ -517,15 +517,45 @@ def fold_batch(texts, fold=FOLD_UNCASED):
     return [r.decode("utf-8", "surrogatepass") for r in rows]
 
 
+class _HostBatch:
+    """A host batch as a sized call takes it: ``lib``, ``u8`` / ``off`` / ``n_str`` / ``total`` and the call's base ``flags``; the
+    call's outputs come from ``out`` (``zero``: the per-string arrays, which start at 0 on the host) and reach the caller through
+    ``fetch``.  Here they are plain numpy arrays that the library fills itself: nothing is allocated on the device and nothing
+    copied beyond what the library call does."""
+
+    flags = 0
+    lib = property(lambda self: _lib.ensure_init())   # (asked for by the call that needs it; Idf.update_utf8 calls through its own)
+
+    def __init__(self, utf8, byte_off):
+        self._arrays = utf8, byte_off = _csr_u8(utf8, byte_off)
+        self.n_str = byte_off.size - 1
+        self.total = int(byte_off[-1]) if self.n_str > 0 else 0
+        self.u8, self.off = _ptr(utf8), _ptr(byte_off)
+
+    def out(self, shape, dtype, zero=False):
+        return (np.zeros if zero else np.empty)(shape, dtype)
+
+    def fetch(self, buf, n=None):
+        """the output itself, or a copy of its first ``n`` rows (never a view of an oversized buffer)"""
+        return buf if n is None else buf[:n].copy()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+
 class _DeviceFolded:
-    """A host batch folded into device memory, and the device buffers of the call that reads it: the batch is uploaded once and
-    folded there (``latok_fold_utf8_bytes_batch`` with device pointers); ``u8`` / ``off`` / ``n_str`` / ``total`` describe the folded
-    batch for a ``LATOK_DEVICE_PTRS`` call, whose outputs come from ``alloc`` and reach the host through ``fetch``.  No folded byte
-    visits the host.  Everything is freed on leaving the ``with`` block."""
+    """The interface of _HostBatch over a host batch folded into device memory: the batch is uploaded once and folded there
+    (``latok_fold_utf8_bytes_batch`` with device pointers); the call runs with ``LATOK_DEVICE_PTRS`` on device buffers, which
+    ``fetch`` copies to the host.  No folded byte visits the host.  Everything is freed on leaving the ``with`` block."""
+
+    flags = _lib.DEVICE_PTRS
 
     def __init__(self, utf8, byte_off, fold):
         utf8, byte_off = _csr_u8(utf8, byte_off)
-        self.lib, self._bufs = _lib.ensure_init(), []
+        self.lib, self._bufs, self._outs = _lib.ensure_init(), [], {}
         self.n_str = byte_off.size - 1
         total = int(byte_off[-1]) if self.n_str > 0 else 0
         try:
@@ -549,10 +579,17 @@ class _DeviceFolded:
         self._bufs.append(p)
         return p
 
-    def fetch(self, ptr, shape, dtype):
-        out = np.empty(shape, dtype)
+    def out(self, shape, dtype, zero=False):
+        shape = shape if isinstance(shape, tuple) else (int(shape),)
+        p = self.alloc(int(np.prod(shape)) * np.dtype(dtype).itemsize)
+        self._outs[p] = shape, dtype
+        return p
+
+    def fetch(self, buf, n=None):
+        shape, dtype = self._outs[buf]
+        out = np.empty(shape if n is None else (n,) + shape[1:], dtype)
         if out.nbytes > 0:
-            _lib.check(self.lib.latok_memcpy_d2h(_ptr(out), ptr, out.nbytes))
+            _lib.check(self.lib.latok_memcpy_d2h(_ptr(out), buf, out.nbytes))
         return out
 
     def close(self):
@@ -568,17 +605,27 @@ class _DeviceFolded:
         return False
 
 
+def _batch_on(utf8, byte_off, fold):
+    """the batch of a sized call: the host arrays as they are, or (``fold``, FOLD_* flags) their folded image in device memory"""
+    return _DeviceFolded(utf8, byte_off, fold) if fold else _HostBatch(utf8, byte_off)
+
+
+def _arg(buf):
+    """an output of ``out`` (or None) as a ctypes argument"""
+    return _ptr(buf) if isinstance(buf, np.ndarray) else buf
+
+
 def _size_then_fill(call, n, alloc):
     """The capacity protocol of the sized calls.  ``call()`` is the size query (no buffer, cap = 0): it reports its need into ``n``, a
-    c_int64, and may refuse the capacity.  ``alloc(need)`` then makes the payload buffers -- numpy arrays, ``_DeviceFolded.alloc``
-    pointers or None -- and ``call(*buffers, need)`` fills them, unless nothing is needed.  Returns (need, buffers)."""
+    c_int64, and may refuse the capacity.  ``alloc(need)`` then makes the payload buffers -- outputs of the batch's ``out``, or
+    None -- and ``call(*buffers, need)`` fills them, unless nothing is needed.  Returns (need, buffers)."""
     rc = call()
     if rc != _lib.OK and not (rc == _lib.ERR_INVALID and n.value > 0):
         _lib.check(rc)
     need = n.value
     bufs = alloc(need)
     if need > 0:
-        _lib.check(call(*[_ptr(b) if isinstance(b, np.ndarray) else b for b in bufs], need))
+        _lib.check(call(*[_arg(b) for b in bufs], need))
     return need, bufs
 
 
@@ -746,22 +793,18 @@ class Vocab(_DeviceObject):
         return self._n
 
 
-def _ids_csr(utf8, byte_off, vocab, unk_id, dtype, want_spans):
+def _ids_csr(utf8, byte_off, vocab, unk_id, dtype, want_spans, fold=0):
     utf8, byte_off = _csr_u8(utf8, byte_off)
     unk_id = _unk32(unk_id)
     dt, flags = _out_dtype(dtype)
     handle = _handle_of(Vocab, vocab, "vocab")
-    n_str = byte_off.size - 1
-    total = int(byte_off[-1]) if n_str > 0 else 0
-    lib = _lib.ensure_init()
-    cap = max(total, 1)                                  # a token has at least one byte
-    counts = np.zeros(n_str, dt)
-    ids = np.empty(cap, np.int32)
-    spans = np.empty((cap, 2), dt) if want_spans else None
-    n = C.c_int64(0)
-    _lib.check(lib.latok_token_ids_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, handle, unk_id, _ptr(counts),
-                                                    _ptr(spans) if want_spans else None, _ptr(ids), cap, C.byref(n), flags, None))
-    return counts, ids[:n.value].copy(), (spans[:n.value].copy() if want_spans else None)
+    with _batch_on(utf8, byte_off, fold) as b:
+        cap = max(b.total, 1)                            # a token has at least one byte
+        counts, ids, spans = b.out(b.n_str, dt, True), b.out(cap, np.int32), (b.out((cap, 2), dt) if want_spans else None)
+        n = C.c_int64(0)
+        _lib.check(b.lib.latok_token_ids_utf8_bytes_batch(b.u8, b.off, b.n_str, b.total, handle, unk_id, _arg(counts), _arg(spans), _arg(ids), cap,
+                                                          C.byref(n), flags | b.flags, None))
+        return b.fetch(counts), b.fetch(ids, n.value), (b.fetch(spans, n.value) if want_spans else None)
 
 
 def token_ids_utf8_csr(utf8, byte_off, vocab, unk_id=-1, dtype=np.int64, spans=False):
@@ -773,18 +816,6 @@ def token_ids_utf8_csr(utf8, byte_off, vocab, unk_id=-1, dtype=np.int64, spans=F
     return (counts, ids, sp) if spans else (counts, ids)
 
 
-def _ids_csr_folded(utf8, byte_off, vocab, unk_id, fold):
-    """_ids_csr (int64, no spans) of the batch folded on the device"""
-    handle = _handle_of(Vocab, vocab, "vocab")
-    with _DeviceFolded(utf8, byte_off, fold) as d:
-        cap = max(d.total, 1)
-        counts, ids = d.alloc(d.n_str * 8), d.alloc(cap * 4)
-        n = C.c_int64(0)
-        _lib.check(d.lib.latok_token_ids_utf8_bytes_batch(d.u8, d.off, d.n_str, d.total, handle, unk_id, counts, None, ids, cap, C.byref(n),
-                                                          _lib.DEVICE_PTRS, None))
-        return d.fetch(counts, d.n_str, np.int64), d.fetch(ids, n.value, np.int32), None
-
-
 def token_ids_utf8_batch(blobs, vocab, unk_id=-1, fold=0):
     """list[bytes] (UTF-8) -> list of int32 arrays: the ids of every string's tokens ('' and whitespace-only -> empty).  ``fold``
     (FOLD_* flags): the batch is folded on the device first (fold_utf8_batch) and the tokens are those of the folded strings."""
@@ -793,7 +824,7 @@ def token_ids_utf8_batch(blobs, vocab, unk_id=-1, fold=0):
     if len(blobs) == 0:
         return []
     utf8, byte_off = pack_utf8(blobs)
-    counts, ids, _ = _ids_csr_folded(utf8, byte_off, vocab, unk_id, fold) if fold else _ids_csr(utf8, byte_off, vocab, unk_id, np.int64, False)
+    counts, ids, _ = _ids_csr(utf8, byte_off, vocab, unk_id, np.int64, False, fold)
     return np.split(ids, np.cumsum(counts)[:-1])
 
 
@@ -827,54 +858,41 @@ def _ngram_spec(ngram_range, sep):
     return None if (min_n, max_n) == (1, 1) else (min_n, max_n, sep)
 
 
-def _terms_call(lib, ng, hashed, u8, off, n_str, total, vocab, indptr, oov, indices, data, cap, nnz, flags):
-    """one call of the term counts: the n-gram entry points when ``ng`` is set, else the existing ones exactly as they were"""
-    if hashed:
-        seed, n_features, alternate_sign = hashed
-        if ng:
-            return lib.latok_hashed_ngram_counts_utf8_bytes_batch(u8, off, n_str, total, seed, n_features, 1 if alternate_sign else 0, ng[0], ng[1],
-                                                                  ng[2], indptr, indices, data, cap, C.byref(nnz), None, flags, None)
-        return lib.latok_hashed_term_counts_utf8_bytes_batch(u8, off, n_str, total, seed, n_features, 1 if alternate_sign else 0, indptr, indices,
-                                                             data, cap, C.byref(nnz), None, flags, None)
-    if ng:
-        return lib.latok_ngram_counts_utf8_bytes_batch(u8, off, n_str, total, vocab, ng[0], ng[1], ng[2], indptr, oov, indices, data, cap,
-                                                       C.byref(nnz), None, flags, None)
-    return lib.latok_term_counts_utf8_bytes_batch(u8, off, n_str, total, vocab, indptr, oov, indices, data, cap, C.byref(nnz), None, flags, None)
-
-
-def _terms_csr_folded(utf8, byte_off, vocab, hashed, fold, ng=None):
-    """_terms_csr (int64) of the batch folded on the device: the size query, then the fill, on device buffers"""
-    with _DeviceFolded(utf8, byte_off, fold) as d:
-        lib, n_str = d.lib, d.n_str
-        indptr = d.alloc((n_str + 1) * 8)
-        oov = None if hashed else d.alloc(n_str * 8)
+def _rows_csr(utf8, byte_off, fold, dtype, hashed, data_dtype, entry):
+    """The sized CSR families (term counts, TF-IDF) on either batch: the size query, then the fill -> (indptr, indices, data, oov or
+    None).  ``entry(b, indptr, oov, indices, data, cap, nnz, flags)`` is the library call on batch ``b``."""
+    dt, flags = _out_dtype(dtype)
+    with _batch_on(utf8, byte_off, fold) as b:
+        indptr, oov = b.out(b.n_str + 1, dt, True), None if hashed else b.out(b.n_str, dt, True)
         nnz = C.c_int64(0)
 
         def call(indices=None, data=None, cap=0):
-            return _terms_call(lib, ng, hashed, d.u8, d.off, n_str, d.total, vocab, indptr, oov, indices, data, cap, nnz, _lib.DEVICE_PTRS)
+            return entry(b, _arg(indptr), _arg(oov), indices, data, cap, nnz, flags | b.flags)
 
-        need, (indices, data) = _size_then_fill(call, nnz, lambda k: (d.alloc(k * 4), d.alloc(k * 4)))
-        return (d.fetch(indptr, n_str + 1, np.int64), d.fetch(indices, need, np.int32), d.fetch(data, need, np.int32),
-                None if hashed else d.fetch(oov, n_str, np.int64))
+        _, (indices, data) = _size_then_fill(call, nnz, lambda k: (b.out(k, np.int32), b.out(k, data_dtype)))
+        return b.fetch(indptr), b.fetch(indices), b.fetch(data), None if hashed else b.fetch(oov)
 
 
-def _terms_csr(utf8, byte_off, vocab, hashed, dtype, ng=None):
-    """the size query, then the fill -> (indptr, indices, data, oov or None)"""
+def _terms_call(b, ng, hashed, vocab, indptr, oov, indices, data, cap, nnz, flags):
+    """one call of the term counts: the n-gram entry points when ``ng`` is set, else the existing ones exactly as they were"""
+    lib, batch = b.lib, (b.u8, b.off, b.n_str, b.total)
+    if hashed:
+        seed, n_features, alternate_sign = hashed
+        if ng:
+            return lib.latok_hashed_ngram_counts_utf8_bytes_batch(*batch, seed, n_features, 1 if alternate_sign else 0, ng[0], ng[1], ng[2], indptr,
+                                                                  indices, data, cap, C.byref(nnz), None, flags, None)
+        return lib.latok_hashed_term_counts_utf8_bytes_batch(*batch, seed, n_features, 1 if alternate_sign else 0, indptr, indices, data, cap,
+                                                             C.byref(nnz), None, flags, None)
+    if ng:
+        return lib.latok_ngram_counts_utf8_bytes_batch(*batch, vocab, ng[0], ng[1], ng[2], indptr, oov, indices, data, cap, C.byref(nnz), None, flags,
+                                                       None)
+    return lib.latok_term_counts_utf8_bytes_batch(*batch, vocab, indptr, oov, indices, data, cap, C.byref(nnz), None, flags, None)
+
+
+def _terms_csr(utf8, byte_off, vocab, hashed, dtype, ng=None, fold=0):
+    """(indptr, indices, data, oov or None) of the batch, or (``fold``) of its folded image"""
     utf8, byte_off = _csr_u8(utf8, byte_off)
-    dt, flags = _out_dtype(dtype)
-    n_str = byte_off.size - 1
-    total = int(byte_off[-1]) if n_str > 0 else 0
-    lib = _lib.ensure_init()
-    indptr = np.zeros(n_str + 1, dt)
-    oov = None if hashed else np.zeros(n_str, dt)
-    nnz = C.c_int64(0)
-
-    def call(indices=None, data=None, cap=0):
-        return _terms_call(lib, ng, hashed, _ptr(utf8), _ptr(byte_off), n_str, total, vocab, _ptr(indptr), None if hashed else _ptr(oov), indices,
-                           data, cap, nnz, flags)
-
-    _, (indices, data) = _size_then_fill(call, nnz, lambda k: (np.empty(k, np.int32), np.empty(k, np.int32)))
-    return indptr, indices, data, oov
+    return _rows_csr(utf8, byte_off, fold, dtype, hashed, np.int32, lambda b, *out: _terms_call(b, ng, hashed, vocab, *out))
 
 
 def term_counts_utf8_csr(utf8, byte_off, vocab, dtype=np.int64, ngram_range=(1, 1), sep=b" "):
@@ -882,8 +900,8 @@ def term_counts_utf8_csr(utf8, byte_off, vocab, dtype=np.int64, ngram_range=(1, 
     canonical CSR matrix -- row s holds the distinct vocabulary ids of its tokens (the byte slices token_spans_utf8_bytes_csr
     reports), ascending, each with its count; ``oov[s]`` counts the tokens the vocabulary does not hold.  What
     ``CountVectorizer(vocabulary=...).transform`` returns: ``scipy.sparse.csr_matrix((data, indices, indptr), shape=(n, n_cols))``.
-    indptr and oov in ``dtype``.  Cut, looked up, sorted and reduced on the device (``latok_term_counts_utf8_bytes_batch``).  ``ngram_range=(min_n, max_n)`` (up to
-    (8, 8)) counts word n-grams instead: every run of n neighbouring tokens of a string joined by the one-byte ``sep``, for every n
+    indptr and oov in ``dtype``.  Cut, looked up, sorted and reduced on the device (``latok_term_counts_utf8_bytes_batch``).
+    ``ngram_range=(min_n, max_n)`` (up to (8, 8)) counts word n-grams instead: every run of n neighbouring tokens of a string joined by the one-byte ``sep``, for every n
     in the range, looked up or hashed as one term -- scikit-learn's ``ngram_range`` (``latok_ngram_counts_utf8_bytes_batch`` /
     ``latok_hashed_ngram_counts_utf8_bytes_batch``); (1, 1) takes the plain calls.
     A vocabulary word may hold the separator (``b"new york"``)."""
@@ -897,9 +915,7 @@ def term_counts_utf8_batch(blobs, vocab, fold=0, ngram_range=(1, 1), sep=b" "):
     grams are those of the folded strings."""
     handle, fold, ng = _handle_of(Vocab, vocab, "vocab"), _fold_bits(fold), _ngram_spec(ngram_range, sep)
     utf8, byte_off = pack_utf8(blobs)
-    if fold:
-        return _terms_csr_folded(utf8, byte_off, handle, None, fold, ng)
-    return _terms_csr(utf8, byte_off, handle, None, np.int64, ng)
+    return _terms_csr(utf8, byte_off, handle, None, np.int64, ng, fold)
 
 
 def term_counts_batch(texts, vocab, ngram_range=(1, 1), sep=b" "):
@@ -914,10 +930,8 @@ def hashed_term_counts_utf8_csr(utf8, byte_off, n_features=1 << 20, seed=0, alte
     column = ``abs(h) % n_features``, value = ``+1`` or (``alternate_sign`` and h < 0) ``-1``, h = MurmurHash3 x86_32 of the token's
     bytes with ``seed`` as int32; a row's columns ascend and a sum may be an explicit 0.  What ``HashingVectorizer(norm=None)
     .transform`` returns: ``scipy.sparse.csr_matrix((data, indices, indptr), shape=(n, n_features))``.  indptr in ``dtype``.  Cut,
-    hashed, sorted and reduced on the device (``latok_hashed_term_counts_utf8_bytes_batch``).  ``ngram_range=(min_n, max_n)`` (up to
-    (8, 8)) counts word n-grams instead: every run of n neighbouring tokens of a string joined by the one-byte ``sep``, for every n
-    in the range, looked up or hashed as one term -- scikit-learn's ``ngram_range`` (``latok_ngram_counts_utf8_bytes_batch`` /
-    ``latok_hashed_ngram_counts_utf8_bytes_batch``); (1, 1) takes the plain calls."""
+    hashed, sorted and reduced on the device (``latok_hashed_term_counts_utf8_bytes_batch``).  ``ngram_range``, ``sep``: word n-grams,
+    as in term_counts_utf8_csr."""
     return _terms_csr(utf8, byte_off, None, (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), dtype, _ngram_spec(ngram_range, sep))[:3]
 
 
@@ -927,9 +941,7 @@ def hashed_term_counts_utf8_batch(blobs, n_features=1 << 20, seed=0, alternate_s
     as in hashed_term_counts_utf8_csr; the grams are those of the folded strings."""
     hashed, fold, ng = (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), _fold_bits(fold), _ngram_spec(ngram_range, sep)
     utf8, byte_off = pack_utf8(blobs)
-    if fold:
-        return _terms_csr_folded(utf8, byte_off, None, hashed, fold, ng)[:3]
-    return _terms_csr(utf8, byte_off, None, hashed, np.int64, ng)[:3]
+    return _terms_csr(utf8, byte_off, None, hashed, np.int64, ng, fold)[:3]
 
 
 def hashed_term_counts_batch(texts, n_features=1 << 20, seed=0, alternate_sign=True, ngram_range=(1, 1), sep=b" "):
@@ -996,15 +1008,9 @@ class Idf(_DeviceObject):
         fold, ng = _fold_bits(fold), _ngram_spec(ngram_range, sep) or (1, 1, _sep_byte(sep))
         h, nnz = self._open(), C.c_int64(0)
         utf8, byte_off = pack_utf8(blobs)
-        if fold:
-            with _DeviceFolded(utf8, byte_off, fold) as d:
-                _lib.check(d.lib.latok_idf_update_utf8_bytes_batch(d.u8, d.off, d.n_str, d.total, handle, seed, n_feat, ng[0], ng[1], ng[2], h,
-                                                                   C.byref(nnz), None, _lib.DEVICE_PTRS, None))
-            return nnz.value
-        utf8, byte_off = _csr_u8(utf8, byte_off)
-        n_str = byte_off.size - 1
-        _lib.check(self._lib.latok_idf_update_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, int(byte_off[-1]) if n_str > 0 else 0, handle,
-                                                               seed, n_feat, ng[0], ng[1], ng[2], h, C.byref(nnz), None, 0, None))
+        with _batch_on(utf8, byte_off, fold) as b:
+            _lib.check(self._lib.latok_idf_update_utf8_bytes_batch(b.u8, b.off, b.n_str, b.total, handle, seed, n_feat, ng[0], ng[1], ng[2], h,
+                                                                   C.byref(nnz), None, b.flags, None))
         return nnz.value
 
     def update(self, texts, **kw):
@@ -1051,44 +1057,17 @@ def tfidf_csr(indptr, indices, data, idf=None, smooth_idf=True, sublinear_tf=Fal
     return out
 
 
-def _tfidf_call(lib, hashed, u8, off, n_str, total, vocab, ng, idf, opts, indptr, oov, indices, data, cap, nnz, flags):
-    if hashed:
-        seed, n_features, alternate_sign = hashed
-        return lib.latok_hashed_tfidf_utf8_bytes_batch(u8, off, n_str, total, seed, n_features, 1 if alternate_sign else 0, ng[0], ng[1], ng[2], idf,
-                                                       opts, indptr, indices, data, cap, C.byref(nnz), flags, None)
-    return lib.latok_tfidf_utf8_bytes_batch(u8, off, n_str, total, vocab, ng[0], ng[1], ng[2], idf, opts, indptr, oov, indices, data, cap,
-                                            C.byref(nnz), flags, None)
-
-
 def _tfidf_rows(utf8, byte_off, vocab, hashed, idf, opts, fold, ng, dtype):
     """the size query, then the fill -> (indptr, indices, data float32, oov or None); folded batches run on device buffers"""
-    dt, flags = _out_dtype(dtype)
-    nnz = C.c_int64(0)
-    if fold:
-        with _DeviceFolded(utf8, byte_off, fold) as d:
-            n_str = d.n_str
-            indptr, oov = d.alloc((n_str + 1) * dt.itemsize), None if hashed else d.alloc(n_str * dt.itemsize)
+    def entry(b, indptr, oov, indices, data, cap, nnz, flags):
+        if hashed:
+            seed, n_features, alternate_sign = hashed
+            return b.lib.latok_hashed_tfidf_utf8_bytes_batch(b.u8, b.off, b.n_str, b.total, seed, n_features, 1 if alternate_sign else 0, ng[0],
+                                                             ng[1], ng[2], idf, opts, indptr, indices, data, cap, C.byref(nnz), flags, None)
+        return b.lib.latok_tfidf_utf8_bytes_batch(b.u8, b.off, b.n_str, b.total, vocab, ng[0], ng[1], ng[2], idf, opts, indptr, oov, indices, data,
+                                                  cap, C.byref(nnz), flags, None)
 
-            def call(indices=None, data=None, cap=0):
-                return _tfidf_call(d.lib, hashed, d.u8, d.off, n_str, d.total, vocab, ng, idf, opts, indptr, oov, indices, data, cap, nnz,
-                                   flags | _lib.DEVICE_PTRS)
-
-            need, (indices, data) = _size_then_fill(call, nnz, lambda k: (d.alloc(k * 4), d.alloc(k * 4)))
-            return (d.fetch(indptr, n_str + 1, dt), d.fetch(indices, need, np.int32), d.fetch(data, need, np.float32),
-                    None if hashed else d.fetch(oov, n_str, dt))
-    utf8, byte_off = _csr_u8(utf8, byte_off)
-    n_str = byte_off.size - 1
-    total = int(byte_off[-1]) if n_str > 0 else 0
-    lib = _lib.ensure_init()
-    indptr = np.zeros(n_str + 1, dt)
-    oov = None if hashed else np.zeros(n_str, dt)
-
-    def call(indices=None, data=None, cap=0):
-        return _tfidf_call(lib, hashed, _ptr(utf8), _ptr(byte_off), n_str, total, vocab, ng, idf, opts, _ptr(indptr),
-                           None if hashed else _ptr(oov), indices, data, cap, nnz, flags)
-
-    _, (indices, data) = _size_then_fill(call, nnz, lambda k: (np.empty(k, np.int32), np.empty(k, np.float32)))
-    return indptr, indices, data, oov
+    return _rows_csr(utf8, byte_off, fold, dtype, hashed, np.float32, entry)
 
 
 def _tfidf_ng(ngram_range, sep):
@@ -1193,43 +1172,30 @@ class WordPiece(_DeviceObject):
         return self._n
 
 
+def _wordpiece_ids(utf8, byte_off, wp, unk_id, dtype, spans, fold=0):
+    """the size query, then the fill -> (indptr, ids, spans or None) of the batch, or (``fold``) of its folded image"""
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    unk_id = _unk32(unk_id)
+    dt, flags = _out_dtype(dtype)
+    handle = _handle_of(WordPiece, wp, "wp")
+    with _batch_on(utf8, byte_off, fold) as b:
+        indptr, n = b.out(b.n_str + 1, dt, True), C.c_int64(0)
+
+        def call(ids=None, sp=None, cap=0):
+            return b.lib.latok_wordpiece_ids_utf8_bytes_batch(b.u8, b.off, b.n_str, b.total, handle, unk_id, _arg(indptr), ids, sp, cap, C.byref(n),
+                                                              None, flags | b.flags, None)
+
+        _, (ids, sp) = _size_then_fill(call, n, lambda k: (b.out(k, np.int32), b.out((k, 2), dt) if spans else None))
+        return b.fetch(indptr), b.fetch(ids), (b.fetch(sp) if spans else None)
+
+
 def wordpiece_ids_utf8_csr(utf8, byte_off, wp, unk_id=-1, dtype=np.int64, spans=True):
     """(indptr[n + 1], ids int32[n_pieces], spans[n_pieces, 2] or None): the WordPiece ids of every string -- each token (the byte
     slices token_spans_utf8_bytes_csr reports) cut greedily into the longest word of ``wp`` and ``prefix``-continuations, or ONE
     ``unk_id`` piece when a part of it matches nothing or it has more than ``max_chars`` chars.  spans[r] = piece r's byte range
     inside its string.  indptr and spans in ``dtype``.  Cut and looked up on the device (``latok_wordpiece_ids_utf8_bytes_batch``):
     the size query, then the fill."""
-    utf8, byte_off = _csr_u8(utf8, byte_off)
-    unk_id = _unk32(unk_id)
-    dt, flags = _out_dtype(dtype)
-    handle = _handle_of(WordPiece, wp, "wp")
-    n_str = byte_off.size - 1
-    total = int(byte_off[-1]) if n_str > 0 else 0
-    lib = _lib.ensure_init()
-    indptr = np.zeros(n_str + 1, dt)
-    n = C.c_int64(0)
-
-    def call(ids=None, sp=None, cap=0):
-        return lib.latok_wordpiece_ids_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, handle, unk_id, _ptr(indptr), ids, sp, cap,
-                                                        C.byref(n), None, flags, None)
-
-    _, (ids, sp) = _size_then_fill(call, n, lambda k: (np.empty(k, np.int32), np.empty((k, 2), dt) if spans else None))
-    return indptr, ids, sp
-
-
-def _wordpiece_ids_folded(utf8, byte_off, wp, unk_id, fold):
-    """wordpiece_ids_utf8_csr (int64, with spans) of the batch folded on the device: the size query, then the fill, on device buffers"""
-    handle = _handle_of(WordPiece, wp, "wp")
-    with _DeviceFolded(utf8, byte_off, fold) as d:
-        indptr = d.alloc((d.n_str + 1) * 8)
-        n = C.c_int64(0)
-
-        def call(ids=None, sp=None, cap=0):
-            return d.lib.latok_wordpiece_ids_utf8_bytes_batch(d.u8, d.off, d.n_str, d.total, handle, unk_id, indptr, ids, sp, cap, C.byref(n), None,
-                                                              _lib.DEVICE_PTRS, None)
-
-        need, (ids, sp) = _size_then_fill(call, n, lambda k: (d.alloc(k * 4), d.alloc(k * 16)))
-        return d.fetch(indptr, d.n_str + 1, np.int64), d.fetch(ids, need, np.int32), d.fetch(sp, (need, 2), np.int64)
+    return _wordpiece_ids(utf8, byte_off, wp, unk_id, dtype, spans)
 
 
 def wordpiece_ids_utf8_batch(blobs, wp, unk_id=-1, fold=0):
@@ -1239,9 +1205,7 @@ def wordpiece_ids_utf8_batch(blobs, wp, unk_id=-1, fold=0):
     unk_id, fold = _unk32(unk_id), _fold_bits(fold)
     _handle_of(WordPiece, wp, "wp")
     utf8, byte_off = pack_utf8(blobs)
-    if fold:
-        return _wordpiece_ids_folded(utf8, byte_off, wp, unk_id, fold)
-    return wordpiece_ids_utf8_csr(utf8, byte_off, wp, unk_id)
+    return _wordpiece_ids(utf8, byte_off, wp, unk_id, np.int64, True, fold)
 
 
 def wordpiece_ids_batch(texts, wp, unk_id=-1, fold=0):
@@ -1265,22 +1229,13 @@ def wordpiece_encode_utf8_batch(blobs, wp, max_length, cls_id=None, sep_id=None,
         raise ValueError("max_length must be an int >= %d" % (1 + 2 * special))
     handle = _handle_of(WordPiece, wp, "wp")
     utf8, byte_off = pack_utf8(blobs)
-    n_str, total = len(blobs), int(byte_off[-1])
-    lib = _lib.ensure_init()
-    if fold and n_str > 0:
-        with _DeviceFolded(utf8, byte_off, fold) as d:
-            d_ids, d_len = d.alloc(n_str * int(max_length) * 4), d.alloc(n_str * 4)
-            _lib.check(lib.latok_wordpiece_padded_utf8_bytes_batch(d.u8, d.off, n_str, d.total, handle, unk_id, int(max_length), 1 if special else 0,
-                                                                   cls_id, sep_id, pad_id, d_ids, d_len, None, _lib.DEVICE_PTRS, None))
-            input_ids, lengths = d.fetch(d_ids, (n_str, int(max_length)), np.int32), d.fetch(d_len, n_str, np.int32)
-        mask = (np.arange(int(max_length), dtype=np.int32)[None, :] < lengths[:, None]).astype(np.int32)
-        return input_ids, mask
-    input_ids = np.empty((n_str, int(max_length)), np.int32)
-    lengths = np.zeros(n_str, np.int32)
-    _lib.check(lib.latok_wordpiece_padded_utf8_bytes_batch(_ptr(utf8), _ptr(byte_off), n_str, total, handle, unk_id, int(max_length),
-                                                           1 if special else 0, cls_id, sep_id, pad_id, _ptr(input_ids), _ptr(lengths), None,
-                                                           0, None))
-    mask = (np.arange(int(max_length), dtype=np.int32)[None, :] < lengths[:, None]).astype(np.int32)
+    n_str, max_length = len(blobs), int(max_length)
+    with _batch_on(utf8, byte_off, fold if n_str > 0 else 0) as b:   # (an empty list needs no device buffers)
+        input_ids, lengths = b.out((n_str, max_length), np.int32), b.out(n_str, np.int32, True)
+        _lib.check(b.lib.latok_wordpiece_padded_utf8_bytes_batch(b.u8, b.off, n_str, b.total, handle, unk_id, max_length, 1 if special else 0, cls_id,
+                                                                 sep_id, pad_id, _arg(input_ids), _arg(lengths), None, b.flags, None))
+        input_ids, lengths = b.fetch(input_ids), b.fetch(lengths)
+    mask = (np.arange(max_length, dtype=np.int32)[None, :] < lengths[:, None]).astype(np.int32)
     return input_ids, mask
 
 

@@ -1211,6 +1211,15 @@ static int next_scan_epoch(Workspace& w, hipStream_t st, unsigned* epoch_out) {
     *epoch_out = w.scan_epoch;
     return LATOK_OK;
 }
+// one chained scan of the sized calls' rows, on its own epoch: dst = the exclusive scan of src[0 .. n), the total -> *d_total and, if
+// asked for, the pinned word r_total; d_flag: the scan's own error flag
+static int enqueue_row_scan(Workspace& w, const int64_t* src, int64_t n, int64_t* dst, int64_t* d_total, int64_t* r_total, int* d_flag, hipStream_t st) {
+    int rc;
+    unsigned epoch = 0;
+    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    HIP_TRY(latok::launch_tile_scan(src, n, dst, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total, r_total, d_flag, st));
+    return LATOK_OK;
+}
 
 // One device-resident (chunk of a) batch for enqueue_compaction_dev
 struct Compaction {
@@ -1761,6 +1770,26 @@ static int enqueue_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* r_
     HIP_TRY(latok::launch_word_counts_scan(true, t.bits, t.space, t.words, b.total, t.kept, t.tcnt, t.pref, t.rank, (unsigned long long*)w.chain.p,
                                            (unsigned*)w.chain_ctl.p, epoch, t.total, r_tokens, d_err + 1, st));
     return LATOK_OK;
+}
+// The front of the sized calls (term counts, n-grams, WordPiece), which need the token total on the host: enqueue_token_front with the
+// pinned words (p_tot / h_tot: word 0 tokens, word 1 the error word), wait 1, then the refusal of 2^31 tokens or more in the caller's
+// words (`too_many`, one %lld).  The caller sizes its buffers by *n_tok.
+static int sized_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* p_tot, const volatile int64_t* h_tot, hipStream_t st,
+                             const char* too_many, TokenPlanes* t, int64_t* n_tok) {
+    int rc;
+    if ((rc = enqueue_token_front(g, w, b, p_tot, (int*)(p_tot + 1), st, t))) return rc;
+    HIP_TRY(hipStreamSynchronize(st));   // wait 1: the token total decides whether the call goes on and what its buffers take
+    if ((rc = finish_totals(w, h_tot, 0, n_tok))) return rc;
+    if (*n_tok >= (1ll << 31)) return fail(LATOK_ERR_INVALID, too_many, (long long)*n_tok);
+    return LATOK_OK;
+}
+// The token rows of the n-gram and WordPiece calls, behind sized_token_front (n_tok > 0, w.wpspans sized for it): the span record of
+// every token at its rank (k_counts_scatter, KIND 1, int64) into w.wpspans, the token count of every string into d_cnt (n_str + 1,
+// cleared by the caller) and the row starts in token space into d_start (k_scan_chained; the total -> scalar word 4).
+static int enqueue_token_rows(Workspace& w, const Batch& b, const TokenPlanes& t, int64_t n_tok, int64_t* d_cnt, int64_t* d_start, int* d_err, hipStream_t st) {
+    HIP_TRY(latok::launch_counts_scatter(1, false, t.bits, t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, b.total, b.row, b.n_str, t.tile_first,
+                                         (int64_t*)w.wpspans.p, t.total, n_tok, d_cnt, d_err, st));
+    return enqueue_row_scan(w, d_cnt, b.n_str + 1, d_start, t.total + 4, nullptr, d_err + 1, st);
 }
 
 // Token hashes and token ids of a UTF-8 batch in BYTE space (latok_token_hashes_utf8_bytes_batch, latok_token_ids_utf8_bytes_batch and
@@ -2535,136 +2564,123 @@ static int csr_refusal(int err) {
     return LATOK_OK;
 }
 static int g_df_add_cached = 1;   // latok_debug_set_df_add: 0 = the plain k_df_add_plain (tools/path_bench.py measures both)
-// what the TF-IDF entry points add to term_counts_common: the update of an idf (update) or the weighting of the rows
-struct TfidfTail {
-    Idf* idf;      // may be NULL (weighting without idf)
-    int opts;
-    bool update;
-};
 
 /* Per-string term counts of a UTF-8 batch in BYTE space (latok_term_counts_utf8_bytes_batch, latok_hashed_term_counts_utf8_bytes_batch):
  * the CSR rows of a document-term matrix.  One stream, every batch size the same kernels:
- *   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
- *   k_word_counts + k_scan_chained                kept mask, token ranks; THE token total -> scalar word 0, pinned word 0
- *   (wait 1)                                      the host reads the token total: 2^31 or more is refused, the key buffers are sized
+ *   sized_token_front (wait 1)                    kept mask, token ranks; the host reads THE token total (pinned word 0): the key buffers are sized
  *   k_term_scatter                                one term key per token at its rank (term_key.h), int64 token count per string
  *   k_scan_chained                                the row starts in token space
- *   k_terms_tile, k_terms_long                    sort and reduce inside every string: distinct and OOV counts, the entries
- *   k_scan_chained                                indptr, nnz -> pinned word 3
- *   k_terms_finish, k_terms_emit                  indptr / oov in the caller's width; indices / data if nnz fits the capacity
+ *   enqueue_csr_tail: k_terms_tile, k_terms_long  sort and reduce inside every string: distinct and OOV counts, the entries
+ *     k_scan_chained, k_terms_emit                indptr, nnz -> pinned word 3; indices / data if nnz fits the capacity
+ *   k_terms_finish                                indptr / oov in the caller's width
  *   (wait 2)                                      nnz; host pointers then copy nnz entries (wait 3)
  * `w` was sized by ws_needs with WsShape{.spans = true, .term_rows = n_str + 1}; the call sizes the key buffers itself. */
-struct TermCounts {
-    Batch b;                       // UTF-8 bytes on the device (16-byte aligned), byte offsets, total in bytes (> 0), n_str > 0
-    const Vocab* vocab = nullptr;  // NULL: the hashed form
-    uint32_t seed = 0, n_features = 0;
-    bool alternate_sign = false;
-    void* indptr = nullptr;        // [n_str + 1]
-    void* oov = nullptr;           // [n_str]; NULL: not asked for
-    int32_t* indices = nullptr;    // NULL (both): a size query
-    int32_t* data = nullptr;
+struct TermsCall {                 // one blocking call of the term family: what its entry point received ...
+    const uint8_t* utf8;
+    const int64_t* byte_off;
+    int64_t n_str, total_bytes;
+    const latok_vocab* vocab = nullptr;   // the vocabulary form, or the hashed one with its parameters
+    bool hashed = false;
+    uint32_t seed = 0;
+    int64_t n_features = 0;
+    int alternate_sign = 0;
+    bool ngrams = false;           // word n-grams (enqueue_ngram_counts): the orders and the separator byte; pinned word 5 = K
+    int min_n = 1, max_n = 1, sep = 0x20;
+    bool tfidf = false, update = false;   // the TF-IDF tail behind the counts: the weighting of the rows, or (update) the update of idf
+    Idf* idf = nullptr;            // may be NULL (weighting without idf)
+    int opts = 0;
+    void *indptr_out = nullptr, *oov_out = nullptr;
+    int32_t *indices_out = nullptr, *data_out = nullptr;   // (data: float32 in the TF-IDF calls, weighted in place)
     int64_t cap = 0;               // in entries
+    int64_t *nnz_out = nullptr, *n_tokens_out = nullptr, *n_grams_out = nullptr;
+    int flags = 0;
+    void* stream = nullptr;
+    // ... and what terms_stage_outputs made of it for the enqueue cores
+    Batch b;                       // UTF-8 bytes on the device (16-byte aligned), byte offsets, total in bytes (> 0), n_str > 0
+    const Vocab* v = nullptr;      // NULL: the hashed form
+    void *indptr = nullptr, *oov = nullptr;        // [n_str + 1], [n_str] or NULL: the caller's device buffers or the context's own
+    int32_t *indices = nullptr, *data = nullptr;   // NULL (both): a size query
+    int64_t fill_cap = 0;          // in entries: what the kernels may write
     bool o32 = false;              // width of indptr and oov
-    int64_t* p_tot = nullptr;      // the pinned words as the device sees them (cleared by the caller): 0 tokens, 1 flags, 3 nnz
+    int64_t* p_tot = nullptr;      // the pinned words as the device sees them (cleared by stage): 0 tokens, 1 flags, 3 nnz
     volatile int64_t* h_tot = nullptr;
-    int64_t n_tokens = 0;          // (out) the token total
-    int min_n = 1, max_n = 1, sep = 0x20;   // word n-grams (enqueue_ngram_counts): the orders and the separator byte; pinned word 5 = K
-    int64_t n_grams = 0;           // (out) the key total K of the n-gram calls
+    int64_t n_tokens = 0, n_grams = 0;   // (out) the token total; the key total K of the n-gram route
     hipStream_t st = nullptr;
 };
-static int enqueue_term_counts(Ctx& g, Workspace& w, TermCounts& a) {
+// the five arrays of w.trows (kTermRowArrays), n_str + 1 int64 each
+struct TermRows {
+    int64_t *cnt, *start, *distinct, *indptr, *oov;   // token counts and row starts in token space, distinct counts, indptr, OOV counts
+    size_t bytes;
+    TermRows(const Workspace& w, int64_t n_str)
+        : cnt((int64_t*)w.trows.p), start(cnt + (n_str + 1)), distinct(cnt + 2 * (n_str + 1)), indptr(cnt + 3 * (n_str + 1)),
+          oov(cnt + 4 * (n_str + 1)), bytes((size_t)(n_str + 1) * 8 * kTermRowArrays) {}
+};
+constexpr const char* kTooManyTermTokens = "the batch has %lld tokens: term counts are int32 (fewer than 2^31 tokens a call)";
+// The CSR tail of the term and n-gram counts: the `n_keys` keys of w.tkeys, whose rows start at d_starts (token space or key space),
+// are sorted and reduced inside every string, the distinct counts scanned into indptr (nnz -> scalar word 5, pinned word 3) and, when
+// the caller gave buffers, the entries emitted.  launch_terms_finish follows at the call site, keys or none.
+static int enqueue_csr_tail(Workspace& w, const TermsCall& a, const TermRows& r, const TokenPlanes& t, const int64_t* d_starts, int64_t n_keys) {
+    int rc;
+    const int64_t n_str = a.b.n_str;
+    uint64_t* d_keys = (uint64_t*)w.tkeys.p;
+    HIP_TRY(latok::launch_terms_reduce(d_keys, (uint64_t*)w.tkeys2.p, d_starts, n_str, n_keys, a.v != nullptr, r.distinct, r.oov, a.st));
+    if ((rc = enqueue_row_scan(w, r.distinct, n_str + 1, r.indptr, t.total + 5, a.p_tot + 3, (int*)(a.p_tot + 1) + 1, a.st))) return rc;
+    if (a.indices) HIP_TRY(latok::launch_terms_emit(d_keys, d_starts, n_str, n_keys, r.distinct, r.indptr, t.total + 5, a.fill_cap, a.indices, a.data, a.st));
+    return LATOK_OK;
+}
+static int enqueue_term_counts(Ctx& g, Workspace& w, TermsCall& a) {
     int rc;
     const hipStream_t st = a.st;
     const int64_t total = a.b.total, n_str = a.b.n_str;
     int* d_err = (int*)(a.p_tot + 1);
-    unsigned epoch = 0;
     TokenPlanes t;
-    if ((rc = enqueue_token_front(g, w, a.b, a.p_tot, d_err, st, &t))) return rc;
-    int64_t* d_total = t.total;
-    HIP_TRY(hipStreamSynchronize(st));   // wait 1: the token total decides whether the call goes on and what the keys take
-    if ((rc = finish_totals(w, a.h_tot, 0, &a.n_tokens))) return rc;
+    if ((rc = sized_token_front(g, w, a.b, a.p_tot, a.h_tot, st, kTooManyTermTokens, &t, &a.n_tokens))) return rc;
     const int64_t n_tok = a.n_tokens;
-    if (n_tok >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld tokens: term counts are int32 (fewer than 2^31 tokens a call)", (long long)n_tok);
     if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .term_tokens = n_tok}).data(), kWsNeeds)))
         return rc;
-    int64_t* rows = (int64_t*)w.trows.p;
-    int64_t* d_cnt = rows;
-    int64_t* d_start = rows + (n_str + 1);
-    int64_t* d_distinct = rows + 2 * (n_str + 1);
-    int64_t* d_indptr = rows + 3 * (n_str + 1);
-    int64_t* d_oov = rows + 4 * (n_str + 1);
-    HIP_TRY(hipMemsetAsync(rows, 0, (size_t)(n_str + 1) * 8 * kTermRowArrays, st));   // (no token: every row is empty, nnz = 0)
+    const TermRows r(w, n_str);
+    HIP_TRY(hipMemsetAsync(r.cnt, 0, r.bytes, st));   // (no token: every row is empty, nnz = 0)
     if (n_tok > 0) {
-        uint64_t* d_keys = (uint64_t*)w.tkeys.p;
         latok::VocabTable vt;
-        if (a.vocab) vt = a.vocab->table.view(a.vocab->seed);
-        HIP_TRY(latok::launch_term_scatter((const uint8_t*)a.b.in.p, a.vocab ? &vt : nullptr, a.seed, a.n_features, a.alternate_sign, t.bits, t.space,
-                                           t.kept, t.rank, t.tcnt, t.pref, t.words, total, a.b.row, n_str, t.tile_first, d_total, d_keys, d_cnt,
-                                           d_err, st));
-        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-        HIP_TRY(latok::launch_tile_scan(d_cnt, n_str + 1, d_start, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 4,
-                                        nullptr, d_err + 1, st));
-        HIP_TRY(latok::launch_terms_reduce(d_keys, (uint64_t*)w.tkeys2.p, d_start, n_str, n_tok, a.vocab != nullptr, d_distinct, d_oov, st));
-        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-        HIP_TRY(latok::launch_tile_scan(d_distinct, n_str + 1, d_indptr, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch,
-                                        d_total + 5, a.p_tot + 3, d_err + 1, st));
-        if (a.indices)
-            HIP_TRY(latok::launch_terms_emit(d_keys, d_start, n_str, n_tok, d_distinct, d_indptr, d_total + 5, a.cap, a.indices, a.data, st));
+        if (a.v) vt = a.v->table.view(a.v->seed);
+        HIP_TRY(latok::launch_term_scatter((const uint8_t*)a.b.in.p, a.v ? &vt : nullptr, a.seed, (uint32_t)a.n_features, a.alternate_sign != 0, t.bits,
+                                           t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, total, a.b.row, n_str, t.tile_first, t.total,
+                                           (uint64_t*)w.tkeys.p, r.cnt, d_err, st));
+        if ((rc = enqueue_row_scan(w, r.cnt, n_str + 1, r.start, t.total + 4, nullptr, d_err + 1, st))) return rc;
+        if ((rc = enqueue_csr_tail(w, a, r, t, r.start, n_tok))) return rc;
     }
-    HIP_TRY(latok::launch_terms_finish(a.o32, d_indptr, d_oov, n_str, a.indptr, a.oov, st));
+    HIP_TRY(latok::launch_terms_finish(a.o32, r.indptr, r.oov, n_str, a.indptr, a.oov, st));
     return LATOK_OK;
 }
 
 /* Word n-grams of the term counts (latok_ngram_counts_utf8_bytes_batch, latok_hashed_ngram_counts_utf8_bytes_batch): one key per gram
  * instead of one per token, then the term counts' own sort and reduce with the row starts in KEY space.  One stream:
- *   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
- *   k_word_counts + k_scan_chained                kept mask, token ranks; THE token total -> scalar word 0, pinned word 0
- *   (wait 1)                                      the host reads the token total: 2^31 or more is refused, the span records are sized
- *   k_counts_scatter (KIND 1, int64)              the span record of every token at its rank in the workspace, token count per string
- *   k_scan_chained                                the row starts in token space
+ *   sized_token_front (wait 1)                    kept mask, token ranks; the host reads THE token total (pinned word 0): the span records are sized
+ *   enqueue_token_rows                            the span record of every token at its rank in the workspace, the row starts in token space
  *   k_ngram_rows + k_scan_chained                 grams per string, the row starts in key space; the key total K -> pinned word 5
  *   (wait 2)                                      the host reads K: 2^31 or more is refused, the two key buffers are sized
  *   k_ngram_keys                                  one term key per gram inside its row's range of keys
- *   k_terms_tile, k_terms_long ... k_terms_emit   as enqueue_term_counts, with the key rows and K in the place of the token rows
+ *   enqueue_csr_tail, k_terms_finish              as enqueue_term_counts, with the key rows and K in the place of the token rows
  *   (wait 3)                                      nnz; host pointers then copy nnz entries (wait 4)
  * `w` was sized by ws_needs with WsShape{.spans = true, .term_rows = n_str + 1, .ng_rows = n_str + 1}; the call sizes the rest. */
-static int enqueue_ngram_counts(Ctx& g, Workspace& w, TermCounts& a) {
+static int enqueue_ngram_counts(Ctx& g, Workspace& w, TermsCall& a) {
     int rc;
     const hipStream_t st = a.st;
     const int64_t total = a.b.total, n_str = a.b.n_str;
     int* d_err = (int*)(a.p_tot + 1);
-    unsigned epoch = 0;
     TokenPlanes t;
-    if ((rc = enqueue_token_front(g, w, a.b, a.p_tot, d_err, st, &t))) return rc;
-    int64_t* d_total = t.total;
-    HIP_TRY(hipStreamSynchronize(st));   // wait 1: the token total decides whether the call goes on and what the records take
-    if ((rc = finish_totals(w, a.h_tot, 0, &a.n_tokens))) return rc;
+    if ((rc = sized_token_front(g, w, a.b, a.p_tot, a.h_tot, st, kTooManyTermTokens, &t, &a.n_tokens))) return rc;
     const int64_t n_tok = a.n_tokens;
-    if (n_tok >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld tokens: term counts are int32 (fewer than 2^31 tokens a call)", (long long)n_tok);
-    WsShape shape{.spans = true, .term_rows = n_str + 1};
-    shape.ng_rows = n_str + 1;
-    shape.ng_tokens = n_tok;
+    WsShape shape{.spans = true, .term_rows = n_str + 1, .ng_tokens = n_tok, .ng_rows = n_str + 1};
     if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, shape).data(), kWsNeeds))) return rc;
-    int64_t* rows = (int64_t*)w.trows.p;
-    int64_t* d_cnt = rows;                       // token space: counts, row starts
-    int64_t* d_start = rows + (n_str + 1);
-    int64_t* d_distinct = rows + 2 * (n_str + 1);
-    int64_t* d_indptr = rows + 3 * (n_str + 1);
-    int64_t* d_oov = rows + 4 * (n_str + 1);
+    const TermRows r(w, n_str);                  // token space: counts, row starts
     int64_t* d_kcnt = (int64_t*)w.ngrows.p;      // key space: counts, row starts
     int64_t* d_kstart = d_kcnt + (n_str + 1);
-    HIP_TRY(hipMemsetAsync(rows, 0, (size_t)(n_str + 1) * 8 * kTermRowArrays, st));   // (no gram: every row is empty, nnz = 0)
+    HIP_TRY(hipMemsetAsync(r.cnt, 0, r.bytes, st));   // (no gram: every row is empty, nnz = 0)
     if (n_tok > 0) {
-        int64_t* d_tspans = (int64_t*)w.wpspans.p;
-        HIP_TRY(latok::launch_counts_scatter(1, false, t.bits, t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, total, a.b.row, n_str, t.tile_first,
-                                             d_tspans, d_total, n_tok, d_cnt, d_err, st));
-        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-        HIP_TRY(latok::launch_tile_scan(d_cnt, n_str + 1, d_start, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 4,
-                                        nullptr, d_err + 1, st));
-        HIP_TRY(latok::launch_ngram_rows(d_cnt, n_str, a.min_n, a.max_n, d_kcnt, st));
-        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-        HIP_TRY(latok::launch_tile_scan(d_kcnt, n_str + 1, d_kstart, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 6,
-                                        a.p_tot + 5, d_err + 1, st));
+        if ((rc = enqueue_token_rows(w, a.b, t, n_tok, r.cnt, r.start, d_err, st))) return rc;
+        HIP_TRY(latok::launch_ngram_rows(r.cnt, n_str, a.min_n, a.max_n, d_kcnt, st));
+        if ((rc = enqueue_row_scan(w, d_kcnt, n_str + 1, d_kstart, t.total + 6, a.p_tot + 5, d_err + 1, st))) return rc;
         HIP_TRY(hipStreamSynchronize(st));   // wait 2: the key total decides whether the call goes on and what the keys take
         int64_t n_tok_again = 0;
         if ((rc = finish_totals(w, a.h_tot, 0, &n_tok_again))) return rc;
@@ -2674,222 +2690,211 @@ static int enqueue_ngram_counts(Ctx& g, Workspace& w, TermCounts& a) {
         if (n_keys > 0) {
             shape.ng_keys = n_keys;
             if ((rc = ws_ensure(ws_needs(w, total, shape).data(), kWsNeeds))) return rc;   // (only the key buffers grow)
-            uint64_t* d_keys = (uint64_t*)w.tkeys.p;
             latok::VocabTable vt;
-            if (a.vocab) vt = a.vocab->table.view(a.vocab->seed);
-            HIP_TRY(latok::launch_ngram_keys((const uint8_t*)a.b.in.p, total, a.b.row, n_str, d_start, d_kstart, d_tspans, n_tok, n_keys, a.min_n, a.max_n,
-                                             a.sep, a.vocab ? &vt : nullptr, a.seed, a.n_features, a.alternate_sign, d_keys, st));
-            HIP_TRY(latok::launch_terms_reduce(d_keys, (uint64_t*)w.tkeys2.p, d_kstart, n_str, n_keys, a.vocab != nullptr, d_distinct, d_oov, st));
-            if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-            HIP_TRY(latok::launch_tile_scan(d_distinct, n_str + 1, d_indptr, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch,
-                                            d_total + 5, a.p_tot + 3, d_err + 1, st));
-            if (a.indices)
-                HIP_TRY(latok::launch_terms_emit(d_keys, d_kstart, n_str, n_keys, d_distinct, d_indptr, d_total + 5, a.cap, a.indices, a.data, st));
+            if (a.v) vt = a.v->table.view(a.v->seed);
+            HIP_TRY(latok::launch_ngram_keys((const uint8_t*)a.b.in.p, total, a.b.row, n_str, r.start, d_kstart, (const int64_t*)w.wpspans.p, n_tok, n_keys,
+                                             a.min_n, a.max_n, a.sep, a.v ? &vt : nullptr, a.seed, (uint32_t)a.n_features, a.alternate_sign != 0,
+                                             (uint64_t*)w.tkeys.p, st));
+            if ((rc = enqueue_csr_tail(w, a, r, t, d_kstart, n_keys))) return rc;
         }
     }
-    HIP_TRY(latok::launch_terms_finish(a.o32, d_indptr, d_oov, n_str, a.indptr, a.oov, st));
+    HIP_TRY(latok::launch_terms_finish(a.o32, r.indptr, r.oov, n_str, a.indptr, a.oov, st));
     return LATOK_OK;
 }
 
-// the n-gram arguments of the two n-gram entry points; NULL: the plain term counts
-struct NgramArgs {
-    int min_n, max_n, sep;
-    int64_t* n_grams_out;
-};
-// the four blocking entry points' shared body: the checks of the ids call, the capacity protocol in entries.  tf: the TF-IDF entry
-// points -- behind the entries that launch_terms_emit wrote, the column check (vocabulary form with an idf), then the update of df
-// from the context's own buffers (tf->update: the caller has no output buffers) or the weighting of data in place; the error word
-// travels to pinned word 7 on the stream and is read behind the counts' own wait.
-static int term_counts_common(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
-                              bool hashed, uint32_t seed, int64_t n_features, int alternate_sign, void* indptr_out, void* oov_out,
-                              int32_t* indices_out, int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_tokens_out, int flags,
-                              void* stream, const NgramArgs* ng = nullptr, const TfidfTail* tf = nullptr) {
+// The argument refusals, none of which touches the device: first those that write nothing, then, behind need_init and with the
+// out-pointers zeroed, the checks of the ids call and the capacity protocol in entries.
+static int terms_refusals(const Ctx& g, TermsCall& a) {
+    int rc;
+    if (a.flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    if (a.tfidf) {
+        if (a.update && (a.flags & LATOK_OUT_INT32)) return fail(LATOK_ERR_INVALID, "unknown flag");
+        if ((rc = tfidf_check_opts(a.opts))) return rc;
+        if (a.update && !a.idf) return fail(LATOK_ERR_INVALID, "idf is NULL");
+        if (a.idf && a.hashed && a.n_features != a.idf->n_cols)
+            return fail(LATOK_ERR_INVALID, "n_features is %lld, the idf has %lld columns", (long long)a.n_features, (long long)a.idf->n_cols);
+    }
+    if (a.ngrams) {
+        if (a.min_n < 1) return fail(LATOK_ERR_INVALID, "min_n must be at least 1");
+        if (a.max_n < a.min_n) return fail(LATOK_ERR_INVALID, "max_n must not be below min_n");
+        if (a.max_n > kNgMax) return fail(LATOK_ERR_INVALID, "max_n must not exceed %d", kNgMax);
+        if (a.sep < 0 || a.sep > 255) return fail(LATOK_ERR_INVALID, "sep must be one byte: 0 .. 255");
+    }
+    if ((rc = need_init(g))) return rc;
+    if (!a.nnz_out) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
+    *a.nnz_out = 0;
+    if (a.n_tokens_out) *a.n_tokens_out = 0;
+    if (a.n_grams_out) *a.n_grams_out = 0;
+    if (!a.indptr_out && !a.update) return fail(LATOK_ERR_INVALID, "indptr_out is NULL");
+    if (a.cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
+    if ((a.indices_out == nullptr) != (a.data_out == nullptr)) return fail(LATOK_ERR_INVALID, "indices_out and data_out go together: one of them is NULL");
+    if (!a.indices_out && a.cap > 0) return fail(LATOK_ERR_INVALID, "indices_out and data_out are NULL but cap > 0 (a size query passes cap = 0)");
+    if (a.hashed && (a.n_features < 1 || a.n_features > 0x7FFFFFFFll)) return fail(LATOK_ERR_INVALID, "n_features must be in 1 .. 2^31 - 1");
+    if (!a.hashed) return check_object(g, a.vocab, "vocab is NULL", &a.v);
+    return LATOK_OK;
+}
+// the enqueue cores' part of a staged call
+static int terms_stage_outputs(Ctx& g, TermsCall& a, const BytesCall& c) {
+    int rc;
+    const int64_t n_str = c.d.n_str;
+    a.b = c.d;
+    // (an entry has at least one token, a token one byte: the staging is sized by it; a token starts one gram of every order at most)
+    const int64_t most = c.total * (a.ngrams ? a.max_n - a.min_n + 1 : 1);
+    a.fill_cap = a.update ? most : a.indices_out ? std::min(a.cap, most) : 0;
+    a.o32 = c.o32;
+    const bool own = !c.dev || a.update;   // a host call's outputs, and every update's, land in the context's own buffers
+    if (own && ((rc = g.h_aux.ensure((size_t)a.fill_cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.fill_cap * 4 + 16)) ||
+                (rc = g.counts.ensure((size_t)(2 * n_str + 2) * 8))))
+        return rc;
+    const bool own_entries = own && (a.indices_out || a.update);
+    a.indptr = own ? g.counts.p : a.indptr_out;
+    a.oov = own && a.oov_out ? (uint8_t*)g.counts.p + (size_t)(n_str + 1) * 8 : a.oov_out;
+    a.indices = own_entries ? (int32_t*)g.h_aux.p : a.indices_out;
+    a.data = own_entries ? (int32_t*)g.h_out.p : a.data_out;
+    a.p_tot = c.p_tot;
+    a.h_tot = c.h_tot;
+    a.st = c.st;
+    return LATOK_OK;
+}
+// The TF-IDF entry points' tail, behind the entries that launch_terms_emit wrote: the column check (vocabulary form with an idf), then
+// the update of df from the context's own buffers (update) or the weighting of data in place; the error word travels to pinned word 7
+// on the stream and is read behind the counts' own wait.  The caller holds the idf's lock.
+static int enqueue_tfidf_tail(Ctx& g, const TermsCall& a) {
+    int rc;
+    Idf* const f = a.idf;
+    const int64_t n_str = a.b.n_str;
+    const int64_t* d_nnz = (const int64_t*)g.ws.scalar.p + 5;   // the scan's own rows and total, as the enqueue left them
+    int* d_err = (int*)g.ws.tfctl.p;
+    HIP_TRY(hipMemsetAsync(d_err, 0, 4, a.st));
+    if (f && !a.hashed) HIP_TRY(latok::launch_csr_check(false, nullptr, a.indices, n_str, 0, d_nnz, a.fill_cap, f->n_cols, d_err, a.st));
+    if (a.update) {
+        HIP_TRY(latok::launch_df_add(g_df_add_cached != 0, a.indices, 0, d_nnz, a.fill_cap, d_err, f->df.as<int32_t>(), a.st));
+    } else {
+        const float* weights = nullptr;
+        if (f && (rc = idf_weights_on(*f, (a.opts & kTwSmoothIdf) != 0, a.st, &weights))) return rc;
+        HIP_TRY(latok::launch_tfidf_rows(false, TermRows(g.ws, n_str).indptr, a.indices, a.data, n_str, 0, d_nnz, a.fill_cap, weights, a.opts, d_err,
+                                         (float*)a.data, a.st));
+    }
+    HIP_TRY(hipMemcpyAsync((void*)(a.h_tot + 7), d_err, 4, hipMemcpyDeviceToHost, a.st));
+    return LATOK_OK;
+}
+// indptr and oov of a host call (valid whatever the capacity), wait 2, the totals, the tail's refusal, then the update's documents or the entries
+static int terms_deliver(Ctx& g, const TermsCall& a, BytesCall& c) {
+    int rc;
+    const int64_t n_str = a.b.n_str;
+    if (!c.dev && !a.update) {
+        HIP_TRY(hipMemcpyAsync(a.indptr_out, a.indptr, (size_t)(n_str + 1) * c.elt, hipMemcpyDeviceToHost, c.st));
+        if (a.oov_out) HIP_TRY(hipMemcpyAsync(a.oov_out, a.oov, (size_t)n_str * c.elt, hipMemcpyDeviceToHost, c.st));
+    }
+    int64_t n_tok = 0;
+    if ((rc = c.wait_totals(g, 0, &n_tok))) return rc;   // wait 2
+    if (a.n_tokens_out) *a.n_tokens_out = n_tok;
+    if (a.n_grams_out) *a.n_grams_out = a.n_grams;
+    const int64_t nnz = c.h_tot[3];
+    *a.nnz_out = nnz;
+    if (a.tfidf && c.h_tot[7]) return csr_refusal((int)c.h_tot[7]);
+    if (!a.update) return deliver_sized(c, nnz, a.cap, "capacity too small: need %lld entries", {{a.indices_out, a.indices, 4}, {a.data_out, a.data, 4}});   // (wait 3)
+    a.idf->n_docs += n_str;
+    idf_drop_weights(*a.idf);
+    return LATOK_OK;
+}
+// the blocking entry points' shared body, step by step; the idf's lock is taken before the call's turn on the stream
+static int term_counts_common(TermsCall a) {
     LATOK_ENTER();
-    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
-    const bool upd = tf && tf->update;
-    Idf* const f = tf ? tf->idf : nullptr;
-    if (tf) {   // refused before any device work, with nothing written
-        int trc;
-        if (upd && (flags & LATOK_OUT_INT32)) return fail(LATOK_ERR_INVALID, "unknown flag");
-        if ((trc = tfidf_check_opts(tf->opts))) return trc;
-        if (upd && !f) return fail(LATOK_ERR_INVALID, "idf is NULL");
-        if (f && hashed && n_features != f->n_cols)
-            return fail(LATOK_ERR_INVALID, "n_features is %lld, the idf has %lld columns", (long long)n_features, (long long)f->n_cols);
-    }
-    if (ng) {   // refused before any device work, with nothing written
-        if (ng->min_n < 1) return fail(LATOK_ERR_INVALID, "min_n must be at least 1");
-        if (ng->max_n < ng->min_n) return fail(LATOK_ERR_INVALID, "max_n must not be below min_n");
-        if (ng->max_n > kNgMax) return fail(LATOK_ERR_INVALID, "max_n must not exceed %d", kNgMax);
-        if (ng->sep < 0 || ng->sep > 255) return fail(LATOK_ERR_INVALID, "sep must be one byte: 0 .. 255");
-    }
-    int rc = need_init(g);
-    if (rc) return rc;
-    if (!nnz_out) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
-    *nnz_out = 0;
-    if (n_tokens_out) *n_tokens_out = 0;
-    if (ng && ng->n_grams_out) *ng->n_grams_out = 0;
-    if (!indptr_out && !upd) return fail(LATOK_ERR_INVALID, "indptr_out is NULL");
-    if (cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
-    if ((indices_out == nullptr) != (data_out == nullptr)) return fail(LATOK_ERR_INVALID, "indices_out and data_out go together: one of them is NULL");
-    if (!indices_out && cap > 0) return fail(LATOK_ERR_INVALID, "indices_out and data_out are NULL but cap > 0 (a size query passes cap = 0)");
-    if (hashed && (n_features < 1 || n_features > 0x7FFFFFFFll)) return fail(LATOK_ERR_INVALID, "n_features must be in 1 .. 2^31 - 1");
-    const Vocab* v = nullptr;
-    if (!hashed && (rc = check_object(g, vocab, "vocab is NULL", &v))) return rc;
+    int rc;
+    if ((rc = terms_refusals(g, a))) return rc;
+    Idf* const f = a.idf;
+    const int64_t n_str = a.n_str;
     std::unique_lock<std::mutex> idf_lock;
     if (f) {
         idf_lock = std::unique_lock<std::mutex>(f->mu);
         if ((rc = check_device(g, "idf", f->device))) return rc;
-        if (upd && f->n_docs + std::max<int64_t>(n_str, 0) >= (1ll << 31))
+        if (a.update && f->n_docs + std::max<int64_t>(n_str, 0) >= (1ll << 31))
             return fail(LATOK_ERR_INVALID, "the idf would hold %lld documents: df is int32 (fewer than 2^31)", (long long)(f->n_docs + n_str));
     }
     BytesCall c;   // (elt: the width of indptr and oov; an index and a count are 4 bytes in every mode)
-    if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
-    const bool dev = c.dev;
-    const size_t elt = c.elt;
-    const hipStream_t st = c.st;
-    if (dev && ((uintptr_t)indptr_out & (elt - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    if (c.empty && upd) {   // rows without an entry: documents all the same
+    if ((rc = c.open(g, a.utf8, a.byte_off, n_str, a.total_bytes, a.flags, a.stream))) return rc;
+    if (c.dev && ((uintptr_t)a.indptr_out & (c.elt - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    if (c.empty && a.update) {   // rows without an entry: documents all the same
         f->n_docs += n_str;
         if (n_str > 0) idf_drop_weights(*f);
         return LATOK_OK;
     }
     if (c.empty) {   // no byte, no token: every row is empty
-        if ((rc = zero_counts(dev, indptr_out, (size_t)(n_str + 1) * elt, st))) return rc;
-        return zero_counts(dev, oov_out, (size_t)n_str * elt, st, true);
+        if ((rc = zero_counts(c.dev, a.indptr_out, (size_t)(n_str + 1) * c.elt, c.st))) return rc;
+        return zero_counts(c.dev, a.oov_out, (size_t)n_str * c.elt, c.st, true);
     }
-    if (dev && (((uintptr_t)oov_out & (elt - 1)) != 0 || ((uintptr_t)indices_out & 3) != 0 || ((uintptr_t)data_out & 3) != 0))
+    if (c.dev && (((uintptr_t)a.oov_out & (c.elt - 1)) != 0 || ((uintptr_t)a.indices_out & 3) != 0 || ((uintptr_t)a.data_out & 3) != 0))
         return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    WsShape shape{.spans = true, .term_rows = n_str + 1};
-    if (ng) shape.ng_rows = n_str + 1;
-    shape.tf_ctl = tf != nullptr;
-    if ((rc = c.stage(g, ng ? (hashed ? 15 : 14) : (hashed ? 10 : 9), shape, (ng ? kClearNgrams : kClearSized) | (tf ? kClearTfidfErr : 0u)))) return rc;
-    TermCounts a;
-    a.b = c.d;
-    a.vocab = v;
-    a.seed = seed;
-    a.n_features = (uint32_t)n_features;
-    a.alternate_sign = alternate_sign != 0;
-    a.indptr = indptr_out;
-    a.oov = oov_out;
-    a.indices = indices_out;
-    a.data = data_out;
-    // (an entry has at least one token, a token one byte: the staging is sized by it; a token starts one gram of every order at most)
-    const int64_t most = c.total * (ng ? ng->max_n - ng->min_n + 1 : 1);
-    a.cap = upd ? most : indices_out ? std::min(cap, most) : 0;
-    if (ng) {
-        a.min_n = ng->min_n;
-        a.max_n = ng->max_n;
-        a.sep = ng->sep;
-    }
-    a.o32 = c.o32;
-    if (!dev || upd) {   // the outputs land in the context's own buffers
-        if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 4 + 16)) ||
-            (rc = g.counts.ensure((size_t)(2 * n_str + 2) * 8)))
-            return rc;
-        if (indices_out || upd) {
-            a.indices = (int32_t*)g.h_aux.p;
-            a.data = (int32_t*)g.h_out.p;
-        }
-        a.indptr = g.counts.p;
-        if (oov_out) a.oov = (uint8_t*)g.counts.p + (size_t)(n_str + 1) * 8;
-    }
-    a.p_tot = c.p_tot;
-    a.h_tot = c.h_tot;
-    a.st = st;
-    if ((rc = ng ? enqueue_ngram_counts(g, g.ws, a) : enqueue_term_counts(g, g.ws, a))) return rc;
-    if (tf && a.indices && (ng ? a.n_grams : a.n_tokens) > 0) {   // (no key: the scan did not run and nnz = 0)
-        const int64_t* d_indptr = (const int64_t*)g.ws.trows.p + 3 * (n_str + 1);   // the scan's own rows and total, as the enqueue left them
-        const int64_t* d_nnz = (const int64_t*)g.ws.scalar.p + 5;
-        int* d_err = (int*)g.ws.tfctl.p;
-        HIP_TRY(hipMemsetAsync(d_err, 0, 4, st));
-        if (f && !hashed) HIP_TRY(latok::launch_csr_check(false, nullptr, a.indices, n_str, 0, d_nnz, a.cap, f->n_cols, d_err, st));
-        if (upd) {
-            HIP_TRY(latok::launch_df_add(g_df_add_cached != 0, a.indices, 0, d_nnz, a.cap, d_err, f->df.as<int32_t>(), st));
-        } else {
-            const float* weights = nullptr;
-            if (f && (rc = idf_weights_on(*f, (tf->opts & kTwSmoothIdf) != 0, st, &weights))) return rc;
-            HIP_TRY(latok::launch_tfidf_rows(false, d_indptr, a.indices, a.data, n_str, 0, d_nnz, a.cap, weights, tf->opts, d_err, (float*)a.data, st));
-        }
-        HIP_TRY(hipMemcpyAsync((void*)(c.h_tot + 7), d_err, 4, hipMemcpyDeviceToHost, st));
-    }
-    if (!dev && !upd) {   // valid whatever the capacity
-        HIP_TRY(hipMemcpyAsync(indptr_out, a.indptr, (size_t)(n_str + 1) * elt, hipMemcpyDeviceToHost, st));
-        if (oov_out) HIP_TRY(hipMemcpyAsync(oov_out, a.oov, (size_t)n_str * elt, hipMemcpyDeviceToHost, st));
-    }
-    int64_t n_tok = 0;
-    if ((rc = c.wait_totals(g, 0, &n_tok))) return rc;   // wait 2
-    if (n_tokens_out) *n_tokens_out = n_tok;
-    if (ng && ng->n_grams_out) *ng->n_grams_out = a.n_grams;
-    const int64_t nnz = c.h_tot[3];
-    *nnz_out = nnz;
-    if (tf && c.h_tot[7]) return csr_refusal((int)c.h_tot[7]);
-    if (upd) {
-        f->n_docs += n_str;
-        idf_drop_weights(*f);
-        return LATOK_OK;
-    }
-    return deliver_sized(c, nnz, cap, "capacity too small: need %lld entries", {{indices_out, a.indices, 4}, {data_out, a.data, 4}});   // (wait 3)
+    const WsShape shape{.spans = true, .term_rows = n_str + 1, .ng_rows = a.ngrams ? n_str + 1 : 0, .tf_ctl = a.tfidf};
+    const int route = a.ngrams ? (a.hashed ? 15 : 14) : (a.hashed ? 10 : 9);
+    if ((rc = c.stage(g, route, shape, (a.ngrams ? kClearNgrams : kClearSized) | (a.tfidf ? kClearTfidfErr : 0u)))) return rc;
+    if ((rc = terms_stage_outputs(g, a, c))) return rc;
+    if ((rc = a.ngrams ? enqueue_ngram_counts(g, g.ws, a) : enqueue_term_counts(g, g.ws, a))) return rc;
+    // (no key: the scan did not run and nnz = 0)
+    if (a.tfidf && a.indices && (a.ngrams ? a.n_grams : a.n_tokens) > 0 && (rc = enqueue_tfidf_tail(g, a))) return rc;
+    return terms_deliver(g, a, c);
 }
 int latok_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
                                         int min_n, int max_n, int sep, int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out,
                                         int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_grams_out, int flags, void* stream) {
-    const NgramArgs ng{min_n, max_n, sep, n_grams_out};
-    return term_counts_common(utf8, byte_off, n_str, total_bytes, vocab, false, 0, 0, 0, indptr_out, oov_out, indices_out, data_out, cap, nnz_out,
-                              nullptr, flags, stream, &ng);
+    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .vocab = vocab, .ngrams = true,
+                               .min_n = min_n, .max_n = max_n, .sep = sep, .indptr_out = indptr_out, .oov_out = oov_out, .indices_out = indices_out,
+                               .data_out = data_out, .cap = cap, .nnz_out = nnz_out, .n_grams_out = n_grams_out, .flags = flags, .stream = stream});
 }
 int latok_hashed_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, uint32_t seed,
                                                int64_t n_features, int alternate_sign, int min_n, int max_n, int sep, int64_t* indptr_out,
                                                int32_t* indices_out, int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_grams_out,
                                                int flags, void* stream) {
-    const NgramArgs ng{min_n, max_n, sep, n_grams_out};
-    return term_counts_common(utf8, byte_off, n_str, total_bytes, nullptr, true, seed, n_features, alternate_sign, indptr_out, nullptr, indices_out,
-                              data_out, cap, nnz_out, nullptr, flags, stream, &ng);
+    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .hashed = true, .seed = seed,
+                               .n_features = n_features, .alternate_sign = alternate_sign, .ngrams = true, .min_n = min_n, .max_n = max_n, .sep = sep,
+                               .indptr_out = indptr_out, .indices_out = indices_out, .data_out = data_out, .cap = cap, .nnz_out = nnz_out,
+                               .n_grams_out = n_grams_out, .flags = flags, .stream = stream});
 }
 int latok_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
                                        int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out, int32_t* data_out, int64_t cap,
                                        int64_t* nnz_out, int64_t* n_tokens_out, int flags, void* stream) {
-    return term_counts_common(utf8, byte_off, n_str, total_bytes, vocab, false, 0, 0, 0, indptr_out, oov_out, indices_out, data_out, cap, nnz_out,
-                              n_tokens_out, flags, stream);
+    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .vocab = vocab,
+                               .indptr_out = indptr_out, .oov_out = oov_out, .indices_out = indices_out, .data_out = data_out, .cap = cap,
+                               .nnz_out = nnz_out, .n_tokens_out = n_tokens_out, .flags = flags, .stream = stream});
 }
 int latok_hashed_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, uint32_t seed,
                                               int64_t n_features, int alternate_sign, int64_t* indptr_out, int32_t* indices_out,
                                               int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_tokens_out, int flags, void* stream) {
-    return term_counts_common(utf8, byte_off, n_str, total_bytes, nullptr, true, seed, n_features, alternate_sign, indptr_out, nullptr, indices_out,
-                              data_out, cap, nnz_out, n_tokens_out, flags, stream);
+    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .hashed = true, .seed = seed,
+                               .n_features = n_features, .alternate_sign = alternate_sign, .indptr_out = indptr_out, .indices_out = indices_out,
+                               .data_out = data_out, .cap = cap, .nnz_out = nnz_out, .n_tokens_out = n_tokens_out, .flags = flags, .stream = stream});
 }
 
-/* the TF-IDF entry points over text: term_counts_common with a tail (min_n = max_n = 1: the plain term counts' kernels) */
-static int tfidf_text_common(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab, bool hashed,
-                             uint32_t seed, int64_t n_features, int alternate_sign, int min_n, int max_n, int sep, const TfidfTail& tf,
-                             void* indptr_out, void* oov_out, int32_t* indices_out, float* data_out, int64_t cap, int64_t* nnz_out,
-                             int64_t* n_tokens_out, int flags, void* stream) {
-    const NgramArgs ng{min_n, max_n, sep, nullptr};
-    const bool plain = min_n == 1 && max_n == 1 && sep >= 0 && sep <= 255;   // (the n-gram route checks its arguments itself)
-    return term_counts_common(utf8, byte_off, n_str, total_bytes, vocab, hashed, seed, n_features, alternate_sign, indptr_out, oov_out, indices_out,
-                              (int32_t*)data_out, cap, nnz_out, n_tokens_out, flags, stream, plain ? nullptr : &ng, &tf);
-}
+/* the TF-IDF entry points over text: term_counts_common with a tail; min_n = max_n = 1 with a one-byte sep takes the plain term counts'
+ * kernels (the n-gram route checks its arguments itself) */
+static bool tfidf_ngrams(int min_n, int max_n, int sep) { return !(min_n == 1 && max_n == 1 && sep >= 0 && sep <= 255); }
 int latok_tfidf_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab, int min_n,
                                  int max_n, int sep, const latok_idf* idf, int opts, int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out,
                                  float* data_out, int64_t cap, int64_t* nnz_out, int flags, void* stream) {
-    const TfidfTail tf{const_cast<Idf*>(reinterpret_cast<const Idf*>(idf)), opts, false};
-    return tfidf_text_common(utf8, byte_off, n_str, total_bytes, vocab, false, 0, 0, 0, min_n, max_n, sep, tf, indptr_out, oov_out, indices_out, data_out,
-                             cap, nnz_out, nullptr, flags, stream);
+    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .vocab = vocab,
+                               .ngrams = tfidf_ngrams(min_n, max_n, sep), .min_n = min_n, .max_n = max_n, .sep = sep, .tfidf = true,
+                               .idf = const_cast<Idf*>(reinterpret_cast<const Idf*>(idf)), .opts = opts, .indptr_out = indptr_out, .oov_out = oov_out,
+                               .indices_out = indices_out, .data_out = (int32_t*)data_out, .cap = cap, .nnz_out = nnz_out, .flags = flags, .stream = stream});
 }
 int latok_hashed_tfidf_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, uint32_t seed,
                                         int64_t n_features, int alternate_sign, int min_n, int max_n, int sep, const latok_idf* idf, int opts,
                                         int64_t* indptr_out, int32_t* indices_out, float* data_out, int64_t cap, int64_t* nnz_out, int flags,
                                         void* stream) {
-    const TfidfTail tf{const_cast<Idf*>(reinterpret_cast<const Idf*>(idf)), opts, false};
-    return tfidf_text_common(utf8, byte_off, n_str, total_bytes, nullptr, true, seed, n_features, alternate_sign, min_n, max_n, sep, tf, indptr_out,
-                             nullptr, indices_out, data_out, cap, nnz_out, nullptr, flags, stream);
+    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .hashed = true, .seed = seed,
+                               .n_features = n_features, .alternate_sign = alternate_sign, .ngrams = tfidf_ngrams(min_n, max_n, sep), .min_n = min_n,
+                               .max_n = max_n, .sep = sep, .tfidf = true, .idf = const_cast<Idf*>(reinterpret_cast<const Idf*>(idf)), .opts = opts,
+                               .indptr_out = indptr_out, .indices_out = indices_out, .data_out = (int32_t*)data_out, .cap = cap, .nnz_out = nnz_out,
+                               .flags = flags, .stream = stream});
 }
 int latok_idf_update_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
                                       uint32_t seed, int64_t n_features, int min_n, int max_n, int sep, latok_idf* idf, int64_t* nnz_out,
                                       int64_t* n_tokens_out, int flags, void* stream) {
-    const TfidfTail tf{reinterpret_cast<Idf*>(idf), 0, true};
     int64_t nnz = 0;
-    return tfidf_text_common(utf8, byte_off, n_str, total_bytes, vocab, vocab == nullptr, seed, n_features, 0, min_n, max_n, sep, tf, nullptr, nullptr,
-                             nullptr, nullptr, 0, nnz_out ? nnz_out : &nnz, n_tokens_out, flags, stream);
+    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .vocab = vocab,
+                               .hashed = vocab == nullptr, .seed = seed, .n_features = n_features, .ngrams = tfidf_ngrams(min_n, max_n, sep),
+                               .min_n = min_n, .max_n = max_n, .sep = sep, .tfidf = true, .update = true, .idf = reinterpret_cast<Idf*>(idf),
+                               .nnz_out = nnz_out ? nnz_out : &nnz, .n_tokens_out = n_tokens_out, .flags = flags, .stream = stream});
 }
 
 int latok_idf_create(int64_t n_cols, latok_idf** out) {
@@ -3136,11 +3141,8 @@ extern "C" int latok_debug_set_df_add(int cached) {
 /* WordPiece in byte space (latok_wordpiece_ids_utf8_bytes_batch, latok_wordpiece_padded_utf8_bytes_batch): the subword ids of every
  * token.  The vocabulary object holds two vocab_table.h tables (wordpiece.h: initial and continuation), built on the host, uploaded
  * once, read only afterwards.  One stream, every batch size the same kernels:
- *   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
- *   k_word_counts + k_scan_chained                kept mask, token ranks; THE token total -> scalar word 0, pinned word 0
- *   (wait 1)                                      the host reads the token total: 2^31 or more is refused, the token buffers are sized
- *   k_counts_scatter (KIND 1, int64)              the span record of every token at its rank in the workspace, token count per string
- *   k_scan_chained                                the row starts in token space
+ *   sized_token_front (wait 1)                    kept mask, token ranks; the host reads THE token total (pinned word 0): the token buffers are sized
+ *   enqueue_token_rows                            the span record of every token at its rank in the workspace, the row starts in token space
  *   k_wp_count                                    pieces per token
  *   k_scan_chained                                piece ranks; the piece total -> scalar word 5, pinned word 3
  *   (padded form: wait 2)                         the piece total sizes the ids of the workspace
@@ -3242,14 +3244,11 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
     const hipStream_t st = a.st;
     const int64_t total = a.b.total, n_str = a.b.n_str;
     int* d_err = (int*)(a.p_tot + 1);
-    unsigned epoch = 0;
     TokenPlanes t;
-    if ((rc = enqueue_token_front(g, w, a.b, a.p_tot, d_err, st, &t))) return rc;
+    if ((rc = sized_token_front(g, w, a.b, a.p_tot, a.h_tot, st, "the batch has %lld tokens: a call takes fewer than 2^31 pieces", &t, &a.n_tokens)))
+        return rc;
     int64_t* d_total = t.total;
-    HIP_TRY(hipStreamSynchronize(st));   // wait 1: the token total decides whether the call goes on and what the token buffers take
-    if ((rc = finish_totals(w, a.h_tot, 0, &a.n_tokens))) return rc;
     const int64_t n_tok = a.n_tokens;
-    if (n_tok >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld tokens: a call takes fewer than 2^31 pieces", (long long)n_tok);
     if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok}).data(), kWsNeeds)))
         return rc;
     int64_t* d_cnt = (int64_t*)w.trows.p;       // token count of every string, one zero entry behind them
@@ -3259,12 +3258,8 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
     const int32_t* d_ids = a.ids;
     if (n_tok > 0) {
         HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)(n_str + 1) * 8, st));
-        int64_t* d_tspans = (int64_t*)w.wpspans.p;
-        HIP_TRY(latok::launch_counts_scatter(1, false, t.bits, t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, total, a.b.row, n_str, t.tile_first,
-                                             d_tspans, d_total, n_tok, d_cnt, d_err, st));
-        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-        HIP_TRY(latok::launch_tile_scan(d_cnt, n_str + 1, d_start, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 4,
-                                        nullptr, d_err + 1, st));
+        const int64_t* d_tspans = (const int64_t*)w.wpspans.p;
+        if ((rc = enqueue_token_rows(w, a.b, t, n_tok, d_cnt, d_start, d_err, st))) return rc;
         latok::WordPieceTables wt;
         wt.initial = a.wp->initial.view(a.wp->seed);
         wt.cont = a.wp->cont.view(a.wp->seed);
@@ -3273,9 +3268,7 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
         wt.max_chars = a.wp->max_chars;
         const uint8_t* u8 = (const uint8_t*)a.b.in.p;
         HIP_TRY(latok::launch_wp_count(u8, total, a.b.row, n_str, d_start, d_tspans, n_tok, wt, d_pcnt, st));
-        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-        HIP_TRY(latok::launch_tile_scan(d_pcnt, n_tok + 1, d_prank, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 5,
-                                        a.p_tot + 3, d_err + 1, st));
+        if ((rc = enqueue_row_scan(w, d_pcnt, n_tok + 1, d_prank, d_total + 5, a.p_tot + 3, d_err + 1, st))) return rc;
         int32_t* ids = a.ids;
         int64_t cap = a.cap;
         if (a.padded) {
