@@ -2,16 +2,16 @@
 //   * the reference's native functions one string at a time, as plain element-parallel kernels (compat surface):
 //       _gen_parse_matrix      reference latok/core/src/latok/latok.c:31-138
 //       _combine_matrix_rows   reference latok/core/src/latok/latok.c:275-370
-//   * device-wide exclusive scan (used by the compaction passes and the UTF-8 decoder)
+//   * device-wide exclusive scan (used by the compaction passes and the UTF-8 decoder; the workgroup step is block_scan_add of block_ops.h)
 //   * the staged UTF-8 decoder (code-point units; the byte-space ingest lives in tile_core.h)
 //   * synthetic corpus fill, UTF-8 size reduction and the streaming-read ceiling kernel for the benchmark
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_ops.h"
 #include "corpus_gen.h"
 #include "kernels.h"
 #include "utf8_decode.h"
-#include "wave_ops.h"
 
 namespace latok {
 
@@ -161,28 +161,6 @@ constexpr int kScanBlock = 1024;
 constexpr int kScanItems = 4;                       // elements per thread
 constexpr int kScanChunk = kScanBlock * kScanItems; // elements per block
 
-__device__ __forceinline__ long long block_exclusive_scan_ll(long long v, long long* total, long long* lds /*[16]*/) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long inc = v;   // (written out: shfl_scan_add here reorders the kernels' instructions)
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    long long before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kScanBlock / 64; ++w) {
-        const long long x = lds[w];
-        if (w < wave) before += x;
-        all += x;
-    }
-    *total = all;
-    return before + inc - v;
-}
-
 // out[i] = exclusive prefix inside the block's chunk; block_tot[b] = sum of the chunk
 __global__ __launch_bounds__(kScanBlock) void k_scan_local(const int64_t* __restrict__ in, int64_t n,
                                                            int64_t* __restrict__ out, int64_t* __restrict__ block_tot) {
@@ -195,7 +173,7 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_local(const int64_t* __rest
         sum += v[j];
     }
     long long tot;
-    long long run = block_exclusive_scan_ll(sum, &tot, lds);
+    long long run = block_scan_add<long long, kScanBlock / 64>(sum, lds, &tot) - sum;
 #pragma unroll
     for (int j = 0; j < kScanItems; ++j) {
         if (base + j < n) out[base + j] = run;
@@ -213,7 +191,7 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_totals(int64_t* __restrict_
     long long sum = 0;
     for (int64_t i = lo; i < hi; ++i) sum += block_tot[i];
     long long tot;
-    long long run = block_exclusive_scan_ll(sum, &tot, lds);
+    long long run = block_scan_add<long long, kScanBlock / 64>(sum, lds, &tot) - sum;
     for (int64_t i = lo; i < hi; ++i) {
         const long long v = block_tot[i];
         block_tot[i] = run;
@@ -243,7 +221,7 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_small(const int64_t* __rest
     long long sum = 0;
     for (int64_t i = lo; i < hi; ++i) sum += in[i];
     long long tot;
-    long long run = block_exclusive_scan_ll(sum, &tot, lds);
+    long long run = block_scan_add<long long, kScanBlock / 64>(sum, lds, &tot) - sum;
     for (int64_t i = lo; i < hi; ++i) {
         const long long v = in[i];
         out[i] = run;
@@ -314,29 +292,13 @@ __device__ __forceinline__ uint32_t utf8_lead_mask16(uint4 v) {
     return utf8_lead_nibble(v.x) | (utf8_lead_nibble(v.y) << 4) | (utf8_lead_nibble(v.z) << 8) | (utf8_lead_nibble(v.w) << 12);
 }
 
-__device__ __forceinline__ int block_exclusive_scan_int(int v, int* total, int* lds /*[kU8Threads/64]*/) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int inc = shfl_scan_add(v, lane);
-    __syncthreads();
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kU8Threads / 64; ++w) {
-        if (w < wave) before += lds[w];
-        all += lds[w];
-    }
-    *total = all;
-    return before + inc - v;
-}
-
 __global__ __launch_bounds__(kU8Threads) void k_utf8_block_counts(const uint8_t* __restrict__ u8, int64_t total,
                                                                   int64_t* __restrict__ block_cnt) {
     __shared__ int lds[kU8Threads / 64];
     const int64_t p = ((int64_t)blockIdx.x * kU8Threads + threadIdx.x) * kU8Chunk;
     const int c = p < total ? __popc(utf8_lead_mask16(utf8_load16(u8, p, total))) : 0;
     int tot;
-    (void)block_exclusive_scan_int(c, &tot, lds);
+    (void)block_scan_add<int, kU8Threads / 64>(c, lds, &tot);
     if (threadIdx.x == 0) block_cnt[blockIdx.x] = tot;
 }
 
@@ -367,7 +329,7 @@ __global__ __launch_bounds__(kU8Threads) void k_utf8_decode_chunks(const uint8_t
         }
     }
     int tot;
-    const int excl = block_exclusive_scan_int(__popc(leads), &tot, lds);
+    const int excl = block_scan_add<int, kU8Threads / 64>(__popc(leads), lds, &tot) - __popc(leads);
     if (p < total) chunk_pref[chunk] = (uint16_t)excl;
     // bytes p+16 .. p+18 (what a sequence that starts in my last bytes may need): the next thread's first dword, taken
     // while every lane is active; the last lane of a wave reads them from memory.  A byte that does not exist reads as 0xFF

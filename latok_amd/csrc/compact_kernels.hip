@@ -22,13 +22,13 @@
 #include <stdint.h>
 
 #include "bitscan.h"
+#include "block_ops.h"
 #include "count_table.h"
 #include "kernels.h"
 #include "lane_math.h"
 #include "term_key.h"
 #include "token_hash.h"
 #include "vocab_table.h"
-#include "wave_ops.h"
 
 namespace latok {
 
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(kChainBlock) void k_scan_chained(const int64_t* __r
         v[j] = base + j < n ? in[base + j] : 0;
         sum += v[j];
     }
-    const long long inc = shfl_scan_add(sum, lane);
+    const long long inc = shfl_scan_add(sum, lane);   // (block_scan_add of block_ops.h written out: no barrier in front of the first use)
     if (lane == 63) s_wave_tot[wave] = inc;
     __syncthreads();
     long long wave_excl = 0, agg = 0;
@@ -740,48 +740,30 @@ __global__ __launch_bounds__(scatter_waves(6) * 64) void k_term_scatter(TermScat
 // the host reads it and grows the blob if it has to.  (b) k_count_commit_copy: every workgroup takes its share of the blob with
 // one atomic add on the cursor ctl[1], its fresh slots copy their <= 256 bytes from the text (ct_commit_word) and store their
 // resident word; ctl[2] (distinct) advances by the workgroup's fresh slots.  A share that would leave the blob is not written and
-// raises ctl[3] (the host sized the blob from (a), so this does not happen; the host then fails the counter).
+// raises ctl[3] (the host sized the blob from (a), so this does not happen; the host then fails the counter).  The workgroup sums
+// and prefixes are block_scan_add (block_ops.h).
 constexpr int kCommitBlock = 256;
-__device__ __forceinline__ unsigned commit_block_scan(unsigned v, unsigned* total) {   // exclusive prefix of v over the workgroup
-    __shared__ unsigned s_wave[kCommitBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    unsigned before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < kCommitBlock / 64; ++k) {
-        const unsigned x = s_wave[k];
-        if (k < wave) before += x;
-        all += x;
-    }
-    *total = all;
-    return before + inc - v;
-}
 __global__ __launch_bounds__(kCommitBlock) void k_count_commit_sum(const uint64_t* __restrict__ slots, uint64_t n_slots,
                                                                    unsigned long long* __restrict__ ctl) {
     const uint64_t i = (uint64_t)blockIdx.x * kCommitBlock + threadIdx.x;
     const uint64_t v = i < n_slots ? slots[i] : kCtEmpty;
+    __shared__ unsigned s_wave[kCommitBlock / 64];
     unsigned total;
-    (void)commit_block_scan(ct_is_fresh(v) ? ct_padded_dwords(v) : 0u, &total);
+    (void)block_scan_add<unsigned, kCommitBlock / 64>(ct_is_fresh(v) ? ct_padded_dwords(v) : 0u, s_wave, &total);
     if (threadIdx.x == 0 && total) (void)__hip_atomic_fetch_add(ctl + 0, (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __global__ __launch_bounds__(kCommitBlock) void k_count_commit_copy(uint64_t* __restrict__ slots, uint64_t n_slots,
                                                                     const uint32_t* __restrict__ text, uint32_t* __restrict__ blob,
                                                                     uint64_t blob_dwords, unsigned long long* __restrict__ ctl) {
     __shared__ unsigned long long s_base;
+    __shared__ unsigned s_wave[kCommitBlock / 64];
     const uint64_t i = (uint64_t)blockIdx.x * kCommitBlock + threadIdx.x;
     const uint64_t v = i < n_slots ? slots[i] : kCtEmpty;
     const bool fresh = ct_is_fresh(v);
+    const unsigned dwords = fresh ? ct_padded_dwords(v) : 0u;
     unsigned total, n_fresh;
-    const unsigned before = commit_block_scan(fresh ? ct_padded_dwords(v) : 0u, &total);
-    __syncthreads();                                   // (commit_block_scan's LDS words are read; the second scan writes them again)
-    (void)commit_block_scan(fresh ? 1u : 0u, &n_fresh);
+    const unsigned before = block_scan_add<unsigned, kCommitBlock / 64>(dwords, s_wave, &total) - dwords;
+    (void)block_scan_add<unsigned, kCommitBlock / 64>(fresh ? 1u : 0u, s_wave, &n_fresh);
     if (total == 0) return;                            // (uniform)
     if (threadIdx.x == 0) {
         s_base = __hip_atomic_fetch_add(ctl + 1, (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

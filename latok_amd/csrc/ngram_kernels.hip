@@ -6,7 +6,8 @@
 //   k_ngram_rows   K_s = sum over n in [min_n, max_n] of max(0, c_s - n + 1): the grams of string s.  The chained scan of the
 //                  n_str + 1 entries (the last is 0) gives the row starts in KEY space and the key total K.
 //   k_ngram_keys   one lane per token t.  The lane finds its string s by bisection of the token-space row starts, narrowed per
-//                  workgroup to the rows that touch its kNgBlock tokens, and its index j = t - row_start[s] in the row.  It walks
+//                  workgroup to the rows that touch its kNgBlock tokens (block_rows, row_of_token of block_ops.h; the checked
+//                  record load is its token_bytes), and its index j = t - row_start[s] in the row.  It walks
 //                  the tokens j .. min(j + max_n, c_s) - 1 ONCE with the streaming hash of ngram_text.h -- separator, token, finish
 //                  -- and behind token j + n - 1 stores the key of the gram g(n, j) if n >= min_n: tk_hashed_key of the hash, or
 //                  tk_vocab_probe with ng_equal over the gram's span records (which walks the gram again, only where hash and
@@ -23,29 +24,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_ops.h"
 #include "kernels.h"
 #include "ngram_text.h"
 #include "term_key.h"
 
 namespace latok {
-
-// first i in [lo, hi) with v[i] >= x (hi if none) / with v[i] > x
-__device__ __forceinline__ int64_t ng_lower(const int64_t* __restrict__ v, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (v[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ int64_t ng_upper(const int64_t* __restrict__ v, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (v[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // grams of a string of c tokens
 __device__ __forceinline__ int64_t ng_row_keys(int64_t c, int min_n, int max_n) {
@@ -80,16 +64,11 @@ struct NgramParams {
 
 template <bool VOCAB>
 __global__ __launch_bounds__(kNgBlock) void k_ngram_keys(NgramParams P) {
-    __shared__ int64_t s_lo, s_end;
     const int64_t t0 = (int64_t)blockIdx.x * kNgBlock, t = t0 + threadIdx.x;
-    if (threadIdx.x == 0) {   // the rows that touch the workgroup's tokens
-        const int64_t first = ng_lower(P.row_start, 0, P.n_str, t0);
-        s_end = ng_lower(P.row_start, first, P.n_str, t0 + kNgBlock);
-        s_lo = first > 0 ? first - 1 : 0;   // the row that was open when the block began
-    }
-    __syncthreads();
+    int64_t lo, end;
+    block_rows<kNgBlock>(P.row_start, P.n_str, t0, &lo, &end);
     if (t >= P.n_tok) return;
-    int64_t r = ng_upper(P.row_start, s_lo, s_end, t) - 1;
+    int64_t r = row_of_token(P.row_start, lo, end, t);
     r = r < 0 ? 0 : (r >= P.n_str ? P.n_str - 1 : r);
     const int64_t rs = P.row_start[r], c = P.row_start[r + 1] - rs, j = t - rs;
     const int64_t base = P.row_off[r];
@@ -103,10 +82,8 @@ __global__ __launch_bounds__(kNgBlock) void k_ngram_keys(NgramParams P) {
     auto ld = [text](int64_t i) { return text[i]; };
     // token k of my grams, absolute; a record that does not lie inside the text is an empty token: nothing of it is read
     auto span = [tok_spans, t, base, total](int k) {
-        typedef long long ll2 __attribute__((ext_vector_type(2)));
-        const ll2 rec = *reinterpret_cast<const ll2*>(tok_spans + 2 * (t + k));
-        const int64_t a = base + rec.x, e = base + rec.y;
-        return (rec.x >= 0 && a < e && e <= total) ? NgSpan{a, e} : NgSpan{0, 0};
+        const TokenBytes b = token_bytes(tok_spans, t + k, base, total);
+        return b.ok ? NgSpan{b.a, b.e} : NgSpan{0, 0};
     };
     const VtSlot* const slots = reinterpret_cast<const VtSlot*>(P.vt.slots);
     const uint32_t* const blob = P.vt.blob;

@@ -18,10 +18,12 @@
 //                the key buffer.  The rows' token ranges are disjoint, so no workgroup waits for or writes into another's.
 //   k_terms_emit behind the scan of distinct[] (= indptr, nnz): entry j of row r from keys[row_start[r] + j] to indptr[r] + j, one
 //                thread per token slot, only if nnz fits the capacity.
-// No kernel here waits for another workgroup; all stores are vector stores from plain C++.
+// No kernel here waits for another workgroup; all stores are vector stores from plain C++.  From block_ops.h: the bisections
+// (lower_bound_i64, row_of_token), block_rows (k_terms_emit), block_scan_add (k_terms_tile, k_terms_long).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_ops.h"
 #include "kernels.h"
 #include "term_key.h"
 
@@ -36,24 +38,6 @@ static_assert(kTermsRowMax == kTermsTile, "at most one long row starts in a tile
 constexpr int kRadixBits = 5, kRadixBins = 1 << kRadixBits, kRadixPasses = 7;
 static_assert(kRadixPasses * kRadixBits >= kTkKeyBits && (kRadixPasses & 1), "the passes cover the key and end in the second buffer");
 
-// first i in [lo, hi) with v[i] >= x (hi if none) / with v[i] > x
-__device__ __forceinline__ int64_t terms_lower(const int64_t* __restrict__ v, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (v[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ int64_t terms_upper(const int64_t* __restrict__ v, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (v[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // What the workgroup of tile `tile` owns: rows [first, end) start in it; their short tokens are [a, b); long_row = the long row
 // that starts in it, or -1.
 struct TermsOwn {
@@ -62,8 +46,8 @@ struct TermsOwn {
 __device__ __forceinline__ TermsOwn terms_own(const int64_t* __restrict__ row_start, int64_t n_str, int64_t tile) {
     TermsOwn o;
     const int64_t t0 = tile * kTermsTile;
-    o.first = terms_lower(row_start, 0, n_str, t0);
-    o.end = terms_lower(row_start, o.first, n_str, t0 + kTermsTile);
+    o.first = lower_bound_i64(row_start, 0, n_str, t0);
+    o.end = lower_bound_i64(row_start, o.first, n_str, t0 + kTermsTile);
     o.a = row_start[o.first];   // (row_start has n_str + 1 entries)
     o.b = row_start[o.end];
     o.long_row = -1;
@@ -75,28 +59,6 @@ __device__ __forceinline__ TermsOwn terms_own(const int64_t* __restrict__ row_st
         }
     }
     return o;
-}
-
-// inclusive scan of one int64 per thread over the workgroup (kTermsBlock threads); *total = the sum
-__device__ __forceinline__ long long terms_block_scan(long long v, long long* s_wave, long long* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const long long u = __shfl_up(v, d);
-        if (lane >= d) v += u;
-    }
-    __syncthreads();   // (s_wave may still be read from the call before)
-    if (lane == 63) s_wave[wave] = v;
-    __syncthreads();
-    long long before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < kTermsBlock / 64; ++k) {
-        const long long x = s_wave[k];
-        if (k < wave) before += x;
-        all += x;
-    }
-    *total = all;
-    return v + before;
 }
 
 // packed scan word of a sorted position: entry heads << 48 | found tokens << 32, plus the (signed) value
@@ -123,7 +85,7 @@ __global__ __launch_bounds__(kTermsBlock) void k_terms_tile(uint64_t* __restrict
     for (int i = tid; i < N; i += kTermsBlock) {
         uint64_t c = ~0ull;   // padding sorts behind every key
         if (i < n) {
-            const int64_t r = terms_upper(row_start, o.first, o.end, o.a + i) - 1;   // the row that holds token a + i
+            const int64_t r = row_of_token(row_start, o.first, o.end, o.a + i);   // the row that holds token a + i
             c = ((uint64_t)(row_start[r] - o.a) << kTermsRowShift) | keys[o.a + i];
         }
         comp[i] = c;
@@ -158,7 +120,7 @@ __global__ __launch_bounds__(kTermsBlock) void k_terms_tile(uint64_t* __restrict
         mine[e] = run;
     }
     long long total;
-    const long long before = terms_block_scan(run, s_wave, &total) - run;
+    const long long before = block_scan_add<long long, kTermsBlock / 64>(run, s_wave, &total) - run;
 #pragma unroll
     for (int e = 0; e < kTermsPer; ++e) {
         const int i = tid * kTermsPer + e;
@@ -186,7 +148,7 @@ __global__ __launch_bounds__(kTermsBlock) void k_terms_tile(uint64_t* __restrict
             keys[o.a + rs + rank] = ((uint64_t)((uint32_t)(c >> kTkColumnShift) ^ flip) << 32) | (uint64_t)(uint32_t)sum;
         }
         if ((next >> kTermsRowShift) != (c >> kTermsRowShift)) {
-            const int64_t row = terms_upper(row_start, o.first, o.end, o.a + rs) - 1;
+            const int64_t row = row_of_token(row_start, o.first, o.end, o.a + rs);
             distinct[row] = terms_heads(p) - terms_heads(p0);
             oov[row] = (i + 1 - rs) - (terms_found(p) - terms_found(p0));
         }
@@ -219,7 +181,7 @@ __global__ __launch_bounds__(kTermsBlock) void k_terms_long(uint64_t* __restrict
         unsigned sum = 0;
         for (int e = 0; e < kRadixBins; ++e) sum += cnt[tid * kRadixBins + e];
         long long total;
-        unsigned at = (unsigned)(terms_block_scan((long long)sum, s_wave, &total) - (long long)sum);
+        unsigned at = (unsigned)(block_scan_add<long long, kTermsBlock / 64>((long long)sum, s_wave, &total) - (long long)sum);
         for (int e = 0; e < kRadixBins; ++e) {
             const unsigned c = cnt[tid * kRadixBins + e];
             cnt[tid * kRadixBins + e] = at;
@@ -257,7 +219,7 @@ __global__ __launch_bounds__(kTermsBlock) void k_terms_long(uint64_t* __restrict
         const bool head = valid && (i == 0 || (c >> 1) != (src[i - 1] >> 1));
         const int v = valid ? tk_value(c) : 0;
         long long total;
-        const long long p = terms_block_scan(((long long)head << 32) + (long long)v, s_wave, &total);
+        const long long p = block_scan_add<long long, kTermsBlock / 64>(((long long)head << 32) + (long long)v, s_wave, &total);
         const int sl = (int)(unsigned)p, st = (int)(unsigned)total;
         const long long my_heads = heads + ((p - sl) >> 32), my_sum = sum + sl;
         const uint64_t col = (uint64_t)((uint32_t)(c >> kTkColumnShift) ^ flip) << 32;
@@ -279,17 +241,11 @@ __global__ __launch_bounds__(kTermsBlock) void k_terms_emit(const uint64_t* __re
                                                             const int64_t* __restrict__ nnz_dev, int64_t cap, int32_t* __restrict__ indices,
                                                             int32_t* __restrict__ data) {
     if (*nnz_dev > cap) return;   // the caller's buffers hold `cap` entries: nothing is written when the batch has more
-    __shared__ int64_t s_lo, s_end;
-    const int64_t t0 = (int64_t)blockIdx.x * kTermsTile;
-    if (threadIdx.x == 0) {
-        const int64_t first = terms_lower(row_start, 0, n_str, t0);
-        s_end = terms_lower(row_start, first, n_str, t0 + kTermsTile);
-        s_lo = first > 0 ? first - 1 : 0;   // the row that was open when the tile began
-    }
-    __syncthreads();
-    const int64_t lo = s_lo, end = s_end, t1 = min(n_tok, t0 + kTermsTile);
+    const int64_t t0 = (int64_t)blockIdx.x * kTermsTile, t1 = min(n_tok, t0 + kTermsTile);
+    int64_t lo, end;
+    block_rows<kTermsTile>(row_start, n_str, t0, &lo, &end);
     for (int64_t t = t0 + threadIdx.x; t < t1; t += kTermsBlock) {
-        const int64_t r = terms_upper(row_start, lo, end, t) - 1;   // (>= lo: row_start[lo] <= t0)
+        const int64_t r = row_of_token(row_start, lo, end, t);   // (>= lo: row_start[lo] <= t0)
         const int64_t j = t - row_start[r];
         if (j < distinct[r]) {
             const uint64_t e = keys[t];

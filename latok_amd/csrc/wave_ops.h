@@ -85,8 +85,8 @@ __device__ __forceinline__ int wave_max(int v, int floor) { return lane_read(wav
 
 // ---- scans on __shfl_up (ds_bpermute: one LDS round trip per step; kept where the kernels were measured with them) -------
 // inclusive prefix sum over the 64 lanes (int or long long); lane 63 holds the wave's total.  Not wave_sum: that one is a
-// total on DPP, this one a scan.  (Three sites keep the loop written out -- block_exclusive_scan_ll, k_lead_compress's look-back,
-// k_small_batch: hipcc schedules those kernels differently around the call, and this header came in without changing a kernel.)
+// total on DPP, this one a scan.  (Two sites keep the loop written out -- k_lead_compress's look-back, k_small_batch: hipcc
+// schedules those kernels differently around the call, and this header came in without changing a kernel.)
 template <typename T>
 __device__ __forceinline__ T shfl_scan_add(T inc, int lane) {
 #pragma unroll

@@ -12,47 +12,17 @@
 //   k_wp_rows    indptr[s] = rank[row_start[s]], in the caller's width
 //   k_wp_pad     one thread per cell (s, j) of the [n_str, max_length] block of the padded form
 // A token's string is found by bisection of row_start, narrowed per workgroup to the rows that touch its 256 tokens, as k_terms_emit
-// does.  Table and blob are read with ordinary cached loads (they are what is worth keeping in L2), the text as aligned dwords up
+// does (block_rows, row_of_token of block_ops.h; the checked record load is its token_bytes).  Table and blob are read with ordinary cached loads (they are what is worth keeping in L2), the text as aligned dwords up
 // to the one that holds the token's last byte.  A lane with a long or unknown token keeps its wave busy while the others idle:
 // accepted in this version.  No kernel here waits for another workgroup; all stores are vector stores from plain C++.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_ops.h"
 #include "kernels.h"
 #include "wordpiece.h"
 
 namespace latok {
-
-// first i in [lo, hi) with v[i] >= x (hi if none) / with v[i] > x
-__device__ __forceinline__ int64_t wp_lower(const int64_t* __restrict__ v, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (v[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ int64_t wp_upper(const int64_t* __restrict__ v, int64_t lo, int64_t hi, int64_t x) {
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (v[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// the rows that touch the workgroup's tokens [t0, t0 + kWpBlock): [*lo, *end) holds the row of every one of them
-__device__ __forceinline__ void wp_block_rows(const int64_t* __restrict__ row_start, int64_t n_str, int64_t t0, int64_t* lo, int64_t* end) {
-    __shared__ int64_t s_lo, s_end;
-    if (threadIdx.x == 0) {
-        const int64_t first = wp_lower(row_start, 0, n_str, t0);
-        s_end = wp_lower(row_start, first, n_str, t0 + kWpBlock);
-        s_lo = first > 0 ? first - 1 : 0;   // the row that was open when the block began
-    }
-    __syncthreads();
-    *lo = s_lo;
-    *end = s_end;
-}
 
 // token t: its string and its absolute byte range; false: the record does not lie inside the text (cannot happen with records from
 // the scatter; such a token is skipped, so no load leaves the buffer whatever the workspace holds)
@@ -61,14 +31,13 @@ struct WpToken {
 };
 __device__ __forceinline__ bool wp_token(const int64_t* __restrict__ row_off, int64_t n_str, int64_t total, const int64_t* __restrict__ row_start,
                                          const int64_t* __restrict__ tok_spans, int64_t lo, int64_t end, int64_t t, WpToken* k) {
-    int64_t r = wp_upper(row_start, lo, end, t) - 1;
+    int64_t r = row_of_token(row_start, lo, end, t);
     r = r < 0 ? 0 : (r >= n_str ? n_str - 1 : r);
-    typedef long long ll2 __attribute__((ext_vector_type(2)));
-    const ll2 rec = *reinterpret_cast<const ll2*>(tok_spans + 2 * t);
     k->base = row_off[r];
-    k->a = k->base + rec.x;
-    k->e = k->base + rec.y;
-    return k->base >= 0 && rec.x >= 0 && k->a < k->e && k->e <= total;
+    const TokenBytes b = token_bytes(tok_spans, t, k->base, total);
+    k->a = b.a;
+    k->e = b.e;
+    return b.ok;
 }
 
 #define LATOK_WP_VIEWS(wt)                                                                                                          \
@@ -87,7 +56,7 @@ __global__ __launch_bounds__(kWpBlock) void k_wp_count(const uint32_t* __restric
                                                        int64_t* __restrict__ cnt) {
     const int64_t t0 = (int64_t)blockIdx.x * kWpBlock, t = t0 + threadIdx.x;
     int64_t lo, end;
-    wp_block_rows(row_start, n_str, t0, &lo, &end);
+    block_rows<kWpBlock>(row_start, n_str, t0, &lo, &end);
     if (t > n_tok) return;
     int64_t n = 0;
     WpToken k;
@@ -108,7 +77,7 @@ __global__ __launch_bounds__(kWpBlock) void k_wp_emit(const uint32_t* __restrict
     if (*n_pieces_dev > cap) return;   // the caller's buffers hold `cap` pieces: nothing is written when the batch has more
     const int64_t t0 = (int64_t)blockIdx.x * kWpBlock, t = t0 + threadIdx.x;
     int64_t lo, end;
-    wp_block_rows(row_start, n_str, t0, &lo, &end);
+    block_rows<kWpBlock>(row_start, n_str, t0, &lo, &end);
     if (t >= n_tok) return;
     WpToken k;
     if (!wp_token(row_off, n_str, total, row_start, tok_spans, lo, end, t, &k)) return;

@@ -279,6 +279,50 @@ def test_token_and_piece_totals_round_one_scan_block(gpu, delta):
     check(gpu, [b"a ab"] * (m // 2) + [b"c"] * (m % 2) + [b"x"], words, what=("workgroup", m), forms=FORMS[:1])
 
 
+def _rows_round_the_edges(block, total, opens_at, straddles):
+    """rows of 1 .. 5 distinct short tokens, `total` tokens in all: a row begins at token `opens_at` behind a run of empty strings, a
+    row of five holds token `straddles` as its third, the last row ends on the last token and a run of empty strings ends the batch
+    -> (blobs, tokens per string)"""
+    cuts, k, i = {0, total, opens_at, straddles - 2, straddles + 3}, 0, 0
+    while k < total:
+        cuts.add(k)
+        k += (1, 3, 2, 5, 1, 4)[i % 6]
+        i += 1
+    cuts = sorted(c for c in cuts if not straddles - 2 < c < straddles + 3)
+    blobs, counts = [], []
+    for a, b in zip(cuts, cuts[1:]):
+        if a == opens_at:
+            blobs += [b"", b" ", b"", b""]
+            counts += [0] * 4
+        blobs.append(b" ".join(_word(t) for t in range(a, b)))
+        counts.append(b - a)
+    return blobs + [b"", b"", b" \t", b""], counts + [0] * 4
+
+
+@pytest.mark.parametrize("opens_at, straddles, short", [(1, 2, 0), (2, 1, 3)])
+def test_rows_at_the_edges_of_a_workgroup_of_tokens(gpu, opens_at, straddles, short):
+    """The rows that touch a workgroup's tokens, on multi-token rows: about three workgroups of tokens, every token a word of its
+    own, so a token read under a wrong row shows in its id and in its string-relative span.  At one edge between two workgroups a
+    row begins exactly on the edge, behind empty strings whose row starts lie on it too; at the other a row of five tokens lies
+    across it.  A row cannot both begin on an edge and lie across it, so the two layouts swap the edges.  The batch ends with empty
+    strings whose row starts are the token total; with `short` = 0 that total is itself an edge (the count kernel's entry behind
+    the last token is a workgroup's first)."""
+    block = limits()[0]
+    total = 3 * block - short
+    blobs, counts = _rows_round_the_edges(block, total, opens_at * block, straddles * block)
+    starts = np.concatenate(([0], np.cumsum(counts)))
+    assert (starts[:-1] == opens_at * block).sum() == 5 and counts[int(np.searchsorted(starts, opens_at * block, "right")) - 1] > 0
+    s = int(np.searchsorted(starts, straddles * block, "right")) - 1
+    assert counts[s] == 5 and starts[s] == straddles * block - 2
+    last = len(counts) - 5
+    assert counts[last] > 0 and starts[last] + counts[last] == total and (starts[last + 1:] == total).all() and len(blobs) > 200
+    stems = [bytes([c]) for c in range(97, 110)]
+    words = [_word(t) for t in range(total) if t % 3] + stems + [b"##" + bytes([c]) for c in range(97, 123)]
+    want = check(gpu, blobs, words, what=("edges", opens_at, straddles))
+    assert want[3] == total and ((np.diff(want[0]) > 0) == (np.array(counts) > 0)).all()
+    assert (want[1] == UNK).any() and len(want[1]) > total                 # whole words, words cut into letters, misses
+
+
 def test_the_smallest_batches(gpu):
     words = [b"a", b"##b"]
     for blobs in ([b"a"], [b"ab"], [b"x"], [b""], [b" "], [b"", b""], [b"", b"ab", b""], [b"abb ab a"]):
