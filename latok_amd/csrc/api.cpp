@@ -1167,28 +1167,26 @@ static int decode_utf8_to_workspace(Ctx& g, const Batch& b, bool dev, hipStream_
     return LATOK_OK;
 }
 
-// featurize: per-token column sums on the tile grid (split_kernels.hip: k_features_tiles)
-static int enqueue_features(Ctx& g, const uint8_t* d_codes, const int64_t* d_row, int64_t n_str, int64_t total, const uint64_t* d_bits,
-                            const uint64_t* d_space, const uint64_t* d_kept, const int64_t* d_rank, const int64_t* d_tile_cnt,
-                            const uint16_t* d_pref, const int64_t* d_tile_first, void* d_spans4, int8_t* d_feat, bool out32,
-                            const int64_t* d_n_tokens, int64_t cap, hipStream_t st, latok::DoneSignal done, latok::DeviceTotal dt) {
+// featurize: per-token column sums on the tile grid (split_kernels.hip: k_features_tiles) over the kept tokens of `p`
+static int enqueue_features(Ctx& g, const uint8_t* d_codes, const latok::TokenPlanes& p, void* d_spans4, int8_t* d_feat, bool out32, int64_t cap,
+                            hipStream_t st, latok::DoneSignal done, latok::DeviceTotal dt) {
     latok::FeatParams F;
     F.codes = d_codes;
-    F.row_off = d_row;
-    F.n_str = n_str;
-    F.total = total;
-    F.n_tiles = (total + latok::kTile - 1) / latok::kTile;
-    F.bits = d_bits;
-    F.kept = d_kept;
-    F.tile_rank = d_rank;
-    F.tile_cnt = d_tile_cnt;
-    F.word_pref = d_pref;
-    F.tile_first = d_tile_first;
-    F.space = d_space;
+    F.row_off = p.row_off;
+    F.n_str = p.n_str;
+    F.total = p.total;
+    F.n_tiles = (p.total + latok::kTile - 1) / latok::kTile;
+    F.bits = p.bits;
+    F.kept = p.item_mask;
+    F.tile_rank = p.tile_rank;
+    F.tile_cnt = p.tile_cnt;
+    F.word_pref = p.word_pref;
+    F.tile_first = p.tile_first;
+    F.space = p.space;
     F.features = d_feat;
     F.spans4 = d_spans4;
     F.out32 = out32;
-    F.n_tokens_dev = d_n_tokens;
+    F.n_tokens_dev = p.n_items;
     F.cap = cap;
     F.done = done;
     F.dt = dt;
@@ -1196,8 +1194,8 @@ static int enqueue_features(Ctx& g, const uint8_t* d_codes, const int64_t* d_row
     return LATOK_OK;
 }
 
-// the next epoch of the chained scan's state in workspace `w` (sized by ws_needs); the state is cleared when it is new
-static int next_scan_epoch(Workspace& w, hipStream_t st, unsigned* epoch_out) {
+// the chained scan's state in workspace `w` (sized by ws_needs) on its next epoch; the state is cleared when it is new
+static int next_scan_epoch(Workspace& w, hipStream_t st, latok::ChainState* out) {
     w.scan_epoch = (w.scan_epoch + 1) & 0x3FFFFu;
     // (the state array may have been re-allocated by this call or by an earlier reserve: fresh memory holds anything)
     if (w.chain.gen != w.chain_seen || w.chain_ctl.gen != w.chain_ctl_seen || w.scan_epoch == 0 || !w.chain_ready) {
@@ -1208,16 +1206,36 @@ static int next_scan_epoch(Workspace& w, hipStream_t st, unsigned* epoch_out) {
         w.scan_epoch = 1;
         w.chain_ready = true;
     }
-    *epoch_out = w.scan_epoch;
+    *out = latok::ChainState{(unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, w.scan_epoch};
     return LATOK_OK;
+}
+// The planes of a scanned batch in workspace `w` (kernels.h: TokenPlanes): `total` units in n_str rows; spans = false: offsets (every
+// boundary is an item, no SPACE plane).  bits / space: the two bitmasks where they are not the workspace's own (masks packed before
+// the call; the byte-space and the code-point pair of featurize in byte space).  The item total is the workspace's scalar word 0.
+static latok::TokenPlanes token_planes(const Workspace& w, const int64_t* row, int64_t n_str, int64_t total, bool spans = true,
+                                       const uint64_t* bits = nullptr, const uint64_t* space = nullptr) {
+    latok::TokenPlanes p;
+    p.bits = bits ? bits : (const uint64_t*)w.bits.p;
+    p.space = !spans ? nullptr : bits ? space : (const uint64_t*)w.space.p;
+    p.item_mask = spans ? (const uint64_t*)w.kept.p : p.bits;
+    p.tile_rank = (const int64_t*)w.bases.p;
+    p.tile_cnt = (const int64_t*)w.wcnt.p;
+    p.word_pref = (const uint16_t*)w.wpref.p;
+    p.n_words = (total + 63) / 64;
+    p.total = total;
+    p.row_off = row;
+    p.n_str = n_str;
+    p.tile_first = (const int64_t*)w.tile_first.p;
+    p.n_items = (const int64_t*)w.scalar.p;
+    return p;
 }
 // one chained scan of the sized calls' rows, on its own epoch: dst = the exclusive scan of src[0 .. n), the total -> *d_total and, if
 // asked for, the pinned word r_total; d_flag: the scan's own error flag
 static int enqueue_row_scan(Workspace& w, const int64_t* src, int64_t n, int64_t* dst, int64_t* d_total, int64_t* r_total, int* d_flag, hipStream_t st) {
     int rc;
-    unsigned epoch = 0;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    HIP_TRY(latok::launch_tile_scan(src, n, dst, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total, r_total, d_flag, st));
+    latok::ChainState chain;
+    if ((rc = next_scan_epoch(w, st, &chain))) return rc;
+    HIP_TRY(latok::launch_tile_scan(src, n, dst, chain, d_total, r_total, d_flag, st));
     return LATOK_OK;
 }
 
@@ -1264,17 +1282,9 @@ static int enqueue_compaction_dev(Ctx& g, Workspace& w, const Compaction& c) {
         HIP_TRY(latok::launch_widen_units(c.b.in.p, (int)c.b.in.width(), total, (uint32_t*)w.widened.p, st));
         a.b.in = Input{w.widened.p, Form::Utf32};
     }
-    const int64_t words = (total + 63) / 64;
-    unsigned epoch = 0;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    uint64_t* d_bits = c.pre_bits ? const_cast<uint64_t*>(c.pre_bits) : (uint64_t*)w.bits.p;
-    uint64_t* d_space = c.spans ? (c.pre_bits ? const_cast<uint64_t*>(c.pre_space) : (uint64_t*)w.space.p) : nullptr;
-    uint64_t* d_kept = c.spans ? (uint64_t*)w.kept.p : nullptr;
-    const uint64_t* d_item_mask = c.spans ? d_kept : d_bits;
-    int64_t* d_rank = (int64_t*)w.bases.p;
-    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
-    uint16_t* d_pref = (uint16_t*)w.wpref.p;
-    int64_t* d_tile_first = (int64_t*)w.tile_first.p;
+    latok::ChainState chain;
+    if ((rc = next_scan_epoch(w, st, &chain))) return rc;
+    const latok::TokenPlanes p = token_planes(w, c.b.row, c.b.n_str, total, c.spans, c.pre_bits, c.pre_space);
     uint8_t* d_codes = nullptr;
     if (c.feats && c.pre_codes) {   // packed before (every char's code is there already): only the padding behind the last char
         d_codes = const_cast<uint8_t*>(c.pre_codes);
@@ -1285,8 +1295,8 @@ static int enqueue_compaction_dev(Ctx& g, Workspace& w, const Compaction& c) {
         const size_t tail0 = (size_t)total & ~(size_t)(latok::kTile - 1);
         HIP_TRY(hipMemsetAsync(d_codes + tail0, 0, (size_t)total + latok::kTile + 256 - tail0, st));
     }
-    a.bits = d_bits;
-    a.space = d_space;
+    a.bits = const_cast<uint64_t*>(p.bits);   // (masks packed before the call are not written: stages = 1)
+    a.space = const_cast<uint64_t*>(p.space);
     a.codes = c.pre_codes ? nullptr : d_codes;
     a.stages = c.pre_bits ? 1 : 7;
     if ((rc = run_pipeline(g, w, a))) return rc;
@@ -1296,19 +1306,13 @@ static int enqueue_compaction_dev(Ctx& g, Workspace& w, const Compaction& c) {
     } else if (!c.dt.total) {   // a flow's result words live wherever the caller put them: cleared on the stream
         HIP_TRY(hipMemsetAsync(c.p_tot, 0, 16, st));
     }
-    const int64_t* d_row = c.b.row;
-    const int64_t n_str = c.b.n_str;
-    int64_t* d_total = (int64_t*)w.scalar.p;
     int* d_err = (int*)(c.p_tot + 1);
-    HIP_TRY(latok::launch_word_counts_scan(c.spans, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank,
-                                           (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total, c.p_tot, d_err + 1, st, c.dt));   // (the scan's own flag: the upper half of the pinned word)
+    HIP_TRY(latok::launch_word_counts_scan(c.spans, p, chain, c.p_tot, d_err + 1, st, c.dt));   // (the scan's own flag: the upper half of the pinned word)
     if (c.feats) {   // spans and sums come from one kernel
-        HIP_TRY(latok::launch_string_counts(c.o32, d_item_mask, d_rank, d_pref, d_row, n_str, total, d_total, c.counts, d_err, st, c.dt));
-        return enqueue_features(g, d_codes, d_row, n_str, total, d_bits, d_space, d_kept, d_rank, d_tcnt, d_pref, d_tile_first, c.items,
-                                c.feat, c.o32, d_total, c.cap, st, c.done, c.dt);
+        HIP_TRY(latok::launch_string_counts(c.o32, p, c.counts, d_err, st, c.dt));
+        return enqueue_features(g, d_codes, p, c.items, c.feat, c.o32, c.cap, st, c.done, c.dt);
     }
-    HIP_TRY(latok::launch_counts_scatter(c.spans ? 1 : 0, c.o32, d_bits, d_space, d_item_mask, d_rank, d_tcnt, d_pref, words, total, d_row,
-                                         n_str, d_tile_first, c.items, d_total, c.cap, c.counts, d_err, st, c.done, c.dt));
+    HIP_TRY(latok::launch_counts_scatter(c.spans ? 1 : 0, c.o32, p, c.items, c.cap, c.counts, d_err, st, c.done, c.dt));
     return LATOK_OK;
 }
 
@@ -1559,8 +1563,8 @@ static int enqueue_lead_front(Ctx& g, Workspace& w, const LeadFront& a, LeadPlan
     int64_t* d_rank = (int64_t*)w.bases.p;
     int64_t* d_tcnt = (int64_t*)w.wcnt.p;
     uint16_t* d_pref = (uint16_t*)w.wpref.p;
-    unsigned epoch = 0;
-    if ((rc = next_scan_epoch(w, a.st, &epoch))) return rc;
+    latok::ChainState chain;
+    if ((rc = next_scan_epoch(w, a.st, &chain))) return rc;
     Pipe p;
     p.b = a.b;
     p.bits = t.bmask;
@@ -1570,8 +1574,7 @@ static int enqueue_lead_front(Ctx& g, Workspace& w, const LeadFront& a, LeadPlan
     p.lead_cnt = d_tcnt;
     p.st = a.st;
     if ((rc = run_pipeline(g, w, p))) return rc;
-    HIP_TRY(latok::launch_tile_scan(d_tcnt, c_tiles, d_rank, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, t.total_cps,
-                                    a.r_cps, a.r_err + 1, a.st));
+    HIP_TRY(latok::launch_tile_scan(d_tcnt, c_tiles, d_rank, chain, t.total_cps, a.r_cps, a.r_err + 1, a.st));
     HIP_TRY(latok::launch_lead_compress(t.bmask, t.bspace, t.lead, d_rank, d_tcnt, d_pref, words_b, total_bytes, a.b.row, a.b.n_str, t.total_cps,
                                         t.cpbits, t.cpspace, a.cpbits ? a.cap_words : words_b, t.cp_row, a.r_odd, a.st));
     if (a.codes)
@@ -1639,26 +1642,20 @@ struct Utf8BytesFeats {
 static int enqueue_utf8_bytes_features(Ctx& g, Workspace& w, const Utf8BytesFeats& a) {
     int rc;
     const hipStream_t st = a.st;
-    const int64_t n_str = a.b.n_str, total_bytes = a.b.total, words_b = (total_bytes + 63) / 64;
+    const int64_t n_str = a.b.n_str, total_bytes = a.b.total;
     int* d_err = (int*)a.r_err;
     const int* d_odd = (const int*)a.r_odd;
     const LeadFront f{.b = a.b, .space = true, .codes = true, .r_cps = a.r_cps, .r_err = d_err, .r_odd = (int*)a.r_odd, .st = st};
     LeadPlanes t;
     if ((rc = enqueue_lead_front(g, w, f, &t))) return rc;
     HIP_TRY(latok::launch_pad_codes(t.codes, t.total_cps, total_bytes, st));
-    uint64_t* d_kept = (uint64_t*)w.kept.p;
-    int64_t* d_rank = (int64_t*)w.bases.p;
-    int64_t* d_tcnt = (int64_t*)w.wcnt.p;
-    uint16_t* d_pref = (uint16_t*)w.wpref.p;
-    int64_t* d_total = (int64_t*)w.scalar.p;        // word 0: the token total
-    unsigned epoch = 0;
-    // byte space: kept tokens, their ranks, the total; counts and the four byte positions of every token (the lead ranks are spent)
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    HIP_TRY(latok::launch_word_counts_scan(true, t.bmask, t.bspace, words_b, total_bytes, d_kept, d_tcnt, d_pref, d_rank,
-                                           (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total, a.r_items, d_err + 1, st));
-    HIP_TRY(latok::launch_counts_scatter(2, a.o32, t.bmask, t.bspace, d_kept, d_rank, d_tcnt, d_pref, words_b, total_bytes, a.b.row, n_str,
-                                         (const int64_t*)w.tile_first.p, a.items, d_total, a.cap, a.counts, d_err, st,
-                                         latok::DoneSignal{nullptr, 0, nullptr}, latok::DeviceTotal{nullptr, d_odd}));
+    latok::ChainState chain;
+    // byte space: kept tokens, their ranks, the total (scalar word 0); counts and the four byte positions of every token (the lead ranks are spent)
+    const latok::TokenPlanes pb = token_planes(w, a.b.row, n_str, total_bytes, true, t.bmask, t.bspace);
+    if ((rc = next_scan_epoch(w, st, &chain))) return rc;
+    HIP_TRY(latok::launch_word_counts_scan(true, pb, chain, a.r_items, d_err + 1, st));
+    HIP_TRY(latok::launch_counts_scatter(2, a.o32, pb, a.items, a.cap, a.counts, d_err, st, latok::DoneSignal{nullptr, 0, nullptr},
+                                         latok::DeviceTotal{nullptr, d_odd}));
     // code-point space: the same tokens on the packed masks (the byte-space ranks and kept mask are spent); sums only
     const latok::DeviceTotal dt{t.total_cps, d_odd};
     Pipe q;
@@ -1666,11 +1663,12 @@ static int enqueue_utf8_bytes_features(Ctx& g, Workspace& w, const Utf8BytesFeat
     q.stages = 1;
     q.st = st;
     if ((rc = run_pipeline(g, w, q))) return rc;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    HIP_TRY(latok::launch_word_counts_scan(true, t.cpbits, t.cpspace, words_b, total_bytes, d_kept, d_tcnt, d_pref, d_rank,
-                                           (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total + 2, nullptr, d_err + 1, st, dt));
-    return enqueue_features(g, t.codes, t.cp_row, n_str, total_bytes, t.cpbits, t.cpspace, d_kept, d_rank, d_tcnt, d_pref,
-                            (const int64_t*)w.tile_first.p, nullptr, a.feat, a.o32, d_total, a.cap, st, latok::DoneSignal{nullptr, 0, nullptr}, dt);
+    latok::TokenPlanes pc = token_planes(w, t.cp_row, n_str, total_bytes, true, t.cpbits, t.cpspace);
+    pc.n_items += 2;   // (this scan's own total goes to scalar word 2 and to no result word ...
+    if ((rc = next_scan_epoch(w, st, &chain))) return rc;
+    HIP_TRY(latok::launch_word_counts_scan(true, pc, chain, nullptr, d_err + 1, st, dt));
+    pc.n_items = pb.n_items;   // ... THE token total, the byte-space scan's, gates the sums as it gates the records)
+    return enqueue_features(g, t.codes, pc, nullptr, a.feat, a.o32, a.cap, st, latok::DoneSignal{nullptr, 0, nullptr}, dt);
 }
 
 // Joined token text of a UTF-8 batch in BYTE space (latok_join_tokens_utf8_bytes_batch and its flow form): for every string its
@@ -1698,36 +1696,32 @@ struct JoinTokens {
 static int enqueue_join_tokens(Ctx& g, Workspace& w, const JoinTokens& a) {
     int rc;
     const hipStream_t st = a.st;
-    const int64_t n_str = a.b.n_str, total = a.b.total, words = (total + 63) / 64, c_tiles = (words + 63) / 64;
-    uint64_t* d_bits = (uint64_t*)w.bits.p;
-    uint64_t* d_space = (uint64_t*)w.space.p;
+    const int64_t n_str = a.b.n_str, total = a.b.total;
+    latok::TokenPlanes t = token_planes(w, a.b.row, n_str, total);
+    const int64_t words = t.n_words, c_tiles = (words + 63) / 64;
     int64_t* d_rank = (int64_t*)w.bases.p;
     int64_t* d_tcnt = (int64_t*)w.wcnt.p;
     uint16_t* d_pref = (uint16_t*)w.wpref.p;
-    const int64_t* d_tile_first = (const int64_t*)w.tile_first.p;
     int64_t* d_total = (int64_t*)w.scalar.p;        // word 0: the byte total (word 2: the token total of the counts)
     int* d_err = (int*)a.r_err;
-    unsigned epoch = 0;
+    latok::ChainState chain;
     Pipe p;
     p.b = a.b;
-    p.bits = d_bits;
-    p.space = d_space;
+    p.bits = (uint64_t*)w.bits.p;
+    p.space = (uint64_t*)w.space.p;
     p.st = st;
     if ((rc = run_pipeline(g, w, p))) return rc;
     if (a.counts) {   // the token counts of the spans call, by its own kernels (the ranks are spent once the counts are written)
-        uint64_t* d_kept = (uint64_t*)w.kept.p;
-        if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-        HIP_TRY(latok::launch_word_counts_scan(true, d_bits, d_space, words, total, d_kept, d_tcnt, d_pref, d_rank, (unsigned long long*)w.chain.p,
-                                               (unsigned*)w.chain_ctl.p, epoch, d_total + 2, nullptr, d_err + 1, st));
-        HIP_TRY(latok::launch_counts_scatter(1, a.o32, d_bits, d_space, d_kept, d_rank, d_tcnt, d_pref, words, total, a.b.row, n_str, d_tile_first,
-                                             nullptr, d_total + 2, 0, a.counts, d_err, st));
+        t.n_items = d_total + 2;
+        if ((rc = next_scan_epoch(w, st, &chain))) return rc;
+        HIP_TRY(latok::launch_word_counts_scan(true, t, chain, nullptr, d_err + 1, st));
+        HIP_TRY(latok::launch_counts_scatter(1, a.o32, t, nullptr, 0, a.counts, d_err, st));
     }
     uint64_t* d_body = (uint64_t*)w.jbody.p;
     uint64_t* d_head = (uint64_t*)w.jhead.p;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    HIP_TRY(latok::launch_join_counts(d_bits, d_space, words, total, a.b.row, n_str, d_tile_first, d_body, d_head, d_tcnt, d_pref, st));
-    HIP_TRY(latok::launch_tile_scan(d_tcnt, c_tiles, d_rank, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total, a.r_bytes,
-                                    d_err + 1, st));
+    if ((rc = next_scan_epoch(w, st, &chain))) return rc;
+    HIP_TRY(latok::launch_join_counts(t.bits, t.space, words, total, a.b.row, n_str, t.tile_first, d_body, d_head, d_tcnt, d_pref, st));
+    HIP_TRY(latok::launch_tile_scan(d_tcnt, c_tiles, d_rank, chain, d_total, a.r_bytes, d_err + 1, st));
     HIP_TRY(latok::launch_join_scatter((const uint8_t*)a.b.in.p, total, d_body, d_head, d_rank, d_tcnt, d_pref, words, a.b.row, n_str, a.sep, a.out,
                                        a.cap, d_total, a.out_off, d_err, st));
     return LATOK_OK;
@@ -1739,43 +1733,25 @@ static int enqueue_join_tokens(Ctx& g, Workspace& w, const JoinTokens& a) {
 //   k_word_counts + k_scan_chained                kept mask, token ranks; THE token total -> scalar word 0, r_tokens
 // d_err = the call's error word; the scan's own flag goes to its high half.  `w` was sized by ws_needs with a shape that has
 // .spans = true.  What comes back are the workspace's planes, for the launches that follow.
-struct TokenPlanes {
-    uint64_t *bits = nullptr, *space = nullptr, *kept = nullptr;
-    int64_t *rank = nullptr, *tcnt = nullptr;
-    uint16_t* pref = nullptr;
-    const int64_t* tile_first = nullptr;
-    int64_t* total = nullptr;      // the workspace's scalar words: word 0 is the token total
-    int64_t words = 0;             // 64-bit words of one plane
-};
-static int enqueue_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* r_tokens, int* d_err, hipStream_t st, TokenPlanes* out) {
+static int enqueue_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* r_tokens, int* d_err, hipStream_t st, latok::TokenPlanes* out) {
     int rc;
-    TokenPlanes& t = *out;
-    t.bits = (uint64_t*)w.bits.p;
-    t.space = (uint64_t*)w.space.p;
-    t.kept = (uint64_t*)w.kept.p;
-    t.rank = (int64_t*)w.bases.p;
-    t.tcnt = (int64_t*)w.wcnt.p;
-    t.pref = (uint16_t*)w.wpref.p;
-    t.tile_first = (const int64_t*)w.tile_first.p;
-    t.total = (int64_t*)w.scalar.p;
-    t.words = (b.total + 63) / 64;
-    unsigned epoch = 0;
+    *out = token_planes(w, b.row, b.n_str, b.total);
+    latok::ChainState chain;
     Pipe p;
     p.b = b;
-    p.bits = t.bits;
-    p.space = t.space;
+    p.bits = (uint64_t*)w.bits.p;
+    p.space = (uint64_t*)w.space.p;
     p.st = st;
     if ((rc = run_pipeline(g, w, p))) return rc;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
-    HIP_TRY(latok::launch_word_counts_scan(true, t.bits, t.space, t.words, b.total, t.kept, t.tcnt, t.pref, t.rank, (unsigned long long*)w.chain.p,
-                                           (unsigned*)w.chain_ctl.p, epoch, t.total, r_tokens, d_err + 1, st));
+    if ((rc = next_scan_epoch(w, st, &chain))) return rc;
+    HIP_TRY(latok::launch_word_counts_scan(true, *out, chain, r_tokens, d_err + 1, st));
     return LATOK_OK;
 }
 // The front of the sized calls (term counts, n-grams, WordPiece), which need the token total on the host: enqueue_token_front with the
 // pinned words (p_tot / h_tot: word 0 tokens, word 1 the error word), wait 1, then the refusal of 2^31 tokens or more in the caller's
 // words (`too_many`, one %lld).  The caller sizes its buffers by *n_tok.
 static int sized_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* p_tot, const volatile int64_t* h_tot, hipStream_t st,
-                             const char* too_many, TokenPlanes* t, int64_t* n_tok) {
+                             const char* too_many, latok::TokenPlanes* t, int64_t* n_tok) {
     int rc;
     if ((rc = enqueue_token_front(g, w, b, p_tot, (int*)(p_tot + 1), st, t))) return rc;
     HIP_TRY(hipStreamSynchronize(st));   // wait 1: the token total decides whether the call goes on and what its buffers take
@@ -1784,12 +1760,11 @@ static int sized_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* p_to
     return LATOK_OK;
 }
 // The token rows of the n-gram and WordPiece calls, behind sized_token_front (n_tok > 0, w.wpspans sized for it): the span record of
-// every token at its rank (k_counts_scatter, KIND 1, int64) into w.wpspans, the token count of every string into d_cnt (n_str + 1,
+// every token at its rank (k_counts_scatter, kind 1, int64) into w.wpspans, the token count of every string into d_cnt (n_str + 1,
 // cleared by the caller) and the row starts in token space into d_start (k_scan_chained; the total -> scalar word 4).
-static int enqueue_token_rows(Workspace& w, const Batch& b, const TokenPlanes& t, int64_t n_tok, int64_t* d_cnt, int64_t* d_start, int* d_err, hipStream_t st) {
-    HIP_TRY(latok::launch_counts_scatter(1, false, t.bits, t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, b.total, b.row, b.n_str, t.tile_first,
-                                         (int64_t*)w.wpspans.p, t.total, n_tok, d_cnt, d_err, st));
-    return enqueue_row_scan(w, d_cnt, b.n_str + 1, d_start, t.total + 4, nullptr, d_err + 1, st);
+static int enqueue_token_rows(Workspace& w, const Batch& b, const latok::TokenPlanes& t, int64_t n_tok, int64_t* d_cnt, int64_t* d_start, int* d_err, hipStream_t st) {
+    HIP_TRY(latok::launch_counts_scatter(1, false, t, (int64_t*)w.wpspans.p, n_tok, d_cnt, d_err, st));
+    return enqueue_row_scan(w, d_cnt, b.n_str + 1, d_start, (int64_t*)w.scalar.p + 4, nullptr, d_err + 1, st);
 }
 
 // Token hashes and token ids of a UTF-8 batch in BYTE space (latok_token_hashes_utf8_bytes_batch, latok_token_ids_utf8_bytes_batch and
@@ -1824,18 +1799,16 @@ struct TokenWords {
 static int enqueue_token_words(Ctx& g, Workspace& w, const TokenWords& a) {
     int rc;
     int* d_err = (int*)a.r_err;
-    TokenPlanes t;
+    latok::TokenPlanes t;
     if ((rc = enqueue_token_front(g, w, a.b, a.r_tokens, d_err, a.st, &t))) return rc;
     const uint8_t* u8 = (const uint8_t*)a.b.in.p;
     void* spans = a.words ? a.spans : nullptr;   // the records are written only when the words are
     if (!a.vocab) {
-        HIP_TRY(latok::launch_hash_scatter(a.o32, u8, a.seed, t.bits, t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, a.b.total, a.b.row, a.b.n_str,
-                                           t.tile_first, spans, (uint32_t*)a.words, t.total, a.cap, a.counts, d_err, a.st));
+        HIP_TRY(latok::launch_hash_scatter(a.o32, t, u8, a.seed, spans, (uint32_t*)a.words, a.cap, a.counts, d_err, a.st));
         return LATOK_OK;
     }
     const latok::VocabTable vt = a.vocab->table.view(a.vocab->seed);
-    HIP_TRY(latok::launch_vocab_scatter(a.o32, u8, vt, a.unk, t.bits, t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, a.b.total, a.b.row, a.b.n_str,
-                                        t.tile_first, spans, (int32_t*)a.words, t.total, a.cap, a.counts, d_err, a.st));
+    HIP_TRY(latok::launch_vocab_scatter(a.o32, t, u8, vt, a.unk, spans, (int32_t*)a.words, a.cap, a.counts, d_err, a.st));
     return LATOK_OK;
 }
 // The blocking call behind compact_common's checks: b = the caller's UTF-8 batch (total resolved, n_str > 0, total > 0).  Every
@@ -2374,12 +2347,11 @@ int latok_fold_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, in
     int64_t* d_rank = (int64_t*)w.bases.p;
     int64_t* d_total = (int64_t*)w.scalar.p;
     const uint8_t* d_u8 = (const uint8_t*)c.d.in.p;
-    unsigned epoch = 0;
-    if ((rc = next_scan_epoch(w, st, &epoch))) return rc;
+    latok::ChainState chain;
+    if ((rc = next_scan_epoch(w, st, &chain))) return rc;
     HIP_TRY(latok::launch_fold_starts(c.d.row, n_str, total, d_start, st));
     HIP_TRY(latok::launch_fold_counts(d_u8, total, d_start, fold, g.fold_t, d_pref, d_tcnt, st));
-    HIP_TRY(latok::launch_tile_scan(d_tcnt, latok::fold_tiles(total), d_rank, (unsigned long long*)w.chain.p, (unsigned*)w.chain_ctl.p, epoch, d_total,
-                                    c.p_tot, (int*)(c.p_tot + 1) + 1, st));
+    HIP_TRY(latok::launch_tile_scan(d_tcnt, latok::fold_tiles(total), d_rank, chain, d_total, c.p_tot, (int*)(c.p_tot + 1) + 1, st));
     HIP_TRY(latok::launch_fold_write(d_u8, total, d_start, fold, g.fold_t, d_pref, d_rank, d_tcnt, c.d.row, n_str, d_out, cap, d_total, d_out_off, st));
     if (!dev) HIP_TRY(hipMemcpyAsync(out_off, d_out_off, (size_t)(n_str + 1) * 8, hipMemcpyDeviceToHost, st));   // valid whatever the capacity
     int64_t n = 0;
@@ -2619,13 +2591,14 @@ constexpr const char* kTooManyTermTokens = "the batch has %lld tokens: term coun
 // The CSR tail of the term and n-gram counts: the `n_keys` keys of w.tkeys, whose rows start at d_starts (token space or key space),
 // are sorted and reduced inside every string, the distinct counts scanned into indptr (nnz -> scalar word 5, pinned word 3) and, when
 // the caller gave buffers, the entries emitted.  launch_terms_finish follows at the call site, keys or none.
-static int enqueue_csr_tail(Workspace& w, const TermsCall& a, const TermRows& r, const TokenPlanes& t, const int64_t* d_starts, int64_t n_keys) {
+static int enqueue_csr_tail(Workspace& w, const TermsCall& a, const TermRows& r, const int64_t* d_starts, int64_t n_keys) {
     int rc;
     const int64_t n_str = a.b.n_str;
     uint64_t* d_keys = (uint64_t*)w.tkeys.p;
+    int64_t* d_nnz = (int64_t*)w.scalar.p + 5;
     HIP_TRY(latok::launch_terms_reduce(d_keys, (uint64_t*)w.tkeys2.p, d_starts, n_str, n_keys, a.v != nullptr, r.distinct, r.oov, a.st));
-    if ((rc = enqueue_row_scan(w, r.distinct, n_str + 1, r.indptr, t.total + 5, a.p_tot + 3, (int*)(a.p_tot + 1) + 1, a.st))) return rc;
-    if (a.indices) HIP_TRY(latok::launch_terms_emit(d_keys, d_starts, n_str, n_keys, r.distinct, r.indptr, t.total + 5, a.fill_cap, a.indices, a.data, a.st));
+    if ((rc = enqueue_row_scan(w, r.distinct, n_str + 1, r.indptr, d_nnz, a.p_tot + 3, (int*)(a.p_tot + 1) + 1, a.st))) return rc;
+    if (a.indices) HIP_TRY(latok::launch_terms_emit(d_keys, d_starts, n_str, n_keys, r.distinct, r.indptr, d_nnz, a.fill_cap, a.indices, a.data, a.st));
     return LATOK_OK;
 }
 static int enqueue_term_counts(Ctx& g, Workspace& w, TermsCall& a) {
@@ -2633,7 +2606,7 @@ static int enqueue_term_counts(Ctx& g, Workspace& w, TermsCall& a) {
     const hipStream_t st = a.st;
     const int64_t total = a.b.total, n_str = a.b.n_str;
     int* d_err = (int*)(a.p_tot + 1);
-    TokenPlanes t;
+    latok::TokenPlanes t;
     if ((rc = sized_token_front(g, w, a.b, a.p_tot, a.h_tot, st, kTooManyTermTokens, &t, &a.n_tokens))) return rc;
     const int64_t n_tok = a.n_tokens;
     if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .term_tokens = n_tok}).data(), kWsNeeds)))
@@ -2643,11 +2616,10 @@ static int enqueue_term_counts(Ctx& g, Workspace& w, TermsCall& a) {
     if (n_tok > 0) {
         latok::VocabTable vt;
         if (a.v) vt = a.v->table.view(a.v->seed);
-        HIP_TRY(latok::launch_term_scatter((const uint8_t*)a.b.in.p, a.v ? &vt : nullptr, a.seed, (uint32_t)a.n_features, a.alternate_sign != 0, t.bits,
-                                           t.space, t.kept, t.rank, t.tcnt, t.pref, t.words, total, a.b.row, n_str, t.tile_first, t.total,
+        HIP_TRY(latok::launch_term_scatter(t, (const uint8_t*)a.b.in.p, a.v ? &vt : nullptr, a.seed, (uint32_t)a.n_features, a.alternate_sign != 0,
                                            (uint64_t*)w.tkeys.p, r.cnt, d_err, st));
-        if ((rc = enqueue_row_scan(w, r.cnt, n_str + 1, r.start, t.total + 4, nullptr, d_err + 1, st))) return rc;
-        if ((rc = enqueue_csr_tail(w, a, r, t, r.start, n_tok))) return rc;
+        if ((rc = enqueue_row_scan(w, r.cnt, n_str + 1, r.start, (int64_t*)w.scalar.p + 4, nullptr, d_err + 1, st))) return rc;
+        if ((rc = enqueue_csr_tail(w, a, r, r.start, n_tok))) return rc;
     }
     HIP_TRY(latok::launch_terms_finish(a.o32, r.indptr, r.oov, n_str, a.indptr, a.oov, st));
     return LATOK_OK;
@@ -2668,7 +2640,7 @@ static int enqueue_ngram_counts(Ctx& g, Workspace& w, TermsCall& a) {
     const hipStream_t st = a.st;
     const int64_t total = a.b.total, n_str = a.b.n_str;
     int* d_err = (int*)(a.p_tot + 1);
-    TokenPlanes t;
+    latok::TokenPlanes t;
     if ((rc = sized_token_front(g, w, a.b, a.p_tot, a.h_tot, st, kTooManyTermTokens, &t, &a.n_tokens))) return rc;
     const int64_t n_tok = a.n_tokens;
     WsShape shape{.spans = true, .term_rows = n_str + 1, .ng_tokens = n_tok, .ng_rows = n_str + 1};
@@ -2680,7 +2652,7 @@ static int enqueue_ngram_counts(Ctx& g, Workspace& w, TermsCall& a) {
     if (n_tok > 0) {
         if ((rc = enqueue_token_rows(w, a.b, t, n_tok, r.cnt, r.start, d_err, st))) return rc;
         HIP_TRY(latok::launch_ngram_rows(r.cnt, n_str, a.min_n, a.max_n, d_kcnt, st));
-        if ((rc = enqueue_row_scan(w, d_kcnt, n_str + 1, d_kstart, t.total + 6, a.p_tot + 5, d_err + 1, st))) return rc;
+        if ((rc = enqueue_row_scan(w, d_kcnt, n_str + 1, d_kstart, (int64_t*)w.scalar.p + 6, a.p_tot + 5, d_err + 1, st))) return rc;
         HIP_TRY(hipStreamSynchronize(st));   // wait 2: the key total decides whether the call goes on and what the keys take
         int64_t n_tok_again = 0;
         if ((rc = finish_totals(w, a.h_tot, 0, &n_tok_again))) return rc;
@@ -2695,7 +2667,7 @@ static int enqueue_ngram_counts(Ctx& g, Workspace& w, TermsCall& a) {
             HIP_TRY(latok::launch_ngram_keys((const uint8_t*)a.b.in.p, total, a.b.row, n_str, r.start, d_kstart, (const int64_t*)w.wpspans.p, n_tok, n_keys,
                                              a.min_n, a.max_n, a.sep, a.v ? &vt : nullptr, a.seed, (uint32_t)a.n_features, a.alternate_sign != 0,
                                              (uint64_t*)w.tkeys.p, st));
-            if ((rc = enqueue_csr_tail(w, a, r, t, d_kstart, n_keys))) return rc;
+            if ((rc = enqueue_csr_tail(w, a, r, d_kstart, n_keys))) return rc;
         }
     }
     HIP_TRY(latok::launch_terms_finish(a.o32, r.indptr, r.oov, n_str, a.indptr, a.oov, st));
@@ -3244,10 +3216,10 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
     const hipStream_t st = a.st;
     const int64_t total = a.b.total, n_str = a.b.n_str;
     int* d_err = (int*)(a.p_tot + 1);
-    TokenPlanes t;
+    latok::TokenPlanes t;
     if ((rc = sized_token_front(g, w, a.b, a.p_tot, a.h_tot, st, "the batch has %lld tokens: a call takes fewer than 2^31 pieces", &t, &a.n_tokens)))
         return rc;
-    int64_t* d_total = t.total;
+    int64_t* d_total = (int64_t*)w.scalar.p;
     const int64_t n_tok = a.n_tokens;
     if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok}).data(), kWsNeeds)))
         return rc;
@@ -3541,12 +3513,11 @@ int latok_counter_info(const latok_counter* counter, int64_t* max_words, int64_t
 }
 
 // everything of an update from k_count_scatter on: a failure in here leaves the counter failed (the caller sets the flag)
-static int count_scatter_and_commit(Ctx& g, Workspace& w, Counter& c, const Batch& d, const TokenPlanes& tp, int64_t* p_tot,
+static int count_scatter_and_commit(Ctx& g, Workspace& w, Counter& c, const Batch& d, const latok::TokenPlanes& tp, int64_t* p_tot,
                                     const volatile int64_t* h_tot, int64_t* stats4, hipStream_t st) {
     uint64_t ctl[8];
     latok::CountTable t = count_table_of(c);
-    HIP_TRY(latok::launch_count_scatter((const uint8_t*)d.in.p, t, tp.bits, tp.space, tp.kept, tp.rank, tp.tcnt, tp.pref, tp.words, d.total, d.row,
-                                        d.n_str, tp.tile_first, tp.total, (int*)(p_tot + 1), st));
+    HIP_TRY(latok::launch_count_scatter(tp, (const uint8_t*)d.in.p, t, (int*)(p_tot + 1), st));
     HIP_TRY(latok::launch_count_commit_sum(t, st));
     HIP_TRY(hipMemcpyAsync(ctl, c.ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));   // the first of the call's two waits: the commit's need is known
@@ -3607,7 +3578,7 @@ int latok_count_tokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
     Workspace& w = g.ws;
     HIP_TRY(hipMemsetAsync(c->ctl.p, 0, 40, st));                    // this call's tallies and fresh dwords
     HIP_TRY(hipMemsetAsync(c->ctl.as<uint64_t>() + 7, 0, 8, st));      // ... and the overflow flag
-    TokenPlanes t;
+    latok::TokenPlanes t;
     if ((rc = enqueue_token_front(g, w, d, p_tot, (int*)(p_tot + 1), st, &t))) return rc;
     // from here to the end of the commit the table may hold slots that point into the caller's text
     if ((rc = count_scatter_and_commit(g, w, *c, d, t, p_tot, call.h_tot, stats4, st))) {

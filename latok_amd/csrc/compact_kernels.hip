@@ -5,7 +5,7 @@
 //   token spans        slice between consecutive boundaries, strip, drop ''   reference default_tokenizer.py:149-158
 //   token features     per-token sums of the 25 matrix columns (featurize)    reference default_tokenizer.py:163-191
 //   joined token text  the tokens themselves, sep.join per string, UTF-8 out  reference default_tokenizer.py:149-160   (below: "joined token text")
-//   token hashes       MurmurHash3 x86_32 of every token's UTF-8 bytes        reference default_tokenizer.py:149-160   (KIND 3 of k_counts_scatter's body)
+//   token hashes       MurmurHash3 x86_32 of every token's UTF-8 bytes        reference default_tokenizer.py:149-160   (HashTokens, k_hash_scatter)
 //
 // Inputs are the two bitmasks the tile kernel writes (boundary bits, SPACE bits; bit i = packed char i) and row_off.
 // Because strings are contiguous and ordered in the packed buffer, "all offsets of string 0, then string 1, ..." is
@@ -20,6 +20,8 @@
 // int64 or, on request (LATOK_OUT_INT32), as int32: the records are most of the traffic of these paths.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "bitscan.h"
 #include "block_ops.h"
@@ -224,49 +226,28 @@ __global__ __launch_bounds__(256) void k_string_counts(const uint64_t* __restric
 // One wave per 64 consecutive words (4096 chars).  The wave
 //   (a) finds where the owning string of every position begins: the string starts inside the tile become bits in LDS,
 //       the last start before each word is a prefix max over the lanes, and the string that was open when the tile began
-//       comes from the per-tile string index the tile kernel publishes;
+//       comes from the per-tile string index the tile kernel publishes (tile_string_starts);
 //   (b) lane = word: walks the items of its word (all mask arithmetic inside the word; only a token that runs past the
 //       word's end follows the masks further) and puts the records into an LDS window at their rank inside the wave;
 //   (c) streams the window to the output: consecutive lanes write consecutive 8-byte words.
-// KIND 0: offsets[k] = p - start of its string.   KIND 1: spans[2k..] = stripped extent.
-// KIND 2: spans4[4k..] = {raw start, raw end, stripped start, stripped end}: featurize's span record, for UTF-8 in BYTE space --
-// the sums of the same tokens are formed in code-point space by k_features_tiles, which then writes no records (a token has
-// the same rank in both spaces).  The other forms of featurize get their records from k_features_tiles, together with the sums.
-// KIND 3 (k_hash_scatter): KIND 1's records (out may be NULL: none) and hashes[k] = MurmurHash3 x86_32 of the stripped token's
-// bytes (token_hash.h).  In the token-major loop lane j holds token j's byte range: it walks its own token -- neighbouring lanes
-// hold neighbouring tokens, their aligned dword loads share cache lines --, unless the token is longer than kHashWaveBytes: those
-// the wave takes one at a time behind the round, 256 bytes per step with coalesced loads, every lane mixing its own block and
-// the h chain folded in lane order, so a long token costs its length once, with the whole wave at work.
-// KIND 4 (k_vocab_scatter): KIND 3 with the hash kept in its lane instead of stored: the lane that hashed a short token probes the
-// vocabulary table with it (vocab_table.h: one 16-byte slot per step, at most n_slots steps), compares the bytes where hash and
-// length agree and stores ids[k] = the word's id or unk.  A long token's hash is wave-uniform, so the wave probes in step -- every
-// lane asks for the same slot, one request -- and compares a candidate 64 dwords per step with coalesced loads; a ballot decides.
-// The table and the blob are read with ordinary cached loads (they are what is worth keeping in L2); no hash goes through memory.
-// KIND 5 (k_count_scatter): KIND 4's lane path with a counting table in the vocabulary's place (count_table.h): the lane finds its
-// token's slot or claims an empty one with one CAS -- nothing waits for another thread --, and the hit is counted in a per-wave
-// accumulator in LDS, a direct-mapped {slot + 1, count} array of kCountAccEntries entries: the tag is claimed with an LDS CAS, a
-// hit is an LDS add, a conflicting entry adds to the global count directly.  Behind the tile's last round the wave flushes its
-// entries with no-return atomic adds, so a hot word costs one global atomic per tile, not one per token.  It writes no records.
-// A token of more than max_word_bytes bytes is tallied as long and never entered: there is no whole-wave form.  The three
-// tallies (counted, long, dropped) are reduced over the wave: one atomic each per tile.
-// KIND 6 (k_term_scatter): KIND 4's two paths with a term key (term_key.h) stored at the token's rank in the workspace instead of an
-// id in caller memory: the id with a found bit of its own, or -- with no table, n_features > 0 -- the hash bucket and the sign.
-// terms_kernels.hip sorts and reduces the keys inside every string.  It writes no records.
-constexpr int scatter_waves(int kind) { return 4; }   // waves per workgroup
+// Offsets (offsets[k] = p - start of its string) take (b) and (c) word-major (offsets_walk).  Every other form takes them
+// token-major (token_walk) and hands each token to its consumer, below: SpanRecords, HashTokens, IdTokens, CountTokens, TermTokens.
+constexpr int kScatterWaves = 4;      // waves per workgroup of every scatter kernel; both block roles use its 256 threads
+constexpr int kScatterCodes = 1024;   // items per round
+constexpr int kScatterRowsEnd = kScatterCodes * 2 + 64 * 48;   // token-major LDS: the item codes (2 B each), then the 48-byte mask rows of the 64 words
 struct HashArgs {
     const uint32_t* text = nullptr;   // the batch's bytes as aligned dwords (the buffer is 16-byte aligned)
     uint32_t* hashes = nullptr;
     uint32_t seed = 0;
 };
-struct VocabArgs {                    // (KIND 4; the text and the seed travel in HashArgs)
+struct VocabArgs {                    // (the text and the seed travel in HashArgs)
     const VtSlot* slots = nullptr;
     const uint32_t* blob = nullptr;
     uint64_t n_slots = 0;             // a power of two
     int32_t* ids = nullptr;
     int32_t unk = 0;
 };
-
-struct CountArgs {                    // (KIND 5; the text and the seed travel in HashArgs)
+struct CountArgs {                    // (the text and the seed travel in HashArgs)
     uint64_t* slots = nullptr;        // one 8-byte word per slot (count_table.h), 0 = empty
     unsigned long long* counts = nullptr;
     const uint32_t* blob = nullptr;   // the resident words, stored by earlier launches
@@ -274,7 +255,7 @@ struct CountArgs {                    // (KIND 5; the text and the seed travel i
     unsigned long long* tally = nullptr;   // this call's {counted, long, dropped}
     int max_word_bytes = 0;           // 1 .. kHashWaveBytes
 };
-struct TermArgs {                     // (KIND 6; the text and the seed travel in HashArgs, the table in VocabArgs)
+struct TermArgs {                     // (the text and the seed travel in HashArgs, the table in VocabArgs)
     uint64_t* keys = nullptr;         // one term_key.h key per token, at its rank
     uint32_t n_features = 0;          // 0: the vocabulary form
     bool alternate_sign = false;
@@ -287,163 +268,315 @@ struct CtDeviceAtomics {              // count_table.h's policy: relaxed, agent 
     }
 };
 
-template <int KIND, typename OUT>
-__device__ __forceinline__ void counts_scatter_block(
-    const uint64_t* __restrict__ bits, const uint64_t* __restrict__ space, const uint64_t* __restrict__ item_mask,
-    const int64_t* __restrict__ tile_rank, const int64_t* __restrict__ tile_cnt, const uint16_t* __restrict__ word_pref,
-    int64_t n_words, int64_t total, const int64_t* __restrict__ row_off, int64_t n_str,
-    const int64_t* __restrict__ tile_first, OUT* __restrict__ out, const int64_t* __restrict__ n_items_dev, int64_t cap,
-    OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, unsigned vb,     // vb: (virtual) workgroup index
-    const HashArgs ha = HashArgs{},                                                              // (KIND 3 and 4 only)
-    const VocabArgs va = VocabArgs{},                                                            // (KIND 4 only)
-    const CountArgs ca = CountArgs{},                                                            // (KIND 5 only)
-    const TermArgs ta = TermArgs{}) {                                                            // (KIND 6 only)
-    constexpr bool kHashes = KIND == 3 || KIND == 4 || KIND == 5 || KIND == 6;                   // records optional, tokens hashed
-    static_assert(scatter_waves(KIND) * 64 == 256, "both roles use 256-thread workgroups");
-    if (vb >= n_scatter_blocks) {   // role 2: one thread per string
-        if (counts)
-            string_counts_role<OUT>((int64_t)(vb - n_scatter_blocks) * 256 + threadIdx.x, item_mask, tile_rank, word_pref,
-                                    row_off, n_str, total, *n_items_dev, counts, err);
-        return;
+// ---- the consumers of the token-major walk ---------------------------------------------------------------------------
+// A consumer says what is done with the stripped token [a2, e2) of rank `rank`: short_token in the lane that holds it (p, e: the raw
+// extent; lo: the start of its string), long_token -- kWaveTokens: a token of more than kHashWaveBytes bytes, taken by the whole wave
+// behind the round with its hash h already formed; `mine`: this lane held it -- and flush once the tile is done.  begin gets the
+// kLdsBytes of LDS a consumer asked for.  The consumers that hash read `text` and `seed` from their HashArgs.
+template <class T>
+struct ArrayOf {   // the loaders of token_hash.h / vocab_table.h / count_table.h over the text, a blob or the slots: ordinary cached loads
+    const T* p;
+    template <class I>
+    __device__ __forceinline__ T operator()(I i) const { return p[i]; }
+};
+using DwordsOf = ArrayOf<uint32_t>;
+// A long token's hash is wave-uniform, so the wave probes in step: every lane asks for the same slot -- one request -- ...
+struct WaveSlotsOf {
+    const VtSlot* p;
+    __device__ __forceinline__ VtSlot operator()(uint64_t i) const {
+        const VtSlot v = p[i];
+        return VtSlot{(uint32_t)__builtin_amdgcn_readfirstlane((int)v.hash), __builtin_amdgcn_readfirstlane(v.id),
+                      (uint32_t)__builtin_amdgcn_readfirstlane((int)v.off), (uint32_t)__builtin_amdgcn_readfirstlane((int)v.len)};
     }
-    // role 1: one wave per tile.  The caller's buffer holds `cap` items; when the batch has more, nothing is written
-    // (the host reports the needed size) -- the launch does not have to wait for the host to learn the total.
-    if (*n_items_dev > cap) return;
-    constexpr int kScatterWaves = scatter_waves(KIND);
-    constexpr int kCodes = 1024;                                    // items per round
-    // KIND 0: window of values (OUT); KIND 1: the item codes (2 B each) + the 48-byte mask rows of the 64 words.  Sized for
-    // what the form needs (it was 8 KB per wave for every form: 4 workgroups per CU).  Measured on C2, same box: int32 offsets
-    // 0.174 -> 0.165 ms and int32 spans 0.233 -> 0.222 at 7 - 8 workgroups per CU, but int64 spans 0.247 -> 0.256 (twice
-    // the store stream per token): that form keeps the footprint that holds it at 4.
-    constexpr int kSpan64Buf = 6656;   // int64 spans: 5 workgroups per CU (4: C3 +2.5 %; 7: C2 +4 %)
-    constexpr int kAccAt = kCodes * 2 + 64 * 48;                                   // (KIND 5, int32 form) the accumulator lies behind the rows
-    constexpr int kBufBytes = (KIND == 0 ? kCodes * (int)sizeof(OUT) : (sizeof(OUT) == 8 ? kSpan64Buf : kCodes * 2 + 64 * 48)) +
-                              (KIND == 5 ? 8 * kCountAccEntries : 0);
-    static_assert(KIND != 5 || sizeof(OUT) == 4, "the counting form is instantiated for int32 only");
-    __shared__ __attribute__((aligned(16))) uint8_t buf_s[kScatterWaves][kBufBytes];
-    __shared__ long long smax_s[kScatterWaves][65];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t w0 = ((int64_t)vb * kScatterWaves + wave) * 64;
-    if (w0 >= n_words) return;                                      // whole wave (no block-wide barrier is used below)
-    const int64_t w = w0 + lane;
-    const int n_wave = (int)tile_cnt[w0 >> 6];
-    if (n_wave == 0) return;
-    const uint64_t x = w < n_words ? item_mask[w] : 0ull;
-    const int off = w < n_words ? (int)word_pref[w] : 0;            // rank of my first item inside the wave
-    const int64_t base_out = tile_rank[w0 >> 6];
-    uint16_t* codes = reinterpret_cast<uint16_t*>(buf_s[wave]);
-    OUT* win = reinterpret_cast<OUT*>(buf_s[wave]);
-    long long* smax = smax_s[wave];
+};
+// ... and compares a candidate 64 dwords per step with coalesced loads; a ballot decides.
+struct WaveEqual {
+    DwordsOf text;
+    int64_t a, e;
+    DwordsOf blob;
+    int lane;
+    __device__ __forceinline__ bool operator()(uint32_t off) const {
+        const int64_t rounds_c = vt_wave_rounds(a, e);
+        for (int64_t r = 0; r < rounds_c; ++r)
+            if (__ballot(vt_wave_differs(text, a, e, blob, off, r, lane))) return false;
+        return true;
+    }
+};
+struct TokenConsumer {   // what a consumer leaves out
+    static constexpr bool kWordMajor = false, kWaveTokens = false;
+    static constexpr int kLdsBytes = 0;
+    __device__ __forceinline__ void begin(uint8_t*, int) {}
+    __device__ __forceinline__ void flush(int) {}
+};
+// the stripped extent of a token, string relative, as one record of two fields at its rank
+template <typename OUT>
+__device__ __forceinline__ void store_span(OUT* out, int64_t rank, int64_t a2, int64_t e2, int64_t lo) {
+    typedef OUT out2 __attribute__((ext_vector_type(2)));
+    out2 v;
+    v.x = (OUT)(a2 - lo);
+    v.y = (OUT)(e2 - lo);
+    __builtin_nontemporal_store(v, reinterpret_cast<out2*>(out) + rank);
+}
+// Span records (k_counts_scatter).  FIELDS = 2 (kind 1): spans[2k..] = stripped extent.  FIELDS = 4 (kind 2): spans4[4k..] = {raw start,
+// raw end, stripped start, stripped end}: featurize's span record, for UTF-8 in BYTE space -- the sums of the same tokens are formed in
+// code-point space by k_features_tiles, which then writes no records (a token has the same rank in both spaces).  The other forms of
+// featurize get their records from k_features_tiles, together with the sums.
+template <typename OUT, int FIELDS>
+struct SpanRecords : TokenConsumer {
+    OUT* out;
+    __device__ __forceinline__ void short_token(int64_t rank, int64_t p, int64_t e, int64_t a2, int64_t e2, int64_t lo) {
+        if (FIELDS == 2) {
+            store_span(out, rank, a2, e2, lo);
+        } else if (sizeof(OUT) == 4) {                    // the record is 16 or 32 bytes: aligned 16-byte stores
+            typedef OUT out4 __attribute__((ext_vector_type(4)));
+            out4 r;
+            r.x = (OUT)(p - lo);
+            r.y = (OUT)(e - lo);
+            r.z = (OUT)(a2 - lo);
+            r.w = (OUT)(e2 - lo);
+            __builtin_nontemporal_store(r, reinterpret_cast<out4*>(out) + rank);
+        } else {
+            store_span(out, 2 * rank, p, e, lo);
+            store_span(out, 2 * rank + 1, a2, e2, lo);
+        }
+    }
+};
+// Token hashes (k_hash_scatter): SpanRecords<OUT, 2>'s records (out may be NULL: none) and hashes[k] = MurmurHash3 x86_32 of the stripped
+// token's bytes (token_hash.h).  In the token-major loop lane j holds token j's byte range: it walks its own token -- neighbouring lanes
+// hold neighbouring tokens, their aligned dword loads share cache lines --, unless the token is longer than kHashWaveBytes: those
+// the wave takes one at a time behind the round, 256 bytes per step with coalesced loads, every lane mixing its own block and
+// the h chain folded in lane order, so a long token costs its length once, with the whole wave at work.
+template <typename OUT>
+struct HashTokens : TokenConsumer {
+    static constexpr bool kWaveTokens = true;
+    HashArgs h;
+    OUT* out;
+    __device__ __forceinline__ void short_token(int64_t rank, int64_t, int64_t, int64_t a2, int64_t e2, int64_t lo) {
+        if (out) store_span(out, rank, a2, e2, lo);
+        if (e2 - a2 <= kHashWaveBytes) __builtin_nontemporal_store(th_hash_lane(DwordsOf{h.text}, a2, e2, h.seed), h.hashes + rank);
+    }
+    __device__ __forceinline__ void long_token(int64_t rank, int64_t, int64_t, uint32_t hash, int, bool mine) {
+        if (mine) __builtin_nontemporal_store(hash, h.hashes + rank);
+    }
+};
+// Token ids (k_vocab_scatter): HashTokens with the hash kept in its lane instead of stored: the lane that hashed a short token probes the
+// vocabulary table with it (vocab_table.h: one 16-byte slot per step, at most n_slots steps), compares the bytes where hash and
+// length agree and stores ids[k] = the word's id or unk.  A long token is probed and compared by the wave in step (WaveSlotsOf,
+// WaveEqual).  The table and the blob are read with ordinary cached loads (they are what is worth keeping in L2); no hash goes
+// through memory.
+template <typename OUT>
+struct IdTokens : TokenConsumer {
+    static constexpr bool kWaveTokens = true;
+    HashArgs h;
+    VocabArgs v;
+    OUT* out;
+    __device__ __forceinline__ void short_token(int64_t rank, int64_t, int64_t, int64_t a2, int64_t e2, int64_t lo) {
+        if (out) store_span(out, rank, a2, e2, lo);
+        if (e2 - a2 > kHashWaveBytes) return;
+        const DwordsOf text{h.text};
+        const int32_t id = vt_lookup_lane(text, a2, e2, th_hash_lane(text, a2, e2, h.seed), ArrayOf<VtSlot>{v.slots}, DwordsOf{v.blob}, v.n_slots, v.unk);
+        __builtin_nontemporal_store(id, v.ids + rank);
+    }
+    __device__ __forceinline__ void long_token(int64_t rank, int64_t a, int64_t e, uint32_t hash, int lane, bool mine) {
+        const uint32_t hu = (uint32_t)__builtin_amdgcn_readfirstlane((int)hash);
+        const int32_t id = vt_probe(WaveSlotsOf{v.slots}, v.n_slots, hu, (uint32_t)(e - a), WaveEqual{{h.text}, a, e, {v.blob}, lane}, v.unk);
+        if (mine) __builtin_nontemporal_store(id, v.ids + rank);
+    }
+};
+// Token counts (k_count_scatter): IdTokens' lane path with a counting table in the vocabulary's place (count_table.h): the lane finds its
+// token's slot or claims an empty one with one CAS -- nothing waits for another thread --, and the hit is counted in a per-wave
+// accumulator in LDS, a direct-mapped {slot + 1, count} array of kCountAccEntries entries: the tag is claimed with an LDS CAS, a
+// hit is an LDS add, a conflicting entry adds to the global count directly.  Behind the tile's last round the wave flushes its
+// entries with no-return atomic adds, so a hot word costs one global atomic per tile, not one per token.  It writes no records.
+// A token of more than max_word_bytes bytes is tallied as long and never entered: there is no whole-wave form.  The three
+// tallies (counted, long, dropped) are reduced over the wave: one atomic each per tile.
+struct CountTokens : TokenConsumer {
+    static constexpr int kLdsBytes = 8 * kCountAccEntries;
+    HashArgs h;
+    CountArgs c;
+    uint32_t* acc = nullptr;   // the wave's accumulator: tags (slot + 1, 0 = free) in the first half, counts in the second
+    unsigned n_counted = 0, n_long = 0, n_dropped = 0;   // my tallies
+    __device__ __forceinline__ void begin(uint8_t* lds, int lane) {
+        acc = reinterpret_cast<uint32_t*>(lds);
+        for (int i = lane; i < 2 * kCountAccEntries; i += 64) acc[i] = 0u;   // (visible behind the round's first wave barrier)
+    }
+    __device__ __forceinline__ void short_token(int64_t, int64_t, int64_t, int64_t a2, int64_t e2, int64_t) {
+        if (e2 - a2 > c.max_word_bytes) {
+            ++n_long;
+            return;
+        }
+        const DwordsOf text{h.text};
+        const int64_t s = ct_find_or_insert<CtDeviceAtomics>(text, a2, e2, th_hash_lane(text, a2, e2, h.seed), c.slots, DwordsOf{c.blob}, c.n_slots,
+                                                             (uint32_t)kCountProbeMax);
+        if (s == kCtDropped) {
+            ++n_dropped;
+            return;
+        }
+        ++n_counted;
+        const uint32_t tag = (uint32_t)s + 1u, at = (uint32_t)s & (uint32_t)(kCountAccEntries - 1);
+        const uint32_t was = atomicCAS(&acc[at], 0u, tag);
+        if (was == 0u || was == tag) atomicAdd(&acc[kCountAccEntries + at], 1u);
+        else (void)__hip_atomic_fetch_add(c.counts + s, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __device__ __forceinline__ void flush(int lane) {   // the tile is done: the accumulator (no-return adds) and the three tallies
+        for (int i = lane; i < kCountAccEntries; i += 64) {
+            const uint32_t tag = acc[i];
+            if (tag) (void)__hip_atomic_fetch_add(c.counts + (tag - 1u), (unsigned long long)acc[kCountAccEntries + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            n_counted += __shfl_xor(n_counted, d);
+            n_long += __shfl_xor(n_long, d);
+            n_dropped += __shfl_xor(n_dropped, d);
+        }
+        if (lane == 0) {
+            if (n_counted) (void)__hip_atomic_fetch_add(c.tally + 0, (unsigned long long)n_counted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (n_long) (void)__hip_atomic_fetch_add(c.tally + 1, (unsigned long long)n_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (n_dropped) (void)__hip_atomic_fetch_add(c.tally + 2, (unsigned long long)n_dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+};
+// Term keys (k_term_scatter): IdTokens' two paths with a term key (term_key.h) stored at the token's rank in the workspace instead of an
+// id in caller memory: the id with a found bit of its own, or -- with no table, n_features > 0 -- the hash bucket and the sign.
+// terms_kernels.hip sorts and reduces the keys inside every string.  It writes no records.
+struct TermTokens : TokenConsumer {
+    static constexpr bool kWaveTokens = true;
+    HashArgs h;
+    VocabArgs v;
+    TermArgs t;
+    __device__ __forceinline__ void short_token(int64_t rank, int64_t, int64_t, int64_t a2, int64_t e2, int64_t) {
+        if (e2 - a2 > kHashWaveBytes) return;
+        const DwordsOf text{h.text}, blob{v.blob};
+        const uint32_t hash = th_hash_lane(text, a2, e2, h.seed);
+        t.keys[rank] = t.n_features ? tk_hashed_key(hash, t.n_features, t.alternate_sign)
+                                    : tk_vocab_probe(ArrayOf<VtSlot>{v.slots}, v.n_slots, hash, (uint32_t)(e2 - a2),
+                                                     [text, a2, e2, blob](uint32_t off) { return vt_equal_lane(text, a2, e2, blob, off); });
+    }
+    __device__ __forceinline__ void long_token(int64_t rank, int64_t a, int64_t e, uint32_t hash, int lane, bool mine) {
+        const uint32_t hu = (uint32_t)__builtin_amdgcn_readfirstlane((int)hash);
+        const uint64_t key = t.n_features ? tk_hashed_key(hu, t.n_features, t.alternate_sign)
+                                          : tk_vocab_probe(WaveSlotsOf{v.slots}, v.n_slots, hu, (uint32_t)(e - a), WaveEqual{{h.text}, a, e, {v.blob}, lane});
+        if (mine) t.keys[rank] = key;
+    }
+};
+// Offsets (k_counts_scatter, kind 0): no tokens, the word-major walk.
+template <typename OUT>
+struct Offsets : TokenConsumer {
+    static constexpr bool kWordMajor = true;
+    OUT* out;
+};
 
-    // (a) where the string that owns a position begins: string-start bits of the tile in LDS (one atomicOr per string
-    //     that starts in it), per lane the last start before its word (prefix max), and for everything before the first
-    //     start the string that was open when the tile began.  No per-item loads: a lane that had to fetch row_off at
-    //     every string change stalled the whole wave on every step of its item loop.
+// (a) where the string that owns a position begins: string-start bits of the tile in LDS (one atomicOr per string
+//     that starts in it), per lane the last start before its word (prefix max), and for everything before the first
+//     start the string that was open when the tile began.  No per-item loads: a lane that had to fetch row_off at
+//     every string change stalled the whole wave on every step of its item loop.
+// bw: 64 words of the wave's LDS.  *Bw = the string starts of my word, *lo_in = the start of the string open at its bit 0.
+__device__ __forceinline__ void tile_string_starts(const TokenPlanes& p, int64_t w0, int lane, unsigned long long* bw, uint64_t* Bw, int64_t* lo_in) {
     const int64_t t0 = w0 << 6;
     // first string starting at or after t0: published by the tile kernel (one wave = one tile), else searched
-    int64_t idx0 = tile_first ? tile_first[w0 >> 6] : wave_lower_bound(row_off, n_str, t0, lane);
+    int64_t idx0 = p.tile_first ? p.tile_first[w0 >> 6] : wave_lower_bound(p.row_off, p.n_str, t0, lane);
     idx0 = idx0 < 0 ? 0 : idx0;
-    if (idx0 > n_str) idx0 = n_str;
-    const int64_t start_before = idx0 > 0 ? row_off[idx0 - 1] : 0;
-    unsigned long long* bw = reinterpret_cast<unsigned long long*>(smax);
+    if (idx0 > p.n_str) idx0 = p.n_str;
+    const int64_t start_before = idx0 > 0 ? p.row_off[idx0 - 1] : 0;
     bw[lane] = 0ull;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    for (int64_t i0 = idx0; i0 < n_str; i0 += 64) {
+    for (int64_t i0 = idx0; i0 < p.n_str; i0 += 64) {
         const int64_t sidx = i0 + lane;
-        const int64_t ro = sidx < n_str ? row_off[sidx] : INT64_MAX;
+        const int64_t ro = sidx < p.n_str ? p.row_off[sidx] : INT64_MAX;
         const int64_t rel = ro - t0;
         if (rel >= 0 && rel < 4096) atomicOr(&bw[rel >> 6], 1ull << (rel & 63));
         if (__shfl(ro, 63) >= t0 + 4096) break;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const uint64_t Bw = bw[lane];
-    const int carry = last_start_before(Bw, lane);
-    const int64_t lo_in = carry >= 0 ? t0 + carry : start_before;
+    *Bw = bw[lane];
+    const int carry = last_start_before(*Bw, lane);
+    *lo_in = carry >= 0 ? t0 + carry : start_before;
+}
 
-    // (b) + (c), window by window
-    const uint64_t xb = w < n_words ? bits[w] : 0ull;               // all boundaries of the word (item_mask is a subset)
-    const uint64_t nn = (KIND != 0 && w < n_words) ? (~space[w] & valid_mask(w, total)) : 0ull;
-    // the next word's masks (a token that crosses the word's end normally ends there): from the neighbour lane
-    uint64_t xb1 = 0, nn1 = 0;
-    if (KIND != 0) {
-        xb1 = __shfl_down(xb, 1);
-        nn1 = __shfl_down(nn, 1);
-        if (lane == 63) {
-            const bool has = w + 1 < n_words;
-            xb1 = has ? bits[w + 1] : 0ull;
-            nn1 = has ? (~space[w + 1] & valid_mask(w + 1, total)) : 0ull;
+// (b) + (c) of the offsets, window by window: offsets are one subtraction per item, and here the word-major loop through an LDS
+// window (win: kScatterCodes values) is the faster form.  rest = the items of my word w, k = the wave rank of its first, n_wave = the
+// tile's items, base_out = the tile's rank in out.
+// Every string start is itself a boundary (splits[0] = 1), so the walk over a word's items meets the string starts
+// in passing: `cur` = offset of the word's bit 0 relative to the string the walk is in -- base - lo_in on entry,
+// -b once the item at bit b is a string start.  32-bit halves: no 64-bit shifts, masks or clz in the loop (the
+// former form -- mask the string starts below the item, clz -- was 3x the instructions).
+template <typename OUT>
+__device__ __forceinline__ void offsets_walk(uint64_t rest, int k, int n_wave, int64_t w, uint64_t Bw, int64_t lo_in, OUT* win, OUT* out, int64_t base_out, int lane) {
+    constexpr int kCodes = kScatterCodes;
+    const int64_t base = w << 6;
+    uint32_t r0 = (uint32_t)rest, r1 = (uint32_t)(rest >> 32);
+    const uint32_t B0 = (uint32_t)Bw, B1 = (uint32_t)(Bw >> 32);
+    OUT cur = (OUT)(base - lo_in);
+    for (int win0 = 0; win0 < n_wave; win0 += kCodes) {
+        const int lim = win0 + kCodes;
+        while (r0 && k < lim) {
+            const int b = __builtin_ctz(r0);
+            r0 &= r0 - 1u;
+            if ((B0 >> b) & 1u) cur = (OUT)(-b);
+            win[k - win0] = (OUT)(cur + b);
+            ++k;
         }
-    }
-    // (b) token spans: every lane lists its items as (lane, bit) codes at their rank inside the wave ...
-    // (c) ... and the wave then takes the items in rank order, lane j the j-th: the owner word's masks arrive through
-    //     shuffles, so all 64 lanes are busy whatever the spread of items over the words is (a word-major loop runs as
-    //     long as the fullest word, typically 2x the mean), and the records go straight to consecutive addresses.
-    uint64_t rest = x;
-    int k = off;                                                    // wave rank of my next item
-    if (KIND == 0) {
-        // offsets are one subtraction per item: here the word-major loop through an LDS window is the faster form
-        // Every string start is itself a boundary (splits[0] = 1), so the walk over a word's items meets the string starts
-        // in passing: `cur` = offset of the word's bit 0 relative to the string the walk is in -- base - lo_in on entry,
-        // -b once the item at bit b is a string start.  32-bit halves: no 64-bit shifts, masks or clz in the loop (the
-        // former form -- mask the string starts below the item, clz -- was 3x the instructions).
-        const int64_t base = w << 6;
-        uint32_t r0 = (uint32_t)rest, r1 = (uint32_t)(rest >> 32);
-        const uint32_t B0 = (uint32_t)Bw, B1 = (uint32_t)(Bw >> 32);
-        OUT cur = (OUT)(base - lo_in);
-        for (int win0 = 0; win0 < n_wave; win0 += kCodes) {
-            const int lim = win0 + kCodes;
-            while (r0 && k < lim) {
-                const int b = __builtin_ctz(r0);
-                r0 &= r0 - 1u;
-                if ((B0 >> b) & 1u) cur = (OUT)(-b);
-                win[k - win0] = (OUT)(cur + b);
-                ++k;
-            }
-            while (!r0 && r1 && k < lim) {
-                const int b = __builtin_ctz(r1);
-                r1 &= r1 - 1u;
-                if ((B1 >> b) & 1u) cur = (OUT)(-(32 + b));
-                win[k - win0] = (OUT)(cur + 32 + b);
-                ++k;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            // stream the window out: single elements up to the first 16-byte boundary of the output, then 16-byte stores
-            const int n_val = min(kCodes, n_wave - win0);
-            OUT* dst = out + base_out + win0;
-            constexpr int kPer = 16 / (int)sizeof(OUT);                   // elements per 16-byte store
-            const int head = min(n_val, (int)(((16u - ((uintptr_t)dst & 15u)) & 15u) / sizeof(OUT)));
-            if (lane < head) __builtin_nontemporal_store(win[lane], dst + lane);
-            const int n_vec = (n_val - head) / kPer;
-            typedef OUT vec_t __attribute__((ext_vector_type(16 / sizeof(OUT))));
-            for (int i = lane; i < n_vec; i += 64) {
-                vec_t v;
+        while (!r0 && r1 && k < lim) {
+            const int b = __builtin_ctz(r1);
+            r1 &= r1 - 1u;
+            if ((B1 >> b) & 1u) cur = (OUT)(-(32 + b));
+            win[k - win0] = (OUT)(cur + 32 + b);
+            ++k;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        // stream the window out: single elements up to the first 16-byte boundary of the output, then 16-byte stores
+        const int n_val = min(kCodes, n_wave - win0);
+        OUT* dst = out + base_out + win0;
+        constexpr int kPer = 16 / (int)sizeof(OUT);                   // elements per 16-byte store
+        const int head = min(n_val, (int)(((16u - ((uintptr_t)dst & 15u)) & 15u) / sizeof(OUT)));
+        if (lane < head) __builtin_nontemporal_store(win[lane], dst + lane);
+        const int n_vec = (n_val - head) / kPer;
+        typedef OUT vec_t __attribute__((ext_vector_type(16 / sizeof(OUT))));
+        for (int i = lane; i < n_vec; i += 64) {
+            vec_t v;
 #pragma unroll
-                for (int e = 0; e < kPer; ++e) v[e] = win[head + kPer * i + e];
-                __builtin_nontemporal_store(v, reinterpret_cast<vec_t*>(dst + head) + i);
-            }
-            const int tail0 = head + kPer * n_vec;
-            if (lane < n_val - tail0) __builtin_nontemporal_store(win[tail0 + lane], dst + tail0 + lane);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            for (int e = 0; e < kPer; ++e) v[e] = win[head + kPer * i + e];
+            __builtin_nontemporal_store(v, reinterpret_cast<vec_t*>(dst + head) + i);
         }
-        return;
+        const int tail0 = head + kPer * n_vec;
+        if (lane < n_val - tail0) __builtin_nontemporal_store(win[tail0 + lane], dst + tail0 + lane);
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// (b) + (c) of every other form.  (b) token spans: every lane lists its items as (lane, bit) codes at their rank inside the wave ...
+// (c) ... and the wave then takes the items in rank order, lane j the j-th: the owner word's masks arrive through
+//     LDS rows, so all 64 lanes are busy whatever the spread of items over the words is (a word-major loop runs as
+//     long as the fullest word, typically 2x the mean), and the records go straight to consecutive addresses.
+// buf: the wave's LDS (codes, rows, the consumer's bytes).  rest = the items of my word w0 + lane, k = the wave rank of its first,
+// n_wave = the tile's items, base_out = the tile's rank; Bw / lo_in from tile_string_starts.
+template <class C>
+__device__ __forceinline__ void token_walk(const TokenPlanes& p, C& c, uint8_t* buf, uint64_t rest, int k, int n_wave, int64_t w0, int64_t base_out,
+                                           uint64_t Bw, int64_t lo_in, int lane) {
+    constexpr int kCodes = kScatterCodes;
+    const int64_t w = w0 + lane, n_words = p.n_words, total = p.total;
+    const uint64_t xb = w < n_words ? p.bits[w] : 0ull;              // all boundaries of the word (item_mask is a subset)
+    const uint64_t nn = w < n_words ? (~p.space[w] & valid_mask(w, total)) : 0ull;
+    // the next word's masks (a token that crosses the word's end normally ends there): from the neighbour lane
+    uint64_t xb1 = __shfl_down(xb, 1), nn1 = __shfl_down(nn, 1);
+    if (lane == 63) {
+        const bool has = w + 1 < n_words;
+        xb1 = has ? p.bits[w + 1] : 0ull;
+        nn1 = has ? (~p.space[w + 1] & valid_mask(w + 1, total)) : 0ull;
     }
     // the lanes' masks as 48-byte rows in LDS (behind the codes): in the token-major loop lane j reads the row of the
     // word that owns its item with three 16-byte reads (six 64-bit shuffles = twelve ds_bpermute before)
-    uint64_t* rows = reinterpret_cast<uint64_t*>(buf_s[wave] + kCodes * 2);            // codes take kCodes * 2 bytes
+    uint16_t* codes = reinterpret_cast<uint16_t*>(buf);
+    uint64_t* rows = reinterpret_cast<uint64_t*>(buf + kCodes * 2);            // codes take kCodes * 2 bytes
     {
         uint64_t* r = rows + 6 * lane;
         r[0] = xb; r[1] = nn; r[2] = xb1; r[3] = nn1; r[4] = Bw; r[5] = (uint64_t)lo_in;
     }
-    // (KIND 5) the wave's accumulator: tags (slot + 1, 0 = free) in the first half, counts in the second; my tallies
-    // (every other kind has neither: the names exist for the `if constexpr (KIND == 5)` blocks below and compile away)
-    [[maybe_unused]] uint32_t* const acc = KIND == 5 ? reinterpret_cast<uint32_t*>(buf_s[wave] + kAccAt) : nullptr;
-    [[maybe_unused]] unsigned n_counted = 0, n_long = 0, n_dropped = 0;
-    if constexpr (KIND == 5)
-        for (int i = lane; i < 2 * kCountAccEntries; i += 64) acc[i] = 0u;   // (visible behind the round's first wave barrier)
+    c.begin(buf + kScatterRowsEnd, lane);
     for (int win0 = 0; win0 < n_wave; win0 += kCodes) {
         while (rest && k < win0 + kCodes) {
             const int b = __builtin_ctzll(rest);
@@ -462,277 +595,171 @@ __device__ __forceinline__ void counts_scatter_block(
             const uint64_t* orow = rows + 6 * owner;
             const uint64_t o_xb = orow[0], o_nn = orow[1], o_xb1 = orow[2], o_nn1 = orow[3], o_Bw = orow[4];
             const int64_t o_lo_in = (int64_t)orow[5];
-            int64_t h_a = 0, h_e = 0;                                 // (KIND 3, 4) my token's absolute byte range
+            int64_t h_a = 0, h_e = 0;                                 // (kWaveTokens) my token's absolute byte range
             if (active) {
                 const int64_t obase = (w0 + owner) << 6;
                 const uint64_t bl = o_Bw & ((2ull << b) - 1ull);      // string starts at or before the item (b = 63: all)
                 const int64_t lo = bl ? obase + 63 - __builtin_clzll(bl) : o_lo_in;
-                {
-                    // token [p, e): e = next boundary; stripped extent [a2, e2).  The 64 positions from the item on, taken out
-                    // of the 128-bit pair (owner word, next word): one form whether the token ends in its own word or in the
-                    // next one (two divergent branches before, and some lane of 64 nearly always crosses a word)
-                    const uint64_t X = (o_xb >> b) | ((o_xb1 << 1) << (63 - b));     // boundaries at p, p+1, ..
-                    const uint64_t N = (o_nn >> b) | ((o_nn1 << 1) << (63 - b));     // non-SPACE chars at p, p+1, ..
-                    const uint64_t after = X & ~1ull;
-                    const int64_t p = obase + b;
-                    int64_t e, a2, e2;                              // (e: the raw end, KIND 2 only)
-                    if (after) {                                    // the token ends within 64 chars (kept => seg != 0)
-                        const uint64_t seg = N & (((after & (~after + 1ull)) - 1ull));
-                        e = p + __builtin_ctzll(after);
-                        a2 = p + __builtin_ctzll(seg);
-                        e2 = p + 64 - __builtin_clzll(seg);
-                    } else if (o_xb1 & ~((1ull << b) - 1ull)) {     // (rare) longer: ends at a boundary of the next word beyond p + 63
-                        const int eb = __builtin_ctzll(o_xb1 & ~((1ull << b) - 1ull));
-                        const uint64_t seg0 = o_nn & (~0ull << b);
-                        const uint64_t seg1 = o_nn1 & ((1ull << eb) - 1ull);
-                        e = obase + 64 + eb;
-                        a2 = seg0 ? obase + __builtin_ctzll(seg0) : obase + 64 + __builtin_ctzll(seg1);
-                        e2 = seg1 ? obase + 128 - __builtin_clzll(seg1) : obase + 64 - __builtin_clzll(seg0);
-                    } else {                                        // (rare) no boundary up to the end of the next word
-                        e = next_set_bit(bits, obase + 128, total);
-                        const uint64_t seg = o_nn & (~0ull << b);
-                        a2 = seg ? obase + __builtin_ctzll(seg) : (o_nn1 ? obase + 64 + __builtin_ctzll(o_nn1) : next_zero_bit(space, obase + 128, e));
-                        e2 = prev_zero_end(space, a2, e);
-                    }
-                    typedef OUT out2 __attribute__((ext_vector_type(2)));
-                    out2 v;
-                    v.x = (OUT)(a2 - lo);
-                    v.y = (OUT)(e2 - lo);
-                    if (KIND == 2) {                                // the record is 16 or 32 bytes: aligned 16-byte stores
-                        if (sizeof(OUT) == 4) {
-                            typedef OUT out4 __attribute__((ext_vector_type(4)));
-                            out4 r;
-                            r.x = (OUT)(p - lo);
-                            r.y = (OUT)(e - lo);
-                            r.z = v.x;
-                            r.w = v.y;
-                            __builtin_nontemporal_store(r, reinterpret_cast<out4*>(out) + base_out + win0 + j);
-                        } else {
-                            out2 r;
-                            r.x = (OUT)(p - lo);
-                            r.y = (OUT)(e - lo);
-                            out2* rec = reinterpret_cast<out2*>(out) + 2 * (base_out + win0 + j);
-                            __builtin_nontemporal_store(r, rec);
-                            __builtin_nontemporal_store(v, rec + 1);
-                        }
-                    } else if (!kHashes || out) {
-                        __builtin_nontemporal_store(v, reinterpret_cast<out2*>(out) + base_out + win0 + j);
-                    }
-                    if (kHashes) {
-                        h_a = a2;
-                        h_e = e2;
-                        if constexpr (KIND == 5) {
-                            if (e2 - a2 > ca.max_word_bytes) {
-                                ++n_long;
-                            } else {
-                                const uint32_t* text = ha.text;
-                                const uint32_t* blob = ca.blob;
-                                const uint32_t h = th_hash_lane([text](int64_t i) { return text[i]; }, a2, e2, ha.seed);
-                                const int64_t s = ct_find_or_insert<CtDeviceAtomics>([text](int64_t i) { return text[i]; }, a2, e2, h, ca.slots,
-                                                                                     [blob](uint64_t i) { return blob[i]; }, ca.n_slots,
-                                                                                     (uint32_t)kCountProbeMax);
-                                if (s == kCtDropped) {
-                                    ++n_dropped;
-                                } else {
-                                    ++n_counted;
-                                    const uint32_t tag = (uint32_t)s + 1u, at = (uint32_t)s & (uint32_t)(kCountAccEntries - 1);
-                                    const uint32_t was = atomicCAS(&acc[at], 0u, tag);
-                                    if (was == 0u || was == tag) atomicAdd(&acc[kCountAccEntries + at], 1u);
-                                    else (void)__hip_atomic_fetch_add(ca.counts + s, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                }
-                            }
-                        } else if (e2 - a2 <= kHashWaveBytes) {
-                            const uint32_t* text = ha.text;
-                            const uint32_t h = th_hash_lane([text](int64_t i) { return text[i]; }, a2, e2, ha.seed);
-                            if (KIND == 3) {
-                                __builtin_nontemporal_store(h, ha.hashes + base_out + win0 + j);
-                            } else if constexpr (KIND == 6) {
-                                uint64_t key;
-                                if (ta.n_features) {
-                                    key = tk_hashed_key(h, ta.n_features, ta.alternate_sign);
-                                } else {
-                                    const VtSlot* slots = va.slots;
-                                    const uint32_t* blob = va.blob;
-                                    key = tk_vocab_probe([slots](uint64_t i) { return slots[i]; }, va.n_slots, h, (uint32_t)(e2 - a2),
-                                                         [text, a2, e2, blob](uint32_t off) {
-                                                             return vt_equal_lane([text](int64_t i) { return text[i]; }, a2, e2,
-                                                                                  [blob](uint64_t i) { return blob[i]; }, off);
-                                                         });
-                                }
-                                ta.keys[base_out + win0 + j] = key;
-                            } else {
-                                const VtSlot* slots = va.slots;
-                                const uint32_t* blob = va.blob;
-                                const int32_t id = vt_lookup_lane([text](int64_t i) { return text[i]; }, a2, e2, h,
-                                                                  [slots](uint64_t i) { return slots[i]; },
-                                                                  [blob](uint64_t i) { return blob[i]; }, va.n_slots, va.unk);
-                                __builtin_nontemporal_store(id, va.ids + base_out + win0 + j);
-                            }
-                        }
-                    }
+                // token [p, e): e = next boundary; stripped extent [a2, e2).  The 64 positions from the item on, taken out
+                // of the 128-bit pair (owner word, next word): one form whether the token ends in its own word or in the
+                // next one (two divergent branches before, and some lane of 64 nearly always crosses a word)
+                const uint64_t X = (o_xb >> b) | ((o_xb1 << 1) << (63 - b));     // boundaries at p, p+1, ..
+                const uint64_t N = (o_nn >> b) | ((o_nn1 << 1) << (63 - b));     // non-SPACE chars at p, p+1, ..
+                const uint64_t after = X & ~1ull;
+                const int64_t pos = obase + b;
+                int64_t e, a2, e2;                              // (e: the raw end, 4-field records only)
+                if (after) {                                    // the token ends within 64 chars (kept => seg != 0)
+                    const uint64_t seg = N & (((after & (~after + 1ull)) - 1ull));
+                    e = pos + __builtin_ctzll(after);
+                    a2 = pos + __builtin_ctzll(seg);
+                    e2 = pos + 64 - __builtin_clzll(seg);
+                } else if (o_xb1 & ~((1ull << b) - 1ull)) {     // (rare) longer: ends at a boundary of the next word beyond p + 63
+                    const int eb = __builtin_ctzll(o_xb1 & ~((1ull << b) - 1ull));
+                    const uint64_t seg0 = o_nn & (~0ull << b);
+                    const uint64_t seg1 = o_nn1 & ((1ull << eb) - 1ull);
+                    e = obase + 64 + eb;
+                    a2 = seg0 ? obase + __builtin_ctzll(seg0) : obase + 64 + __builtin_ctzll(seg1);
+                    e2 = seg1 ? obase + 128 - __builtin_clzll(seg1) : obase + 64 - __builtin_clzll(seg0);
+                } else {                                        // (rare) no boundary up to the end of the next word
+                    e = next_set_bit(p.bits, obase + 128, total);
+                    const uint64_t seg = o_nn & (~0ull << b);
+                    a2 = seg ? obase + __builtin_ctzll(seg) : (o_nn1 ? obase + 64 + __builtin_ctzll(o_nn1) : next_zero_bit(p.space, obase + 128, e));
+                    e2 = prev_zero_end(p.space, a2, e);
                 }
+                c.short_token(base_out + win0 + j, pos, e, a2, e2, lo);
+                h_a = a2;
+                h_e = e2;
             }
-            if (kHashes && KIND != 5) {
+            if constexpr (C::kWaveTokens) {
                 // the long tokens of the round, one at a time by the whole wave (wave-uniform loop: `todo` is a ballot)
-                const uint32_t* text = ha.text;
-                auto ld = [text](int64_t i) { return text[i]; };
+                const DwordsOf ld{c.h.text};
                 for (uint64_t todo = __ballot(h_e - h_a > kHashWaveBytes); todo; todo &= todo - 1ull) {
                     const int src = __builtin_ctzll(todo);
                     const int64_t a = __shfl(h_a, src), e = __shfl(h_e, src);
                     const int64_t rounds = (((e - a) >> 2) + kThWaveBlocks - 1) / kThWaveBlocks;
-                    uint32_t h = ha.seed;
+                    uint32_t h = c.h.seed;
                     uint32_t mk = th_wave_block(ld, a, e, 0, lane);
                     for (int64_t r = 0; r < rounds; ++r) {
                         const uint32_t cur = mk;
                         if (r + 1 < rounds) mk = th_wave_block(ld, a, e, r + 1, lane);   // (the next round's loads fly during the fold)
                         h = th_wave_fold(h, [cur](int l) { return (uint32_t)__builtin_amdgcn_readlane((int)cur, l); }, th_wave_count(a, e, r));
                     }
-                    h = th_wave_tail(ld, a, e, h);
-                    if (KIND == 3) {
-                        if (lane == src) __builtin_nontemporal_store(h, ha.hashes + base_out + win0 + j);
-                    } else if constexpr (KIND == 6) {
-                        const uint32_t hu = (uint32_t)__builtin_amdgcn_readfirstlane((int)h);
-                        uint64_t key;
-                        if (ta.n_features) {
-                            key = tk_hashed_key(hu, ta.n_features, ta.alternate_sign);
-                        } else {   // the wave probes in step, as KIND 4 does
-                            const VtSlot* slots = va.slots;
-                            const uint32_t* blob = va.blob;
-                            key = tk_vocab_probe(
-                                [slots](uint64_t i) {
-                                    const VtSlot v = slots[i];
-                                    return VtSlot{(uint32_t)__builtin_amdgcn_readfirstlane((int)v.hash), __builtin_amdgcn_readfirstlane(v.id),
-                                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)v.off),
-                                                  (uint32_t)__builtin_amdgcn_readfirstlane((int)v.len)};
-                                },
-                                va.n_slots, hu, (uint32_t)(e - a), [ld, a, e, blob, lane](uint32_t off) {
-                                    const int64_t rounds_c = vt_wave_rounds(a, e);
-                                    for (int64_t r = 0; r < rounds_c; ++r)
-                                        if (__ballot(vt_wave_differs(ld, a, e, [blob](uint64_t i) { return blob[i]; }, off, r, lane))) return false;
-                                    return true;
-                                });
-                        }
-                        if (lane == src) ta.keys[base_out + win0 + j] = key;
-                    } else {
-                        // every lane holds the same h: the wave walks the slots in step and compares a candidate together
-                        const VtSlot* slots = va.slots;
-                        const uint32_t* blob = va.blob;
-                        const uint32_t hu = (uint32_t)__builtin_amdgcn_readfirstlane((int)h);
-                        const int32_t id = vt_probe(
-                            [slots](uint64_t i) {
-                                const VtSlot v = slots[i];
-                                return VtSlot{(uint32_t)__builtin_amdgcn_readfirstlane((int)v.hash), __builtin_amdgcn_readfirstlane(v.id),
-                                              (uint32_t)__builtin_amdgcn_readfirstlane((int)v.off),
-                                              (uint32_t)__builtin_amdgcn_readfirstlane((int)v.len)};
-                            },
-                            va.n_slots, hu, (uint32_t)(e - a),
-                            [ld, a, e, blob, lane](uint32_t off) {
-                                const int64_t rounds_c = vt_wave_rounds(a, e);
-                                for (int64_t r = 0; r < rounds_c; ++r)
-                                    if (__ballot(vt_wave_differs(ld, a, e, [blob](uint64_t i) { return blob[i]; }, off, r, lane))) return false;
-                                return true;
-                            },
-                            va.unk);
-                        if (lane == src) __builtin_nontemporal_store(id, va.ids + base_out + win0 + j);
-                    }
+                    c.long_token(base_out + win0 + j, a, e, th_wave_tail(ld, a, e, h), lane, lane == src);
                 }
             }
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-    if constexpr (KIND == 5) {   // the tile is done: flush the accumulator (no-return adds) and the three tallies
-        for (int i = lane; i < kCountAccEntries; i += 64) {
-            const uint32_t tag = acc[i];
-            if (tag) (void)__hip_atomic_fetch_add(ca.counts + (tag - 1u), (unsigned long long)acc[kCountAccEntries + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            n_counted += __shfl_xor(n_counted, d);
-            n_long += __shfl_xor(n_long, d);
-            n_dropped += __shfl_xor(n_dropped, d);
-        }
-        if (lane == 0) {
-            if (n_counted) (void)__hip_atomic_fetch_add(ca.tally + 0, (unsigned long long)n_counted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (n_long) (void)__hip_atomic_fetch_add(ca.tally + 1, (unsigned long long)n_long, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (n_dropped) (void)__hip_atomic_fetch_add(ca.tally + 2, (unsigned long long)n_dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+    c.flush(lane);
+}
+
+// The body of every scatter kernel.  c: the kernel's consumer (Offsets: the word-major form); counts (or NULL): the per-string item
+// counts; cap: the items the caller's buffers hold; vb: the (virtual) workgroup index.
+template <typename OUT, class C>
+__device__ __forceinline__ void scatter_block(const TokenPlanes& p, C& c, OUT* counts, int64_t cap, unsigned n_scatter_blocks, int* err, unsigned vb) {
+    if (vb >= n_scatter_blocks) {   // role 2: one thread per string
+        if (counts)
+            string_counts_role<OUT>((int64_t)(vb - n_scatter_blocks) * (kScatterWaves * 64) + threadIdx.x, p.item_mask, p.tile_rank, p.word_pref,
+                                    p.row_off, p.n_str, p.total, *p.n_items, counts, err);
+        return;
+    }
+    // role 1: one wave per tile.  The caller's buffer holds `cap` items; when the batch has more, nothing is written
+    // (the host reports the needed size) -- the launch does not have to wait for the host to learn the total.
+    if (*p.n_items > cap) return;
+    // Offsets: window of values (OUT); token-major: the item codes + the mask rows.  Sized for
+    // what the form needs (it was 8 KB per wave for every form: 4 workgroups per CU).  Measured on C2, same box: int32 offsets
+    // 0.174 -> 0.165 ms and int32 spans 0.233 -> 0.222 at 7 - 8 workgroups per CU, but int64 spans 0.247 -> 0.256 (twice
+    // the store stream per token): that form keeps the footprint that holds it at 4.
+    constexpr int kSpan64Buf = 6656;   // int64 spans: 5 workgroups per CU (4: C3 +2.5 %; 7: C2 +4 %)
+    constexpr int kBufBytes = C::kWordMajor ? kScatterCodes * (int)sizeof(OUT)
+                                            : (sizeof(OUT) == 8 ? kSpan64Buf : kScatterRowsEnd) + C::kLdsBytes;   // (a consumer's own bytes lie behind the rows)
+    __shared__ __attribute__((aligned(16))) uint8_t buf_s[kScatterWaves][kBufBytes];
+    __shared__ long long smax_s[kScatterWaves][65];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t w0 = ((int64_t)vb * kScatterWaves + wave) * 64;
+    if (w0 >= p.n_words) return;                                    // whole wave (no block-wide barrier is used below)
+    const int64_t w = w0 + lane;
+    const int n_wave = (int)p.tile_cnt[w0 >> 6];
+    if (n_wave == 0) return;
+    const uint64_t x = w < p.n_words ? p.item_mask[w] : 0ull;
+    const int off = w < p.n_words ? (int)p.word_pref[w] : 0;        // rank of my first item inside the wave
+    const int64_t base_out = p.tile_rank[w0 >> 6];
+    uint8_t* buf = buf_s[wave];
+    uint64_t Bw;
+    int64_t lo_in;
+    tile_string_starts(p, w0, lane, reinterpret_cast<unsigned long long*>(smax_s[wave]), &Bw, &lo_in);
+    if constexpr (C::kWordMajor) {
+        offsets_walk<OUT>(x, off, n_wave, w, Bw, lo_in, reinterpret_cast<OUT*>(buf), c.out, base_out, lane);
+    } else {
+        static_assert(C::kLdsBytes == 0 || sizeof(OUT) == 4, "a consumer with LDS of its own is instantiated for int32 only");
+        token_walk(p, c, buf, x, off, n_wave, w0, base_out, Bw, lo_in, lane);
     }
 }
 
 template <int KIND, typename OUT>
-__global__ __launch_bounds__(scatter_waves(KIND) * 64) void k_counts_scatter(
+__global__ __launch_bounds__(kScatterWaves * 64) void k_counts_scatter(
     const uint64_t* __restrict__ bits, const uint64_t* __restrict__ space, const uint64_t* __restrict__ item_mask,
     const int64_t* __restrict__ tile_rank, const int64_t* __restrict__ tile_cnt, const uint16_t* __restrict__ word_pref,
     int64_t n_words, int64_t total, const int64_t* __restrict__ row_off, int64_t n_str,
     const int64_t* __restrict__ tile_first, OUT* __restrict__ out, const int64_t* __restrict__ n_items_dev, int64_t cap,
     OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, DoneSignal done, DeviceTotal dt) {
+    TokenPlanes p{bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str, tile_first, n_items_dev};
     if (dt.total) {   // (uniform) the size from device memory; the records are not written for a batch reported as malformed
-        total = device_total(dt.total, total);
-        n_words = (total + 63) >> 6;
+        p.total = device_total(dt.total, total);
+        p.n_words = (p.total + 63) >> 6;
     }
-    if (!(dt.gate && *dt.gate != 0 && blockIdx.x < n_scatter_blocks))   // (the counts role still runs: counts may be written)
-        counts_scatter_block<KIND, OUT>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str,
-                                        tile_first, out, n_items_dev, cap, counts, n_scatter_blocks, err, blockIdx.x);
+    if (!(dt.gate && *dt.gate != 0 && blockIdx.x < n_scatter_blocks)) {   // (the counts role still runs: counts may be written)
+        std::conditional_t<KIND == 0, Offsets<OUT>, SpanRecords<OUT, KIND == 2 ? 4 : 2>> c{{}, out};
+        scatter_block<OUT>(p, c, counts, cap, n_scatter_blocks, err, blockIdx.x);
+    }
     signal_block_done(done);   // (pinned outputs of a small host batch: the host polls the completion word)
 }
 
-// Token hashes: KIND 3 of the body above in a kernel of its own (the three kernels above keep their arguments).
+// Token hashes and token ids in kernels of their own (k_counts_scatter keeps its arguments and its code).
 template <typename OUT>
-__global__ __launch_bounds__(scatter_waves(3) * 64) void k_hash_scatter(
+__global__ __launch_bounds__(kScatterWaves * 64) void k_hash_scatter(
     const uint64_t* __restrict__ bits, const uint64_t* __restrict__ space, const uint64_t* __restrict__ item_mask,
     const int64_t* __restrict__ tile_rank, const int64_t* __restrict__ tile_cnt, const uint16_t* __restrict__ word_pref,
     int64_t n_words, int64_t total, const int64_t* __restrict__ row_off, int64_t n_str,
     const int64_t* __restrict__ tile_first, OUT* __restrict__ out, const int64_t* __restrict__ n_items_dev, int64_t cap,
     OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, HashArgs ha) {
-    counts_scatter_block<3, OUT>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str, tile_first, out,
-                                 n_items_dev, cap, counts, n_scatter_blocks, err, blockIdx.x, ha);
+    const TokenPlanes p{bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str, tile_first, n_items_dev};
+    HashTokens<OUT> c{{}, ha, out};
+    scatter_block<OUT>(p, c, counts, cap, n_scatter_blocks, err, blockIdx.x);
 }
-
-// Token ids: KIND 4 of the body above in a kernel of its own (the kernels above keep their arguments and their code).
 template <typename OUT>
-__global__ __launch_bounds__(scatter_waves(4) * 64) void k_vocab_scatter(
+__global__ __launch_bounds__(kScatterWaves * 64) void k_vocab_scatter(
     const uint64_t* __restrict__ bits, const uint64_t* __restrict__ space, const uint64_t* __restrict__ item_mask,
     const int64_t* __restrict__ tile_rank, const int64_t* __restrict__ tile_cnt, const uint16_t* __restrict__ word_pref,
     int64_t n_words, int64_t total, const int64_t* __restrict__ row_off, int64_t n_str,
     const int64_t* __restrict__ tile_first, OUT* __restrict__ out, const int64_t* __restrict__ n_items_dev, int64_t cap,
     OUT* __restrict__ counts, unsigned n_scatter_blocks, int* __restrict__ err, HashArgs ha, VocabArgs va) {
-    counts_scatter_block<4, OUT>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str, tile_first, out,
-                                 n_items_dev, cap, counts, n_scatter_blocks, err, blockIdx.x, ha, va);
+    const TokenPlanes p{bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str, tile_first, n_items_dev};
+    IdTokens<OUT> c{{}, ha, va, out};
+    scatter_block<OUT>(p, c, counts, cap, n_scatter_blocks, err, blockIdx.x);
 }
 
-// Token counts: KIND 5 of the body above in a kernel of its own (the kernels above keep their arguments and their code).  No
-// records, no per-string counts: `out` only switches the tile role on, and nothing is gated by a capacity.
+// Token counts and term keys: the planes and the consumer's state as one argument.  Neither writes records nor is gated by a
+// capacity.  Token counts have no per-string counts; those of the term keys are int64 (they feed the row scan of the term-count calls).
 struct CountScatterArgs {
-    const uint64_t* bits; const uint64_t* space; const uint64_t* item_mask;
-    const int64_t* tile_rank; const int64_t* tile_cnt; const uint16_t* word_pref;
-    int64_t n_words, total;
-    const int64_t* row_off; int64_t n_str;
-    const int64_t* tile_first; const int64_t* n_items_dev;
+    TokenPlanes p;
     unsigned n_scatter_blocks; int* err;
     HashArgs ha; CountArgs ca;
 };
-__global__ __launch_bounds__(scatter_waves(5) * 64) void k_count_scatter(CountScatterArgs a) {
-    counts_scatter_block<5, int32_t>(a.bits, a.space, a.item_mask, a.tile_rank, a.tile_cnt, a.word_pref, a.n_words, a.total, a.row_off, a.n_str,
-                                     a.tile_first, nullptr, a.n_items_dev, INT64_MAX, nullptr, a.n_scatter_blocks, a.err, blockIdx.x, a.ha,
-                                     VocabArgs{}, a.ca);
+__global__ __launch_bounds__(kScatterWaves * 64) void k_count_scatter(CountScatterArgs a) {
+    CountTokens c{{}, a.ha, a.ca};
+    scatter_block<int32_t>(a.p, c, (int32_t*)nullptr, INT64_MAX, a.n_scatter_blocks, a.err, blockIdx.x);
 }
-
-// Term keys: KIND 6 of the body above in a kernel of its own (the kernels above keep their arguments and their code).  No records;
-// the per-string token counts are int64 (they feed the row scan of the term-count calls) and nothing is gated by a capacity.
 struct TermScatterArgs {
-    const uint64_t* bits; const uint64_t* space; const uint64_t* item_mask;
-    const int64_t* tile_rank; const int64_t* tile_cnt; const uint16_t* word_pref;
-    int64_t n_words, total;
-    const int64_t* row_off; int64_t n_str;
-    const int64_t* tile_first; const int64_t* n_items_dev; int64_t* counts;
+    TokenPlanes p;
+    int64_t* counts;
     unsigned n_scatter_blocks; int* err;
     HashArgs ha; VocabArgs va; TermArgs ta;
 };
-__global__ __launch_bounds__(scatter_waves(6) * 64) void k_term_scatter(TermScatterArgs a) {
-    counts_scatter_block<6, int64_t>(a.bits, a.space, a.item_mask, a.tile_rank, a.tile_cnt, a.word_pref, a.n_words, a.total, a.row_off, a.n_str,
-                                     a.tile_first, nullptr, a.n_items_dev, INT64_MAX, a.counts, a.n_scatter_blocks, a.err, blockIdx.x, a.ha,
-                                     a.va, CountArgs{}, a.ta);
+__global__ __launch_bounds__(kScatterWaves * 64) void k_term_scatter(TermScatterArgs a) {
+    TermTokens c{{}, a.ha, a.va, a.ta};
+    scatter_block<int64_t>(a.p, c, a.counts, INT64_MAX, a.n_scatter_blocks, a.err, blockIdx.x);
 }
 
 // The commit behind k_count_scatter: two launches over the slots, one thread per slot, that make the table independent of the
@@ -1137,16 +1164,6 @@ hipError_t launch_lead_codes(const uint8_t* u8, int64_t total_bytes, const uint6
     return hipGetLastError();
 }
 
-// exclusive scan of per-tile counts that some other kernel left (the byte-space tile kernel: leads per tile): k_scan_chained alone
-hipError_t launch_tile_scan(const int64_t* tile_cnt, int64_t n_tiles, int64_t* tile_rank, unsigned long long* chain, unsigned* ticket,
-                            unsigned epoch, int64_t* total_dev, int64_t* total_host, int* err, hipStream_t st) {
-    if (n_tiles <= 0) return hipSuccess;
-    const unsigned n_blocks = (unsigned)((n_tiles + kChainChunk - 1) / kChainChunk);
-    hipLaunchKernelGGL(k_scan_chained, dim3(n_blocks), dim3(kChainBlock), 0, st, tile_cnt, n_tiles, tile_rank, chain, ticket, epoch,
-                       n_blocks, total_dev, total_host, err, (const int64_t*)nullptr);
-    return hipGetLastError();
-}
-
 // The zero padding k_features_tiles reads behind the last rule code (one tile + 256 B), for a batch whose code-point total only
 // the device knows: written at codes[*total_dev ..) by this launch instead of a memset the host would have to place.
 __global__ __launch_bounds__(256) void k_pad_codes(uint8_t* __restrict__ codes, const int64_t* __restrict__ total_dev, int64_t bound,
@@ -1369,131 +1386,117 @@ hipError_t launch_join_scatter(const uint8_t* u8, int64_t total, const uint64_t*
 int64_t scan_chunk() { return kChainChunk; }
 int64_t count_blocks(int64_t n_words) { return n_words > 0 ? ((n_words + 63) / 64 + kChainChunk - 1) / kChainChunk : 0; }
 
-hipError_t launch_word_counts_scan(bool spans, const uint64_t* bits, const uint64_t* space, int64_t n_words, int64_t total,
-                                   uint64_t* kept, int64_t* tile_cnt, uint16_t* word_pref, int64_t* tile_rank,
-                                   unsigned long long* chain, unsigned* ticket, unsigned epoch, int64_t* total_dev,
-                                   int64_t* total_host, int* err, hipStream_t st, DeviceTotal dt) {
-    if (n_words <= 0) return hipSuccess;
-    const int64_t n_tiles = (n_words + 63) / 64;
+// exclusive scan of per-tile counts that some other kernel left (the byte-space tile kernel: leads per tile): k_scan_chained alone
+hipError_t launch_tile_scan(const int64_t* tile_cnt, int64_t n_tiles, int64_t* tile_rank, const ChainState& c, int64_t* total_dev,
+                            int64_t* total_host, int* err, hipStream_t st) {
+    if (n_tiles <= 0) return hipSuccess;
+    const unsigned n_blocks = (unsigned)((n_tiles + kChainChunk - 1) / kChainChunk);
+    hipLaunchKernelGGL(k_scan_chained, dim3(n_blocks), dim3(kChainBlock), 0, st, tile_cnt, n_tiles, tile_rank, c.chain, c.ticket, c.epoch,
+                       n_blocks, total_dev, total_host, err, (const int64_t*)nullptr);
+    return hipGetLastError();
+}
+
+// the planes' one writer: p's item mask (spans: the kept mask), tile counts, word prefixes, tile ranks and *p.n_items are its outputs
+hipError_t launch_word_counts_scan(bool spans, const TokenPlanes& p, const ChainState& c, int64_t* total_host, int* err, hipStream_t st,
+                                   DeviceTotal dt) {
+    if (p.n_words <= 0) return hipSuccess;
+    const int64_t n_tiles = (p.n_words + 63) / 64;
     const dim3 grid((unsigned)((n_tiles + 3) / 4)), block(256);
-    if (spans) hipLaunchKernelGGL((k_word_counts<true>), grid, block, 0, st, bits, space, n_words, total, kept, tile_cnt, word_pref, dt.total);
-    else hipLaunchKernelGGL((k_word_counts<false>), grid, block, 0, st, bits, space, n_words, total, kept, tile_cnt, word_pref, dt.total);
-    const unsigned n_blocks = (unsigned)count_blocks(n_words);
-    hipLaunchKernelGGL(k_scan_chained, dim3(n_blocks), dim3(kChainBlock), 0, st, tile_cnt, n_tiles, tile_rank, chain, ticket, epoch,
-                       n_blocks, total_dev, total_host, err, dt.total);
+    uint64_t* kept = spans ? const_cast<uint64_t*>(p.item_mask) : nullptr;
+    int64_t* tile_cnt = const_cast<int64_t*>(p.tile_cnt);
+    uint16_t* word_pref = const_cast<uint16_t*>(p.word_pref);
+    if (spans) hipLaunchKernelGGL((k_word_counts<true>), grid, block, 0, st, p.bits, p.space, p.n_words, p.total, kept, tile_cnt, word_pref, dt.total);
+    else hipLaunchKernelGGL((k_word_counts<false>), grid, block, 0, st, p.bits, p.space, p.n_words, p.total, kept, tile_cnt, word_pref, dt.total);
+    const unsigned n_blocks = (unsigned)count_blocks(p.n_words);
+    hipLaunchKernelGGL(k_scan_chained, dim3(n_blocks), dim3(kChainBlock), 0, st, p.tile_cnt, n_tiles, const_cast<int64_t*>(p.tile_rank), c.chain,
+                       c.ticket, c.epoch, n_blocks, const_cast<int64_t*>(p.n_items), total_host, err, dt.total);
     return hipGetLastError();
 }
 
-hipError_t launch_string_counts(bool out32, const uint64_t* mask, const int64_t* tile_rank, const uint16_t* word_pref,
-                                const int64_t* row_off, int64_t n_str, int64_t total, const int64_t* n_items, void* counts, int* err,
-                                hipStream_t st, DeviceTotal dt) {
-    if (n_str <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((n_str + 255) / 256)), block(256);
+hipError_t launch_string_counts(bool out32, const TokenPlanes& p, void* counts, int* err, hipStream_t st, DeviceTotal dt) {
+    if (p.n_str <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((p.n_str + 255) / 256)), block(256);
     if (out32)
-        hipLaunchKernelGGL((k_string_counts<int32_t>), grid, block, 0, st, mask, tile_rank, word_pref, row_off, n_str, total, n_items,
-                           (int32_t*)counts, err, dt.total);
+        hipLaunchKernelGGL((k_string_counts<int32_t>), grid, block, 0, st, p.item_mask, p.tile_rank, p.word_pref, p.row_off, p.n_str, p.total,
+                           p.n_items, (int32_t*)counts, err, dt.total);
     else
-        hipLaunchKernelGGL((k_string_counts<int64_t>), grid, block, 0, st, mask, tile_rank, word_pref, row_off, n_str, total, n_items,
-                           (int64_t*)counts, err, dt.total);
+        hipLaunchKernelGGL((k_string_counts<int64_t>), grid, block, 0, st, p.item_mask, p.tile_rank, p.word_pref, p.row_off, p.n_str, p.total,
+                           p.n_items, (int64_t*)counts, err, dt.total);
     return hipGetLastError();
 }
 
-template <int KIND, typename OUT>
-static hipError_t launch_counts_scatter_t(const uint64_t* bits, const uint64_t* space, const uint64_t* item_mask,
-                                          const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref,
-                                          int64_t n_words, int64_t total, const int64_t* row_off, int64_t n_str,
-                                          const int64_t* tile_first, void* out, const int64_t* n_items_dev, int64_t cap,
-                                          void* counts, int* err, hipStream_t st, DoneSignal done, DeviceTotal dt) {
-    const int64_t per_block = (int64_t)scatter_waves(KIND) * 64;
-    const unsigned nb_scatter = out ? (unsigned)((n_words + per_block - 1) / per_block) : 0u;
-    const unsigned nb_counts = counts ? (unsigned)((n_str + 255) / 256) : 0u;
+// The grid of every scatter launch, two block roles: one wave per tile only if there is a payload to write, then one thread per string
+// only if counts are asked for; nothing is launched for neither.  launch(OUT{}, grid, block, nb_scatter) enqueues the kernel for
+// records and counts of type OUT.
+template <class Launch>
+static hipError_t launch_scatter(bool out32, const TokenPlanes& p, bool payload, bool counts, Launch launch) {
+    if (p.n_words <= 0) return hipSuccess;
+    constexpr int kThreads = kScatterWaves * 64;
+    const unsigned nb_scatter = payload ? (unsigned)((p.n_words + kThreads - 1) / kThreads) : 0u;
+    const unsigned nb_counts = counts ? (unsigned)((p.n_str + kThreads - 1) / kThreads) : 0u;
     if (nb_scatter + nb_counts == 0) return hipSuccess;
-    hipLaunchKernelGGL((k_counts_scatter<KIND, OUT>), dim3(nb_scatter + nb_counts), dim3(scatter_waves(KIND) * 64), 0, st, bits, space,
-                       item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, n_str, tile_first, (OUT*)out, n_items_dev,
-                       cap, (OUT*)counts, nb_scatter, err, done, dt);
+    const dim3 grid(nb_scatter + nb_counts), block(kThreads);
+    if (out32) launch(int32_t{}, grid, block, nb_scatter);
+    else launch(int64_t{}, grid, block, nb_scatter);
     return hipGetLastError();
+}
+// the positional arguments that k_counts_scatter, k_hash_scatter and k_vocab_scatter share, then each kernel's own
+template <class Kernel, typename OUT, class... Own>
+static void launch_positional(Kernel kernel, dim3 grid, dim3 block, hipStream_t st, const TokenPlanes& p, OUT* out, int64_t cap, OUT* counts,
+                              unsigned nb_scatter, int* err, Own... own) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, p.bits, p.space, p.item_mask, p.tile_rank, p.tile_cnt, p.word_pref, p.n_words, p.total, p.row_off,
+                       p.n_str, p.tile_first, out, p.n_items, cap, counts, nb_scatter, err, own...);
 }
 
 // counts (may be NULL: already written) and / or items (out may be NULL: counts only) in one launch
-hipError_t launch_counts_scatter(int kind, bool out32, const uint64_t* bits, const uint64_t* space, const uint64_t* item_mask,
-                                 const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words,
-                                 int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,
-                                 const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st, DoneSignal done,
-                                 DeviceTotal dt) {
-    if (n_words <= 0) return hipSuccess;
-#define LATOK_CS(K, T) launch_counts_scatter_t<K, T>(bits, space, item_mask, tile_rank, tile_cnt, word_pref, n_words, total, row_off, \
-                                                     n_str, tile_first, out, n_items_dev, cap, counts, err, st, done, dt)
-    if (kind == 0) return out32 ? LATOK_CS(0, int32_t) : LATOK_CS(0, int64_t);
-    if (kind == 2) return out32 ? LATOK_CS(2, int32_t) : LATOK_CS(2, int64_t);
-    return out32 ? LATOK_CS(1, int32_t) : LATOK_CS(1, int64_t);
-#undef LATOK_CS
+hipError_t launch_counts_scatter(int kind, bool out32, const TokenPlanes& p, void* out, int64_t cap, void* counts, int* err, hipStream_t st,
+                                 DoneSignal done, DeviceTotal dt) {
+    return launch_scatter(out32, p, out, counts, [&](auto t, dim3 grid, dim3 block, unsigned nb) {
+        using OUT = decltype(t);
+        const auto kernel = kind == 0 ? k_counts_scatter<0, OUT> : kind == 2 ? k_counts_scatter<2, OUT> : k_counts_scatter<1, OUT>;
+        launch_positional(kernel, grid, block, st, p, (OUT*)out, cap, (OUT*)counts, nb, err, done, dt);
+    });
 }
 
 // token hashes (+ the span records if out != NULL, + the counts if counts != NULL); hashes == NULL: counts only (a size query)
-hipError_t launch_hash_scatter(bool out32, const uint8_t* u8, uint32_t seed, const uint64_t* bits, const uint64_t* space,
-                               const uint64_t* kept, const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref,
-                               int64_t n_words, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,
-                               uint32_t* hashes, const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st) {
-    if (n_words <= 0) return hipSuccess;
-    const unsigned nb_scatter = hashes ? (unsigned)((n_words + 255) / 256) : 0u;
-    const unsigned nb_counts = counts ? (unsigned)((n_str + 255) / 256) : 0u;
-    if (nb_scatter + nb_counts == 0) return hipSuccess;
+hipError_t launch_hash_scatter(bool out32, const TokenPlanes& p, const uint8_t* u8, uint32_t seed, void* out, uint32_t* hashes, int64_t cap,
+                               void* counts, int* err, hipStream_t st) {
     HashArgs ha;
     ha.text = reinterpret_cast<const uint32_t*>(u8);
     ha.hashes = hashes;
     ha.seed = seed;
-    const dim3 grid(nb_scatter + nb_counts), block(scatter_waves(3) * 64);
-    if (out32)
-        hipLaunchKernelGGL((k_hash_scatter<int32_t>), grid, block, 0, st, bits, space, kept, tile_rank, tile_cnt, word_pref, n_words, total,
-                           row_off, n_str, tile_first, (int32_t*)out, n_items_dev, cap, (int32_t*)counts, nb_scatter, err, ha);
-    else
-        hipLaunchKernelGGL((k_hash_scatter<int64_t>), grid, block, 0, st, bits, space, kept, tile_rank, tile_cnt, word_pref, n_words, total,
-                           row_off, n_str, tile_first, (int64_t*)out, n_items_dev, cap, (int64_t*)counts, nb_scatter, err, ha);
-    return hipGetLastError();
+    return launch_scatter(out32, p, hashes, counts, [&](auto t, dim3 grid, dim3 block, unsigned nb) {
+        using OUT = decltype(t);
+        launch_positional(k_hash_scatter<OUT>, grid, block, st, p, (OUT*)out, cap, (OUT*)counts, nb, err, ha);
+    });
 }
 
-// token ids (+ the span records if out != NULL, + the counts if counts != NULL); ids == NULL: counts only (a size query)
-hipError_t launch_vocab_scatter(bool out32, const uint8_t* u8, const VocabTable& vt, int32_t unk_id, const uint64_t* bits,
-                                const uint64_t* space, const uint64_t* kept, const int64_t* tile_rank, const int64_t* tile_cnt,
-                                const uint16_t* word_pref, int64_t n_words, int64_t total, const int64_t* row_off, int64_t n_str,
-                                const int64_t* tile_first, void* out, int32_t* ids, const int64_t* n_items_dev, int64_t cap, void* counts,
-                                int* err, hipStream_t st) {
-    if (n_words <= 0) return hipSuccess;
-    const unsigned nb_scatter = ids ? (unsigned)((n_words + 255) / 256) : 0u;
-    const unsigned nb_counts = counts ? (unsigned)((n_str + 255) / 256) : 0u;
-    if (nb_scatter + nb_counts == 0) return hipSuccess;
-    HashArgs ha;
-    ha.text = reinterpret_cast<const uint32_t*>(u8);
-    ha.seed = vt.seed;
+static VocabArgs vocab_args(const VocabTable& vt, int32_t* ids, int32_t unk_id) {
     VocabArgs va;
     va.slots = reinterpret_cast<const VtSlot*>(vt.slots);
     va.blob = vt.blob;
     va.n_slots = vt.n_slots;
     va.ids = ids;
     va.unk = unk_id;
-    const dim3 grid(nb_scatter + nb_counts), block(scatter_waves(4) * 64);
-    if (out32)
-        hipLaunchKernelGGL((k_vocab_scatter<int32_t>), grid, block, 0, st, bits, space, kept, tile_rank, tile_cnt, word_pref, n_words, total,
-                           row_off, n_str, tile_first, (int32_t*)out, n_items_dev, cap, (int32_t*)counts, nb_scatter, err, ha, va);
-    else
-        hipLaunchKernelGGL((k_vocab_scatter<int64_t>), grid, block, 0, st, bits, space, kept, tile_rank, tile_cnt, word_pref, n_words, total,
-                           row_off, n_str, tile_first, (int64_t*)out, n_items_dev, cap, (int64_t*)counts, nb_scatter, err, ha, va);
-    return hipGetLastError();
+    return va;
+}
+// token ids (+ the span records if out != NULL, + the counts if counts != NULL); ids == NULL: counts only (a size query)
+hipError_t launch_vocab_scatter(bool out32, const TokenPlanes& p, const uint8_t* u8, const VocabTable& vt, int32_t unk_id, void* out,
+                                int32_t* ids, int64_t cap, void* counts, int* err, hipStream_t st) {
+    HashArgs ha;
+    ha.text = reinterpret_cast<const uint32_t*>(u8);
+    ha.seed = vt.seed;
+    const VocabArgs va = vocab_args(vt, ids, unk_id);
+    return launch_scatter(out32, p, ids, counts, [&](auto t, dim3 grid, dim3 block, unsigned nb) {
+        using OUT = decltype(t);
+        launch_positional(k_vocab_scatter<OUT>, grid, block, st, p, (OUT*)out, cap, (OUT*)counts, nb, err, ha, va);
+    });
 }
 
-// token counts (KIND 5): every token of the batch found or entered in the counting table and counted; no output but the table
-hipError_t launch_count_scatter(const uint8_t* u8, const CountTable& ct, const uint64_t* bits, const uint64_t* space, const uint64_t* kept,
-                                const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, int64_t total,
-                                const int64_t* row_off, int64_t n_str, const int64_t* tile_first, const int64_t* n_items_dev, int* err,
-                                hipStream_t st) {
-    if (n_words <= 0) return hipSuccess;
-    CountScatterArgs a;
-    a.bits = bits; a.space = space; a.item_mask = kept;
-    a.tile_rank = tile_rank; a.tile_cnt = tile_cnt; a.word_pref = word_pref;
-    a.n_words = n_words; a.total = total;
-    a.row_off = row_off; a.n_str = n_str;
-    a.tile_first = tile_first; a.n_items_dev = n_items_dev;
-    a.n_scatter_blocks = (unsigned)((n_words + 255) / 256);
+// token counts: every token of the batch found or entered in the counting table and counted; no output but the table
+hipError_t launch_count_scatter(const TokenPlanes& p, const uint8_t* u8, const CountTable& ct, int* err, hipStream_t st) {
+    CountScatterArgs a{};
+    a.p = p;
     a.err = err;
     a.ha.text = reinterpret_cast<const uint32_t*>(u8);
     a.ha.seed = ct.seed;
@@ -1503,36 +1506,28 @@ hipError_t launch_count_scatter(const uint8_t* u8, const CountTable& ct, const u
     a.ca.n_slots = ct.n_slots;
     a.ca.tally = ct.tally;
     a.ca.max_word_bytes = ct.max_word_bytes;
-    hipLaunchKernelGGL(k_count_scatter, dim3(a.n_scatter_blocks), dim3(scatter_waves(5) * 64), 0, st, a);
-    return hipGetLastError();
+    return launch_scatter(true, p, true, false, [&](auto, dim3 grid, dim3 block, unsigned nb) {
+        a.n_scatter_blocks = nb;
+        hipLaunchKernelGGL(k_count_scatter, grid, block, 0, st, a);
+    });
 }
-// term keys (KIND 6): keys[rank] of every token and the int64 token count of every string (vt == NULL: the hashed form)
-hipError_t launch_term_scatter(const uint8_t* u8, const VocabTable* vt, uint32_t seed, uint32_t n_features, bool alternate_sign,
-                               const uint64_t* bits, const uint64_t* space, const uint64_t* kept, const int64_t* tile_rank,
-                               const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, int64_t total, const int64_t* row_off,
-                               int64_t n_str, const int64_t* tile_first, const int64_t* n_items_dev, uint64_t* keys, int64_t* counts, int* err,
-                               hipStream_t st) {
-    if (n_words <= 0) return hipSuccess;
+// term keys: keys[rank] of every token and the int64 token count of every string (vt == NULL: the hashed form)
+hipError_t launch_term_scatter(const TokenPlanes& p, const uint8_t* u8, const VocabTable* vt, uint32_t seed, uint32_t n_features,
+                               bool alternate_sign, uint64_t* keys, int64_t* counts, int* err, hipStream_t st) {
     TermScatterArgs a{};
-    a.bits = bits; a.space = space; a.item_mask = kept;
-    a.tile_rank = tile_rank; a.tile_cnt = tile_cnt; a.word_pref = word_pref;
-    a.n_words = n_words; a.total = total;
-    a.row_off = row_off; a.n_str = n_str;
-    a.tile_first = tile_first; a.n_items_dev = n_items_dev; a.counts = counts;
-    a.n_scatter_blocks = (unsigned)((n_words + 255) / 256);
+    a.p = p;
+    a.counts = counts;
     a.err = err;
     a.ha.text = reinterpret_cast<const uint32_t*>(u8);
     a.ha.seed = vt ? vt->seed : seed;
-    if (vt) {
-        a.va.slots = reinterpret_cast<const VtSlot*>(vt->slots);
-        a.va.blob = vt->blob;
-        a.va.n_slots = vt->n_slots;
-    }
+    if (vt) a.va = vocab_args(*vt, nullptr, 0);
     a.ta.keys = keys;
     a.ta.n_features = vt ? 0u : n_features;
     a.ta.alternate_sign = alternate_sign;
-    hipLaunchKernelGGL(k_term_scatter, dim3(a.n_scatter_blocks + (unsigned)((n_str + 255) / 256)), dim3(scatter_waves(6) * 64), 0, st, a);
-    return hipGetLastError();
+    return launch_scatter(false, p, true, counts, [&](auto, dim3 grid, dim3 block, unsigned nb) {
+        a.n_scatter_blocks = nb;
+        hipLaunchKernelGGL(k_term_scatter, grid, block, 0, st, a);
+    });
 }
 
 hipError_t launch_count_commit_sum(const CountTable& ct, hipStream_t st) {

@@ -1,4 +1,4 @@
-// count_table.h -- the counting table of the token-count call (compact_kernels.hip: KIND 5 of counts_scatter_block and the two
+// count_table.h -- the counting table of the token-count call (compact_kernels.hip: CountTokens of scatter_block and the two
 // commit kernels): an exact, insert-only map from a token's bytes to a 64-bit count, filled by many threads at once.  Plain C++17,
 // like vocab_table.h: it compiles on the host (tests/helpers/count_table_harness.cpp runs it with std::atomic, single-threaded and
 // with 8 threads on one table) and, under hipcc, on the device.  The atomic operations come through a policy parameter `A`:

@@ -151,6 +151,31 @@ __device__ __forceinline__ int64_t device_total(const int64_t* p, int64_t bound)
 }
 #endif
 
+// The read view of a scanned batch: the two bitmasks of the tile kernel and what k_word_counts + k_scan_chained leave over them.
+// Every consumer of the token scatter and k_string_counts read a batch through this record (k_features_tiles: through FeatParams,
+// which the host fills from it); launch_word_counts_scan is its one writer (the item mask where it is the kept mask, the tile counts,
+// the word prefixes, the tile ranks and *n_items).
+// The field order is the kernel-argument layout of k_count_scatter and k_term_scatter.
+struct TokenPlanes {
+    const uint64_t* bits;         // final boundary bitmask (bit i = packed unit i)
+    const uint64_t* space;        // SPACE bitmask (NULL: offsets); only walked for tokens that span more than two words
+    const uint64_t* item_mask;    // the items: every boundary (offsets) or the boundaries whose token is kept (k_word_counts<true>)
+    const int64_t* tile_rank;     // index of a tile's first item (exclusive scan of the per-tile item counts)
+    const int64_t* tile_cnt;      // items per tile
+    const uint16_t* word_pref;    // items of the tile before each word
+    int64_t n_words, total;       // 64-bit words of one plane, units of the batch (an upper bound under a DeviceTotal)
+    const int64_t* row_off;       // [n_str + 1]
+    int64_t n_str;
+    const int64_t* tile_first;    // per tile: first string that starts at or after its first unit (NULL: searched)
+    const int64_t* n_items;       // device: the item total of the batch (k_scan_chained)
+};
+// The state of one chained scan (k_scan_chained): the published words, the ticket counter and the launch's epoch.
+struct ChainState {
+    unsigned long long* chain;
+    unsigned* ticket;
+    unsigned epoch;
+};
+
 // featurize on the tile grid (feature_kernels.hip: k_features_tiles)
 struct FeatParams {
     const uint8_t* codes;         // rule code of every char (SplitParams::codes_out of the tile kernel), padded by one tile + 256 B
@@ -239,19 +264,13 @@ hipError_t launch_exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int
 // compact_kernels.hip: word-parallel compaction (offsets / token spans / featurize spans)
 int64_t count_blocks(int64_t n_words);   // workgroups of launch_word_counts_scan = entries of its `chain` state
 int64_t scan_chunk();                  // kChainChunk: entries one workgroup of the chained scan takes (latok_debug_wordpiece_limits)
-hipError_t launch_word_counts_scan(bool spans, const uint64_t* bits, const uint64_t* space, int64_t n_words, int64_t total,
-                                   uint64_t* kept, int64_t* tile_cnt, uint16_t* word_pref, int64_t* tile_rank,
-                                   unsigned long long* chain, unsigned* ticket, unsigned epoch, int64_t* total_dev,
-                                   int64_t* total_host, int* err, hipStream_t st, DeviceTotal dt = DeviceTotal{nullptr, nullptr});
-hipError_t launch_string_counts(bool out32, const uint64_t* mask, const int64_t* tile_rank, const uint16_t* word_pref,
-                                const int64_t* row_off, int64_t n_str, int64_t total, const int64_t* n_items, void* counts, int* err,
-                                hipStream_t st, DeviceTotal dt = DeviceTotal{nullptr, nullptr});
+hipError_t launch_word_counts_scan(bool spans, const TokenPlanes& p, const ChainState& c, int64_t* total_host, int* err, hipStream_t st,
+                                   DeviceTotal dt = DeviceTotal{nullptr, nullptr});
+hipError_t launch_string_counts(bool out32, const TokenPlanes& p, void* counts, int* err, hipStream_t st,
+                                DeviceTotal dt = DeviceTotal{nullptr, nullptr});
 // kind 0 = offsets, 1 = stripped token spans, 2 = featurize's 4-field span records {raw start, raw end, stripped start, stripped end}
-hipError_t launch_counts_scatter(int kind, bool out32, const uint64_t* bits, const uint64_t* space, const uint64_t* item_mask,
-                                 const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words,
-                                 int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,
-                                 const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st, DoneSignal done = DoneSignal{nullptr, 0, nullptr},
-                                 DeviceTotal dt = DeviceTotal{nullptr, nullptr});
+hipError_t launch_counts_scatter(int kind, bool out32, const TokenPlanes& p, void* out, int64_t cap, void* counts, int* err, hipStream_t st,
+                                 DoneSignal done = DoneSignal{nullptr, 0, nullptr}, DeviceTotal dt = DeviceTotal{nullptr, nullptr});
 // k_features_tiles (feature_kernels.hip, where the measurements behind these values are told); latok_debug_limits reports them
 constexpr int kFeatWaves = 7;                                         // (6 -> 7: C2 -4.5 %, C3 -6 %; 8 would need rounds of < 800 tokens: two rounds per C2 tile)
 constexpr int kFeatRound = 896;                                       // tokens per round (word-major form)
@@ -270,8 +289,8 @@ hipError_t launch_lead_compress(const uint64_t* bmask, const uint64_t* bmask2, c
 // the bytes, the lead-byte mask and the lead ranks of the byte-space pipeline; tb6rule = the byte-space rule-code table (featurize)
 hipError_t launch_lead_codes(const uint8_t* u8, int64_t total_bytes, const uint64_t* lead, const int64_t* tile_rank, const int64_t* tile_cnt,
                              const uint16_t* word_pref, int64_t n_words, const uint8_t* tb6rule, uint8_t* codes, int n_cu, hipStream_t st);
-hipError_t launch_tile_scan(const int64_t* tile_cnt, int64_t n_tiles, int64_t* tile_rank, unsigned long long* chain, unsigned* ticket,
-                            unsigned epoch, int64_t* total_dev, int64_t* total_host, int* err, hipStream_t st);
+hipError_t launch_tile_scan(const int64_t* tile_cnt, int64_t n_tiles, int64_t* tile_rank, const ChainState& c, int64_t* total_dev,
+                            int64_t* total_host, int* err, hipStream_t st);
 // joined token text of a UTF-8 batch in byte space (compact_kernels.hip: "joined token text"): the body / head planes with the
 // items (output bytes) per word and per tile; then, behind a scan of the tile counts, the output bytes (only if the total
 // fits cap; out may be NULL) and out_off[n_str + 1].  *err gets bit 2 (value 4) when the total exceeds cap.
@@ -282,15 +301,13 @@ hipError_t launch_join_scatter(const uint8_t* u8, int64_t total, const uint64_t*
                                const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, const int64_t* row_off,
                                int64_t n_str, int sep, uint8_t* out, int64_t cap, const int64_t* n_items_dev, int64_t* out_off,
                                int* err, hipStream_t st);
-// token hashes of a UTF-8 batch in byte space (compact_kernels.hip: KIND 3): behind k_word_counts<true> + k_scan_chained, the
-// per-string counts (counts may be NULL), the span records of KIND 1 (out may be NULL) and one MurmurHash3 x86_32 word per token
+// token hashes of a UTF-8 batch in byte space (compact_kernels.hip: HashTokens): behind k_word_counts<true> + k_scan_chained, the
+// per-string counts (counts may be NULL), the two-field span records (out may be NULL) and one MurmurHash3 x86_32 word per token
 // at its rank, the last two only if the total fits cap.  A token of more than kHashWaveBytes bytes is hashed by its whole wave.
 constexpr int kHashWaveBytes = 256;
-hipError_t launch_hash_scatter(bool out32, const uint8_t* u8, uint32_t seed, const uint64_t* bits, const uint64_t* space,
-                               const uint64_t* kept, const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref,
-                               int64_t n_words, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* tile_first, void* out,
-                               uint32_t* hashes, const int64_t* n_items_dev, int64_t cap, void* counts, int* err, hipStream_t st);
-// token ids of a UTF-8 batch in byte space (compact_kernels.hip: KIND 4): launch_hash_scatter's launch with the hash kept in its
+hipError_t launch_hash_scatter(bool out32, const TokenPlanes& p, const uint8_t* u8, uint32_t seed, void* out, uint32_t* hashes, int64_t cap,
+                               void* counts, int* err, hipStream_t st);
+// token ids of a UTF-8 batch in byte space (compact_kernels.hip: IdTokens): launch_hash_scatter's launch with the hash kept in its
 // lane and looked up in a vocabulary table (vocab_table.h) -- exact: the hash finds the slot, the bytes decide.  ids[rank] = the
 // word's id or unk_id.  The table is device memory, read only.
 struct VocabTable {
@@ -299,12 +316,9 @@ struct VocabTable {
     uint64_t n_slots = 0;             // a power of two
     uint32_t seed = 0;
 };
-hipError_t launch_vocab_scatter(bool out32, const uint8_t* u8, const VocabTable& vt, int32_t unk_id, const uint64_t* bits,
-                                const uint64_t* space, const uint64_t* kept, const int64_t* tile_rank, const int64_t* tile_cnt,
-                                const uint16_t* word_pref, int64_t n_words, int64_t total, const int64_t* row_off, int64_t n_str,
-                                const int64_t* tile_first, void* out, int32_t* ids, const int64_t* n_items_dev, int64_t cap, void* counts,
-                                int* err, hipStream_t st);
-// token counts of a UTF-8 batch in byte space (compact_kernels.hip: KIND 5): launch_vocab_scatter's launch without outputs; every
+hipError_t launch_vocab_scatter(bool out32, const TokenPlanes& p, const uint8_t* u8, const VocabTable& vt, int32_t unk_id, void* out,
+                                int32_t* ids, int64_t cap, void* counts, int* err, hipStream_t st);
+// token counts of a UTF-8 batch in byte space (compact_kernels.hip: CountTokens): launch_vocab_scatter's launch without outputs; every
 // token of at most max_word_bytes bytes is found or entered in a counting table (count_table.h) and counted, exactly.
 // kCountProbeMax bounds a probe whatever the table holds: at load <= 0.5 a run of 128 occupied slots has probability about
 // 0.82^128 ~ 1e-11 per slot, so the bound never fires on a table sized as documented and keeps a full one from costing n_slots
@@ -325,18 +339,12 @@ struct CountTable {
     unsigned long long* tally = nullptr;    // this call's {counted, long, dropped}
     unsigned long long* ctl = nullptr;      // {fresh dwords of this call, blob cursor, distinct, overflow flag}
 };
-hipError_t launch_count_scatter(const uint8_t* u8, const CountTable& ct, const uint64_t* bits, const uint64_t* space, const uint64_t* kept,
-                                const int64_t* tile_rank, const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, int64_t total,
-                                const int64_t* row_off, int64_t n_str, const int64_t* tile_first, const int64_t* n_items_dev, int* err,
-                                hipStream_t st);
-// term keys of a UTF-8 batch in byte space (compact_kernels.hip: KIND 6): launch_vocab_scatter's launch with one term key
+hipError_t launch_count_scatter(const TokenPlanes& p, const uint8_t* u8, const CountTable& ct, int* err, hipStream_t st);
+// term keys of a UTF-8 batch in byte space (compact_kernels.hip: TermTokens): launch_vocab_scatter's launch with one term key
 // (term_key.h) per token at its rank in `keys` and the int64 token count of every string in `counts`; vt == NULL: the hashed form
 // (bucket = |h| mod n_features, sign).  No records, no capacity.
-hipError_t launch_term_scatter(const uint8_t* u8, const VocabTable* vt, uint32_t seed, uint32_t n_features, bool alternate_sign,
-                               const uint64_t* bits, const uint64_t* space, const uint64_t* kept, const int64_t* tile_rank,
-                               const int64_t* tile_cnt, const uint16_t* word_pref, int64_t n_words, int64_t total, const int64_t* row_off,
-                               int64_t n_str, const int64_t* tile_first, const int64_t* n_items_dev, uint64_t* keys, int64_t* counts, int* err,
-                               hipStream_t st);
+hipError_t launch_term_scatter(const TokenPlanes& p, const uint8_t* u8, const VocabTable* vt, uint32_t seed, uint32_t n_features,
+                               bool alternate_sign, uint64_t* keys, int64_t* counts, int* err, hipStream_t st);
 // per-string term counts (terms_kernels.hip): the segmented sort-and-reduce of the term keys.  A workgroup owns the rows that start
 // in its tile of kTermsTile tokens; a row of more than kTermsRowMax tokens is sorted by a workgroup of its own through `alt`
 // (as large as `keys`).  row_start[n_str + 1] = the exclusive scan of the per-string token counts.  launch_terms_reduce leaves
@@ -351,7 +359,7 @@ hipError_t launch_terms_emit(const uint64_t* keys, const int64_t* row_start, int
                              const int64_t* indptr, const int64_t* nnz_dev, int64_t cap, int32_t* indices, int32_t* data, hipStream_t st);
 hipError_t launch_terms_finish(bool out32, const int64_t* indptr, const int64_t* oov, int64_t n_str, void* indptr_out, void* oov_out,
                                hipStream_t st);
-// WordPiece ids of a UTF-8 batch in byte space (wordpiece_kernels.hip), in token space, one lane per token: behind KIND 1 of
+// WordPiece ids of a UTF-8 batch in byte space (wordpiece_kernels.hip), in token space, one lane per token: behind kind 1 of
 // launch_counts_scatter (int64 span records at rank in the workspace, int64 token count per string) and the scan of those counts
 // (row_start[n_str + 1]).  launch_wp_count leaves the pieces of every token in cnt[0 .. n_tok) and 0 in cnt[n_tok]; the caller scans
 // the n_tok + 1 entries into rank[] (rank[n_tok] = the piece total); launch_wp_emit walks every token again and stores ids, and
@@ -373,7 +381,7 @@ hipError_t launch_wp_emit(bool out32, const uint8_t* u8, int64_t total, const in
 hipError_t launch_wp_rows(bool out32, const int64_t* row_start, const int64_t* rank, int64_t n_str, int64_t n_tok, void* indptr_out, hipStream_t st);
 hipError_t launch_wp_pad(const int32_t* ids, const int64_t* row_start, const int64_t* rank, int64_t n_str, int64_t n_tok, int64_t max_length, int add_special,
                          int32_t cls_id, int32_t sep_id, int32_t pad_id, int32_t* input_ids, int32_t* lengths, hipStream_t st);
-// word n-grams of a UTF-8 batch in byte space (ngram_kernels.hip), in token space, one lane per token: behind KIND 1 of
+// word n-grams of a UTF-8 batch in byte space (ngram_kernels.hip), in token space, one lane per token: behind kind 1 of
 // launch_counts_scatter and the scan of the token counts, as WordPiece.  launch_ngram_rows leaves the grams of every string in
 // key_cnt[0 .. n_str) and 0 in key_cnt[n_str]; the caller scans the n_str + 1 entries into key_start[] (key_start[n_str] = the key
 // total).  launch_ngram_keys stores one term key (term_key.h) per gram of the orders min_n .. max_n inside its row's range of

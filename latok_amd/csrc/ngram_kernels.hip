@@ -1,6 +1,6 @@
 // ngram_kernels.hip -- word n-grams of a UTF-8 batch in byte space: one term key (term_key.h) per gram, the kernels behind
 // latok_ngram_counts_utf8_bytes_batch and latok_hashed_ngram_counts_utf8_bytes_batch.  They work in TOKEN space, as the WordPiece
-// kernels do.  KIND 1 of counts_scatter_block (compact_kernels.hip) has left the int64 span record of every token at its rank in
+// kernels do.  SpanRecords of scatter_block (compact_kernels.hip) has left the int64 span record of every token at its rank in
 // the workspace and the token count c_s of every string; the chained scan the row starts in token space (row_start[n_str + 1]).
 //
 //   k_ngram_rows   K_s = sum over n in [min_n, max_n] of max(0, c_s - n + 1): the grams of string s.  The chained scan of the

@@ -1,4 +1,4 @@
-// term_key.h -- the per-token key of the term-count calls (compact_kernels.hip: KIND 6 of counts_scatter_block writes it at the
+// term_key.h -- the per-token key of the term-count calls (compact_kernels.hip: TermTokens of scatter_block writes it at the
 // token's rank, terms_kernels.hip sorts and reduces it).  Plain C++17, like token_hash.h: it compiles on the host
 // (tests/helpers/term_key_harness.cpp runs it against a Python restatement of the rule) and, under hipcc, on the device.
 //

@@ -1,5 +1,5 @@
 // terms_kernels.hip -- per-string term counts: the segmented sort-and-reduce behind latok_term_counts_utf8_bytes_batch and
-// latok_hashed_term_counts_utf8_bytes_batch.  k_term_scatter (compact_kernels.hip, KIND 6) has left one term key (term_key.h) per
+// latok_hashed_term_counts_utf8_bytes_batch.  k_term_scatter (compact_kernels.hip, TermTokens) has left one term key (term_key.h) per
 // token at its rank and the chained scan the row starts in token space (row_start[n_str + 1], row_start[n_str] = the token total).
 //
 //   ownership    token space is cut into tiles of kTermsTile tokens; a workgroup owns the rows that START in its tile -- found by

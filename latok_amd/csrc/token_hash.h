@@ -1,5 +1,5 @@
 // token_hash.h -- MurmurHash3 x86_32 (Austin Appleby, public domain) of a token's bytes, in the two forms the hash kernel uses
-// (compact_kernels.hip: KIND 3 of counts_scatter_block).  Plain C++: it compiles on the host (tests/helpers/token_hash_harness.cpp
+// (compact_kernels.hip: HashTokens of scatter_block).  Plain C++: it compiles on the host (tests/helpers/token_hash_harness.cpp
 // runs it against an independent implementation) and, under hipcc, on the device.
 //
 //   the function     h = seed

@@ -1,4 +1,4 @@
-// vocab_table.h -- the vocabulary table of the token-id call (compact_kernels.hip: KIND 4 of counts_scatter_block): an exact map
+// vocab_table.h -- the vocabulary table of the token-id call (compact_kernels.hip: IdTokens of scatter_block): an exact map
 // from a token's bytes to an int32 id.  Plain C++17, like token_hash.h: the build runs on the host only; the probe and the
 // compares compile on the host (tests/helpers/vocab_harness.cpp runs them against a Python dict) and, under hipcc, on the device.
 //

@@ -1,5 +1,5 @@
 // wordpiece_kernels.hip -- WordPiece ids of a UTF-8 batch in byte space: the kernels behind latok_wordpiece_ids_utf8_bytes_batch and
-// latok_wordpiece_padded_utf8_bytes_batch.  They work in TOKEN space, one lane per token.  KIND 1 of counts_scatter_block
+// latok_wordpiece_padded_utf8_bytes_batch.  They work in TOKEN space, one lane per token.  SpanRecords of scatter_block
 // (compact_kernels.hip) has left the int64 span record of every token at its rank in the workspace and the token count of every
 // string; the chained scan the row starts in token space (row_start[n_str + 1], row_start[n_str] = the token total).
 //

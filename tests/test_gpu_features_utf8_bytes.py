@@ -239,6 +239,20 @@ def test_long_tokens(gpu):
     _check(["short one", docs[4], "", docs[0][:5000] + " x", docs[5], "tail #tag"], "long documents among short ones")
 
 
+def test_a_tile_of_two_rounds_and_long_tokens_through_device_pointers(gpu):
+    """The byte route at a small size (device pointers) against the host-decoded result of the same batch: 2048 tokens in one
+    4096-byte tile (two rounds of its wave), then one string over several tiles whose tokens end in the next word and beyond it."""
+    from latok_amd import batch
+    runs = ["".join(chr(97 + (i + j * j) % 26) for j in range(n)) for i, n in enumerate((70, 127, 129, 200, 3000, 5000))]
+    u8, boff = _check(["a " * 2048, " ".join(runs), "xy", ""], "two rounds", route=HOST_DECODE)
+    for dt in DTYPES:
+        want = batch.token_features_utf8_bytes_csr(u8, boff, dtype=dt)
+        assert want[0].tolist() == [2048, 6, 1, 0]
+        rc, n, got, _ = _dev_features(gpu, u8, boff, dt)
+        assert rc == 0 and n == 2055 and _route() == BYTE_ROUTE
+        _same(got, want, ("two rounds, device batch", dt))
+
+
 def test_edges_of_words_tiles_and_workgroups(gpu):
     text = _edge_text()
     assert len(text.encode()) > 6 * 65536

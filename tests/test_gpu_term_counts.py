@@ -49,6 +49,16 @@ def limits():
     return tile, row_max
 
 
+def wave_bytes():
+    """kHashWaveBytes: entry 14 of latok_debug_limits"""
+    from latok_amd import _lib
+    fn = _lib.load().latok_debug_limits
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int]
+    out = np.zeros(15, np.int64)
+    assert fn(out.ctypes.data, 15) == 15 and out[14] >= 64
+    return int(out[14])
+
+
 # ---- the definition --------------------------------------------------------------------------------------------------------
 def _i32(u):
     return u - (1 << 32) if u >= (1 << 31) else u
@@ -265,6 +275,28 @@ def test_a_long_row_among_short_rows_and_runs_of_empty_strings(gpu, where):
     assert sorted(len(r) for r in got)[-1] == 8 * row_max + 3 and sum(len(r) == 0 for r in got) == 600
     check_hashed(gpu, blobs, 1 << 20, 3, True, ("long row", where), dtypes=(np.int32,))
     check_hashed(gpu, blobs, 2, 0, True, ("long row", where))
+
+
+def _run(i, n):
+    """one lower-case token of n bytes, its own for every i"""
+    return bytes(97 + (i + j * j) % 26 for j in range(n))
+
+
+def test_every_path_of_the_token_walk(gpu):
+    """Term keys on every path the token walk has: a token that ends in the word after its own (65 .. 128 bytes) and beyond it (more
+    than 128), tokens the whole wave takes (more than kHashWaveBytes bytes: a word, absent, one byte off a word), a tile of two rounds
+    (2048 tokens in 4096 bytes) and a string that began before the tile it is in."""
+    T = wave_bytes()
+    sizes = [70, 127, 129, 200, T - 1, T, T + 1, T + 3, 2 * T + 50, 3000]
+    toks = [_run(i, n) for i, n in enumerate(sizes)]
+    near = [t[:-1] + bytes([97 + (t[-1] - 96) % 26]) for t in toks]              # the last byte is another letter
+    blobs = [b"a " * 2048, b" ".join(toks) + b" xy " + b" ".join(near), b"xy", toks[6] + b" " + toks[2], b""]
+    assert len(blobs[0]) == 4096 and len(blobs[1]) > 2 * 4096 and not set(toks) & set(near)
+    words = toks[::2] + near[1::2] + [b"a", b"xy"]
+    rows, want = check_vocab(gpu, blobs, words, None, "token walk")
+    assert [len(r) for r in rows] == [2048, 21, 1, 2, 0] and rows[1][:10] == toks and rows[1][11:] == near
+    assert want[3].tolist() == [0, 10, 0, 0, 0] and np.diff(want[0]).tolist() == [1, 11, 1, 2, 0]
+    check_hashed(gpu, blobs, 1 << 20, 5, True, "token walk", dtypes=(np.int32,))
 
 
 def test_rows_that_start_exactly_on_a_tile_edge(gpu):

@@ -277,6 +277,14 @@ def test_a_mebibyte_token_under_the_built_in_tables(gpu):
     assert [len(t) for t in toks] == [2, 1 << 20, 2, 2]
 
 
+def test_a_tile_of_two_rounds_and_a_string_that_began_before_its_tile(gpu):
+    """2048 tokens in one 4096-byte tile (two rounds of its wave), then one string over three tiles with long tokens in it"""
+    T = wave_bytes()
+    blobs = [b"a " * 2048, b" ".join(bytes(97 + (i + j * j) % 26 for j in range(n)) for i, n in enumerate((70, 129, T + 1, 3000, 2 * T, 5000))), b"xy"]
+    u8, boff, counts, toks = _check_definition(gpu, blobs, "two rounds")
+    assert counts.tolist() == [2048, 6, 1] and [len(t) for t in toks[2048:]] == [70, 129, T + 1, 3000, 2 * T, 5000, 2]
+
+
 def test_many_long_tokens_meet_in_one_wave(gpu, one_token_per_string):
     rng = random.Random(53)
     T = wave_bytes()

@@ -313,6 +313,15 @@ def test_long_tokens_hit_and_their_look_alikes_miss(gpu, one_token_per_string):
     assert ids.tolist() == [-1] * 7 + list(range(len(look_alikes)))
 
 
+def test_a_tile_of_two_rounds_and_a_string_that_began_before_its_tile(gpu):
+    """2048 tokens in one 4096-byte tile (two rounds of its wave), then one string over three tiles with long tokens in it"""
+    T = wave_bytes()
+    long_toks = [bytes(97 + (i + j * j) % 26 for j in range(n)) for i, n in enumerate((70, 129, T + 1, 3000, 2 * T, 5000))]
+    blobs = [b"a " * 2048, b" ".join(long_toks), b"xy"]
+    u8, boff, counts, toks, ids = _check_definition(gpu, blobs, [b"a"] + long_toks[::2], "two rounds", dtypes=(np.int64,), unks=(-1,), id_forms=(False,))
+    assert counts.tolist() == [2048, 6, 1] and ids.tolist() == [0] * 2048 + [1, -1, 2, -1, 3, -1, -1]
+
+
 def test_many_long_tokens_meet_in_one_wave(gpu, one_token_per_string):
     rng = random.Random(53)
     T = wave_bytes()
