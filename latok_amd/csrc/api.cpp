@@ -4074,6 +4074,65 @@ extern "C" int latok_debug_wordpiece_limits(int64_t* out, int n) {
     return k;
 }
 
+/* test hook (not part of the ABI; needs no device): the constants of the two device-wide int64 scans: out[0] = kChainChunk (entries per
+ * workgroup of k_scan_chained), out[1] = predecessors one look-back round reads (64), out[2] = kChainValueBits, out[3] = bits of the
+ * launch epoch (18), out[4] = kScanSmallMax, out[5] = kScanChunk (entries per workgroup of k_scan_local), out[6] = kScanBlock.  Returns
+ * the number of values written. */
+extern "C" int latok_debug_scan_limits(int64_t* out, int n) {
+    const int64_t v[7] = {latok::scan_chunk(), latok::chain_lookback(), latok::chain_value_bits(), latok::chain_epoch_bits(),
+                          latok::scan_small_max(), latok::scan_local_chunk(), latok::scan_block_threads()};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 7 ? n : 7;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
+/* test hook (not part of the ABI): one device-wide exclusive scan of d_in[0 .. n) into d_out (device pointers), exactly as the calls
+ * run it, on the current context and its stream; blocking.  which = 0: the chained scan as enqueue_row_scan runs it -- next_scan_epoch
+ * on the context's workspace, whose chain array ws_needs sizes as for a call of n rows, then launch_tile_scan; d_units (or NULL): the
+ * device word of the kernel's device-sized form (ceil(*d_units / kTile) entries are real, the grid is sized for n).  which = 1:
+ * launch_exclusive_scan with the context's own block totals and total words, as decode_utf8_to_workspace calls it.  *total_out = the
+ * total the device wrote (the device word and the pinned word must agree), *flag_out = the scan's own error flag.
+ * THE BOUND: a chained scan's total must stay below 2^kChainValueBits (2^44) -- the value field of a published word holds no more and
+ * wraps silently; every count the calls scan (rows, tokens, pieces, bytes of a batch) is far below it. */
+extern "C" int latok_debug_scan(int which, const int64_t* d_in, int64_t n, int64_t* d_out, const int64_t* d_units, int64_t* total_out,
+                                int* flag_out) {
+    LATOK_ENTER();
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (n < 1) return fail(LATOK_ERR_INVALID, "n must be >= 1");
+    if ((which != 0 && which != 1) || !d_in || !d_out || !total_out || !flag_out || (which == 1 && d_units)) return fail(LATOK_ERR_INVALID, "bad args");
+    StreamTurn turn(g, nullptr);
+    const hipStream_t st = turn.st;
+    Workspace& w = g.ws;
+    if ((rc = g.pin_tot.ensure(64))) return rc;
+    volatile int64_t* h = (volatile int64_t*)g.pin_tot.h;
+    int64_t* p = (int64_t*)g.pin_tot.d;
+    h[0] = -1;
+    h[1] = 0;
+    int64_t* d_total = nullptr;
+    if (which == 0) {
+        for (const WsNeed& need : ws_needs(w, 0, WsShape{.term_rows = n}))
+            if ((need.buf == &w.chain || need.buf == &w.chain_ctl || need.buf == &w.scalar) && (rc = need.buf->ensure(need.bytes))) return rc;
+        d_total = (int64_t*)w.scalar.p + 4;
+        latok::ChainState chain;
+        if ((rc = next_scan_epoch(w, st, &chain))) return rc;
+        HIP_TRY(latok::launch_tile_scan(d_in, n, d_out, chain, d_total, p, (int*)(p + 1) + 1, st, d_units));
+    } else {
+        if ((rc = w.scalar.ensure(64)) || (rc = g.scan_tot.ensure((size_t)latok::scan_blocks(n) * 8))) return rc;
+        d_total = (int64_t*)w.scalar.p;
+        HIP_TRY(latok::launch_exclusive_scan(d_in, n, d_out, d_total, (int64_t*)g.scan_tot.p, st, p));
+    }
+    int64_t dev_total = -2;
+    HIP_TRY(hipMemcpyAsync(&dev_total, d_total, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *flag_out = (int)(h[1] >> 32);
+    *total_out = h[0];
+    if (*flag_out) w.chain_ready = false;   // (as finish_totals: the next scan clears the state)
+    else if (dev_total != h[0]) return fail(LATOK_ERR_HIP, "the scan's device total %lld and pinned total %lld differ", (long long)dev_total, (long long)h[0]);
+    return LATOK_OK;
+}
+
 // LaunchPlan as the hooks report it: out[0..11] = n_cu_eff, seg_tiles, n_segs, rounds, grid of k_tiles_main, grid of
 // k_resolve_fix, fast_tail, pf, wpb, nw, one_launch, n_tiles
 static int put_plan(const latok::LaunchPlan& L, int64_t n_tiles, int64_t* out, int n) {

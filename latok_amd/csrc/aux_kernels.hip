@@ -425,6 +425,8 @@ __global__ void k_utf8_cp_offsets(const uint8_t* __restrict__ u8, int64_t total,
 int64_t utf8_blocks(int64_t total_bytes) { return total_bytes > 0 ? (total_bytes + kU8Block - 1) / kU8Block : 1; }
 int64_t utf8_block_bytes() { return kU8Block; }
 int64_t scan_small_max() { return kScanSmallMax; }
+int64_t scan_local_chunk() { return kScanChunk; }
+int64_t scan_block_threads() { return kScanBlock; }
 
 hipError_t launch_utf8_block_counts(const uint8_t* u8, int64_t total, int64_t* block_cnt, hipStream_t st) {
     hipLaunchKernelGGL(k_utf8_block_counts, dim3((unsigned)utf8_blocks(total)), dim3(kU8Threads), 0, st, u8, total, block_cnt);

@@ -1384,15 +1384,18 @@ hipError_t launch_join_scatter(const uint8_t* u8, int64_t total, const uint64_t*
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
 int64_t scan_chunk() { return kChainChunk; }
+int chain_lookback() { return 64; }   // one predecessor per lane of the look-back wave
+int chain_value_bits() { return kChainValueBits; }
+int chain_epoch_bits() { return 64 - kChainEpochShift; }
 int64_t count_blocks(int64_t n_words) { return n_words > 0 ? ((n_words + 63) / 64 + kChainChunk - 1) / kChainChunk : 0; }
 
 // exclusive scan of per-tile counts that some other kernel left (the byte-space tile kernel: leads per tile): k_scan_chained alone
 hipError_t launch_tile_scan(const int64_t* tile_cnt, int64_t n_tiles, int64_t* tile_rank, const ChainState& c, int64_t* total_dev,
-                            int64_t* total_host, int* err, hipStream_t st) {
+                            int64_t* total_host, int* err, hipStream_t st, const int64_t* units_dev) {
     if (n_tiles <= 0) return hipSuccess;
     const unsigned n_blocks = (unsigned)((n_tiles + kChainChunk - 1) / kChainChunk);
     hipLaunchKernelGGL(k_scan_chained, dim3(n_blocks), dim3(kChainBlock), 0, st, tile_cnt, n_tiles, tile_rank, c.chain, c.ticket, c.epoch,
-                       n_blocks, total_dev, total_host, err, (const int64_t*)nullptr);
+                       n_blocks, total_dev, total_host, err, units_dev);
     return hipGetLastError();
 }
 

@@ -264,6 +264,11 @@ hipError_t launch_exclusive_scan(const int64_t* in, int64_t n, int64_t* out, int
 // compact_kernels.hip: word-parallel compaction (offsets / token spans / featurize spans)
 int64_t count_blocks(int64_t n_words);   // workgroups of launch_word_counts_scan = entries of its `chain` state
 int64_t scan_chunk();                  // kChainChunk: entries one workgroup of the chained scan takes (latok_debug_wordpiece_limits)
+// the chained scan's other constants (latok_debug_scan_limits): predecessors one look-back round reads, bits of a published word's
+// value field (a scan's total must stay below 2^bits: the field wraps silently) and bits of its launch epoch
+int chain_lookback();
+int chain_value_bits();
+int chain_epoch_bits();
 hipError_t launch_word_counts_scan(bool spans, const TokenPlanes& p, const ChainState& c, int64_t* total_host, int* err, hipStream_t st,
                                    DeviceTotal dt = DeviceTotal{nullptr, nullptr});
 hipError_t launch_string_counts(bool out32, const TokenPlanes& p, void* counts, int* err, hipStream_t st,
@@ -289,8 +294,9 @@ hipError_t launch_lead_compress(const uint64_t* bmask, const uint64_t* bmask2, c
 // the bytes, the lead-byte mask and the lead ranks of the byte-space pipeline; tb6rule = the byte-space rule-code table (featurize)
 hipError_t launch_lead_codes(const uint8_t* u8, int64_t total_bytes, const uint64_t* lead, const int64_t* tile_rank, const int64_t* tile_cnt,
                              const uint16_t* word_pref, int64_t n_words, const uint8_t* tb6rule, uint8_t* codes, int n_cu, hipStream_t st);
+// units_dev (or NULL): the kernel's device-sized form -- ceil(*units_dev / kTile) counts, at most the n_tiles the grid is sized for
 hipError_t launch_tile_scan(const int64_t* tile_cnt, int64_t n_tiles, int64_t* tile_rank, const ChainState& c, int64_t* total_dev,
-                            int64_t* total_host, int* err, hipStream_t st);
+                            int64_t* total_host, int* err, hipStream_t st, const int64_t* units_dev = nullptr);
 // joined token text of a UTF-8 batch in byte space (compact_kernels.hip: "joined token text"): the body / head planes with the
 // items (output bytes) per word and per tile; then, behind a scan of the tile counts, the output bytes (only if the total
 // fits cap; out may be NULL) and out_off[n_str + 1].  *err gets bit 2 (value 4) when the total exceeds cap.
@@ -417,6 +423,8 @@ hipError_t launch_pad_codes(uint8_t* codes, const int64_t* total_dev, int64_t bo
 int64_t utf8_blocks(int64_t total_bytes);   // 4 KiB blocks of the chunk-parallel UTF-8 decoder
 int64_t utf8_block_bytes();                 // kU8Block: bytes per block of that decoder (latok_debug_limits)
 int64_t scan_small_max();                   // kScanSmallMax: entries above which launch_exclusive_scan takes three launches
+int64_t scan_local_chunk();                 // kScanChunk: entries per workgroup of k_scan_local / k_scan_add (latok_debug_scan_limits)
+int64_t scan_block_threads();               // kScanBlock: threads of every kernel of launch_exclusive_scan
 hipError_t launch_utf8_block_counts(const uint8_t* u8, int64_t total, int64_t* block_cnt, hipStream_t st);
 hipError_t launch_utf8_decode(const uint8_t* u8, int64_t total, const int64_t* byte_off, int64_t n_str,
                               const int64_t* block_base, uint16_t* chunk_pref, int64_t total_cps, uint32_t* cps,

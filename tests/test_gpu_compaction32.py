@@ -102,7 +102,7 @@ def test_scan_epoch_wrap(gpu, oracle):
     from latok_amd import _lib, batch
     lib = C.CDLL(_lib.LIB_PATH)
     rng = random.Random(1)
-    texts = random_strings(rng, 9000, 0, 90, ALPHABETS["mixed"])        # ~100 tiles: several scan workgroups
+    texts = random_strings(rng, 9000, 0, 90, ALPHABETS["mixed"])        # ~100 tile counts: ONE scan workgroup (the multi-workgroup wrap: test_gpu_scans.py)
     cps, row = pack(texts)
     want = batch.split_offsets_csr(cps, row)
     assert lib.latok_debug_set_scan_epoch(0x3FFFC) == 0
