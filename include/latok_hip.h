@@ -355,6 +355,45 @@ int latok_hashed_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_
                                                int64_t* indptr_out /* [n_str+1] */, int32_t* indices_out, int32_t* data_out, int64_t cap,
                                                int64_t* nnz_out, int64_t* n_grams_out /* may be NULL */, int flags, void* stream);
 
+/* Character n-grams inside tokens in the term counts: the same CSR rows with one term per CHARACTER GRAM of every token -- what
+ * CountVectorizer(analyzer="char_wb", vocabulary=..., ngram_range=(min_n, max_n)) and HashingVectorizer(analyzer="char_wb", norm=None,
+ * ngram_range=(min_n, max_n)) return for " ".join(tokens); scikit-learn's _char_wb_ngrams feeds exactly these strings to its
+ * vocabulary or hasher.  The tokens are what latok_token_spans_utf8_bytes_batch reports for string s; run-time rule tables and
+ * malformed bytes are taken as that call takes them.
+ *   character     a character of a token starts at the token's first byte and at every later byte b with (b & 0xC0) != 0x80.  For
+ *                 valid UTF-8 these are the code points; for malformed bytes the rule is still total.  A character's bytes run to the
+ *                 next start or to the token's end.
+ *   padded word   for a token of L >= 1 characters: pad, c_0 .. c_(L-1), pad -- W = L + 2 characters; pad is one byte, 0 .. 255
+ *                 (scikit-learn uses 0x20).
+ *   grams         for n from min_n up to max_n, in this order, 1 <= min_n <= max_n <= 8: if n < W, the W - n + 1 runs of n
+ *                 neighbouring characters of the padded word; if n >= W, the only gram is the whole padded word, once, and NO HIGHER
+ *                 ORDER CONTRIBUTES (scikit-learn: "count a short word only once").
+ *   gram count    G(W) = sum over n in [min_n, min(max_n, W - 1)] of (W - n + 1), plus 1 if max_n >= W.  A token whose record is empty
+ *                 or does not lie in the text has no gram.  A string's grams are those of its tokens; K is the batch's gram total.
+ * Every gram gets a key and a value by exactly the rules of the term-counts comment above, applied to the BYTES OF THE GRAM:
+ *   vocabulary form   byte-for-byte lookup in the latok_vocab; a vocabulary word may hold the pad (" th").  A found gram contributes
+ *                     its id with value 1; a gram that is not found adds 1 to oov[s].
+ *   hashed form       h = MurmurHash3 x86_32 of the gram's bytes with `seed`; column = |h| mod n_features in 64 bits; the sign follows
+ *                     alternate_sign.
+ * Rows, CSR layout and determinism carry over unchanged, and so do flags, host pointers or LATOK_DEVICE_PTRS, total_bytes = -1, the
+ * check of the vocabulary's device, the capacity protocol in ENTRIES with its size query, LATOK_OUT_INT32 and the empty batch.
+ * *n_grams_out (may be NULL) = K.  A batch whose token total, or whose K, is 2^31 or more is refused with nothing written to indices or
+ * data.  min_n < 1, max_n < min_n, max_n > 8 and pad outside 0 .. 255 are refused with LATOK_ERR_INVALID before any device work, with
+ * nothing written.  The calls are blocking and wait for their kernels THREE times, as the word n-gram calls do, and a fourth time for
+ * the copy of the entries when the outputs are host pointers.  Every batch size takes the same kernels.  One lane walks a token alone:
+ * a batch with very long tokens runs at the speed of its longest; there is no whole-wave form for long tokens.
+ * Not built: the plain analyzer="char" (over the whole string, with scikit-learn's whitespace collapsing: it needs no tokenizer);
+ * one-call TF-IDF and idf-update forms (the composition of these counts with latok_idf_update_csr and latok_tfidf_csr works with
+ * device pointers and no host visit); fitting a gram vocabulary; a flow form. */
+int latok_chargram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                           const latok_vocab* vocab, int min_n, int max_n, int pad, int64_t* indptr_out /* [n_str+1] */,
+                                           int64_t* oov_out /* [n_str], may be NULL */, int32_t* indices_out, int32_t* data_out, int64_t cap,
+                                           int64_t* nnz_out, int64_t* n_grams_out /* may be NULL */, int flags, void* stream);
+int latok_hashed_chargram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                                  uint32_t seed, int64_t n_features, int alternate_sign, int min_n, int max_n, int pad,
+                                                  int64_t* indptr_out /* [n_str+1] */, int32_t* indices_out, int32_t* data_out, int64_t cap,
+                                                  int64_t* nnz_out, int64_t* n_grams_out /* may be NULL */, int flags, void* stream);
+
 /* TF-IDF on the device: document frequencies over many batches, and the float32 weighting of CSR rows -- what TfidfTransformer /
  * TfidfVectorizer add to the term counts above, and the norm="l2" / "l1" of HashingVectorizer.
  * A latok_idf is a mutable device object like latok_counter: int32 df[n_cols] (in how many rows a column was stored) and int64 n_docs

@@ -63,6 +63,9 @@ SIGNATURES = {
     "latok_ngram_counts_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, ci, ci, ci, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
     "latok_hashed_ngram_counts_utf8_bytes_batch": (ci, [vp, vp, i64, i64, C.c_uint32, i64, ci, ci, ci, ci, vp, vp, vp, i64, C.POINTER(i64),
                                                         C.POINTER(i64), ci, vp]),
+    "latok_chargram_counts_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, ci, ci, ci, vp, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
+    "latok_hashed_chargram_counts_utf8_bytes_batch": (ci, [vp, vp, i64, i64, C.c_uint32, i64, ci, ci, ci, ci, vp, vp, vp, i64, C.POINTER(i64),
+                                                           C.POINTER(i64), ci, vp]),
     "latok_idf_create": (ci, [i64, C.POINTER(vp)]),
     "latok_idf_destroy": (ci, [vp]),
     "latok_idf_clear": (ci, [vp]),

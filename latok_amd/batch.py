@@ -858,6 +858,21 @@ def _ngram_spec(ngram_range, sep):
     return None if (min_n, max_n) == (1, 1) else (min_n, max_n, sep)
 
 
+def _analyzer_spec(analyzer, ngram_range, sep, pad):
+    """What the term counts count: ``analyzer="word"`` gives _ngram_spec (None: the plain term counts), ``"char_wb"`` gives
+    ("char_wb", min_n, max_n, pad byte) -- character n-grams inside every token's padded word, ``ngram_range`` the character range
+    ((1, 1) is a real request there) and ``sep`` ignored.  Anything else is a ValueError (raised before any device is asked for)."""
+    if isinstance(analyzer, str) and analyzer == "word":
+        return _ngram_spec(ngram_range, sep)
+    if not (isinstance(analyzer, str) and analyzer == "char_wb"):
+        raise ValueError('analyzer must be "word" or "char_wb"')
+    if not (isinstance(pad, (bytes, bytearray)) and len(pad) == 1) and not (
+            isinstance(pad, (int, np.integer)) and not isinstance(pad, bool) and 0 <= int(pad) <= 255):
+        raise ValueError("pad must be one byte (bytes of length 1, or an int 0..255)")
+    _ngram_spec(ngram_range, b" ")   # (the range check)
+    return "char_wb", int(ngram_range[0]), int(ngram_range[1]), pad[0] if isinstance(pad, (bytes, bytearray)) else int(pad)
+
+
 def _rows_csr(utf8, byte_off, fold, dtype, hashed, data_dtype, entry):
     """The sized CSR families (term counts, TF-IDF) on either batch: the size query, then the fill -> (indptr, indices, data, oov or
     None).  ``entry(b, indptr, oov, indices, data, cap, nnz, flags)`` is the library call on batch ``b``."""
@@ -874,8 +889,16 @@ def _rows_csr(utf8, byte_off, fold, dtype, hashed, data_dtype, entry):
 
 
 def _terms_call(b, ng, hashed, vocab, indptr, oov, indices, data, cap, nnz, flags):
-    """one call of the term counts: the n-gram entry points when ``ng`` is set, else the existing ones exactly as they were"""
+    """one call of the term counts: the n-gram entry points when ``ng`` is set (the character n-gram ones when it is a "char_wb"
+    spec), else the existing ones exactly as they were"""
     lib, batch = b.lib, (b.u8, b.off, b.n_str, b.total)
+    if ng and ng[0] == "char_wb":
+        if hashed:
+            seed, n_features, alternate_sign = hashed
+            return lib.latok_hashed_chargram_counts_utf8_bytes_batch(*batch, seed, n_features, 1 if alternate_sign else 0, ng[1], ng[2], ng[3],
+                                                                     indptr, indices, data, cap, C.byref(nnz), None, flags, None)
+        return lib.latok_chargram_counts_utf8_bytes_batch(*batch, vocab, ng[1], ng[2], ng[3], indptr, oov, indices, data, cap, C.byref(nnz), None,
+                                                          flags, None)
     if hashed:
         seed, n_features, alternate_sign = hashed
         if ng:
@@ -895,7 +918,7 @@ def _terms_csr(utf8, byte_off, vocab, hashed, dtype, ng=None, fold=0):
     return _rows_csr(utf8, byte_off, fold, dtype, hashed, np.int32, lambda b, *out: _terms_call(b, ng, hashed, vocab, *out))
 
 
-def term_counts_utf8_csr(utf8, byte_off, vocab, dtype=np.int64, ngram_range=(1, 1), sep=b" "):
+def term_counts_utf8_csr(utf8, byte_off, vocab, dtype=np.int64, ngram_range=(1, 1), sep=b" ", analyzer="word", pad=b" "):
     """(indptr[n + 1], indices int32[nnz], data int32[nnz], oov[n]): the term counts of every string against ``vocab`` as a
     canonical CSR matrix -- row s holds the distinct vocabulary ids of its tokens (the byte slices token_spans_utf8_bytes_csr
     reports), ascending, each with its count; ``oov[s]`` counts the tokens the vocabulary does not hold.  What
@@ -904,50 +927,60 @@ def term_counts_utf8_csr(utf8, byte_off, vocab, dtype=np.int64, ngram_range=(1, 
     ``ngram_range=(min_n, max_n)`` (up to (8, 8)) counts word n-grams instead: every run of n neighbouring tokens of a string joined by the one-byte ``sep``, for every n
     in the range, looked up or hashed as one term -- scikit-learn's ``ngram_range`` (``latok_ngram_counts_utf8_bytes_batch`` /
     ``latok_hashed_ngram_counts_utf8_bytes_batch``); (1, 1) takes the plain calls.
-    A vocabulary word may hold the separator (``b"new york"``)."""
-    return _terms_csr(utf8, byte_off, _handle_of(Vocab, vocab, "vocab"), None, dtype, _ngram_spec(ngram_range, sep))
+    A vocabulary word may hold the separator (``b"new york"``).
+    ``analyzer="char_wb"`` counts character n-grams inside tokens instead (scikit-learn's analyzer of that name over
+    ``" ".join(tokens)``): every token is padded with the one-byte ``pad`` on both sides, ``ngram_range`` is the range in CHARACTERS
+    (a character starts at every byte that is no UTF-8 continuation byte; (1, 1) is a real request), a padded word shorter than n
+    counts once, and ``sep`` is ignored (``latok_chargram_counts_utf8_bytes_batch`` / ``latok_hashed_chargram_counts_utf8_bytes_batch``).
+    A vocabulary word may hold the pad (``b" th"``).  ``analyzer="word"`` is the default; anything else is a ValueError."""
+    return _terms_csr(utf8, byte_off, _handle_of(Vocab, vocab, "vocab"), None, dtype, _analyzer_spec(analyzer, ngram_range, sep, pad))
 
 
-def term_counts_utf8_batch(blobs, vocab, fold=0, ngram_range=(1, 1), sep=b" "):
+def term_counts_utf8_batch(blobs, vocab, fold=0, ngram_range=(1, 1), sep=b" ", analyzer="word", pad=b" "):
     """list[bytes] (UTF-8) -> (indptr, indices, data, oov) of term_counts_utf8_csr, int64 ('' and whitespace-only -> empty rows).
     ``fold`` (FOLD_* flags): the batch is folded on the device first (fold_utf8_batch) -- ``CountVectorizer(lowercase=True)`` is
-    ``FOLD_LOWER``, ``strip_accents="unicode"`` adds ``FOLD_STRIP_MARKS``.  ``ngram_range``, ``sep``: as in term_counts_utf8_csr; the
-    grams are those of the folded strings."""
-    handle, fold, ng = _handle_of(Vocab, vocab, "vocab"), _fold_bits(fold), _ngram_spec(ngram_range, sep)
+    ``FOLD_LOWER``, ``strip_accents="unicode"`` adds ``FOLD_STRIP_MARKS``.  ``ngram_range``, ``sep``, ``analyzer``, ``pad``: as in
+    term_counts_utf8_csr; the grams are those of the folded strings."""
+    handle, fold, ng = _handle_of(Vocab, vocab, "vocab"), _fold_bits(fold), _analyzer_spec(analyzer, ngram_range, sep, pad)
     utf8, byte_off = pack_utf8(blobs)
     return _terms_csr(utf8, byte_off, handle, None, np.int64, ng, fold)
 
 
-def term_counts_batch(texts, vocab, ngram_range=(1, 1), sep=b" "):
+def term_counts_batch(texts, vocab, ngram_range=(1, 1), sep=b" ", analyzer="word", pad=b" "):
     """list[str] -> (indptr, indices, data, oov): per string ``Counter(d[t] for t in tokenize(text) if t in d)`` with sorted keys,
     d = the vocabulary as a dict; oov = the tokens not in d.  The strings go through UTF-8 ("surrogatepass") on the host.
-    ``ngram_range``, ``sep``: as in term_counts_utf8_csr."""
-    return term_counts_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], vocab, ngram_range=ngram_range, sep=sep)
+    ``ngram_range``, ``sep``, ``analyzer``, ``pad``: as in term_counts_utf8_csr."""
+    return term_counts_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], vocab, ngram_range=ngram_range, sep=sep, analyzer=analyzer,
+                                  pad=pad)
 
 
-def hashed_term_counts_utf8_csr(utf8, byte_off, n_features=1 << 20, seed=0, alternate_sign=True, dtype=np.int64, ngram_range=(1, 1), sep=b" "):
+def hashed_term_counts_utf8_csr(utf8, byte_off, n_features=1 << 20, seed=0, alternate_sign=True, dtype=np.int64, ngram_range=(1, 1), sep=b" ",
+                                analyzer="word", pad=b" "):
     """(indptr[n + 1], indices int32[nnz], data int32[nnz]): the hashed term counts of every string as a canonical CSR matrix --
     column = ``abs(h) % n_features``, value = ``+1`` or (``alternate_sign`` and h < 0) ``-1``, h = MurmurHash3 x86_32 of the token's
     bytes with ``seed`` as int32; a row's columns ascend and a sum may be an explicit 0.  What ``HashingVectorizer(norm=None)
     .transform`` returns: ``scipy.sparse.csr_matrix((data, indices, indptr), shape=(n, n_features))``.  indptr in ``dtype``.  Cut,
     hashed, sorted and reduced on the device (``latok_hashed_term_counts_utf8_bytes_batch``).  ``ngram_range``, ``sep``: word n-grams,
-    as in term_counts_utf8_csr."""
-    return _terms_csr(utf8, byte_off, None, (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), dtype, _ngram_spec(ngram_range, sep))[:3]
+    ``analyzer="char_wb"``, ``pad``: character n-grams inside tokens, as in term_counts_utf8_csr."""
+    return _terms_csr(utf8, byte_off, None, (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), dtype,
+                      _analyzer_spec(analyzer, ngram_range, sep, pad))[:3]
 
 
-def hashed_term_counts_utf8_batch(blobs, n_features=1 << 20, seed=0, alternate_sign=True, fold=0, ngram_range=(1, 1), sep=b" "):
+def hashed_term_counts_utf8_batch(blobs, n_features=1 << 20, seed=0, alternate_sign=True, fold=0, ngram_range=(1, 1), sep=b" ", analyzer="word",
+                                  pad=b" "):
     """list[bytes] (UTF-8) -> (indptr, indices, data) of hashed_term_counts_utf8_csr, int64.  ``fold`` (FOLD_* flags): the batch is
-    folded on the device first (fold_utf8_batch); ``HashingVectorizer`` lower-cases by default: ``FOLD_LOWER``.  ``ngram_range``, ``sep``:
-    as in hashed_term_counts_utf8_csr; the grams are those of the folded strings."""
-    hashed, fold, ng = (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), _fold_bits(fold), _ngram_spec(ngram_range, sep)
+    folded on the device first (fold_utf8_batch); ``HashingVectorizer`` lower-cases by default: ``FOLD_LOWER``.  ``ngram_range``, ``sep``,
+    ``analyzer``, ``pad``: as in hashed_term_counts_utf8_csr; the grams are those of the folded strings."""
+    hashed, fold = (_seed32(seed), _n_features31(n_features), bool(alternate_sign)), _fold_bits(fold)
+    ng = _analyzer_spec(analyzer, ngram_range, sep, pad)
     utf8, byte_off = pack_utf8(blobs)
     return _terms_csr(utf8, byte_off, None, hashed, np.int64, ng, fold)[:3]
 
 
-def hashed_term_counts_batch(texts, n_features=1 << 20, seed=0, alternate_sign=True, ngram_range=(1, 1), sep=b" "):
+def hashed_term_counts_batch(texts, n_features=1 << 20, seed=0, alternate_sign=True, ngram_range=(1, 1), sep=b" ", analyzer="word", pad=b" "):
     """list[str] -> (indptr, indices, data): hashed_term_counts_utf8_batch of the strings' UTF-8 ("surrogatepass")."""
     return hashed_term_counts_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], n_features, seed, alternate_sign, ngram_range=ngram_range,
-                                         sep=sep)
+                                         sep=sep, analyzer=analyzer, pad=pad)
 
 
 # TF-IDF: document frequencies over many batches and the float32 weighting of the CSR rows, on the device -- TfidfVectorizer's last step

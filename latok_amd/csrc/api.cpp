@@ -32,6 +32,7 @@
 #include "kernels.h"
 #include "unicode_tables.inc"
 #include "vocab_table.h"
+#include "chargram_text.h"
 #include "ngram_text.h"
 #include "count_table.h"
 #include "wordpiece.h"
@@ -2558,6 +2559,8 @@ struct TermsCall {                 // one blocking call of the term family: what
     int alternate_sign = 0;
     bool ngrams = false;           // word n-grams (enqueue_ngram_counts): the orders and the separator byte; pinned word 5 = K
     int min_n = 1, max_n = 1, sep = 0x20;
+    bool chargrams = false;        // character n-grams inside tokens (enqueue_chargram_counts): the orders and the pad byte; pinned word 5 = K
+    int pad = 0x20;
     bool tfidf = false, update = false;   // the TF-IDF tail behind the counts: the weighting of the rows, or (update) the update of idf
     Idf* idf = nullptr;            // may be NULL (weighting without idf)
     int opts = 0;
@@ -2674,6 +2677,61 @@ static int enqueue_ngram_counts(Ctx& g, Workspace& w, TermsCall& a) {
     return LATOK_OK;
 }
 
+/* Character n-grams inside tokens (latok_chargram_counts_utf8_bytes_batch, latok_hashed_chargram_counts_utf8_bytes_batch): one key per
+ * gram of every token's padded word (chargram_text.h), then the term counts' own sort and reduce with the row starts in KEY space.  One
+ * stream, every batch size the same kernels:
+ *   sized_token_front (wait 1)                    kept mask, token ranks; the host reads THE token total (pinned word 0): the per-token buffers are sized
+ *   enqueue_token_rows                            the span record of every token at its rank in the workspace, the row starts in token space
+ *   k_cgram_count + k_scan_chained                grams per token, each token's key rank; the key total K -> pinned word 5
+ *   k_wp_rows                                     the row starts in key space: the key rank of every string's first token
+ *   (wait 2)                                      the host reads K: 2^31 or more is refused, the two key buffers are sized
+ *   k_cgram_keys                                  one term key per gram inside its token's range of keys
+ *   enqueue_csr_tail, k_terms_finish              as enqueue_term_counts, with the key rows and K in the place of the token rows
+ *   (wait 3)                                      nnz; host pointers then copy nnz entries (wait 4)
+ * The buffers are those the WordPiece and n-gram calls keep: span records, per-token count and rank, the key-space rows, the keys. */
+static int enqueue_chargram_counts(Ctx& g, Workspace& w, TermsCall& a) {
+    int rc;
+    const hipStream_t st = a.st;
+    const int64_t total = a.b.total, n_str = a.b.n_str;
+    int* d_err = (int*)(a.p_tot + 1);
+    latok::TokenPlanes t;
+    if ((rc = sized_token_front(g, w, a.b, a.p_tot, a.h_tot, st, kTooManyTermTokens, &t, &a.n_tokens))) return rc;
+    const int64_t n_tok = a.n_tokens;
+    WsShape shape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok, .ng_rows = n_str + 1};
+    if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, shape).data(), kWsNeeds))) return rc;
+    const TermRows r(w, n_str);                                // token space: counts, row starts
+    int64_t* d_kstart = (int64_t*)w.ngrows.p + (n_str + 1);    // key space: row starts
+    int64_t* d_gcnt = (int64_t*)w.wpcnt.p;                     // per token: grams, key rank (n_tok + 1 entries)
+    int64_t* d_grank = (int64_t*)w.wprank.p;
+    HIP_TRY(hipMemsetAsync(r.cnt, 0, r.bytes, st));   // (no gram: every row is empty, nnz = 0)
+    if (n_tok > 0) {
+        const uint8_t* u8 = (const uint8_t*)a.b.in.p;
+        const int64_t* d_tspans = (const int64_t*)w.wpspans.p;
+        if ((rc = enqueue_token_rows(w, a.b, t, n_tok, r.cnt, r.start, d_err, st))) return rc;
+        HIP_TRY(latok::launch_cgram_count(u8, total, a.b.row, n_str, r.start, d_tspans, n_tok, a.min_n, a.max_n, d_gcnt, st));
+        if ((rc = enqueue_row_scan(w, d_gcnt, n_tok + 1, d_grank, (int64_t*)w.scalar.p + 6, a.p_tot + 5, d_err + 1, st))) return rc;
+        HIP_TRY(latok::launch_wp_rows(false, r.start, d_grank, n_str, n_tok, d_kstart, st));
+        HIP_TRY(hipStreamSynchronize(st));   // wait 2: the key total decides whether the call goes on and what the keys take
+        int64_t n_tok_again = 0;
+        if ((rc = finish_totals(w, a.h_tot, 0, &n_tok_again))) return rc;
+        const int64_t n_keys = a.h_tot[5];
+        a.n_grams = n_keys;
+        if (n_keys >= (1ll << 31))
+            return fail(LATOK_ERR_INVALID, "the batch has %lld character n-grams: term counts are int32 (fewer than 2^31 grams a call)", (long long)n_keys);
+        if (n_keys > 0) {
+            shape.ng_keys = n_keys;
+            if ((rc = ws_ensure(ws_needs(w, total, shape).data(), kWsNeeds))) return rc;   // (only the key buffers grow)
+            latok::VocabTable vt;
+            if (a.v) vt = a.v->table.view(a.v->seed);
+            HIP_TRY(latok::launch_cgram_keys(u8, total, a.b.row, n_str, r.start, d_grank, d_tspans, n_tok, n_keys, a.min_n, a.max_n, a.pad,
+                                             a.v ? &vt : nullptr, a.seed, (uint32_t)a.n_features, a.alternate_sign != 0, (uint64_t*)w.tkeys.p, st));
+            if ((rc = enqueue_csr_tail(w, a, r, d_kstart, n_keys))) return rc;
+        }
+    }
+    HIP_TRY(latok::launch_terms_finish(a.o32, r.indptr, r.oov, n_str, a.indptr, a.oov, st));
+    return LATOK_OK;
+}
+
 // The argument refusals, none of which touches the device: first those that write nothing, then, behind need_init and with the
 // out-pointers zeroed, the checks of the ids call and the capacity protocol in entries.
 static int terms_refusals(const Ctx& g, TermsCall& a) {
@@ -2686,11 +2744,12 @@ static int terms_refusals(const Ctx& g, TermsCall& a) {
         if (a.idf && a.hashed && a.n_features != a.idf->n_cols)
             return fail(LATOK_ERR_INVALID, "n_features is %lld, the idf has %lld columns", (long long)a.n_features, (long long)a.idf->n_cols);
     }
-    if (a.ngrams) {
+    if (a.ngrams || a.chargrams) {
         if (a.min_n < 1) return fail(LATOK_ERR_INVALID, "min_n must be at least 1");
         if (a.max_n < a.min_n) return fail(LATOK_ERR_INVALID, "max_n must not be below min_n");
         if (a.max_n > kNgMax) return fail(LATOK_ERR_INVALID, "max_n must not exceed %d", kNgMax);
-        if (a.sep < 0 || a.sep > 255) return fail(LATOK_ERR_INVALID, "sep must be one byte: 0 .. 255");
+        if (a.ngrams && (a.sep < 0 || a.sep > 255)) return fail(LATOK_ERR_INVALID, "sep must be one byte: 0 .. 255");
+        if (a.chargrams && (a.pad < 0 || a.pad > 255)) return fail(LATOK_ERR_INVALID, "pad must be one byte: 0 .. 255");
     }
     if ((rc = need_init(g))) return rc;
     if (!a.nnz_out) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
@@ -2710,8 +2769,9 @@ static int terms_stage_outputs(Ctx& g, TermsCall& a, const BytesCall& c) {
     int rc;
     const int64_t n_str = c.d.n_str;
     a.b = c.d;
-    // (an entry has at least one token, a token one byte: the staging is sized by it; a token starts one gram of every order at most)
-    const int64_t most = c.total * (a.ngrams ? a.max_n - a.min_n + 1 : 1);
+    // (an entry has at least one token, a token one byte: the staging is sized by it; a token starts one gram of every order at most;
+    // a token of b >= 1 bytes has at most b + 2 <= 3 b padded characters, each of which starts one character gram of every order at most)
+    const int64_t most = a.chargrams ? 3 * c.total * (a.max_n - a.min_n + 1) : c.total * (a.ngrams ? a.max_n - a.min_n + 1 : 1);
     a.fill_cap = a.update ? most : a.indices_out ? std::min(a.cap, most) : 0;
     a.o32 = c.o32;
     const bool own = !c.dev || a.update;   // a host call's outputs, and every update's, land in the context's own buffers
@@ -2798,13 +2858,14 @@ static int term_counts_common(TermsCall a) {
     }
     if (c.dev && (((uintptr_t)a.oov_out & (c.elt - 1)) != 0 || ((uintptr_t)a.indices_out & 3) != 0 || ((uintptr_t)a.data_out & 3) != 0))
         return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    const WsShape shape{.spans = true, .term_rows = n_str + 1, .ng_rows = a.ngrams ? n_str + 1 : 0, .tf_ctl = a.tfidf};
-    const int route = a.ngrams ? (a.hashed ? 15 : 14) : (a.hashed ? 10 : 9);
-    if ((rc = c.stage(g, route, shape, (a.ngrams ? kClearNgrams : kClearSized) | (a.tfidf ? kClearTfidfErr : 0u)))) return rc;
+    const bool grams = a.ngrams || a.chargrams;   // the routes whose rows lie in key space
+    const WsShape shape{.spans = true, .term_rows = n_str + 1, .ng_rows = grams ? n_str + 1 : 0, .tf_ctl = a.tfidf};
+    const int route = a.chargrams ? (a.hashed ? 17 : 16) : a.ngrams ? (a.hashed ? 15 : 14) : (a.hashed ? 10 : 9);
+    if ((rc = c.stage(g, route, shape, (grams ? kClearNgrams : kClearSized) | (a.tfidf ? kClearTfidfErr : 0u)))) return rc;
     if ((rc = terms_stage_outputs(g, a, c))) return rc;
-    if ((rc = a.ngrams ? enqueue_ngram_counts(g, g.ws, a) : enqueue_term_counts(g, g.ws, a))) return rc;
+    if ((rc = a.chargrams ? enqueue_chargram_counts(g, g.ws, a) : a.ngrams ? enqueue_ngram_counts(g, g.ws, a) : enqueue_term_counts(g, g.ws, a))) return rc;
     // (no key: the scan did not run and nnz = 0)
-    if (a.tfidf && a.indices && (a.ngrams ? a.n_grams : a.n_tokens) > 0 && (rc = enqueue_tfidf_tail(g, a))) return rc;
+    if (a.tfidf && a.indices && (grams ? a.n_grams : a.n_tokens) > 0 && (rc = enqueue_tfidf_tail(g, a))) return rc;
     return terms_deliver(g, a, c);
 }
 int latok_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
@@ -2822,6 +2883,23 @@ int latok_hashed_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_
                                .n_features = n_features, .alternate_sign = alternate_sign, .ngrams = true, .min_n = min_n, .max_n = max_n, .sep = sep,
                                .indptr_out = indptr_out, .indices_out = indices_out, .data_out = data_out, .cap = cap, .nnz_out = nnz_out,
                                .n_grams_out = n_grams_out, .flags = flags, .stream = stream});
+}
+int latok_chargram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
+                                           int min_n, int max_n, int pad, int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out,
+                                           int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_grams_out, int flags, void* stream) {
+    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .vocab = vocab, .min_n = min_n,
+                               .max_n = max_n, .chargrams = true, .pad = pad, .indptr_out = indptr_out, .oov_out = oov_out,
+                               .indices_out = indices_out, .data_out = data_out, .cap = cap, .nnz_out = nnz_out, .n_grams_out = n_grams_out,
+                               .flags = flags, .stream = stream});
+}
+int latok_hashed_chargram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, uint32_t seed,
+                                                  int64_t n_features, int alternate_sign, int min_n, int max_n, int pad, int64_t* indptr_out,
+                                                  int32_t* indices_out, int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_grams_out,
+                                                  int flags, void* stream) {
+    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .hashed = true, .seed = seed,
+                               .n_features = n_features, .alternate_sign = alternate_sign, .min_n = min_n, .max_n = max_n, .chargrams = true,
+                               .pad = pad, .indptr_out = indptr_out, .indices_out = indices_out, .data_out = data_out, .cap = cap,
+                               .nnz_out = nnz_out, .n_grams_out = n_grams_out, .flags = flags, .stream = stream});
 }
 int latok_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
                                        int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out, int32_t* data_out, int64_t cap,
@@ -4043,6 +4121,15 @@ extern "C" int latok_debug_terms_limits(int64_t* out, int n) {
     return k;
 }
 
+/* test hook (not part of the ABI; needs no device): the constants of the character n-gram calls: out[0] = kCgBlock (tokens per
+ * workgroup of k_cgram_count / k_cgram_keys), out[1] = kNgMax (the highest order).  Returns the number of values written. */
+extern "C" int latok_debug_chargram_limits(int64_t* out, int n) {
+    const int64_t v[2] = {latok::kCgBlock, kNgMax};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 2 ? n : 2;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
 /* test hook (not part of the ABI; needs no device): the constants of the n-gram calls: out[0] = kNgBlock (tokens per workgroup of
  * k_ngram_keys), out[1] = kNgMax (the highest order).  Returns the number of values written. */
 extern "C" int latok_debug_ngram_limits(int64_t* out, int n) {
@@ -4226,7 +4313,8 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
  * 6: token hashes of UTF-8 in byte space (every batch size as well); 7: token ids of UTF-8 in byte space (likewise);
  * 9 / 10: term counts of UTF-8 in byte space, vocabulary form / hashed form (likewise);
  * 11 / 12: WordPiece ids of UTF-8 in byte space, CSR form / padded form (likewise);
- * 13: case folding of UTF-8 in byte space (likewise) */
+ * 13: case folding of UTF-8 in byte space (likewise); 14 / 15: word n-gram counts, vocabulary form / hashed form (likewise);
+ * 16 / 17: character n-gram counts inside tokens, vocabulary form / hashed form (likewise) */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;

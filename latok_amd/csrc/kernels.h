@@ -398,6 +398,18 @@ hipError_t launch_ngram_rows(const int64_t* tok_cnt, int64_t n_str, int min_n, i
 hipError_t launch_ngram_keys(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
                              const int64_t* key_start, const int64_t* tok_spans, int64_t n_tok, int64_t n_keys, int min_n, int max_n, int sep,
                              const VocabTable* vt, uint32_t seed, uint32_t n_features, bool alternate_sign, uint64_t* keys, hipStream_t st);
+// character n-grams inside tokens (chargram_kernels.hip, chargram_text.h), in token space, one lane per token: behind kind 1 of
+// launch_counts_scatter and the scan of the token counts, as WordPiece.  launch_cgram_count leaves the grams G(W) of every token in
+// cnt[0 .. n_tok) and 0 in cnt[n_tok]; the caller scans the n_tok + 1 entries into rank[] (rank[n_tok] = the key total) and takes the
+// row starts in key space from launch_wp_rows.  launch_cgram_keys stores one term key (term_key.h) per gram of the orders min_n ..
+// max_n inside its token's range of `keys`, which holds n_keys keys: vt == NULL the hashed form, else the lookup of the gram's bytes
+// (pad included) in the table.  launch_terms_reduce / _emit / _finish then take keys and the key-space row starts.
+constexpr int kCgBlock = 256;   // tokens per workgroup of k_cgram_count / k_cgram_keys (latok_debug_chargram_limits)
+hipError_t launch_cgram_count(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
+                              const int64_t* tok_spans, int64_t n_tok, int min_n, int max_n, int64_t* cnt, hipStream_t st);
+hipError_t launch_cgram_keys(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
+                             const int64_t* rank, const int64_t* tok_spans, int64_t n_tok, int64_t n_keys, int min_n, int max_n, int pad,
+                             const VocabTable* vt, uint32_t seed, uint32_t n_features, bool alternate_sign, uint64_t* keys, hipStream_t st);
 // tfidf_kernels.hip: TF-IDF on a CSR in device memory (tfidf_weight.h).  indptr is int32 (ip32) or int64; nnz_dev != NULL: the entry
 // count is the scan's own word, not yet read by the host -- the kernels then do nothing when it exceeds `cap`, what the buffers hold
 // (launch_terms_emit's rule), and `nnz` is ignored.  launch_csr_check ORs kCsrBad* bits into *err (indptr == NULL: the columns alone;

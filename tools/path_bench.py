@@ -45,6 +45,11 @@
                   range (1, 2) and the separator 0x20, everything else as bytes_terms32 / bytes_terms_hashed (the vocabulary of the ids
                   paths holds single tokens only, so every bigram's probe ends in a miss); capacity = twice the token bound; same
                   process run as bytes_terms32, bytes_terms_hashed and bytes_spans32
+  bytes_chargrams32 / bytes_chargrams_hashed   latok_chargram_counts_utf8_bytes_batch / latok_hashed_chargram_counts_utf8_bytes_batch with
+                  the character range (3, 5) and the pad 0x20, everything else as bytes_terms32 / bytes_terms_hashed (the vocabulary of
+                  the ids paths holds whole tokens, so nearly every gram's probe ends in a miss); capacity = nnz of a size query, which
+                  also prints one line with the token total, the gram total K and nnz; same process run as bytes_terms32,
+                  bytes_terms_hashed, bytes_ngrams_hashed and bytes_spans32
   bytes_tfidf32 / bytes_tfidf_hashed   latok_tfidf_utf8_bytes_batch / latok_hashed_tfidf_utf8_bytes_batch with range (1, 1), L2, smooth
                   idf and an idf fitted on the corpus by one update call; everything else as bytes_terms32 / bytes_terms_hashed -- run
                   them in the same process: the ratio of the two times is what the weighting costs
@@ -418,7 +423,7 @@ def main():
     join_leg = [p for p in paths if p in ("bytes_join", "bytes_join_flow", "bytes_spans32", "bytes_spans32_flow", "bytes_hashes32",
                                           "bytes_hashes32_flow", "bytes_hashes_only", "bytes_hashes_only_flow", "bytes_ids32", "bytes_ids32_flow",
                                           "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "bytes_ngrams32", "bytes_ngrams_hashed", "py_terms",
-                                          "bytes_tfidf32", "bytes_tfidf_hashed", "bytes_df_update", "csr_tfidf", "csr_df", "py_tfidf",
+                                          "bytes_chargrams32", "bytes_chargrams_hashed", "bytes_tfidf32", "bytes_tfidf_hashed", "bytes_df_update", "csr_tfidf", "csr_df", "py_tfidf",
                                           "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join", "bytes_wp32", "bytes_wp_padded", "py_wp",
                                           "bytes_fold", "bytes_fold_wp", "py_fold")]
     if join_leg:
@@ -542,6 +547,41 @@ def main():
                                                                       C.byref(nout), None, D32, None)
             return lib.latok_ngram_counts_utf8_bytes_batch(d_u8, d_boff, n, n8, corpus_vocab().handle, 1, 2, 32, g_indptr, g_oov, g_a, g_b, 2 * cap,
                                                            C.byref(nout), None, D32, None)
+
+        note_cg = ("as bytes_terms32 / bytes_terms_hashed with one key per character gram of the orders 3 .. 5 of every token's padded word: "
+                   "16 B/token span records, 8 B/token gram counts and 8 B/token key ranks written and read, the bytes of every token read by "
+                   "the walk from each of its characters; 8 B/gram keys written, read by the sort and written back; 4 B/string indptr "
+                   "(+ 4 B/string oov) and 8 B/entry written (--vocab " + args.vocab + " / 2^20 features)")
+        chargrams_box = {}
+
+        def chargrams_call(hashed, indices, data, cap_, n_grams=None):
+            g_indptr, g_oov = chargrams_box["rows"]
+            if hashed:
+                return lib.latok_hashed_chargram_counts_utf8_bytes_batch(d_u8, d_boff, n, n8, SEED, 1 << 20, 1, 3, 5, 32, g_indptr, indices, data, cap_,
+                                                                         C.byref(nout), n_grams, D32, None)
+            return lib.latok_chargram_counts_utf8_bytes_batch(d_u8, d_boff, n, n8, corpus_vocab().handle, 3, 5, 32, g_indptr, g_oov, indices, data, cap_,
+                                                              C.byref(nout), n_grams, D32, None)
+
+        def chargrams_blocking(hashed):
+            if "rows" not in chargrams_box:
+                chargrams_box["rows"] = [lib.latok_dev_alloc(sz) for sz in ((n + 1) * 4 + 64, n * 4 + 64)]
+                if not all(chargrams_box["rows"]):
+                    raise RuntimeError(_lib.last_error())
+            if hashed not in chargrams_box:   # the size query: K and nnz of the workload, one line; then buffers of exactly nnz entries
+                k = C.c_int64(0)
+                chargrams_call(hashed, None, None, 0, C.byref(k))
+                need = nout.value
+                n_tok = C.c_int64(0)   # (a size query of the plain counts: the token total of the same batch)
+                lib.latok_hashed_term_counts_utf8_bytes_batch(d_u8, d_boff, n, n8, SEED, 1 << 20, 1, chargrams_box["rows"][0], None, None, 0,
+                                                              C.byref(nout), C.byref(n_tok), D32, None)
+                print(json.dumps({"chargrams": "hashed" if hashed else "vocab", "workload": args.workload, "strings": n, "utf8_bytes": n8,
+                                  "range": [3, 5], "pad": 32, "tokens": n_tok.value, "n_grams": k.value, "nnz": need}), flush=True)
+                bufs = [lib.latok_dev_alloc(need * 4 + 64), lib.latok_dev_alloc(need * 4 + 64)]
+                if not all(bufs):
+                    raise RuntimeError(_lib.last_error())
+                chargrams_box[hashed] = bufs + [need]
+            g_a, g_b, need = chargrams_box[hashed]
+            return chargrams_call(hashed, g_a, g_b, need)
 
         note_w = ("UTF-8 bytes + 8 B/string read; 4 B/string indptr + 4 B/piece ids + 8 B/piece spans written (--vocab " + args.vocab + "). NOT "
                   "counted: the workspace traffic (16 B/token span records, 8 B/token piece counts, 8 B/token piece ranks, each written "
@@ -882,6 +922,9 @@ def main():
             elif name in ("bytes_ngrams32", "bytes_ngrams_hashed"):   # (items = nnz; the keys are sized by the gram total)
                 hashed = name == "bytes_ngrams_hashed"
                 run(name, lambda: ngrams_blocking(hashed), lambda: n8 + csr + 4 * n + (0 if hashed else 4 * n) + 8 * nout.value, note_g)
+            elif name in ("bytes_chargrams32", "bytes_chargrams_hashed"):   # (items = nnz; the keys are sized by the gram total K)
+                hashed = name == "bytes_chargrams_hashed"
+                run(name, lambda: chargrams_blocking(hashed), lambda: n8 + csr + 4 * n + (0 if hashed else 4 * n) + 8 * nout.value, note_cg)
             elif name == "py_terms":   # host blobs in, the CSR arrays out, both routes in this process
                 import collections
                 from latok_amd import batch
@@ -999,7 +1042,7 @@ def main():
                 lib.latok_dev_free(p_)
         for f_ in tfidf_box.values():
             f_.close()
-        for p_ in terms_box + ngrams_box + tfidf_bufs:
+        for p_ in terms_box + ngrams_box + tfidf_bufs + [q for v_ in chargrams_box.values() for q in v_[:2]]:
             lib.latok_dev_free(p_)
         for p_ in jb:
             lib.latok_dev_free(p_)
