@@ -1762,10 +1762,23 @@ static int sized_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* p_to
 }
 // The token rows of the n-gram and WordPiece calls, behind sized_token_front (n_tok > 0, w.wpspans sized for it): the span record of
 // every token at its rank (k_counts_scatter, kind 1, int64) into w.wpspans, the token count of every string into d_cnt (n_str + 1,
-// cleared by the caller) and the row starts in token space into d_start (k_scan_chained; the total -> scalar word 4).
-static int enqueue_token_rows(Workspace& w, const Batch& b, const latok::TokenPlanes& t, int64_t n_tok, int64_t* d_cnt, int64_t* d_start, int* d_err, hipStream_t st) {
+// cleared by the caller) and the row starts in token space into d_start (k_scan_chained; the total -> scalar word 4).  *text = the
+// batch in token space, for the kernels that take one token per lane.
+static int enqueue_token_rows(Workspace& w, const Batch& b, const latok::TokenPlanes& t, int64_t n_tok, int64_t* d_cnt, int64_t* d_start, int* d_err,
+                              hipStream_t st, latok::TokenText* text) {
     HIP_TRY(latok::launch_counts_scatter(1, false, t, (int64_t*)w.wpspans.p, n_tok, d_cnt, d_err, st));
+    *text = {(const uint32_t*)b.in.p, b.total, b.row, b.n_str, d_start, (const int64_t*)w.wpspans.p, n_tok};
     return enqueue_row_scan(w, d_cnt, b.n_str + 1, d_start, (int64_t*)w.scalar.p + 4, nullptr, d_err + 1, st);
+}
+// "Wait 2" of a sized call whose second total sizes buffers: the wait, the scan's own flag, then the total that the stream left in
+// pinned word `word`; 2^31 or more is refused in the caller's words (`too_many`, one %lld; NULL: the caller refuses it itself).
+static int second_sized_total(Workspace& w, const volatile int64_t* h_tot, int word, hipStream_t st, const char* too_many, int64_t* out) {
+    int rc;
+    HIP_TRY(hipStreamSynchronize(st));   // the total decides whether the call goes on and what its buffers take
+    if ((rc = finish_totals(w, h_tot, 0, out))) return rc;   // (leaves the token total again, which wait 1 has delivered)
+    *out = h_tot[word];
+    if (too_many && *out >= (1ll << 31)) return fail(LATOK_ERR_INVALID, too_many, (long long)*out);
+    return LATOK_OK;
 }
 
 // Token hashes and token ids of a UTF-8 batch in BYTE space (latok_token_hashes_utf8_bytes_batch, latok_token_ids_utf8_bytes_batch and
@@ -2538,16 +2551,11 @@ static int csr_refusal(int err) {
 }
 static int g_df_add_cached = 1;   // latok_debug_set_df_add: 0 = the plain k_df_add_plain (tools/path_bench.py measures both)
 
-/* Per-string term counts of a UTF-8 batch in BYTE space (latok_term_counts_utf8_bytes_batch, latok_hashed_term_counts_utf8_bytes_batch):
- * the CSR rows of a document-term matrix.  One stream, every batch size the same kernels:
- *   sized_token_front (wait 1)                    kept mask, token ranks; the host reads THE token total (pinned word 0): the key buffers are sized
- *   k_term_scatter                                one term key per token at its rank (term_key.h), int64 token count per string
- *   k_scan_chained                                the row starts in token space
- *   enqueue_csr_tail: k_terms_tile, k_terms_long  sort and reduce inside every string: distinct and OOV counts, the entries
- *     k_scan_chained, k_terms_emit                indptr, nnz -> pinned word 3; indices / data if nnz fits the capacity
- *   k_terms_finish                                indptr / oov in the caller's width
- *   (wait 2)                                      nnz; host pointers then copy nnz entries (wait 3)
- * `w` was sized by ws_needs with WsShape{.spans = true, .term_rows = n_str + 1}; the call sizes the key buffers itself. */
+/* The term family: per-string counts of a UTF-8 batch in BYTE space, the CSR rows of a document-term matrix, with one key per token
+ * (latok_term_counts_*, latok_hashed_term_counts_*), per word n-gram (latok_ngram_counts_*, latok_hashed_ngram_counts_*) or per character
+ * n-gram inside a token (latok_chargram_counts_*, latok_hashed_chargram_counts_*), and the TF-IDF calls over text behind them.  One core,
+ * enqueue_term_keys, which lists what each kind launches. */
+enum class TermKind { Tokens, WordGrams, CharGrams };   // one key per token / per word n-gram / per character n-gram inside a token
 struct TermsCall {                 // one blocking call of the term family: what its entry point received ...
     const uint8_t* utf8;
     const int64_t* byte_off;
@@ -2557,10 +2565,9 @@ struct TermsCall {                 // one blocking call of the term family: what
     uint32_t seed = 0;
     int64_t n_features = 0;
     int alternate_sign = 0;
-    bool ngrams = false;           // word n-grams (enqueue_ngram_counts): the orders and the separator byte; pinned word 5 = K
-    int min_n = 1, max_n = 1, sep = 0x20;
-    bool chargrams = false;        // character n-grams inside tokens (enqueue_chargram_counts): the orders and the pad byte; pinned word 5 = K
-    int pad = 0x20;
+    TermKind kind = TermKind::Tokens;   // what a key stands for; the two gram kinds: the orders, pinned word 5 = the key total K
+    int min_n = 1, max_n = 1;
+    int sep = 0x20, pad = 0x20;    // the byte between the tokens of a word gram / around the word of a character gram
     bool tfidf = false, update = false;   // the TF-IDF tail behind the counts: the weighting of the rows, or (update) the update of idf
     Idf* idf = nullptr;            // may be NULL (weighting without idf)
     int opts = 0;
@@ -2604,130 +2611,96 @@ static int enqueue_csr_tail(Workspace& w, const TermsCall& a, const TermRows& r,
     if (a.indices) HIP_TRY(latok::launch_terms_emit(d_keys, d_starts, n_str, n_keys, r.distinct, r.indptr, d_nnz, a.fill_cap, a.indices, a.data, a.st));
     return LATOK_OK;
 }
-static int enqueue_term_counts(Ctx& g, Workspace& w, TermsCall& a) {
+// the key form of a call: the vocabulary's table and seed, or the hashed form's parameters
+static latok::TermKeyForm term_key_form(const TermsCall& a) {
+    latok::TermKeyForm f;
+    f.vocab = a.v != nullptr;
+    if (a.v) f.vt = a.v->table.view(a.v->seed);
+    f.seed = a.v ? a.v->seed : a.seed;
+    f.n_features = a.v ? 0u : (uint32_t)a.n_features;
+    f.alternate_sign = a.alternate_sign != 0;
+    return f;
+}
+/* The core of the term family.  One stream, every batch size the same kernels: the head (wait 1: the token total, pinned word 0, sizes
+ * the per-token buffers), the keys of the call's kind with their row starts, then the term counts' own sort and reduce inside every
+ * string (enqueue_csr_tail) and the rows in the caller's width (k_terms_finish, keys or none).  The two gram kinds work in token space
+ * and wait a second time (second_sized_total), for the key total K that sizes the two key buffers; their rows then lie in KEY space.
+ * `w` was sized by ws_needs with WsShape{.spans = true, .term_rows = n_str + 1} and, for the gram kinds, .ng_rows = n_str + 1; the call
+ * sizes the rest.  The gram kinds use the buffers the WordPiece calls keep: span records, per-token count and rank. */
+static int enqueue_term_keys(Ctx& g, Workspace& w, TermsCall& a) {
     int rc;
     const hipStream_t st = a.st;
     const int64_t total = a.b.total, n_str = a.b.n_str;
+    const bool words = a.kind == TermKind::WordGrams, chars = a.kind == TermKind::CharGrams;
     int* d_err = (int*)(a.p_tot + 1);
     latok::TokenPlanes t;
     if ((rc = sized_token_front(g, w, a.b, a.p_tot, a.h_tot, st, kTooManyTermTokens, &t, &a.n_tokens))) return rc;
     const int64_t n_tok = a.n_tokens;
-    if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .term_tokens = n_tok}).data(), kWsNeeds)))
-        return rc;
-    const TermRows r(w, n_str);
-    HIP_TRY(hipMemsetAsync(r.cnt, 0, r.bytes, st));   // (no token: every row is empty, nnz = 0)
-    if (n_tok > 0) {
-        latok::VocabTable vt;
-        if (a.v) vt = a.v->table.view(a.v->seed);
-        HIP_TRY(latok::launch_term_scatter(t, (const uint8_t*)a.b.in.p, a.v ? &vt : nullptr, a.seed, (uint32_t)a.n_features, a.alternate_sign != 0,
-                                           (uint64_t*)w.tkeys.p, r.cnt, d_err, st));
+    WsShape shape{.spans = true, .term_rows = n_str + 1};
+    (chars ? shape.wp_tokens : words ? shape.ng_tokens : shape.term_tokens) = n_tok;
+    if (chars || words) shape.ng_rows = n_str + 1;
+    if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, shape).data(), kWsNeeds))) return rc;
+    const TermRows r(w, n_str);                       // token space: counts, row starts
+    HIP_TRY(hipMemsetAsync(r.cnt, 0, r.bytes, st));   // (no key: every row is empty, nnz = 0)
+    const latok::TermKeyForm form = term_key_form(a);
+    const int64_t* d_starts = r.start;                // the rows of the keys: token space, or key space for the gram kinds
+    int64_t n_keys = n_tok;
+    if (n_tok > 0 && a.kind == TermKind::Tokens) {
+        /*   sized_token_front (wait 1)                    kept mask, token ranks; the host reads THE token total (pinned word 0): the key buffers are sized
+         *   k_term_scatter                                one term key per token at its rank (term_key.h), int64 token count per string
+         *   k_scan_chained                                the row starts in token space
+         *   enqueue_csr_tail: k_terms_tile, k_terms_long  sort and reduce inside every string: distinct and OOV counts, the entries
+         *     k_scan_chained, k_terms_emit                indptr, nnz -> pinned word 3; indices / data if nnz fits the capacity
+         *   k_terms_finish                                indptr / oov in the caller's width
+         *   (wait 2)                                      nnz; host pointers then copy nnz entries (wait 3) */
+        HIP_TRY(latok::launch_term_scatter(t, (const uint8_t*)a.b.in.p, form, (uint64_t*)w.tkeys.p, r.cnt, d_err, st));
         if ((rc = enqueue_row_scan(w, r.cnt, n_str + 1, r.start, (int64_t*)w.scalar.p + 4, nullptr, d_err + 1, st))) return rc;
-        if ((rc = enqueue_csr_tail(w, a, r, r.start, n_tok))) return rc;
-    }
-    HIP_TRY(latok::launch_terms_finish(a.o32, r.indptr, r.oov, n_str, a.indptr, a.oov, st));
-    return LATOK_OK;
-}
-
-/* Word n-grams of the term counts (latok_ngram_counts_utf8_bytes_batch, latok_hashed_ngram_counts_utf8_bytes_batch): one key per gram
- * instead of one per token, then the term counts' own sort and reduce with the row starts in KEY space.  One stream:
- *   sized_token_front (wait 1)                    kept mask, token ranks; the host reads THE token total (pinned word 0): the span records are sized
- *   enqueue_token_rows                            the span record of every token at its rank in the workspace, the row starts in token space
- *   k_ngram_rows + k_scan_chained                 grams per string, the row starts in key space; the key total K -> pinned word 5
- *   (wait 2)                                      the host reads K: 2^31 or more is refused, the two key buffers are sized
- *   k_ngram_keys                                  one term key per gram inside its row's range of keys
- *   enqueue_csr_tail, k_terms_finish              as enqueue_term_counts, with the key rows and K in the place of the token rows
- *   (wait 3)                                      nnz; host pointers then copy nnz entries (wait 4)
- * `w` was sized by ws_needs with WsShape{.spans = true, .term_rows = n_str + 1, .ng_rows = n_str + 1}; the call sizes the rest. */
-static int enqueue_ngram_counts(Ctx& g, Workspace& w, TermsCall& a) {
-    int rc;
-    const hipStream_t st = a.st;
-    const int64_t total = a.b.total, n_str = a.b.n_str;
-    int* d_err = (int*)(a.p_tot + 1);
-    latok::TokenPlanes t;
-    if ((rc = sized_token_front(g, w, a.b, a.p_tot, a.h_tot, st, kTooManyTermTokens, &t, &a.n_tokens))) return rc;
-    const int64_t n_tok = a.n_tokens;
-    WsShape shape{.spans = true, .term_rows = n_str + 1, .ng_tokens = n_tok, .ng_rows = n_str + 1};
-    if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, shape).data(), kWsNeeds))) return rc;
-    const TermRows r(w, n_str);                  // token space: counts, row starts
-    int64_t* d_kcnt = (int64_t*)w.ngrows.p;      // key space: counts, row starts
-    int64_t* d_kstart = d_kcnt + (n_str + 1);
-    HIP_TRY(hipMemsetAsync(r.cnt, 0, r.bytes, st));   // (no gram: every row is empty, nnz = 0)
-    if (n_tok > 0) {
-        if ((rc = enqueue_token_rows(w, a.b, t, n_tok, r.cnt, r.start, d_err, st))) return rc;
-        HIP_TRY(latok::launch_ngram_rows(r.cnt, n_str, a.min_n, a.max_n, d_kcnt, st));
-        if ((rc = enqueue_row_scan(w, d_kcnt, n_str + 1, d_kstart, (int64_t*)w.scalar.p + 6, a.p_tot + 5, d_err + 1, st))) return rc;
-        HIP_TRY(hipStreamSynchronize(st));   // wait 2: the key total decides whether the call goes on and what the keys take
-        int64_t n_tok_again = 0;
-        if ((rc = finish_totals(w, a.h_tot, 0, &n_tok_again))) return rc;
-        const int64_t n_keys = a.h_tot[5];
-        a.n_grams = n_keys;
-        if (n_keys >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld n-grams: term counts are int32 (fewer than 2^31 grams a call)", (long long)n_keys);
+    } else if (n_tok > 0) {
+        latok::TokenText text;
+        if ((rc = enqueue_token_rows(w, a.b, t, n_tok, r.cnt, r.start, d_err, st, &text))) return rc;
+        int64_t* d_kcnt = (int64_t*)w.ngrows.p;       // key space: counts per row (word grams only), row starts
+        int64_t* d_kstart = d_kcnt + (n_str + 1);
+        int64_t* d_gcnt = (int64_t*)w.wpcnt.p;        // per token (character grams only): grams, key rank (n_tok + 1 entries)
+        int64_t* d_grank = (int64_t*)w.wprank.p;
+        int64_t* d_ktotal = (int64_t*)w.scalar.p + 6;
+        const int max_n = std::min(a.max_n, kNgMax);  // (terms_refusals has refused more; the kernels' walks rest on it)
+        if (words) {
+            /*   sized_token_front (wait 1)                    kept mask, token ranks; the host reads THE token total (pinned word 0): the span records are sized
+             *   enqueue_token_rows                            the span record of every token at its rank in the workspace, the row starts in token space
+             *   k_ngram_rows + k_scan_chained                 grams per string, the row starts in key space; the key total K -> pinned word 5
+             *   (wait 2)                                      the host reads K: 2^31 or more is refused, the two key buffers are sized
+             *   k_ngram_keys                                  one term key per gram inside its row's range of keys
+             *   enqueue_csr_tail, k_terms_finish              as the token kind, with the key rows and K in the place of the token rows
+             *   (wait 3)                                      nnz; host pointers then copy nnz entries (wait 4) */
+            HIP_TRY(latok::launch_ngram_rows(r.cnt, n_str, a.min_n, max_n, d_kcnt, st));
+            if ((rc = enqueue_row_scan(w, d_kcnt, n_str + 1, d_kstart, d_ktotal, a.p_tot + 5, d_err + 1, st))) return rc;
+        } else {
+            /*   sized_token_front (wait 1)                    kept mask, token ranks; the host reads THE token total (pinned word 0): the per-token buffers are sized
+             *   enqueue_token_rows                            the span record of every token at its rank in the workspace, the row starts in token space
+             *   k_cgram_count + k_scan_chained                grams per token (chargram_text.h), each token's key rank; the key total K -> pinned word 5
+             *   k_wp_rows                                     the row starts in key space: the key rank of every string's first token
+             *   (wait 2)                                      the host reads K: 2^31 or more is refused, the two key buffers are sized
+             *   k_cgram_keys                                  one term key per gram inside its token's range of keys
+             *   enqueue_csr_tail, k_terms_finish              as the token kind, with the key rows and K in the place of the token rows
+             *   (wait 3)                                      nnz; host pointers then copy nnz entries (wait 4) */
+            HIP_TRY(latok::launch_cgram_count(text, a.min_n, max_n, d_gcnt, st));
+            if ((rc = enqueue_row_scan(w, d_gcnt, n_tok + 1, d_grank, d_ktotal, a.p_tot + 5, d_err + 1, st))) return rc;
+            HIP_TRY(latok::launch_wp_rows(false, r.start, d_grank, n_str, n_tok, d_kstart, st));
+        }
+        const char* too_many = words ? "the batch has %lld n-grams: term counts are int32 (fewer than 2^31 grams a call)"
+                                     : "the batch has %lld character n-grams: term counts are int32 (fewer than 2^31 grams a call)";
+        if ((rc = second_sized_total(w, a.h_tot, 5, st, too_many, &a.n_grams))) return rc;   // wait 2
+        n_keys = a.n_grams;
+        d_starts = d_kstart;
         if (n_keys > 0) {
             shape.ng_keys = n_keys;
             if ((rc = ws_ensure(ws_needs(w, total, shape).data(), kWsNeeds))) return rc;   // (only the key buffers grow)
-            latok::VocabTable vt;
-            if (a.v) vt = a.v->table.view(a.v->seed);
-            HIP_TRY(latok::launch_ngram_keys((const uint8_t*)a.b.in.p, total, a.b.row, n_str, r.start, d_kstart, (const int64_t*)w.wpspans.p, n_tok, n_keys,
-                                             a.min_n, a.max_n, a.sep, a.v ? &vt : nullptr, a.seed, (uint32_t)a.n_features, a.alternate_sign != 0,
-                                             (uint64_t*)w.tkeys.p, st));
-            if ((rc = enqueue_csr_tail(w, a, r, d_kstart, n_keys))) return rc;
+            const latok::GramKeys keys{text, words ? d_kstart : d_grank, n_keys, a.min_n, max_n, (uint32_t)(words ? a.sep : a.pad) & 0xFFu,
+                                       form, (uint64_t*)w.tkeys.p};
+            HIP_TRY(words ? latok::launch_ngram_keys(keys, st) : latok::launch_cgram_keys(keys, st));
         }
     }
-    HIP_TRY(latok::launch_terms_finish(a.o32, r.indptr, r.oov, n_str, a.indptr, a.oov, st));
-    return LATOK_OK;
-}
-
-/* Character n-grams inside tokens (latok_chargram_counts_utf8_bytes_batch, latok_hashed_chargram_counts_utf8_bytes_batch): one key per
- * gram of every token's padded word (chargram_text.h), then the term counts' own sort and reduce with the row starts in KEY space.  One
- * stream, every batch size the same kernels:
- *   sized_token_front (wait 1)                    kept mask, token ranks; the host reads THE token total (pinned word 0): the per-token buffers are sized
- *   enqueue_token_rows                            the span record of every token at its rank in the workspace, the row starts in token space
- *   k_cgram_count + k_scan_chained                grams per token, each token's key rank; the key total K -> pinned word 5
- *   k_wp_rows                                     the row starts in key space: the key rank of every string's first token
- *   (wait 2)                                      the host reads K: 2^31 or more is refused, the two key buffers are sized
- *   k_cgram_keys                                  one term key per gram inside its token's range of keys
- *   enqueue_csr_tail, k_terms_finish              as enqueue_term_counts, with the key rows and K in the place of the token rows
- *   (wait 3)                                      nnz; host pointers then copy nnz entries (wait 4)
- * The buffers are those the WordPiece and n-gram calls keep: span records, per-token count and rank, the key-space rows, the keys. */
-static int enqueue_chargram_counts(Ctx& g, Workspace& w, TermsCall& a) {
-    int rc;
-    const hipStream_t st = a.st;
-    const int64_t total = a.b.total, n_str = a.b.n_str;
-    int* d_err = (int*)(a.p_tot + 1);
-    latok::TokenPlanes t;
-    if ((rc = sized_token_front(g, w, a.b, a.p_tot, a.h_tot, st, kTooManyTermTokens, &t, &a.n_tokens))) return rc;
-    const int64_t n_tok = a.n_tokens;
-    WsShape shape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok, .ng_rows = n_str + 1};
-    if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, shape).data(), kWsNeeds))) return rc;
-    const TermRows r(w, n_str);                                // token space: counts, row starts
-    int64_t* d_kstart = (int64_t*)w.ngrows.p + (n_str + 1);    // key space: row starts
-    int64_t* d_gcnt = (int64_t*)w.wpcnt.p;                     // per token: grams, key rank (n_tok + 1 entries)
-    int64_t* d_grank = (int64_t*)w.wprank.p;
-    HIP_TRY(hipMemsetAsync(r.cnt, 0, r.bytes, st));   // (no gram: every row is empty, nnz = 0)
-    if (n_tok > 0) {
-        const uint8_t* u8 = (const uint8_t*)a.b.in.p;
-        const int64_t* d_tspans = (const int64_t*)w.wpspans.p;
-        if ((rc = enqueue_token_rows(w, a.b, t, n_tok, r.cnt, r.start, d_err, st))) return rc;
-        HIP_TRY(latok::launch_cgram_count(u8, total, a.b.row, n_str, r.start, d_tspans, n_tok, a.min_n, a.max_n, d_gcnt, st));
-        if ((rc = enqueue_row_scan(w, d_gcnt, n_tok + 1, d_grank, (int64_t*)w.scalar.p + 6, a.p_tot + 5, d_err + 1, st))) return rc;
-        HIP_TRY(latok::launch_wp_rows(false, r.start, d_grank, n_str, n_tok, d_kstart, st));
-        HIP_TRY(hipStreamSynchronize(st));   // wait 2: the key total decides whether the call goes on and what the keys take
-        int64_t n_tok_again = 0;
-        if ((rc = finish_totals(w, a.h_tot, 0, &n_tok_again))) return rc;
-        const int64_t n_keys = a.h_tot[5];
-        a.n_grams = n_keys;
-        if (n_keys >= (1ll << 31))
-            return fail(LATOK_ERR_INVALID, "the batch has %lld character n-grams: term counts are int32 (fewer than 2^31 grams a call)", (long long)n_keys);
-        if (n_keys > 0) {
-            shape.ng_keys = n_keys;
-            if ((rc = ws_ensure(ws_needs(w, total, shape).data(), kWsNeeds))) return rc;   // (only the key buffers grow)
-            latok::VocabTable vt;
-            if (a.v) vt = a.v->table.view(a.v->seed);
-            HIP_TRY(latok::launch_cgram_keys(u8, total, a.b.row, n_str, r.start, d_grank, d_tspans, n_tok, n_keys, a.min_n, a.max_n, a.pad,
-                                             a.v ? &vt : nullptr, a.seed, (uint32_t)a.n_features, a.alternate_sign != 0, (uint64_t*)w.tkeys.p, st));
-            if ((rc = enqueue_csr_tail(w, a, r, d_kstart, n_keys))) return rc;
-        }
-    }
+    if (n_keys > 0 && (rc = enqueue_csr_tail(w, a, r, d_starts, n_keys))) return rc;
     HIP_TRY(latok::launch_terms_finish(a.o32, r.indptr, r.oov, n_str, a.indptr, a.oov, st));
     return LATOK_OK;
 }
@@ -2744,12 +2717,12 @@ static int terms_refusals(const Ctx& g, TermsCall& a) {
         if (a.idf && a.hashed && a.n_features != a.idf->n_cols)
             return fail(LATOK_ERR_INVALID, "n_features is %lld, the idf has %lld columns", (long long)a.n_features, (long long)a.idf->n_cols);
     }
-    if (a.ngrams || a.chargrams) {
+    if (a.kind != TermKind::Tokens) {
         if (a.min_n < 1) return fail(LATOK_ERR_INVALID, "min_n must be at least 1");
         if (a.max_n < a.min_n) return fail(LATOK_ERR_INVALID, "max_n must not be below min_n");
         if (a.max_n > kNgMax) return fail(LATOK_ERR_INVALID, "max_n must not exceed %d", kNgMax);
-        if (a.ngrams && (a.sep < 0 || a.sep > 255)) return fail(LATOK_ERR_INVALID, "sep must be one byte: 0 .. 255");
-        if (a.chargrams && (a.pad < 0 || a.pad > 255)) return fail(LATOK_ERR_INVALID, "pad must be one byte: 0 .. 255");
+        if (a.kind == TermKind::WordGrams && (a.sep < 0 || a.sep > 255)) return fail(LATOK_ERR_INVALID, "sep must be one byte: 0 .. 255");
+        if (a.kind == TermKind::CharGrams && (a.pad < 0 || a.pad > 255)) return fail(LATOK_ERR_INVALID, "pad must be one byte: 0 .. 255");
     }
     if ((rc = need_init(g))) return rc;
     if (!a.nnz_out) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
@@ -2771,7 +2744,7 @@ static int terms_stage_outputs(Ctx& g, TermsCall& a, const BytesCall& c) {
     a.b = c.d;
     // (an entry has at least one token, a token one byte: the staging is sized by it; a token starts one gram of every order at most;
     // a token of b >= 1 bytes has at most b + 2 <= 3 b padded characters, each of which starts one character gram of every order at most)
-    const int64_t most = a.chargrams ? 3 * c.total * (a.max_n - a.min_n + 1) : c.total * (a.ngrams ? a.max_n - a.min_n + 1 : 1);
+    const int64_t most = c.total * (a.kind == TermKind::Tokens ? 1 : a.max_n - a.min_n + 1) * (a.kind == TermKind::CharGrams ? 3 : 1);
     a.fill_cap = a.update ? most : a.indices_out ? std::min(a.cap, most) : 0;
     a.o32 = c.o32;
     const bool own = !c.dev || a.update;   // a host call's outputs, and every update's, land in the context's own buffers
@@ -2858,12 +2831,12 @@ static int term_counts_common(TermsCall a) {
     }
     if (c.dev && (((uintptr_t)a.oov_out & (c.elt - 1)) != 0 || ((uintptr_t)a.indices_out & 3) != 0 || ((uintptr_t)a.data_out & 3) != 0))
         return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    const bool grams = a.ngrams || a.chargrams;   // the routes whose rows lie in key space
+    const bool grams = a.kind != TermKind::Tokens;   // the kinds whose rows lie in key space
+    const int route = (a.kind == TermKind::CharGrams ? 16 : a.kind == TermKind::WordGrams ? 14 : 9) + (a.hashed ? 1 : 0);
     const WsShape shape{.spans = true, .term_rows = n_str + 1, .ng_rows = grams ? n_str + 1 : 0, .tf_ctl = a.tfidf};
-    const int route = a.chargrams ? (a.hashed ? 17 : 16) : a.ngrams ? (a.hashed ? 15 : 14) : (a.hashed ? 10 : 9);
     if ((rc = c.stage(g, route, shape, (grams ? kClearNgrams : kClearSized) | (a.tfidf ? kClearTfidfErr : 0u)))) return rc;
     if ((rc = terms_stage_outputs(g, a, c))) return rc;
-    if ((rc = a.chargrams ? enqueue_chargram_counts(g, g.ws, a) : a.ngrams ? enqueue_ngram_counts(g, g.ws, a) : enqueue_term_counts(g, g.ws, a))) return rc;
+    if ((rc = enqueue_term_keys(g, g.ws, a))) return rc;
     // (no key: the scan did not run and nnz = 0)
     if (a.tfidf && a.indices && (grams ? a.n_grams : a.n_tokens) > 0 && (rc = enqueue_tfidf_tail(g, a))) return rc;
     return terms_deliver(g, a, c);
@@ -2871,7 +2844,7 @@ static int term_counts_common(TermsCall a) {
 int latok_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
                                         int min_n, int max_n, int sep, int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out,
                                         int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_grams_out, int flags, void* stream) {
-    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .vocab = vocab, .ngrams = true,
+    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .vocab = vocab, .kind = TermKind::WordGrams,
                                .min_n = min_n, .max_n = max_n, .sep = sep, .indptr_out = indptr_out, .oov_out = oov_out, .indices_out = indices_out,
                                .data_out = data_out, .cap = cap, .nnz_out = nnz_out, .n_grams_out = n_grams_out, .flags = flags, .stream = stream});
 }
@@ -2880,15 +2853,15 @@ int latok_hashed_ngram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_
                                                int32_t* indices_out, int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_grams_out,
                                                int flags, void* stream) {
     return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .hashed = true, .seed = seed,
-                               .n_features = n_features, .alternate_sign = alternate_sign, .ngrams = true, .min_n = min_n, .max_n = max_n, .sep = sep,
+                               .n_features = n_features, .alternate_sign = alternate_sign, .kind = TermKind::WordGrams, .min_n = min_n, .max_n = max_n, .sep = sep,
                                .indptr_out = indptr_out, .indices_out = indices_out, .data_out = data_out, .cap = cap, .nnz_out = nnz_out,
                                .n_grams_out = n_grams_out, .flags = flags, .stream = stream});
 }
 int latok_chargram_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab,
                                            int min_n, int max_n, int pad, int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out,
                                            int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_grams_out, int flags, void* stream) {
-    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .vocab = vocab, .min_n = min_n,
-                               .max_n = max_n, .chargrams = true, .pad = pad, .indptr_out = indptr_out, .oov_out = oov_out,
+    return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .vocab = vocab, .kind = TermKind::CharGrams,
+                               .min_n = min_n, .max_n = max_n, .pad = pad, .indptr_out = indptr_out, .oov_out = oov_out,
                                .indices_out = indices_out, .data_out = data_out, .cap = cap, .nnz_out = nnz_out, .n_grams_out = n_grams_out,
                                .flags = flags, .stream = stream});
 }
@@ -2897,7 +2870,7 @@ int latok_hashed_chargram_counts_utf8_bytes_batch(const uint8_t* utf8, const int
                                                   int32_t* indices_out, int32_t* data_out, int64_t cap, int64_t* nnz_out, int64_t* n_grams_out,
                                                   int flags, void* stream) {
     return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .hashed = true, .seed = seed,
-                               .n_features = n_features, .alternate_sign = alternate_sign, .min_n = min_n, .max_n = max_n, .chargrams = true,
+                               .n_features = n_features, .alternate_sign = alternate_sign, .kind = TermKind::CharGrams, .min_n = min_n, .max_n = max_n,
                                .pad = pad, .indptr_out = indptr_out, .indices_out = indices_out, .data_out = data_out, .cap = cap,
                                .nnz_out = nnz_out, .n_grams_out = n_grams_out, .flags = flags, .stream = stream});
 }
@@ -2918,12 +2891,14 @@ int latok_hashed_term_counts_utf8_bytes_batch(const uint8_t* utf8, const int64_t
 
 /* the TF-IDF entry points over text: term_counts_common with a tail; min_n = max_n = 1 with a one-byte sep takes the plain term counts'
  * kernels (the n-gram route checks its arguments itself) */
-static bool tfidf_ngrams(int min_n, int max_n, int sep) { return !(min_n == 1 && max_n == 1 && sep >= 0 && sep <= 255); }
+static TermKind tfidf_kind(int min_n, int max_n, int sep) {
+    return min_n == 1 && max_n == 1 && sep >= 0 && sep <= 255 ? TermKind::Tokens : TermKind::WordGrams;
+}
 int latok_tfidf_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_vocab* vocab, int min_n,
                                  int max_n, int sep, const latok_idf* idf, int opts, int64_t* indptr_out, int64_t* oov_out, int32_t* indices_out,
                                  float* data_out, int64_t cap, int64_t* nnz_out, int flags, void* stream) {
     return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .vocab = vocab,
-                               .ngrams = tfidf_ngrams(min_n, max_n, sep), .min_n = min_n, .max_n = max_n, .sep = sep, .tfidf = true,
+                               .kind = tfidf_kind(min_n, max_n, sep), .min_n = min_n, .max_n = max_n, .sep = sep, .tfidf = true,
                                .idf = const_cast<Idf*>(reinterpret_cast<const Idf*>(idf)), .opts = opts, .indptr_out = indptr_out, .oov_out = oov_out,
                                .indices_out = indices_out, .data_out = (int32_t*)data_out, .cap = cap, .nnz_out = nnz_out, .flags = flags, .stream = stream});
 }
@@ -2932,7 +2907,7 @@ int latok_hashed_tfidf_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
                                         int64_t* indptr_out, int32_t* indices_out, float* data_out, int64_t cap, int64_t* nnz_out, int flags,
                                         void* stream) {
     return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .hashed = true, .seed = seed,
-                               .n_features = n_features, .alternate_sign = alternate_sign, .ngrams = tfidf_ngrams(min_n, max_n, sep), .min_n = min_n,
+                               .n_features = n_features, .alternate_sign = alternate_sign, .kind = tfidf_kind(min_n, max_n, sep), .min_n = min_n,
                                .max_n = max_n, .sep = sep, .tfidf = true, .idf = const_cast<Idf*>(reinterpret_cast<const Idf*>(idf)), .opts = opts,
                                .indptr_out = indptr_out, .indices_out = indices_out, .data_out = (int32_t*)data_out, .cap = cap, .nnz_out = nnz_out,
                                .flags = flags, .stream = stream});
@@ -2942,7 +2917,7 @@ int latok_idf_update_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_o
                                       int64_t* n_tokens_out, int flags, void* stream) {
     int64_t nnz = 0;
     return term_counts_common({.utf8 = utf8, .byte_off = byte_off, .n_str = n_str, .total_bytes = total_bytes, .vocab = vocab,
-                               .hashed = vocab == nullptr, .seed = seed, .n_features = n_features, .ngrams = tfidf_ngrams(min_n, max_n, sep),
+                               .hashed = vocab == nullptr, .seed = seed, .n_features = n_features, .kind = tfidf_kind(min_n, max_n, sep),
                                .min_n = min_n, .max_n = max_n, .sep = sep, .tfidf = true, .update = true, .idf = reinterpret_cast<Idf*>(idf),
                                .nnz_out = nnz_out ? nnz_out : &nnz, .n_tokens_out = n_tokens_out, .flags = flags, .stream = stream});
 }
@@ -3308,24 +3283,20 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
     const int32_t* d_ids = a.ids;
     if (n_tok > 0) {
         HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)(n_str + 1) * 8, st));
-        const int64_t* d_tspans = (const int64_t*)w.wpspans.p;
-        if ((rc = enqueue_token_rows(w, a.b, t, n_tok, d_cnt, d_start, d_err, st))) return rc;
+        latok::TokenText text;
+        if ((rc = enqueue_token_rows(w, a.b, t, n_tok, d_cnt, d_start, d_err, st, &text))) return rc;
         latok::WordPieceTables wt;
         wt.initial = a.wp->initial.view(a.wp->seed);
         wt.cont = a.wp->cont.view(a.wp->seed);
         wt.max_len0 = a.wp->max_len0;
         wt.max_len1 = a.wp->max_len1;
         wt.max_chars = a.wp->max_chars;
-        const uint8_t* u8 = (const uint8_t*)a.b.in.p;
-        HIP_TRY(latok::launch_wp_count(u8, total, a.b.row, n_str, d_start, d_tspans, n_tok, wt, d_pcnt, st));
+        HIP_TRY(latok::launch_wp_count(text, wt, d_pcnt, st));
         if ((rc = enqueue_row_scan(w, d_pcnt, n_tok + 1, d_prank, d_total + 5, a.p_tot + 3, d_err + 1, st))) return rc;
         int32_t* ids = a.ids;
         int64_t cap = a.cap;
         if (a.padded) {
-            HIP_TRY(hipStreamSynchronize(st));   // wait 2 (padded form): the piece total sizes the ids
-            int64_t n_tok_again = 0;
-            if ((rc = finish_totals(w, a.h_tot, 0, &n_tok_again))) return rc;
-            cap = a.h_tot[3];
+            if ((rc = second_sized_total(w, a.h_tot, 3, st, nullptr, &cap))) return rc;   // wait 2 (padded form): the piece total sizes the ids
             if (cap >= (1ll << 31)) return LATOK_OK;   // (the caller refuses it)
             if ((rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok, .wp_pieces = cap}).data(),
                                 kWsNeeds)))
@@ -3333,9 +3304,7 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
             ids = (int32_t*)w.wpids.p;
             d_ids = ids;
         }
-        if (ids)
-            HIP_TRY(latok::launch_wp_emit(a.o32, u8, total, a.b.row, n_str, d_start, d_tspans, n_tok, wt, a.unk, d_prank, d_total + 5, cap, ids,
-                                          a.spans, st));
+        if (ids) HIP_TRY(latok::launch_wp_emit(a.o32, text, wt, a.unk, d_prank, d_total + 5, cap, ids, a.spans, st));
         if (a.indptr) HIP_TRY(latok::launch_wp_rows(a.o32, d_start, d_prank, n_str, n_tok, a.indptr, st));
     } else if (a.indptr) {
         HIP_TRY(hipMemsetAsync(a.indptr, 0, (size_t)(n_str + 1) * (a.o32 ? 4 : 8), st));   // (no token: every row is empty)

@@ -1,8 +1,10 @@
 // block_ops.h -- what the threads of one workgroup do together, and the per-thread searches they share: the bisections of a row-start
-// array, the rows that touch a workgroup's tokens, the checked load of a token's span record, the workgroup prefix sum.  Device code
+// array, the rows that touch a workgroup's tokens, the checked load of a token's span record, the three composed into a lane's token, the
+// workgroup prefix sum.  Device code
 // only; beside wave_ops.h (what one wavefront does), for the same reason: a kernel calls these instead of carrying a copy.
 #ifndef LATOK_BLOCK_OPS_H
 #define LATOK_BLOCK_OPS_H
+#include "kernels.h"
 #include "wave_ops.h"
 
 namespace latok {
@@ -57,6 +59,30 @@ __device__ __forceinline__ TokenBytes token_bytes(const int64_t* __restrict__ to
     const ll2 rec = *reinterpret_cast<const ll2*>(tok_spans + 2 * t);
     const int64_t a = base + rec.x, e = base + rec.y;
     return TokenBytes{a, e, base >= 0 && rec.x >= 0 && a < e && e <= total};
+}
+
+// The token of this lane in a kernel that takes one token per lane, BLOCK per workgroup, of a text in token space (TokenText of
+// kernels.h): t = the token, row = its string, held inside [0, n_str) whatever row_start holds, base = the string's first byte, b = the
+// token's checked byte range.  b.ok is false for a lane behind the last token (nothing of it is loaded) and for a record that does not
+// lie inside the text (cannot happen with records from the scatter): a caller that reads the text only where b.ok -- or where a
+// token_bytes of its own says so -- leaves the buffer with no load, whatever the workspace holds; a record is read only inside
+// [0, n_tok).  Every thread of the workgroup calls it before any early return: block_rows contains a barrier.
+struct LaneToken {
+    int64_t t, row, base;
+    TokenBytes b;
+};
+template <int BLOCK>
+__device__ __forceinline__ LaneToken lane_token(const TokenText& T) {
+    const int64_t t0 = (int64_t)blockIdx.x * BLOCK, t = t0 + threadIdx.x;
+    int64_t lo, end;
+    block_rows<BLOCK>(T.row_start, T.n_str, t0, &lo, &end);
+    LaneToken k{t, 0, 0, TokenBytes{0, 0, false}};
+    if (t >= T.n_tok) return k;
+    const int64_t r = row_of_token(T.row_start, lo, end, t);
+    k.row = r < 0 ? 0 : (r >= T.n_str ? T.n_str - 1 : r);
+    k.base = T.row_off[k.row];
+    k.b = token_bytes(T.tok_spans, t, k.base, T.total);
+    return k;
 }
 
 // inclusive prefix sum of one value per thread over a workgroup of WAVES wavefronts; *total = the workgroup's sum (the exclusive

@@ -1514,19 +1514,19 @@ hipError_t launch_count_scatter(const TokenPlanes& p, const uint8_t* u8, const C
         hipLaunchKernelGGL(k_count_scatter, grid, block, 0, st, a);
     });
 }
-// term keys: keys[rank] of every token and the int64 token count of every string (vt == NULL: the hashed form)
-hipError_t launch_term_scatter(const TokenPlanes& p, const uint8_t* u8, const VocabTable* vt, uint32_t seed, uint32_t n_features,
-                               bool alternate_sign, uint64_t* keys, int64_t* counts, int* err, hipStream_t st) {
+// term keys: keys[rank] of every token and the int64 token count of every string
+hipError_t launch_term_scatter(const TokenPlanes& p, const uint8_t* u8, const TermKeyForm& form, uint64_t* keys, int64_t* counts, int* err,
+                               hipStream_t st) {
     TermScatterArgs a{};
     a.p = p;
     a.counts = counts;
     a.err = err;
     a.ha.text = reinterpret_cast<const uint32_t*>(u8);
-    a.ha.seed = vt ? vt->seed : seed;
-    if (vt) a.va = vocab_args(*vt, nullptr, 0);
+    a.ha.seed = form.seed;
+    if (form.vocab) a.va = vocab_args(form.vt, nullptr, 0);
     a.ta.keys = keys;
-    a.ta.n_features = vt ? 0u : n_features;
-    a.ta.alternate_sign = alternate_sign;
+    a.ta.n_features = form.n_features;
+    a.ta.alternate_sign = form.alternate_sign;
     return launch_scatter(false, p, true, counts, [&](auto, dim3 grid, dim3 block, unsigned nb) {
         a.n_scatter_blocks = nb;
         hipLaunchKernelGGL(k_term_scatter, grid, block, 0, st, a);

@@ -346,11 +346,18 @@ struct CountTable {
     unsigned long long* ctl = nullptr;      // {fresh dwords of this call, blob cursor, distinct, overflow flag}
 };
 hipError_t launch_count_scatter(const TokenPlanes& p, const uint8_t* u8, const CountTable& ct, int* err, hipStream_t st);
+// the key form of the term family (term_key.h): the lookup in a vocabulary table, or the hashed form (bucket = |h| mod n_features, sign)
+struct TermKeyForm {
+    bool vocab = false;
+    VocabTable vt;                // vocab
+    uint32_t seed = 0;            // of the hash: the table's own in the vocabulary form
+    uint32_t n_features = 0;      // hashed form (0 in the vocabulary form)
+    bool alternate_sign = false;
+};
 // term keys of a UTF-8 batch in byte space (compact_kernels.hip: TermTokens): launch_vocab_scatter's launch with one term key
-// (term_key.h) per token at its rank in `keys` and the int64 token count of every string in `counts`; vt == NULL: the hashed form
-// (bucket = |h| mod n_features, sign).  No records, no capacity.
-hipError_t launch_term_scatter(const TokenPlanes& p, const uint8_t* u8, const VocabTable* vt, uint32_t seed, uint32_t n_features,
-                               bool alternate_sign, uint64_t* keys, int64_t* counts, int* err, hipStream_t st);
+// per token at its rank in `keys` and the int64 token count of every string in `counts`.  No records, no capacity.
+hipError_t launch_term_scatter(const TokenPlanes& p, const uint8_t* u8, const TermKeyForm& form, uint64_t* keys, int64_t* counts, int* err,
+                               hipStream_t st);
 // per-string term counts (terms_kernels.hip): the segmented sort-and-reduce of the term keys.  A workgroup owns the rows that start
 // in its tile of kTermsTile tokens; a row of more than kTermsRowMax tokens is sorted by a workgroup of its own through `alt`
 // (as large as `keys`).  row_start[n_str + 1] = the exclusive scan of the per-string token counts.  launch_terms_reduce leaves
@@ -365,11 +372,21 @@ hipError_t launch_terms_emit(const uint64_t* keys, const int64_t* row_start, int
                              const int64_t* indptr, const int64_t* nnz_dev, int64_t cap, int32_t* indices, int32_t* data, hipStream_t st);
 hipError_t launch_terms_finish(bool out32, const int64_t* indptr, const int64_t* oov, int64_t n_str, void* indptr_out, void* oov_out,
                                hipStream_t st);
-// WordPiece ids of a UTF-8 batch in byte space (wordpiece_kernels.hip), in token space, one lane per token: behind kind 1 of
-// launch_counts_scatter (int64 span records at rank in the workspace, int64 token count per string) and the scan of those counts
-// (row_start[n_str + 1]).  launch_wp_count leaves the pieces of every token in cnt[0 .. n_tok) and 0 in cnt[n_tok]; the caller scans
-// the n_tok + 1 entries into rank[] (rank[n_tok] = the piece total); launch_wp_emit walks every token again and stores ids, and
-// string-relative spans if asked for, at the piece rank, only if the total fits cap; launch_wp_rows types indptr[s] =
+// The text of a batch in TOKEN space, what the kernels with one lane per token read (lane_token of block_ops.h): behind kind 1 of
+// launch_counts_scatter (the int64 span record of every token at its rank, the int64 token count of every string) and the scan of
+// those counts.  Device memory, read only; the host builds it once per call.
+struct TokenText {
+    const uint32_t* text;       // the UTF-8 bytes as aligned dwords
+    int64_t total;              // in bytes
+    const int64_t* row_off;     // first byte of every string
+    int64_t n_str;
+    const int64_t* row_start;   // token space, n_str + 1 entries (row_start[n_str] = the token total)
+    const int64_t* tok_spans;   // two string-relative byte offsets per token
+    int64_t n_tok;
+};
+// WordPiece ids (wordpiece_kernels.hip).  launch_wp_count leaves the pieces of every token in cnt[0 .. n_tok) and 0 in cnt[n_tok]; the
+// caller scans the n_tok + 1 entries into rank[] (rank[n_tok] = the piece total); launch_wp_emit walks every token again and stores
+// ids, and string-relative spans if asked for, at the piece rank, only if the total fits cap; launch_wp_rows types indptr[s] =
 // rank[row_start[s]], s = 0 .. n_str.  launch_wp_pad fills an [n_str, max_length] int32 block from the ids: cls (if add_special),
 // the first max_length - 2 add_special pieces of the row, sep (if add_special), pad; lengths[s] = cells used.  rank == NULL there:
 // a batch without a token, every row is empty.  The tables are device memory, read only.
@@ -379,37 +396,43 @@ struct WordPieceTables {
     uint32_t max_len0 = 0, max_len1 = 0;
     int max_chars = 0;
 };
-hipError_t launch_wp_count(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
-                           const int64_t* tok_spans, int64_t n_tok, const WordPieceTables& wt, int64_t* cnt, hipStream_t st);
-hipError_t launch_wp_emit(bool out32, const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
-                          const int64_t* tok_spans, int64_t n_tok, const WordPieceTables& wt, int32_t unk_id, const int64_t* rank,
+hipError_t launch_wp_count(const TokenText& t, const WordPieceTables& wt, int64_t* cnt, hipStream_t st);
+hipError_t launch_wp_emit(bool out32, const TokenText& t, const WordPieceTables& wt, int32_t unk_id, const int64_t* rank,
                           const int64_t* n_pieces_dev, int64_t cap, int32_t* ids, void* spans, hipStream_t st);
 hipError_t launch_wp_rows(bool out32, const int64_t* row_start, const int64_t* rank, int64_t n_str, int64_t n_tok, void* indptr_out, hipStream_t st);
 hipError_t launch_wp_pad(const int32_t* ids, const int64_t* row_start, const int64_t* rank, int64_t n_str, int64_t n_tok, int64_t max_length, int add_special,
                          int32_t cls_id, int32_t sep_id, int32_t pad_id, int32_t* input_ids, int32_t* lengths, hipStream_t st);
-// word n-grams of a UTF-8 batch in byte space (ngram_kernels.hip), in token space, one lane per token: behind kind 1 of
-// launch_counts_scatter and the scan of the token counts, as WordPiece.  launch_ngram_rows leaves the grams of every string in
-// key_cnt[0 .. n_str) and 0 in key_cnt[n_str]; the caller scans the n_str + 1 entries into key_start[] (key_start[n_str] = the key
-// total).  launch_ngram_keys stores one term key (term_key.h) per gram of the orders min_n .. max_n inside its row's range of
-// `keys`, which holds n_keys keys: vt == NULL the hashed form, else the lookup of the gram's bytes (tokens joined by `sep`) in the
-// table.  launch_terms_reduce / _emit / _finish then take keys and key_start as they take the token keys and the token rows.
-constexpr int kNgBlock = 256;   // tokens per workgroup of k_ngram_keys (latok_debug_ngram_limits); the highest order: kNgMax of ngram_text.h
+// The gram keys of the term family: one term key per gram of the orders min_n .. max_n, each inside its own range of `keys`, which
+// holds n_keys keys; the lookup spells a gram with `joiner` between its tokens (word grams) or around the word (character grams).
+// launch_terms_reduce / _emit / _finish then take keys and the key-space row starts as they take the token keys and the token rows.
+struct GramKeys {
+    TokenText t;
+    const int64_t* rank;   // key space, from the caller's scan: per ROW for word grams (n_str + 1 entries, where the row's keys start),
+                           // per TOKEN for character grams (n_tok + 1 entries); the last entry = n_keys
+    int64_t n_keys;
+    int min_n, max_n;      // 1 <= min_n <= max_n <= kNgMax of ngram_text.h (the caller holds max_n there)
+    uint32_t joiner;       // one byte: sep / pad
+    TermKeyForm form;
+    uint64_t* keys;
+};
+// one lane per token in workgroups of `block`, the kernel of the key form
+template <typename K>
+inline hipError_t launch_gram_keys(K* vocab, K* hashed, int block, const GramKeys& P, hipStream_t st) {
+    if (P.t.n_str <= 0 || P.t.n_tok <= 0 || P.n_keys <= 0) return hipSuccess;
+    hipLaunchKernelGGL(P.form.vocab ? vocab : hashed, dim3((unsigned)((P.t.n_tok + block - 1) / block)), dim3(block), 0, st, P);
+    return hipGetLastError();
+}
+// word n-grams (ngram_kernels.hip).  launch_ngram_rows leaves the grams of every string in key_cnt[0 .. n_str) and 0 in
+// key_cnt[n_str]; the caller scans the n_str + 1 entries into the rows' key ranks.
+constexpr int kNgBlock = 256;   // tokens per workgroup of k_ngram_keys (latok_debug_ngram_limits)
 hipError_t launch_ngram_rows(const int64_t* tok_cnt, int64_t n_str, int min_n, int max_n, int64_t* key_cnt, hipStream_t st);
-hipError_t launch_ngram_keys(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
-                             const int64_t* key_start, const int64_t* tok_spans, int64_t n_tok, int64_t n_keys, int min_n, int max_n, int sep,
-                             const VocabTable* vt, uint32_t seed, uint32_t n_features, bool alternate_sign, uint64_t* keys, hipStream_t st);
-// character n-grams inside tokens (chargram_kernels.hip, chargram_text.h), in token space, one lane per token: behind kind 1 of
-// launch_counts_scatter and the scan of the token counts, as WordPiece.  launch_cgram_count leaves the grams G(W) of every token in
-// cnt[0 .. n_tok) and 0 in cnt[n_tok]; the caller scans the n_tok + 1 entries into rank[] (rank[n_tok] = the key total) and takes the
-// row starts in key space from launch_wp_rows.  launch_cgram_keys stores one term key (term_key.h) per gram of the orders min_n ..
-// max_n inside its token's range of `keys`, which holds n_keys keys: vt == NULL the hashed form, else the lookup of the gram's bytes
-// (pad included) in the table.  launch_terms_reduce / _emit / _finish then take keys and the key-space row starts.
+hipError_t launch_ngram_keys(const GramKeys& P, hipStream_t st);
+// character n-grams inside tokens (chargram_kernels.hip, chargram_text.h).  launch_cgram_count leaves the grams G(W) of every token in
+// cnt[0 .. n_tok) and 0 in cnt[n_tok]; the caller scans the n_tok + 1 entries into the tokens' key ranks and takes the row starts in
+// key space from launch_wp_rows.
 constexpr int kCgBlock = 256;   // tokens per workgroup of k_cgram_count / k_cgram_keys (latok_debug_chargram_limits)
-hipError_t launch_cgram_count(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
-                              const int64_t* tok_spans, int64_t n_tok, int min_n, int max_n, int64_t* cnt, hipStream_t st);
-hipError_t launch_cgram_keys(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
-                             const int64_t* rank, const int64_t* tok_spans, int64_t n_tok, int64_t n_keys, int min_n, int max_n, int pad,
-                             const VocabTable* vt, uint32_t seed, uint32_t n_features, bool alternate_sign, uint64_t* keys, hipStream_t st);
+hipError_t launch_cgram_count(const TokenText& t, int min_n, int max_n, int64_t* cnt, hipStream_t st);
+hipError_t launch_cgram_keys(const GramKeys& P, hipStream_t st);
 // tfidf_kernels.hip: TF-IDF on a CSR in device memory (tfidf_weight.h).  indptr is int32 (ip32) or int64; nnz_dev != NULL: the entry
 // count is the scan's own word, not yet read by the host -- the kernels then do nothing when it exceeds `cap`, what the buffers hold
 // (launch_terms_emit's rule), and `nnz` is ignored.  launch_csr_check ORs kCsrBad* bits into *err (indptr == NULL: the columns alone;

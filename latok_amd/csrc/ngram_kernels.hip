@@ -5,9 +5,8 @@
 //
 //   k_ngram_rows   K_s = sum over n in [min_n, max_n] of max(0, c_s - n + 1): the grams of string s.  The chained scan of the
 //                  n_str + 1 entries (the last is 0) gives the row starts in KEY space and the key total K.
-//   k_ngram_keys   one lane per token t.  The lane finds its string s by bisection of the token-space row starts, narrowed per
-//                  workgroup to the rows that touch its kNgBlock tokens (block_rows, row_of_token of block_ops.h; the checked
-//                  record load is its token_bytes), and its index j = t - row_start[s] in the row.  It walks
+//   k_ngram_keys   one lane per token t.  The lane takes its string s (lane_token of block_ops.h; the checked record load of the
+//                  tokens it walks is token_bytes there) and its index j = t - row_start[s] in the row.  It walks
 //                  the tokens j .. min(j + max_n, c_s) - 1 ONCE with the streaming hash of ngram_text.h -- separator, token, finish
 //                  -- and behind token j + n - 1 stores the key of the gram g(n, j) if n >= min_n: tk_hashed_key of the hash, or
 //                  tk_vocab_probe with ng_equal over the gram's span records (which walks the gram again, only where hash and
@@ -18,9 +17,10 @@
 // A lane whose grams are long or whose probes collide keeps its wave busy while the others idle: accepted in this version, as in
 // WordPiece; there is no whole-wave form for long tokens.  Every loop runs by its own counter: the walk at most max_n <= kNgMax
 // tokens, a token's dwords, a probe at most n_slots steps.  A key is stored only inside [0, n_keys), a record read only inside
-// [0, n_tok), the text only where a checked record says -- whatever the workspace holds.  Table and blob are read with ordinary
-// cached loads, the text as aligned dwords up to the one that holds a token's last byte.  No kernel here waits for another
-// workgroup; all stores are vector stores from plain C++.
+// [0, n_tok) (the walk ends with the batch's last token), the text only where a checked record says -- whatever the workspace holds;
+// the string's part of the argument stands at lane_token of block_ops.h.  Table and blob are read with ordinary cached loads, the
+// text as aligned dwords up to the one that holds a token's last byte.  No kernel here waits for another workgroup; all stores are
+// vector stores from plain C++.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -45,51 +45,30 @@ __global__ __launch_bounds__(256) void k_ngram_rows(const int64_t* __restrict__ 
     key_cnt[s] = s < n_str ? ng_row_keys(tok_cnt[s], min_n, max_n) : 0;   // (the entry behind the last string)
 }
 
-struct NgramParams {
-    const uint32_t* text;
-    int64_t total;
-    const int64_t* row_off;
-    int64_t n_str;
-    const int64_t* row_start;   // token space
-    const int64_t* key_start;   // key space
-    const int64_t* tok_spans;
-    int64_t n_tok, n_keys;
-    int min_n, max_n;
-    uint32_t sep;
-    VocabTable vt;              // VOCAB
-    uint32_t seed, n_features;  // hashed form
-    bool alternate_sign;
-    uint64_t* keys;
-};
-
 template <bool VOCAB>
-__global__ __launch_bounds__(kNgBlock) void k_ngram_keys(NgramParams P) {
-    const int64_t t0 = (int64_t)blockIdx.x * kNgBlock, t = t0 + threadIdx.x;
-    int64_t lo, end;
-    block_rows<kNgBlock>(P.row_start, P.n_str, t0, &lo, &end);
-    if (t >= P.n_tok) return;
-    int64_t r = row_of_token(P.row_start, lo, end, t);
-    r = r < 0 ? 0 : (r >= P.n_str ? P.n_str - 1 : r);
-    const int64_t rs = P.row_start[r], c = P.row_start[r + 1] - rs, j = t - rs;
-    const int64_t base = P.row_off[r];
+__global__ __launch_bounds__(kNgBlock) void k_ngram_keys(GramKeys P) {
+    const LaneToken me = lane_token<kNgBlock>(P.t);
+    const int64_t t = me.t, r = me.row, base = me.base, n_tok = P.t.n_tok;
+    if (t >= n_tok) return;
+    const int64_t rs = P.t.row_start[r], c = P.t.row_start[r + 1] - rs, j = t - rs;
     if (j < 0 || j >= c || base < 0) return;   // (cannot happen with row starts from the scan)
     int64_t left = c - j;                       // tokens from mine to the row's end ...
-    if (left > P.n_tok - t) left = P.n_tok - t;
+    if (left > n_tok - t) left = n_tok - t;
     const int n_walk = left < P.max_n ? (int)left : P.max_n;   // ... of which the walk takes at most max_n <= kNgMax
-    const uint32_t* const text = P.text;
-    const int64_t total = P.total;
-    const int64_t* const tok_spans = P.tok_spans;
+    const uint32_t* const text = P.t.text;
+    const int64_t total = P.t.total;
+    const int64_t* const tok_spans = P.t.tok_spans;
     auto ld = [text](int64_t i) { return text[i]; };
     // token k of my grams, absolute; a record that does not lie inside the text is an empty token: nothing of it is read
     auto span = [tok_spans, t, base, total](int k) {
         const TokenBytes b = token_bytes(tok_spans, t + k, base, total);
         return b.ok ? NgSpan{b.a, b.e} : NgSpan{0, 0};
     };
-    const VtSlot* const slots = reinterpret_cast<const VtSlot*>(P.vt.slots);
-    const uint32_t* const blob = P.vt.blob;
-    const uint32_t sep = P.sep;
-    NgHash st = ng_hash_init(VOCAB ? P.vt.seed : P.seed);
-    int64_t at = P.key_start[r] + j;            // where g(n, j) goes: the orders before n add their c - m + 1 each
+    const VtSlot* const slots = reinterpret_cast<const VtSlot*>(P.form.vt.slots);
+    const uint32_t* const blob = P.form.vt.blob;
+    const uint32_t sep = P.joiner;
+    NgHash st = ng_hash_init(P.form.seed);
+    int64_t at = P.rank[r] + j;   // where g(n, j) goes: the orders before n add their c - m + 1 each
     for (int n = 1; n <= n_walk; ++n) {
         if (n > 1) ng_hash_byte(st, sep);
         const NgSpan tok = span(n - 1);
@@ -99,11 +78,11 @@ __global__ __launch_bounds__(kNgBlock) void k_ngram_keys(NgramParams P) {
         uint64_t key;
         if (VOCAB) {
             const uint32_t len = st.s.len;
-            key = tk_vocab_probe([slots](uint64_t i) { return slots[i]; }, P.vt.n_slots, h, len, [&](uint32_t off) {
+            key = tk_vocab_probe([slots](uint64_t i) { return slots[i]; }, P.form.vt.n_slots, h, len, [&](uint32_t off) {
                 return ng_equal(ld, span, n, sep, [blob](uint64_t i) { return blob[i]; }, off, len);
             });
         } else {
-            key = tk_hashed_key(h, P.n_features, P.alternate_sign);
+            key = tk_hashed_key(h, P.form.n_features, P.form.alternate_sign);
         }
         if (at >= 0 && at < P.n_keys) P.keys[at] = key;
         at += c - n + 1;
@@ -117,32 +96,6 @@ hipError_t launch_ngram_rows(const int64_t* tok_cnt, int64_t n_str, int min_n, i
     return hipGetLastError();
 }
 
-hipError_t launch_ngram_keys(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
-                             const int64_t* key_start, const int64_t* tok_spans, int64_t n_tok, int64_t n_keys, int min_n, int max_n, int sep,
-                             const VocabTable* vt, uint32_t seed, uint32_t n_features, bool alternate_sign, uint64_t* keys, hipStream_t st) {
-    if (n_str <= 0 || n_tok <= 0 || n_keys <= 0) return hipSuccess;
-    NgramParams P;
-    P.text = reinterpret_cast<const uint32_t*>(u8);
-    P.total = total;
-    P.row_off = row_off;
-    P.n_str = n_str;
-    P.row_start = row_start;
-    P.key_start = key_start;
-    P.tok_spans = tok_spans;
-    P.n_tok = n_tok;
-    P.n_keys = n_keys;
-    P.min_n = min_n;
-    P.max_n = max_n < kNgMax ? max_n : kNgMax;
-    P.sep = (uint32_t)sep & 0xFFu;
-    P.vt = vt ? *vt : VocabTable{};
-    P.seed = seed;
-    P.n_features = n_features;
-    P.alternate_sign = alternate_sign;
-    P.keys = keys;
-    const dim3 grid((unsigned)((n_tok + kNgBlock - 1) / kNgBlock)), block(kNgBlock);
-    if (vt) hipLaunchKernelGGL((k_ngram_keys<true>), grid, block, 0, st, P);
-    else hipLaunchKernelGGL((k_ngram_keys<false>), grid, block, 0, st, P);
-    return hipGetLastError();
-}
+hipError_t launch_ngram_keys(const GramKeys& P, hipStream_t st) { return launch_gram_keys(k_ngram_keys<true>, k_ngram_keys<false>, kNgBlock, P, st); }
 
 }  // namespace latok

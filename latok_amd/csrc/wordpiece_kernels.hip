@@ -11,9 +11,10 @@
 //                the count the first pass found: nothing is ever written outside the token's own range of ranks
 //   k_wp_rows    indptr[s] = rank[row_start[s]], in the caller's width
 //   k_wp_pad     one thread per cell (s, j) of the [n_str, max_length] block of the padded form
-// A token's string is found by bisection of row_start, narrowed per workgroup to the rows that touch its 256 tokens, as k_terms_emit
-// does (block_rows, row_of_token of block_ops.h; the checked record load is its token_bytes).  Table and blob are read with ordinary cached loads (they are what is worth keeping in L2), the text as aligned dwords up
-// to the one that holds the token's last byte.  A lane with a long or unknown token keeps its wave busy while the others idle:
+// A lane's token, its string and its checked byte range are lane_token of block_ops.h, where the bounds argument of that part stands:
+// a token that is not ok is skipped, so no load leaves the buffer whatever the workspace holds.  Table and blob are read with
+// ordinary cached loads (they are what is worth keeping in L2), the text as aligned dwords up to the one that holds the token's
+// last byte.  A lane with a long or unknown token keeps its wave busy while the others idle:
 // accepted in this version.  No kernel here waits for another workgroup; all stores are vector stores from plain C++.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,22 +24,6 @@
 #include "wordpiece.h"
 
 namespace latok {
-
-// token t: its string and its absolute byte range; false: the record does not lie inside the text (cannot happen with records from
-// the scatter; such a token is skipped, so no load leaves the buffer whatever the workspace holds)
-struct WpToken {
-    int64_t base, a, e;   // base = first byte of the string
-};
-__device__ __forceinline__ bool wp_token(const int64_t* __restrict__ row_off, int64_t n_str, int64_t total, const int64_t* __restrict__ row_start,
-                                         const int64_t* __restrict__ tok_spans, int64_t lo, int64_t end, int64_t t, WpToken* k) {
-    int64_t r = row_of_token(row_start, lo, end, t);
-    r = r < 0 ? 0 : (r >= n_str ? n_str - 1 : r);
-    k->base = row_off[r];
-    const TokenBytes b = token_bytes(tok_spans, t, k->base, total);
-    k->a = b.a;
-    k->e = b.e;
-    return b.ok;
-}
 
 #define LATOK_WP_VIEWS(wt)                                                                                                          \
     const VtSlot* const slots0 = reinterpret_cast<const VtSlot*>((wt).initial.slots);                                               \
@@ -50,46 +35,36 @@ __device__ __forceinline__ bool wp_token(const int64_t* __restrict__ row_off, in
     const auto tab1 = wp_table_view([slots1](uint64_t i) { return slots1[i]; }, [blob1](uint64_t i) { return blob1[i]; },          \
                                     (wt).cont.n_slots, (wt).max_len1)
 
-__global__ __launch_bounds__(kWpBlock) void k_wp_count(const uint32_t* __restrict__ text, int64_t total, const int64_t* __restrict__ row_off,
-                                                       int64_t n_str, const int64_t* __restrict__ row_start,
-                                                       const int64_t* __restrict__ tok_spans, int64_t n_tok, WordPieceTables wt,
-                                                       int64_t* __restrict__ cnt) {
-    const int64_t t0 = (int64_t)blockIdx.x * kWpBlock, t = t0 + threadIdx.x;
-    int64_t lo, end;
-    block_rows<kWpBlock>(row_start, n_str, t0, &lo, &end);
-    if (t > n_tok) return;
+__global__ __launch_bounds__(kWpBlock) void k_wp_count(TokenText T, WordPieceTables wt, int64_t* __restrict__ cnt) {
+    const LaneToken k = lane_token<kWpBlock>(T);
+    if (k.t > T.n_tok) return;
     int64_t n = 0;
-    WpToken k;
-    if (t < n_tok && wp_token(row_off, n_str, total, row_start, tok_spans, lo, end, t, &k)) {
+    if (k.b.ok) {
+        const uint32_t* const text = T.text;
         LATOK_WP_VIEWS(wt);
-        n = wp_walk([text](int64_t i) { return text[i]; }, k.a, k.e, tab0, tab1, wt.initial.seed, wt.max_chars, 0,
+        n = wp_walk([text](int64_t i) { return text[i]; }, k.b.a, k.b.e, tab0, tab1, wt.initial.seed, wt.max_chars, 0,
                     [](int, int32_t, int64_t, int64_t) {});
     }
-    cnt[t] = n;   // (t == n_tok: the entry behind the last token)
+    cnt[k.t] = n;   // (t == n_tok: the entry behind the last token)
 }
 
 template <typename OUT>
-__global__ __launch_bounds__(kWpBlock) void k_wp_emit(const uint32_t* __restrict__ text, int64_t total, const int64_t* __restrict__ row_off,
-                                                      int64_t n_str, const int64_t* __restrict__ row_start,
-                                                      const int64_t* __restrict__ tok_spans, int64_t n_tok, WordPieceTables wt, int32_t unk,
-                                                      const int64_t* __restrict__ rank, const int64_t* __restrict__ n_pieces_dev,
-                                                      int64_t cap, int32_t* __restrict__ ids, OUT* __restrict__ spans) {
+__global__ __launch_bounds__(kWpBlock) void k_wp_emit(TokenText T, WordPieceTables wt, int32_t unk, const int64_t* __restrict__ rank,
+                                                      const int64_t* __restrict__ n_pieces_dev, int64_t cap, int32_t* __restrict__ ids,
+                                                      OUT* __restrict__ spans) {
     if (*n_pieces_dev > cap) return;   // the caller's buffers hold `cap` pieces: nothing is written when the batch has more
-    const int64_t t0 = (int64_t)blockIdx.x * kWpBlock, t = t0 + threadIdx.x;
-    int64_t lo, end;
-    block_rows<kWpBlock>(row_start, n_str, t0, &lo, &end);
-    if (t >= n_tok) return;
-    WpToken k;
-    if (!wp_token(row_off, n_str, total, row_start, tok_spans, lo, end, t, &k)) return;
-    const int64_t at = rank[t];
-    const int n_mine = (int)(rank[t + 1] - at);   // (rank has n_tok + 1 entries)
+    const LaneToken k = lane_token<kWpBlock>(T);
+    if (!k.b.ok) return;
+    const int64_t at = rank[k.t];
+    const int n_mine = (int)(rank[k.t + 1] - at);   // (rank has n_tok + 1 entries)
     if (n_mine < 1 || at < 0 || at + n_mine > cap) return;
     typedef OUT out2 __attribute__((ext_vector_type(2)));
     const int64_t base = k.base;
     int32_t id0 = unk;
-    int64_t a0 = k.a, e0 = k.e;
+    int64_t a0 = k.b.a, e0 = k.b.e;
+    const uint32_t* const text = T.text;
     LATOK_WP_VIEWS(wt);
-    wp_walk([text](int64_t i) { return text[i]; }, k.a, k.e, tab0, tab1, wt.initial.seed, wt.max_chars, unk,
+    wp_walk([text](int64_t i) { return text[i]; }, k.b.a, k.b.e, tab0, tab1, wt.initial.seed, wt.max_chars, unk,
             [&id0, &a0, &e0, ids, spans, at, n_mine, base](int j, int32_t id, int64_t a, int64_t e) {
                 if (j == 0) {   // kept back: a later piece 0 replaces it
                     id0 = id;
@@ -145,27 +120,19 @@ __global__ __launch_bounds__(256) void k_wp_pad(const int32_t* __restrict__ ids,
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------
-hipError_t launch_wp_count(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
-                           const int64_t* tok_spans, int64_t n_tok, const WordPieceTables& wt, int64_t* cnt, hipStream_t st) {
-    if (n_str <= 0 || n_tok <= 0) return hipSuccess;
-    const unsigned blocks = (unsigned)((n_tok + 1 + kWpBlock - 1) / kWpBlock);   // (+ 1: the entry behind the last token)
-    hipLaunchKernelGGL(k_wp_count, dim3(blocks), dim3(kWpBlock), 0, st, reinterpret_cast<const uint32_t*>(u8), total, row_off, n_str, row_start,
-                       tok_spans, n_tok, wt, cnt);
+hipError_t launch_wp_count(const TokenText& t, const WordPieceTables& wt, int64_t* cnt, hipStream_t st) {
+    if (t.n_str <= 0 || t.n_tok <= 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((t.n_tok + 1 + kWpBlock - 1) / kWpBlock);   // (+ 1: the entry behind the last token)
+    hipLaunchKernelGGL(k_wp_count, dim3(blocks), dim3(kWpBlock), 0, st, t, wt, cnt);
     return hipGetLastError();
 }
 
-hipError_t launch_wp_emit(bool out32, const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, const int64_t* row_start,
-                          const int64_t* tok_spans, int64_t n_tok, const WordPieceTables& wt, int32_t unk_id, const int64_t* rank,
+hipError_t launch_wp_emit(bool out32, const TokenText& t, const WordPieceTables& wt, int32_t unk_id, const int64_t* rank,
                           const int64_t* n_pieces_dev, int64_t cap, int32_t* ids, void* spans, hipStream_t st) {
-    if (n_str <= 0 || n_tok <= 0 || !ids) return hipSuccess;
-    const dim3 grid((unsigned)((n_tok + kWpBlock - 1) / kWpBlock)), block(kWpBlock);
-    const uint32_t* text = reinterpret_cast<const uint32_t*>(u8);
-    if (out32)
-        hipLaunchKernelGGL((k_wp_emit<int32_t>), grid, block, 0, st, text, total, row_off, n_str, row_start, tok_spans, n_tok, wt, unk_id, rank,
-                           n_pieces_dev, cap, ids, (int32_t*)spans);
-    else
-        hipLaunchKernelGGL((k_wp_emit<int64_t>), grid, block, 0, st, text, total, row_off, n_str, row_start, tok_spans, n_tok, wt, unk_id, rank,
-                           n_pieces_dev, cap, ids, (int64_t*)spans);
+    if (t.n_str <= 0 || t.n_tok <= 0 || !ids) return hipSuccess;
+    const dim3 grid((unsigned)((t.n_tok + kWpBlock - 1) / kWpBlock)), block(kWpBlock);
+    if (out32) hipLaunchKernelGGL((k_wp_emit<int32_t>), grid, block, 0, st, t, wt, unk_id, rank, n_pieces_dev, cap, ids, (int32_t*)spans);
+    else hipLaunchKernelGGL((k_wp_emit<int64_t>), grid, block, 0, st, t, wt, unk_id, rank, n_pieces_dev, cap, ids, (int64_t*)spans);
     return hipGetLastError();
 }
 

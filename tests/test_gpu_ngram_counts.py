@@ -183,6 +183,12 @@ def test_strings_with_few_tokens_and_runs_of_empty_strings_across_a_workgroup_ed
         for r, a, b in zip(rows, want[0][:-1], want[0][1:]):
             assert len(r) >= lo or a == b                                              # fewer than min_n tokens: an empty row
         check_vocab(gpu, blobs, ng, _some_grams(rows, ng), None, "few tokens", dtypes=(np.int64,), rows=rows)
+    # a whole batch with tokens and no key (K == 0): no key launch and no reduce, the rows are still delivered -- all empty
+    blobs, ng = [b"a b", b"c", b""], (3, 3, 0x20)
+    for check in (lambda: check_hashed(gpu, blobs, ng, 1 << 20, 0, True, "tokens, no key", dtypes=(np.int64, np.int32)),
+                  lambda: check_vocab(gpu, blobs, ng, [b"a b c", b"a"], None, "tokens, no key")):
+        rows, want = check()                                                           # (rc == 0, n_grams == 0 and the guard bands: _compare)
+        assert [len(r) for r in rows] == [2, 1, 0] and len(want[1]) == 0 and not want[0].any() and all(not w.any() for w in want[3:])
 
 
 # ---- 3. bigram shapes ----------------------------------------------------------------------------------------------------------

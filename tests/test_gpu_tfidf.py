@@ -152,6 +152,13 @@ def test_widths_pointers_fold_and_ngrams(shapes, vocab):
             for smooth, sub, norm in ((True, False, "l2"), (False, True, "l1")):
                 _hold(batch.tfidf_utf8_batch(sub_docs, gv, gi, smooth, sub, norm, ngram_range=rng), c,
                       ref.idf(gi.df(), gi.n_docs, smooth), sub, norm, ("ngram", rng))
+        # a batch with tokens and no key (no string has three tokens): an empty matrix; documents all the same, df as it was
+        none = [b"a b", b"c", b""]
+        got = batch.tfidf_utf8_batch(none, gv, gi, ngram_range=(3, 3))
+        assert got[0].tolist() == [0, 0, 0, 0] and got[1].size == 0 and got[2].size == 0 and got[2].dtype == np.float32 and not got[3].any()
+        df_before, docs_before = gi.df().copy(), gi.n_docs
+        assert gi.update_utf8(none, vocab=gv, ngram_range=(3, 3)) == 0
+        assert gi.n_docs == docs_before + len(none) and np.array_equal(gi.df(), df_before)
 
 
 def _i32(u):
