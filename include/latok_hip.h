@@ -526,7 +526,7 @@ int latok_hashed_tfidf_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
  * Lower-casing, accent stripping, control-character cleaning and CJK spacing (the normalizer of BERT's BasicTokenizer) are a call of
  * their own, latok_fold_utf8_bytes_batch below: its output, left on the device, is this call's input, and an uncased vocabulary is
  * served by folding first.  Out of scope: the punctuation split of BERT's BasicTokenizer -- tokens are latok's --, the final-sigma
- * rule of lower-casing, BPE and Unigram models, a flow form, sentence pairs. */
+ * rule of lower-casing, Unigram models, a flow form, sentence pairs.  Byte-level BPE is a call of its own: latok_bpe_* below. */
 typedef struct latok_wordpiece latok_wordpiece;
 int latok_wordpiece_create(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
                            const int32_t* word_ids /* may be NULL */, const uint8_t* prefix, int prefix_len, int max_chars, uint32_t seed,
@@ -544,6 +544,56 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
                                             int32_t sep_id, int32_t pad_id, int32_t* input_ids_out /* [n_str*max_length] */,
                                             int32_t* lengths_out /* [n_str] */, int64_t* n_pieces_out /* may be NULL */, int flags,
                                             void* stream);
+
+/* Byte-level BPE in byte space: the merge-rank ids a GPT-family model takes (GPT-2 / RoBERTa, the .tiktoken files of the newer
+ * models), for every token of a batch.
+ * A BPE VOCABULARY is an ordered list of byte strings w_0 .. w_(V-1), in the words / word_off layout latok_vocab_create takes.  The
+ * RANK of a word is its position in the list; of duplicates the first wins, so the lowest rank is kept; the empty word gets no slot.
+ * word_ids is an optional int32 array (NULL means id = rank); every int32 is a legal id.  The 32-bit seed places the words in the
+ * table and changes no id.  max_bytes is in 1 .. 4096, lead_space is 0 or 1.  This is tiktoken's model: a .tiktoken file is exactly
+ * such a list, and GPT-2's vocab.json + merges.txt convert to one.  The object is one immutable table of the kind latok_vocab holds
+ * (the slot holds the rank), an int32 array rank -> id and the byte length of the longest word.
+ * A token is what latok_token_spans_utf8_bytes_batch yields: bytes [a, e) of string s.  With lead_space = 1 a token with a > 0
+ * (string-relative) whose byte a - 1 is 0x20 is taken as [a - 1, e): the " word" convention of GPT-style vocabularies.  Any other
+ * whitespace is dropped, as everywhere else in the library.  The cut, per token T = bytes[a:e], L = e - a:
+ *   1. L > max_bytes: ONE piece (unk_id, a, e).
+ *   2. T is a word: ONE piece (id(T), a, e) -- tiktoken's shortcut; step 3 does not imply it (a word need not be reachable by merges).
+ *   3. otherwise the parts are the L single bytes.  Repeat: among all ADJACENT parts (p_i, p_(i+1)) whose concatenation is a word,
+ *      take the pair whose concatenation has the LOWEST rank; of equal ranks (the same bytes at several places) the LEFTMOST;
+ *      replace the two parts by their concatenation.  Stop when no adjacent pair concatenates to a word.
+ *   4. emit every remaining part in order as (id, start, end).  A part that is not a word emits unk_id: this can only be a single
+ *      byte, since every merged part is a word by construction.  The other parts keep their ids: a token is NOT withdrawn as a whole,
+ *      unlike WordPiece.
+ * Bytes are bytes: nothing looks at UTF-8 structure, and a character may be split across pieces.  V = 0 is accepted: every token
+ * becomes L unk pieces, or one when L > max_bytes.  Exact as the ids call is: the hash finds the slot, the bytes decide.
+ * latok_bpe_create takes HOST pointers and refuses, before any device work, what latok_vocab_create refuses and a max_bytes outside
+ * 1 .. 4096 or a lead_space other than 0 / 1.  The object may be used by any context of its device, concurrently;
+ * latok_bpe_destroy drains the current context first, like latok_vocab_destroy.  latok_bpe_info reports the word count as given, the
+ * slots, the longest word, max_bytes, lead_space, the seed and the device; any output pointer may be NULL.
+ * The two calls have the contract of the WordPiece calls above, word for word: indptr / ids / spans as there, host pointers or
+ * LATOK_DEVICE_PTRS, total_bytes = -1, the check of the object's device, LATOK_OUT_INT32 for indptr and spans, any other flag bit
+ * refused before any device work; the capacity protocol in PIECES (cap too small: nothing is written to ids or spans, indptr stays
+ * valid, the need is in *n_pieces_out, LATOK_ERR_INVALID; cap = 0 with ids_out = NULL is a size query; ids_out = NULL with cap > 0 is
+ * refused); a batch with 2^31 pieces or more is refused; n_str = 0 or total_bytes = 0 as there.  The PADDED form writes the
+ * [n_str, max_length] int32 block with bos_id / eos_id where the WordPiece call puts cls_id / sep_id (add_special), and lengths_out.
+ * Out of scope: GPT-2's regex pre-tokenizer -- tokens are latok's, and runs of whitespace are not encoded --, a vocab.json /
+ * merges.txt loader, special-token strings inside the text, Unigram models, folding inside the call, a flow form, decoding ids back
+ * to text. */
+typedef struct latok_bpe latok_bpe;
+int latok_bpe_create(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
+                     const int32_t* word_ids /* may be NULL */, int max_bytes, int lead_space, uint32_t seed, latok_bpe** bpe_out);
+int latok_bpe_destroy(latok_bpe* bpe);
+int latok_bpe_info(const latok_bpe* bpe, int64_t* n_words, int64_t* n_slots, int64_t* max_len, int* max_bytes, int* lead_space,
+                   uint32_t* seed, int* device);
+int latok_bpe_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_bpe* bpe,
+                                   int32_t unk_id, int64_t* indptr_out /* [n_str+1] */, int32_t* ids_out,
+                                   int64_t* spans_out /* may be NULL */, int64_t cap, int64_t* n_pieces_out,
+                                   int64_t* n_tokens_out /* may be NULL */, int flags, void* stream);
+int latok_bpe_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                      const latok_bpe* bpe, int32_t unk_id, int64_t max_length, int add_special, int32_t bos_id,
+                                      int32_t eos_id, int32_t pad_id, int32_t* input_ids_out /* [n_str*max_length] */,
+                                      int32_t* lengths_out /* [n_str] */, int64_t* n_pieces_out /* may be NULL */, int flags,
+                                      void* stream);
 
 /* Case folding and accent stripping in byte space: UTF-8 in, folded UTF-8 out, what an uncased vocabulary (bert-base-uncased and its
  * relatives) or a lower-casing vectorizer needs in front of the token calls above.  `fold` is a set of LATOK_FOLD_* bits in an

@@ -86,6 +86,12 @@ SIGNATURES = {
     "latok_wordpiece_ids_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
     "latok_wordpiece_padded_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, i64, ci, C.c_int32, C.c_int32, C.c_int32, vp, vp,
                                                      C.POINTER(i64), ci, vp]),
+    "latok_bpe_create": (ci, [vp, vp, i64, vp, ci, ci, C.c_uint32, C.POINTER(vp)]),
+    "latok_bpe_destroy": (ci, [vp]),
+    "latok_bpe_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_uint32), C.POINTER(ci)]),
+    "latok_bpe_ids_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
+    "latok_bpe_padded_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, i64, ci, C.c_int32, C.c_int32, C.c_int32, vp, vp,
+                                               C.POINTER(i64), ci, vp]),
     "latok_fold_utf8_bytes_batch": (ci, [vp, vp, i64, i64, ci, vp, i64, vp, C.POINTER(i64), ci, vp]),
     "latok_counter_create": (ci, [i64, ci, C.c_uint32, C.POINTER(vp)]),
     "latok_counter_destroy": (ci, [vp]),

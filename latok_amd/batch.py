@@ -630,7 +630,7 @@ def _size_then_fill(call, n, alloc):
 
 
 class _DeviceObject:
-    """What Vocab, WordPiece, Idf and TokenCounter share: ``handle`` (None once closed) of an object that ``_lib`` made and its call
+    """What Vocab, WordPiece, BPE, Idf and TokenCounter share: ``handle`` (None once closed) of an object that ``_lib`` made and its call
     named ``_destroy`` frees -- by ``close()``, on leaving a ``with`` block, or with the object.  ``_closed``: what ``_open()`` says."""
 
     handle = _destroy = _closed = None
@@ -1162,8 +1162,8 @@ class WordPiece(_DeviceObject):
     Bytes are compared verbatim: the object itself does no lower-casing and no accent stripping.  An uncased vocabulary
     (``bert-base-uncased``) is served by the ``fold=FOLD_UNCASED`` keyword of the ``wordpiece_*`` calls, which folds the batch on the
     device first (``fold_utf8_batch``; fold the words the same way if the file is not folded already).  Still out of scope: the
-    punctuation split of BERT's BasicTokenizer (tokens are latok's), the final-sigma rule, BPE and Unigram models, a flow form and
-    sentence pairs.  Immutable; ``len()`` is the number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
+    punctuation split of BERT's BasicTokenizer (tokens are latok's), the final-sigma rule, Unigram models, a flow form and
+    sentence pairs; byte-level BPE is a class of its own, ``BPE``.  Immutable; ``len()`` is the number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
 
     _destroy, _closed = "latok_wordpiece_destroy", "wp must be an open latok_amd.batch.WordPiece"
 
@@ -1267,6 +1267,126 @@ def wordpiece_encode_utf8_batch(blobs, wp, max_length, cls_id=None, sep_id=None,
         input_ids, lengths = b.out((n_str, max_length), np.int32), b.out(n_str, np.int32, True)
         _lib.check(b.lib.latok_wordpiece_padded_utf8_bytes_batch(b.u8, b.off, n_str, b.total, handle, unk_id, max_length, 1 if special else 0, cls_id,
                                                                  sep_id, pad_id, _arg(input_ids), _arg(lengths), None, b.flags, None))
+        input_ids, lengths = b.fetch(input_ids), b.fetch(lengths)
+    mask = (np.arange(max_length, dtype=np.int32)[None, :] < lengths[:, None]).astype(np.int32)
+    return input_ids, mask
+
+
+# byte-level BPE: every token cut by the merge ranks of a GPT-family vocabulary, on the device -- as CSR rows or as the padded [n, L] block
+class BPE(_DeviceObject):
+    """A byte-level BPE vocabulary on the device of the current context (``latok_bpe_create``): ``words`` is the list of ``bytes`` (or
+    ``str``, encoded as UTF-8 with surrogatepass) in RANK order -- a word's rank is its position, of a duplicate the first wins --,
+    ``ids`` an optional int32 per word (default: its rank), ``max_bytes`` in 1 .. 4096 (a longer token is one unknown piece),
+    ``lead_space``: a token that follows a 0x20 byte inside its string takes that byte in front (the ``" word"`` convention of
+    GPT-style vocabularies), ``seed`` the 32-bit seed of the table's hash.  This is ``tiktoken``'s model.  Out of scope: GPT-2's regex
+    pre-tokenizer (tokens are latok's; runs of whitespace are not encoded), a ``vocab.json`` / ``merges.txt`` loader, special-token
+    strings inside the text, Unigram models, a ``fold=`` keyword, a flow form, ``DevicePool`` forms, decoding.  Immutable; ``len()`` is the
+    number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
+
+    _destroy, _closed = "latok_bpe_destroy", "bpe must be an open latok_amd.batch.BPE"
+
+    def __init__(self, words, ids=None, max_bytes=4096, lead_space=False, seed=0):
+        seed = _seed32(seed)
+        if not isinstance(max_bytes, (int, np.integer)) or isinstance(max_bytes, bool) or not 1 <= int(max_bytes) <= 4096:
+            raise ValueError("max_bytes must be an int in 1 .. 4096")
+        if not isinstance(lead_space, (bool, np.bool_)) and lead_space not in (0, 1):
+            raise ValueError("lead_space must be a bool")
+        data, off, ids = _pack_words(words, ids)
+        lib = _lib.ensure_init()
+        h = C.c_void_p()
+        _lib.check(lib.latok_bpe_create(_ptr(data) if data.size else None, _ptr(off), off.size - 1, _ptr(ids) if ids is not None else None,
+                                        int(max_bytes), 1 if lead_space else 0, seed, C.byref(h)))
+        self._lib, self.handle, self.seed, self._n = lib, h, seed, off.size - 1
+        self.max_bytes, self.lead_space = int(max_bytes), bool(lead_space)
+
+    @classmethod
+    def from_tiktoken_file(cls, path, **kw):
+        """a ``.tiktoken`` file: lines of ``base64(token) rank``.  The lines are sorted by rank; a line's rank must then equal its
+        position, else ValueError."""
+        import base64
+        pairs = []
+        with open(path, "rb") as f:
+            for line in f.read().splitlines():
+                if not line.strip():
+                    continue
+                fields = line.split()
+                if len(fields) != 2:
+                    raise ValueError("a line of a .tiktoken file is `base64(token) rank`: %r" % line[:60])
+                try:
+                    pairs.append((int(fields[1]), base64.b64decode(fields[0], validate=True)))
+                except Exception:
+                    raise ValueError("a line of a .tiktoken file is `base64(token) rank`: %r" % line[:60]) from None
+        pairs.sort(key=lambda p: p[0])
+        for i, (rank, _) in enumerate(pairs):
+            if rank != i:
+                raise ValueError("the ranks of a .tiktoken file must be 0 .. n - 1, each once: position %d holds rank %d" % (i, rank))
+        return cls([w for _, w in pairs], **kw)
+
+    def info(self):
+        """dict of what ``latok_bpe_info`` reports"""
+        v = [C.c_int64(0) for _ in range(3)]
+        mb, ls, seed, dev = C.c_int(0), C.c_int(0), C.c_uint32(0), C.c_int(0)
+        _lib.check(self._lib.latok_bpe_info(self._open(), *[C.byref(x) for x in v], C.byref(mb), C.byref(ls), C.byref(seed), C.byref(dev)))
+        return dict(n_words=v[0].value, n_slots=v[1].value, max_len=v[2].value, max_bytes=mb.value, lead_space=ls.value, seed=seed.value,
+                    device=dev.value)
+
+    def __len__(self):
+        return self._n
+
+
+def bpe_ids_utf8_csr(utf8, byte_off, bpe, unk_id=-1, dtype=np.int64, spans=True):
+    """(indptr[n + 1], ids int32[n_pieces], spans[n_pieces, 2] or None): the BPE ids of every string -- each token (the byte slices
+    token_spans_utf8_bytes_csr reports, with the space in front under ``lead_space``) is one piece if it is a word of ``bpe``, else
+    its bytes merged pair by pair, lowest rank first and leftmost among equals; a byte that is no word is an ``unk_id`` piece, a token of
+    more than ``max_bytes`` bytes ONE.  spans[r] = piece r's byte range inside its string.  indptr and spans in ``dtype``.  Cut on the
+    device (``latok_bpe_ids_utf8_bytes_batch``): the size query, then the fill."""
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    unk_id = _unk32(unk_id)
+    dt, flags = _out_dtype(dtype)
+    handle = _handle_of(BPE, bpe, "bpe")
+    with _HostBatch(utf8, byte_off) as b:
+        indptr, n = b.out(b.n_str + 1, dt, True), C.c_int64(0)
+
+        def call(ids=None, sp=None, cap=0):
+            return b.lib.latok_bpe_ids_utf8_bytes_batch(b.u8, b.off, b.n_str, b.total, handle, unk_id, _arg(indptr), ids, sp, cap, C.byref(n), None,
+                                                        flags | b.flags, None)
+
+        _, (ids, sp) = _size_then_fill(call, n, lambda k: (b.out(k, np.int32), b.out((k, 2), dt) if spans else None))
+        return b.fetch(indptr), b.fetch(ids), (b.fetch(sp) if spans else None)
+
+
+def bpe_ids_utf8_batch(blobs, bpe, unk_id=-1):
+    """list[bytes] (UTF-8) -> (indptr, ids, spans) of bpe_ids_utf8_csr, int64 ('' and whitespace-only -> empty rows)"""
+    unk_id = _unk32(unk_id)
+    _handle_of(BPE, bpe, "bpe")
+    utf8, byte_off = pack_utf8(blobs)
+    return bpe_ids_utf8_csr(utf8, byte_off, bpe, unk_id, np.int64, True)
+
+
+def bpe_ids_batch(texts, bpe, unk_id=-1):
+    """list[str] -> (indptr, ids, spans): bpe_ids_utf8_batch of the strings' UTF-8 ("surrogatepass"); the spans are in bytes"""
+    return bpe_ids_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], bpe, unk_id)
+
+
+def bpe_encode_utf8_batch(blobs, bpe, max_length, bos_id=None, eos_id=None, pad_id=0, unk_id=-1):
+    """list[bytes] (UTF-8) -> (input_ids int32[n, max_length], attention_mask int32[n, max_length]): what a GPT-family model takes.
+    Row s = ``bos_id``, the first pieces of string s, ``eos_id``, then ``pad_id``; the two specials are added when BOTH are given and
+    omitted when both are None.  A longer row is truncated to ``max_length`` cells, specials included.  attention_mask is 1 on the
+    cells in front of the padding.  One call of ``latok_bpe_padded_utf8_bytes_batch``."""
+    unk_id, pad_id = _unk32(unk_id), _unk32(pad_id)
+    if (bos_id is None) != (eos_id is None):
+        raise ValueError("bos_id and eos_id go together: give both or neither")
+    special = bos_id is not None
+    bos_id, eos_id = (_unk32(bos_id), _unk32(eos_id)) if special else (0, 0)
+    if not isinstance(max_length, (int, np.integer)) or isinstance(max_length, bool) or not 1 + 2 * special <= int(max_length) <= 0x7FFFFFFF:
+        raise ValueError("max_length must be an int >= %d" % (1 + 2 * special))
+    handle = _handle_of(BPE, bpe, "bpe")
+    utf8, byte_off = pack_utf8(blobs)
+    n_str, max_length = len(blobs), int(max_length)
+    with _HostBatch(utf8, byte_off) as b:
+        input_ids, lengths = b.out((n_str, max_length), np.int32), b.out(n_str, np.int32, True)
+        _lib.check(b.lib.latok_bpe_padded_utf8_bytes_batch(b.u8, b.off, n_str, b.total, handle, unk_id, max_length, 1 if special else 0, bos_id,
+                                                           eos_id, pad_id, _arg(input_ids), _arg(lengths), None, b.flags, None))
         input_ids, lengths = b.fetch(input_ids), b.fetch(lengths)
     mask = (np.arange(max_length, dtype=np.int32)[None, :] < lengths[:, None]).astype(np.int32)
     return input_ids, mask

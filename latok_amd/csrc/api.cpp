@@ -36,6 +36,7 @@
 #include "ngram_text.h"
 #include "count_table.h"
 #include "wordpiece.h"
+#include "bpe.h"
 #include "fold_map.h"
 #include "fold_tables.inc"
 #include "tfidf_weight.h"
@@ -231,6 +232,7 @@ struct Workspace {
     DevBuf jbody, jhead;   // joined token text: the body / head planes over the bytes (k_join_counts)
     DevBuf tkeys, tkeys2, trows;   // term counts: one key per token, the long rows' second buffer, five int64 arrays over the rows
     DevBuf wpspans, wpcnt, wprank, wpids;   // WordPiece: per token its span record, piece count and piece rank; the padded form's ids
+    DevBuf bpemask;   // BPE (which uses the WordPiece buffers as well): per token of at most 64 bytes its final part-start mask
     DevBuf ngrows;   // word n-grams: gram counts and row starts in key space (the span records share wpspans, the keys tkeys / tkeys2)
     DevBuf tfptr, tfidx, tfval, tfctl;   // TF-IDF: a host caller's CSR on the device (indptr, indices, data) and the error word of k_csr_check
     // the single-pass scan of k_word_counts_scan keeps its look-back state (chain: per workgroup, chain_ctl: {ticket
@@ -241,7 +243,7 @@ struct Workspace {
     void release() {
         for (DevBuf* b : {&summ, &seg_agg, &fix_count, &tile_first, &bits, &space, &kept, &wcnt, &wpref, &bases, &scalar, &chain,
                           &chain_ctl, &codes, &widened, &lead, &bspace, &cpbits, &cpspace, &cprow, &jbody, &jhead, &tkeys,
-                          &tkeys2, &trows, &wpspans, &wpcnt, &wprank, &wpids, &ngrows, &tfptr, &tfidx, &tfval, &tfctl})
+                          &tkeys2, &trows, &wpspans, &wpcnt, &wprank, &wpids, &bpemask, &ngrows, &tfptr, &tfidx, &tfval, &tfctl})
             b->release();
         scan_epoch = chain_seen = chain_ctl_seen = 0;
         chain_ready = false;
@@ -252,7 +254,7 @@ struct WsNeed {
     size_t bytes;   // 0: the batch does not use the buffer
 };
 constexpr int kTileNeeds = 4;   // the first entries of ws_needs: the tile stage
-constexpr int kWsNeeds = 34;
+constexpr int kWsNeeds = 35;
 // What a batch asks of its workspace beyond the tile stage.  token spans (spans) add the SPACE and kept planes, featurize (feats)
 // the code bytes, and narrow units read by featurize (widen) a UTF-32 copy.  cp_rows > 0: the units are UTF-8 bytes whose results
 // are reported in code points (cp_rows = n_str + 1): every buffer is sized by the byte count, which bounds the code-point count.
@@ -261,6 +263,7 @@ constexpr int kWsNeeds = 34;
 // waits for before it sizes the two key buffers.  wp_tokens: the token total again, for the WordPiece calls (which use the first two
 // row arrays of term_rows): 16 bytes of span record, 8 of piece count and 8 of piece rank per token, one entry more in the last two,
 // and a scan state for that many entries; wp_pieces: the piece total, which the padded form waits for before it sizes its ids.
+// bpe_tokens: the token total once more, for the BPE calls (which set wp_tokens too): 8 bytes of part-start mask per token.
 // Word n-grams (which use the row arrays of term_rows as well): ng_tokens, the token total: 16 bytes of span record per token, in the
 // buffer the WordPiece calls keep theirs in; ng_rows > 0 (= n_str + 1): the gram counts and the row starts in key space; ng_keys:
 // the key total, which the n-gram call waits for before it sizes the two key buffers -- the term counts' own, one key per gram.
@@ -272,6 +275,7 @@ struct WsShape {
     int64_t cp_rows = 0;
     int64_t term_rows = 0, term_tokens = 0;
     int64_t wp_tokens = 0, wp_pieces = 0;
+    int64_t bpe_tokens = 0;
     int64_t ng_tokens = 0, ng_rows = 0, ng_keys = 0;
     bool tf_ctl = false;
     int64_t tf_ptr_bytes = 0, tf_entries = 0;
@@ -315,6 +319,7 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const 
              {&w.wpcnt, shape.wp_tokens > 0 ? (size_t)(shape.wp_tokens + 1) * 8 : 0},
              {&w.wprank, shape.wp_tokens > 0 ? (size_t)(shape.wp_tokens + 1) * 8 : 0},
              {&w.wpids, shape.wp_pieces > 0 ? (size_t)shape.wp_pieces * 4 : 0},
+             {&w.bpemask, shape.bpe_tokens > 0 ? (size_t)shape.bpe_tokens * 8 : 0},
              {&w.tfptr, (size_t)shape.tf_ptr_bytes},
              {&w.tfidx, shape.tf_entries > 0 ? (size_t)shape.tf_entries * 4 + 16 : 0},
              {&w.tfval, shape.tf_entries > 0 ? (size_t)shape.tf_entries * 4 + 16 : 0},
@@ -752,7 +757,7 @@ int check_object(const Ctx& g, const Handle* handle, const char* null_msg, const
     if (!*v) return fail(LATOK_ERR_INVALID, "%s", null_msg);
     return check_device(g, "vocabulary", (*v)->device);
 }
-// the word list of latok_vocab_create and latok_wordpiece_create; needs no device
+// the word list of latok_vocab_create, latok_wordpiece_create and latok_bpe_create; needs no device
 int check_word_list(const uint8_t* words, const int64_t* word_off, int64_t n_words) {
     if (n_words < 0 || n_words >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "n_words must be in 0 .. 2^31 - 1");
     if (!word_off) return fail(LATOK_ERR_INVALID, "word_off is NULL");
@@ -2433,7 +2438,7 @@ int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
 
 /* vocabularies: built on the host (vocab_table.h), uploaded once, read only afterwards */
 static int flow_drain(Ctx& g);   // batch flow (below): its three streams
-// The end of a shared object (latok_vocab, latok_wordpiece, latok_idf, latok_counter; `mu`: the lock of a mutable one).  The current
+// The end of a shared object (latok_vocab, latok_wordpiece, latok_bpe, latok_idf, latok_counter; `mu`: the lock of a mutable one).  The current
 // context's own work on it is waited for first: its stream and its flow; whatever they report, the object is freed.
 extern "C++" template <class Obj>
 static int destroy_object(Ctx& g, Obj* obj, std::mutex Obj::*mu = nullptr) {
@@ -3244,9 +3249,89 @@ int latok_wordpiece_info(const latok_wordpiece* wp, int64_t* n_words, int64_t* n
     return LATOK_OK;
 }
 
+/* Byte-level BPE in byte space (latok_bpe_ids_utf8_bytes_batch, latok_bpe_padded_utf8_bytes_batch): the calls of the WordPiece pair with
+ * another cut.  The object holds one vocab_table.h table whose id slot is the word's rank, the rank -> id array and the longest word
+ * (bpe.h), built on the host, uploaded once, read only afterwards.  The stream is enqueue_wordpiece's, with k_bpe_count / k_bpe_emit
+ * (bpe_kernels.hip) in place of k_wp_count / k_wp_emit and 8 bytes of part-start mask per token between the two. */
+struct Bpe {                       // latok_bpe: immutable once created
+    int device = -1;
+    int64_t n_words = 0;
+    uint32_t max_len = 0;
+    int max_bytes = 0, lead_space = 0;
+    uint32_t seed = 0;
+    DevTable table;
+    DevMem rank_id;
+};
+int latok_bpe_create(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, int max_bytes, int lead_space,
+                     uint32_t seed, latok_bpe** bpe_out) {
+    LATOK_ENTER();
+    // what needs no device is refused first
+    if (!bpe_out) return fail(LATOK_ERR_INVALID, "bpe_out is NULL");
+    *bpe_out = nullptr;
+    if (max_bytes < 1 || max_bytes > kBpeMaxBytes) return fail(LATOK_ERR_INVALID, "max_bytes must be in 1 .. %d", kBpeMaxBytes);
+    if (lead_space != 0 && lead_space != 1) return fail(LATOK_ERR_INVALID, "lead_space must be 0 or 1");
+    int rc = check_word_list(words, word_off, n_words);
+    if (rc || (rc = need_init(g))) return rc;
+    BpeTables t;
+    Bpe* v = nullptr;
+    try {
+        bpe_build(words, word_off, n_words, word_ids, seed, &t);
+        v = new Bpe();
+    } catch (const std::bad_alloc&) {
+        return fail(LATOK_ERR_NOMEM, "out of host memory");
+    }
+    v->device = g.device;
+    v->n_words = n_words;
+    v->max_len = t.max_len;
+    v->max_bytes = max_bytes;
+    v->lead_space = lead_space;
+    v->seed = seed;
+    if ((rc = v->table.upload(t.table, g.stream)) == LATOK_OK) {
+        const size_t bytes = t.rank_id.size() * 4;
+        hipError_t e = v->rank_id.alloc(bytes);
+        if (e != hipSuccess) rc = fail(LATOK_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+        else if ((e = hipMemcpyAsync(v->rank_id.p, t.rank_id.data(), bytes, hipMemcpyHostToDevice, g.stream)) != hipSuccess)
+            rc = fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(g.stream);   // (the host tables die with this call, and every context may use the object at once)
+    if (!rc && e != hipSuccess) rc = fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
+    if (rc) {
+        delete v;
+        return rc;
+    }
+    *bpe_out = reinterpret_cast<latok_bpe*>(v);
+    return LATOK_OK;
+}
+
+int latok_bpe_destroy(latok_bpe* bpe) {
+    LATOK_ENTER();
+    return destroy_object(g, reinterpret_cast<Bpe*>(bpe));
+}
+
+int latok_bpe_info(const latok_bpe* bpe, int64_t* n_words, int64_t* n_slots, int64_t* max_len, int* max_bytes, int* lead_space, uint32_t* seed,
+                   int* device) {
+    const Bpe* v = reinterpret_cast<const Bpe*>(bpe);
+    if (!v) return fail(LATOK_ERR_INVALID, "bpe is NULL");
+    if (n_words) *n_words = v->n_words;
+    if (n_slots) *n_slots = (int64_t)v->table.n_slots;
+    if (max_len) *max_len = v->max_len;
+    if (max_bytes) *max_bytes = v->max_bytes;
+    if (lead_space) *lead_space = v->lead_space;
+    if (seed) *seed = v->seed;
+    if (device) *device = v->device;
+    return LATOK_OK;
+}
+
+// the object of a piece call: a WordPiece vocabulary or a BPE one (exactly one is set), and the route numbers of its two forms
+struct PieceCut {
+    const WordPiece* wp = nullptr;
+    const Bpe* bpe = nullptr;
+    int route_ids = 11, route_padded = 12;
+};
+
 struct WordPieceCall {
     Batch b;                       // UTF-8 bytes on the device (16-byte aligned), byte offsets, total in bytes (> 0), n_str > 0
-    const WordPiece* wp = nullptr;
+    PieceCut cut;
     int32_t unk = 0;
     void* indptr = nullptr;        // [n_str + 1]; NULL: the padded form
     int32_t* ids = nullptr;        // NULL: a size query (ids form)
@@ -3274,7 +3359,8 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
         return rc;
     int64_t* d_total = (int64_t*)w.scalar.p;
     const int64_t n_tok = a.n_tokens;
-    if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok}).data(), kWsNeeds)))
+    if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok, .bpe_tokens = a.cut.bpe ? n_tok : 0}).data(),
+                                    kWsNeeds)))
         return rc;
     int64_t* d_cnt = (int64_t*)w.trows.p;       // token count of every string, one zero entry behind them
     int64_t* d_start = d_cnt + (n_str + 1);     // their exclusive scan: d_start[n_str] = the token total
@@ -3286,25 +3372,40 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
         latok::TokenText text;
         if ((rc = enqueue_token_rows(w, a.b, t, n_tok, d_cnt, d_start, d_err, st, &text))) return rc;
         latok::WordPieceTables wt;
-        wt.initial = a.wp->initial.view(a.wp->seed);
-        wt.cont = a.wp->cont.view(a.wp->seed);
-        wt.max_len0 = a.wp->max_len0;
-        wt.max_len1 = a.wp->max_len1;
-        wt.max_chars = a.wp->max_chars;
-        HIP_TRY(latok::launch_wp_count(text, wt, d_pcnt, st));
+        latok::BpeTable bt;
+        uint64_t* d_mask = (uint64_t*)w.bpemask.p;
+        if (const Bpe* b = a.cut.bpe) {
+            bt.table = b->table.view(b->seed);
+            bt.rank_id = b->rank_id.as<const int32_t>();
+            bt.n_words = b->n_words;
+            bt.max_len = b->max_len;
+            bt.max_bytes = b->max_bytes;
+            bt.lead_space = b->lead_space;
+            HIP_TRY(latok::launch_bpe_count(text, bt, d_pcnt, d_mask, st));
+        } else {
+            const WordPiece* v = a.cut.wp;
+            wt.initial = v->initial.view(v->seed);
+            wt.cont = v->cont.view(v->seed);
+            wt.max_len0 = v->max_len0;
+            wt.max_len1 = v->max_len1;
+            wt.max_chars = v->max_chars;
+            HIP_TRY(latok::launch_wp_count(text, wt, d_pcnt, st));
+        }
         if ((rc = enqueue_row_scan(w, d_pcnt, n_tok + 1, d_prank, d_total + 5, a.p_tot + 3, d_err + 1, st))) return rc;
         int32_t* ids = a.ids;
         int64_t cap = a.cap;
         if (a.padded) {
             if ((rc = second_sized_total(w, a.h_tot, 3, st, nullptr, &cap))) return rc;   // wait 2 (padded form): the piece total sizes the ids
             if (cap >= (1ll << 31)) return LATOK_OK;   // (the caller refuses it)
-            if ((rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok, .wp_pieces = cap}).data(),
+            if ((rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok, .wp_pieces = cap,
+                                                              .bpe_tokens = a.cut.bpe ? n_tok : 0}).data(),
                                 kWsNeeds)))
                 return rc;
             ids = (int32_t*)w.wpids.p;
             d_ids = ids;
         }
-        if (ids) HIP_TRY(latok::launch_wp_emit(a.o32, text, wt, a.unk, d_prank, d_total + 5, cap, ids, a.spans, st));
+        if (ids && a.cut.bpe) HIP_TRY(latok::launch_bpe_emit(a.o32, text, bt, a.unk, d_prank, d_mask, d_total + 5, cap, ids, a.spans, st));
+        else if (ids) HIP_TRY(latok::launch_wp_emit(a.o32, text, wt, a.unk, d_prank, d_total + 5, cap, ids, a.spans, st));
         if (a.indptr) HIP_TRY(latok::launch_wp_rows(a.o32, d_start, d_prank, n_str, n_tok, a.indptr, st));
     } else if (a.indptr) {
         HIP_TRY(hipMemsetAsync(a.indptr, 0, (size_t)(n_str + 1) * (a.o32 ? 4 : 8), st));   // (no token: every row is empty)
@@ -3314,9 +3415,11 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
                                      a.input_ids, a.lengths, st));
     return LATOK_OK;
 }
-int latok_wordpiece_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
-                                         const latok_wordpiece* wp, int32_t unk_id, int64_t* indptr_out, int32_t* ids_out, int64_t* spans_out,
-                                         int64_t cap, int64_t* n_pieces_out, int64_t* n_tokens_out, int flags, void* stream) {
+// the body of latok_wordpiece_ids_utf8_bytes_batch and latok_bpe_ids_utf8_bytes_batch; Handle / Obj: the object's two types
+extern "C++" template <class Obj, class Handle>
+static int piece_ids_call(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const Handle* handle,
+                          const char* null_msg, PieceCut cut, const Obj* PieceCut::*slot, int32_t unk_id, int64_t* indptr_out, int32_t* ids_out,
+                          int64_t* spans_out, int64_t cap, int64_t* n_pieces_out, int64_t* n_tokens_out, int flags, void* stream) {
     LATOK_ENTER();
     if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
     int rc = need_init(g);
@@ -3327,8 +3430,9 @@ int latok_wordpiece_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byt
     if (!indptr_out) return fail(LATOK_ERR_INVALID, "indptr_out is NULL");
     if (cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
     if (!ids_out && cap > 0) return fail(LATOK_ERR_INVALID, "ids_out is NULL but cap > 0 (a size query passes cap = 0)");
-    const WordPiece* v = nullptr;
-    if ((rc = check_object(g, wp, "wp is NULL", &v))) return rc;
+    const Obj* v = nullptr;
+    if ((rc = check_object(g, handle, null_msg, &v))) return rc;
+    cut.*slot = v;
     BytesCall c;   // (elt: the width of indptr and of one field of a span; an id is 4 bytes in every mode)
     if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
     const bool dev = c.dev;
@@ -3336,10 +3440,10 @@ int latok_wordpiece_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byt
     if (dev && ((uintptr_t)indptr_out & (elt - 1)) != 0) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
     if (c.empty) return zero_counts(dev, indptr_out, (size_t)(n_str + 1) * elt, c.st, true);   // no byte, no piece
     if (dev && (((uintptr_t)spans_out & (2 * elt - 1)) != 0 || ((uintptr_t)ids_out & 3) != 0)) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    if ((rc = c.stage(g, 11, WsShape{.spans = true, .term_rows = n_str + 1}, kClearSized))) return rc;
+    if ((rc = c.stage(g, cut.route_ids, WsShape{.spans = true, .term_rows = n_str + 1}, kClearSized))) return rc;
     WordPieceCall a;
     a.b = c.d;
-    a.wp = v;
+    a.cut = cut;
     a.unk = unk_id;
     a.indptr = indptr_out;
     a.ids = ids_out;
@@ -3367,11 +3471,25 @@ int latok_wordpiece_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byt
     if (n >= (1ll << 31)) return fail(LATOK_ERR_INVALID, "the batch has %lld pieces: a call takes fewer than 2^31", (long long)n);
     return deliver_sized(c, n, cap, "capacity too small: need %lld pieces", {{ids_out, a.ids, 4}, {spans_out, a.spans, 2 * elt}});   // (wait 3)
 }
+int latok_wordpiece_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                         const latok_wordpiece* wp, int32_t unk_id, int64_t* indptr_out, int32_t* ids_out, int64_t* spans_out,
+                                         int64_t cap, int64_t* n_pieces_out, int64_t* n_tokens_out, int flags, void* stream) {
+    return piece_ids_call(utf8, byte_off, n_str, total_bytes, wp, "wp is NULL", PieceCut{}, &PieceCut::wp, unk_id, indptr_out, ids_out, spans_out, cap,
+                          n_pieces_out, n_tokens_out, flags, stream);
+}
+int latok_bpe_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_bpe* bpe,
+                                   int32_t unk_id, int64_t* indptr_out, int32_t* ids_out, int64_t* spans_out, int64_t cap, int64_t* n_pieces_out,
+                                   int64_t* n_tokens_out, int flags, void* stream) {
+    return piece_ids_call(utf8, byte_off, n_str, total_bytes, bpe, "bpe is NULL", PieceCut{nullptr, nullptr, 18, 19}, &PieceCut::bpe, unk_id, indptr_out,
+                          ids_out, spans_out, cap, n_pieces_out, n_tokens_out, flags, stream);
+}
 
-int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
-                                            const latok_wordpiece* wp, int32_t unk_id, int64_t max_length, int add_special, int32_t cls_id,
-                                            int32_t sep_id, int32_t pad_id, int32_t* input_ids_out, int32_t* lengths_out, int64_t* n_pieces_out,
-                                            int flags, void* stream) {
+// the body of the two padded forms; cls_id / sep_id: BOS / EOS of the BPE call
+extern "C++" template <class Obj, class Handle>
+static int piece_padded_call(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const Handle* handle,
+                             const char* null_msg, PieceCut cut, const Obj* PieceCut::*slot, int32_t unk_id, int64_t max_length, int add_special,
+                             int32_t cls_id, int32_t sep_id, int32_t pad_id, int32_t* input_ids_out, int32_t* lengths_out, int64_t* n_pieces_out,
+                             int flags, void* stream) {
     LATOK_ENTER();
     if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
     int rc = need_init(g);
@@ -3379,8 +3497,9 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
     if (n_pieces_out) *n_pieces_out = 0;
     const int sp = add_special ? 1 : 0;
     if (max_length < 1 + 2 * sp || max_length > 0x7FFFFFFF) return fail(LATOK_ERR_INVALID, "max_length must be in %d .. 2^31 - 1", 1 + 2 * sp);
-    const WordPiece* v = nullptr;
-    if ((rc = check_object(g, wp, "wp is NULL", &v))) return rc;
+    const Obj* v = nullptr;
+    if ((rc = check_object(g, handle, null_msg, &v))) return rc;
+    cut.*slot = v;
     BytesCall c;
     if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
     const bool dev = c.dev;
@@ -3398,13 +3517,13 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
         d_len = (int32_t*)g.counts.p;
     }
     if (c.empty) {   // no byte, no piece: every row is its specials and padding
-        g.last_route = 12;
+        g.last_route = cut.route_padded;
         HIP_TRY(latok::launch_wp_pad(nullptr, nullptr, nullptr, n_str, 0, max_length, sp, cls_id, sep_id, pad_id, d_block, d_len, st));
     } else {
-        if ((rc = c.stage(g, 12, WsShape{.spans = true, .term_rows = n_str + 1}, kClearSized))) return rc;
+        if ((rc = c.stage(g, cut.route_padded, WsShape{.spans = true, .term_rows = n_str + 1}, kClearSized))) return rc;
         WordPieceCall a;
         a.b = c.d;
-        a.wp = v;
+        a.cut = cut;
         a.unk = unk_id;
         a.padded = true;
         a.max_length = max_length;
@@ -3430,6 +3549,19 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
     if (!c.empty) return c.wait_totals(g, 0, &n_tok);   // the last wait
     HIP_TRY(hipStreamSynchronize(st));
     return LATOK_OK;
+}
+int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                            const latok_wordpiece* wp, int32_t unk_id, int64_t max_length, int add_special, int32_t cls_id,
+                                            int32_t sep_id, int32_t pad_id, int32_t* input_ids_out, int32_t* lengths_out, int64_t* n_pieces_out,
+                                            int flags, void* stream) {
+    return piece_padded_call(utf8, byte_off, n_str, total_bytes, wp, "wp is NULL", PieceCut{}, &PieceCut::wp, unk_id, max_length, add_special, cls_id,
+                             sep_id, pad_id, input_ids_out, lengths_out, n_pieces_out, flags, stream);
+}
+int latok_bpe_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_bpe* bpe,
+                                      int32_t unk_id, int64_t max_length, int add_special, int32_t bos_id, int32_t eos_id, int32_t pad_id,
+                                      int32_t* input_ids_out, int32_t* lengths_out, int64_t* n_pieces_out, int flags, void* stream) {
+    return piece_padded_call(utf8, byte_off, n_str, total_bytes, bpe, "bpe is NULL", PieceCut{nullptr, nullptr, 18, 19}, &PieceCut::bpe, unk_id, max_length,
+                             add_special, bos_id, eos_id, pad_id, input_ids_out, lengths_out, n_pieces_out, flags, stream);
 }
 
 /* token counting in byte space: a mutable, exact counting table on the device (count_table.h), filled by k_count_scatter and made
@@ -4130,6 +4262,18 @@ extern "C" int latok_debug_wordpiece_limits(int64_t* out, int n) {
     return k;
 }
 
+/* test hook (not part of the ABI; needs no device): the constants of the BPE calls: out[0] = kBpeBlock (tokens per workgroup of
+ * k_bpe_count / k_bpe_emit), out[1] = entries per workgroup of the chained scan over the piece counts (one scan block), out[2] =
+ * kBpeLaneBytes (the longest token of the lane form), out[3] = kBpeMaxBytes (the ceiling of max_bytes).  Returns the number of values
+ * written. */
+extern "C" int latok_debug_bpe_limits(int64_t* out, int n) {
+    const int64_t v[4] = {latok::kBpeBlock, latok::scan_chunk(), kBpeLaneBytes, kBpeMaxBytes};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 4 ? n : 4;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
 /* test hook (not part of the ABI; needs no device): the constants of the two device-wide int64 scans: out[0] = kChainChunk (entries per
  * workgroup of k_scan_chained), out[1] = predecessors one look-back round reads (64), out[2] = kChainValueBits, out[3] = bits of the
  * launch epoch (18), out[4] = kScanSmallMax, out[5] = kScanChunk (entries per workgroup of k_scan_local), out[6] = kScanBlock.  Returns
@@ -4283,7 +4427,8 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
  * 9 / 10: term counts of UTF-8 in byte space, vocabulary form / hashed form (likewise);
  * 11 / 12: WordPiece ids of UTF-8 in byte space, CSR form / padded form (likewise);
  * 13: case folding of UTF-8 in byte space (likewise); 14 / 15: word n-gram counts, vocabulary form / hashed form (likewise);
- * 16 / 17: character n-gram counts inside tokens, vocabulary form / hashed form (likewise) */
+ * 16 / 17: character n-gram counts inside tokens, vocabulary form / hashed form (likewise);
+ * 18 / 19: byte-level BPE ids of UTF-8 in byte space, CSR form / padded form (likewise) */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;

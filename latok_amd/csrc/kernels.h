@@ -402,6 +402,22 @@ hipError_t launch_wp_emit(bool out32, const TokenText& t, const WordPieceTables&
 hipError_t launch_wp_rows(bool out32, const int64_t* row_start, const int64_t* rank, int64_t n_str, int64_t n_tok, void* indptr_out, hipStream_t st);
 hipError_t launch_wp_pad(const int32_t* ids, const int64_t* row_start, const int64_t* rank, int64_t n_str, int64_t n_tok, int64_t max_length, int add_special,
                          int32_t cls_id, int32_t sep_id, int32_t pad_id, int32_t* input_ids, int32_t* lengths, hipStream_t st);
+// byte-level BPE ids (bpe_kernels.hip, bpe.h).  launch_bpe_count leaves the pieces of every token in cnt[0 .. n_tok) and 0 in
+// cnt[n_tok], and the final part-start mask of every token of at most 64 bytes in masks[0 .. n_tok); the caller scans the n_tok + 1
+// entries into rank[]; launch_bpe_emit stores ids (through rank_id) and string-relative spans if asked for at the piece rank, only
+// if the total fits cap.  Row pointers and the padded block are launch_wp_rows / launch_wp_pad.  Device memory, read only.
+constexpr int kBpeBlock = 256;   // tokens per workgroup of k_bpe_count / k_bpe_emit (latok_debug_bpe_limits)
+struct BpeTable {
+    VocabTable table;                   // id slot = the word's rank
+    const int32_t* rank_id = nullptr;   // [max(n_words, 1)]
+    int64_t n_words = 0;
+    uint32_t max_len = 0;               // bytes of the longest word
+    int max_bytes = 0;                  // 1 .. 4096
+    int lead_space = 0;
+};
+hipError_t launch_bpe_count(const TokenText& t, const BpeTable& bt, int64_t* cnt, uint64_t* masks, hipStream_t st);
+hipError_t launch_bpe_emit(bool out32, const TokenText& t, const BpeTable& bt, int32_t unk_id, const int64_t* rank, const uint64_t* masks,
+                           const int64_t* n_pieces_dev, int64_t cap, int32_t* ids, void* spans, hipStream_t st);
 // The gram keys of the term family: one term key per gram of the orders min_n .. max_n, each inside its own range of `keys`, which
 // holds n_keys keys; the lookup spells a gram with `joiner` between its tokens (word grams) or around the word (character grams).
 // launch_terms_reduce / _emit / _finish then take keys and the key-space row starts as they take the token keys and the token rows.

@@ -83,6 +83,17 @@ __device__ __forceinline__ int wave_scan_max(int v, int floor) {
 // maximum over the wave, in every lane (wave-uniform)
 __device__ __forceinline__ int wave_max(int v, int floor) { return lane_read(wave_scan_max(v, floor), 63); }
 
+// unsigned minimum over the wave, in every lane (wave-uniform): the same six DPP steps; a lane without a source takes 0xFFFFFFFF
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+    v = min(v, (uint32_t)dpp_mov<kDppRowShr1, 0xF>(-1, (int)v));
+    v = min(v, (uint32_t)dpp_mov<kDppRowShr2, 0xF>(-1, (int)v));
+    v = min(v, (uint32_t)dpp_mov<kDppRowShr4, 0xF>(-1, (int)v));
+    v = min(v, (uint32_t)dpp_mov<kDppRowShr8, 0xF>(-1, (int)v));
+    v = min(v, (uint32_t)dpp_mov<kDppRowBcast15, 0xA>(-1, (int)v));
+    v = min(v, (uint32_t)dpp_mov<kDppRowBcast31, 0xC>(-1, (int)v));
+    return (uint32_t)lane_read((int)v, 63);
+}
+
 // ---- scans on __shfl_up (ds_bpermute: one LDS round trip per step; kept where the kernels were measured with them) -------
 // inclusive prefix sum over the 64 lanes (int or long long); lane 63 holds the wave's total.  Not wave_sum: that one is a
 // total on DPP, this one a scan.  (Two sites keep the loop written out -- k_lead_compress's look-back, k_small_batch: hipcc

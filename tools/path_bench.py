@@ -65,6 +65,13 @@
   py_wp          end to end in Python on host blobs (the first --py-strings strings): batch.wordpiece_ids_utf8_batch(blobs, wp) against
                   batch.tokenize_utf8_batch(blobs) + the greedy longest-match loop over a dict; the vocabulary there also holds 2-byte
                   stems and ##-suffixes, so tokens do split; one line each
+  bytes_bpe32 / bytes_bpe_padded   latok_bpe_ids_utf8_bytes_batch (int32 indptr and spans, capacity = the piece total of a size query) /
+                  latok_bpe_padded_utf8_bytes_batch ([n, 64] block with BOS / EOS); the vocabulary is the 256 single bytes plus the merges
+                  of a small byte-pair trainer over the 5000 most frequent tokens of the first --py-strings strings of the leg's own corpus (--bpe-merges,
+                  lead_space = 1); same process run as bytes_ids32 and bytes_wp32, which are its yardsticks
+  py_bpe         end to end in Python on host blobs (the first --py-strings strings): batch.bpe_ids_utf8_batch(blobs, bpe) against
+                  batch.tokenize_utf8_batch(blobs) + the merge loop over a dict (lead_space = 0 there: the host route has no spans);
+                  equal rows asserted first; one line each
   py_terms       end to end in Python on host blobs (the first --py-strings strings): batch.term_counts_utf8_batch(blobs, vocab)
                   against batch.tokenize_utf8_batch(blobs) + a dict and collections.Counter per row; one line each
   py_count       end to end in Python on host blobs (the first --py-strings strings): TokenCounter.update_utf8 + most_common()
@@ -142,6 +149,7 @@ def main():
                                        "rules_mask,kind_mask,kind_offsets,kind_offsets32,"
                                        "kind_spans,kind_spans32")
     ap.add_argument("--py-strings", type=int, default=200_000, help="strings of the py_join / py_ids / py_terms paths (host blobs)")
+    ap.add_argument("--bpe-merges", type=int, default=400, help="merges of the byte-pair trainer of the bpe paths")
     ap.add_argument("--vocab", default="all", choices=("all", "half"), help="vocabulary of the ids paths: every distinct token of the corpus, or every second one")
     args = ap.parse_args()
     lib = _lib.ensure_init()
@@ -425,6 +433,7 @@ def main():
                                           "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "bytes_ngrams32", "bytes_ngrams_hashed", "py_terms",
                                           "bytes_chargrams32", "bytes_chargrams_hashed", "bytes_tfidf32", "bytes_tfidf_hashed", "bytes_df_update", "csr_tfidf", "csr_df", "py_tfidf",
                                           "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join", "bytes_wp32", "bytes_wp_padded", "py_wp",
+                                          "bytes_bpe32", "bytes_bpe_padded", "py_bpe",
                                           "bytes_fold", "bytes_fold_wp", "py_fold")]
     if join_leg:
         jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64, cap * 4, cap * 4)]
@@ -614,6 +623,80 @@ def main():
             w, _, w_block, w_len = corpus_wordpiece()
             return lib.latok_wordpiece_padded_utf8_bytes_batch(d_u8, d_boff, n, n8, w.handle, -1, WP_LEN, 1, 101, 102, 0, w_block, w_len,
                                                                C.byref(nout), D, None)
+
+        note_b = ("UTF-8 bytes + 8 B/string read; 4 B/string indptr + 4 B/piece ids + 8 B/piece spans written. NOT counted: the workspace "
+                  "traffic (16 B/token span records, 8 B/token piece counts, ranks and part-start masks), the walks of every token's bytes and "
+                  "the table reads of every pair lookup")
+        bpe_box = []
+
+        def bpe_train(tokens, n_merges):
+            """the 256 single bytes, then n_merges times the most frequent adjacent pair of the tokens (bytes), merged everywhere"""
+            from collections import Counter
+            freq = dict(Counter(tokens).most_common(5000))   # (the trainer is plain Python: the frequent tokens decide the merges anyway)
+            seqs = {t: [t[i:i + 1] for i in range(len(t))] for t in freq}
+            words = [bytes([b]) for b in range(256)]
+            for _ in range(n_merges):
+                pairs = Counter()
+                for t, parts in seqs.items():
+                    for x, y in zip(parts, parts[1:]):
+                        pairs[(x, y)] += freq[t]
+                if not pairs:
+                    break
+                x, y = min(pairs.items(), key=lambda kv: (-kv[1], kv[0]))[0]
+                words.append(x + y)
+                for t, parts in seqs.items():
+                    if len(parts) < 2:
+                        continue
+                    i, out = 0, []
+                    while i < len(parts):
+                        if i + 1 < len(parts) and parts[i] == x and parts[i + 1] == y:
+                            out.append(x + y)
+                            i += 2
+                        else:
+                            out.append(parts[i])
+                            i += 1
+                    seqs[t] = out
+            return words
+
+        def bpe_sample_tokens(lead):
+            from latok_amd import batch
+            m = min(args.py_strings, n)
+            blob = u8[:int(boff[m])].tobytes()
+            blobs = [blob[int(a):int(b)] for a, b in zip(boff[:m], boff[1:m + 1])]
+            toks = [t for row in batch.tokenize_utf8_batch(blobs) for t in row]
+            return blobs, blob, ([b" " + t for t in toks[::2]] + toks[1::2] if lead else toks)
+
+        def corpus_bpe():
+            """the BPE vocabulary of the bpe paths and their buffers, built once (the ids are sized by a size query)"""
+            if not bpe_box:
+                from latok_amd import batch
+                t = time.perf_counter()
+                words = bpe_train(bpe_sample_tokens(True)[2], args.bpe_merges)
+                train_ms = (time.perf_counter() - t) * 1e3
+                t = time.perf_counter()
+                b = batch.BPE(words, lead_space=True, seed=SEED)
+                print(json.dumps(dict(b.info(), bpe_merges=len(words) - 256, workload=args.workload, train_ms=train_ms,
+                                      create_ms=(time.perf_counter() - t) * 1e3)), flush=True)
+                bufs = [lib.latok_dev_alloc(sz) for sz in ((n + 1) * 4 + 64, n * WP_LEN * 4 + 64, n * 4 + 64)]
+                if not all(bufs):
+                    raise RuntimeError(_lib.last_error())
+                need = C.c_int64(0)
+                rc = lib.latok_bpe_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, bufs[0], None, None, 0, C.byref(need), None, D32, None)
+                if rc != _lib.OK and need.value <= 0:
+                    _lib.check(rc)
+                pieces = [lib.latok_dev_alloc(need.value * 4 + 64), lib.latok_dev_alloc(need.value * 8 + 64)]
+                if not all(pieces):
+                    raise RuntimeError(_lib.last_error())
+                bpe_box.extend([b] + bufs + pieces + [need.value])
+            return bpe_box
+
+        def bpe_blocking():
+            b, b_indptr, _, _, b_ids, b_spans, need = corpus_bpe()
+            return lib.latok_bpe_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, b_indptr, b_ids, b_spans, need, C.byref(nout), None, D32, None)
+
+        def bpe_padded_blocking():
+            b, _, b_block, b_len = corpus_bpe()[:4]
+            return lib.latok_bpe_padded_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, WP_LEN, 1, 1, 2, 0, b_block, b_len, C.byref(nout), D, None)
 
         note_f = ("UTF-8 bytes + 8 B/string read twice (count pass, write pass); 1 bit/byte string-end bitmap written and read; 2 B per 16 bytes "
                   "group prefixes written and read; 1 B/output byte + 8 B/string row offsets written (LOWER | STRIP_MARKS)")
@@ -834,6 +917,63 @@ def main():
                             got = fn()
                             dt = time.perf_counter() - t
                             print(json.dumps({"path": rname, "workload": args.workload, "strings": m, "utf8_bytes": len(blob), "vocab": args.vocab,
+                                              "words": len(words), "pieces": int(got[1].size), "unk": int((got[1] == -1).sum()), "ms_per_call": dt * 1e3,
+                                              "utf8_GBps": len(blob) / dt / 1e9,
+                                              "note": "end to end in Python: list[bytes] in, (indptr, ids) out, pack and host work included",
+                                              "repeat": r}), flush=True)
+            elif name == "bytes_bpe32":   # (items = pieces)
+                run(name, bpe_blocking, lambda: n8 + csr + 4 * n + 12 * nout.value, note_b)
+            elif name == "bytes_bpe_padded":   # (items = the untruncated piece total; the block is [n, WP_LEN] with BOS / EOS)
+                run(name, bpe_padded_blocking, lambda: n8 + csr + 4 * n + 4 * n * WP_LEN,
+                    note_b.replace("4 B/string indptr + 4 B/piece ids + 8 B/piece spans", "4 B/string lengths + 4 B/cell of the [n, %d] block" % WP_LEN))
+            elif name == "py_bpe":   # host blobs in, the CSR arrays out, both routes in this process
+                from latok_amd import batch
+                blobs, blob, toks = bpe_sample_tokens(False)
+                words = bpe_train(toks, args.bpe_merges)
+                d = {}
+                for i, w in enumerate(words):
+                    d.setdefault(w, i)
+                memo = {}
+
+                def cut(tok):
+                    got = memo.get(tok)
+                    if got is None:
+                        if tok in d:
+                            got = [d[tok]]
+                        else:
+                            parts = [tok[i:i + 1] for i in range(len(tok))]
+                            while True:
+                                best = None
+                                for i in range(len(parts) - 1):
+                                    r = d.get(parts[i] + parts[i + 1])
+                                    if r is not None and (best is None or r < best[0]):
+                                        best = (r, i)
+                                if best is None:
+                                    break
+                                parts[best[1]:best[1] + 2] = [parts[best[1]] + parts[best[1] + 1]]
+                            got = [d.get(p, -1) for p in parts]
+                        memo[tok] = got
+                    return got
+
+                def on_host():
+                    memo.clear()   # (the memo is part of the loop: one merge walk per distinct token of the call)
+                    indptr, ids = [0], []
+                    for row in batch.tokenize_utf8_batch(blobs):
+                        for tok in row:
+                            ids.extend(cut(tok))
+                        indptr.append(len(ids))
+                    return np.array(indptr, np.int64), np.array(ids, np.int32)
+
+                with batch.BPE(words, seed=SEED) as b:
+                    routes = (("py_bpe_ids_utf8_batch", lambda: batch.bpe_ids_utf8_batch(blobs, b)[:2]),
+                              ("py_tokenize_utf8_batch_then_bpe_loop", on_host))
+                    assert all(np.array_equal(x, y) for x, y in zip(routes[0][1](), routes[1][1]()))
+                    for r in range(args.repeat):
+                        for rname, fn in routes:
+                            t = time.perf_counter()
+                            got = fn()
+                            dt = time.perf_counter() - t
+                            print(json.dumps({"path": rname, "workload": args.workload, "strings": len(blobs), "utf8_bytes": len(blob),
                                               "words": len(words), "pieces": int(got[1].size), "unk": int((got[1] == -1).sum()), "ms_per_call": dt * 1e3,
                                               "utf8_GBps": len(blob) / dt / 1e9,
                                               "note": "end to end in Python: list[bytes] in, (indptr, ids) out, pack and host work included",
