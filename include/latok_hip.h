@@ -578,7 +578,7 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
  * [n_str, max_length] int32 block with bos_id / eos_id where the WordPiece call puts cls_id / sep_id (add_special), and lengths_out.
  * Out of scope: GPT-2's regex pre-tokenizer -- tokens are latok's, and runs of whitespace are not encoded --, a vocab.json /
  * merges.txt loader, special-token strings inside the text, Unigram models, folding inside the call, a flow form, decoding ids back
- * to text. */
+ * to text.  (Decoding is a call family of its own: latok_detok_* below.) */
 typedef struct latok_bpe latok_bpe;
 int latok_bpe_create(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
                      const int32_t* word_ids /* may be NULL */, int max_bytes, int lead_space, uint32_t seed, latok_bpe** bpe_out);
@@ -594,6 +594,56 @@ int latok_bpe_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_o
                                       int32_t eos_id, int32_t pad_id, int32_t* input_ids_out /* [n_str*max_length] */,
                                       int32_t* lengths_out /* [n_str] */, int64_t* n_pieces_out /* may be NULL */, int flags,
                                       void* stream);
+
+/* Decoding: ids back to UTF-8 bytes, for the ids of both encoder families above, whatever pre-tokenizer made them.
+ * A DECODER is a device object of its own, built from a word list in the words / word_off layout latok_vocab_create takes (HOST
+ * pointers) and an optional int32 array word_ids (NULL means id = index).  Every int32 is a legal id; of several words with one id the
+ * LOWEST INDEX wins; the empty word is a legal entry and contributes no bytes; duplicate words with different ids are all kept (a
+ * decoder maps ids, not words).  mode: LATOK_DETOK_CONCAT (BPE: tiktoken's decode_bytes) or LATOK_DETOK_WORDPIECE (the
+ * " ".join(tokens).replace(" ##", "") rule of BERT tokenizers, with `prefix` of prefix_len = 0 .. 8 bytes and the separator byte `sep`
+ * = 0 .. 255).  A word is a CONTINUATION word iff it starts with the prefix and is longer than the prefix.  The object holds the word
+ * bytes in one blob below 2^32 bytes, one record per word and a map id -> word: a dense array over [min_id, max_id] when that range is
+ * small against the word count (default ids, .tiktoken files, vocab.txt), else the sorted distinct ids, searched by bisection.
+ * latok_detok_create refuses, before any device work, what latok_vocab_create refuses, a mode other than the two, a prefix_len outside
+ * 0 .. 8, a sep outside 0 .. 255, and in CONCAT mode a prefix_len or sep other than 0.  The object may be used by any context of its
+ * device, concurrently; latok_detok_destroy drains the current context first, like latok_vocab_destroy.  latok_detok_info reports the
+ * word count as given, the distinct ids, the bytes of the blob, the longest word, the mode, whether the map is dense, and the device;
+ * any output pointer may be NULL.
+ * THE RULE.  A row is a sequence of ids.  A piece is DROPPED when its id is one of the n_skip = 0 .. 16 ids of skip_ids (a HOST pointer
+ * in every mode: pad / BOS / EOS / [CLS] / [SEP]) or when its id is not in the object (unknown); a dropped piece leaves no trace in
+ * its row.  Unknown pieces are counted in *n_unknown_out (may be NULL), skipped pieces are not.  The remaining pieces have words
+ * w_0 .. w_k.  CONCAT: the row is w_0 + w_1 + .. + w_k.  WORDPIECE: w_0 verbatim, prefix included; for j >= 1 a continuation word
+ * without its prefix, any other word as the sep byte followed by the word.  For a vocabulary in which no word contains the sep byte
+ * and the bare prefix is not a word this equals sep.join(words).replace(sep + prefix, b"").  Bytes out: nothing looks at UTF-8
+ * structure; the caller decodes.
+ * latok_detok_csr takes the rows as a CSR: indptr [n_rows + 1] (int64, or int32 under LATOK_OUT_INT32; out_off is int64 in every mode)
+ * and n_pieces ids, validated as latok_tfidf_csr validates its CSR -- a refused call writes nothing.  latok_detok_padded takes the
+ * [n_rows, max_length] block of the padded encoder calls: row s is the first lengths[s] cells of row s of the block; lengths == NULL
+ * means all max_length cells (put pad_id into skip_ids); a length outside [0, max_length] refuses the call.  Host pointers, or
+ * LATOK_DEVICE_PTRS for ids, indptr, lengths and the outputs; any other flag bit is refused before any device work; the object's
+ * device is checked as in the calls above.  Output: out_bytes, the rows' bytes back to back, and out_off [n_rows + 1], row s =
+ * out_bytes[out_off[s] : out_off[s + 1]].  The capacity protocol in BYTES is latok_fold_utf8_bytes_batch's: out_cap too small: nothing
+ * is written to out_bytes, out_off stays valid, the need is in *n_out_bytes, LATOK_ERR_INVALID; out_cap = 0 with out_bytes = NULL is a
+ * size query; out_bytes = NULL with out_cap > 0 is refused.  n_rows = 0 or no pieces: zero bytes, out_off cleared.  Blocking: one wait
+ * for the totals, one more behind the copies with host pointers.  Every batch size takes the same kernels.  The output of a device
+ * call is a valid utf8 / byte_off input of every byte-space call when its start is 16-byte aligned.
+ * Out of scope: a flow form, decoding to text with error replacement, special-token strings beyond what the vocabulary holds as
+ * words, Unigram models. */
+#define LATOK_DETOK_CONCAT 0      /* BPE: a row is the concatenation of its words */
+#define LATOK_DETOK_WORDPIECE 1   /* continuation words lose the prefix, other words get a separator in front */
+typedef struct latok_detok latok_detok;
+int latok_detok_create(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
+                       const int32_t* word_ids /* may be NULL: id = index */, int mode, const uint8_t* prefix, int prefix_len /* 0 .. 8 */,
+                       int sep /* 0 .. 255 */, latok_detok** out);
+int latok_detok_destroy(latok_detok* d);
+int latok_detok_info(const latok_detok* d, int64_t* n_words, int64_t* n_ids, int64_t* blob_bytes, int64_t* max_len, int* mode, int* dense,
+                     int* device);
+int latok_detok_csr(const latok_detok* d, const void* indptr /* [n_rows+1] */, const int32_t* ids, int64_t n_rows, int64_t n_pieces,
+                    const int32_t* skip_ids, int n_skip, uint8_t* out_bytes, int64_t out_cap, int64_t* out_off /* [n_rows+1] */,
+                    int64_t* n_out_bytes, int64_t* n_unknown_out /* may be NULL */, int flags, void* stream);
+int latok_detok_padded(const latok_detok* d, const int32_t* input_ids /* [n_rows*max_length] */, const int32_t* lengths /* [n_rows], may be NULL */,
+                       int64_t n_rows, int64_t max_length, const int32_t* skip_ids, int n_skip, uint8_t* out_bytes, int64_t out_cap,
+                       int64_t* out_off, int64_t* n_out_bytes, int64_t* n_unknown_out, int flags, void* stream);
 
 /* Case folding and accent stripping in byte space: UTF-8 in, folded UTF-8 out, what an uncased vocabulary (bert-base-uncased and its
  * relatives) or a lower-casing vectorizer needs in front of the token calls above.  `fold` is a set of LATOK_FOLD_* bits in an

@@ -92,6 +92,11 @@ SIGNATURES = {
     "latok_bpe_ids_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
     "latok_bpe_padded_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, i64, ci, C.c_int32, C.c_int32, C.c_int32, vp, vp,
                                                C.POINTER(i64), ci, vp]),
+    "latok_detok_create": (ci, [vp, vp, i64, vp, ci, vp, ci, ci, C.POINTER(vp)]),
+    "latok_detok_destroy": (ci, [vp]),
+    "latok_detok_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
+    "latok_detok_csr": (ci, [vp, vp, vp, i64, i64, vp, ci, vp, i64, vp, C.POINTER(i64), C.POINTER(i64), ci, vp]),
+    "latok_detok_padded": (ci, [vp, vp, vp, i64, i64, vp, ci, vp, i64, vp, C.POINTER(i64), C.POINTER(i64), ci, vp]),
     "latok_fold_utf8_bytes_batch": (ci, [vp, vp, i64, i64, ci, vp, i64, vp, C.POINTER(i64), ci, vp]),
     "latok_counter_create": (ci, [i64, ci, C.c_uint32, C.POINTER(vp)]),
     "latok_counter_destroy": (ci, [vp]),

@@ -630,7 +630,7 @@ def _size_then_fill(call, n, alloc):
 
 
 class _DeviceObject:
-    """What Vocab, WordPiece, BPE, Idf and TokenCounter share: ``handle`` (None once closed) of an object that ``_lib`` made and its call
+    """What Vocab, WordPiece, BPE, Detokenizer, Idf and TokenCounter share: ``handle`` (None once closed) of an object that ``_lib`` made and its call
     named ``_destroy`` frees -- by ``close()``, on leaving a ``with`` block, or with the object.  ``_closed``: what ``_open()`` says."""
 
     handle = _destroy = _closed = None
@@ -1280,8 +1280,8 @@ class BPE(_DeviceObject):
     ``lead_space``: a token that follows a 0x20 byte inside its string takes that byte in front (the ``" word"`` convention of
     GPT-style vocabularies), ``seed`` the 32-bit seed of the table's hash.  This is ``tiktoken``'s model.  Out of scope: GPT-2's regex
     pre-tokenizer (tokens are latok's; runs of whitespace are not encoded), a ``vocab.json`` / ``merges.txt`` loader, special-token
-    strings inside the text, Unigram models, a ``fold=`` keyword, a flow form, ``DevicePool`` forms, decoding.  Immutable; ``len()`` is the
-    number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
+    strings inside the text, Unigram models, a ``fold=`` keyword, a flow form, ``DevicePool`` forms, decoding (a class of its own,
+    ``Detokenizer``).  Immutable; ``len()`` is the number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
 
     _destroy, _closed = "latok_bpe_destroy", "bpe must be an open latok_amd.batch.BPE"
 
@@ -1390,6 +1390,147 @@ def bpe_encode_utf8_batch(blobs, bpe, max_length, bos_id=None, eos_id=None, pad_
         input_ids, lengths = b.fetch(input_ids), b.fetch(lengths)
     mask = (np.arange(max_length, dtype=np.int32)[None, :] < lengths[:, None]).astype(np.int32)
     return input_ids, mask
+
+
+# decoding: ids back to UTF-8 bytes on the device, for the ids of BPE and WordPiece alike
+DETOK_MODES = {"concat": 0, "wordpiece": 1}             # LATOK_DETOK_CONCAT / LATOK_DETOK_WORDPIECE
+
+
+class Detokenizer(_DeviceObject):
+    """A decoder on the device of the current context (``latok_detok_create``): ``words`` is a list of ``bytes`` or ``str`` (``str`` is
+    encoded as UTF-8 with surrogatepass), ``ids`` an optional int32 per word (default: its index; of several words with one id the
+    lowest index wins).  ``mode="concat"``: a row decodes to the concatenation of its words -- ``tiktoken``'s ``decode_bytes``;
+    ``prefix`` and ``sep`` are not used.  ``mode="wordpiece"``: the first word of a row verbatim, a later word that starts with
+    ``prefix`` (0 .. 8 bytes) and is longer than it without the prefix, any other later word behind the ``sep`` byte -- the
+    ``" ".join(tokens).replace(" ##", "")`` rule of BERT tokenizers.  Ids in a call's ``skip_ids`` and ids the object does not hold
+    leave no trace.  Bytes out: the caller decodes them.  Immutable; ``len()`` is the number of words given.  Freed by ``close()``,
+    on leaving a ``with`` block, or with the object."""
+
+    _destroy, _closed = "latok_detok_destroy", "detok must be an open latok_amd.batch.Detokenizer"
+
+    def __init__(self, words, ids=None, mode="concat", prefix=b"##", sep=b" "):
+        if mode not in DETOK_MODES:
+            raise ValueError('mode must be "concat" or "wordpiece"')
+        wordpiece = mode == "wordpiece"
+        prefix = (prefix.encode("utf-8") if isinstance(prefix, str) else bytes(prefix)) if wordpiece else b""
+        if len(prefix) > 8:
+            raise ValueError("prefix must be 0 .. 8 bytes")
+        sep = _sep_byte(sep.encode("utf-8") if isinstance(sep, str) else sep) if wordpiece else 0
+        data, off, ids = _pack_words(words, ids)
+        lib = _lib.ensure_init()
+        h = C.c_void_p()
+        pre = np.frombuffer(prefix + b"\x00", np.uint8)
+        _lib.check(lib.latok_detok_create(_ptr(data) if data.size else None, _ptr(off), off.size - 1, _ptr(ids) if ids is not None else None,
+                                          DETOK_MODES[mode], _ptr(pre), len(prefix), sep, C.byref(h)))
+        self._lib, self.handle, self._n = lib, h, off.size - 1
+        self.mode, self.prefix, self.sep = mode, prefix, bytes([sep]) if wordpiece else b""
+
+    @classmethod
+    def from_tiktoken_file(cls, path):
+        """the decoder of a ``.tiktoken`` file (what ``BPE.from_tiktoken_file`` reads): id = rank, ``mode="concat"``"""
+        import base64
+        with open(path, "rb") as f:
+            pairs = [line.split() for line in f.read().splitlines() if line.strip()]
+        try:
+            words, ids = [base64.b64decode(p[0], validate=True) for p in pairs], [int(p[1]) for p in pairs]
+            if any(len(p) != 2 for p in pairs):
+                raise ValueError
+        except Exception:
+            raise ValueError("a line of a .tiktoken file is `base64(token) rank`") from None
+        return cls(words, ids or None)
+
+    @classmethod
+    def from_vocab_file(cls, path, prefix=b"##", sep=b" "):
+        """the decoder of a BERT ``vocab.txt`` (what ``WordPiece.from_vocab_file`` reads): id = line number, ``mode="wordpiece"``"""
+        with open(path, "rb") as f:
+            words = [line.rstrip(b"\r\n") for line in f.read().split(b"\n")]
+        if words and words[-1] == b"":
+            words.pop()
+        return cls(words, mode="wordpiece", prefix=prefix, sep=sep)
+
+    def info(self):
+        """dict of what ``latok_detok_info`` reports"""
+        v = [C.c_int64(0) for _ in range(4)]
+        mode, dense, dev = C.c_int(0), C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.latok_detok_info(self._open(), *[C.byref(x) for x in v], C.byref(mode), C.byref(dense), C.byref(dev)))
+        return dict(n_words=v[0].value, n_ids=v[1].value, blob_bytes=v[2].value, max_len=v[3].value, mode=mode.value, dense=dense.value,
+                    device=dev.value)
+
+    def __len__(self):
+        return self._n
+
+
+def _decode(detok, skip_ids, errors, n_rows, entry):
+    """the size query, then the fill of one decode call -> (out_bytes, out_off); ``entry(lib, handle, skip, n_skip, out, cap, out_off, n, unk)``"""
+    if errors not in ("strict", "ignore"):
+        raise ValueError('errors must be "strict" or "ignore"')
+    skip = list(skip_ids)
+    if len(skip) > 16:
+        raise ValueError("skip_ids holds at most 16 ids")
+    skip = _int32_each(skip, len(skip), "skip_ids", "skipped id")
+    handle = _handle_of(Detokenizer, detok, "detok")
+    lib = _lib.ensure_init()
+    out_off, n, unk = np.zeros(n_rows + 1, np.int64), C.c_int64(0), C.c_int64(0)
+
+    def call(out=None, cap=0):
+        return entry(lib, handle, _ptr(skip) if skip.size else None, skip.size, out, cap, _ptr(out_off), C.byref(n), C.byref(unk))
+
+    _, (out,) = _size_then_fill(call, n, lambda k: (np.empty(k, np.uint8),))
+    if errors == "strict" and unk.value:
+        raise ValueError("%d ids are not in the decoder (errors=\"ignore\" drops them)" % unk.value)
+    return out, out_off
+
+
+def decode_csr(detok, indptr, ids, skip_ids=(), errors="strict"):
+    """(out_bytes uint8[], out_off int64[n + 1]): row s of the CSR (``indptr`` int32 or int64, ``ids`` int32) decoded by ``detok``;
+    row s = out_bytes[out_off[s]:out_off[s+1]].  Ids in ``skip_ids`` (at most 16: pad / BOS / EOS / [CLS] / [SEP]) and unknown ids
+    leave no trace; ``errors="strict"`` raises ValueError naming the count when any id was unknown, ``"ignore"`` returns the bytes.
+    Decoded on the device (``latok_detok_csr``): the size query, then the fill."""
+    ids = np.asarray(ids)
+    ids = _int32_each(ids, ids.size if ids.ndim == 1 else -1, "ids", "piece")
+    indptr, ids, flags = _csr_arrays(indptr, ids)
+    return _decode(detok, skip_ids, errors, indptr.size - 1,
+                   lambda lib, h, skip, n_skip, out, cap, out_off, n, unk: lib.latok_detok_csr(
+                       h, _ptr(indptr), _ptr(ids) if ids.size else None, indptr.size - 1, ids.size, skip, n_skip, out, cap, out_off, n, unk, flags, None))
+
+
+def decode_padded(detok, input_ids, lengths=None, attention_mask=None, skip_ids=(), errors="strict"):
+    """(out_bytes, out_off) of decode_csr for the padded ``input_ids`` int32[n, max_length] of the ``*_encode_utf8_batch`` calls: row s
+    is its first ``lengths[s]`` cells; ``attention_mask`` (its row sums are the lengths) may be given instead; with neither, every
+    cell counts and the pad id belongs into ``skip_ids``.  One call of ``latok_detok_padded`` per pass."""
+    block = np.asarray(input_ids)
+    if block.ndim != 2 or (block.size and block.dtype.kind not in "iu"):
+        raise ValueError("input_ids must be a 2-d integer array [n, max_length]")
+    n_rows, max_length = block.shape
+    block = _int32_each(block.reshape(-1), block.size, "input_ids", "cell")
+    if lengths is not None and attention_mask is not None:
+        raise ValueError("give lengths or attention_mask, not both")
+    if attention_mask is not None:
+        mask = np.asarray(attention_mask)
+        if mask.shape != (n_rows, max_length):
+            raise ValueError("attention_mask must have the shape of input_ids")
+        lengths = (mask != 0).sum(axis=1)
+    if lengths is not None:
+        lengths = _int32_each(lengths, n_rows, "lengths", "row")
+    return _decode(detok, skip_ids, errors, n_rows,
+                   lambda lib, h, skip, n_skip, out, cap, out_off, n, unk: lib.latok_detok_padded(
+                       h, _ptr(block) if block.size else None, _ptr(lengths) if lengths is not None and n_rows else None, n_rows, max_length, skip,
+                       n_skip, out, cap, out_off, n, unk, 0, None))
+
+
+def decode_batch(detok, rows, skip_ids=(), errors="strict"):
+    """list[bytes]: the decoded rows.  ``rows`` is a list of int sequences (decode_csr) or a 2-d int32 array (decode_padded with every
+    cell counted: put the pad id into ``skip_ids``)."""
+    if isinstance(rows, np.ndarray) and rows.ndim == 2:
+        out, off = decode_padded(detok, rows, skip_ids=skip_ids, errors=errors)
+    else:
+        rows = [np.asarray(r).reshape(-1) if len(r) else np.zeros(0, np.int32) for r in rows]   # (an empty list has no integer dtype of its own)
+        indptr = np.zeros(len(rows) + 1, np.int64)
+        np.cumsum([r.size for r in rows], out=indptr[1:])
+        ids = np.concatenate(rows) if rows and indptr[-1] else np.zeros(0, np.int32)
+        out, off = decode_csr(detok, indptr, ids, skip_ids, errors)
+    data = out.tobytes()
+    return [data[off[s]:off[s + 1]] for s in range(off.size - 1)]
 
 
 # token counts: the vocabulary of a corpus -- every distinct token with its frequency --, counted on the device, exactly

@@ -235,6 +235,9 @@ struct Workspace {
     DevBuf bpemask;   // BPE (which uses the WordPiece buffers as well): per token of at most 64 bytes its final part-start mask
     DevBuf ngrows;   // word n-grams: gram counts and row starts in key space (the span records share wpspans, the keys tkeys / tkeys2)
     DevBuf tfptr, tfidx, tfval, tfctl;   // TF-IDF: a host caller's CSR on the device (indptr, indices, data) and the error word of k_csr_check
+    // decoding (which stages a host caller's rows and ids in tfptr / tfidx and keeps its error word and unknown tally in tfctl): output
+    // bytes per piece, the sum and the first output byte of every workgroup of pieces, the int64 row starts of an int32 indptr
+    DevBuf dtcnt, dtsum, dtrank, dtrows;
     // the single-pass scan of k_word_counts_scan keeps its look-back state (chain: per workgroup, chain_ctl: {ticket
     // counter}) between launches: entries carry an epoch, so the array is cleared only when it is (re)allocated or when the
     // 18-bit epoch wraps (next_scan_epoch); *_seen = DevBuf::gen of the allocations it was last cleared in
@@ -243,7 +246,7 @@ struct Workspace {
     void release() {
         for (DevBuf* b : {&summ, &seg_agg, &fix_count, &tile_first, &bits, &space, &kept, &wcnt, &wpref, &bases, &scalar, &chain,
                           &chain_ctl, &codes, &widened, &lead, &bspace, &cpbits, &cpspace, &cprow, &jbody, &jhead, &tkeys,
-                          &tkeys2, &trows, &wpspans, &wpcnt, &wprank, &wpids, &bpemask, &ngrows, &tfptr, &tfidx, &tfval, &tfctl})
+                          &tkeys2, &trows, &wpspans, &wpcnt, &wprank, &wpids, &bpemask, &ngrows, &tfptr, &tfidx, &tfval, &tfctl, &dtcnt, &dtsum, &dtrank, &dtrows})
             b->release();
         scan_epoch = chain_seen = chain_ctl_seen = 0;
         chain_ready = false;
@@ -254,7 +257,7 @@ struct WsNeed {
     size_t bytes;   // 0: the batch does not use the buffer
 };
 constexpr int kTileNeeds = 4;   // the first entries of ws_needs: the tile stage
-constexpr int kWsNeeds = 35;
+constexpr int kWsNeeds = 39;
 // What a batch asks of its workspace beyond the tile stage.  token spans (spans) add the SPACE and kept planes, featurize (feats)
 // the code bytes, and narrow units read by featurize (widen) a UTF-32 copy.  cp_rows > 0: the units are UTF-8 bytes whose results
 // are reported in code points (cp_rows = n_str + 1): every buffer is sized by the byte count, which bounds the code-point count.
@@ -269,6 +272,9 @@ constexpr int kWsNeeds = 35;
 // the key total, which the n-gram call waits for before it sizes the two key buffers -- the term counts' own, one key per gram.
 // TF-IDF: tf_ctl, the error word of the CSR check; tf_ptr_bytes / tf_entries: the staging of a host caller's CSR (latok_idf_update_csr,
 // latok_tfidf_csr) -- its indptr in the caller's width, one int32 index and one 4-byte value per entry.
+// Decoding (latok_detok_csr / _padded, which set the TF-IDF fields for their own staging): dt_cells, the pieces -- 4 bytes of count per
+// piece, 8 + 8 bytes per workgroup of kDetokBlock pieces and a scan state for that many sums; dt_rows > 0 (= n_rows + 1): the int64 row
+// starts of an int32 indptr.
 constexpr int kTermRowArrays = 5;   // token counts, row starts, distinct counts, indptr, OOV counts
 struct WsShape {
     bool spans = false, feats = false, widen = false, join = false;
@@ -279,6 +285,7 @@ struct WsShape {
     int64_t ng_tokens = 0, ng_rows = 0, ng_keys = 0;
     bool tf_ctl = false;
     int64_t tf_ptr_bytes = 0, tf_entries = 0;
+    int64_t dt_cells = 0, dt_rows = 0;
 };
 // The one sizing rule of a workspace: every buffer a batch of `units` positions uses and its byte size.
 static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const WsShape& shape) {
@@ -300,7 +307,8 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const 
              {&w.bases, c_tiles * 8 + 8},   // rank of each tile's first item
              {&w.scalar, 64},
              {&w.chain, (size_t)std::max({latok::count_blocks((int64_t)words), latok::count_blocks(shape.term_rows * 64),
-                                            latok::count_blocks(shape.wp_tokens > 0 ? (shape.wp_tokens + 1) * 64 : 0)}) * 8 + 64},
+                                            latok::count_blocks(shape.wp_tokens > 0 ? (shape.wp_tokens + 1) * 64 : 0),
+                                            latok::count_blocks(latok::detok_groups(shape.dt_cells) * 64)}) * 8 + 64},
              {&w.chain_ctl, 64},
              {&w.codes, feats ? (size_t)units + latok::kTile + 256 : 0},   // read (never used) up to a tile behind the last char
              {&w.widened, widen ? (size_t)units * 4 + 16 : 0},
@@ -323,7 +331,11 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const 
              {&w.tfptr, (size_t)shape.tf_ptr_bytes},
              {&w.tfidx, shape.tf_entries > 0 ? (size_t)shape.tf_entries * 4 + 16 : 0},
              {&w.tfval, shape.tf_entries > 0 ? (size_t)shape.tf_entries * 4 + 16 : 0},
-             {&w.tfctl, shape.tf_ctl ? (size_t)64 : 0}}};
+             {&w.tfctl, shape.tf_ctl ? (size_t)64 : 0},
+             {&w.dtcnt, shape.dt_cells > 0 ? (size_t)shape.dt_cells * 4 + 16 : 0},
+             {&w.dtsum, shape.dt_cells > 0 ? (size_t)latok::detok_groups(shape.dt_cells) * 8 + 16 : 0},
+             {&w.dtrank, shape.dt_cells > 0 ? (size_t)latok::detok_groups(shape.dt_cells) * 8 + 16 : 0},
+             {&w.dtrows, shape.dt_rows > 0 ? (size_t)shape.dt_rows * 8 : 0}}};
 }
 static int ws_ensure(const WsNeed* needs, int n) {
     for (int i = 0; i < n; ++i) {
@@ -3564,6 +3576,284 @@ int latok_bpe_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_o
                              add_special, bos_id, eos_id, pad_id, input_ids_out, lengths_out, n_pieces_out, flags, stream);
 }
 
+/* Decoding (latok_detok_create / _destroy / _info, latok_detok_csr, latok_detok_padded; detok_kernels.hip, detok.h): ids back to bytes.
+ * The object holds the blob, the entry records and the id map of detok.h, built on the host, uploaded once, read only afterwards.  One
+ * stream, every batch size the same kernels:
+ *   k_csr_check / k_detok_lengths    the caller's rows; what fails sets the error word, and every kernel behind it returns at once
+ *   k_detok_widen                    an int32 indptr as int64 row starts
+ *   k_detok_count                    output bytes per piece, per workgroup of pieces; the unknown ids
+ *   k_scan_chained                   each workgroup's first output byte; THE byte total -> scalar word 0, pinned word 0
+ *   device pointers:  k_detok_write (gate: total <= capacity), then the call's one wait: total, error word, unknown tally
+ *   host pointers:    the wait for the same three words, which sizes the staging; k_detok_write into it; the copies and a second wait
+ * `w` is sized by ws_needs with WsShape{.tf_ctl, .tf_ptr_bytes, .tf_entries (host staging), .dt_cells, .dt_rows}. */
+struct Detok {                     // latok_detok: immutable once created
+    int device = -1;
+    int64_t n_words = 0, n_ids = 0;
+    uint64_t blob_bytes = 0;
+    uint32_t max_len = 0;
+    int mode = 0;
+    uint32_t sep = 0;
+    DtMap map{0, 0, 0};
+    DevMem blob, entries, keys, vals;
+    latok::DetokTable view() const {
+        latok::DetokTable t;
+        t.blob = blob.as<const uint32_t>();
+        t.entries = entries.p;
+        t.keys = keys.as<const int32_t>();
+        t.vals = vals.as<const int32_t>();
+        t.map = map;
+        t.mode = mode;
+        t.sep = sep;
+        return t;
+    }
+};
+int latok_detok_create(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, int mode, const uint8_t* prefix,
+                       int prefix_len, int sep, latok_detok** out) {
+    LATOK_ENTER();
+    // what needs no device is refused first
+    if (!out) return fail(LATOK_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (mode != LATOK_DETOK_CONCAT && mode != LATOK_DETOK_WORDPIECE) return fail(LATOK_ERR_INVALID, "mode must be LATOK_DETOK_CONCAT or LATOK_DETOK_WORDPIECE");
+    if (prefix_len < 0 || prefix_len > kDtMaxPrefix) return fail(LATOK_ERR_INVALID, "prefix_len must be in 0 .. %d", kDtMaxPrefix);
+    if (prefix_len > 0 && !prefix) return fail(LATOK_ERR_INVALID, "prefix is NULL");
+    if (sep < 0 || sep > 255) return fail(LATOK_ERR_INVALID, "sep must be one byte (0 .. 255)");
+    if (mode == LATOK_DETOK_CONCAT && (prefix_len != 0 || sep != 0)) return fail(LATOK_ERR_INVALID, "LATOK_DETOK_CONCAT takes prefix_len = 0 and sep = 0");
+    int rc = check_word_list(words, word_off, n_words);
+    if (rc || (rc = need_init(g))) return rc;
+    DtTable t;
+    Detok* v = nullptr;
+    try {
+        dt_build(words, word_off, n_words, word_ids, mode, prefix, prefix_len, &t);
+        v = new Detok();
+    } catch (const std::bad_alloc&) {
+        return fail(LATOK_ERR_NOMEM, "out of host memory");
+    }
+    v->device = g.device;
+    v->n_words = n_words;
+    v->n_ids = t.n_ids;
+    v->blob_bytes = t.blob_bytes;
+    v->max_len = t.max_len;
+    v->mode = mode;
+    v->sep = (uint32_t)sep;
+    v->map = t.map;
+    const size_t bytes[4] = {t.blob.size() * 4, t.entries.size() * sizeof(DtEntry), t.keys.size() * 4, t.vals.size() * 4};
+    const void* src[4] = {t.blob.data(), t.entries.data(), t.keys.data(), t.vals.data()};
+    DevMem* dst[4] = {&v->blob, &v->entries, &v->keys, &v->vals};
+    for (int i = 0; i < 4 && !rc; ++i) {
+        hipError_t e = dst[i]->alloc(bytes[i]);
+        if (e != hipSuccess) rc = fail(LATOK_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes[i], hipGetErrorString(e));
+        else if ((e = hipMemcpyAsync(dst[i]->p, src[i], bytes[i], hipMemcpyHostToDevice, g.stream)) != hipSuccess)
+            rc = fail(LATOK_ERR_HIP, "uploading the decoder failed: %s", hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(g.stream);   // (the host table dies with this call, and every context may use the object at once)
+    if (!rc && e != hipSuccess) rc = fail(LATOK_ERR_HIP, "uploading the decoder failed: %s", hipGetErrorString(e));
+    if (rc) {
+        delete v;
+        return rc;
+    }
+    *out = reinterpret_cast<latok_detok*>(v);
+    return LATOK_OK;
+}
+int latok_detok_destroy(latok_detok* d) {
+    LATOK_ENTER();
+    return destroy_object(g, reinterpret_cast<Detok*>(d));
+}
+int latok_detok_info(const latok_detok* d, int64_t* n_words, int64_t* n_ids, int64_t* blob_bytes, int64_t* max_len, int* mode, int* dense, int* device) {
+    const Detok* v = reinterpret_cast<const Detok*>(d);
+    if (!v) return fail(LATOK_ERR_INVALID, "detok is NULL");
+    if (n_words) *n_words = v->n_words;
+    if (n_ids) *n_ids = v->n_ids;
+    if (blob_bytes) *blob_bytes = (int64_t)v->blob_bytes;
+    if (max_len) *max_len = v->max_len;
+    if (mode) *mode = v->mode;
+    if (dense) *dense = v->map.dense;
+    if (device) *device = v->device;
+    return LATOK_OK;
+}
+
+struct DetokCall {                 // what an entry point of the pair received
+    const latok_detok* handle = nullptr;
+    bool padded = false;
+    const void* rows = nullptr;    // CSR: indptr; padded: lengths (may be NULL)
+    const int32_t* ids = nullptr;
+    int64_t n_rows = 0, n_pieces = 0, max_length = 0;
+    const int32_t* skip = nullptr;
+    int n_skip = 0;
+    uint8_t* out = nullptr;
+    int64_t cap = 0;
+    int64_t* out_off = nullptr;
+    int64_t* n_out = nullptr;
+    int64_t* n_unknown = nullptr;
+    int flags = 0;
+    void* stream = nullptr;
+};
+static int detok_refusal(int err) {
+    if (err & latok::kDetokBadLength) return fail(LATOK_ERR_INVALID, "a length lies outside [0, max_length]");
+    return csr_refusal(err);
+}
+static int detok_common(const DetokCall& a) {
+    LATOK_ENTER();
+    int rc;
+    if (a.flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    if (!a.n_out) return fail(LATOK_ERR_INVALID, "the total-size output pointer is NULL");
+    *a.n_out = 0;
+    if (a.n_unknown) *a.n_unknown = 0;
+    if (a.n_skip < 0 || a.n_skip > kDtMaxSkip) return fail(LATOK_ERR_INVALID, "n_skip must be in 0 .. %d", kDtMaxSkip);
+    if (a.n_skip > 0 && !a.skip) return fail(LATOK_ERR_INVALID, "skip_ids is NULL");
+    if (a.cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
+    if (!a.out && a.cap > 0) return fail(LATOK_ERR_INVALID, "out_bytes is NULL but out_cap > 0 (a size query passes out_cap = 0)");
+    int64_t n_cells = a.n_pieces;
+    if (a.padded) {
+        if (a.n_rows < 0) return fail(LATOK_ERR_INVALID, "n_rows must be >= 0");
+        if (a.max_length < 0) return fail(LATOK_ERR_INVALID, "max_length must be >= 0");
+        if (a.max_length > 0 && a.n_rows > (int64_t)((1ull << 62) / (uint64_t)a.max_length)) return fail(LATOK_ERR_INVALID, "n_rows * max_length is too large");
+        n_cells = a.n_rows * a.max_length;
+        if (n_cells > 0 && !a.ids) return fail(LATOK_ERR_INVALID, "input_ids is NULL");
+    } else if ((rc = csr_args(a.rows, a.ids, a.n_rows, a.n_pieces, a.flags))) {
+        return rc;
+    }
+    if (a.n_rows > 0 && !a.out_off) return fail(LATOK_ERR_INVALID, "out_off is NULL");
+    if ((rc = need_init(g))) return rc;
+    const Detok* v = nullptr;
+    if ((rc = check_object(g, a.handle, "detok is NULL", &v))) return rc;
+    const bool dev = (a.flags & LATOK_DEVICE_PTRS) != 0, o32 = !a.padded && (a.flags & LATOK_OUT_INT32) != 0;
+    const size_t elt = a.padded || o32 ? 4 : 8;   // width of one entry of `rows`
+    if (dev && (((uintptr_t)a.rows & (elt - 1)) != 0 || ((uintptr_t)a.ids & 3) != 0 || ((uintptr_t)a.out_off & 7) != 0))
+        return fail(LATOK_ERR_INVALID, "misaligned buffer");
+    StreamTurn turn(g, a.stream);
+    const hipStream_t st = turn.st;
+    if (a.n_rows == 0) return zero_counts(dev, a.out_off, 8, st, true);   // no row: the one offset, if the caller has room for it
+    Workspace& w = g.ws;
+    const int64_t n_rows = a.n_rows;
+    const size_t rows_bytes = a.rows ? (size_t)(a.padded ? n_rows : n_rows + 1) * elt : 0;
+    WsShape shape;
+    shape.tf_ctl = true;
+    shape.dt_cells = n_cells;
+    shape.dt_rows = o32 ? n_rows + 1 : 0;
+    if (!dev) {
+        shape.tf_ptr_bytes = (int64_t)rows_bytes;
+        shape.tf_entries = n_cells;
+    }
+    if ((rc = ws_ensure(ws_needs(w, 0, shape).data(), kWsNeeds)) || (rc = g.pin_tot.ensure(64))) return rc;
+    g.last_route = a.padded ? 21 : 20;
+    const void* d_rows = a.rows;
+    const int32_t* d_ids = a.ids;
+    if (!dev) {
+        if (rows_bytes > 0) {
+            HIP_TRY(hipMemcpyAsync(w.tfptr.p, a.rows, rows_bytes, hipMemcpyHostToDevice, st));
+            d_rows = w.tfptr.p;
+        }
+        if (n_cells > 0) {
+            HIP_TRY(hipMemcpyAsync(w.tfidx.p, a.ids, (size_t)n_cells * 4, hipMemcpyHostToDevice, st));
+            d_ids = (const int32_t*)w.tfidx.p;
+        }
+    }
+    // the control words: the error word of the row checks, the unknown tally; copied into the pinned words 5 and 6 in front of the wait
+    int* d_err = (int*)w.tfctl.p;
+    unsigned long long* d_unk = (unsigned long long*)w.tfctl.p + 1;
+    HIP_TRY(hipMemsetAsync(d_err, 0, 16, st));
+    volatile int64_t* h_tot = (volatile int64_t*)g.pin_tot.h;
+    int64_t* p_tot = (int64_t*)g.pin_tot.d;
+    h_tot[0] = h_tot[1] = h_tot[5] = h_tot[6] = 0;
+    latok::DetokRows R{nullptr, nullptr, n_rows, a.max_length, n_cells};
+    if (a.padded) {
+        R.lengths = (const int32_t*)d_rows;
+        HIP_TRY(latok::launch_detok_lengths(R.lengths, n_rows, a.max_length, d_err, st));
+    } else {
+        HIP_TRY(latok::launch_csr_check(o32, d_rows, d_ids, n_rows, n_cells, nullptr, 0, 0, d_err, st));
+        R.row_start = (const int64_t*)d_rows;
+        if (o32) {
+            HIP_TRY(latok::launch_detok_widen((const int32_t*)d_rows, n_rows + 1, (int64_t*)w.dtrows.p, st));
+            R.row_start = (const int64_t*)w.dtrows.p;
+        }
+    }
+    latok::DetokSkip S;
+    for (int i = 0; i < kDtMaxSkip; ++i) S.id[i] = i < a.n_skip ? a.skip[i] : 0;
+    S.n = a.n_skip;
+    const latok::DetokTable T = v->view();
+    uint32_t* d_cnt = (uint32_t*)w.dtcnt.p;
+    int64_t* d_sum = (int64_t*)w.dtsum.p;
+    int64_t* d_rank = (int64_t*)w.dtrank.p;
+    int64_t* d_total = (int64_t*)w.scalar.p;
+    if (n_cells > 0) {
+        latok::ChainState chain;
+        if ((rc = next_scan_epoch(w, st, &chain))) return rc;
+        HIP_TRY(latok::launch_detok_count(T, R, d_ids, S, d_err, d_cnt, d_sum, d_unk, st));
+        HIP_TRY(latok::launch_tile_scan(d_sum, latok::detok_groups(n_cells), d_rank, chain, d_total, p_tot, (int*)(p_tot + 1) + 1, st));
+        if (dev) HIP_TRY(latok::launch_detok_write(T, R, d_ids, S, d_err, d_cnt, d_rank, d_total, a.out, a.cap, a.out_off, st));
+    }
+    HIP_TRY(hipMemcpyAsync((void*)(h_tot + 5), d_err, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the call's wait for the totals
+    if ((rc = detok_refusal((int)h_tot[5]))) return rc;   // (a refused call has written nothing: the kernels behind the check returned at once)
+    int64_t n = 0;
+    if ((rc = finish_totals(w, h_tot, 0, &n))) return rc;
+    *a.n_out = n;
+    if (a.n_unknown) *a.n_unknown = h_tot[6];
+    if (n_cells == 0) return zero_counts(dev, a.out_off, (size_t)(n_rows + 1) * 8, st, true);   // no piece: empty rows
+    if (!dev) {   // the staging is sized by the total; out_off is valid whatever the capacity
+        const bool fits = a.out && n <= a.cap;
+        if ((rc = g.h_aux.ensure((size_t)(n_rows + 1) * 8)) || (fits && (rc = g.h_out.ensure((size_t)n + 16)))) return rc;
+        uint8_t* d_out = fits ? (uint8_t*)g.h_out.p : nullptr;
+        HIP_TRY(latok::launch_detok_write(T, R, d_ids, S, d_err, d_cnt, d_rank, d_total, d_out, n, (int64_t*)g.h_aux.p, st));
+        HIP_TRY(hipMemcpyAsync(a.out_off, g.h_aux.p, (size_t)(n_rows + 1) * 8, hipMemcpyDeviceToHost, st));
+        if (fits && n > 0) HIP_TRY(hipMemcpyAsync(a.out, d_out, (size_t)n, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (n > a.cap) return fail(LATOK_ERR_INVALID, "output capacity too small: need %lld bytes", (long long)n);
+    return LATOK_OK;
+}
+int latok_detok_csr(const latok_detok* d, const void* indptr, const int32_t* ids, int64_t n_rows, int64_t n_pieces, const int32_t* skip_ids, int n_skip,
+                    uint8_t* out_bytes, int64_t out_cap, int64_t* out_off, int64_t* n_out_bytes, int64_t* n_unknown_out, int flags, void* stream) {
+    DetokCall a;
+    a.handle = d;
+    a.rows = indptr;
+    a.ids = ids;
+    a.n_rows = n_rows;
+    a.n_pieces = n_pieces;
+    a.skip = skip_ids;
+    a.n_skip = n_skip;
+    a.out = out_bytes;
+    a.cap = out_cap;
+    a.out_off = out_off;
+    a.n_out = n_out_bytes;
+    a.n_unknown = n_unknown_out;
+    a.flags = flags;
+    a.stream = stream;
+    return detok_common(a);
+}
+int latok_detok_padded(const latok_detok* d, const int32_t* input_ids, const int32_t* lengths, int64_t n_rows, int64_t max_length,
+                       const int32_t* skip_ids, int n_skip, uint8_t* out_bytes, int64_t out_cap, int64_t* out_off, int64_t* n_out_bytes,
+                       int64_t* n_unknown_out, int flags, void* stream) {
+    DetokCall a;
+    a.handle = d;
+    a.padded = true;
+    a.rows = lengths;
+    a.ids = input_ids;
+    a.n_rows = n_rows;
+    a.max_length = max_length;
+    a.skip = skip_ids;
+    a.n_skip = n_skip;
+    a.out = out_bytes;
+    a.cap = out_cap;
+    a.out_off = out_off;
+    a.n_out = n_out_bytes;
+    a.n_unknown = n_unknown_out;
+    a.flags = flags;
+    a.stream = stream;
+    return detok_common(a);
+}
+/* test hook (not part of the ABI; needs no device): the constants of the decode calls: out[0] = kDetokBlock (pieces per workgroup of
+ * k_detok_count / k_detok_write), out[1] = kDetokWin (bytes of the LDS window), out[2] = kDtDenseSpread (the map is dense when the id
+ * range is at most this many times the word count), out[3] = entries per workgroup of the chained scan over the workgroup sums, out[4] =
+ * kDetokLaneBytes (the longest stretch a lane copies into a window itself).  Returns the number of values written. */
+extern "C" int latok_debug_detok_limits(int64_t* out, int n) {
+    const int64_t v[5] = {latok::kDetokBlock, latok::kDetokWin, kDtDenseSpread, latok::scan_chunk(), latok::kDetokLaneBytes};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 5 ? n : 5;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
 /* token counting in byte space: a mutable, exact counting table on the device (count_table.h), filled by k_count_scatter and made
  * independent of the caller's text by the two commit launches before the call returns.  One stream:
  *   tile index -> byte-space tiles -> resolve     boundary mask, smeared SPACE plane over the BYTES
@@ -4428,7 +4718,8 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
  * 11 / 12: WordPiece ids of UTF-8 in byte space, CSR form / padded form (likewise);
  * 13: case folding of UTF-8 in byte space (likewise); 14 / 15: word n-gram counts, vocabulary form / hashed form (likewise);
  * 16 / 17: character n-gram counts inside tokens, vocabulary form / hashed form (likewise);
- * 18 / 19: byte-level BPE ids of UTF-8 in byte space, CSR form / padded form (likewise) */
+ * 18 / 19: byte-level BPE ids of UTF-8 in byte space, CSR form / padded form (likewise);
+ * 20 / 21: decoding, ids back to bytes, CSR form / padded form (likewise) */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "detok.h"
 #include "fold_map.h"
 #include "split_code.h"
 
@@ -498,6 +499,42 @@ hipError_t launch_fold_counts(const uint8_t* u8, int64_t total, const uint32_t* 
 hipError_t launch_fold_write(const uint8_t* u8, int64_t total, const uint32_t* start32, int fold, const FoldTables& T, const uint16_t* group_pref,
                              const int64_t* tile_rank, const int64_t* tile_cnt, const int64_t* row_off, int64_t n_str, uint8_t* out, int64_t cap,
                              const int64_t* n_items_dev, int64_t* out_off, hipStream_t st);
+// detok_kernels.hip: decoding, ids back to bytes (detok.h).  The pieces are the ids of a CSR (row_start: its int64 row starts, n_cells =
+// the id count) or the cells of a padded [n_rows, max_length] block (row_start == NULL; lengths may be NULL: every cell counts).
+// launch_detok_count leaves the output bytes of every piece in cnt[0 .. n_cells) and the sum of every workgroup of kDetokBlock pieces in
+// wg_sum[0 .. detok_groups(n_cells)), and adds the unknown ids to *n_unknown; the caller scans the sums into wg_rank (launch_tile_scan);
+// launch_detok_write stores out_off[n_rows + 1] always and the bytes only if the total fits cap (out may be NULL).  *err: the error word
+// of launch_csr_check / launch_detok_lengths in front of them; the launches return at once when it is set.  latok_debug_detok_limits
+// reports the three constants.
+constexpr int kDetokBlock = 256;       // pieces per workgroup of k_detok_count / k_detok_write
+constexpr int kDetokWin = 4096;        // bytes of the LDS window of k_detok_write, a multiple of 16
+constexpr int kDetokLaneBytes = 64;    // bytes a piece puts into a window by its own lane at most
+constexpr int kDetokBadLength = 16;    // beside kCsrBad*: a length of the padded form lies outside [0, max_length]
+struct DetokTable {
+    const uint32_t* blob = nullptr;
+    const void* entries = nullptr;     // DtEntry[n_words]
+    const int32_t* keys = nullptr;     // sorted form: the distinct ids
+    const int32_t* vals = nullptr;     // the entry by id - min_id (dense) or beside keys[i]
+    DtMap map{0, 0, 0};
+    int mode = 0;
+    uint32_t sep = 0;
+};
+struct DetokSkip {
+    int32_t id[kDtMaxSkip];
+    int n;
+};
+struct DetokRows {
+    const int64_t* row_start;
+    const int32_t* lengths;
+    int64_t n_rows, max_length, n_cells;
+};
+int64_t detok_groups(int64_t n_cells);
+hipError_t launch_detok_lengths(const int32_t* lengths, int64_t n_rows, int64_t max_length, int* err, hipStream_t st);
+hipError_t launch_detok_widen(const int32_t* indptr, int64_t n, int64_t* row_start, hipStream_t st);
+hipError_t launch_detok_count(const DetokTable& T, const DetokRows& R, const int32_t* ids, const DetokSkip& S, const int* err, uint32_t* cnt,
+                              int64_t* wg_sum, unsigned long long* n_unknown, hipStream_t st);
+hipError_t launch_detok_write(const DetokTable& T, const DetokRows& R, const int32_t* ids, const DetokSkip& S, const int* err, const uint32_t* cnt,
+                              const int64_t* wg_rank, const int64_t* total_dev, uint8_t* out, int64_t cap, int64_t* out_off, hipStream_t st);
 
 }  // namespace latok
 #endif

@@ -69,6 +69,9 @@
                   latok_bpe_padded_utf8_bytes_batch ([n, 64] block with BOS / EOS); the vocabulary is the 256 single bytes plus the merges
                   of a small byte-pair trainer over the 5000 most frequent tokens of the first --py-strings strings of the leg's own corpus (--bpe-merges,
                   lead_space = 1); same process run as bytes_ids32 and bytes_wp32, which are its yardsticks
+  ids_detok_bpe / ids_detok_wp   latok_detok_csr on the resident int32 CSR that bytes_bpe32 / bytes_wp32 leave (CONCAT / WORDPIECE decoder
+                 of the same words; yardsticks: bytes_join of the same run and the HBM cost of 4 B/id + the output bytes + 8 B/row)
+  py_detok       end to end in Python: batch.decode_batch(detok, rows) against the host loop b"".join(words[i] for i in row)
   py_bpe         end to end in Python on host blobs (the first --py-strings strings): batch.bpe_ids_utf8_batch(blobs, bpe) against
                   batch.tokenize_utf8_batch(blobs) + the merge loop over a dict (lead_space = 0 there: the host route has no spans);
                   equal rows asserted first; one line each
@@ -433,7 +436,7 @@ def main():
                                           "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "bytes_ngrams32", "bytes_ngrams_hashed", "py_terms",
                                           "bytes_chargrams32", "bytes_chargrams_hashed", "bytes_tfidf32", "bytes_tfidf_hashed", "bytes_df_update", "csr_tfidf", "csr_df", "py_tfidf",
                                           "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join", "bytes_wp32", "bytes_wp_padded", "py_wp",
-                                          "bytes_bpe32", "bytes_bpe_padded", "py_bpe",
+                                          "bytes_bpe32", "bytes_bpe_padded", "py_bpe", "ids_detok_bpe", "ids_detok_wp", "py_detok",
                                           "bytes_fold", "bytes_fold_wp", "py_fold")]
     if join_leg:
         jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64, cap * 4, cap * 4)]
@@ -627,7 +630,7 @@ def main():
         note_b = ("UTF-8 bytes + 8 B/string read; 4 B/string indptr + 4 B/piece ids + 8 B/piece spans written. NOT counted: the workspace "
                   "traffic (16 B/token span records, 8 B/token piece counts, ranks and part-start masks), the walks of every token's bytes and "
                   "the table reads of every pair lookup")
-        bpe_box = []
+        bpe_box, bpe_words, detok_box = [], [], {}
 
         def bpe_train(tokens, n_merges):
             """the 256 single bytes, then n_merges times the most frequent adjacent pair of the tokens (bytes), merged everywhere"""
@@ -675,6 +678,7 @@ def main():
                 train_ms = (time.perf_counter() - t) * 1e3
                 t = time.perf_counter()
                 b = batch.BPE(words, lead_space=True, seed=SEED)
+                bpe_words.extend(words)
                 print(json.dumps(dict(b.info(), bpe_merges=len(words) - 256, workload=args.workload, train_ms=train_ms,
                                       create_ms=(time.perf_counter() - t) * 1e3)), flush=True)
                 bufs = [lib.latok_dev_alloc(sz) for sz in ((n + 1) * 4 + 64, n * WP_LEN * 4 + 64, n * 4 + 64)]
@@ -697,6 +701,29 @@ def main():
         def bpe_padded_blocking():
             b, _, b_block, b_len = corpus_bpe()[:4]
             return lib.latok_bpe_padded_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, WP_LEN, 1, 1, 2, 0, b_block, b_len, C.byref(nout), D, None)
+
+        note_d = ("4 B/id read + 4 B/string indptr read; 1 B/output byte + 8 B/string row offsets written. NOT counted: the second read of the "
+                  "ids and the 4 B/piece byte counts written and read (workspace), the id map and entry records (cache resident), the blob bytes")
+
+        def detok_of(kind):
+            """the decoder of the detok paths, built once per kind, behind one encode call that leaves the ids resident (int32 indptr)"""
+            if kind not in detok_box:
+                from latok_amd import batch
+                if kind == "bpe":
+                    _lib.check(bpe_blocking())
+                    _, indptr, _, _, ids = corpus_bpe()[:5]
+                    dt_ = batch.Detokenizer(bpe_words)
+                else:
+                    _lib.check(wp_blocking())
+                    indptr, ids = corpus_wordpiece()[1], h_a
+                    dt_ = batch.Detokenizer(words_box[0], mode="wordpiece")
+                print(json.dumps(dict(dt_.info(), detok=kind, workload=args.workload, pieces=nout.value)), flush=True)
+                detok_box[kind] = (dt_, indptr, ids, nout.value)
+            return detok_box[kind]
+
+        def detok_blocking(kind):
+            dt_, indptr, ids, n_pieces = detok_of(kind)
+            return lib.latok_detok_csr(dt_.handle, indptr, ids, n, n_pieces, None, 0, j_out, 2 * n8, j_off, C.byref(nout), None, D32, None)
 
         note_f = ("UTF-8 bytes + 8 B/string read twice (count pass, write pass); 1 bit/byte string-end bitmap written and read; 2 B per 16 bytes "
                   "group prefixes written and read; 1 B/output byte + 8 B/string row offsets written (LOWER | STRIP_MARKS)")
@@ -926,6 +953,32 @@ def main():
             elif name == "bytes_bpe_padded":   # (items = the untruncated piece total; the block is [n, WP_LEN] with BOS / EOS)
                 run(name, bpe_padded_blocking, lambda: n8 + csr + 4 * n + 4 * n * WP_LEN,
                     note_b.replace("4 B/string indptr + 4 B/piece ids + 8 B/piece spans", "4 B/string lengths + 4 B/cell of the [n, %d] block" % WP_LEN))
+            elif name in ("ids_detok_bpe", "ids_detok_wp"):   # (items = output bytes) the resident ids of one encode call decoded back
+                kind = name[len("ids_detok_"):]
+                n_pieces = detok_of(kind)[3]
+                _lib.check(bpe_blocking() if kind == "bpe" else wp_blocking())   # (the ids again: another leg may have used their buffer since)
+                assert nout.value == n_pieces
+                run(name, lambda: detok_blocking(kind), lambda: 4 * n_pieces + 4 * (n + 1) + nout.value + csr, note_d)
+            elif name == "py_detok":   # host rows in, list[bytes] out, against the join loop of the host
+                from latok_amd import batch
+                blobs, blob, toks = bpe_sample_tokens(False)
+                words = bpe_train(toks, args.bpe_merges)
+                with batch.BPE(words, seed=SEED) as b:
+                    indptr, ids, _ = batch.bpe_ids_utf8_batch(blobs, b)
+                rows = [ids[a:e] for a, e in zip(indptr[:-1].tolist(), indptr[1:].tolist())]
+                with batch.Detokenizer(words) as dt_:
+                    routes = (("py_decode_batch", lambda: batch.decode_batch(dt_, rows)),
+                              ("py_join_loop", lambda: [b"".join(words[i] for i in row) for row in rows]))
+                    assert routes[0][1]() == routes[1][1]()
+                    for r in range(args.repeat):
+                        for rname, fn in routes:
+                            t = time.perf_counter()
+                            got = fn()
+                            dt = time.perf_counter() - t
+                            print(json.dumps({"path": rname, "workload": args.workload, "strings": len(blobs), "pieces": int(ids.size),
+                                              "out_bytes": sum(map(len, got)), "ms_per_call": dt * 1e3, "out_GBps": sum(map(len, got)) / dt / 1e9,
+                                              "note": "end to end in Python: list of int32 rows in, list[bytes] out, pack and host slicing included",
+                                              "repeat": r}), flush=True)
             elif name == "py_bpe":   # host blobs in, the CSR arrays out, both routes in this process
                 from latok_amd import batch
                 blobs, blob, toks = bpe_sample_tokens(False)
@@ -1168,6 +1221,8 @@ def main():
                                           "out_bytes": sum(map(len, rows)), "ms_per_call": dt * 1e3, "utf8_GBps": len(blob) / dt / 1e9,
                                           "note": "end to end in Python: list[bytes] in, list[bytes] out, pack and host slicing included",
                                           "repeat": r}), flush=True)
+        for v_ in detok_box.values():
+            v_[0].close()
         if vocab_box:
             vocab_box[0].close()
         if counter_box:
