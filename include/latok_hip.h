@@ -526,7 +526,8 @@ int latok_hashed_tfidf_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
  * Lower-casing, accent stripping, control-character cleaning and CJK spacing (the normalizer of BERT's BasicTokenizer) are a call of
  * their own, latok_fold_utf8_bytes_batch below: its output, left on the device, is this call's input, and an uncased vocabulary is
  * served by folding first.  Out of scope: the punctuation split of BERT's BasicTokenizer -- tokens are latok's --, the final-sigma
- * rule of lower-casing, Unigram models, a flow form, sentence pairs.  Byte-level BPE is a call of its own: latok_bpe_* below. */
+ * rule of lower-casing, a flow form, sentence pairs.  Byte-level BPE and Unigram models are calls of their own: latok_bpe_* and
+ * latok_unigram_* below. */
 typedef struct latok_wordpiece latok_wordpiece;
 int latok_wordpiece_create(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
                            const int32_t* word_ids /* may be NULL */, const uint8_t* prefix, int prefix_len, int max_chars, uint32_t seed,
@@ -577,8 +578,8 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
  * refused); a batch with 2^31 pieces or more is refused; n_str = 0 or total_bytes = 0 as there.  The PADDED form writes the
  * [n_str, max_length] int32 block with bos_id / eos_id where the WordPiece call puts cls_id / sep_id (add_special), and lengths_out.
  * Out of scope: GPT-2's regex pre-tokenizer -- tokens are latok's, and runs of whitespace are not encoded --, a vocab.json /
- * merges.txt loader, special-token strings inside the text, Unigram models, folding inside the call, a flow form, decoding ids back
- * to text.  (Decoding is a call family of its own: latok_detok_* below.) */
+ * merges.txt loader, special-token strings inside the text, folding inside the call, a flow form, decoding ids back
+ * to text.  (Decoding is a call family of its own: latok_detok_* below; so are Unigram models: latok_unigram_*.) */
 typedef struct latok_bpe latok_bpe;
 int latok_bpe_create(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
                      const int32_t* word_ids /* may be NULL */, int max_bytes, int lead_space, uint32_t seed, latok_bpe** bpe_out);
@@ -595,7 +596,74 @@ int latok_bpe_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_o
                                       int32_t* lengths_out /* [n_str] */, int64_t* n_pieces_out /* may be NULL */, int flags,
                                       void* stream);
 
-/* Decoding: ids back to UTF-8 bytes, for the ids of both encoder families above, whatever pre-tokenizer made them.
+/* Unigram in byte space: the Viterbi piece ids of a SentencePiece Unigram language model (T5, mT5, ALBERT, XLNet, XLM-R, mBART,
+ * Pegasus), for every token of a batch.
+ * THE VOCABULARY.  A Unigram vocabulary is an ordered list of byte strings w_0 .. w_(V-1) in the words / word_off layout of
+ * latok_vocab_create.  scores[V] is a float32 array; every score must be finite, else the create call refuses.  word_ids is optional;
+ * NULL means id = position.  Of duplicate words the first wins.  The empty word gets no slot.
+ * THE PARAMETERS.  marker: 0 to 4 bytes; when it is not empty it must be exactly one character by the rule below (for SentencePiece it
+ * is U+2581 = E2 96 81).  unk_score: a finite float32 (SentencePiece's penalty is min(scores) - 10).  fuse_unk: 0 or 1.  max_bytes: in
+ * 1 .. 4096.  seed: places the words in the tables and changes no id.
+ * A TOKEN AND ITS MARKER.  A token is what latok_token_spans_utf8_bytes_batch yields: bytes [a, e) of string s.  A token is MARKED
+ * when the marker is not empty, and the token is the first token of its string, or the previous token of the same string ends before
+ * a, that is, whitespace was dropped in front of it.  A token that touches its predecessor is not marked: "hello," gives (marker)hello
+ * and ",".
+ * CHARACTERS AND POSITIONS.  A CHARACTER of a byte range starts at the range's first byte and at every later byte b with
+ * (b & 0xC0) != 0x80; the rule is total on malformed bytes.  The VIRTUAL TEXT of a token is marker + bytes[a:e] when the token is
+ * marked, else bytes[a:e].  Its POSITIONS 0 .. n are its character starts, plus its end.
+ * THE CUT, per token:
+ *   1. Long token.  If e - a > max_bytes, the token is ONE piece (unk_id, a, e).
+ *   2. Forward pass.  Set best[0] = 0.0f; every other position is unset.  For i = 0 .. n-1 in ascending order, skipping an unset
+ *      best[i]: for every position j > i whose virtual bytes [i, j) are a word w, compute cand = best[i] + score(w) -- ONE float32
+ *      addition, nothing fused or reordered.  If best[j] is unset or cand > best[j] (strictly greater), then best[j] = cand and
+ *      back[j] = (i, w).  If no word equals the single character [i, i+1), the same update is tried for j = i+1 with unk_score and
+ *      w = unknown.  Every position ends up set.  Of equal scores the candidate met first stays, that is, the LOWER START and so the
+ *      longer last piece.
+ *   3. Backtrack.  Walk back from n through back.  A piece of virtual bytes [p, q) is reported with the string-relative byte range
+ *      [max(p - m, 0) + a, (q - m) + a), where m is the marker's length for a marked token and 0 otherwise.  A piece that is the
+ *      marker alone therefore has the empty range (a, a); a piece marker + prefix has range (a, a + len(prefix)).  An unknown piece
+ *      emits unk_id.  With fuse_unk = 1, every maximal run of neighbouring unknown pieces of a token becomes ONE piece over the union
+ *      of their ranges.  Runs never cross a token.
+ *   4. Empty vocabulary.  V = 0 is accepted.  A token is then one unk piece (fused), or n unk pieces (not fused).
+ * Exact as the ids call is: the hash finds the slot, the bytes decide.  This is the search of SentencePiece and of
+ * tokenizers.models.Unigram (which adds in float64: with scores whose sums are exact in float32 the two agree).
+ * latok_unigram_create takes HOST pointers and refuses, before any device work, what latok_vocab_create refuses, a non-finite score or
+ * unk_score, a marker longer than 4 bytes or of more than one character, a fuse_unk outside 0 / 1 and a max_bytes outside 1 .. 4096.
+ * The object holds two immutable tables of the kind latok_vocab holds (every word; the words behind the marker, without it; the slot
+ * holds the word's position), an int32 array position -> id, a float32 array position -> score, the longest word and the
+ * marker-alone word.  It may be used by any context of its device, concurrently; latok_unigram_destroy drains the current context
+ * first, like latok_vocab_destroy.  latok_unigram_info reports the word count as given, the slots of the two tables, the longest word
+ * of either table in bytes, the position of the marker-alone word (-1: none), the marker (4 bytes are written) and its length,
+ * unk_score, fuse_unk, max_bytes, the seed and the device; any output pointer may be NULL.
+ * The two calls have the contract of the BPE calls above, word for word: indptr / ids / spans as there, host pointers or
+ * LATOK_DEVICE_PTRS, total_bytes = -1, the check of the object's device, LATOK_OUT_INT32 for indptr and spans, any other flag bit
+ * refused before any device work; the capacity protocol in PIECES (cap too small: nothing is written to ids or spans, indptr stays
+ * valid, the need is in *n_pieces_out, LATOK_ERR_INVALID; cap = 0 with ids_out = NULL is a size query; ids_out = NULL with cap > 0 is
+ * refused); a batch with 2^31 pieces or more is refused; n_str = 0 or total_bytes = 0 as there.  The PADDED form writes the
+ * [n_str, max_length] int32 block with bos_id / eos_id under add_special, and lengths_out.
+ * Out of scope: SentencePiece's normalizer (NFKC, whitespace escaping) -- tokens are latok's, and folding is not part of these calls --,
+ * byte_fallback, sampling / n-best, a .model protobuf loader, a flow form, an EOS-only padded layout (T5), a decoder mode that turns
+ * the marker back into spaces (LATOK_DETOK_CONCAT gives the bytes with the marker in them), a prefix filter or trie in front of the
+ * probes. */
+typedef struct latok_unigram latok_unigram;
+int latok_unigram_create(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
+                         const float* scores /* [n_words] */, const int32_t* word_ids /* may be NULL */, const uint8_t* marker,
+                         int marker_len /* 0 .. 4 */, float unk_score, int fuse_unk, int max_bytes, uint32_t seed, latok_unigram** uni_out);
+int latok_unigram_destroy(latok_unigram* uni);
+int latok_unigram_info(const latok_unigram* uni, int64_t* n_words, int64_t* n_slots_plain, int64_t* n_slots_marked, int64_t* max_len,
+                       int64_t* marker_word, uint8_t* marker_out /* [4] */, int* marker_len, float* unk_score, int* fuse_unk,
+                       int* max_bytes, uint32_t* seed, int* device);
+int latok_unigram_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                       const latok_unigram* uni, int32_t unk_id, int64_t* indptr_out /* [n_str+1] */, int32_t* ids_out,
+                                       int64_t* spans_out /* may be NULL */, int64_t cap, int64_t* n_pieces_out,
+                                       int64_t* n_tokens_out /* may be NULL */, int flags, void* stream);
+int latok_unigram_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes,
+                                          const latok_unigram* uni, int32_t unk_id, int64_t max_length, int add_special, int32_t bos_id,
+                                          int32_t eos_id, int32_t pad_id, int32_t* input_ids_out /* [n_str*max_length] */,
+                                          int32_t* lengths_out /* [n_str] */, int64_t* n_pieces_out /* may be NULL */, int flags,
+                                          void* stream);
+
+/* Decoding: ids back to UTF-8 bytes, for the ids of the encoder families above, whatever pre-tokenizer made them.
  * A DECODER is a device object of its own, built from a word list in the words / word_off layout latok_vocab_create takes (HOST
  * pointers) and an optional int32 array word_ids (NULL means id = index).  Every int32 is a legal id; of several words with one id the
  * LOWEST INDEX wins; the empty word is a legal entry and contributes no bytes; duplicate words with different ids are all kept (a
@@ -628,7 +696,7 @@ int latok_bpe_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_o
  * for the totals, one more behind the copies with host pointers.  Every batch size takes the same kernels.  The output of a device
  * call is a valid utf8 / byte_off input of every byte-space call when its start is 16-byte aligned.
  * Out of scope: a flow form, decoding to text with error replacement, special-token strings beyond what the vocabulary holds as
- * words, Unigram models. */
+ * words.  (The ids of a Unigram model decode in CONCAT mode with a decoder built from the same word list: the marker stays in the bytes.) */
 #define LATOK_DETOK_CONCAT 0      /* BPE: a row is the concatenation of its words */
 #define LATOK_DETOK_WORDPIECE 1   /* continuation words lose the prefix, other words get a separator in front */
 typedef struct latok_detok latok_detok;

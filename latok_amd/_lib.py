@@ -92,6 +92,13 @@ SIGNATURES = {
     "latok_bpe_ids_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
     "latok_bpe_padded_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, i64, ci, C.c_int32, C.c_int32, C.c_int32, vp, vp,
                                                C.POINTER(i64), ci, vp]),
+    "latok_unigram_create": (ci, [vp, vp, i64, vp, vp, vp, ci, C.c_float, ci, ci, C.c_uint32, C.POINTER(vp)]),
+    "latok_unigram_destroy": (ci, [vp]),
+    "latok_unigram_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, C.POINTER(ci),
+                                C.POINTER(C.c_float), C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_uint32), C.POINTER(ci)]),
+    "latok_unigram_ids_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
+    "latok_unigram_padded_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, i64, ci, C.c_int32, C.c_int32, C.c_int32, vp, vp,
+                                                   C.POINTER(i64), ci, vp]),
     "latok_detok_create": (ci, [vp, vp, i64, vp, ci, vp, ci, ci, C.POINTER(vp)]),
     "latok_detok_destroy": (ci, [vp]),
     "latok_detok_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),

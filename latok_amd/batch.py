@@ -630,7 +630,7 @@ def _size_then_fill(call, n, alloc):
 
 
 class _DeviceObject:
-    """What Vocab, WordPiece, BPE, Detokenizer, Idf and TokenCounter share: ``handle`` (None once closed) of an object that ``_lib`` made and its call
+    """What Vocab, WordPiece, BPE, Unigram, Detokenizer, Idf and TokenCounter share: ``handle`` (None once closed) of an object that ``_lib`` made and its call
     named ``_destroy`` frees -- by ``close()``, on leaving a ``with`` block, or with the object.  ``_closed``: what ``_open()`` says."""
 
     handle = _destroy = _closed = None
@@ -1162,7 +1162,7 @@ class WordPiece(_DeviceObject):
     Bytes are compared verbatim: the object itself does no lower-casing and no accent stripping.  An uncased vocabulary
     (``bert-base-uncased``) is served by the ``fold=FOLD_UNCASED`` keyword of the ``wordpiece_*`` calls, which folds the batch on the
     device first (``fold_utf8_batch``; fold the words the same way if the file is not folded already).  Still out of scope: the
-    punctuation split of BERT's BasicTokenizer (tokens are latok's), the final-sigma rule, Unigram models, a flow form and
+    punctuation split of BERT's BasicTokenizer (tokens are latok's), the final-sigma rule, a flow form and
     sentence pairs; byte-level BPE is a class of its own, ``BPE``.  Immutable; ``len()`` is the number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
 
     _destroy, _closed = "latok_wordpiece_destroy", "wp must be an open latok_amd.batch.WordPiece"
@@ -1280,7 +1280,7 @@ class BPE(_DeviceObject):
     ``lead_space``: a token that follows a 0x20 byte inside its string takes that byte in front (the ``" word"`` convention of
     GPT-style vocabularies), ``seed`` the 32-bit seed of the table's hash.  This is ``tiktoken``'s model.  Out of scope: GPT-2's regex
     pre-tokenizer (tokens are latok's; runs of whitespace are not encoded), a ``vocab.json`` / ``merges.txt`` loader, special-token
-    strings inside the text, Unigram models, a ``fold=`` keyword, a flow form, ``DevicePool`` forms, decoding (a class of its own,
+    strings inside the text, a ``fold=`` keyword, a flow form, ``DevicePool`` forms, decoding (a class of its own,
     ``Detokenizer``).  Immutable; ``len()`` is the number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
 
     _destroy, _closed = "latok_bpe_destroy", "bpe must be an open latok_amd.batch.BPE"
@@ -1387,6 +1387,143 @@ def bpe_encode_utf8_batch(blobs, bpe, max_length, bos_id=None, eos_id=None, pad_
         input_ids, lengths = b.out((n_str, max_length), np.int32), b.out(n_str, np.int32, True)
         _lib.check(b.lib.latok_bpe_padded_utf8_bytes_batch(b.u8, b.off, n_str, b.total, handle, unk_id, max_length, 1 if special else 0, bos_id,
                                                            eos_id, pad_id, _arg(input_ids), _arg(lengths), None, b.flags, None))
+        input_ids, lengths = b.fetch(input_ids), b.fetch(lengths)
+    mask = (np.arange(max_length, dtype=np.int32)[None, :] < lengths[:, None]).astype(np.int32)
+    return input_ids, mask
+
+
+# Unigram: every token cut by the Viterbi search of a SentencePiece Unigram model, on the device -- as CSR rows or as the padded [n, L] block
+class Unigram(_DeviceObject):
+    """A Unigram vocabulary on the device of the current context (``latok_unigram_create``): ``words`` is the list of ``bytes`` (or
+    ``str``, encoded as UTF-8 with surrogatepass), ``scores`` one finite float32 per word (log probabilities), ``ids`` an optional int32
+    per word (default: its position; of a duplicate word the first wins), ``marker`` the 0 .. 4 bytes of ONE character that stand in
+    front of a token at a string's start or behind whitespace (SentencePiece's U+2581), ``unk_score`` the score of an unknown
+    character (default: ``float32(min(scores)) - 10``, SentencePiece's penalty; -10 for an empty vocabulary), ``fuse_unk``: neighbouring
+    unknown pieces of a token become one, ``max_bytes`` in 1 .. 4096 (a longer token is one unknown piece), ``seed`` the 32-bit seed of
+    the tables' hash.  The cut is the best-scoring split of ``marker + token`` into words, float32 sums, of equal scores the lower
+    start.  Out of scope: SentencePiece's normalizer (tokens are latok's), ``byte_fallback``, sampling, a ``.model`` protobuf loader, a
+    ``fold=`` keyword, a flow form, ``DevicePool`` forms, an EOS-only padded layout, turning the marker back into spaces when decoding
+    (a ``Detokenizer`` built from the same word list decodes the ids in ``mode="concat"``, the marker in the bytes).  Immutable;
+    ``len()`` is the number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
+
+    _destroy, _closed = "latok_unigram_destroy", "unigram must be an open latok_amd.batch.Unigram"
+
+    def __init__(self, words, scores, ids=None, marker="\u2581".encode(), unk_score=None, fuse_unk=True, max_bytes=4096, seed=0):
+        seed = _seed32(seed)
+        if not isinstance(max_bytes, (int, np.integer)) or isinstance(max_bytes, bool) or not 1 <= int(max_bytes) <= 4096:
+            raise ValueError("max_bytes must be an int in 1 .. 4096")
+        if not isinstance(fuse_unk, (bool, np.bool_)) and fuse_unk not in (0, 1):
+            raise ValueError("fuse_unk must be a bool")
+        if isinstance(marker, str):
+            marker = marker.encode("utf-8", "surrogatepass")
+        marker = bytes(marker)
+        if len(marker) > 4 or any((b & 0xC0) != 0x80 for b in marker[1:]):
+            raise ValueError("marker must be the bytes of one character, 4 at most, or empty")
+        data, off, ids = _pack_words(words, ids)
+        scores = np.ascontiguousarray(np.asarray(scores, dtype=np.float32).reshape(-1))
+        if scores.size != off.size - 1:
+            raise ValueError("scores must hold one float per word")
+        if not np.isfinite(scores).all():
+            raise ValueError("every score must be finite")
+        if unk_score is None:
+            unk_score = np.float32(scores.min()) - np.float32(10) if scores.size else np.float32(-10)
+        unk_score = np.float32(unk_score)
+        if not np.isfinite(unk_score):
+            raise ValueError("unk_score must be finite")
+        mk = np.frombuffer(marker + b"\0", np.uint8)
+        lib = _lib.ensure_init()
+        h = C.c_void_p()
+        _lib.check(lib.latok_unigram_create(_ptr(data) if data.size else None, _ptr(off), off.size - 1, _ptr(scores) if scores.size else None,
+                                            _ptr(ids) if ids is not None else None, _ptr(mk), len(marker), float(unk_score), 1 if fuse_unk else 0,
+                                            int(max_bytes), seed, C.byref(h)))
+        self._lib, self.handle, self.seed, self._n = lib, h, seed, off.size - 1
+        self.marker, self.unk_score, self.fuse_unk, self.max_bytes = marker, float(unk_score), bool(fuse_unk), int(max_bytes)
+
+    @classmethod
+    def from_vocab_file(cls, path, **kw):
+        """SentencePiece's exported ``.vocab``: one ``piece<TAB>score`` per line, the id is the line's position"""
+        words, scores = [], []
+        with open(path, "rb") as f:
+            for line in f.read().split(b"\n"):
+                if not line:
+                    continue
+                fields = line.rstrip(b"\r").split(b"\t")
+                try:
+                    if len(fields) != 2:
+                        raise ValueError
+                    scores.append(float(fields[1]))
+                except ValueError:
+                    raise ValueError("a line of a .vocab file is `piece<TAB>score`: %r" % line[:60]) from None
+                words.append(fields[0])
+        return cls(words, scores, **kw)
+
+    def info(self):
+        """dict of what ``latok_unigram_info`` reports"""
+        v = [C.c_int64(0) for _ in range(5)]
+        mk = np.zeros(4, np.uint8)
+        ml, us, fu, mb, seed, dev = C.c_int(0), C.c_float(0), C.c_int(0), C.c_int(0), C.c_uint32(0), C.c_int(0)
+        _lib.check(self._lib.latok_unigram_info(self._open(), *[C.byref(x) for x in v], _ptr(mk), C.byref(ml), C.byref(us), C.byref(fu), C.byref(mb),
+                                                C.byref(seed), C.byref(dev)))
+        return dict(n_words=v[0].value, n_slots_plain=v[1].value, n_slots_marked=v[2].value, max_len=v[3].value, marker_word=v[4].value,
+                    marker=mk.tobytes()[:ml.value], unk_score=us.value, fuse_unk=fu.value, max_bytes=mb.value, seed=seed.value, device=dev.value)
+
+    def __len__(self):
+        return self._n
+
+
+def unigram_ids_utf8_csr(utf8, byte_off, unigram, unk_id=-1, dtype=np.int64, spans=True):
+    """(indptr[n + 1], ids int32[n_pieces], spans[n_pieces, 2] or None): the Unigram ids of every string -- each token (the byte slices
+    token_spans_utf8_bytes_csr reports, the marker in front of it at a string's start and behind whitespace) is cut into the words of
+    ``unigram`` with the highest float32 score sum; a character that is no word is an ``unk_id`` piece (neighbours fused under
+    ``fuse_unk``), a token of more than ``max_bytes`` bytes ONE.  spans[r] = piece r's byte range inside its string (empty for the
+    marker alone).  indptr and spans in ``dtype``.  Cut on the device (``latok_unigram_ids_utf8_bytes_batch``): the size query, then the fill."""
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    unk_id = _unk32(unk_id)
+    dt, flags = _out_dtype(dtype)
+    handle = _handle_of(Unigram, unigram, "unigram")
+    with _HostBatch(utf8, byte_off) as b:
+        indptr, n = b.out(b.n_str + 1, dt, True), C.c_int64(0)
+
+        def call(ids=None, sp=None, cap=0):
+            return b.lib.latok_unigram_ids_utf8_bytes_batch(b.u8, b.off, b.n_str, b.total, handle, unk_id, _arg(indptr), ids, sp, cap, C.byref(n), None,
+                                                            flags | b.flags, None)
+
+        _, (ids, sp) = _size_then_fill(call, n, lambda k: (b.out(k, np.int32), b.out((k, 2), dt) if spans else None))
+        return b.fetch(indptr), b.fetch(ids), (b.fetch(sp) if spans else None)
+
+
+def unigram_ids_utf8_batch(blobs, unigram, unk_id=-1):
+    """list[bytes] (UTF-8) -> (indptr, ids, spans) of unigram_ids_utf8_csr, int64 ('' and whitespace-only -> empty rows)"""
+    unk_id = _unk32(unk_id)
+    _handle_of(Unigram, unigram, "unigram")
+    utf8, byte_off = pack_utf8(blobs)
+    return unigram_ids_utf8_csr(utf8, byte_off, unigram, unk_id, np.int64, True)
+
+
+def unigram_ids_batch(texts, unigram, unk_id=-1):
+    """list[str] -> (indptr, ids, spans): unigram_ids_utf8_batch of the strings' UTF-8 ("surrogatepass"); the spans are in bytes"""
+    return unigram_ids_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], unigram, unk_id)
+
+
+def unigram_encode_utf8_batch(blobs, unigram, max_length, bos_id=None, eos_id=None, pad_id=0, unk_id=-1):
+    """list[bytes] (UTF-8) -> (input_ids int32[n, max_length], attention_mask int32[n, max_length]).  Row s = ``bos_id``, the first
+    pieces of string s, ``eos_id``, then ``pad_id``; the two specials are added when BOTH are given and omitted when both are None.  A
+    longer row is truncated to ``max_length`` cells, specials included.  attention_mask is 1 on the cells in front of the padding.
+    One call of ``latok_unigram_padded_utf8_bytes_batch``."""
+    unk_id, pad_id = _unk32(unk_id), _unk32(pad_id)
+    if (bos_id is None) != (eos_id is None):
+        raise ValueError("bos_id and eos_id go together: give both or neither")
+    special = bos_id is not None
+    bos_id, eos_id = (_unk32(bos_id), _unk32(eos_id)) if special else (0, 0)
+    if not isinstance(max_length, (int, np.integer)) or isinstance(max_length, bool) or not 1 + 2 * special <= int(max_length) <= 0x7FFFFFFF:
+        raise ValueError("max_length must be an int >= %d" % (1 + 2 * special))
+    handle = _handle_of(Unigram, unigram, "unigram")
+    utf8, byte_off = pack_utf8(blobs)
+    n_str, max_length = len(blobs), int(max_length)
+    with _HostBatch(utf8, byte_off) as b:
+        input_ids, lengths = b.out((n_str, max_length), np.int32), b.out(n_str, np.int32, True)
+        _lib.check(b.lib.latok_unigram_padded_utf8_bytes_batch(b.u8, b.off, n_str, b.total, handle, unk_id, max_length, 1 if special else 0, bos_id,
+                                                               eos_id, pad_id, _arg(input_ids), _arg(lengths), None, b.flags, None))
         input_ids, lengths = b.fetch(input_ids), b.fetch(lengths)
     mask = (np.arange(max_length, dtype=np.int32)[None, :] < lengths[:, None]).astype(np.int32)
     return input_ids, mask

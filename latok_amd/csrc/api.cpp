@@ -15,6 +15,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cmath>
 #include <array>
 #include <atomic>
 #include <chrono>
@@ -37,6 +38,7 @@
 #include "count_table.h"
 #include "wordpiece.h"
 #include "bpe.h"
+#include "unigram.h"
 #include "fold_map.h"
 #include "fold_tables.inc"
 #include "tfidf_weight.h"
@@ -233,6 +235,7 @@ struct Workspace {
     DevBuf tkeys, tkeys2, trows;   // term counts: one key per token, the long rows' second buffer, five int64 arrays over the rows
     DevBuf wpspans, wpcnt, wprank, wpids;   // WordPiece: per token its span record, piece count and piece rank; the padded form's ids
     DevBuf bpemask;   // BPE (which uses the WordPiece buffers as well): per token of at most 64 bytes its final part-start mask
+    DevBuf unimarks;   // Unigram (which uses the WordPiece buffers as well): per token of at most 64 bytes three words of the count pass
     DevBuf ngrows;   // word n-grams: gram counts and row starts in key space (the span records share wpspans, the keys tkeys / tkeys2)
     DevBuf tfptr, tfidx, tfval, tfctl;   // TF-IDF: a host caller's CSR on the device (indptr, indices, data) and the error word of k_csr_check
     // decoding (which stages a host caller's rows and ids in tfptr / tfidx and keeps its error word and unknown tally in tfctl): output
@@ -246,7 +249,7 @@ struct Workspace {
     void release() {
         for (DevBuf* b : {&summ, &seg_agg, &fix_count, &tile_first, &bits, &space, &kept, &wcnt, &wpref, &bases, &scalar, &chain,
                           &chain_ctl, &codes, &widened, &lead, &bspace, &cpbits, &cpspace, &cprow, &jbody, &jhead, &tkeys,
-                          &tkeys2, &trows, &wpspans, &wpcnt, &wprank, &wpids, &bpemask, &ngrows, &tfptr, &tfidx, &tfval, &tfctl, &dtcnt, &dtsum, &dtrank, &dtrows})
+                          &tkeys2, &trows, &wpspans, &wpcnt, &wprank, &wpids, &bpemask, &unimarks, &ngrows, &tfptr, &tfidx, &tfval, &tfctl, &dtcnt, &dtsum, &dtrank, &dtrows})
             b->release();
         scan_epoch = chain_seen = chain_ctl_seen = 0;
         chain_ready = false;
@@ -257,7 +260,7 @@ struct WsNeed {
     size_t bytes;   // 0: the batch does not use the buffer
 };
 constexpr int kTileNeeds = 4;   // the first entries of ws_needs: the tile stage
-constexpr int kWsNeeds = 39;
+constexpr int kWsNeeds = 40;
 // What a batch asks of its workspace beyond the tile stage.  token spans (spans) add the SPACE and kept planes, featurize (feats)
 // the code bytes, and narrow units read by featurize (widen) a UTF-32 copy.  cp_rows > 0: the units are UTF-8 bytes whose results
 // are reported in code points (cp_rows = n_str + 1): every buffer is sized by the byte count, which bounds the code-point count.
@@ -267,6 +270,7 @@ constexpr int kWsNeeds = 39;
 // row arrays of term_rows): 16 bytes of span record, 8 of piece count and 8 of piece rank per token, one entry more in the last two,
 // and a scan state for that many entries; wp_pieces: the piece total, which the padded form waits for before it sizes its ids.
 // bpe_tokens: the token total once more, for the BPE calls (which set wp_tokens too): 8 bytes of part-start mask per token.
+// uni_tokens: the same for the Unigram calls: 24 bytes per token (the piece starts, the unknown pieces, the marker piece's flag).
 // Word n-grams (which use the row arrays of term_rows as well): ng_tokens, the token total: 16 bytes of span record per token, in the
 // buffer the WordPiece calls keep theirs in; ng_rows > 0 (= n_str + 1): the gram counts and the row starts in key space; ng_keys:
 // the key total, which the n-gram call waits for before it sizes the two key buffers -- the term counts' own, one key per gram.
@@ -282,6 +286,7 @@ struct WsShape {
     int64_t term_rows = 0, term_tokens = 0;
     int64_t wp_tokens = 0, wp_pieces = 0;
     int64_t bpe_tokens = 0;
+    int64_t uni_tokens = 0;
     int64_t ng_tokens = 0, ng_rows = 0, ng_keys = 0;
     bool tf_ctl = false;
     int64_t tf_ptr_bytes = 0, tf_entries = 0;
@@ -328,6 +333,7 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const 
              {&w.wprank, shape.wp_tokens > 0 ? (size_t)(shape.wp_tokens + 1) * 8 : 0},
              {&w.wpids, shape.wp_pieces > 0 ? (size_t)shape.wp_pieces * 4 : 0},
              {&w.bpemask, shape.bpe_tokens > 0 ? (size_t)shape.bpe_tokens * 8 : 0},
+             {&w.unimarks, shape.uni_tokens > 0 ? (size_t)shape.uni_tokens * 24 : 0},
              {&w.tfptr, (size_t)shape.tf_ptr_bytes},
              {&w.tfidx, shape.tf_entries > 0 ? (size_t)shape.tf_entries * 4 + 16 : 0},
              {&w.tfval, shape.tf_entries > 0 ? (size_t)shape.tf_entries * 4 + 16 : 0},
@@ -3334,10 +3340,110 @@ int latok_bpe_info(const latok_bpe* bpe, int64_t* n_words, int64_t* n_slots, int
     return LATOK_OK;
 }
 
-// the object of a piece call: a WordPiece vocabulary or a BPE one (exactly one is set), and the route numbers of its two forms
+/* Unigram in byte space (latok_unigram_ids_utf8_bytes_batch, latok_unigram_padded_utf8_bytes_batch): the calls of the WordPiece and BPE
+ * pairs with a third cut.  The object holds two vocab_table.h tables whose id slot is the word's position in the list (every word; the
+ * words behind the marker), the position -> id and position -> score arrays, the longest word of either table and the marker-alone
+ * word (unigram.h), built on the host, uploaded once, read only afterwards.  The stream is enqueue_wordpiece's, with k_uni_count /
+ * k_uni_emit (unigram_kernels.hip) in place of k_wp_count / k_wp_emit and 24 bytes per token between the two. */
+struct Unigram {                   // latok_unigram: immutable once created
+    int device = -1;
+    int64_t n_words = 0;
+    uint32_t max_len_plain = 0, max_len_marked = 0;
+    int32_t marker_pos = -1;
+    uint8_t marker[kUniMaxMarker] = {0};
+    int marker_len = 0;
+    float unk_score = 0.0f;
+    int fuse_unk = 0, max_bytes = 0;
+    uint32_t seed = 0;
+    DevTable plain, marked;
+    DevMem pos_id, pos_score;
+};
+int latok_unigram_create(const uint8_t* words, const int64_t* word_off, int64_t n_words, const float* scores, const int32_t* word_ids,
+                         const uint8_t* marker, int marker_len, float unk_score, int fuse_unk, int max_bytes, uint32_t seed, latok_unigram** uni_out) {
+    LATOK_ENTER();
+    // what needs no device is refused first
+    if (!uni_out) return fail(LATOK_ERR_INVALID, "uni_out is NULL");
+    *uni_out = nullptr;
+    if (max_bytes < 1 || max_bytes > kUniMaxBytes) return fail(LATOK_ERR_INVALID, "max_bytes must be in 1 .. %d", kUniMaxBytes);
+    if (fuse_unk != 0 && fuse_unk != 1) return fail(LATOK_ERR_INVALID, "fuse_unk must be 0 or 1");
+    if (marker_len < 0 || marker_len > kUniMaxMarker) return fail(LATOK_ERR_INVALID, "marker_len must be in 0 .. %d", kUniMaxMarker);
+    if (marker_len > 0 && !marker) return fail(LATOK_ERR_INVALID, "marker is NULL");
+    if (!uni_marker_ok(marker, marker_len)) return fail(LATOK_ERR_INVALID, "the marker must be exactly one character");
+    if (!std::isfinite(unk_score)) return fail(LATOK_ERR_INVALID, "unk_score must be finite");
+    int rc = check_word_list(words, word_off, n_words);
+    if (rc) return rc;
+    if (n_words > 0 && !scores) return fail(LATOK_ERR_INVALID, "scores is NULL");
+    for (int64_t i = 0; i < n_words; ++i)
+        if (!std::isfinite(scores[i])) return fail(LATOK_ERR_INVALID, "scores[%lld] is not finite", (long long)i);
+    if ((rc = need_init(g))) return rc;
+    UniTables t;
+    Unigram* v = nullptr;
+    try {
+        uni_build(words, word_off, n_words, scores, word_ids, marker, marker_len, seed, &t);
+        v = new Unigram();
+    } catch (const std::bad_alloc&) {
+        return fail(LATOK_ERR_NOMEM, "out of host memory");
+    }
+    v->device = g.device;
+    v->n_words = n_words;
+    v->max_len_plain = t.max_len_plain;
+    v->max_len_marked = t.max_len_marked;
+    v->marker_pos = t.marker_pos;
+    for (int i = 0; i < marker_len; ++i) v->marker[i] = marker[i];
+    v->marker_len = marker_len;
+    v->unk_score = unk_score;
+    v->fuse_unk = fuse_unk;
+    v->max_bytes = max_bytes;
+    v->seed = seed;
+    if ((rc = v->plain.upload(t.plain, g.stream)) == LATOK_OK && (rc = v->marked.upload(t.marked, g.stream)) == LATOK_OK) {
+        const size_t bytes = t.pos_id.size() * 4;
+        hipError_t e = v->pos_id.alloc(bytes);
+        if (e == hipSuccess) e = v->pos_score.alloc(bytes);
+        if (e != hipSuccess) rc = fail(LATOK_ERR_NOMEM, "hipMalloc(%zu) failed: %s", 2 * bytes, hipGetErrorString(e));
+        else if ((e = hipMemcpyAsync(v->pos_id.p, t.pos_id.data(), bytes, hipMemcpyHostToDevice, g.stream)) != hipSuccess ||
+                 (e = hipMemcpyAsync(v->pos_score.p, t.pos_score.data(), bytes, hipMemcpyHostToDevice, g.stream)) != hipSuccess)
+            rc = fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(g.stream);   // (the host tables die with this call, and every context may use the object at once)
+    if (!rc && e != hipSuccess) rc = fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
+    if (rc) {
+        delete v;
+        return rc;
+    }
+    *uni_out = reinterpret_cast<latok_unigram*>(v);
+    return LATOK_OK;
+}
+
+int latok_unigram_destroy(latok_unigram* uni) {
+    LATOK_ENTER();
+    return destroy_object(g, reinterpret_cast<Unigram*>(uni));
+}
+
+int latok_unigram_info(const latok_unigram* uni, int64_t* n_words, int64_t* n_slots_plain, int64_t* n_slots_marked, int64_t* max_len,
+                       int64_t* marker_word, uint8_t* marker_out, int* marker_len, float* unk_score, int* fuse_unk, int* max_bytes, uint32_t* seed,
+                       int* device) {
+    const Unigram* v = reinterpret_cast<const Unigram*>(uni);
+    if (!v) return fail(LATOK_ERR_INVALID, "uni is NULL");
+    if (n_words) *n_words = v->n_words;
+    if (n_slots_plain) *n_slots_plain = (int64_t)v->plain.n_slots;
+    if (n_slots_marked) *n_slots_marked = (int64_t)v->marked.n_slots;
+    if (max_len) *max_len = std::max(v->max_len_plain, v->max_len_marked);
+    if (marker_word) *marker_word = v->marker_pos;
+    if (marker_out) memcpy(marker_out, v->marker, kUniMaxMarker);
+    if (marker_len) *marker_len = v->marker_len;
+    if (unk_score) *unk_score = v->unk_score;
+    if (fuse_unk) *fuse_unk = v->fuse_unk;
+    if (max_bytes) *max_bytes = v->max_bytes;
+    if (seed) *seed = v->seed;
+    if (device) *device = v->device;
+    return LATOK_OK;
+}
+
+// the object of a piece call: a WordPiece vocabulary, a BPE one or a Unigram one (exactly one is set), and the route numbers of its two forms
 struct PieceCut {
     const WordPiece* wp = nullptr;
     const Bpe* bpe = nullptr;
+    const Unigram* uni = nullptr;
     int route_ids = 11, route_padded = 12;
 };
 
@@ -3371,7 +3477,8 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
         return rc;
     int64_t* d_total = (int64_t*)w.scalar.p;
     const int64_t n_tok = a.n_tokens;
-    if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok, .bpe_tokens = a.cut.bpe ? n_tok : 0}).data(),
+    if (n_tok > 0 && (rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok, .bpe_tokens = a.cut.bpe ? n_tok : 0,
+                                                                 .uni_tokens = a.cut.uni ? n_tok : 0}).data(),
                                     kWsNeeds)))
         return rc;
     int64_t* d_cnt = (int64_t*)w.trows.p;       // token count of every string, one zero entry behind them
@@ -3386,6 +3493,8 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
         latok::WordPieceTables wt;
         latok::BpeTable bt;
         uint64_t* d_mask = (uint64_t*)w.bpemask.p;
+        latok::UniTable ut;
+        uint64_t* d_marks = (uint64_t*)w.unimarks.p;
         if (const Bpe* b = a.cut.bpe) {
             bt.table = b->table.view(b->seed);
             bt.rank_id = b->rank_id.as<const int32_t>();
@@ -3394,6 +3503,20 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
             bt.max_bytes = b->max_bytes;
             bt.lead_space = b->lead_space;
             HIP_TRY(latok::launch_bpe_count(text, bt, d_pcnt, d_mask, st));
+        } else if (const Unigram* u = a.cut.uni) {
+            ut.plain = u->plain.view(u->seed);
+            ut.marked = u->marked.view(u->seed);
+            ut.pos_id = u->pos_id.as<const int32_t>();
+            ut.pos_score = u->pos_score.as<const float>();
+            ut.n_words = u->n_words;
+            ut.max_len_plain = u->max_len_plain;
+            ut.max_len_marked = u->max_len_marked;
+            ut.marker_pos = u->marker_pos;
+            ut.marker_len = u->marker_len;
+            ut.unk_score = u->unk_score;
+            ut.fuse_unk = u->fuse_unk;
+            ut.max_bytes = u->max_bytes;
+            HIP_TRY(latok::launch_uni_count(text, ut, d_pcnt, d_marks, st));
         } else {
             const WordPiece* v = a.cut.wp;
             wt.initial = v->initial.view(v->seed);
@@ -3410,13 +3533,14 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
             if ((rc = second_sized_total(w, a.h_tot, 3, st, nullptr, &cap))) return rc;   // wait 2 (padded form): the piece total sizes the ids
             if (cap >= (1ll << 31)) return LATOK_OK;   // (the caller refuses it)
             if ((rc = ws_ensure(ws_needs(w, total, WsShape{.spans = true, .term_rows = n_str + 1, .wp_tokens = n_tok, .wp_pieces = cap,
-                                                              .bpe_tokens = a.cut.bpe ? n_tok : 0}).data(),
+                                                              .bpe_tokens = a.cut.bpe ? n_tok : 0, .uni_tokens = a.cut.uni ? n_tok : 0}).data(),
                                 kWsNeeds)))
                 return rc;
             ids = (int32_t*)w.wpids.p;
             d_ids = ids;
         }
         if (ids && a.cut.bpe) HIP_TRY(latok::launch_bpe_emit(a.o32, text, bt, a.unk, d_prank, d_mask, d_total + 5, cap, ids, a.spans, st));
+        else if (ids && a.cut.uni) HIP_TRY(latok::launch_uni_emit(a.o32, text, ut, a.unk, d_prank, d_marks, d_total + 5, cap, ids, a.spans, st));
         else if (ids) HIP_TRY(latok::launch_wp_emit(a.o32, text, wt, a.unk, d_prank, d_total + 5, cap, ids, a.spans, st));
         if (a.indptr) HIP_TRY(latok::launch_wp_rows(a.o32, d_start, d_prank, n_str, n_tok, a.indptr, st));
     } else if (a.indptr) {
@@ -3460,8 +3584,9 @@ static int piece_ids_call(const uint8_t* utf8, const int64_t* byte_off, int64_t 
     a.indptr = indptr_out;
     a.ids = ids_out;
     a.spans = ids_out ? spans_out : nullptr;
-    // (a piece has at least one byte: a larger capacity gates nothing, and the staging is sized by it; 2^31 pieces or more are refused)
-    a.cap = ids_out ? std::min({cap, c.total, (int64_t)0x7FFFFFFF}) : 0;
+    // (a piece has at least one byte -- but for the marker-alone piece of a Unigram token, one per token at most: a larger capacity
+    // gates nothing, and the staging is sized by it; 2^31 pieces or more are refused)
+    a.cap = ids_out ? std::min({cap, cut.uni ? 2 * c.total : c.total, (int64_t)0x7FFFFFFF}) : 0;
     a.o32 = c.o32;
     if (!dev) {
         if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 2 * elt + 16)) || (rc = g.counts.ensure((size_t)(n_str + 1) * 8)))
@@ -3492,7 +3617,13 @@ int latok_wordpiece_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byt
 int latok_bpe_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_bpe* bpe,
                                    int32_t unk_id, int64_t* indptr_out, int32_t* ids_out, int64_t* spans_out, int64_t cap, int64_t* n_pieces_out,
                                    int64_t* n_tokens_out, int flags, void* stream) {
-    return piece_ids_call(utf8, byte_off, n_str, total_bytes, bpe, "bpe is NULL", PieceCut{nullptr, nullptr, 18, 19}, &PieceCut::bpe, unk_id, indptr_out,
+    return piece_ids_call(utf8, byte_off, n_str, total_bytes, bpe, "bpe is NULL", PieceCut{.route_ids = 18, .route_padded = 19}, &PieceCut::bpe, unk_id, indptr_out,
+                          ids_out, spans_out, cap, n_pieces_out, n_tokens_out, flags, stream);
+}
+int latok_unigram_ids_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_unigram* uni,
+                                       int32_t unk_id, int64_t* indptr_out, int32_t* ids_out, int64_t* spans_out, int64_t cap, int64_t* n_pieces_out,
+                                       int64_t* n_tokens_out, int flags, void* stream) {
+    return piece_ids_call(utf8, byte_off, n_str, total_bytes, uni, "uni is NULL", PieceCut{.route_ids = 22, .route_padded = 23}, &PieceCut::uni, unk_id, indptr_out,
                           ids_out, spans_out, cap, n_pieces_out, n_tokens_out, flags, stream);
 }
 
@@ -3572,7 +3703,13 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
 int latok_bpe_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_bpe* bpe,
                                       int32_t unk_id, int64_t max_length, int add_special, int32_t bos_id, int32_t eos_id, int32_t pad_id,
                                       int32_t* input_ids_out, int32_t* lengths_out, int64_t* n_pieces_out, int flags, void* stream) {
-    return piece_padded_call(utf8, byte_off, n_str, total_bytes, bpe, "bpe is NULL", PieceCut{nullptr, nullptr, 18, 19}, &PieceCut::bpe, unk_id, max_length,
+    return piece_padded_call(utf8, byte_off, n_str, total_bytes, bpe, "bpe is NULL", PieceCut{.route_ids = 18, .route_padded = 19}, &PieceCut::bpe, unk_id, max_length,
+                             add_special, bos_id, eos_id, pad_id, input_ids_out, lengths_out, n_pieces_out, flags, stream);
+}
+int latok_unigram_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, const latok_unigram* uni,
+                                          int32_t unk_id, int64_t max_length, int add_special, int32_t bos_id, int32_t eos_id, int32_t pad_id,
+                                          int32_t* input_ids_out, int32_t* lengths_out, int64_t* n_pieces_out, int flags, void* stream) {
+    return piece_padded_call(utf8, byte_off, n_str, total_bytes, uni, "uni is NULL", PieceCut{.route_ids = 22, .route_padded = 23}, &PieceCut::uni, unk_id, max_length,
                              add_special, bos_id, eos_id, pad_id, input_ids_out, lengths_out, n_pieces_out, flags, stream);
 }
 
@@ -4564,6 +4701,17 @@ extern "C" int latok_debug_bpe_limits(int64_t* out, int n) {
     return k;
 }
 
+/* test hook (not part of the ABI; needs no device): the constants of the Unigram calls: out[0] = kUniBlock (tokens per workgroup of
+ * k_uni_count / k_uni_emit), out[1] = entries per workgroup of the chained scan over the piece counts, out[2] = kUniLaneBytes (the
+ * longest token of the lane form), out[3] = kUniMaxBytes (the ceiling of max_bytes).  Returns the number of values written. */
+extern "C" int latok_debug_unigram_limits(int64_t* out, int n) {
+    const int64_t v[4] = {latok::kUniBlock, latok::scan_chunk(), kUniLaneBytes, kUniMaxBytes};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 4 ? n : 4;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
 /* test hook (not part of the ABI; needs no device): the constants of the two device-wide int64 scans: out[0] = kChainChunk (entries per
  * workgroup of k_scan_chained), out[1] = predecessors one look-back round reads (64), out[2] = kChainValueBits, out[3] = bits of the
  * launch epoch (18), out[4] = kScanSmallMax, out[5] = kScanChunk (entries per workgroup of k_scan_local), out[6] = kScanBlock.  Returns
@@ -4719,7 +4867,8 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
  * 13: case folding of UTF-8 in byte space (likewise); 14 / 15: word n-gram counts, vocabulary form / hashed form (likewise);
  * 16 / 17: character n-gram counts inside tokens, vocabulary form / hashed form (likewise);
  * 18 / 19: byte-level BPE ids of UTF-8 in byte space, CSR form / padded form (likewise);
- * 20 / 21: decoding, ids back to bytes, CSR form / padded form (likewise) */
+ * 20 / 21: decoding, ids back to bytes, CSR form / padded form (likewise);
+ * 22 / 23: Unigram ids of UTF-8 in byte space, CSR form / padded form (likewise) */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;

@@ -419,6 +419,27 @@ struct BpeTable {
 hipError_t launch_bpe_count(const TokenText& t, const BpeTable& bt, int64_t* cnt, uint64_t* masks, hipStream_t st);
 hipError_t launch_bpe_emit(bool out32, const TokenText& t, const BpeTable& bt, int32_t unk_id, const int64_t* rank, const uint64_t* masks,
                            const int64_t* n_pieces_dev, int64_t cap, int32_t* ids, void* spans, hipStream_t st);
+// Unigram (Viterbi) ids (unigram_kernels.hip, unigram.h).  launch_uni_count leaves the pieces of every token in cnt[0 .. n_tok) and 0
+// in cnt[n_tok], and three words per token of at most 64 bytes in marks[] (three arrays of n_tok words: the piece starts, which of them
+// are unknown, whether the marker's piece is); the caller scans the n_tok + 1 entries into rank[]; launch_uni_emit stores ids (through
+// pos_id) and string-relative spans if asked for at the piece rank, only if the total fits cap.  Row pointers and the padded block are
+// launch_wp_rows / launch_wp_pad.  Device memory, read only.
+constexpr int kUniBlock = 128;   // tokens per workgroup of k_uni_count / k_uni_emit (latok_debug_unigram_limits)
+struct UniTable {
+    VocabTable plain, marked;           // id slot = the word's position in the list (the seed is the same in both)
+    const int32_t* pos_id = nullptr;    // [max(n_words, 1)]
+    const float* pos_score = nullptr;   // [max(n_words, 1)]
+    int64_t n_words = 0;
+    uint32_t max_len_plain = 0, max_len_marked = 0;   // bytes of the longest word of either table
+    int32_t marker_pos = -1;            // the word that is the marker alone
+    int marker_len = 0;                 // 0: no token is marked
+    float unk_score = 0.0f;
+    int fuse_unk = 0;
+    int max_bytes = 0;                  // 1 .. 4096
+};
+hipError_t launch_uni_count(const TokenText& t, const UniTable& ut, int64_t* cnt, uint64_t* marks, hipStream_t st);
+hipError_t launch_uni_emit(bool out32, const TokenText& t, const UniTable& ut, int32_t unk_id, const int64_t* rank, const uint64_t* marks,
+                           const int64_t* n_pieces_dev, int64_t cap, int32_t* ids, void* spans, hipStream_t st);
 // The gram keys of the term family: one term key per gram of the orders min_n .. max_n, each inside its own range of `keys`, which
 // holds n_keys keys; the lookup spells a gram with `joiner` between its tokens (word grams) or around the word (character grams).
 // launch_terms_reduce / _emit / _finish then take keys and the key-space row starts as they take the token keys and the token rows.

@@ -75,6 +75,14 @@
   py_bpe         end to end in Python on host blobs (the first --py-strings strings): batch.bpe_ids_utf8_batch(blobs, bpe) against
                   batch.tokenize_utf8_batch(blobs) + the merge loop over a dict (lead_space = 0 there: the host route has no spans);
                   equal rows asserted first; one line each
+  bytes_uni32 / bytes_uni_padded   latok_unigram_ids_utf8_bytes_batch (int32 indptr and spans, capacity = the piece total of a size query) /
+                  latok_unigram_padded_utf8_bytes_batch ([n, 64] block with BOS / EOS); the vocabulary is the characters of the 256 single
+                  bytes plus the --uni-words most frequent tokens of the first --py-strings strings of the leg's own corpus, their
+                  prefixes and suffixes, and the tokens once more behind the marker U+2581 (and the marker alone); scores = log of the
+                  relative frequency, rounded to 1/64; same process run as bytes_bpe32, bytes_wp32 and bytes_ids32, which are its yardsticks
+  py_uni         end to end in Python on host blobs (the first --py-strings strings): batch.unigram_ids_utf8_batch(blobs, unigram) against
+                  batch.token_spans_utf8_bytes_csr + the Viterbi loop over a dict (memoised per distinct token); equal rows asserted first;
+                  one line each
   py_terms       end to end in Python on host blobs (the first --py-strings strings): batch.term_counts_utf8_batch(blobs, vocab)
                   against batch.tokenize_utf8_batch(blobs) + a dict and collections.Counter per row; one line each
   py_count       end to end in Python on host blobs (the first --py-strings strings): TokenCounter.update_utf8 + most_common()
@@ -153,6 +161,7 @@ def main():
                                        "kind_spans,kind_spans32")
     ap.add_argument("--py-strings", type=int, default=200_000, help="strings of the py_join / py_ids / py_terms paths (host blobs)")
     ap.add_argument("--bpe-merges", type=int, default=400, help="merges of the byte-pair trainer of the bpe paths")
+    ap.add_argument("--uni-words", type=int, default=4000, help="most frequent tokens that seed the vocabulary of the unigram paths")
     ap.add_argument("--vocab", default="all", choices=("all", "half"), help="vocabulary of the ids paths: every distinct token of the corpus, or every second one")
     args = ap.parse_args()
     lib = _lib.ensure_init()
@@ -436,7 +445,7 @@ def main():
                                           "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "bytes_ngrams32", "bytes_ngrams_hashed", "py_terms",
                                           "bytes_chargrams32", "bytes_chargrams_hashed", "bytes_tfidf32", "bytes_tfidf_hashed", "bytes_df_update", "csr_tfidf", "csr_df", "py_tfidf",
                                           "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join", "bytes_wp32", "bytes_wp_padded", "py_wp",
-                                          "bytes_bpe32", "bytes_bpe_padded", "py_bpe", "ids_detok_bpe", "ids_detok_wp", "py_detok",
+                                          "bytes_bpe32", "bytes_bpe_padded", "py_bpe", "bytes_uni32", "bytes_uni_padded", "py_uni", "ids_detok_bpe", "ids_detok_wp", "py_detok",
                                           "bytes_fold", "bytes_fold_wp", "py_fold")]
     if join_leg:
         jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64, cap * 4, cap * 4)]
@@ -702,6 +711,64 @@ def main():
             b, _, b_block, b_len = corpus_bpe()[:4]
             return lib.latok_bpe_padded_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, WP_LEN, 1, 1, 2, 0, b_block, b_len, C.byref(nout), D, None)
 
+        uni_box = []
+        UNI_MARKER = "\u2581".encode()
+
+        def uni_vocab(tokens):
+            """(words, scores): the characters of the 256 single bytes, the --uni-words most frequent tokens with their prefixes and
+            suffixes (cut at character starts), the tokens behind the marker, the marker alone; scores = log relative frequency in 1/64"""
+            import math
+            from collections import Counter
+            freq = Counter()
+            for t, c in Counter(tokens).most_common(args.uni_words):
+                starts = [i for i in range(len(t)) if i == 0 or (t[i] & 0xC0) != 0x80] + [len(t)]
+                for k in starts[1:]:
+                    freq[t[:k]] += c
+                for k in starts[1:-1]:
+                    freq[t[k:]] += c
+                freq[UNI_MARKER + t] += c
+                freq[UNI_MARKER] += c
+            for b in range(256):
+                freq[chr(b).encode()] += 1
+            total = sum(freq.values())
+            words = sorted(freq, key=lambda w: (-freq[w], w))
+            return words, [round(math.log(freq[w] / total) * 64) / 64 for w in words]
+
+        def corpus_uni():
+            """the Unigram vocabulary of the uni paths and their buffers, built once (the ids are sized by a size query)"""
+            if not uni_box:
+                from latok_amd import batch
+                t = time.perf_counter()
+                words, scores = uni_vocab(bpe_sample_tokens(False)[2])
+                train_ms = (time.perf_counter() - t) * 1e3
+                t = time.perf_counter()
+                u = batch.Unigram(words, scores, seed=SEED)
+                create_ms = (time.perf_counter() - t) * 1e3
+                bufs = [lib.latok_dev_alloc(sz) for sz in ((n + 1) * 4 + 64, n * WP_LEN * 4 + 64, n * 4 + 64)]
+                if not all(bufs):
+                    raise RuntimeError(_lib.last_error())
+                need, n_tok = C.c_int64(0), C.c_int64(0)
+                rc = lib.latok_unigram_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, u.handle, -1, bufs[0], None, None, 0, C.byref(need), C.byref(n_tok), D32, None)
+                if rc != _lib.OK and need.value <= 0:
+                    _lib.check(rc)
+                info = u.info()
+                info["marker"] = info["marker"].hex()
+                print(json.dumps(dict(info, unigram_words=len(words), workload=args.workload, train_ms=train_ms, create_ms=create_ms, pieces=need.value,
+                                      tokens=n_tok.value, pieces_per_token=need.value / max(n_tok.value, 1))), flush=True)
+                pieces = [lib.latok_dev_alloc(need.value * 4 + 64), lib.latok_dev_alloc(need.value * 8 + 64)]
+                if not all(pieces):
+                    raise RuntimeError(_lib.last_error())
+                uni_box.extend([u] + bufs + pieces + [need.value])
+            return uni_box
+
+        def uni_blocking():
+            u, u_indptr, _, _, u_ids, u_spans, need = corpus_uni()
+            return lib.latok_unigram_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, u.handle, -1, u_indptr, u_ids, u_spans, need, C.byref(nout), None, D32, None)
+
+        def uni_padded_blocking():
+            u, _, u_block, u_len = corpus_uni()[:4]
+            return lib.latok_unigram_padded_utf8_bytes_batch(d_u8, d_boff, n, n8, u.handle, -1, WP_LEN, 1, 1, 2, 0, u_block, u_len, C.byref(nout), D, None)
+
         note_d = ("4 B/id read + 4 B/string indptr read; 1 B/output byte + 8 B/string row offsets written. NOT counted: the second read of the "
                   "ids and the 4 B/piece byte counts written and read (workspace), the id map and entry records (cache resident), the blob bytes")
 
@@ -953,6 +1020,87 @@ def main():
             elif name == "bytes_bpe_padded":   # (items = the untruncated piece total; the block is [n, WP_LEN] with BOS / EOS)
                 run(name, bpe_padded_blocking, lambda: n8 + csr + 4 * n + 4 * n * WP_LEN,
                     note_b.replace("4 B/string indptr + 4 B/piece ids + 8 B/piece spans", "4 B/string lengths + 4 B/cell of the [n, %d] block" % WP_LEN))
+            elif name == "bytes_uni32":   # (items = pieces)
+                run(name, uni_blocking, lambda: n8 + csr + 4 * n + 12 * nout.value,
+                    note_b.replace("ranks and part-start masks", "ranks and 24 B/token piece masks").replace("every pair lookup", "every (start, end) lookup"))
+            elif name == "bytes_uni_padded":   # (items = the untruncated piece total; the block is [n, WP_LEN] with BOS / EOS)
+                run(name, uni_padded_blocking, lambda: n8 + csr + 4 * n + 4 * n * WP_LEN,
+                    note_b.replace("4 B/string indptr + 4 B/piece ids + 8 B/piece spans", "4 B/string lengths + 4 B/cell of the [n, %d] block" % WP_LEN)
+                    .replace("ranks and part-start masks", "ranks and 24 B/token piece masks").replace("every pair lookup", "every (start, end) lookup"))
+            elif name == "py_uni":   # host blobs in, the CSR arrays out, both routes in this process
+                from latok_amd import batch
+                blobs, blob, toks = bpe_sample_tokens(False)
+                words, scores = uni_vocab(toks)
+                d = {}
+                for i, w in enumerate(words):
+                    d.setdefault(w, i)
+                unk_score = min(scores) - 10
+                longest = max(map(len, words))
+                memo = {}
+
+                def cut(tok, marked):
+                    got = memo.get((tok, marked))
+                    if got is None:
+                        text = UNI_MARKER + tok if marked else tok
+                        pos = [i for i in range(len(text)) if i == 0 or (text[i] & 0xC0) != 0x80] + [len(text)]
+                        k = len(pos) - 1
+                        best, back = [None] * (k + 1), [None] * (k + 1)
+                        best[0] = 0.0
+                        for i in range(k):
+                            single = False
+                            for j in range(i + 1, k + 1):
+                                if pos[j] - pos[i] > longest:
+                                    break
+                                w = d.get(text[pos[i]:pos[j]])
+                                if w is not None:
+                                    single = single or j == i + 1
+                                    c = best[i] + scores[w]
+                                    if best[j] is None or c > best[j]:
+                                        best[j], back[j] = c, (i, w)
+                            if not single:
+                                c = best[i] + unk_score
+                                if best[i + 1] is None or c > best[i + 1]:
+                                    best[i + 1], back[i + 1] = c, (i, -1)
+                        got, j = [], k
+                        while j > 0:
+                            i, w = back[j]
+                            if not (w == -1 and got and got[-1] == -1):   # (fused)
+                                got.append(w)
+                            j = i
+                        got.reverse()
+                        memo[(tok, marked)] = got
+                    return got
+
+                def on_host():
+                    memo.clear()   # (the memo is part of the loop: one search per distinct (token, marked) of the call)
+                    u8h, offh = batch.pack_utf8(blobs)
+                    counts, spans = batch.token_spans_utf8_bytes_csr(u8h, offh)
+                    raw, sp = u8h.tobytes(), spans.tolist()
+                    indptr, ids, t = [0], [], 0
+                    for s, c in enumerate(counts.tolist()):
+                        base, prev = int(offh[s]), -1
+                        for _ in range(c):
+                            a, e = sp[t]
+                            ids.extend(cut(raw[base + a:base + e], prev < a))
+                            prev = e
+                            t += 1
+                        indptr.append(len(ids))
+                    return np.array(indptr, np.int64), np.array(ids, np.int32)
+
+                with batch.Unigram(words, scores, seed=SEED) as u:
+                    routes = (("py_unigram_ids_utf8_batch", lambda: batch.unigram_ids_utf8_batch(blobs, u)[:2]),
+                              ("py_token_spans_then_viterbi_loop", on_host))
+                    assert all(np.array_equal(x, y) for x, y in zip(routes[0][1](), routes[1][1]()))
+                    for r in range(args.repeat):
+                        for rname, fn in routes:
+                            t = time.perf_counter()
+                            got = fn()
+                            dt = time.perf_counter() - t
+                            print(json.dumps({"path": rname, "workload": args.workload, "strings": len(blobs), "utf8_bytes": len(blob),
+                                              "words": len(words), "pieces": int(got[1].size), "unk": int((got[1] == -1).sum()), "ms_per_call": dt * 1e3,
+                                              "utf8_GBps": len(blob) / dt / 1e9,
+                                              "note": "end to end in Python: list[bytes] in, (indptr, ids) out, pack and host work included",
+                                              "repeat": r}), flush=True)
             elif name in ("ids_detok_bpe", "ids_detok_wp"):   # (items = output bytes) the resident ids of one encode call decoded back
                 kind = name[len("ids_detok_"):]
                 n_pieces = detok_of(kind)[3]
