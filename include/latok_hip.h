@@ -577,9 +577,12 @@ int latok_wordpiece_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* 
  * valid, the need is in *n_pieces_out, LATOK_ERR_INVALID; cap = 0 with ids_out = NULL is a size query; ids_out = NULL with cap > 0 is
  * refused); a batch with 2^31 pieces or more is refused; n_str = 0 or total_bytes = 0 as there.  The PADDED form writes the
  * [n_str, max_length] int32 block with bos_id / eos_id where the WordPiece call puts cls_id / sep_id (add_special), and lengths_out.
- * Out of scope: GPT-2's regex pre-tokenizer -- tokens are latok's, and runs of whitespace are not encoded --, a vocab.json /
- * merges.txt loader, special-token strings inside the text, folding inside the call, a flow form, decoding ids back
- * to text.  (Decoding is a call family of its own: latok_detok_* below; so are Unigram models: latok_unigram_*.) */
+ * GPT-2's regex pre-tokenizer is a property of the object: latok_bpe_create_pretok with LATOK_PRETOK_GPT2 (below) makes one whose two
+ * calls cut the text into GPT-2's pre-tokens instead of latok's tokens -- whitespace runs are encoded, nothing is dropped -- and then
+ * merge each as above; an object of latok_bpe_create keeps latok's tokens.  A vocab.json / merges.txt pair converts to the word list
+ * on the host (latok_amd.batch.BPE.from_gpt2_files does it).  Out of scope: special-token strings inside the text, folding inside the
+ * call, a flow form, decoding ids back to text.  (Decoding is a call family of its own: latok_detok_* below; so are Unigram models:
+ * latok_unigram_*.) */
 typedef struct latok_bpe latok_bpe;
 int latok_bpe_create(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
                      const int32_t* word_ids /* may be NULL */, int max_bytes, int lead_space, uint32_t seed, latok_bpe** bpe_out);
@@ -595,6 +598,55 @@ int latok_bpe_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_o
                                       int32_t eos_id, int32_t pad_id, int32_t* input_ids_out /* [n_str*max_length] */,
                                       int32_t* lengths_out /* [n_str] */, int64_t* n_pieces_out /* may be NULL */, int flags,
                                       void* stream);
+
+/* GPT-2's pre-tokenizer in byte space: the pre-tokens of GPT-2, RoBERTa, BART and the r50k / p50k encodings, and byte-level BPE behind
+ * them -- the ids GPT2TokenizerFast gives.  The pattern is GPT-2's,
+ *     's|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+
+ * applied to each string on its own, leftmost match first, alternatives in order.  Every byte of a string lies in exactly one
+ * pre-token; nothing is dropped.  Pre-tokens are byte ranges [a, e) relative to their string.  No regex engine runs: the pattern is
+ * restated as a LOCAL rule, which is the definition here (latok_amd/csrc/pretok.h implements it; Unicode 13.0.0):
+ * CHARACTERS.  A character starts at a string's first byte and at every later byte b with (b & 0xC0) != 0x80.
+ * CLASSES.  Every byte of a character carries that character's class.  If the character's bytes are exactly one well-formed UTF-8
+ *   sequence, the class is that of its code point: S = Unicode White_Space (U+0009-000D, 0020, 0085, 00A0, 1680, 2000-200A, 2028,
+ *   2029, 202F, 205F, 3000: 25 code points; U+001C-001F are not in it), L = general category L*, N = general category N*, O =
+ *   everything else, unassigned code points included.  Any other character is O: a stray continuation byte at a string's start, a
+ *   truncated or overlong sequence, a sequence followed by further continuation bytes, a surrogate, a value above U+10FFFF, F5 .. FF.
+ * STARTS.  With prev / next the neighbouring characters of the same string, a pre-token starts at character i by these rules:
+ *   1. Contractions.  An apostrophe (the one-byte character 0x27) at i is a SCAN START if i is the string's first character, or prev
+ *      is L or N, or prev is S and is not the byte 0x20.  A scan-start apostrophe opens a CONTRACTION of k = 2 or 3 bytes if it is
+ *      followed by one of s, t, re, ve, m, ll, d -- lower-case ASCII, whole characters (byte i + k, if the string has it, starts a
+ *      character), inside the string.  A contraction has no start at its bytes i + 1 .. i + k - 1 and a FORCED start at i + k if
+ *      that byte lies inside the string.
+ *   2. An S character starts a pre-token if it is the string's first character, or prev is not S, or next exists and is not S (the
+ *      last character of a whitespace run in front of text: the lead space of what follows, or a pre-token of its own), or it is forced.
+ *   3. A character that is not S and not inside a contraction starts a pre-token if it is the string's first character, or it is
+ *      forced, or prev is S and is not the byte 0x20, or prev is not S and its class differs from this character's.  After a 0x20
+ *      there is no start: the space is this pre-token's first byte.
+ *   4. A string's end ends its last pre-token.  Nothing looks across a string boundary.
+ * A start bit depends on the bytes from 7 behind it to 6 ahead of it and on nothing else; latok_set_rules has no influence.
+ * latok_pretokens_utf8_bytes_batch has the contract of latok_token_spans_utf8_bytes_batch, word for word (host pointers or
+ * LATOK_DEVICE_PTRS with a 16-byte aligned buffer, total_bytes = -1, LATOK_OUT_INT32, the capacity protocol, n_str = 0 and total_bytes
+ * = 0), with one argument more: pretok = LATOK_PRETOK_LATOK returns exactly what that call returns, LATOK_PRETOK_GPT2 the pre-tokens
+ * above (counts_out[s] = pre-tokens of string s, spans_out = their [a, e) records; every batch size takes the same kernels).  Any
+ * other pretok, and any flag bit but those two, is refused before any device work.
+ * latok_bpe_create_pretok is latok_bpe_create with the pre-tokenizer as a property of the model, as in a tokenizer.json; it refuses
+ * an unknown pretok, and LATOK_PRETOK_GPT2 with lead_space = 1 (the space is already in the pre-token), before any device work.
+ * latok_bpe_create means LATOK_PRETOK_LATOK.  latok_bpe_pretokenizer reports it.  The two BPE calls dispatch on the object.
+ * Known difference from tiktoken: a pre-token of more than max_bytes (at most 4096) bytes is ONE unk piece, e.g. a run of 5 000
+ * spaces, which tiktoken would encode.
+ * Out of scope: the cl100k_base / o200k_base patterns (case-insensitive contractions, digits in groups of three, \r\n handling: a
+ * position-in-run count and a third constant; the pretok argument is there so that they can follow), add_prefix_space, special-token
+ * strings recognised inside the text, a flow form, folding inside the call, DevicePool forms, this pre-tokenizer on the hash, ids,
+ * count, term-count, WordPiece or Unigram calls (the planes make it possible; it is not wired), a Detokenizer loader for GPT-2 files. */
+#define LATOK_PRETOK_LATOK 0
+#define LATOK_PRETOK_GPT2 1
+int latok_pretokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, int pretok,
+                                     int64_t* counts_out, int64_t* spans_out, int64_t spans_cap, int64_t* n_tokens_out, int flags,
+                                     void* stream);
+int latok_bpe_create_pretok(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
+                            const int32_t* word_ids /* may be NULL */, int max_bytes, int lead_space, int pretok, uint32_t seed,
+                            latok_bpe** bpe_out);
+int latok_bpe_pretokenizer(const latok_bpe* bpe, int* pretok);
 
 /* Unigram in byte space: the Viterbi piece ids of a SentencePiece Unigram language model (T5, mT5, ALBERT, XLNet, XLM-R, mBART,
  * Pegasus), for every token of a batch.

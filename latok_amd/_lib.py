@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("LATOK_HIP_LIB", os.path.join(_HERE, "liblatok_hip.so"
 OK, ERR_INVALID, ERR_HIP, ERR_NOT_INIT, ERR_NOMEM = 0, -1, -2, -3, -4
 DEVICE_PTRS = 1
 OUT_INT32 = 2
+PRETOK_LATOK, PRETOK_GPT2 = 0, 1     # LATOK_PRETOK_* (latok_pretokens_utf8_bytes_batch, latok_bpe_create_pretok)
 FOLD_LOWER, FOLD_STRIP_MARKS, FOLD_CLEAN, FOLD_CJK_SPACE = 1, 2, 4, 8     # LATOK_FOLD_* (latok_fold_utf8_bytes_batch)
 TFIDF_SMOOTH_IDF, TFIDF_SUBLINEAR_TF, TFIDF_NORM_L1, TFIDF_NORM_L2 = 1, 2, 4, 8   # LATOK_TFIDF_* (latok_tfidf_csr)
 FEATURE_COUNT = 25
@@ -92,6 +93,9 @@ SIGNATURES = {
     "latok_bpe_ids_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), ci, vp]),
     "latok_bpe_padded_utf8_bytes_batch": (ci, [vp, vp, i64, i64, vp, C.c_int32, i64, ci, C.c_int32, C.c_int32, C.c_int32, vp, vp,
                                                C.POINTER(i64), ci, vp]),
+    "latok_pretokens_utf8_bytes_batch": (ci, [vp, vp, i64, i64, ci, vp, vp, i64, C.POINTER(i64), ci, vp]),
+    "latok_bpe_create_pretok": (ci, [vp, vp, i64, vp, ci, ci, ci, C.c_uint32, C.POINTER(vp)]),
+    "latok_bpe_pretokenizer": (ci, [vp, C.POINTER(ci)]),
     "latok_unigram_create": (ci, [vp, vp, i64, vp, vp, vp, ci, C.c_float, ci, ci, C.c_uint32, C.POINTER(vp)]),
     "latok_unigram_destroy": (ci, [vp]),
     "latok_unigram_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, C.POINTER(ci),

@@ -406,6 +406,55 @@ def tokenize_utf8_batch(blobs):
     return out
 
 
+# pre-tokens: the byte ranges a model's pre-tokenizer cuts a string into (GPT-2's pattern on the device; "latok": the tokens above)
+_PRETOKENIZERS = {"latok": _lib.PRETOK_LATOK, "gpt2": _lib.PRETOK_GPT2}
+
+
+def _pretok_code(pretokenizer) -> int:
+    """the LATOK_PRETOK_* value of a name; anything else is a ValueError (raised before any device is asked for)"""
+    if not isinstance(pretokenizer, str) or pretokenizer not in _PRETOKENIZERS:
+        raise ValueError("pretokenizer must be one of %s" % ", ".join(repr(k) for k in _PRETOKENIZERS))
+    return _PRETOKENIZERS[pretokenizer]
+
+
+def pretokens_utf8_csr(utf8, byte_off, pretokenizer="gpt2", dtype=np.int64):
+    """(counts, spans[n, 2]): the [start, end) BYTE ranges of every string's pre-tokens (``latok_pretokens_utf8_bytes_batch``).
+    ``"gpt2"``: GPT-2's pattern -- every byte of a string lies in exactly one pre-token, whitespace included; ``"latok"``: exactly
+    what token_spans_utf8_bytes_csr returns."""
+    utf8, byte_off = _csr_u8(utf8, byte_off)
+    code = _pretok_code(pretokenizer)
+    _out_dtype(dtype)
+    n_str = byte_off.size - 1
+    total = int(byte_off[-1]) if n_str > 0 else 0
+    lib = _lib.ensure_init()
+
+    def fn(u8, off, n, t, *rest):
+        return lib.latok_pretokens_utf8_bytes_batch(u8, off, n, t, code, *rest)
+
+    return _compact(fn, [_ptr(utf8), _ptr(byte_off)], n_str, total, 2, dtype)
+
+
+def pretokenize_utf8_batch(blobs, pretokenizer="gpt2"):
+    """list[bytes] (UTF-8) -> list[list[bytes]]: every string's pre-tokens as slices of the input; with ``"gpt2"`` they join back
+    to the string byte for byte."""
+    _pretok_code(pretokenizer)
+    if len(blobs) == 0:
+        return []
+    utf8, byte_off = pack_utf8(blobs)
+    counts, spans = pretokens_utf8_csr(utf8, byte_off, pretokenizer, _record_dtype(byte_off))
+    out, k = [], 0
+    for blob, n in zip(blobs, counts.tolist()):
+        out.append([blob[a:b] for a, b in spans[k:k + n].tolist()])
+        k += n
+    return out
+
+
+def pretokenize_batch(texts, pretokenizer="gpt2"):
+    """list[str] -> list[list[str]]: pretokenize_utf8_batch of the strings' UTF-8 ("surrogatepass"), decoded again"""
+    rows = pretokenize_utf8_batch([t.encode("utf-8", "surrogatepass") for t in texts], pretokenizer)
+    return [[p.decode("utf-8", "surrogatepass") for p in row] for row in rows]
+
+
 # joined token text: the tokens themselves, each string's joined by one separator (what a pre-tokenized corpus holds)
 def _sep_byte(sep) -> int:
     """the separator as one byte value; anything else is a ValueError (raised before any device is asked for)"""
@@ -1278,26 +1327,34 @@ class BPE(_DeviceObject):
     ``str``, encoded as UTF-8 with surrogatepass) in RANK order -- a word's rank is its position, of a duplicate the first wins --,
     ``ids`` an optional int32 per word (default: its rank), ``max_bytes`` in 1 .. 4096 (a longer token is one unknown piece),
     ``lead_space``: a token that follows a 0x20 byte inside its string takes that byte in front (the ``" word"`` convention of
-    GPT-style vocabularies), ``seed`` the 32-bit seed of the table's hash.  This is ``tiktoken``'s model.  Out of scope: GPT-2's regex
-    pre-tokenizer (tokens are latok's; runs of whitespace are not encoded), a ``vocab.json`` / ``merges.txt`` loader, special-token
-    strings inside the text, a ``fold=`` keyword, a flow form, ``DevicePool`` forms, decoding (a class of its own,
-    ``Detokenizer``).  Immutable; ``len()`` is the number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
+    GPT-style vocabularies), ``seed`` the 32-bit seed of the table's hash.  This is ``tiktoken``'s model.  ``pretokenizer`` says what
+    cuts the text into the tokens that are merged: ``"latok"`` (the library's tokens; runs of whitespace are not encoded) or ``"gpt2"``
+    (GPT-2's regex pre-tokenizer on the device: the ids ``GPT2TokenizerFast`` gives; it carries the space itself, so ``lead_space``
+    must be off).  ``from_gpt2_files`` loads a ``vocab.json`` / ``merges.txt`` pair.  Out of scope: special-token strings inside the
+    text, a ``fold=`` keyword, a flow form, ``DevicePool`` forms, decoding (a class of its own, ``Detokenizer``).  Immutable; ``len()``
+    is the number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
 
     _destroy, _closed = "latok_bpe_destroy", "bpe must be an open latok_amd.batch.BPE"
 
-    def __init__(self, words, ids=None, max_bytes=4096, lead_space=False, seed=0):
+    def __init__(self, words, ids=None, max_bytes=4096, lead_space=False, seed=0, pretokenizer="latok"):
         seed = _seed32(seed)
         if not isinstance(max_bytes, (int, np.integer)) or isinstance(max_bytes, bool) or not 1 <= int(max_bytes) <= 4096:
             raise ValueError("max_bytes must be an int in 1 .. 4096")
         if not isinstance(lead_space, (bool, np.bool_)) and lead_space not in (0, 1):
             raise ValueError("lead_space must be a bool")
+        code = _pretok_code(pretokenizer)
+        if code == _lib.PRETOK_GPT2 and lead_space:
+            raise ValueError("lead_space must be off with pretokenizer='gpt2': the space is already in the pre-token")
         data, off, ids = _pack_words(words, ids)
         lib = _lib.ensure_init()
         h = C.c_void_p()
-        _lib.check(lib.latok_bpe_create(_ptr(data) if data.size else None, _ptr(off), off.size - 1, _ptr(ids) if ids is not None else None,
-                                        int(max_bytes), 1 if lead_space else 0, seed, C.byref(h)))
+        lead = [_ptr(data) if data.size else None, _ptr(off), off.size - 1, _ptr(ids) if ids is not None else None, int(max_bytes), 1 if lead_space else 0]
+        if code == _lib.PRETOK_LATOK:
+            _lib.check(lib.latok_bpe_create(*lead, seed, C.byref(h)))
+        else:
+            _lib.check(lib.latok_bpe_create_pretok(*lead, code, seed, C.byref(h)))
         self._lib, self.handle, self.seed, self._n = lib, h, seed, off.size - 1
-        self.max_bytes, self.lead_space = int(max_bytes), bool(lead_space)
+        self.max_bytes, self.lead_space, self.pretokenizer, self.specials = int(max_bytes), bool(lead_space), pretokenizer, {}
 
     @classmethod
     def from_tiktoken_file(cls, path, **kw):
@@ -1322,6 +1379,68 @@ class BPE(_DeviceObject):
                 raise ValueError("the ranks of a .tiktoken file must be 0 .. n - 1, each once: position %d holds rank %d" % (i, rank))
         return cls([w for _, w in pairs], **kw)
 
+    @staticmethod
+    def gpt2_byte_decoder():
+        """dict: the printable character GPT-2 writes for a byte in vocab.json and merges.txt -> that byte (its ``bytes_to_unicode``, inverted)"""
+        keep = list(range(33, 127)) + list(range(161, 173)) + list(range(174, 256))
+        table, n = {chr(b): b for b in keep}, 0
+        for b in range(256):
+            if b not in keep:
+                table[chr(256 + n)] = b
+                n += 1
+        return table
+
+    @staticmethod
+    def gpt2_word_list(vocab_json, merges_txt):
+        """(words, ids, specials) of a GPT-2 ``vocab.json`` / ``merges.txt`` pair; needs no device.  ``words``: the single bytes that
+        vocab.json holds, in byte order, then the result of every merge in the file's order, which is the rank order; ``ids``: theirs in
+        vocab.json.  An entry of vocab.json that is neither is a special token: it is NOT made a word (the whole-token shortcut would
+        match its literal text) and goes to ``specials`` (name -> id).  A merge result that vocab.json lacks is a ValueError."""
+        import json
+        with open(vocab_json, encoding="utf-8") as f:
+            vocab = json.load(f)
+        if not isinstance(vocab, dict) or not all(isinstance(k, str) and isinstance(v, int) and not isinstance(v, bool) for k, v in vocab.items()):
+            raise ValueError("vocab.json must be one object of token -> id")
+        dec = BPE.gpt2_byte_decoder()
+
+        def raw(token, where):
+            try:
+                return bytes(dec[ch] for ch in token)
+            except KeyError:
+                raise ValueError("%s: %r is not written in GPT-2's byte alphabet" % (where, token[:40])) from None
+
+        enc = {b: ch for ch, b in dec.items()}
+        words, ids, used = [], [], set()
+        for b in range(256):
+            if enc[b] in vocab:
+                words.append(bytes([b]))
+                ids.append(vocab[enc[b]])
+                used.add(enc[b])
+        with open(merges_txt, encoding="utf-8") as f:
+            for no, line in enumerate(f.read().split("\n"), 1):
+                if not line.strip() or (no == 1 and line.startswith("#version")):
+                    continue
+                pair = line.split(" ")
+                if len(pair) != 2 or not pair[0] or not pair[1]:
+                    raise ValueError("merges.txt line %d is not `left right`: %r" % (no, line[:60]))
+                token = pair[0] + pair[1]
+                if token not in vocab:
+                    raise ValueError("merges.txt line %d: the merge result %r is not in vocab.json" % (no, token[:40]))
+                words.append(raw(token, "merges.txt line %d" % no))
+                ids.append(vocab[token])
+                used.add(token)
+        specials = {k: v for k, v in vocab.items() if k not in used}
+        return words, ids, specials
+
+    @classmethod
+    def from_gpt2_files(cls, vocab_json, merges_txt, pretokenizer="gpt2", **kw):
+        """GPT-2's own files (also RoBERTa's and BART's): ``gpt2_word_list`` of the pair, cut by ``pretokenizer``.  The special tokens of
+        vocab.json are in the ``specials`` attribute (name -> id); they are not recognised inside text."""
+        words, ids, specials = cls.gpt2_word_list(vocab_json, merges_txt)
+        self = cls(words, ids=ids, pretokenizer=pretokenizer, **kw)
+        self.specials = specials
+        return self
+
     def info(self):
         """dict of what ``latok_bpe_info`` reports"""
         v = [C.c_int64(0) for _ in range(3)]
@@ -1330,13 +1449,20 @@ class BPE(_DeviceObject):
         return dict(n_words=v[0].value, n_slots=v[1].value, max_len=v[2].value, max_bytes=mb.value, lead_space=ls.value, seed=seed.value,
                     device=dev.value)
 
+    def pretokenizer_of_object(self):
+        """the name of what ``latok_bpe_pretokenizer`` reports for the device object"""
+        pt = C.c_int(-1)
+        _lib.check(self._lib.latok_bpe_pretokenizer(self._open(), C.byref(pt)))
+        return {v: k for k, v in _PRETOKENIZERS.items()}[pt.value]
+
     def __len__(self):
         return self._n
 
 
 def bpe_ids_utf8_csr(utf8, byte_off, bpe, unk_id=-1, dtype=np.int64, spans=True):
     """(indptr[n + 1], ids int32[n_pieces], spans[n_pieces, 2] or None): the BPE ids of every string -- each token (the byte slices
-    token_spans_utf8_bytes_csr reports, with the space in front under ``lead_space``) is one piece if it is a word of ``bpe``, else
+    token_spans_utf8_bytes_csr reports, with the space in front under ``lead_space``; GPT-2's pre-tokens, the slices of
+    pretokens_utf8_csr, when ``bpe`` was made with ``pretokenizer="gpt2"``) is one piece if it is a word of ``bpe``, else
     its bytes merged pair by pair, lowest rank first and leftmost among equals; a byte that is no word is an ``unk_id`` piece, a token of
     more than ``max_bytes`` bytes ONE.  spans[r] = piece r's byte range inside its string.  indptr and spans in ``dtype``.  Cut on the
     device (``latok_bpe_ids_utf8_bytes_batch``): the size query, then the fill."""

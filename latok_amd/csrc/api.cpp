@@ -39,6 +39,7 @@
 #include "wordpiece.h"
 #include "bpe.h"
 #include "unigram.h"
+#include "pretok.h"
 #include "fold_map.h"
 #include "fold_tables.inc"
 #include "tfidf_weight.h"
@@ -47,6 +48,7 @@ static_assert(LATOK_TBL_SHIFT == latok::kTblShift, "table shift");
 static_assert(LATOK_TBL_STAGE1_LEN == latok::kStage1Len, "stage-1 length");
 static_assert(LATOK_TBL_NBLOCKS * (1 << LATOK_TBL_SHIFT) == latok::kStage2Len, "stage-2 length");
 static_assert(LATOK_TILE_CHARS == latok::kTile, "tile size");
+static_assert(LATOK_PRETOK_LATOK == kPretokLatok && LATOK_PRETOK_GPT2 == kPretokGpt2, "pre-tokenizer constants");
 
 namespace {
 
@@ -1757,16 +1759,25 @@ static int enqueue_join_tokens(Ctx& g, Workspace& w, const JoinTokens& a) {
 //   k_word_counts + k_scan_chained                kept mask, token ranks; THE token total -> scalar word 0, r_tokens
 // d_err = the call's error word; the scan's own flag goes to its high half.  `w` was sized by ws_needs with a shape that has
 // .spans = true.  What comes back are the workspace's planes, for the launches that follow.
-static int enqueue_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* r_tokens, int* d_err, hipStream_t st, latok::TokenPlanes* out) {
+// pretok = LATOK_PRETOK_GPT2: the first line is ONE launch instead, k_pretok_planes (pretok_kernels.hip): a bit at every byte where a
+// pre-token of GPT-2's pattern starts, an all-zero SPACE plane (every pre-token is kept, nothing is stripped) and the per-tile string
+// index, in the same buffers.  The context's rule tables play no part in it.
+static int enqueue_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* r_tokens, int* d_err, hipStream_t st, latok::TokenPlanes* out,
+                               int pretok = kPretokLatok) {
     int rc;
     *out = token_planes(w, b.row, b.n_str, b.total);
     latok::ChainState chain;
-    Pipe p;
-    p.b = b;
-    p.bits = (uint64_t*)w.bits.p;
-    p.space = (uint64_t*)w.space.p;
-    p.st = st;
-    if ((rc = run_pipeline(g, w, p))) return rc;
+    if (pretok == kPretokGpt2) {
+        HIP_TRY(latok::launch_pretok_planes((const uint8_t*)b.in.p, b.total, b.row, b.n_str, (uint64_t*)w.bits.p, (uint64_t*)w.space.p,
+                                            (int64_t*)w.tile_first.p, st));
+    } else {
+        Pipe p;
+        p.b = b;
+        p.bits = (uint64_t*)w.bits.p;
+        p.space = (uint64_t*)w.space.p;
+        p.st = st;
+        if ((rc = run_pipeline(g, w, p))) return rc;
+    }
     if ((rc = next_scan_epoch(w, st, &chain))) return rc;
     HIP_TRY(latok::launch_word_counts_scan(true, *out, chain, r_tokens, d_err + 1, st));
     return LATOK_OK;
@@ -1775,9 +1786,9 @@ static int enqueue_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* r_
 // pinned words (p_tot / h_tot: word 0 tokens, word 1 the error word), wait 1, then the refusal of 2^31 tokens or more in the caller's
 // words (`too_many`, one %lld).  The caller sizes its buffers by *n_tok.
 static int sized_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* p_tot, const volatile int64_t* h_tot, hipStream_t st,
-                             const char* too_many, latok::TokenPlanes* t, int64_t* n_tok) {
+                             const char* too_many, latok::TokenPlanes* t, int64_t* n_tok, int pretok = kPretokLatok) {
     int rc;
-    if ((rc = enqueue_token_front(g, w, b, p_tot, (int*)(p_tot + 1), st, t))) return rc;
+    if ((rc = enqueue_token_front(g, w, b, p_tot, (int*)(p_tot + 1), st, t, pretok))) return rc;
     HIP_TRY(hipStreamSynchronize(st));   // wait 1: the token total decides whether the call goes on and what its buffers take
     if ((rc = finish_totals(w, h_tot, 0, n_tok))) return rc;
     if (*n_tok >= (1ll << 31)) return fail(LATOK_ERR_INVALID, too_many, (long long)*n_tok);
@@ -2452,6 +2463,63 @@ int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
                                         int flags, void* stream) {
     return token_words_common(utf8, byte_off, n_str, total_bytes, false, nullptr, seed, -1, counts_out, spans_out, hashes_out, cap, n_tokens_out, flags,
                               stream);
+}
+
+/* Pre-tokens in byte space (latok_pretokens_utf8_bytes_batch): the span call of a pre-tokenizer.  LATOK_PRETOK_LATOK is
+ * latok_token_spans_utf8_bytes_batch itself.  LATOK_PRETOK_GPT2, one stream, every batch size the same kernels:
+ *   enqueue_token_front (GPT2)     k_pretok_planes: start plane, zero SPACE plane, tile index; k_word_counts + k_scan_chained: ranks, THE total
+ *   k_counts_scatter (kind 1)      per-string counts and the [start, end) records (gate: total <= capacity)
+ * One wait; host pointers: the copies and a second wait.  Route 26 of latok_debug_last_route. */
+static int pretokens_gpt2(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, void* counts_out, void* spans_out,
+                          int64_t spans_cap, int64_t* n_tokens_out, int flags, void* stream) {
+    LATOK_ENTER();
+    int rc = need_init(g);
+    if (rc) return rc;
+    if (!n_tokens_out) return fail(LATOK_ERR_INVALID, "the total-count output pointer is NULL");
+    *n_tokens_out = 0;
+    if (spans_cap < 0) return fail(LATOK_ERR_INVALID, "negative capacity");
+    const bool o32 = (flags & LATOK_OUT_INT32) != 0;
+    if (o32 && !(flags & LATOK_DEVICE_PTRS) && byte_off && n_str > 0) {   // before anything is staged (device-resident offsets: the kernel checks)
+        for (int64_t s = 0; s < n_str; ++s)
+            if (byte_off[s + 1] - byte_off[s] > 0x7FFFFFFFll)
+                return fail(LATOK_ERR_INVALID, "string %lld is too long for LATOK_OUT_INT32; use the 64-bit form", (long long)s);
+    }
+    BytesCall c;
+    if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
+    const bool dev = c.dev;
+    const size_t elt = c.elt;
+    if (n_str == 0) return LATOK_OK;
+    if (!counts_out) return fail(LATOK_ERR_INVALID, "counts_out is NULL");
+    if (c.empty) return zero_counts(dev, counts_out, (size_t)n_str * elt, c.st, true);   // only empty strings
+    if (dev && (((uintptr_t)spans_out & (2 * elt - 1)) != 0 || ((uintptr_t)counts_out & (elt - 1)) != 0)) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
+    if ((rc = c.stage(g, 26, WsShape{.spans = true}, kClearPair))) return rc;
+    void* d_counts = counts_out;
+    void* d_spans = spans_out;
+    int64_t cap = spans_out ? spans_cap : 0;
+    if (!dev) {   // device staging sized for the worst case of one pre-token per byte
+        if ((rc = g.counts.ensure((size_t)n_str * 8)) || (rc = g.h_out.ensure((size_t)c.total * 2 * elt))) return rc;
+        d_counts = g.counts.p;
+        d_spans = g.h_out.p;
+        cap = c.total;
+    }
+    int* d_err = (int*)(c.p_tot + 1);
+    latok::TokenPlanes t;
+    if ((rc = enqueue_token_front(g, g.ws, c.d, c.p_tot, d_err, c.st, &t, kPretokGpt2))) return rc;
+    HIP_TRY(latok::launch_counts_scatter(1, o32, t, d_spans, cap, d_counts, d_err, c.st));
+    HIP_TRY(hipStreamSynchronize(c.st));
+    int64_t n = *n_tokens_out = c.h_tot[0];   // (the total is reported whatever the flags say)
+    if ((rc = finish_totals(g.ws, c.h_tot, 0xFFFFFFFFll, &n))) return rc;
+    return deliver_records(false, dev ? nullptr : g.counts.p, g.h_out.p, nullptr, counts_out, spans_out, nullptr, n_str, elt, 2 * elt, n, spans_cap, c.st);
+}
+int latok_pretokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, int pretok, int64_t* counts_out,
+                                     int64_t* spans_out, int64_t spans_cap, int64_t* n_tokens_out, int flags, void* stream) {
+    // what needs no device is refused first
+    if (pretok != LATOK_PRETOK_LATOK && pretok != LATOK_PRETOK_GPT2)
+        return fail(LATOK_ERR_INVALID, "unknown pretok %d (LATOK_PRETOK_LATOK or LATOK_PRETOK_GPT2)", pretok);
+    if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
+    if (pretok == LATOK_PRETOK_LATOK)
+        return latok_token_spans_utf8_bytes_batch(utf8, byte_off, n_str, total_bytes, counts_out, spans_out, spans_cap, n_tokens_out, flags, stream);
+    return pretokens_gpt2(utf8, byte_off, n_str, total_bytes, counts_out, spans_out, spans_cap, n_tokens_out, flags, stream);
 }
 
 /* vocabularies: built on the host (vocab_table.h), uploaded once, read only afterwards */
@@ -3276,18 +3344,21 @@ struct Bpe {                       // latok_bpe: immutable once created
     int64_t n_words = 0;
     uint32_t max_len = 0;
     int max_bytes = 0, lead_space = 0;
+    int pretok = kPretokLatok;     // what cuts the text into the tokens that are merged (LATOK_PRETOK_*)
     uint32_t seed = 0;
     DevTable table;
     DevMem rank_id;
 };
-int latok_bpe_create(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, int max_bytes, int lead_space,
-                     uint32_t seed, latok_bpe** bpe_out) {
+int latok_bpe_create_pretok(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, int max_bytes, int lead_space,
+                            int pretok, uint32_t seed, latok_bpe** bpe_out) {
     LATOK_ENTER();
     // what needs no device is refused first
     if (!bpe_out) return fail(LATOK_ERR_INVALID, "bpe_out is NULL");
     *bpe_out = nullptr;
     if (max_bytes < 1 || max_bytes > kBpeMaxBytes) return fail(LATOK_ERR_INVALID, "max_bytes must be in 1 .. %d", kBpeMaxBytes);
     if (lead_space != 0 && lead_space != 1) return fail(LATOK_ERR_INVALID, "lead_space must be 0 or 1");
+    if (pretok != kPretokLatok && pretok != kPretokGpt2) return fail(LATOK_ERR_INVALID, "unknown pretok %d (LATOK_PRETOK_LATOK or LATOK_PRETOK_GPT2)", pretok);
+    if (pretok == kPretokGpt2 && lead_space) return fail(LATOK_ERR_INVALID, "lead_space must be 0 with LATOK_PRETOK_GPT2: the space is already in the pre-token");
     int rc = check_word_list(words, word_off, n_words);
     if (rc || (rc = need_init(g))) return rc;
     BpeTables t;
@@ -3303,6 +3374,7 @@ int latok_bpe_create(const uint8_t* words, const int64_t* word_off, int64_t n_wo
     v->max_len = t.max_len;
     v->max_bytes = max_bytes;
     v->lead_space = lead_space;
+    v->pretok = pretok;
     v->seed = seed;
     if ((rc = v->table.upload(t.table, g.stream)) == LATOK_OK) {
         const size_t bytes = t.rank_id.size() * 4;
@@ -3318,6 +3390,19 @@ int latok_bpe_create(const uint8_t* words, const int64_t* word_off, int64_t n_wo
         return rc;
     }
     *bpe_out = reinterpret_cast<latok_bpe*>(v);
+    return LATOK_OK;
+}
+
+int latok_bpe_create(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, int max_bytes, int lead_space,
+                     uint32_t seed, latok_bpe** bpe_out) {
+    return latok_bpe_create_pretok(words, word_off, n_words, word_ids, max_bytes, lead_space, LATOK_PRETOK_LATOK, seed, bpe_out);
+}
+
+int latok_bpe_pretokenizer(const latok_bpe* bpe, int* pretok) {
+    const Bpe* v = reinterpret_cast<const Bpe*>(bpe);
+    if (!v) return fail(LATOK_ERR_INVALID, "bpe is NULL");
+    if (!pretok) return fail(LATOK_ERR_INVALID, "pretok is NULL");
+    *pretok = v->pretok;
     return LATOK_OK;
 }
 
@@ -3445,6 +3530,11 @@ struct PieceCut {
     const Bpe* bpe = nullptr;
     const Unigram* uni = nullptr;
     int route_ids = 11, route_padded = 12;
+    // the front of the call: a BPE object made with LATOK_PRETOK_GPT2 brings its own, and its two routes
+    int pretok() const { return bpe ? bpe->pretok : kPretokLatok; }
+    void route_by_front() {
+        if (pretok() == kPretokGpt2) { route_ids = 24; route_padded = 25; }
+    }
 };
 
 struct WordPieceCall {
@@ -3473,7 +3563,8 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
     const int64_t total = a.b.total, n_str = a.b.n_str;
     int* d_err = (int*)(a.p_tot + 1);
     latok::TokenPlanes t;
-    if ((rc = sized_token_front(g, w, a.b, a.p_tot, a.h_tot, st, "the batch has %lld tokens: a call takes fewer than 2^31 pieces", &t, &a.n_tokens)))
+    if ((rc = sized_token_front(g, w, a.b, a.p_tot, a.h_tot, st, "the batch has %lld tokens: a call takes fewer than 2^31 pieces", &t, &a.n_tokens,
+                                a.cut.pretok())))
         return rc;
     int64_t* d_total = (int64_t*)w.scalar.p;
     const int64_t n_tok = a.n_tokens;
@@ -3569,6 +3660,7 @@ static int piece_ids_call(const uint8_t* utf8, const int64_t* byte_off, int64_t 
     const Obj* v = nullptr;
     if ((rc = check_object(g, handle, null_msg, &v))) return rc;
     cut.*slot = v;
+    cut.route_by_front();
     BytesCall c;   // (elt: the width of indptr and of one field of a span; an id is 4 bytes in every mode)
     if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
     const bool dev = c.dev;
@@ -3643,6 +3735,7 @@ static int piece_padded_call(const uint8_t* utf8, const int64_t* byte_off, int64
     const Obj* v = nullptr;
     if ((rc = check_object(g, handle, null_msg, &v))) return rc;
     cut.*slot = v;
+    cut.route_by_front();
     BytesCall c;
     if ((rc = c.open(g, utf8, byte_off, n_str, total_bytes, flags, stream))) return rc;
     const bool dev = c.dev;
@@ -4701,6 +4794,17 @@ extern "C" int latok_debug_bpe_limits(int64_t* out, int n) {
     return k;
 }
 
+/* test hook (not part of the ABI; needs no device): the constants of the GPT-2 pre-tokenizer's front (k_pretok_planes): out[0] = bytes per
+ * word (one lane), out[1] = bytes per tile (one wave), out[2] = threads per workgroup, out[3] = kPtHalo (the bytes a word's window holds
+ * on either side of the word).  Returns the number of values written. */
+extern "C" int latok_debug_pretok_limits(int64_t* out, int n) {
+    const int64_t v[4] = {kPtWord, latok::kTile, latok::kPretokWaves * 64, kPtHalo};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 4 ? n : 4;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
 /* test hook (not part of the ABI; needs no device): the constants of the Unigram calls: out[0] = kUniBlock (tokens per workgroup of
  * k_uni_count / k_uni_emit), out[1] = entries per workgroup of the chained scan over the piece counts, out[2] = kUniLaneBytes (the
  * longest token of the lane form), out[3] = kUniMaxBytes (the ceiling of max_bytes).  Returns the number of values written. */
@@ -4868,7 +4972,9 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
  * 16 / 17: character n-gram counts inside tokens, vocabulary form / hashed form (likewise);
  * 18 / 19: byte-level BPE ids of UTF-8 in byte space, CSR form / padded form (likewise);
  * 20 / 21: decoding, ids back to bytes, CSR form / padded form (likewise);
- * 22 / 23: Unigram ids of UTF-8 in byte space, CSR form / padded form (likewise) */
+ * 22 / 23: Unigram ids of UTF-8 in byte space, CSR form / padded form (likewise);
+ * 24 / 25: byte-level BPE ids behind GPT-2's pre-tokenizer (an object of latok_bpe_create_pretok), CSR form / padded form (likewise);
+ * 26: pre-token spans of GPT-2's pre-tokenizer (latok_pretokens_utf8_bytes_batch; LATOK_PRETOK_LATOK reports the span call's routes) */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;

@@ -419,6 +419,13 @@ struct BpeTable {
 hipError_t launch_bpe_count(const TokenText& t, const BpeTable& bt, int64_t* cnt, uint64_t* masks, hipStream_t st);
 hipError_t launch_bpe_emit(bool out32, const TokenText& t, const BpeTable& bt, int32_t unk_id, const int64_t* rank, const uint64_t* masks,
                            const int64_t* n_pieces_dev, int64_t cap, int32_t* ids, void* spans, hipStream_t st);
+// GPT-2's pre-tokenizer as a token front (pretok_kernels.hip, pretok.h): one launch, one wave per tile of kTile bytes, leaves the planes a
+// token call reads -- bits = a bit at every byte where a pre-token starts, space = all zero (every pre-token is kept, nothing is
+// stripped), both n_words = ceil(total / 64) words with zero bits behind the batch's end -- and tile_first[tile], as k_tile_index does.
+// u8 is 16-byte aligned; nothing outside [0, total) is read.  latok_debug_pretok_limits reports the constants.
+constexpr int kPretokWaves = 4;   // tiles per workgroup of k_pretok_planes
+hipError_t launch_pretok_planes(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, uint64_t* bits, uint64_t* space,
+                                int64_t* tile_first, hipStream_t st);
 // Unigram (Viterbi) ids (unigram_kernels.hip, unigram.h).  launch_uni_count leaves the pieces of every token in cnt[0 .. n_tok) and 0
 // in cnt[n_tok], and three words per token of at most 64 bytes in marks[] (three arrays of n_tok words: the piece starts, which of them
 // are unknown, whether the marker's piece is); the caller scans the n_tok + 1 entries into rank[]; launch_uni_emit stores ids (through

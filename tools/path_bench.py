@@ -75,6 +75,14 @@
   py_bpe         end to end in Python on host blobs (the first --py-strings strings): batch.bpe_ids_utf8_batch(blobs, bpe) against
                   batch.tokenize_utf8_batch(blobs) + the merge loop over a dict (lead_space = 0 there: the host route has no spans);
                   equal rows asserted first; one line each
+  bytes_pretok_gpt2   latok_pretokens_utf8_bytes_batch with LATOK_PRETOK_GPT2 and LATOK_OUT_INT32: the span records of GPT-2's pre-tokens
+                  (white-space pre-tokens are records too: items per call are reported beside the time); yardstick: bytes_spans32 of the same
+                  process run
+  bytes_bpe_gpt2  latok_bpe_ids_utf8_bytes_batch on an object of the same trained words as bytes_bpe32, made with pretokenizer="gpt2"
+                  (lead_space = 0: the space is in the pre-token); yardstick: bytes_bpe32 of the same process run
+  py_bpe_gpt2    end to end in Python on host blobs (the first min(--py-strings, 50000) strings): batch.bpe_ids_utf8_batch(blobs, bpe) of a
+                  pretokenizer="gpt2" object against the `regex` package with GPT-2's pattern + the merge loop over a dict on the host;
+                  equal rows asserted first; skipped with a note where `regex` is not importable
   bytes_uni32 / bytes_uni_padded   latok_unigram_ids_utf8_bytes_batch (int32 indptr and spans, capacity = the piece total of a size query) /
                   latok_unigram_padded_utf8_bytes_batch ([n, 64] block with BOS / EOS); the vocabulary is the characters of the 256 single
                   bytes plus the --uni-words most frequent tokens of the first --py-strings strings of the leg's own corpus, their
@@ -445,7 +453,7 @@ def main():
                                           "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "bytes_ngrams32", "bytes_ngrams_hashed", "py_terms",
                                           "bytes_chargrams32", "bytes_chargrams_hashed", "bytes_tfidf32", "bytes_tfidf_hashed", "bytes_df_update", "csr_tfidf", "csr_df", "py_tfidf",
                                           "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join", "bytes_wp32", "bytes_wp_padded", "py_wp",
-                                          "bytes_bpe32", "bytes_bpe_padded", "py_bpe", "bytes_uni32", "bytes_uni_padded", "py_uni", "ids_detok_bpe", "ids_detok_wp", "py_detok",
+                                          "bytes_bpe32", "bytes_bpe_padded", "py_bpe", "bytes_pretok_gpt2", "bytes_bpe_gpt2", "py_bpe_gpt2", "bytes_uni32", "bytes_uni_padded", "py_uni", "ids_detok_bpe", "ids_detok_wp", "py_detok",
                                           "bytes_fold", "bytes_fold_wp", "py_fold")]
     if join_leg:
         jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64, cap * 4, cap * 4)]
@@ -710,6 +718,30 @@ def main():
         def bpe_padded_blocking():
             b, _, b_block, b_len = corpus_bpe()[:4]
             return lib.latok_bpe_padded_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, WP_LEN, 1, 1, 2, 0, b_block, b_len, C.byref(nout), D, None)
+
+        # GPT-2's pre-tokenizer: the span call, and the BPE call on an object of bytes_bpe32's words that brings it as its front
+        pretok_gpt2_blocking = lambda: lib.latok_pretokens_utf8_bytes_batch(d_u8, d_boff, n, n8, _lib.PRETOK_GPT2, s_counts, s_items, cap, C.byref(nout), D32, None)  # noqa: E731
+        gpt2_box = []
+
+        def corpus_bpe_gpt2():
+            if not gpt2_box:
+                from latok_amd import batch
+                corpus_bpe()
+                b = batch.BPE(bpe_words, pretokenizer="gpt2", seed=SEED)
+                g_indptr = lib.latok_dev_alloc((n + 1) * 4 + 64)
+                need = C.c_int64(0)
+                rc = lib.latok_bpe_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, g_indptr, None, None, 0, C.byref(need), None, D32, None)
+                if rc != _lib.OK and need.value <= 0:
+                    _lib.check(rc)
+                pieces = [lib.latok_dev_alloc(need.value * 4 + 64), lib.latok_dev_alloc(need.value * 8 + 64)]
+                if not (g_indptr and all(pieces)):
+                    raise RuntimeError(_lib.last_error())
+                gpt2_box.extend([b, g_indptr] + pieces + [need.value])
+            return gpt2_box
+
+        def bpe_gpt2_blocking():
+            b, g_indptr, g_ids, g_spans, need = corpus_bpe_gpt2()
+            return lib.latok_bpe_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, g_indptr, g_ids, g_spans, need, C.byref(nout), None, D32, None)
 
         uni_box = []
         UNI_MARKER = "\u2581".encode()
@@ -1017,6 +1049,73 @@ def main():
                                               "repeat": r}), flush=True)
             elif name == "bytes_bpe32":   # (items = pieces)
                 run(name, bpe_blocking, lambda: n8 + csr + 4 * n + 12 * nout.value, note_b)
+            elif name == "bytes_pretok_gpt2":   # (items = pre-tokens, white space included)
+                run(name, pretok_gpt2_blocking, lambda: n8 + csr + 4 * n + 8 * nout.value,
+                    "UTF-8 bytes + 8 B/string read once by one launch; 2 x 1 bit/byte planes written; 4 B/string + 8 B/pre-token written "
+                    "(byte ranges, LATOK_OUT_INT32); every byte lies in a pre-token, so there are more records than bytes_spans32 has")
+            elif name == "bytes_bpe_gpt2":   # (items = pieces)
+                run(name, bpe_gpt2_blocking, lambda: n8 + csr + 4 * n + 12 * nout.value,
+                    note_b + "; the front is GPT-2's pre-tokenizer: one launch for the planes, white-space pre-tokens are merged too")
+            elif name == "py_bpe_gpt2":   # host blobs in, the CSR arrays out, both routes in this process
+                from latok_amd import batch
+                try:
+                    import regex
+                except ImportError:
+                    print(json.dumps({"path": name, "workload": args.workload, "note": "skipped: the `regex` package is not importable"}), flush=True)
+                    continue
+                blobs, blob, toks = bpe_sample_tokens(False)
+                blobs = blobs[:50000]
+                blob = b"".join(blobs)
+                pat = regex.compile(r"'s|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+")
+                words = bpe_train([b" " + t for t in toks[::2]] + toks[1::2], args.bpe_merges)
+                d = {}
+                for i, w in enumerate(words):
+                    d.setdefault(w, i)
+                memo = {}
+
+                def cut_gpt2(tok):
+                    got = memo.get(tok)
+                    if got is None:
+                        if tok in d:
+                            got = [d[tok]]
+                        else:
+                            parts = [tok[i:i + 1] for i in range(len(tok))]
+                            while True:
+                                best = None
+                                for i in range(len(parts) - 1):
+                                    r = d.get(parts[i] + parts[i + 1])
+                                    if r is not None and (best is None or r < best[0]):
+                                        best = (r, i)
+                                if best is None:
+                                    break
+                                parts[best[1]:best[1] + 2] = [parts[best[1]] + parts[best[1] + 1]]
+                            got = [d.get(p, -1) for p in parts]
+                        memo[tok] = got
+                    return got
+
+                def on_host_gpt2():
+                    memo.clear()   # (the memo is part of the loop: one merge walk per distinct pre-token of the call)
+                    indptr, ids = [0], []
+                    for b_ in blobs:
+                        for piece in pat.findall(b_.decode("utf-8", "surrogatepass")):
+                            ids.extend(cut_gpt2(piece.encode("utf-8", "surrogatepass")))
+                        indptr.append(len(ids))
+                    return np.array(indptr, np.int64), np.array(ids, np.int32)
+
+                with batch.BPE(words, pretokenizer="gpt2", seed=SEED) as b:
+                    routes = (("py_bpe_gpt2_ids_utf8_batch", lambda: batch.bpe_ids_utf8_batch(blobs, b)[:2]),
+                              ("py_regex_findall_then_bpe_loop", on_host_gpt2))
+                    assert all(np.array_equal(x, y) for x, y in zip(routes[0][1](), routes[1][1]()))
+                    for r in range(args.repeat):
+                        for rname, fn in routes:
+                            t = time.perf_counter()
+                            got = fn()
+                            dt = time.perf_counter() - t
+                            print(json.dumps({"path": rname, "workload": args.workload, "strings": len(blobs), "utf8_bytes": len(blob),
+                                              "words": len(words), "pieces": int(got[1].size), "unk": int((got[1] == -1).sum()), "ms_per_call": dt * 1e3,
+                                              "utf8_GBps": len(blob) / dt / 1e9,
+                                              "note": "end to end in Python: list[bytes] in, (indptr, ids) out, pack and host work included",
+                                              "repeat": r}), flush=True)
             elif name == "bytes_bpe_padded":   # (items = the untruncated piece total; the block is [n, WP_LEN] with BOS / EOS)
                 run(name, bpe_padded_blocking, lambda: n8 + csr + 4 * n + 4 * n * WP_LEN,
                     note_b.replace("4 B/string indptr + 4 B/piece ids + 8 B/piece spans", "4 B/string lengths + 4 B/cell of the [n, %d] block" % WP_LEN))
