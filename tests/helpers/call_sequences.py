@@ -14,6 +14,7 @@ and the driver holds every step of a plan to its expectation -- it skips nothing
 SequenceError that names the step, the predecessor and its batch, the family, the batch, the width, the array and the index.
 
   pair_cover(n)         a cyclic sequence of n * n + 1 indices in which every ordered pair (a, b), a == b included, is adjacent once
+  pair_cover_touching(n, new)   the same for the pairs that have a member of ``new`` in them, and no other pair
   after_each(r, f)      every refusing step followed once by every family
   rotation(plan, ..)    the batch of every step: contents alternate DENSE, SPARSE, the sparse batch never longer than the dense one before it
   build_batches(..)     the batches E, S, S600, SN, M, M5, L in both contents, fixed seeds, sized by the library's thresholds (passed in)
@@ -41,6 +42,31 @@ def pair_cover(n):
     rng = random.Random(0xC0FFEE + n)
     exits = {a: rng.sample(range(n), n) for a in range(n)}
     stack, circuit = [0], []
+    while stack:
+        v = stack[-1]
+        if exits[v]:
+            stack.append(exits[v].pop())
+        else:
+            circuit.append(stack.pop())
+    return circuit[::-1]
+
+
+def pair_cover_touching(n, new):
+    """The part of pair_cover(n) that has a member of ``new`` in it, closed: every ordered pair (a, b) of range(n) with a in new or b in
+    new adjacent exactly once, a == b for a new a included, and no pair of two old indices.  In that graph a new vertex has n exits and
+    n entries, an old one len(new) of each, and every vertex reaches a new one in one step: an Euler circuit exists.  Walked by the
+    same rule as pair_cover, exits in an order fixed by a seeded shuffle, from the lowest new index.  n * n - (n - len(new)) ** 2 pairs,
+    one element more."""
+    new = sorted(set(new))
+    if n < 1 or not new or new[0] < 0 or new[-1] >= n:
+        raise ValueError("new must be a non-empty subset of range(n)")
+    is_new = set(new)
+    rng = random.Random(0xC0FFEE + n)
+    exits = {}
+    for a in range(n):
+        to = list(range(n)) if a in is_new else new
+        exits[a] = rng.sample(to, len(to))
+    stack, circuit = [new[0]], []
     while stack:
         v = stack[-1]
         if exits[v]:

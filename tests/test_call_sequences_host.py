@@ -6,7 +6,11 @@
   only on its second occurrence after a refusal, one whose result is read late -- it fails on exactly that step and names predecessor,
   family, size, array and index, and it passes the all-correct plan.  That is the proof that the GPU test sees an order-dependent error;
 * the batches have the shapes the issue names, relative to the library's own thresholds (latok_debug_limits needs no device);
-* every family's expectation can be computed here, for every batch it gets."""
+* every family's expectation can be computed here, for every batch it gets;
+* for the ten families that came after the 35: the touching plan holds every ordered pair with one of them in it exactly once and no
+  other, the rotation serves it, their expectations have the right arrays, shapes and dtypes, follow the rule tables exactly where the
+  family cuts at latok's boundaries, and none is vacuous -- unk pieces, merged pieces, marked and unmarked Unigram pieces, unknown and
+  skipped ids, out-of-vocabulary grams are all there on both contents of M5."""
 import time
 
 import numpy as np
@@ -377,3 +381,179 @@ def test_every_expectation_is_computable_here(oracle, capsys):
     assert len(seq._refusers(env)) >= 80
     env.device = True
     assert len(seq._refusers(env)) >= 50
+
+
+# ---- the ten later families: the touching plan, their expectations ---------------------------------------------------------------------
+N_ALL = N_FAMILIES + 10
+NEW = range(N_FAMILIES, N_ALL)
+
+
+@pytest.mark.parametrize("n, new", [(N_ALL, tuple(NEW)), (5, (4,)), (3, (0, 1, 2)), (6, (0, 3)), (1, (0,)), (9, (2, 7, 8))])
+def test_pair_cover_touching_holds_every_pair_with_a_new_member_once(n, new):
+    plan = cs.pair_cover_touching(n, new)
+    want = {(a, b) for a in range(n) for b in range(n) if a in new or b in new}
+    assert len(want) == n * n - (n - len(new)) ** 2
+    pairs = cs.pairs_of(plan)
+    assert len(plan) == len(want) + 1 and plan[0] == plan[-1]
+    assert len(pairs) == len(set(pairs)) and set(pairs) == want                # each required pair once, and no pair of two old ones
+    assert plan == cs.pair_cover_touching(n, list(reversed(new)))              # deterministic, whatever the order of ``new``
+    if len(new) == n:
+        assert set(pairs) == set(cs.pairs_of(cs.pair_cover(n)))
+    for bad in ((), (n,), (-1,)):
+        with pytest.raises(ValueError):
+            cs.pair_cover_touching(n, bad)
+
+
+def test_touching_plan_of_the_45_has_800_pairs_and_801_steps():
+    plan = cs.pair_cover_touching(N_ALL, NEW)
+    assert len(plan) == 801 and len(set(cs.pairs_of(plan))) == 800 == N_ALL ** 2 - N_FAMILIES ** 2
+    assert not any(a < N_FAMILIES and b < N_FAMILIES for a, b in cs.pairs_of(plan))
+
+
+def test_rotation_puts_a_sparse_batch_behind_a_longer_dense_one_in_front_of_every_new_family():
+    env = seq.Env(None, None, False)
+    fams = seq._all_families(env)
+    uses_l = [f.uses_l for f in fams]
+    assert sum(uses_l) == 12 and not any(uses_l[f] for f in NEW)             # the later families are all byte-space
+    plan, sizes = seq._touching_plan(fams)
+    keys = cs.rotation(plan, uses_l)
+    assert [b.key for b in sizes] == ["%s/%s" % k for k in keys]
+    B = seq._batches()
+    seen, sizes_of, streams_of = set(), {}, {}
+    for k in range(1, len(plan)):
+        (s0, c0), (s1, c1) = keys[k - 1], keys[k]
+        if c0 == cs.DENSE and c1 == cs.SPARSE and B[(s0, c0)].total_bytes >= B[(s1, c1)].total_bytes and B[(s0, c0)].total_bytes > 0:
+            seen.add(plan[k])
+    assert seen >= set(NEW)
+    for k, f in enumerate(plan):
+        sizes_of.setdefault(f, set()).add(keys[k])
+        streams_of.setdefault(f, set()).add(k % 3)
+        assert keys[k][0] != "L" or uses_l[f]
+    assert all(len(sizes_of[f]) >= 6 and len(streams_of[f]) == 3 for f in NEW)
+    # int32 and int64 occurrences of every later family meet both contents; each meets the dense M5 and a sparse batch of several tiles
+    occ, met = {}, set()
+    for k, f in enumerate(plan):
+        met.add((f, occ.get(f, 0) % 2, keys[k][1]))
+        occ[f] = occ.get(f, 0) + 1
+    assert all((f, odd, c) in met for f in NEW for odd in (0, 1) for c in (cs.DENSE, cs.SPARSE))
+    assert all(("M5", cs.DENSE) in sizes_of[f] and {("M", cs.SPARSE), ("M5", cs.SPARSE)} & sizes_of[f] for f in NEW)     # (more than a tile)
+
+
+SHAPES = {"indptr": 1, "oov": 1, "indices": 1, "data": 1, "ids": 1, "spans": 2, "items": 2, "counts": 1, "input_ids": 2, "lengths": 1, "bytes": 1,
+          "out_off": 1}
+DTYPES = {"indices": np.int32, "data": np.int32, "ids": np.int32, "input_ids": np.int32, "lengths": np.int32, "bytes": np.uint8, "out_off": np.int64}
+
+
+def test_every_new_expectation_is_computable_here(oracle):
+    """every later family's expect(), on the CPU, for every batch it can meet, in both widths and under the rule tables: the right
+    arrays, shapes and dtypes; and none of them is vacuous on M5"""
+    env = seq.Env(None, oracle, False)
+    fams = seq._all_families(env)[N_FAMILIES:]
+    assert [f.name for f in fams] == [name for name, _ in seq._new_makers()] and len(fams) == 10
+    B = seq._batches()
+    for f in fams:
+        for (size, content), b in B.items():
+            if size == "L":
+                assert not f.uses_l
+                continue
+            for odd in (0, 1):
+                f.occ = f.odd = odd
+                want = f.expect(b)
+                assert want["rc"].tolist() == [0] and set(want) - {"rc", "guard bytes overwritten"} <= set(SHAPES) | {"n", "nnz", "total", "n_pieces",
+                                                                                                                  "n_tokens", "n_unknown"}
+                for name, v in want.items():
+                    assert isinstance(v, np.ndarray), (f.name, name)
+                    if name in SHAPES:
+                        assert v.ndim == SHAPES[name] and v.dtype == DTYPES.get(name, np.int64), (f.name, b.key, name, v.dtype, v.shape)
+                rows = next(want[k] for k in ("indptr", "out_off", "counts", "lengths") if k in want)
+                assert rows.shape[0] == b.n_str + (0 if rows is want.get("counts") or rows is want.get("lengths") else 1), (f.name, b.key)
+                for rec, total in (("indices", "nnz"), ("data", "nnz"), ("ids", "n_pieces"), ("spans", "n_pieces"), ("items", "n"), ("bytes", "n")):
+                    if rec in want:
+                        assert want[rec].shape[0] == int(want[total][0]) == int(rows.sum() if rows.shape[0] == b.n_str else rows[-1]), (f.name, b.key, rec)
+                if "input_ids" in want:
+                    assert want["input_ids"].shape == (b.n_str, seq.PIECE_LEN) and (want["lengths"] >= 2).all() and (want["lengths"] <= seq.PIECE_LEN).all()
+    # the refusing forms, and the boundary families under the rule tables: other tokens, so another expectation
+    assert len(seq._refusers(env, seq._new_makers())) == 25
+    env.device = True
+    assert len(seq._refusers(env, seq._new_makers())) == 16
+    env.device = False
+    m5 = B[("M5", cs.DENSE)]
+    for odd in (0, 1):
+        plain = {}
+        for f in fams:
+            f.occ = f.odd = odd
+            plain[f.name] = f.expect(m5)
+        env.rules = "all_columns"
+        for f in fams:
+            f.occ = f.odd = odd
+            ruled = f.expect(m5)
+            same = all(cs.first_difference(ruled[k], plain[f.name][k]) is None for k in ruled)
+            # (the padded BPE call takes the latok-token object on even occurrences and GPT-2's pre-tokens on odd ones)
+            assert same == (not f.boundary or (f.name == "latok_bpe_padded_utf8_bytes_batch" and odd == 1)), (f.name, odd)
+        env.rules = None
+    env.rules = None
+
+
+def test_no_new_expectation_is_vacuous(oracle):
+    """from the reference alone, on both contents of M5: BPE leaves an unk piece and a piece of several bytes, on either front; Unigram a
+    piece behind the marker and one without; both decoders meet an id they do not hold and ids they skip; the char-gram CSR has entries and
+    grams that are not in the vocabulary"""
+    env = seq.Env(None, oracle, False)
+    inverse = {i: w for w, i in seq.UNI_DICT.items()}
+    for c in (cs.DENSE, cs.SPARSE):
+        b = seq._batches()[("M5", c)]
+        for kind in ("bpe", "gpt2"):
+            _, ids, spans, n_tok = seq._pieces(env, b, kind)
+            width = spans[:, 1] - spans[:, 0]
+            assert (ids == seq.BPE_UNK).any() and ((ids != seq.BPE_UNK) & (width > 1)).any() and ids.size > n_tok > 0, (c, kind)
+        over = (np.diff(cs.reference(oracle, b).byte_spans, axis=1) > seq.PIECE_MAX_BYTES).any()
+        assert over == (c == cs.SPARSE)                                       # the over-long tokens are the SPARSE batch's
+        _, ids, spans, _ = seq._pieces(env, b, "uni")
+        words = [inverse.get(int(i)) for i in ids]
+        assert any(w is not None and w.startswith(seq.unigram_ref.MARKER) for w in words), c
+        assert any(w is not None and not w.startswith(seq.unigram_ref.MARKER) for w in words) and (ids == seq.UNI_UNK).any(), c
+        assert (spans[:, 1] == spans[:, 0]).any() or c == cs.SPARSE           # the marker alone: an empty range
+        for fam in (seq.DetokCsr(env), seq.DetokPadded(env)):
+            for odd in (0, 1):
+                fam.occ = fam.odd = odd
+                want = fam.full(b)
+                assert want["n_unknown"] > 0 and want["n"] > 0, (c, fam.name, odd)
+        for odd, (kind, skip) in enumerate((("bpe", seq.DETOK_BPE_SKIP), ("wp", seq.DETOK_WP_SKIP))):
+            ids = seq._pieces(env, b, kind, rules=False)[1]
+            assert any((ids == s).any() for s in skip), (c, kind)
+        for odd in (0, 1):
+            fam = seq.CharGrams(env, "fit", "latok_chargram_counts_utf8_bytes_batch", False)
+            fam.occ = fam.odd = odd
+            want = fam.full(b)
+            assert want["oov"].sum() > 0 and (want["data"] > 0).any() and want["nnz"] > 0 and want["total"] > want["oov"].sum(), (c, odd)
+            fam = seq.CharGrams(env, "fit", "latok_hashed_chargram_counts_utf8_bytes_batch", True)
+            fam.occ = fam.odd = odd
+            want = fam.full(b)
+            assert (want["data"] != 0).any() and ((want["data"] < 0).any() == bool(odd)), (c, odd)
+
+
+def test_the_memoised_cut_is_the_helpers_cut(oracle):
+    """seq._cut_rows cuts every distinct token once; bpe_ref.cut_rows, unigram_ref.cut_rows and wordpiece_ref.cut_rows cut each where it
+    stands: the same rows.  And the vectorised padded block is the rows written out one by one"""
+    env = seq.Env(None, oracle, False)
+    for key in (("M5", cs.DENSE), ("M5", cs.SPARSE), ("S600", cs.DENSE), ("M", cs.SPARSE)):
+        b = seq._batches()[key]
+        r = cs.reference(oracle, b)
+        counts, spans = seq._pretok(b)
+        want = {"bpe": seq.bpe_ref.cut_rows(b.u8, b.boff, r.counts, r.byte_spans.tolist(), seq.BPE_DICT, seq.PIECE_MAX_BYTES, True, seq.BPE_UNK),
+                "gpt2": seq.bpe_ref.cut_rows(b.u8, b.boff, counts, spans.tolist(), seq.GPT2_DICT, seq.PIECE_MAX_BYTES, False, seq.BPE_UNK),
+                "uni": seq.unigram_ref.cut_rows(b.u8, b.boff, r.counts, r.byte_spans.tolist(), seq.UNI_DICT, seq.UNI_SCORES, seq.UNI_UNK_SCORE,
+                                                seq.unigram_ref.MARKER, True, seq.PIECE_MAX_BYTES, seq.UNI_UNK),
+                "wp": seq.wpr.cut_rows(b.u8, b.boff, r.counts, r.byte_spans.tolist(), seq.WP_DICT, cs.WP_PREFIX, 100, seq.DETOK_WP_UNK)}
+        for kind, (indptr, ids, sp) in want.items():
+            got = seq._pieces(env, b, kind)
+            assert got[0].tolist() == list(indptr) and got[1].tolist() == list(ids), (key, kind)
+            assert got[2].tolist() == [list(x) for x in np.asarray(sp).reshape(-1, 2).tolist()], (key, kind)
+            if kind != "wp":
+                rows, lengths = seq._padded(got[0], got[1], b.n_str, 91, 92, 93)
+                for s in range(b.n_str):
+                    row = [91] + list(ids[indptr[s]:indptr[s + 1]])[:seq.PIECE_LEN - 2] + [92]
+                    assert rows[s].tolist() == row + [93] * (seq.PIECE_LEN - len(row)) and lengths[s] == len(row), (key, kind, s)
+        # every pre-token range lies in its string, and together they cover it
+        assert counts.sum() == spans.shape[0] and (spans[:, 1] > spans[:, 0]).all()
+        assert int((spans[:, 1] - spans[:, 0]).sum()) == b.total_bytes

@@ -13,7 +13,14 @@ from helpers/fold_ref.py, hashes from helpers/murmur3_ref.py, WordPiece from hel
 under the header's bounds, term / n-gram / counter results from collections.Counter over the reference tokens.  Integer and byte outputs
 are compared exactly and in full; every output buffer ends in 64 poison elements that must survive; the output width is int64 on a
 family's even occurrences and LATOK_OUT_INT32 on its odd ones.  tests/test_call_sequences_host.py shows that the driver sees an
-order-dependent error."""
+order-dependent error.
+
+Ten families came after those 35: character n-grams inside tokens (vocabulary and hashed), byte-level BPE (ids on latok's tokens, ids on
+GPT-2's pre-tokens, padded), the pre-tokens themselves, Unigram (ids, padded) and decoding (CSR, padded).  They stand beside the 35 in
+plans of their own: every ordered pair that has one of the ten in it (helpers/call_sequences.pair_cover_touching), every family behind
+every refusal of the ten and the ten behind every refusal of the 35, the rule tables in front of the ten, the touching plan on rotating
+caller streams, the epoch wrap inside their multi-scan calls.  Their expectations come from helpers/bpe_ref.py, unigram_ref.py,
+pretok_ref.py, chargram_ref.py and detok_ref.py over the reference tokens, and their word lists are built here without the library."""
 import ctypes as C
 import functools
 
@@ -21,9 +28,14 @@ import numpy as np
 import pytest
 
 from conftest import RULE_SETS
+from helpers import bpe_ref
 from helpers import call_sequences as cs
+from helpers import chargram_ref
+from helpers import detok_ref
 from helpers import fold_ref
+from helpers import pretok_ref
 from helpers import tfidf_ref
+from helpers import unigram_ref
 from helpers import utf8_ref
 from helpers import wordpiece_ref as wpr
 from helpers.murmur3_ref import murmur3_ref
@@ -110,13 +122,21 @@ class Env:
         self.counter = batch.TokenCounter(1 << 14, 256, seed=SEED)
         self.idf_acc, self.idf_frozen = batch.Idf(NC), batch.Idf(NC)
         self.idf_frozen.load(FROZEN_DF, FROZEN_DOCS)
+        # the objects of the ten later families (their word lists: below, beside the families)
+        self.cg_vocab = batch.Vocab(CG_WORDS)
+        self.bpe = batch.BPE(BPE_WORDS, max_bytes=PIECE_MAX_BYTES, lead_space=True)
+        self.bpe_gpt2 = batch.BPE(GPT2_WORDS, max_bytes=PIECE_MAX_BYTES, lead_space=False, pretokenizer="gpt2")
+        self.uni = batch.Unigram(UNI_WORDS, UNI_SCORES, marker=unigram_ref.MARKER, unk_score=UNI_UNK_SCORE, fuse_unk=True, max_bytes=PIECE_MAX_BYTES)
+        self.detok_bpe = batch.Detokenizer(BPE_WORDS, mode="concat")
+        self.detok_wp = batch.Detokenizer(cs.WP_WORDS, mode="wordpiece", prefix=cs.WP_PREFIX, sep=b" ")
 
     def close(self):
         self.release(self.kept)
         for p, _ in self.inputs.values():
             if self.device:
                 self.lib.latok_dev_free(p)
-        for o in (self.vocab, self.vocab_bad, self.wp, self.counter, self.idf_acc, self.idf_frozen):
+        for o in (self.vocab, self.vocab_bad, self.wp, self.counter, self.idf_acc, self.idf_frozen, self.cg_vocab, self.bpe, self.bpe_gpt2, self.uni,
+                  self.detok_bpe, self.detok_wp):
             o.close()
 
     # -- memory
@@ -861,15 +881,379 @@ def _families(env):
     return fams
 
 
-def _refusers(env):
+def _refusers(env, makers=None):
     """every refusing step of the issue that the pointer mode allows"""
     out = []
-    for _, make in _makers():
+    for _, make in (_makers() if makers is None else makers):
         for mode in make(env).modes[1:]:
             if mode == "decreasing" and env.device:
                 continue                               # device-resident row offsets are the caller's promise
             out.append(make(env, mode))
     return out
+
+
+# ---- the ten later families: word lists, built without the library --------------------------------------------------------------------
+PIECE_MAX_BYTES, PIECE_LEN, BPE_MERGES = 24, 12, 60             # LONG_WORDS run to 29 bytes: a SPARSE batch holds over-long tokens
+BPE_UNK, BPE_BOS, BPE_EOS, BPE_PAD = -3, 1001, 1002, 1003       # none of them is an id of the decoder over BPE_WORDS
+UNI_UNK, UNI_BOS, UNI_EOS, UNI_PAD, UNI_UNK_SCORE = -5, 2001, 2002, 2003, -20.0
+DETOK_WP_UNK = -9                                               # the unknown piece of the WordPiece rows: not an id of the decoder
+_LONG = [w.encode() for w in cs.LONG_WORDS]
+# BPE: every single byte but `q` and 0xF0 (a SPARSE word with a q and the 4-byte letter of a DENSE batch leave unk pieces), the merges of
+# the long words, then what a DENSE batch merges: the 2- and 3-byte letters and " a" .. " e" (lead_space puts the space in front)
+BPE_TRAINED = bpe_ref.train(_LONG, BPE_MERGES, base=[x for x in range(256) if x not in (ord("q"), 0xF0)])
+BPE_WORDS = BPE_TRAINED + [w for w in [x.encode("utf-8") for x in cs.WIDE_LETTERS[:4]] + [b" " + c.encode() for c in "abcde"] if w not in BPE_TRAINED]
+GPT2_WORDS = BPE_WORDS + [b" " + w for w in BPE_WORDS if len(w) > 1 and not w.startswith(b" ")] + [b" ", b"  ", b"\t"]
+BPE_DICT, GPT2_DICT = bpe_ref.rank_dict(BPE_WORDS), bpe_ref.rank_dict(GPT2_WORDS)
+assert len(GPT2_WORDS) < BPE_BOS and len(BPE_TRAINED) == 254 + BPE_MERGES and len(set(BPE_WORDS)) == len(BPE_WORDS)      # (ranks are positions)
+
+
+def _uni_words():
+    """single letters but q and x, the wide letters, the 2 .. 6-byte prefixes of the long words; every third also behind the marker; the
+    marker itself"""
+    plain = [c.encode() for c in cs.ASCII_LETTERS if c not in "qx"] + [w.encode("utf-8") for w in cs.WIDE_LETTERS] + \
+        sorted({w[:k] for w in _LONG for k in range(2, 7)})
+    words = []
+    for i, w in enumerate(plain):
+        words.append(w)
+        if i % 3 == 0:
+            words.append(unigram_ref.MARKER + w)
+    return words + [unigram_ref.MARKER]
+
+
+UNI_WORDS = _uni_words()
+UNI_SCORES = np.array([-(8 + (i * 5) % 11) / 8 for i in range(len(UNI_WORDS))], np.float32)       # multiples of 1/8: every sum is exact
+UNI_DICT = unigram_ref.word_dict(UNI_WORDS)
+
+
+def _cg_words():
+    """cs.VOCAB_WORDS, then character grams of the long words and of the one-letter tokens, pads included"""
+    extra = [g for w in _LONG[::4] for g in [x[2] for x in chargram_ref.token_grams(w, 2, 3)][::3]]
+    extra += [b" " + c.encode() for c in cs.ASCII_LETTERS[:12]] + [c.encode() + b" " for c in cs.ASCII_LETTERS[:6]] + [b" a ", b" b ", b" "]
+    out, seen = list(cs.VOCAB_WORDS), set(cs.VOCAB_WORDS)
+    for g in extra:
+        if g not in seen:
+            seen.add(g)
+            out.append(g)
+    return out
+
+
+CG_WORDS = _cg_words()
+CG_VOCAB = {w: i for i, w in reversed(list(enumerate(CG_WORDS)))}
+DETOK_BPE_MAP, DETOK_WP_MAP = detok_ref.id_map(BPE_WORDS), detok_ref.id_map(cs.WP_WORDS)
+DETOK_BPE_SKIP = (BPE_DICT[b"a"], BPE_DICT[b"e"])               # two ids that occur in the rows
+DETOK_WP_SKIP = (WP_DICT[b"a"], WP_DICT[b"##e"])
+
+
+# ---- their references: one cut of a batch, kept with the batch ------------------------------------------------------------------------
+def _pretok(b):
+    """(counts, spans) of GPT-2's pre-tokens of every string; no rule table has a say"""
+    k = ("pretok", None, None)
+    if k not in b._ref:
+        raw, counts, spans = b.u8.tobytes(), [], []
+        for s in range(b.n_str):
+            p = pretok_ref.pretokens(raw[int(b.boff[s]):int(b.boff[s + 1])])
+            counts.append(len(p))
+            spans += p
+        b._ref[k] = (np.array(counts, np.int64), np.array(spans, np.int64).reshape(-1, 2))
+    return b._ref[k]
+
+
+@functools.lru_cache(maxsize=None)
+def _bpe_cut(token, gpt2):
+    return tuple(bpe_ref.cut(token, GPT2_DICT if gpt2 else BPE_DICT, PIECE_MAX_BYTES, BPE_UNK))
+
+
+@functools.lru_cache(maxsize=None)
+def _uni_cut(token, marked):
+    return tuple(unigram_ref.cut(token, marked, UNI_DICT, UNI_SCORES, UNI_UNK_SCORE, unigram_ref.MARKER, True, PIECE_MAX_BYTES, UNI_UNK))
+
+
+@functools.lru_cache(maxsize=None)
+def _wp_cut(token):
+    return tuple(wpr.cut(token, WP_DICT, cs.WP_PREFIX, 100, DETOK_WP_UNK))
+
+
+def _cut_rows(b, counts, spans, kind):
+    """bpe_ref.cut_rows / unigram_ref.cut_rows / wordpiece_ref.cut_rows with every distinct token cut once (a batch repeats few tokens
+    many times); tests/test_call_sequences_host.py holds this loop to the three helpers, in its four kinds"""
+    raw, indptr, ids, out, k = b.u8.tobytes(), [0], [], [], 0
+    for s in range(b.n_str):
+        base, prev = int(b.boff[s]), None
+        for _ in range(int(counts[s])):
+            a, e = spans[k]
+            k += 1
+            if kind == "uni":
+                pieces = _uni_cut(raw[base + a:base + e], unigram_ref.is_marked(prev, a))
+            elif kind == "wp":
+                pieces = _wp_cut(raw[base + a:base + e])
+            else:
+                if kind == "bpe" and a > 0 and raw[base + a - 1] == 0x20:       # lead_space
+                    a -= 1
+                pieces = _bpe_cut(raw[base + a:base + e], kind == "gpt2")
+            for pid, p0, p1 in pieces:
+                ids.append(pid)
+                out.append((a + p0, a + p1))
+            prev = e
+        indptr.append(len(ids))
+    return indptr, ids, out
+
+
+def _pieces(env, b, kind, rules=True):
+    """(indptr int64, ids int32, spans int64 [n, 2], n_tokens) of one cut of a batch.  kind: "bpe" (latok's tokens, the space in front),
+    "gpt2" (GPT-2's pre-tokens), "uni", "wp" (the WordPiece rows the decoder gets, unknown = DETOK_WP_UNK).  rules=False: the tokens
+    under the built-in rules whatever the context holds"""
+    k = ("pieces", kind, env.rules if (rules and kind != "gpt2") else None)
+    if k not in b._ref:
+        if kind == "gpt2":
+            counts, spans = _pretok(b)
+            cut, n_tok = _cut_rows(b, counts, spans.tolist(), kind), len(spans)
+        else:
+            r = env.ref(b) if rules else cs.reference(env.oracle, b)
+            n_tok = r.n_tokens
+            cut = _cut_rows(b, r.counts, r.byte_spans.tolist(), kind)
+        b._ref[k] = (np.array(cut[0], np.int64), np.array(cut[1], np.int32).reshape(-1), np.array(cut[2], np.int64).reshape(-1, 2), n_tok)
+    return b._ref[k]
+
+
+def _padded(indptr, ids, n_str, bos, eos, pad):
+    """the [n_str, PIECE_LEN] block with its specials, and the lengths: row s = bos, the first PIECE_LEN - 2 ids of row s, eos, then pad"""
+    take = np.minimum(np.diff(indptr), PIECE_LEN - 2)
+    rows = np.full((n_str, PIECE_LEN), pad, np.int32)
+    rows[:, 0] = bos
+    cols = np.arange(PIECE_LEN - 2)
+    held = cols[None, :] < take[:, None]
+    rows[:, 1:PIECE_LEN - 1][held] = ids[(indptr[:-1, None] + cols[None, :])[held]]
+    rows[np.arange(n_str), take + 1] = eos
+    return rows, (take + 2).astype(np.int32)
+
+
+def _decoded(texts, unknown):
+    off = np.zeros(len(texts) + 1, np.int64)
+    np.cumsum([len(t) for t in texts], out=off[1:])
+    return {"bytes": np.frombuffer(b"".join(texts), np.uint8), "out_off": off, "n": int(off[-1]), "n_unknown": unknown}
+
+
+# ---- the ten families -----------------------------------------------------------------------------------------------------------------
+class Later(Fam):
+    """a later family: what full() gives is a function of (family, batch, width, rules) alone and is kept with the batch, for every test
+    of the session"""
+
+    def cached(self, b):
+        k = ("full", self.entry, self.odd, self.env.rules)
+        if k not in b._ref:
+            b._ref[k] = self.full(b)
+        return b._ref[k]
+
+
+@functools.lru_cache(maxsize=None)
+def _token_grams(token, lo, hi, pad):
+    return tuple(chargram_ref.row_grams((token,), lo, hi, pad))
+
+
+class CharGrams(Later):
+    """latok_chargram_counts_utf8_bytes_batch / latok_hashed_chargram_counts_utf8_bytes_batch: orders 2 .. 3 on even occurrences, 1 .. 4 on
+    odd ones; the hashed form alternates its sign on the odd ones"""
+    boundary = True
+    records, modes = ("indices", "data"), CAP_MODES
+    PAD = 0x20
+
+    def __init__(self, env, mode, entry, hashed):
+        self.entry, self.hashed = entry, hashed
+        super().__init__(env, mode)
+
+    def orders(self):
+        return (1, 4) if self.odd else (2, 3)
+
+    @staticmethod
+    @functools.lru_cache(maxsize=None)
+    def key(gram):
+        h = _hash(gram)
+        h = h - (1 << 32) if h >= (1 << 31) else h
+        return abs(h) % NC, (-1 if h < 0 else 1)
+
+    def full(self, b):
+        k = ("chargrams", self.orders(), self.env.rules)                                    # the two forms share the grams
+        if k not in b._ref:
+            b._ref[k] = [[g for t in row for g in _token_grams(t, *self.orders(), self.PAD)] for row in self.env.ref(b).rows()]
+        grams = b._ref[k]
+        total = sum(len(g) for g in grams)
+        if self.hashed:
+            indptr, indices, data = cs._csr([[(self.key(x)[0], self.key(x)[1] if self.odd else 1) for x in g] for g in grams])
+            return {"indptr": indptr, "indices": indices, "data": data, "nnz": int(indptr[-1]), "total": total}
+        rows = [[(CG_VOCAB[x], 1) for x in g if x in CG_VOCAB] for g in grams]
+        indptr, indices, data = cs._csr(rows)
+        oov = np.array([len(g) - len(r) for g, r in zip(grams, rows)], np.int64)
+        return {"indptr": indptr, "oov": oov, "indices": indices, "data": data, "nnz": int(indptr[-1]), "total": total}
+
+    def run(self, b):
+        env, need = self.env, self.cached(b)["nnz"]
+        indptr, oov = self.out(b.n_str + 1, self.dt), None if self.hashed else self.out(b.n_str, self.dt)
+        indices, data = self.rec(need, np.int32), self.rec(need, np.int32)
+        nnz, total = C.c_int64(-1), C.c_int64(-1)
+        mid = [SEED, NC, self.odd] if self.hashed else [env.cg_vocab.handle]
+        tail = [indptr.ptr] + ([] if self.hashed else [oov.ptr]) + [P(indices), P(data), self.cap(need), C.byref(nnz), C.byref(total), self.flags, self.stream]
+        rc = getattr(env.lib, self.entry)(env.inp(b.u8), self.offs(b.boff), b.n_str, b.total_bytes, *mid, *self.orders(), self.PAD, *tail)
+        outs = [("indptr", indptr, b.n_str + 1), ("oov", oov, b.n_str), ("indices", indices, need), ("data", data, need)]
+        return rc, outs, {"nnz": nnz.value, "total": total.value}
+
+
+class PieceIds(Later):
+    """latok_bpe_ids_utf8_bytes_batch (on latok's tokens; on GPT-2's pre-tokens) / latok_unigram_ids_utf8_bytes_batch"""
+    records, modes = ("ids", "spans"), CAP_MODES
+
+    def __init__(self, env, mode, entry, fn, kind, obj, unk):
+        self.entry, self.fn, self.kind, self.obj, self.unk, self.boundary = entry, fn, kind, obj, unk, kind != "gpt2"
+        super().__init__(env, mode)
+
+    def full(self, b):
+        indptr, ids, spans, n_tok = _pieces(self.env, b, self.kind)
+        return {"indptr": indptr, "ids": ids, "spans": spans, "n_pieces": int(ids.size), "n_tokens": n_tok}
+
+    def run(self, b):
+        env, need = self.env, self.cached(b)["n_pieces"]
+        indptr, ids, spans = self.out(b.n_str + 1, self.dt), self.rec(need, np.int32), self.rec(need, self.dt, (2,))
+        n, n_tok = C.c_int64(-1), C.c_int64(-1)
+        rc = getattr(env.lib, self.fn)(env.inp(b.u8), self.offs(b.boff), b.n_str, b.total_bytes, getattr(env, self.obj).handle, self.unk, indptr.ptr,
+                                       P(ids), P(spans), self.cap(need), C.byref(n), C.byref(n_tok), self.flags, self.stream)
+        return rc, [("indptr", indptr, b.n_str + 1), ("ids", ids, need), ("spans", spans, need)], {"n_pieces": n.value, "n_tokens": n_tok.value}
+
+
+class PiecePadded(Later):
+    """latok_bpe_padded_utf8_bytes_batch (the latok-token object on even occurrences, the GPT-2 object on odd ones) /
+    latok_unigram_padded_utf8_bytes_batch: PIECE_LEN cells a row, specials on"""
+    has_width, boundary, modes = False, True, ("fit", "decreasing")
+
+    def __init__(self, env, mode, entry, kinds, objs, ids4):
+        self.entry, self.kinds, self.objs, self.ids4 = entry, kinds, objs, ids4           # ids4: (unk, bos, eos, pad)
+        super().__init__(env, mode)
+
+    def full(self, b):
+        indptr, ids, _, _ = _pieces(self.env, b, self.kinds[self.odd])
+        rows, lengths = _padded(indptr, ids, b.n_str, *self.ids4[1:])
+        return {"input_ids": rows, "lengths": lengths, "n_pieces": int(ids.size)}
+
+    def run(self, b):
+        env = self.env
+        unk, bos, eos, pad = self.ids4
+        ids, lengths, n = self.out(b.n_str, np.int32, (PIECE_LEN,)), self.out(b.n_str, np.int32), C.c_int64(-1)
+        rc = getattr(env.lib, self.entry)(env.inp(b.u8), self.offs(b.boff), b.n_str, b.total_bytes, getattr(env, self.objs[self.odd]).handle, unk,
+                                          PIECE_LEN, 1, bos, eos, pad, ids.ptr, lengths.ptr, C.byref(n), self.flags, self.stream)
+        return rc, [("input_ids", ids, b.n_str), ("lengths", lengths, b.n_str)], {"n_pieces": n.value}
+
+
+class Pretokens(Later):
+    """latok_pretokens_utf8_bytes_batch with LATOK_PRETOK_GPT2: the other front, on its own"""
+    entry, records, modes = "latok_pretokens_utf8_bytes_batch", ("items",), CAP_MODES
+    GPT2 = 1
+
+    def full(self, b):
+        counts, spans = _pretok(b)
+        return {"counts": counts, "items": spans, "n": int(spans.shape[0])}
+
+    def run(self, b):
+        env, need = self.env, self.cached(b)["n"]
+        counts, items, n = self.out(b.n_str, self.dt), self.rec(need, self.dt, (2,)), C.c_int64(-1)
+        rc = env.lib.latok_pretokens_utf8_bytes_batch(env.inp(b.u8), self.offs(b.boff), b.n_str, b.total_bytes, self.GPT2, counts.ptr, P(items),
+                                                      self.cap(need), C.byref(n), self.flags, self.stream)
+        return rc, [("counts", counts, b.n_str), ("items", items, need)], {"n": n.value}
+
+
+class DetokCsr(Later):
+    """latok_detok_csr: on even occurrences the CONCAT decoder over BPE_WORDS on the batch's reference BPE ids (int64 indptr), on odd ones
+    the WORDPIECE decoder over cs.WP_WORDS on its reference WordPiece ids (int32 indptr).  The unknown pieces of either cut carry an id
+    the decoder does not hold; two ids that occur are skipped.  The rows are those under the built-in rules: no rule table has a say"""
+    entry, records, modes = "latok_detok_csr", ("bytes",), CAP_MODES
+
+    def parts(self):
+        return ("wp", "detok_wp", DETOK_WP_MAP, detok_ref.WORDPIECE, DETOK_WP_SKIP) if self.odd else \
+               ("bpe", "detok_bpe", DETOK_BPE_MAP, detok_ref.CONCAT, DETOK_BPE_SKIP)
+
+    def full(self, b):
+        kind, _, d, mode, skip = self.parts()
+        indptr, ids, _, _ = _pieces(self.env, b, kind, rules=False)
+        ids, at = ids.tolist(), indptr.tolist()
+        rows = [ids[at[s]:at[s + 1]] for s in range(b.n_str)]
+        return _decoded(*detok_ref.decode(rows, d, mode, cs.WP_PREFIX, b" ", skip))
+
+    def run(self, b):
+        env, need = self.env, self.cached(b)["n"]
+        kind, obj, _, _, skip = self.parts()
+        indptr, ids, _, _ = _pieces(env, b, kind, rules=False)
+        ip = indptr.astype(self.dt)
+        p_ip = self.offs(ip) if self.mode == "decreasing" else env.inp(ip, cache=False)
+        skip = np.array(skip, np.int32)                                                    # a host pointer in every mode
+        out, off, n, unk = self.rec(need, np.uint8), self.out(b.n_str + 1, np.int64), C.c_int64(-1), C.c_int64(-1)
+        rc = env.lib.latok_detok_csr(getattr(env, obj).handle, p_ip, env.inp(ids, cache=False), b.n_str, ids.size, skip.ctypes.data, skip.size, P(out),
+                                     self.cap(need), off.ptr, C.byref(n), C.byref(unk), self.flags, self.stream)
+        return rc, [("bytes", out, need), ("out_off", off, b.n_str + 1)], {"n": n.value, "n_unknown": unk.value}
+
+
+class DetokPadded(Later):
+    """latok_detok_padded on the reference padded BPE block: with its lengths on even occurrences (BOS and one id that occurs skipped, so
+    that every EOS is an unknown id), with lengths = NULL and the pad id among the skipped ones on odd occurrences"""
+    entry, has_width, records, modes = "latok_detok_padded", False, ("bytes",), ("fit", "short", "query")
+
+    def block(self, b):
+        k = ("block", None, None)
+        if k not in b._ref:
+            indptr, ids, _, _ = _pieces(self.env, b, "bpe", rules=False)
+            b._ref[k] = _padded(indptr, ids, b.n_str, BPE_BOS, BPE_EOS, BPE_PAD)
+        return b._ref[k]
+
+    def skip(self):
+        return (BPE_BOS, BPE_EOS, BPE_PAD) if self.odd else (BPE_BOS, DETOK_BPE_SKIP[0])
+
+    def full(self, b):
+        rows, lengths = self.block(b)
+        return _decoded(*detok_ref.decode(detok_ref.padded_rows(rows.tolist(), None if self.odd else lengths.tolist()), DETOK_BPE_MAP, detok_ref.CONCAT,
+                                          skip=self.skip()))
+
+    def run(self, b):
+        env, need = self.env, self.cached(b)["n"]
+        rows, lengths = self.block(b)
+        skip = np.array(self.skip(), np.int32)
+        out, off, n, unk = self.rec(need, np.uint8), self.out(b.n_str + 1, np.int64), C.c_int64(-1), C.c_int64(-1)
+        rc = env.lib.latok_detok_padded(env.detok_bpe.handle, env.inp(rows, cache=False), None if self.odd else env.inp(lengths, cache=False), b.n_str,
+                                        PIECE_LEN, skip.ctypes.data, skip.size, P(out), self.cap(need), off.ptr, C.byref(n), C.byref(unk), self.flags,
+                                        self.stream)
+        return rc, [("bytes", out, need), ("out_off", off, b.n_str + 1)], {"n": n.value, "n_unknown": unk.value}
+
+
+def _new_makers():
+    """[(family name, maker(env, mode))] of the ten families that came after the 35, in the order of the header"""
+    bpe, uni = "latok_bpe_ids_utf8_bytes_batch", "latok_unigram_ids_utf8_bytes_batch"
+
+    def grams(entry, hashed):
+        return entry, lambda env, mode="fit": CharGrams(env, mode, entry, hashed)
+
+    def ids(entry, fn, kind, obj, unk):
+        return entry, lambda env, mode="fit": PieceIds(env, mode, entry, fn, kind, obj, unk)
+
+    def padded(entry, kinds, objs, ids4):
+        return entry, lambda env, mode="fit": PiecePadded(env, mode, entry, kinds, objs, ids4)
+
+    return [
+        grams("latok_chargram_counts_utf8_bytes_batch", False),
+        grams("latok_hashed_chargram_counts_utf8_bytes_batch", True),
+        ids(bpe, bpe, "bpe", "bpe", BPE_UNK),
+        ids(bpe + "[gpt2]", bpe, "gpt2", "bpe_gpt2", BPE_UNK),
+        padded("latok_bpe_padded_utf8_bytes_batch", ("bpe", "gpt2"), ("bpe", "bpe_gpt2"), (BPE_UNK, BPE_BOS, BPE_EOS, BPE_PAD)),
+        (Pretokens.entry, lambda env, mode="fit": Pretokens(env, mode)),
+        ids(uni, uni, "uni", "uni", UNI_UNK),
+        padded("latok_unigram_padded_utf8_bytes_batch", ("uni", "uni"), ("uni", "uni"), (UNI_UNK, UNI_BOS, UNI_EOS, UNI_PAD)),
+        (DetokCsr.entry, lambda env, mode="fit": DetokCsr(env, mode)),
+        (DetokPadded.entry, lambda env, mode="fit": DetokPadded(env, mode)),
+    ]
+
+
+N_OLD, N_NEW = 35, 10
+
+
+def _all_families(env):
+    """the 35, then the ten"""
+    fams = _families(env) + [make(env) for _, make in _new_makers()]
+    assert len(fams) == N_OLD + N_NEW and len({f.name for f in fams}) == N_OLD + N_NEW
+    return fams
 
 
 class _Session:
@@ -1000,3 +1384,134 @@ def test_scan_epoch_wrap_inside_multi_scan_calls(gpu, oracle, pointers):
         turn = list(range(35))
         keys = cs.rotation(turn, [f.uses_l for f in fams])
         assert cs.run(turn, fams, [B[k] for k in keys]) == 35
+
+
+# ---- the ten later families beside the 35 ---------------------------------------------------------------------------------------------
+NEW = range(N_OLD, N_OLD + N_NEW)
+# the later families that enqueue more than one device-wide scan per call (latok_amd/csrc/api.cpp): the char-gram calls (token rows, grams
+# per token, the CSR tail) and the piece calls of BPE and Unigram (token rows, pieces per token), each behind the scan of the token front;
+# the pre-tokens and the decoders scan once
+NEW_MULTI_SCAN = ("latok_chargram_counts_utf8_bytes_batch", "latok_hashed_chargram_counts_utf8_bytes_batch", "latok_bpe_ids_utf8_bytes_batch",
+                  "latok_bpe_ids_utf8_bytes_batch[gpt2]", "latok_bpe_padded_utf8_bytes_batch", "latok_unigram_ids_utf8_bytes_batch",
+                  "latok_unigram_padded_utf8_bytes_batch")
+RULE_FREE_NEW = ("latok_pretokens_utf8_bytes_batch", "latok_bpe_ids_utf8_bytes_batch[gpt2]", "latok_detok_csr")
+
+
+def _touching_plan(fams):
+    plan = cs.pair_cover_touching(len(fams), NEW)
+    keys = cs.rotation(plan, [f.uses_l for f in fams])
+    return plan, [_batches()[k] for k in keys]
+
+
+def _touching_pairs():
+    n = N_OLD + N_NEW
+    return {(a, b) for a in range(n) for b in range(n) if a >= N_OLD or b >= N_OLD}
+
+
+def _refusal_sizes(plan, every):
+    """the batches of an after_each plan, as test_every_family_after_every_refusal picks them"""
+    B = _batches()
+    follow = [("S", cs.SPARSE), ("M5", cs.SPARSE), ("E", cs.SPARSE), ("S600", cs.SPARSE), ("M", cs.SPARSE), ("S", cs.DENSE), ("M", cs.DENSE)]
+    sizes = []
+    for k in range(0, len(plan), 2):
+        refused = "M" if (k // 2) % 2 else "S600" if every[plan[k]].mode == "decreasing" else "S"
+        sizes += [B[(refused, cs.DENSE)], B[follow[(k // 2) % len(follow)]]]
+    return sizes
+
+
+@POINTERS
+def test_every_new_family_beside_every_family(gpu, oracle, pointers):
+    """every ordered pair of the 45 families that has one of the ten later ones in it, each once: 45 * 45 - 35 * 35 = 800 pairs"""
+    with _Session(gpu, oracle, pointers) as env:
+        fams = _all_families(env)
+        plan, sizes = _touching_plan(fams)
+        pairs = cs.pairs_of(plan)
+        assert len(plan) == 801 and len(pairs) == len(set(pairs)) == 800 and set(pairs) == _touching_pairs()
+        assert cs.run(plan, fams, sizes) == 801
+
+
+@POINTERS
+def test_every_family_after_every_new_refusal_and_back(gpu, oracle, pointers):
+    """every refusing mode of the ten later families in front of all 45, and every refusing mode of the 35 in front of the ten"""
+    with _Session(gpu, oracle, pointers) as env:
+        fams = _all_families(env)
+        refs_new, refs_old = _refusers(env, _new_makers()), _refusers(env)
+        every = refs_new + refs_old + fams
+        first = len(refs_new) + len(refs_old)
+        plan = cs.after_each(range(len(refs_new)), range(first, first + len(fams))) + \
+            cs.after_each(range(len(refs_new), first), range(first + N_OLD, first + len(fams)))
+        assert len(refs_new) == (16 if env.device else 25) and len(refs_old) >= (50 if env.device else 80)
+        assert len(plan) == 2 * (len(refs_new) * 45 + len(refs_old) * 10)
+        assert {every[r].entry for r in plan[0::2]} >= {f.entry for f in fams if set(f.modes) - {"fit", "decreasing"}}
+        assert cs.run(plan, every, _refusal_sizes(plan, every)) == len(plan)
+
+
+@POINTERS
+def test_rules_do_not_leak_into_or_out_of_the_new_families(gpu, oracle, pointers):
+    """every later family that cuts at latok's boundaries straight after latok_set_rules(all_columns) and straight after
+    latok_reset_rules, a family that reads no rule between each pair; and the same for the three that must NOT change: the pre-tokens,
+    the BPE ids on them and the decoder hold, behind latok_set_rules, what they hold under the built-in rules ("latok_set_rules has no
+    influence")"""
+    with _Session(gpu, oracle, pointers) as env:
+        fams = _all_families(env)
+        fold = next(i for i, f in enumerate(fams) if f.entry == "latok_fold_utf8_bytes_batch")
+        csr = next(i for i, f in enumerate(fams) if f.entry == "latok_tfidf_csr")
+        every = fams + [Rules(env, "all_columns"), Rules(env, None)]
+        on, off = len(fams), len(fams) + 1
+        plan, n_boundary, n_free = [], 0, 0
+        for i in NEW:
+            if fams[i].boundary or fams[i].entry in RULE_FREE_NEW:
+                k = n_boundary + n_free
+                plan += [on, i, fold if k % 2 else csr, off, i, csr if k % 2 else fold]
+                n_boundary, n_free = n_boundary + fams[i].boundary, n_free + (not fams[i].boundary)
+        assert (n_boundary, n_free) == (6, 3)
+        B = _batches()
+        shapes = [("M5", cs.DENSE), ("M", cs.SPARSE), ("S", cs.DENSE), ("S600", cs.SPARSE)]
+        sizes = [B[shapes[(k // 3) % len(shapes)]] for k in range(len(plan))]
+        # the tables do change the tokens of these batches: else the six boundary families would show nothing
+        assert any(not np.array_equal(cs.reference(oracle, b).byte_spans, cs.reference(oracle, b, RULE_SETS["all_columns"], "cps", "all_columns").byte_spans)
+                   for b in sizes)
+        assert cs.run(plan, every, sizes) == len(plan) == 6 * 9
+
+
+def test_new_families_on_rotating_caller_streams(gpu, oracle):
+    """device pointers, the touching plan, step k on stream k % 3 of {NULL, s1, s2}; an asynchronous call of the 35 is read only after
+    the later family behind it has been enqueued"""
+    with _Session(gpu, oracle, "device") as env:
+        hip = env.lib
+        s1, s2 = C.c_void_p(), C.c_void_p()
+        assert hip.hipStreamCreate(C.byref(s1)) == 0 and hip.hipStreamCreate(C.byref(s2)) == 0
+        try:
+            env.streams, env.defer, env.keep = [None, s1, s2], True, True
+            fams = _all_families(env)
+            plan, sizes = _touching_plan(fams)
+            used = set()
+            assert cs.run(plan, fams, sizes, on_step=lambda k, f, b, o: used.add((f.name, (k % 3)))) == 801
+            assert used == {(fams[f].name, k % 3) for k, f in enumerate(plan)}
+            assert all(sum((fams[f].name, s) in used for s in range(3)) == 3 for f in NEW)       # every later family on all three streams
+            assert sum(fams[a].asynchronous and b >= N_OLD for a, b in cs.pairs_of(plan)) == 6 * N_NEW      # each read behind a later family
+            assert hip.hipStreamSynchronize(s1) == 0 and hip.hipStreamSynchronize(s2) == 0
+            env._lib.check(env.lib.latok_sync())
+        finally:
+            env.streams = None
+            hip.hipStreamDestroy(s1)
+            hip.hipStreamDestroy(s2)
+
+
+@POINTERS
+def test_scan_epoch_wrap_inside_the_new_multi_scan_calls(gpu, oracle, pointers):
+    """the 18-bit scan epoch wraps between two scans of one call: each later multi-scan family starts four epochs in front of the wrap at
+    M5, then one full turn of all 45 families"""
+    with _Session(gpu, oracle, pointers) as env:
+        fams = _all_families(env)
+        B = _batches()
+        gpu.latok_debug_set_scan_epoch.restype, gpu.latok_debug_set_scan_epoch.argtypes = C.c_int, [C.c_uint]
+        for start in (0x3FFFE, 0x3FFFF, 0x3FFFD, 0x3FFFC):
+            for name in NEW_MULTI_SCAN:
+                i = next(i for i, f in enumerate(fams) if f.name == name)
+                assert gpu.latok_debug_set_scan_epoch(start) == 0
+                assert cs.run([i, i], fams, [B[("M5", cs.DENSE)], B[("M5", cs.SPARSE)]]) == 2
+        assert gpu.latok_debug_set_scan_epoch(0x3FFFC) == 0
+        turn = list(range(len(fams)))
+        keys = cs.rotation(turn, [f.uses_l for f in fams])
+        assert cs.run(turn, fams, [B[k] for k in keys]) == 45

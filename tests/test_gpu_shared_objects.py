@@ -2,6 +2,8 @@
 in a context of its own on ONE device, sharing the objects.
 
   latok_vocab, latok_wordpiece   "any context of the same device may use it, concurrently"
+  latok_bpe, latok_unigram,      "may be used by any context of its device, concurrently"
+  latok_detok
   latok_counter                  "calls on one counter are serialised by a lock inside it; two contexts of one device may share it"
   latok_idf                      "calls on one object are serialised by a lock inside it", and the float32 idf vector it keeps per smoothing
                                  mode, computed on one context's stream and handed to the others through an event, dropped by every
@@ -30,9 +32,13 @@ import threading
 import numpy as np
 import pytest
 
+from helpers import bpe_ref
+from helpers import detok_ref
 from helpers import fold_ref
+from helpers import pretok_ref
 from helpers import shared_state as ss
 from helpers import tfidf_ref as ref
+from helpers import unigram_ref as uni_ref
 from helpers import wordpiece_ref as wpr
 from helpers.murmur3_ref import murmur3_ref
 
@@ -743,3 +749,214 @@ def test_the_four_objects_share_one_lifecycle(gpu):
         assert destroy(None) == 0
     for r in range(32):
         assert _life_round(gpu, device) == first, r
+
+
+# ---- the later immutable objects: BPE, Unigram, Detokenizer ------------------------------------------------------------------------------
+# latok_bpe, latok_unigram, latok_detok: "may be used by any context of its device, concurrently".  The word lists are fixed and built
+# without the library; the expected values are helpers/bpe_ref.py, unigram_ref.py, pretok_ref.py and detok_ref.py over the file's tokens.
+PIECE_UNK, PIECE_BOS, PIECE_EOS, PIECE_PAD, PIECE_LEN, PIECE_MAX_BYTES = -1, 5001, 5002, 5003, 12, 24
+P_BPE_WORDS = bpe_ref.train(WORDS[:500], 120, base=[x for x in range(256) if x != ord("z")])       # no `z`: every word with one leaves an unk piece
+P_GPT2_WORDS = P_BPE_WORDS + [b" " + w for w in P_BPE_WORDS if len(w) > 1] + [b" ", b"  ", b"\t"]
+P_BPE_DICT, P_GPT2_DICT = bpe_ref.rank_dict(P_BPE_WORDS), bpe_ref.rank_dict(P_GPT2_WORDS)
+P_UNI_PLAIN = [bytes([x]) for x in LETTERS if x != ord("z")] + sorted({w[:k] for w in WORDS[:900] for k in (2, 3, 4)})
+P_UNI_WORDS = [w for i, p in enumerate(P_UNI_PLAIN) for w in ([p, uni_ref.MARKER + p] if i % 3 == 0 else [p])] + [uni_ref.MARKER]
+P_UNI_SCORES = np.array([-(8 + (i * 7) % 13) / 8 for i in range(len(P_UNI_WORDS))], np.float32)   # multiples of 1/8: every sum is exact
+P_UNI_DICT, P_UNI_UNK_SCORE = uni_ref.word_dict(P_UNI_WORDS), -20.0
+P_DETOK_MAP = detok_ref.id_map(P_BPE_WORDS)
+P_DETOK_SKIP = (P_BPE_DICT[b"a"], P_BPE_DICT[b"q"])
+assert len(P_GPT2_WORDS) < PIECE_BOS
+
+
+@functools.lru_cache(maxsize=None)
+def _bpe_cut(token, gpt2=False):
+    return tuple(bpe_ref.cut(token, P_GPT2_DICT if gpt2 else P_BPE_DICT, PIECE_MAX_BYTES, PIECE_UNK))
+
+
+@functools.lru_cache(maxsize=None)
+def _uni_cut(token, marked):
+    return tuple(uni_ref.cut(token, marked, P_UNI_DICT, P_UNI_SCORES, P_UNI_UNK_SCORE, uni_ref.MARKER, True, PIECE_MAX_BYTES, PIECE_UNK))
+
+
+def _piece_rows(rows):
+    """rows of [(id, start, end)] -> (indptr, ids, spans) as the ids calls return them"""
+    indptr = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([len(r) for r in rows], out=indptr[1:])
+    flat = [p for r in rows for p in r]
+    return indptr, np.array([p[0] for p in flat], np.int32), np.array([p[1:] for p in flat], np.int64).reshape(-1, 2)
+
+
+class Pieces:
+    """One of the four later call families on one batch of documents built by _join (a token touches no other: one separator byte lies
+    between two): 0 BPE ids on the latok-token object with lead_space, 1 the padded BPE block on the GPT-2 object, 2 Unigram ids, 3 the
+    decoder on the reference BPE ids of kind 0"""
+
+    def __init__(self, kind, docs):
+        self.kind, self.docs = kind, docs
+        rows = []
+        for d in docs:
+            row = []
+            if kind == 1:
+                for a, e in pretok_ref.pretokens(d):
+                    row += [(i, a + p0, a + p1) for i, p0, p1 in _bpe_cut(d[a:e], True)]
+            else:
+                a = 0
+                for w in d.split():
+                    if kind == 2:                                    # behind a separator or at the start: every token takes the marker
+                        row += [(i, a + p0, a + p1) for i, p0, p1 in _uni_cut(w, True)]
+                    else:
+                        lead = 1 if a > 0 and d[a - 1] == 0x20 else 0
+                        row += [(i, a - lead + p0, a - lead + p1) for i, p0, p1 in _bpe_cut(d[a - lead:a + len(w)])]
+                    a += len(w) + 1
+            rows.append(row)
+        self.csr = _piece_rows(rows)
+        if kind == 1:
+            block, mask = np.full((len(docs), PIECE_LEN), PIECE_PAD, np.int32), np.zeros((len(docs), PIECE_LEN), np.int32)
+            for s, r in enumerate(rows):
+                cells = [PIECE_BOS] + [p[0] for p in r][:PIECE_LEN - 2] + [PIECE_EOS]
+                block[s, :len(cells)], mask[s, :len(cells)] = cells, 1
+            self.expect = (block, mask)
+        elif kind == 3:
+            texts, self.unknown = detok_ref.decode([[p[0] for p in r] for r in rows], P_DETOK_MAP, detok_ref.CONCAT, skip=P_DETOK_SKIP)
+            off = np.zeros(len(docs) + 1, np.int64)
+            np.cumsum([len(t) for t in texts], out=off[1:])
+            self.expect = (np.frombuffer(b"".join(texts), np.uint8), off)
+        else:
+            self.expect = self.csr
+
+    def check(self, objects):
+        from latok_amd import batch
+        bpe, gpt2, uni, detok = objects
+        if self.kind == 0:
+            _same(batch.bpe_ids_utf8_batch(self.docs, bpe, PIECE_UNK), self.expect, "bpe ids")
+        elif self.kind == 1:
+            _same(batch.bpe_encode_utf8_batch(self.docs, gpt2, PIECE_LEN, PIECE_BOS, PIECE_EOS, PIECE_PAD, PIECE_UNK), self.expect, "bpe padded on GPT-2's pre-tokens")
+        elif self.kind == 2:
+            _same(batch.unigram_ids_utf8_batch(self.docs, uni, PIECE_UNK), self.expect, "unigram ids")
+        else:
+            _same(batch.decode_csr(detok, self.csr[0], self.csr[1], P_DETOK_SKIP, errors="ignore"), self.expect, "decoded rows")
+            with pytest.raises(ValueError, match="^%d ids are not in the decoder" % self.unknown):
+                batch.decode_csr(detok, self.csr[0], self.csr[1], P_DETOK_SKIP)
+
+
+@pytest.fixture(scope="module")
+def shared_pieces(gpu, shared):
+    """the shared fixture's first family's three batches under the four later families, and the objects they share"""
+    from latok_amd import batch
+    _, families = shared
+    pieces = [[Pieces(k, f.docs) for f in families[0]] for k in range(4)]
+    for f in families[0]:
+        assert f.toks == [d.split() for d in f.docs]                  # the tokens confirm_tokenisation held the spans call to
+    big = pieces[0][1]
+    assert (big.csr[1] == PIECE_UNK).any() and (np.diff(big.csr[2], axis=1) > 1).any()                      # unk pieces, merged pieces,
+    assert pieces[3][1].unknown > 0 and any((big.csr[1] == s).any() for s in P_DETOK_SKIP)                  # unknown and skipped ids,
+    assert (pieces[1][1].expect[1].sum(axis=1) == PIECE_LEN).any() and (pieces[1][2].expect[1].sum(axis=1) == 2).any()   # truncated and empty rows,
+    assert (pieces[2][1].csr[1] == PIECE_UNK).any() and len(set(pieces[2][1].csr[1].tolist())) > 100        # many Unigram words
+    with batch.BPE(P_BPE_WORDS, max_bytes=PIECE_MAX_BYTES, lead_space=True) as bpe, \
+            batch.BPE(P_GPT2_WORDS, max_bytes=PIECE_MAX_BYTES, pretokenizer="gpt2") as gpt2, \
+            batch.Unigram(P_UNI_WORDS, P_UNI_SCORES, unk_score=P_UNI_UNK_SCORE, fuse_unk=True, max_bytes=PIECE_MAX_BYTES) as uni, \
+            batch.Detokenizer(P_BPE_WORDS) as detok:
+        yield (bpe, gpt2, uni, detok), pieces
+
+
+def test_piece_objects_serve_four_contexts_with_different_families_at_once(gpu, shared_pieces):
+    """latok_bpe / latok_unigram / latok_detok: "may be used by any context of its device, concurrently".  Worker k runs family k -- 0: BPE
+    ids on the latok-token object; 1: the padded BPE block on the GPT-2 object; 2: Unigram ids; 3: the decoder on the reference BPE ids --
+    ROUNDS times, on batches of changing size; every array equals the reference."""
+    objects, pieces = shared_pieces
+
+    def job(k, gate):
+        for r in range(ROUNDS):
+            pieces[k][r % len(SIZES)].check(objects)
+
+    _run_workers([job] * 4, device=_device_of(gpu))
+    assert gpu.latok_ctx_get_current() is None
+    for k in range(4):                                               # the default context, from this thread: the same answers
+        pieces[k][2].check(objects)
+
+
+LIFE_BPE = [b"a", b"b", b"ab", b"c"]                               # ab -> ab, cd -> c and an unknown byte
+LIFE_UNI = [b"ab", uni_ref.MARKER + b"ab", b"c", b"d", uni_ref.MARKER]
+LIFE_DETOK = [b"ab", b"cd", b" "]
+
+
+DRAIN_BYTES, DRAIN_SETS = 256 << 20, 8                             # 2 GiB of device memsets: far longer in flight than the way to destroy
+
+
+def _destroy_behind_work(lib, obj, d_buf, flag):
+    """The object's destroy behind asynchronous work of the current context: DRAIN_SETS memsets of DRAIN_BYTES and then one of the pinned
+    ``flag``, all enqueued by latok_memset_dev, which returns without waiting.  "latok_*_destroy drains the current context first": when
+    the destroy has returned 0 the flag, read from pinned memory with no further wait of any kind, is set everywhere.  Returns whether
+    the flag was still clear when the destroy was called, that is, whether there was something to drain."""
+    from latok_amd import _lib
+    flag[:] = 0                                                      # (nothing is in flight: the close before this one drained)
+    for _ in range(DRAIN_SETS):
+        _lib.check(lib.latok_memset_dev(d_buf, 0, DRAIN_BYTES))
+    _lib.check(lib.latok_memset_dev(flag.ctypes.data, 0x5A, flag.nbytes))
+    pending = not flag.any()
+    h, obj.handle = obj.handle, None
+    assert getattr(lib, obj._destroy)(h) == 0
+    assert (flag == 0x5A).all(), "%s returned before the context's stream had drained" % obj._destroy
+    return pending
+
+
+def _life_round_pieces(lib, device, d_buf, flag, pending):
+    """create, one call that reads the object's device memory, info, destroy behind work in flight, a refused use, close again -- for BPE,
+    Unigram, Detokenizer"""
+    from latok_amd import batch
+    got = {}
+    bpe = batch.BPE(LIFE_BPE)
+    got["bpe"] = [a.tolist() for a in batch.bpe_ids_utf8_batch(LIFE_BLOBS, bpe)]
+    got["bpe_info"] = bpe.info()
+    uni = batch.Unigram(LIFE_UNI, [-1.0] * 5, unk_score=-11.0)
+    got["uni"] = [a.tolist() for a in batch.unigram_ids_utf8_batch(LIFE_BLOBS, uni)]
+    got["uni_info"] = uni.info()
+    detok = batch.Detokenizer(LIFE_DETOK)
+    got["detok"] = batch.decode_batch(detok, [[0, 2, 1, 7], []], errors="ignore")
+    got["detok_info"] = detok.info()
+    for obj, use in ((detok, lambda: batch.decode_batch(detok, [[0]])), (uni, lambda: batch.unigram_ids_utf8_batch(LIFE_BLOBS, uni)),
+                     (bpe, lambda: batch.bpe_ids_utf8_batch(LIFE_BLOBS, bpe))):
+        pending.append(_destroy_behind_work(lib, obj, d_buf, flag))
+        assert obj.handle is None
+        with pytest.raises(ValueError, match="must be an open latok_amd.batch"):     # the wrapper's refusal: the library never sees the handle
+            use()
+        with pytest.raises(ValueError, match="must be an open latok_amd.batch"):
+            obj.info()
+        obj.close()                                                  # the second close is no call at all
+    assert got["bpe_info"]["device"] == got["uni_info"]["device"] == got["detok_info"]["device"] == device
+    return got
+
+
+def test_the_three_piece_objects_share_that_lifecycle(gpu):
+    """BPE, Unigram and Detokenizer on the two-string batch of test_the_four_objects_share_one_lifecycle, every value written out.
+    * The destroy drains the current context: it is called behind 2 GiB of asynchronous memsets and a last one that sets a pinned flag,
+      it returns 0, and the flag is then set with no further wait (_destroy_behind_work).  In at least one of the 99 destroys the flag
+      was still clear when the destroy was called; the count is printed.
+    * Use after close is refused BY THE WRAPPER, which drops the handle: a ValueError before any library call.  The library cannot
+      refuse a freed handle, it is a plain pointer; that a closed object never reaches it is what is pinned here.
+    * The second close is harmless, the NULL handle is accepted, and 32 more rounds give the first round's values."""
+    from latok_amd import batch
+    device = _device_of(gpu)
+    flag, pending = batch.pinned_empty(64, np.uint8), []
+    d_buf = gpu.latok_dev_alloc(DRAIN_BYTES)
+    assert d_buf
+    try:
+        first = _life_round_pieces(gpu, device, d_buf, flag, pending)
+        rounds = [_life_round_pieces(gpu, device, d_buf, flag, pending) for _ in range(32)]
+    finally:
+        gpu.latok_sync()
+        gpu.latok_dev_free(d_buf)
+    print("destroys that found work in flight: %d of %d" % (sum(pending), len(pending)))
+    assert len(pending) == 99 and any(pending)
+    assert first["bpe"] == [[0, 4, 4], [2, 3, -1, 2], [[0, 2], [3, 4], [4, 5], [6, 8]]]
+    info = dict(first["bpe_info"])
+    assert info.pop("n_slots") >= 4 and info == dict(n_words=4, max_len=2, max_bytes=4096, lead_space=0, seed=0, device=device)
+    assert first["uni"] == [[0, 5, 5], [1, 4, 2, 3, 1], [[0, 2], [3, 3], [3, 4], [4, 5], [6, 8]]]
+    info = dict(first["uni_info"])
+    assert info.pop("n_slots_plain") >= 5 and info.pop("n_slots_marked") >= 1
+    assert info == dict(n_words=5, max_len=5, marker_word=4, marker=uni_ref.MARKER, unk_score=-11.0, fuse_unk=1, max_bytes=4096, seed=0, device=device)
+    assert first["detok"] == [b"ab cd", b""]
+    assert first["detok_info"] == dict(n_words=3, n_ids=3, blob_bytes=12, max_len=2, mode=0, dense=1, device=device)       # (the blob holds every word in whole 4-byte units)
+    for destroy in (gpu.latok_bpe_destroy, gpu.latok_unigram_destroy, gpu.latok_detok_destroy):
+        assert destroy(None) == 0
+    for r, got in enumerate(rounds):
+        assert got == first, r
