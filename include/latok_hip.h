@@ -634,8 +634,8 @@ int latok_bpe_padded_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_o
  * latok_bpe_create means LATOK_PRETOK_LATOK.  latok_bpe_pretokenizer reports it.  The two BPE calls dispatch on the object.
  * Known difference from tiktoken: a pre-token of more than max_bytes (at most 4096) bytes is ONE unk piece, e.g. a run of 5 000
  * spaces, which tiktoken would encode.
- * Out of scope: the cl100k_base / o200k_base patterns (case-insensitive contractions, digits in groups of three, \r\n handling: a
- * position-in-run count and a third constant; the pretok argument is there so that they can follow), add_prefix_space, special-token
+ * Out of scope here: the cl100k_base pattern is LATOK_PRETOK_CL100K, defined behind latok_bpe_pretokenizer below (case-insensitive
+ * contractions, digits in groups of three, \r\n handling); the o200k_base pattern is not there either.  Also add_prefix_space, special-token
  * strings recognised inside the text, a flow form, folding inside the call, DevicePool forms, this pre-tokenizer on the hash, ids,
  * count, term-count, WordPiece or Unigram calls (the planes make it possible; it is not wired), a Detokenizer loader for GPT-2 files. */
 #define LATOK_PRETOK_LATOK 0
@@ -647,6 +647,38 @@ int latok_bpe_create_pretok(const uint8_t* words, const int64_t* word_off /* [n_
                             const int32_t* word_ids /* may be NULL */, int max_bytes, int lead_space, int pretok, uint32_t seed,
                             latok_bpe** bpe_out);
 int latok_bpe_pretokenizer(const latok_bpe* bpe, int* pretok);
+
+/* The cl100k / Llama 3 pre-tokenizer in byte space: the pre-tokens of cl100k_base (GPT-3.5, GPT-4) and of Llama 3, and byte-level BPE
+ * behind them.  pretok = LATOK_PRETOK_CL100K (3; the value 2 is reserved and refused) in latok_pretokens_utf8_bytes_batch and
+ * latok_bpe_create_pretok, with the contracts stated above; lead_space = 1 is refused as for LATOK_PRETOK_GPT2.  The pattern is
+ *     (?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+
+ * applied to each string on its own, leftmost match first, alternatives in order.  No regex engine runs: the rule below is the
+ * definition (latok_amd/csrc/pretok.h implements it).  CHARACTERS and CLASSES are those of the GPT-2 rule above (Unicode 13.0.0;
+ * malformed characters are O).  NL is the characters CR (0x0D) and LF (0x0A), both S; SP is the byte 0x20; prev / next are the
+ * neighbouring characters of the same string; open(i) holds when i is the string's first character or prev is neither O nor SP.
+ *   1. Contractions.  An apostrophe (0x27) at i with open(i) opens a contraction if it is followed by one of s t m d re ve ll, the
+ *      ASCII letters in either case and any mix, or by U+017F (LATIN SMALL LETTER LONG S, bytes C5 BF: the only other character
+ *      that (?i) admits) -- whole characters, inside the string.  The contraction is 2 or 3 bytes; it has no start inside it and a
+ *      FORCED start at the byte behind it if the string has one.
+ *   2. L at i (not first, not forced, not inside a contraction) starts a pre-token if prev is N, or prev is NL, or prev is O and
+ *      open(prev) is false.  After L, after S that is not NL (the pre-token's first character) and after an O with open(prev)
+ *      (likewise) there is no start.
+ *   3. N at i starts a pre-token if prev is not N or d(i) % 3 == 0, d(i) = the number of N characters (not bytes) that directly
+ *      precede i in an unbroken run inside the string.
+ *   4. O at i starts a pre-token if open(i).
+ *   5. S at i, with absorbed(i) = i is NL and (prev is O or absorbed(prev)), and nl_ahead(i) = i is NL or (next is S and
+ *      nl_ahead(next)): no start if absorbed(i); else a start if i is first or prev is not S; else a start if absorbed(prev); else a
+ *      start if (prev is NL and not nl_ahead(i)) or (next exists, is not S, and i is not NL).
+ *   6. A string's end ends its last pre-token.  Nothing looks across a string boundary: d, absorbed and nl_ahead reset there.
+ * E.g. "!\n\n  \n x 1234567  \t!" is cut into "!\n\n", "  \n", " x", " ", "123", "456", "7", "  ", "\t", "!".
+ * d, absorbed and nl_ahead reach as far as a run of characters goes (and so does open(prev) across ONE malformed character of any
+ * length); everything else depends on at most 8 bytes behind a position and 6 ahead.  The device carries the four across words, tiles
+ * and workgroups by composing small records, in two launches and without waiting; latok_set_rules has no influence.
+ * The known difference from tiktoken for pre-tokens of more than max_bytes bytes stands (it matters for whitespace runs above 4096
+ * bytes).  Out of scope: the o200k_base pattern (letter case structure, \p{M}), special-token strings recognised inside the text,
+ * add_prefix_space, a flow form, folding inside the call, DevicePool forms, this pre-tokenizer on the hash, ids, count, term-count,
+ * WordPiece or Unigram calls. */
+#define LATOK_PRETOK_CL100K 3
 
 /* Unigram in byte space: the Viterbi piece ids of a SentencePiece Unigram language model (T5, mT5, ALBERT, XLNet, XLM-R, mBART,
  * Pegasus), for every token of a batch.

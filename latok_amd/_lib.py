@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("LATOK_HIP_LIB", os.path.join(_HERE, "liblatok_hip.so"
 OK, ERR_INVALID, ERR_HIP, ERR_NOT_INIT, ERR_NOMEM = 0, -1, -2, -3, -4
 DEVICE_PTRS = 1
 OUT_INT32 = 2
-PRETOK_LATOK, PRETOK_GPT2 = 0, 1     # LATOK_PRETOK_* (latok_pretokens_utf8_bytes_batch, latok_bpe_create_pretok)
+PRETOK_LATOK, PRETOK_GPT2, PRETOK_CL100K = 0, 1, 3     # LATOK_PRETOK_* (2 is reserved) (latok_pretokens_utf8_bytes_batch, latok_bpe_create_pretok)
 FOLD_LOWER, FOLD_STRIP_MARKS, FOLD_CLEAN, FOLD_CJK_SPACE = 1, 2, 4, 8     # LATOK_FOLD_* (latok_fold_utf8_bytes_batch)
 TFIDF_SMOOTH_IDF, TFIDF_SUBLINEAR_TF, TFIDF_NORM_L1, TFIDF_NORM_L2 = 1, 2, 4, 8   # LATOK_TFIDF_* (latok_tfidf_csr)
 FEATURE_COUNT = 25

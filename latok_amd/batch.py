@@ -407,7 +407,7 @@ def tokenize_utf8_batch(blobs):
 
 
 # pre-tokens: the byte ranges a model's pre-tokenizer cuts a string into (GPT-2's pattern on the device; "latok": the tokens above)
-_PRETOKENIZERS = {"latok": _lib.PRETOK_LATOK, "gpt2": _lib.PRETOK_GPT2}
+_PRETOKENIZERS = {"latok": _lib.PRETOK_LATOK, "gpt2": _lib.PRETOK_GPT2, "cl100k": _lib.PRETOK_CL100K}
 
 
 def _pretok_code(pretokenizer) -> int:
@@ -419,8 +419,8 @@ def _pretok_code(pretokenizer) -> int:
 
 def pretokens_utf8_csr(utf8, byte_off, pretokenizer="gpt2", dtype=np.int64):
     """(counts, spans[n, 2]): the [start, end) BYTE ranges of every string's pre-tokens (``latok_pretokens_utf8_bytes_batch``).
-    ``"gpt2"``: GPT-2's pattern -- every byte of a string lies in exactly one pre-token, whitespace included; ``"latok"``: exactly
-    what token_spans_utf8_bytes_csr returns."""
+    ``"gpt2"``: GPT-2's pattern -- every byte of a string lies in exactly one pre-token, whitespace included; ``"cl100k"``: the
+    cl100k_base / Llama 3 pattern, likewise; ``"latok"``: exactly what token_spans_utf8_bytes_csr returns."""
     utf8, byte_off = _csr_u8(utf8, byte_off)
     code = _pretok_code(pretokenizer)
     _out_dtype(dtype)
@@ -435,7 +435,7 @@ def pretokens_utf8_csr(utf8, byte_off, pretokenizer="gpt2", dtype=np.int64):
 
 
 def pretokenize_utf8_batch(blobs, pretokenizer="gpt2"):
-    """list[bytes] (UTF-8) -> list[list[bytes]]: every string's pre-tokens as slices of the input; with ``"gpt2"`` they join back
+    """list[bytes] (UTF-8) -> list[list[bytes]]: every string's pre-tokens as slices of the input; with ``"gpt2"`` and ``"cl100k"`` they join back
     to the string byte for byte."""
     _pretok_code(pretokenizer)
     if len(blobs) == 0:
@@ -1330,7 +1330,8 @@ class BPE(_DeviceObject):
     GPT-style vocabularies), ``seed`` the 32-bit seed of the table's hash.  This is ``tiktoken``'s model.  ``pretokenizer`` says what
     cuts the text into the tokens that are merged: ``"latok"`` (the library's tokens; runs of whitespace are not encoded) or ``"gpt2"``
     (GPT-2's regex pre-tokenizer on the device: the ids ``GPT2TokenizerFast`` gives; it carries the space itself, so ``lead_space``
-    must be off).  ``from_gpt2_files`` loads a ``vocab.json`` / ``merges.txt`` pair.  Out of scope: special-token strings inside the
+    must be off) or ``"cl100k"`` (the cl100k_base / Llama 3 pattern, likewise).  ``from_gpt2_files`` loads a ``vocab.json`` /
+    ``merges.txt`` pair, ``from_tokenizer_json`` a Hugging Face ``tokenizer.json``.  Out of scope: special-token strings inside the
     text, a ``fold=`` keyword, a flow form, ``DevicePool`` forms, decoding (a class of its own, ``Detokenizer``).  Immutable; ``len()``
     is the number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
 
@@ -1343,8 +1344,8 @@ class BPE(_DeviceObject):
         if not isinstance(lead_space, (bool, np.bool_)) and lead_space not in (0, 1):
             raise ValueError("lead_space must be a bool")
         code = _pretok_code(pretokenizer)
-        if code == _lib.PRETOK_GPT2 and lead_space:
-            raise ValueError("lead_space must be off with pretokenizer='gpt2': the space is already in the pre-token")
+        if code != _lib.PRETOK_LATOK and lead_space:
+            raise ValueError("lead_space must be off with pretokenizer=%r: the space is already in the pre-token" % pretokenizer)
         data, off, ids = _pack_words(words, ids)
         lib = _lib.ensure_init()
         h = C.c_void_p()
@@ -1438,6 +1439,92 @@ class BPE(_DeviceObject):
         vocab.json are in the ``specials`` attribute (name -> id); they are not recognised inside text."""
         words, ids, specials = cls.gpt2_word_list(vocab_json, merges_txt)
         self = cls(words, ids=ids, pretokenizer=pretokenizer, **kw)
+        self.specials = specials
+        return self
+
+    # the cl100k / Llama 3 pattern as a tokenizer.json spells it
+    CL100K_PATTERN = (r"(?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+"
+                      r"|\s+(?!\S)|\s+")
+
+    @staticmethod
+    def _tokenizer_json_pretokenizer(pre):
+        """the pre-tokenizer name of a tokenizer.json's ``pre_tokenizer`` entry: recognised, never guessed"""
+        def byte_level(p, use_regex):
+            if p.get("add_prefix_space"):
+                raise ValueError("tokenizer.json: add_prefix_space is not supported")
+            return p.get("type") == "ByteLevel" and bool(p.get("use_regex", True)) == use_regex
+
+        if isinstance(pre, dict) and pre.get("type") == "ByteLevel" and byte_level(pre, True):
+            return "gpt2"
+        if isinstance(pre, dict) and pre.get("type") == "Sequence":
+            steps = pre.get("pretokenizers")
+            if isinstance(steps, list) and len(steps) == 2 and all(isinstance(p, dict) for p in steps):
+                split, level = steps
+                if (split.get("type") == "Split" and split.get("pattern") == {"Regex": BPE.CL100K_PATTERN} and not split.get("invert")
+                        and str(split.get("behavior")).lower() == "isolated" and level.get("type") == "ByteLevel" and byte_level(level, False)):
+                    return "cl100k"
+        import json
+        raise ValueError("tokenizer.json: the pre_tokenizer is neither ByteLevel with its regex (gpt2) nor Split by the cl100k pattern "
+                         "followed by ByteLevel without it (cl100k): %s" % json.dumps(pre)[:300])
+
+    @staticmethod
+    def tokenizer_json_word_list(path):
+        """(words, ids, specials, pretokenizer) of a Hugging Face ``tokenizer.json`` whose model is byte-level BPE; needs no device.
+        ``words``, ``ids`` and ``specials`` follow ``gpt2_word_list``: the single bytes of the vocabulary in byte order, then the result of
+        every merge in the file's order (a merge is ``"left right"`` or a pair); the ``added_tokens`` and whatever else the vocabulary
+        holds are ``specials`` (content -> id), never words.  ``pretokenizer`` is ``"gpt2"`` or ``"cl100k"``, read off the file's
+        ``pre_tokenizer``; anything else there, a normalizer, ``add_prefix_space`` or another model is a ValueError that names it."""
+        import json
+        with open(path, encoding="utf-8") as f:
+            tj = json.load(f)
+        model = tj.get("model") if isinstance(tj, dict) else None
+        if not isinstance(model, dict) or model.get("type", "BPE") != "BPE" or not isinstance(model.get("vocab"), dict) or not isinstance(model.get("merges"), list):
+            raise ValueError("tokenizer.json: the model is not BPE with a vocab and merges: %r" % (model.get("type") if isinstance(model, dict) else model,))
+        for key in ("byte_fallback", "dropout", "continuing_subword_prefix", "end_of_word_suffix"):
+            if model.get(key):
+                raise ValueError("tokenizer.json: the model's %s (%r) is not supported" % (key, model[key]))
+        if tj.get("normalizer") is not None:
+            raise ValueError("tokenizer.json: a normalizer is not supported: %s" % json.dumps(tj["normalizer"])[:200])
+        pretokenizer = BPE._tokenizer_json_pretokenizer(tj.get("pre_tokenizer"))
+        vocab = model["vocab"]
+        if not all(isinstance(k, str) and isinstance(v, int) and not isinstance(v, bool) for k, v in vocab.items()):
+            raise ValueError("tokenizer.json: the vocab must be one object of token -> id")
+        dec = BPE.gpt2_byte_decoder()
+        enc = {b: ch for ch, b in dec.items()}
+        words, ids, used = [], [], set()
+        for b in range(256):
+            if enc[b] in vocab:
+                words.append(bytes([b]))
+                ids.append(vocab[enc[b]])
+                used.add(enc[b])
+        for no, merge in enumerate(model["merges"], 1):
+            pair = merge.split(" ") if isinstance(merge, str) else merge
+            if not isinstance(pair, list) or len(pair) != 2 or not all(isinstance(x, str) and x for x in pair):
+                raise ValueError("tokenizer.json: merge %d is not `left right`: %r" % (no, merge))
+            token = pair[0] + pair[1]
+            if token not in vocab:
+                raise ValueError("tokenizer.json: merge %d: the merge result %r is not in the vocab" % (no, token[:40]))
+            try:
+                words.append(bytes(dec[ch] for ch in token))
+            except KeyError:
+                raise ValueError("tokenizer.json: merge %d: %r is not written in GPT-2's byte alphabet" % (no, token[:40])) from None
+            ids.append(vocab[token])
+            used.add(token)
+        specials = {k: v for k, v in vocab.items() if k not in used}
+        for a in tj.get("added_tokens") or []:
+            if not isinstance(a, dict) or not isinstance(a.get("content"), str) or not isinstance(a.get("id"), int):
+                raise ValueError("tokenizer.json: an added token is not {id, content}: %r" % (a,))
+            specials[a["content"]] = a["id"]
+        return words, ids, specials, pretokenizer
+
+    @classmethod
+    def from_tokenizer_json(cls, path, **kw):
+        """a Hugging Face ``tokenizer.json`` with a byte-level BPE model (GPT-2's, Llama 3's, ...): ``tokenizer_json_word_list`` of it, cut
+        by the pre-tokenizer the file names (``pretokenizer=`` overrides it).  The added tokens are in the ``specials`` attribute (content
+        -> id); they are not recognised inside text."""
+        words, ids, specials, pretokenizer = cls.tokenizer_json_word_list(path)
+        kw.setdefault("pretokenizer", pretokenizer)
+        self = cls(words, ids=ids, **kw)
         self.specials = specials
         return self
 

@@ -48,7 +48,7 @@ static_assert(LATOK_TBL_SHIFT == latok::kTblShift, "table shift");
 static_assert(LATOK_TBL_STAGE1_LEN == latok::kStage1Len, "stage-1 length");
 static_assert(LATOK_TBL_NBLOCKS * (1 << LATOK_TBL_SHIFT) == latok::kStage2Len, "stage-2 length");
 static_assert(LATOK_TILE_CHARS == latok::kTile, "tile size");
-static_assert(LATOK_PRETOK_LATOK == kPretokLatok && LATOK_PRETOK_GPT2 == kPretokGpt2, "pre-tokenizer constants");
+static_assert(LATOK_PRETOK_LATOK == kPretokLatok && LATOK_PRETOK_GPT2 == kPretokGpt2 && LATOK_PRETOK_CL100K == kPretokCl100k, "pre-tokenizer constants");
 
 namespace {
 
@@ -300,7 +300,7 @@ static std::array<WsNeed, kWsNeeds> ws_needs(Workspace& w, int64_t units, const 
     const int64_t cp_rows = shape.cp_rows;
     const size_t t = (size_t)std::max<int64_t>((units + latok::kTile - 1) / latok::kTile, 1);
     const size_t words = (size_t)((units + 63) / 64), c_tiles = (words + 63) / 64;
-    return {{{&w.summ, t * 16},
+    return {{{&w.summ, t * 16},   // (also the cl100k front's carry records, 4 bytes per tile: that front never runs the tile stage)
              // one Fn64 + Hd64 pair per segment; plan_segments never makes a segment shorter than kWPB tiles (unless it is the
              // only one), so n_segs <= t / kWPB + 1
              {&w.seg_agg, (t / latok::kWPB + 2) * (sizeof(latok::Fn64) + sizeof(latok::Hd64))},
@@ -1762,6 +1762,8 @@ static int enqueue_join_tokens(Ctx& g, Workspace& w, const JoinTokens& a) {
 // pretok = LATOK_PRETOK_GPT2: the first line is ONE launch instead, k_pretok_planes (pretok_kernels.hip): a bit at every byte where a
 // pre-token of GPT-2's pattern starts, an all-zero SPACE plane (every pre-token is kept, nothing is stripped) and the per-tile string
 // index, in the same buffers.  The context's rule tables play no part in it.
+// pretok = LATOK_PRETOK_CL100K: TWO launches instead (k_pretok_cl100k_records, k_pretok_cl100k_planes), which leave the same three for
+// the cl100k / Llama 3 pattern; the carry records of the tiles between the two live in w.summ.
 static int enqueue_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* r_tokens, int* d_err, hipStream_t st, latok::TokenPlanes* out,
                                int pretok = kPretokLatok) {
     int rc;
@@ -1770,6 +1772,9 @@ static int enqueue_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* r_
     if (pretok == kPretokGpt2) {
         HIP_TRY(latok::launch_pretok_planes((const uint8_t*)b.in.p, b.total, b.row, b.n_str, (uint64_t*)w.bits.p, (uint64_t*)w.space.p,
                                             (int64_t*)w.tile_first.p, st));
+    } else if (pretok == kPretokCl100k) {
+        HIP_TRY(latok::launch_pretok_cl100k_planes((const uint8_t*)b.in.p, b.total, b.row, b.n_str, (uint32_t*)w.summ.p, (uint64_t*)w.bits.p,
+                                                   (uint64_t*)w.space.p, (int64_t*)w.tile_first.p, st));
     } else {
         Pipe p;
         p.b = b;
@@ -2469,9 +2474,10 @@ int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
  * latok_token_spans_utf8_bytes_batch itself.  LATOK_PRETOK_GPT2, one stream, every batch size the same kernels:
  *   enqueue_token_front (GPT2)     k_pretok_planes: start plane, zero SPACE plane, tile index; k_word_counts + k_scan_chained: ranks, THE total
  *   k_counts_scatter (kind 1)      per-string counts and the [start, end) records (gate: total <= capacity)
- * One wait; host pointers: the copies and a second wait.  Route 26 of latok_debug_last_route. */
-static int pretokens_gpt2(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, void* counts_out, void* spans_out,
-                          int64_t spans_cap, int64_t* n_tokens_out, int flags, void* stream) {
+ * One wait; host pointers: the copies and a second wait.  Route 26 of latok_debug_last_route.
+ * LATOK_PRETOK_CL100K: the same call with the cl100k front (two launches in place of k_pretok_planes), route 29. */
+static int pretokens_planes(int pretok, const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, void* counts_out, void* spans_out,
+                            int64_t spans_cap, int64_t* n_tokens_out, int flags, void* stream) {
     LATOK_ENTER();
     int rc = need_init(g);
     if (rc) return rc;
@@ -2492,7 +2498,7 @@ static int pretokens_gpt2(const uint8_t* utf8, const int64_t* byte_off, int64_t 
     if (!counts_out) return fail(LATOK_ERR_INVALID, "counts_out is NULL");
     if (c.empty) return zero_counts(dev, counts_out, (size_t)n_str * elt, c.st, true);   // only empty strings
     if (dev && (((uintptr_t)spans_out & (2 * elt - 1)) != 0 || ((uintptr_t)counts_out & (elt - 1)) != 0)) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    if ((rc = c.stage(g, 26, WsShape{.spans = true}, kClearPair))) return rc;
+    if ((rc = c.stage(g, pretok == kPretokCl100k ? 29 : 26, WsShape{.spans = true}, kClearPair))) return rc;
     void* d_counts = counts_out;
     void* d_spans = spans_out;
     int64_t cap = spans_out ? spans_cap : 0;
@@ -2504,7 +2510,7 @@ static int pretokens_gpt2(const uint8_t* utf8, const int64_t* byte_off, int64_t 
     }
     int* d_err = (int*)(c.p_tot + 1);
     latok::TokenPlanes t;
-    if ((rc = enqueue_token_front(g, g.ws, c.d, c.p_tot, d_err, c.st, &t, kPretokGpt2))) return rc;
+    if ((rc = enqueue_token_front(g, g.ws, c.d, c.p_tot, d_err, c.st, &t, pretok))) return rc;
     HIP_TRY(latok::launch_counts_scatter(1, o32, t, d_spans, cap, d_counts, d_err, c.st));
     HIP_TRY(hipStreamSynchronize(c.st));
     int64_t n = *n_tokens_out = c.h_tot[0];   // (the total is reported whatever the flags say)
@@ -2514,12 +2520,12 @@ static int pretokens_gpt2(const uint8_t* utf8, const int64_t* byte_off, int64_t 
 int latok_pretokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, int pretok, int64_t* counts_out,
                                      int64_t* spans_out, int64_t spans_cap, int64_t* n_tokens_out, int flags, void* stream) {
     // what needs no device is refused first
-    if (pretok != LATOK_PRETOK_LATOK && pretok != LATOK_PRETOK_GPT2)
-        return fail(LATOK_ERR_INVALID, "unknown pretok %d (LATOK_PRETOK_LATOK or LATOK_PRETOK_GPT2)", pretok);
+    if (pretok != LATOK_PRETOK_LATOK && pretok != LATOK_PRETOK_GPT2 && pretok != LATOK_PRETOK_CL100K)
+        return fail(LATOK_ERR_INVALID, "unknown pretok %d (LATOK_PRETOK_LATOK, LATOK_PRETOK_GPT2 or LATOK_PRETOK_CL100K)", pretok);
     if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
     if (pretok == LATOK_PRETOK_LATOK)
         return latok_token_spans_utf8_bytes_batch(utf8, byte_off, n_str, total_bytes, counts_out, spans_out, spans_cap, n_tokens_out, flags, stream);
-    return pretokens_gpt2(utf8, byte_off, n_str, total_bytes, counts_out, spans_out, spans_cap, n_tokens_out, flags, stream);
+    return pretokens_planes(pretok, utf8, byte_off, n_str, total_bytes, counts_out, spans_out, spans_cap, n_tokens_out, flags, stream);
 }
 
 /* vocabularies: built on the host (vocab_table.h), uploaded once, read only afterwards */
@@ -3357,8 +3363,10 @@ int latok_bpe_create_pretok(const uint8_t* words, const int64_t* word_off, int64
     *bpe_out = nullptr;
     if (max_bytes < 1 || max_bytes > kBpeMaxBytes) return fail(LATOK_ERR_INVALID, "max_bytes must be in 1 .. %d", kBpeMaxBytes);
     if (lead_space != 0 && lead_space != 1) return fail(LATOK_ERR_INVALID, "lead_space must be 0 or 1");
-    if (pretok != kPretokLatok && pretok != kPretokGpt2) return fail(LATOK_ERR_INVALID, "unknown pretok %d (LATOK_PRETOK_LATOK or LATOK_PRETOK_GPT2)", pretok);
-    if (pretok == kPretokGpt2 && lead_space) return fail(LATOK_ERR_INVALID, "lead_space must be 0 with LATOK_PRETOK_GPT2: the space is already in the pre-token");
+    if (pretok != kPretokLatok && pretok != kPretokGpt2 && pretok != kPretokCl100k)
+        return fail(LATOK_ERR_INVALID, "unknown pretok %d (LATOK_PRETOK_LATOK, LATOK_PRETOK_GPT2 or LATOK_PRETOK_CL100K)", pretok);
+    if (pretok != kPretokLatok && lead_space)
+        return fail(LATOK_ERR_INVALID, "lead_space must be 0 with %s: the space is already in the pre-token", pretok == kPretokGpt2 ? "LATOK_PRETOK_GPT2" : "LATOK_PRETOK_CL100K");
     int rc = check_word_list(words, word_off, n_words);
     if (rc || (rc = need_init(g))) return rc;
     BpeTables t;
@@ -3534,6 +3542,7 @@ struct PieceCut {
     int pretok() const { return bpe ? bpe->pretok : kPretokLatok; }
     void route_by_front() {
         if (pretok() == kPretokGpt2) { route_ids = 24; route_padded = 25; }
+        if (pretok() == kPretokCl100k) { route_ids = 27; route_padded = 28; }
     }
 };
 
@@ -4805,6 +4814,17 @@ extern "C" int latok_debug_pretok_limits(int64_t* out, int n) {
     return k;
 }
 
+/* test hook (not part of the ABI; needs no device): the constants of the cl100k pre-tokenizer's front (k_pretok_cl100k_records,
+ * k_pretok_cl100k_planes): out[0] .. out[3] as latok_debug_pretok_limits, out[4] = tile records per step of the walk.  Returns the
+ * number of values written. */
+extern "C" int latok_debug_pretok_cl100k_limits(int64_t* out, int n) {
+    const int64_t v[5] = {kPtWord, latok::kTile, latok::kPretokWaves * 64, kPtHalo, latok::kPretokWalk};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 5 ? n : 5;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
 /* test hook (not part of the ABI; needs no device): the constants of the Unigram calls: out[0] = kUniBlock (tokens per workgroup of
  * k_uni_count / k_uni_emit), out[1] = entries per workgroup of the chained scan over the piece counts, out[2] = kUniLaneBytes (the
  * longest token of the lane form), out[3] = kUniMaxBytes (the ceiling of max_bytes).  Returns the number of values written. */
@@ -4974,7 +4994,8 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
  * 20 / 21: decoding, ids back to bytes, CSR form / padded form (likewise);
  * 22 / 23: Unigram ids of UTF-8 in byte space, CSR form / padded form (likewise);
  * 24 / 25: byte-level BPE ids behind GPT-2's pre-tokenizer (an object of latok_bpe_create_pretok), CSR form / padded form (likewise);
- * 26: pre-token spans of GPT-2's pre-tokenizer (latok_pretokens_utf8_bytes_batch; LATOK_PRETOK_LATOK reports the span call's routes) */
+ * 26: pre-token spans of GPT-2's pre-tokenizer (latok_pretokens_utf8_bytes_batch; LATOK_PRETOK_LATOK reports the span call's routes);
+ * 27 / 28: byte-level BPE ids behind the cl100k pre-tokenizer, CSR form / padded form; 29: pre-token spans of the cl100k pre-tokenizer */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;

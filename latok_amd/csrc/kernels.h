@@ -426,6 +426,12 @@ hipError_t launch_bpe_emit(bool out32, const TokenText& t, const BpeTable& bt, i
 constexpr int kPretokWaves = 4;   // tiles per workgroup of k_pretok_planes
 hipError_t launch_pretok_planes(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, uint64_t* bits, uint64_t* space,
                                 int64_t* tile_first, hipStream_t st);
+// The cl100k / Llama 3 pre-tokenizer as a token front: the same planes and tile index by the same geometry, in two launches --
+// k_pretok_cl100k_records leaves one 4-byte carry record per tile in tile_rec[ceil(total / kTile)], k_pretok_cl100k_planes walks them
+// (kPretokWalk = 64 records per step) and writes the planes.  latok_debug_pretok_cl100k_limits reports the constants.
+constexpr int kPretokWalk = 64;   // tile records per walk step: one per lane
+hipError_t launch_pretok_cl100k_planes(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, uint32_t* tile_rec, uint64_t* bits,
+                                       uint64_t* space, int64_t* tile_first, hipStream_t st);
 // Unigram (Viterbi) ids (unigram_kernels.hip, unigram.h).  launch_uni_count leaves the pieces of every token in cnt[0 .. n_tok) and 0
 // in cnt[n_tok], and three words per token of at most 64 bytes in marks[] (three arrays of n_tok words: the piece starts, which of them
 // are unknown, whether the marker's piece is); the caller scans the n_tok + 1 entries into rank[]; launch_uni_emit stores ids (through

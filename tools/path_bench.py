@@ -83,6 +83,8 @@
   py_bpe_gpt2    end to end in Python on host blobs (the first min(--py-strings, 50000) strings): batch.bpe_ids_utf8_batch(blobs, bpe) of a
                   pretokenizer="gpt2" object against the `regex` package with GPT-2's pattern + the merge loop over a dict on the host;
                   equal rows asserted first; skipped with a note where `regex` is not importable
+  bytes_pretok_cl100k / bytes_bpe_cl100k / py_bpe_cl100k   the same three with LATOK_PRETOK_CL100K / pretokenizer="cl100k" (the cl100k /
+                  Llama 3 pattern: two launches for the planes); yardsticks: bytes_pretok_gpt2 and bytes_bpe_gpt2 of the same process run
   bytes_uni32 / bytes_uni_padded   latok_unigram_ids_utf8_bytes_batch (int32 indptr and spans, capacity = the piece total of a size query) /
                   latok_unigram_padded_utf8_bytes_batch ([n, 64] block with BOS / EOS); the vocabulary is the characters of the 256 single
                   bytes plus the --uni-words most frequent tokens of the first --py-strings strings of the leg's own corpus, their
@@ -453,7 +455,7 @@ def main():
                                           "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "bytes_ngrams32", "bytes_ngrams_hashed", "py_terms",
                                           "bytes_chargrams32", "bytes_chargrams_hashed", "bytes_tfidf32", "bytes_tfidf_hashed", "bytes_df_update", "csr_tfidf", "csr_df", "py_tfidf",
                                           "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join", "bytes_wp32", "bytes_wp_padded", "py_wp",
-                                          "bytes_bpe32", "bytes_bpe_padded", "py_bpe", "bytes_pretok_gpt2", "bytes_bpe_gpt2", "py_bpe_gpt2", "bytes_uni32", "bytes_uni_padded", "py_uni", "ids_detok_bpe", "ids_detok_wp", "py_detok",
+                                          "bytes_bpe32", "bytes_bpe_padded", "py_bpe", "bytes_pretok_gpt2", "bytes_bpe_gpt2", "py_bpe_gpt2", "bytes_pretok_cl100k", "bytes_bpe_cl100k", "py_bpe_cl100k", "bytes_uni32", "bytes_uni_padded", "py_uni", "ids_detok_bpe", "ids_detok_wp", "py_detok",
                                           "bytes_fold", "bytes_fold_wp", "py_fold")]
     if join_leg:
         jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64, cap * 4, cap * 4)]
@@ -721,13 +723,14 @@ def main():
 
         # GPT-2's pre-tokenizer: the span call, and the BPE call on an object of bytes_bpe32's words that brings it as its front
         pretok_gpt2_blocking = lambda: lib.latok_pretokens_utf8_bytes_batch(d_u8, d_boff, n, n8, _lib.PRETOK_GPT2, s_counts, s_items, cap, C.byref(nout), D32, None)  # noqa: E731
-        gpt2_box = []
+        pretok_cl100k_blocking = lambda: lib.latok_pretokens_utf8_bytes_batch(d_u8, d_boff, n, n8, _lib.PRETOK_CL100K, s_counts, s_items, cap, C.byref(nout), D32, None)  # noqa: E731
+        gpt2_box, cl100k_box = [], []
 
-        def corpus_bpe_gpt2():
+        def corpus_bpe_gpt2(gpt2_box=gpt2_box, pretokenizer="gpt2"):
             if not gpt2_box:
                 from latok_amd import batch
                 corpus_bpe()
-                b = batch.BPE(bpe_words, pretokenizer="gpt2", seed=SEED)
+                b = batch.BPE(bpe_words, pretokenizer=pretokenizer, seed=SEED)
                 g_indptr = lib.latok_dev_alloc((n + 1) * 4 + 64)
                 need = C.c_int64(0)
                 rc = lib.latok_bpe_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, g_indptr, None, None, 0, C.byref(need), None, D32, None)
@@ -741,6 +744,10 @@ def main():
 
         def bpe_gpt2_blocking():
             b, g_indptr, g_ids, g_spans, need = corpus_bpe_gpt2()
+            return lib.latok_bpe_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, g_indptr, g_ids, g_spans, need, C.byref(nout), None, D32, None)
+
+        def bpe_cl100k_blocking():
+            b, g_indptr, g_ids, g_spans, need = corpus_bpe_gpt2(cl100k_box, "cl100k")
             return lib.latok_bpe_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, g_indptr, g_ids, g_spans, need, C.byref(nout), None, D32, None)
 
         uni_box = []
@@ -1056,7 +1063,15 @@ def main():
             elif name == "bytes_bpe_gpt2":   # (items = pieces)
                 run(name, bpe_gpt2_blocking, lambda: n8 + csr + 4 * n + 12 * nout.value,
                     note_b + "; the front is GPT-2's pre-tokenizer: one launch for the planes, white-space pre-tokens are merged too")
-            elif name == "py_bpe_gpt2":   # host blobs in, the CSR arrays out, both routes in this process
+            elif name == "bytes_pretok_cl100k":   # (items = pre-tokens, white space included)
+                run(name, pretok_cl100k_blocking, lambda: 2 * n8 + csr + 4 * n + 8 * nout.value,
+                    "UTF-8 bytes + 8 B/string read TWICE by two launches (carry records of 4 B/tile between them); 2 x 1 bit/byte planes written; "
+                    "4 B/string + 8 B/pre-token written (byte ranges, LATOK_OUT_INT32)")
+            elif name == "bytes_bpe_cl100k":   # (items = pieces)
+                run(name, bpe_cl100k_blocking, lambda: 2 * n8 + csr + 4 * n + 12 * nout.value,
+                    note_b + "; the front is the cl100k pre-tokenizer: two launches for the planes, white-space pre-tokens are merged too")
+            elif name in ("py_bpe_gpt2", "py_bpe_cl100k"):   # host blobs in, the CSR arrays out, both routes in this process
+                pretokenizer = name[len("py_bpe_"):]
                 from latok_amd import batch
                 try:
                     import regex
@@ -1066,7 +1081,8 @@ def main():
                 blobs, blob, toks = bpe_sample_tokens(False)
                 blobs = blobs[:50000]
                 blob = b"".join(blobs)
-                pat = regex.compile(r"'s|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+")
+                pat = regex.compile(r"'s|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+" if pretokenizer == "gpt2"
+                                    else batch.BPE.CL100K_PATTERN)
                 words = bpe_train([b" " + t for t in toks[::2]] + toks[1::2], args.bpe_merges)
                 d = {}
                 for i, w in enumerate(words):
@@ -1102,8 +1118,8 @@ def main():
                         indptr.append(len(ids))
                     return np.array(indptr, np.int64), np.array(ids, np.int32)
 
-                with batch.BPE(words, pretokenizer="gpt2", seed=SEED) as b:
-                    routes = (("py_bpe_gpt2_ids_utf8_batch", lambda: batch.bpe_ids_utf8_batch(blobs, b)[:2]),
+                with batch.BPE(words, pretokenizer=pretokenizer, seed=SEED) as b:
+                    routes = (("py_bpe_%s_ids_utf8_batch" % pretokenizer, lambda: batch.bpe_ids_utf8_batch(blobs, b)[:2]),
                               ("py_regex_findall_then_bpe_loop", on_host_gpt2))
                     assert all(np.array_equal(x, y) for x, y in zip(routes[0][1](), routes[1][1]()))
                     for r in range(args.repeat):
