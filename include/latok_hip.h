@@ -680,6 +680,54 @@ int latok_bpe_pretokenizer(const latok_bpe* bpe, int* pretok);
  * WordPiece or Unigram calls. */
 #define LATOK_PRETOK_CL100K 3
 
+/* SentencePiece BPE in byte space: the ids of a SentencePiece model of type BPE (the tokenizer.model of Llama 2, Code Llama, Mistral 7B,
+ * Mixtral, TinyLlama, Yi), with byte fallback.  It differs from the byte-level BPE above in four ways: it merges CHARACTERS, not bytes;
+ * it has NO whole-token shortcut; every U+0020 becomes the marker U+2581 (bytes E2 96 81), one more marker stands in front of the string,
+ * and merges run through runs of markers; a character that no word covers becomes one piece per byte.  The rule below is the definition
+ * (latok_amd/csrc/spbpe.h implements it; tests/helpers/spbpe_ref.py restates it).
+ *   CHARACTERS  as everywhere: a character starts at a range's first byte and at every later byte b with (b & 0xC0) != 0x80.  The rule
+ *               is total on malformed bytes.
+ *   SPACE-LIKE  a character whose bytes are exactly 20, or exactly E2 96 81.
+ *   SEGMENTS    LATOK_PRETOK_SPM (5; the values 2 and 4 are reserved and refused) in latok_pretokens_utf8_bytes_batch: a segment starts at
+ *               a string's first byte, and at every space-like character whose previous character in the same string is not space-like.
+ *               Every byte lies in exactly one segment and nothing is dropped; tabs and newlines are ordinary characters.  So a segment is
+ *               a (possibly empty) LEAD RUN of space-like characters followed by characters that are not.  A start bit depends on 3 bytes
+ *               behind it and 3 ahead: no carry, one launch.  An empty string has no segment.  Route 32.
+ *   VIRTUAL TEXT of a segment: one E2 96 81 if the object has add_dummy_prefix and the segment is its string's first; then one E2 96 81
+ *               per character of the lead run; then the remaining bytes verbatim.  Its VIRTUAL LENGTH is in bytes.
+ *   THE CUT     1. virtual length > max_bytes (1 .. 4096): ONE piece (unk_id, a, e) -- the known difference that the other BPE calls
+ *               document.  2. The parts are the CHARACTERS of the virtual text.  There is no whole-segment shortcut: a word that no
+ *               sequence of merges reaches is never produced.  3. Repeat: among all adjacent parts whose concatenation is a word, the pair
+ *               with the lowest rank (position in the word list), of equal ranks the leftmost, becomes one part; stop when no adjacent pair
+ *               is a word.  4. The parts in order: a part that is a word is a piece with its id; a part that is no word is a single
+ *               character: with byte_ids one piece per byte b of that character, byte_ids[b]; without byte_ids one unk_id piece, and with
+ *               fuse_unk = 1 every maximal run of neighbouring unknown parts of a segment is ONE piece.
+ *   SPANS       string-relative bytes.  A virtual character maps to a real range: the dummy marker to the empty range at the segment's
+ *               start, the j-th lead marker to the bytes of the j-th lead character (1 or 3), any other character to its own bytes.  A
+ *               piece reports from the start of its first character's range to the end of its last character's; every byte piece
+ *               reports its character's range; a fused unk the union of its parts' ranges.
+ *   PARITY      for well-formed UTF-8 and a model that passes the loader's checks the ids equal SentencePieceProcessor.encode, but for
+ *               segments over max_bytes and for distinct words with exactly equal scores (list order here, position in SentencePiece;
+ *               trained models have no such ties among merge results).  Malformed input follows the rule above, where SentencePiece
+ *               would substitute U+FFFD.
+ * Cutting a string into independent segments is exact as long as no word holds E2 96 81 directly behind a character that is not
+ * E2 96 81 (true of every model trained with SentencePiece's default split_by_whitespace); latok_bpe_create_spm checks it.
+ * latok_bpe_create_spm makes a latok_bpe object of this kind: words / word_off / word_ids as latok_bpe_create takes them (rank = position),
+ * byte_ids[256] or NULL (no byte fallback), add_dummy_prefix and fuse_unk 0 or 1.  It refuses, before any device work, what
+ * latok_bpe_create refuses, a flag outside 0 / 1 and a word that breaks the condition above (the message names its position).
+ * latok_bpe_create_pretok goes on refusing 5: byte merges over these segments mean nothing.  latok_bpe_pretokenizer reports 5 for such
+ * an object, latok_bpe_info lead_space = 0; latok_bpe_spm_info reports the three properties and returns LATOK_ERR_INVALID for an object
+ * of another kind.  latok_bpe_ids_utf8_bytes_batch and latok_bpe_padded_utf8_bytes_batch dispatch on the object with their contracts
+ * unchanged (routes 30 / 31); a batch of this kind has at most 3 * (total_bytes + n_str) pieces.  Objects of latok_bpe_create and
+ * latok_bpe_create_pretok take exactly the kernels they took before.
+ * Out of scope: NFKC and other normalizers, USER_DEFINED pieces, a decoder mode that turns the marker back into spaces, a BOS-only
+ * padded layout, special-token strings inside the text, a flow form, folding inside the call, DevicePool forms. */
+#define LATOK_PRETOK_SPM 5
+int latok_bpe_create_spm(const uint8_t* words, const int64_t* word_off /* [n_words+1], host */, int64_t n_words,
+                         const int32_t* word_ids /* may be NULL */, const int32_t* byte_ids /* [256], NULL: no byte fallback */,
+                         int add_dummy_prefix, int fuse_unk, int max_bytes, uint32_t seed, latok_bpe** bpe_out);
+int latok_bpe_spm_info(const latok_bpe* bpe, int* byte_fallback, int* add_dummy_prefix, int* fuse_unk);
+
 /* Unigram in byte space: the Viterbi piece ids of a SentencePiece Unigram language model (T5, mT5, ALBERT, XLNet, XLM-R, mBART,
  * Pegasus), for every token of a batch.
  * THE VOCABULARY.  A Unigram vocabulary is an ordered list of byte strings w_0 .. w_(V-1) in the words / word_off layout of

@@ -14,6 +14,7 @@ OK, ERR_INVALID, ERR_HIP, ERR_NOT_INIT, ERR_NOMEM = 0, -1, -2, -3, -4
 DEVICE_PTRS = 1
 OUT_INT32 = 2
 PRETOK_LATOK, PRETOK_GPT2, PRETOK_CL100K = 0, 1, 3     # LATOK_PRETOK_* (2 is reserved) (latok_pretokens_utf8_bytes_batch, latok_bpe_create_pretok)
+PRETOK_SPM = 5                                          # SentencePiece's segments (4 is reserved); its BPE objects come from latok_bpe_create_spm
 FOLD_LOWER, FOLD_STRIP_MARKS, FOLD_CLEAN, FOLD_CJK_SPACE = 1, 2, 4, 8     # LATOK_FOLD_* (latok_fold_utf8_bytes_batch)
 TFIDF_SMOOTH_IDF, TFIDF_SUBLINEAR_TF, TFIDF_NORM_L1, TFIDF_NORM_L2 = 1, 2, 4, 8   # LATOK_TFIDF_* (latok_tfidf_csr)
 FEATURE_COUNT = 25
@@ -96,6 +97,8 @@ SIGNATURES = {
     "latok_pretokens_utf8_bytes_batch": (ci, [vp, vp, i64, i64, ci, vp, vp, i64, C.POINTER(i64), ci, vp]),
     "latok_bpe_create_pretok": (ci, [vp, vp, i64, vp, ci, ci, ci, C.c_uint32, C.POINTER(vp)]),
     "latok_bpe_pretokenizer": (ci, [vp, C.POINTER(ci)]),
+    "latok_bpe_create_spm": (ci, [vp, vp, i64, vp, vp, ci, ci, ci, C.c_uint32, C.POINTER(vp)]),
+    "latok_bpe_spm_info": (ci, [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]),
     "latok_unigram_create": (ci, [vp, vp, i64, vp, vp, vp, ci, C.c_float, ci, ci, C.c_uint32, C.POINTER(vp)]),
     "latok_unigram_destroy": (ci, [vp]),
     "latok_unigram_info": (ci, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), vp, C.POINTER(ci),

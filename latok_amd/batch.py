@@ -407,7 +407,7 @@ def tokenize_utf8_batch(blobs):
 
 
 # pre-tokens: the byte ranges a model's pre-tokenizer cuts a string into (GPT-2's pattern on the device; "latok": the tokens above)
-_PRETOKENIZERS = {"latok": _lib.PRETOK_LATOK, "gpt2": _lib.PRETOK_GPT2, "cl100k": _lib.PRETOK_CL100K}
+_PRETOKENIZERS = {"latok": _lib.PRETOK_LATOK, "gpt2": _lib.PRETOK_GPT2, "cl100k": _lib.PRETOK_CL100K, "spm": _lib.PRETOK_SPM}
 
 
 def _pretok_code(pretokenizer) -> int:
@@ -420,7 +420,8 @@ def _pretok_code(pretokenizer) -> int:
 def pretokens_utf8_csr(utf8, byte_off, pretokenizer="gpt2", dtype=np.int64):
     """(counts, spans[n, 2]): the [start, end) BYTE ranges of every string's pre-tokens (``latok_pretokens_utf8_bytes_batch``).
     ``"gpt2"``: GPT-2's pattern -- every byte of a string lies in exactly one pre-token, whitespace included; ``"cl100k"``: the
-    cl100k_base / Llama 3 pattern, likewise; ``"latok"``: exactly what token_spans_utf8_bytes_csr returns."""
+    cl100k_base / Llama 3 pattern, likewise; ``"spm"``: SentencePiece's segments -- a lead run of spaces and U+2581, then what follows up
+    to the next space, nothing dropped; ``"latok"``: exactly what token_spans_utf8_bytes_csr returns."""
     utf8, byte_off = _csr_u8(utf8, byte_off)
     code = _pretok_code(pretokenizer)
     _out_dtype(dtype)
@@ -435,8 +436,8 @@ def pretokens_utf8_csr(utf8, byte_off, pretokenizer="gpt2", dtype=np.int64):
 
 
 def pretokenize_utf8_batch(blobs, pretokenizer="gpt2"):
-    """list[bytes] (UTF-8) -> list[list[bytes]]: every string's pre-tokens as slices of the input; with ``"gpt2"`` and ``"cl100k"`` they join back
-    to the string byte for byte."""
+    """list[bytes] (UTF-8) -> list[list[bytes]]: every string's pre-tokens as slices of the input; with ``"gpt2"``, ``"cl100k"`` and ``"spm"`` they join
+    back to the string byte for byte."""
     _pretok_code(pretokenizer)
     if len(blobs) == 0:
         return []
@@ -1331,7 +1332,9 @@ class BPE(_DeviceObject):
     cuts the text into the tokens that are merged: ``"latok"`` (the library's tokens; runs of whitespace are not encoded) or ``"gpt2"``
     (GPT-2's regex pre-tokenizer on the device: the ids ``GPT2TokenizerFast`` gives; it carries the space itself, so ``lead_space``
     must be off) or ``"cl100k"`` (the cl100k_base / Llama 3 pattern, likewise).  ``from_gpt2_files`` loads a ``vocab.json`` /
-    ``merges.txt`` pair, ``from_tokenizer_json`` a Hugging Face ``tokenizer.json``.  Out of scope: special-token strings inside the
+    ``merges.txt`` pair, ``from_tokenizer_json`` a Hugging Face ``tokenizer.json``.  SentencePiece BPE (Llama 2, Mistral: characters
+    merged, U+2581 for spaces, byte fallback) is another kind of object of the same class: ``BPE.sentencepiece``,
+    ``from_sentencepiece_model`` (a ``tokenizer.model``), ``from_spm_tokenizer_json``.  Out of scope: special-token strings inside the
     text, a ``fold=`` keyword, a flow form, ``DevicePool`` forms, decoding (a class of its own, ``Detokenizer``).  Immutable; ``len()``
     is the number of words given.  Freed by ``close()``, on leaving a ``with`` block, or with the object."""
 
@@ -1344,6 +1347,9 @@ class BPE(_DeviceObject):
         if not isinstance(lead_space, (bool, np.bool_)) and lead_space not in (0, 1):
             raise ValueError("lead_space must be a bool")
         code = _pretok_code(pretokenizer)
+        if code == _lib.PRETOK_SPM:
+            raise ValueError("pretokenizer='spm' belongs to SentencePiece BPE objects: use BPE.sentencepiece, from_sentencepiece_model or "
+                             "from_spm_tokenizer_json (byte merges over these segments mean nothing)")
         if code != _lib.PRETOK_LATOK and lead_space:
             raise ValueError("lead_space must be off with pretokenizer=%r: the space is already in the pre-token" % pretokenizer)
         data, off, ids = _pack_words(words, ids)
@@ -1527,6 +1533,263 @@ class BPE(_DeviceObject):
         self = cls(words, ids=ids, **kw)
         self.specials = specials
         return self
+
+    # ---- SentencePiece BPE (latok_bpe_create_spm): Llama 2, Mistral, ... -----------------------------------------------------------------
+    @classmethod
+    def sentencepiece(cls, words, ids=None, byte_ids=None, add_dummy_prefix=True, fuse_unk=True, max_bytes=4096, seed=0):
+        """A SentencePiece BPE vocabulary on the device (``latok_bpe_create_spm``): ``words`` in RANK order (characters and merge results;
+        the marker U+2581 stands for a space), ``ids`` as above, ``byte_ids`` 256 int32 ids of the byte pieces or None (no byte
+        fallback: an unknown character is one ``unk_id`` piece, a run of them ONE with ``fuse_unk``), ``add_dummy_prefix``: one marker
+        in front of every string.  The text is cut into SentencePiece's segments (``pretokenize_batch(texts, "spm")``), characters are
+        merged, there is no whole-segment shortcut.  ``bpe_ids_*`` and ``bpe_encode_*`` take the object as they take any other."""
+        seed = _seed32(seed)
+        if not isinstance(max_bytes, (int, np.integer)) or isinstance(max_bytes, bool) or not 1 <= int(max_bytes) <= 4096:
+            raise ValueError("max_bytes must be an int in 1 .. 4096")
+        for name, flag in (("add_dummy_prefix", add_dummy_prefix), ("fuse_unk", fuse_unk)):
+            if not isinstance(flag, (bool, np.bool_)) and flag not in (0, 1):
+                raise ValueError("%s must be a bool" % name)
+        if byte_ids is not None:
+            byte_ids = _int32_each(byte_ids, 256, "byte_ids", "byte")
+        data, off, ids = _pack_words(words, ids)
+        lib = _lib.ensure_init()
+        h = C.c_void_p()
+        _lib.check(lib.latok_bpe_create_spm(_ptr(data) if data.size else None, _ptr(off), off.size - 1, _ptr(ids) if ids is not None else None,
+                                            _ptr(byte_ids) if byte_ids is not None else None, 1 if add_dummy_prefix else 0, 1 if fuse_unk else 0,
+                                            int(max_bytes), seed, C.byref(h)))
+        self = cls.__new__(cls)
+        self._lib, self.handle, self.seed, self._n = lib, h, seed, off.size - 1
+        self.max_bytes, self.lead_space, self.pretokenizer, self.specials = int(max_bytes), False, "spm", {}
+        self.byte_fallback, self.add_dummy_prefix, self.fuse_unk = byte_ids is not None, bool(add_dummy_prefix), bool(fuse_unk)
+        return self
+
+    @staticmethod
+    def _proto_fields(buf):
+        """the fields of one protobuf message: (number, wire type, value) -- varint and fixed values as ints, length-delimited as bytes"""
+        i, n = 0, len(buf)
+
+        def varint():
+            nonlocal i
+            v = shift = 0
+            while True:
+                if i >= n or shift > 63:
+                    raise ValueError("not a SentencePiece model: a varint runs out of the message")
+                b = buf[i]
+                i += 1
+                v |= (b & 0x7F) << shift
+                shift += 7
+                if not b & 0x80:
+                    return v
+
+        while i < n:
+            key = varint()
+            no, wt = key >> 3, key & 7
+            if wt == 0:
+                yield no, wt, varint()
+            elif wt in (1, 5):
+                size = 8 if wt == 1 else 4
+                if i + size > n:
+                    raise ValueError("not a SentencePiece model: a fixed field runs out of the message")
+                yield no, wt, int.from_bytes(buf[i:i + size], "little")
+                i += size
+            elif wt == 2:
+                size = varint()
+                if i + size > n:
+                    raise ValueError("not a SentencePiece model: a field runs out of the message")
+                yield no, wt, bytes(buf[i:i + size])
+                i += size
+            else:
+                raise ValueError("not a SentencePiece model: wire type %d" % wt)
+
+    @staticmethod
+    def read_sentencepiece_model(path):
+        """what a ``tokenizer.model`` (a serialized ``ModelProto``) says, by a reader of the wire format of its own -- no ``protobuf``, no
+        ``sentencepiece``: dict of ``pieces`` [(bytes, score, type)] in id order, ``model_type``, ``byte_fallback``,
+        ``treat_whitespace_as_suffix``, ``normalizer_name``, ``charsmap`` (bytes), ``add_dummy_prefix``, ``remove_extra_whitespaces``,
+        ``escape_whitespaces``.  Field numbers as in sentencepiece_model.proto; absent fields take the proto's defaults."""
+        import struct
+        with open(path, "rb") as f:
+            buf = f.read()
+        m = dict(pieces=[], model_type=1, byte_fallback=False, treat_whitespace_as_suffix=False, normalizer_name="", charsmap=b"",
+                 add_dummy_prefix=True, remove_extra_whitespaces=True, escape_whitespaces=True)
+        for no, wt, v in BPE._proto_fields(buf):
+            if no == 1 and wt == 2:                      # repeated SentencePiece pieces = 1
+                piece, score, kind = b"", 0.0, 1
+                for n2, w2, v2 in BPE._proto_fields(v):
+                    if n2 == 1 and w2 == 2:
+                        piece = v2
+                    elif n2 == 2 and w2 == 5:
+                        score = struct.unpack("<f", v2.to_bytes(4, "little"))[0]
+                    elif n2 == 3 and w2 == 0:
+                        kind = v2
+                m["pieces"].append((piece, score, kind))
+            elif no == 2 and wt == 2:                    # TrainerSpec trainer_spec = 2
+                for n2, w2, v2 in BPE._proto_fields(v):
+                    if n2 == 3 and w2 == 0:
+                        m["model_type"] = v2
+                    elif n2 == 35 and w2 == 0:
+                        m["byte_fallback"] = bool(v2)
+                    elif n2 == 24 and w2 == 0:
+                        m["treat_whitespace_as_suffix"] = bool(v2)
+            elif no == 3 and wt == 2:                    # NormalizerSpec normalizer_spec = 3
+                for n2, w2, v2 in BPE._proto_fields(v):
+                    if n2 == 1 and w2 == 2:
+                        m["normalizer_name"] = v2.decode("utf-8", "replace")
+                    elif n2 == 2 and w2 == 2:
+                        m["charsmap"] = v2
+                    elif n2 == 3 and w2 == 0:
+                        m["add_dummy_prefix"] = bool(v2)
+                    elif n2 == 4 and w2 == 0:
+                        m["remove_extra_whitespaces"] = bool(v2)
+                    elif n2 == 5 and w2 == 0:
+                        m["escape_whitespaces"] = bool(v2)
+        if not m["pieces"]:
+            raise ValueError("not a SentencePiece model: it holds no piece")
+        return m
+
+    @staticmethod
+    def sentencepiece_word_list(path):
+        """(words, ids, byte_ids, specials, add_dummy_prefix) of a SentencePiece ``tokenizer.model`` of type BPE; needs no device.
+        ``words``: the NORMAL pieces sorted by score descending, stable in id order, ``ids`` theirs in the file; ``byte_ids``: the ids
+        of the 256 BYTE pieces, or None without ``byte_fallback``; ``specials``: the CONTROL and UNKNOWN pieces (name -> id).  A
+        ValueError names whatever the device rule does not cover: another model type, a normalizer other than ``identity`` with an empty
+        charsmap, ``remove_extra_whitespaces``, no ``escape_whitespaces``, whitespace as suffix, USER_DEFINED or UNUSED pieces, fewer
+        than 256 byte pieces under ``byte_fallback``."""
+        m = BPE.read_sentencepiece_model(path)
+        if m["model_type"] != 2:
+            raise ValueError("SentencePiece model: model_type is %s, not BPE" % {1: "UNIGRAM", 3: "WORD", 4: "CHAR"}.get(m["model_type"], m["model_type"]))
+        if m["normalizer_name"] != "identity" or m["charsmap"]:
+            raise ValueError("SentencePiece model: the normalizer is %r with a charsmap of %d bytes; only `identity` with an empty charsmap is "
+                             "supported" % (m["normalizer_name"], len(m["charsmap"])))
+        if m["remove_extra_whitespaces"]:
+            raise ValueError("SentencePiece model: remove_extra_whitespaces is not supported")
+        if not m["escape_whitespaces"]:
+            raise ValueError("SentencePiece model: escape_whitespaces must be on")
+        if m["treat_whitespace_as_suffix"]:
+            raise ValueError("SentencePiece model: treat_whitespace_as_suffix is not supported")
+        normal, specials, by_byte = [], {}, {}
+        for pid, (piece, score, kind) in enumerate(m["pieces"]):
+            if kind == 1:
+                normal.append((piece, score, pid))
+            elif kind in (2, 3):
+                specials[piece.decode("utf-8", "surrogateescape")] = pid
+            elif kind == 6:
+                name = piece.decode("ascii", "replace")
+                if len(name) != 6 or not name.startswith("<0x") or not name.endswith(">"):
+                    raise ValueError("SentencePiece model: the BYTE piece %r is not <0xXX>" % name)
+                by_byte.setdefault(int(name[3:5], 16), pid)
+            else:
+                raise ValueError("SentencePiece model: piece %d (%r) is %s; such pieces are not supported"
+                                 % (pid, piece[:40], {4: "USER_DEFINED", 5: "UNUSED"}.get(kind, "of type %d" % kind)))
+        byte_ids = None
+        if m["byte_fallback"]:
+            if len(by_byte) != 256:
+                raise ValueError("SentencePiece model: byte_fallback with %d of the 256 byte pieces" % len(by_byte))
+            byte_ids = [by_byte[b] for b in range(256)]
+        normal.sort(key=lambda t: -t[1])   # (stable: equal scores stay in id order)
+        return [t[0] for t in normal], [t[2] for t in normal], byte_ids, specials, m["add_dummy_prefix"]
+
+    @classmethod
+    def from_sentencepiece_model(cls, path, **kw):
+        """a SentencePiece ``tokenizer.model`` of type BPE (Llama 2, Code Llama, Mistral 7B, Mixtral, TinyLlama, Yi):
+        ``sentencepiece_word_list`` of it as a ``BPE.sentencepiece`` object.  The CONTROL and UNKNOWN pieces are in the ``specials``
+        attribute (name -> id) and the unknown piece's id in ``unk_id``; they are not recognised inside text."""
+        words, ids, byte_ids, specials, dummy = cls.sentencepiece_word_list(path)
+        kw.setdefault("add_dummy_prefix", dummy)
+        self = cls.sentencepiece(words, ids=ids, byte_ids=byte_ids, **kw)
+        self.specials = specials
+        self.unk_id = specials.get("<unk>", -1)
+        return self
+
+    @staticmethod
+    def spm_tokenizer_json_word_list(path):
+        """(words, ids, byte_ids, specials, add_dummy_prefix) of a Hugging Face ``tokenizer.json`` that spells a SentencePiece BPE model;
+        needs no device.  Accepted: model ``BPE`` with ``byte_fallback: true``; normalizer exactly ``Sequence[Prepend("▁"),
+        Replace(" " -> "▁")]`` or the ``Replace`` alone (no dummy prefix); ``pre_tokenizer`` null.  ``words``: the merge results in
+        merge order, the first producer winning, then every remaining entry of the vocabulary that is neither ``<0xXX>`` nor an added
+        token.  Everything else is a ValueError."""
+        import json
+        with open(path, encoding="utf-8") as f:
+            tj = json.load(f)
+        model = tj.get("model") if isinstance(tj, dict) else None
+        if not isinstance(model, dict) or model.get("type", "BPE") != "BPE" or not isinstance(model.get("vocab"), dict) or not isinstance(model.get("merges"), list):
+            raise ValueError("tokenizer.json: the model is not BPE with a vocab and merges: %r" % (model.get("type") if isinstance(model, dict) else model,))
+        if not model.get("byte_fallback"):
+            raise ValueError("tokenizer.json: the model has no byte_fallback: not a SentencePiece BPE file (see from_tokenizer_json)")
+        for key in ("dropout", "continuing_subword_prefix", "end_of_word_suffix", "ignore_merges"):
+            if model.get(key):
+                raise ValueError("tokenizer.json: the model's %s (%r) is not supported" % (key, model[key]))
+        if tj.get("pre_tokenizer") is not None:
+            raise ValueError("tokenizer.json: a pre_tokenizer is not supported here: %s" % json.dumps(tj["pre_tokenizer"])[:200])
+        mark = "▁"
+
+        def is_replace(p):
+            return isinstance(p, dict) and p.get("type") == "Replace" and p.get("pattern") == {"String": " "} and p.get("content") == mark
+
+        norm = tj.get("normalizer")
+        if is_replace(norm):
+            dummy = False
+        elif (isinstance(norm, dict) and norm.get("type") == "Sequence" and isinstance(norm.get("normalizers"), list) and len(norm["normalizers"]) == 2
+              and isinstance(norm["normalizers"][0], dict) and norm["normalizers"][0].get("type") == "Prepend"
+              and norm["normalizers"][0].get("prepend") == mark and is_replace(norm["normalizers"][1])):
+            dummy = True
+        else:
+            raise ValueError("tokenizer.json: the normalizer is neither Sequence[Prepend(U+2581), Replace(' ' -> U+2581)] nor that Replace "
+                             "alone: %s" % json.dumps(norm)[:300])
+        vocab = model["vocab"]
+        if not all(isinstance(k, str) and isinstance(v, int) and not isinstance(v, bool) for k, v in vocab.items()):
+            raise ValueError("tokenizer.json: the vocab must be one object of token -> id")
+        specials = {}
+        for a in tj.get("added_tokens") or []:
+            if not isinstance(a, dict) or not isinstance(a.get("content"), str) or not isinstance(a.get("id"), int):
+                raise ValueError("tokenizer.json: an added token is not {id, content}: %r" % (a,))
+            specials[a["content"]] = a["id"]
+        if isinstance(model.get("unk_token"), str) and model["unk_token"] in vocab:
+            specials.setdefault(model["unk_token"], vocab[model["unk_token"]])
+        words, ids, used = [], [], set()
+        for no, merge in enumerate(model["merges"], 1):
+            pair = merge.split(" ") if isinstance(merge, str) else merge
+            if not isinstance(pair, list) or len(pair) != 2 or not all(isinstance(x, str) and x for x in pair):
+                raise ValueError("tokenizer.json: merge %d is not `left right`: %r" % (no, merge))
+            token = pair[0] + pair[1]
+            if token not in vocab:
+                raise ValueError("tokenizer.json: merge %d: the merge result %r is not in the vocab" % (no, token[:40]))
+            if token in used:
+                continue                             # (the first producer wins)
+            used.add(token)
+            words.append(token.encode("utf-8", "surrogatepass"))
+            ids.append(vocab[token])
+        by_byte = {}
+        for token, pid in vocab.items():
+            if len(token) == 6 and token.startswith("<0x") and token.endswith(">"):
+                try:
+                    by_byte.setdefault(int(token[3:5], 16), pid)
+                    continue
+                except ValueError:
+                    pass
+            if token in used or token in specials:
+                continue
+            words.append(token.encode("utf-8", "surrogatepass"))
+            ids.append(pid)
+        if len(by_byte) != 256:
+            raise ValueError("tokenizer.json: byte_fallback with %d of the 256 <0xXX> entries" % len(by_byte))
+        return words, ids, [by_byte[b] for b in range(256)], specials, dummy
+
+    @classmethod
+    def from_spm_tokenizer_json(cls, path, **kw):
+        """the Hugging Face ``tokenizer.json`` of a SentencePiece BPE model (Llama 2's, Mistral's): ``spm_tokenizer_json_word_list`` of it as
+        a ``BPE.sentencepiece`` object; ``specials`` and ``unk_id`` as ``from_sentencepiece_model`` leaves them."""
+        words, ids, byte_ids, specials, dummy = cls.spm_tokenizer_json_word_list(path)
+        kw.setdefault("add_dummy_prefix", dummy)
+        self = cls.sentencepiece(words, ids=ids, byte_ids=byte_ids, **kw)
+        self.specials = specials
+        self.unk_id = specials.get("<unk>", -1)
+        return self
+
+    def spm_info(self):
+        """dict of what ``latok_bpe_spm_info`` reports (a SentencePiece object only)"""
+        v = [C.c_int(0) for _ in range(3)]
+        _lib.check(self._lib.latok_bpe_spm_info(self._open(), *[C.byref(x) for x in v]))
+        return dict(byte_fallback=v[0].value, add_dummy_prefix=v[1].value, fuse_unk=v[2].value)
 
     def info(self):
         """dict of what ``latok_bpe_info`` reports"""

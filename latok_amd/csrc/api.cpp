@@ -40,6 +40,7 @@
 #include "bpe.h"
 #include "unigram.h"
 #include "pretok.h"
+#include "spbpe.h"
 #include "fold_map.h"
 #include "fold_tables.inc"
 #include "tfidf_weight.h"
@@ -48,7 +49,8 @@ static_assert(LATOK_TBL_SHIFT == latok::kTblShift, "table shift");
 static_assert(LATOK_TBL_STAGE1_LEN == latok::kStage1Len, "stage-1 length");
 static_assert(LATOK_TBL_NBLOCKS * (1 << LATOK_TBL_SHIFT) == latok::kStage2Len, "stage-2 length");
 static_assert(LATOK_TILE_CHARS == latok::kTile, "tile size");
-static_assert(LATOK_PRETOK_LATOK == kPretokLatok && LATOK_PRETOK_GPT2 == kPretokGpt2 && LATOK_PRETOK_CL100K == kPretokCl100k, "pre-tokenizer constants");
+static_assert(LATOK_PRETOK_LATOK == kPretokLatok && LATOK_PRETOK_GPT2 == kPretokGpt2 && LATOK_PRETOK_CL100K == kPretokCl100k && LATOK_PRETOK_SPM == kPretokSpm,
+              "pre-tokenizer constants");
 
 namespace {
 
@@ -1764,6 +1766,7 @@ static int enqueue_join_tokens(Ctx& g, Workspace& w, const JoinTokens& a) {
 // index, in the same buffers.  The context's rule tables play no part in it.
 // pretok = LATOK_PRETOK_CL100K: TWO launches instead (k_pretok_cl100k_records, k_pretok_cl100k_planes), which leave the same three for
 // the cl100k / Llama 3 pattern; the carry records of the tiles between the two live in w.summ.
+// pretok = LATOK_PRETOK_SPM: ONE launch, k_pretok_spm_planes: SentencePiece's segments (spbpe.h) by k_pretok_planes' geometry.
 static int enqueue_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* r_tokens, int* d_err, hipStream_t st, latok::TokenPlanes* out,
                                int pretok = kPretokLatok) {
     int rc;
@@ -1772,6 +1775,9 @@ static int enqueue_token_front(Ctx& g, Workspace& w, const Batch& b, int64_t* r_
     if (pretok == kPretokGpt2) {
         HIP_TRY(latok::launch_pretok_planes((const uint8_t*)b.in.p, b.total, b.row, b.n_str, (uint64_t*)w.bits.p, (uint64_t*)w.space.p,
                                             (int64_t*)w.tile_first.p, st));
+    } else if (pretok == kPretokSpm) {
+        HIP_TRY(latok::launch_pretok_spm_planes((const uint8_t*)b.in.p, b.total, b.row, b.n_str, (uint64_t*)w.bits.p, (uint64_t*)w.space.p,
+                                                (int64_t*)w.tile_first.p, st));
     } else if (pretok == kPretokCl100k) {
         HIP_TRY(latok::launch_pretok_cl100k_planes((const uint8_t*)b.in.p, b.total, b.row, b.n_str, (uint32_t*)w.summ.p, (uint64_t*)w.bits.p,
                                                    (uint64_t*)w.space.p, (int64_t*)w.tile_first.p, st));
@@ -2475,7 +2481,8 @@ int latok_token_hashes_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte
  *   enqueue_token_front (GPT2)     k_pretok_planes: start plane, zero SPACE plane, tile index; k_word_counts + k_scan_chained: ranks, THE total
  *   k_counts_scatter (kind 1)      per-string counts and the [start, end) records (gate: total <= capacity)
  * One wait; host pointers: the copies and a second wait.  Route 26 of latok_debug_last_route.
- * LATOK_PRETOK_CL100K: the same call with the cl100k front (two launches in place of k_pretok_planes), route 29. */
+ * LATOK_PRETOK_CL100K: the same call with the cl100k front (two launches in place of k_pretok_planes), route 29.
+ * LATOK_PRETOK_SPM: the same call with SentencePiece's segments (k_pretok_spm_planes in place of k_pretok_planes), route 32. */
 static int pretokens_planes(int pretok, const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, void* counts_out, void* spans_out,
                             int64_t spans_cap, int64_t* n_tokens_out, int flags, void* stream) {
     LATOK_ENTER();
@@ -2498,7 +2505,7 @@ static int pretokens_planes(int pretok, const uint8_t* utf8, const int64_t* byte
     if (!counts_out) return fail(LATOK_ERR_INVALID, "counts_out is NULL");
     if (c.empty) return zero_counts(dev, counts_out, (size_t)n_str * elt, c.st, true);   // only empty strings
     if (dev && (((uintptr_t)spans_out & (2 * elt - 1)) != 0 || ((uintptr_t)counts_out & (elt - 1)) != 0)) return fail(LATOK_ERR_INVALID, "misaligned output buffer");
-    if ((rc = c.stage(g, pretok == kPretokCl100k ? 29 : 26, WsShape{.spans = true}, kClearPair))) return rc;
+    if ((rc = c.stage(g, pretok == kPretokCl100k ? 29 : pretok == kPretokSpm ? 32 : 26, WsShape{.spans = true}, kClearPair))) return rc;
     void* d_counts = counts_out;
     void* d_spans = spans_out;
     int64_t cap = spans_out ? spans_cap : 0;
@@ -2520,8 +2527,8 @@ static int pretokens_planes(int pretok, const uint8_t* utf8, const int64_t* byte
 int latok_pretokens_utf8_bytes_batch(const uint8_t* utf8, const int64_t* byte_off, int64_t n_str, int64_t total_bytes, int pretok, int64_t* counts_out,
                                      int64_t* spans_out, int64_t spans_cap, int64_t* n_tokens_out, int flags, void* stream) {
     // what needs no device is refused first
-    if (pretok != LATOK_PRETOK_LATOK && pretok != LATOK_PRETOK_GPT2 && pretok != LATOK_PRETOK_CL100K)
-        return fail(LATOK_ERR_INVALID, "unknown pretok %d (LATOK_PRETOK_LATOK, LATOK_PRETOK_GPT2 or LATOK_PRETOK_CL100K)", pretok);
+    if (pretok != LATOK_PRETOK_LATOK && pretok != LATOK_PRETOK_GPT2 && pretok != LATOK_PRETOK_CL100K && pretok != LATOK_PRETOK_SPM)
+        return fail(LATOK_ERR_INVALID, "unknown pretok %d (LATOK_PRETOK_LATOK, LATOK_PRETOK_GPT2, LATOK_PRETOK_CL100K or LATOK_PRETOK_SPM)", pretok);
     if (flags & ~(LATOK_OUT_INT32 | LATOK_DEVICE_PTRS)) return fail(LATOK_ERR_INVALID, "unknown flag");
     if (pretok == LATOK_PRETOK_LATOK)
         return latok_token_spans_utf8_bytes_batch(utf8, byte_off, n_str, total_bytes, counts_out, spans_out, spans_cap, n_tokens_out, flags, stream);
@@ -3354,19 +3361,47 @@ struct Bpe {                       // latok_bpe: immutable once created
     uint32_t seed = 0;
     DevTable table;
     DevMem rank_id;
+    // an object of latok_bpe_create_spm (pretok == kPretokSpm): SentencePiece BPE (spbpe.h)
+    int add_dummy_prefix = 0, fuse_unk = 0;
+    bool byte_fallback = false;
+    DevMem byte_ids;               // [256] int32 when byte_fallback
 };
+// the body of latok_bpe_create_pretok and latok_bpe_create_spm, behind their own refusals
+static int bpe_create_object(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, int max_bytes, int lead_space,
+                             int pretok, const int32_t* byte_ids, int add_dummy_prefix, int fuse_unk, uint32_t seed, latok_bpe** bpe_out);
 int latok_bpe_create_pretok(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, int max_bytes, int lead_space,
                             int pretok, uint32_t seed, latok_bpe** bpe_out) {
-    LATOK_ENTER();
     // what needs no device is refused first
     if (!bpe_out) return fail(LATOK_ERR_INVALID, "bpe_out is NULL");
     *bpe_out = nullptr;
     if (max_bytes < 1 || max_bytes > kBpeMaxBytes) return fail(LATOK_ERR_INVALID, "max_bytes must be in 1 .. %d", kBpeMaxBytes);
     if (lead_space != 0 && lead_space != 1) return fail(LATOK_ERR_INVALID, "lead_space must be 0 or 1");
+    if (pretok == kPretokSpm)
+        return fail(LATOK_ERR_INVALID, "LATOK_PRETOK_SPM takes latok_bpe_create_spm: byte merges over SentencePiece's segments mean nothing");
     if (pretok != kPretokLatok && pretok != kPretokGpt2 && pretok != kPretokCl100k)
         return fail(LATOK_ERR_INVALID, "unknown pretok %d (LATOK_PRETOK_LATOK, LATOK_PRETOK_GPT2 or LATOK_PRETOK_CL100K)", pretok);
     if (pretok != kPretokLatok && lead_space)
         return fail(LATOK_ERR_INVALID, "lead_space must be 0 with %s: the space is already in the pre-token", pretok == kPretokGpt2 ? "LATOK_PRETOK_GPT2" : "LATOK_PRETOK_CL100K");
+    return bpe_create_object(words, word_off, n_words, word_ids, max_bytes, lead_space, pretok, nullptr, 0, 0, seed, bpe_out);
+}
+int latok_bpe_create_spm(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, const int32_t* byte_ids,
+                         int add_dummy_prefix, int fuse_unk, int max_bytes, uint32_t seed, latok_bpe** bpe_out) {
+    // what needs no device is refused first
+    if (!bpe_out) return fail(LATOK_ERR_INVALID, "bpe_out is NULL");
+    *bpe_out = nullptr;
+    if (max_bytes < 1 || max_bytes > kBpeMaxBytes) return fail(LATOK_ERR_INVALID, "max_bytes must be in 1 .. %d", kBpeMaxBytes);
+    if (add_dummy_prefix != 0 && add_dummy_prefix != 1) return fail(LATOK_ERR_INVALID, "add_dummy_prefix must be 0 or 1");
+    if (fuse_unk != 0 && fuse_unk != 1) return fail(LATOK_ERR_INVALID, "fuse_unk must be 0 or 1");
+    const int rc = check_word_list(words, word_off, n_words);
+    if (rc) return rc;
+    const int64_t bad = sp_first_bad_word(words, word_off, n_words);
+    if (bad >= 0)
+        return fail(LATOK_ERR_INVALID, "word %lld holds E2 96 81 behind another character: segments would not be independent", (long long)bad);
+    return bpe_create_object(words, word_off, n_words, word_ids, max_bytes, 0, kPretokSpm, byte_ids, add_dummy_prefix, fuse_unk, seed, bpe_out);
+}
+static int bpe_create_object(const uint8_t* words, const int64_t* word_off, int64_t n_words, const int32_t* word_ids, int max_bytes, int lead_space,
+                             int pretok, const int32_t* byte_ids, int add_dummy_prefix, int fuse_unk, uint32_t seed, latok_bpe** bpe_out) {
+    LATOK_ENTER();
     int rc = check_word_list(words, word_off, n_words);
     if (rc || (rc = need_init(g))) return rc;
     BpeTables t;
@@ -3384,11 +3419,20 @@ int latok_bpe_create_pretok(const uint8_t* words, const int64_t* word_off, int64
     v->lead_space = lead_space;
     v->pretok = pretok;
     v->seed = seed;
+    v->add_dummy_prefix = add_dummy_prefix;
+    v->fuse_unk = fuse_unk;
+    v->byte_fallback = byte_ids != nullptr;
     if ((rc = v->table.upload(t.table, g.stream)) == LATOK_OK) {
         const size_t bytes = t.rank_id.size() * 4;
         hipError_t e = v->rank_id.alloc(bytes);
         if (e != hipSuccess) rc = fail(LATOK_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
         else if ((e = hipMemcpyAsync(v->rank_id.p, t.rank_id.data(), bytes, hipMemcpyHostToDevice, g.stream)) != hipSuccess)
+            rc = fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
+    }
+    if (!rc && byte_ids) {   // (pageable host memory: the copy has read it when the call returns)
+        hipError_t e = v->byte_ids.alloc(256 * 4);
+        if (e != hipSuccess) rc = fail(LATOK_ERR_NOMEM, "hipMalloc(%zu) failed: %s", (size_t)1024, hipGetErrorString(e));
+        else if ((e = hipMemcpyAsync(v->byte_ids.p, byte_ids, 256 * 4, hipMemcpyHostToDevice, g.stream)) != hipSuccess)
             rc = fail(LATOK_ERR_HIP, "uploading the vocabulary failed: %s", hipGetErrorString(e));
     }
     const hipError_t e = hipStreamSynchronize(g.stream);   // (the host tables die with this call, and every context may use the object at once)
@@ -3411,6 +3455,16 @@ int latok_bpe_pretokenizer(const latok_bpe* bpe, int* pretok) {
     if (!v) return fail(LATOK_ERR_INVALID, "bpe is NULL");
     if (!pretok) return fail(LATOK_ERR_INVALID, "pretok is NULL");
     *pretok = v->pretok;
+    return LATOK_OK;
+}
+
+int latok_bpe_spm_info(const latok_bpe* bpe, int* byte_fallback, int* add_dummy_prefix, int* fuse_unk) {
+    const Bpe* v = reinterpret_cast<const Bpe*>(bpe);
+    if (!v) return fail(LATOK_ERR_INVALID, "bpe is NULL");
+    if (v->pretok != kPretokSpm) return fail(LATOK_ERR_INVALID, "bpe is not an object of latok_bpe_create_spm");
+    if (byte_fallback) *byte_fallback = v->byte_fallback ? 1 : 0;
+    if (add_dummy_prefix) *add_dummy_prefix = v->add_dummy_prefix;
+    if (fuse_unk) *fuse_unk = v->fuse_unk;
     return LATOK_OK;
 }
 
@@ -3543,6 +3597,7 @@ struct PieceCut {
     void route_by_front() {
         if (pretok() == kPretokGpt2) { route_ids = 24; route_padded = 25; }
         if (pretok() == kPretokCl100k) { route_ids = 27; route_padded = 28; }
+        if (pretok() == kPretokSpm) { route_ids = 30; route_padded = 31; }
     }
 };
 
@@ -3592,6 +3647,8 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
         if ((rc = enqueue_token_rows(w, a.b, t, n_tok, d_cnt, d_start, d_err, st, &text))) return rc;
         latok::WordPieceTables wt;
         latok::BpeTable bt;
+        latok::SpBpeTable spt;
+        const bool spm = a.cut.pretok() == kPretokSpm;
         uint64_t* d_mask = (uint64_t*)w.bpemask.p;
         latok::UniTable ut;
         uint64_t* d_marks = (uint64_t*)w.unimarks.p;
@@ -3602,7 +3659,15 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
             bt.max_len = b->max_len;
             bt.max_bytes = b->max_bytes;
             bt.lead_space = b->lead_space;
-            HIP_TRY(latok::launch_bpe_count(text, bt, d_pcnt, d_mask, st));
+            if (spm) {
+                spt.bt = bt;
+                spt.byte_ids = b->byte_fallback ? b->byte_ids.as<const int32_t>() : nullptr;
+                spt.add_dummy_prefix = b->add_dummy_prefix;
+                spt.fuse_unk = b->fuse_unk;
+                HIP_TRY(latok::launch_spbpe_count(text, spt, d_pcnt, d_mask, st));
+            } else {
+                HIP_TRY(latok::launch_bpe_count(text, bt, d_pcnt, d_mask, st));
+            }
         } else if (const Unigram* u = a.cut.uni) {
             ut.plain = u->plain.view(u->seed);
             ut.marked = u->marked.view(u->seed);
@@ -3639,7 +3704,8 @@ static int enqueue_wordpiece(Ctx& g, Workspace& w, WordPieceCall& a) {
             ids = (int32_t*)w.wpids.p;
             d_ids = ids;
         }
-        if (ids && a.cut.bpe) HIP_TRY(latok::launch_bpe_emit(a.o32, text, bt, a.unk, d_prank, d_mask, d_total + 5, cap, ids, a.spans, st));
+        if (ids && spm) HIP_TRY(latok::launch_spbpe_emit(a.o32, text, spt, a.unk, d_prank, d_mask, d_total + 5, cap, ids, a.spans, st));
+        else if (ids && a.cut.bpe) HIP_TRY(latok::launch_bpe_emit(a.o32, text, bt, a.unk, d_prank, d_mask, d_total + 5, cap, ids, a.spans, st));
         else if (ids && a.cut.uni) HIP_TRY(latok::launch_uni_emit(a.o32, text, ut, a.unk, d_prank, d_marks, d_total + 5, cap, ids, a.spans, st));
         else if (ids) HIP_TRY(latok::launch_wp_emit(a.o32, text, wt, a.unk, d_prank, d_total + 5, cap, ids, a.spans, st));
         if (a.indptr) HIP_TRY(latok::launch_wp_rows(a.o32, d_start, d_prank, n_str, n_tok, a.indptr, st));
@@ -3687,7 +3753,9 @@ static int piece_ids_call(const uint8_t* utf8, const int64_t* byte_off, int64_t 
     a.spans = ids_out ? spans_out : nullptr;
     // (a piece has at least one byte -- but for the marker-alone piece of a Unigram token, one per token at most: a larger capacity
     // gates nothing, and the staging is sized by it; 2^31 pieces or more are refused)
-    a.cap = ids_out ? std::min({cap, cut.uni ? 2 * c.total : c.total, (int64_t)0x7FFFFFFF}) : 0;
+    // (SentencePiece BPE: byte fallback of a marker gives three pieces for one space and three for the dummy)
+    const int64_t most = cut.pretok() == kPretokSpm ? 3 * (c.total + n_str) : cut.uni ? 2 * c.total : c.total;
+    a.cap = ids_out ? std::min({cap, most, (int64_t)0x7FFFFFFF}) : 0;
     a.o32 = c.o32;
     if (!dev) {
         if ((rc = g.h_aux.ensure((size_t)a.cap * 4 + 16)) || (rc = g.h_out.ensure((size_t)a.cap * 2 * elt + 16)) || (rc = g.counts.ensure((size_t)(n_str + 1) * 8)))
@@ -4803,6 +4871,17 @@ extern "C" int latok_debug_bpe_limits(int64_t* out, int n) {
     return k;
 }
 
+/* test hook (not part of the ABI; needs no device): the constants of the SentencePiece BPE calls: out[0] = kBpeBlock (segments per
+ * workgroup of k_spbpe_count / k_spbpe_emit), out[1] = kSpLaneBytes (the longest virtual text of the lane form), out[2] = kBpeMaxBytes
+ * (the ceiling of max_bytes).  Returns the number of values written. */
+extern "C" int latok_debug_spbpe_limits(int64_t* out, int n) {
+    const int64_t v[3] = {latok::kBpeBlock, kSpLaneBytes, kBpeMaxBytes};
+    if (!out || n < 0) return fail(LATOK_ERR_INVALID, "NULL output");
+    const int k = n < 3 ? n : 3;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
 /* test hook (not part of the ABI; needs no device): the constants of the GPT-2 pre-tokenizer's front (k_pretok_planes): out[0] = bytes per
  * word (one lane), out[1] = bytes per tile (one wave), out[2] = threads per workgroup, out[3] = kPtHalo (the bytes a word's window holds
  * on either side of the word).  Returns the number of values written. */
@@ -4995,7 +5074,8 @@ extern "C" int latok_debug_last_plan(int64_t* out, int n) {
  * 22 / 23: Unigram ids of UTF-8 in byte space, CSR form / padded form (likewise);
  * 24 / 25: byte-level BPE ids behind GPT-2's pre-tokenizer (an object of latok_bpe_create_pretok), CSR form / padded form (likewise);
  * 26: pre-token spans of GPT-2's pre-tokenizer (latok_pretokens_utf8_bytes_batch; LATOK_PRETOK_LATOK reports the span call's routes);
- * 27 / 28: byte-level BPE ids behind the cl100k pre-tokenizer, CSR form / padded form; 29: pre-token spans of the cl100k pre-tokenizer */
+ * 27 / 28: byte-level BPE ids behind the cl100k pre-tokenizer, CSR form / padded form; 29: pre-token spans of the cl100k pre-tokenizer;
+ * 30 / 31: SentencePiece BPE ids (an object of latok_bpe_create_spm), CSR form / padded form; 32: the segments of LATOK_PRETOK_SPM */
 extern "C" int latok_debug_last_route(void) {
     LATOK_ENTER();
     return g.last_route;

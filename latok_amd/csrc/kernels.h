@@ -432,6 +432,22 @@ hipError_t launch_pretok_planes(const uint8_t* u8, int64_t total, const int64_t*
 constexpr int kPretokWalk = 64;   // tile records per walk step: one per lane
 hipError_t launch_pretok_cl100k_planes(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, uint32_t* tile_rec, uint64_t* bits,
                                        uint64_t* space, int64_t* tile_first, hipStream_t st);
+// SentencePiece's segments as a token front (pretok_kernels.hip, spbpe.h): launch_pretok_planes' contract with another rule -- a bit at every
+// byte where a segment starts.  No table is read.
+hipError_t launch_pretok_spm_planes(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, uint64_t* bits, uint64_t* space,
+                                    int64_t* tile_first, hipStream_t st);
+// SentencePiece BPE ids (spbpe_kernels.hip, spbpe.h): launch_bpe_count / launch_bpe_emit's contract for an object of latok_bpe_create_spm.  The
+// tokens are the segments of the front above; the lookups read every segment's virtual text; a segment may have more pieces than bytes
+// (byte fallback of a marker: three pieces for one space, three for the dummy), at most 3 * (bytes + strings) in a batch.
+struct SpBpeTable {
+    BpeTable bt;                         // (lead_space is not read)
+    const int32_t* byte_ids = nullptr;   // [256], or NULL: no byte fallback
+    int add_dummy_prefix = 0;
+    int fuse_unk = 0;
+};
+hipError_t launch_spbpe_count(const TokenText& t, const SpBpeTable& sp, int64_t* cnt, uint64_t* masks, hipStream_t st);
+hipError_t launch_spbpe_emit(bool out32, const TokenText& t, const SpBpeTable& sp, int32_t unk_id, const int64_t* rank, const uint64_t* masks,
+                             const int64_t* n_pieces_dev, int64_t cap, int32_t* ids, void* spans, hipStream_t st);
 // Unigram (Viterbi) ids (unigram_kernels.hip, unigram.h).  launch_uni_count leaves the pieces of every token in cnt[0 .. n_tok) and 0
 // in cnt[n_tok], and three words per token of at most 64 bytes in marks[] (three arrays of n_tok words: the piece starts, which of them
 // are unknown, whether the marker's piece is); the caller scans the n_tok + 1 entries into rank[]; launch_uni_emit stores ids (through

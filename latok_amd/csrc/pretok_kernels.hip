@@ -20,6 +20,7 @@
 #include "bitscan.h"
 #include "kernels.h"
 #include "pretok.h"
+#include "spbpe.h"
 #include "wave_ops.h"
 
 namespace latok {
@@ -224,6 +225,47 @@ __global__ __launch_bounds__(kPretokWaves * 64) void k_pretok_cl100k_planes(cons
     const uint32_t left = pt_rec_then(in, pt_rec_left(K, lt)), right = pt_rec_then(pt_rec_right(K, gt), in);
     bits[w] = pt_cl100k_finish(c, pt_carry_of((left & 0x7Fu) | (right & 0x180u))) & valid_mask(w, total);
     space[w] = 0ull;
+}
+
+// ---- SentencePiece's segments (spbpe.h; LATOK_PRETOK_SPM) ------------------------------------------------------------------------------
+// The rule has no carry (a start bit depends on 3 bytes behind it and 3 ahead), so this is k_pretok_planes' geometry once more: one
+// launch, one wave per tile, the image and the string-start map of pretok_stage, every lane its word alone.  No table is read.
+__global__ __launch_bounds__(kPretokWaves * 64) void k_pretok_spm_planes(const uint8_t* __restrict__ u8, int64_t total, const int64_t* __restrict__ row_off,
+                                                                         int64_t n_str, uint64_t* __restrict__ bits, uint64_t* __restrict__ space,
+                                                                         int64_t* __restrict__ tile_first) {
+    __shared__ __attribute__((aligned(16))) uint8_t image_s[kPretokWaves][kPretokRows * kPretokRow];
+    __shared__ unsigned long long map_s[kPretokWaves][kPretokMapWords];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t t = (int64_t)blockIdx.x * kPretokWaves + wave;
+    const int64_t t0 = t * kTile;
+    if (t0 >= total) return;                                    // whole wave (no workgroup barrier below)
+    const uint8_t* image = image_s[wave];
+    const unsigned long long* map = map_s[wave];
+    const int64_t first = pretok_stage(u8, total, row_off, n_str, t0, lane, image_s[wave], map_s[wave]);
+    if (lane == 0) tile_first[t] = first;
+    const int64_t w = t * 64 + lane;
+    if (w * 64 >= total) return;
+    PretokWindow win;
+    win.lds = image;
+    win.o0 = 64 + 64 * lane - kPtHalo;
+#pragma unroll
+    for (int j = 0; j < kPtWindow / 16; ++j) {
+        const uint4 v = *reinterpret_cast<const uint4*>(image + pretok_lds_at(win.o0 + 16 * j));
+        win.q[2 * j] = (uint64_t)v.x | ((uint64_t)v.y << 32);
+        win.q[2 * j + 1] = (uint64_t)v.z | ((uint64_t)v.w << 32);
+    }
+    const pt_u128 B = (pt_u128)(map[lane] >> (64 - kPtHalo)) | ((pt_u128)map[lane + 1] << kPtHalo) | ((pt_u128)map[lane + 2] << (64 + kPtHalo));
+    bits[w] = sp_word_starts(win, B) & valid_mask(w, total);
+    space[w] = 0ull;
+}
+
+hipError_t launch_pretok_spm_planes(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, uint64_t* bits, uint64_t* space,
+                                    int64_t* tile_first, hipStream_t st) {
+    if (total <= 0 || n_str <= 0) return hipSuccess;
+    const int64_t n_tiles = (total + kTile - 1) / kTile;
+    hipLaunchKernelGGL(k_pretok_spm_planes, dim3((unsigned)((n_tiles + kPretokWaves - 1) / kPretokWaves)), dim3(kPretokWaves * 64), 0, st, u8, total,
+                       row_off, n_str, bits, space, tile_first);
+    return hipGetLastError();
 }
 
 hipError_t launch_pretok_cl100k_planes(const uint8_t* u8, int64_t total, const int64_t* row_off, int64_t n_str, uint32_t* tile_rec, uint64_t* bits,

@@ -83,6 +83,15 @@
   py_bpe_gpt2    end to end in Python on host blobs (the first min(--py-strings, 50000) strings): batch.bpe_ids_utf8_batch(blobs, bpe) of a
                   pretokenizer="gpt2" object against the `regex` package with GPT-2's pattern + the merge loop over a dict on the host;
                   equal rows asserted first; skipped with a note where `regex` is not importable
+  bytes_pretok_spm    latok_pretokens_utf8_bytes_batch with LATOK_PRETOK_SPM and LATOK_OUT_INT32: the span records of SentencePiece's segments
+                  (one launch for the planes, like GPT-2's front); yardstick: bytes_pretok_gpt2 of the same process run
+  bytes_spbpe32 / bytes_spbpe_padded   latok_bpe_ids_utf8_bytes_batch / latok_bpe_padded_utf8_bytes_batch on a SentencePiece BPE object
+                  (latok_bpe_create_spm, byte fallback, dummy prefix): the words are bytes_bpe32's trainer on the same tokens with U+2581 in
+                  front of every second one, kept where they are well-formed UTF-8; yardstick: bytes_bpe_gpt2 of the same process run
+  py_spbpe       end to end in Python on host blobs (the first min(--py-strings, 50000) strings): batch.bpe_ids_utf8_batch(blobs, bpe) of
+                  such an object against a host loop (replace, split into segments, a memoised merge walk over characters, byte fallback),
+                  equal rows asserted first; beside it, where the package is importable and not as a pass condition, sentencepiece's own
+                  encode of a model made of the same words
   bytes_pretok_cl100k / bytes_bpe_cl100k / py_bpe_cl100k   the same three with LATOK_PRETOK_CL100K / pretokenizer="cl100k" (the cl100k /
                   Llama 3 pattern: two launches for the planes); yardsticks: bytes_pretok_gpt2 and bytes_bpe_gpt2 of the same process run
   bytes_uni32 / bytes_uni_padded   latok_unigram_ids_utf8_bytes_batch (int32 indptr and spans, capacity = the piece total of a size query) /
@@ -455,7 +464,8 @@ def main():
                                           "bytes_ids_only", "bytes_ids_only_flow", "bytes_terms32", "bytes_terms_hashed", "bytes_ngrams32", "bytes_ngrams_hashed", "py_terms",
                                           "bytes_chargrams32", "bytes_chargrams_hashed", "bytes_tfidf32", "bytes_tfidf_hashed", "bytes_df_update", "csr_tfidf", "csr_df", "py_tfidf",
                                           "bytes_count_cold", "bytes_count_warm", "py_count", "py_ids", "py_join", "bytes_wp32", "bytes_wp_padded", "py_wp",
-                                          "bytes_bpe32", "bytes_bpe_padded", "py_bpe", "bytes_pretok_gpt2", "bytes_bpe_gpt2", "py_bpe_gpt2", "bytes_pretok_cl100k", "bytes_bpe_cl100k", "py_bpe_cl100k", "bytes_uni32", "bytes_uni_padded", "py_uni", "ids_detok_bpe", "ids_detok_wp", "py_detok",
+                                          "bytes_bpe32", "bytes_bpe_padded", "py_bpe", "bytes_pretok_gpt2", "bytes_bpe_gpt2", "py_bpe_gpt2", "bytes_pretok_cl100k", "bytes_bpe_cl100k", "py_bpe_cl100k",
+                                          "bytes_pretok_spm", "bytes_spbpe32", "bytes_spbpe_padded", "py_spbpe", "bytes_uni32", "bytes_uni_padded", "py_uni", "ids_detok_bpe", "ids_detok_wp", "py_detok",
                                           "bytes_fold", "bytes_fold_wp", "py_fold")]
     if join_leg:
         jb = [lib.latok_dev_alloc(sz) for sz in (2 * n8 + 64, (n + 1) * 8, 2 * n8 + 64, (n + 1) * 8, cap * 8, n * 4, cap * 8, n * 4, 64, cap * 4, cap * 4)]
@@ -724,7 +734,45 @@ def main():
         # GPT-2's pre-tokenizer: the span call, and the BPE call on an object of bytes_bpe32's words that brings it as its front
         pretok_gpt2_blocking = lambda: lib.latok_pretokens_utf8_bytes_batch(d_u8, d_boff, n, n8, _lib.PRETOK_GPT2, s_counts, s_items, cap, C.byref(nout), D32, None)  # noqa: E731
         pretok_cl100k_blocking = lambda: lib.latok_pretokens_utf8_bytes_batch(d_u8, d_boff, n, n8, _lib.PRETOK_CL100K, s_counts, s_items, cap, C.byref(nout), D32, None)  # noqa: E731
-        gpt2_box, cl100k_box = [], []
+        pretok_spm_blocking = lambda: lib.latok_pretokens_utf8_bytes_batch(d_u8, d_boff, n, n8, _lib.PRETOK_SPM, s_counts, s_items, cap, C.byref(nout), D32, None)  # noqa: E731
+        gpt2_box, cl100k_box, spm_box = [], [], []
+        SPM_MARK = "\u2581".encode()
+
+        def spm_words(toks):
+            """the words of the spbpe paths: bpe_train on the tokens with the marker in front of every second one, the well-formed ones"""
+            def ok(w):
+                try:
+                    w.decode("utf-8")
+                    return True
+                except UnicodeDecodeError:
+                    return False
+            return [w for w in bpe_train([SPM_MARK + t for t in toks[::2]] + toks[1::2], args.bpe_merges) if ok(w)]
+
+        def corpus_spbpe():
+            if not spm_box:
+                from latok_amd import batch
+                words = spm_words(bpe_sample_tokens(False)[2])
+                b = batch.BPE.sentencepiece(words, byte_ids=[len(words) + x for x in range(256)], seed=SEED)
+                bufs = [lib.latok_dev_alloc(sz) for sz in ((n + 1) * 4 + 64, n * WP_LEN * 4 + 64, n * 4 + 64)]
+                need, n_seg = C.c_int64(0), C.c_int64(0)
+                rc = lib.latok_bpe_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, bufs[0], None, None, 0, C.byref(need), C.byref(n_seg), D32, None)
+                if rc != _lib.OK and need.value <= 0:
+                    _lib.check(rc)
+                pieces = [lib.latok_dev_alloc(need.value * 4 + 64), lib.latok_dev_alloc(need.value * 8 + 64)]
+                if not (all(bufs) and all(pieces)):
+                    raise RuntimeError(_lib.last_error())
+                print(json.dumps(dict(b.info(), **b.spm_info(), spbpe_words=len(words), workload=args.workload, segments=n_seg.value, pieces=need.value,
+                                      pieces_per_segment=need.value / max(n_seg.value, 1))), flush=True)
+                spm_box.extend([b] + bufs + pieces + [need.value])
+            return spm_box
+
+        def spbpe_blocking():
+            b, g_indptr, _, _, g_ids, g_spans, need = corpus_spbpe()
+            return lib.latok_bpe_ids_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, g_indptr, g_ids, g_spans, need, C.byref(nout), None, D32, None)
+
+        def spbpe_padded_blocking():
+            b, _, g_block, g_len = corpus_spbpe()[:4]
+            return lib.latok_bpe_padded_utf8_bytes_batch(d_u8, d_boff, n, n8, b.handle, -1, WP_LEN, 1, 1, 2, 0, g_block, g_len, C.byref(nout), D, None)
 
         def corpus_bpe_gpt2(gpt2_box=gpt2_box, pretokenizer="gpt2"):
             if not gpt2_box:
@@ -1070,6 +1118,90 @@ def main():
             elif name == "bytes_bpe_cl100k":   # (items = pieces)
                 run(name, bpe_cl100k_blocking, lambda: 2 * n8 + csr + 4 * n + 12 * nout.value,
                     note_b + "; the front is the cl100k pre-tokenizer: two launches for the planes, white-space pre-tokens are merged too")
+            elif name == "bytes_pretok_spm":   # (items = segments, white space included)
+                run(name, pretok_spm_blocking, lambda: n8 + csr + 4 * n + 8 * nout.value,
+                    "UTF-8 bytes + 8 B/string read once by one launch; 2 x 1 bit/byte planes written; 4 B/string + 8 B/segment written "
+                    "(byte ranges, LATOK_OUT_INT32); no class table is read")
+            elif name == "bytes_spbpe32":   # (items = pieces)
+                run(name, spbpe_blocking, lambda: n8 + csr + 4 * n + 12 * nout.value,
+                    note_b + "; the front is SentencePiece's segments: one launch for the planes; the lookups read a virtual text composed on the fly")
+            elif name == "bytes_spbpe_padded":   # (items = the untruncated piece total; the block is [n, WP_LEN] with BOS / EOS)
+                run(name, spbpe_padded_blocking, lambda: n8 + csr + 4 * n + 4 * n * WP_LEN,
+                    note_b.replace("4 B/string indptr + 4 B/piece ids + 8 B/piece spans", "4 B/string lengths + 4 B/cell of the [n, %d] block" % WP_LEN))
+            elif name == "py_spbpe":   # host blobs in, the CSR arrays out, both routes in this process
+                import re
+                from latok_amd import batch
+                blobs, blob, toks = bpe_sample_tokens(False)
+                blobs = blobs[:50000]
+                blob = b"".join(blobs)
+                words = spm_words(toks)
+                d = {}
+                for i, w in enumerate(words):
+                    d.setdefault(w.decode(), i)
+                n_w, mark, memo = len(words), "\u2581", {}
+                seg_pat = re.compile(mark + "*[^" + mark + "]*")
+
+                def cut_spm(seg):
+                    got = memo.get(seg)
+                    if got is None:
+                        parts = list(seg)
+                        while True:
+                            best = None
+                            for i in range(len(parts) - 1):
+                                r = d.get(parts[i] + parts[i + 1])
+                                if r is not None and (best is None or r < best[0]):
+                                    best = (r, i)
+                            if best is None:
+                                break
+                            parts[best[1]:best[1] + 2] = [parts[best[1]] + parts[best[1] + 1]]
+                        got = []
+                        for p_ in parts:
+                            r = d.get(p_)
+                            got.extend([r] if r is not None else [n_w + x for x in p_.encode("utf-8", "surrogatepass")])
+                        memo[seg] = got
+                    return got
+
+                def on_host_spm():
+                    memo.clear()   # (the memo is part of the loop: one merge walk per distinct segment of the call)
+                    indptr, ids = [0], []
+                    for b_ in blobs:
+                        if b_:
+                            text = mark + b_.decode("utf-8", "surrogatepass").replace(" ", mark)   # (the dummy joins the first lead run)
+                            for seg in seg_pat.findall(text):
+                                if seg:
+                                    ids.extend(cut_spm(seg))
+                        indptr.append(len(ids))
+                    return np.array(indptr, np.int64), np.array(ids, np.int32)
+
+                with batch.BPE.sentencepiece(words, byte_ids=[n_w + x for x in range(256)], seed=SEED) as b:
+                    routes = [("py_spbpe_ids_utf8_batch", lambda: batch.bpe_ids_utf8_batch(blobs, b)[:2]), ("py_replace_split_then_bpe_loop", on_host_spm)]
+                    assert all(np.array_equal(x, y) for x, y in zip(routes[0][1](), routes[1][1]()))
+                    try:   # beside the two, not a pass condition: the package's own encode of a model made of the same words
+                        import sentencepiece as spm
+                        from sentencepiece import sentencepiece_model_pb2 as pb2
+                        mp = pb2.ModelProto()
+                        mp.trainer_spec.model_type, mp.trainer_spec.byte_fallback, mp.trainer_spec.vocab_size = 2, True, 3 + 256 + n_w
+                        mp.normalizer_spec.name, mp.normalizer_spec.add_dummy_prefix, mp.normalizer_spec.remove_extra_whitespaces = "identity", True, False
+                        for piece, kind in (("<unk>", 2), ("<s>", 3), ("</s>", 3)):
+                            mp.pieces.add(piece=piece, score=0.0, type=kind)
+                        for x in range(256):
+                            mp.pieces.add(piece="<0x%02X>" % x, score=0.0, type=6)
+                        for i, w in enumerate(words):
+                            mp.pieces.add(piece=w.decode(), score=-float(i), type=1)
+                        sp = spm.SentencePieceProcessor(model_proto=mp.SerializeToString())
+                        texts = [b_.decode("utf-8", "replace") for b_ in blobs]
+                        routes.append(("py_sentencepiece_encode", lambda: (np.zeros(1, np.int64), np.fromiter((i for row in sp.encode(texts) for i in row), np.int32))))
+                    except Exception as exc:   # noqa: BLE001
+                        print(json.dumps({"path": "py_sentencepiece_encode", "workload": args.workload, "note": "skipped: %s" % str(exc)[:200]}), flush=True)
+                    for r in range(args.repeat):
+                        for rname, fn in routes:
+                            t = time.perf_counter()
+                            got = fn()
+                            dt = time.perf_counter() - t
+                            print(json.dumps({"path": rname, "workload": args.workload, "strings": len(blobs), "utf8_bytes": len(blob),
+                                              "words": len(words), "pieces": int(got[1].size), "ms_per_call": dt * 1e3, "utf8_GBps": len(blob) / dt / 1e9,
+                                              "note": "end to end in Python: list[bytes] in, (indptr, ids) out, pack and host work included",
+                                              "repeat": r}), flush=True)
             elif name in ("py_bpe_gpt2", "py_bpe_cl100k"):   # host blobs in, the CSR arrays out, both routes in this process
                 pretokenizer = name[len("py_bpe_"):]
                 from latok_amd import batch
